@@ -14,10 +14,16 @@ the MSM of step i + 1; all K folds complete inside the timed region) and folded 
 
 Prints ONE JSON line on rank 0.  `value` = bucket-accumulation G1 adds per second over the
 whole job = N * n * W / t (W = ceil(255 / c) signed windows at the engine's window width c;
-SURVEY.md 8(d)); pairs/s, the other sizes and the NTT figures ride along as extra keys.
-`roofline` prices the dominant kernel (msm_accum_kernel) at its algorithmic 96 B per pair
-against 8 TB/s, timed with HIP events on the stream it is launched on; `cpu_baseline` is the
-oracle's restatement of the reference's rayon path timed on this box's host cores.
+SURVEY.md 8(d)); `ms_per_step` = t / steps.  `roofline` prices the dominant kernel
+(msm_accum_kernel) at its algorithmic 96 B per pair against 8 TB/s, timed with HIP events on the
+stream it is launched on during the timed steps.
+A plain run does nothing else: it sets up, warms up, times the steps and prints the line.
+`--full` adds every other measurement as extra keys: the per-stage times, the other form, the
+batched commits, the NTT figures, the other sizes, the evaluate_h / g_to_lagrange legs, the
+counter passes behind `roofline.traffic` / `valu_roofline.issue_slots`, `cpu_baseline` (the
+oracle's restatement of the reference's rayon path timed on the host's cores) and, for
+N > 1, the strong-scaling and single-process legs.
+`--dump-outputs DIR` writes the last timed step's result to DIR (see its help).
 """
 import argparse
 import ctypes
@@ -289,6 +295,11 @@ def main():
     ap.add_argument("--only-step", action="store_true", help="nothing but the timed step (counter passes: one kernel mix per run)")
     ap.add_argument("--only-ntt", action="store_true", help="nothing but the NTT leg (counter passes)")
     ap.add_argument("--inlib", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true", help="after the headline, every other measurement (per-stage times, other form, batched "
+                    "commits, NTT, other sizes, evaluate_h / g_to_lagrange, counter passes, CPU baseline, N > 1 legs); the --no-* "
+                    "options and --batch / --config4-log-n trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's MSM result to DIR/msm_result_affine.npy: the affine point "
+                    "(x, y as h2hip_g1_to_affine gives them), each coordinate as its 8 little-endian 32-bit words, float64 (exact), shape (2, 8)")
     args = ap.parse_args()
 
     if args.only_step or args.only_ntt:
@@ -296,6 +307,11 @@ def main():
         args.batch = 0
         args.config4_log_n = 0
         args.no_ntt = args.only_step
+        args.full = True  # the counter passes' children keep the per-stage run (--only-step) and the NTT leg (--only-ntt)
+    elif not args.full:
+        args.no_cpu_baseline = args.no_ntt = args.no_sizes = args.no_next_rows = args.no_inlib = args.no_measure_traffic = True
+        args.batch = 0
+        args.config4_log_n = 0
     if args.inlib:
         return inlib_child(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -400,24 +416,28 @@ def main():
     h2.profile_enable(False)
     accum_tot, accum_cnt = h2.profile_get("msm_accum")
     accum_ms_live = accum_tot / accum_cnt if accum_cnt else None
-    # per-stage times: the same step, untimed, with every stage bracketed by events
-    h2.profile_enable(True)
-    h2.profile_reset()
-    for _ in range(min(args.steps, 10)):
-        step()
-    if world > 1:
-        drain()
-    sync_all()
-    h2.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        xy = h2.g1_to_affine(result).view(np.uint32).reshape(2, 8).astype(np.float64)
+        np.save(os.path.join(args.dump_outputs, "msm_result_affine.npy"), xy)
+    stages = None
+    if args.full:  # per-stage times: the same step, untimed, with every stage bracketed by events
+        h2.profile_enable(True)
+        h2.profile_reset()
+        for _ in range(min(args.steps, 10)):
+            step()
+        if world > 1:
+            drain()
+        sync_all()
+        h2.profile_enable(False)
+        stages = {}
+        for st in STAGES:
+            ms, cnt = h2.profile_get(st)
+            stages[st] = ms / cnt if cnt else None
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-
-    stages = {}
-    for st in STAGES:
-        ms, cnt = h2.profile_get(st)
-        stages[st] = ms / cnt if cnt else None
 
     # ---- N > 1: BASELINE.json configs[3] -- ONE MSM of 2^24 pairs in total, sharded over the N GPUs (strong scaling: 2^24 / N pairs per
     # rank, fixed-base, 96-byte partials all-gathered over RCCL and folded on every rank), next to the weak-scaling figure above ----
@@ -492,7 +512,7 @@ def main():
 
     # ---- the other form of the same MSM (plain when the step is fixed-base and vice versa), rank 0, N = 1 ----
     other_form = None
-    if solo and not (args.only_step or args.only_ntt):
+    if solo and args.full and not (args.only_step or args.only_ntt):
         if args.form == "fixed":
             h2.bases_unpin_device(d_points)
         else:
@@ -830,7 +850,7 @@ def main():
     if rank == 0:
         ms_step = elapsed / args.steps * 1e3
         adds = world * n * W * args.steps
-        accum_ms = accum_ms_live or stages.get("msm_accum")
+        accum_ms = accum_ms_live or (stages or {}).get("msm_accum")
         roof = msm_roofline(n, accum_ms, "msm_2p%d_%s" % (args.log_n, args.form)) if accum_ms else None
         if roof and solo and not args.no_measure_traffic:  # the dominant kernel's HBM bytes, re-observed by this run
             live = measure_traffic(["--only-step", "--log-n", str(args.log_n), "--form", args.form, "--steps", "5", "--warmup", "2", "--prewarm-ms", "0"],

@@ -3,12 +3,10 @@ reference tree it patches.  No Rust toolchain exists in this image, so nothing h
   * halo2hip-sys/src/ffi.rs is the translation of include/halo2hip.h by tools/gen_rust_extern.py -- regenerated and compared;
   * every `extern "C"` name is exported by libhalo2hip.so, with the header's arity;
   * the #[repr(C)] structs of halo2hip-sys/src/evalh.rs list the header's fields, in the header's order, with matching types;
-  * patches/*.patch apply cleanly (dry run) to a scratch copy of the reference files they touch (skipped where
-    /root/reference does not exist, i.e. on the GPU box)."""
+  * patches/*.patch apply with no fuzz to the reference files they touch, checked against hashes of those files' hunk regions
+    recorded by tests/golden/make_patch_golden.py (the reference tree itself is not needed)."""
 import os
 import re
-import shutil
-import subprocess
 import sys
 
 import pytest
@@ -19,7 +17,6 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import gen_rust_extern  # noqa: E402
 
 SYS = os.path.join(ROOT, "halo2hip-sys")
-REF = "/root/reference"
 
 
 def test_ffi_rs_is_the_translation_of_the_header():
@@ -115,52 +112,84 @@ def test_crate_sources_are_complete():
     assert "rustc-link-lib=dylib=halo2hip" in open(os.path.join(SYS, "build.rs")).read()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF) or shutil.which("patch") is None, reason="needs the reference tree and patch(1)")
-def test_patches_apply_to_the_reference(tmp_path):
+def patch_hunks(path):
+    """[(file, old start line, old line count, old-side lines, new-side lines)] of one unified diff, in order; a hunk whose body
+    does not hold the line counts of its header fails here"""
+    out, rel, lines, i = [], None, open(path).read().split("\n"), 0
+    while i < len(lines):
+        ln = lines[i]
+        i += 1
+        if ln.startswith("+++ b/"):
+            rel = ln[6:].strip()
+        elif ln.startswith("@@ "):
+            m = re.match(r"@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@", ln)
+            start, n_old, n_new = int(m.group(1)), int(m.group(2) or 1), int(m.group(4) or 1)
+            pre, post = [], []
+            while len(pre) < n_old or len(post) < n_new:
+                body = lines[i]
+                i += 1
+                if body.startswith("\\"):
+                    continue
+                tag, text = (body[:1] or " "), body[1:]
+                assert tag in " -+" and len(pre) + (tag != "+") <= n_old and len(post) + (tag != "-") <= n_new, (path, start, body)
+                if tag != "+":
+                    pre.append(text)
+                if tag != "-":
+                    post.append(text)
+            out.append((rel, start, n_old, pre, post))
+    return out
+
+
+# what the patched reference files must hold: {file: {string: occurrences, or None for at least one}}; tests/golden/make_patch_golden.py
+# records how often the unpatched files hold each, and the hunks account for the rest
+PATCHED = {
+    # 0004: the domain conversions try the fused engine calls first, and the two places that convert columns back to back batch them
+    "halo2_proofs/src/poly/domain.rs": dict.fromkeys((
+        "halo2hip_sys::try_ifft(a, &omega_inv, log_n, &divisor)", "halo2hip_sys::try_coeff_to_extended_in_place(", "halo2hip_sys::try_extended_to_coeff(",
+        "halo2hip_sys::try_ifft_batch(", "halo2hip_sys::try_coeff_to_extended_batch(", "pub fn lagrange_to_coeff_batch(", "pub fn coeff_to_extended_batch(")),
+    "halo2_proofs/src/plonk/prover.rs": {"domain.lagrange_to_coeff_batch(advice_polys)": None, ".map(|poly| domain.lagrange_to_coeff(poly))": 0,
+                                         # 0005: the back-to-back commits go through the batch methods ...
+                                         "params.commit_lagrange_batch(&advice_values, &blinds)": None, "params.commit_lagrange(poly, *blind)": 0},
+    "halo2_proofs/src/plonk/evaluation.rs": {"domain.coeff_to_extended_batch(": 2, "domain.coeff_to_extended(poly.clone())": 0},
+    "halo2_proofs/src/plonk/vanishing/prover.rs": {"params.commit_batch(&h_pieces, &h_blinds)": None},
+    # ... which ParamsKZG overrides with try_multiexp_batch
+    "halo2_proofs/src/poly/kzg/commitment.rs": {"halo2hip_sys::try_multiexp_batch::<E::G1Affine>(": 2},
+    "halo2_proofs/src/poly/commitment.rs": {"fn commit_lagrange_batch(": None, "fn commit_batch(": None},
+    # 0006: the proving key releases the device copies of its constant columns
+    "halo2_proofs/src/plonk.rs": {"impl<C: CurveAffine> Drop for ProvingKey<C>": None, "halo2hip_sys::evalh::unpin_key_columns(&columns)": None},
+}
+
+
+def test_patches_apply_to_the_reference():
+    """patches/*.patch apply, in order and with no fuzz, to the reference files they were written against, without the reference
+    tree: every hunk's old side hashes to what tests/golden/make_patch_golden.py recorded at the hunk's own line of that file (with
+    the earlier patches applied), so each hunk lands where its header says.  The patched files are then judged on the hunks' new
+    sides and on the recorded number of each asserted string in the unpatched files."""
+    import hashlib
+    import json
     patches = sorted(f for f in os.listdir(os.path.join(ROOT, "patches")) if f.endswith(".patch"))
     assert len(patches) >= 6
-    touched = set()
-    for p in patches:
-        for line in open(os.path.join(ROOT, "patches", p)):
-            if line.startswith("+++ b/"):
-                touched.add(line[6:].strip())
+    hunks = [(p,) + h for p in patches for h in patch_hunks(os.path.join(ROOT, "patches", p))]
+    touched = {h[1] for h in hunks}
     assert {"halo2_proofs/src/arithmetic.rs", "halo2_proofs/src/poly/kzg/commitment.rs", "halo2_proofs/src/plonk/evaluation.rs",
             "halo2_proofs/Cargo.toml", "halo2_proofs/src/poly/domain.rs", "halo2_proofs/src/plonk/prover.rs",
             "halo2_proofs/src/poly/commitment.rs", "halo2_proofs/src/plonk/vanishing/prover.rs", "halo2_proofs/src/plonk.rs"} <= touched
-    for rel in touched:  # a scratch copy of just those files (nothing of the reference enters the repository)
-        dst = tmp_path / rel
-        dst.parent.mkdir(parents=True, exist_ok=True)
-        shutil.copy(os.path.join(REF, rel), dst)
-    for p in patches:
-        r = subprocess.run(["patch", "-p1", "--dry-run", "--fuzz=0", "-i", os.path.join(ROOT, "patches", p)], cwd=tmp_path, capture_output=True, text=True)
-        assert r.returncode == 0, p + "\n" + r.stdout + r.stderr
-    # and for real, so that the dispatch lines can be seen where DESIGN.md says they land
-    for p in patches:
-        subprocess.run(["patch", "-p1", "--fuzz=0", "-i", os.path.join(ROOT, "patches", p)], cwd=tmp_path, check=True, capture_output=True)
-    arith = (tmp_path / "halo2_proofs/src/arithmetic.rs").read_text().splitlines()
-    i = next(k for k, ln in enumerate(arith) if ln.startswith("pub fn best_multiexp"))
-    assert "assert_eq!(coeffs.len(), bases.len());" in arith[i + 1] and "halo2hip_sys::try_multiexp::<C>(coeffs, bases)" in arith[i + 2]
-    j = next(k for k, ln in enumerate(arith) if "assert_eq!(n, 1 << log_n);" in ln)
-    assert "halo2hip_sys::try_fft(a, &omega, log_n)" in arith[j + 1]
-    # 0004: the domain conversions try the fused engine calls first, and the two places that convert columns back to back batch them
-    dom = (tmp_path / "halo2_proofs/src/poly/domain.rs").read_text()
-    for call in ("halo2hip_sys::try_ifft(a, &omega_inv, log_n, &divisor)", "halo2hip_sys::try_coeff_to_extended_in_place(", "halo2hip_sys::try_extended_to_coeff(",
-                 "halo2hip_sys::try_ifft_batch(", "halo2hip_sys::try_coeff_to_extended_batch(", "pub fn lagrange_to_coeff_batch(", "pub fn coeff_to_extended_batch("):
-        assert call in dom, call
-    prover = (tmp_path / "halo2_proofs/src/plonk/prover.rs").read_text()
-    assert "domain.lagrange_to_coeff_batch(advice_polys)" in prover and ".map(|poly| domain.lagrange_to_coeff(poly))" not in prover
-    evaluation = (tmp_path / "halo2_proofs/src/plonk/evaluation.rs").read_text()
-    assert evaluation.count("domain.coeff_to_extended_batch(") == 2 and "domain.coeff_to_extended(poly.clone())" not in evaluation
-    # 0005: the back-to-back commits go through the batch methods, which ParamsKZG overrides with try_multiexp_batch
-    assert "params.commit_lagrange_batch(&advice_values, &blinds)" in prover and "params.commit_lagrange(poly, *blind)" not in prover
-    assert "params.commit_batch(&h_pieces, &h_blinds)" in (tmp_path / "halo2_proofs/src/plonk/vanishing/prover.rs").read_text()
-    kzg = (tmp_path / "halo2_proofs/src/poly/kzg/commitment.rs").read_text()
-    assert kzg.count("halo2hip_sys::try_multiexp_batch::<E::G1Affine>(") == 2
-    trait = (tmp_path / "halo2_proofs/src/poly/commitment.rs").read_text()
-    assert "fn commit_lagrange_batch(" in trait and "fn commit_batch(" in trait
-    # 0006: the proving key releases the device copies of its constant columns
-    plonk = (tmp_path / "halo2_proofs/src/plonk.rs").read_text()
-    assert "impl<C: CurveAffine> Drop for ProvingKey<C>" in plonk and "halo2hip_sys::evalh::unpin_key_columns(&columns)" in plonk
+    ref = json.load(open(os.path.join(ROOT, "tests", "golden", "patches_reference.json")))
+    assert [(p, rel, start, n) for p, rel, start, n, _, _ in hunks] == [(g["patch"], g["file"], g["old_start"], g["old_lines"]) for g in ref["hunks"]]
+    for (p, rel, start, _, pre, _), g in zip(hunks, ref["hunks"]):
+        assert hashlib.sha256("\n".join(pre).encode()).hexdigest() == g["sha256"], "%s does not apply at %s:%d" % (p, rel, start)
+    # the dispatch lines land where DESIGN.md says: right after the reference's length asserts
+    arith = [h[5] for h in hunks if h[1] == "halo2_proofs/src/arithmetic.rs"]
+    i, post = next((k, post) for post in arith for k, ln in enumerate(post) if ln.startswith("pub fn best_multiexp"))
+    assert "assert_eq!(coeffs.len(), bases.len());" in post[i + 1] and "halo2hip_sys::try_multiexp::<C>(coeffs, bases)" in post[i + 2]
+    j, post = next((k, post) for post in arith for k, ln in enumerate(post) if "assert_eq!(n, 1 << log_n);" in ln)
+    assert "halo2hip_sys::try_fft(a, &omega, log_n)" in post[j + 1]
+    assert set(ref["counts"]) == set(PATCHED)
+    for rel, want in PATCHED.items():
+        assert set(ref["counts"][rel]) == set(want), rel
+        for s, n in want.items():
+            got = ref["counts"][rel][s] + sum(sum(ln.count(s) for ln in h[5]) - sum(ln.count(s) for ln in h[4]) for h in hunks if h[1] == rel)
+            assert got == n if n is not None else got >= 1, (rel, s, got)
     # every halo2hip_sys item the patches call exists in the crate
     called = set()
     for p in patches:

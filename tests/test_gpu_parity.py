@@ -1,10 +1,15 @@
 """GPU parity tests: the HIP path, called through the C ABI, against the CPU oracle and the
 golden vectors.  Bit-exact: NTT outputs limb for limb, MSM outputs after normalising to affine
 (SURVEY.md Appendix B).  Run with `pytest -m gpu` on an MI355X."""
+import json
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
+
+from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
@@ -136,6 +141,24 @@ def test_msm_full_size_2p20(h2, oracle):
     assert np.array_equal(aff(h2, full), want)
     parts = [h2.msm_device(ds[i * (n // 4):(i + 1) * (n // 4)], dp[i * (n // 4):(i + 1) * (n // 4)]) for i in range(4)]
     assert np.array_equal(aff(h2, h2.g1_fold(np.stack(parts))), want)
+
+
+def test_bench_dump_outputs_is_the_msm_of_its_inputs(oracle, tmp_path):
+    """A plain `bench.py --dump-outputs DIR` run: exactly --steps timed steps, none of the --full legs, and DIR holds the last
+    step's MSM -- the oracle's MSM of the benchmark's seeded inputs, as the affine point's 32-bit words in float64."""
+    log_n = 16
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--log-n", str(log_n),
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["metric"] == "bn254_msm_g1_adds_per_sec" and line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert all(line[k] is None for k in ("stage_ms", "cpu_baseline", "other_form", "batched", "ntt", "sizes", "next_rows"))
+    assert os.listdir(tmp_path / "out") == ["msm_result_affine.npy"]
+    got = np.load(tmp_path / "out" / "msm_result_affine.npy")
+    n = 1 << log_n
+    want = oracle.g1_to_affine(oracle.best_multiexp(oracle.gen_scalars(0x5EED0001, n, num_threads=NT),
+                                                    oracle.gen_points(0x5EED0002, n, num_threads=NT), NT))
+    assert got.dtype == np.float64 and np.array_equal(got, want.view(np.uint32).reshape(2, 8).astype(np.float64))
 
 
 # ---------------------------------------------------------------------------- NTT
