@@ -304,6 +304,69 @@ def fr_to_int(limbs):
     m = sum(int(x) << (64 * i) for i, x in enumerate(np.asarray(limbs, dtype=np.uint64).reshape(4)))
     return m * pow(_FR_R, -1, FR_MODULUS) % FR_MODULUS
 
+# ------------------------------------------------------------------ grand products (permutation / lookup arguments), BatchInvert
+def _cols(arrays, n, what):
+    out = []
+    for a in arrays:
+        a = _u64(a, 4)
+        if a.shape[0] != n:
+            raise ValueError("%s: expected %d rows, got %d" % (what, n, a.shape[0]))
+        out.append(a)
+    return out
+
+
+def _blinding(blinding, n_out, b):
+    if blinding is None:
+        return np.zeros((max(1, n_out * b), 4), dtype=np.uint64)
+    bl = np.ascontiguousarray(_u64(blinding).reshape(-1, 4))
+    if bl.shape[0] != n_out * b:
+        raise ValueError("blinding: expected %d values (%d outputs x %d), got %d" % (n_out * b, n_out, b, bl.shape[0]))
+    return bl if bl.shape[0] else np.zeros((1, 4), dtype=np.uint64)
+
+
+def permutation_products(k, omega, delta, beta, gamma, columns, permutations, chunk_len, blinding, blinding_factors):
+    """permutation::Argument::commit's z columns (permutation/prover.rs:96-166): columns[c] / permutations[c] are (2^k, 4) uint64
+    Lagrange columns p_c / s_c; blinding is (n_sets * blinding_factors, 4), the caller's values for rows 2^k - b .. 2^k - 1 of each set.
+    Returns the list of n_sets = ceil(len(columns) / chunk_len) columns z_t, (2^k, 4) uint64 each."""
+    n = 1 << int(k)
+    cols = _cols(columns, n, "columns")
+    perms = _cols(permutations, n, "permutations")
+    if len(cols) != len(perms):
+        raise ValueError("columns and permutations differ in length")
+    n_sets = -(-len(cols) // int(chunk_len)) if chunk_len else 0
+    bl = _blinding(blinding, n_sets, int(blinding_factors))
+    z = [np.zeros((n, 4), dtype=np.uint64) for _ in range(n_sets)]
+    _check(lib().h2hip_permutation_products_bn254(ctypes.c_uint32(k), _p(_fe(omega)), _p(_fe(delta)), _p(_fe(beta)), _p(_fe(gamma)),
+                                                  _host_ptrs(cols), _host_ptrs(perms), ctypes.c_uint32(len(cols)), ctypes.c_uint32(chunk_len),
+                                                  _p(bl), ctypes.c_uint32(blinding_factors), _host_ptrs(z)),
+           "h2hip_permutation_products_bn254")
+    return z
+
+
+def lookup_products(k, beta, gamma, compressed_inputs, compressed_tables, permuted_inputs, permuted_tables, blinding, blinding_factors):
+    """lookup::Permuted::commit_product's z columns (lookup/prover.rs:194-249), one per lookup: lists of (2^k, 4) uint64 columns A, S, A', S';
+    blinding is (count * blinding_factors, 4).  Returns the list of z columns."""
+    n = 1 << int(k)
+    a, s = _cols(compressed_inputs, n, "compressed_inputs"), _cols(compressed_tables, n, "compressed_tables")
+    ap, sp = _cols(permuted_inputs, n, "permuted_inputs"), _cols(permuted_tables, n, "permuted_tables")
+    count = len(a)
+    if not (len(s) == len(ap) == len(sp) == count):
+        raise ValueError("lookup columns differ in count")
+    bl = _blinding(blinding, count, int(blinding_factors))
+    z = [np.zeros((n, 4), dtype=np.uint64) for _ in range(count)]
+    _check(lib().h2hip_lookup_products_bn254(ctypes.c_uint32(k), _p(_fe(beta)), _p(_fe(gamma)), _host_ptrs(a), _host_ptrs(s), _host_ptrs(ap),
+                                             _host_ptrs(sp), ctypes.c_size_t(count), _p(bl), ctypes.c_uint32(blinding_factors), _host_ptrs(z)),
+           "h2hip_lookup_products_bn254")
+    return z
+
+
+def batch_invert(a):
+    """ff's BatchInvert on a (n, 4) uint64 array of Montgomery Fr elements: a new array of the inverses, zeros stay zero"""
+    out = _u64(a, 4).copy()
+    _check(lib().h2hip_batch_invert_bn254_fr(_p(out), ctypes.c_size_t(out.shape[0])), "h2hip_batch_invert_bn254_fr")
+    return out
+
+
 
 # ------------------------------------------------------------------ poly/domain.rs
 class EvaluationDomain:
@@ -605,6 +668,32 @@ def coeff_to_extended_batch_device(d_list, k, extended_k, extended_omega, g_cose
     _check(lib().h2hip_coeff_to_extended_bn254_fr_batch_device(_ptr_array(d_list), ctypes.c_size_t(len(d_list)), ctypes.c_uint32(k),
                                                                ctypes.c_uint32(extended_k), _p(_fe(extended_omega)), _p(_fe(g_coset)),
                                                                _p(_fe(g_coset_inv)), _stream()), "h2hip_coeff_to_extended_bn254_fr_batch_device")
+
+def permutation_products_device(k, omega, delta, beta, gamma, d_columns, d_permutations, chunk_len, blinding, blinding_factors, d_z):
+    """device form of permutation_products: torch CUDA tensors of 2^k x 32 B in, the n_sets tensors of d_z written; queued on the
+    current stream, not waited for"""
+    bl = _blinding(blinding, len(d_z), int(blinding_factors))
+    _check(lib().h2hip_permutation_products_bn254_device(ctypes.c_uint32(k), _p(_fe(omega)), _p(_fe(delta)), _p(_fe(beta)), _p(_fe(gamma)),
+                                                         _ptr_array(d_columns), _ptr_array(d_permutations), ctypes.c_uint32(len(d_columns)),
+                                                         ctypes.c_uint32(chunk_len), _p(bl), ctypes.c_uint32(blinding_factors), _ptr_array(d_z),
+                                                         _stream()), "h2hip_permutation_products_bn254_device")
+
+
+def lookup_products_device(k, beta, gamma, d_compressed_inputs, d_compressed_tables, d_permuted_inputs, d_permuted_tables, blinding,
+                           blinding_factors, d_z):
+    """device form of lookup_products; queued on the current stream, not waited for"""
+    bl = _blinding(blinding, len(d_z), int(blinding_factors))
+    _check(lib().h2hip_lookup_products_bn254_device(ctypes.c_uint32(k), _p(_fe(beta)), _p(_fe(gamma)), _ptr_array(d_compressed_inputs),
+                                                    _ptr_array(d_compressed_tables), _ptr_array(d_permuted_inputs), _ptr_array(d_permuted_tables),
+                                                    ctypes.c_size_t(len(d_z)), _p(bl), ctypes.c_uint32(blinding_factors), _ptr_array(d_z),
+                                                    _stream()), "h2hip_lookup_products_bn254_device")
+
+
+def batch_invert_device(d_a, n=None):
+    """BatchInvert in place on a torch CUDA tensor of n x 32 B; queued on the current stream, not waited for"""
+    n = d_a.numel() * d_a.element_size() // 32 if n is None else int(n)
+    _check(lib().h2hip_batch_invert_bn254_fr_device(_dptr(d_a), ctypes.c_size_t(n), _stream()), "h2hip_batch_invert_bn254_fr_device")
+
 
 
 def gen_scalars_device(seed, n, start=0, device="cuda"):

@@ -719,7 +719,7 @@ static inline void xyzz_to_out(const XYZZ& r, uint64_t out_xyz[12]) {
     memcpy(out_xyz, &j, 96);
 }
 
-static int check_fr(const uint64_t v[4], const char* what) {
+int check_fr(const uint64_t v[4], const char* what) {
     Fe f = fe_from_u64x4(v);
     if (!fe_is_canonical<FrP>(f)) {
         set_error("%s is not a reduced Fr element", what);
@@ -728,60 +728,51 @@ static int check_fr(const uint64_t v[4], const char* what) {
     return 0;
 }
 
-struct Entry {
-    Ctx* c;
-    std::shared_lock<std::shared_mutex> engine;
-    std::vector<std::unique_lock<std::recursive_mutex>> held;  // the contexts this call owns, in list order
-    int rc;
-    bool ranged = false;
-    // d_ptr: a device pointer of the call, or nullptr; with several devices the call runs on the device that owns it.
-    // all_devices: the call reads or changes every device's state (pinned caches, multi-device MSM).
-    explicit Entry(const char* name = nullptr, const void* d_ptr = nullptr, bool all_devices = false) : c(ctx()), rc(0) {
-        for (;;) {
-            rc = ensure_init();
-            if (rc) return;
-            engine = std::shared_lock<std::shared_mutex>(g_engine_mu);
-            if (ctx()->ready) break;
-            engine.unlock();  // shut down by another thread in between: initialise again
-        }
-        if (d_ptr && g_devs.size() > 1) {
-            hipPointerAttribute_t at;
-            if (hipPointerGetAttributes(&at, d_ptr) == hipSuccess) {
-                Ctx* owner = nullptr;
-                for (Ctx* x : g_devs)
-                    if (x->device == at.device) {
-                        owner = x;
-                        break;
-                    }
-                if (!owner) {
-                    set_error("device pointer belongs to device %d, which is not in h2hip_init's list", at.device);
-                    rc = H2HIP_EINVAL;
-                    return;
+Entry::Entry(const char* name, const void* d_ptr, bool all_devices) : c(ctx()), rc(0) {
+    for (;;) {
+        rc = ensure_init();
+        if (rc) return;
+        engine = std::shared_lock<std::shared_mutex>(g_engine_mu);
+        if (ctx()->ready) break;
+        engine.unlock();  // shut down by another thread in between: initialise again
+    }
+    if (d_ptr && g_devs.size() > 1) {
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, d_ptr) == hipSuccess) {
+            Ctx* owner = nullptr;
+            for (Ctx* x : g_devs)
+                if (x->device == at.device) {
+                    owner = x;
+                    break;
                 }
-                c = owner;
-            } else {
-                (void)hipGetLastError();
+            if (!owner) {
+                set_error("device pointer belongs to device %d, which is not in h2hip_init's list", at.device);
+                rc = H2HIP_EINVAL;
+                return;
             }
-        }
-        if (all_devices) {
-            for (Ctx* x : g_devs) held.emplace_back(x->mu);
+            c = owner;
         } else {
-            held.emplace_back(c->mu);
-        }
-        if (hipSetDevice(c->device) != hipSuccess) {
-            set_error("hipSetDevice(%d) failed", c->device);
-            rc = H2HIP_EDEVICE;
-            return;
-        }
-        if (name && g_roctx_push) {
-            g_roctx_push(name);
-            ranged = true;
+            (void)hipGetLastError();
         }
     }
-    ~Entry() {
-        if (ranged) g_roctx_pop();
+    if (all_devices) {
+        for (Ctx* x : g_devs) held.emplace_back(x->mu);
+    } else {
+        held.emplace_back(c->mu);
     }
-};
+    if (hipSetDevice(c->device) != hipSuccess) {
+        set_error("hipSetDevice(%d) failed", c->device);
+        rc = H2HIP_EDEVICE;
+        return;
+    }
+    if (name && g_roctx_push) {
+        g_roctx_push(name);
+        ranged = true;
+    }
+}
+Entry::~Entry() {
+    if (ranged) g_roctx_pop();
+}
 
 static int ntt_host(uint64_t* a, const Fe& omega, uint32_t log_n, const NttScale* sc, const uint64_t* src, size_t src_elems) {
     Entry en("h2hip_ntt_host");
@@ -962,6 +953,8 @@ static void release_ctx(Ctx* c) {
     c->ntt_ptrs.release();
     c->gather.release();
     c->gen_table.release();
+    c->prod_ws.release();
+    c->prod_io.release();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     c->stream = nullptr;
     for (auto e : c->aux_events) (void)hipEventDestroy(e);

@@ -7,6 +7,7 @@
 
 #include <map>
 #include <mutex>
+#include <shared_mutex>
 #include <string>
 #include <vector>
 
@@ -153,6 +154,7 @@ struct Ctx {
     hipStream_t stream = nullptr;  // the engine's own stream (host-pointer entry points)
     std::recursive_mutex mu;       // serialises entry points: re-entrant callers (rayon workers) are safe
     DevBuf ntt_ws, ntt_io, msm_scalars[3], msm_bases, msm_slot[3], misc, evalh_ws, evalh_slots, ecfft_ws, ntt_ptrs, gather, gen_table;
+    DevBuf prod_ws, prod_io;       // product.hip: scans' workspace; the host-pointer forms' columns
     HostBuf host_ws;               // pinned host memory for the window sums coming back
     HostBuf host_planes;           // ... and for the bit-plane sums of a run whose tail the host finishes (msm.hip msm_planes_finish)
     HostBuf pin_flag;              // one word the device-key fingerprint check writes its verdict to
@@ -231,6 +233,19 @@ struct WsGuard {
     }
 };
 
+// api.hip: the guard every entry point takes -- the engine initialised and held shared, the context's lock, hipSetDevice, a roctx range.
+// d_ptr: a device pointer of the call, or nullptr; with several devices the call runs on the device that owns it.
+// all_devices: the call reads or changes every device's state (pinned caches, multi-device MSM).  rc != 0: the call must return it.
+struct Entry {
+    Ctx* c;
+    std::shared_lock<std::shared_mutex> engine;
+    std::vector<std::unique_lock<std::recursive_mutex>> held;  // the contexts this call owns, in list order
+    int rc;
+    bool ranged = false;
+    explicit Entry(const char* name = nullptr, const void* d_ptr = nullptr, bool all_devices = false);
+    ~Entry();
+};
+int check_fr(const uint64_t v[4], const char* what);  // H2HIP_EINVAL (and set_error) unless v is a reduced Fr element
 Ctx* ctx();             // the primary device's context (device_ids[0] of h2hip_init)
 int n_devices();        // devices the engine was initialised with (>= 1 once ready)
 Ctx* ctx_at(int i);     // context of the i-th device of h2hip_init's list
@@ -261,6 +276,14 @@ int g_to_lagrange_device(Ctx* c, const Affine* d_g, uint32_t k, Affine* d_out, h
 int ec_normalize_device(const XYZZ* d_in, Affine* d_out, uint64_t n, hipStream_t s);  // batched XYZZ -> affine
 int fft_g1_device(Ctx* c, Jac* d_a, const Fe& omega, uint32_t log_n, hipStream_t s);   // best_fft::<G1>, in place on Jacobian points
 
+// product.hip: the permutation / lookup grand products and ff's BatchInvert, enqueued on s (no synchronisation).  cols / perms are
+// host arrays of device pointers; for lookups inputs_tables[2j], [2j + 1] = A_j, S_j and permuted[2j], [2j + 1] = A'_j, S'_j
+int permutation_products_device(Ctx* c, uint32_t k, const Fe& omega, const Fe& delta, const Fe& beta, const Fe& gamma,
+                                const Fe* const* cols, const Fe* const* perms, uint32_t n_columns, uint32_t chunk_len,
+                                const uint64_t* blinding, uint32_t bf, Fe* const* z, hipStream_t s);
+int lookup_products_device(Ctx* c, uint32_t k, const Fe& beta, const Fe& gamma, const Fe* const* inputs_tables,
+                           const Fe* const* permuted, size_t count, const uint64_t* blinding, uint32_t bf, Fe* const* z, hipStream_t s);
+int batch_invert_device(Ctx* c, Fe* d_a, uint64_t n, hipStream_t s);
 // setup.hip
 int kzg_setup_device(Ctx* c, uint32_t k, const Fe& s, Affine* d_g, Affine* d_gl, hipStream_t stream);
 

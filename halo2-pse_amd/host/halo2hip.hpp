@@ -388,4 +388,67 @@ class ParamsKZG {
 
 }  // namespace kzg
 }  // namespace poly
+
+// The grand-product columns of create_proof (h2hip_permutation_products_bn254 / h2hip_lookup_products_bn254).  Blinding values are the
+// caller's, drawn in the reference's order: b per set or lookup, set-major.
+namespace plonk {
+
+// permutation::Argument::commit's z columns (plonk/permutation/prover.rs:96-166): one per set of chunk_len columns, last_z carried
+// from set to set.  columns[c] = p_c resolved from advice / fixed / instance, permutations[c] = pkey.permutations[c].
+inline std::vector<poly::Polynomial<poly::LagrangeCoeff>> permutation_products(
+    const poly::EvaluationDomain& domain, const std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>& columns,
+    const std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>& permutations, size_t chunk_len, const Fr& beta, const Fr& gamma,
+    const std::vector<Fr>& blinding, size_t blinding_factors) {
+    if (columns.size() != permutations.size()) throw std::logic_error("columns and permutations differ in length");
+    if (chunk_len == 0) throw std::logic_error("chunk_len == 0");
+    const size_t n_sets = (columns.size() + chunk_len - 1) / chunk_len;
+    if (blinding.size() != n_sets * blinding_factors) throw std::logic_error("blinding: n_sets * blinding_factors values expected");
+    std::vector<const uint64_t*> p, s;
+    for (size_t c = 0; c < columns.size(); c++) {
+        if (columns[c]->len() != domain.n || permutations[c]->len() != domain.n) throw std::logic_error("column length != n");
+        p.push_back(columns[c]->values[0].l);
+        s.push_back(permutations[c]->values[0].l);
+    }
+    std::vector<poly::Polynomial<poly::LagrangeCoeff>> z(n_sets, poly::Polynomial<poly::LagrangeCoeff>{std::vector<Fr>(domain.n)});
+    std::vector<uint64_t*> zp;
+    for (auto& col : z) zp.push_back(col.values[0].l);
+    Fr delta = Fr::delta();
+    engine_check(h2hip_permutation_products_bn254(domain.k, domain.omega.l, delta.l, beta.l, gamma.l, p.data(), s.data(), uint32_t(p.size()),
+                                                  uint32_t(chunk_len), blinding.empty() ? nullptr : blinding[0].l, uint32_t(blinding_factors),
+                                                  zp.data()),
+                 "permutation_products");
+    return z;
+}
+
+// lookup::Permuted::commit_product's z columns (plonk/lookup/prover.rs:194-249), one per lookup: inputs / tables are the compressed
+// expressions A, S, permuted_inputs / permuted_tables A', S'
+inline std::vector<poly::Polynomial<poly::LagrangeCoeff>> lookup_products(
+    const poly::EvaluationDomain& domain, const std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>& inputs,
+    const std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>& tables,
+    const std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>& permuted_inputs,
+    const std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>& permuted_tables, const Fr& beta, const Fr& gamma,
+    const std::vector<Fr>& blinding, size_t blinding_factors) {
+    const size_t count = inputs.size();
+    if (tables.size() != count || permuted_inputs.size() != count || permuted_tables.size() != count)
+        throw std::logic_error("lookup columns differ in count");
+    if (blinding.size() != count * blinding_factors) throw std::logic_error("blinding: count * blinding_factors values expected");
+    std::vector<const uint64_t*> a, s, ap, sp;
+    for (size_t j = 0; j < count; j++) {
+        for (auto* col : {inputs[j], tables[j], permuted_inputs[j], permuted_tables[j]})
+            if (col->len() != domain.n) throw std::logic_error("column length != n");
+        a.push_back(inputs[j]->values[0].l);
+        s.push_back(tables[j]->values[0].l);
+        ap.push_back(permuted_inputs[j]->values[0].l);
+        sp.push_back(permuted_tables[j]->values[0].l);
+    }
+    std::vector<poly::Polynomial<poly::LagrangeCoeff>> z(count, poly::Polynomial<poly::LagrangeCoeff>{std::vector<Fr>(domain.n)});
+    std::vector<uint64_t*> zp;
+    for (auto& col : z) zp.push_back(col.values[0].l);
+    engine_check(h2hip_lookup_products_bn254(domain.k, beta.l, gamma.l, a.data(), s.data(), ap.data(), sp.data(), count,
+                                             blinding.empty() ? nullptr : blinding[0].l, uint32_t(blinding_factors), zp.data()),
+                 "lookup_products");
+    return z;
+}
+
+}  // namespace plonk
 }  // namespace halo2_proofs

@@ -250,3 +250,61 @@ pub fn try_extended_to_coeff<G: 'static, S: 'static>(a: &mut [G], extended_k: u3
         ffi::h2hip_extended_to_coeff_bn254_fr(a.as_mut_ptr() as *mut u64, extended_k, fr_ptr(extended_omega_inv), fr_ptr(extended_ifft_divisor), fr_ptr(g_coset), fr_ptr(g_coset_inv)) == 0
     }
 }
+
+/// `permutation::Argument::commit`'s z columns (plonk/permutation/prover.rs:96-166) for every set in one call: `columns[c]` are the
+/// permutation's columns resolved from advice / fixed / instance, `permutations[c]` is `pkey.permutations[c]`, `blinding` the
+/// `blinding_factors` values of each set, set-major, drawn by the caller in the reference's rng order.
+/// `Some(z)` (one column per set) when the engine took the call; `None` for any other field, shape or engine failure.
+#[allow(clippy::too_many_arguments)]
+pub fn try_permutation_products<F: Field + 'static>(k: u32, omega: &F, delta: &F, beta: &F, gamma: &F, columns: &[&[F]], permutations: &[&[F]],
+                                                    chunk_len: usize, blinding: &[F], blinding_factors: usize) -> Option<Vec<Vec<F>>> {
+    if !is::<F, Fr>() || !layout_ok() || k > 28 || chunk_len == 0 || columns.len() != permutations.len() || chunk_len > u32::MAX as usize {
+        return None;
+    }
+    let n = 1usize << k;
+    let n_sets = (columns.len() + chunk_len - 1) / chunk_len;
+    if columns.iter().chain(permutations.iter()).any(|c| c.len() != n) || blinding.len() != n_sets * blinding_factors || blinding_factors + 1 >= n {
+        return None;
+    }
+    let p: Vec<*const u64> = columns.iter().map(|c| c.as_ptr() as *const u64).collect();
+    let s: Vec<*const u64> = permutations.iter().map(|c| c.as_ptr() as *const u64).collect();
+    let mut z: Vec<Vec<F>> = (0..n_sets).map(|_| vec![F::zero(); n]).collect();
+    let zp: Vec<*mut u64> = z.iter_mut().map(|c| c.as_mut_ptr() as *mut u64).collect();
+    let rc = unsafe {
+        ffi::h2hip_permutation_products_bn254(k, fr_ptr(omega), fr_ptr(delta), fr_ptr(beta), fr_ptr(gamma), p.as_ptr(), s.as_ptr(), p.len() as u32,
+                                              chunk_len as u32, blinding.as_ptr() as *const u64, blinding_factors as u32, zp.as_ptr())
+    };
+    if rc != 0 {
+        return None;
+    }
+    Some(z)
+}
+
+/// `lookup::Permuted::commit_product`'s z columns (plonk/lookup/prover.rs:194-249) for several lookups in one call: the compressed
+/// input / table expressions and the permuted columns of each lookup, `blinding` lookup-major.  `None` on any failure.
+#[allow(clippy::too_many_arguments)]
+pub fn try_lookup_products<F: Field + 'static>(k: u32, beta: &F, gamma: &F, compressed_inputs: &[&[F]], compressed_tables: &[&[F]],
+                                               permuted_inputs: &[&[F]], permuted_tables: &[&[F]], blinding: &[F],
+                                               blinding_factors: usize) -> Option<Vec<Vec<F>>> {
+    let count = compressed_inputs.len();
+    if !is::<F, Fr>() || !layout_ok() || k > 28 || compressed_tables.len() != count || permuted_inputs.len() != count || permuted_tables.len() != count {
+        return None;
+    }
+    let n = 1usize << k;
+    let all = compressed_inputs.iter().chain(compressed_tables.iter()).chain(permuted_inputs.iter()).chain(permuted_tables.iter());
+    if all.clone().any(|c| c.len() != n) || blinding.len() != count * blinding_factors || blinding_factors + 1 >= n {
+        return None;
+    }
+    let ptrs = |cols: &[&[F]]| -> Vec<*const u64> { cols.iter().map(|c| c.as_ptr() as *const u64).collect() };
+    let (a, s, ap, sp) = (ptrs(compressed_inputs), ptrs(compressed_tables), ptrs(permuted_inputs), ptrs(permuted_tables));
+    let mut z: Vec<Vec<F>> = (0..count).map(|_| vec![F::zero(); n]).collect();
+    let zp: Vec<*mut u64> = z.iter_mut().map(|c| c.as_mut_ptr() as *mut u64).collect();
+    let rc = unsafe {
+        ffi::h2hip_lookup_products_bn254(k, fr_ptr(beta), fr_ptr(gamma), a.as_ptr(), s.as_ptr(), ap.as_ptr(), sp.as_ptr(), count,
+                                         blinding.as_ptr() as *const u64, blinding_factors as u32, zp.as_ptr())
+    };
+    if rc != 0 {
+        return None;
+    }
+    Some(z)
+}

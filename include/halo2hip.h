@@ -339,6 +339,38 @@ int h2hip_evaluate_h_bn254(const h2hip_evalh_desc* desc, uint64_t* values);
  * the call does not wait for them. */
 int h2hip_evaluate_h_bn254_device(const h2hip_evalh_desc* desc, void* d_values, void* stream);
 
+/* ---- grand products: permutation::Argument::commit (plonk/permutation/prover.rs:96-166) and lookup::Permuted::commit_product
+ * (plonk/lookup/prover.rs:194-249) -- the z columns create_proof builds between the advice commits and evaluate_h ----------------
+ * n = 2^k, b = blinding_factors, u = n - b - 1; every column is 2^k Fr elements in Lagrange form.
+ * Permutation: columns[c] = p_c (the permutation's columns, resolved from advice / fixed / instance), permutations[c] = pkey.permutations[c];
+ * sets of chunk_len columns (the last may be shorter), n_sets = ceil(n_columns / chunk_len) outputs z[t]:
+ *   z_t[0] = last_z (one for set 0), z_t[i] = z_t[i-1] * prod_c (p_c + beta delta^c omega^(i-1) + gamma) * inv(prod_c (p_c + beta s_c + gamma))
+ *   at row i - 1 (c the global column index), rows n - b .. n - 1 = blinding[t * b ..], last_z = z_t[u] (computed, never a blinding row).
+ * Lookups: z_j[0] = 1, z_j[i] = z_j[i-1] * (A + beta)(S + gamma) * inv((A' + beta)(S' + gamma)) at row i - 1, rows n - b .. = blinding[j * b ..].
+ * inv is ff's BatchInvert: a zero denominator stays zero, so z is zero from the next row on.  The caller draws the blinding values (b per set
+ * or lookup, in the reference's order); the engine draws no randomness.  k <= 28, chunk_len >= 1, b + 1 < n; n_columns == 0 / count == 0 write
+ * nothing.  Host forms: a permutations[c] pinned with h2hip_columns_pin (elems = 2^k) is not uploaded.  _device forms: every column and output
+ * is a device pointer (the pointer tables, scalars and blinding values are host memory, read before the call returns); kernels are queued on
+ * `stream` and the call does not wait for them. */
+int h2hip_permutation_products_bn254(uint32_t k, const uint64_t omega[4], const uint64_t delta[4], const uint64_t beta[4], const uint64_t gamma[4],
+                                     const uint64_t* const* columns, const uint64_t* const* permutations, uint32_t n_columns, uint32_t chunk_len,
+                                     const uint64_t* blinding, uint32_t blinding_factors, uint64_t* const* z);
+int h2hip_permutation_products_bn254_device(uint32_t k, const uint64_t omega[4], const uint64_t delta[4], const uint64_t beta[4],
+                                            const uint64_t gamma[4], const void* const* d_columns, const void* const* d_permutations,
+                                            uint32_t n_columns, uint32_t chunk_len, const uint64_t* blinding, uint32_t blinding_factors,
+                                            void* const* d_z, void* stream);
+int h2hip_lookup_products_bn254(uint32_t k, const uint64_t beta[4], const uint64_t gamma[4], const uint64_t* const* compressed_input,
+                                const uint64_t* const* compressed_table, const uint64_t* const* permuted_input,
+                                const uint64_t* const* permuted_table, size_t count, const uint64_t* blinding, uint32_t blinding_factors,
+                                uint64_t* const* z);
+int h2hip_lookup_products_bn254_device(uint32_t k, const uint64_t beta[4], const uint64_t gamma[4], const void* const* d_compressed_input,
+                                       const void* const* d_compressed_table, const void* const* d_permuted_input,
+                                       const void* const* d_permuted_table, size_t count, const uint64_t* blinding, uint32_t blinding_factors,
+                                       void* const* d_z, void* stream);
+/* ff::BatchInvert (permutation/prover.rs:117, lookup/prover.rs:208): a[i] <- a[i]^-1 in place, zeros stay zero; n <= 2^30 */
+int h2hip_batch_invert_bn254_fr(uint64_t* a, size_t n);
+int h2hip_batch_invert_bn254_fr_device(void* d_a, size_t n, void* stream);
+
 /* ---- synthetic workload; same streams as oracle_gen_{scalars,points} ---- */
 
 int h2hip_gen_scalars_device(uint64_t seed, uint64_t start, size_t n, void* d_out, void* stream);
