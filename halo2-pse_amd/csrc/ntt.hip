@@ -29,6 +29,7 @@
 
 #include <vector>
 
+#include "../../include/halo2hip_debug.h"
 #include "engine.h"
 #include "fieldu.h"
 
@@ -681,7 +682,7 @@ void ntt_set_smax(uint32_t v) { g_ntt_smax = v < 4 ? 4 : (v > 10 ? 10 : v); }
 // a lone 2^19 already 0.078 / 0.091).
 static uint32_t g_ntt_two_lo = 19, g_ntt_two_hi = 22, g_ntt_two_batch_lo = 17;
 static uint64_t g_ntt_two_batch_wgs = 512;
-static bool g_ntt2_attr[64];
+static bool g_ntt_lds_attr[64];
 void ntt_set_two_pass(uint32_t lo, uint32_t hi) {
     if (lo == 0 && hi == 0) {  // the defaults
         g_ntt_two_lo = 19;
@@ -708,6 +709,23 @@ static int plan_passes(uint32_t log_n, uint32_t s_out[4]) {
     uint32_t base = log_n / P, rem = log_n % P;
     for (int t = 0; t < P; t++) s_out[t] = base + ((uint32_t)t < rem ? 1 : 0);
     return P;
+}
+
+// The plan ntt_run takes for `count` transforms of 2^log_n points: the number of passes, their tile radices (first pass first) in S,
+// and in *two whether they are the two-pass plan's (ntt2_*_kernel).  h2hip_debug_ntt_plan reports the same.
+static int ntt_plan(uint32_t log_n, size_t count, uint32_t S[4], bool* two) {
+    *two = log_n <= g_ntt_two_hi &&
+           (log_n >= g_ntt_two_lo || (log_n >= g_ntt_two_batch_lo && ((uint64_t)count << (log_n - (log_n + 1) / 2 - 1)) >= g_ntt_two_batch_wgs));
+    if (*two) {
+        S[0] = (log_n + 1) / 2;
+        S[1] = log_n - S[0];
+        return 2;
+    }
+    if (!log_n) {
+        S[0] = 0;
+        return 1;
+    }
+    return plan_passes(log_n, S);
 }
 
 // The passes of `count` same-size transforms, each launched once with gridDim.y = count.  count == 1: plain pointers
@@ -740,15 +758,9 @@ static int ntt_run(Ctx* c, size_t count, Fe* const* h_datas, const Fe* const* h_
     if (rc0) return rc0;
     WsGuard guard(c, s);
     int tid = c->timer_begin("ntt", s);
-    const bool two = log_n <= g_ntt_two_hi &&
-                     (log_n >= g_ntt_two_lo || (log_n >= g_ntt_two_batch_lo && ((uint64_t)count << (log_n - (log_n + 1) / 2 - 1)) >= g_ntt_two_batch_wgs));
     uint32_t S[4];
-    int P = log_n ? plan_passes(log_n, S) : 1;
-    if (two) {
-        P = 2;
-        S[0] = (log_n + 1) / 2;
-        S[1] = log_n - S[0];
-    }
+    bool two;
+    const int P = ntt_plan(log_n, count, S, &two);
     Fe* ws = nullptr;
     int rc;
     if (P > 1) {
@@ -801,12 +813,15 @@ static int ntt_run(Ctx* c, size_t count, Fe* const* h_datas, const Fe* const* h_
     p.tw_hi = tw.hi;
     p.lo_bits = tw.lo_bits;
     bool folded = false;
+    if (c->device >= 0 && c->device < 64 && !g_ntt_lds_attr[c->device]) {
+        // more than the default 64 KB of dynamic LDS: a 2^11-point image (two-pass plan), two columns of 2^10 points (smax 10)
+        H2_CHECK(hipFuncSetAttribute((const void*)ntt2_strided_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 73728));
+        H2_CHECK(hipFuncSetAttribute((const void*)ntt2_final_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 73728));
+        H2_CHECK(hipFuncSetAttribute((const void*)ntt_strided_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 73728));
+        H2_CHECK(hipFuncSetAttribute((const void*)ntt_final_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 73728));
+        g_ntt_lds_attr[c->device] = true;
+    }
     if (two) {
-        if (c->device >= 0 && c->device < 64 && !g_ntt2_attr[c->device]) {  // a 2^11-point image: more than the default 64 KB of dynamic LDS
-            H2_CHECK(hipFuncSetAttribute((const void*)ntt2_strided_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 73728));
-            H2_CHECK(hipFuncSetAttribute((const void*)ntt2_final_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 73728));
-            g_ntt2_attr[c->device] = true;
-        }
         p.s = S[0];
         // up to 2^21 points the table (36 B per point), the data and the workspace share the 256 MB Infinity Cache: -6 %; at 2^22 they
         // no longer do and the table costs 7 % instead
@@ -946,3 +961,10 @@ int ntt_device_batch(Ctx* c, Fe* const* h_datas, const Fe* const* h_srcs, size_t
 }
 
 }  // namespace h2
+
+// test hook, needs no GPU: the passes ntt_run would take for this call (here, not in api.hip: that file is also built alone against a stub runtime)
+extern "C" int h2hip_debug_ntt_plan(uint32_t log_n, size_t count, uint32_t radices[4]) {
+    if (!radices || log_n > h2::FrP::S) return -1;
+    bool two;
+    return h2::ntt_plan(log_n, count, radices, &two);
+}

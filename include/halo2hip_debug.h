@@ -50,6 +50,10 @@ int h2hip_debug_set_reserved_cus(uint32_t k);
 int h2hip_debug_set_msm_fuse_small(int on);
 /* largest log2 tile of an NTT pass (4..10; default 8, 9 beyond 2^24 points) */
 int h2hip_debug_set_ntt_smax(uint32_t v);
+/* needs no GPU: the plan an NTT of `count` columns of 2^log_n points takes under the settings in force -- returns its number of passes
+ * (1..4; the two-pass plan of 2^19..2^22 reports 2) and fills radices[0 .. passes) with the log2 tile of each pass, first pass first;
+ * -1 for log_n > 28 or a null array */
+int h2hip_debug_ntt_plan(uint32_t log_n, size_t count, uint32_t radices[4]);
 int h2hip_debug_set_lazy_pin(uint32_t after);
 /* sizes 2^lo..2^hi take the two-pass plan (default 19..22; hi < lo: never; 0, 0: back to the defaults) */
 int h2hip_debug_set_ntt_two_pass(uint32_t lo, uint32_t hi);
