@@ -367,6 +367,177 @@ def batch_invert(a):
     return out
 
 
+# ------------------------------------------------------------------ opening: query evaluations and the KZG multiopen quotients
+def _fes(values, what):
+    """a list of field elements ((4,) uint64 Montgomery limbs each) or an (m, 4) array -> a contiguous (max(1, m), 4) array, and m"""
+    a = np.ascontiguousarray(np.asarray(values, dtype=np.uint64).reshape(-1, 4)) if len(values) else np.zeros((0, 4), dtype=np.uint64)
+    m = a.shape[0]
+    return (a if m else np.zeros((1, 4), dtype=np.uint64)), m
+
+
+def eval_polynomials(polys, query_poly, points):
+    """eval_polynomial (arithmetic.rs:304-328) for every query in one call: polys is a list of (len_j, 4) uint64 coefficient arrays,
+    query q evaluates polys[query_poly[q]] at points[q].  Returns (n_queries, 4) uint64."""
+    ps = [_u64(a, 4) if len(a) else np.zeros((0, 4), dtype=np.uint64) for a in polys]
+    lens = (ctypes.c_size_t * max(1, len(ps)))(*[a.shape[0] for a in ps])
+    qp = np.ascontiguousarray(query_poly, dtype=np.uint32).reshape(-1)
+    pts, nq = _fes(points, "points")
+    if qp.shape[0] != nq:
+        raise ValueError("query_poly and points differ in length")
+    out = np.zeros((max(1, nq), 4), dtype=np.uint64)
+    _check(lib().h2hip_eval_polynomials_bn254(_host_ptrs(ps) if ps else None, lens, ctypes.c_size_t(len(ps)), _p(qp if nq else np.zeros(1, np.uint32)),
+                                              _p(pts), ctypes.c_size_t(nq), _p(out)), "h2hip_eval_polynomials_bn254")
+    return out[:nq]
+
+
+def _combine_args(scalars, sub, roots, scale):
+    sc, n_sc = _fes(scalars, "scalars")
+    sb, n_sub = _fes(sub if sub is not None else [], "sub")
+    rt, n_roots = _fes(roots, "roots")
+    one = fr_from_int(1)
+    sl = _fe(scale if scale is not None else one)
+    return sc, n_sc, sb, n_sub, rt, n_roots, sl
+
+
+def poly_combine(polys, scalars, sub=None, roots=(), scale=None, out=None, accumulate=False, out_len=None, remainder=False):
+    """a = sum_j scalars[j] polys[j] - sub, divided by (X - r) for r in roots in order, times scale (h2hip_poly_combine_bn254_fr).
+    polys: (L, 4) uint64 arrays of one length; sub: up to min(L, 16) low coefficients.  Without `out` the result is a new (out_len, 4)
+    array (out_len defaults to L - len(roots)), zero past L - len(roots); with accumulate=True it is added to `out` in place.
+    remainder=True returns (q, a(roots[0]))."""
+    ps = [_u64(a, 4) for a in polys]
+    L = ps[0].shape[0] if ps else 0
+    for a in ps:
+        if a.shape[0] != L:
+            raise ValueError("poly_combine: polynomials differ in length")
+    sc, n_sc, sb, n_sub, rt, n_roots, sl = _combine_args(scalars, sub, roots, scale)
+    if n_sc != len(ps):
+        raise ValueError("poly_combine: %d scalars for %d polynomials" % (n_sc, len(ps)))
+    if out is None:
+        out = np.zeros((max(0, L - n_roots) if out_len is None else int(out_len), 4), dtype=np.uint64)
+    else:
+        assert out.dtype == np.uint64 and out.flags["C_CONTIGUOUS"] and out.ndim == 2 and out.shape[1] == 4
+    rem = np.zeros(4, dtype=np.uint64)
+    _check(lib().h2hip_poly_combine_bn254_fr(_host_ptrs(ps) if ps else None, ctypes.c_size_t(L), _p(sc), ctypes.c_size_t(len(ps)), _p(sb),
+                                             ctypes.c_size_t(n_sub), _p(rt), ctypes.c_size_t(n_roots), _p(sl), ctypes.c_uint32(1 if accumulate else 0),
+                                             _p(out) if out.shape[0] else None, ctypes.c_size_t(out.shape[0]), _p(rem) if remainder else None),
+           "h2hip_poly_combine_bn254_fr")
+    return (out, rem) if remainder else out
+
+
+def kate_division(a, b):
+    """arithmetic.rs:348-366: a(X) / (X - b) without the remainder; a is (L, 4) uint64 with L >= 1, the result (L - 1, 4)"""
+    return poly_combine([a], [fr_from_int(1)], roots=[b])
+
+
+def div_by_vanishing(a, roots):
+    """shplonk/prover.rs:26-31: kate_division by each root in order; (L - len(roots), 4)"""
+    return poly_combine([a], [fr_from_int(1)], roots=list(roots))
+
+
+def _fr_powers(x, m):
+    """powers() (poly/kzg/multiopen/shplonk.rs): 1, x, x^2, ... as integers"""
+    out, acc = [], 1
+    for _ in range(m):
+        out.append(acc)
+        acc = acc * x % FR_MODULUS
+    return out
+
+
+def _fr_lagrange_interpolate(points, evals):
+    """arithmetic.rs:405-460 on integers: the polynomial of degree < len(points) through (points[i], evals[i])"""
+    p, m = FR_MODULUS, len(points)
+    final = [0] * m
+    for j in range(m):
+        basis, denom = [1], 1
+        for k in range(m):
+            if k == j:
+                continue
+            basis = [((basis[i - 1] if i else 0) - points[k] * (basis[i] if i < len(basis) else 0)) % p for i in range(len(basis) + 1)]
+            denom = denom * (points[j] - points[k]) % p
+        f = evals[j] * pow(denom, -1, p) % p
+        for i in range(m):
+            final[i] = (final[i] + f * basis[i]) % p
+    return final
+
+
+def _fr_eval(coeffs, x):
+    acc = 0
+    for c in reversed(coeffs):
+        acc = (acc * x + c) % FR_MODULUS
+    return acc
+
+
+def _fr_vanishing(roots, z):
+    """evaluate_vanishing_polynomial (arithmetic.rs): prod (z - r)"""
+    acc = 1
+    for r in roots:
+        acc = acc * (z - r) % FR_MODULUS
+    return acc
+
+
+def gwc_witnesses(polys, point_groups, v):
+    """GWC's witness polynomials (poly/kzg/multiopen/gwc/prover.rs:61-89), one per point, as (n - 1, 4) arrays.  point_groups is
+    construct_intermediate_sets' output in order: a list of (point, [(poly index, eval), ...]); evals and challenges are Montgomery limbs."""
+    vv = fr_to_int(v)
+    out = []
+    for point, queries in point_groups:
+        pw = _fr_powers(vv, len(queries))
+        ev = sum(pw[i] * fr_to_int(e) for i, (_, e) in enumerate(queries)) % FR_MODULUS
+        out.append(poly_combine([polys[j] for j, _ in queries], [fr_from_int(x) for x in pw], sub=[fr_from_int(ev)], roots=[point]))
+    return out
+
+
+def _shplonk_sets(rotation_sets):
+    """(points as integers, [(poly index, [evals as integers])], interpolants) per rotation set"""
+    out = []
+    for points, commitments in rotation_sets:
+        pts = [fr_to_int(x) for x in points]
+        coms = [(j, [fr_to_int(e) for e in evs]) for j, evs in commitments]
+        out.append((pts, coms, [_fr_lagrange_interpolate(pts, evs) for _, evs in coms]))
+    return out
+
+
+def shplonk_h(polys, rotation_sets, y, v):
+    """SHPLONK's first quotient h_x (shplonk/prover.rs:138-203): rotation_sets in construct_intermediate_sets' order, each
+    (points, [(poly index, [eval at each point]), ...]); polys are (n, 4) coefficient arrays.  Returns h_x, (n, 4)."""
+    yy, vv = fr_to_int(y), fr_to_int(v)
+    n = polys[0].shape[0]
+    h = np.zeros((n, 4), dtype=np.uint64)
+    for i, (pts, coms, interp) in enumerate(_shplonk_sets(rotation_sets)):
+        py = _fr_powers(yy, len(coms))
+        sub = [sum(py[c] * interp[c][t] for c in range(len(coms))) % FR_MODULUS for t in range(len(pts))]
+        poly_combine([polys[j] for j, _ in coms], [fr_from_int(x) for x in py], sub=[fr_from_int(x) for x in sub],
+                     roots=[fr_from_int(x) for x in pts], scale=fr_from_int(pow(vv, i, FR_MODULUS)), out=h, accumulate=i > 0)
+    return h
+
+
+def shplonk_final(polys, rotation_sets, h_x, y, v, u):
+    """SHPLONK's second quotient (shplonk/prover.rs:209-275): l_x over every polynomial and h_x, divided by (X - u) and normalised by
+    z_diffs[0]^-1.  u is drawn by the caller after h_x is committed.  Returns (n - 1, 4)."""
+    yy, vv, uu = fr_to_int(y), fr_to_int(v), fr_to_int(u)
+    sets = _shplonk_sets(rotation_sets)
+    super_set = []
+    for pts, _, _ in sets:
+        for x in pts:
+            if x not in super_set:
+                super_set.append(x)
+    p = FR_MODULUS
+    cols, scal, const, z0 = [], [], 0, None
+    for i, (pts, coms, interp) in enumerate(sets):
+        z_i = _fr_vanishing([x for x in super_set if x not in pts], uu)
+        z0 = z_i if z0 is None else z0
+        f = pow(vv, i, p) * z_i % p
+        for c, (j, _) in enumerate(coms):
+            w = f * pow(yy, c, p) % p
+            cols.append(polys[j])
+            scal.append(w)
+            const = (const + w * _fr_eval(interp[c], uu)) % p
+    cols.append(h_x)
+    scal.append(-_fr_vanishing(super_set, uu) % p)
+    return poly_combine(cols, [fr_from_int(x) for x in scal], sub=[fr_from_int(const)], roots=[u], scale=fr_from_int(pow(z0, -1, p)))
+
+
+
 
 # ------------------------------------------------------------------ poly/domain.rs
 class EvaluationDomain:
@@ -693,6 +864,38 @@ def batch_invert_device(d_a, n=None):
     """BatchInvert in place on a torch CUDA tensor of n x 32 B; queued on the current stream, not waited for"""
     n = d_a.numel() * d_a.element_size() // 32 if n is None else int(n)
     _check(lib().h2hip_batch_invert_bn254_fr_device(_dptr(d_a), ctypes.c_size_t(n), _stream()), "h2hip_batch_invert_bn254_fr_device")
+
+
+def eval_polynomials_device(d_polys, query_poly, points, lens=None):
+    """eval_polynomials over torch CUDA tensors (len_j x 32 B each; lens defaults to their sizes); waits for the result, (n_queries, 4)"""
+    lens = [t.numel() * t.element_size() // 32 for t in d_polys] if lens is None else [int(x) for x in lens]
+    ln = (ctypes.c_size_t * max(1, len(lens)))(*lens)
+    qp = np.ascontiguousarray(query_poly, dtype=np.uint32).reshape(-1)
+    pts, nq = _fes(points, "points")
+    out = np.zeros((max(1, nq), 4), dtype=np.uint64)
+    _check(lib().h2hip_eval_polynomials_bn254_device(_ptr_array(d_polys), ln, ctypes.c_size_t(len(lens)), _p(qp if nq else np.zeros(1, np.uint32)),
+                                                     _p(pts), ctypes.c_size_t(nq), _p(out), _stream()), "h2hip_eval_polynomials_bn254_device")
+    return out[:nq]
+
+
+def poly_combine_device(d_polys, scalars, d_out, sub=None, roots=(), scale=None, accumulate=False, out_len=None, length=None, remainder=False):
+    """poly_combine over torch CUDA tensors; d_out receives out_len elements (default: its size).  Queued on the current stream and not
+    waited for, unless remainder=True, which returns a(roots[0]) as (4,) uint64."""
+    L = (d_polys[0].numel() * d_polys[0].element_size() // 32 if d_polys else 0) if length is None else int(length)
+    out_len = d_out.numel() * d_out.element_size() // 32 if out_len is None else int(out_len)
+    sc, n_sc, sb, n_sub, rt, n_roots, sl = _combine_args(scalars, sub, roots, scale)
+    rem = np.zeros(4, dtype=np.uint64)
+    _check(lib().h2hip_poly_combine_bn254_fr_device(_ptr_array(d_polys), ctypes.c_size_t(L), _p(sc), ctypes.c_size_t(len(d_polys)), _p(sb),
+                                                    ctypes.c_size_t(n_sub), _p(rt), ctypes.c_size_t(n_roots), _p(sl),
+                                                    ctypes.c_uint32(1 if accumulate else 0), _dptr(d_out), ctypes.c_size_t(out_len),
+                                                    _p(rem) if remainder else None, _stream()), "h2hip_poly_combine_bn254_fr_device")
+    return rem if remainder else None
+
+
+def set_opening_tile(rows_per_thread=0, threads_per_tile=0):
+    """test hook: force the opening kernels' tile shape (0, 0 = default)"""
+    _check(lib().h2hip_debug_set_opening_tile(ctypes.c_uint32(rows_per_thread), ctypes.c_uint32(threads_per_tile)), "h2hip_debug_set_opening_tile")
+
 
 
 

@@ -955,6 +955,8 @@ static void release_ctx(Ctx* c) {
     c->gen_table.release();
     c->prod_ws.release();
     c->prod_io.release();
+    c->open_ws.release();
+    c->open_io.release();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     c->stream = nullptr;
     for (auto e : c->aux_events) (void)hipEventDestroy(e);

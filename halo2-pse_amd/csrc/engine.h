@@ -155,6 +155,7 @@ struct Ctx {
     std::recursive_mutex mu;       // serialises entry points: re-entrant callers (rayon workers) are safe
     DevBuf ntt_ws, ntt_io, msm_scalars[3], msm_bases, msm_slot[3], misc, evalh_ws, evalh_slots, ecfft_ws, ntt_ptrs, gather, gen_table;
     DevBuf prod_ws, prod_io;       // product.hip: scans' workspace; the host-pointer forms' columns
+    DevBuf open_ws, open_io;       // opening.hip: scans' workspace and tables; evaluations and the host-pointer forms' columns
     HostBuf host_ws;               // pinned host memory for the window sums coming back
     HostBuf host_planes;           // ... and for the bit-plane sums of a run whose tail the host finishes (msm.hip msm_planes_finish)
     HostBuf pin_flag;              // one word the device-key fingerprint check writes its verdict to

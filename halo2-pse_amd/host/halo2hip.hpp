@@ -120,6 +120,88 @@ inline std::vector<G1Affine> g_to_lagrange(const std::vector<G1Affine>& g, uint3
     engine_check(h2hip_g_to_lagrange_bn254(g[0].x, k, out[0].x), "h2hip_g_to_lagrange_bn254");
     return out;
 }
+
+// eval_polynomial (arithmetic.rs:304-328) on the engine (h2hip_eval_polynomials_bn254); a batch of queries is one call
+inline std::vector<Fr> eval_polynomials(const std::vector<const std::vector<Fr>*>& polys, const std::vector<uint32_t>& query_poly,
+                                        const std::vector<Fr>& points) {
+    if (query_poly.size() != points.size()) throw std::logic_error("query_poly and points differ in length");
+    std::vector<const uint64_t*> p;
+    std::vector<size_t> lens;
+    for (auto* v : polys) {
+        p.push_back(v->empty() ? nullptr : (*v)[0].l);
+        lens.push_back(v->size());
+    }
+    std::vector<Fr> evals(points.size());
+    if (!points.empty())
+        engine_check(h2hip_eval_polynomials_bn254(p.data(), lens.data(), p.size(), query_poly.data(), points[0].l, points.size(), evals[0].l),
+                     "eval_polynomials");
+    return evals;
+}
+
+inline Fr eval_polynomial(const std::vector<Fr>& poly, const Fr& point) { return eval_polynomials({&poly}, {0}, {point})[0]; }
+
+// The engine's combine / divide / scale primitive (h2hip_poly_combine_bn254_fr): (sum_j scalars[j] polys[j] - sub) / prod (X - r), times
+// scale; out_len coefficients (at least len - roots.size()), zero past the quotient
+inline std::vector<Fr> poly_combine(const std::vector<const std::vector<Fr>*>& polys, const std::vector<Fr>& scalars, const std::vector<Fr>& sub,
+                                    const std::vector<Fr>& roots, const Fr& scale, size_t out_len) {
+    if (polys.empty() || scalars.size() != polys.size()) throw std::logic_error("poly_combine: one scalar per polynomial");
+    const size_t len = polys[0]->size();
+    std::vector<const uint64_t*> p;
+    for (auto* v : polys) {
+        if (v->size() != len) throw std::logic_error("poly_combine: polynomials differ in length");
+        p.push_back(len ? (*v)[0].l : nullptr);
+    }
+    std::vector<Fr> out(out_len);
+    engine_check(h2hip_poly_combine_bn254_fr(p.data(), len, scalars[0].l, p.size(), sub.empty() ? nullptr : sub[0].l, sub.size(),
+                                             roots.empty() ? nullptr : roots[0].l, roots.size(), scale.l, 0, out.empty() ? nullptr : out[0].l,
+                                             out_len, nullptr),
+                 "poly_combine");
+    return out;
+}
+
+// kate_division (arithmetic.rs:348-366): a(X) / (X - b) without the remainder; panics (logic_error) on an empty a, as the reference does
+inline std::vector<Fr> kate_division(const std::vector<Fr>& a, const Fr& b) {
+    if (a.empty()) throw std::logic_error("kate_division of an empty polynomial");
+    return poly_combine({&a}, {Fr::one()}, {}, {b}, Fr::one(), a.size() - 1);
+}
+
+// the host-side O(points^2) helpers the multiopen provers keep: powers, evaluate_vanishing_polynomial, lagrange_interpolate (:405-460)
+inline std::vector<Fr> powers(const Fr& x, size_t m) {
+    std::vector<Fr> out;
+    Fr acc = Fr::one();
+    for (size_t i = 0; i < m; i++, acc = acc * x) out.push_back(acc);
+    return out;
+}
+
+inline Fr evaluate_vanishing_polynomial(const std::vector<Fr>& roots, const Fr& z) {
+    Fr acc = Fr::one();
+    for (auto& r : roots) acc = acc * (z - r);
+    return acc;
+}
+
+inline std::vector<Fr> lagrange_interpolate(const std::vector<Fr>& points, const std::vector<Fr>& evals) {
+    if (points.size() != evals.size()) throw std::logic_error("lagrange_interpolate: lengths differ");
+    const size_t m = points.size();
+    std::vector<Fr> out(m, Fr::zero());
+    for (size_t j = 0; j < m; j++) {
+        std::vector<Fr> basis{Fr::one()};
+        Fr denom = Fr::one();
+        for (size_t k = 0; k < m; k++) {
+            if (k == j) continue;
+            std::vector<Fr> next(basis.size() + 1, Fr::zero());
+            for (size_t i = 0; i < basis.size(); i++) {
+                next[i + 1] = next[i + 1] + basis[i];
+                next[i] = next[i] - basis[i] * points[k];
+            }
+            basis.swap(next);
+            denom = denom * (points[j] - points[k]);
+        }
+        const Fr f = evals[j] * denom.invert();
+        for (size_t i = 0; i < m; i++) out[i] = out[i] + f * basis[i];
+    }
+    return out;
+}
+
 }  // namespace arithmetic
 
 namespace poly {
@@ -451,4 +533,115 @@ inline std::vector<poly::Polynomial<poly::LagrangeCoeff>> lookup_products(
 }
 
 }  // namespace plonk
+
+// The KZG multiopen provers restated over the engine's primitive.  The caller builds the sets (construct_intermediate_sets), draws the
+// challenges from its transcript and commits; the engine takes ordered scalars only.
+namespace poly {
+namespace kzg {
+namespace multiopen {
+
+// one point of GWC with the polynomials queried there and their evaluations, in construct_intermediate_sets' order
+struct PointQueries {
+    Fr point;
+    std::vector<std::pair<const Polynomial<Coeff>*, Fr>> queries;
+};
+
+// GWC's witness polynomials (gwc/prover.rs:61-89): per point, (sum v^i p_i - sum v^i e_i) / (X - z), n - 1 coefficients each
+inline std::vector<Polynomial<Coeff>> gwc_witnesses(const std::vector<PointQueries>& sets, const Fr& v) {
+    std::vector<Polynomial<Coeff>> out;
+    for (auto& set : sets) {
+        const auto pw = arithmetic::powers(v, set.queries.size());
+        std::vector<const std::vector<Fr>*> polys;
+        Fr eval_batch = Fr::zero();
+        for (size_t i = 0; i < set.queries.size(); i++) {
+            polys.push_back(&set.queries[i].first->values);
+            eval_batch = eval_batch + pw[i] * set.queries[i].second;
+        }
+        const size_t n = polys.at(0)->size();
+        out.push_back(Polynomial<Coeff>{arithmetic::poly_combine(polys, pw, {eval_batch}, {set.point}, Fr::one(), n - 1)});
+    }
+    return out;
+}
+
+// one rotation set of SHPLONK: its points and, per polynomial, the evaluations at each point
+struct RotationSet {
+    std::vector<Fr> points;
+    std::vector<std::pair<const Polynomial<Coeff>*, std::vector<Fr>>> commitments;
+};
+
+struct ShplonkQuotients {
+    Polynomial<Coeff> h_x;    // the first quotient (shplonk/prover.rs:196-203), n coefficients
+    Polynomial<Coeff> final_poly;  // l_x / (X - u) normalised by z_diffs[0]^-1 (:261-275), n - 1 coefficients
+};
+
+// SHPLONK's two stages (shplonk/prover.rs:138-275).  squeeze_u(h_x) is called after the first quotient is formed: the caller commits h_x,
+// writes it to the transcript and returns u, so that u is drawn after h as in the reference.
+template <class SqueezeU>
+inline ShplonkQuotients shplonk(const std::vector<RotationSet>& sets, const Fr& y, const Fr& v, SqueezeU squeeze_u) {
+    if (sets.empty()) throw std::logic_error("shplonk: no rotation sets");
+    const size_t n = sets[0].commitments.at(0).first->len();
+    std::vector<std::vector<Fr>> interp;  // low_degree_equivalent of every commitment, set-major
+    std::vector<Fr> super_set;
+    for (auto& set : sets) {
+        for (auto& c : set.commitments) interp.push_back(arithmetic::lagrange_interpolate(set.points, c.second));
+        for (auto& p : set.points) {
+            bool seen = false;
+            for (auto& q : super_set) seen = seen || q == p;
+            if (!seen) super_set.push_back(p);
+        }
+    }
+    // stage 1: h_x = sum_i v^i div_by_vanishing(sum_j y^j (p_ij - R_ij), points_i), each zero-padded to n
+    std::vector<Fr> h(n, Fr::zero());
+    const auto pv = arithmetic::powers(v, sets.size());
+    size_t c0 = 0;
+    for (size_t i = 0; i < sets.size(); i++) {
+        const auto& set = sets[i];
+        const auto py = arithmetic::powers(y, set.commitments.size());
+        std::vector<const std::vector<Fr>*> polys;
+        std::vector<Fr> sub(set.points.size(), Fr::zero());
+        for (size_t j = 0; j < set.commitments.size(); j++) {
+            polys.push_back(&set.commitments[j].first->values);
+            for (size_t t = 0; t < sub.size(); t++) sub[t] = sub[t] + py[j] * interp[c0 + j][t];
+        }
+        c0 += set.commitments.size();
+        auto q = arithmetic::poly_combine(polys, py, sub, set.points, pv[i], n);
+        for (size_t t = 0; t < n; t++) h[t] = h[t] + q[t];  // the host form; a resident prover accumulates on the device
+    }
+    ShplonkQuotients out{Polynomial<Coeff>{h}, Polynomial<Coeff>{}};
+    const Fr u = squeeze_u(out.h_x);
+    // stage 2: l_x = sum_i v^i z_i sum_j y^j (p_ij - R_ij(u)) - Z_T(u) h_x, divided by (X - u), times z_diffs[0]^-1
+    std::vector<const std::vector<Fr>*> polys;
+    std::vector<Fr> scalars;
+    Fr constant = Fr::zero(), z0 = Fr::zero();
+    c0 = 0;
+    for (size_t i = 0; i < sets.size(); i++) {
+        const auto& set = sets[i];
+        std::vector<Fr> diffs;
+        for (auto& p : super_set) {
+            bool in = false;
+            for (auto& q : set.points) in = in || q == p;
+            if (!in) diffs.push_back(p);
+        }
+        const Fr z_i = arithmetic::evaluate_vanishing_polynomial(diffs, u);
+        if (i == 0) z0 = z_i;
+        const auto py = arithmetic::powers(y, set.commitments.size());
+        for (size_t j = 0; j < set.commitments.size(); j++) {
+            const Fr w = pv[i] * z_i * py[j];
+            polys.push_back(&set.commitments[j].first->values);
+            scalars.push_back(w);
+            Fr r = Fr::zero();  // R_ij(u), Horner on the host (|points| coefficients)
+            for (size_t t = interp[c0 + j].size(); t-- > 0;) r = r * u + interp[c0 + j][t];
+            constant = constant + w * r;
+        }
+        c0 += set.commitments.size();
+    }
+    polys.push_back(&out.h_x.values);
+    scalars.push_back(Fr::zero() - arithmetic::evaluate_vanishing_polynomial(super_set, u));
+    out.final_poly.values = arithmetic::poly_combine(polys, scalars, {constant}, {u}, z0.invert(), n - 1);
+    return out;
+}
+
+}  // namespace multiopen
+}  // namespace kzg
+}  // namespace poly
 }  // namespace halo2_proofs

@@ -308,3 +308,68 @@ pub fn try_lookup_products<F: Field + 'static>(k: u32, beta: &F, gamma: &F, comp
     }
     Some(z)
 }
+
+/// `eval_polynomial` (arithmetic.rs:304-328) for every query of a proof in one call: query `q` evaluates `polys[query_poly[q]]` at
+/// `points[q]`; queries of one polynomial share its reads.  `Some(evals)` when the engine took the call; `None` on any failure.
+pub fn try_eval_polynomials<F: Field + 'static>(polys: &[&[F]], query_poly: &[u32], points: &[F]) -> Option<Vec<F>> {
+    if !is::<F, Fr>() || !layout_ok() || query_poly.len() != points.len() || query_poly.iter().any(|&j| j as usize >= polys.len()) {
+        return None;
+    }
+    if polys.iter().any(|p| p.len() > 1usize << 28) {
+        return None;
+    }
+    let ptrs: Vec<*const u64> = polys.iter().map(|p| p.as_ptr() as *const u64).collect();
+    let lens: Vec<usize> = polys.iter().map(|p| p.len()).collect();
+    let mut evals = vec![F::zero(); points.len()];
+    let rc = unsafe {
+        ffi::h2hip_eval_polynomials_bn254(ptrs.as_ptr(), lens.as_ptr(), ptrs.len(), query_poly.as_ptr(), points.as_ptr() as *const u64,
+                                          points.len(), evals.as_mut_ptr() as *mut u64)
+    };
+    if rc != 0 {
+        return None;
+    }
+    Some(evals)
+}
+
+/// The opening's combine / divide / scale primitive (h2hip_poly_combine_bn254_fr): `(sum_j scalars[j] polys[j] - sub)` divided by
+/// `(X - r)` for each `r` of `roots` in order, times `scale`, zero-padded to `out_len` coefficients.  Covers GWC's witnesses
+/// (gwc/prover.rs:61-89), SHPLONK's quotients (shplonk/prover.rs:138-275) and the h_poly fold (vanishing/prover.rs:131-135).
+/// Every polynomial has the same length.  `None` on any failure.
+#[allow(clippy::too_many_arguments)]
+pub fn try_poly_combine<F: Field + 'static>(polys: &[&[F]], scalars: &[F], sub: &[F], roots: &[F], scale: &F, out_len: usize) -> Option<Vec<F>> {
+    if !is::<F, Fr>() || !layout_ok() || polys.is_empty() || scalars.len() != polys.len() {
+        return None;
+    }
+    let len = polys[0].len();
+    if polys.iter().any(|p| p.len() != len) || len > 1usize << 28 || roots.len() > 16 || len < roots.len() || sub.len() > len.min(16)
+        || out_len < len - roots.len() || out_len > 1usize << 28 {
+        return None;
+    }
+    let ptrs: Vec<*const u64> = polys.iter().map(|p| p.as_ptr() as *const u64).collect();
+    let mut out = vec![F::zero(); out_len];
+    let rc = unsafe {
+        ffi::h2hip_poly_combine_bn254_fr(ptrs.as_ptr(), len, scalars.as_ptr() as *const u64, ptrs.len(), sub.as_ptr() as *const u64, sub.len(),
+                                         roots.as_ptr() as *const u64, roots.len(), fr_ptr(scale), 0, out.as_mut_ptr() as *mut u64, out_len,
+                                         std::ptr::null_mut())
+    };
+    if rc != 0 {
+        return None;
+    }
+    Some(out)
+}
+
+/// `kate_division` (arithmetic.rs:348-366): `a(X) / (X - b)` without the remainder, `a.len() - 1` coefficients.
+pub fn try_kate_division<F: Field + 'static>(a: &[F], b: &F) -> Option<Vec<F>> {
+    if a.is_empty() {
+        return None;
+    }
+    try_poly_combine(&[a], &[F::one()], &[], std::slice::from_ref(b), &F::one(), a.len() - 1)
+}
+
+/// `div_by_vanishing` (shplonk/prover.rs:26-31): `kate_division` by each root in order, `a.len() - roots.len()` coefficients.
+pub fn try_div_by_vanishing<F: Field + 'static>(a: &[F], roots: &[F]) -> Option<Vec<F>> {
+    if a.len() < roots.len() {
+        return None;
+    }
+    try_poly_combine(&[a], &[F::one()], &[], roots, &F::one(), a.len() - roots.len())
+}

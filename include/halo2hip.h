@@ -371,6 +371,32 @@ int h2hip_lookup_products_bn254_device(uint32_t k, const uint64_t beta[4], const
 int h2hip_batch_invert_bn254_fr(uint64_t* a, size_t n);
 int h2hip_batch_invert_bn254_fr_device(void* d_a, size_t n, void* stream);
 
+/* ---- opening: the query evaluations and the KZG multiopen quotients that follow evaluate_h --------------------------------------
+ * Evaluation (eval_polynomial, arithmetic.rs:304-328): evals[q] = polys[query_poly[q]] evaluated at points[q], for n_queries queries
+ * (4 limbs each); polys[j] has lens[j] coefficients (0 evaluates to zero), query_poly[q] < n_polys.  Queries of one polynomial share
+ * its reads.  Both forms write evals (host memory) before they return.
+ * Combine (gwc/prover.rs:61-89, shplonk/prover.rs:26-31 and 138-275, vanishing/prover.rs:131-135, kate_division arithmetic.rs:348-366):
+ *   a = sum_j scalars[j] polys[j] - sub      every polys[j] has len coefficients; sub: sub_len <= min(len, 16) low coefficients
+ *   q = a, then q = kate_division(q, r) for each r of roots in order (n_roots <= 16; q has len - n_roots coefficients)
+ *   out[0 .. len - n_roots) = scale q, out[len - n_roots .. out_len) = 0;  with accumulate = 1: out[0 .. len - n_roots) += scale q only.
+ * remainder (4 limbs, host, or NULL) receives a(roots[0]) = a[0] + roots[0] q[0] of the first division (H2HIP_EINVAL without roots).
+ * Scalars, sub, roots and scale are host memory and reduced Fr elements; len, lens and out_len <= 2^28, out_len >= len - n_roots.
+ * n_polys == 0 / n_queries == 0 write nothing.  The engine draws no challenge and orders nothing: the caller passes the y / v powers,
+ * the interpolant and the points as the reference computes them.  Host forms: a polynomial pinned with h2hip_columns_pin (elems = its
+ * length) is not uploaded.  _device forms: polynomials and out are device pointers, out aliases no input (the accumulator is read when
+ * accumulate is set); kernels are queued on `stream`; the evaluation synchronises (its results go to the transcript), the combine
+ * does not unless it is asked for a remainder. */
+int h2hip_eval_polynomials_bn254(const uint64_t* const* polys, const size_t* lens, size_t n_polys, const uint32_t* query_poly, const uint64_t* points,
+                                 size_t n_queries, uint64_t* evals);
+int h2hip_eval_polynomials_bn254_device(const void* const* d_polys, const size_t* lens, size_t n_polys, const uint32_t* query_poly,
+                                        const uint64_t* points, size_t n_queries, uint64_t* evals, void* stream);
+int h2hip_poly_combine_bn254_fr(const uint64_t* const* polys, size_t len, const uint64_t* scalars, size_t n_polys, const uint64_t* sub,
+                                size_t sub_len, const uint64_t* roots, size_t n_roots, const uint64_t scale[4], uint32_t accumulate, uint64_t* out,
+                                size_t out_len, uint64_t* remainder);
+int h2hip_poly_combine_bn254_fr_device(const void* const* d_polys, size_t len, const uint64_t* scalars, size_t n_polys, const uint64_t* sub,
+                                       size_t sub_len, const uint64_t* roots, size_t n_roots, const uint64_t scale[4], uint32_t accumulate,
+                                       void* d_out, size_t out_len, uint64_t* remainder, void* stream);
+
 /* ---- synthetic workload; same streams as oracle_gen_{scalars,points} ---- */
 
 int h2hip_gen_scalars_device(uint64_t seed, uint64_t start, size_t n, void* d_out, void* stream);
