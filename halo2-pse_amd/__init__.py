@@ -367,6 +367,92 @@ def batch_invert(a):
     return out
 
 
+# ------------------------------------------------------------------ lookup compression and permutation (commit_permuted)
+H2HIP_ELOOKUP = 4
+
+
+class H2HipLookupError(H2HipError):
+    """H2HIP_ELOOKUP: a lookup's input holds a value its table lacks (the reference's Error::ConstraintSystemFailure)"""
+
+
+def _check_lookup(rc, what):
+    if rc == H2HIP_ELOOKUP:
+        raise H2HipLookupError("%s failed (rc=%d): %s" % (what, rc, lib().h2hip_last_error().decode()))
+    _check(rc, what)
+
+
+def _lookup_challenges(challenges):
+    ch = np.ascontiguousarray(np.asarray(challenges, dtype=np.uint64).reshape(-1, 4)) if len(challenges) else np.zeros((0, 4), dtype=np.uint64)
+    return (ch if ch.shape[0] else np.zeros((1, 4), dtype=np.uint64)), ch.shape[0]
+
+
+def lookup_compress(k, graphs, theta, fixed=(), advice=(), instance=(), challenges=()):
+    """commit_permuted's compressed expressions (lookup/prover.rs:90-115): graphs are flattened compression graphs
+    (evaluation.lookup_compress_graphs), columns (2^k, 4) uint64 Lagrange values.  Returns one (2^k, 4) column per graph."""
+    n = 1 << int(k)
+    fx, ad, ins = _cols(fixed, n, "fixed"), _cols(advice, n, "advice"), _cols(instance, n, "instance")
+    from .evaluation import graph_array
+    arr, keep = graph_array(graphs)
+    ch, n_ch = _lookup_challenges(challenges)
+    out = [np.zeros((n, 4), dtype=np.uint64) for _ in graphs]
+    _check(lib().h2hip_lookup_compress_bn254(ctypes.c_uint32(k), _host_ptrs(fx), ctypes.c_uint32(len(fx)), _host_ptrs(ad), ctypes.c_uint32(len(ad)),
+                                             _host_ptrs(ins), ctypes.c_uint32(len(ins)), _p(ch), ctypes.c_uint32(n_ch), _p(_fe(theta)), arr,
+                                             ctypes.c_size_t(len(graphs)), _host_ptrs(out)), "h2hip_lookup_compress_bn254")
+    del keep
+    return out
+
+
+def _lookup_blinding(blinding, count, b):
+    bl = np.ascontiguousarray(_u64(blinding).reshape(-1, 4)) if blinding is not None else np.zeros((0, 4), dtype=np.uint64)
+    if bl.shape[0] != count * 2 * (b + 1):
+        raise ValueError("blinding: expected %d values (%d lookups x 2(b + 1)), got %d" % (count * 2 * (b + 1), count, bl.shape[0]))
+    return bl if bl.shape[0] else np.zeros((1, 4), dtype=np.uint64)
+
+
+def lookup_permute(k, compressed_inputs, compressed_tables, blinding, blinding_factors):
+    """permute_expression_pair (lookup/prover.rs:391-475) for every lookup: lists of (2^k, 4) uint64 compressed columns; blinding is
+    (count * 2(b + 1), 4): per lookup the A' rows u .. n - 1, then the S' rows.  Returns (permuted_inputs, permuted_tables).
+    Raises H2HipLookupError when an input value is missing from its table."""
+    n = 1 << int(k)
+    a, t = _cols(compressed_inputs, n, "compressed_inputs"), _cols(compressed_tables, n, "compressed_tables")
+    if len(a) != len(t):
+        raise ValueError("compressed inputs and tables differ in count")
+    bl = _lookup_blinding(blinding, len(a), int(blinding_factors))
+    pa = [np.zeros((n, 4), dtype=np.uint64) for _ in a]
+    pt = [np.zeros((n, 4), dtype=np.uint64) for _ in a]
+    _check_lookup(lib().h2hip_lookup_permute_bn254(ctypes.c_uint32(k), _host_ptrs(a), _host_ptrs(t), ctypes.c_size_t(len(a)), _p(bl),
+                                                   ctypes.c_uint32(blinding_factors), _host_ptrs(pa), _host_ptrs(pt)), "h2hip_lookup_permute_bn254")
+    return pa, pt
+
+
+def commit_permuted(params, domain, lookups, theta, blinding, blinding_factors, blinds, fixed=(), advice=(), instance=(), challenges=()):
+    """lookup::Argument::commit_permuted (lookup/prover.rs:64-170) for every lookup of one instance, in the reference's order:
+    compress the input and table expressions (:90-115), permute them (:118-126), commit A' then S' in Lagrange form with the caller's
+    blinds (:129-135; two per lookup, blinds[2j], blinds[2j + 1]), and take both to coefficient form (:137-143), batched.  lookups:
+    [(input_exprs, table_exprs)] expression tuples (evaluation.py); blinding as for lookup_permute.  Returns one dict per lookup:
+    permuted_input / permuted_table (Lagrange), permuted_input_poly / permuted_table_poly (coefficients), and the two commitments
+    (Jacobian (12,) uint64; ParamsKZG's commit ignores the blind, as the reference's KZG commit_lagrange does)."""
+    from .evaluation import flatten_graph, lookup_compress_graphs
+    k = int(domain.k)
+    graphs = []
+    for inp, tab in lookups:
+        gi, gt = lookup_compress_graphs(inp, tab)
+        graphs += [flatten_graph(gi), flatten_graph(gt)]
+    comp = lookup_compress(k, graphs, theta, fixed, advice, instance, challenges)
+    pa, pt = lookup_permute(k, comp[0::2], comp[1::2], blinding, blinding_factors)
+    if len(blinds) != 2 * len(lookups):
+        raise ValueError("blinds: expected two per lookup")
+    out = []
+    for j in range(len(lookups)):
+        out.append({"compressed_input": comp[2 * j], "compressed_table": comp[2 * j + 1], "permuted_input": pa[j], "permuted_table": pt[j],
+                    "permuted_input_commitment": params.commit_lagrange(pa[j], blinds[2 * j]),
+                    "permuted_table_commitment": params.commit_lagrange(pt[j], blinds[2 * j + 1])})
+    polys = domain.lagrange_to_coeff_batch([c for j in range(len(lookups)) for c in (pa[j], pt[j])])
+    for j, d in enumerate(out):
+        d["permuted_input_poly"], d["permuted_table_poly"] = polys[2 * j], polys[2 * j + 1]
+    return out
+
+
 # ------------------------------------------------------------------ opening: query evaluations and the KZG multiopen quotients
 def _fes(values, what):
     """a list of field elements ((4,) uint64 Montgomery limbs each) or an (m, 4) array -> a contiguous (max(1, m), 4) array, and m"""
@@ -897,6 +983,40 @@ def set_opening_tile(rows_per_thread=0, threads_per_tile=0):
     _check(lib().h2hip_debug_set_opening_tile(ctypes.c_uint32(rows_per_thread), ctypes.c_uint32(threads_per_tile)), "h2hip_debug_set_opening_tile")
 
 
+
+
+def lookup_compress_device(k, graphs, theta, d_out, d_fixed=(), d_advice=(), d_instance=(), challenges=()):
+    """lookup_compress over torch CUDA tensors (2^k x 32 B each); d_out[g] receives graph g.  Queued on the current stream, not waited for"""
+    from .evaluation import graph_array
+    arr, keep = graph_array(graphs)
+    ch, n_ch = _lookup_challenges(challenges)
+    _check(lib().h2hip_lookup_compress_bn254_device(ctypes.c_uint32(k), _ptr_array(d_fixed), ctypes.c_uint32(len(d_fixed)), _ptr_array(d_advice),
+                                                    ctypes.c_uint32(len(d_advice)), _ptr_array(d_instance), ctypes.c_uint32(len(d_instance)), _p(ch),
+                                                    ctypes.c_uint32(n_ch), _p(_fe(theta)), arr, ctypes.c_size_t(len(graphs)), _ptr_array(d_out),
+                                                    _stream()), "h2hip_lookup_compress_bn254_device")
+    del keep
+
+
+def lookup_permute_device(k, d_compressed_inputs, d_compressed_tables, blinding, blinding_factors, d_permuted_inputs, d_permuted_tables):
+    """lookup_permute over torch CUDA tensors; queued on the current stream, which the call then waits for once (the not-found flags).
+    Raises H2HipLookupError when an input value is missing from its table."""
+    bl = _lookup_blinding(blinding, len(d_compressed_inputs), int(blinding_factors))
+    _check_lookup(lib().h2hip_lookup_permute_bn254_device(ctypes.c_uint32(k), _ptr_array(d_compressed_inputs), _ptr_array(d_compressed_tables),
+                                                          ctypes.c_size_t(len(d_compressed_inputs)), _p(bl), ctypes.c_uint32(blinding_factors),
+                                                          _ptr_array(d_permuted_inputs), _ptr_array(d_permuted_tables), _stream()),
+                  "h2hip_lookup_permute_bn254_device")
+
+
+def set_lookup_sort(lds_keys=0):
+    """test hook: force the lookup sort's in-LDS block (a power of two in [4, 1024]; 0 = default)"""
+    _check(lib().h2hip_debug_set_lookup_sort(ctypes.c_uint32(lds_keys)), "h2hip_debug_set_lookup_sort")
+
+
+def lookup_sort_stats():
+    """(block, merge passes) of the last lookup permute call"""
+    out = (ctypes.c_uint32 * 2)()
+    _check(lib().h2hip_debug_lookup_sort_stats(out), "h2hip_debug_lookup_sort_stats")
+    return int(out[0]), int(out[1])
 
 
 def gen_scalars_device(seed, n, start=0, device="cuda"):

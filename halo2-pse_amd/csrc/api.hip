@@ -957,6 +957,9 @@ static void release_ctx(Ctx* c) {
     c->prod_io.release();
     c->open_ws.release();
     c->open_io.release();
+    c->lookup_ws.release();
+    c->lookup_io.release();
+    c->lookup_flag.release();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     c->stream = nullptr;
     for (auto e : c->aux_events) (void)hipEventDestroy(e);

@@ -156,6 +156,8 @@ struct Ctx {
     DevBuf ntt_ws, ntt_io, msm_scalars[3], msm_bases, msm_slot[3], misc, evalh_ws, evalh_slots, ecfft_ws, ntt_ptrs, gather, gen_table;
     DevBuf prod_ws, prod_io;       // product.hip: scans' workspace; the host-pointer forms' columns
     DevBuf open_ws, open_io;       // opening.hip: scans' workspace and tables; evaluations and the host-pointer forms' columns
+    DevBuf lookup_ws, lookup_io;   // lookup.hip: sort keys, marks and scans; the host-pointer forms' columns
+    HostBuf lookup_flag;           // lookup.hip: the per-lookup not-found flags read back at the end of a permute call
     HostBuf host_ws;               // pinned host memory for the window sums coming back
     HostBuf host_planes;           // ... and for the bit-plane sums of a run whose tail the host finishes (msm.hip msm_planes_finish)
     HostBuf pin_flag;              // one word the device-key fingerprint check writes its verdict to
@@ -285,6 +287,10 @@ int permutation_products_device(Ctx* c, uint32_t k, const Fe& omega, const Fe& d
 int lookup_products_device(Ctx* c, uint32_t k, const Fe& beta, const Fe& gamma, const Fe* const* inputs_tables,
                            const Fe* const* permuted, size_t count, const uint64_t* blinding, uint32_t bf, Fe* const* z, hipStream_t s);
 int batch_invert_device(Ctx* c, Fe* d_a, uint64_t n, hipStream_t s);
+// lookup.hip: commit_permuted's A' / S' of `count` lookups from device columns; waits for s once, H2HIP_ELOOKUP when an input value is
+// missing from its table
+int lookup_permute_device(Ctx* c, uint32_t k, const Fe* const* in, const Fe* const* tab, size_t count, const uint64_t* blinding, uint32_t bf,
+                          Fe* const* pa, Fe* const* pt, hipStream_t s);
 // setup.hip
 int kzg_setup_device(Ctx* c, uint32_t k, const Fe& s, Affine* d_g, Affine* d_gl, hipStream_t stream);
 
@@ -303,6 +309,12 @@ void evalh_modules_free(Ctx* c);                            // unload this devic
 void evalh_rtc_shutdown();                                  // join the compile threads (h2hip_shutdown)
 int evaluate_h_validate(const h2hip_evalh_desc* d, const void* values);
 int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, uint64_t* values, bool dev, hipStream_t s);
+// lookup compression (commit_permuted's compressed expressions) on the interpreter: validation needs no device; the run is enqueued on s
+int lookup_compress_validate(uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance, uint32_t n_challenges, const h2hip_graph* graphs,
+                             size_t n_graphs);
+int lookup_compress_device(Ctx* c, uint32_t k, const Fe* const* fixed, uint32_t n_fixed, const Fe* const* advice, uint32_t n_advice,
+                           const Fe* const* instance, uint32_t n_instance, const uint64_t* challenges, uint32_t n_challenges,
+                           const uint64_t theta[4], const h2hip_graph* graphs, size_t n_graphs, Fe* const* out, hipStream_t s);
 
 // msm.hip
 void msm_set_fuse_small(bool on);

@@ -1398,4 +1398,130 @@ int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, uint64_t* values, bool de
     return 0;
 }
 
+
+// ---- lookup compression (plonk/lookup/prover.rs:90-115): the compressed input / table expressions of commit_permuted over the n
+// Lagrange rows.  Each graph is Horner(Constant(0), parts, Theta) over the lookup's expressions (evaluation.py lookup_compress_graphs),
+// run by the interpreter above with rot_scale = 1 over the 2^k rows; one launch serves every graph of a call.
+template <int MAXI>
+__global__ void __launch_bounds__(256) lookup_compress_kernel(const ProgDev* progs, ColsDev c, Fe* const* outs, Fu* gws, uint32_t lanes) {
+    const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= lanes) return;
+    const ProgDev g = progs[blockIdx.y];
+    Fe* out = outs[blockIdx.y];
+    Slots<MAXI> slots(gws + tid, lanes);
+    for (uint64_t row = tid; row < (1ull << c.log_size); row += lanes) {
+        const uint32_t idx = (uint32_t)row;
+        const Fu r = prog_eval(g, c, idx, fu_zero(), slots);
+        out[idx] = prog_result_e<Slots<MAXI>>(g, c, idx, fe_zero<FrP>(), r);
+    }
+}
+
+static bool compress_vs_allowed(const h2hip_value_source& v) {
+    return v.kind != H2HIP_VS_BETA && v.kind != H2HIP_VS_GAMMA && v.kind != H2HIP_VS_Y && v.kind != H2HIP_VS_PREVIOUS;
+}
+
+int lookup_compress_validate(uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance, uint32_t n_challenges, const h2hip_graph* graphs,
+                             size_t n_graphs) {
+    if (n_graphs && !graphs) {
+        set_error("lookup_compress: null graphs");
+        return H2HIP_EINVAL;
+    }
+    if (n_graphs > 65535) {
+        set_error("lookup_compress: %zu graphs > 65535", n_graphs);
+        return H2HIP_EINVAL;
+    }
+    h2hip_evalh_desc d;
+    memset(&d, 0, sizeof(d));
+    d.n_fixed = n_fixed;
+    d.n_advice = n_advice;
+    d.n_instance = n_instance;
+    d.n_challenges = n_challenges;
+    for (size_t i = 0; i < n_graphs; i++) {
+        const h2hip_graph& g = graphs[i];
+        if (graph_validate(g, d, "lookup compression")) return H2HIP_EINVAL;
+        for (uint32_t q = 0; q < g.n_calculations; q++) {
+            const h2hip_calculation& cl = g.calculations[q];
+            bool ok = compress_vs_allowed(cl.x);
+            if (cl.op == H2HIP_CALC_ADD || cl.op == H2HIP_CALC_SUB || cl.op == H2HIP_CALC_MUL || cl.op == H2HIP_CALC_HORNER) ok = ok && compress_vs_allowed(cl.y);
+            if (cl.op == H2HIP_CALC_HORNER)
+                for (uint32_t t = 0; ok && t < cl.parts_count; t++) ok = compress_vs_allowed(g.parts[cl.parts_offset + t]);
+            if (!ok) {
+                set_error("lookup_compress: graph %zu, calculation %u reads beta, gamma, y or the previous value", i, q);
+                return H2HIP_EINVAL;
+            }
+        }
+    }
+    return 0;
+}
+
+// Validated arguments (lookup_compress_validate); columns and outputs are device pointers, the rest host memory.  Enqueued on s.
+int lookup_compress_device(Ctx* c, uint32_t k, const Fe* const* fixed, uint32_t n_fixed, const Fe* const* advice, uint32_t n_advice,
+                           const Fe* const* instance, uint32_t n_instance, const uint64_t* challenges, uint32_t n_challenges,
+                           const uint64_t theta[4], const h2hip_graph* graphs, size_t n_graphs, Fe* const* out, hipStream_t s) {
+    if (n_graphs == 0) return 0;
+    const size_t n = (size_t)1 << k;
+    std::vector<Program> progs(n_graphs);
+    uint32_t max_slots = 0;
+    size_t meta_cap = 4096 + ((size_t)n_challenges + n_fixed + n_advice + n_instance) * sizeof(Fu) + n_graphs * (sizeof(ProgDev) + sizeof(Fe*) + 512);
+    for (size_t i = 0; i < n_graphs; i++) {
+        progs[i] = compile_graph(graphs[i]);
+        if (progs[i].n_slots > max_slots) max_slots = progs[i].n_slots;
+        meta_cap += prog_bytes(graphs[i], progs[i]);
+    }
+    meta_cap = (meta_cap + 255) / 256 * 256;
+    SlotPlan plan;
+    int rc = slot_plan(max_slots, n, &plan);
+    if (rc) return rc;
+    if ((rc = c->ws_acquire(s))) return rc;
+    WsGuard guard(c, s);
+    if ((rc = c->evalh_ws.ensure(meta_cap))) return rc;
+    if (plan.ws_bytes && (rc = c->evalh_slots.ensure(plan.ws_bytes))) return rc;
+    MetaBlob mb;
+    mb.dev_base = (char*)c->evalh_ws.p;
+    mb.cap = meta_cap;
+    ColsDev cols;
+    memset(&cols, 0, sizeof(cols));
+    cols.fixed = mb.put(fixed, n_fixed);
+    cols.advice = mb.put(advice, n_advice);
+    cols.instance = mb.put(instance, n_instance);
+    {
+        std::vector<Fu> hch(n_challenges);
+        for (uint32_t i = 0; i < n_challenges; i++) hch[i] = to_i(load_fe(challenges + 4 * (size_t)i));
+        cols.challenges = mb.put(hch.data(), hch.size());
+    }
+    cols.theta = to_i(load_fe(theta));
+    cols.log_size = k;
+    cols.rot_scale = 1;
+    std::vector<ProgDev> pd(n_graphs);
+    for (size_t i = 0; i < n_graphs; i++) prog_put(mb, graphs[i], progs[i], &pd[i]);
+    const ProgDev* d_progs = mb.put(pd.data(), pd.size());
+    Fe* const* d_outs = mb.put(out, n_graphs);
+    if (mb.overflow) {
+        set_error("lookup_compress: metadata region overflow");
+        return 1;
+    }
+    if ((rc = c->stage_h2d(mb.dev_base, mb.host.data(), mb.host.size(), s))) return rc;
+    Fu* const gws = (Fu*)c->evalh_slots.p;
+    const dim3 block(256);
+    int tm = c->timer_begin("lookup_compress", s);
+    // the global-workspace form (a graph with more than 256 live values) shares one workspace: one graph per launch
+    const uint32_t per_launch = plan.tier == 0 ? 1u : (uint32_t)n_graphs;
+    for (size_t g0 = 0; g0 < n_graphs; g0 += per_launch) {
+        const dim3 grid(plan.lanes / 256, per_launch);
+        const ProgDev* p = d_progs + g0;
+        Fe* const* o = d_outs + g0;
+        switch (plan.tier) {
+            case 4: hipLaunchKernelGGL(lookup_compress_kernel<4>, grid, block, 4 * 9 * 256 * 4, s, p, cols, o, gws, plan.lanes); break;
+            case 8: hipLaunchKernelGGL(lookup_compress_kernel<8>, grid, block, 8 * 9 * 256 * 4, s, p, cols, o, gws, plan.lanes); break;
+            case 16: hipLaunchKernelGGL(lookup_compress_kernel<16>, grid, block, EVALH_LDS_HOT * 9 * 256 * 4, s, p, cols, o, gws, plan.lanes); break;
+            case 64: hipLaunchKernelGGL(lookup_compress_kernel<64>, grid, block, EVALH_LDS_HOT * 9 * 256 * 4, s, p, cols, o, gws, plan.lanes); break;
+            case 256: hipLaunchKernelGGL(lookup_compress_kernel<256>, grid, block, EVALH_LDS_HOT * 9 * 256 * 4, s, p, cols, o, gws, plan.lanes); break;
+            default: hipLaunchKernelGGL(lookup_compress_kernel<0>, grid, block, 0, s, p, cols, o, gws, plan.lanes);
+        }
+        H2_CHECK(hipGetLastError());
+    }
+    c->timer_end(tm, s);
+    return guard.release();
+}
+
 }  // namespace h2

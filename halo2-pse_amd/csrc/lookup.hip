@@ -1,0 +1,607 @@
+// lookup.hip -- lookup::Argument::commit_permuted (plonk/lookup/prover.rs:64-170) on the GPU: the permuted input A' and the permuted
+// table S' of every lookup, from the compressed input and table columns (the compression itself runs on evaluate_h's interpreter,
+// evalh.hip lookup_compress_device).
+//
+// The reference (permute_expression_pair, :391-475), with n = 2^k, b = blinding_factors and u = n - b - 1:
+//   A'[0 .. u) = C_in[0 .. u) sorted by Fr's Ord -- the order of the canonical integers (halo2curves' to_repr compared from the top);
+//   S'[i] = A'[i] on every first row (i = 0 or A'[i] != A'[i-1]), each taking one copy of its value out of the table multiset
+//   T = C_tab[0 .. u); the leftovers L (ascending) go to the repeated rows R (ascending) as S'[R[j]] = L[|L| - 1 - j]
+//   (repeated_input_rows.pop() while the BTreeMap is walked upwards); rows u .. n - 1 of both are the caller's blinding values.
+//   An input value missing from T is Error::ConstraintSystemFailure, here H2HIP_ELOOKUP.
+//
+// Plan (Lookup permutation).  Keys are the canonical 256-bit values (one Montgomery reduction per element on the way
+// in, one multiplication by R^2 on the way out).  Every input and table column of a call is sorted by the same launches:
+//   1. lk_block_sort_kernel  (tiles x columns): blocks of up to LK_TILE keys sorted in LDS by a bitonic network over full 256-bit
+//                            compares; rows u .. n - 1 enter as all-ones keys, above every canonical value, and stay at the end;
+//   2. lk_merge_kernel       (tiles x columns, log2(n / block) launches): merge path -- every workgroup finds the split of its
+//                            output range in the two runs by a binary search, stages both slices in LDS and merges them there.
+// A comparison sort is exact for every key distribution (one repeated value, 16-bit keys, keys sharing their high or low bits)
+// with a launch count fixed by n alone, so no pass waits on a count the host has to read back.  Then per lookup:
+//   3. lk_mark_kernel        first rows; each one's value found in the sorted table (galloping search from the thread's previous
+//                            hit), that slot marked used, or the lookup's not-found flag raised;
+//   4. lk_count_kernel       per tile: unused table slots (L) and repeated rows (R);
+//   5. lk_scan_kernel        one workgroup per lookup: exclusive scans of the tile counts (reduce-then-scan, no workgroup waits
+//                            on another);
+//   6. lk_compact_kernel     L compacted in ascending order;
+//   7. lk_final_kernel       A', S'[first] = A'[first], S'[R[j]] = L[|L| - 1 - j], the blinding rows, back to Montgomery form.
+// The host reads the not-found flags once, after the last kernel.  No kernel uses scratch (profiles/lookup_resources.txt).
+#include <string.h>
+#include <vector>
+#include "engine.h"
+#include "field.h"
+
+namespace h2 {
+
+#define LK_THREADS 256
+#define LK_TILE 1024                  // keys one workgroup sorts, merges or permutes (32 KB of LDS)
+#define LK_E (LK_TILE / LK_THREADS)   // consecutive keys / rows per thread
+#define LK_MAX_COUNT 32767            // lookups per call: 2 count sorted columns in grid.y
+
+static uint32_t g_lk_block = 0;            // h2hip_debug_set_lookup_sort: forced in-LDS sort block (0 = LK_TILE)
+static uint32_t g_lk_last[2] = {0, 0};     // block keys and merge passes of the last permute call
+
+__device__ __forceinline__ Fe lk_ld(const Fe* p, uint64_t i) {
+    const uint4* q = (const uint4*)(p + i);
+    uint4 a = q[0], b = q[1];
+    Fe o;
+    o.l[0] = a.x, o.l[1] = a.y, o.l[2] = a.z, o.l[3] = a.w, o.l[4] = b.x, o.l[5] = b.y, o.l[6] = b.z, o.l[7] = b.w;
+    return o;
+}
+__device__ __forceinline__ void lk_st(Fe* p, uint64_t i, const Fe& v) {
+    uint4* q = (uint4*)(p + i);
+    q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
+    q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
+}
+// a < b as 256-bit integers (limb 7 most significant): Fr's Ord on canonical values
+__device__ __forceinline__ bool key_lt(const Fe& a, const Fe& b) {
+#pragma unroll
+    for (int i = 7; i >= 0; i--)
+        if (a.l[i] != b.l[i]) return a.l[i] < b.l[i];
+    return false;
+}
+// merge path: how many of the first d outputs of merge(A[0 .. na), B[0 .. nb)) come from A (on ties A first)
+__device__ __forceinline__ uint32_t lk_split(const Fe* A, uint32_t na, const Fe* B, uint32_t nb, uint32_t d) {
+    uint32_t lo = d > nb ? d - nb : 0, hi = d < na ? d : na;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (!key_lt(lk_ld(B, d - 1 - mid), lk_ld(A, mid))) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// ---- 1. canonical keys, blocks of `block` keys sorted in LDS --------------------------------------------------------------------
+// ts = min(LK_TILE, n) keys per workgroup; block <= ts, both powers of two
+__global__ __launch_bounds__(LK_THREADS) void lk_block_sort_kernel(const Fe* const* src, Fe* const* dst, uint64_t u, uint32_t ts, uint32_t block) {
+    __shared__ Fe sk[LK_TILE];
+    const Fe* in = src[blockIdx.y];
+    Fe* out = dst[blockIdx.y];
+    const uint64_t base = (uint64_t)blockIdx.x * ts;
+    for (uint32_t i = threadIdx.x; i < ts; i += LK_THREADS) {
+        const uint64_t r = base + i;
+        Fe v;
+        if (r < u) {
+            v = fe_to_canonical<FrP>(lk_ld(in, r));
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; j++) v.l[j] = 0xffffffffu;
+        }
+        sk[i] = v;
+    }
+    __syncthreads();
+    for (uint32_t kk = 2; kk <= block; kk <<= 1)
+        for (uint32_t j = kk >> 1; j > 0; j >>= 1) {
+            for (uint32_t t = threadIdx.x; t < ts / 2; t += LK_THREADS) {
+                const uint32_t i = 2 * t - (t & (j - 1)), l = i + j;  // the pair (i, i + j), bit j of i clear
+                const bool asc = kk == block || (i & kk) == 0;         // the last stage sorts every block ascending
+                const Fe a = sk[i], b = sk[l];
+                if (key_lt(b, a) == asc) {
+                    sk[i] = b;
+                    sk[l] = a;
+                }
+            }
+            __syncthreads();
+        }
+    for (uint32_t i = threadIdx.x; i < ts; i += LK_THREADS) lk_st(out, base + i, sk[i]);
+}
+
+// ---- 2. one merge pass: sorted runs of w keys -> runs of 2w ---------------------------------------------------------------------
+__global__ __launch_bounds__(LK_THREADS) void lk_merge_kernel(const Fe* const* src, Fe* const* dst, uint32_t w, uint32_t ts) {
+    __shared__ Fe sk[LK_TILE];
+    __shared__ uint32_t s_a[2];
+    const Fe* in = src[blockIdx.y];
+    Fe* out = dst[blockIdx.y];
+    const uint64_t o0 = (uint64_t)blockIdx.x * ts;
+    const uint32_t tid = threadIdx.x, t = tid * LK_E;
+    const Fe *A, *B;
+    uint32_t na, nb, d;
+    if (2ull * w >= ts) {  // the tile lies in one pair of runs: its slices of both, found by merge path on global memory
+        const uint64_t pbase = o0 / (2ull * w) * (2ull * w);
+        const Fe* gA = in + pbase;
+        const Fe* gB = gA + w;
+        const uint32_t d0 = (uint32_t)(o0 - pbase);
+        if (tid < 2) s_a[tid] = lk_split(gA, w, gB, w, d0 + tid * ts);
+        __syncthreads();
+        const uint32_t a0 = s_a[0], a1 = s_a[1], b0 = d0 - a0;
+        na = a1 - a0;
+        nb = ts - na;
+        for (uint32_t i = tid; i < ts; i += LK_THREADS) sk[i] = i < na ? lk_ld(gA, a0 + i) : lk_ld(gB, b0 + (i - na));
+        __syncthreads();
+        A = sk;
+        B = sk + na;
+        d = t;
+    } else {  // whole pairs of runs inside the tile
+        for (uint32_t i = tid; i < ts; i += LK_THREADS) sk[i] = lk_ld(in, o0 + i);
+        __syncthreads();
+        const uint32_t pb = t / (2 * w) * (2 * w);
+        A = sk + pb;
+        B = A + w;
+        na = nb = w;
+        d = t - pb;
+    }
+    if (t >= ts) return;
+    uint32_t ia = lk_split(A, na, B, nb, d), ib = d - ia;
+#pragma unroll
+    for (int e = 0; e < LK_E; e++) {  // LK_E <= 2w: a thread's outputs lie in one pair
+        const bool take_a = ib >= nb || (ia < na && !key_lt(B[ib], A[ia]));
+        const Fe x = take_a ? A[ia] : B[ib];
+        if (take_a) ia++;
+        else ib++;
+        lk_st(out, o0 + t + e, x);
+    }
+}
+
+// ---- 3.-7. the permutation ------------------------------------------------------------------------------------------------------
+struct LkPerm {           // one lookup
+    const Fe* a;          // sorted canonical input keys (A'), all-ones from row u on
+    const Fe* t;          // sorted canonical table keys
+    uint32_t* used;       // table slots taken by a first row
+    Fe* lc;               // the leftovers L, compacted
+    uint32_t* cnt_l;      // per-tile counts of L, then their exclusive scan; [tiles] = |L|
+    uint32_t* cnt_r;      // the same for the repeated rows R
+    uint32_t* flag;       // an input value is not in the table
+    Fe* pa;               // outputs, Montgomery form
+    Fe* pt;
+    const Fe* blind;      // 2 (b + 1) values: A' rows u .. n - 1, then S' rows u .. n - 1
+};
+
+__device__ __forceinline__ bool lk_repeated(const Fe* a, uint64_t i) { return i > 0 && fe_eq(lk_ld(a, i), lk_ld(a, i - 1)); }
+
+// exclusive sum over the workgroup's threads in order; *total = sum of all
+__device__ __forceinline__ uint32_t lk_scan_excl(uint32_t v, uint32_t* lds, uint32_t* total) {
+    const uint32_t tid = threadIdx.x;
+    lds[tid] = v;
+    __syncthreads();
+    for (uint32_t off = 1; off < LK_THREADS; off <<= 1) {
+        const uint32_t x = tid >= off ? lds[tid - off] : 0u;
+        __syncthreads();
+        lds[tid] += x;
+        __syncthreads();
+    }
+    const uint32_t inc = lds[tid];
+    *total = lds[LK_THREADS - 1];
+    __syncthreads();
+    return inc - v;
+}
+
+__global__ __launch_bounds__(LK_THREADS) void lk_mark_kernel(const LkPerm* P, uint64_t u) {
+    const LkPerm D = P[blockIdx.y];
+    const uint64_t r0 = ((uint64_t)blockIdx.x * LK_THREADS + threadIdx.x) * LK_E;
+    uint64_t pos = 0;
+    bool have = false;
+    for (int e = 0; e < LK_E; e++) {
+        const uint64_t i = r0 + e;
+        if (i >= u) break;
+        if (lk_repeated(D.a, i)) continue;
+        const Fe v = lk_ld(D.a, i);
+        // lower bound of v in T[0 .. u): every T[< lo] < v; galloping from the previous hit, whose value is smaller
+        uint64_t lo = have ? pos : 0, hi = u;
+        if (have) {
+            uint64_t step = 1;
+            hi = lo;
+            while (hi < u && key_lt(lk_ld(D.t, hi), v)) {
+                lo = hi + 1;
+                hi = lo + step;
+                step <<= 1;
+            }
+            if (hi > u) hi = u;
+        }
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi) >> 1;
+            if (key_lt(lk_ld(D.t, mid), v)) lo = mid + 1;
+            else hi = mid;
+        }
+        pos = lo;
+        have = true;
+        if (pos >= u || !fe_eq(lk_ld(D.t, pos), v)) atomicOr(D.flag, 1u);
+        else D.used[pos] = 1u;  // distinct first values land on distinct slots
+    }
+}
+
+__device__ __forceinline__ void lk_local_counts(const LkPerm& D, uint64_t r0, uint64_t u, uint32_t* nl, uint32_t* nr) {
+    uint32_t l = 0, r = 0;
+    for (int e = 0; e < LK_E; e++) {
+        const uint64_t i = r0 + e;
+        if (i >= u) break;
+        l += D.used[i] == 0u;
+        r += lk_repeated(D.a, i);
+    }
+    *nl = l;
+    *nr = r;
+}
+
+__global__ __launch_bounds__(LK_THREADS) void lk_count_kernel(const LkPerm* P, uint64_t u) {
+    __shared__ uint32_t lds[LK_THREADS];
+    const LkPerm D = P[blockIdx.y];
+    const uint64_t r0 = ((uint64_t)blockIdx.x * LK_THREADS + threadIdx.x) * LK_E;
+    uint32_t nl, nr, tl, tr;
+    lk_local_counts(D, r0, u, &nl, &nr);
+    (void)lk_scan_excl(nl, lds, &tl);
+    (void)lk_scan_excl(nr, lds, &tr);
+    if (threadIdx.x == 0) {
+        D.cnt_l[blockIdx.x] = tl;
+        D.cnt_r[blockIdx.x] = tr;
+    }
+}
+
+__global__ __launch_bounds__(LK_THREADS) void lk_scan_kernel(const LkPerm* P, uint32_t tiles) {
+    __shared__ uint32_t lds[LK_THREADS];
+    const LkPerm D = P[blockIdx.x];
+    uint32_t carry_l = 0, carry_r = 0;
+    for (uint32_t base = 0; base < tiles; base += LK_THREADS) {
+        const uint32_t j = base + threadIdx.x;
+        uint32_t tl, tr;
+        const uint32_t el = lk_scan_excl(j < tiles ? D.cnt_l[j] : 0u, lds, &tl);
+        const uint32_t er = lk_scan_excl(j < tiles ? D.cnt_r[j] : 0u, lds, &tr);
+        if (j < tiles) {
+            D.cnt_l[j] = carry_l + el;
+            D.cnt_r[j] = carry_r + er;
+        }
+        carry_l += tl;
+        carry_r += tr;
+    }
+    if (threadIdx.x == 0) {
+        D.cnt_l[tiles] = carry_l;
+        D.cnt_r[tiles] = carry_r;
+    }
+}
+
+__global__ __launch_bounds__(LK_THREADS) void lk_compact_kernel(const LkPerm* P, uint64_t u) {
+    __shared__ uint32_t lds[LK_THREADS];
+    const LkPerm D = P[blockIdx.y];
+    const uint64_t r0 = ((uint64_t)blockIdx.x * LK_THREADS + threadIdx.x) * LK_E;
+    uint32_t nl = 0, tot;
+    for (int e = 0; e < LK_E; e++)
+        if (r0 + e < u) nl += D.used[r0 + e] == 0u;
+    uint32_t at = D.cnt_l[blockIdx.x] + lk_scan_excl(nl, lds, &tot);
+    for (int e = 0; e < LK_E; e++) {
+        const uint64_t i = r0 + e;
+        if (i >= u) break;
+        if (D.used[i] == 0u) lk_st(D.lc, at++, lk_ld(D.t, i));
+    }
+}
+
+__global__ __launch_bounds__(LK_THREADS) void lk_final_kernel(const LkPerm* P, uint64_t u, uint64_t n, uint32_t tiles) {
+    __shared__ uint32_t lds[LK_THREADS];
+    const LkPerm D = P[blockIdx.y];
+    const uint64_t r0 = ((uint64_t)blockIdx.x * LK_THREADS + threadIdx.x) * LK_E;
+    uint32_t nr = 0, tot;
+    for (int e = 0; e < LK_E; e++)
+        if (r0 + e < u) nr += lk_repeated(D.a, r0 + e);
+    uint32_t rank = D.cnt_r[blockIdx.x] + lk_scan_excl(nr, lds, &tot);  // repeated rows before this thread's first row
+    const uint32_t n_l = D.cnt_l[tiles];                                // |L| (>= |R|; equal unless a value was missing)
+    for (int e = 0; e < LK_E; e++) {
+        const uint64_t i = r0 + e;
+        if (i >= n) break;
+        if (i >= u) {
+            lk_st(D.pa, i, D.blind[i - u]);
+            lk_st(D.pt, i, D.blind[(n - u) + (i - u)]);
+            continue;
+        }
+        const Fe v = lk_ld(D.a, i);
+        Fe s = v;
+        if (lk_repeated(D.a, i)) {
+            if (rank < n_l) s = lk_ld(D.lc, n_l - 1 - rank);
+            rank++;
+        }
+        lk_st(D.pa, i, fe_from_canonical<FrP>(v));
+        lk_st(D.pt, i, fe_from_canonical<FrP>(s));
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------------
+static size_t lk_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Validated arguments; columns and outputs are device pointers (in[j], tab[j], pa[j], pt[j] for lookup j), blinding host memory.
+// Enqueues everything on s, then waits for s once to read the not-found flags: H2HIP_ELOOKUP names the lowest failing lookup.
+int lookup_permute_device(Ctx* c, uint32_t k, const Fe* const* in, const Fe* const* tab, size_t count, const uint64_t* blinding, uint32_t bf,
+                          Fe* const* pa, Fe* const* pt, hipStream_t s) {
+    if (count == 0) return 0;
+    const uint64_t n = 1ull << k, u = n - bf - 1;
+    const uint32_t ts = (uint32_t)(n < LK_TILE ? n : LK_TILE);
+    uint32_t block = g_lk_block ? g_lk_block : LK_TILE;
+    if (block > ts) block = ts;
+    const uint32_t tiles = (uint32_t)(n / ts);
+    uint32_t passes = 0;
+    for (uint64_t w = block; w < n; w <<= 1) passes++;
+    const size_t cols = 2 * count, col_bytes = n * sizeof(Fe);
+    const size_t nb = (size_t)bf + 1;
+    // workspace: two key buffers per sorted column, per lookup the used marks, L, the tile counts; the flags
+    const size_t used_bytes = lk_align(n * sizeof(uint32_t)), cnt_bytes = lk_align(((size_t)tiles + 1) * sizeof(uint32_t));
+    const size_t per_lookup = used_bytes + col_bytes + 2 * cnt_bytes;
+    const size_t flag_bytes = lk_align(count * sizeof(uint32_t));
+    const size_t blob_perm = lk_align(count * sizeof(LkPerm)), blob_ptr = lk_align(3 * cols * sizeof(void*));
+    const size_t blob = blob_perm + blob_ptr + lk_align(count * 2 * nb * sizeof(Fe));
+    int rc = c->ws_acquire(s);
+    if (rc) return rc;
+    WsGuard guard(c, s);
+    if ((rc = c->lookup_ws.ensure(2 * cols * col_bytes + count * per_lookup + flag_bytes + blob))) return rc;
+    if ((rc = c->lookup_flag.ensure(count * sizeof(uint32_t)))) return rc;
+    char* base = (char*)c->lookup_ws.p;
+    Fe* keys = (Fe*)base;  // [buffer][column][n]
+    char* per = base + 2 * cols * col_bytes;
+    uint32_t* d_flag = (uint32_t*)(per + count * per_lookup);
+    char* d_blob = per + count * per_lookup + flag_bytes;
+    std::vector<char> h(blob, 0);
+    LkPerm* hp = (LkPerm*)h.data();
+    const Fe** hsrc = (const Fe**)(h.data() + blob_perm);
+    Fe** hk0 = (Fe**)(h.data() + blob_perm) + cols;
+    Fe** hk1 = (Fe**)(h.data() + blob_perm) + 2 * cols;
+    Fe* hblind = (Fe*)(h.data() + blob_perm + blob_ptr);
+    if (nb) memcpy(hblind, blinding, count * 2 * nb * sizeof(Fe));
+    const Fe* const* d_src = (const Fe* const*)(d_blob + blob_perm);
+    Fe* const* d_k0 = (Fe* const*)(d_blob + blob_perm) + cols;
+    Fe* const* d_k1 = (Fe* const*)(d_blob + blob_perm) + 2 * cols;
+    for (size_t q = 0; q < cols; q++) {
+        hsrc[q] = q & 1 ? tab[q / 2] : in[q / 2];
+        hk0[q] = keys + q * n;
+        hk1[q] = keys + (cols + q) * n;
+    }
+    Fe* const* h_sorted = passes & 1 ? hk1 : hk0;  // where the last pass leaves the keys
+    for (size_t j = 0; j < count; j++) {
+        char* pj = per + j * per_lookup;
+        LkPerm& D = hp[j];
+        D.a = h_sorted[2 * j];
+        D.t = h_sorted[2 * j + 1];
+        D.used = (uint32_t*)pj;
+        D.lc = (Fe*)(pj + used_bytes);
+        D.cnt_l = (uint32_t*)(pj + used_bytes + col_bytes);
+        D.cnt_r = (uint32_t*)(pj + used_bytes + col_bytes + cnt_bytes);
+        D.flag = d_flag + j;
+        D.pa = pa[j];
+        D.pt = pt[j];
+        D.blind = (const Fe*)(d_blob + blob_perm + blob_ptr) + j * 2 * nb;
+    }
+    if ((rc = c->stage_h2d(d_blob, h.data(), blob, s))) return rc;
+    for (size_t j = 0; j < count; j++) H2_CHECK(hipMemsetAsync(per + j * per_lookup, 0, used_bytes, s));
+    H2_CHECK(hipMemsetAsync(d_flag, 0, count * sizeof(uint32_t), s));
+    const LkPerm* d_perm = (const LkPerm*)d_blob;
+    int tm = c->timer_begin("lookup_permute", s);
+    hipLaunchKernelGGL(lk_block_sort_kernel, dim3(tiles, (uint32_t)cols), dim3(LK_THREADS), 0, s, d_src, d_k0, u, ts, block);
+    H2_CHECK(hipGetLastError());
+    uint32_t w = block;
+    for (uint32_t p = 0; p < passes; p++, w <<= 1) {
+        const Fe* const* from = p & 1 ? (const Fe* const*)d_k1 : (const Fe* const*)d_k0;
+        hipLaunchKernelGGL(lk_merge_kernel, dim3(tiles, (uint32_t)cols), dim3(LK_THREADS), 0, s, from, p & 1 ? d_k0 : d_k1, w, ts);
+        H2_CHECK(hipGetLastError());
+    }
+    const dim3 grid(tiles, (uint32_t)count);
+    hipLaunchKernelGGL(lk_mark_kernel, grid, dim3(LK_THREADS), 0, s, d_perm, u);
+    H2_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(lk_count_kernel, grid, dim3(LK_THREADS), 0, s, d_perm, u);
+    H2_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(lk_scan_kernel, dim3((uint32_t)count), dim3(LK_THREADS), 0, s, d_perm, tiles);
+    H2_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(lk_compact_kernel, grid, dim3(LK_THREADS), 0, s, d_perm, u);
+    H2_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(lk_final_kernel, grid, dim3(LK_THREADS), 0, s, d_perm, u, n, tiles);
+    H2_CHECK(hipGetLastError());
+    c->timer_end(tm, s);
+    H2_CHECK(hipMemcpyAsync(c->lookup_flag.p, d_flag, count * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if ((rc = guard.release())) return rc;
+    g_lk_last[0] = block;
+    g_lk_last[1] = passes;
+    H2_CHECK(hipStreamSynchronize(s));  // the caller must know before it commits
+    const uint32_t* flags = (const uint32_t*)c->lookup_flag.p;
+    for (size_t j = 0; j < count; j++)
+        if (flags[j]) {
+            set_error("lookup_permute: lookup %zu: an input value is not in the table (ConstraintSystemFailure)", j);
+            return H2HIP_ELOOKUP;
+        }
+    return 0;
+}
+
+}  // namespace h2
+
+using namespace h2;
+
+extern "C" {
+// ---- C ABI (include/halo2hip.h, "lookup compression and permutation") -----------------------------------------------------------
+// Here rather than in api.hip, for the reason product.hip gives.
+static int lk_ptrs_check(const char* what, const void* const* p, size_t count, const char* name) {
+    if (count && !p) {
+        set_error("%s: null %s", what, name);
+        return H2HIP_EINVAL;
+    }
+    for (size_t i = 0; i < count; i++)
+        if (!p[i]) {
+            set_error("%s: %s[%zu] is null", what, name, i);
+            return H2HIP_EINVAL;
+        }
+    return 0;
+}
+
+static int compress_check(uint32_t k, const void* const* fixed, uint32_t n_fixed, const void* const* advice, uint32_t n_advice,
+                          const void* const* instance, uint32_t n_instance, const uint64_t* challenges, uint32_t n_challenges,
+                          const uint64_t* theta, const h2hip_graph* graphs, size_t n_graphs, const void* const* out) {
+    const char* what = "lookup_compress";
+    if (k > 28) {
+        set_error("%s: k = %u > 28", what, k);
+        return H2HIP_EINVAL;
+    }
+    if (!theta || (n_challenges && !challenges)) {
+        set_error("%s: null theta or challenges", what);
+        return H2HIP_EINVAL;
+    }
+    if (check_fr(theta, "theta")) return H2HIP_EINVAL;
+    for (uint32_t i = 0; i < n_challenges; i++)
+        if (check_fr(challenges + 4 * (size_t)i, "challenge")) return H2HIP_EINVAL;
+    if (lk_ptrs_check(what, fixed, n_fixed, "fixed_values") || lk_ptrs_check(what, advice, n_advice, "advice_values") ||
+        lk_ptrs_check(what, instance, n_instance, "instance_values") || lk_ptrs_check(what, out, n_graphs, "out"))
+        return H2HIP_EINVAL;
+    return lookup_compress_validate(n_fixed, n_advice, n_instance, n_challenges, graphs, n_graphs);
+}
+
+static int permute_check(uint32_t k, const void* const* in, const void* const* tab, size_t count, const uint64_t* blinding, uint32_t bf,
+                         const void* const* pa, const void* const* pt) {
+    const char* what = "lookup_permute";
+    if (k > 28) {
+        set_error("%s: k = %u > 28", what, k);
+        return H2HIP_EINVAL;
+    }
+    if ((uint64_t)bf + 1 >= (1ull << k)) {
+        set_error("%s: blinding_factors + 1 >= 2^k", what);
+        return H2HIP_EINVAL;
+    }
+    if (count > LK_MAX_COUNT) {
+        set_error("%s: count %zu > %d", what, count, LK_MAX_COUNT);
+        return H2HIP_EINVAL;
+    }
+    if (count && !blinding) {
+        set_error("%s: null blinding", what);
+        return H2HIP_EINVAL;
+    }
+    for (size_t i = 0; i < count * 2 * ((size_t)bf + 1); i++)
+        if (check_fr(blinding + 4 * i, "blinding value")) return H2HIP_EINVAL;
+    if (lk_ptrs_check(what, in, count, "compressed_input") || lk_ptrs_check(what, tab, count, "compressed_table") ||
+        lk_ptrs_check(what, pa, count, "permuted_input") || lk_ptrs_check(what, pt, count, "permuted_table"))
+        return H2HIP_EINVAL;
+    return 0;
+}
+
+int h2hip_lookup_compress_bn254_device(uint32_t k, const void* const* d_fixed_values, uint32_t n_fixed, const void* const* d_advice_values,
+                                       uint32_t n_advice, const void* const* d_instance_values, uint32_t n_instance, const uint64_t* challenges,
+                                       uint32_t n_challenges, const uint64_t theta[4], const h2hip_graph* graphs, size_t n_graphs, void* const* d_out,
+                                       void* stream) {
+    if (int rc = compress_check(k, d_fixed_values, n_fixed, d_advice_values, n_advice, d_instance_values, n_instance, challenges, n_challenges,
+                                theta, graphs, n_graphs, (const void* const*)d_out))
+        return rc;
+    if (n_graphs == 0) return 0;
+    Entry en("h2hip_lookup_compress_bn254_device", d_out[0]);
+    if (en.rc) return en.rc;
+    return lookup_compress_device(en.c, k, (const Fe* const*)d_fixed_values, n_fixed, (const Fe* const*)d_advice_values, n_advice,
+                                  (const Fe* const*)d_instance_values, n_instance, challenges, n_challenges, theta, graphs, n_graphs,
+                                  (Fe* const*)d_out, (hipStream_t)stream);
+}
+
+int h2hip_lookup_compress_bn254(uint32_t k, const uint64_t* const* fixed_values, uint32_t n_fixed, const uint64_t* const* advice_values,
+                                uint32_t n_advice, const uint64_t* const* instance_values, uint32_t n_instance, const uint64_t* challenges,
+                                uint32_t n_challenges, const uint64_t theta[4], const h2hip_graph* graphs, size_t n_graphs, uint64_t* const* out) {
+    if (int rc = compress_check(k, (const void* const*)fixed_values, n_fixed, (const void* const*)advice_values, n_advice,
+                                (const void* const*)instance_values, n_instance, challenges, n_challenges, theta, graphs, n_graphs,
+                                (const void* const*)out))
+        return rc;
+    if (n_graphs == 0) return 0;
+    Entry en("h2hip_lookup_compress_bn254");
+    if (en.rc) return en.rc;
+    Ctx* c = en.c;
+    hipStream_t s = c->stream;
+    const size_t n = (size_t)1 << k, bytes = n * sizeof(Fe);
+    // fixed columns pinned with h2hip_columns_pin are read where they lie; the witness columns and the rest cross PCIe
+    std::vector<const Fe*> d_fixed(n_fixed, nullptr), d_advice(n_advice), d_instance(n_instance);
+    std::vector<Fe*> d_out(n_graphs);
+    size_t unpinned = 0;
+    for (uint32_t j = 0; j < n_fixed; j++) {
+        d_fixed[j] = pinned_column_lookup(c, fixed_values[j], n);
+        if (!d_fixed[j]) unpinned++;
+    }
+    int rc = c->lookup_io.ensure((unpinned + n_advice + n_instance + n_graphs) * bytes);
+    if (rc) return rc;
+    char* io = (char*)c->lookup_io.p;
+    size_t slot = 0;
+    auto up = [&](const uint64_t* src) -> const Fe* {
+        Fe* d = (Fe*)(io + slot++ * bytes);
+        return hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, s) == hipSuccess ? d : nullptr;
+    };
+    for (uint32_t j = 0; j < n_fixed; j++)
+        if (!d_fixed[j] && !(d_fixed[j] = up(fixed_values[j]))) return H2HIP_EDEVICE;
+    for (uint32_t j = 0; j < n_advice; j++)
+        if (!(d_advice[j] = up(advice_values[j]))) return H2HIP_EDEVICE;
+    for (uint32_t j = 0; j < n_instance; j++)
+        if (!(d_instance[j] = up(instance_values[j]))) return H2HIP_EDEVICE;
+    for (size_t g = 0; g < n_graphs; g++) d_out[g] = (Fe*)(io + slot++ * bytes);
+    rc = lookup_compress_device(c, k, d_fixed.data(), n_fixed, d_advice.data(), n_advice, d_instance.data(), n_instance, challenges, n_challenges,
+                                theta, graphs, n_graphs, d_out.data(), s);
+    if (rc) return rc;
+    for (size_t g = 0; g < n_graphs; g++) H2_CHECK(hipMemcpyAsync(out[g], d_out[g], bytes, hipMemcpyDeviceToHost, s));
+    H2_CHECK(hipStreamSynchronize(s));
+    return 0;
+}
+
+int h2hip_lookup_permute_bn254_device(uint32_t k, const void* const* d_compressed_input, const void* const* d_compressed_table, size_t count,
+                                      const uint64_t* blinding, uint32_t blinding_factors, void* const* d_permuted_input,
+                                      void* const* d_permuted_table, void* stream) {
+    if (int rc = permute_check(k, d_compressed_input, d_compressed_table, count, blinding, blinding_factors, (const void* const*)d_permuted_input,
+                               (const void* const*)d_permuted_table))
+        return rc;
+    if (count == 0) return 0;
+    Entry en("h2hip_lookup_permute_bn254_device", d_permuted_input[0]);
+    if (en.rc) return en.rc;
+    return lookup_permute_device(en.c, k, (const Fe* const*)d_compressed_input, (const Fe* const*)d_compressed_table, count, blinding,
+                                 blinding_factors, (Fe* const*)d_permuted_input, (Fe* const*)d_permuted_table, (hipStream_t)stream);
+}
+
+int h2hip_lookup_permute_bn254(uint32_t k, const uint64_t* const* compressed_input, const uint64_t* const* compressed_table, size_t count,
+                               const uint64_t* blinding, uint32_t blinding_factors, uint64_t* const* permuted_input, uint64_t* const* permuted_table) {
+    if (int rc = permute_check(k, (const void* const*)compressed_input, (const void* const*)compressed_table, count, blinding, blinding_factors,
+                               (const void* const*)permuted_input, (const void* const*)permuted_table))
+        return rc;
+    if (count == 0) return 0;
+    Entry en("h2hip_lookup_permute_bn254");
+    if (en.rc) return en.rc;
+    Ctx* c = en.c;
+    hipStream_t s = c->stream;
+    const size_t n = (size_t)1 << k, bytes = n * sizeof(Fe);
+    int rc = c->lookup_io.ensure(4 * count * bytes);
+    if (rc) return rc;
+    char* io = (char*)c->lookup_io.p;
+    std::vector<const Fe*> in(count), tab(count);
+    std::vector<Fe*> pa(count), pt(count);
+    for (size_t j = 0; j < count; j++) {
+        in[j] = (const Fe*)(io + (4 * j) * bytes);
+        tab[j] = (const Fe*)(io + (4 * j + 1) * bytes);
+        pa[j] = (Fe*)(io + (4 * j + 2) * bytes);
+        pt[j] = (Fe*)(io + (4 * j + 3) * bytes);
+        H2_CHECK(hipMemcpyAsync((void*)in[j], compressed_input[j], bytes, hipMemcpyHostToDevice, s));
+        H2_CHECK(hipMemcpyAsync((void*)tab[j], compressed_table[j], bytes, hipMemcpyHostToDevice, s));
+    }
+    rc = lookup_permute_device(c, k, in.data(), tab.data(), count, blinding, blinding_factors, pa.data(), pt.data(), s);
+    if (rc) return rc;
+    for (size_t j = 0; j < count; j++) {
+        H2_CHECK(hipMemcpyAsync(permuted_input[j], pa[j], bytes, hipMemcpyDeviceToHost, s));
+        H2_CHECK(hipMemcpyAsync(permuted_table[j], pt[j], bytes, hipMemcpyDeviceToHost, s));
+    }
+    H2_CHECK(hipStreamSynchronize(s));
+    return 0;
+}
+
+int h2hip_debug_set_lookup_sort(uint32_t lds_keys) {
+    if (lds_keys && (lds_keys < 4 || lds_keys > LK_TILE || (lds_keys & (lds_keys - 1)))) {
+        set_error("debug_set_lookup_sort: the in-LDS sort block must be a power of two in [4, %d], or 0", LK_TILE);
+        return H2HIP_EINVAL;
+    }
+    g_lk_block = lds_keys;
+    return 0;
+}
+
+int h2hip_debug_lookup_sort_stats(uint32_t out[2]) {
+    if (!out) {
+        set_error("debug_lookup_sort_stats: null argument");
+        return H2HIP_EINVAL;
+    }
+    out[0] = g_lk_last[0];
+    out[1] = g_lk_last[1];
+    return 0;
+}
+
+}  // extern "C"

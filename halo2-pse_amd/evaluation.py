@@ -140,6 +140,18 @@ def lookup_graph(input_exprs, table_exprs):
     return g
 
 
+def lookup_compress_graphs(input_exprs, table_exprs):
+    """commit_permuted's compression (lookup/prover.rs:90-115) as two graphs, one per side: each expression added with add_expression,
+    then Horner(Constant(0), parts, Theta) -- theta^(m-1) e_0 + ... + e_(m-1), lookup_graph's evaluate_lc on a graph of its own"""
+    out = []
+    for exprs in (input_exprs, table_exprs):
+        g = GraphEvaluator()
+        parts = tuple(g.add_expression(e) for e in exprs)
+        g.add_calculation((CALC_HORNER, (VS_CONSTANT, 0, 0), (VS_THETA, 0, 0), parts))
+        out.append(g)
+    return tuple(out)
+
+
 # ------------------------------------------------------------------ flat arrays <-> ctypes
 def to_mont_limbs(vals):
     out = np.zeros((len(vals), 4), dtype=np.uint64)
@@ -259,18 +271,33 @@ class DescHolder:
         return n, ctypes.addressof(p)
 
     def _graph(self, g):
-        G = Graph()
-        consts, rots = self._c(g["constants"]), self._c(g["rotations"], np.int32)
-        calcs, parts = self._c(g["calcs"], np.uint32), self._c(g["parts"], np.uint32)
-        G.constants, G.n_constants = _ptr(consts), consts.shape[0]
-        G.rotations, G.n_rotations = _ptr(rots), rots.shape[0]
-        G.calculations, G.n_calculations = _ptr(calcs), calcs.shape[0]
-        G.parts, G.n_parts = _ptr(parts), parts.shape[0]
-        G.num_intermediates = int(g["num_intermediates"])
-        return G
+        return graph_struct(g, self.keep)
 
     def byref(self):
         return ctypes.byref(self.desc)
+
+
+def graph_struct(g, keep):
+    """one flattened graph (flatten_graph dict) -> h2hip_graph; the arrays it points into are appended to `keep`"""
+    c = lambda a, dt: keep.append(np.ascontiguousarray(a, dtype=dt)) or keep[-1]  # noqa: E731
+    consts, rots = c(g["constants"], np.uint64), c(g["rotations"], np.int32)
+    calcs, parts = c(g["calcs"], np.uint32), c(g["parts"], np.uint32)
+    G = Graph()
+    G.constants, G.n_constants = _ptr(consts), consts.shape[0]
+    G.rotations, G.n_rotations = _ptr(rots), rots.shape[0]
+    G.calculations, G.n_calculations = _ptr(calcs), calcs.shape[0]
+    G.parts, G.n_parts = _ptr(parts), parts.shape[0]
+    G.num_intermediates = int(g["num_intermediates"])
+    return G
+
+
+def graph_array(flat_graphs):
+    """flattened graphs -> (a ctypes array of h2hip_graph, the list of arrays it points into): keep the second alive while the first is used"""
+    keep = []
+    arr = (Graph * max(1, len(flat_graphs)))()
+    for i, g in enumerate(flat_graphs):
+        arr[i] = graph_struct(g, keep)
+    return arr, keep
 
 
 GraphBuilder = GraphEvaluator  # older name used by the tests

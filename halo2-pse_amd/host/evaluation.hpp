@@ -253,6 +253,20 @@ struct EvaluateHInputs {
     std::vector<std::array<const std::vector<Fr>*, 3>> lookups;
 };
 
+// commit_permuted's compression (plonk/lookup/prover.rs:90-115) as two graphs, input side then table side: each expression added with
+// add_expression, then Horner(Constant(0), parts, Theta) -- Evaluator::create's evaluate_lc on a graph of its own (halo2hip.hpp
+// lookup_compress runs them)
+inline std::pair<GraphEvaluator, GraphEvaluator> lookup_compress_graphs(const LookupArgument& lookup) {
+    auto side = [](const std::vector<Expr>& expressions) {
+        GraphEvaluator g;
+        std::vector<ValueSource> p;
+        for (const auto& e : expressions) p.push_back(g.add_expression(e));
+        g.add_calculation(Calculation::Horner(ValueSource::Constant(0), p, ValueSource::Theta()));
+        return g;
+    };
+    return {side(lookup.input_expressions), side(lookup.table_expressions)};
+}
+
 class Evaluator {  // :182-189
   public:
     GraphEvaluator custom_gates;

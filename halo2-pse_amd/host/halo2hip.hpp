@@ -532,6 +532,61 @@ inline std::vector<poly::Polynomial<poly::LagrangeCoeff>> lookup_products(
     return z;
 }
 
+// lookup::Argument::commit_permuted's compression (plonk/lookup/prover.rs:90-115): out[g] = graphs[g] over the n Lagrange rows.  Each
+// graph is one side of a lookup, add_expression of its expressions then Horner(Constant(0), parts, Theta) (evaluation.hpp
+// lookup_compress_graphs builds them); fixed / advice / instance are the Lagrange columns the graphs index.
+inline std::vector<poly::Polynomial<poly::LagrangeCoeff>> lookup_compress(
+    const poly::EvaluationDomain& domain, const std::vector<h2hip_graph>& graphs, const std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>& fixed,
+    const std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>& advice, const std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>& instance,
+    const std::vector<Fr>& challenges, const Fr& theta) {
+    auto ptrs = [&](const std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>& cols) {
+        std::vector<const uint64_t*> p;
+        for (auto* c : cols) {
+            if (c->len() != domain.n) throw std::logic_error("column length != n");
+            p.push_back(c->values[0].l);
+        }
+        return p;
+    };
+    const auto f = ptrs(fixed), a = ptrs(advice), i = ptrs(instance);
+    std::vector<poly::Polynomial<poly::LagrangeCoeff>> out(graphs.size(), poly::Polynomial<poly::LagrangeCoeff>{std::vector<Fr>(domain.n)});
+    std::vector<uint64_t*> op;
+    for (auto& col : out) op.push_back(col.values[0].l);
+    engine_check(h2hip_lookup_compress_bn254(domain.k, f.data(), uint32_t(f.size()), a.data(), uint32_t(a.size()), i.data(), uint32_t(i.size()),
+                                             challenges.empty() ? nullptr : challenges[0].l, uint32_t(challenges.size()), theta.l, graphs.data(),
+                                             graphs.size(), op.data()),
+                 "lookup_compress");
+    return out;
+}
+
+// permute_expression_pair (plonk/lookup/prover.rs:391-475) for every lookup: returns (A'_j, S'_j) per lookup.  blinding holds
+// 2(blinding_factors + 1) values per lookup, the A' rows then the S' rows, drawn in the reference's order.
+// A value of an input missing from its table is the reference's Error::ConstraintSystemFailure: std::domain_error here.
+inline std::vector<std::pair<poly::Polynomial<poly::LagrangeCoeff>, poly::Polynomial<poly::LagrangeCoeff>>> lookup_permute(
+    const poly::EvaluationDomain& domain, const std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>& inputs,
+    const std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>& tables, const std::vector<Fr>& blinding, size_t blinding_factors) {
+    const size_t count = inputs.size();
+    if (tables.size() != count) throw std::logic_error("lookup columns differ in count");
+    if (blinding.size() != count * 2 * (blinding_factors + 1)) throw std::logic_error("blinding: count * 2(blinding_factors + 1) values expected");
+    std::vector<const uint64_t*> a, s;
+    for (size_t j = 0; j < count; j++) {
+        if (inputs[j]->len() != domain.n || tables[j]->len() != domain.n) throw std::logic_error("column length != n");
+        a.push_back(inputs[j]->values[0].l);
+        s.push_back(tables[j]->values[0].l);
+    }
+    using Col = poly::Polynomial<poly::LagrangeCoeff>;
+    std::vector<std::pair<Col, Col>> out(count, {Col{std::vector<Fr>(domain.n)}, Col{std::vector<Fr>(domain.n)}});
+    std::vector<uint64_t*> pa, pt;
+    for (auto& p : out) {
+        pa.push_back(p.first.values[0].l);
+        pt.push_back(p.second.values[0].l);
+    }
+    const int rc = h2hip_lookup_permute_bn254(domain.k, a.data(), s.data(), count, blinding.empty() ? nullptr : blinding[0].l,
+                                              uint32_t(blinding_factors), pa.data(), pt.data());
+    if (rc == H2HIP_ELOOKUP) throw std::domain_error(std::string("lookup_permute: ") + h2hip_last_error());
+    engine_check(rc, "lookup_permute");
+    return out;
+}
+
 }  // namespace plonk
 
 // The KZG multiopen provers restated over the engine's primitive.  The caller builds the sets (construct_intermediate_sets), draws the

@@ -29,6 +29,8 @@ pub const H2HIP_OK: i32 = 0;
 pub const H2HIP_EINVAL: i32 = 1;
 pub const H2HIP_EDEVICE: i32 = 2;
 pub const H2HIP_ENOMEM: i32 = 3;
+/// a lookup's input holds a value its table lacks: the reference's `Error::ConstraintSystemFailure`
+pub const H2HIP_ELOOKUP: i32 = 4;
 
 /// Initialise the engine on the given GPUs (one context, stream and worker thread each; host-pointer MSMs shard over
 /// them).  Optional: the first call initialises lazily on the current device, or on `HALO2_HIP_DEVICES`.
@@ -307,6 +309,66 @@ pub fn try_lookup_products<F: Field + 'static>(k: u32, beta: &F, gamma: &F, comp
         return None;
     }
     Some(z)
+}
+
+/// `commit_permuted`'s compressed expressions (plonk/lookup/prover.rs:90-115): `graphs[g]` (an input or table side of a lookup, built
+/// as `add_expression` of each expression and `Horner(Constant(0), parts, Theta)`) over the Lagrange columns.  `None` on any failure.
+#[allow(clippy::too_many_arguments)]
+pub fn try_lookup_compress<F: Field + 'static>(k: u32, fixed: &[&[F]], advice: &[&[F]], instance: &[&[F]], challenges: &[F], theta: &F,
+                                               graphs: &[&evalh::FlatGraph]) -> Option<Vec<Vec<F>>> {
+    if !is::<F, Fr>() || !layout_ok() || k > 28 {
+        return None;
+    }
+    let n = 1usize << k;
+    if fixed.iter().chain(advice.iter()).chain(instance.iter()).any(|c| c.len() != n) {
+        return None;
+    }
+    let ptrs = |cols: &[&[F]]| -> Vec<*const u64> { cols.iter().map(|c| c.as_ptr() as *const u64).collect() };
+    let (f, a, i) = (ptrs(fixed), ptrs(advice), ptrs(instance));
+    let views: Vec<evalh::h2hip_graph> = graphs.iter().map(|g| g.view()).collect();
+    let mut out: Vec<Vec<F>> = (0..graphs.len()).map(|_| vec![F::zero(); n]).collect();
+    let op: Vec<*mut u64> = out.iter_mut().map(|c| c.as_mut_ptr() as *mut u64).collect();
+    let rc = unsafe {
+        ffi::h2hip_lookup_compress_bn254(k, f.as_ptr(), f.len() as u32, a.as_ptr(), a.len() as u32, i.as_ptr(), i.len() as u32,
+                                         challenges.as_ptr() as *const u64, challenges.len() as u32, fr_ptr(theta), views.as_ptr(),
+                                         views.len(), op.as_ptr())
+    };
+    if rc != 0 {
+        return None;
+    }
+    Some(out)
+}
+
+/// `permute_expression_pair` (plonk/lookup/prover.rs:391-475) for several lookups in one call: `blinding` holds 2(b + 1) values per
+/// lookup, the A' rows then the S' rows, drawn by the caller in the reference's order.  `Ok(None)` when the engine did not take the
+/// call, `Err(H2HIP_ELOOKUP)` when an input value is missing from its table (`Error::ConstraintSystemFailure`).
+#[allow(clippy::type_complexity)]
+pub fn try_lookup_permute<F: Field + 'static>(k: u32, compressed_inputs: &[&[F]], compressed_tables: &[&[F]], blinding: &[F],
+                                              blinding_factors: usize) -> Result<Option<(Vec<Vec<F>>, Vec<Vec<F>>)>, i32> {
+    let count = compressed_inputs.len();
+    if !is::<F, Fr>() || !layout_ok() || k > 28 || compressed_tables.len() != count {
+        return Ok(None);
+    }
+    let n = 1usize << k;
+    if compressed_inputs.iter().chain(compressed_tables.iter()).any(|c| c.len() != n) || blinding_factors + 1 >= n
+        || blinding.len() != count * 2 * (blinding_factors + 1) {
+        return Ok(None);
+    }
+    let ptrs = |cols: &[&[F]]| -> Vec<*const u64> { cols.iter().map(|c| c.as_ptr() as *const u64).collect() };
+    let (a, s) = (ptrs(compressed_inputs), ptrs(compressed_tables));
+    let mut pa: Vec<Vec<F>> = (0..count).map(|_| vec![F::zero(); n]).collect();
+    let mut pt: Vec<Vec<F>> = (0..count).map(|_| vec![F::zero(); n]).collect();
+    let pap: Vec<*mut u64> = pa.iter_mut().map(|c| c.as_mut_ptr() as *mut u64).collect();
+    let ptp: Vec<*mut u64> = pt.iter_mut().map(|c| c.as_mut_ptr() as *mut u64).collect();
+    let rc = unsafe {
+        ffi::h2hip_lookup_permute_bn254(k, a.as_ptr(), s.as_ptr(), count, blinding.as_ptr() as *const u64, blinding_factors as u32,
+                                        pap.as_ptr(), ptp.as_ptr())
+    };
+    match rc {
+        0 => Ok(Some((pa, pt))),
+        H2HIP_ELOOKUP => Err(H2HIP_ELOOKUP),
+        _ => Ok(None),
+    }
 }
 
 /// `eval_polynomial` (arithmetic.rs:304-328) for every query of a proof in one call: query `q` evaluates `polys[query_poly[q]]` at

@@ -56,6 +56,7 @@ extern "C" {
 #define H2HIP_EINVAL 1   /* contract violation (the reference would panic: arithmetic.rs:133,184) */
 #define H2HIP_EDEVICE 2  /* HIP runtime / device error, or no GPU */
 #define H2HIP_ENOMEM 3
+#define H2HIP_ELOOKUP 4  /* a lookup's input holds a value its table lacks (lookup::Argument::commit_permuted: Error::ConstraintSystemFailure) */
 
 /* ---- lifecycle ------------------------------------------------------------------------- */
 
@@ -370,6 +371,35 @@ int h2hip_lookup_products_bn254_device(uint32_t k, const uint64_t beta[4], const
 /* ff::BatchInvert (permutation/prover.rs:117, lookup/prover.rs:208): a[i] <- a[i]^-1 in place, zeros stay zero; n <= 2^30 */
 int h2hip_batch_invert_bn254_fr(uint64_t* a, size_t n);
 int h2hip_batch_invert_bn254_fr_device(void* d_a, size_t n, void* stream);
+
+/* ---- lookup compression and permutation: lookup::Argument::commit_permuted (plonk/lookup/prover.rs:64-170), between the theta and the
+ * beta squeeze of create_proof -------------------------------------------------------------------------------------------------------
+ * n = 2^k, b = blinding_factors, u = n - b - 1 (usable_rows; here rows u .. n - 1, b + 1 of them, are blinding rows).
+ * Compress (:90-115): out[g][i] = graph g evaluated at row i < n over the Lagrange columns fixed / advice / instance (2^k Fr elements
+ * each), the challenges and theta, with rotations wrapping modulo n.  Graph g is GraphEvaluator::add_expression of each of a lookup's
+ * input (or table) expressions, then Horner(Constant(0), parts, Theta) -- C = theta^(m-1) e_0 + ... + e_(m-1) (evaluation.py
+ * lookup_compress_graphs).  A graph that reads beta, gamma, y or the previous value, or an index out of range, is H2HIP_EINVAL.
+ * Permute (permute_expression_pair, :391-475), per lookup j: A' = compressed_input[0 .. u) sorted by Fr's Ord (the canonical integers);
+ * S'[i] = A'[i] on the first row of each distinct value, taking one copy of it out of the multiset T = compressed_table[0 .. u); the
+ * leftovers L (ascending) fill the repeated rows R (ascending) as S'[R[t]] = L[|L| - 1 - t].  blinding holds 2(b + 1) values per lookup,
+ * A' rows u .. n - 1 then S' rows u .. n - 1, drawn by the caller in the reference's order; the engine draws nothing.  An input value
+ * missing from its table is H2HIP_ELOOKUP: h2hip_last_error() names the lowest such lookup, and the outputs are unspecified.
+ * k <= 28, b + 1 < n (permute), count <= 32767, n_graphs <= 65535; n_graphs == 0 / count == 0 write nothing.  Host forms: a fixed column
+ * pinned with h2hip_columns_pin (elems = 2^k) is not uploaded.  _device forms: columns and outputs are device pointers (the pointer tables,
+ * graphs, challenges, theta and blinding values are host memory, read before the call returns) and kernels are queued on `stream`; the
+ * compress call does not wait for them, the permute call synchronises `stream` once, to read the not-found flags. */
+int h2hip_lookup_compress_bn254(uint32_t k, const uint64_t* const* fixed_values, uint32_t n_fixed, const uint64_t* const* advice_values,
+                                uint32_t n_advice, const uint64_t* const* instance_values, uint32_t n_instance, const uint64_t* challenges,
+                                uint32_t n_challenges, const uint64_t theta[4], const h2hip_graph* graphs, size_t n_graphs, uint64_t* const* out);
+int h2hip_lookup_compress_bn254_device(uint32_t k, const void* const* d_fixed_values, uint32_t n_fixed, const void* const* d_advice_values,
+                                       uint32_t n_advice, const void* const* d_instance_values, uint32_t n_instance, const uint64_t* challenges,
+                                       uint32_t n_challenges, const uint64_t theta[4], const h2hip_graph* graphs, size_t n_graphs, void* const* d_out,
+                                       void* stream);
+int h2hip_lookup_permute_bn254(uint32_t k, const uint64_t* const* compressed_input, const uint64_t* const* compressed_table, size_t count,
+                               const uint64_t* blinding, uint32_t blinding_factors, uint64_t* const* permuted_input, uint64_t* const* permuted_table);
+int h2hip_lookup_permute_bn254_device(uint32_t k, const void* const* d_compressed_input, const void* const* d_compressed_table, size_t count,
+                                      const uint64_t* blinding, uint32_t blinding_factors, void* const* d_permuted_input,
+                                      void* const* d_permuted_table, void* stream);
 
 /* ---- opening: the query evaluations and the KZG multiopen quotients that follow evaluate_h --------------------------------------
  * Evaluation (eval_polynomial, arithmetic.rs:304-328): evals[q] = polys[query_poly[q]] evaluated at points[q], for n_queries queries

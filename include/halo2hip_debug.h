@@ -92,6 +92,10 @@ int h2hip_debug_evalh_compile_stats(const h2hip_graph* g, uint32_t* n_ops, uint3
 /* opening (evaluations and combine / divide): force the tile shape, consecutive rows per thread (power of two <= 64) and threads per
  * tile (power of two <= 256), so that small inputs span many tiles; 0 restores the size-based default.  Needs no GPU. */
 int h2hip_debug_set_opening_tile(uint32_t rows_per_thread, uint32_t threads_per_tile);
+/* lookup permutation: force the in-LDS sort block (a power of two in [4, 1024]; 0 = default 1024) so that small columns run the merge
+ * passes; needs no GPU.  Stats: out[0] = the block and out[1] = the merge passes (log2(2^k / block)) of the last permute call. */
+int h2hip_debug_set_lookup_sort(uint32_t lds_keys);
+int h2hip_debug_lookup_sort_stats(uint32_t out[2]);
 
 #ifdef __cplusplus
 }
