@@ -453,6 +453,157 @@ def commit_permuted(params, domain, lookups, theta, blinding, blinding_factors, 
     return out
 
 
+# ------------------------------------------------------------------ keygen: permutation key, batch_invert_assigned, l0 / l_last / l_active_row
+FR_DELTA = pow(7, 1 << FR_S, FR_MODULUS)  # Fr::DELTA = MULTIPLICATIVE_GENERATOR^(2^S)
+
+
+class PermutationAssembly:
+    """permutation::keygen::Assembly (plonk/permutation/keygen.rs:16-103), a literal host port: `mapping`, `aux` and `sizes`, and
+    `copy` merging the smaller cycle into the larger.  Columns are the permutation argument's column indices 0 .. n_columns - 1."""
+
+    def __init__(self, n, n_columns):
+        self.n, self.n_columns = int(n), int(n_columns)
+        ident = np.zeros((self.n_columns, self.n, 2), dtype=np.uint32)         # :31-35: (i, j) for column i, row j
+        ident[:, :, 0] = np.arange(self.n_columns, dtype=np.uint32)[:, None]
+        ident[:, :, 1] = np.arange(self.n, dtype=np.uint32)[None, :]
+        self.mapping = ident                                                   # :42
+        self.aux = ident.copy()                                                # :43
+        self.sizes = np.ones((self.n_columns, self.n), dtype=np.int64)         # :44
+
+    def copy(self, left_column, left_row, right_column, right_row):
+        lc, lr, rc, rr = int(left_column), int(left_row), int(right_column), int(right_row)
+        if not (0 <= lc < self.n_columns and 0 <= rc < self.n_columns):        # :55-64 ColumnNotInPermutation
+            raise ValueError("column not in the permutation")
+        if not (0 <= lr < self.n and 0 <= rr < self.n):                        # :67-71 BoundsFailure
+            raise ValueError("row out of bounds")
+        mapping, aux, sizes = self.mapping, self.aux, self.sizes
+        left = (int(aux[lc, lr, 0]), int(aux[lc, lr, 1]))                      # :75-76
+        right = (int(aux[rc, rr, 0]), int(aux[rc, rr, 1]))
+        if left == right:                                                      # :79-81
+            return
+        if sizes[left] < sizes[right]:                                         # :83-85
+            left, right = right, left
+        sizes[left] += sizes[right]                                            # :88
+        i = right                                                              # :89-96
+        while True:
+            aux[i[0], i[1]] = left
+            i = (int(mapping[i[0], i[1], 0]), int(mapping[i[0], i[1], 1]))
+            if i == right:
+                break
+        tmp = mapping[lc, lr].copy()                                           # :98-100: the cells named in the call
+        mapping[lc, lr] = mapping[rc, rr]
+        mapping[rc, rr] = tmp
+
+
+def _domain_args(domain):
+    return (ctypes.c_uint32(domain.k), _p(domain.omega), _p(domain.omega_inv), _p(domain.ifft_divisor), ctypes.c_uint32(domain.extended_k),
+            _p(domain.extended_omega), _p(domain.g_coset), _p(domain.g_coset_inv))
+
+
+_KEYGEN_FORMS = ("permutations", "polys", "cosets")
+
+
+def _keygen_want(want):
+    want = tuple(want)
+    for w in want:
+        if w not in _KEYGEN_FORMS:
+            raise ValueError("want: unknown form %r" % (w,))
+    return want
+
+
+def permutation_keygen(domain, mapping, want=_KEYGEN_FORMS, delta=None):
+    """Assembly::build_vk / build_pk's columns (plonk/permutation/keygen.rs:105-242) from `mapping`, an (m, 2^k, 2) uint32 array of
+    (column, row) pairs: a dict with the forms named in `want`, each a list of m columns -- permutations (2^k, 4), polys (2^k, 4),
+    cosets (2^extended_k, 4).  delta defaults to Fr::DELTA."""
+    want = _keygen_want(want)
+    mp = np.ascontiguousarray(mapping, dtype=np.uint32)
+    n = 1 << int(domain.k)
+    if mp.ndim != 3 or mp.shape[1:] != (n, 2):
+        raise ValueError("mapping: expected shape (m, %d, 2), got %s" % (n, mp.shape))
+    m = mp.shape[0]
+    rows = [mp[j] for j in range(m)]
+    sizes = {"permutations": n, "polys": n, "cosets": domain.extended_len()}
+    out = {w: [np.zeros((sizes[w], 4), dtype=np.uint64) for _ in range(m)] for w in want}
+    tabs = [(_host_ptrs(out[w]) if w in out else None) for w in _KEYGEN_FORMS]
+    d = fr_from_int(FR_DELTA) if delta is None else _fe(delta)
+    _check(lib().h2hip_permutation_keygen_bn254(*_domain_args(domain), _p(d), _host_ptrs(rows), ctypes.c_uint32(m), *tabs),
+           "h2hip_permutation_keygen_bn254")
+    return out
+
+
+def _assigned_args(rat_rows, rat_denoms, m):
+    rat_rows = [None] * m if rat_rows is None else list(rat_rows)
+    rat_denoms = [None] * m if rat_denoms is None else list(rat_denoms)
+    if len(rat_rows) != m or len(rat_denoms) != m:
+        raise ValueError("rat_rows / rat_denoms: one entry per column")
+    return rat_rows, rat_denoms
+
+
+def batch_invert_assigned(k, numerators, rat_rows=None, rat_denoms=None, in_place=False):
+    """batch_invert_assigned (poly.rs:180-209): numerators[j] (2^k, 4); rat_rows[j] the ascending uint32 rows of column j's Rational
+    cells and rat_denoms[j] (count, 4) their denominators (None: none).  Returns the list of inverted columns; with in_place the
+    numerators (contiguous uint64 arrays) are overwritten and returned (out == numerators at the ABI)."""
+    n = 1 << int(k)
+    nums = _cols(numerators, n, "numerators")
+    m = len(nums)
+    rat_rows, rat_denoms = _assigned_args(rat_rows, rat_denoms, m)
+    rows, dens, counts = [], [], []
+    for j in range(m):
+        r = np.zeros(0, dtype=np.uint32) if rat_rows[j] is None else np.ascontiguousarray(rat_rows[j], dtype=np.uint32).reshape(-1)
+        dn = np.zeros((0, 4), dtype=np.uint64) if rat_denoms[j] is None else np.ascontiguousarray(_u64(rat_denoms[j]).reshape(-1, 4))
+        if r.shape[0] != dn.shape[0]:
+            raise ValueError("column %d: %d rows but %d denominators" % (j, r.shape[0], dn.shape[0]))
+        rows.append(r)
+        dens.append(dn)
+        counts.append(r.shape[0])
+    if in_place:
+        if any(a is not b for a, b in zip(nums, numerators)):
+            raise ValueError("in_place needs contiguous uint64 numerators")
+        outs = nums
+    else:
+        outs = [np.zeros((n, 4), dtype=np.uint64) for _ in range(m)]
+    rp = (ctypes.c_void_p * max(1, m))(*[(r.ctypes.data if r.shape[0] else None) for r in rows])
+    dp = (ctypes.c_void_p * max(1, m))(*[(d.ctypes.data if d.shape[0] else None) for d in dens])
+    cnt = (ctypes.c_size_t * max(1, m))(*counts)
+    _check(lib().h2hip_batch_invert_assigned_bn254(ctypes.c_uint32(k), _host_ptrs(nums), rp, cnt, dp, ctypes.c_size_t(m), _host_ptrs(outs)),
+           "h2hip_batch_invert_assigned_bn254")
+    return outs
+
+
+def key_lagrange_columns(domain, blinding_factors):
+    """pk.l0, pk.l_last, pk.l_active_row (plonk/keygen.rs:320-351): three (2^extended_k, 4) columns"""
+    cols = [np.zeros((domain.extended_len(), 4), dtype=np.uint64) for _ in range(3)]
+    _check(lib().h2hip_key_lagrange_columns_bn254(ctypes.c_uint32(domain.k), _p(domain.omega_inv), _p(domain.ifft_divisor),
+                                                  ctypes.c_uint32(domain.extended_k), _p(domain.extended_omega), _p(domain.g_coset),
+                                                  _p(domain.g_coset_inv), ctypes.c_uint32(blinding_factors), _p(cols[0]), _p(cols[1]), _p(cols[2])),
+           "h2hip_key_lagrange_columns_bn254")
+    return tuple(cols)
+
+
+def keygen_columns(params, domain, fixed, mapping, blinding_factors, delta=None):
+    """The columns of keygen_vk + keygen_pk (plonk/keygen.rs:203-367) that are data-parallel, composed from the calls above: `fixed` is
+    a list of (2^k, 4) Lagrange columns (batch_invert_assigned and compress_selectors applied), or of
+    (numerators, rat_rows, rat_denoms) triples, which are inverted here (:298); mapping is the assembly's.  Returns a dict under the names
+    evaluation.py's describe() takes -- fixed_cosets, perm_cosets, l0, l_last, l_active_row -- plus fixed_values, fixed_polys,
+    fixed_commitments, permutations (the list permutation_products takes), perm_polys, permutation_commitments (Jacobian (12,) uint64)."""
+    k, n = int(domain.k), 1 << int(domain.k)
+    fixed = list(fixed)
+    if fixed and isinstance(fixed[0], tuple):
+        fixed_values = batch_invert_assigned(k, [f[0] for f in fixed], [f[1] for f in fixed], [f[2] for f in fixed])
+    else:
+        fixed_values = _cols(fixed, n, "fixed")
+    fixed_polys = domain.lagrange_to_coeff_batch(fixed_values)                      # :306-309
+    fixed_cosets = domain.coeff_to_extended_batch(fixed_polys)                      # :311-314
+    perm = permutation_keygen(domain, mapping, delta=delta)                         # :316-318
+    l0, l_last, l_active_row = key_lagrange_columns(domain, blinding_factors)       # :320-351
+    commit = lambda cols: list(best_multiexp_batch(cols, params.g_lagrange)) if cols else []
+    return {"fixed_values": fixed_values, "fixed_polys": fixed_polys, "fixed_cosets": fixed_cosets,
+            "fixed_commitments": commit(fixed_values),                              # keygen_vk :235-243
+            "permutations": perm["permutations"], "perm_polys": perm["polys"], "perm_cosets": perm["cosets"],
+            "permutation_commitments": commit(perm["permutations"]),                # build_vk :153-162
+            "l0": l0, "l_last": l_last, "l_active_row": l_active_row}
+
+
 # ------------------------------------------------------------------ opening: query evaluations and the KZG multiopen quotients
 def _fes(values, what):
     """a list of field elements ((4,) uint64 Montgomery limbs each) or an (m, 4) array -> a contiguous (max(1, m), 4) array, and m"""
@@ -1017,6 +1168,44 @@ def lookup_sort_stats():
     out = (ctypes.c_uint32 * 2)()
     _check(lib().h2hip_debug_lookup_sort_stats(out), "h2hip_debug_lookup_sort_stats")
     return int(out[0]), int(out[1])
+
+
+def _opt_ptr_array(tensors):
+    return None if tensors is None else _ptr_array(tensors)
+
+
+def permutation_keygen_device(domain, d_mapping, d_permutations=None, d_polys=None, d_cosets=None, delta=None):
+    """permutation_keygen over torch CUDA tensors: d_mapping[j] holds 2^k (column, row) uint32 pairs (8 B per cell); each output is a list
+    of m tensors (2^k x 32 B; cosets 2^extended_k x 32 B) or None.  Queued on the current stream, which the call waits for once at its end
+    (the out-of-range flag)."""
+    d = fr_from_int(FR_DELTA) if delta is None else _fe(delta)
+    _check(lib().h2hip_permutation_keygen_bn254_device(*_domain_args(domain), _p(d), _ptr_array(d_mapping), ctypes.c_uint32(len(d_mapping)),
+                                                       _opt_ptr_array(d_permutations), _opt_ptr_array(d_polys), _opt_ptr_array(d_cosets),
+                                                       _stream()), "h2hip_permutation_keygen_bn254_device")
+
+
+def batch_invert_assigned_device(k, d_numerators, d_rat_rows, rat_counts, d_rat_denoms, d_out):
+    """batch_invert_assigned over torch CUDA tensors; d_rat_rows[j] / d_rat_denoms[j] may be None where rat_counts[j] == 0; d_out[j] may
+    be d_numerators[j].  Queued on the current stream, not waited for."""
+    m = len(d_numerators)
+    opt = lambda ts: (ctypes.c_void_p * max(1, m))(*[(None if t is None else t.data_ptr()) for t in ts])
+    cnt = (ctypes.c_size_t * max(1, m))(*[int(x) for x in rat_counts])
+    _check(lib().h2hip_batch_invert_assigned_bn254_device(ctypes.c_uint32(k), _ptr_array(d_numerators), opt(d_rat_rows), cnt, opt(d_rat_denoms),
+                                                          ctypes.c_size_t(m), _ptr_array(d_out), _stream()),
+           "h2hip_batch_invert_assigned_bn254_device")
+
+
+def key_lagrange_columns_device(domain, blinding_factors, d_l0, d_l_last, d_l_active_row):
+    """key_lagrange_columns into three torch CUDA tensors of 2^extended_k x 32 B; queued on the current stream, not waited for"""
+    _check(lib().h2hip_key_lagrange_columns_bn254_device(ctypes.c_uint32(domain.k), _p(domain.omega_inv), _p(domain.ifft_divisor),
+                                                         ctypes.c_uint32(domain.extended_k), _p(domain.extended_omega), _p(domain.g_coset),
+                                                         _p(domain.g_coset_inv), ctypes.c_uint32(blinding_factors), _dptr(d_l0), _dptr(d_l_last),
+                                                         _dptr(d_l_active_row), _stream()), "h2hip_key_lagrange_columns_bn254_device")
+
+
+def set_keygen_group(group_bytes=0):
+    """test hook: the HBM one group of columns of a host-pointer keygen call takes (0 = default), so that small inputs run several groups"""
+    _check(lib().h2hip_debug_set_keygen_group(ctypes.c_uint64(group_bytes)), "h2hip_debug_set_keygen_group")
 
 
 def gen_scalars_device(seed, n, start=0, device="cuda"):

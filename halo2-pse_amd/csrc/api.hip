@@ -960,6 +960,9 @@ static void release_ctx(Ctx* c) {
     c->lookup_ws.release();
     c->lookup_io.release();
     c->lookup_flag.release();
+    c->keygen_ws.release();
+    c->keygen_io.release();
+    c->keygen_flag.release();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     c->stream = nullptr;
     for (auto e : c->aux_events) (void)hipEventDestroy(e);

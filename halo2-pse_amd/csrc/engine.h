@@ -158,6 +158,8 @@ struct Ctx {
     DevBuf open_ws, open_io;       // opening.hip: scans' workspace and tables; evaluations and the host-pointer forms' columns
     DevBuf lookup_ws, lookup_io;   // lookup.hip: sort keys, marks and scans; the host-pointer forms' columns
     HostBuf lookup_flag;           // lookup.hip: the per-lookup not-found flags read back at the end of a permute call
+    DevBuf keygen_ws, keygen_io;   // keygen.hip: power tables, flag, pointer blobs and inverses; the host-pointer forms' columns
+    HostBuf keygen_flag;           // keygen.hip: the out-of-range flag of a permutation keygen read back at the end of the call
     HostBuf host_ws;               // pinned host memory for the window sums coming back
     HostBuf host_planes;           // ... and for the bit-plane sums of a run whose tail the host finishes (msm.hip msm_planes_finish)
     HostBuf pin_flag;              // one word the device-key fingerprint check writes its verdict to

@@ -8,6 +8,8 @@
 //   halo2_proofs::poly::EvaluationDomain         halo2_proofs/src/poly/domain.rs:18-361
 //   halo2_proofs::poly::kzg::ParamsKZG           halo2_proofs/src/poly/kzg/commitment.rs:22-339
 //   halo2_proofs::plonk::{GraphEvaluator, Evaluator}   halo2_proofs/src/plonk/evaluation.rs   (in evaluation.hpp)
+//   halo2_proofs::plonk::permutation::keygen::Assembly, batch_invert_assigned, keygen_pk's columns
+//                                                halo2_proofs/src/plonk/permutation/keygen.rs, poly.rs:180-209, plonk/keygen.rs:298-366
 //
 // Error behaviour: where the reference panics on a contract violation (assert_eq! / assert!),
 // this mirror throws std::logic_error; a non-zero engine status throws std::runtime_error
@@ -20,6 +22,7 @@
 #include <istream>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/halo2hip.h"
@@ -585,6 +588,152 @@ inline std::vector<std::pair<poly::Polynomial<poly::LagrangeCoeff>, poly::Polyno
     if (rc == H2HIP_ELOOKUP) throw std::domain_error(std::string("lookup_permute: ") + h2hip_last_error());
     engine_check(rc, "lookup_permute");
     return out;
+}
+
+// batch_invert_assigned (poly.rs:180-209).  Assigned<F> (plonk/assigned.rs): Zero, Trivial(x) or Rational(numerator, denominator).
+struct Assigned {
+    enum Kind { Zero, Trivial, Rational } kind = Zero;
+    Fr numerator = Fr::zero(), denominator = Fr::one();
+    static Assigned trivial(const Fr& x) { return {Trivial, x, Fr::one()}; }
+    static Assigned rational(const Fr& n, const Fr& d) { return {Rational, n, d}; }
+};
+
+inline std::vector<poly::Polynomial<poly::LagrangeCoeff>> batch_invert_assigned(const poly::EvaluationDomain& domain,
+                                                                                const std::vector<std::vector<Assigned>>& assigned) {
+    const size_t m = assigned.size();
+    std::vector<poly::Polynomial<poly::LagrangeCoeff>> out(m);
+    std::vector<std::vector<uint32_t>> rows(m);
+    std::vector<std::vector<Fr>> denoms(m);
+    std::vector<const uint32_t*> rp(m);
+    std::vector<const uint64_t*> np(m), dp(m);
+    std::vector<uint64_t*> op(m);
+    std::vector<size_t> counts(m);
+    for (size_t j = 0; j < m; j++) {
+        if (assigned[j].size() != domain.n) throw std::logic_error("column length != n");
+        out[j].values.resize(domain.n);
+        for (size_t i = 0; i < domain.n; i++) {
+            const Assigned& a = assigned[j][i];
+            out[j].values[i] = a.kind == Assigned::Zero ? Fr::zero() : a.numerator;  // numerator(), assigned.rs
+            if (a.kind == Assigned::Rational) {                                       // denominator() is Some: :183-200
+                rows[j].push_back(uint32_t(i));
+                denoms[j].push_back(a.denominator);
+            }
+        }
+        counts[j] = rows[j].size();
+        rp[j] = rows[j].data();
+        dp[j] = denoms[j].empty() ? nullptr : denoms[j][0].l;
+        np[j] = op[j] = out[j].values[0].l;  // in place: out == numerators
+    }
+    engine_check(h2hip_batch_invert_assigned_bn254(domain.k, np.data(), rp.data(), counts.data(), dp.data(), m, op.data()), "batch_invert_assigned");
+    return out;
+}
+
+namespace permutation {
+struct ProvingKey {  // plonk/permutation.rs ProvingKey
+    std::vector<poly::Polynomial<poly::LagrangeCoeff>> permutations;
+    std::vector<poly::Polynomial<poly::Coeff>> polys;
+    std::vector<poly::Polynomial<poly::ExtendedLagrangeCoeff>> cosets;
+};
+struct VerifyingKey {
+    std::vector<G1Affine> commitments;
+};
+
+namespace keygen {
+// permutation::keygen::Assembly (plonk/permutation/keygen.rs:16-242); columns are the argument's column indices
+struct Assembly {
+    using Cell = std::pair<uint32_t, uint32_t>;
+    std::vector<std::vector<Cell>> mapping, aux;
+    std::vector<std::vector<size_t>> sizes;
+
+    Assembly(size_t n, size_t n_columns) {  // :28-46
+        for (size_t i = 0; i < n_columns; i++) {
+            std::vector<Cell> col;
+            for (size_t j = 0; j < n; j++) col.push_back({uint32_t(i), uint32_t(j)});
+            mapping.push_back(col);
+        }
+        aux = mapping;
+        sizes.assign(n_columns, std::vector<size_t>(n, 1));
+    }
+
+    void copy(size_t left_column, size_t left_row, size_t right_column, size_t right_row) {  // :48-103
+        if (left_column >= mapping.size() || right_column >= mapping.size()) throw std::out_of_range("ColumnNotInPermutation");
+        if (left_row >= mapping[left_column].size() || right_row >= mapping[right_column].size()) throw std::out_of_range("BoundsFailure");  // :67-71
+        Cell left_cycle = aux[left_column][left_row], right_cycle = aux[right_column][right_row];  // :75-76
+        if (left_cycle == right_cycle) return;                                                      // :79-81
+        if (sizes[left_cycle.first][left_cycle.second] < sizes[right_cycle.first][right_cycle.second]) std::swap(left_cycle, right_cycle);
+        sizes[left_cycle.first][left_cycle.second] += sizes[right_cycle.first][right_cycle.second];  // :88
+        Cell i = right_cycle;                                                                       // :89-96
+        do {
+            aux[i.first][i.second] = left_cycle;
+            i = mapping[i.first][i.second];
+        } while (i != right_cycle);
+        std::swap(mapping[left_column][left_row], mapping[right_column][right_row]);                // :98-100
+    }
+
+    // build_vk (:105-165): the sigma columns on the engine, committed in Lagrange form as one batch
+    VerifyingKey build_vk(const poly::kzg::ParamsKZG& params, const poly::EvaluationDomain& domain) const {
+        ProvingKey pk = build(domain, true, false, false);
+        std::vector<const poly::Polynomial<poly::LagrangeCoeff>*> ptrs;
+        for (auto& c : pk.permutations) ptrs.push_back(&c);
+        VerifyingKey vk;
+        for (auto& c : params.commit_lagrange_many(ptrs)) vk.commitments.push_back(c.to_affine());  // :153-162
+        return vk;
+    }
+
+    // build_pk (:167-242)
+    ProvingKey build_pk(const poly::EvaluationDomain& domain) const { return build(domain, true, true, true); }
+
+   private:
+    ProvingKey build(const poly::EvaluationDomain& domain, bool perms, bool polys, bool cosets) const {
+        const size_t m = mapping.size();
+        static_assert(sizeof(Cell) == 8, "a (column, row) pair is two interleaved uint32_t");
+        ProvingKey pk;
+        std::vector<const uint32_t*> mp(m);
+        std::vector<uint64_t*> a(m), b(m), c(m);
+        if (perms) pk.permutations.resize(m);
+        if (polys) pk.polys.resize(m);
+        if (cosets) pk.cosets.resize(m);
+        for (size_t j = 0; j < m; j++) {
+            if (mapping[j].size() != domain.n) throw std::logic_error("mapping column length != n");
+            mp[j] = &mapping[j][0].first;
+            if (perms) pk.permutations[j].values.resize(domain.n), a[j] = pk.permutations[j].values[0].l;
+            if (polys) pk.polys[j].values.resize(domain.n), b[j] = pk.polys[j].values[0].l;
+            if (cosets) pk.cosets[j].values.resize(domain.extended_len()), c[j] = pk.cosets[j].values[0].l;
+        }
+        Fr delta = Fr::delta();
+        engine_check(h2hip_permutation_keygen_bn254(domain.k, domain.omega.l, domain.omega_inv.l, domain.ifft_divisor.l, domain.extended_k,
+                                                    domain.extended_omega.l, domain.g_coset.l, domain.g_coset_inv.l, delta.l, mp.data(), uint32_t(m),
+                                                    perms ? a.data() : nullptr, polys ? b.data() : nullptr, cosets ? c.data() : nullptr),
+                     "permutation_keygen");
+        return pk;
+    }
+};
+}  // namespace keygen
+}  // namespace permutation
+
+// The columns of plonk::ProvingKey that keygen_pk computes (plonk/keygen.rs:298-366), given what synthesis left behind: the fixed columns
+// as Assigned values and the permutation assembly
+struct ProvingKeyColumns {
+    poly::Polynomial<poly::ExtendedLagrangeCoeff> l0, l_last, l_active_row;
+    std::vector<poly::Polynomial<poly::LagrangeCoeff>> fixed_values;
+    std::vector<poly::Polynomial<poly::Coeff>> fixed_polys;
+    std::vector<poly::Polynomial<poly::ExtendedLagrangeCoeff>> fixed_cosets;
+    permutation::ProvingKey permutation;
+};
+
+inline ProvingKeyColumns keygen_pk(const poly::EvaluationDomain& domain, const std::vector<std::vector<Assigned>>& fixed,
+                                   const permutation::keygen::Assembly& assembly, size_t blinding_factors) {
+    ProvingKeyColumns pk;
+    pk.fixed_values = batch_invert_assigned(domain, fixed);                    // :298
+    pk.fixed_polys = domain.lagrange_to_coeff_batch(pk.fixed_values);          // :306-309
+    pk.fixed_cosets = domain.coeff_to_extended_batch(pk.fixed_polys);          // :311-314
+    pk.permutation = assembly.build_pk(domain);                                // :316-318
+    for (auto* c : {&pk.l0, &pk.l_last, &pk.l_active_row}) c->values.resize(domain.extended_len());
+    engine_check(h2hip_key_lagrange_columns_bn254(domain.k, domain.omega_inv.l, domain.ifft_divisor.l, domain.extended_k, domain.extended_omega.l,
+                                                  domain.g_coset.l, domain.g_coset_inv.l, uint32_t(blinding_factors), pk.l0.values[0].l,
+                                                  pk.l_last.values[0].l, pk.l_active_row.values[0].l),
+                 "key_lagrange_columns");                                      // :320-351
+    return pk;
 }
 
 }  // namespace plonk

@@ -435,3 +435,98 @@ pub fn try_div_by_vanishing<F: Field + 'static>(a: &[F], roots: &[F]) -> Option<
     }
     try_poly_combine(&[a], &[F::one()], &[], roots, &F::one(), a.len() - roots.len())
 }
+
+/// The domain constants the keygen entry points take, as `EvaluationDomain` holds them (poly/domain.rs:18-34).
+pub struct KeygenDomain<'a, F> {
+    pub k: u32,
+    pub extended_k: u32,
+    pub omega: &'a F,
+    pub omega_inv: &'a F,
+    pub ifft_divisor: &'a F,
+    pub extended_omega: &'a F,
+    pub g_coset: &'a F,
+    pub g_coset_inv: &'a F,
+}
+
+/// What `try_permutation_keygen` returns: the forms that were asked for, one column per permutation column.
+pub struct PermutationKeyColumns<F> {
+    pub permutations: Option<Vec<Vec<F>>>,
+    pub polys: Option<Vec<Vec<F>>>,
+    pub cosets: Option<Vec<Vec<F>>>,
+}
+
+/// `Assembly::build_vk` / `build_pk`'s columns (plonk/permutation/keygen.rs:105-242) from `Assembly::mapping`, flattened per column to
+/// `(column, row)` pairs of `u32`: `permutations[j][i] = delta^c omega^r`, its `lagrange_to_coeff` and its `coeff_to_extended`.
+/// `want = (permutations, polys, cosets)`; build_vk asks for the first alone.  `None` on any failure (the CPU body then runs).
+pub fn try_permutation_keygen<F: Field + 'static>(domain: &KeygenDomain<F>, delta: &F, mapping: &[&[[u32; 2]]],
+                                                  want: (bool, bool, bool)) -> Option<PermutationKeyColumns<F>> {
+    let (k, ek) = (domain.k, domain.extended_k);
+    if !is::<F, Fr>() || !layout_ok() || k > ek || ek > 28 || mapping.len() > 65535 {
+        return None;
+    }
+    let (n, len, m) = (1usize << k, 1usize << ek, mapping.len());
+    if mapping.iter().any(|c| c.len() != n) {
+        return None;
+    }
+    let mp: Vec<*const u32> = mapping.iter().map(|c| c.as_ptr() as *const u32).collect();
+    let alloc = |on: bool, rows: usize| -> Option<Vec<Vec<F>>> { if on { Some((0..m).map(|_| vec![F::zero(); rows]).collect()) } else { None } };
+    let (mut perms, mut polys, mut cosets) = (alloc(want.0, n), alloc(want.1, n), alloc(want.2, len));
+    let table = |cols: &mut Option<Vec<Vec<F>>>| -> Vec<*mut u64> {
+        cols.as_mut().map(|v| v.iter_mut().map(|c| c.as_mut_ptr() as *mut u64).collect()).unwrap_or_default()
+    };
+    let (pp, qp, cp) = (table(&mut perms), table(&mut polys), table(&mut cosets));
+    let arg = |t: &Vec<*mut u64>, on: bool| if on { t.as_ptr() } else { std::ptr::null() };
+    let rc = unsafe {
+        ffi::h2hip_permutation_keygen_bn254(k, fr_ptr(domain.omega), fr_ptr(domain.omega_inv), fr_ptr(domain.ifft_divisor), ek,
+                                            fr_ptr(domain.extended_omega), fr_ptr(domain.g_coset), fr_ptr(domain.g_coset_inv), fr_ptr(delta),
+                                            mp.as_ptr(), m as u32, arg(&pp, want.0), arg(&qp, want.1), arg(&cp, want.2))
+    };
+    if rc != 0 {
+        return None;
+    }
+    Some(PermutationKeyColumns { permutations: perms, polys, cosets })
+}
+
+/// `batch_invert_assigned` (poly.rs:180-209) over columns the caller has flattened from `Assigned<F>`: `numerators[j]` (zero for `Zero`,
+/// `x` for `Trivial(x)`), and for the `Rational` cells their ascending rows `rat_rows[j]` and denominators `rat_denoms[j]`.  One
+/// inversion over all columns.  `None` on any failure.
+pub fn try_batch_invert_assigned<F: Field + 'static>(k: u32, numerators: &[&[F]], rat_rows: &[&[u32]], rat_denoms: &[&[F]]) -> Option<Vec<Vec<F>>> {
+    let m = numerators.len();
+    if !is::<F, Fr>() || !layout_ok() || k > 28 || rat_rows.len() != m || rat_denoms.len() != m {
+        return None;
+    }
+    let n = 1usize << k;
+    if numerators.iter().any(|c| c.len() != n) || rat_rows.iter().zip(rat_denoms.iter()).any(|(r, d)| r.len() != d.len() || r.len() > n) {
+        return None;
+    }
+    let np: Vec<*const u64> = numerators.iter().map(|c| c.as_ptr() as *const u64).collect();
+    let rp: Vec<*const u32> = rat_rows.iter().map(|c| if c.is_empty() { std::ptr::null() } else { c.as_ptr() }).collect();
+    let dp: Vec<*const u64> = rat_denoms.iter().map(|c| if c.is_empty() { std::ptr::null() } else { c.as_ptr() as *const u64 }).collect();
+    let counts: Vec<usize> = rat_rows.iter().map(|c| c.len()).collect();
+    let mut out: Vec<Vec<F>> = (0..m).map(|_| vec![F::zero(); n]).collect();
+    let op: Vec<*mut u64> = out.iter_mut().map(|c| c.as_mut_ptr() as *mut u64).collect();
+    let rc = unsafe { ffi::h2hip_batch_invert_assigned_bn254(k, np.as_ptr(), rp.as_ptr(), counts.as_ptr(), dp.as_ptr(), m, op.as_ptr()) };
+    if rc != 0 {
+        return None;
+    }
+    Some(out)
+}
+
+/// `pk.l0`, `pk.l_last`, `pk.l_active_row` (plonk/keygen.rs:320-351) in extended-coset form.  `None` on any failure.
+pub fn try_key_lagrange_columns<F: Field + 'static>(domain: &KeygenDomain<F>, blinding_factors: usize) -> Option<(Vec<F>, Vec<F>, Vec<F>)> {
+    let (k, ek) = (domain.k, domain.extended_k);
+    if !is::<F, Fr>() || !layout_ok() || k > ek || ek > 28 || blinding_factors + 1 >= 1usize << k {
+        return None;
+    }
+    let len = 1usize << ek;
+    let (mut l0, mut l_last, mut l_active_row) = (vec![F::zero(); len], vec![F::zero(); len], vec![F::zero(); len]);
+    let rc = unsafe {
+        ffi::h2hip_key_lagrange_columns_bn254(k, fr_ptr(domain.omega_inv), fr_ptr(domain.ifft_divisor), ek, fr_ptr(domain.extended_omega),
+                                              fr_ptr(domain.g_coset), fr_ptr(domain.g_coset_inv), blinding_factors as u32,
+                                              l0.as_mut_ptr() as *mut u64, l_last.as_mut_ptr() as *mut u64, l_active_row.as_mut_ptr() as *mut u64)
+    };
+    if rc != 0 {
+        return None;
+    }
+    Some((l0, l_last, l_active_row))
+}

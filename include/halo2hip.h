@@ -427,6 +427,56 @@ int h2hip_poly_combine_bn254_fr_device(const void* const* d_polys, size_t len, c
                                        size_t sub_len, const uint64_t* roots, size_t n_roots, const uint64_t scale[4], uint32_t accumulate,
                                        void* d_out, size_t out_len, uint64_t* remainder, void* stream);
 
+/* ---- keygen: the data-parallel columns of keygen_vk / keygen_pk (plonk/keygen.rs:203-367, plonk/permutation/keygen.rs:105-242) and
+ * batch_invert_assigned (poly.rs:180-209), which the prover also applies to every advice column (plonk/prover.rs:334) ------------------
+ * n = 2^k; the domain constants are the EvaluationDomain's (poly/domain.rs:18-34), passed as h2hip_ifft_bn254_fr and
+ * h2hip_coeff_to_extended_bn254_fr take them; k <= extended_k <= 28.
+ * Permutation key (Assembly::build_vk :105-165, build_pk :167-242): mapping[j] is Assembly::mapping[j], 2^k (column, row) pairs as
+ * interleaved uint32_t (8 bytes per cell), n_columns <= 65535.  Each of the three output tables holds n_columns pointers and may be NULL as a whole:
+ *   permutations[j][i] = delta^c omega^r, (c, r) = mapping[j][i]      Lagrange form, 2^k elements (:111-151, :173-212);
+ *   polys[j]  = lagrange_to_coeff(permutations[j])                   2^k elements (:214-223);
+ *   cosets[j] = coeff_to_extended(polys[j])                          2^extended_k elements (:225-234).
+ * With only permutations this is build_vk's table (its commitments are one h2hip_msm_bn254_batch over the pinned g_lagrange), with all
+ * three build_pk.  Every element is the reduced Montgomery representative the reference stores.  A pair with column >= n_columns or
+ * row >= 2^k is H2HIP_EINVAL: the host form finds it before any device work and names it; the _device form raises a flag in the kernel,
+ * takes that cell's sigma value as zero, and synchronises `stream` once at the end of the call to read it.  After such a call permutations
+ * is complete but for the zero at that cell, and polys / cosets are the transforms of that column with the zero in it: not a key.
+ * n_columns == 0, or all three tables NULL, writes nothing.  Host form: only the mapping is uploaded; the columns are built, transformed
+ * and downloaded in groups (bounded HBM whatever n_columns is), the download of one group under the work of the next.  _device form:
+ * mapping[j] and the outputs are device pointers, no output aliases another or the mapping; the pointer tables and scalars are host
+ * memory read before the call returns; kernels are queued on `stream`. */
+int h2hip_permutation_keygen_bn254(uint32_t k, const uint64_t omega[4], const uint64_t omega_inv[4], const uint64_t ifft_divisor[4],
+                                   uint32_t extended_k, const uint64_t extended_omega[4], const uint64_t g_coset[4], const uint64_t g_coset_inv[4],
+                                   const uint64_t delta[4], const uint32_t* const* mapping, uint32_t n_columns, uint64_t* const* permutations,
+                                   uint64_t* const* polys, uint64_t* const* cosets);
+int h2hip_permutation_keygen_bn254_device(uint32_t k, const uint64_t omega[4], const uint64_t omega_inv[4], const uint64_t ifft_divisor[4],
+                                          uint32_t extended_k, const uint64_t extended_omega[4], const uint64_t g_coset[4],
+                                          const uint64_t g_coset_inv[4], const uint64_t delta[4], const void* const* d_mapping, uint32_t n_columns,
+                                          void* const* d_permutations, void* const* d_polys, void* const* d_cosets, void* stream);
+/* batch_invert_assigned (poly.rs:180-209).  Rust's Assigned<F> has no stable layout, so per column j: numerators[j], 2^k elements (zero for
+ * Zero, x for Trivial(x), the numerator for Rational); rat_rows[j], the rat_counts[j] strictly ascending row indices of its Rational cells;
+ * rat_denoms[j], their denominators (rat_counts NULL, or a count of 0 with NULL arrays: no Rational cell).  out[j][i] = numerators[j][i],
+ * except out[j][rat_rows[j][t]] = numerator * inv(rat_denoms[j][t]), where a zero denominator inverts to zero as ff's BatchInvert leaves it
+ * (Assigned evaluates x / 0 to 0).  One inversion over the denominators of all columns together (:192-200; at most 2^30 of them).
+ * out[j] may equal numerators[j].  Host form: rows out of range or not ascending and unreduced denominators are H2HIP_EINVAL; the
+ * numerators are not examined, and a column without a Rational cell is copied on the host (its out[j] == numerators[j]: not touched) and
+ * never crosses PCIe.  _device form: every array is a device pointer (the tables and rat_counts are host memory); the rows are
+ * the caller's contract, an index >= 2^k is skipped; queued on `stream`, not waited for. */
+int h2hip_batch_invert_assigned_bn254(uint32_t k, const uint64_t* const* numerators, const uint32_t* const* rat_rows, const size_t* rat_counts,
+                                      const uint64_t* const* rat_denoms, size_t n_columns, uint64_t* const* out);
+int h2hip_batch_invert_assigned_bn254_device(uint32_t k, const void* const* d_numerators, const void* const* d_rat_rows, const size_t* rat_counts,
+                                             const void* const* d_rat_denoms, size_t n_columns, void* const* d_out, void* stream);
+/* pk.l0, pk.l_last, pk.l_active_row (plonk/keygen.rs:320-351), 2^extended_k elements each: coeff_to_extended(lagrange_to_coeff(.)) of the
+ * Lagrange columns e_0 and e_u (u = 2^k - blinding_factors - 1), and 1 - (l_last + l_blind) with l_blind the same transform of the column
+ * that is one on the last blinding_factors rows (an intermediate, not returned).  blinding_factors + 1 < 2^k.  The _device form writes
+ * three device buffers, queues on `stream` and does not wait. */
+int h2hip_key_lagrange_columns_bn254(uint32_t k, const uint64_t omega_inv[4], const uint64_t ifft_divisor[4], uint32_t extended_k,
+                                     const uint64_t extended_omega[4], const uint64_t g_coset[4], const uint64_t g_coset_inv[4],
+                                     uint32_t blinding_factors, uint64_t* l0, uint64_t* l_last, uint64_t* l_active_row);
+int h2hip_key_lagrange_columns_bn254_device(uint32_t k, const uint64_t omega_inv[4], const uint64_t ifft_divisor[4], uint32_t extended_k,
+                                            const uint64_t extended_omega[4], const uint64_t g_coset[4], const uint64_t g_coset_inv[4],
+                                            uint32_t blinding_factors, void* d_l0, void* d_l_last, void* d_l_active_row, void* stream);
+
 /* ---- synthetic workload; same streams as oracle_gen_{scalars,points} ---- */
 
 int h2hip_gen_scalars_device(uint64_t seed, uint64_t start, size_t n, void* d_out, void* stream);

@@ -96,6 +96,9 @@ int h2hip_debug_set_opening_tile(uint32_t rows_per_thread, uint32_t threads_per_
  * passes; needs no GPU.  Stats: out[0] = the block and out[1] = the merge passes (log2(2^k / block)) of the last permute call. */
 int h2hip_debug_set_lookup_sort(uint32_t lds_keys);
 int h2hip_debug_lookup_sort_stats(uint32_t out[2]);
+/* keygen: the HBM one group of columns of a host-pointer h2hip_permutation_keygen_bn254 / h2hip_batch_invert_assigned_bn254 call may take
+ * (0 = default 1 GB), so that small inputs run several pipelined groups.  Needs no GPU. */
+int h2hip_debug_set_keygen_group(uint64_t group_bytes);
 
 #ifdef __cplusplus
 }
