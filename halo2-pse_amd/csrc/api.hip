@@ -26,35 +26,6 @@ static void lazy_pin_consider(const uint64_t* bases_xy, size_t n);
 
 namespace h2 {
 
-int gen_scalars_device(uint64_t seed, uint64_t start, size_t n, Fe* d_out, hipStream_t s);
-int gen_points_device(uint64_t seed, uint64_t start, size_t n, Affine* d_out, hipStream_t s);
-void msm_set_window(uint32_t c);
-void msm_set_max_chunk(size_t m);
-void msm_set_stream(uint32_t chunks, double ratio, size_t min_n);
-size_t msm_debug_ladder(size_t n, uint32_t chunks, double ratio, bool with_bases, size_t* out, size_t cap);
-void msm_set_heavy_div(size_t d);
-void msm_set_bin_entries(size_t d);
-void msm_set_split_records(bool on);
-void msm_set_bucket_order(int local);
-void msm_set_quad_tail(bool on);
-void msm_set_split_buckets(bool on);
-void msm_set_plane_tail(bool on);
-void ecfft_set_quad(bool on);
-void ecfft_set_lazy(bool on);
-void msm_set_fuse_limits(size_t entries, size_t max_n);
-void msm_set_rowcol(uint64_t lanes, uint32_t flavour);
-void ntt_set_smax(uint32_t v);
-void ntt_set_two_pass(uint32_t lo, uint32_t hi);
-void ntt_set_full_twiddle_budget(uint64_t bytes);
-void ntt_set_batch_bytes(uint64_t bytes);
-void ntt_set_two_pass_log_j(int v);
-void ntt_set_full_max_log_m(uint32_t v);
-void ntt_set_fold_tables(bool on);
-void ntt_set_two_pass_batch_wgs(uint64_t v);
-void msm_set_reserved_cus(uint32_t k);
-uint32_t msm_get_reserved_cus();
-uint32_t msm_get_window(size_t n);
-
 static thread_local char g_err[512] = "";
 
 void set_error(const char* fmt, ...) {
@@ -143,7 +114,7 @@ int Ctx::stage_h2d(void* d_dst, const void* h_src, size_t bytes, hipStream_t s) 
         if (rc) return rc;
         stage_off = 0;
     }
-    const size_t need = (bytes + 255) & ~(size_t)255;
+    const size_t need = align256(bytes);
     if (stage_off + need > ring) {  // wrap: copies queued from the old contents must have left the ring
         H2_CHECK(hipDeviceSynchronize());
         stage_off = 0;
@@ -708,12 +679,6 @@ int ensure_init() {
     return do_init(nullptr, 0);  // takes the engine lock exclusively; a second thread arriving here finds the engine ready
 }
 
-static inline Fe fe_from_u64x4(const uint64_t v[4]) {
-    Fe o;
-    memcpy(o.l, v, 32);
-    return o;
-}
-
 static inline void xyzz_to_out(const XYZZ& r, uint64_t out_xyz[12]) {
     Jac j = xyzz_to_jac(r);
     memcpy(out_xyz, &j, 96);
@@ -898,25 +863,6 @@ static int ntt_host_batch(const char* name, const uint64_t* const* in, size_t in
         return ntt_host_batch_on(x, in + lo, in_elems, out + lo, hi - lo, omega, log_n, sc);
     });
 }
-
-static void make_zeta_scale(NttScale* sc, bool into_coset, const uint64_t g_coset[4], const uint64_t g_coset_inv[4], const Fe* divisor) {
-    // distribute_powers_zeta (poly/domain.rs:335-351): a[i] *= [1, c0, c1][i % 3],
-    // (c0, c1) = (g_coset, g_coset_inv) into the coset, swapped on the way out
-    Fe c0 = fe_from_u64x4(into_coset ? g_coset : g_coset_inv);
-    Fe c1 = fe_from_u64x4(into_coset ? g_coset_inv : g_coset);
-    if (into_coset) {
-        sc->in_scale = true;
-        sc->in3[0] = fe_one<FrP>();
-        sc->in3[1] = c0;
-        sc->in3[2] = c1;
-    } else {
-        sc->out_scale = true;
-        sc->out3[0] = *divisor;
-        sc->out3[1] = fe_mul<FrP>(*divisor, c0);
-        sc->out3[2] = fe_mul<FrP>(*divisor, c1);
-    }
-}
-
 
 static void release_ctx(Ctx* c) {
     copier_stop(c);
@@ -1807,9 +1753,7 @@ int h2hip_ifft_bn254_fr_device(void* d_a, const uint64_t omega_inv[4], uint32_t 
     Entry en("h2hip_ifft_bn254_fr_device", d_a);
     if (en.rc) return en.rc;
     hipStream_t s = (hipStream_t)stream;
-    NttScale sc;
-    sc.out_scale = true;
-    sc.out3[0] = sc.out3[1] = sc.out3[2] = fe_from_u64x4(divisor);
+    NttScale sc = NttScale::inverse(fe_from_u64x4(divisor));
     return ntt_device(en.c, (Fe*)d_a, fe_from_u64x4(omega_inv), log_n, &sc, s);
 }
 
@@ -1819,9 +1763,7 @@ int h2hip_ifft_bn254_fr(uint64_t* a, const uint64_t omega_inv[4], uint32_t log_n
         return H2HIP_EINVAL;
     }
     if (check_fr(omega_inv, "omega_inv") || check_fr(divisor, "divisor")) return H2HIP_EINVAL;
-    NttScale sc;
-    sc.out_scale = true;
-    sc.out3[0] = sc.out3[1] = sc.out3[2] = fe_from_u64x4(divisor);
+    NttScale sc = NttScale::inverse(fe_from_u64x4(divisor));
     return ntt_host(a, fe_from_u64x4(omega_inv), log_n, &sc, nullptr, 0);
 }
 
@@ -1835,9 +1777,7 @@ int h2hip_coeff_to_extended_bn254_fr_device(void* d_a, uint32_t k, uint32_t exte
     Entry en("h2hip_coeff_to_extended_bn254_fr_device", d_a);
     if (en.rc) return en.rc;
     hipStream_t s = (hipStream_t)stream;
-    NttScale sc;
-    make_zeta_scale(&sc, true, g_coset, g_coset_inv, nullptr);
-    sc.in_len = 1ull << k;
+    NttScale sc = NttScale::into_coset(fe_from_u64x4(g_coset), fe_from_u64x4(g_coset_inv), 1ull << k);
     return ntt_device(en.c, (Fe*)d_a, fe_from_u64x4(extended_omega), extended_k, &sc, s);
 }
 
@@ -1848,9 +1788,7 @@ int h2hip_coeff_to_extended_bn254_fr(const uint64_t* a, uint32_t k, uint64_t* ou
         return H2HIP_EINVAL;
     }
     if (check_fr(extended_omega, "extended_omega") || check_fr(g_coset, "g_coset") || check_fr(g_coset_inv, "g_coset_inv")) return H2HIP_EINVAL;
-    NttScale sc;
-    make_zeta_scale(&sc, true, g_coset, g_coset_inv, nullptr);
-    sc.in_len = 1ull << k;
+    NttScale sc = NttScale::into_coset(fe_from_u64x4(g_coset), fe_from_u64x4(g_coset_inv), 1ull << k);
     return ntt_host(out, fe_from_u64x4(extended_omega), extended_k, &sc, a, (size_t)1 << k);
 }
 
@@ -1867,9 +1805,7 @@ int h2hip_extended_to_coeff_bn254_fr_device(void* d_a, uint32_t extended_k, cons
     Entry en("h2hip_extended_to_coeff_bn254_fr_device", d_a);
     if (en.rc) return en.rc;
     hipStream_t s = (hipStream_t)stream;
-    NttScale sc;
-    Fe div = fe_from_u64x4(extended_ifft_divisor);
-    make_zeta_scale(&sc, false, g_coset, g_coset_inv, &div);
+    NttScale sc = NttScale::out_of_coset(fe_from_u64x4(extended_ifft_divisor), fe_from_u64x4(g_coset), fe_from_u64x4(g_coset_inv));
     return ntt_device(en.c, (Fe*)d_a, fe_from_u64x4(extended_omega_inv), extended_k, &sc, s);
 }
 
@@ -1882,9 +1818,7 @@ int h2hip_extended_to_coeff_bn254_fr(uint64_t* a, uint32_t extended_k, const uin
     if (check_fr(extended_omega_inv, "extended_omega_inv") || check_fr(extended_ifft_divisor, "extended_ifft_divisor") ||
         check_fr(g_coset, "g_coset") || check_fr(g_coset_inv, "g_coset_inv"))
         return H2HIP_EINVAL;
-    NttScale sc;
-    Fe div = fe_from_u64x4(extended_ifft_divisor);
-    make_zeta_scale(&sc, false, g_coset, g_coset_inv, &div);
+    NttScale sc = NttScale::out_of_coset(fe_from_u64x4(extended_ifft_divisor), fe_from_u64x4(g_coset), fe_from_u64x4(g_coset_inv));
     return ntt_host(a, fe_from_u64x4(extended_omega_inv), extended_k, &sc, nullptr, 0);
 }
 
@@ -2010,9 +1944,7 @@ int h2hip_ifft_bn254_fr_batch_device(void* const* d_a, size_t count, const uint6
                                      void* stream) {
     if (!omega_inv || !divisor || !batch_args_ok(d_a, count, log_n, "ifft_batch")) return H2HIP_EINVAL;
     if (check_fr(omega_inv, "omega_inv") || check_fr(divisor, "divisor")) return H2HIP_EINVAL;
-    NttScale sc;
-    sc.out_scale = true;
-    sc.out3[0] = sc.out3[1] = sc.out3[2] = fe_from_u64x4(divisor);
+    NttScale sc = NttScale::inverse(fe_from_u64x4(divisor));
     return batch_over_devices("h2hip_ifft_bn254_fr_batch_device", d_a, count, stream, log_n, fe_from_u64x4(omega_inv), &sc);
 }
 
@@ -2021,9 +1953,7 @@ int h2hip_coeff_to_extended_bn254_fr_batch_device(void* const* d_a, size_t count
     if (!extended_omega || !g_coset || !g_coset_inv || k > extended_k || !batch_args_ok(d_a, count, extended_k, "coeff_to_extended_batch"))
         return H2HIP_EINVAL;
     if (check_fr(extended_omega, "extended_omega") || check_fr(g_coset, "g_coset") || check_fr(g_coset_inv, "g_coset_inv")) return H2HIP_EINVAL;
-    NttScale sc;
-    make_zeta_scale(&sc, true, g_coset, g_coset_inv, nullptr);
-    sc.in_len = 1ull << k;
+    NttScale sc = NttScale::into_coset(fe_from_u64x4(g_coset), fe_from_u64x4(g_coset_inv), 1ull << k);
     return batch_over_devices("h2hip_coeff_to_extended_bn254_fr_batch_device", d_a, count, stream, extended_k, fe_from_u64x4(extended_omega), &sc);
 }
 
@@ -2050,9 +1980,7 @@ int h2hip_ntt_bn254_fr_batch(uint64_t* const* a, size_t count, const uint64_t om
 int h2hip_ifft_bn254_fr_batch(uint64_t* const* a, size_t count, const uint64_t omega_inv[4], uint32_t log_n, const uint64_t divisor[4]) {
     if (!omega_inv || !divisor || !host_batch_args_ok(a, a, count, log_n, "ifft_batch")) return H2HIP_EINVAL;
     if (check_fr(omega_inv, "omega_inv") || check_fr(divisor, "divisor")) return H2HIP_EINVAL;
-    NttScale sc;
-    sc.out_scale = true;
-    sc.out3[0] = sc.out3[1] = sc.out3[2] = fe_from_u64x4(divisor);
+    NttScale sc = NttScale::inverse(fe_from_u64x4(divisor));
     return ntt_host_batch("h2hip_ifft_bn254_fr_batch", a, (size_t)1 << log_n, a, count, fe_from_u64x4(omega_inv), log_n, &sc);
 }
 
@@ -2061,9 +1989,7 @@ int h2hip_coeff_to_extended_bn254_fr_batch(const uint64_t* const* a, uint32_t k,
     if (!extended_omega || !g_coset || !g_coset_inv || k > extended_k || !host_batch_args_ok(a, out, count, extended_k, "coeff_to_extended_batch"))
         return H2HIP_EINVAL;
     if (check_fr(extended_omega, "extended_omega") || check_fr(g_coset, "g_coset") || check_fr(g_coset_inv, "g_coset_inv")) return H2HIP_EINVAL;
-    NttScale sc;
-    make_zeta_scale(&sc, true, g_coset, g_coset_inv, nullptr);
-    sc.in_len = 1ull << k;
+    NttScale sc = NttScale::into_coset(fe_from_u64x4(g_coset), fe_from_u64x4(g_coset_inv), 1ull << k);
     return ntt_host_batch("h2hip_coeff_to_extended_bn254_fr_batch", a, (size_t)1 << k, out, count, fe_from_u64x4(extended_omega), extended_k, &sc);
 }
 
@@ -2074,9 +2000,7 @@ int h2hip_extended_to_coeff_bn254_fr_batch(uint64_t* const* a, size_t count, uin
     if (check_fr(extended_omega_inv, "extended_omega_inv") || check_fr(extended_ifft_divisor, "extended_ifft_divisor") ||
         check_fr(g_coset, "g_coset") || check_fr(g_coset_inv, "g_coset_inv"))
         return H2HIP_EINVAL;
-    NttScale sc;
-    Fe div = fe_from_u64x4(extended_ifft_divisor);
-    make_zeta_scale(&sc, false, g_coset, g_coset_inv, &div);
+    NttScale sc = NttScale::out_of_coset(fe_from_u64x4(extended_ifft_divisor), fe_from_u64x4(g_coset), fe_from_u64x4(g_coset_inv));
     return ntt_host_batch("h2hip_extended_to_coeff_bn254_fr_batch", a, (size_t)1 << extended_k, a, count, fe_from_u64x4(extended_omega_inv), extended_k, &sc);
 }
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 
 #include <map>
 #include <mutex>
@@ -251,6 +252,90 @@ struct Entry {
     ~Entry();
 };
 int check_fr(const uint64_t v[4], const char* what);  // H2HIP_EINVAL (and set_error) unless v is a reduced Fr element
+
+// ---- what the stage files' entry points and host drivers share (inline: api.hip is also built alone, as plain C++) ----------------
+// caller memory is only 8-byte aligned (4 x u64); Fe is alignas(16)
+inline Fe fe_from_u64x4(const uint64_t v[4]) {
+    Fe o;
+    memcpy(o.l, v, 32);
+    return o;
+}
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// a table of `count` pointers, none of them null; nullable: the table itself may be absent (an output form that is not wanted)
+inline int check_ptrs(const char* what, const void* const* p, size_t count, const char* name, bool nullable = false) {
+    if (!p) {
+        if (nullable || !count) return 0;
+        set_error("%s: null %s", what, name);
+        return H2HIP_EINVAL;
+    }
+    for (size_t i = 0; i < count; i++)
+        if (!p[i]) {
+            set_error("%s: %s[%zu] is null", what, name, i);
+            return H2HIP_EINVAL;
+        }
+    return 0;
+}
+// an array of `count` reduced Fr elements
+inline int check_frs(const char* what, const uint64_t* v, size_t count, const char* name) {
+    if (count && !v) {
+        set_error("%s: null %s", what, name);
+        return H2HIP_EINVAL;
+    }
+    for (size_t i = 0; i < count; i++)
+        if (check_fr(v + 4 * i, name)) return H2HIP_EINVAL;
+    return 0;
+}
+// columns of 2^k rows, k <= 28 ...
+inline int check_k(const char* what, uint32_t k) {
+    if (k > 28) {
+        set_error("%s: k = %u > 28", what, k);
+        return H2HIP_EINVAL;
+    }
+    return 0;
+}
+// ... of which the last blinding_factors + 1 are not the circuit's: at least one row must be
+inline int check_k_blinding(const char* what, uint32_t k, uint32_t bf) {
+    if (int rc = check_k(what, k)) return rc;
+    if ((uint64_t)bf + 1 >= (1ull << k)) {
+        set_error("%s: blinding_factors + 1 >= 2^k", what);
+        return H2HIP_EINVAL;
+    }
+    return 0;
+}
+
+// The layout of one workspace buffer.  Regions are taken in call order, each rounded up to 256 bytes, and `total` is what
+// DevBuf::ensure is asked for.  A Carve owns nothing and points nowhere: it adds up offsets, so that a region's offset is written
+// once and the buffer's size, the host image and the device pointers all come from it.  A layout that repeats (one argument's
+// regions, the descriptor blob) is a Carve of its own whose total the outer one takes.
+struct Carve {
+    size_t total = 0;
+    size_t take(size_t bytes) {
+        const size_t off = total;
+        total += align256(bytes);
+        return off;
+    }
+    size_t take_packed(size_t bytes) {  // not rounded: elements of a stride the kernels fix (columns of 2^k, one layout per argument)
+        const size_t off = total;
+        total += bytes;
+        return off;
+    }
+};
+// The descriptor blob of a call: filled in on the host (h), staged to the device in one copy (d).  A region's two pointers come
+// from one offset, so what the host writes and what the kernels read cannot drift apart.
+template <class T>
+struct Mirror {
+    T* h;
+    T* d;
+};
+struct Blob {
+    char* h;
+    char* d;
+    template <class T>
+    Mirror<T> at(size_t off) const {
+        return {(T*)(h + off), (T*)(d + off)};
+    }
+};
 Ctx* ctx();             // the primary device's context (device_ids[0] of h2hip_init)
 int n_devices();        // devices the engine was initialised with (>= 1 once ready)
 Ctx* ctx_at(int i);     // context of the i-th device of h2hip_init's list
@@ -264,6 +349,33 @@ struct NttScale {
     uint64_t in_len = 0;      // elements at index >= in_len are read as zero (resize(.., zero), domain.rs:247)
     bool out_scale = false;   // a[i] *= out3[i % 3] on the final-pass store
     Fe out3[3];
+    // the inverse transform's 1 / n
+    static NttScale inverse(const Fe& divisor) {
+        NttScale sc;
+        sc.out_scale = true;
+        sc.out3[0] = sc.out3[1] = sc.out3[2] = divisor;
+        return sc;
+    }
+    // distribute_powers_zeta (poly/domain.rs:335-351): a[i] *= [1, g_coset, g_coset_inv][i % 3] into the coset, zero-padded from in_len
+    // elements when that is set (:240-254) ...
+    static NttScale into_coset(const Fe& g_coset, const Fe& g_coset_inv, uint64_t in_len = 0) {
+        NttScale sc;
+        sc.in_scale = true;
+        sc.in3[0] = fe_one<FrP>();
+        sc.in3[1] = g_coset;
+        sc.in3[2] = g_coset_inv;
+        sc.in_len = in_len;
+        return sc;
+    }
+    // ... and the two constants swapped on the way out, times the inverse transform's divisor
+    static NttScale out_of_coset(const Fe& divisor, const Fe& g_coset, const Fe& g_coset_inv) {
+        NttScale sc;
+        sc.out_scale = true;
+        sc.out3[0] = divisor;
+        sc.out3[1] = fe_mul<FrP>(divisor, g_coset_inv);
+        sc.out3[2] = fe_mul<FrP>(divisor, g_coset);
+        return sc;
+    }
 };
 // d_src (optional): the first pass reads its input there instead of d_data (which is then output only); with
 // sc->in_len set only d_src[0 .. in_len) is read
@@ -275,11 +387,25 @@ int ntt_device_batch(Ctx* c, Fe* const* h_datas, const Fe* const* h_srcs, size_t
                      hipStream_t s);
 
 int scale_periodic_device(Ctx* c, Fe* d_a, uint64_t n, const uint64_t* h_t, uint32_t t_len, hipStream_t s);
+void ntt_set_smax(uint32_t v);
+void ntt_set_two_pass(uint32_t lo, uint32_t hi);
+void ntt_set_full_twiddle_budget(uint64_t bytes);
+void ntt_set_batch_bytes(uint64_t bytes);
+void ntt_set_two_pass_log_j(int v);
+void ntt_set_full_max_log_m(uint32_t v);
+void ntt_set_fold_tables(bool on);
+void ntt_set_two_pass_batch_wgs(uint64_t v);
 
 // ecfft.hip
 int g_to_lagrange_device(Ctx* c, const Affine* d_g, uint32_t k, Affine* d_out, hipStream_t s);
 int ec_normalize_device(const XYZZ* d_in, Affine* d_out, uint64_t n, hipStream_t s);  // batched XYZZ -> affine
 int fft_g1_device(Ctx* c, Jac* d_a, const Fe& omega, uint32_t log_n, hipStream_t s);   // best_fft::<G1>, in place on Jacobian points
+void ecfft_set_quad(bool on);
+void ecfft_set_lazy(bool on);
+
+// gen.hip
+int gen_scalars_device(uint64_t seed, uint64_t start, size_t n, Fe* d_out, hipStream_t s);
+int gen_points_device(uint64_t seed, uint64_t start, size_t n, Affine* d_out, hipStream_t s);
 
 // product.hip: the permutation / lookup grand products and ff's BatchInvert, enqueued on s (no synchronisation).  cols / perms are
 // host arrays of device pointers; for lookups inputs_tables[2j], [2j + 1] = A_j, S_j and permuted[2j], [2j + 1] = A'_j, S'_j
@@ -320,6 +446,22 @@ int lookup_compress_device(Ctx* c, uint32_t k, const Fe* const* fixed, uint32_t 
 
 // msm.hip
 void msm_set_fuse_small(bool on);
+void msm_set_window(uint32_t c);
+void msm_set_max_chunk(size_t m);
+void msm_set_stream(uint32_t chunks, double ratio, size_t min_n);
+size_t msm_debug_ladder(size_t n, uint32_t chunks, double ratio, bool with_bases, size_t* out, size_t cap);
+void msm_set_heavy_div(size_t d);
+void msm_set_bin_entries(size_t d);
+void msm_set_split_records(bool on);
+void msm_set_bucket_order(int local);
+void msm_set_quad_tail(bool on);
+void msm_set_split_buckets(bool on);
+void msm_set_plane_tail(bool on);
+void msm_set_fuse_limits(size_t entries, size_t max_n);
+void msm_set_rowcol(uint64_t lanes, uint32_t flavour);
+void msm_set_reserved_cus(uint32_t k);
+uint32_t msm_get_reserved_cus();
+uint32_t msm_get_window(size_t n);
 // tab != nullptr: fixed-base form over tab's window table (d_bases unused)
 int msm_device(Ctx* c, const Fe* d_scalars, const Affine* d_bases, size_t n, XYZZ* h_out, hipStream_t s, const MsmTable* tab = nullptr);
 int msm_batch_device(Ctx* c, const Fe* const* scalars, bool scalars_on_host, const Affine* d_bases, size_t n, size_t count, XYZZ* h_out,

@@ -280,13 +280,6 @@ __global__ void __launch_bounds__(256) evalh_lookup_kernel(ProgDev g, LookupDev 
 
 // ---------------------------------------------------------------------------------------------- host side
 
-// caller memory is only 8-byte aligned (4 x u64); Fe is alignas(16)
-static inline Fe load_fe(const uint64_t* v) {
-    Fe o;
-    memcpy(o.l, v, sizeof(o.l));
-    return o;
-}
-
 // E-form canonical element -> I-form canonical limbs (x * 2^5 mod r, sliced): how constants, challenges and the
 // y / beta / gamma / theta scalars enter the kernels
 static inline Fu to_i(const Fe& x) {
@@ -635,7 +628,7 @@ static std::string gen_source(const h2hip_graph& g, const Program& P, bool looku
     src += "    (void)prev;\n";
     for (uint32_t i = 0; i < g.n_constants; i++)
         if (use_const[i]) {
-            const Fu k = to_i(load_fe(g.constants + 4 * (size_t)i));
+            const Fu k = to_i(fe_from_u64x4(g.constants + 4 * (size_t)i));
             add("    const Fu K%u = {{%d, %d, %d, %d, %d, %d, %d, %d, %d}};\n", i, k.l[0], k.l[1], k.l[2], k.l[3], k.l[4], k.l[5], k.l[6], k.l[7], k.l[8]);
         }
     for (int t = 0; t < 3; t++)
@@ -1125,7 +1118,7 @@ struct MetaBlob {
 
 static void prog_put(MetaBlob& mb, const h2hip_graph& g, const Program& P, ProgDev* out) {
     std::vector<Fu> hc(g.n_constants);
-    for (uint32_t i = 0; i < g.n_constants; i++) hc[i] = to_i(load_fe(g.constants + 4 * (size_t)i));
+    for (uint32_t i = 0; i < g.n_constants; i++) hc[i] = to_i(fe_from_u64x4(g.constants + 4 * (size_t)i));
     out->constants = mb.put(hc.data(), hc.size());
     out->rotations = mb.put(g.rotations, g.n_rotations);
     out->ops = mb.put(P.ops.data(), P.ops.size());
@@ -1255,16 +1248,16 @@ int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, uint64_t* values, bool de
     cols.instance = mb.put(instance.data(), instance.size());
     {
         std::vector<Fu> hch(d->n_challenges);
-        for (uint32_t i = 0; i < d->n_challenges; i++) hch[i] = to_i(load_fe(d->challenges + 4 * (size_t)i));
+        for (uint32_t i = 0; i < d->n_challenges; i++) hch[i] = to_i(fe_from_u64x4(d->challenges + 4 * (size_t)i));
         cols.challenges = mb.put(hch.data(), hch.size());
     }
-    cols.beta = to_i(load_fe(d->beta));
-    cols.gamma = to_i(load_fe(d->gamma));
-    cols.theta = to_i(load_fe(d->theta));
-    cols.y = to_i(load_fe(d->y));
+    cols.beta = to_i(fe_from_u64x4(d->beta));
+    cols.gamma = to_i(fe_from_u64x4(d->gamma));
+    cols.theta = to_i(fe_from_u64x4(d->theta));
+    cols.y = to_i(fe_from_u64x4(d->y));
     cols.log_size = ek;
     cols.rot_scale = 1 << (ek - k);
-    const Fe ext_omega = load_fe(d->extended_omega);
+    const Fe ext_omega = fe_from_u64x4(d->extended_omega);
     ProgDev gd;
     prog_put(mb, d->custom_gates, gates_prog, &gd);
     std::vector<ProgDev> lgs(d->n_lookups);
@@ -1279,8 +1272,8 @@ int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, uint64_t* values, bool de
         pd.l0 = l0;
         pd.l_last = l_last;
         pd.l_active = l_active;
-        pd.delta = to_i(load_fe(d->delta));
-        pd.delta_start = to_i(fe_mul<FrP>(load_fe(d->beta), load_fe(d->zeta)));
+        pd.delta = to_i(fe_from_u64x4(d->delta));
+        pd.delta_start = to_i(fe_mul<FrP>(fe_from_u64x4(d->beta), fe_from_u64x4(d->zeta)));
         pd.n_sets = d->n_perm_sets;
         pd.n_cols = d->n_perm_columns;
         pd.chunk_len = d->chunk_len;
@@ -1305,12 +1298,7 @@ int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, uint64_t* values, bool de
         else H2_CHECK(hipMemcpyAsync(u.dst, u.src, u.elems * sizeof(Fe), hipMemcpyHostToDevice, s));
     }
     if (any_late && (rc = c->ensure_aux(2))) return rc;
-    NttScale sc;
-    sc.in_scale = true;
-    sc.in3[0] = fe_one<FrP>();
-    sc.in3[1] = load_fe(d->g_coset);
-    sc.in3[2] = load_fe(d->g_coset_inv);
-    sc.in_len = n;
+    NttScale sc = NttScale::into_coset(fe_from_u64x4(d->g_coset), fe_from_u64x4(d->g_coset_inv), n);
     int t_c = c->timer_begin("evalh_cosets", s);
     if ((rc = ntt_device_batch(c, poly_dst.data(), poly_src.data(), poly_dst.size(), ext_omega, ek, &sc, s))) return rc;
     c->timer_end(t_c, s);
@@ -1486,10 +1474,10 @@ int lookup_compress_device(Ctx* c, uint32_t k, const Fe* const* fixed, uint32_t 
     cols.instance = mb.put(instance, n_instance);
     {
         std::vector<Fu> hch(n_challenges);
-        for (uint32_t i = 0; i < n_challenges; i++) hch[i] = to_i(load_fe(challenges + 4 * (size_t)i));
+        for (uint32_t i = 0; i < n_challenges; i++) hch[i] = to_i(fe_from_u64x4(challenges + 4 * (size_t)i));
         cols.challenges = mb.put(hch.data(), hch.size());
     }
-    cols.theta = to_i(load_fe(theta));
+    cols.theta = to_i(fe_from_u64x4(theta));
     cols.log_size = k;
     cols.rot_scale = 1;
     std::vector<ProgDev> pd(n_graphs);

@@ -19,7 +19,7 @@
 #include <atomic>
 #include <vector>
 #include "engine.h"
-#include "field.h"
+#include "fe_io.h"
 
 namespace h2 {
 
@@ -40,19 +40,6 @@ struct KgScatter {
     uint32_t count;
     uint32_t pad;
 };
-
-__device__ __forceinline__ Fe kg_ld(const Fe* p, uint64_t i) {
-    const uint4* q = (const uint4*)(p + i);
-    uint4 a = q[0], b = q[1];
-    Fe o;
-    o.l[0] = a.x, o.l[1] = a.y, o.l[2] = a.z, o.l[3] = a.w, o.l[4] = b.x, o.l[5] = b.y, o.l[6] = b.z, o.l[7] = b.w;
-    return o;
-}
-__device__ __forceinline__ void kg_st(Fe* p, uint64_t i, const Fe& v) {
-    uint4* q = (uint4*)(p + i);
-    q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
-    q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
-}
 
 // a^e from the top set bit of e down
 __device__ Fe kg_pow(const Fe& a, uint32_t e) {
@@ -75,7 +62,7 @@ __global__ void __launch_bounds__(KG_THREADS) kg_tables_kernel(Fe* tab, Fe omega
         const uint64_t q = t - lo_n;
         v = fe_mul<FrP>(kg_pow(delta, (uint32_t)(q / hi_n)), kg_pow(omega_hi, (uint32_t)(q % hi_n)));
     }
-    kg_st(tab, t, v);
+    fe_st(tab, t, v);
 }
 
 // outs[j][i] = delta^c omega^r for (c, r) = maps[j][i], j = blockIdx.y < columns of this launch; c is checked against m_total (the
@@ -93,9 +80,9 @@ __global__ void __launch_bounds__(KG_THREADS) kg_sigma_kernel(const uint2* const
             atomicOr(flag, 1u);
             v = fe_zero<FrP>();
         } else {
-            v = fe_mul<FrP>(kg_ld(tab, cr.y & (lo_n - 1)), kg_ld(tab, lo_n + (uint64_t)cr.x * hi_n + (cr.y >> lo_bits)));
+            v = fe_mul<FrP>(fe_ld(tab, cr.y & (lo_n - 1)), fe_ld(tab, lo_n + (uint64_t)cr.x * hi_n + (cr.y >> lo_bits)));
         }
-        kg_st(out, i, v);
+        fe_st(out, i, v);
     }
 }
 
@@ -104,7 +91,7 @@ __global__ void __launch_bounds__(KG_THREADS) kg_scatter_kernel(const KgScatter*
     const KgScatter d = descs[blockIdx.y];
     for (uint64_t t = blockIdx.x * (uint64_t)KG_THREADS + threadIdx.x; t < d.count; t += gridDim.x * (uint64_t)KG_THREADS) {
         const uint32_t r = d.rows[t];
-        if (r < n) kg_st(d.out, r, fe_mul<FrP>(kg_ld(d.out, r), kg_ld(inv, d.off + t)));
+        if (r < n) fe_st(d.out, r, fe_mul<FrP>(fe_ld(d.out, r), fe_ld(inv, d.off + t)));
     }
 }
 
@@ -113,40 +100,21 @@ __global__ void __launch_bounds__(KG_THREADS) kg_units_kernel(Fe* l0, Fe* l_last
     const uint64_t i = blockIdx.x * (uint64_t)KG_THREADS + threadIdx.x;
     if (i >= n) return;
     const Fe one = fe_one<FrP>(), zero = fe_zero<FrP>();
-    kg_st(l0, i, i == 0 ? one : zero);
-    kg_st(l_last, i, i == n - b - 1 ? one : zero);
-    kg_st(l_blind, i, i >= n - b ? one : zero);
+    fe_st(l0, i, i == 0 ? one : zero);
+    fe_st(l_last, i, i == n - b - 1 ? one : zero);
+    fe_st(l_blind, i, i >= n - b ? one : zero);
 }
 
 // l_active_row = 1 - (l_last + l_blind) (plonk/keygen.rs:344-351), in place over l_blind
 __global__ void __launch_bounds__(KG_THREADS) kg_active_kernel(Fe* l_active, const Fe* l_last, uint64_t len) {
     const uint64_t i = blockIdx.x * (uint64_t)KG_THREADS + threadIdx.x;
     if (i >= len) return;
-    kg_st(l_active, i, fe_sub<FrP>(fe_one<FrP>(), fe_add<FrP>(kg_ld(l_last, i), kg_ld(l_active, i))));
+    fe_st(l_active, i, fe_sub<FrP>(fe_one<FrP>(), fe_add<FrP>(fe_ld(l_last, i), fe_ld(l_active, i))));
 }
-
-static inline size_t kg_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 static uint32_t kg_grid(uint64_t items) {
     uint64_t g = (items + KG_THREADS - 1) / KG_THREADS;
     return (uint32_t)(g < 1 ? 1 : g > 8192 ? 8192 : g);
-}
-
-static NttScale kg_ifft_scale(const KgDomain& d) {
-    NttScale sc;
-    sc.out_scale = true;
-    sc.out3[0] = sc.out3[1] = sc.out3[2] = d.divisor;
-    return sc;
-}
-
-static NttScale kg_coset_scale(const KgDomain& d) {  // distribute_powers_zeta into the coset, zero-padded from 2^k (poly/domain.rs:240-254)
-    NttScale sc;
-    sc.in_scale = true;
-    sc.in3[0] = fe_one<FrP>();
-    sc.in3[1] = d.g_coset;
-    sc.in3[2] = d.g_coset_inv;
-    sc.in_len = 1ull << d.k;
-    return sc;
 }
 
 // the workspace of one permutation keygen call: the power tables of all m_total columns, the flag, one group's pointer blob
@@ -160,21 +128,23 @@ struct KgPerm {
 static int kg_perm_prepare(Ctx* c, const KgDomain& d, const Fe& delta, uint32_t m_total, uint32_t group_cols, hipStream_t s, KgPerm* w) {
     const uint32_t lo_bits = (d.k + 1) / 2;
     const uint32_t lo_n = 1u << lo_bits, hi_n = 1u << (d.k - lo_bits);
-    const size_t tab_bytes = kg_align(((size_t)lo_n + (size_t)m_total * hi_n) * sizeof(Fe));
-    int rc = c->keygen_ws.ensure(tab_bytes + 256 + kg_align(2 * (size_t)group_cols * sizeof(void*)));
+    Carve ws;
+    const size_t o_tab = ws.take(((size_t)lo_n + (size_t)m_total * hi_n) * sizeof(Fe)), o_flag = ws.take(256),
+                 o_blob = ws.take(2 * (size_t)group_cols * sizeof(void*));
+    int rc = c->keygen_ws.ensure(ws.total);
     if (rc) return rc;
     char* base = (char*)c->keygen_ws.p;
-    w->tab = (const Fe*)base;
-    w->flag = (uint32_t*)(base + tab_bytes);
-    w->blob = base + tab_bytes + 256;
+    w->tab = (const Fe*)(base + o_tab);
+    w->flag = (uint32_t*)(base + o_flag);
+    w->blob = base + o_blob;
     w->lo_bits = lo_bits;
     w->m_total = m_total;
     H2_CHECK(hipMemsetAsync(w->flag, 0, 256, s));
     Fe omega_hi = d.omega;
     for (uint32_t i = 0; i < lo_bits; i++) omega_hi = fe_sqr<FrP>(omega_hi);
     const uint64_t total = lo_n + (uint64_t)m_total * hi_n;
-    hipLaunchKernelGGL(kg_tables_kernel, dim3((uint32_t)((total + KG_THREADS - 1) / KG_THREADS)), dim3(KG_THREADS), 0, s, (Fe*)base, d.omega, omega_hi,
-                       delta, lo_n, hi_n, m_total);
+    hipLaunchKernelGGL(kg_tables_kernel, dim3((uint32_t)((total + KG_THREADS - 1) / KG_THREADS)), dim3(KG_THREADS), 0, s, (Fe*)(base + o_tab), d.omega,
+                       omega_hi, delta, lo_n, hi_n, m_total);
     H2_CHECK(hipGetLastError());
     return 0;
 }
@@ -196,10 +166,10 @@ static int kg_perm_group(Ctx* c, const KgDomain& d, const KgPerm& w, const uint3
     H2_CHECK(hipGetLastError());
     if (!polys && !cosets) return 0;
     Fe* const* coeff = polys ? polys : cosets;
-    NttScale isc = kg_ifft_scale(d);
+    NttScale isc = NttScale::inverse(d.divisor);
     if ((rc = ntt_device_batch(c, coeff, coeff == sigma ? nullptr : (const Fe* const*)sigma, count, d.omega_inv, d.k, &isc, s))) return rc;
     if (!cosets) return 0;
-    NttScale csc = kg_coset_scale(d);
+    NttScale csc = NttScale::into_coset(d.g_coset, d.g_coset_inv, 1ull << d.k);
     return ntt_device_batch(c, cosets, cosets == coeff ? nullptr : (const Fe* const*)coeff, count, d.ext_omega, d.ek, &csc, s);
 }
 
@@ -236,7 +206,7 @@ static int kg_lagrange_device(Ctx* c, const KgDomain& d, uint32_t bf, Fe* l0, Fe
                        (uint64_t)bf);
     H2_CHECK(hipGetLastError());
     Fe* cols[3] = {l0, l_last, l_active};
-    NttScale isc = kg_ifft_scale(d), csc = kg_coset_scale(d);
+    NttScale isc = NttScale::inverse(d.divisor), csc = NttScale::into_coset(d.g_coset, d.g_coset_inv, 1ull << d.k);
     int rc;
     if ((rc = ntt_device_batch(c, cols, nullptr, 3, d.omega_inv, d.k, &isc, s))) return rc;
     if ((rc = ntt_device_batch(c, cols, nullptr, 3, d.ext_omega, d.ek, &csc, s))) return rc;
@@ -259,12 +229,6 @@ struct KgDrain {  // every exit of a pipelined host call: the download copier id
 }  // namespace h2
 
 using namespace h2;
-
-static inline Fe fe_from_u64x4(const uint64_t v[4]) {
-    Fe o;
-    memcpy(o.l, v, 32);
-    return o;
-}
 
 extern "C" {
 // ---- C ABI (include/halo2hip.h, "keygen") -----------------------------------------------------------------------------------------
@@ -293,20 +257,6 @@ static int kg_domain_check(const char* what, uint32_t k, const uint64_t* omega, 
     return 0;
 }
 
-static int kg_table_check(const char* what, const void* const* p, size_t count, const char* name, bool nullable) {
-    if (!p) {
-        if (nullable || !count) return 0;
-        set_error("%s: null %s", what, name);
-        return H2HIP_EINVAL;
-    }
-    for (size_t i = 0; i < count; i++)
-        if (!p[i]) {
-            set_error("%s: %s[%zu] is null", what, name, i);
-            return H2HIP_EINVAL;
-        }
-    return 0;
-}
-
 static int kg_perm_check(uint32_t k, const uint64_t* omega, const uint64_t* omega_inv, const uint64_t* divisor, uint32_t ek,
                          const uint64_t* ext_omega, const uint64_t* g_coset, const uint64_t* g_coset_inv, const uint64_t* delta,
                          const void* const* mapping, uint32_t m, const void* const* perms, const void* const* polys, const void* const* cosets,
@@ -322,8 +272,8 @@ static int kg_perm_check(uint32_t k, const uint64_t* omega, const uint64_t* omeg
         set_error("%s: n_columns %u > %d", what, m, KG_MAX_COLUMNS);
         return H2HIP_EINVAL;
     }
-    if (kg_table_check(what, mapping, m, "mapping", false) || kg_table_check(what, perms, m, "permutations", true) ||
-        kg_table_check(what, polys, m, "polys", true) || kg_table_check(what, cosets, m, "cosets", true))
+    if (check_ptrs(what, mapping, m, "mapping") || check_ptrs(what, perms, m, "permutations", true) || check_ptrs(what, polys, m, "polys", true) ||
+        check_ptrs(what, cosets, m, "cosets", true))
         return H2HIP_EINVAL;
     return 0;
 }
@@ -450,11 +400,8 @@ int h2hip_permutation_keygen_bn254(uint32_t k, const uint64_t omega[4], const ui
 static int kg_assigned_check(uint32_t k, const void* const* numerators, const void* const* rat_rows, const size_t* rat_counts,
                              const void* const* rat_denoms, size_t m, const void* const* out, size_t* total) {
     const char* what = "batch_invert_assigned";
-    if (k > 28) {
-        set_error("%s: k = %u > 28", what, k);
-        return H2HIP_EINVAL;
-    }
-    if (kg_table_check(what, numerators, m, "numerators", false) || kg_table_check(what, out, m, "out", false)) return H2HIP_EINVAL;
+    if (int rc = check_k(what, k)) return rc;
+    if (check_ptrs(what, numerators, m, "numerators") || check_ptrs(what, out, m, "out")) return H2HIP_EINVAL;
     size_t t = 0;
     for (size_t j = 0; j < m; j++) {
         const size_t cnt = rat_counts ? rat_counts[j] : 0;
@@ -492,9 +439,10 @@ int h2hip_batch_invert_assigned_bn254_device(uint32_t k, const void* const* d_nu
     int rc = c->ws_acquire(s);
     if (rc) return rc;
     WsGuard guard(c, s);
-    const size_t inv_b = kg_align(total * sizeof(Fe));
-    if ((rc = c->keygen_ws.ensure(inv_b + kg_align(n_columns * sizeof(KgScatter))))) return rc;
-    Fe* inv = (Fe*)c->keygen_ws.p;
+    Carve ws;
+    const size_t o_inv = ws.take(total * sizeof(Fe)), o_descs = ws.take(n_columns * sizeof(KgScatter));
+    if ((rc = c->keygen_ws.ensure(ws.total))) return rc;
+    Fe* inv = (Fe*)((char*)c->keygen_ws.p + o_inv);
     std::vector<KgScatter> descs;
     size_t off = 0;
     for (size_t j = 0; j < n_columns; j++) {
@@ -505,7 +453,7 @@ int h2hip_batch_invert_assigned_bn254_device(uint32_t k, const void* const* d_nu
         off += cnt;
     }
     if ((rc = batch_invert_device(c, inv, total, s))) return rc;
-    if ((rc = kg_scatter(c, n, descs, (char*)c->keygen_ws.p + inv_b, inv, s))) return rc;
+    if ((rc = kg_scatter(c, n, descs, (char*)c->keygen_ws.p + o_descs, inv, s))) return rc;
     return guard.release();
 }
 
@@ -546,18 +494,19 @@ int h2hip_batch_invert_assigned_bn254(uint32_t k, const uint64_t* const* numerat
     Ctx* c = en.c;
     hipStream_t s = c->stream;
     // the sparse part whole (one inversion over all columns, poly.rs:192-200), the columns that have Rational cells in groups
-    const size_t inv_b = kg_align(total * sizeof(Fe)), rows_b = kg_align(total * sizeof(uint32_t));
     size_t gc = g_kg_group_bytes.load() / col_b;
     if (gc < 1) gc = 1;
     if (gc > rat_cols.size()) gc = rat_cols.size();
-    int rc = c->keygen_io.ensure(inv_b + rows_b + gc * col_b);
+    Carve io;
+    const size_t o_inv = io.take(total * sizeof(Fe)), o_rows = io.take(total * sizeof(uint32_t)), o_cols = io.take_packed(gc * col_b);
+    int rc = c->keygen_io.ensure(io.total);
     if (rc) return rc;
     if ((rc = c->ws_acquire(s))) return rc;
     WsGuard guard(c, s);
-    if ((rc = c->keygen_ws.ensure(kg_align(gc * sizeof(KgScatter))))) return rc;
-    Fe* inv = (Fe*)c->keygen_io.p;
-    uint32_t* rows = (uint32_t*)((char*)c->keygen_io.p + inv_b);
-    char* cols = (char*)c->keygen_io.p + inv_b + rows_b;
+    if ((rc = c->keygen_ws.ensure(align256(gc * sizeof(KgScatter))))) return rc;
+    Fe* inv = (Fe*)((char*)c->keygen_io.p + o_inv);
+    uint32_t* rows = (uint32_t*)((char*)c->keygen_io.p + o_rows);
+    char* cols = (char*)c->keygen_io.p + o_cols;
     std::vector<size_t> offs(rat_cols.size(), 0);
     size_t off = 0;
     for (size_t q = 0; q < rat_cols.size(); q++) {
@@ -590,10 +539,7 @@ static int kg_lagrange_check(uint32_t k, const uint64_t* omega_inv, const uint64
                              const void* l_active, KgDomain* d) {
     const char* what = "key_lagrange_columns";
     if (int rc = kg_domain_check(what, k, omega_inv, omega_inv, divisor, ek, ext_omega, g_coset, g_coset_inv, d)) return rc;
-    if ((uint64_t)bf + 1 >= (1ull << k)) {
-        set_error("%s: blinding_factors + 1 >= 2^k", what);
-        return H2HIP_EINVAL;
-    }
+    if (int rc = check_k_blinding(what, k, bf)) return rc;  // (k itself has passed kg_domain_check)
     if (!l0 || !l_last || !l_active) {
         set_error("%s: null output", what);
         return H2HIP_EINVAL;

@@ -28,7 +28,7 @@
 #include <string.h>
 #include <vector>
 #include "engine.h"
-#include "field.h"
+#include "fe_io.h"
 
 namespace h2 {
 
@@ -40,18 +40,6 @@ namespace h2 {
 static uint32_t g_lk_block = 0;            // h2hip_debug_set_lookup_sort: forced in-LDS sort block (0 = LK_TILE)
 static uint32_t g_lk_last[2] = {0, 0};     // block keys and merge passes of the last permute call
 
-__device__ __forceinline__ Fe lk_ld(const Fe* p, uint64_t i) {
-    const uint4* q = (const uint4*)(p + i);
-    uint4 a = q[0], b = q[1];
-    Fe o;
-    o.l[0] = a.x, o.l[1] = a.y, o.l[2] = a.z, o.l[3] = a.w, o.l[4] = b.x, o.l[5] = b.y, o.l[6] = b.z, o.l[7] = b.w;
-    return o;
-}
-__device__ __forceinline__ void lk_st(Fe* p, uint64_t i, const Fe& v) {
-    uint4* q = (uint4*)(p + i);
-    q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
-    q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
-}
 // a < b as 256-bit integers (limb 7 most significant): Fr's Ord on canonical values
 __device__ __forceinline__ bool key_lt(const Fe& a, const Fe& b) {
 #pragma unroll
@@ -64,7 +52,7 @@ __device__ __forceinline__ uint32_t lk_split(const Fe* A, uint32_t na, const Fe*
     uint32_t lo = d > nb ? d - nb : 0, hi = d < na ? d : na;
     while (lo < hi) {
         const uint32_t mid = (lo + hi) >> 1;
-        if (!key_lt(lk_ld(B, d - 1 - mid), lk_ld(A, mid))) lo = mid + 1;
+        if (!key_lt(fe_ld(B, d - 1 - mid), fe_ld(A, mid))) lo = mid + 1;
         else hi = mid;
     }
     return lo;
@@ -81,7 +69,7 @@ __global__ __launch_bounds__(LK_THREADS) void lk_block_sort_kernel(const Fe* con
         const uint64_t r = base + i;
         Fe v;
         if (r < u) {
-            v = fe_to_canonical<FrP>(lk_ld(in, r));
+            v = fe_to_canonical<FrP>(fe_ld(in, r));
         } else {
 #pragma unroll
             for (int j = 0; j < 8; j++) v.l[j] = 0xffffffffu;
@@ -102,7 +90,7 @@ __global__ __launch_bounds__(LK_THREADS) void lk_block_sort_kernel(const Fe* con
             }
             __syncthreads();
         }
-    for (uint32_t i = threadIdx.x; i < ts; i += LK_THREADS) lk_st(out, base + i, sk[i]);
+    for (uint32_t i = threadIdx.x; i < ts; i += LK_THREADS) fe_st(out, base + i, sk[i]);
 }
 
 // ---- 2. one merge pass: sorted runs of w keys -> runs of 2w ---------------------------------------------------------------------
@@ -125,13 +113,13 @@ __global__ __launch_bounds__(LK_THREADS) void lk_merge_kernel(const Fe* const* s
         const uint32_t a0 = s_a[0], a1 = s_a[1], b0 = d0 - a0;
         na = a1 - a0;
         nb = ts - na;
-        for (uint32_t i = tid; i < ts; i += LK_THREADS) sk[i] = i < na ? lk_ld(gA, a0 + i) : lk_ld(gB, b0 + (i - na));
+        for (uint32_t i = tid; i < ts; i += LK_THREADS) sk[i] = i < na ? fe_ld(gA, a0 + i) : fe_ld(gB, b0 + (i - na));
         __syncthreads();
         A = sk;
         B = sk + na;
         d = t;
     } else {  // whole pairs of runs inside the tile
-        for (uint32_t i = tid; i < ts; i += LK_THREADS) sk[i] = lk_ld(in, o0 + i);
+        for (uint32_t i = tid; i < ts; i += LK_THREADS) sk[i] = fe_ld(in, o0 + i);
         __syncthreads();
         const uint32_t pb = t / (2 * w) * (2 * w);
         A = sk + pb;
@@ -147,7 +135,7 @@ __global__ __launch_bounds__(LK_THREADS) void lk_merge_kernel(const Fe* const* s
         const Fe x = take_a ? A[ia] : B[ib];
         if (take_a) ia++;
         else ib++;
-        lk_st(out, o0 + t + e, x);
+        fe_st(out, o0 + t + e, x);
     }
 }
 
@@ -165,7 +153,7 @@ struct LkPerm {           // one lookup
     const Fe* blind;      // 2 (b + 1) values: A' rows u .. n - 1, then S' rows u .. n - 1
 };
 
-__device__ __forceinline__ bool lk_repeated(const Fe* a, uint64_t i) { return i > 0 && fe_eq(lk_ld(a, i), lk_ld(a, i - 1)); }
+__device__ __forceinline__ bool lk_repeated(const Fe* a, uint64_t i) { return i > 0 && fe_eq(fe_ld(a, i), fe_ld(a, i - 1)); }
 
 // exclusive sum over the workgroup's threads in order; *total = sum of all
 __device__ __forceinline__ uint32_t lk_scan_excl(uint32_t v, uint32_t* lds, uint32_t* total) {
@@ -193,13 +181,13 @@ __global__ __launch_bounds__(LK_THREADS) void lk_mark_kernel(const LkPerm* P, ui
         const uint64_t i = r0 + e;
         if (i >= u) break;
         if (lk_repeated(D.a, i)) continue;
-        const Fe v = lk_ld(D.a, i);
+        const Fe v = fe_ld(D.a, i);
         // lower bound of v in T[0 .. u): every T[< lo] < v; galloping from the previous hit, whose value is smaller
         uint64_t lo = have ? pos : 0, hi = u;
         if (have) {
             uint64_t step = 1;
             hi = lo;
-            while (hi < u && key_lt(lk_ld(D.t, hi), v)) {
+            while (hi < u && key_lt(fe_ld(D.t, hi), v)) {
                 lo = hi + 1;
                 hi = lo + step;
                 step <<= 1;
@@ -208,12 +196,12 @@ __global__ __launch_bounds__(LK_THREADS) void lk_mark_kernel(const LkPerm* P, ui
         }
         while (lo < hi) {
             const uint64_t mid = (lo + hi) >> 1;
-            if (key_lt(lk_ld(D.t, mid), v)) lo = mid + 1;
+            if (key_lt(fe_ld(D.t, mid), v)) lo = mid + 1;
             else hi = mid;
         }
         pos = lo;
         have = true;
-        if (pos >= u || !fe_eq(lk_ld(D.t, pos), v)) atomicOr(D.flag, 1u);
+        if (pos >= u || !fe_eq(fe_ld(D.t, pos), v)) atomicOr(D.flag, 1u);
         else D.used[pos] = 1u;  // distinct first values land on distinct slots
     }
 }
@@ -277,7 +265,7 @@ __global__ __launch_bounds__(LK_THREADS) void lk_compact_kernel(const LkPerm* P,
     for (int e = 0; e < LK_E; e++) {
         const uint64_t i = r0 + e;
         if (i >= u) break;
-        if (D.used[i] == 0u) lk_st(D.lc, at++, lk_ld(D.t, i));
+        if (D.used[i] == 0u) fe_st(D.lc, at++, fe_ld(D.t, i));
     }
 }
 
@@ -294,24 +282,22 @@ __global__ __launch_bounds__(LK_THREADS) void lk_final_kernel(const LkPerm* P, u
         const uint64_t i = r0 + e;
         if (i >= n) break;
         if (i >= u) {
-            lk_st(D.pa, i, D.blind[i - u]);
-            lk_st(D.pt, i, D.blind[(n - u) + (i - u)]);
+            fe_st(D.pa, i, D.blind[i - u]);
+            fe_st(D.pt, i, D.blind[(n - u) + (i - u)]);
             continue;
         }
-        const Fe v = lk_ld(D.a, i);
+        const Fe v = fe_ld(D.a, i);
         Fe s = v;
         if (lk_repeated(D.a, i)) {
-            if (rank < n_l) s = lk_ld(D.lc, n_l - 1 - rank);
+            if (rank < n_l) s = fe_ld(D.lc, n_l - 1 - rank);
             rank++;
         }
-        lk_st(D.pa, i, fe_from_canonical<FrP>(v));
-        lk_st(D.pt, i, fe_from_canonical<FrP>(s));
+        fe_st(D.pa, i, fe_from_canonical<FrP>(v));
+        fe_st(D.pt, i, fe_from_canonical<FrP>(s));
     }
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
-static size_t lk_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // Validated arguments; columns and outputs are device pointers (in[j], tab[j], pa[j], pt[j] for lookup j), blinding host memory.
 // Enqueues everything on s, then waits for s once to read the not-found flags: H2HIP_ELOOKUP names the lowest failing lookup.
 int lookup_permute_device(Ctx* c, uint32_t k, const Fe* const* in, const Fe* const* tab, size_t count, const uint64_t* blinding, uint32_t bf,
@@ -326,56 +312,63 @@ int lookup_permute_device(Ctx* c, uint32_t k, const Fe* const* in, const Fe* con
     for (uint64_t w = block; w < n; w <<= 1) passes++;
     const size_t cols = 2 * count, col_bytes = n * sizeof(Fe);
     const size_t nb = (size_t)bf + 1;
-    // workspace: two key buffers per sorted column, per lookup the used marks, L, the tile counts; the flags
-    const size_t used_bytes = lk_align(n * sizeof(uint32_t)), cnt_bytes = lk_align(((size_t)tiles + 1) * sizeof(uint32_t));
-    const size_t per_lookup = used_bytes + col_bytes + 2 * cnt_bytes;
-    const size_t flag_bytes = lk_align(count * sizeof(uint32_t));
-    const size_t blob_perm = lk_align(count * sizeof(LkPerm)), blob_ptr = lk_align(3 * cols * sizeof(void*));
-    const size_t blob = blob_perm + blob_ptr + lk_align(count * 2 * nb * sizeof(Fe));
+    // one lookup's workspace: the used marks, L (a column, packed), the tile counts of L and of R
+    const size_t used_bytes = align256(n * sizeof(uint32_t)), cnt_bytes = ((size_t)tiles + 1) * sizeof(uint32_t);
+    Carve lk;
+    const size_t o_used = lk.take(used_bytes), o_lc = lk.take_packed(col_bytes), o_cnt_l = lk.take(cnt_bytes), o_cnt_r = lk.take(cnt_bytes);
+    // the blob the kernels read: descriptors, three pointer tables of `cols` entries (sources, key buffers 0 and 1), blinding
+    Carve blob;
+    const size_t o_perm = blob.take(count * sizeof(LkPerm)), o_ptr = blob.take(3 * cols * sizeof(void*)),
+                 o_blind = blob.take(count * 2 * nb * sizeof(Fe));
+    // the call's workspace: two key buffers per sorted column ([buffer][column][n]), every lookup's, the flags, the blob
+    Carve ws;
+    const size_t o_keys = ws.take_packed(2 * cols * col_bytes), o_per = ws.take_packed(count * lk.total);
+    const size_t o_flag = ws.take(count * sizeof(uint32_t)), o_blob = ws.take(blob.total);
     int rc = c->ws_acquire(s);
     if (rc) return rc;
     WsGuard guard(c, s);
-    if ((rc = c->lookup_ws.ensure(2 * cols * col_bytes + count * per_lookup + flag_bytes + blob))) return rc;
+    if ((rc = c->lookup_ws.ensure(ws.total))) return rc;
     if ((rc = c->lookup_flag.ensure(count * sizeof(uint32_t)))) return rc;
     char* base = (char*)c->lookup_ws.p;
-    Fe* keys = (Fe*)base;  // [buffer][column][n]
-    char* per = base + 2 * cols * col_bytes;
-    uint32_t* d_flag = (uint32_t*)(per + count * per_lookup);
-    char* d_blob = per + count * per_lookup + flag_bytes;
-    std::vector<char> h(blob, 0);
-    LkPerm* hp = (LkPerm*)h.data();
-    const Fe** hsrc = (const Fe**)(h.data() + blob_perm);
-    Fe** hk0 = (Fe**)(h.data() + blob_perm) + cols;
-    Fe** hk1 = (Fe**)(h.data() + blob_perm) + 2 * cols;
-    Fe* hblind = (Fe*)(h.data() + blob_perm + blob_ptr);
-    if (nb) memcpy(hblind, blinding, count * 2 * nb * sizeof(Fe));
-    const Fe* const* d_src = (const Fe* const*)(d_blob + blob_perm);
-    Fe* const* d_k0 = (Fe* const*)(d_blob + blob_perm) + cols;
-    Fe* const* d_k1 = (Fe* const*)(d_blob + blob_perm) + 2 * cols;
+    Fe* keys = (Fe*)(base + o_keys);
+    char* per = base + o_per;
+    uint32_t* d_flag = (uint32_t*)(base + o_flag);
+    std::vector<char> h(blob.total, 0);
+    const Blob img{h.data(), base + o_blob};
+    const Mirror<LkPerm> perm = img.at<LkPerm>(o_perm);
+    const Mirror<const Fe*> src = img.at<const Fe*>(o_ptr);  // one table: the sources in entries [0, cols) ...
+    const Mirror<Fe*> kbuf = img.at<Fe*>(o_ptr);             // ... key buffer 0 in [cols, 2 cols), key buffer 1 in [2 cols, 3 cols)
+    const Mirror<Fe> blind = img.at<Fe>(o_blind);
+    if (nb) memcpy(blind.h, blinding, count * 2 * nb * sizeof(Fe));
+    Fe** hk0 = kbuf.h + cols;
+    Fe** hk1 = kbuf.h + 2 * cols;
+    const Fe* const* d_src = src.d;
+    Fe* const* d_k0 = kbuf.d + cols;
+    Fe* const* d_k1 = kbuf.d + 2 * cols;
     for (size_t q = 0; q < cols; q++) {
-        hsrc[q] = q & 1 ? tab[q / 2] : in[q / 2];
+        src.h[q] = q & 1 ? tab[q / 2] : in[q / 2];
         hk0[q] = keys + q * n;
         hk1[q] = keys + (cols + q) * n;
     }
     Fe* const* h_sorted = passes & 1 ? hk1 : hk0;  // where the last pass leaves the keys
     for (size_t j = 0; j < count; j++) {
-        char* pj = per + j * per_lookup;
-        LkPerm& D = hp[j];
+        char* pj = per + j * lk.total;
+        LkPerm& D = perm.h[j];
         D.a = h_sorted[2 * j];
         D.t = h_sorted[2 * j + 1];
-        D.used = (uint32_t*)pj;
-        D.lc = (Fe*)(pj + used_bytes);
-        D.cnt_l = (uint32_t*)(pj + used_bytes + col_bytes);
-        D.cnt_r = (uint32_t*)(pj + used_bytes + col_bytes + cnt_bytes);
+        D.used = (uint32_t*)(pj + o_used);
+        D.lc = (Fe*)(pj + o_lc);
+        D.cnt_l = (uint32_t*)(pj + o_cnt_l);
+        D.cnt_r = (uint32_t*)(pj + o_cnt_r);
         D.flag = d_flag + j;
         D.pa = pa[j];
         D.pt = pt[j];
-        D.blind = (const Fe*)(d_blob + blob_perm + blob_ptr) + j * 2 * nb;
+        D.blind = blind.d + j * 2 * nb;
     }
-    if ((rc = c->stage_h2d(d_blob, h.data(), blob, s))) return rc;
-    for (size_t j = 0; j < count; j++) H2_CHECK(hipMemsetAsync(per + j * per_lookup, 0, used_bytes, s));
+    if ((rc = c->stage_h2d(img.d, img.h, blob.total, s))) return rc;
+    for (size_t j = 0; j < count; j++) H2_CHECK(hipMemsetAsync(per + j * lk.total + o_used, 0, used_bytes, s));
     H2_CHECK(hipMemsetAsync(d_flag, 0, count * sizeof(uint32_t), s));
-    const LkPerm* d_perm = (const LkPerm*)d_blob;
+    const LkPerm* d_perm = perm.d;
     int tm = c->timer_begin("lookup_permute", s);
     hipLaunchKernelGGL(lk_block_sort_kernel, dim3(tiles, (uint32_t)cols), dim3(LK_THREADS), 0, s, d_src, d_k0, u, ts, block);
     H2_CHECK(hipGetLastError());
@@ -418,36 +411,19 @@ using namespace h2;
 extern "C" {
 // ---- C ABI (include/halo2hip.h, "lookup compression and permutation") -----------------------------------------------------------
 // Here rather than in api.hip, for the reason product.hip gives.
-static int lk_ptrs_check(const char* what, const void* const* p, size_t count, const char* name) {
-    if (count && !p) {
-        set_error("%s: null %s", what, name);
-        return H2HIP_EINVAL;
-    }
-    for (size_t i = 0; i < count; i++)
-        if (!p[i]) {
-            set_error("%s: %s[%zu] is null", what, name, i);
-            return H2HIP_EINVAL;
-        }
-    return 0;
-}
-
 static int compress_check(uint32_t k, const void* const* fixed, uint32_t n_fixed, const void* const* advice, uint32_t n_advice,
                           const void* const* instance, uint32_t n_instance, const uint64_t* challenges, uint32_t n_challenges,
                           const uint64_t* theta, const h2hip_graph* graphs, size_t n_graphs, const void* const* out) {
     const char* what = "lookup_compress";
-    if (k > 28) {
-        set_error("%s: k = %u > 28", what, k);
-        return H2HIP_EINVAL;
-    }
+    if (int rc = check_k(what, k)) return rc;
     if (!theta || (n_challenges && !challenges)) {
         set_error("%s: null theta or challenges", what);
         return H2HIP_EINVAL;
     }
     if (check_fr(theta, "theta")) return H2HIP_EINVAL;
-    for (uint32_t i = 0; i < n_challenges; i++)
-        if (check_fr(challenges + 4 * (size_t)i, "challenge")) return H2HIP_EINVAL;
-    if (lk_ptrs_check(what, fixed, n_fixed, "fixed_values") || lk_ptrs_check(what, advice, n_advice, "advice_values") ||
-        lk_ptrs_check(what, instance, n_instance, "instance_values") || lk_ptrs_check(what, out, n_graphs, "out"))
+    if (check_frs(what, challenges, n_challenges, "challenge")) return H2HIP_EINVAL;
+    if (check_ptrs(what, fixed, n_fixed, "fixed_values") || check_ptrs(what, advice, n_advice, "advice_values") ||
+        check_ptrs(what, instance, n_instance, "instance_values") || check_ptrs(what, out, n_graphs, "out"))
         return H2HIP_EINVAL;
     return lookup_compress_validate(n_fixed, n_advice, n_instance, n_challenges, graphs, n_graphs);
 }
@@ -455,14 +431,7 @@ static int compress_check(uint32_t k, const void* const* fixed, uint32_t n_fixed
 static int permute_check(uint32_t k, const void* const* in, const void* const* tab, size_t count, const uint64_t* blinding, uint32_t bf,
                          const void* const* pa, const void* const* pt) {
     const char* what = "lookup_permute";
-    if (k > 28) {
-        set_error("%s: k = %u > 28", what, k);
-        return H2HIP_EINVAL;
-    }
-    if ((uint64_t)bf + 1 >= (1ull << k)) {
-        set_error("%s: blinding_factors + 1 >= 2^k", what);
-        return H2HIP_EINVAL;
-    }
+    if (int rc = check_k_blinding(what, k, bf)) return rc;
     if (count > LK_MAX_COUNT) {
         set_error("%s: count %zu > %d", what, count, LK_MAX_COUNT);
         return H2HIP_EINVAL;
@@ -471,10 +440,9 @@ static int permute_check(uint32_t k, const void* const* in, const void* const* t
         set_error("%s: null blinding", what);
         return H2HIP_EINVAL;
     }
-    for (size_t i = 0; i < count * 2 * ((size_t)bf + 1); i++)
-        if (check_fr(blinding + 4 * i, "blinding value")) return H2HIP_EINVAL;
-    if (lk_ptrs_check(what, in, count, "compressed_input") || lk_ptrs_check(what, tab, count, "compressed_table") ||
-        lk_ptrs_check(what, pa, count, "permuted_input") || lk_ptrs_check(what, pt, count, "permuted_table"))
+    if (check_frs(what, blinding, count * 2 * ((size_t)bf + 1), "blinding value")) return H2HIP_EINVAL;
+    if (check_ptrs(what, in, count, "compressed_input") || check_ptrs(what, tab, count, "compressed_table") ||
+        check_ptrs(what, pa, count, "permuted_input") || check_ptrs(what, pt, count, "permuted_table"))
         return H2HIP_EINVAL;
     return 0;
 }

@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <vector>
 #include "engine.h"
+#include "fe_io.h"
 #include "fieldu.h"
 #include "../../include/halo2hip_debug.h"
 
@@ -38,19 +39,6 @@ namespace h2 {
 typedef FrUA OpU;
 
 static uint32_t g_open_rows = 0, g_open_threads = 0;  // h2hip_debug_set_opening_tile: forced tile shape (0 = default)
-
-__device__ __forceinline__ Fe op_ld(const Fe* p, uint64_t i) {
-    const uint4* q = (const uint4*)(p + i);
-    uint4 a = q[0], b = q[1];
-    Fe o;
-    o.l[0] = a.x, o.l[1] = a.y, o.l[2] = a.z, o.l[3] = a.w, o.l[4] = b.x, o.l[5] = b.y, o.l[6] = b.z, o.l[7] = b.w;
-    return o;
-}
-__device__ __forceinline__ void op_st(Fe* p, uint64_t i, const Fe& v) {
-    uint4* q = (uint4*)(p + i);
-    q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
-    q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
-}
 
 // s + y * v for canonical s, v (E-form) and an I-form power y (fu_from_ext): value < 0.2 p + 2 p, back to canonical
 __device__ __forceinline__ Fe op_axpy(const Fe& s, const Fu& y, const Fe& v) {
@@ -89,7 +77,7 @@ __global__ __launch_bounds__(OPEN_MAX_THREADS) void open_eval_kernel(EvalParams 
     for (int j = (int)P.R - 1; j >= 0; j--) {  // indices above len come first and leave acc at zero
         const uint64_t i = base + (uint64_t)j * P.B;
         if (i >= D.len) continue;
-        const Fu nc = fu_neg(fu_slice(op_ld(D.poly, i)));
+        const Fu nc = fu_neg(fu_slice(fe_ld(D.poly, i)));
 #pragma unroll
         for (int k = 0; k < NP; k++) acc[k] = fu_mul_subh<OpU>(acc[k], y[k], nc);  // acc y + c: value stays below 2.5 p
     }
@@ -110,7 +98,7 @@ __global__ __launch_bounds__(OPEN_MAX_THREADS) void open_eval_kernel(EvalParams 
             Fu v = fu_slice(lds[0]);
             for (uint32_t b = 0; b < 40; b++)
                 if ((tile_lo >> b) & 1) v = fu_mul<OpU>(v, xp[b]);
-            op_st(P.partial, (size_t)D.q[k] * P.max_tiles + tile, fu_canon_fast<OpU>(v));
+            fe_st(P.partial, (size_t)D.q[k] * P.max_tiles + tile, fu_canon_fast<OpU>(v));
         }
         __syncthreads();
     }
@@ -121,14 +109,14 @@ __global__ __launch_bounds__(OPEN_MAX_THREADS) void open_eval_sum_kernel(const F
     __shared__ Fe lds[OPEN_MAX_THREADS];
     const uint32_t q = blockIdx.x, tid = threadIdx.x, T = qtiles[q];
     Fe s = fe_zero<FrP>();
-    for (uint32_t t = tid; t < T; t += OPEN_MAX_THREADS) s = fe_add<FrP>(s, op_ld(partial, (size_t)q * max_tiles + t));
+    for (uint32_t t = tid; t < T; t += OPEN_MAX_THREADS) s = fe_add<FrP>(s, fe_ld(partial, (size_t)q * max_tiles + t));
     lds[tid] = s;
     __syncthreads();
     for (uint32_t h = OPEN_MAX_THREADS / 2; h > 0; h >>= 1) {
         if (tid < h) lds[tid] = fe_add<FrP>(lds[tid], lds[tid + h]);
         __syncthreads();
     }
-    if (tid == 0) op_st(evals, q, lds[0]);
+    if (tid == 0) fe_st(evals, q, lds[0]);
 }
 
 // ---- combine / divide ----------------------------------------------------------------------------------------------------
@@ -151,30 +139,30 @@ struct CombParams {
 
 // a[i] = sum_j s_j p_j[i] - sub[i]: E-form, |value| < 14 p
 __device__ __forceinline__ Fu comb_load(const CombParams& P, uint64_t i) {
-    if (!P.first) return fu_slice(op_ld(P.in, i));
+    if (!P.first) return fu_slice(fe_ld(P.in, i));
     Fu acc = fu_zero();
     uint32_t j = 0, cnt = 0;
     for (; j + 1 < P.n_polys; j += 2) {  // two products, one reduction: (p_j s_j - p_{j+1} (-s_{j+1})) / 2^261, value < 1.4 p
-        Fu t = fu_mul_sub<OpU>(fu_slice(op_ld(P.polys[j], i)), P.scal[2 * j], fu_slice(op_ld(P.polys[j + 1], i)), P.scal[2 * j + 3]);
+        Fu t = fu_mul_sub<OpU>(fu_slice(fe_ld(P.polys[j], i)), P.scal[2 * j], fu_slice(fe_ld(P.polys[j + 1], i)), P.scal[2 * j + 3]);
         acc = fu_norm(fu_add(acc, t));
         if (++cnt == 8) {  // < p + 8 x 1.4 p: back to canonical before the sum leaves fu_canon_fast's range
             acc = fu_slice(fu_canon_fast<OpU>(acc));
             cnt = 0;
         }
     }
-    if (j < P.n_polys) acc = fu_norm(fu_add(acc, fu_mul<OpU>(fu_slice(op_ld(P.polys[j], i)), P.scal[2 * j])));
+    if (j < P.n_polys) acc = fu_norm(fu_add(acc, fu_mul<OpU>(fu_slice(fe_ld(P.polys[j], i)), P.scal[2 * j])));
     if (i < P.sub_len) acc = fu_norm(fu_sub(acc, fu_slice(P.sub[i])));
     return acc;
 }
 
 __device__ __forceinline__ void comb_store(const CombParams& P, uint64_t o, const Fu& v) {
     if (!P.last) {
-        op_st(P.out, o, fu_canon_fast<OpU>(v));
+        fe_st(P.out, o, fu_canon_fast<OpU>(v));
         return;
     }
     Fe r = P.scale_one ? fu_canon_fast<OpU>(v) : fu_mul_canon<OpU>(v, P.scale);
-    if (P.accumulate) r = fe_add<FrP>(r, op_ld(P.out, o));
-    op_st(P.out, o, r);
+    if (P.accumulate) r = fe_add<FrP>(r, fe_ld(P.out, o));
+    fe_st(P.out, o, r);
 }
 
 // descending inclusive scan over the B threads of a workgroup: I_t = v_t + m I_{t+1}, m^(2^l) = pw[l]; returns I_{t+1} (0 for the last)
@@ -210,12 +198,12 @@ __global__ __launch_bounds__(OPEN_MAX_THREADS) void open_scan_kernel(CombParams 
         const uint64_t hi = lo + P.R < P.L ? lo + P.R : P.L;
         for (uint64_t i = hi; i-- > lo;) {  // S = a[i] + r S: value < 0.2 p + 14 p + p
             S = fu_canon_fast<OpU>(fu_mul_subh<OpU>(fu_slice(S), r, fu_neg(comb_load(P, i))));
-            op_st(P.w, i, S);
+            fe_st(P.w, i, S);
         }
     }
     const Fe ex = block_suffix_scan(S, P.rpow + P.logR, P.B, lds);  // the suffix of the threads above, weighted by r^R per thread
-    op_st(P.thr, (size_t)tile * P.B + tid, ex);
-    if (tid == 0) op_st(P.tile, tile, op_axpy(S, P.rpow[P.logR], ex));
+    fe_st(P.thr, (size_t)tile * P.B + tid, ex);
+    if (tid == 0) fe_st(P.tile, tile, op_axpy(S, P.rpow[P.logR], ex));
 }
 
 // one workgroup of OPEN_MAX_THREADS: thread t takes tiles [t 2^log_per, (t + 1) 2^log_per)
@@ -226,14 +214,14 @@ __global__ __launch_bounds__(OPEN_MAX_THREADS) void open_tiles_kernel(CombParams
     const uint64_t lo = (uint64_t)tid << P.log_per, T = P.tiles;
     const uint64_t hi = lo + (1ull << P.log_per) < T ? lo + (1ull << P.log_per) : T;
     Fe S = fe_zero<FrP>();
-    for (uint64_t u = hi; u-- > lo;) S = op_axpy(op_ld(P.tile, u), m, S);
+    for (uint64_t u = hi; u-- > lo;) S = op_axpy(fe_ld(P.tile, u), m, S);
     Fe c = block_suffix_scan(S, P.rpow + lm + P.log_per, OPEN_MAX_THREADS, lds);
     for (uint64_t u = hi; u-- > lo;) {
-        const Fe agg = op_ld(P.tile, u);
-        op_st(P.tile, u, c);
+        const Fe agg = fe_ld(P.tile, u);
+        fe_st(P.tile, u, c);
         c = op_axpy(agg, m, c);
     }
-    if (tid == 0 && P.rem) op_st(P.rem, 0, c);  // S(0) = a(r)
+    if (tid == 0 && P.rem) fe_st(P.rem, 0, c);  // S(0) = a(r)
 }
 
 __global__ __launch_bounds__(OPEN_MAX_THREADS) void open_apply_kernel(CombParams P) {
@@ -241,17 +229,17 @@ __global__ __launch_bounds__(OPEN_MAX_THREADS) void open_apply_kernel(CombParams
     const uint64_t lo = ((uint64_t)tile * P.B + tid) * P.R;
     if (lo >= P.L) return;
     // this thread's carry S(lo + R) = (suffix of the threads above in the tile) + r^(R (B - 1 - tid)) (the tile's carry)
-    Fu pc = fu_slice(op_ld(P.tile, tile));
+    Fu pc = fu_slice(fe_ld(P.tile, tile));
     const uint32_t e = P.B - 1 - tid;
     for (uint32_t b = 0; b < P.logB; b++)
         if ((e >> b) & 1) pc = fu_mul<OpU>(pc, P.rpow[P.logR + b]);
-    Fu p = fu_slice(fu_canon_fast<OpU>(fu_norm(fu_add(pc, fu_slice(op_ld(P.thr, (size_t)tile * P.B + tid))))));
+    Fu p = fu_slice(fu_canon_fast<OpU>(fu_norm(fu_add(pc, fu_slice(fe_ld(P.thr, (size_t)tile * P.B + tid))))));
     const Fu r = P.rpow[0];
     const uint64_t hi = lo + P.R < P.L ? lo + P.R : P.L;  // past L the carry is zero
     for (uint64_t i = hi; i-- > lo;) {
         p = fu_mul<OpU>(p, r);  // r^(lo + R - i) carry: value below 1.25 p
         if (i == 0) break;      // S(0) is the remainder (open_tiles_kernel)
-        comb_store(P, i - 1, fu_norm(fu_add(fu_slice(op_ld(P.w, i)), p)));
+        comb_store(P, i - 1, fu_norm(fu_add(fu_slice(fe_ld(P.w, i)), p)));
     }
 }
 
@@ -261,8 +249,6 @@ static uint32_t ilog2(uint64_t v) {
     while ((1ull << (l + 1)) <= v) l++;
     return l;
 }
-
-static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // rows per thread and threads per tile: about 2^17 threads over the call (8 waves per CU), or the debug hook's shape
 static void open_shape(uint64_t elems, uint32_t max_r, uint32_t* R, uint32_t* B) {
@@ -311,23 +297,29 @@ static int eval_run(Ctx* c, const Fe* const* polys, const size_t* lens, size_t n
     }
     // passes sorted by point count: one launch per count
     std::stable_sort(passes.begin(), passes.end(), [](const EvalPass& a, const EvalPass& b) { return a.np < b.np; });
-    const size_t b_pass = al256(passes.size() * sizeof(EvalPass)), b_pow = al256(n_queries * OPEN_POW * sizeof(Fu)),
-                 b_qt = al256(n_queries * sizeof(uint32_t)), b_part = al256(n_queries * (size_t)max_tiles * sizeof(Fe));
-    const size_t blob = b_pass + b_pow + b_qt;
+    // the blob the kernels read (passes, power tables, tile counts), then the tile partials
+    Carve blob;
+    const size_t o_pass = blob.take(passes.size() * sizeof(EvalPass)), o_pow = blob.take(n_queries * OPEN_POW * sizeof(Fu)),
+                 o_qt = blob.take(n_queries * sizeof(uint32_t));
+    Carve ws;
+    const size_t o_blob = ws.take(blob.total), o_part = ws.take(n_queries * (size_t)max_tiles * sizeof(Fe));
     int rc = c->ws_acquire(s);
     if (rc) return rc;
     WsGuard guard(c, s);
-    if ((rc = c->open_ws.ensure(blob + b_part))) return rc;
+    if ((rc = c->open_ws.ensure(ws.total))) return rc;
     char* base = (char*)c->open_ws.p;
-    std::vector<char> h(blob, 0);
-    memcpy(h.data(), passes.data(), passes.size() * sizeof(EvalPass));
-    Fu* hp = (Fu*)(h.data() + b_pass);
-    for (size_t q = 0; q < n_queries; q++) pow_table(points[q], hp + q * OPEN_POW);
-    memcpy(h.data() + b_pass + b_pow, qtiles.data(), n_queries * sizeof(uint32_t));
-    if ((rc = c->stage_h2d(base, h.data(), blob, s))) return rc;
+    std::vector<char> h(blob.total, 0);
+    const Blob img{h.data(), base + o_blob};
+    const Mirror<EvalPass> pass = img.at<EvalPass>(o_pass);
+    const Mirror<Fu> xpow = img.at<Fu>(o_pow);
+    const Mirror<uint32_t> qt = img.at<uint32_t>(o_qt);
+    memcpy(pass.h, passes.data(), passes.size() * sizeof(EvalPass));
+    for (size_t q = 0; q < n_queries; q++) pow_table(points[q], xpow.h + q * OPEN_POW);
+    memcpy(qt.h, qtiles.data(), n_queries * sizeof(uint32_t));
+    if ((rc = c->stage_h2d(img.d, img.h, blob.total, s))) return rc;
     EvalParams P;
-    P.xpow = (const Fu*)(base + b_pass);
-    P.partial = (Fe*)(base + blob);
+    P.xpow = xpow.d;
+    P.partial = (Fe*)(base + o_part);
     P.R = R;
     P.B = B;
     P.logB = ilog2(B);
@@ -336,7 +328,7 @@ static int eval_run(Ctx* c, const Fe* const* polys, const size_t* lens, size_t n
     for (size_t first = 0; first < passes.size();) {
         size_t end = first;
         while (end < passes.size() && passes[end].np == passes[first].np) end++;
-        P.passes = (const EvalPass*)base + first;
+        P.passes = pass.d + first;
         dim3 grid(max_tiles, (uint32_t)(end - first));
         switch (passes[first].np) {
 #define OPEN_EVAL_CASE(N) \
@@ -348,8 +340,7 @@ static int eval_run(Ctx* c, const Fe* const* polys, const size_t* lens, size_t n
         H2_CHECK(hipGetLastError());
         first = end;
     }
-    hipLaunchKernelGGL(open_eval_sum_kernel, dim3((uint32_t)n_queries), dim3(OPEN_MAX_THREADS), 0, s, P.partial,
-                       (const uint32_t*)(base + b_pass + b_pow), max_tiles, d_evals);
+    hipLaunchKernelGGL(open_eval_sum_kernel, dim3((uint32_t)n_queries), dim3(OPEN_MAX_THREADS), 0, s, P.partial, qt.d, max_tiles, d_evals);
     H2_CHECK(hipGetLastError());
     c->timer_end(tm, s);
     return guard.release();
@@ -368,42 +359,43 @@ static int combine_run(Ctx* c, const Fe* const* polys, uint64_t L, const Fe* sca
         return H2HIP_EINVAL;
     }
     // workspace: two scratch columns (one with a single root, none without), per-thread and per-tile carries, the remainder, the blob
-    const size_t col = al256(L * sizeof(Fe));
-    const size_t n_cols = n_roots == 0 ? 0 : (n_roots == 1 ? 1 : 2);
-    const size_t b_thr = al256(tiles * B * sizeof(Fe)), b_tile = al256(tiles * sizeof(Fe)), b_rem = 256;
-    const size_t b_ptr = al256(n_polys * sizeof(void*)), b_scal = al256(2 * n_polys * sizeof(Fu)), b_sub = al256(OPEN_MAX_SUB * sizeof(Fe)),
-                 b_pow = al256(std::max<size_t>(1, n_roots) * OPEN_POW * sizeof(Fu));
-    const size_t blob = b_ptr + b_scal + b_sub + b_pow;
+    const size_t col = L * sizeof(Fe);
+    Carve ws;
+    const size_t o_x = ws.take(n_roots >= 1 ? col : 0), o_y = ws.take(n_roots >= 2 ? col : 0);  // a column that is not there is never touched
+    const size_t o_thr = ws.take(tiles * B * sizeof(Fe)), o_tile = ws.take(tiles * sizeof(Fe)), o_rem = ws.take(sizeof(Fe));
+    Carve blob;
+    const size_t o_ptr = blob.take(n_polys * sizeof(void*)), o_scal = blob.take(2 * n_polys * sizeof(Fu)),
+                 o_sub = blob.take(OPEN_MAX_SUB * sizeof(Fe)), o_pow = blob.take(std::max<size_t>(1, n_roots) * OPEN_POW * sizeof(Fu));
+    const size_t o_blob = ws.take(blob.total);
     int rc = c->ws_acquire(s);
     if (rc) return rc;
     WsGuard guard(c, s);
-    if ((rc = c->open_ws.ensure(n_cols * col + b_thr + b_tile + b_rem + blob))) return rc;
+    if ((rc = c->open_ws.ensure(ws.total))) return rc;
     char* base = (char*)c->open_ws.p;
-    Fe* X = (Fe*)base;
-    Fe* Y = (Fe*)(base + col);
-    Fe* d_thr = (Fe*)(base + n_cols * col);
-    Fe* d_tile = (Fe*)(base + n_cols * col + b_thr);
-    Fe* d_rem = (Fe*)(base + n_cols * col + b_thr + b_tile);
-    char* d_blob = base + n_cols * col + b_thr + b_tile + b_rem;
-    std::vector<char> h(blob, 0);
-    memcpy(h.data(), polys, n_polys * sizeof(void*));
-    Fu* hs = (Fu*)(h.data() + b_ptr);
+    Fe* X = (Fe*)(base + o_x);
+    Fe* Y = (Fe*)(base + o_y);
+    Fe* d_rem = (Fe*)(base + o_rem);
+    std::vector<char> h(blob.total, 0);
+    const Blob img{h.data(), base + o_blob};
+    const Mirror<const Fe*> ptr = img.at<const Fe*>(o_ptr);
+    const Mirror<Fu> scal = img.at<Fu>(o_scal), rpow = img.at<Fu>(o_pow);
+    const Mirror<Fe> subs = img.at<Fe>(o_sub);
+    memcpy(ptr.h, polys, n_polys * sizeof(void*));
     for (size_t j = 0; j < n_polys; j++) {
-        hs[2 * j] = fu_from_ext(scalars[j]);
-        hs[2 * j + 1] = fu_neg(hs[2 * j]);
+        scal.h[2 * j] = fu_from_ext(scalars[j]);
+        scal.h[2 * j + 1] = fu_neg(scal.h[2 * j]);
     }
-    if (sub_len) memcpy(h.data() + b_ptr + b_scal, sub, sub_len * sizeof(Fe));
-    Fu* hp = (Fu*)(h.data() + b_ptr + b_scal + b_sub);
-    for (size_t t = 0; t < n_roots; t++) pow_table(roots[t], hp + t * OPEN_POW);
-    if ((rc = c->stage_h2d(d_blob, h.data(), blob, s))) return rc;
+    if (sub_len) memcpy(subs.h, sub, sub_len * sizeof(Fe));
+    for (size_t t = 0; t < n_roots; t++) pow_table(roots[t], rpow.h + t * OPEN_POW);
+    if ((rc = c->stage_h2d(img.d, img.h, blob.total, s))) return rc;
 
     CombParams P;
     memset(&P, 0, sizeof(P));
-    P.polys = (const Fe* const*)d_blob;
-    P.scal = (const Fu*)(d_blob + b_ptr);
-    P.sub = (const Fe*)(d_blob + b_ptr + b_scal);
-    P.thr = d_thr;
-    P.tile = d_tile;
+    P.polys = ptr.d;
+    P.scal = scal.d;
+    P.sub = subs.d;
+    P.thr = (Fe*)(base + o_thr);
+    P.tile = (Fe*)(base + o_tile);
     P.n_polys = (uint32_t)n_polys;
     P.sub_len = (uint32_t)sub_len;
     P.R = R;
@@ -432,7 +424,7 @@ static int combine_run(Ctx* c, const Fe* const* polys, uint64_t L, const Fe* sca
         P.w = t == 0 ? X : (Fe*)P.in;
         P.out = P.last ? d_out : (t % 2 ? X : Y);
         P.rem = t == 0 && want_rem ? d_rem : nullptr;
-        P.rpow = (const Fu*)(d_blob + b_ptr + b_scal + b_sub) + t * OPEN_POW;
+        P.rpow = rpow.d + t * OPEN_POW;
         uint32_t lp = 0;
         while (((uint64_t)OPEN_MAX_THREADS << lp) < P.tiles) lp++;
         P.log_per = lp;
@@ -455,38 +447,9 @@ static int combine_run(Ctx* c, const Fe* const* polys, uint64_t L, const Fe* sca
 
 using namespace h2;
 
-static inline Fe open_fe(const uint64_t v[4]) {
-    Fe o;
-    memcpy(o.l, v, 32);
-    return o;
-}
-
 extern "C" {
 // ---- C ABI (include/halo2hip.h, "opening") ---------------------------------------------------------------------------------
 // Here rather than in api.hip for the reason product.hip gives: api.hip is also compiled alone against a stub runtime.
-static int open_ptrs_check(const char* what, const void* const* p, size_t count, const char* name) {
-    if (count && !p) {
-        set_error("%s: null %s", what, name);
-        return H2HIP_EINVAL;
-    }
-    for (size_t i = 0; i < count; i++)
-        if (!p[i]) {
-            set_error("%s: %s[%zu] is null", what, name, i);
-            return H2HIP_EINVAL;
-        }
-    return 0;
-}
-
-static int open_frs_check(const char* what, const uint64_t* v, size_t count, const char* name) {
-    if (count && !v) {
-        set_error("%s: null %s", what, name);
-        return H2HIP_EINVAL;
-    }
-    for (size_t i = 0; i < count; i++)
-        if (check_fr(v + 4 * i, name)) return H2HIP_EINVAL;
-    return 0;
-}
-
 static int eval_check(const void* const* polys, const size_t* lens, size_t n_polys, const uint32_t* query_poly, const uint64_t* points,
                       size_t n_queries, const uint64_t* evals) {
     const char* what = "eval_polynomials";
@@ -517,14 +480,14 @@ static int eval_check(const void* const* polys, const size_t* lens, size_t n_pol
             set_error("%s: query_poly[%zu] = %u out of range (%zu polynomials)", what, q, query_poly[q], n_polys);
             return H2HIP_EINVAL;
         }
-    return open_frs_check(what, points, n_queries, "point");
+    return check_frs(what, points, n_queries, "point");
 }
 
 static int eval_finish(Ctx* c, const Fe* const* d_polys, const size_t* lens, size_t n_polys, const uint32_t* query_poly, const uint64_t* points,
                        size_t n_queries, uint64_t* evals, hipStream_t s) {
     std::vector<Fe> pts(n_queries);
     memcpy(pts.data(), points, n_queries * sizeof(Fe));
-    int rc = c->open_io.ensure(al256(n_queries * sizeof(Fe)));
+    int rc = c->open_io.ensure(align256(n_queries * sizeof(Fe)));
     if (rc) return rc;
     // open_io holds the evaluations at its start; the host form's uploaded polynomials follow at an offset of their own
     if ((rc = eval_run(c, d_polys, lens, n_polys, query_poly, pts.data(), n_queries, (Fe*)c->open_io.p, s))) return rc;
@@ -558,10 +521,10 @@ int h2hip_eval_polynomials_bn254(const uint64_t* const* polys, const size_t* len
     std::vector<char> queried(n_polys, 0);
     for (size_t q = 0; q < n_queries; q++) queried[query_poly[q]] = 1;
     std::vector<const Fe*> d(n_polys, nullptr);
-    const size_t head = al256(n_queries * sizeof(Fe));
+    const size_t head = align256(n_queries * sizeof(Fe));
     size_t bytes = head;
     for (size_t j = 0; j < n_polys; j++)
-        if (queried[j] && lens[j] && !(d[j] = pinned_column_lookup(c, polys[j], lens[j]))) bytes += al256(lens[j] * sizeof(Fe));
+        if (queried[j] && lens[j] && !(d[j] = pinned_column_lookup(c, polys[j], lens[j]))) bytes += align256(lens[j] * sizeof(Fe));
     int rc = c->open_io.ensure(bytes);
     if (rc) return rc;
     size_t off = head;
@@ -569,7 +532,7 @@ int h2hip_eval_polynomials_bn254(const uint64_t* const* polys, const size_t* len
         if (queried[j] && lens[j] && !d[j]) {
             d[j] = (const Fe*)((char*)c->open_io.p + off);
             H2_CHECK(hipMemcpyAsync((void*)d[j], polys[j], lens[j] * sizeof(Fe), hipMemcpyHostToDevice, s));
-            off += al256(lens[j] * sizeof(Fe));
+            off += align256(lens[j] * sizeof(Fe));
         }
     return eval_finish(c, d.data(), lens, n_polys, query_poly, points, n_queries, evals, s);
 }
@@ -614,10 +577,10 @@ static int combine_check(const void* const* polys, size_t len, const uint64_t* s
         return H2HIP_EINVAL;
     }
     if (check_fr(scale, "scale")) return H2HIP_EINVAL;
-    if (open_frs_check(what, scalars, n_polys, "scalar") || open_frs_check(what, sub, sub_len, "sub") ||
-        open_frs_check(what, roots, n_roots, "root"))
+    if (check_frs(what, scalars, n_polys, "scalar") || check_frs(what, sub, sub_len, "sub") ||
+        check_frs(what, roots, n_roots, "root"))
         return H2HIP_EINVAL;
-    if (len && open_ptrs_check(what, polys, n_polys, "polys")) return H2HIP_EINVAL;
+    if (len && check_ptrs(what, polys, n_polys, "polys")) return H2HIP_EINVAL;
     for (size_t j = 0; j < n_polys && len; j++)
         if (polys[j] == out) {
             set_error("%s: out aliases polys[%zu]", what, j);
@@ -638,7 +601,7 @@ int h2hip_poly_combine_bn254_fr_device(const void* const* d_polys, size_t len, c
     if (!accumulate && out_len > Lout) H2_CHECK(hipMemsetAsync((Fe*)d_out + Lout, 0, (out_len - Lout) * sizeof(Fe), s));
     std::vector<Fe> h_rem(1);
     int rc = combine_run(en.c, (const Fe* const*)d_polys, len, (const Fe*)scalars, n_polys, (const Fe*)sub, sub_len, (const Fe*)roots, n_roots,
-                         open_fe(scale), accumulate != 0, (Fe*)d_out, remainder != nullptr, h_rem.data(), s);
+                         fe_from_u64x4(scale), accumulate != 0, (Fe*)d_out, remainder != nullptr, h_rem.data(), s);
     if (rc) return rc;
     if (remainder) memcpy(remainder, h_rem.data(), sizeof(Fe));
     return 0;
@@ -658,7 +621,7 @@ int h2hip_poly_combine_bn254_fr(const uint64_t* const* polys, size_t len, const 
     if (en.rc) return en.rc;
     Ctx* c = en.c;
     hipStream_t s = c->stream;
-    const size_t bytes = al256(len * sizeof(Fe));
+    const size_t bytes = align256(len * sizeof(Fe));
     std::vector<const Fe*> d(n_polys, nullptr);
     size_t need = bytes;  // the output first
     for (size_t j = 0; j < n_polys; j++)
@@ -675,7 +638,7 @@ int h2hip_poly_combine_bn254_fr(const uint64_t* const* polys, size_t len, const 
         }
     if (accumulate && Lout) H2_CHECK(hipMemcpyAsync(d_out, out, Lout * sizeof(Fe), hipMemcpyHostToDevice, s));
     std::vector<Fe> h_rem(1);
-    rc = combine_run(c, d.data(), len, (const Fe*)scalars, n_polys, (const Fe*)sub, sub_len, (const Fe*)roots, n_roots, open_fe(scale),
+    rc = combine_run(c, d.data(), len, (const Fe*)scalars, n_polys, (const Fe*)sub, sub_len, (const Fe*)roots, n_roots, fe_from_u64x4(scale),
                      accumulate != 0, d_out, remainder != nullptr, h_rem.data(), s);
     if (rc) return rc;
     if (Lout) H2_CHECK(hipMemcpyAsync(out, d_out, Lout * sizeof(Fe), hipMemcpyDeviceToHost, s));

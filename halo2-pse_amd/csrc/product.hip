@@ -23,7 +23,7 @@
 #include <string.h>
 #include <vector>
 #include "engine.h"
-#include "field.h"
+#include "fe_io.h"
 
 namespace h2 {
 
@@ -65,19 +65,6 @@ enum { PROD_PERM = 0, PROD_LOOKUP = 1, PROD_INVERT = 2 };
 
 __device__ __forceinline__ Fe prod_one() { return fe_one<FrP>(); }
 __device__ __forceinline__ Fe prod_nz(const Fe& x) { return fe_is_zero(x) ? prod_one() : x; }
-
-__device__ __forceinline__ Fe ld(const Fe* p, uint64_t i) {
-    const uint4* q = (const uint4*)(p + i);
-    uint4 a = q[0], b = q[1];
-    Fe o;
-    o.l[0] = a.x, o.l[1] = a.y, o.l[2] = a.z, o.l[3] = a.w, o.l[4] = b.x, o.l[5] = b.y, o.l[6] = b.z, o.l[7] = b.w;
-    return o;
-}
-__device__ __forceinline__ void st(Fe* p, uint64_t i, const Fe& v) {
-    uint4* q = (uint4*)(p + i);
-    q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
-    q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
-}
 
 // ---- inversion: binary extended Euclid (Guide to ECC, Alg. 2.22) on the canonical integer, one lane ----------------------
 H2_HD bool big_is_one(const Fe& a) {
@@ -188,8 +175,8 @@ __global__ __launch_bounds__(PROD_THREADS) void prod_fraction_kernel(const ProdD
         const uint64_t i1 = i0 + P.R < P.L ? i0 + P.R : P.L;
         if (KIND == PROD_INVERT) {
             for (uint64_t i = i0; i < i1; i++) {
-                Fe a = ld(D.z, i);
-                st(D.w, i, a);
+                Fe a = fe_ld(D.z, i);
+                fe_st(D.w, i, a);
                 pe = fe_mul<FrP>(pe, prod_nz(a));
             }
             pd = pe;
@@ -210,27 +197,27 @@ __global__ __launch_bounds__(PROD_THREADS) void prod_fraction_kernel(const ProdD
                     const uint64_t t = i - 1;
                     if (KIND == PROD_PERM) {
                         for (uint32_t c = 0; c < D.ncols; c++) {
-                            Fe f = fe_add<FrP>(fe_add<FrP>(ld(D.p[c], t), fe_mul<FrP>(bw, P.delta_pow[D.col0 + c])), P.gamma);
+                            Fe f = fe_add<FrP>(fe_add<FrP>(fe_ld(D.p[c], t), fe_mul<FrP>(bw, P.delta_pow[D.col0 + c])), P.gamma);
                             e = c ? fe_mul<FrP>(e, f) : f;
                         }
                         bw = fe_mul<FrP>(bw, omega);
                     } else {
-                        e = fe_mul<FrP>(fe_add<FrP>(ld(D.p[0], t), P.beta), fe_add<FrP>(ld(D.p[1], t), P.gamma));
+                        e = fe_mul<FrP>(fe_add<FrP>(fe_ld(D.p[0], t), P.beta), fe_add<FrP>(fe_ld(D.p[1], t), P.gamma));
                     }
                 }
                 if (i < P.u) {  // d_i = den_i
                     if (KIND == PROD_PERM) {
                         for (uint32_t c = 0; c < D.ncols; c++) {
-                            Fe f = fe_add<FrP>(fe_add<FrP>(ld(D.p[c], i), fe_mul<FrP>(P.beta, ld(D.s[c], i))), P.gamma);
+                            Fe f = fe_add<FrP>(fe_add<FrP>(fe_ld(D.p[c], i), fe_mul<FrP>(P.beta, fe_ld(D.s[c], i))), P.gamma);
                             d = c ? fe_mul<FrP>(d, f) : f;
                         }
                     } else {
-                        d = fe_mul<FrP>(fe_add<FrP>(ld(D.s[0], i), P.beta), fe_add<FrP>(ld(D.s[1], i), P.gamma));
+                        d = fe_mul<FrP>(fe_add<FrP>(fe_ld(D.s[0], i), P.beta), fe_add<FrP>(fe_ld(D.s[1], i), P.gamma));
                     }
                     if (fe_is_zero(d) && zmin == 0xffffffffu) zmin = (uint32_t)i;
                 }
-                st(D.z, i, e);
-                st(D.w, i, d);
+                fe_st(D.z, i, e);
+                fe_st(D.w, i, d);
                 pe = fe_mul<FrP>(pe, e);
                 pd = fe_mul<FrP>(pd, prod_nz(d));
             }
@@ -238,8 +225,8 @@ __global__ __launch_bounds__(PROD_THREADS) void prod_fraction_kernel(const ProdD
         }
     }
     const uint64_t ti = (uint64_t)tile * PROD_THREADS + tid;
-    st(D.thr_e, ti, pe);
-    st(D.thr_d, ti, pd);
+    fe_st(D.thr_e, ti, pe);
+    fe_st(D.thr_d, ti, pd);
     // tile products: a tree over the threads
     Fe te, td;
     lds[tid] = pe;
@@ -258,8 +245,8 @@ __global__ __launch_bounds__(PROD_THREADS) void prod_fraction_kernel(const ProdD
     }
     td = lds[0];
     if (tid == 0) {
-        st(D.tile_e, tile, te);
-        st(D.tile_d, tile, td);
+        fe_st(D.tile_e, tile, te);
+        fe_st(D.tile_d, tile, td);
     }
 }
 
@@ -271,24 +258,24 @@ __global__ __launch_bounds__(PROD_THREADS) void prod_tiles_kernel(const ProdDesc
     Fe carry_e = prod_one(), carry_d = prod_one(), tot;
     for (uint32_t base = 0; base < T; base += PROD_THREADS) {  // forward, exclusive
         const uint32_t j = base + tid;
-        Fe v = j < T ? ld(D.tile_e, j) : prod_one();
+        Fe v = j < T ? fe_ld(D.tile_e, j) : prod_one();
         Fe ex = block_scan_excl(v, lds, false, &tot);
-        if (j < T) st(D.tile_e, j, fe_mul<FrP>(carry_e, ex));
+        if (j < T) fe_st(D.tile_e, j, fe_mul<FrP>(carry_e, ex));
         carry_e = fe_mul<FrP>(carry_e, tot);
     }
     for (uint32_t base = 0; base < T; base += PROD_THREADS) {  // backward, exclusive: chunks from the last tile down
         const int64_t j = (int64_t)T - 1 - base - (PROD_THREADS - 1 - tid);  // thread order == tile order inside the chunk
-        Fe v = j >= 0 ? ld(D.tile_d, (uint64_t)j) : prod_one();
+        Fe v = j >= 0 ? fe_ld(D.tile_d, (uint64_t)j) : prod_one();
         Fe ex = block_scan_excl(v, lds, true, &tot);
-        if (j >= 0) st(D.tile_d, (uint64_t)j, fe_mul<FrP>(carry_d, ex));
+        if (j >= 0) fe_st(D.tile_d, (uint64_t)j, fe_mul<FrP>(carry_d, ex));
         carry_d = fe_mul<FrP>(carry_d, tot);
     }
     if (tid == 0) {
         Fe inv = fr_inv_binary(carry_d);  // prod d' is never zero
-        st(D.meta, 0, inv);
+        fe_st(D.meta, 0, inv);
         Fe end = fe_mul<FrP>(carry_e, inv);  // z[u] / last_z = prod_{t<u} num_t / den_t while no denominator is zero
         if (*D.j0 != (uint32_t)P.u) end = fe_zero<FrP>();
-        st(D.meta, 1, end);
+        fe_st(D.meta, 1, end);
     }
 }
 
@@ -300,44 +287,44 @@ __global__ __launch_bounds__(PROD_THREADS) void prod_apply_kernel(const ProdDesc
     const ProdDesc D = descs[a];
     const uint32_t tid = threadIdx.x, tile = blockIdx.x;
     const uint64_t ti = (uint64_t)tile * PROD_THREADS + tid;
-    Fe scale = ld(D.meta, 0);
+    Fe scale = fe_ld(D.meta, 0);
     uint64_t j0 = P.L;
     if (KIND != PROD_INVERT) {
-        for (uint32_t s = D.chain_first; s < a; s++) scale = fe_mul<FrP>(scale, ld(descs[s].meta, 1));  // last_z
+        for (uint32_t s = D.chain_first; s < a; s++) scale = fe_mul<FrP>(scale, fe_ld(descs[s].meta, 1));  // last_z
         j0 = *D.j0;
     }
-    Fe fwd = fe_mul<FrP>(ld(D.tile_e, tile), block_scan_excl(ld(D.thr_e, ti), lds, false, nullptr));
-    Fe bwd = fe_mul<FrP>(ld(D.tile_d, tile), block_scan_excl(ld(D.thr_d, ti), lds, true, nullptr));
+    Fe fwd = fe_mul<FrP>(fe_ld(D.tile_e, tile), block_scan_excl(fe_ld(D.thr_e, ti), lds, false, nullptr));
+    Fe bwd = fe_mul<FrP>(fe_ld(D.tile_d, tile), block_scan_excl(fe_ld(D.thr_d, ti), lds, true, nullptr));
     const uint64_t i0 = ti * P.R;
     if (i0 < P.L) {
         const uint64_t i1 = i0 + P.R < P.L ? i0 + P.R : P.L;
         for (uint64_t i = i0; i < i1; i++) {  // forward: prefix of e (inclusive for the products, exclusive for the inversion)
-            Fe e = ld(D.e, i);
+            Fe e = fe_ld(D.e, i);
             if (KIND == PROD_INVERT) {
-                st(D.z, i, fwd);
+                fe_st(D.z, i, fwd);
                 fwd = fe_mul<FrP>(fwd, prod_nz(e));
             } else {
                 fwd = fe_mul<FrP>(fwd, e);
-                st(D.z, i, fwd);
+                fe_st(D.z, i, fwd);
             }
         }
         for (uint64_t i = i1; i-- > i0;) {  // backward: suffix of d', the scale, the zero rule
-            Fe d = ld(D.w, i);
+            Fe d = fe_ld(D.w, i);
             Fe v;
             if (KIND == PROD_INVERT) {
-                v = fe_mul<FrP>(fe_mul<FrP>(ld(D.z, i), bwd), scale);
+                v = fe_mul<FrP>(fe_mul<FrP>(fe_ld(D.z, i), bwd), scale);
                 bwd = fe_mul<FrP>(bwd, prod_nz(d));
                 if (fe_is_zero(d)) v = fe_zero<FrP>();
             } else {
                 bwd = fe_mul<FrP>(bwd, prod_nz(d));
-                v = fe_mul<FrP>(fe_mul<FrP>(ld(D.z, i), bwd), scale);
+                v = fe_mul<FrP>(fe_mul<FrP>(fe_ld(D.z, i), bwd), scale);
                 if (i > j0) v = fe_zero<FrP>();
             }
-            st(D.z, i, v);
+            fe_st(D.z, i, v);
         }
     }
     if (KIND != PROD_INVERT && tile == 0)
-        for (uint32_t j = tid; j < P.bf; j += PROD_THREADS) st(D.z, P.u + 1 + j, D.blind[j]);
+        for (uint32_t j = tid; j < P.bf; j += PROD_THREADS) fe_st(D.z, P.u + 1 + j, D.blind[j]);
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
@@ -348,8 +335,6 @@ static uint32_t prod_rows_per_thread(uint64_t L, size_t n_args) {
     while (R < 16 && (uint64_t)R * 2 <= want) R *= 2;
     return R;
 }
-
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // kind: PROD_PERM / PROD_LOOKUP / PROD_INVERT.  cols / perms: host arrays of device pointers (for lookups cols[2j], cols[2j + 1] =
 // A, S and perms[2j], perms[2j + 1] = A', S' of lookup j).  n_args outputs z[a] (2^k or n elements, device).  Enqueued on s.
@@ -364,84 +349,84 @@ static int products_run(Ctx* c, int kind, uint64_t n, uint64_t L, uint64_t u, co
         set_error("products: %llu tiles", (unsigned long long)tiles);
         return H2HIP_EINVAL;
     }
-    // workspace: w (L each), per-thread products (2 x tiles x 256 each), tile products (2 x tiles), meta (2), j0
-    const size_t w_bytes = align256(L * sizeof(Fe));
-    const size_t thr_bytes = align256(tiles * PROD_THREADS * sizeof(Fe));
-    const size_t tile_bytes = align256(tiles * sizeof(Fe));
-    const size_t per_arg = w_bytes + 2 * thr_bytes + 2 * tile_bytes + align256(2 * sizeof(Fe));
+    // one argument's workspace: w (L), per-thread products (2 x tiles x 256), tile products (2 x tiles), meta (2)
+    Carve arg;
+    const size_t o_w = arg.take(L * sizeof(Fe));
+    const size_t o_thr_e = arg.take(tiles * PROD_THREADS * sizeof(Fe)), o_thr_d = arg.take(tiles * PROD_THREADS * sizeof(Fe));
+    const size_t o_tile_e = arg.take(tiles * sizeof(Fe)), o_tile_d = arg.take(tiles * sizeof(Fe));
+    const size_t o_meta = arg.take(2 * sizeof(Fe));
     // the blob the kernels read: descriptors, pointer tables, omega^(2^b), delta^c, blinding
     const size_t n_ptr = kind == PROD_PERM ? 2 * (size_t)n_columns : (kind == PROD_LOOKUP ? 4 * n_args : 0);
     const size_t n_delta = kind == PROD_PERM ? n_columns : 0;
-    const size_t blob_desc = align256(n_args * sizeof(ProdDesc));
-    const size_t blob_ptr = align256(n_ptr * sizeof(void*));
-    const size_t blob_fe = align256((32 + n_delta + n_args * (size_t)bf) * sizeof(Fe));
-    const size_t j0_bytes = align256(n_args * sizeof(uint32_t));
-    const size_t blob = blob_desc + blob_ptr + blob_fe;
+    Carve blob;
+    const size_t o_desc = blob.take(n_args * sizeof(ProdDesc));
+    const size_t o_ptr = blob.take(n_ptr * sizeof(void*));
+    const size_t o_fe = blob.take((32 + n_delta + n_args * (size_t)bf) * sizeof(Fe));
+    // the call's workspace: every argument's, the j0 words, the blob
+    Carve ws;
+    const size_t o_args = ws.take(n_args * arg.total), o_j0 = ws.take(n_args * sizeof(uint32_t)), o_blob = ws.take(blob.total);
     int rc = c->ws_acquire(s);
     if (rc) return rc;
     WsGuard guard(c, s);
-    if ((rc = c->prod_ws.ensure(n_args * per_arg + j0_bytes + blob))) return rc;
+    if ((rc = c->prod_ws.ensure(ws.total))) return rc;
     char* base = (char*)c->prod_ws.p;
-    uint32_t* d_j0 = (uint32_t*)(base + n_args * per_arg);
-    char* d_blob = base + n_args * per_arg + j0_bytes;
-    const ProdDesc* d_desc = (const ProdDesc*)d_blob;
-    const Fe** d_ptr = (const Fe**)(d_blob + blob_desc);
-    Fe* d_fe = (Fe*)(d_blob + blob_desc + blob_ptr);
+    uint32_t* d_j0 = (uint32_t*)(base + o_j0);
 
-    std::vector<char> h(blob, 0);
-    ProdDesc* hd = (ProdDesc*)h.data();
-    const Fe** hp = (const Fe**)(h.data() + blob_desc);
-    Fe* hf = (Fe*)(h.data() + blob_desc + blob_ptr);
+    std::vector<char> h(blob.total, 0);
+    const Blob img{h.data(), base + o_blob};
+    const Mirror<ProdDesc> desc = img.at<ProdDesc>(o_desc);
+    const Mirror<const Fe*> ptr = img.at<const Fe*>(o_ptr);
+    const Mirror<Fe> fe = img.at<Fe>(o_fe);
     Fe w = omega;
     for (int b = 0; b < 32; b++) {  // omega^(2^b)
-        hf[b] = w;
+        fe.h[b] = w;
         w = fe_mul<FrP>(w, w);
     }
     Fe dl = fe_one<FrP>();
     for (size_t c2 = 0; c2 < n_delta; c2++) {
-        hf[32 + c2] = dl;
+        fe.h[32 + c2] = dl;
         dl = fe_mul<FrP>(dl, delta);
     }
-    if (bf) memcpy(hf + 32 + n_delta, blinding, n_args * (size_t)bf * sizeof(Fe));
+    if (bf) memcpy(fe.h + 32 + n_delta, blinding, n_args * (size_t)bf * sizeof(Fe));
     for (size_t a = 0; a < n_args; a++) {
-        ProdDesc& D = hd[a];
-        char* ab = base + a * per_arg;
+        ProdDesc& D = desc.h[a];
+        char* ab = base + o_args + a * arg.total;
         D.z = z[a];
-        D.w = (Fe*)ab;
+        D.w = (Fe*)(ab + o_w);
         D.e = kind == PROD_INVERT ? D.w : D.z;
-        D.thr_e = (Fe*)(ab + w_bytes);
-        D.thr_d = (Fe*)(ab + w_bytes + thr_bytes);
-        D.tile_e = (Fe*)(ab + w_bytes + 2 * thr_bytes);
-        D.tile_d = (Fe*)(ab + w_bytes + 2 * thr_bytes + tile_bytes);
-        D.meta = (Fe*)(ab + w_bytes + 2 * thr_bytes + 2 * tile_bytes);
+        D.thr_e = (Fe*)(ab + o_thr_e);
+        D.thr_d = (Fe*)(ab + o_thr_d);
+        D.tile_e = (Fe*)(ab + o_tile_e);
+        D.tile_d = (Fe*)(ab + o_tile_d);
+        D.meta = (Fe*)(ab + o_meta);
         D.j0 = d_j0 + a;
-        D.blind = d_fe + 32 + n_delta + a * (size_t)bf;
+        D.blind = fe.d + 32 + n_delta + a * (size_t)bf;
         D.chain_first = kind == PROD_PERM ? 0 : (uint32_t)a;
         if (kind == PROD_PERM) {
             D.col0 = (uint32_t)(a * chunk_len);
             D.ncols = (uint32_t)(n_columns - D.col0 < chunk_len ? n_columns - D.col0 : chunk_len);
-            D.p = d_ptr + D.col0;
-            D.s = d_ptr + n_columns + D.col0;
+            D.p = ptr.d + D.col0;
+            D.s = ptr.d + n_columns + D.col0;
         } else if (kind == PROD_LOOKUP) {
             D.ncols = 2;
-            D.p = d_ptr + 4 * a;
-            D.s = d_ptr + 4 * a + 2;
+            D.p = ptr.d + 4 * a;
+            D.s = ptr.d + 4 * a + 2;
         }
     }
     if (kind == PROD_PERM) {
         for (uint32_t j = 0; j < n_columns; j++) {
-            hp[j] = cols[j];
-            hp[n_columns + j] = perms[j];
+            ptr.h[j] = cols[j];
+            ptr.h[n_columns + j] = perms[j];
         }
     } else if (kind == PROD_LOOKUP) {
         for (size_t a = 0; a < n_args; a++) {
-            hp[4 * a] = cols[2 * a];
-            hp[4 * a + 1] = cols[2 * a + 1];
-            hp[4 * a + 2] = perms[2 * a];
-            hp[4 * a + 3] = perms[2 * a + 1];
+            ptr.h[4 * a] = cols[2 * a];
+            ptr.h[4 * a + 1] = cols[2 * a + 1];
+            ptr.h[4 * a + 2] = perms[2 * a];
+            ptr.h[4 * a + 3] = perms[2 * a + 1];
         }
     }
-    if ((rc = c->stage_h2d(d_blob, h.data(), blob, s))) return rc;
+    if ((rc = c->stage_h2d(img.d, img.h, blob.total, s))) return rc;
     H2_CHECK(hipMemsetD32Async((hipDeviceptr_t)d_j0, (int)(uint32_t)u, n_args, s));
 
     ProdParams P;
@@ -454,24 +439,24 @@ static int products_run(Ctx* c, int kind, uint64_t n, uint64_t L, uint64_t u, co
     P.bf = bf;
     P.beta = beta;
     P.gamma = gamma;
-    P.omega_pow2 = d_fe;
-    P.delta_pow = d_fe + 32;
+    P.omega_pow2 = fe.d;
+    P.delta_pow = fe.d + 32;
     dim3 grid((uint32_t)tiles, (uint32_t)n_args);
     int tm = c->timer_begin("products", s);
     if (kind == PROD_PERM) {
-        hipLaunchKernelGGL(prod_fraction_kernel<PROD_PERM>, grid, dim3(PROD_THREADS), 0, s, d_desc, P);
+        hipLaunchKernelGGL(prod_fraction_kernel<PROD_PERM>, grid, dim3(PROD_THREADS), 0, s, desc.d, P);
     } else if (kind == PROD_LOOKUP) {
-        hipLaunchKernelGGL(prod_fraction_kernel<PROD_LOOKUP>, grid, dim3(PROD_THREADS), 0, s, d_desc, P);
+        hipLaunchKernelGGL(prod_fraction_kernel<PROD_LOOKUP>, grid, dim3(PROD_THREADS), 0, s, desc.d, P);
     } else {
-        hipLaunchKernelGGL(prod_fraction_kernel<PROD_INVERT>, grid, dim3(PROD_THREADS), 0, s, d_desc, P);
+        hipLaunchKernelGGL(prod_fraction_kernel<PROD_INVERT>, grid, dim3(PROD_THREADS), 0, s, desc.d, P);
     }
     H2_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(prod_tiles_kernel, dim3((uint32_t)n_args), dim3(PROD_THREADS), 0, s, d_desc, P);
+    hipLaunchKernelGGL(prod_tiles_kernel, dim3((uint32_t)n_args), dim3(PROD_THREADS), 0, s, desc.d, P);
     H2_CHECK(hipGetLastError());
     if (kind == PROD_INVERT) {
-        hipLaunchKernelGGL(prod_apply_kernel<PROD_INVERT>, grid, dim3(PROD_THREADS), 0, s, d_desc, P);
+        hipLaunchKernelGGL(prod_apply_kernel<PROD_INVERT>, grid, dim3(PROD_THREADS), 0, s, desc.d, P);
     } else {
-        hipLaunchKernelGGL(prod_apply_kernel<PROD_PERM>, grid, dim3(PROD_THREADS), 0, s, d_desc, P);
+        hipLaunchKernelGGL(prod_apply_kernel<PROD_PERM>, grid, dim3(PROD_THREADS), 0, s, desc.d, P);
     }
     H2_CHECK(hipGetLastError());
     c->timer_end(tm, s);
@@ -503,45 +488,17 @@ int batch_invert_device(Ctx* c, Fe* d_a, uint64_t n, hipStream_t s) {
 
 using namespace h2;
 
-static inline Fe fe_from_u64x4(const uint64_t v[4]) {
-    Fe o;
-    memcpy(o.l, v, 32);
-    return o;
-}
-
 extern "C" {
 // ---- C ABI (include/halo2hip.h, "grand products") ----------------------------------------------------------------------------------
 // Here rather than in api.hip: api.hip is also compiled alone, as plain C++ against a stub runtime, for the ThreadSanitizer test of the
 // engine's host logic, and the stubs stand in for the kernels of the other translation units only.
 static int products_check_common(const char* what, uint32_t k, uint32_t bf, const uint64_t* blinding, size_t n_outputs) {
-    if (k > 28) {
-        set_error("%s: k = %u > 28", what, k);
-        return H2HIP_EINVAL;
-    }
-    if ((uint64_t)bf + 1 >= (1ull << k)) {
-        set_error("%s: blinding_factors + 1 >= 2^k", what);
-        return H2HIP_EINVAL;
-    }
+    if (int rc = check_k_blinding(what, k, bf)) return rc;
     if (bf && n_outputs && !blinding) {
         set_error("%s: null blinding", what);
         return H2HIP_EINVAL;
     }
-    for (size_t i = 0; i < n_outputs * (size_t)bf; i++)
-        if (check_fr(blinding + 4 * i, "blinding value")) return H2HIP_EINVAL;
-    return 0;
-}
-
-static int ptrs_check(const char* what, const void* const* p, size_t count, const char* name) {
-    if (count && !p) {
-        set_error("%s: null %s", what, name);
-        return H2HIP_EINVAL;
-    }
-    for (size_t i = 0; i < count; i++)
-        if (!p[i]) {
-            set_error("%s: %s[%zu] is null", what, name, i);
-            return H2HIP_EINVAL;
-        }
-    return 0;
+    return check_frs(what, blinding, n_outputs * (size_t)bf, "blinding value");
 }
 
 static int permutation_check(uint32_t k, const uint64_t omega[4], const uint64_t delta[4], const uint64_t beta[4], const uint64_t gamma[4],
@@ -559,7 +516,7 @@ static int permutation_check(uint32_t k, const uint64_t omega[4], const uint64_t
     if (check_fr(omega, "omega") || check_fr(delta, "delta") || check_fr(beta, "beta") || check_fr(gamma, "gamma")) return H2HIP_EINVAL;
     const size_t n_sets = ((size_t)n_columns + chunk_len - 1) / chunk_len;
     if (int rc = products_check_common(what, k, bf, blinding, n_sets)) return rc;
-    if (ptrs_check(what, columns, n_columns, "columns") || ptrs_check(what, permutations, n_columns, "permutations") || ptrs_check(what, z, n_sets, "z"))
+    if (check_ptrs(what, columns, n_columns, "columns") || check_ptrs(what, permutations, n_columns, "permutations") || check_ptrs(what, z, n_sets, "z"))
         return H2HIP_EINVAL;
     return 0;
 }
@@ -577,8 +534,8 @@ static int lookup_check(uint32_t k, const uint64_t beta[4], const uint64_t gamma
         return H2HIP_EINVAL;
     }
     if (int rc = products_check_common(what, k, bf, blinding, count)) return rc;
-    if (ptrs_check(what, a, count, "compressed_input") || ptrs_check(what, s, count, "compressed_table") ||
-        ptrs_check(what, ap, count, "permuted_input") || ptrs_check(what, sp, count, "permuted_table") || ptrs_check(what, z, count, "z"))
+    if (check_ptrs(what, a, count, "compressed_input") || check_ptrs(what, s, count, "compressed_table") ||
+        check_ptrs(what, ap, count, "permuted_input") || check_ptrs(what, sp, count, "permuted_table") || check_ptrs(what, z, count, "z"))
         return H2HIP_EINVAL;
     return 0;
 }
