@@ -2272,9 +2272,11 @@ int h2hip_debug_set_msm_heavy_div(size_t d) {
     return 0;
 }
 
-// tuning hook: g_to_lagrange layers with one quad of lanes per butterfly up to k = 14 (1, default) or one lane (0)
+// tuning hook: g_to_lagrange layers up to k = 14 -- bit 0: one quad of lanes per butterfly (1, default) or one lane (0); bit 1 set: a
+// normalisation after every layer (default clear: the points stay XYZZ between the layers)
 int h2hip_debug_set_g2l_quad(int on) {
-    ecfft_set_quad(on != 0);
+    ecfft_set_quad((on & 1) != 0);
+    ecfft_set_lazy((on & 2) == 0);
     return 0;
 }
 

@@ -190,7 +190,9 @@ def test_gpu_best_fft_g1_vs_oracle(h2, oracle, k):
 @pytest.mark.parametrize("k", [1, 2, 5, 9, 13, 14])
 def test_gpu_small_transforms_lazy_and_normalised_paths_agree(h2, oracle, k):
     """k <= 14: the layers keep their points XYZZ and normalise once at the end (round 4) -- same affine output as round 3's path (a
-    normalisation after every layer), as the one-lane ladder, and as the oracle; identities and repeated points among the inputs"""
+    normalisation after every layer), as the one-lane ladder, and as the oracle.  One input is the identity and g[6] repeats g[1], but
+    after the bit reversal those two never meet in a butterfly: no addition here doubles or cancels.  Inputs that make the butterflies
+    exceptional cases of the group law are in test_g1_fft_edges.py"""
     import ctypes
     h2.init()
     L = h2.lib()
