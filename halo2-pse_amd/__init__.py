@@ -453,6 +453,103 @@ def commit_permuted(params, domain, lookups, theta, blinding, blinding_factors, 
     return out
 
 
+# ------------------------------------------------------------------ witness check: MockProver::verify's three column-wide loops
+def _check_out(items, max_rows):
+    max_rows = int(max_rows)
+    counts = np.zeros(max(1, items), dtype=np.uint64)
+    rows = np.full((max(1, items), max(1, max_rows)), 0xFFFFFFFF, dtype=np.uint32)
+    return counts, rows, (_p(rows) if max_rows else None)
+
+
+def _check_result(counts, rows, items, max_rows):
+    return counts[:items], rows[:items, :int(max_rows)]
+
+
+def check_gates(k, graphs, fixed=(), advice=(), instance=(), challenges=(), max_rows=16):
+    """MockProver::verify's gate loop (dev.rs:676-746) over all 2^k rows: graphs are flattened evaluation.gate_check_graphs, columns
+    (2^k, 4) uint64 Lagrange values.  Returns (counts, rows): counts[g] rows fail polynomial g, rows[g] holds the lowest max_rows of
+    them in ascending order, then 0xFFFFFFFF."""
+    n = 1 << int(k)
+    fx, ad, ins = _cols(fixed, n, "fixed"), _cols(advice, n, "advice"), _cols(instance, n, "instance")
+    from .evaluation import graph_array
+    arr, keep = graph_array(graphs)
+    ch, n_ch = _lookup_challenges(challenges)
+    counts, rows, prow = _check_out(len(graphs), max_rows)
+    _check(lib().h2hip_check_gates_bn254(ctypes.c_uint32(k), _host_ptrs(fx), ctypes.c_uint32(len(fx)), _host_ptrs(ad), ctypes.c_uint32(len(ad)),
+                                         _host_ptrs(ins), ctypes.c_uint32(len(ins)), _p(ch), ctypes.c_uint32(n_ch), arr,
+                                         ctypes.c_size_t(len(graphs)), ctypes.c_uint32(max_rows), _p(counts), prow), "h2hip_check_gates_bn254")
+    del keep
+    return _check_result(counts, rows, len(graphs), max_rows)
+
+
+def _check_mapping(mapping, n):
+    mp = np.ascontiguousarray(mapping, dtype=np.uint32)
+    if mp.ndim != 3 or mp.shape[1:] != (n, 2):
+        raise ValueError("mapping: expected shape (m, %d, 2), got %s" % (n, mp.shape))
+    return mp
+
+
+def check_permutation(k, columns, mapping, max_rows=16):
+    """MockProver::verify's copy-constraint loop (dev.rs:889-931): columns are the permutation argument's (2^k, 4) uint64 Lagrange
+    columns, mapping the Assembly's (m, 2^k, 2) uint32 (column, row) pairs.  Returns (counts, rows) per column as check_gates does."""
+    n = 1 << int(k)
+    cols = _cols(columns, n, "columns")
+    mp = _check_mapping(mapping, n)
+    if mp.shape[0] != len(cols):
+        raise ValueError("columns and mapping differ in count")
+    maps = [mp[j] for j in range(len(cols))]
+    counts, rows, prow = _check_out(len(cols), max_rows)
+    _check(lib().h2hip_check_permutation_bn254(ctypes.c_uint32(k), _host_ptrs(cols), _host_ptrs(maps), ctypes.c_uint32(len(cols)),
+                                               ctypes.c_uint32(max_rows), _p(counts), prow), "h2hip_check_permutation_bn254")
+    return _check_result(counts, rows, len(cols), max_rows)
+
+
+def check_lookups(k, compressed_inputs, compressed_tables, blinding_factors, max_rows=16):
+    """MockProver::verify's lookup loop (dev.rs:751-886) on compressed columns (lookup_compress): input rows below u = 2^k -
+    blinding_factors - 1 whose value no table row below u holds.  Returns (counts, rows) per lookup as check_gates does."""
+    n = 1 << int(k)
+    a, t = _cols(compressed_inputs, n, "compressed_inputs"), _cols(compressed_tables, n, "compressed_tables")
+    if len(a) != len(t):
+        raise ValueError("compressed inputs and tables differ in count")
+    counts, rows, prow = _check_out(len(a), max_rows)
+    _check(lib().h2hip_check_lookups_bn254(ctypes.c_uint32(k), _host_ptrs(a), _host_ptrs(t), ctypes.c_size_t(len(a)),
+                                           ctypes.c_uint32(blinding_factors), ctypes.c_uint32(max_rows), _p(counts), prow),
+           "h2hip_check_lookups_bn254")
+    return _check_result(counts, rows, len(a), max_rows)
+
+
+def _failures(kind, counts, rows):
+    return [(kind, j, int(r)) for j in range(len(counts)) for r in rows[j][:min(int(counts[j]), rows.shape[1])]]
+
+
+def verify_witness(k, gate_polys, lookups, theta, blinding_factors, permutation_columns, mapping, fixed=(), advice=(), instance=(),
+                   challenges=(), max_rows=64):
+    """The three column-wide loops of MockProver::verify over one instance's columns: gate_polys are expression tuples (evaluation.py;
+    every gate's polynomials in cs.gates order), lookups [(input_exprs, table_exprs)], compressed here with the caller's theta;
+    permutation_columns [(kind, index)] with kind 'advice' / 'fixed' / 'instance' names the permutation argument's columns, mapping its
+    Assembly's (m, 2^k, 2) uint32 pairs (None, or m = 0: no copy constraint).  Challenges and theta are the caller's: the engine draws
+    nothing.  Returns the failures as ("gate", graph_index, row), ("lookup", lookup_index, row), ("permutation", column, row) tuples in
+    verify's order (dev.rs:933-938), at most the max_rows lowest rows of each constraint; an empty list is a satisfied witness."""
+    from .evaluation import flatten_graph, gate_check_graphs, lookup_compress_graphs
+    k = int(k)
+    out = []
+    graphs = [flatten_graph(g) for g in gate_check_graphs(gate_polys)]
+    if graphs:
+        out += _failures("gate", *check_gates(k, graphs, fixed, advice, instance, challenges, max_rows))
+    lg = []
+    for inp, tab in lookups:
+        gi, gt = lookup_compress_graphs(inp, tab)
+        lg += [flatten_graph(gi), flatten_graph(gt)]
+    if lg:
+        comp = lookup_compress(k, lg, theta, fixed, advice, instance, challenges)
+        out += _failures("lookup", *check_lookups(k, comp[0::2], comp[1::2], blinding_factors, max_rows))
+    if mapping is not None and len(permutation_columns):
+        pools = {"advice": advice, "fixed": fixed, "instance": instance}
+        cols = [pools[kind][int(i)] for kind, i in permutation_columns]
+        out += _failures("permutation", *check_permutation(k, cols, mapping, max_rows))
+    return out
+
+
 # ------------------------------------------------------------------ keygen: permutation key, batch_invert_assigned, l0 / l_last / l_active_row
 FR_DELTA = pow(7, 1 << FR_S, FR_MODULUS)  # Fr::DELTA = MULTIPLICATIVE_GENERATOR^(2^S)
 
@@ -1158,13 +1255,48 @@ def lookup_permute_device(k, d_compressed_inputs, d_compressed_tables, blinding,
                   "h2hip_lookup_permute_bn254_device")
 
 
+def check_gates_device(k, graphs, d_fixed=(), d_advice=(), d_instance=(), challenges=(), max_rows=16):
+    """check_gates over torch CUDA tensors (2^k x 32 B each): queued on the current stream, which the call waits for once to deliver
+    (counts, rows)"""
+    from .evaluation import graph_array
+    arr, keep = graph_array(graphs)
+    ch, n_ch = _lookup_challenges(challenges)
+    counts, rows, prow = _check_out(len(graphs), max_rows)
+    _check(lib().h2hip_check_gates_bn254_device(ctypes.c_uint32(k), _ptr_array(d_fixed), ctypes.c_uint32(len(d_fixed)), _ptr_array(d_advice),
+                                                ctypes.c_uint32(len(d_advice)), _ptr_array(d_instance), ctypes.c_uint32(len(d_instance)), _p(ch),
+                                                ctypes.c_uint32(n_ch), arr, ctypes.c_size_t(len(graphs)), ctypes.c_uint32(max_rows), _p(counts),
+                                                prow, _stream()), "h2hip_check_gates_bn254_device")
+    del keep
+    return _check_result(counts, rows, len(graphs), max_rows)
+
+
+def check_permutation_device(k, d_columns, d_mapping, max_rows=16):
+    """check_permutation over torch CUDA tensors: d_mapping[j] holds 2^k (column, row) uint32 pairs (8 B per cell).  Queued on the
+    current stream, waited for once; a pair out of range is not followed and raises H2HipError (H2HIP_EINVAL)."""
+    counts, rows, prow = _check_out(len(d_columns), max_rows)
+    _check(lib().h2hip_check_permutation_bn254_device(ctypes.c_uint32(k), _ptr_array(d_columns), _ptr_array(d_mapping),
+                                                      ctypes.c_uint32(len(d_columns)), ctypes.c_uint32(max_rows), _p(counts), prow, _stream()),
+           "h2hip_check_permutation_bn254_device")
+    return _check_result(counts, rows, len(d_columns), max_rows)
+
+
+def check_lookups_device(k, d_compressed_inputs, d_compressed_tables, blinding_factors, max_rows=16):
+    """check_lookups over torch CUDA tensors; queued on the current stream, waited for once"""
+    count = len(d_compressed_inputs)
+    counts, rows, prow = _check_out(count, max_rows)
+    _check(lib().h2hip_check_lookups_bn254_device(ctypes.c_uint32(k), _ptr_array(d_compressed_inputs), _ptr_array(d_compressed_tables),
+                                                  ctypes.c_size_t(count), ctypes.c_uint32(blinding_factors), ctypes.c_uint32(max_rows), _p(counts),
+                                                  prow, _stream()), "h2hip_check_lookups_bn254_device")
+    return _check_result(counts, rows, count, max_rows)
+
+
 def set_lookup_sort(lds_keys=0):
     """test hook: force the lookup sort's in-LDS block (a power of two in [4, 1024]; 0 = default)"""
     _check(lib().h2hip_debug_set_lookup_sort(ctypes.c_uint32(lds_keys)), "h2hip_debug_set_lookup_sort")
 
 
 def lookup_sort_stats():
-    """(block, merge passes) of the last lookup permute call"""
+    """(block, merge passes) of the last lookup sort (a permute or a lookup-check call)"""
     out = (ctypes.c_uint32 * 2)()
     _check(lib().h2hip_debug_lookup_sort_stats(out), "h2hip_debug_lookup_sort_stats")
     return int(out[0]), int(out[1])

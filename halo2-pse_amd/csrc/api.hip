@@ -909,6 +909,9 @@ static void release_ctx(Ctx* c) {
     c->keygen_ws.release();
     c->keygen_io.release();
     c->keygen_flag.release();
+    c->check_ws.release();
+    c->check_io.release();
+    c->check_flag.release();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     c->stream = nullptr;
     for (auto e : c->aux_events) (void)hipEventDestroy(e);

@@ -161,6 +161,8 @@ struct Ctx {
     HostBuf lookup_flag;           // lookup.hip: the per-lookup not-found flags read back at the end of a permute call
     DevBuf keygen_ws, keygen_io;   // keygen.hip: power tables, flag, pointer blobs and inverses; the host-pointer forms' columns
     HostBuf keygen_flag;           // keygen.hip: the out-of-range flag of a permutation keygen read back at the end of the call
+    DevBuf check_ws, check_io;     // check.hip: failure masks, tile counts, row lists and sort keys; the host-pointer forms' columns
+    HostBuf check_flag;            // check.hip: the out-of-range flag of a permutation check read back at the end of the call
     HostBuf host_ws;               // pinned host memory for the window sums coming back
     HostBuf host_planes;           // ... and for the bit-plane sums of a run whose tail the host finishes (msm.hip msm_planes_finish)
     HostBuf pin_flag;              // one word the device-key fingerprint check writes its verdict to
@@ -419,6 +421,10 @@ int batch_invert_device(Ctx* c, Fe* d_a, uint64_t n, hipStream_t s);
 // missing from its table
 int lookup_permute_device(Ctx* c, uint32_t k, const Fe* const* in, const Fe* const* tab, size_t count, const uint64_t* blinding, uint32_t bf,
                           Fe* const* pa, Fe* const* pt, hipStream_t s);
+// lookup.hip: its sort alone, enqueued on s: d_src[q] -> canonical keys sorted ascending, rows u .. 2^k - 1 as all-ones keys at the end;
+// the three device tables hold `cols` device pointers, and the keys end in d_k1[q] when lookup_sort_passes(k) is odd, else in d_k0[q]
+uint32_t lookup_sort_passes(uint32_t k);
+int lookup_sort_enqueue(const Fe* const* d_src, Fe* const* d_k0, Fe* const* d_k1, uint32_t cols, uint32_t k, uint64_t u, hipStream_t s);
 // setup.hip
 int kzg_setup_device(Ctx* c, uint32_t k, const Fe& s, Affine* d_g, Affine* d_gl, hipStream_t stream);
 
@@ -443,6 +449,13 @@ int lookup_compress_validate(uint32_t n_fixed, uint32_t n_advice, uint32_t n_ins
 int lookup_compress_device(Ctx* c, uint32_t k, const Fe* const* fixed, uint32_t n_fixed, const Fe* const* advice, uint32_t n_advice,
                            const Fe* const* instance, uint32_t n_instance, const uint64_t* challenges, uint32_t n_challenges,
                            const uint64_t theta[4], const h2hip_graph* graphs, size_t n_graphs, Fe* const* out, hipStream_t s);
+// the witness check's gate loop on the interpreter (check.hip drives it): bit (row % 64) of d_mask[g * words + row / 64] is set where
+// gate polynomial g is non-zero at Lagrange row `row`; the caller holds the workspaces, this only enqueues on s
+int check_gates_validate(uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance, uint32_t n_challenges, const h2hip_graph* graphs,
+                         size_t n_graphs);
+int check_gates_enqueue(Ctx* c, uint32_t k, const Fe* const* fixed, uint32_t n_fixed, const Fe* const* advice, uint32_t n_advice,
+                        const Fe* const* instance, uint32_t n_instance, const uint64_t* challenges, uint32_t n_challenges,
+                        const h2hip_graph* graphs, size_t n_graphs, uint64_t* d_mask, uint32_t words, hipStream_t s);
 
 // msm.hip
 void msm_set_fuse_small(bool on);

@@ -25,6 +25,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/halo2hip.h"
@@ -1404,18 +1405,20 @@ __global__ void __launch_bounds__(256) lookup_compress_kernel(const ProgDev* pro
     }
 }
 
-static bool compress_vs_allowed(const h2hip_value_source& v) {
-    return v.kind != H2HIP_VS_BETA && v.kind != H2HIP_VS_GAMMA && v.kind != H2HIP_VS_Y && v.kind != H2HIP_VS_PREVIOUS;
+static bool compress_vs_allowed(const h2hip_value_source& v, bool theta) {
+    return v.kind != H2HIP_VS_BETA && v.kind != H2HIP_VS_GAMMA && v.kind != H2HIP_VS_Y && v.kind != H2HIP_VS_PREVIOUS &&
+           (theta || v.kind != H2HIP_VS_THETA);
 }
 
-int lookup_compress_validate(uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance, uint32_t n_challenges, const h2hip_graph* graphs,
-                             size_t n_graphs) {
+// graphs the interpreter runs over Lagrange rows: `theta`: the compression's graphs may read theta, a gate polynomial's may not
+static int row_graphs_validate(const char* what, bool theta, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance, uint32_t n_challenges,
+                               const h2hip_graph* graphs, size_t n_graphs) {
     if (n_graphs && !graphs) {
-        set_error("lookup_compress: null graphs");
+        set_error("%s: null graphs", what);
         return H2HIP_EINVAL;
     }
     if (n_graphs > 65535) {
-        set_error("lookup_compress: %zu graphs > 65535", n_graphs);
+        set_error("%s: %zu graphs > 65535", what, n_graphs);
         return H2HIP_EINVAL;
     }
     h2hip_evalh_desc d;
@@ -1426,15 +1429,16 @@ int lookup_compress_validate(uint32_t n_fixed, uint32_t n_advice, uint32_t n_ins
     d.n_challenges = n_challenges;
     for (size_t i = 0; i < n_graphs; i++) {
         const h2hip_graph& g = graphs[i];
-        if (graph_validate(g, d, "lookup compression")) return H2HIP_EINVAL;
+        if (graph_validate(g, d, theta ? "lookup compression" : "gate check")) return H2HIP_EINVAL;
         for (uint32_t q = 0; q < g.n_calculations; q++) {
             const h2hip_calculation& cl = g.calculations[q];
-            bool ok = compress_vs_allowed(cl.x);
-            if (cl.op == H2HIP_CALC_ADD || cl.op == H2HIP_CALC_SUB || cl.op == H2HIP_CALC_MUL || cl.op == H2HIP_CALC_HORNER) ok = ok && compress_vs_allowed(cl.y);
+            bool ok = compress_vs_allowed(cl.x, theta);
+            if (cl.op == H2HIP_CALC_ADD || cl.op == H2HIP_CALC_SUB || cl.op == H2HIP_CALC_MUL || cl.op == H2HIP_CALC_HORNER)
+                ok = ok && compress_vs_allowed(cl.y, theta);
             if (cl.op == H2HIP_CALC_HORNER)
-                for (uint32_t t = 0; ok && t < cl.parts_count; t++) ok = compress_vs_allowed(g.parts[cl.parts_offset + t]);
+                for (uint32_t t = 0; ok && t < cl.parts_count; t++) ok = compress_vs_allowed(g.parts[cl.parts_offset + t], theta);
             if (!ok) {
-                set_error("lookup_compress: graph %zu, calculation %u reads beta, gamma, y or the previous value", i, q);
+                set_error("%s: graph %zu, calculation %u reads beta, gamma, %sy or the previous value", what, i, q, theta ? "" : "theta, ");
                 return H2HIP_EINVAL;
             }
         }
@@ -1442,15 +1446,30 @@ int lookup_compress_validate(uint32_t n_fixed, uint32_t n_advice, uint32_t n_ins
     return 0;
 }
 
-// Validated arguments (lookup_compress_validate); columns and outputs are device pointers, the rest host memory.  Enqueued on s.
-int lookup_compress_device(Ctx* c, uint32_t k, const Fe* const* fixed, uint32_t n_fixed, const Fe* const* advice, uint32_t n_advice,
-                           const Fe* const* instance, uint32_t n_instance, const uint64_t* challenges, uint32_t n_challenges,
-                           const uint64_t theta[4], const h2hip_graph* graphs, size_t n_graphs, Fe* const* out, hipStream_t s) {
-    if (n_graphs == 0) return 0;
+int lookup_compress_validate(uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance, uint32_t n_challenges, const h2hip_graph* graphs,
+                             size_t n_graphs) {
+    return row_graphs_validate("lookup_compress", true, n_fixed, n_advice, n_instance, n_challenges, graphs, n_graphs);
+}
+
+int check_gates_validate(uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance, uint32_t n_challenges, const h2hip_graph* graphs,
+                         size_t n_graphs) {
+    return row_graphs_validate("check_gates", false, n_fixed, n_advice, n_instance, n_challenges, graphs, n_graphs);
+}
+
+// What the two drivers of row graphs share (the compression below, the witness check's gate loop after it): the graphs compiled, one slot
+// plan for the call (the tier of its largest program), programs, column tables, challenges and `tail` (a per-graph table of the caller's, or
+// nothing) in one metadata image, one copy, and one launch for every graph -- one per graph in the global-workspace form, whose workspace
+// is shared.  launch(tier, grid, lds_bytes, progs, cols, g0, d_tail, gws, lanes) starts the caller's kernel instance of that tier for
+// the graphs from g0 on.  The caller holds the workspaces (ws_acquire); this only enqueues on s.  theta may be null (a graph that cannot read it).
+template <class Launch>
+static int row_graphs_enqueue(Ctx* c, const char* what, uint32_t k, const Fe* const* fixed, uint32_t n_fixed, const Fe* const* advice,
+                              uint32_t n_advice, const Fe* const* instance, uint32_t n_instance, const uint64_t* challenges, uint32_t n_challenges,
+                              const uint64_t* theta, const h2hip_graph* graphs, size_t n_graphs, const void* tail, size_t tail_bytes, hipStream_t s,
+                              Launch launch) {
     const size_t n = (size_t)1 << k;
     std::vector<Program> progs(n_graphs);
     uint32_t max_slots = 0;
-    size_t meta_cap = 4096 + ((size_t)n_challenges + n_fixed + n_advice + n_instance) * sizeof(Fu) + n_graphs * (sizeof(ProgDev) + sizeof(Fe*) + 512);
+    size_t meta_cap = 4096 + ((size_t)n_challenges + n_fixed + n_advice + n_instance) * sizeof(Fu) + n_graphs * (sizeof(ProgDev) + 512) + tail_bytes;
     for (size_t i = 0; i < n_graphs; i++) {
         progs[i] = compile_graph(graphs[i]);
         if (progs[i].n_slots > max_slots) max_slots = progs[i].n_slots;
@@ -1460,8 +1479,6 @@ int lookup_compress_device(Ctx* c, uint32_t k, const Fe* const* fixed, uint32_t 
     SlotPlan plan;
     int rc = slot_plan(max_slots, n, &plan);
     if (rc) return rc;
-    if ((rc = c->ws_acquire(s))) return rc;
-    WsGuard guard(c, s);
     if ((rc = c->evalh_ws.ensure(meta_cap))) return rc;
     if (plan.ws_bytes && (rc = c->evalh_slots.ensure(plan.ws_bytes))) return rc;
     MetaBlob mb;
@@ -1477,39 +1494,93 @@ int lookup_compress_device(Ctx* c, uint32_t k, const Fe* const* fixed, uint32_t 
         for (uint32_t i = 0; i < n_challenges; i++) hch[i] = to_i(fe_from_u64x4(challenges + 4 * (size_t)i));
         cols.challenges = mb.put(hch.data(), hch.size());
     }
-    cols.theta = to_i(fe_from_u64x4(theta));
+    if (theta) cols.theta = to_i(fe_from_u64x4(theta));
     cols.log_size = k;
     cols.rot_scale = 1;
     std::vector<ProgDev> pd(n_graphs);
     for (size_t i = 0; i < n_graphs; i++) prog_put(mb, graphs[i], progs[i], &pd[i]);
     const ProgDev* d_progs = mb.put(pd.data(), pd.size());
-    Fe* const* d_outs = mb.put(out, n_graphs);
+    const void* d_tail = mb.put((const char*)tail, tail_bytes);
     if (mb.overflow) {
-        set_error("lookup_compress: metadata region overflow");
+        set_error("%s: metadata region overflow", what);
         return 1;
     }
     if ((rc = c->stage_h2d(mb.dev_base, mb.host.data(), mb.host.size(), s))) return rc;
     Fu* const gws = (Fu*)c->evalh_slots.p;
-    const dim3 block(256);
-    int tm = c->timer_begin("lookup_compress", s);
     // the global-workspace form (a graph with more than 256 live values) shares one workspace: one graph per launch
     const uint32_t per_launch = plan.tier == 0 ? 1u : (uint32_t)n_graphs;
     for (size_t g0 = 0; g0 < n_graphs; g0 += per_launch) {
         const dim3 grid(plan.lanes / 256, per_launch);
-        const ProgDev* p = d_progs + g0;
-        Fe* const* o = d_outs + g0;
+        auto go = [&](auto tier, size_t lds) { launch(tier, grid, lds, d_progs + g0, cols, g0, d_tail, gws, plan.lanes); };
         switch (plan.tier) {
-            case 4: hipLaunchKernelGGL(lookup_compress_kernel<4>, grid, block, 4 * 9 * 256 * 4, s, p, cols, o, gws, plan.lanes); break;
-            case 8: hipLaunchKernelGGL(lookup_compress_kernel<8>, grid, block, 8 * 9 * 256 * 4, s, p, cols, o, gws, plan.lanes); break;
-            case 16: hipLaunchKernelGGL(lookup_compress_kernel<16>, grid, block, EVALH_LDS_HOT * 9 * 256 * 4, s, p, cols, o, gws, plan.lanes); break;
-            case 64: hipLaunchKernelGGL(lookup_compress_kernel<64>, grid, block, EVALH_LDS_HOT * 9 * 256 * 4, s, p, cols, o, gws, plan.lanes); break;
-            case 256: hipLaunchKernelGGL(lookup_compress_kernel<256>, grid, block, EVALH_LDS_HOT * 9 * 256 * 4, s, p, cols, o, gws, plan.lanes); break;
-            default: hipLaunchKernelGGL(lookup_compress_kernel<0>, grid, block, 0, s, p, cols, o, gws, plan.lanes);
+            case 4: go(std::integral_constant<int, 4>{}, 4 * 9 * 256 * 4); break;
+            case 8: go(std::integral_constant<int, 8>{}, 8 * 9 * 256 * 4); break;
+            case 16: go(std::integral_constant<int, 16>{}, EVALH_LDS_HOT * 9 * 256 * 4); break;
+            case 64: go(std::integral_constant<int, 64>{}, EVALH_LDS_HOT * 9 * 256 * 4); break;
+            case 256: go(std::integral_constant<int, 256>{}, EVALH_LDS_HOT * 9 * 256 * 4); break;
+            default: go(std::integral_constant<int, 0>{}, 0);
         }
         H2_CHECK(hipGetLastError());
     }
+    return 0;
+}
+
+// Validated arguments (lookup_compress_validate); columns and outputs are device pointers, the rest host memory.  Enqueued on s.
+int lookup_compress_device(Ctx* c, uint32_t k, const Fe* const* fixed, uint32_t n_fixed, const Fe* const* advice, uint32_t n_advice,
+                           const Fe* const* instance, uint32_t n_instance, const uint64_t* challenges, uint32_t n_challenges,
+                           const uint64_t theta[4], const h2hip_graph* graphs, size_t n_graphs, Fe* const* out, hipStream_t s) {
+    if (n_graphs == 0) return 0;
+    int rc = c->ws_acquire(s);
+    if (rc) return rc;
+    WsGuard guard(c, s);
+    int tm = c->timer_begin("lookup_compress", s);
+    rc = row_graphs_enqueue(c, "lookup_compress", k, fixed, n_fixed, advice, n_advice, instance, n_instance, challenges, n_challenges, theta, graphs,
+                            n_graphs, out, n_graphs * sizeof(Fe*), s,
+                            [&](auto tier, dim3 grid, size_t lds, const ProgDev* p, const ColsDev& cols, size_t g0, const void* d_outs, Fu* gws,
+                                uint32_t lanes) {
+                                hipLaunchKernelGGL(lookup_compress_kernel<decltype(tier)::value>, grid, dim3(256), lds, s, p, cols,
+                                                   (Fe* const*)d_outs + g0, gws, lanes);
+                            });
+    if (rc) return rc;
     c->timer_end(tm, s);
     return guard.release();
+}
+
+// ---- witness check, gates (check.hip; MockProver::verify's gate loop, dev.rs:676-746): graph g is ONE gate polynomial, run by the
+// interpreter exactly as the compression above runs its graphs, but the row's exact canonical value never leaves the registers: it is
+// tested for zero and goes out as one bit of mask[g][row / 64], a wave's ballot stored by the lane of the word's first row.  lanes is a
+// multiple of 256 and 2^k one of 64 (or below 64: one partial wave), so the 64 rows of a word are one wave's in one turn of the loop.
+template <int MAXI>
+__global__ void __launch_bounds__(256) check_gates_kernel(const ProgDev* progs, ColsDev c, uint64_t* mask, uint32_t words, Fu* gws, uint32_t lanes) {
+    const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= lanes) return;
+    const ProgDev g = progs[blockIdx.y];
+    uint64_t* m = mask + (size_t)blockIdx.y * words;
+    Slots<MAXI> slots(gws + tid, lanes);
+    for (uint64_t row = tid; row < (1ull << c.log_size); row += lanes) {
+        const uint32_t idx = (uint32_t)row;
+        const Fu r = prog_eval(g, c, idx, fu_zero(), slots);
+        const Fe e = prog_result_e<Slots<MAXI>>(g, c, idx, fe_zero<FrP>(), r);
+        uint32_t any = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) any |= e.l[j];
+        const uint64_t bits = __ballot(any != 0);
+        if ((idx & 63) == 0) m[idx >> 6] = bits;
+    }
+}
+
+// Validated arguments (check_gates_validate); columns and d_mask (n_graphs x words 64-bit words, words = max(1, 2^k / 64)) are device
+// memory.  The caller holds the workspaces (ws_acquire): this only enqueues on s.
+int check_gates_enqueue(Ctx* c, uint32_t k, const Fe* const* fixed, uint32_t n_fixed, const Fe* const* advice, uint32_t n_advice,
+                        const Fe* const* instance, uint32_t n_instance, const uint64_t* challenges, uint32_t n_challenges,
+                        const h2hip_graph* graphs, size_t n_graphs, uint64_t* d_mask, uint32_t words, hipStream_t s) {
+    return row_graphs_enqueue(c, "check_gates", k, fixed, n_fixed, advice, n_advice, instance, n_instance, challenges, n_challenges, nullptr, graphs,
+                              n_graphs, nullptr, 0, s,
+                              [&](auto tier, dim3 grid, size_t lds, const ProgDev* p, const ColsDev& cols, size_t g0, const void*, Fu* gws,
+                                  uint32_t lanes) {
+                                  hipLaunchKernelGGL(check_gates_kernel<decltype(tier)::value>, grid, dim3(256), lds, s, p, cols,
+                                                     d_mask + g0 * words, words, gws, lanes);
+                              });
 }
 
 }  // namespace h2

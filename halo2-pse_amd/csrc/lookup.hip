@@ -29,24 +29,17 @@
 #include <vector>
 #include "engine.h"
 #include "fe_io.h"
+#include "lk_dev.h"
 
 namespace h2 {
 
-#define LK_THREADS 256
 #define LK_TILE 1024                  // keys one workgroup sorts, merges or permutes (32 KB of LDS)
 #define LK_E (LK_TILE / LK_THREADS)   // consecutive keys / rows per thread
 #define LK_MAX_COUNT 32767            // lookups per call: 2 count sorted columns in grid.y
 
 static uint32_t g_lk_block = 0;            // h2hip_debug_set_lookup_sort: forced in-LDS sort block (0 = LK_TILE)
-static uint32_t g_lk_last[2] = {0, 0};     // block keys and merge passes of the last permute call
+static uint32_t g_lk_last[2] = {0, 0};     // block keys and merge passes of the last sort (a permute or a lookup-check call)
 
-// a < b as 256-bit integers (limb 7 most significant): Fr's Ord on canonical values
-__device__ __forceinline__ bool key_lt(const Fe& a, const Fe& b) {
-#pragma unroll
-    for (int i = 7; i >= 0; i--)
-        if (a.l[i] != b.l[i]) return a.l[i] < b.l[i];
-    return false;
-}
 // merge path: how many of the first d outputs of merge(A[0 .. na), B[0 .. nb)) come from A (on ties A first)
 __device__ __forceinline__ uint32_t lk_split(const Fe* A, uint32_t na, const Fe* B, uint32_t nb, uint32_t d) {
     uint32_t lo = d > nb ? d - nb : 0, hi = d < na ? d : na;
@@ -154,23 +147,6 @@ struct LkPerm {           // one lookup
 };
 
 __device__ __forceinline__ bool lk_repeated(const Fe* a, uint64_t i) { return i > 0 && fe_eq(fe_ld(a, i), fe_ld(a, i - 1)); }
-
-// exclusive sum over the workgroup's threads in order; *total = sum of all
-__device__ __forceinline__ uint32_t lk_scan_excl(uint32_t v, uint32_t* lds, uint32_t* total) {
-    const uint32_t tid = threadIdx.x;
-    lds[tid] = v;
-    __syncthreads();
-    for (uint32_t off = 1; off < LK_THREADS; off <<= 1) {
-        const uint32_t x = tid >= off ? lds[tid - off] : 0u;
-        __syncthreads();
-        lds[tid] += x;
-        __syncthreads();
-    }
-    const uint32_t inc = lds[tid];
-    *total = lds[LK_THREADS - 1];
-    __syncthreads();
-    return inc - v;
-}
 
 __global__ __launch_bounds__(LK_THREADS) void lk_mark_kernel(const LkPerm* P, uint64_t u) {
     const LkPerm D = P[blockIdx.y];
@@ -298,6 +274,36 @@ __global__ __launch_bounds__(LK_THREADS) void lk_final_kernel(const LkPerm* P, u
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
+// The sort alone (steps 1 and 2), for lookup_permute_device below and the witness check (check.hip): `cols` columns of 2^k elements,
+// src[q] -> canonical keys, rows u .. n - 1 as all-ones keys at the end.  src, k0 and k1 are device tables of `cols` device pointers
+// (k0[q], k1[q]: two key buffers of 2^k elements per column); the sorted keys end in k1[q] when lookup_sort_passes(k) is odd, else in k0[q].
+static uint32_t lk_sort_block(uint32_t ts) {
+    const uint32_t block = g_lk_block ? g_lk_block : LK_TILE;
+    return block > ts ? ts : block;
+}
+uint32_t lookup_sort_passes(uint32_t k) {
+    const uint64_t n = 1ull << k;
+    uint32_t passes = 0;
+    for (uint64_t w = lk_sort_block((uint32_t)(n < LK_TILE ? n : LK_TILE)); w < n; w <<= 1) passes++;
+    return passes;
+}
+int lookup_sort_enqueue(const Fe* const* d_src, Fe* const* d_k0, Fe* const* d_k1, uint32_t cols, uint32_t k, uint64_t u, hipStream_t s) {
+    const uint64_t n = 1ull << k;
+    const uint32_t ts = (uint32_t)(n < LK_TILE ? n : LK_TILE), tiles = (uint32_t)(n / ts), block = lk_sort_block(ts);
+    const uint32_t passes = lookup_sort_passes(k);
+    hipLaunchKernelGGL(lk_block_sort_kernel, dim3(tiles, cols), dim3(LK_THREADS), 0, s, d_src, d_k0, u, ts, block);
+    H2_CHECK(hipGetLastError());
+    uint32_t w = block;
+    for (uint32_t p = 0; p < passes; p++, w <<= 1) {
+        const Fe* const* from = p & 1 ? (const Fe* const*)d_k1 : (const Fe* const*)d_k0;
+        hipLaunchKernelGGL(lk_merge_kernel, dim3(tiles, cols), dim3(LK_THREADS), 0, s, from, p & 1 ? d_k0 : d_k1, w, ts);
+        H2_CHECK(hipGetLastError());
+    }
+    g_lk_last[0] = block;
+    g_lk_last[1] = passes;
+    return 0;
+}
+
 // Validated arguments; columns and outputs are device pointers (in[j], tab[j], pa[j], pt[j] for lookup j), blinding host memory.
 // Enqueues everything on s, then waits for s once to read the not-found flags: H2HIP_ELOOKUP names the lowest failing lookup.
 int lookup_permute_device(Ctx* c, uint32_t k, const Fe* const* in, const Fe* const* tab, size_t count, const uint64_t* blinding, uint32_t bf,
@@ -305,11 +311,7 @@ int lookup_permute_device(Ctx* c, uint32_t k, const Fe* const* in, const Fe* con
     if (count == 0) return 0;
     const uint64_t n = 1ull << k, u = n - bf - 1;
     const uint32_t ts = (uint32_t)(n < LK_TILE ? n : LK_TILE);
-    uint32_t block = g_lk_block ? g_lk_block : LK_TILE;
-    if (block > ts) block = ts;
-    const uint32_t tiles = (uint32_t)(n / ts);
-    uint32_t passes = 0;
-    for (uint64_t w = block; w < n; w <<= 1) passes++;
+    const uint32_t tiles = (uint32_t)(n / ts), passes = lookup_sort_passes(k);
     const size_t cols = 2 * count, col_bytes = n * sizeof(Fe);
     const size_t nb = (size_t)bf + 1;
     // one lookup's workspace: the used marks, L (a column, packed), the tile counts of L and of R
@@ -370,14 +372,7 @@ int lookup_permute_device(Ctx* c, uint32_t k, const Fe* const* in, const Fe* con
     H2_CHECK(hipMemsetAsync(d_flag, 0, count * sizeof(uint32_t), s));
     const LkPerm* d_perm = perm.d;
     int tm = c->timer_begin("lookup_permute", s);
-    hipLaunchKernelGGL(lk_block_sort_kernel, dim3(tiles, (uint32_t)cols), dim3(LK_THREADS), 0, s, d_src, d_k0, u, ts, block);
-    H2_CHECK(hipGetLastError());
-    uint32_t w = block;
-    for (uint32_t p = 0; p < passes; p++, w <<= 1) {
-        const Fe* const* from = p & 1 ? (const Fe* const*)d_k1 : (const Fe* const*)d_k0;
-        hipLaunchKernelGGL(lk_merge_kernel, dim3(tiles, (uint32_t)cols), dim3(LK_THREADS), 0, s, from, p & 1 ? d_k0 : d_k1, w, ts);
-        H2_CHECK(hipGetLastError());
-    }
+    if ((rc = lookup_sort_enqueue(d_src, d_k0, d_k1, (uint32_t)cols, k, u, s))) return rc;
     const dim3 grid(tiles, (uint32_t)count);
     hipLaunchKernelGGL(lk_mark_kernel, grid, dim3(LK_THREADS), 0, s, d_perm, u);
     H2_CHECK(hipGetLastError());
@@ -392,8 +387,6 @@ int lookup_permute_device(Ctx* c, uint32_t k, const Fe* const* in, const Fe* con
     c->timer_end(tm, s);
     H2_CHECK(hipMemcpyAsync(c->lookup_flag.p, d_flag, count * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     if ((rc = guard.release())) return rc;
-    g_lk_last[0] = block;
-    g_lk_last[1] = passes;
     H2_CHECK(hipStreamSynchronize(s));  // the caller must know before it commits
     const uint32_t* flags = (const uint32_t*)c->lookup_flag.p;
     for (size_t j = 0; j < count; j++)

@@ -152,6 +152,19 @@ def lookup_compress_graphs(input_exprs, table_exprs):
     return tuple(out)
 
 
+def gate_check_graphs(gate_polys):
+    """The witness check's graphs (h2hip_check_gates_bn254): one per gate polynomial, add_expression of that polynomial alone, its value
+    designated by a closing Store calculation -- so a bare query or a constant is a polynomial like any other.  None stands for the
+    zero polynomial, an empty graph.  A polynomial shared by several gates (a selector, say) is evaluated once per graph."""
+    out = []
+    for p in gate_polys:
+        g = GraphEvaluator()
+        if p is not None:
+            g.add_calculation((CALC_STORE, g.add_expression(p), None, ()))
+        out.append(g)
+    return out
+
+
 # ------------------------------------------------------------------ flat arrays <-> ctypes
 def to_mont_limbs(vals):
     out = np.zeros((len(vals), 4), dtype=np.uint64)

@@ -267,6 +267,18 @@ inline std::pair<GraphEvaluator, GraphEvaluator> lookup_compress_graphs(const Lo
     return {side(lookup.input_expressions), side(lookup.table_expressions)};
 }
 
+// The witness check's graphs (halo2hip.hpp dev::verify, h2hip_check_gates_bn254): one per gate polynomial, add_expression of that
+// polynomial alone, its value designated by a closing Store calculation; a null Expr stands for the zero polynomial, an empty graph
+inline std::vector<GraphEvaluator> gate_check_graphs(const std::vector<Expr>& gate_polys) {
+    std::vector<GraphEvaluator> out;
+    for (const auto& poly : gate_polys) {
+        GraphEvaluator g;
+        if (poly) g.add_calculation(Calculation::Store(g.add_expression(poly)));
+        out.push_back(std::move(g));
+    }
+    return out;
+}
+
 class Evaluator {  // :182-189
   public:
     GraphEvaluator custom_gates;

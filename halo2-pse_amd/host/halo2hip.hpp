@@ -738,6 +738,91 @@ inline ProvingKeyColumns keygen_pk(const poly::EvaluationDomain& domain, const s
 
 }  // namespace plonk
 
+// The three column-wide loops of MockProver::verify (dev.rs:603-1300) over the prover's own columns: h2hip_check_gates_bn254,
+// h2hip_check_lookups_bn254 (on columns compressed with the caller's theta) and h2hip_check_permutation_bn254.  MockProver's regions,
+// names, CellNotAssigned, Poison and selector checks are host bookkeeping and not mirrored.
+namespace dev {
+
+struct VerifyFailure {
+    enum Kind { Gate, Lookup, Permutation } kind;  // index: the gate polynomial (graph), the lookup, the permutation column
+    size_t index;
+    uint32_t row;
+    bool operator==(const VerifyFailure& o) const { return kind == o.kind && index == o.index && row == o.row; }
+};
+
+struct Columns {
+    std::vector<const poly::Polynomial<poly::LagrangeCoeff>*> fixed, advice, instance;
+    std::vector<Fr> challenges;
+};
+
+// gate_graphs: one graph per gate polynomial (evaluation.hpp gate_check_graphs); lookup_graphs: input side then table side of every lookup
+// (evaluation.hpp lookup_compress_graphs), compressed with theta; permutation_columns: the argument's columns, resolved, with their
+// assembly (nullptr: no copy constraint).  Failures in verify's order (dev.rs:933-938): gates, lookups, permutation; of each
+// constraint at most its max_rows lowest rows.  An empty vector is a satisfied witness.
+inline std::vector<VerifyFailure> verify(const poly::EvaluationDomain& domain, const Columns& cols, const std::vector<h2hip_graph>& gate_graphs,
+                                         const std::vector<h2hip_graph>& lookup_graphs, const Fr& theta, size_t blinding_factors,
+                                         const std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>& permutation_columns,
+                                         const plonk::permutation::keygen::Assembly* assembly, uint32_t max_rows = 64) {
+    auto ptrs = [&](const std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>& cs) {
+        std::vector<const uint64_t*> p;
+        for (auto* c : cs) {
+            if (c->len() != domain.n) throw std::logic_error("column length != n");
+            p.push_back(c->values[0].l);
+        }
+        return p;
+    };
+    std::vector<VerifyFailure> out;
+    std::vector<uint64_t> counts;
+    std::vector<uint32_t> rows;
+    auto prepare = [&](size_t items) {
+        counts.assign(items, 0);
+        rows.assign(items * max_rows, UINT32_MAX);
+    };
+    auto collect = [&](VerifyFailure::Kind kind) {
+        for (size_t j = 0; j < counts.size(); j++)
+            for (size_t t = 0; t < max_rows && t < counts[j]; t++) out.push_back({kind, j, rows[j * max_rows + t]});
+    };
+    if (!gate_graphs.empty()) {
+        const auto f = ptrs(cols.fixed), a = ptrs(cols.advice), i = ptrs(cols.instance);
+        prepare(gate_graphs.size());
+        engine_check(h2hip_check_gates_bn254(domain.k, f.data(), uint32_t(f.size()), a.data(), uint32_t(a.size()), i.data(), uint32_t(i.size()),
+                                             cols.challenges.empty() ? nullptr : cols.challenges[0].l, uint32_t(cols.challenges.size()),
+                                             gate_graphs.data(), gate_graphs.size(), max_rows, counts.data(), rows.data()),
+                     "check_gates");
+        collect(VerifyFailure::Gate);
+    }
+    if (!lookup_graphs.empty()) {
+        if (lookup_graphs.size() % 2) throw std::logic_error("lookup_graphs: an input and a table graph per lookup expected");
+        const auto comp = plonk::lookup_compress(domain, lookup_graphs, cols.fixed, cols.advice, cols.instance, cols.challenges, theta);
+        std::vector<const uint64_t*> in, tab;
+        for (size_t j = 0; j < comp.size(); j += 2) {
+            in.push_back(comp[j].values[0].l);
+            tab.push_back(comp[j + 1].values[0].l);
+        }
+        prepare(in.size());
+        engine_check(h2hip_check_lookups_bn254(domain.k, in.data(), tab.data(), in.size(), uint32_t(blinding_factors), max_rows, counts.data(),
+                                               rows.data()),
+                     "check_lookups");
+        collect(VerifyFailure::Lookup);
+    }
+    if (assembly && !permutation_columns.empty()) {
+        const auto p = ptrs(permutation_columns);
+        if (assembly->mapping.size() != p.size()) throw std::logic_error("permutation columns and assembly differ in count");
+        std::vector<const uint32_t*> mp;
+        for (const auto& col : assembly->mapping) {
+            if (col.size() != domain.n) throw std::logic_error("mapping column length != n");
+            mp.push_back(&col[0].first);
+        }
+        prepare(p.size());
+        engine_check(h2hip_check_permutation_bn254(domain.k, p.data(), mp.data(), uint32_t(p.size()), max_rows, counts.data(), rows.data()),
+                     "check_permutation");
+        collect(VerifyFailure::Permutation);
+    }
+    return out;
+}
+
+}  // namespace dev
+
 // The KZG multiopen provers restated over the engine's primitive.  The caller builds the sets (construct_intermediate_sets), draws the
 // challenges from its transcript and commits; the engine takes ordered scalars only.
 namespace poly {

@@ -530,3 +530,94 @@ pub fn try_key_lagrange_columns<F: Field + 'static>(domain: &KeygenDomain<F>, bl
     }
     Some((l0, l_last, l_active_row))
 }
+
+/// What a witness check returns: per constraint how many rows fail, and the lowest `max_rows` of them in ascending order.
+pub struct CheckReport {
+    pub counts: Vec<u64>,
+    pub rows: Vec<Vec<u32>>,
+}
+
+fn check_report(counts: Vec<u64>, flat: Vec<u32>, max_rows: usize) -> CheckReport {
+    let rows = counts.iter().enumerate().map(|(j, &c)| flat[j * max_rows..j * max_rows + (c as usize).min(max_rows)].to_vec()).collect();
+    CheckReport { counts, rows }
+}
+
+/// `MockProver::verify`'s gate loop (dev.rs:676-746) over the prover's own Lagrange columns, all 2^k rows: `graphs[g]` is
+/// `add_expression` of one gate polynomial closed by a `Store` of its value.  Failures are data; `None` when the engine did not take
+/// the call.
+#[allow(clippy::too_many_arguments)]
+pub fn try_check_gates<F: Field + 'static>(k: u32, fixed: &[&[F]], advice: &[&[F]], instance: &[&[F]], challenges: &[F],
+                                           graphs: &[&evalh::FlatGraph], max_rows: usize) -> Option<CheckReport> {
+    if !is::<F, Fr>() || !layout_ok() || k > 28 || graphs.len() > 65535 || max_rows > 65535 {
+        return None;
+    }
+    let n = 1usize << k;
+    if fixed.iter().chain(advice.iter()).chain(instance.iter()).any(|c| c.len() != n) {
+        return None;
+    }
+    let ptrs = |cols: &[&[F]]| -> Vec<*const u64> { cols.iter().map(|c| c.as_ptr() as *const u64).collect() };
+    let (f, a, i) = (ptrs(fixed), ptrs(advice), ptrs(instance));
+    let views: Vec<evalh::h2hip_graph> = graphs.iter().map(|g| g.view()).collect();
+    let mut counts = vec![0u64; graphs.len()];
+    let mut rows = vec![u32::MAX; graphs.len() * max_rows];
+    let rc = unsafe {
+        ffi::h2hip_check_gates_bn254(k, f.as_ptr(), f.len() as u32, a.as_ptr(), a.len() as u32, i.as_ptr(), i.len() as u32,
+                                     challenges.as_ptr() as *const u64, challenges.len() as u32, views.as_ptr(), views.len(),
+                                     max_rows as u32, counts.as_mut_ptr(), rows.as_mut_ptr())
+    };
+    if rc != 0 {
+        return None;
+    }
+    Some(check_report(counts, rows, max_rows))
+}
+
+/// `MockProver::verify`'s copy-constraint loop (dev.rs:889-931): `columns` are the permutation argument's Lagrange columns, `mapping`
+/// is `Assembly::mapping` as `try_permutation_keygen` takes it.  `None` when the engine did not take the call (a pair out of range
+/// included).
+pub fn try_check_permutation<F: Field + 'static>(k: u32, columns: &[&[F]], mapping: &[&[[u32; 2]]], max_rows: usize) -> Option<CheckReport> {
+    let m = columns.len();
+    if !is::<F, Fr>() || !layout_ok() || k > 28 || m > 65535 || mapping.len() != m || max_rows > 65535 {
+        return None;
+    }
+    let n = 1usize << k;
+    if columns.iter().any(|c| c.len() != n) || mapping.iter().any(|c| c.len() != n) {
+        return None;
+    }
+    let cp: Vec<*const u64> = columns.iter().map(|c| c.as_ptr() as *const u64).collect();
+    let mp: Vec<*const u32> = mapping.iter().map(|c| c.as_ptr() as *const u32).collect();
+    let mut counts = vec![0u64; m];
+    let mut rows = vec![u32::MAX; m * max_rows];
+    let rc = unsafe {
+        ffi::h2hip_check_permutation_bn254(k, cp.as_ptr(), mp.as_ptr(), m as u32, max_rows as u32, counts.as_mut_ptr(), rows.as_mut_ptr())
+    };
+    if rc != 0 {
+        return None;
+    }
+    Some(check_report(counts, rows, max_rows))
+}
+
+/// `MockProver::verify`'s lookup loop (dev.rs:751-886) on the columns `try_lookup_compress` produces for a theta of the caller's
+/// choosing: the input rows below u = 2^k - blinding_factors - 1 whose value no table row below u holds.
+pub fn try_check_lookups<F: Field + 'static>(k: u32, compressed_inputs: &[&[F]], compressed_tables: &[&[F]], blinding_factors: usize,
+                                             max_rows: usize) -> Option<CheckReport> {
+    let count = compressed_inputs.len();
+    if !is::<F, Fr>() || !layout_ok() || k > 28 || count > 32767 || compressed_tables.len() != count || max_rows > 65535 {
+        return None;
+    }
+    let n = 1usize << k;
+    if compressed_inputs.iter().chain(compressed_tables.iter()).any(|c| c.len() != n) || blinding_factors + 1 >= n {
+        return None;
+    }
+    let ptrs = |cols: &[&[F]]| -> Vec<*const u64> { cols.iter().map(|c| c.as_ptr() as *const u64).collect() };
+    let (a, s) = (ptrs(compressed_inputs), ptrs(compressed_tables));
+    let mut counts = vec![0u64; count];
+    let mut rows = vec![u32::MAX; count * max_rows];
+    let rc = unsafe {
+        ffi::h2hip_check_lookups_bn254(k, a.as_ptr(), s.as_ptr(), count, blinding_factors as u32, max_rows as u32, counts.as_mut_ptr(),
+                                       rows.as_mut_ptr())
+    };
+    if rc != 0 {
+        return None;
+    }
+    Some(check_report(counts, rows, max_rows))
+}

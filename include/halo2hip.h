@@ -383,7 +383,8 @@ int h2hip_batch_invert_bn254_fr_device(void* d_a, size_t n, void* stream);
  * S'[i] = A'[i] on the first row of each distinct value, taking one copy of it out of the multiset T = compressed_table[0 .. u); the
  * leftovers L (ascending) fill the repeated rows R (ascending) as S'[R[t]] = L[|L| - 1 - t].  blinding holds 2(b + 1) values per lookup,
  * A' rows u .. n - 1 then S' rows u .. n - 1, drawn by the caller in the reference's order; the engine draws nothing.  An input value
- * missing from its table is H2HIP_ELOOKUP: h2hip_last_error() names the lowest such lookup, and the outputs are unspecified.
+ * missing from its table is H2HIP_ELOOKUP: h2hip_last_error() names the lowest such lookup, and the outputs are unspecified;
+ * h2hip_check_lookups_bn254 on the same compressed columns gives the failing rows of every lookup.
  * k <= 28, b + 1 < n (permute), count <= 32767, n_graphs <= 65535; n_graphs == 0 / count == 0 write nothing.  Host forms: a fixed column
  * pinned with h2hip_columns_pin (elems = 2^k) is not uploaded.  _device forms: columns and outputs are device pointers (the pointer tables,
  * graphs, challenges, theta and blinding values are host memory, read before the call returns) and kernels are queued on `stream`; the
@@ -477,6 +478,49 @@ int h2hip_key_lagrange_columns_bn254_device(uint32_t k, const uint64_t omega_inv
                                             const uint64_t extended_omega[4], const uint64_t g_coset[4], const uint64_t g_coset_inv[4],
                                             uint32_t blinding_factors, void* d_l0, void* d_l_last, void* d_l_active_row, void* stream);
 
+/* ---- witness check: the three column-wide loops of MockProver::verify (dev.rs:603-1300) over the prover's own columns -----------------
+ * n = 2^k, k <= 28.  Each call checks n_items constraints over the rows and reports, per constraint, how many rows fail and which are
+ * the lowest: counts (host memory) receives one uint64_t per item; rows (host memory, n_items x max_rows uint32_t, item-major; may be
+ * NULL when max_rows == 0; max_rows <= 65535) receives in rows[j][t], t < min(counts[j], max_rows), the lowest failing rows of item j in
+ * ascending order, and UINT32_MAX in the remaining slots.  The result is a function of the inputs alone: two runs are byte-identical.
+ * Failures are data: a call that finds some returns H2HIP_OK; a non-zero status is a contract violation or a device error.  Zero items
+ * write nothing.  MockProver's regions, names, CellNotAssigned, Poison and selector checks are host bookkeeping and not done here.
+ * Gates (:676-746): graphs[g] is GraphEvaluator::add_expression of ONE gate polynomial, its value designated by a closing Store
+ * calculation (evaluation.py gate_check_graphs), so a bare query or a constant is a legal polynomial; an empty graph is the zero
+ * polynomial.  Item g fails at row i when that value is non-zero at Lagrange row i, rotations wrapping modulo n.  ALL n rows are
+ * checked, the blinding rows included (verify's default, and what divisibility by X^n - 1 demands): on the prover's real columns
+ * those rows hold random values where MockProver holds Poison, and a gate that is not switched off there fails there.  n_graphs <=
+ * 65535.  A graph that reads beta, gamma, theta, y or the previous value, or an index out of range, is H2HIP_EINVAL before any device work.
+ * Permutation (:889-931): columns are the n_columns <= 65535 Lagrange columns of the argument, already resolved from advice / fixed /
+ * instance as h2hip_permutation_products_bn254 takes them; mapping as h2hip_permutation_keygen_bn254 takes it.  Item j fails at row i
+ * when columns[j][i] != columns[c][r], (c, r) = mapping[j][i]: equality of reduced elements, over all n rows.  A wrong cell in a cycle
+ * of length >= 2 is therefore reported twice, at the cell and at its predecessor, as in the reference.  A pair with column >=
+ * n_columns or row >= 2^k is H2HIP_EINVAL: the host form finds it before any device work and names it; the _device form checks the
+ * bounds in the kernel, never dereferences the pair, raises a flag and returns H2HIP_EINVAL after its one synchronisation.
+ * Lookups (:751-886): with u = n - blinding_factors - 1 (blinding_factors + 1 < n), lookup j fails at row i < u when
+ * compressed_input[j][i] equals none of compressed_table[j][0 .. u).  Rows >= u are never reported and table rows >= u never satisfy
+ * an input (:818-836).  count <= 32767.  The columns are what h2hip_lookup_compress_bn254 produces for a theta of the caller's
+ * choosing: for single-expression lookups this is MockProver's check exactly; for tuples it is that check up to a theta collision
+ * (two different tuples compressing to one value), which is the soundness the proof itself has.
+ * Host forms upload their columns; one pinned with h2hip_columns_pin (elems = 2^k) is not uploaded.  _device forms: columns (and the
+ * mapping) are device pointers, the pointer tables, graphs and challenges host memory read before the call returns; kernels are
+ * queued on `stream`, which is synchronised once to deliver counts / rows (as h2hip_eval_polynomials_bn254_device does for its results). */
+int h2hip_check_gates_bn254(uint32_t k, const uint64_t* const* fixed_values, uint32_t n_fixed, const uint64_t* const* advice_values,
+                            uint32_t n_advice, const uint64_t* const* instance_values, uint32_t n_instance, const uint64_t* challenges,
+                            uint32_t n_challenges, const h2hip_graph* graphs, size_t n_graphs, uint32_t max_rows, uint64_t* counts, uint32_t* rows);
+int h2hip_check_gates_bn254_device(uint32_t k, const void* const* d_fixed_values, uint32_t n_fixed, const void* const* d_advice_values,
+                                   uint32_t n_advice, const void* const* d_instance_values, uint32_t n_instance, const uint64_t* challenges,
+                                   uint32_t n_challenges, const h2hip_graph* graphs, size_t n_graphs, uint32_t max_rows, uint64_t* counts,
+                                   uint32_t* rows, void* stream);
+int h2hip_check_permutation_bn254(uint32_t k, const uint64_t* const* columns, const uint32_t* const* mapping, uint32_t n_columns, uint32_t max_rows,
+                                  uint64_t* counts, uint32_t* rows);
+int h2hip_check_permutation_bn254_device(uint32_t k, const void* const* d_columns, const void* const* d_mapping, uint32_t n_columns,
+                                         uint32_t max_rows, uint64_t* counts, uint32_t* rows, void* stream);
+int h2hip_check_lookups_bn254(uint32_t k, const uint64_t* const* compressed_input, const uint64_t* const* compressed_table, size_t count,
+                              uint32_t blinding_factors, uint32_t max_rows, uint64_t* counts, uint32_t* rows);
+int h2hip_check_lookups_bn254_device(uint32_t k, const void* const* d_compressed_input, const void* const* d_compressed_table, size_t count,
+                                     uint32_t blinding_factors, uint32_t max_rows, uint64_t* counts, uint32_t* rows, void* stream);
+
 /* ---- synthetic workload; same streams as oracle_gen_{scalars,points} ---- */
 
 int h2hip_gen_scalars_device(uint64_t seed, uint64_t start, size_t n, void* d_out, void* stream);
@@ -491,7 +535,9 @@ int h2hip_set_msm_window(uint32_t c);
 uint32_t h2hip_get_msm_window(size_t n);
 uint32_t h2hip_get_msm_window_fixed_base(size_t n);
 /* Per-stage HIP-event timers recorded on the stream each kernel group is launched on.
- * Stages: "ntt", "msm_total", "msm_digits", "msm_sort", "msm_accum" (over-full buckets included), "msm_reduce", "g_to_lagrange", "kzg_setup". */
+ * Stages: "ntt", "msm_total", "msm_digits", "msm_sort", "msm_accum" (over-full buckets included), "msm_reduce", "g_to_lagrange", "kzg_setup",
+ * "evalh_cosets", "evalh_gates", "evalh_perm", "evalh_lookups", "products", "opening_eval", "opening_combine", "lookup_compress",
+ * "lookup_permute", "check_gates", "check_permutation", "check_lookups" (each check: its kernels, without the delivery of counts / rows). */
 /* on = 1: every stage (each event record costs the stream ~10 us of gap); on = 2: only the dominant kernel ("msm_accum"),
  * timed through its own dispatch packet with no gap; 0: off */
 int h2hip_profile_enable(int on);

@@ -23,7 +23,8 @@ from __graft_entry__ import load_pkg  # noqa: E402
 R_MOD = 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001
 
 
-def build_system(ev, args, rng):
+def system_expressions(args, rng):
+    """(gate polynomials, [(input expressions, table expressions)]) of the synthetic system"""
     A = lambda c, r=0: ('advice', c, r)  # noqa: E731
     F = lambda c, r=0: ('fixed', c, r)  # noqa: E731
     gates = []
@@ -35,7 +36,11 @@ def build_system(ev, args, rng):
                                       ('scaled', F(f3), 3 + gi))))
     lookups = [([A(li % args.advice), ('prod', A((li + 1) % args.advice), F(li % args.fixed))], [F((li + 1) % args.fixed), F((li + 2) % args.fixed, 1)])
                for li in range(args.lookups)]
-    return ev.Evaluator.new(gates, lookups)
+    return gates, lookups
+
+
+def build_system(ev, args, rng):
+    return ev.Evaluator.new(*system_expressions(args, rng))
 
 
 def bench(args):
