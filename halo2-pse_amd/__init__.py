@@ -1019,20 +1019,317 @@ class EvaluationDomain:
         return a
 
 
+# ------------------------------------------------------------------ helpers.rs (SerdeFormat), poly.rs:152-177
+import enum  # noqa: E402
+
+
+class SerdeFormat(enum.Enum):
+    """helpers.rs:8-20"""
+    Processed = 0           # curve points compressed (32 B per G1, 64 B per G2), field elements canonical; every element checked
+    RawBytes = 1            # the in-memory Montgomery limbs; coordinates below the modulus and points on the curve checked
+    RawBytesUnchecked = 2   # the same bytes, no checks
+
+
+H2HIP_EENCODING = 5
+FQ_MODULUS = 0x30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47
+_FQ_R = (1 << 256) % FQ_MODULUS
+
+
+class H2HipEncodingError(H2HipError):
+    """an element fails its format's checks (H2HIP_EENCODING; the reference's io::Error "invalid point encoding" / "Invalid prime
+    field point encoding").  count: invalid elements; index: the lowest of them; output: what the call wrote, invalid elements as zeros"""
+
+    def __init__(self, what, rc, count, index, output=None):
+        H2HipError.__init__(self, "%s failed (rc=%d): %s" % (what, rc, lib().h2hip_last_error().decode()))
+        self.rc, self.count, self.index, self.output = rc, count, index, output
+
+
+def _check_encoding(rc, what, invalid, output=None):
+    if rc == H2HIP_EENCODING:
+        raise H2HipEncodingError(what, rc, int(invalid[0]), int(invalid[1]), output)
+    _check(rc, what)
+
+
+def _bytes32(a, what):
+    a = np.ascontiguousarray(np.frombuffer(a, dtype=np.uint8) if isinstance(a, (bytes, bytearray, memoryview)) else a)
+    if a.dtype != np.uint8 or a.size % 32:
+        raise ValueError("%s: expected uint8 data, 32 bytes per element" % what)
+    return a.reshape(-1, 32)
+
+
+def g1_from_bytes(data):
+    """G1Affine::from_bytes over an array (SerdeFormat::Processed read): (n, 32) uint8 -> (n, 8) uint64 Montgomery points, on the GPU.
+    H2HipEncodingError when an encoding is invalid."""
+    data = _bytes32(data, "g1_from_bytes")
+    n = data.shape[0]
+    out, invalid = np.zeros((n, 8), dtype=np.uint64), np.zeros(2, dtype=np.uint64)
+    _check_encoding(lib().h2hip_g1_decompress_bn254(_p(data), ctypes.c_size_t(n), _p(out), _p(invalid)), "h2hip_g1_decompress_bn254", invalid, out)
+    return out
+
+
+def g1_to_bytes(points):
+    """G1Affine::to_bytes over an array (Processed write): (n, 8) uint64 -> (n, 32) uint8"""
+    points = _u64(points, 8)
+    n = points.shape[0]
+    out = np.zeros((n, 32), dtype=np.uint8)
+    _check(lib().h2hip_g1_compress_bn254(_p(points), ctypes.c_size_t(n), _p(out)), "h2hip_g1_compress_bn254")
+    return out
+
+
+def g1_validate(points):
+    """read_raw's checks (SerdeFormat::RawBytes read) on (n, 8) uint64 points; H2HipEncodingError when one fails"""
+    points = _u64(points, 8)
+    invalid = np.zeros(2, dtype=np.uint64)
+    _check_encoding(lib().h2hip_g1_validate_bn254(_p(points), ctypes.c_size_t(points.shape[0]), _p(invalid)), "h2hip_g1_validate_bn254", invalid)
+
+
+def fr_from_repr(data):
+    """Fr::from_repr over an array: (n, 32) uint8 canonical little-endian -> (n, 4) uint64 Montgomery; H2HipEncodingError for a value >= r"""
+    data = _bytes32(data, "fr_from_repr")
+    n = data.shape[0]
+    out, invalid = np.zeros((n, 4), dtype=np.uint64), np.zeros(2, dtype=np.uint64)
+    _check_encoding(lib().h2hip_fr_from_repr_bn254(_p(data), ctypes.c_size_t(n), _p(out), _p(invalid)), "h2hip_fr_from_repr_bn254", invalid, out)
+    return out
+
+
+def fr_to_repr(a):
+    """Fr::to_repr over an array: (n, 4) uint64 Montgomery -> (n, 32) uint8"""
+    a = _u64(a, 4)
+    out = np.zeros((a.shape[0], 32), dtype=np.uint8)
+    _check(lib().h2hip_fr_to_repr_bn254(_p(a), ctypes.c_size_t(a.shape[0]), _p(out)), "h2hip_fr_to_repr_bn254")
+    return out
+
+
+# The two G2 points of a params file are converted on the host, in Python integers: Fq2 = Fq[u] / (u^2 + 1), the twist
+# y^2 = x^3 + 3 / (9 + u).  Raw: x.c0 || x.c1 || y.c0 || y.c1, 32-B Montgomery each; compressed: x.c0 || x.c1 canonical little-endian
+# with the low bit of canonical y.c0 in bit 7 of byte 63; all zero bytes: the identity.
+def _fq2_mul(a, b):
+    return ((a[0] * b[0] - a[1] * b[1]) % FQ_MODULUS, (a[0] * b[1] + a[1] * b[0]) % FQ_MODULUS)
+
+
+_G2_B = _fq2_mul((3, 0), (9 * pow(82, -1, FQ_MODULUS) % FQ_MODULUS, -pow(82, -1, FQ_MODULUS) % FQ_MODULUS))  # 3 / (9 + u) = 3 (9 - u) / 82
+
+
+def _fq_sqrt(a):
+    y = pow(a, (FQ_MODULUS + 1) // 4, FQ_MODULUS)
+    return y if y * y % FQ_MODULUS == a % FQ_MODULUS else None
+
+
+def _fq2_sqrt(a):
+    """a square root of a in Fq2 or None: with s^2 = a0^2 + a1^2, x0^2 = (a0 + s) / 2 or (a0 - s) / 2 and x1 = a1 / (2 x0)"""
+    if a == (0, 0):
+        return (0, 0)
+    s = _fq_sqrt((a[0] * a[0] + a[1] * a[1]) % FQ_MODULUS)
+    if s is None:
+        return None
+    half = pow(2, -1, FQ_MODULUS)
+    for cand in ((a[0] + s) * half % FQ_MODULUS, (a[0] - s) * half % FQ_MODULUS):
+        x0 = _fq_sqrt(cand)
+        if x0:
+            r = (x0, a[1] * pow(2 * x0, -1, FQ_MODULUS) % FQ_MODULUS)
+            if _fq2_mul(r, r) == a:
+                return r
+    if a[1] == 0:  # a = -c^2 in Fq: the root is purely imaginary
+        x1 = _fq_sqrt(-a[0] % FQ_MODULUS)
+        if x1 is not None:
+            return (0, x1)
+    return None
+
+
+def _g2_rhs(x):
+    x3 = _fq2_mul(_fq2_mul(x, x), x)
+    return ((x3[0] + _G2_B[0]) % FQ_MODULUS, (x3[1] + _G2_B[1]) % FQ_MODULUS)
+
+
+def _g2_raw(data, check=False):
+    """128 raw bytes of a G2 point (None: the identity); check: RawBytes' checks"""
+    if data is None:
+        return bytes(128)
+    data = bytes(data)
+    if len(data) != 128:
+        raise ValueError("a raw G2 point is 128 bytes")
+    if check and data != bytes(128):
+        c = [int.from_bytes(data[32 * i:32 * i + 32], "little") for i in range(4)]
+        if max(c) >= FQ_MODULUS:
+            raise H2HipError("invalid point encoding: a G2 coordinate is not below q")
+        rinv = pow(_FQ_R, -1, FQ_MODULUS)
+        x, y = tuple(v * rinv % FQ_MODULUS for v in c[:2]), tuple(v * rinv % FQ_MODULUS for v in c[2:])
+        if _fq2_mul(y, y) != _g2_rhs(x):
+            raise H2HipError("invalid point encoding: the G2 point is not on the curve")
+    return data
+
+
+def g2_from_bytes(data):
+    """G2Affine::from_bytes: 64 B compressed -> 128 B raw; H2HipError for an invalid encoding"""
+    data = bytes(data)
+    if len(data) != 64:
+        raise ValueError("a compressed G2 point is 64 bytes")
+    if data == bytes(64):
+        return bytes(128)
+    sign = data[63] >> 7
+    x = (int.from_bytes(data[:32], "little"), int.from_bytes(data[32:63] + bytes([data[63] & 0x7f]), "little"))
+    y = _fq2_sqrt(_g2_rhs(x)) if max(x) < FQ_MODULUS else None
+    if y is None or x == (0, 0):
+        raise H2HipError("invalid point encoding: not a compressed G2 point")
+    if (y[0] & 1) != sign:
+        y = (-y[0] % FQ_MODULUS, -y[1] % FQ_MODULUS)
+    return b"".join((v * _FQ_R % FQ_MODULUS).to_bytes(32, "little") for v in x + y)
+
+
+def g2_to_bytes(raw):
+    """G2Affine::to_bytes: 128 B raw (reduced, on the curve) -> 64 B compressed"""
+    raw = _g2_raw(raw)
+    if raw == bytes(128):
+        return bytes(64)
+    rinv = pow(_FQ_R, -1, FQ_MODULUS)
+    c = [int.from_bytes(raw[32 * i:32 * i + 32], "little") * rinv % FQ_MODULUS for i in range(4)]
+    out = bytearray(c[0].to_bytes(32, "little") + c[1].to_bytes(32, "little"))
+    out[63] |= (c[2] & 1) << 7
+    return bytes(out)
+
+
+def _read_exact(reader, n, what):
+    buf = reader.read(n)
+    if len(buf) != n:
+        raise H2HipError("%s: short read" % what)
+    return buf
+
+
+def read_polynomial(reader, format):
+    """Polynomial::read (poly.rs:152-165): a big-endian u32 length, then that many Fr in the format's encoding (SerdePrimeField,
+    helpers.rs:61-93: Processed canonical, RawBytes* the Montgomery limbs, RawBytes checked to be below r) -> (len, 4) uint64"""
+    format = SerdeFormat(format)
+    n = int.from_bytes(_read_exact(reader, 4, "Polynomial::read"), "big")
+    data = np.frombuffer(_read_exact(reader, 32 * n, "Polynomial::read"), dtype=np.uint8).reshape(n, 32)
+    if format is SerdeFormat.Processed:
+        return fr_from_repr(data)
+    out = data.copy().view(np.uint64).reshape(n, 4)
+    if format is SerdeFormat.RawBytes:
+        top = np.array([(FR_MODULUS >> (64 * i)) & (2**64 - 1) for i in range(4)], dtype=np.uint64)
+        ge = np.zeros(n, dtype=bool)   # limb-wise comparison with r, most significant limb last to decide
+        for i in range(4):
+            ge = np.where(out[:, i] != top[i], out[:, i] > top[i], ge)
+        ge |= (out == top).all(axis=1)
+        if ge.any():
+            raise H2HipError("Invalid prime field point encoding: element %d is not below r" % int(np.argmax(ge)))
+    return out
+
+
+def write_polynomial(poly, writer, format):
+    """Polynomial::write (poly.rs:167-177)"""
+    format = SerdeFormat(format)
+    poly = _u64(poly, 4)
+    writer.write(int(poly.shape[0]).to_bytes(4, "big"))
+    writer.write(fr_to_repr(poly).tobytes() if format is SerdeFormat.Processed else poly.tobytes())
+
+
+def read_polynomial_vec(reader, format):
+    """helpers.rs:116-127: a big-endian u32 count, then that many polynomials"""
+    count = int.from_bytes(_read_exact(reader, 4, "read_polynomial_vec"), "big")
+    return [read_polynomial(reader, format) for _ in range(count)]
+
+
+def write_polynomial_slice(polys, writer, format):
+    """helpers.rs:130-140"""
+    writer.write(len(polys).to_bytes(4, "big"))
+    for poly in polys:
+        write_polynomial(poly, writer, format)
+
+
 # ------------------------------------------------------------------ poly/kzg/commitment.rs
 class ParamsKZG:
     """poly::kzg::commitment::ParamsKZG<Bn256> (poly/kzg/commitment.rs:22-30): g and g_lagrange
     are pinned on the GPU for the life of the object; commit / commit_lagrange are
     best_multiexp over them (:281-292, :327-334; the blind is ignored there too)."""
 
-    def __init__(self, k, g, g_lagrange=None):
-        """g_lagrange None: derived from g with g_to_lagrange, as downsize does (:274)"""
+    def __init__(self, k, g, g_lagrange=None, g2=None, s_g2=None):
+        """g_lagrange None: derived from g with g_to_lagrange, as downsize does (:274).  g2 / s_g2: the verifier's two G2 points, 128 raw
+        bytes each (x.c0 || x.c1 || y.c0 || y.c1, Montgomery), carried for read / write only; zeros (the identity) when not given"""
         self.k, self.n = int(k), 1 << int(k)
         self.g = _u64(g, 8).copy()
         self.g_lagrange = g_to_lagrange(self.g, self.k) if g_lagrange is None else _u64(g_lagrange, 8).copy()
         assert self.g.shape[0] == self.n and self.g_lagrange.shape[0] == self.n
+        self.g2, self.s_g2 = _g2_raw(g2), _g2_raw(s_g2)
+        self._d_g = self._d_g_lagrange = None  # read_custom: the device copies the points were converted or checked in, pinned as they lie
         bases_pin(self.g)
         bases_pin(self.g_lagrange)
+
+    # ---- read / write (poly/kzg/commitment.rs:142-244): k as u32 LE, then g, g_lagrange, g2, s_g2 in the format's point encoding
+    @classmethod
+    def read(cls, reader):
+        """Params::read = read_custom(reader, SerdeFormat::RawBytes) (:300-302)"""
+        return cls.read_custom(reader, SerdeFormat.RawBytes)
+
+    @classmethod
+    def read_custom(cls, reader, format):
+        """ParamsKZG::read_custom (:160-244).  Processed: 32 B per G1 point are uploaded, decompressed on the GPU (one square root each),
+        that device copy is pinned for the commits (bases_pin_device) and the 64-B points come back for g / g_lagrange.  RawBytes: the
+        uploaded copy is checked on the GPU (read_raw's checks) and pinned in the same way.  RawBytesUnchecked: no checks.  A short file
+        or a point that fails its format's checks raises H2HipError, where the reference returns io::Error."""
+        format = SerdeFormat(format)
+        if device_count() < 1:
+            raise H2HipError("ParamsKZG::read: no GPU (the points are converted and checked there; no CPU fallback exists)")
+        import torch
+        kb = reader.read(4)
+        if len(kb) != 4:
+            raise H2HipError("ParamsKZG::read: short read")
+        k = int.from_bytes(kb, "little")
+        if k > FR_S:
+            raise H2HipError("ParamsKZG::read: k = %d > Fr::S" % k)
+        n = 1 << k
+        size = 32 if format is SerdeFormat.Processed else 64
+        host, dev = [], []
+        for what in ("g", "g_lagrange"):
+            buf = reader.read(n * size)
+            if len(buf) != n * size:
+                raise H2HipError("ParamsKZG::read: short read")
+            d_in = torch.from_numpy(np.frombuffer(buf, dtype=np.uint8).reshape(n, size).copy()).cuda()
+            if format is SerdeFormat.Processed:
+                d_pts = torch.empty((n, 8), dtype=torch.int64, device="cuda")
+                g1_from_bytes_device(d_in, d_pts, n)
+            else:
+                d_pts = d_in.view(torch.int64)
+                if format is SerdeFormat.RawBytes:
+                    g1_validate_device(d_pts, n)
+            dev.append(d_pts)
+            host.append(to_numpy_u64(d_pts).copy())
+        g2s = []
+        for what in ("g2", "s_g2"):
+            buf = reader.read(size * 2)
+            if len(buf) != size * 2:
+                raise H2HipError("ParamsKZG::read: short read")
+            g2s.append(g2_from_bytes(buf) if format is SerdeFormat.Processed else _g2_raw(buf, check=format is SerdeFormat.RawBytes))
+        self = cls.__new__(cls)
+        self.k, self.n = k, n
+        self.g, self.g_lagrange = host
+        self.g2, self.s_g2 = g2s
+        self._d_g = self._d_g_lagrange = None
+        for name, d in zip(("_d_g", "_d_g_lagrange"), dev):
+            bases_pin_device(d, n)
+            setattr(self, name, d)
+        return self
+
+    def write(self, writer):
+        """Params::write = write_custom(writer, SerdeFormat::RawBytes) (:296-298)"""
+        self.write_custom(writer, SerdeFormat.RawBytes)
+
+    def write_custom(self, writer, format):
+        """ParamsKZG::write_custom (:142-157); Processed compresses the G1 points on the GPU"""
+        format = SerdeFormat(format)
+        writer.write(int(self.k).to_bytes(4, "little"))
+        for pts in (self.g, self.g_lagrange):
+            writer.write(g1_to_bytes(pts).tobytes() if format is SerdeFormat.Processed else pts.tobytes())
+        for pt in (self.g2, self.s_g2):
+            writer.write(g2_to_bytes(pt) if format is SerdeFormat.Processed else pt)
+
+    def _msm(self, poly, host_bases, d_bases):
+        size = poly.shape[0]
+        if d_bases is None:
+            out = np.zeros(12, dtype=np.uint64)
+            _check(lib().h2hip_msm_bn254(_p(poly), _p(host_bases), ctypes.c_size_t(size), _p(out)), "h2hip_msm_bn254")
+            return out
+        import torch
+        return msm_device(torch.from_numpy(poly.view(np.int64)).cuda(), d_bases, size)
 
     @classmethod
     def setup(cls, k, secret):
@@ -1051,21 +1348,19 @@ class ParamsKZG:
         poly = _u64(poly, 4)
         size = poly.shape[0]
         assert self.g_lagrange.shape[0] >= size  # assert!(bases.len() >= size), :290
-        out = np.zeros(12, dtype=np.uint64)
-        _check(lib().h2hip_msm_bn254(_p(poly), _p(self.g_lagrange), ctypes.c_size_t(size), _p(out)), "h2hip_msm_bn254")
-        return out
+        return self._msm(poly, self.g_lagrange, self._d_g_lagrange)
 
     def commit_lagrange_many(self, polys):
         """the advice-column loop of plonk/prover.rs:361-365 as one pipelined batch"""
-        return best_multiexp_batch(polys, self.g_lagrange)
+        if self._d_g_lagrange is None:
+            return best_multiexp_batch(polys, self.g_lagrange)
+        return np.stack([self.commit_lagrange(p) for p in polys])
 
     def commit(self, poly, blind=None):
         poly = _u64(poly, 4)
         size = poly.shape[0]
         assert self.g.shape[0] >= size  # :332
-        out = np.zeros(12, dtype=np.uint64)
-        _check(lib().h2hip_msm_bn254(_p(poly), _p(self.g), ctypes.c_size_t(size), _p(out)), "h2hip_msm_bn254")
-        return out
+        return self._msm(poly, self.g, self._d_g)
 
     def downsize(self, k):
         """ParamsKZG::downsize (poly/kzg/commitment.rs:267-275)"""
@@ -1080,11 +1375,16 @@ class ParamsKZG:
     def close(self):
         """unpin both arrays (idempotent); also runs when the object is dropped or leaves a `with` block, so a dead
         ParamsKZG never leaves its device copies behind under host addresses numpy may hand out again"""
-        for b in (getattr(self, "g", None), getattr(self, "g_lagrange", None)):
+        for name in ("g", "g_lagrange"):
+            b, d = getattr(self, name, None), getattr(self, "_d_" + name, None)
             if b is None:
                 continue
             try:
-                bases_unpin(b)
+                if d is None:
+                    bases_unpin(b)
+                else:
+                    bases_unpin_device(d)
+                    setattr(self, "_d_" + name, None)
             except H2HipError:
                 pass
 
@@ -1338,6 +1638,34 @@ def key_lagrange_columns_device(domain, blinding_factors, d_l0, d_l_last, d_l_ac
 def set_keygen_group(group_bytes=0):
     """test hook: the HBM one group of columns of a host-pointer keygen call takes (0 = default), so that small inputs run several groups"""
     _check(lib().h2hip_debug_set_keygen_group(ctypes.c_uint64(group_bytes)), "h2hip_debug_set_keygen_group")
+
+
+def g1_from_bytes_device(d_bytes, d_points, n):
+    """d_bytes: n x 32 B, d_points: n x 64 B (torch CUDA tensors); H2HipEncodingError when an encoding is invalid (d_points is written whole)"""
+    invalid = np.zeros(2, dtype=np.uint64)
+    _check_encoding(lib().h2hip_g1_decompress_bn254_device(_dptr(d_bytes), ctypes.c_size_t(n), _dptr(d_points), _p(invalid), _stream()),
+                    "h2hip_g1_decompress_bn254_device", invalid)
+
+
+def g1_to_bytes_device(d_points, d_bytes, n):
+    _check(lib().h2hip_g1_compress_bn254_device(_dptr(d_points), ctypes.c_size_t(n), _dptr(d_bytes), _stream()), "h2hip_g1_compress_bn254_device")
+
+
+def g1_validate_device(d_points, n):
+    invalid = np.zeros(2, dtype=np.uint64)
+    _check_encoding(lib().h2hip_g1_validate_bn254_device(_dptr(d_points), ctypes.c_size_t(n), _p(invalid), _stream()),
+                    "h2hip_g1_validate_bn254_device", invalid)
+
+
+def fr_from_repr_device(d_repr, d_out, n):
+    """d_out may be d_repr"""
+    invalid = np.zeros(2, dtype=np.uint64)
+    _check_encoding(lib().h2hip_fr_from_repr_bn254_device(_dptr(d_repr), ctypes.c_size_t(n), _dptr(d_out), _p(invalid), _stream()),
+                    "h2hip_fr_from_repr_bn254_device", invalid)
+
+
+def fr_to_repr_device(d_in, d_repr, n):
+    _check(lib().h2hip_fr_to_repr_bn254_device(_dptr(d_in), ctypes.c_size_t(n), _dptr(d_repr), _stream()), "h2hip_fr_to_repr_bn254_device")
 
 
 def gen_scalars_device(seed, n, start=0, device="cuda"):

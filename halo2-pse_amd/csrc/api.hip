@@ -912,6 +912,8 @@ static void release_ctx(Ctx* c) {
     c->check_ws.release();
     c->check_io.release();
     c->check_flag.release();
+    c->serde_ws.release();
+    c->serde_io.release();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     c->stream = nullptr;
     for (auto e : c->aux_events) (void)hipEventDestroy(e);

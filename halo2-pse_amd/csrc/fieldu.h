@@ -54,6 +54,13 @@ struct FqU {  // base field, 29-bit limbs
                                           0x11b7bc3cu, 0x1cbd99bau, 0x183340fbu, 0x000e0a77u};  // 2^256 mod p
     static constexpr uint32_t P16[9] = {0x07cfd470u, 0x10460b6cu, 0x072a34f0u, 0x0d522d0eu, 0x185d9781u,
                                         0x0db40c0au, 0x0a6e1411u, 0x05c26340u, 0x030644e7u};    // 16 p
+    static constexpr uint32_t R2_I[9] = {0x059bac10u, 0x0d1503a3u, 0x018016b8u, 0x10ab0ca8u, 0x02632639u,
+                                         0x02c0169fu, 0x169bfd53u, 0x11869d4cu, 0x002a11a6u};   // 2^522 mod p: integer -> I-form
+    static constexpr uint32_t THREE_I[9] = {0x00766463u, 0x1c54760au, 0x08f6927au, 0x03e40c4du, 0x1fea4f2bu,
+                                            0x17c6c26au, 0x157fe417u, 0x0f8056f9u, 0x002958a2u};  // the curve's b = 3, I-form
+    // (p + 1) / 4, 8 x 32-bit little-endian words: p = 3 (mod 4), so t^((p + 1) / 4) is a square root of every square t
+    static constexpr uint32_t SQRT_E[8] = {0xb61f3f52u, 0x4f082305u, 0x5a1c72a3u, 0x65e05aa4u,
+                                           0xa0605617u, 0x6e14116du, 0xb84c680au, 0x0c19139cu};
 };
 
 struct FrU {  // scalar field, 29-bit limbs
@@ -534,6 +541,51 @@ H2_HD Fu fu_inv(const Fu& a) {
     for (int i = top - 1; i >= 0; i--) {
         r = fu_sqr<U>(r);
         if ((e[i >> 5] >> (i & 31)) & 1) r = fu_mul<U>(r, base);
+    }
+    return r;
+}
+
+// t^((p + 1) / 4) on the unsaturated multiplier, for U = FqU (p = 3 mod 4): the candidate square root of halo2curves' Fq::sqrt, whose
+// caller finishes with the test y^2 == t (a non-residue t gives a y whose square is -t).  I-form in (|value| < 32 p, limbs < 2^29 in
+// magnitude: a normalised value), I-form out in (-0.2 p, 1.2 p) with limbs 0..7 in [0, 2^29); 0 -> 0.  Every operand of every product
+// below is a fu_mul / fu_sqr result, so fu_mul's bound holds with room (9 * 2^58 + 9 * 2^58 + 2^36 < 2^63).
+// The exponent is a constant of 252 bits = 63 windows of 4: the top window (0xc) starts the chain as (t^3)^4, each further window is
+// 4 squarings and, where its digit d = odd * 2^s is non-zero, one product by t^odd placed after the first 4 - s of them: 251 squarings
+// and 56 + 8 products in all, against 251 + 108 for the binary chain.  The loop is kept (about 310 multipliers unrolled would not fit the
+// instruction cache); the digits come from literal words and are the same in every lane, so the walk is uniform over a wave, and the 8
+// odd powers are picked by a switch over named values, never by indexing an array with a run-time digit (which would put it in scratch).
+template <class U>
+H2_HD Fu fu_sqrt(const Fu& t) {
+    const Fu p1 = fu_mul<U>(t, fu_one_i<U>());  // bring |value| inside (-0.2 p, 1.2 p), same residue
+    const Fu t2 = fu_sqr<U>(p1);
+    const Fu p3 = fu_mul<U>(p1, t2), p5 = fu_mul<U>(p3, t2), p7 = fu_mul<U>(p5, t2), p9 = fu_mul<U>(p7, t2), p11 = fu_mul<U>(p9, t2),
+             p13 = fu_mul<U>(p11, t2), p15 = fu_mul<U>(p13, t2);
+    static_assert((U::SQRT_E[7] >> 24) == 0xc, "the chain below starts from the top window 0xc = 3 << 2");
+    Fu r = fu_sqr<U>(fu_sqr<U>(p3));
+    for (int w = 61; w >= 0; w--) {
+        uint32_t word = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            if (i == (w >> 3)) word = U::SQRT_E[i];
+        const uint32_t d = (word >> ((w & 7) * 4)) & 15u;
+        // d = odd * 2^s: the product by t^odd follows squaring 4 - s of the window's four (at = 4: none, a zero digit)
+        const int at = !d ? 4 : (d & 1) ? 3 : (d & 2) ? 2 : (d & 4) ? 1 : 0;
+        Fu m;
+        switch (d >> (3 - (at & 3))) {
+            case 3: m = p3; break;
+            case 5: m = p5; break;
+            case 7: m = p7; break;
+            case 9: m = p9; break;
+            case 11: m = p11; break;
+            case 13: m = p13; break;
+            case 15: m = p15; break;
+            default: m = p1; break;
+        }
+#pragma unroll 1
+        for (int j = 0; j < 4; j++) {
+            r = fu_sqr<U>(r);
+            if (j == at) r = fu_mul<U>(r, m);
+        }
     }
     return r;
 }

@@ -20,6 +20,7 @@
 #include <cstdint>
 #include <cstring>
 #include <istream>
+#include <ostream>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -84,6 +85,135 @@ struct G1 {
     bool operator==(const G1& o) const { return to_affine() == o.to_affine(); }
 };
 static_assert(sizeof(G1) == 96, "G1 layout");
+
+// SerdeFormat (helpers.rs:8-20)
+enum class SerdeFormat {
+    Processed,          // curve points compressed, field elements canonical; every element checked
+    RawBytes,           // the in-memory Montgomery limbs; coordinates below the modulus and points on the curve checked
+    RawBytesUnchecked,  // the same bytes, no checks
+};
+
+// The host-only part of the formats: the two G2 points of a params file (Fq2 = Fq[u] / (u^2 + 1), the twist y^2 = x^3 + 3 / (9 + u))
+// over field.h, and a host decompression of one G1 point by fe_pow, the yardstick tools/serde_host.cpp times the GPU against.
+// Raw G2: x.c0 || x.c1 || y.c0 || y.c1, 32-B Montgomery each; compressed: x.c0 || x.c1 canonical little-endian with the low bit of
+// canonical y.c0 in bit 7 of byte 63; all zero bytes: the identity.
+namespace serde {
+typedef h2::FqP Q;
+using h2::Fe;
+struct Fq2 {
+    Fe c0, c1;
+};
+inline const uint32_t* fq_sqrt_exponent() {  // (q + 1) / 4
+    static const uint32_t e[8] = {0xb61f3f52u, 0x4f082305u, 0x5a1c72a3u, 0x65e05aa4u, 0xa0605617u, 0x6e14116du, 0xb84c680au, 0x0c19139cu};
+    return e;
+}
+// q = 3 (mod 4): t^((q + 1) / 4) is a root of every square
+inline bool fq_sqrt(const Fe& t, Fe* y) {
+    *y = h2::fe_pow<Q>(t, fq_sqrt_exponent());
+    return h2::fe_eq(h2::fe_sqr<Q>(*y), t);
+}
+inline Fq2 fq2_mul(const Fq2& a, const Fq2& b) {
+    return {h2::fe_sub<Q>(h2::fe_mul<Q>(a.c0, b.c0), h2::fe_mul<Q>(a.c1, b.c1)), h2::fe_add<Q>(h2::fe_mul<Q>(a.c0, b.c1), h2::fe_mul<Q>(a.c1, b.c0))};
+}
+inline bool fq2_eq(const Fq2& a, const Fq2& b) { return h2::fe_eq(a.c0, b.c0) && h2::fe_eq(a.c1, b.c1); }
+// x^3 + 3 / (9 + u), with 3 / (9 + u) = 3 (9 - u) / 82
+inline Fq2 g2_rhs(const Fq2& x) {
+    const Fe i82 = h2::fe_inv<Q>(h2::fe_from_u64<Q>(82));
+    const Fq2 b = {h2::fe_mul<Q>(h2::fe_from_u64<Q>(27), i82), h2::fe_neg<Q>(h2::fe_mul<Q>(h2::fe_from_u64<Q>(3), i82))};
+    const Fq2 x3 = fq2_mul(fq2_mul(x, x), x);
+    return {h2::fe_add<Q>(x3.c0, b.c0), h2::fe_add<Q>(x3.c1, b.c1)};
+}
+// a root of a, any of the two: with s^2 = a0^2 + a1^2, x0^2 = (a0 + s) / 2 or (a0 - s) / 2 and x1 = a1 / (2 x0)
+inline bool fq2_sqrt(const Fq2& a, Fq2* r) {
+    if (h2::fe_is_zero(a.c0) && h2::fe_is_zero(a.c1)) {
+        *r = a;
+        return true;
+    }
+    Fe s, x0;
+    if (!fq_sqrt(h2::fe_add<Q>(h2::fe_sqr<Q>(a.c0), h2::fe_sqr<Q>(a.c1)), &s)) return false;
+    const Fe half = h2::fe_inv<Q>(h2::fe_from_u64<Q>(2));
+    for (const Fe& cand : {h2::fe_mul<Q>(h2::fe_add<Q>(a.c0, s), half), h2::fe_mul<Q>(h2::fe_sub<Q>(a.c0, s), half)}) {
+        if (!fq_sqrt(cand, &x0) || h2::fe_is_zero(x0)) continue;
+        *r = {x0, h2::fe_mul<Q>(a.c1, h2::fe_inv<Q>(h2::fe_dbl<Q>(x0)))};
+        if (fq2_eq(fq2_mul(*r, *r), a)) return true;
+    }
+    if (h2::fe_is_zero(a.c1) && fq_sqrt(h2::fe_neg<Q>(a.c0), &x0)) {  // a = -c^2 in Fq: the root is purely imaginary
+        *r = {h2::fe_zero<Q>(), x0};
+        return true;
+    }
+    return false;
+}
+inline bool all_zero(const uint8_t* p, size_t n) {
+    for (size_t i = 0; i < n; i++)
+        if (p[i]) return false;
+    return true;
+}
+// read_raw's checks for a raw G2 point
+inline bool g2_is_valid(const std::array<uint8_t, 128>& raw) {
+    if (all_zero(raw.data(), 128)) return true;
+    Fe c[4];
+    std::memcpy(c, raw.data(), 128);
+    for (const Fe& v : c)
+        if (!h2::fe_is_canonical<Q>(v)) return false;
+    const Fq2 y = {c[2], c[3]};
+    return fq2_eq(fq2_mul(y, y), g2_rhs({c[0], c[1]}));
+}
+inline bool g2_from_bytes(const uint8_t in[64], std::array<uint8_t, 128>& raw) {
+    raw.fill(0);
+    if (all_zero(in, 64)) return true;
+    Fe c[2];
+    std::memcpy(c, in, 64);
+    const uint32_t sign = c[1].l[7] >> 31;
+    c[1].l[7] &= 0x7fffffffu;
+    if (!h2::fe_is_canonical<Q>(c[0]) || !h2::fe_is_canonical<Q>(c[1])) return false;
+    const Fq2 x = {h2::fe_from_canonical<Q>(c[0]), h2::fe_from_canonical<Q>(c[1])};
+    Fq2 y;
+    if ((h2::fe_is_zero(x.c0) && h2::fe_is_zero(x.c1)) || !fq2_sqrt(g2_rhs(x), &y)) return false;
+    if ((h2::fe_to_canonical<Q>(y.c0).l[0] & 1u) != sign) y = {h2::fe_neg<Q>(y.c0), h2::fe_neg<Q>(y.c1)};
+    const Fe out[4] = {x.c0, x.c1, y.c0, y.c1};
+    std::memcpy(raw.data(), out, 128);
+    return true;
+}
+inline void g2_to_bytes(const std::array<uint8_t, 128>& raw, uint8_t out[64]) {
+    std::memset(out, 0, 64);
+    if (all_zero(raw.data(), 128)) return;
+    Fe c[4];
+    std::memcpy(c, raw.data(), 128);
+    Fe x[2] = {h2::fe_to_canonical<Q>(c[0]), h2::fe_to_canonical<Q>(c[1])};
+    x[1].l[7] |= (h2::fe_to_canonical<Q>(c[2]).l[0] & 1u) << 31;
+    std::memcpy(out, x, 64);
+}
+// G1Affine::from_bytes on the host, one point: what h2hip_g1_decompress_bn254 does per lane
+inline bool g1_from_bytes_host(const uint8_t in[32], G1Affine& out) {
+    std::memset(&out, 0, 64);
+    Fe xc;
+    std::memcpy(xc.l, in, 32);
+    const uint32_t sign = xc.l[7] >> 31;
+    xc.l[7] &= 0x7fffffffu;
+    if (h2::fe_is_zero(xc)) return !sign;
+    if (!h2::fe_is_canonical<Q>(xc)) return false;
+    const Fe x = h2::fe_from_canonical<Q>(xc);
+    Fe y;
+    if (!fq_sqrt(h2::fe_add<Q>(h2::fe_mul<Q>(h2::fe_sqr<Q>(x), x), h2::fe_from_u64<Q>(3)), &y)) return false;
+    if ((h2::fe_to_canonical<Q>(y).l[0] & 1u) != sign) y = h2::fe_neg<Q>(y);
+    std::memcpy(out.x, x.l, 32);
+    std::memcpy(out.y, y.l, 32);
+    return true;
+}
+inline void read_exact(std::istream& reader, void* dst, size_t n, const char* what) {
+    reader.read(reinterpret_cast<char*>(dst), std::streamsize(n));
+    if (!reader || size_t(reader.gcount()) != n) throw std::runtime_error(std::string(what) + ": short read");
+}
+inline uint32_t read_u32_be(std::istream& reader, const char* what) {
+    uint8_t b[4];
+    read_exact(reader, b, 4, what);
+    return uint32_t(b[0]) << 24 | uint32_t(b[1]) << 16 | uint32_t(b[2]) << 8 | uint32_t(b[3]);
+}
+inline void write_u32_be(std::ostream& writer, uint32_t v) {
+    const char b[4] = {char(v >> 24), char(v >> 16), char(v >> 8), char(v)};
+    writer.write(b, 4);
+}
+}  // namespace serde
 
 inline void engine_check(int rc, const char* what) {
     if (rc != 0) throw std::runtime_error(std::string(what) + ": " + h2hip_last_error());
@@ -222,6 +352,51 @@ struct Polynomial {
     const Fr& operator[](size_t i) const { return values[i]; }
 };
 
+// Polynomial::read (poly.rs:152-165): a big-endian u32 length, then that many Fr in the format's encoding (SerdePrimeField,
+// helpers.rs:61-93).  Processed: canonical little-endian, converted and checked on the GPU (h2hip_fr_from_repr_bn254); RawBytes: the
+// Montgomery limbs, checked to be below r; RawBytesUnchecked: no checks.  A failed check throws where the reference returns io::Error.
+template <class Basis>
+inline Polynomial<Basis> read_polynomial(std::istream& reader, SerdeFormat format) {
+    const uint32_t len = serde::read_u32_be(reader, "Polynomial::read");
+    Polynomial<Basis> p{std::vector<Fr>(len)};
+    if (len == 0) return p;
+    serde::read_exact(reader, p.values.data(), size_t(len) * 32, "Polynomial::read");
+    if (format == SerdeFormat::Processed) {
+        uint64_t invalid[2];
+        engine_check(h2hip_fr_from_repr_bn254(p.values[0].l, len, p.values[0].l, invalid), "Invalid prime field point encoding");
+    } else if (format == SerdeFormat::RawBytes) {
+        for (const Fr& v : p.values)
+            if (!h2::fe_is_canonical<h2::FrP>(v.fe())) throw std::runtime_error("Polynomial::read: Invalid prime field point encoding");
+    }
+    return p;
+}
+// Polynomial::write (poly.rs:167-177)
+template <class Basis>
+inline void write_polynomial(const Polynomial<Basis>& p, std::ostream& writer, SerdeFormat format) {
+    serde::write_u32_be(writer, uint32_t(p.len()));
+    if (p.len() == 0) return;
+    if (format == SerdeFormat::Processed) {
+        std::vector<uint8_t> repr(p.len() * 32);
+        engine_check(h2hip_fr_to_repr_bn254(p.values[0].l, p.len(), repr.data()), "h2hip_fr_to_repr_bn254");
+        writer.write(reinterpret_cast<const char*>(repr.data()), std::streamsize(repr.size()));
+    } else {
+        writer.write(reinterpret_cast<const char*>(p.values.data()), std::streamsize(p.len() * 32));
+    }
+}
+// read_polynomial_vec / write_polynomial_slice (helpers.rs:116-140): a big-endian u32 count, then the polynomials
+template <class Basis>
+inline std::vector<Polynomial<Basis>> read_polynomial_vec(std::istream& reader, SerdeFormat format) {
+    const uint32_t count = serde::read_u32_be(reader, "read_polynomial_vec");
+    std::vector<Polynomial<Basis>> out;
+    for (uint32_t i = 0; i < count; i++) out.push_back(read_polynomial<Basis>(reader, format));
+    return out;
+}
+template <class Basis>
+inline void write_polynomial_slice(const std::vector<Polynomial<Basis>>& slice, std::ostream& writer, SerdeFormat format) {
+    serde::write_u32_be(writer, uint32_t(slice.size()));
+    for (const auto& p : slice) write_polynomial(p, writer, format);
+}
+
 // EvaluationDomain<Fr> (poly/domain.rs:18-34)
 class EvaluationDomain {
    public:
@@ -345,7 +520,7 @@ class ParamsKZG {
     uint32_t k = 0;
     uint64_t n = 0;
     std::vector<G1Affine> g, g_lagrange;
-    std::array<uint8_t, 128> g2{}, s_g2{};  // carried opaquely (pairing is not on this path)
+    std::array<uint8_t, 128> g2{}, s_g2{};  // raw bytes, carried for read / write only (pairing is not on this path)
 
     ParamsKZG() = default;
     ParamsKZG(const ParamsKZG&) = delete;
@@ -372,42 +547,71 @@ class ParamsKZG {
         setup(k, s, p);
     }
 
-    // SerdeFormat (helpers.rs:8-21); `Processed` (compressed points) is not on this path
-    enum class SerdeFormat { RawBytes, RawBytesUnchecked };
+    using SerdeFormat = halo2_proofs::SerdeFormat;  // helpers.rs:8-20
 
-    // Params::read = read_custom(reader, SerdeFormat::RawBytes) (poly/kzg/commitment.rs:160-244, :300-302):
-    // k as u32 LE, then g, g_lagrange as 64-B Montgomery points, then g2, s_g2 (128 B each).  RawBytes checks that
-    // every coordinate is below the modulus and every point lies on the curve (helpers.rs:15-18, read_raw);
-    // RawBytesUnchecked performs no checks (:19-20).
+    // Params::read = read_custom(reader, SerdeFormat::RawBytes) (poly/kzg/commitment.rs:160-244, :300-302): k as u32 LE, then g,
+    // g_lagrange, g2, s_g2 in the format's point encoding.  Processed: 32-B compressed G1 points, decompressed on the GPU
+    // (h2hip_g1_decompress_bn254: one square root per point), 64-B compressed G2 points on the host.  RawBytes: 64-B Montgomery
+    // points whose checks -- every coordinate below the modulus, every point on the curve (helpers.rs:15-18, read_raw) -- run on the
+    // GPU (h2hip_g1_validate_bn254).  RawBytesUnchecked performs no checks (:19-20).
     static void read(std::istream& reader, ParamsKZG& p) { read_custom(reader, p, SerdeFormat::RawBytes); }
     static void read_custom(std::istream& reader, ParamsKZG& p, SerdeFormat format) {
         uint8_t kb[4];
-        reader.read(reinterpret_cast<char*>(kb), 4);
-        if (!reader) throw std::runtime_error("ParamsKZG::read: short read");
+        serde::read_exact(reader, kb, 4, "ParamsKZG::read");
         p.unpin();
         p.k = uint32_t(kb[0]) | uint32_t(kb[1]) << 8 | uint32_t(kb[2]) << 16 | uint32_t(kb[3]) << 24;
         if (p.k > Fr::S) throw std::runtime_error("ParamsKZG::read: k too large");
         p.n = uint64_t(1) << p.k;
         p.g.resize(p.n);
         p.g_lagrange.resize(p.n);
-        reader.read(reinterpret_cast<char*>(p.g.data()), std::streamsize(p.n * 64));
-        reader.read(reinterpret_cast<char*>(p.g_lagrange.data()), std::streamsize(p.n * 64));
-        reader.read(reinterpret_cast<char*>(p.g2.data()), 128);
-        reader.read(reinterpret_cast<char*>(p.s_g2.data()), 128);
-        if (!reader) throw std::runtime_error("ParamsKZG::read: short read");
-        if (format == SerdeFormat::RawBytes) {
-            for (const auto* v : {&p.g, &p.g_lagrange})
-                for (const G1Affine& pt : *v)
-                    if (!point_is_valid(pt)) throw std::runtime_error("ParamsKZG::read: invalid point encoding");
+        uint64_t invalid[2];
+        std::vector<uint8_t> packed(format == SerdeFormat::Processed ? p.n * 32 : 0);
+        for (auto* v : {&p.g, &p.g_lagrange}) {
+            if (format == SerdeFormat::Processed) {
+                serde::read_exact(reader, packed.data(), packed.size(), "ParamsKZG::read");
+                engine_check(h2hip_g1_decompress_bn254(packed.data(), p.n, (*v)[0].x, invalid), "ParamsKZG::read: invalid point encoding");
+            } else {
+                serde::read_exact(reader, v->data(), p.n * 64, "ParamsKZG::read");
+                if (format == SerdeFormat::RawBytes)
+                    engine_check(h2hip_g1_validate_bn254((*v)[0].x, p.n, invalid), "ParamsKZG::read: invalid point encoding");
+            }
+        }
+        for (auto* pt : {&p.g2, &p.s_g2}) {
+            if (format == SerdeFormat::Processed) {
+                uint8_t c[64];
+                serde::read_exact(reader, c, 64, "ParamsKZG::read");
+                if (!serde::g2_from_bytes(c, *pt)) throw std::runtime_error("ParamsKZG::read: invalid point encoding");
+            } else {
+                serde::read_exact(reader, pt->data(), 128, "ParamsKZG::read");
+                if (format == SerdeFormat::RawBytes && !serde::g2_is_valid(*pt)) throw std::runtime_error("ParamsKZG::read: invalid point encoding");
+            }
         }
         p.pin();
     }
 
-    // read_raw's checks for one G1Affine: limbs below the modulus, point on y^2 = x^3 + 3 (the identity is (0, 0))
-    static bool point_is_valid(const G1Affine& pt) {
-        h2::Affine a;
-        std::memcpy(&a, &pt, 64);
-        return h2::fe_is_canonical<h2::FqP>(a.x) && h2::fe_is_canonical<h2::FqP>(a.y) && h2::affine_on_curve(a);
+    // Params::write = write_custom(writer, SerdeFormat::RawBytes) (poly/kzg/commitment.rs:142-157, :296-298)
+    void write(std::ostream& writer) const { write_custom(writer, SerdeFormat::RawBytes); }
+    void write_custom(std::ostream& writer, SerdeFormat format) const {
+        const char kb[4] = {char(k), char(k >> 8), char(k >> 16), char(k >> 24)};
+        writer.write(kb, 4);
+        std::vector<uint8_t> packed(format == SerdeFormat::Processed ? n * 32 : 0);
+        for (const auto* v : {&g, &g_lagrange}) {
+            if (format == SerdeFormat::Processed) {
+                engine_check(h2hip_g1_compress_bn254((*v)[0].x, n, packed.data()), "h2hip_g1_compress_bn254");
+                writer.write(reinterpret_cast<const char*>(packed.data()), std::streamsize(packed.size()));
+            } else {
+                writer.write(reinterpret_cast<const char*>(v->data()), std::streamsize(n * 64));
+            }
+        }
+        for (const auto* pt : {&g2, &s_g2}) {
+            if (format == SerdeFormat::Processed) {
+                uint8_t c[64];
+                serde::g2_to_bytes(*pt, c);
+                writer.write(reinterpret_cast<const char*>(c), 64);
+            } else {
+                writer.write(reinterpret_cast<const char*>(pt->data()), 128);
+            }
+        }
     }
 
     // downsize (poly/kzg/commitment.rs:267-275)

@@ -621,3 +621,86 @@ pub fn try_check_lookups<F: Field + 'static>(k: u32, compressed_inputs: &[&[F]],
     }
     Some(check_report(counts, rows, max_rows))
 }
+
+/// What a fallible conversion found: how many elements fail the format's checks, and the lowest index of them.  The caller turns
+/// it into the reference's `io::Error` ("invalid point encoding" / "Invalid prime field point encoding").
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct InvalidEncoding {
+    pub count: u64,
+    pub first: u64,
+}
+
+/// an element fails its format's checks
+pub const H2HIP_EENCODING: i32 = 5;
+
+/// `rc` and `invalid[]` of a fallible call: `None` when the engine did not take it, `Some(Err)` when it did and elements are invalid
+fn encoding_result<T>(rc: i32, invalid: [u64; 2], value: T) -> Option<Result<T, InvalidEncoding>> {
+    match rc {
+        H2HIP_OK => Some(Ok(value)),
+        H2HIP_EENCODING => Some(Err(InvalidEncoding { count: invalid[0], first: invalid[1] })),
+        _ => None,
+    }
+}
+
+/// `SerdeFormat::Processed` read of `bytes.len()` G1 points (`G1Affine::from_bytes` per element, one square root each) on the GPU.
+pub fn try_g1_decompress<C: CurveAffine>(bytes: &[[u8; 32]]) -> Option<Result<Vec<C>, InvalidEncoding>> {
+    if !is::<C, G1Affine>() || !layout_ok() || bytes.len() > 1 << 30 {
+        return None;
+    }
+    let mut out = vec![C::identity(); bytes.len()];
+    let mut invalid = [0u64; 2];
+    let rc = unsafe {
+        ffi::h2hip_g1_decompress_bn254(bytes.as_ptr() as *const std::os::raw::c_void, bytes.len(), out.as_mut_ptr() as *mut u64, invalid.as_mut_ptr())
+    };
+    encoding_result(rc, invalid, out)
+}
+
+/// `SerdeFormat::Processed` write: `G1Affine::to_bytes` per element.
+pub fn try_g1_compress<C: CurveAffine>(points: &[C]) -> Option<Vec<[u8; 32]>> {
+    if !is::<C, G1Affine>() || !layout_ok() || points.len() > 1 << 30 {
+        return None;
+    }
+    let mut out = vec![[0u8; 32]; points.len()];
+    let rc = unsafe { ffi::h2hip_g1_compress_bn254(points.as_ptr() as *const u64, points.len(), out.as_mut_ptr() as *mut std::os::raw::c_void) };
+    if rc != 0 {
+        return None;
+    }
+    Some(out)
+}
+
+/// `SerdeFormat::RawBytes` read: `read_raw`'s checks (coordinates below the modulus, point on the curve) on points read with
+/// `read_raw_unchecked`.
+pub fn try_g1_validate<C: CurveAffine>(points: &[C]) -> Option<Result<(), InvalidEncoding>> {
+    if !is::<C, G1Affine>() || !layout_ok() || points.len() > 1 << 30 {
+        return None;
+    }
+    let mut invalid = [0u64; 2];
+    let rc = unsafe { ffi::h2hip_g1_validate_bn254(points.as_ptr() as *const u64, points.len(), invalid.as_mut_ptr()) };
+    encoding_result(rc, invalid, ())
+}
+
+/// `Fr::from_repr` over a vector (`SerdePrimeField::read`, `Processed`): canonical little-endian to Montgomery, values >= r invalid.
+pub fn try_fr_from_repr<F: Field + 'static>(repr: &[[u8; 32]]) -> Option<Result<Vec<F>, InvalidEncoding>> {
+    if !is::<F, Fr>() || !layout_ok() || repr.len() > 1 << 30 {
+        return None;
+    }
+    let mut out = vec![F::zero(); repr.len()];
+    let mut invalid = [0u64; 2];
+    let rc = unsafe {
+        ffi::h2hip_fr_from_repr_bn254(repr.as_ptr() as *const std::os::raw::c_void, repr.len(), out.as_mut_ptr() as *mut u64, invalid.as_mut_ptr())
+    };
+    encoding_result(rc, invalid, out)
+}
+
+/// `Fr::to_repr` over a vector (`SerdePrimeField::write`, `Processed`).
+pub fn try_fr_to_repr<F: Field + 'static>(values: &[F]) -> Option<Vec<[u8; 32]>> {
+    if !is::<F, Fr>() || !layout_ok() || values.len() > 1 << 30 {
+        return None;
+    }
+    let mut out = vec![[0u8; 32]; values.len()];
+    let rc = unsafe { ffi::h2hip_fr_to_repr_bn254(values.as_ptr() as *const u64, values.len(), out.as_mut_ptr() as *mut std::os::raw::c_void) };
+    if rc != 0 {
+        return None;
+    }
+    Some(out)
+}

@@ -57,6 +57,7 @@ extern "C" {
 #define H2HIP_EDEVICE 2  /* HIP runtime / device error, or no GPU */
 #define H2HIP_ENOMEM 3
 #define H2HIP_ELOOKUP 4  /* a lookup's input holds a value its table lacks (lookup::Argument::commit_permuted: Error::ConstraintSystemFailure) */
+#define H2HIP_EENCODING 5  /* an element fails its format's checks (the reference's io::Error "invalid point encoding" / "Invalid prime field point encoding") */
 
 /* ---- lifecycle ------------------------------------------------------------------------- */
 
@@ -521,6 +522,35 @@ int h2hip_check_lookups_bn254(uint32_t k, const uint64_t* const* compressed_inpu
 int h2hip_check_lookups_bn254_device(uint32_t k, const void* const* d_compressed_input, const void* const* d_compressed_table, size_t count,
                                      uint32_t blinding_factors, uint32_t max_rows, uint64_t* counts, uint32_t* rows, void* stream);
 
+/* ---- serialisation: the per-element work of SerdeFormat (helpers.rs:8-20) in ParamsKZG::read_custom / write_custom
+ * (poly/kzg/commitment.rs:142-244) and Polynomial::read / write (poly.rs:152-177) ------------------------------------------------------
+ * n <= 2^30 elements, one GPU lane each; n == 0 succeeds and touches nothing but invalid[].  Byte buffers are plain bytes (no alignment
+ * is asked of host memory).  Encodings (halo2curves 0.3.1 GroupEncoding / SerdePrimeField as DESIGN.md section 2 records them):
+ *   compressed G1 : 32 B, canonical (non-Montgomery) x little-endian, bit 7 of byte 31 = the low bit of canonical y; identity = 32 zero bytes
+ *   Fr repr       : 32 B, the canonical integer little-endian
+ * g1_decompress (SerdeFormat::Processed read, helpers.rs:36-40): points[i] = x || y, 64 B Montgomery.  An encoding is invalid when
+ * x >= q (bit 254 set included), when x^3 + 3 is not a square, or when it is x = 0 with the sign bit set.
+ * g1_compress (Processed write, helpers.rs:49-57) is the inverse; (0, 0) gives 32 zero bytes.  Points are taken as reduced and on the curve.
+ * g1_validate (SerdeFormat::RawBytes read, read_raw): a point is invalid unless both coordinates are below q and it is (0, 0) or
+ * satisfies y^2 = x^3 + 3.
+ * fr_from_repr / fr_to_repr (SerdePrimeField, helpers.rs:61-93): canonical integer <-> Montgomery form; a value >= r is invalid.  The
+ * output may be the input buffer.
+ * The three fallible calls write ALL of their output -- an invalid element as zero bytes -- and invalid[] (host memory) =
+ * {number of invalid elements, lowest invalid index} ({0, 0} when there is none), a function of the input alone; they return
+ * H2HIP_EENCODING exactly when invalid[0] > 0.  Host forms upload, convert and download on the engine's stream.  _device forms take
+ * device pointers and queue on `stream`; the fallible ones synchronise it once to deliver invalid[] (as the witness check does for its
+ * counts), g1_compress / fr_to_repr return with their kernel queued. */
+int h2hip_g1_decompress_bn254(const void* bytes, size_t n, uint64_t* points_xy, uint64_t invalid[2]);
+int h2hip_g1_decompress_bn254_device(const void* d_bytes, size_t n, void* d_points_xy, uint64_t invalid[2], void* stream);
+int h2hip_g1_compress_bn254(const uint64_t* points_xy, size_t n, void* bytes);
+int h2hip_g1_compress_bn254_device(const void* d_points_xy, size_t n, void* d_bytes, void* stream);
+int h2hip_g1_validate_bn254(const uint64_t* points_xy, size_t n, uint64_t invalid[2]);
+int h2hip_g1_validate_bn254_device(const void* d_points_xy, size_t n, uint64_t invalid[2], void* stream);
+int h2hip_fr_from_repr_bn254(const void* repr, size_t n, uint64_t* out, uint64_t invalid[2]);
+int h2hip_fr_from_repr_bn254_device(const void* d_repr, size_t n, void* d_out, uint64_t invalid[2], void* stream);
+int h2hip_fr_to_repr_bn254(const uint64_t* in, size_t n, void* repr);
+int h2hip_fr_to_repr_bn254_device(const void* d_in, size_t n, void* d_repr, void* stream);
+
 /* ---- synthetic workload; same streams as oracle_gen_{scalars,points} ---- */
 
 int h2hip_gen_scalars_device(uint64_t seed, uint64_t start, size_t n, void* d_out, void* stream);
@@ -537,7 +567,8 @@ uint32_t h2hip_get_msm_window_fixed_base(size_t n);
 /* Per-stage HIP-event timers recorded on the stream each kernel group is launched on.
  * Stages: "ntt", "msm_total", "msm_digits", "msm_sort", "msm_accum" (over-full buckets included), "msm_reduce", "g_to_lagrange", "kzg_setup",
  * "evalh_cosets", "evalh_gates", "evalh_perm", "evalh_lookups", "products", "opening_eval", "opening_combine", "lookup_compress",
- * "lookup_permute", "check_gates", "check_permutation", "check_lookups" (each check: its kernels, without the delivery of counts / rows). */
+ * "lookup_permute", "check_gates", "check_permutation", "check_lookups" (each check: its kernels, without the delivery of counts / rows),
+ * "g1_decompress", "g1_validate", "fr_from_repr" (each with its failure count; the _device forms too), "g1_compress", "fr_to_repr" (host forms). */
 /* on = 1: every stage (each event record costs the stream ~10 us of gap); on = 2: only the dominant kernel ("msm_accum"),
  * timed through its own dispatch packet with no gap; 0: off */
 int h2hip_profile_enable(int on);
