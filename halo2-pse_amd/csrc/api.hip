@@ -987,10 +987,11 @@ __global__ void pin_sample_kernel(const Affine* __restrict__ src, size_t total, 
 static const MsmTable* pinned_table(Ctx* c, const void* key, size_t n, MsmTable* out, const PinnedBases** entry) {
     auto it = c->pinned.find(key);
     if (it == c->pinned.end() || !it->second.device_key || n > it->second.n || !it->second.c) return nullptr;
-    out->table = (const Affine*)it->second.d;
+    out->table = it->second.d;
     out->stride = it->second.n;
     out->c = it->second.c;
     out->W = it->second.W;
+    out->rec = it->second.rec;
     *entry = &it->second;
     return out;
 }
@@ -1142,12 +1143,13 @@ static int msm_shard_host(Ctx* c, const uint64_t* const* scalars, const uint64_t
     auto it = c->pinned.find((const void*)bases_xy);
     if (use_cache && it != c->pinned.end() && it->second.lo <= lo && lo + n <= it->second.hi) {
         const PinnedBases& pb = it->second;
-        d_bases = (const Affine*)pb.d + (lo - pb.lo);
+        d_bases = (const Affine*)pb.d + (lo - pb.lo);  // (without a table: the points themselves)
         if (pb.c) {
-            tab.table = d_bases;
+            tab.table = (const char*)pb.d + (lo - pb.lo) * pb.rec;
             tab.stride = pb.n;
             tab.c = pb.c;
             tab.W = pb.W;
+            tab.rec = pb.rec;
             t = &tab;
         }
     } else {
@@ -1316,6 +1318,8 @@ int h2hip_msm_bn254_batch_device(const void* const* d_scalars, const void* d_bas
     return 0;
 }
 
+static uint32_t g_table_records = 0;  // h2hip_debug_set_table_records
+
 // Pin points [lo, hi) of the caller's array on device context c (worker thread of that device, or the caller's for
 // device 0): device copy + window table.  d_src != nullptr: the points already live on this device.
 static int pin_on_device(Ctx* c, const void* key, const uint64_t* h_points, const void* d_src, size_t lo, size_t hi, size_t n_total,
@@ -1336,13 +1340,20 @@ static int pin_on_device(Ctx* c, const void* key, const uint64_t* h_points, cons
     pb.hi = hi;
     pb.device_key = device_key;
     if (sample) memcpy(pb.sample, sample, sizeof(pb.sample));
-    uint32_t cw = 0, W = 1;
+    uint32_t cw = 0, W = 1, rec = sizeof(Affine);
     if (g_cfg.fixed_base && n <= ((size_t)1 << 26)) {
         cw = msm_table_window(n);
         W = (255 + cw - 1) / cw;
-        if ((size_t)W * n * sizeof(Affine) > g_cfg.table_max_bytes) cw = 0, W = 1;
+        rec = msm_table_rec(n, g_table_records);
+        if ((size_t)W * n * rec > g_cfg.table_max_bytes) rec = sizeof(Affine);  // the native table would be refused: the E-form one may still fit
+        if ((size_t)W * n * rec > g_cfg.table_max_bytes) cw = 0, W = 1;
     }
-    hipError_t e = hipMalloc(&pb.d, (size_t)W * n * sizeof(Affine));
+    hipError_t e = hipMalloc(&pb.d, (size_t)W * n * rec);
+    if (e != hipSuccess && cw && rec != sizeof(Affine)) {  // no room for the native table: the E-form one
+        (void)hipGetLastError();
+        rec = sizeof(Affine);
+        e = hipMalloc(&pb.d, (size_t)W * n * rec);
+    }
     if (e != hipSuccess && cw) {  // no room for the table: keep the points only
         (void)hipGetLastError();
         cw = 0;
@@ -1350,16 +1361,20 @@ static int pin_on_device(Ctx* c, const void* key, const uint64_t* h_points, cons
         e = hipMalloc(&pb.d, n * sizeof(Affine));
     }
     if (e != hipSuccess) {
-        set_error("bases_pin: hipMalloc(%zu) failed: %s", (size_t)W * n * sizeof(Affine), hipGetErrorString(e));
+        set_error("bases_pin: hipMalloc(%zu) failed: %s", (size_t)W * n * rec, hipGetErrorString(e));
         return H2HIP_ENOMEM;
     }
     int rc = 0;
     if (d_src) {
         if (!cw) H2_CHECK(hipMemcpyAsync(pb.d, (const Affine*)d_src + lo, n * sizeof(Affine), hipMemcpyDeviceToDevice, c->stream));
-    } else {
+    } else {  // (under a native table the points only pass through here: the build copies them out before it writes row 0 over them)
         H2_CHECK(hipMemcpyAsync(pb.d, (const Affine*)h_points + lo, n * sizeof(Affine), hipMemcpyHostToDevice, c->stream));
     }
-    if (cw) rc = msm_table_build(c, d_src ? (const Affine*)d_src + lo : (const Affine*)pb.d, n, cw, (Affine*)pb.d, c->stream);
+    if (cw) {
+        c->table_rec = rec;
+        rc = msm_table_build(c, d_src ? (const Affine*)d_src + lo : (const Affine*)pb.d, n, cw, (Affine*)pb.d, c->stream);
+        c->table_rec = sizeof(Affine);
+    }
     if (!rc && device_key) {  // the fingerprint of a device key stays on the device
         if (hipMalloc(&pb.d_sample, H2_PIN_SAMPLES * sizeof(Affine)) != hipSuccess) {
             (void)hipGetLastError();
@@ -1381,6 +1396,7 @@ static int pin_on_device(Ctx* c, const void* key, const uint64_t* h_points, cons
     }
     pb.c = cw;
     pb.W = cw ? W : 0;
+    pb.rec = cw ? rec : (uint32_t)sizeof(Affine);
     c->pinned[key] = pb;
     return 0;
 }
@@ -1587,7 +1603,7 @@ int h2hip_bases_pinned_info(const void* bases_xy, size_t* n_points, uint32_t* wi
         if (it == x->pinned.end()) continue;
         found = true;
         n += it->second.n;
-        bytes += (size_t)(it->second.c ? it->second.W : 1) * it->second.n * sizeof(Affine);
+        bytes += (size_t)(it->second.c ? it->second.W : 1) * it->second.n * it->second.rec;
         if (it->second.c) c = it->second.c, W = it->second.W;
     }
     if (!found) {
@@ -2269,6 +2285,16 @@ int h2hip_debug_set_msm_stream(uint32_t chunks, uint32_t ratio_permille, size_t 
 size_t h2hip_debug_msm_stream_ladder(size_t n, uint32_t chunks, uint32_t ratio_permille, int with_bases, size_t* sizes, size_t cap) {
     if (!sizes && cap) return 0;
     return msm_debug_ladder(n, chunks, ratio_permille / 1000.0, with_bases != 0, sizes, cap);
+}
+
+// record form of the window tables pinned from now on: 0 = the engine's choice, 64 = E-form, 80 / 128 = native records at that stride
+int h2hip_debug_set_table_records(uint32_t bytes) {
+    if (bytes != 0 && bytes != 64 && bytes != 80 && bytes != 128) {
+        set_error("debug_set_table_records: 0, 64, 80 or 128 expected");
+        return H2HIP_EINVAL;
+    }
+    g_table_records = bytes;
+    return 0;
 }
 
 // tuning hook: buckets above (entries of the MSM) / d go to the chunked path (default 32768; 0 restores it)

@@ -9,7 +9,10 @@
 // Bound bookkeeping (units of p; a Montgomery product of magnitudes a, b lies in
 // (-ab/169, ab/169 + 1)): mixed add with a freshly loaded point (|32 x| < 32):
 //   U2, S2 in (-0.25, 1.25); |P|, |R| < 5.8; PP, RR < 1.4; |PPP|, |Q| < 1.1; |X3| < 4.5; |Y3| < 2.3.
-// Limb bookkeeping: products always see one operand with |l| < 2^29 and the other < 2^30.
+// Mixed add with a native table record (x in [0, 1), |y| < 1: tighter everywhere): U2, S2 in (-0.01, 1.01); |P|, |R| < 5.6; the rest as above.
+// A bucket's first record becomes the accumulator as it is: x, +-y (normalised), one, one, all below 1.
+// Limb bookkeeping: products always see one operand with |l| < 2^29 and the other < 2^30 (the record's limbs are in [0, 2^29), its
+// negated y in (-2^29, 0]; as the accumulator's y it is normalised first, so R = S2 - Y1 keeps |l| < 2^29 for the square).
 #pragma once
 #include "ec.h"
 #include "fieldu.h"
@@ -36,12 +39,10 @@ H2_HD bool xyzzu_is_identity(const XYZZu& p) { return fu_all_zero(p.zz); }
 // The three functions of the bucket-accumulation inner loop take the field flavour as a template parameter: the
 // accumulate kernel instantiates them with FqUA (explicit-mad multiplier), everything else with QU.
 
-// 2 * (px, py) for a non-identity affine point in I-form (mdbl-2008-s-1)
+// 2 * (x, y) for a non-identity affine point in I-form with normalised coordinates, |x|, |y| < 1.2 p (mdbl-2008-s-1)
 template <class QU = FqU>
-H2_HD XYZZu xyzzu_double_affine(const Fu& px, const Fu& py) {
+H2_HD XYZZu xyzzu_double_affine_reduced(const Fu& x, const Fu& y) {
     XYZZu o;
-    const Fu one = fu_one_i<QU>();
-    Fu x = fu_mul<QU>(px, one), y = fu_mul<QU>(py, one);  // 32x -> (-0.2 p, 1.2 p), same residue
     Fu u = fu_norm(fu_dbl(y));
     Fu v = fu_sqr<QU>(u);
     Fu w = fu_mul<QU>(u, v);
@@ -53,6 +54,13 @@ H2_HD XYZZu xyzzu_double_affine(const Fu& px, const Fu& py) {
     o.zz = v;
     o.zzz = w;
     return o;
+}
+
+// the same for fu_from_ext output (32x, 32y, |.| < 32 p)
+template <class QU = FqU>
+H2_HD XYZZu xyzzu_double_affine(const Fu& px, const Fu& py) {
+    const Fu one = fu_one_i<QU>();
+    return xyzzu_double_affine_reduced<QU>(fu_mul<QU>(px, one), fu_mul<QU>(py, one));  // 32x -> (-0.2 p, 1.2 p), same residue
 }
 
 // dbl-2008-s-1
@@ -73,20 +81,12 @@ H2_HD XYZZu xyzzu_double(const XYZZu& p) {
     return o;
 }
 
-// acc += (px, py): madd-2008-s.  (px, py) is a non-identity affine point in I-form with limbs of
-// magnitude < 2^29 (fu_from_ext output, possibly negated).  All exceptional cases of the group
-// law are exact: the cheap residue filter on P sends possible hits to an exact reduction.
-template <class QU = FqU>
-H2_HD void xyzzu_add_mixed(XYZZu& acc, const Fu& px, const Fu& py) {
-    if (xyzzu_is_identity(acc)) {
-        // first point of a bucket: bring 32x, 32y (|.| < 32 p) inside the accumulator bounds
-        const Fu one = fu_one_i<QU>();
-        acc.x = fu_mul<QU>(px, one);
-        acc.y = fu_mul<QU>(py, one);
-        acc.zz = one;
-        acc.zzz = one;
-        return;
-    }
+// acc += (px, py) for an accumulator that is NOT the identity: madd-2008-s.  (px, py) is a non-identity affine point in I-form with
+// limbs of magnitude < 2^29: fu_from_ext output, possibly negated (REDUCED = false: |32 x| < 32 p), or the coordinates of a native
+// table record, y possibly negated (REDUCED = true: |x|, |y| < p).  All exceptional cases of the group law are exact: the cheap
+// residue filter on P sends possible hits to an exact reduction.  Returns false when the sum is the identity (acc is then marked so).
+template <class QU, bool REDUCED>
+H2_HD bool xyzzu_add_mixed_nonid(XYZZu& acc, const Fu& px, const Fu& py) {
     Fu u2 = fu_mul<QU>(px, acc.zz);
     Fu s2 = fu_mul<QU>(py, acc.zzz);
     Fu p_ = fu_sub(u2, acc.x);
@@ -94,11 +94,12 @@ H2_HD void xyzzu_add_mixed(XYZZu& acc, const Fu& px, const Fu& py) {
     if (fu_maybe_zero_mod_p<QU>(p_)) {
         if (fu_is_zero_mod_p<QU>(p_)) {
             if (fu_is_zero_mod_p<QU>(r)) {
-                acc = xyzzu_double_affine<QU>(px, py);
-            } else {
-                acc = xyzzu_identity();
+                if constexpr (REDUCED) acc = xyzzu_double_affine_reduced<QU>(px, fu_norm(py));
+                else acc = xyzzu_double_affine<QU>(px, py);
+                return true;
             }
-            return;
+            acc = xyzzu_identity();
+            return false;
         }
     }
     Fu pp = fu_sqr<QU>(p_);
@@ -111,6 +112,22 @@ H2_HD void xyzzu_add_mixed(XYZZu& acc, const Fu& px, const Fu& py) {
     acc.y = y3;
     acc.zz = fu_mul<QU>(acc.zz, pp);
     acc.zzz = fu_mul<QU>(acc.zzz, ppp);
+    return true;
+}
+
+// acc += (px, py), fu_from_ext output (possibly negated), any accumulator
+template <class QU = FqU>
+H2_HD void xyzzu_add_mixed(XYZZu& acc, const Fu& px, const Fu& py) {
+    if (xyzzu_is_identity(acc)) {
+        // first point of a bucket: bring 32x, 32y (|.| < 32 p) inside the accumulator bounds
+        const Fu one = fu_one_i<QU>();
+        acc.x = fu_mul<QU>(px, one);
+        acc.y = fu_mul<QU>(py, one);
+        acc.zz = one;
+        acc.zzz = one;
+        return;
+    }
+    xyzzu_add_mixed_nonid<QU, false>(acc, px, py);
 }
 
 // a += b: add-2008-s with exceptional cases
@@ -157,6 +174,66 @@ H2_HD void xyzzu_add_affine(XYZZu& acc, const Affine& p, bool negate) {
     Fu py = fu_from_ext(p.y);
     if (negate) py = fu_neg(py);
     xyzzu_add_mixed<QU>(acc, px, py);
+}
+
+// ---- native records of the fixed-base window table ----------------------------------------------------------------------------
+// The table is the engine's own data, built once at pin time, so its records are kept in the form xyzzu_add_mixed_nonid multiplies:
+// both coordinates I-form and canonical (the integer in [0, p)) as 9 limbs of 29 bits, limbs 0..7 in [0, 2^29), top limb in [0, 2^22).
+// `valid` is 1 for a point of the curve; the identity is the all-zero record.  80 bytes: five 16-byte pieces for the accumulate kernel's
+// LDS-DMA fetch; in the table the records lie a 128-byte line apart (engine.h H2_TABLE_REC_NATIVE).  Against an E-form Affine the kernel saves fu_from_ext on both coordinates, and the first point of a bucket needs no
+// product: x, +-y, one, one are inside the accumulator's bounds as they are.
+struct AffineU {
+    Fu x, y;
+    uint32_t valid, pad;
+};
+static_assert(sizeof(AffineU) == 80, "five 16-byte pieces");
+
+// E-form Fe (canonical) -> the canonical I-form limbs of a native record, and back
+H2_HD Fu fu_native_from_ext(const Fe& e) { return fu_slice(fu_canon<QU>(fu_mul<QU>(fu_from_ext(e), fu_one_i<QU>()))); }
+H2_HD Fe fu_native_to_ext(const Fu& a) { return fu_mul_canon<QU>(a, fu_one_e<QU>()); }
+
+H2_HD AffineU affineu_from_ext(const Affine& p) {
+    AffineU o;
+    const bool id = affine_is_identity(p);
+    o.x = id ? fu_zero() : fu_native_from_ext(p.x);
+    o.y = id ? fu_zero() : fu_native_from_ext(p.y);
+    o.valid = id ? 0u : 1u;
+    o.pad = 0;
+    return o;
+}
+
+H2_HD Affine affineu_to_ext(const AffineU& p) {
+    Affine o;
+    if (!p.valid) {
+        o.x = fe_zero<Q>();
+        o.y = fe_zero<Q>();
+        return o;
+    }
+    o.x = fu_native_to_ext(p.x);
+    o.y = fu_native_to_ext(p.y);
+    return o;
+}
+
+// acc += +-p for a native record.  acc_id (0 / 1) says whether acc is the identity: the caller sets it once (1 for a fresh accumulator)
+// and this function keeps it, so the loop tests one word against the record's marker instead of or-ing the nine limbs of zz and the
+// sixteen words of the point on every entry.  The sign is applied without a branch: (y ^ m) - m with m = 0 or -1.
+template <class QU = FqU>
+H2_HD void xyzzu_add_native(XYZZu& acc, uint32_t& acc_id, const AffineU& p, bool negate) {
+    const int32_t m = -(int32_t)negate, one_if = (int32_t)negate;
+    Fu py;
+#pragma unroll
+    for (int i = 0; i < 9; i++) py.l[i] = (p.y.l[i] ^ m) + one_if;  // |l| < 2^29, |value| < p
+    if (p.valid <= acc_id) {  // rare: an identity record (nothing to add), or an identity accumulator (the first point of a bucket, or after a cancellation)
+        if (p.valid) {
+            acc.x = p.x;
+            acc.y = fu_norm(py);  // limbs 0..7 back in [0, 2^29): the accumulator's invariant
+            acc.zz = fu_one_i<QU>();
+            acc.zzz = acc.zz;
+            acc_id = 0;
+        }
+        return;
+    }
+    acc_id = xyzzu_add_mixed_nonid<QU, true>(acc, p.x, py) ? 0u : 1u;
 }
 
 // I-form accumulator -> the E-form XYZZ of ec.h with canonical coordinates

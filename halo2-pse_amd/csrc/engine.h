@@ -78,10 +78,20 @@ struct TwiddleTable {
 
 // Fixed-base window table of a pinned base array (msm.hip): row j (of `stride` points) = 2^(c j) * P, j < W
 struct MsmTable {
-    const Affine* table = nullptr;
+    const void* table = nullptr;
     size_t stride = 0;
     uint32_t c = 0, W = 0;
+    uint32_t rec = 64;  // bytes from one record to the next: 64 = E-form Affine, otherwise native records (ecu.h AffineU) at that stride (128; 80 for A/B)
 };
+
+// Record form of the window tables.  Native records (80 bytes of limbs, one per 128-byte line) spare the accumulation the slicing of
+// both coordinates, the branch around the negation and the first point's two products.  Packed at 80 bytes they straddle the 64-byte
+// sectors and the gathers cost more than the instructions save ("Native table records"), so the stride is a line.  Below
+// 2^13 points the MSM is all reduction tail (msm_table_window), a table twice the size buys nothing, and it stays E-form.
+// `forced`: h2hip_debug_set_table_records (0 = no wish).
+#define H2_TABLE_REC_NATIVE 128u
+#define H2_TABLE_NATIVE_MIN_N ((size_t)1 << 13)
+static inline uint32_t msm_table_rec(size_t n, uint32_t forced) { return forced ? forced : n >= H2_TABLE_NATIVE_MIN_N ? H2_TABLE_REC_NATIVE : 64u; }
 
 #define H2_GATHER_OWN ((size_t)64 << 10)  // bytes of Ctx::gather a device's own set sums may take; the gathered ones follow
 #define H2_PIN_SAMPLES 16
@@ -89,9 +99,10 @@ struct MsmTable {
 static inline __host__ __device__ size_t pin_sample_index(size_t total, uint32_t k) { return k == 0 ? 0 : (total - 1) >> (H2_PIN_SAMPLES - 1 - k); }
 // One entry of the pinned-bases cache, keyed by the caller's pointer (host or device).
 struct PinnedBases {
-    void* d = nullptr;         // device copy: W x n points with the window table, or n points without one
+    void* d = nullptr;         // device copy: W x n records with the window table, or n points without one
     size_t n = 0;              // points per row
     uint32_t c = 0, W = 0;     // window width of the table; 0: no table (rows = 1)
+    uint32_t rec = 64;         // bytes per record of the table (MsmTable::rec); without a table the points are E-form Affine
     bool device_key = false;   // the key is a device pointer (h2hip_bases_pin_device)
     // fingerprint of the caller's array at pin time: H2_PIN_SAMPLES points (pin_sample_index: the first one and a geometric
     // ladder up to the last, so that every prefix length still sees several), compared byte for byte on every lookup -- a
@@ -175,6 +186,7 @@ struct Ctx {
         uint32_t* flag = nullptr;
         size_t n = 0, total = 0;
     } pin_chk;
+    uint32_t table_rec = 64;       // record stride of the table msm_table_build is to write (MsmTable::rec); set by pin_on_device around its call
     // Small host tables the kernels read (pointer lists, constants) go through this pinned ring, so that the
     // asynchronous copy never reads a caller's stack or a std::vector that is gone by the time the DMA runs.
     HostBuf stage;

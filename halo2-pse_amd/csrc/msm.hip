@@ -44,6 +44,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "ecq.h"
@@ -534,28 +535,32 @@ __global__ void __launch_bounds__(1024) msm_bucket_scatter_kernel(const uint32_t
 }
 
 // the heavy role of msm_accum_kernel (defined below, after the tree sums it uses)
-__device__ __noinline__ void msm_heavy_role(const Affine* __restrict__ bases, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ heavy_counts,
-                                            HeavyBucket* __restrict__ heavy_buckets, const HeavyChunk* __restrict__ heavy_chunks,
-                                            XYZZu* __restrict__ chunk_sums, uint32_t split_log, uint32_t cont, XYZZu* __restrict__ parts, uint32_t hgrid,
-                                            XYZZu* sh);
+template <bool NATIVE>
+__device__ __noinline__ void msm_heavy_role(const char* __restrict__ bases, uint32_t rec, const uint32_t* __restrict__ vals,
+                                            const uint32_t* __restrict__ heavy_counts, HeavyBucket* __restrict__ heavy_buckets,
+                                            const HeavyChunk* __restrict__ heavy_chunks, XYZZu* __restrict__ chunk_sums, uint32_t split_log, uint32_t cont,
+                                            XYZZu* __restrict__ parts, uint32_t hgrid, XYZZu* sh);
 
 // B: 2^split_log lanes per bucket (one when split_log = 0): lane (bucket, sub) adds the bucket's entries sub, sub + S,
 // sub + 2S, ... into parts[bucket * S + sub].  A run with few buckets (a lone MSM of <= 2^17 pairs over a window table
 // has 2^16) would otherwise be one wave per SIMD walking ~30 dependent additions per lane.
-// `bases` is the caller's point array (plain form) or the window table (fixed-base form).
+// `bases` is the caller's point array (plain form) or the window table (fixed-base form), records of `rec` bytes.  NATIVE: the records
+// are the table's native form (ecu.h AffineU, 80 bytes used of `rec`); otherwise E-form Affine (rec = 64).
 #ifdef H2_ACCUM_TIMELINE  // measurement builds only (tools/accum_timeline.py): entry / exit time, first lane's bucket size and HW_ID of every accumulate wave
 __device__ unsigned long long g_accum_tl[6 * 16384];
 #endif
-__global__ void __launch_bounds__(256, 4) msm_accum_kernel(const Affine* __restrict__ bases, const uint32_t* __restrict__ vals,
+template <bool NATIVE>
+__global__ void __launch_bounds__(256, 4) msm_accum_kernel(const char* __restrict__ bases, uint32_t rec, const uint32_t* __restrict__ vals,
                                                         const uint32_t* __restrict__ start, const uint32_t* __restrict__ counts,
                                                         const uint32_t* __restrict__ perm, uint32_t n_buckets, uint32_t split_log, uint32_t heavy_t,
                                                         uint32_t cont, XYZZu* __restrict__ parts, uint32_t hgrid, const uint32_t* __restrict__ heavy_counts,
                                                         HeavyBucket* __restrict__ heavy_buckets, const HeavyChunk* __restrict__ heavy_chunks,
                                                         XYZZu* __restrict__ chunk_sums) {
-    // one LDS block for both roles: the heavy role's 256 sums (27 KB) or the accumulate role's point buffer (16 KB); four workgroups per CU
+    // one LDS block for both roles: the heavy role's 256 sums (36 KB) or the accumulate role's point buffer (16 KB, native records 20 KB); four workgroups per CU
     __shared__ __align__(16) unsigned char lds_raw[256 * sizeof(XYZZu)];
     if (blockIdx.x < hgrid) {
-        msm_heavy_role(bases, vals, heavy_counts, heavy_buckets, heavy_chunks, chunk_sums, split_log, cont, parts, hgrid, reinterpret_cast<XYZZu*>(lds_raw));
+        msm_heavy_role<NATIVE>(bases, rec, vals, heavy_counts, heavy_buckets, heavy_chunks, chunk_sums, split_log, cont, parts, hgrid,
+                               reinterpret_cast<XYZZu*>(lds_raw));
         return;
     }
     uint32_t t = (blockIdx.x - hgrid) * blockDim.x + threadIdx.x;
@@ -574,47 +579,72 @@ __global__ void __launch_bounds__(256, 4) msm_accum_kernel(const Affine* __restr
         store = store && sub != 0;  // the bucket's first part belongs to the heavy role (which runs beside this lane); the others are identities
     } else if (s + sub < e) {
         // The point of the next entry is fetched before the current addition starts: with a window table the points
-        // are gathers from hundreds of MB of HBM, and one addition (~2.3 k instructions) hides the whole miss.  The fetch
+        // are gathers from hundreds of MB of HBM, and one addition (~2 k instructions) hides the whole miss.  The fetch
         // is an LDS-DMA (global_load_lds_dwordx4, per-lane source address, lane-linear destination): holding the next
         // point in registers instead costs 16 of them and with that the fourth wave per SIMD.
-        typedef uint4 (*PBuf)[4][64];  // [wave][16-byte chunk of the point][lane]
+        constexpr int NCH = NATIVE ? 5 : 4;  // 16-byte pieces of a record
+        typedef uint4 (*PBuf)[NCH][64];      // [wave][piece][lane]
         const PBuf pbuf = reinterpret_cast<PBuf>(lds_raw);
+        static_assert(4 * NCH * 64 * sizeof(uint4) <= sizeof(lds_raw), "the point buffer fits the block's LDS");
         const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-        auto issue = [&](uint32_t v) {
-            const char* g = reinterpret_cast<const char*>(&bases[v & 0x7fffffffu]);
+        auto issue = [&](uint32_t v) __attribute__((always_inline)) {
+            const char* g = bases + (size_t)(v & 0x7fffffffu) * rec;
 #pragma unroll
-            for (int ch = 0; ch < 4; ch++)
+            for (int ch = 0; ch < NCH; ch++)
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + 16 * ch),
                                                  (__attribute__((address_space(3))) void*)&pbuf[wave][ch][0], 16, 0, 0);
         };
-        auto take = [&]() {
+        uint32_t w[4 * NCH];  // the record's words
+        auto take = [&]() __attribute__((always_inline)) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            Affine p;
 #pragma unroll
-            for (int ch = 0; ch < 4; ch++) {
+            for (int ch = 0; ch < NCH; ch++) {
                 const uint4 q = pbuf[wave][ch][lane];
-                Fe& f = ch < 2 ? p.x : p.y;
-                f.l[4 * (ch & 1)] = q.x;
-                f.l[4 * (ch & 1) + 1] = q.y;
-                f.l[4 * (ch & 1) + 2] = q.z;
-                f.l[4 * (ch & 1) + 3] = q.w;
+                w[4 * ch] = q.x;
+                w[4 * ch + 1] = q.y;
+                w[4 * ch + 2] = q.z;
+                w[4 * ch + 3] = q.w;
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the buffer is free for the next fetch
-            return p;
+        };
+        uint32_t acc_id = 1;  // native records: 1 while acc is the identity (xyzzu_add_native)
+        auto add = [&](uint32_t v) __attribute__((always_inline)) {  // throughput-bound: explicit-mad multiplier
+            if constexpr (NATIVE) {
+                AffineU p;
+#pragma unroll
+                for (int i = 0; i < 9; i++) {
+                    p.x.l[i] = (int32_t)w[i];
+                    p.y.l[i] = (int32_t)w[9 + i];
+                }
+                p.valid = w[18];
+                p.pad = 0;
+                xyzzu_add_native<FqUA>(acc, acc_id, p, (v >> 31) != 0);
+            } else {
+                Affine p;
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    p.x.l[i] = w[i];
+                    p.y.l[i] = w[8 + i];
+                }
+                xyzzu_add_affine<FqUA>(acc, p, (v >> 31) != 0);
+            }
         };
         uint32_t v = vals[s + sub];
         issue(v);
-        if (cont) acc = *mine;
+        if (cont) {
+            acc = *mine;
+            acc_id = xyzzu_is_identity(acc) ? 1u : 0u;
+        }
         store = true;
         for (uint32_t i = s + sub + S; i < e; i += S) {
             const uint32_t vn = vals[i];
-            const Affine p = take();
+            take();
             issue(vn);
-            xyzzu_add_affine<FqUA>(acc, p, (v >> 31) != 0);  // throughput-bound: explicit-mad multiplier
+            add(v);
             v = vn;
         }
-        const Affine p = take();
-        xyzzu_add_affine<FqUA>(acc, p, (v >> 31) != 0);
+        take();
+        add(v);
     }
     if (store) *mine = acc;
 #ifdef H2_ACCUM_TIMELINE
@@ -698,27 +728,35 @@ __device__ __forceinline__ XYZZu block_tree_sum_q(const XYZZu& v, XYZZu* sh) {
 // addition; the chunk's 256 lane sums meet in a tree of quad additions.  The workgroup that finishes a bucket's LAST chunk (arrival
 // counter, as in msm_final_quad_kernel) sums the bucket's chunk sums and puts the total into the bucket's first part -- stored in a
 // fresh run, added in a continued one; the accumulate lanes leave that part alone, so the two roles never touch the same word.
-__device__ __noinline__ void msm_heavy_role(const Affine* __restrict__ bases, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ heavy_counts,
-                                            HeavyBucket* __restrict__ heavy_buckets, const HeavyChunk* __restrict__ heavy_chunks,
-                                            XYZZu* __restrict__ chunk_sums, uint32_t split_log, uint32_t cont, XYZZu* __restrict__ parts, uint32_t hgrid,
-                                            XYZZu* sh) {
+template <bool NATIVE>
+__device__ __noinline__ void msm_heavy_role(const char* __restrict__ bases, uint32_t rec, const uint32_t* __restrict__ vals,
+                                            const uint32_t* __restrict__ heavy_counts, HeavyBucket* __restrict__ heavy_buckets,
+                                            const HeavyChunk* __restrict__ heavy_chunks, XYZZu* __restrict__ chunk_sums, uint32_t split_log, uint32_t cont,
+                                            XYZZu* __restrict__ parts, uint32_t hgrid, XYZZu* sh) {
+    typedef typename std::conditional<NATIVE, AffineU, Affine>::type Rec;
     __shared__ uint32_t last_flag;
     const uint32_t total = heavy_counts[1];
     for (uint32_t ci = blockIdx.x; ci < total; ci += hgrid) {
         const HeavyChunk ch = heavy_chunks[ci];
         XYZZu acc = xyzzu_identity();
+        uint32_t acc_id = 1;
+        auto fetch = [&](uint32_t v) { return *reinterpret_cast<const Rec*>(bases + (size_t)(v & 0x7fffffffu) * rec); };
+        auto add = [&](const Rec& p, uint32_t v) {
+            if constexpr (NATIVE) xyzzu_add_native<FqU>(acc, acc_id, p, (v >> 31) != 0);
+            else xyzzu_add_affine<FqU>(acc, p, (v >> 31) != 0);
+        };
         uint32_t i = ch.begin + threadIdx.x;
         if (i < ch.end) {
             uint32_t v = vals[i];
-            Affine p = bases[v & 0x7fffffffu];
+            Rec p = fetch(v);
             for (i += blockDim.x; i < ch.end; i += blockDim.x) {
                 const uint32_t vn = vals[i];
-                const Affine pn = bases[vn & 0x7fffffffu];
-                xyzzu_add_affine<FqU>(acc, p, (v >> 31) != 0);
+                const Rec pn = fetch(vn);
+                add(p, v);
                 v = vn;
                 p = pn;
             }
-            xyzzu_add_affine<FqU>(acc, p, (v >> 31) != 0);
+            add(p, v);
         }
         const XYZZu r = block_tree_sum_q(acc, sh);
         if (threadIdx.x == 0) {
@@ -1098,6 +1136,12 @@ __global__ void __launch_bounds__(256) msm_table_step_kernel(const Affine* __res
     out[i] = xyzzu_to_ext(q);
 }
 
+// one finished row of the table, E-form Affine -> native records `rec` bytes apart (the bytes past a record's 80 are never read)
+__global__ void __launch_bounds__(256) msm_table_native_kernel(const Affine* __restrict__ row, char* __restrict__ out, uint32_t rec, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) *reinterpret_cast<AffineU*>(out + i * rec) = affineu_from_ext(row[i]);
+}
+
 static uint32_t g_window_override = 0;
 static size_t g_heavy_div = 32768;
 static size_t g_bin_entries = 8192;
@@ -1204,6 +1248,9 @@ static XYZZ combine_windows(const XYZZ* ws, const MsmPlan& p) {
     }
     return h64::to_xyzz(acc);
 }
+
+// bytes per record of the array the accumulation reads: the table's, or an E-form Affine
+static inline uint32_t rec_bytes(const MsmTable* tab) { return tab ? tab->rec : (uint32_t)sizeof(Affine); }
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
@@ -1416,8 +1463,9 @@ static int msm_stage_a(Ctx* c, const MsmLayout& L, char* base, const Fe* const* 
 // stage B (VALU-bound): bucket accumulation, plus the chunked path for over-full buckets.  `base` holds the sorted entries of
 // this run, `bbase` the parts / buckets they are added to (the same arena unless the run is one chunk of a streamed MSM);
 // cont: the parts already hold sums (msm_accum_kernel); combine: fold the parts of every bucket afterwards.
-static int msm_stage_b(Ctx* c, const MsmLayout& L, char* base, const Affine* d_points, hipStream_t s, char* bbase = nullptr, bool cont = false,
-                       bool combine = true) {
+// d_points: records of `rec` bytes -- E-form Affine (64), or the native records of a window table (MsmTable::rec)
+static int msm_stage_b(Ctx* c, const MsmLayout& L, char* base, const void* d_points, uint32_t rec, hipStream_t s, char* bbase = nullptr,
+                       bool cont = false, bool combine = true) {
     const MsmPlan& p = L.p;
     if (!bbase) bbase = base;
     uint32_t* vals = (uint32_t*)(base + L.o_vals);
@@ -1435,12 +1483,14 @@ static int msm_stage_b(Ctx* c, const MsmLayout& L, char* base, const Affine* d_p
     // the first hgrid workgroups take the over-full buckets' chunks (none on uniform scalars: they leave at once), the rest one lane per part
     const uint32_t hgrid = (uint32_t)(L.max_chunks < (size_t)c->sm_count ? L.max_chunks : (size_t)c->sm_count);
     const dim3 agrid(hgrid + (lanes + 255) / 256);
+    const auto kernel = rec == sizeof(Affine) ? msm_accum_kernel<false> : msm_accum_kernel<true>;
+    const char* recs = (const char*)d_points;
     if (c->timer_kernel("msm_accum", &ke0, &ke1) >= 0)  // the dispatch's own begin / end timestamps: no marker packets around it
-        hipExtLaunchKernelGGL(msm_accum_kernel, agrid, dim3(256), 0, s, ke0, ke1, 0, d_points, (const uint32_t*)vals, (const uint32_t*)start,
+        hipExtLaunchKernelGGL(kernel, agrid, dim3(256), 0, s, ke0, ke1, 0, recs, rec, (const uint32_t*)vals, (const uint32_t*)start,
                               (const uint32_t*)counts, (const uint32_t*)perm, L.K, L.split_log, p.heavy_t, cont_u, parts, hgrid, (const uint32_t*)hcnt, hb,
                               (const HeavyChunk*)hc, hs);
     else
-        hipLaunchKernelGGL(msm_accum_kernel, agrid, dim3(256), 0, s, d_points, (const uint32_t*)vals, (const uint32_t*)start, (const uint32_t*)counts,
+        hipLaunchKernelGGL(kernel, agrid, dim3(256), 0, s, recs, rec, (const uint32_t*)vals, (const uint32_t*)start, (const uint32_t*)counts,
                            (const uint32_t*)perm, L.K, L.split_log, p.heavy_t, cont_u, parts, hgrid, (const uint32_t*)hcnt, hb, (const HeavyChunk*)hc, hs);
     H2_CHECK(hipGetLastError());
     c->timer_end(t2, s);
@@ -1669,7 +1719,7 @@ static int msm_batch_chunk(Ctx* c, const Fe* const* d_scalars, bool scalars_on_h
         const Fe* sc;
         if ((rc = scalars_for(0, s, &sc))) return rc;
         if ((rc = msm_stage_a(c, L, base, &sc, tab, s))) return rc;
-        if ((rc = msm_stage_b(c, L, base, d_points, s))) return rc;
+        if ((rc = msm_stage_b(c, L, base, d_points, rec_bytes(tab), s))) return rc;
         if ((rc = msm_stage_c(c, L, base, h_ws, s, h_pl))) return rc;
     } else {
         // Three internal streams.  A full-size accumulate holds every wave slot for ~0.65 ms at a time, so the other
@@ -1691,7 +1741,7 @@ static int msm_batch_chunk(Ctx* c, const Fe* const* d_scalars, bool scalars_on_h
             if ((rc = msm_stage_a(c, L, base, &sc, tab, a1))) return rc;
             H2_CHECK(hipEventRecord(ev[1 + 3 * j], a1));
             H2_CHECK(hipStreamWaitEvent(sb, ev[1 + 3 * j], 0));
-            if ((rc = msm_stage_b(c, L, base, d_points, sb))) return rc;
+            if ((rc = msm_stage_b(c, L, base, d_points, rec_bytes(tab), sb))) return rc;
             H2_CHECK(hipEventRecord(ev[2 + 3 * j], sb));
             H2_CHECK(hipStreamWaitEvent(a2, ev[2 + 3 * j], 0));
             if ((rc = msm_stage_c(c, L, base, h_ws + j * spm, a2))) return rc;
@@ -1737,7 +1787,7 @@ static int msm_fused_chunk(Ctx* c, const Fe* const* d_scalars, bool scalars_on_h
     char* base = (char*)c->msm_slot[0].p;
     int t_all = c->timer_begin("msm_total", s);
     if ((rc = msm_stage_a(c, L, base, list.data(), tab, s))) return rc;
-    if ((rc = msm_stage_b(c, L, base, d_points, s))) return rc;
+    if ((rc = msm_stage_b(c, L, base, d_points, rec_bytes(tab), s))) return rc;
     if ((rc = msm_stage_c(c, L, base, h_ws, s, h_pl))) return rc;
     c->timer_end(t_all, s);
     H2_CHECK(hipStreamSynchronize(s));
@@ -1865,7 +1915,8 @@ static int msm_stream_host(Ctx* c, const Fe* h_scalars, const Affine* h_bases, c
     H2_CHECK(hipEventRecord(ev[0], s));
     H2_CHECK(hipStreamWaitEvent(cs, ev[0], 0));
     char* base = (char*)c->msm_slot[0].p;
-    const Affine* points0 = tab ? tab->table : d_points;
+    const char* points0 = tab ? (const char*)tab->table : (const char*)d_points;
+    const uint32_t rec = rec_bytes(tab);
     size_t o = 0;
     std::vector<CopyJob> jobs;
     for (size_t k = 0; k < K; k++) {
@@ -1884,7 +1935,7 @@ static int msm_stream_host(Ctx* c, const Fe* h_scalars, const Affine* h_bases, c
         H2_CHECK(hipStreamWaitEvent(s, ev[1 + k], 0));
         const Fe* sc = d_sc + o;
         if ((rc = msm_stage_a(c, Lk[k], base, &sc, tab, s))) return rc;
-        if ((rc = msm_stage_b(c, Lk[k], base, points0 + o, s, base, k > 0, k + 1 == K))) return rc;
+        if ((rc = msm_stage_b(c, Lk[k], base, points0 + o * rec, rec, s, base, k > 0, k + 1 == K))) return rc;
         o += sz[k];
     }
     if ((rc = msm_stage_c(c, Lk[K - 1], base, h_ws, s, h_pl))) return rc;
@@ -1953,7 +2004,7 @@ static int msm_fused_groups_host(Ctx* c, const Fe* const* h_scalars, const Affin
         H2_CHECK(hipStreamWaitEvent(sa, ev[1 + 3 * g], 0));
         if (g >= 2) H2_CHECK(hipStreamWaitEvent(sa, ev[3 + 3 * (g - 2)], 0));  // the slot is free once group g - 2 is reduced
         if ((rc = msm_stage_a(c, Lg[g], base, list.data() + j0, tab, sa))) return rc;
-        if ((rc = msm_stage_b(c, Lg[g], base, d_points, sa))) return rc;
+        if ((rc = msm_stage_b(c, Lg[g], base, d_points, rec_bytes(tab), sa))) return rc;
         H2_CHECK(hipEventRecord(ev[2 + 3 * g], sa));
         H2_CHECK(hipStreamWaitEvent(sc_, ev[2 + 3 * g], 0));
         if ((rc = msm_stage_c(c, Lg[g], base, h_ws + set0, sc_))) return rc;
@@ -2005,9 +2056,9 @@ int msm_batch_device(Ctx* c, const Fe* const* d_scalars, bool scalars_on_host, c
         const Affine* points = d_bases ? d_bases + o : nullptr;
         if (tab) {
             sub = *tab;
-            sub.table = tab->table + o;  // row j of the sub-table starts at table + j * stride + o
+            sub.table = (const char*)tab->table + o * tab->rec;  // row j of the sub-table starts at record j * stride + o
             tsub = &sub;
-            points = sub.table;
+            points = (const Affine*)sub.table;  // (opaque when the records are native: msm_stage_b takes the record size from the table)
         }
         const bool stream = scalars_on_host && g_stream_chunks > 1 && copier_ready(c, false);
         if (stream && count == 1 && m >= g_stream_min_n) {  // a lone host-resident MSM: chunks stream in under the work
@@ -2063,9 +2114,34 @@ int msm_device(Ctx* c, const Fe* d_scalars, const Affine* d_bases, size_t n, XYZ
 // first bit of window j (MsmPlan).
 // Row 0 is a copy of the points.  Rows are built one from the other (c doublings in XYZZ, then one batched
 // normalisation back to affine), in slices of 2^22 points so the XYZZ scratch stays at 512 MB.
+// Ctx::table_rec = 64: the rows are E-form Affine.  Otherwise d_table takes native records (ecu.h AffineU) that many bytes apart: every
+// row is still built in E-form from the one before, in two scratch rows of this call's own, and converted as it is finished.
 int msm_table_build(Ctx* c, const Affine* d_points, size_t n, uint32_t cw, Affine* d_table, hipStream_t s) {
     const uint32_t W = (255 + cw - 1) / cw, q = 255 - W * (cw - 1);
-    if (d_table != d_points) H2_CHECK(hipMemcpyAsync(d_table, d_points, n * sizeof(Affine), hipMemcpyDeviceToDevice, s));  // row 0 = the points
+    const uint32_t rec = c->table_rec;
+    const bool native = rec != sizeof(Affine);
+    Affine* rows = d_table;  // E-form rows: the table itself, or the two scratch rows
+    if (native) {
+        if (hipMalloc((void**)&rows, 2 * n * sizeof(Affine)) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("msm: no room for the scratch rows of the table build");
+            return H2HIP_ENOMEM;
+        }
+    }
+    struct Scratch {  // hipFree waits for the device: the kernels below are done with the rows by then
+        Affine* p;
+        ~Scratch() {
+            if (p) (void)hipFree(p);
+        }
+    } scratch{native ? rows : nullptr};
+    const auto row = [&](uint32_t j) { return native ? rows + (size_t)(j & 1) * n : rows + (size_t)j * n; };
+    const auto convert = [&](uint32_t j) {
+        hipLaunchKernelGGL(msm_table_native_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, (const Affine*)row(j),
+                           (char*)d_table + (size_t)j * n * rec, rec, n);
+        return hipGetLastError();
+    };
+    if (row(0) != d_points) H2_CHECK(hipMemcpyAsync(row(0), d_points, n * sizeof(Affine), hipMemcpyDeviceToDevice, s));  // row 0 = the points
+    if (native) H2_CHECK(convert(0));
     const size_t slice = (size_t)1 << 22;
     const size_t m_max = n < slice ? n : slice;
     int rc = c->ecfft_ws.ensure(m_max * sizeof(XYZZ));
@@ -2076,11 +2152,12 @@ int msm_table_build(Ctx* c, const Affine* d_points, size_t n, uint32_t cw, Affin
     for (uint32_t j = 1; j < W; j++) {
         for (size_t o = 0; o < n; o += slice) {
             const size_t m = n - o < slice ? n - o : slice;
-            hipLaunchKernelGGL(msm_table_step_kernel, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, s, d_table + (size_t)(j - 1) * n + o, tmp,
-                               (uint32_t)m, (j - 1) < q ? cw : cw - 1);  // window j starts width(j - 1) bits above window j - 1
+            hipLaunchKernelGGL(msm_table_step_kernel, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, s, (const Affine*)row(j - 1) + o, tmp, (uint32_t)m,
+                               (j - 1) < q ? cw : cw - 1);  // window j starts width(j - 1) bits above window j - 1
             H2_CHECK(hipGetLastError());
-            if ((rc = ec_normalize_device(tmp, d_table + (size_t)j * n + o, m, s))) return rc;
+            if ((rc = ec_normalize_device(tmp, row(j) + o, m, s))) return rc;
         }
+        if (native) H2_CHECK(convert(j));
     }
     return guard.release();
 }

@@ -101,9 +101,10 @@ int h2hip_msm_bn254(const uint64_t* scalars, const uint64_t* bases_xy, size_t n,
  * whose bases pointer equals `bases_xy` (and n' <= n) skip the upload.  For ParamsKZG::{g, g_lagrange}
  * (poly/kzg/commitment.rs:26-27), which live as long as the params; call unpin before the Vec is dropped
  * or mutated (downsize, :267-275).  With several devices each one keeps its contiguous share.
- * Pinning also builds the fixed-base window table 2^(pos_j) * P_i (pos_j = first bit of window j, W = ceil(255/c) windows; n <= 2^26; W * n * 64
- * bytes of HBM, e.g. 0.8 GB at 2^20, 12 GB at 2^24): all windows of an MSM then share one bucket set, the
- * windows are wider (c = 20 instead of 16 at 2^20) and no Horner pass is needed.
+ * Pinning also builds the fixed-base window table 2^(pos_j) * P_i (pos_j = first bit of window j, W = ceil(255/c) windows; n <= 2^26; from 2^13
+ * points W * n * 128 bytes of HBM -- the multiplier's own limb form, one record per line: 1.7 GB at 2^20, 26 GB at 2^24 -- and W * n * 64 bytes
+ * below that, or where the larger table exceeds HALO2_HIP_TABLE_MAX_GB or does not fit; h2hip_bases_pinned_info reports the bytes in use):
+ * all windows of an MSM then share one bucket set, the windows are wider (c = 20 instead of 16 at 2^20) and no Horner pass is needed.
  * The cache is safe against stale pointers: every lookup compares 16 sampled points of the caller's array (the first
  * point and a geometric ladder of indices up to the last, so that a shorter prefix still sees several) with the ones seen
  * at pin time and falls back to a plain upload (dropping the entry) on a mismatch. */

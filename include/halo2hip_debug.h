@@ -23,6 +23,10 @@ int h2hip_debug_set_msm_max_chunk(size_t m);
 /* push `count` Jacobian partials per engine device through the library's RCCL all-gather (communicators created on
  * demand, also for one device) and fold them on the host: exercises the multi-GPU gather on any box */
 int h2hip_debug_rccl_gather_selftest(const uint64_t* partials_xyz, size_t count, uint64_t* out_xyz);
+/* record form of the window tables built by h2hip_bases_pin* from now on (read at pin time): 64 = E-form points as the reference stores them,
+ * 80 or 128 = the multiplier's own limb form (80 bytes) at that stride; 0 = the engine's choice (128 from 2^13 points, where its memory
+ * rules allow the larger table; 64 otherwise).  h2hip_bases_pinned_info reports the bytes the table really takes. */
+int h2hip_debug_set_table_records(uint32_t bytes);
 /* buckets with more than (entries of the MSM) / d entries take the chunked path (default d = 32768; 0 restores it) */
 int h2hip_debug_set_msm_heavy_div(size_t d);
 /* g_to_lagrange / fft_g1 up to k = 14: bit 0 -- one quad of lanes per butterfly (1, default) or one lane (0); bit 1 set -- normalise to affine
