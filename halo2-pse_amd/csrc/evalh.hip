@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/halo2hip.h"
+#include "../../include/halo2hip_debug.h"
 #include "engine.h"
 #include "evalh_dev.h"
 
@@ -1127,6 +1128,98 @@ static void prog_put(MetaBlob& mb, const h2hip_graph& g, const Program& P, ProgD
     out->result = P.result;
 }
 
+// One launch of the custom gates over `rows` rows of `values`: the kernel generated for this circuit once it is compiled, the
+// interpreter until then (and for programs beyond the generator's limits)
+static int enqueue_gates(Ctx* c, const h2hip_graph& graph, const Program& prog, const SlotPlan& plan, const ProgDev& gd, const ColsDev& cols,
+                         Fe* d_values, Fu* gws, size_t rows, hipStream_t s) {
+    const dim3 block(256);
+    hipFunction_t gen = plan.tier != 0 ? gates_kernel_for(c, graph, prog) : nullptr;
+    if (gen) {
+        Fe* vals = d_values;
+        void* args[] = {(void*)&cols, (void*)&vals};
+        H2_CHECK(hipModuleLaunchKernel(gen, (uint32_t)((rows + 255) / 256), 1, 1, 256, 1, 1, 0, s, args, nullptr));
+        g_rtc_stats.launches++;
+    } else {
+        g_rtc_stats.interpreted++;
+        const dim3 g(plan.lanes / 256);
+        switch (plan.tier) {
+            case 4: hipLaunchKernelGGL(evalh_gates_kernel<4>, g, block, 4 * 9 * 256 * 4, s, gd, cols, d_values, gws, plan.lanes); break;
+            case 8: hipLaunchKernelGGL(evalh_gates_kernel<8>, g, block, 8 * 9 * 256 * 4, s, gd, cols, d_values, gws, plan.lanes); break;
+            case 16: hipLaunchKernelGGL(evalh_gates_kernel<16>, g, block, EVALH_LDS_HOT * 9 * 256 * 4, s, gd, cols, d_values, gws, plan.lanes); break;
+            case 64: hipLaunchKernelGGL(evalh_gates_kernel<64>, g, block, EVALH_LDS_HOT * 9 * 256 * 4, s, gd, cols, d_values, gws, plan.lanes); break;
+            case 256: hipLaunchKernelGGL(evalh_gates_kernel<256>, g, block, EVALH_LDS_HOT * 9 * 256 * 4, s, gd, cols, d_values, gws, plan.lanes); break;
+            default: hipLaunchKernelGGL(evalh_gates_kernel<0>, g, block, 0, s, gd, cols, d_values, gws, plan.lanes);
+        }
+    }
+    H2_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ... and of one lookup argument's constraints
+static int enqueue_lookup(Ctx* c, const h2hip_graph& graph, const Program& prog, const SlotPlan& lp, const ProgDev& lg, const LookupDev& ld,
+                          const ColsDev& cols, Fe* d_values, Fu* gws, size_t rows, hipStream_t s) {
+    const dim3 block(256);
+    if (hipFunction_t lgen = gates_kernel_for(c, graph, prog, true)) {  // generated for this circuit, as the gates kernel is
+        Fe* vals = d_values;
+        void* args[] = {(void*)&cols, (void*)&ld, (void*)&vals};
+        H2_CHECK(hipModuleLaunchKernel(lgen, (uint32_t)((rows + 255) / 256), 1, 1, 256, 1, 1, 0, s, args, nullptr));
+        g_rtc_stats.launches++;
+        return 0;
+    }
+    g_rtc_stats.interpreted++;
+    const dim3 g(lp.lanes / 256);
+    switch (lp.tier) {
+        case 4: hipLaunchKernelGGL(evalh_lookup_kernel<4>, g, block, 4 * 9 * 256 * 4, s, lg, ld, cols, d_values, gws, lp.lanes); break;
+        case 8: hipLaunchKernelGGL(evalh_lookup_kernel<8>, g, block, 8 * 9 * 256 * 4, s, lg, ld, cols, d_values, gws, lp.lanes); break;
+        case 16: hipLaunchKernelGGL(evalh_lookup_kernel<16>, g, block, EVALH_LDS_HOT * 9 * 256 * 4, s, lg, ld, cols, d_values, gws, lp.lanes); break;
+        case 64: hipLaunchKernelGGL(evalh_lookup_kernel<64>, g, block, EVALH_LDS_HOT * 9 * 256 * 4, s, lg, ld, cols, d_values, gws, lp.lanes); break;
+        case 256: hipLaunchKernelGGL(evalh_lookup_kernel<256>, g, block, EVALH_LDS_HOT * 9 * 256 * 4, s, lg, ld, cols, d_values, gws, lp.lanes); break;
+        default: hipLaunchKernelGGL(evalh_lookup_kernel<0>, g, block, 0, s, lg, ld, cols, d_values, gws, lp.lanes);
+    }
+    H2_CHECK(hipGetLastError());
+    return 0;
+}
+
+// lookups whose three cosets are resident at once: as many as g_evalh_lookup_group_bytes hold, at least one
+static size_t lookup_group(size_t n_lookups, size_t col_bytes) {
+    if (!n_lookups) return 0;
+    const size_t fit = g_evalh_lookup_group_bytes / (3 * col_bytes);
+    return n_lookups <= fit ? n_lookups : fit ? fit : 1;
+}
+
+// The arena every form of evaluate_h allocates behind its metadata region: the columns the engine itself keeps resident and, in the
+// host-pointer forms, its copy of `values`.  The call paths size their arena here and h2hip_evaluate_h_workspace_bytes reports it.
+//   full form:  columns of 2^ek.  Host: every column of the description, the lookup cosets of one group and `values`; device: only
+//               the cosets the call itself forms (advice, instance, one group of lookups).
+//   parts form: columns of 2^k.  One part's cosets of EVERY column (the key's too: they arrive as polynomials), one group of lookups
+//               and the part's rows of `values`; host: also the coefficient columns, uploaded once, and `values`.
+static int evaluate_h_workspace_bytes(uint32_t k, uint32_t ek, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance, uint32_t n_perm_sets,
+                                      uint32_t n_perm_columns, uint32_t n_lookups, bool parts, bool dev, size_t* bytes) {
+    if (!bytes) {
+        set_error("evaluate_h: null argument");
+        return 1;
+    }
+    if (k > ek || ek > 28 || ek - k > 8) {
+        set_error("evaluate_h: bad domain (k = %u, extended_k = %u)", k, ek);
+        return 1;
+    }
+    const size_t col_bytes = sizeof(Fe) << ek;
+    if (!parts) {
+        const size_t lk_group = lookup_group(n_lookups, col_bytes);
+        const size_t n_cols = dev ? (size_t)n_advice + n_instance + 3 * lk_group
+                                  : (size_t)n_fixed + n_advice + n_instance + 3 /* l0, l_last, l_active */ + n_perm_sets + n_perm_columns +
+                                        3 * lk_group /* lookup cosets, reused per group */ + 1 /* values */;
+        *bytes = n_cols * (col_bytes + 256) + 4096;
+        return 0;
+    }
+    const size_t part_bytes = align256(sizeof(Fe) << k);
+    const size_t key_and_witness = (size_t)n_fixed + n_advice + n_instance + 3 + (n_perm_sets ? (size_t)n_perm_sets + n_perm_columns : 0);
+    const size_t resident = key_and_witness + 3 * lookup_group(n_lookups, part_bytes) + 1 /* the part's rows of values */;
+    *bytes = resident * part_bytes;
+    if (!dev) *bytes += (key_and_witness + 3 * (size_t)n_lookups) * part_bytes + align256(col_bytes);
+    return 0;
+}
+
 // dev = false: every column pointer in `d` and `values` are host memory (the reference's Vec<F>s); values is updated in place
 //              and the call returns when it is.
 // dev = true:  the columns and `values` are device memory (extended cosets are used where they lie, the first NTT pass reads
@@ -1152,19 +1245,15 @@ int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, uint64_t* values, bool de
     // ---- device arena: [metadata | columns the engine owns]
     // lookup cosets: three buffers per lookup for as many lookups as 2 GB hold (a group); the first group's transforms join the advice /
     // instance batch, later groups reuse the buffers once the kernels of the group before are queued
-    size_t lk_group = d->n_lookups;
-    if (lk_group) {
-        const size_t fit = g_evalh_lookup_group_bytes / (3 * col_bytes);
-        if (lk_group > fit) lk_group = fit ? fit : 1;
-    }
-    const size_t n_cols = dev ? (size_t)d->n_advice + d->n_instance + 3 * lk_group
-                              : (size_t)d->n_fixed + d->n_advice + d->n_instance + 3 /* l0, l_last, l_active */ + d->n_perm_sets + d->n_perm_columns +
-                                    3 * lk_group /* lookup cosets, reused per group */ + 1 /* values */;
+    const size_t lk_group = lookup_group(d->n_lookups, col_bytes);
+    size_t arena_bytes;
+    if ((rc = evaluate_h_workspace_bytes(k, ek, d->n_fixed, d->n_advice, d->n_instance, d->n_perm_sets, d->n_perm_columns, d->n_lookups, false, dev, &arena_bytes)))
+        return rc;
     size_t meta_cap = 64 * 1024 + prog_bytes(d->custom_gates, gates_prog) + ((size_t)d->n_challenges + 28) * sizeof(Fu) +
                       (8 + 256) * ((size_t)d->n_fixed + d->n_advice + d->n_instance + d->n_perm_sets + 2 * (size_t)d->n_perm_columns + 16);
     for (uint32_t i = 0; i < d->n_lookups; i++) meta_cap += prog_bytes(d->lookup_graphs[i], lookup_progs[i]);
     meta_cap = (meta_cap + 255) / 256 * 256;
-    if ((rc = c->evalh_ws.ensure(meta_cap + n_cols * (col_bytes + 256) + 4096))) return rc;
+    if ((rc = c->evalh_ws.ensure(meta_cap + arena_bytes))) return rc;
     if (slots_ws && (rc = c->evalh_slots.ensure(slots_ws))) return rc;
     Fu* const gws = (Fu*)c->evalh_slots.p;
     if ((rc = c->ws_acquire(s))) return rc;
@@ -1305,27 +1394,9 @@ int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, uint64_t* values, bool de
     c->timer_end(t_c, s);
     const dim3 grid((uint32_t)((size + 255) / 256)), block(256);
 
-    // ---- custom gates (:334-360): the kernel generated for this circuit once it is compiled, the interpreter until then
+    // ---- custom gates (:334-360)
     int t_g = c->timer_begin("evalh_gates", s);
-    hipFunction_t gen = gates_plan.tier != 0 ? gates_kernel_for(c, d->custom_gates, gates_prog) : nullptr;
-    if (gen) {
-        Fe* vals = d_values;
-        void* args[] = {(void*)&cols, (void*)&vals};
-        H2_CHECK(hipModuleLaunchKernel(gen, (uint32_t)((size + 255) / 256), 1, 1, 256, 1, 1, 0, s, args, nullptr));
-        g_rtc_stats.launches++;
-    } else {
-        g_rtc_stats.interpreted++;
-        const dim3 g(gates_plan.lanes / 256);
-        switch (gates_plan.tier) {
-            case 4: hipLaunchKernelGGL(evalh_gates_kernel<4>, g, block, 4 * 9 * 256 * 4, s, gd, cols, d_values, gws, gates_plan.lanes); break;
-            case 8: hipLaunchKernelGGL(evalh_gates_kernel<8>, g, block, 8 * 9 * 256 * 4, s, gd, cols, d_values, gws, gates_plan.lanes); break;
-            case 16: hipLaunchKernelGGL(evalh_gates_kernel<16>, g, block, EVALH_LDS_HOT * 9 * 256 * 4, s, gd, cols, d_values, gws, gates_plan.lanes); break;
-            case 64: hipLaunchKernelGGL(evalh_gates_kernel<64>, g, block, EVALH_LDS_HOT * 9 * 256 * 4, s, gd, cols, d_values, gws, gates_plan.lanes); break;
-            case 256: hipLaunchKernelGGL(evalh_gates_kernel<256>, g, block, EVALH_LDS_HOT * 9 * 256 * 4, s, gd, cols, d_values, gws, gates_plan.lanes); break;
-            default: hipLaunchKernelGGL(evalh_gates_kernel<0>, g, block, 0, s, gd, cols, d_values, gws, gates_plan.lanes);
-        }
-    }
-    H2_CHECK(hipGetLastError());
+    if ((rc = enqueue_gates(c, d->custom_gates, gates_prog, gates_plan, gd, cols, d_values, gws, size, s))) return rc;
     c->timer_end(t_g, s);
 
     // ---- permutations (:362-441)
@@ -1357,32 +1428,328 @@ int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, uint64_t* values, bool de
             }
             if ((rc = ntt_device_batch(c, lbuf.data(), lsrc.data(), 3 * cnt, ext_omega, ek, &sc, s))) return rc;
         }
-        const ProgDev& lg = lgs[i];
-        LookupDev ld = {lbuf[3 * gi], lbuf[3 * gi + 1], lbuf[3 * gi + 2], l0, l_last, l_active};
-        const SlotPlan& lp = lookup_plans[i];
-        if (hipFunction_t lgen = gates_kernel_for(c, d->lookup_graphs[i], lookup_progs[i], true)) {  // generated for this circuit, as the gates kernel is
-            Fe* vals = d_values;
-            void* args[] = {(void*)&cols, (void*)&ld, (void*)&vals};
-            H2_CHECK(hipModuleLaunchKernel(lgen, (uint32_t)((size + 255) / 256), 1, 1, 256, 1, 1, 0, s, args, nullptr));
-            g_rtc_stats.launches++;
-            continue;
-        }
-        g_rtc_stats.interpreted++;
-        const dim3 g(lp.lanes / 256);
-        switch (lp.tier) {
-            case 4: hipLaunchKernelGGL(evalh_lookup_kernel<4>, g, block, 4 * 9 * 256 * 4, s, lg, ld, cols, d_values, gws, lp.lanes); break;
-            case 8: hipLaunchKernelGGL(evalh_lookup_kernel<8>, g, block, 8 * 9 * 256 * 4, s, lg, ld, cols, d_values, gws, lp.lanes); break;
-            case 16: hipLaunchKernelGGL(evalh_lookup_kernel<16>, g, block, EVALH_LDS_HOT * 9 * 256 * 4, s, lg, ld, cols, d_values, gws, lp.lanes); break;
-            case 64: hipLaunchKernelGGL(evalh_lookup_kernel<64>, g, block, EVALH_LDS_HOT * 9 * 256 * 4, s, lg, ld, cols, d_values, gws, lp.lanes); break;
-            case 256: hipLaunchKernelGGL(evalh_lookup_kernel<256>, g, block, EVALH_LDS_HOT * 9 * 256 * 4, s, lg, ld, cols, d_values, gws, lp.lanes); break;
-            default: hipLaunchKernelGGL(evalh_lookup_kernel<0>, g, block, 0, s, lg, ld, cols, d_values, gws, lp.lanes);
-        }
-        H2_CHECK(hipGetLastError());
+        const LookupDev ld = {lbuf[3 * gi], lbuf[3 * gi + 1], lbuf[3 * gi + 2], l0, l_last, l_active};
+        if ((rc = enqueue_lookup(c, d->lookup_graphs[i], lookup_progs[i], lookup_plans[i], lgs[i], ld, cols, d_values, gws, size, s))) return rc;
     }
     c->timer_end(t_l, s);
     if ((rc = guard.release())) return rc;
     if (dev) return 0;
     H2_CHECK(hipMemcpyAsync(values, d_values, col_bytes, hipMemcpyDeviceToHost, s));
+    H2_CHECK(hipStreamSynchronize(s));
+    return 0;
+}
+
+
+// ---- evaluate_h one coset of the 2^k domain at a time (h2hip_evaluate_h_parts_bn254[_device]) ---------------------------------------
+// With P = 2^(ek - k), extended row i = j P + p lies at X_i = g_p omega^j, where g_p = zeta extended_omega^p and omega =
+// extended_omega^P is the 2^k-th root.  The rows of part p are therefore the size-2^k transform of f(g_p X), and a rotation by r rows of
+// the 2^k domain moves (j, p) to (j + r, p): a part is closed under every rotation the constraints use.  The kernels above run on a part
+// as they are, with log_size = k and rot_scale = 1 (as lookup_compress runs them), the permutation kernel with the 2^k domain's power
+// table and delta_start = beta g_p.  What is new is the scaling f_m -> f_m g_p^m in front of the transform and the gather / scatter
+// between a part's 2^k rows and values[j P + p].  Every column arrives as a polynomial of 2^k coefficients, the proving key's too, so the
+// engine holds columns of 2^k elements where the full form holds columns of 2^ek.
+
+// One of three kernel-argument constants by a lane-dependent residue, as bit-mask arithmetic (ntt.hip's pick3, where the reason is given)
+__device__ __forceinline__ Fu pick3(const Fu (&c)[3], uint32_t m) {
+    const int32_t m1 = -(int32_t)(m == 1), m2 = -(int32_t)(m == 2);
+    Fu r;
+#pragma unroll
+    for (int i = 0; i < 9; i++) r.l[i] = c[0].l[i] ^ ((c[0].l[i] ^ c[1].l[i]) & m1) ^ ((c[0].l[i] ^ c[2].l[i]) & m2);
+    return r;
+}
+
+struct PartScaleDev {
+    const Fe* const* src;        // n_cols coefficient-form columns of 2^log_n elements
+    const Fe* const* dst;        // where each goes, scaled (arena columns; written through)
+    uint32_t n_cols, log_n, part;
+    Fu c3[3];                    // 1, zeta, zeta^2: I-form canonical
+    const Fu *pow_lo, *pow_hi;   // the EXTENDED domain's two-level power table (ntt_power_table), I-form canonical
+    uint32_t pow_bits;
+};
+#define EVALH_SCALE_COLS 8  // columns one lane scales with the power it formed
+
+// out_c[m] = f_c[m] g_p^m for the columns of a batch.  g_p^m = zeta^(m mod 3) extended_omega^(p m): zeta is a cube root of one, and
+// p m < P 2^k = 2^ek indexes the extended domain's table without a reduction.  The lane of row m forms the power once (two
+// multiplications) and spends one more per column.  Data is E-form, the power I-form, and the product leaves canonical, as every NTT
+// pass stores it.  Magnitudes: table entries and c3 are canonical, so each fu_mul result lies in [0, 1.01 r) -- fu_mul_canon's
+// constant operand.
+__global__ void __launch_bounds__(256) evalh_part_scale_kernel(PartScaleDev a) {
+    const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= (1u << a.log_n)) return;
+    const uint32_t e = a.part * m;
+    Fu g = fu_mul<UF>(a.pow_lo[e & ((1u << a.pow_bits) - 1)], a.pow_hi[e >> a.pow_bits]);
+    g = fu_mul<UF>(g, pick3(a.c3, m % 3u));
+    const uint32_t c0 = blockIdx.y * EVALH_SCALE_COLS, c1 = c0 + EVALH_SCALE_COLS < a.n_cols ? c0 + EVALH_SCALE_COLS : a.n_cols;
+    for (uint32_t col = c0; col < c1; col++) {
+        Fe* out = (Fe*)ld_const_col(a.dst, col);
+        out[m] = fu_mul_canon<UF>(fu_slice(ld_const_col(a.src, col)[m]), g);
+    }
+}
+
+// A part's rows of `values` lie 32 P bytes apart: a lane moves one row (two 16-byte accesses), a wave touches 64 consecutive lines (of
+// 128 bytes, at P = 4) and a quarter of each.  The other quarters belong to other parts and must stay as they are -- a call may be given a
+// range of parts -- so the lines cannot be written whole; the hardware merges the partial writes in L2.
+__global__ void __launch_bounds__(256) evalh_part_gather_kernel(const Fe* __restrict__ values, Fe* __restrict__ part, uint32_t log_n,
+                                                                uint32_t log_p, uint32_t p) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= (1u << log_n)) return;
+    part[j] = values[((size_t)j << log_p) + p];
+}
+// scaled: the rows leave multiplied by t_evaluations[p] (t_i: I-form canonical), which is divide_by_vanishing_poly on this part
+__global__ void __launch_bounds__(256) evalh_part_scatter_kernel(const Fe* __restrict__ part, Fe* __restrict__ values, uint32_t log_n,
+                                                                 uint32_t log_p, uint32_t p, Fu t_i, int scaled) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= (1u << log_n)) return;
+    const Fe v = part[j];
+    values[((size_t)j << log_p) + p] = scaled ? fu_mul_canon<UF>(fu_slice(v), t_i) : v;
+}
+
+// the full form's view of a parts description, for the checks the two share (the graphs, the scalars, the permutation layout); the
+// pointers the full form expects as extended cosets carry the polynomials here, and only their presence is looked at
+static h2hip_evalh_desc parts_as_full(const h2hip_evalh_parts_desc& d) {
+    h2hip_evalh_desc f;
+    memset(&f, 0, sizeof(f));
+    f.k = d.k, f.extended_k = d.extended_k;
+    f.extended_omega = d.extended_omega, f.g_coset = d.g_coset, f.g_coset_inv = d.g_coset_inv;
+    f.n_fixed = d.n_fixed, f.n_advice = d.n_advice, f.n_instance = d.n_instance, f.n_challenges = d.n_challenges;
+    f.fixed_cosets = d.fixed_polys, f.advice_polys = d.advice_polys, f.instance_polys = d.instance_polys;
+    f.challenges = d.challenges;
+    f.y = d.y, f.beta = d.beta, f.gamma = d.gamma, f.theta = d.theta;
+    f.l0 = d.l0_poly, f.l_last = d.l_last_poly, f.l_active_row = d.l_active_row_poly;
+    f.custom_gates = d.custom_gates;
+    f.n_perm_sets = d.n_perm_sets, f.n_perm_columns = d.n_perm_columns, f.chunk_len = d.chunk_len, f.last_rotation = d.last_rotation;
+    f.perm_product_cosets = d.perm_product_polys, f.perm_column_kind = d.perm_column_kind, f.perm_column_index = d.perm_column_index;
+    f.perm_cosets = d.perm_polys;
+    f.zeta = d.zeta, f.delta = d.delta;
+    f.n_lookups = d.n_lookups, f.lookup_graphs = d.lookup_graphs;
+    f.lookup_product_polys = d.lookup_product_polys, f.lookup_permuted_input_polys = d.lookup_permuted_input_polys;
+    f.lookup_permuted_table_polys = d.lookup_permuted_table_polys;
+    return f;
+}
+
+// As evaluate_h_validate, and what only this form can get wrong: a null polynomial in any table (the full form finds those while it
+// places its columns; here nothing is placed before the device is in use) and a part range beyond P.  Needs no device.
+static int evaluate_h_parts_validate(const h2hip_evalh_parts_desc* d, const void* values) {
+    const h2hip_evalh_desc f = parts_as_full(*d);
+    if (evaluate_h_validate(&f, values)) return 1;
+    const uint32_t P = 1u << (d->extended_k - d->k);
+    if ((uint64_t)d->part_begin + d->part_count > P || (d->part_count == 0 && d->part_begin != 0)) {
+        set_error("evaluate_h: parts %u .. %u + %u of %u", d->part_begin, d->part_begin, d->part_count, P);
+        return 1;
+    }
+    const struct { const uint64_t* const* tab; size_t count; const char* name; } tabs[] = {
+        {d->fixed_polys, d->n_fixed, "fixed_polys"},
+        {d->advice_polys, d->n_advice, "advice_polys"},
+        {d->instance_polys, d->n_instance, "instance_polys"},
+        {d->perm_product_polys, d->n_perm_sets, "perm_product_polys"},
+        {d->perm_polys, d->n_perm_sets ? d->n_perm_columns : 0, "perm_polys"},
+        {d->lookup_product_polys, d->n_lookups, "lookup_product_polys"},
+        {d->lookup_permuted_input_polys, d->n_lookups, "lookup_permuted_input_polys"},
+        {d->lookup_permuted_table_polys, d->n_lookups, "lookup_permuted_table_polys"},
+    };
+    for (const auto& t : tabs)
+        if (check_ptrs("evaluate_h", (const void* const*)t.tab, t.count, t.name)) return 1;
+    return 0;
+}
+
+// dev as in evaluate_h_host.  Host form: every coefficient column crosses once (2^k elements), `values` crosses both ways once.
+static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, uint64_t* values, bool dev, hipStream_t s) {
+    const uint32_t k = d->k, ek = d->extended_k, log_p = ek - k;
+    const size_t n = (size_t)1 << k, size = (size_t)1 << ek;
+    const size_t part_bytes = align256(n * sizeof(Fe));
+    const uint32_t p_begin = d->part_count ? d->part_begin : 0, p_end = d->part_count ? d->part_begin + d->part_count : 1u << log_p;
+    const Program gates_prog = compile_graph(d->custom_gates);
+    std::vector<Program> lookup_progs(d->n_lookups);
+    for (uint32_t i = 0; i < d->n_lookups; i++) lookup_progs[i] = compile_graph(d->lookup_graphs[i]);
+    int rc;
+    SlotPlan gates_plan;
+    std::vector<SlotPlan> lookup_plans(d->n_lookups);
+    if ((rc = slot_plan(gates_prog.n_slots, n, &gates_plan))) return rc;
+    size_t slots_ws = gates_plan.ws_bytes;
+    for (uint32_t i = 0; i < d->n_lookups; i++) {
+        if ((rc = slot_plan(lookup_progs[i].n_slots, n, &lookup_plans[i]))) return rc;
+        if (lookup_plans[i].ws_bytes > slots_ws) slots_ws = lookup_plans[i].ws_bytes;
+    }
+    // ---- the coefficient columns, in the order of the batch that transforms them: key and witness columns, then the lookups'
+    std::vector<const uint64_t*> polys;
+    for (uint32_t i = 0; i < d->n_fixed; i++) polys.push_back(d->fixed_polys[i]);
+    for (uint32_t i = 0; i < d->n_advice; i++) polys.push_back(d->advice_polys[i]);
+    for (uint32_t i = 0; i < d->n_instance; i++) polys.push_back(d->instance_polys[i]);
+    const size_t at_l0 = polys.size();
+    polys.push_back(d->l0_poly), polys.push_back(d->l_last_poly), polys.push_back(d->l_active_row_poly);
+    const size_t at_z = polys.size();
+    if (d->n_perm_sets) {
+        for (uint32_t i = 0; i < d->n_perm_sets; i++) polys.push_back(d->perm_product_polys[i]);
+        for (uint32_t j = 0; j < d->n_perm_columns; j++) polys.push_back(d->perm_polys[j]);
+    }
+    const size_t n_main = polys.size();  // every part transforms these; the lookups follow in groups
+    for (uint32_t i = 0; i < d->n_lookups; i++)
+        polys.push_back(d->lookup_product_polys[i]), polys.push_back(d->lookup_permuted_input_polys[i]), polys.push_back(d->lookup_permuted_table_polys[i]);
+    const size_t lk_group = lookup_group(d->n_lookups, part_bytes);
+    const size_t n_part_cols = n_main + 3 * lk_group;
+    // ---- device arena: [metadata | (host form) coefficient columns | one part's cosets | the part's rows of values | (host form) values]
+    size_t arena_bytes;
+    if ((rc = evaluate_h_workspace_bytes(k, ek, d->n_fixed, d->n_advice, d->n_instance, d->n_perm_sets, d->n_perm_columns, d->n_lookups, true, dev, &arena_bytes)))
+        return rc;
+    size_t meta_cap = 64 * 1024 + prog_bytes(d->custom_gates, gates_prog) + ((size_t)d->n_challenges + 28) * sizeof(Fu) +
+                      (8 + 256) * ((size_t)d->n_fixed + d->n_advice + d->n_instance + d->n_perm_sets + 2 * (size_t)d->n_perm_columns + 16) +
+                      8 * (polys.size() + n_part_cols);
+    for (uint32_t i = 0; i < d->n_lookups; i++) meta_cap += prog_bytes(d->lookup_graphs[i], lookup_progs[i]);
+    meta_cap = align256(meta_cap);
+    if ((rc = c->evalh_ws.ensure(meta_cap + arena_bytes))) return rc;
+    if (slots_ws && (rc = c->evalh_slots.ensure(slots_ws))) return rc;
+    Fu* const gws = (Fu*)c->evalh_slots.p;
+    if ((rc = c->ws_acquire(s))) return rc;
+    WsGuard guard(c, s);
+    Arena ar;
+    ar.base = (char*)c->evalh_ws.p;
+    ar.cap = meta_cap + arena_bytes;  // what was asked for, not what the buffer happens to hold: the sizing function is the contract
+    MetaBlob mb;
+    mb.dev_base = (char*)ar.take(meta_cap);
+    mb.cap = meta_cap;
+    std::vector<const Fe*> src(polys.size());
+    for (size_t i = 0; i < polys.size(); i++) src[i] = dev ? (const Fe*)polys[i] : (const Fe*)ar.take(part_bytes);
+    std::vector<Fe*> part_cols(n_part_cols);
+    for (size_t i = 0; i < n_part_cols; i++) part_cols[i] = (Fe*)ar.take(part_bytes);
+    Fe* const d_part = (Fe*)ar.take(part_bytes);
+    Fe* const d_values = dev ? (Fe*)values : (Fe*)ar.take(size * sizeof(Fe));
+    if (!mb.dev_base || !d_part || !d_values || ar.off > ar.cap) {
+        set_error("evaluate_h: arena overflow");
+        return 1;
+    }
+    // ---- the two domains' power tables.  A table handed out by ntt_power_table lives until the twiddle cache is cleared, which only
+    // the insertion of a domain the cache does not hold yet can do (ntt.hip, get_twiddles).  So both domains are brought into the cache
+    // first -- the second request may clear it, in which case the third puts the extended domain back into a cache of one -- and only
+    // then are the pointers kept.  Everything this call transforms afterwards is over (omega, k), a cache hit that inserts nothing, and
+    // the context's lock keeps other calls out until this one has queued its last kernel: no kernel queued below can outlive its table.
+    const Fe ext_omega = fe_from_u64x4(d->extended_omega);
+    const Fe omega = fe_pow_u64<FrP>(ext_omega, (uint64_t)1 << log_p);
+    PartScaleDev sd;
+    memset(&sd, 0, sizeof(sd));
+    PermDev pd;
+    memset(&pd, 0, sizeof(pd));
+    if ((rc = ntt_power_table(c, ext_omega, ek, s, &sd.pow_lo, &sd.pow_hi, &sd.pow_bits))) return rc;
+    if ((rc = ntt_power_table(c, omega, k, s, &pd.pow_lo, &pd.pow_hi, &pd.pow_bits))) return rc;
+    if ((rc = ntt_power_table(c, ext_omega, ek, s, &sd.pow_lo, &sd.pow_hi, &sd.pow_bits))) return rc;
+    // ---- metadata image
+    const Fe* const* d_src = mb.put(src.data(), src.size());
+    const Fe* const* d_dst = (const Fe* const*)mb.put(part_cols.data(), part_cols.size());
+    const Fe* const* col = part_cols.data();  // one part's cosets, in the order of `polys`
+    ColsDev cols;
+    cols.fixed = mb.put(col, d->n_fixed);
+    cols.advice = mb.put(col + d->n_fixed, d->n_advice);
+    cols.instance = mb.put(col + d->n_fixed + d->n_advice, d->n_instance);
+    {
+        std::vector<Fu> hch(d->n_challenges);
+        for (uint32_t i = 0; i < d->n_challenges; i++) hch[i] = to_i(fe_from_u64x4(d->challenges + 4 * (size_t)i));
+        cols.challenges = mb.put(hch.data(), hch.size());
+    }
+    cols.beta = to_i(fe_from_u64x4(d->beta));
+    cols.gamma = to_i(fe_from_u64x4(d->gamma));
+    cols.theta = to_i(fe_from_u64x4(d->theta));
+    cols.y = to_i(fe_from_u64x4(d->y));
+    cols.log_size = k;
+    cols.rot_scale = 1;
+    ProgDev gd;
+    prog_put(mb, d->custom_gates, gates_prog, &gd);
+    std::vector<ProgDev> lgs(d->n_lookups);
+    for (uint32_t i = 0; i < d->n_lookups; i++) prog_put(mb, d->lookup_graphs[i], lookup_progs[i], &lgs[i]);
+    const Fe *l0 = col[at_l0], *l_last = col[at_l0 + 1], *l_active = col[at_l0 + 2];
+    if (d->n_perm_sets) {
+        std::vector<const Fe*> pcols(d->n_perm_columns);
+        for (uint32_t j = 0; j < d->n_perm_columns; j++) {
+            const uint32_t kind = d->perm_column_kind[j], idx = d->perm_column_index[j];
+            pcols[j] = kind == H2HIP_ANY_ADVICE ? col[d->n_fixed + idx] : kind == H2HIP_ANY_FIXED ? col[idx] : col[d->n_fixed + d->n_advice + idx];
+        }
+        pd.z = mb.put(col + at_z, d->n_perm_sets);
+        pd.cols = mb.put(pcols.data(), pcols.size());
+        pd.cosets = mb.put(col + at_z + d->n_perm_sets, d->n_perm_columns);
+        pd.l0 = l0;
+        pd.l_last = l_last;
+        pd.l_active = l_active;
+        pd.delta = to_i(fe_from_u64x4(d->delta));
+        pd.n_sets = d->n_perm_sets;
+        pd.n_cols = d->n_perm_columns;
+        pd.chunk_len = d->chunk_len;
+        pd.last_rotation = d->last_rotation;
+    }
+    if (mb.overflow) {
+        set_error("evaluate_h: metadata region overflow");
+        return 1;
+    }
+    if ((rc = c->stage_h2d(mb.dev_base, mb.host.data(), mb.host.size(), s))) return rc;
+    // ---- host form: every coefficient column and `values` cross once, on `s` like everything else of this call.  Of `values` only the
+    // rows of this call's parts cross, in either direction: P rows of consecutive parts are contiguous, so a range of parts is a 2-D copy
+    auto copy_values = [&](Fe* dst, const Fe* from, hipMemcpyKind kind) -> int {
+        if (p_end - p_begin == 1u << log_p) {
+            H2_CHECK(hipMemcpyAsync(dst, from, size * sizeof(Fe), kind, s));
+        } else {
+            const size_t pitch = sizeof(Fe) << log_p;
+            H2_CHECK(hipMemcpy2DAsync(dst + p_begin, pitch, from + p_begin, pitch, (p_end - p_begin) * sizeof(Fe), n, kind, s));
+        }
+        return 0;
+    };
+    if (!dev) {
+        for (size_t i = 0; i < polys.size(); i++) H2_CHECK(hipMemcpyAsync((void*)src[i], polys[i], n * sizeof(Fe), hipMemcpyHostToDevice, s));
+        if ((rc = copy_values(d_values, (const Fe*)values, hipMemcpyHostToDevice))) return rc;
+    }
+    sd.log_n = k;
+    sd.c3[0] = fu_one_i<UF>();
+    sd.c3[1] = to_i(fe_from_u64x4(d->g_coset));
+    sd.c3[2] = to_i(fe_from_u64x4(d->g_coset_inv));
+    // columns first .. first + count of `polys` -> part_cols[to ..], scaled for part p and transformed over the 2^k domain
+    auto to_part = [&](uint32_t p, size_t first, size_t to, size_t count) -> int {
+        sd.src = d_src + first;
+        sd.dst = d_dst + to;
+        sd.n_cols = (uint32_t)count;
+        sd.part = p;
+        const dim3 g((uint32_t)((n + 255) / 256), (uint32_t)((count + EVALH_SCALE_COLS - 1) / EVALH_SCALE_COLS));
+        int t_s = c->timer_begin("evalh_part_scale", s);
+        hipLaunchKernelGGL(evalh_part_scale_kernel, g, dim3(256), 0, s, sd);
+        H2_CHECK(hipGetLastError());
+        c->timer_end(t_s, s);
+        return ntt_device_batch(c, part_cols.data() + to, nullptr, count, omega, k, nullptr, s);
+    };
+    const dim3 grid((uint32_t)((n + 255) / 256)), block(256);
+    const Fe beta_zeta = fe_mul<FrP>(fe_from_u64x4(d->beta), fe_from_u64x4(d->zeta));
+    for (uint32_t p = p_begin; p < p_end; p++) {
+        int t_c = c->timer_begin("evalh_cosets", s);
+        if ((rc = to_part(p, 0, 0, n_part_cols))) return rc;
+        c->timer_end(t_c, s);
+        int t_io = c->timer_begin("evalh_part_io", s);
+        hipLaunchKernelGGL(evalh_part_gather_kernel, grid, block, 0, s, (const Fe*)d_values, d_part, k, log_p, p);
+        H2_CHECK(hipGetLastError());
+        c->timer_end(t_io, s);
+        int t_g = c->timer_begin("evalh_gates", s);
+        if ((rc = enqueue_gates(c, d->custom_gates, gates_prog, gates_plan, gd, cols, d_part, gws, n, s))) return rc;
+        c->timer_end(t_g, s);
+        if (d->n_perm_sets) {
+            pd.delta_start = to_i(fe_mul<FrP>(beta_zeta, fe_pow_u64<FrP>(ext_omega, p)));  // beta g_p; the kernel multiplies by omega^j
+            int t_p = c->timer_begin("evalh_perm", s);
+            hipLaunchKernelGGL(evalh_perm_kernel, grid, block, 0, s, pd, cols, d_part);
+            H2_CHECK(hipGetLastError());
+            c->timer_end(t_p, s);
+        }
+        int t_l = d->n_lookups ? c->timer_begin("evalh_lookups", s) : -1;
+        for (uint32_t i = 0; i < d->n_lookups; i++) {
+            const size_t gi = i % lk_group;
+            if (gi == 0 && i) {  // the next group's cosets, into the group's buffers
+                const size_t cnt = d->n_lookups - i < lk_group ? d->n_lookups - i : lk_group;
+                if ((rc = to_part(p, n_main + 3 * (size_t)i, n_main, 3 * cnt))) return rc;
+            }
+            const LookupDev ld = {col[n_main + 3 * gi], col[n_main + 3 * gi + 1], col[n_main + 3 * gi + 2], l0, l_last, l_active};
+            if ((rc = enqueue_lookup(c, d->lookup_graphs[i], lookup_progs[i], lookup_plans[i], lgs[i], ld, cols, d_part, gws, n, s))) return rc;
+        }
+        c->timer_end(t_l, s);
+        t_io = c->timer_begin("evalh_part_io", s);
+        const Fu t_i = d->t_evaluations ? to_i(fe_from_u64x4(d->t_evaluations + 4 * (size_t)p)) : fu_one_i<UF>();
+        hipLaunchKernelGGL(evalh_part_scatter_kernel, grid, block, 0, s, (const Fe*)d_part, d_values, k, log_p, p, t_i, d->t_evaluations ? 1 : 0);
+        H2_CHECK(hipGetLastError());
+        c->timer_end(t_io, s);
+    }
+    if ((rc = guard.release())) return rc;
+    if (dev) return 0;
+    if ((rc = copy_values((Fe*)values, d_values, hipMemcpyDeviceToHost))) return rc;
     H2_CHECK(hipStreamSynchronize(s));
     return 0;
 }
@@ -1584,3 +1951,51 @@ int check_gates_enqueue(Ctx* c, uint32_t k, const Fe* const* fixed, uint32_t n_f
 }
 
 }  // namespace h2
+
+using namespace h2;
+
+extern "C" {
+// ---- C ABI (include/halo2hip.h, evaluate_h one coset of the 2^k domain at a time) ------------------------------------------------------
+// Here rather than in api.hip for the reason product.hip gives: api.hip is also compiled alone against a stub runtime.
+int h2hip_evaluate_h_parts_bn254(const h2hip_evalh_parts_desc* desc, uint64_t* values) {
+    if (!desc || !values) {
+        set_error("evaluate_h: null argument");
+        return H2HIP_EINVAL;
+    }
+    if (evaluate_h_parts_validate(desc, values)) return H2HIP_EINVAL;
+    Entry en("h2hip_evaluate_h_parts_bn254");
+    if (en.rc) return en.rc;
+    return evaluate_h_parts_host(en.c, desc, values, false, en.c->stream);
+}
+
+int h2hip_evaluate_h_parts_bn254_device(const h2hip_evalh_parts_desc* desc, void* d_values, void* stream) {
+    if (!desc || !d_values) {
+        set_error("evaluate_h: null argument");
+        return H2HIP_EINVAL;
+    }
+    if (evaluate_h_parts_validate(desc, d_values)) return H2HIP_EINVAL;
+    Entry en("h2hip_evaluate_h_parts_bn254_device", d_values);
+    if (en.rc) return en.rc;
+    return evaluate_h_parts_host(en.c, desc, (uint64_t*)d_values, true, (hipStream_t)stream);
+}
+
+int h2hip_evaluate_h_workspace_bytes(uint32_t k, uint32_t extended_k, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance,
+                                     uint32_t n_perm_sets, uint32_t n_perm_columns, uint32_t n_lookups, int parts_form, int device_form,
+                                     size_t* bytes) {
+    return evaluate_h_workspace_bytes(k, extended_k, n_fixed, n_advice, n_instance, n_perm_sets, n_perm_columns, n_lookups, parts_form != 0,
+                                      device_form != 0, bytes)
+               ? H2HIP_EINVAL
+               : 0;
+}
+
+int h2hip_debug_evalh_power_table_bits(const uint64_t omega[4], uint32_t log_n, uint32_t* lo_bits) {
+    if (!omega || !lo_bits || log_n > 28) {
+        set_error("evaluate_h: bad power table query");
+        return H2HIP_EINVAL;
+    }
+    Entry en("h2hip_debug_evalh_power_table_bits");
+    if (en.rc) return en.rc;
+    const Fu *lo, *hi;
+    return ntt_power_table(en.c, fe_from_u64x4(omega), log_n, en.c->stream, &lo, &hi, lo_bits);
+}
+}  // extern "C"

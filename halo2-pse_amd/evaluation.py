@@ -6,6 +6,8 @@
   Evaluator        Evaluator::new (:221-279) from gate polynomials + lookup argument expressions, and evaluate_h
                    (:280-522) which hands the flattened description to h2hip_evaluate_h_bn254[_device]
   ValueSource / Calculation / Graph / EvalhDesc    ctypes mirrors of the h2hip_* structs;  DescHolder builds one from numpy arrays
+  EvalhPartsDesc / PartsDescHolder / Evaluator.evaluate_h_parts    the same one coset of the 2^k domain at a time, every column given
+                   as a polynomial of 2^k coefficients (h2hip_evaluate_h_parts_bn254[_device])
 
 Expression trees are tuples:  ('const', int) ('fixed', col, rot) ('advice', col, rot) ('instance', col, rot)
 ('challenge', i) ('neg', e) ('sum', e, e) ('prod', e, e) ('scaled', e, int)   (plonk/circuit.rs Expression).
@@ -290,6 +292,49 @@ class DescHolder:
         return ctypes.byref(self.desc)
 
 
+# h2hip_evalh_desc field -> its name in h2hip_evalh_parts_desc, where the column is a polynomial of 2^k coefficients
+_PARTS_RENAMED = {"fixed_cosets": "fixed_polys", "l0": "l0_poly", "l_last": "l_last_poly", "l_active_row": "l_active_row_poly",
+                  "perm_product_cosets": "perm_product_polys", "perm_cosets": "perm_polys"}
+
+
+class EvalhPartsDesc(ctypes.Structure):
+    """h2hip_evalh_parts_desc: h2hip_evalh_desc's fields with every column a coefficient-form polynomial, then the part range and t_evaluations"""
+    _fields_ = [(_PARTS_RENAMED.get(name, name), t) for name, t in EvalhDesc._fields_] + [
+        ("part_begin", ctypes.c_uint32), ("part_count", ctypes.c_uint32), ("t_evaluations", ctypes.c_void_p)]
+
+
+class PartsDescHolder(DescHolder):
+    """Builds an EvalhPartsDesc from numpy arrays and keeps every buffer alive.
+
+    case: as for DescHolder with the columns under the names of h2hip_evalh_parts_desc -- fixed_polys (nf, n, 4), l0_poly / l_last_poly /
+    l_active_row_poly (n, 4), perm_product_polys (ns, n, 4), perm_polys (ncols, n, 4) -- and optionally part_begin, part_count (0, 0 = every
+    part) and t_evaluations (P, 4)"""
+
+    def __init__(self, case):
+        full = dict(case)
+        for old, new in _PARTS_RENAMED.items():
+            full[old] = case[new]
+        super().__init__(full)
+        d = EvalhPartsDesc()
+        for name, _ in EvalhDesc._fields_:
+            setattr(d, _PARTS_RENAMED.get(name, name), getattr(self.desc, name))
+        d.part_begin, d.part_count = int(case.get("part_begin", 0)), int(case.get("part_count", 0))
+        t = case.get("t_evaluations")
+        d.t_evaluations = None if t is None else _ptr(self._c(t))
+        self.desc = d
+
+
+def evaluate_h_workspace_bytes(k, extended_k, n_fixed, n_advice, n_instance, n_perm_sets, n_perm_columns, n_lookups, parts_form, device_form):
+    """HBM the engine allocates for the columns of one evaluate_h call and its copy of `values` (h2hip_evaluate_h_workspace_bytes; no GPU needed)"""
+    from . import _check, lib
+    out = ctypes.c_size_t()
+    u = ctypes.c_uint32
+    _check(lib().h2hip_evaluate_h_workspace_bytes(u(k), u(extended_k), u(n_fixed), u(n_advice), u(n_instance), u(n_perm_sets), u(n_perm_columns),
+                                                  u(n_lookups), ctypes.c_int(bool(parts_form)), ctypes.c_int(bool(device_form)), ctypes.byref(out)),
+           "evaluate_h_workspace_bytes")
+    return out.value
+
+
 def graph_struct(g, keep):
     """one flattened graph (flatten_graph dict) -> h2hip_graph; the arrays it points into are appended to `keep`"""
     c = lambda a, dt: keep.append(np.ascontiguousarray(a, dtype=dt)) or keep[-1]  # noqa: E731
@@ -334,6 +379,29 @@ class Evaluator:
         full["custom"] = flatten_graph(self.custom_gates)
         full["lookups"] = [(flatten_graph(g), *polys) for g, polys in zip(self.lookups, case["lookups"])]
         return DescHolder(full)
+
+    def describe_parts(self, case):
+        """case as for PartsDescHolder minus `custom` and the graphs inside `lookups`"""
+        full = dict(case)
+        full["custom"] = flatten_graph(self.custom_gates)
+        full["lookups"] = [(flatten_graph(g), *polys) for g, polys in zip(self.lookups, case["lookups"])]
+        return PartsDescHolder(full)
+
+    def evaluate_h_parts(self, case, values, parts=None, t_evaluations=None):
+        """evaluate_h for one circuit instance, one coset of the 2^k domain at a time, from coefficient-form columns: values
+        (2^extended_k, 4) u64 is folded in place and returned.  parts: (first, count) of the 2^(extended_k - k) parts to compute, None for
+        all -- the rows of the others are left as they are; t_evaluations: EvaluationDomain.t_evaluations on the last instance's call, which
+        then returns divide_by_vanishing_poly(h)"""
+        from . import _check, lib
+        full = dict(case)
+        if parts is not None:
+            full["part_begin"], full["part_count"] = parts
+        if t_evaluations is not None:
+            full["t_evaluations"] = t_evaluations
+        h = self.describe_parts(full)
+        values = np.ascontiguousarray(values, dtype=np.uint64)
+        _check(lib().h2hip_evaluate_h_parts_bn254(h.byref(), values.ctypes.data_as(ctypes.c_void_p)), "evaluate_h_parts")
+        return values
 
     def evaluate_h(self, case, values):
         """evaluate_h for one circuit instance (:280-522): values (2^extended_k, 4) u64 is folded in place and returned"""

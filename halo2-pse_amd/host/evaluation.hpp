@@ -4,7 +4,8 @@
 //   plonk::ValueSource       evaluation.rs:37-60   (same variant order: the derived PartialOrd is (kind, a, b))
 //   plonk::Calculation       evaluation.rs:108-127
 //   plonk::GraphEvaluator    evaluation.rs:191-201, :526-706  add_rotation / add_constant / add_calculation / add_expression
-//   plonk::Evaluator         evaluation.rs:182-189, new :221-279, evaluate_h :280-522 -> h2hip_evaluate_h_bn254
+//   plonk::Evaluator         evaluation.rs:182-189, new :221-279, evaluate_h :280-522 -> h2hip_evaluate_h_bn254, and coset by coset of the
+//                            2^k domain from coefficient-form columns (evaluate_h_parts -> h2hip_evaluate_h_parts_bn254)
 //
 // The graph builder is a faithful restatement (same deduplication by linear search, same operand ordering and
 // constant folding), so the flattened graph has the calculations the reference builds, in the same order.
@@ -253,6 +254,24 @@ struct EvaluateHInputs {
     std::vector<std::array<const std::vector<Fr>*, 3>> lookups;
 };
 
+// evaluate_h_parts' inputs: EvaluateHInputs with every column a polynomial of n coefficients -- pk.fixed_polys, pk.l0 / l_last /
+// l_active_row as polynomials, pk.permutation.polys, the product polynomials -- so neither the key nor the engine holds an extended coset
+struct EvaluateHPartsInputs {
+    const poly::EvaluationDomain* domain = nullptr;
+    std::vector<const std::vector<Fr>*> fixed_polys, advice_polys, instance_polys;
+    std::vector<Fr> challenges;
+    Fr y, beta, gamma, theta;
+    const std::vector<Fr>*l0_poly = nullptr, *l_last_poly = nullptr, *l_active_row_poly = nullptr;
+    std::vector<std::pair<uint32_t, uint32_t>> permutation_columns;
+    std::vector<const std::vector<Fr>*> permutation_polys;             // pk.permutation.polys
+    std::vector<const std::vector<Fr>*> permutation_product_polys;     // sets[i].permutation_product_poly
+    uint32_t cs_degree = 3;
+    uint32_t blinding_factors = 5;
+    std::vector<std::array<const std::vector<Fr>*, 3>> lookups;
+    uint32_t part_begin = 0, part_count = 0;  // the parts (cosets of the 2^k domain) to compute; 0, 0 = all 2^(extended_k - k)
+    bool divide_by_vanishing_poly = false;    // the last instance's call: the rows leave multiplied by domain->t_evaluations
+};
+
 // commit_permuted's compression (plonk/lookup/prover.rs:90-115) as two graphs, input side then table side: each expression added with
 // add_expression, then Horner(Constant(0), parts, Theta) -- Evaluator::create's evaluate_lc on a graph of its own (halo2hip.hpp
 // lookup_compress runs them)
@@ -389,6 +408,86 @@ class Evaluator {  // :182-189
             (void)h2hip_columns_pin(key.data(), key.size(), size);
         }
         engine_check(h2hip_evaluate_h_bn254(&desc, values[0].l), "h2hip_evaluate_h_bn254");
+    }
+
+    // the same one coset of the 2^k domain at a time (h2hip_evaluate_h_parts_bn254): rows of `values` outside the parts asked for are
+    // left as they are
+    void evaluate_h_parts(const EvaluateHPartsInputs& in, std::vector<Fr>& values) const {
+        const poly::EvaluationDomain& d = *in.domain;
+        const size_t n = (size_t)1 << d.k, size = d.extended_len();
+        auto need = [&](const std::vector<Fr>* v) {
+            if (!v || v->size() != n) throw std::logic_error("evaluate_h_parts: polynomial of the wrong length");
+            return v->data()->l;
+        };
+        if (values.size() != size || in.lookups.size() != lookups.size() || in.permutation_polys.size() != in.permutation_columns.size() ||
+            (in.divide_by_vanishing_poly && d.t_evaluations.size() != size / n))
+            throw std::logic_error("evaluate_h_parts: inconsistent inputs");
+        auto table = [&](const std::vector<const std::vector<Fr>*>& cols) {
+            std::vector<const uint64_t*> t;
+            for (auto* c : cols) t.push_back(need(c));
+            return t;
+        };
+        const auto fixed = table(in.fixed_polys), advice = table(in.advice_polys), instance = table(in.instance_polys);
+        const auto ppolys = table(in.permutation_polys), pprod = table(in.permutation_product_polys);
+        std::vector<uint32_t> pkind, pindex;
+        for (auto& c : in.permutation_columns) {
+            pkind.push_back(c.first);
+            pindex.push_back(c.second);
+        }
+        const FlatGraph cg = custom_gates.flatten();
+        std::vector<FlatGraph> lg;
+        std::vector<h2hip_graph> lg_abi;
+        std::vector<const uint64_t*> lprod, lpin, lptab;
+        for (size_t i = 0; i < lookups.size(); i++) {
+            lg.push_back(lookups[i].flatten());
+            lprod.push_back(need(in.lookups[i][0]));
+            lpin.push_back(need(in.lookups[i][1]));
+            lptab.push_back(need(in.lookups[i][2]));
+        }
+        for (auto& g : lg) lg_abi.push_back(g.abi());
+        const Fr zeta = Fr::zeta(), delta = Fr::delta();
+        h2hip_evalh_parts_desc desc;
+        std::memset(&desc, 0, sizeof(desc));
+        desc.k = d.k;
+        desc.extended_k = d.extended_k;
+        desc.extended_omega = d.extended_omega.l;
+        desc.g_coset = d.g_coset.l;
+        desc.g_coset_inv = d.g_coset_inv.l;
+        desc.n_fixed = (uint32_t)fixed.size();
+        desc.n_advice = (uint32_t)advice.size();
+        desc.n_instance = (uint32_t)instance.size();
+        desc.n_challenges = (uint32_t)in.challenges.size();
+        desc.fixed_polys = fixed.data();
+        desc.advice_polys = advice.data();
+        desc.instance_polys = instance.data();
+        desc.challenges = in.challenges.empty() ? nullptr : in.challenges[0].l;
+        desc.y = in.y.l;
+        desc.beta = in.beta.l;
+        desc.gamma = in.gamma.l;
+        desc.theta = in.theta.l;
+        desc.l0_poly = need(in.l0_poly);
+        desc.l_last_poly = need(in.l_last_poly);
+        desc.l_active_row_poly = need(in.l_active_row_poly);
+        desc.custom_gates = cg.abi();
+        desc.n_perm_sets = (uint32_t)pprod.size();
+        desc.n_perm_columns = (uint32_t)ppolys.size();
+        desc.chunk_len = in.cs_degree - 2;
+        desc.last_rotation = -(int32_t)(in.blinding_factors + 1);
+        desc.perm_product_polys = pprod.data();
+        desc.perm_column_kind = pkind.data();
+        desc.perm_column_index = pindex.data();
+        desc.perm_polys = ppolys.data();
+        desc.zeta = zeta.l;
+        desc.delta = delta.l;
+        desc.n_lookups = (uint32_t)lookups.size();
+        desc.lookup_graphs = lg_abi.data();
+        desc.lookup_product_polys = lprod.data();
+        desc.lookup_permuted_input_polys = lpin.data();
+        desc.lookup_permuted_table_polys = lptab.data();
+        desc.part_begin = in.part_begin;
+        desc.part_count = in.part_count;
+        desc.t_evaluations = in.divide_by_vanishing_poly ? d.t_evaluations[0].l : nullptr;
+        engine_check(h2hip_evaluate_h_parts_bn254(&desc, values[0].l), "h2hip_evaluate_h_parts_bn254");
     }
 
     // ProvingKey's Drop (patch 0006): release the device copies of the key's constant columns

@@ -110,6 +110,52 @@ pub struct h2hip_evalh_desc {
     pub lookup_permuted_table_polys: *const *const u64,
 }
 
+/// `h2hip_evalh_parts_desc`: `h2hip_evalh_desc` with every column a coefficient-form polynomial of 2^k elements -- the proving key's
+/// too -- followed by the range of parts (cosets of the 2^k domain) a call computes and the optional `t_evaluations`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct EvalhPartsDesc {
+    pub k: u32,
+    pub extended_k: u32,
+    pub extended_omega: *const u64,
+    pub g_coset: *const u64,
+    pub g_coset_inv: *const u64,
+    pub n_fixed: u32,
+    pub n_advice: u32,
+    pub n_instance: u32,
+    pub n_challenges: u32,
+    pub fixed_polys: *const *const u64,
+    pub advice_polys: *const *const u64,
+    pub instance_polys: *const *const u64,
+    pub challenges: *const u64,
+    pub y: *const u64,
+    pub beta: *const u64,
+    pub gamma: *const u64,
+    pub theta: *const u64,
+    pub l0_poly: *const u64,
+    pub l_last_poly: *const u64,
+    pub l_active_row_poly: *const u64,
+    pub custom_gates: h2hip_graph,
+    pub n_perm_sets: u32,
+    pub n_perm_columns: u32,
+    pub chunk_len: u32,
+    pub last_rotation: i32,
+    pub perm_product_polys: *const *const u64,
+    pub perm_column_kind: *const u32,
+    pub perm_column_index: *const u32,
+    pub perm_polys: *const *const u64,
+    pub zeta: *const u64,
+    pub delta: *const u64,
+    pub n_lookups: u32,
+    pub lookup_graphs: *const h2hip_graph,
+    pub lookup_product_polys: *const *const u64,
+    pub lookup_permuted_input_polys: *const *const u64,
+    pub lookup_permuted_table_polys: *const *const u64,
+    pub part_begin: u32,
+    pub part_count: u32,
+    pub t_evaluations: *const u64,
+}
+
 // ---- owning builder -------------------------------------------------------------------------------------------------
 /// A `GraphEvaluator` flattened into plain vectors.  halo2_proofs builds one per graph once per proving key; `view()`
 /// lends it to the engine for the duration of a call.
@@ -326,4 +372,139 @@ pub fn unpin_key_columns<F: 'static>(columns: &[&[F]]) {
     }
     let ptrs: Vec<*const u64> = columns.iter().map(|c| c.as_ptr() as *const u64).collect();
     unsafe { super::ffi::h2hip_columns_unpin(ptrs.as_ptr(), ptrs.len()) };
+}
+
+/// One circuit instance of `evaluate_h` evaluated one coset of the 2^k domain at a time: `EvalHInput` with every column a polynomial in
+/// coefficient form (2^k each), so that neither the proving key nor the engine holds an extended coset.
+pub struct EvalHPartsInput<'a, F> {
+    pub k: u32,
+    pub extended_k: u32,
+    pub extended_omega: F,
+    pub g_coset: F,
+    pub g_coset_inv: F,
+    /// pk.fixed_polys
+    pub fixed_polys: Vec<&'a [F]>,
+    pub advice_polys: Vec<&'a [F]>,
+    pub instance_polys: Vec<&'a [F]>,
+    pub challenges: &'a [F],
+    pub y: F,
+    pub beta: F,
+    pub gamma: F,
+    pub theta: F,
+    /// pk.l0 / l_last / l_active_row as polynomials
+    pub l0_poly: &'a [F],
+    pub l_last_poly: &'a [F],
+    pub l_active_row_poly: &'a [F],
+    pub custom_gates: &'a FlatGraph,
+    /// sets[i].permutation_product_poly; empty skips the permutation argument
+    pub perm_product_polys: Vec<&'a [F]>,
+    pub perm_columns: Vec<(u32, u32)>,
+    /// pk.permutation.polys[j]
+    pub perm_polys: Vec<&'a [F]>,
+    pub chunk_len: u32,
+    pub last_rotation: i32,
+    pub zeta: F,
+    pub delta: F,
+    pub lookup_graphs: &'a [FlatGraph],
+    pub lookup_product_polys: Vec<&'a [F]>,
+    pub lookup_permuted_input_polys: Vec<&'a [F]>,
+    pub lookup_permuted_table_polys: Vec<&'a [F]>,
+    /// the parts this call computes, `part_begin .. part_begin + part_count` of the 2^(extended_k - k); 0, 0 = all of them
+    pub part_begin: u32,
+    pub part_count: u32,
+    /// `EvaluationDomain::t_evaluations` on the call of the last circuit instance: `values` then leaves as
+    /// `divide_by_vanishing_poly(h)`; `None` otherwise
+    pub t_evaluations: Option<&'a [F]>,
+}
+
+/// Safe front of `h2hip_evaluate_h_parts_bn254`: checks the element type and every slice length, builds the pointer tables, calls the
+/// engine.  `values` (2^extended_k elements) is read and written on the rows of the requested parts only.  false: the engine declined,
+/// run the CPU body.
+pub fn try_evaluate_h_parts<F: 'static + Copy>(inp: &EvalHPartsInput<'_, F>, values: &mut [F]) -> bool {
+    if std::any::TypeId::of::<F>() != std::any::TypeId::of::<halo2curves::bn256::Fr>() || std::mem::size_of::<F>() != 32 {
+        return false;
+    }
+    if inp.extended_k < inp.k || inp.extended_k > 28 {
+        return false;
+    }
+    let n = 1usize << inp.k;
+    let en = 1usize << inp.extended_k;
+    let all_n = |v: &Vec<&[F]>| v.iter().all(|s| s.len() == n);
+    let n_lookups = inp.lookup_graphs.len();
+    if values.len() != en
+        || !all_n(&inp.fixed_polys)
+        || !all_n(&inp.advice_polys)
+        || !all_n(&inp.instance_polys)
+        || inp.l0_poly.len() != n
+        || inp.l_last_poly.len() != n
+        || inp.l_active_row_poly.len() != n
+        || !all_n(&inp.perm_product_polys)
+        || !all_n(&inp.perm_polys)
+        || inp.perm_polys.len() != inp.perm_columns.len()
+        || !all_n(&inp.lookup_product_polys)
+        || !all_n(&inp.lookup_permuted_input_polys)
+        || !all_n(&inp.lookup_permuted_table_polys)
+        || inp.lookup_product_polys.len() != n_lookups
+        || inp.lookup_permuted_input_polys.len() != n_lookups
+        || inp.lookup_permuted_table_polys.len() != n_lookups
+        || inp.t_evaluations.map_or(false, |t| t.len() != en / n)
+    {
+        return false;
+    }
+    let table = |v: &Vec<&[F]>| -> Vec<*const u64> { v.iter().map(|s| s.as_ptr() as *const u64).collect() };
+    let fixed = table(&inp.fixed_polys);
+    let advice = table(&inp.advice_polys);
+    let instance = table(&inp.instance_polys);
+    let perm_prod = table(&inp.perm_product_polys);
+    let perm_polys = table(&inp.perm_polys);
+    let lk_prod = table(&inp.lookup_product_polys);
+    let lk_in = table(&inp.lookup_permuted_input_polys);
+    let lk_tab = table(&inp.lookup_permuted_table_polys);
+    let kinds: Vec<u32> = inp.perm_columns.iter().map(|c| c.0).collect();
+    let indices: Vec<u32> = inp.perm_columns.iter().map(|c| c.1).collect();
+    let lookup_views: Vec<h2hip_graph> = inp.lookup_graphs.iter().map(|g| g.view()).collect();
+    let p = |x: &F| x as *const F as *const u64;
+    let desc = EvalhPartsDesc {
+        k: inp.k,
+        extended_k: inp.extended_k,
+        extended_omega: p(&inp.extended_omega),
+        g_coset: p(&inp.g_coset),
+        g_coset_inv: p(&inp.g_coset_inv),
+        n_fixed: fixed.len() as u32,
+        n_advice: advice.len() as u32,
+        n_instance: instance.len() as u32,
+        n_challenges: inp.challenges.len() as u32,
+        fixed_polys: fixed.as_ptr(),
+        advice_polys: advice.as_ptr(),
+        instance_polys: instance.as_ptr(),
+        challenges: inp.challenges.as_ptr() as *const u64,
+        y: p(&inp.y),
+        beta: p(&inp.beta),
+        gamma: p(&inp.gamma),
+        theta: p(&inp.theta),
+        l0_poly: inp.l0_poly.as_ptr() as *const u64,
+        l_last_poly: inp.l_last_poly.as_ptr() as *const u64,
+        l_active_row_poly: inp.l_active_row_poly.as_ptr() as *const u64,
+        custom_gates: inp.custom_gates.view(),
+        n_perm_sets: perm_prod.len() as u32,
+        n_perm_columns: perm_polys.len() as u32,
+        chunk_len: inp.chunk_len,
+        last_rotation: inp.last_rotation,
+        perm_product_polys: perm_prod.as_ptr(),
+        perm_column_kind: kinds.as_ptr(),
+        perm_column_index: indices.as_ptr(),
+        perm_polys: perm_polys.as_ptr(),
+        zeta: p(&inp.zeta),
+        delta: p(&inp.delta),
+        n_lookups: n_lookups as u32,
+        lookup_graphs: lookup_views.as_ptr(),
+        lookup_product_polys: lk_prod.as_ptr(),
+        lookup_permuted_input_polys: lk_in.as_ptr(),
+        lookup_permuted_table_polys: lk_tab.as_ptr(),
+        part_begin: inp.part_begin,
+        part_count: inp.part_count,
+        t_evaluations: inp.t_evaluations.map_or(std::ptr::null(), |t| t.as_ptr() as *const u64),
+    };
+    let rc: c_int = unsafe { super::ffi::h2hip_evaluate_h_parts_bn254(&desc as *const EvalhPartsDesc, values.as_mut_ptr() as *mut u64) };
+    rc == 0
 }

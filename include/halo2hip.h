@@ -342,6 +342,57 @@ int h2hip_evaluate_h_bn254(const h2hip_evalh_desc* desc, uint64_t* values);
  * the call does not wait for them. */
 int h2hip_evaluate_h_bn254_device(const h2hip_evalh_desc* desc, void* d_values, void* stream);
 
+/* evaluate_h one coset of the 2^k domain at a time.  With P = 2^(extended_k - k), extended row j * P + p lies at g_p * omega^j with
+ * g_p = g_coset * extended_omega^p and omega = extended_omega^P, so the rows of part p are the 2^k-point transform of f(g_p X) and are
+ * closed under every rotation the constraints use.  Every column is given as a coefficient-form polynomial of 2^k elements -- the key's
+ * too: pk.fixed_polys, pk.l0 / l_last / l_active_row as polynomials, pk.permutation.polys -- and the engine forms one part's cosets at a
+ * time, so it holds columns of 2^k elements where the full form holds columns of 2^extended_k, and a proving key need not keep its
+ * extended cosets at all.  The result is the full form's, limb for limb.  Fields up to lookup_permuted_table_polys mirror
+ * h2hip_evalh_desc. */
+typedef struct h2hip_evalh_parts_desc {
+    uint32_t k, extended_k;
+    const uint64_t *extended_omega, *g_coset, *g_coset_inv;
+    uint32_t n_fixed, n_advice, n_instance, n_challenges;
+    const uint64_t* const* fixed_polys;      /* every column below: coefficient form, 2^k elements */
+    const uint64_t* const* advice_polys;
+    const uint64_t* const* instance_polys;
+    const uint64_t* challenges;              /* n_challenges x 4 */
+    const uint64_t *y, *beta, *gamma, *theta;
+    const uint64_t *l0_poly, *l_last_poly, *l_active_row_poly;
+    h2hip_graph custom_gates;
+    uint32_t n_perm_sets, n_perm_columns, chunk_len;
+    int32_t last_rotation;
+    const uint64_t* const* perm_product_polys; /* sets[i].permutation_product_poly */
+    const uint32_t* perm_column_kind;
+    const uint32_t* perm_column_index;
+    const uint64_t* const* perm_polys;       /* pk.permutation.polys[j] */
+    const uint64_t *zeta, *delta;
+    uint32_t n_lookups;
+    const h2hip_graph* lookup_graphs;
+    const uint64_t* const* lookup_product_polys;
+    const uint64_t* const* lookup_permuted_input_polys;
+    const uint64_t* const* lookup_permuted_table_polys;
+    /* the parts this call computes: part_begin .. part_begin + part_count - 1 of the P; 0, 0 = all of them.  Rows of `values` that
+     * belong to other parts are neither read nor written, so two devices, or two calls, can split one h(X). */
+    uint32_t part_begin, part_count;
+    /* NULL, or the P elements of EvaluationDomain::t_evaluations: part p's rows then leave multiplied by t_evaluations[p], which makes
+     * the result divide_by_vanishing_poly(h) (poly/domain.rs:307-326).  Set it on the call of the last circuit instance only. */
+    const uint64_t* t_evaluations;
+} h2hip_evalh_parts_desc;
+
+/* values: 2^extended_k elements, in/out, host memory, in the reference's row order; every column pointer in desc is host memory.  Each
+ * column is uploaded once per call (2^k elements), not once per part. */
+int h2hip_evaluate_h_parts_bn254(const h2hip_evalh_parts_desc* desc, uint64_t* values);
+/* Device-resident form: the columns and d_values are device pointers, no input is modified; kernels are queued on `stream` only and the
+ * call does not wait for them. */
+int h2hip_evaluate_h_parts_bn254_device(const h2hip_evalh_parts_desc* desc, void* d_values, void* stream);
+/* HBM the engine itself allocates for the columns of one evaluate_h call and, in the host-pointer forms, its copy of `values` (the
+ * metadata and the slot workspace of programs with more than 256 live values come on top).  parts_form / device_form select among the
+ * four entry points above.  Host only: needs no device. */
+int h2hip_evaluate_h_workspace_bytes(uint32_t k, uint32_t extended_k, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance,
+                                     uint32_t n_perm_sets, uint32_t n_perm_columns, uint32_t n_lookups, int parts_form, int device_form,
+                                     size_t* bytes);
+
 /* ---- grand products: permutation::Argument::commit (plonk/permutation/prover.rs:96-166) and lookup::Permuted::commit_product
  * (plonk/lookup/prover.rs:194-249) -- the z columns create_proof builds between the advice commits and evaluate_h ----------------
  * n = 2^k, b = blinding_factors, u = n - b - 1; every column is 2^k Fr elements in Lagrange form.
@@ -567,7 +618,7 @@ uint32_t h2hip_get_msm_window(size_t n);
 uint32_t h2hip_get_msm_window_fixed_base(size_t n);
 /* Per-stage HIP-event timers recorded on the stream each kernel group is launched on.
  * Stages: "ntt", "msm_total", "msm_digits", "msm_sort", "msm_accum" (over-full buckets included), "msm_reduce", "g_to_lagrange", "kzg_setup",
- * "evalh_cosets", "evalh_gates", "evalh_perm", "evalh_lookups", "products", "opening_eval", "opening_combine", "lookup_compress",
+ * "evalh_cosets", "evalh_gates", "evalh_perm", "evalh_lookups", "evalh_part_scale" (inside "evalh_cosets") and "evalh_part_io" (the parts form), "products", "opening_eval", "opening_combine", "lookup_compress",
  * "lookup_permute", "check_gates", "check_permutation", "check_lookups" (each check: its kernels, without the delivery of counts / rows),
  * "g1_decompress", "g1_validate", "fr_from_repr" (each with its failure count; the _device forms too), "g1_compress", "fr_to_repr" (host forms). */
 /* on = 1: every stage (each event record costs the stream ~10 us of gap); on = 2: only the dominant kernel ("msm_accum"),

@@ -93,6 +93,9 @@ int h2hip_debug_evalh_codegen_source(const h2hip_graph* g, char* buf, size_t cap
 int h2hip_debug_evalh_codegen_stats(uint64_t out[5]);
 /* evaluate_h: compile a graph as the engine would and report the program's size; needs no GPU */
 int h2hip_debug_evalh_compile_stats(const h2hip_graph* g, uint32_t* n_ops, uint32_t* n_slots);
+/* the split of a domain's two-level power table (omega^e = lo[e & (2^lo_bits - 1)] * hi[e >> lo_bits]) that evaluate_h's permutation
+ * kernel walks: rows at or beyond 2^lo_bits take the second factor.  Builds the table when the domain has none yet; needs a GPU. */
+int h2hip_debug_evalh_power_table_bits(const uint64_t omega[4], uint32_t log_n, uint32_t* lo_bits);
 /* opening (evaluations and combine / divide): force the tile shape, consecutive rows per thread (power of two <= 64) and threads per
  * tile (power of two <= 256), so that small inputs span many tiles; 0 restores the size-based default.  Needs no GPU. */
 int h2hip_debug_set_opening_tile(uint32_t rows_per_thread, uint32_t threads_per_tile);

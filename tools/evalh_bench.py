@@ -5,6 +5,7 @@ gate polynomials over `--advice` advice and `--fixed` fixed columns with rotatio
 `--perm` columns, `--lookups` lookups.  Columns come from the engine's on-device generator.
 
   python tools/evalh_bench.py --k 18 [--check-k 12]     (run on the GPU box)
+  python tools/evalh_bench.py --k 18 --parts            (the parts form beside the full form)
 """
 import argparse
 import ctypes
@@ -222,6 +223,155 @@ def bench(args):
     return out
 
 
+def bench_parts(args):
+    """--parts: the parts form (h2hip_evaluate_h_parts_bn254[_device], one coset of the 2^k domain at a time from coefficient-form
+    columns) beside the full form on the same polynomials: device-resident time (median of --iters after a warm-up call) with the
+    per-stage times, host-pointer time with the bytes each form sends over PCIe, and the HBM the engine allocates for each beside what
+    h2hip_evaluate_h_workspace_bytes predicts.  The parts form runs first: the engine's arena only grows."""
+    import importlib
+    import torch
+    h2 = load_pkg()
+    ev = importlib.import_module("halo2_pse_amd.evaluation")
+    from oracle import oracle as orc
+    orc.build()
+    L = h2.lib()
+    evaluator = build_system(ev, args, np.random.default_rng(1))
+    k, ek = args.k, args.k + 2
+    n, size, chunk_len = 1 << k, 1 << (args.k + 2), 2
+    n_sets = -(-args.perm // chunk_len)
+    d, t_eval = orc.domain_new(4, k)
+    h2.init()
+    gen = lambda s: h2.gen_scalars_device(1000 + s, n)  # noqa: E731
+    fe1 = lambda s: orc.gen_scalars(s, 1)[0]  # noqa: E731
+    polys = {"fixed_polys": [gen(10 + i) for i in range(args.fixed)], "advice_polys": [gen(100 + i) for i in range(args.advice)], "instance_polys": [],
+             "perm_product_polys": [gen(200 + i) for i in range(n_sets)], "perm_polys": [gen(300 + i) for i in range(args.perm)],
+             "l0_poly": gen(1), "l_last_poly": gen(2), "l_active_row_poly": gen(3),
+             "lookups": [[gen(400 + 3 * i + t) for t in range(3)] for i in range(args.lookups)]}
+    v0 = h2.gen_scalars_device(1999, size)
+    torch.cuda.synchronize()
+    scal = {"extended_omega": d.fe("extended_omega"), "g_coset": d.fe("g_coset"), "g_coset_inv": d.fe("g_coset_inv"),
+            "zeta": orc.constant(orc.FR, 5), "delta": orc.fe_from_int(orc.FR, pow(7, 1 << 28, R_MOD)),
+            "y": fe1(1), "beta": fe1(2), "gamma": fe1(3), "theta": fe1(4)}
+    common = {"k": k, "extended_k": ek, **scal, "challenges": np.zeros((0, 4), dtype=np.uint64), "chunk_len": chunk_len, "last_rotation": -6,
+              "perm_column_kind": np.zeros(args.perm, dtype=np.uint32), "perm_column_index": (np.arange(args.perm) % args.advice).astype(np.uint32)}
+    renamed = {"fixed_polys": "fixed_cosets", "perm_product_polys": "perm_product_cosets", "perm_polys": "perm_cosets", "l0_poly": "l0",
+               "l_last_poly": "l_last", "l_active_row_poly": "l_active_row", "advice_polys": "advice_polys", "instance_polys": "instance_polys"}
+    host = lambda t: h2.to_numpy_u64(t)  # noqa: E731
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    keep = []
+
+    def table(ts):
+        arr = (ctypes.c_void_p * max(1, len(ts)))(*[t.data_ptr() for t in ts])
+        keep.append(arr)
+        return ctypes.addressof(arr)
+
+    def describe(form, cols, on_device):
+        """a description of `cols` (tensors) for the parts or the full form, with host arrays or device addresses"""
+        stub = np.zeros((1, 4), dtype=np.uint64)
+        conv = (lambda t: stub) if on_device else host
+        case = dict(common)
+        for name, v in cols.items():
+            if name != "lookups":
+                case[name] = [conv(t) for t in v] if isinstance(v, list) else conv(v)
+        case["lookups"] = [tuple(conv(t) for t in l) for l in cols["lookups"]]
+        hd = evaluator.describe_parts(case) if form == "parts" else evaluator.describe(case)
+        if on_device:
+            for name, v in cols.items():
+                if name != "lookups":
+                    setattr(hd.desc, name, table(v) if isinstance(v, list) else v.data_ptr())
+            for t, name in enumerate(("lookup_product_polys", "lookup_permuted_input_polys", "lookup_permuted_table_polys")):
+                setattr(hd.desc, name, table([l[t] for l in cols["lookups"]]))
+        return hd
+
+    def measure(form, cols):
+        res = {}
+        fn_dev = L.h2hip_evaluate_h_parts_bn254_device if form == "parts" else L.h2hip_evaluate_h_bn254_device
+        fn_host = L.h2hip_evaluate_h_parts_bn254 if form == "parts" else L.h2hip_evaluate_h_bn254
+        hd = describe(form, cols, True)
+        d_values = v0.clone()
+        torch.cuda.synchronize()
+        free0 = torch.cuda.mem_get_info()[0]
+
+        def call():
+            assert fn_dev(hd.byref(), ctypes.c_void_p(d_values.data_ptr()), stream) == 0, L.h2hip_last_error()
+
+        L.h2hip_debug_set_evalh_codegen(ctypes.c_int(2), ctypes.c_uint32(0))
+        call()  # warm-up: tables, arena, the generated kernels compiled inline
+        torch.cuda.synchronize()
+        res["engine_hbm_MiB_device_form"] = (free0 - torch.cuda.mem_get_info()[0]) / 2**20
+        d_values.copy_(v0)
+        call()
+        torch.cuda.synchronize()
+        result = d_values.clone()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ts = []
+        for _ in range(args.iters):
+            e0.record()
+            call()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        res["gpu_ms"] = float(np.median(ts))
+        h2.profile_enable(True)
+        h2.profile_reset()
+        for _ in range(3):
+            call()
+        torch.cuda.synchronize()
+        h2.profile_enable(False)
+        res["stage_ms"] = {}
+        for name in ("evalh_cosets", "evalh_part_scale", "ntt", "evalh_part_io", "evalh_gates", "evalh_perm", "evalh_lookups"):
+            tot, cnt = h2.profile_get(name)
+            res["stage_ms"][name] = tot / 3 if cnt else None  # per call: a stage runs once per part in the parts form
+        # host pointers: what a patched prover's Vec<F>s cost, PCIe included
+        hh = describe(form, cols, False)
+        vals = host(v0).copy()
+
+        def host_call():
+            np.copyto(vals, host(v0))
+            t0 = time.perf_counter()
+            assert fn_host(hh.byref(), vals.ctypes.data_as(ctypes.c_void_p)) == 0, L.h2hip_last_error()
+            return (time.perf_counter() - t0) * 1e3
+
+        free1 = torch.cuda.mem_get_info()[0]
+        host_call()
+        res["engine_hbm_MiB_host_form_on_top"] = (free1 - torch.cuda.mem_get_info()[0]) / 2**20
+        res["host_ms"] = float(np.median([host_call() for _ in range(5)]))
+        res["host_matches_device"] = bool(np.array_equal(vals, host(result)))
+        n_small = args.advice + 3 * args.lookups
+        n_key = args.fixed + args.perm + 3 + n_sets
+        up = (n_key + n_small) * (32 << k) if form == "parts" else n_key * (32 << ek) + n_small * (32 << k)
+        res["pcie_MiB"] = {"up_columns": up / 2**20, "values_each_way": (32 << ek) / 2**20}
+        q = lambda dev: ev.evaluate_h_workspace_bytes(k, ek, args.fixed, args.advice, 0, n_sets, args.perm, args.lookups, form == "parts", dev)  # noqa: E731
+        res["workspace_bytes_MiB"] = {"device_form": q(True) / 2**20, "host_form": q(False) / 2**20}
+        L.h2hip_debug_set_evalh_codegen(ctypes.c_int(1), ctypes.c_uint32(0))
+        return res, result
+
+    out = {"k": k, "extended_k": ek, "gates": args.gates, "advice": args.advice, "fixed": args.fixed, "perm_columns": args.perm, "perm_sets": n_sets,
+           "lookups": args.lookups, "iters": args.iters}
+    out["parts"], got = measure("parts", polys)
+    # the full form's columns: the extended cosets of the same polynomials, formed by the engine
+    cosets = {}
+    for name, v in polys.items():
+        if name in ("advice_polys", "instance_polys", "lookups"):
+            cosets[name] = v
+            continue
+        ts = v if isinstance(v, list) else [v]
+        ext = []
+        for t in ts:
+            e = torch.zeros((size,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+            e[:n] = t
+            ext.append(e)
+        if ext:
+            h2.coeff_to_extended_batch_device(ext, k, ek, d.fe("extended_omega"), d.fe("g_coset"), d.fe("g_coset_inv"))
+        cosets[renamed[name]] = ext if isinstance(v, list) else ext[0]
+    torch.cuda.synchronize()
+    out["full"], want = measure("full", cosets)
+    out["parts_equal_full"] = bool(torch.equal(got, want))
+    assert out["parts_equal_full"], "the parts form differs from the full form"
+    out["parts_over_full_gpu"] = out["parts"]["gpu_ms"] / out["full"]["gpu_ms"]
+    return out
+
+
 def default_args(**over):
     ns = argparse.Namespace(k=18, check_k=12, gates=24, advice=12, fixed=10, perm=9, lookups=2, iters=5, cpu=False, host_k=16)
     for key, v in over.items():
@@ -241,8 +391,9 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--cpu", action="store_true", help="time the oracle at --k too (single thread)")
     ap.add_argument("--host-k", type=int, default=16, help="also time the host-pointer call at this k, with and without the key's columns pinned (0 = skip)")
+    ap.add_argument("--parts", action="store_true", help="time the parts form beside the full form at --k instead (device and host pointers, HBM)")
     args = ap.parse_args()
-    print(json.dumps(bench(args)))
+    print(json.dumps(bench_parts(args) if args.parts else bench(args)))
 
 
 if __name__ == "__main__":
