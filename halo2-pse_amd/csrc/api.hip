@@ -1,5 +1,13 @@
-// api.hip -- the extern "C" surface of libhalo2hip.so (include/halo2hip.h), the device
-// context, workspace buffers and HIP-event stage timers.
+// api.hip -- the engine of libhalo2hip.so: the device contexts, their locks, worker and copier threads, workspace buffers and
+// HIP-event stage timers, and the entry points whose host logic is the engine's own.
+//
+// The rule: a stage file owns the extern "C" entry points and the h2hip_debug_* hooks of its stage (msm.hip, ntt.hip, evalh.hip,
+// ecfft.hip, setup.hip, gen.hip, product.hip, opening.hip, lookup.hip, keygen.hip, check.hip, serde.hip).  This file keeps init /
+// shutdown / errors / profile, the device memory helpers, the MSM's host and device forms (sharding, fold, RCCL gather), the pins
+// (bases, lazy, columns), the NTT / domain family (batch_over_devices, the host pipeline), h2hip_g1_fold / _batch_normalize /
+// _to_affine, and the hooks that set its own statics (h2hip_debug_set_ntt_host_batch, _set_lazy_pin, _set_table_records,
+// _rccl_gather_selftest).  That is also all that runs in the stub build: this file compiled alone, as plain C++ against
+// tests/cpp/hipstub, and linked with tests/cpp/engine_stubs.cpp, which stands in for what this file calls in the stage files.
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 #include <stdarg.h>
@@ -1744,150 +1752,97 @@ int h2hip_g1_to_affine(const uint64_t xyz[12], uint64_t xy[8]) {
     return 0;
 }
 
-int h2hip_ntt_bn254_fr_device(void* d_a, const uint64_t omega[4], uint32_t log_n, void* stream) {
-    if (!d_a || !omega) {
-        set_error("ntt: null argument");
-        return H2HIP_EINVAL;
-    }
-    if (check_fr(omega, "omega")) return H2HIP_EINVAL;
-    Entry en("h2hip_ntt_bn254_fr_device", d_a);
-    if (en.rc) return en.rc;
-    hipStream_t s = (hipStream_t)stream;
-    return ntt_device(en.c, (Fe*)d_a, fe_from_u64x4(omega), log_n, nullptr, s);
+// ---- the NTT / domain family ---------------------------------------------------------------------------------------------------------
+// Four operations (ntt, ifft, coeff_to_extended, extended_to_coeff) in up to four forms each: _device, host, _batch_device and _batch.
+// What an operation accepts is written once, in its parse_* below.  An entry point says what is its form's own (Form: its pointers, how its
+// rejections are worded), has the operation parsed into a DomainOp and hands that to its form's runner: ntt_device under an Entry,
+// ntt_host, batch_over_devices or ntt_host_batch.
+// One struct for both kinds of form, because a batch form's column checks fall between the null / size checks and the check_fr list.
+struct Form {
+    // the single forms:
+    bool ptrs;          // the form's own pointers are there
+    const char* msg;    // text for a null pointer, a bad size or k > extended_k; nullptr (the batch forms): H2HIP_EINVAL without a text
+    bool size;          // log_n > 28 is rejected under `msg` (the _device forms of ntt and ifft leave that to ntt_device)
+    // the batch forms: the name their column checks speak of, and the tables of `count` columns (in == out: in place)
+    const char* batch;
+    const void* const* in;
+    const void* const* out;
+    size_t count;
+};
+static Form single(bool ptrs, const char* msg, bool size = true) { return {ptrs, msg, size, nullptr, nullptr, nullptr, 0}; }
+static Form batch_host(const char* name, const uint64_t* const* in, uint64_t* const* out, size_t count) {  // host columns
+    return {true, nullptr, false, name, (const void* const*)in, (const void* const*)out, count};
+}
+static Form batch_device(const char* name, void* const* d_a, size_t count) {  // device columns, in place
+    return {true, nullptr, false, name, (const void* const*)d_a, (const void* const*)d_a, count};
 }
 
-int h2hip_ntt_bn254_fr(uint64_t* a, const uint64_t omega[4], uint32_t log_n) {
-    if (!a || !omega || log_n > 28) {
-        set_error("ntt: bad argument");
+// the checks that come before an operation's check_fr list; args_ok: its scalars are there and k <= extended_k
+static int form_check(const Form& f, bool args_ok, uint32_t log_n) {
+    if (!f.ptrs || !args_ok || (f.size && log_n > 28)) {
+        if (f.msg) set_error("%s", f.msg);
         return H2HIP_EINVAL;
     }
-    if (check_fr(omega, "omega")) return H2HIP_EINVAL;
-    return ntt_host(a, fe_from_u64x4(omega), log_n, nullptr, nullptr, 0);
-}
-
-int h2hip_ifft_bn254_fr_device(void* d_a, const uint64_t omega_inv[4], uint32_t log_n, const uint64_t divisor[4], void* stream) {
-    if (!d_a || !omega_inv || !divisor) {
-        set_error("ifft: null argument");
+    if (!f.batch) return 0;
+    if (log_n > 28 || (f.count && (!f.in || !f.out))) {
+        set_error("%s: bad argument", f.batch);
         return H2HIP_EINVAL;
     }
-    if (check_fr(omega_inv, "omega_inv") || check_fr(divisor, "divisor")) return H2HIP_EINVAL;
-    Entry en("h2hip_ifft_bn254_fr_device", d_a);
-    if (en.rc) return en.rc;
-    hipStream_t s = (hipStream_t)stream;
-    NttScale sc = NttScale::inverse(fe_from_u64x4(divisor));
-    return ntt_device(en.c, (Fe*)d_a, fe_from_u64x4(omega_inv), log_n, &sc, s);
-}
-
-int h2hip_ifft_bn254_fr(uint64_t* a, const uint64_t omega_inv[4], uint32_t log_n, const uint64_t divisor[4]) {
-    if (!a || !omega_inv || !divisor || log_n > 28) {
-        set_error("ifft: bad argument");
-        return H2HIP_EINVAL;
-    }
-    if (check_fr(omega_inv, "omega_inv") || check_fr(divisor, "divisor")) return H2HIP_EINVAL;
-    NttScale sc = NttScale::inverse(fe_from_u64x4(divisor));
-    return ntt_host(a, fe_from_u64x4(omega_inv), log_n, &sc, nullptr, 0);
-}
-
-int h2hip_coeff_to_extended_bn254_fr_device(void* d_a, uint32_t k, uint32_t extended_k, const uint64_t extended_omega[4],
-                                            const uint64_t g_coset[4], const uint64_t g_coset_inv[4], void* stream) {
-    if (!d_a || !extended_omega || !g_coset || !g_coset_inv || k > extended_k || extended_k > 28) {
-        set_error("coeff_to_extended: bad argument");
-        return H2HIP_EINVAL;
-    }
-    if (check_fr(extended_omega, "extended_omega") || check_fr(g_coset, "g_coset") || check_fr(g_coset_inv, "g_coset_inv")) return H2HIP_EINVAL;
-    Entry en("h2hip_coeff_to_extended_bn254_fr_device", d_a);
-    if (en.rc) return en.rc;
-    hipStream_t s = (hipStream_t)stream;
-    NttScale sc = NttScale::into_coset(fe_from_u64x4(g_coset), fe_from_u64x4(g_coset_inv), 1ull << k);
-    return ntt_device(en.c, (Fe*)d_a, fe_from_u64x4(extended_omega), extended_k, &sc, s);
-}
-
-int h2hip_coeff_to_extended_bn254_fr(const uint64_t* a, uint32_t k, uint64_t* out, uint32_t extended_k,
-                                     const uint64_t extended_omega[4], const uint64_t g_coset[4], const uint64_t g_coset_inv[4]) {
-    if (!a || !out || !extended_omega || !g_coset || !g_coset_inv || k > extended_k || extended_k > 28) {
-        set_error("coeff_to_extended: bad argument");
-        return H2HIP_EINVAL;
-    }
-    if (check_fr(extended_omega, "extended_omega") || check_fr(g_coset, "g_coset") || check_fr(g_coset_inv, "g_coset_inv")) return H2HIP_EINVAL;
-    NttScale sc = NttScale::into_coset(fe_from_u64x4(g_coset), fe_from_u64x4(g_coset_inv), 1ull << k);
-    return ntt_host(out, fe_from_u64x4(extended_omega), extended_k, &sc, a, (size_t)1 << k);
-}
-
-int h2hip_extended_to_coeff_bn254_fr_device(void* d_a, uint32_t extended_k, const uint64_t extended_omega_inv[4],
-                                            const uint64_t extended_ifft_divisor[4], const uint64_t g_coset[4],
-                                            const uint64_t g_coset_inv[4], void* stream) {
-    if (!d_a || !extended_omega_inv || !extended_ifft_divisor || !g_coset || !g_coset_inv || extended_k > 28) {
-        set_error("extended_to_coeff: bad argument");
-        return H2HIP_EINVAL;
-    }
-    if (check_fr(extended_omega_inv, "extended_omega_inv") || check_fr(extended_ifft_divisor, "extended_ifft_divisor") ||
-        check_fr(g_coset, "g_coset") || check_fr(g_coset_inv, "g_coset_inv"))
-        return H2HIP_EINVAL;
-    Entry en("h2hip_extended_to_coeff_bn254_fr_device", d_a);
-    if (en.rc) return en.rc;
-    hipStream_t s = (hipStream_t)stream;
-    NttScale sc = NttScale::out_of_coset(fe_from_u64x4(extended_ifft_divisor), fe_from_u64x4(g_coset), fe_from_u64x4(g_coset_inv));
-    return ntt_device(en.c, (Fe*)d_a, fe_from_u64x4(extended_omega_inv), extended_k, &sc, s);
-}
-
-int h2hip_extended_to_coeff_bn254_fr(uint64_t* a, uint32_t extended_k, const uint64_t extended_omega_inv[4],
-                                     const uint64_t extended_ifft_divisor[4], const uint64_t g_coset[4], const uint64_t g_coset_inv[4]) {
-    if (!a || !extended_omega_inv || !extended_ifft_divisor || !g_coset || !g_coset_inv || extended_k > 28) {
-        set_error("extended_to_coeff: bad argument");
-        return H2HIP_EINVAL;
-    }
-    if (check_fr(extended_omega_inv, "extended_omega_inv") || check_fr(extended_ifft_divisor, "extended_ifft_divisor") ||
-        check_fr(g_coset, "g_coset") || check_fr(g_coset_inv, "g_coset_inv"))
-        return H2HIP_EINVAL;
-    NttScale sc = NttScale::out_of_coset(fe_from_u64x4(extended_ifft_divisor), fe_from_u64x4(g_coset), fe_from_u64x4(g_coset_inv));
-    return ntt_host(a, fe_from_u64x4(extended_omega_inv), extended_k, &sc, nullptr, 0);
-}
-
-int h2hip_divide_by_vanishing_poly_bn254_fr_device(void* d_a, uint32_t extended_k, const uint64_t* t_evaluations, uint32_t t_len, void* stream) {
-    if (!d_a || !t_evaluations || extended_k > 28 || t_len == 0) {
-        set_error("divide_by_vanishing_poly: bad argument");
-        return H2HIP_EINVAL;
-    }
-    for (uint32_t i = 0; i < t_len; i++)
-        if (check_fr(t_evaluations + 4 * i, "t_evaluations[i]")) return H2HIP_EINVAL;
-    Entry en("h2hip_divide_by_vanishing_poly_bn254_fr_device", d_a);
-    if (en.rc) return en.rc;
-    return scale_periodic_device(en.c, (Fe*)d_a, 1ull << extended_k, t_evaluations, t_len, (hipStream_t)stream);
-}
-
-int h2hip_divide_by_vanishing_poly_bn254_fr(uint64_t* a, uint32_t extended_k, const uint64_t* t_evaluations, uint32_t t_len) {
-    if (!a || !t_evaluations || extended_k > 28 || t_len == 0) {
-        set_error("divide_by_vanishing_poly: bad argument");
-        return H2HIP_EINVAL;
-    }
-    for (uint32_t i = 0; i < t_len; i++)
-        if (check_fr(t_evaluations + 4 * i, "t_evaluations[i]")) return H2HIP_EINVAL;
-    Entry en("h2hip_divide_by_vanishing_poly_bn254_fr");
-    if (en.rc) return en.rc;
-    Ctx* c = en.c;
-    size_t bytes = sizeof(Fe) << extended_k;
-    int rc = c->ntt_io.ensure(bytes);
-    if (rc) return rc;
-    H2_CHECK(hipMemcpyAsync(c->ntt_io.p, a, bytes, hipMemcpyHostToDevice, c->stream));
-    rc = scale_periodic_device(c, (Fe*)c->ntt_io.p, 1ull << extended_k, t_evaluations, t_len, c->stream);
-    if (rc) return rc;
-    H2_CHECK(hipMemcpyAsync(a, c->ntt_io.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    H2_CHECK(hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < f.count; i++)
+        if (!f.in[i] || !f.out[i]) {
+            set_error("%s: null column %zu", f.batch, i);
+            return H2HIP_EINVAL;
+        }
     return 0;
 }
 
-// ---- batched device-resident transforms: `count` columns of the same size, one launch per NTT pass
-static int batch_args_ok(void* const* d_a, size_t count, uint32_t log_n, const char* what) {
-    if (log_n > 28 || (count && !d_a)) {
-        set_error("%s: bad argument", what);
-        return 0;
-    }
-    for (size_t i = 0; i < count; i++)
-        if (!d_a[i]) {
-            set_error("%s: null column %zu", what, i);
-            return 0;
-        }
-    return 1;
+struct DomainOp {  // a parsed call: the transform's root and size, log2 of the elements read per column, the fused scaling if any
+    Fe omega;
+    uint32_t log_n, in_log;
+    bool scaled;
+    NttScale scale;
+    const NttScale* sc() const { return scaled ? &scale : nullptr; }
+    size_t in_elems() const { return (size_t)1 << in_log; }  // for the host forms, whose sizes have been checked
+};
+
+static int parse_ntt(const Form& f, const uint64_t* omega, uint32_t log_n, DomainOp* op) {
+    if (int rc = form_check(f, omega, log_n)) return rc;
+    if (check_fr(omega, "omega")) return H2HIP_EINVAL;
+    *op = {fe_from_u64x4(omega), log_n, log_n, false, NttScale()};
+    return 0;
+}
+
+static int parse_ifft(const Form& f, const uint64_t* omega_inv, uint32_t log_n, const uint64_t* divisor, DomainOp* op) {
+    if (int rc = form_check(f, omega_inv && divisor, log_n)) return rc;
+    if (check_fr(omega_inv, "omega_inv") || check_fr(divisor, "divisor")) return H2HIP_EINVAL;
+    *op = {fe_from_u64x4(omega_inv), log_n, log_n, true, NttScale::inverse(fe_from_u64x4(divisor))};
+    return 0;
+}
+
+static int parse_coeff_to_extended(const Form& f, uint32_t k, uint32_t extended_k, const uint64_t* extended_omega, const uint64_t* g_coset,
+                                   const uint64_t* g_coset_inv, DomainOp* op) {
+    if (int rc = form_check(f, extended_omega && g_coset && g_coset_inv && k <= extended_k, extended_k)) return rc;
+    if (check_fr(extended_omega, "extended_omega") || check_fr(g_coset, "g_coset") || check_fr(g_coset_inv, "g_coset_inv")) return H2HIP_EINVAL;
+    *op = {fe_from_u64x4(extended_omega), extended_k, k, true, NttScale::into_coset(fe_from_u64x4(g_coset), fe_from_u64x4(g_coset_inv), 1ull << k)};
+    return 0;
+}
+
+static int parse_extended_to_coeff(const Form& f, uint32_t extended_k, const uint64_t* extended_omega_inv, const uint64_t* extended_ifft_divisor,
+                                   const uint64_t* g_coset, const uint64_t* g_coset_inv, DomainOp* op) {
+    if (int rc = form_check(f, extended_omega_inv && extended_ifft_divisor && g_coset && g_coset_inv, extended_k)) return rc;
+    if (check_fr(extended_omega_inv, "extended_omega_inv") || check_fr(extended_ifft_divisor, "extended_ifft_divisor") ||
+        check_fr(g_coset, "g_coset") || check_fr(g_coset_inv, "g_coset_inv"))
+        return H2HIP_EINVAL;
+    *op = {fe_from_u64x4(extended_omega_inv), extended_k, extended_k, true,
+           NttScale::out_of_coset(fe_from_u64x4(extended_ifft_divisor), fe_from_u64x4(g_coset), fe_from_u64x4(g_coset_inv))};
+    return 0;
+}
+
+// the _device forms' runner: in place on a device column, under the Entry of the device that owns it
+static int run_device(const char* name, void* d_a, const DomainOp& op, void* stream) {
+    Entry en(name, d_a);
+    if (en.rc) return en.rc;
+    return ntt_device(en.c, (Fe*)d_a, op.omega, op.log_n, op.sc(), (hipStream_t)stream);
 }
 
 // SURVEY.md 8(e), second bullet: NTTs are single-GPU, but independent transforms (the coset NTTs of
@@ -1955,74 +1910,144 @@ static int batch_over_devices(const char* name, void* const* d_a, size_t count, 
     });
 }
 
+int h2hip_ntt_bn254_fr_device(void* d_a, const uint64_t omega[4], uint32_t log_n, void* stream) {
+    DomainOp op;
+    if (int rc = parse_ntt(single(d_a, "ntt: null argument", false), omega, log_n, &op)) return rc;
+    return run_device("h2hip_ntt_bn254_fr_device", d_a, op, stream);
+}
+
+int h2hip_ntt_bn254_fr(uint64_t* a, const uint64_t omega[4], uint32_t log_n) {
+    DomainOp op;
+    if (int rc = parse_ntt(single(a, "ntt: bad argument"), omega, log_n, &op)) return rc;
+    return ntt_host(a, op.omega, op.log_n, op.sc(), nullptr, 0);
+}
+
 int h2hip_ntt_bn254_fr_batch_device(void* const* d_a, size_t count, const uint64_t omega[4], uint32_t log_n, void* stream) {
-    if (!omega || !batch_args_ok(d_a, count, log_n, "ntt_batch")) return H2HIP_EINVAL;
-    if (check_fr(omega, "omega")) return H2HIP_EINVAL;
-    return batch_over_devices("h2hip_ntt_bn254_fr_batch_device", d_a, count, stream, log_n, fe_from_u64x4(omega), nullptr);
+    DomainOp op;
+    if (int rc = parse_ntt(batch_device("ntt_batch", d_a, count), omega, log_n, &op)) return rc;
+    return batch_over_devices("h2hip_ntt_bn254_fr_batch_device", d_a, count, stream, op.log_n, op.omega, op.sc());
+}
+
+int h2hip_ntt_bn254_fr_batch(uint64_t* const* a, size_t count, const uint64_t omega[4], uint32_t log_n) {
+    DomainOp op;
+    if (int rc = parse_ntt(batch_host("ntt_batch", a, a, count), omega, log_n, &op)) return rc;
+    return ntt_host_batch("h2hip_ntt_bn254_fr_batch", a, op.in_elems(), a, count, op.omega, op.log_n, op.sc());
+}
+
+int h2hip_ifft_bn254_fr_device(void* d_a, const uint64_t omega_inv[4], uint32_t log_n, const uint64_t divisor[4], void* stream) {
+    DomainOp op;
+    if (int rc = parse_ifft(single(d_a, "ifft: null argument", false), omega_inv, log_n, divisor, &op)) return rc;
+    return run_device("h2hip_ifft_bn254_fr_device", d_a, op, stream);
+}
+
+int h2hip_ifft_bn254_fr(uint64_t* a, const uint64_t omega_inv[4], uint32_t log_n, const uint64_t divisor[4]) {
+    DomainOp op;
+    if (int rc = parse_ifft(single(a, "ifft: bad argument"), omega_inv, log_n, divisor, &op)) return rc;
+    return ntt_host(a, op.omega, op.log_n, op.sc(), nullptr, 0);
 }
 
 int h2hip_ifft_bn254_fr_batch_device(void* const* d_a, size_t count, const uint64_t omega_inv[4], uint32_t log_n, const uint64_t divisor[4],
                                      void* stream) {
-    if (!omega_inv || !divisor || !batch_args_ok(d_a, count, log_n, "ifft_batch")) return H2HIP_EINVAL;
-    if (check_fr(omega_inv, "omega_inv") || check_fr(divisor, "divisor")) return H2HIP_EINVAL;
-    NttScale sc = NttScale::inverse(fe_from_u64x4(divisor));
-    return batch_over_devices("h2hip_ifft_bn254_fr_batch_device", d_a, count, stream, log_n, fe_from_u64x4(omega_inv), &sc);
+    DomainOp op;
+    if (int rc = parse_ifft(batch_device("ifft_batch", d_a, count), omega_inv, log_n, divisor, &op)) return rc;
+    return batch_over_devices("h2hip_ifft_bn254_fr_batch_device", d_a, count, stream, op.log_n, op.omega, op.sc());
+}
+
+int h2hip_ifft_bn254_fr_batch(uint64_t* const* a, size_t count, const uint64_t omega_inv[4], uint32_t log_n, const uint64_t divisor[4]) {
+    DomainOp op;
+    if (int rc = parse_ifft(batch_host("ifft_batch", a, a, count), omega_inv, log_n, divisor, &op)) return rc;
+    return ntt_host_batch("h2hip_ifft_bn254_fr_batch", a, op.in_elems(), a, count, op.omega, op.log_n, op.sc());
+}
+
+int h2hip_coeff_to_extended_bn254_fr_device(void* d_a, uint32_t k, uint32_t extended_k, const uint64_t extended_omega[4],
+                                            const uint64_t g_coset[4], const uint64_t g_coset_inv[4], void* stream) {
+    DomainOp op;
+    const Form f = single(d_a, "coeff_to_extended: bad argument");
+    if (int rc = parse_coeff_to_extended(f, k, extended_k, extended_omega, g_coset, g_coset_inv, &op)) return rc;
+    return run_device("h2hip_coeff_to_extended_bn254_fr_device", d_a, op, stream);
+}
+
+int h2hip_coeff_to_extended_bn254_fr(const uint64_t* a, uint32_t k, uint64_t* out, uint32_t extended_k,
+                                     const uint64_t extended_omega[4], const uint64_t g_coset[4], const uint64_t g_coset_inv[4]) {
+    DomainOp op;
+    const Form f = single(a && out, "coeff_to_extended: bad argument");
+    if (int rc = parse_coeff_to_extended(f, k, extended_k, extended_omega, g_coset, g_coset_inv, &op)) return rc;
+    return ntt_host(out, op.omega, op.log_n, op.sc(), a, op.in_elems());
 }
 
 int h2hip_coeff_to_extended_bn254_fr_batch_device(void* const* d_a, size_t count, uint32_t k, uint32_t extended_k, const uint64_t extended_omega[4],
                                                   const uint64_t g_coset[4], const uint64_t g_coset_inv[4], void* stream) {
-    if (!extended_omega || !g_coset || !g_coset_inv || k > extended_k || !batch_args_ok(d_a, count, extended_k, "coeff_to_extended_batch"))
-        return H2HIP_EINVAL;
-    if (check_fr(extended_omega, "extended_omega") || check_fr(g_coset, "g_coset") || check_fr(g_coset_inv, "g_coset_inv")) return H2HIP_EINVAL;
-    NttScale sc = NttScale::into_coset(fe_from_u64x4(g_coset), fe_from_u64x4(g_coset_inv), 1ull << k);
-    return batch_over_devices("h2hip_coeff_to_extended_bn254_fr_batch_device", d_a, count, stream, extended_k, fe_from_u64x4(extended_omega), &sc);
-}
-
-// ---- the same conversions on host columns, pipelined (ntt_host_batch)
-static int host_batch_args_ok(const uint64_t* const* in, uint64_t* const* out, size_t count, uint32_t log_n, const char* what) {
-    if (log_n > 28 || (count && (!in || !out))) {
-        set_error("%s: bad argument", what);
-        return 0;
-    }
-    for (size_t i = 0; i < count; i++)
-        if (!in[i] || !out[i]) {
-            set_error("%s: null column %zu", what, i);
-            return 0;
-        }
-    return 1;
-}
-
-int h2hip_ntt_bn254_fr_batch(uint64_t* const* a, size_t count, const uint64_t omega[4], uint32_t log_n) {
-    if (!omega || !host_batch_args_ok(a, a, count, log_n, "ntt_batch")) return H2HIP_EINVAL;
-    if (check_fr(omega, "omega")) return H2HIP_EINVAL;
-    return ntt_host_batch("h2hip_ntt_bn254_fr_batch", a, (size_t)1 << log_n, a, count, fe_from_u64x4(omega), log_n, nullptr);
-}
-
-int h2hip_ifft_bn254_fr_batch(uint64_t* const* a, size_t count, const uint64_t omega_inv[4], uint32_t log_n, const uint64_t divisor[4]) {
-    if (!omega_inv || !divisor || !host_batch_args_ok(a, a, count, log_n, "ifft_batch")) return H2HIP_EINVAL;
-    if (check_fr(omega_inv, "omega_inv") || check_fr(divisor, "divisor")) return H2HIP_EINVAL;
-    NttScale sc = NttScale::inverse(fe_from_u64x4(divisor));
-    return ntt_host_batch("h2hip_ifft_bn254_fr_batch", a, (size_t)1 << log_n, a, count, fe_from_u64x4(omega_inv), log_n, &sc);
+    DomainOp op;
+    const Form f = batch_device("coeff_to_extended_batch", d_a, count);
+    if (int rc = parse_coeff_to_extended(f, k, extended_k, extended_omega, g_coset, g_coset_inv, &op)) return rc;
+    return batch_over_devices("h2hip_coeff_to_extended_bn254_fr_batch_device", d_a, count, stream, op.log_n, op.omega, op.sc());
 }
 
 int h2hip_coeff_to_extended_bn254_fr_batch(const uint64_t* const* a, uint32_t k, uint64_t* const* out, size_t count, uint32_t extended_k,
                                            const uint64_t extended_omega[4], const uint64_t g_coset[4], const uint64_t g_coset_inv[4]) {
-    if (!extended_omega || !g_coset || !g_coset_inv || k > extended_k || !host_batch_args_ok(a, out, count, extended_k, "coeff_to_extended_batch"))
-        return H2HIP_EINVAL;
-    if (check_fr(extended_omega, "extended_omega") || check_fr(g_coset, "g_coset") || check_fr(g_coset_inv, "g_coset_inv")) return H2HIP_EINVAL;
-    NttScale sc = NttScale::into_coset(fe_from_u64x4(g_coset), fe_from_u64x4(g_coset_inv), 1ull << k);
-    return ntt_host_batch("h2hip_coeff_to_extended_bn254_fr_batch", a, (size_t)1 << k, out, count, fe_from_u64x4(extended_omega), extended_k, &sc);
+    DomainOp op;
+    const Form f = batch_host("coeff_to_extended_batch", a, out, count);
+    if (int rc = parse_coeff_to_extended(f, k, extended_k, extended_omega, g_coset, g_coset_inv, &op)) return rc;
+    return ntt_host_batch("h2hip_coeff_to_extended_bn254_fr_batch", a, op.in_elems(), out, count, op.omega, op.log_n, op.sc());
+}
+
+int h2hip_extended_to_coeff_bn254_fr_device(void* d_a, uint32_t extended_k, const uint64_t extended_omega_inv[4],
+                                            const uint64_t extended_ifft_divisor[4], const uint64_t g_coset[4],
+                                            const uint64_t g_coset_inv[4], void* stream) {
+    DomainOp op;
+    const Form f = single(d_a, "extended_to_coeff: bad argument");
+    if (int rc = parse_extended_to_coeff(f, extended_k, extended_omega_inv, extended_ifft_divisor, g_coset, g_coset_inv, &op)) return rc;
+    return run_device("h2hip_extended_to_coeff_bn254_fr_device", d_a, op, stream);
+}
+
+int h2hip_extended_to_coeff_bn254_fr(uint64_t* a, uint32_t extended_k, const uint64_t extended_omega_inv[4],
+                                     const uint64_t extended_ifft_divisor[4], const uint64_t g_coset[4], const uint64_t g_coset_inv[4]) {
+    DomainOp op;
+    const Form f = single(a, "extended_to_coeff: bad argument");
+    if (int rc = parse_extended_to_coeff(f, extended_k, extended_omega_inv, extended_ifft_divisor, g_coset, g_coset_inv, &op)) return rc;
+    return ntt_host(a, op.omega, op.log_n, op.sc(), nullptr, 0);
 }
 
 int h2hip_extended_to_coeff_bn254_fr_batch(uint64_t* const* a, size_t count, uint32_t extended_k, const uint64_t extended_omega_inv[4],
                                            const uint64_t extended_ifft_divisor[4], const uint64_t g_coset[4], const uint64_t g_coset_inv[4]) {
-    if (!extended_omega_inv || !extended_ifft_divisor || !g_coset || !g_coset_inv || !host_batch_args_ok(a, a, count, extended_k, "extended_to_coeff_batch"))
+    DomainOp op;
+    const Form f = batch_host("extended_to_coeff_batch", a, a, count);
+    if (int rc = parse_extended_to_coeff(f, extended_k, extended_omega_inv, extended_ifft_divisor, g_coset, g_coset_inv, &op)) return rc;
+    return ntt_host_batch("h2hip_extended_to_coeff_bn254_fr_batch", a, op.in_elems(), a, count, op.omega, op.log_n, op.sc());
+}
+
+// EvaluationDomain::divide_by_vanishing_poly: what both forms reject
+static int divide_check(const void* a, uint32_t extended_k, const uint64_t* t_evaluations, uint32_t t_len) {
+    if (!a || !t_evaluations || extended_k > 28 || t_len == 0) {
+        set_error("divide_by_vanishing_poly: bad argument");
         return H2HIP_EINVAL;
-    if (check_fr(extended_omega_inv, "extended_omega_inv") || check_fr(extended_ifft_divisor, "extended_ifft_divisor") ||
-        check_fr(g_coset, "g_coset") || check_fr(g_coset_inv, "g_coset_inv"))
-        return H2HIP_EINVAL;
-    NttScale sc = NttScale::out_of_coset(fe_from_u64x4(extended_ifft_divisor), fe_from_u64x4(g_coset), fe_from_u64x4(g_coset_inv));
-    return ntt_host_batch("h2hip_extended_to_coeff_bn254_fr_batch", a, (size_t)1 << extended_k, a, count, fe_from_u64x4(extended_omega_inv), extended_k, &sc);
+    }
+    for (uint32_t i = 0; i < t_len; i++)
+        if (check_fr(t_evaluations + 4 * i, "t_evaluations[i]")) return H2HIP_EINVAL;
+    return 0;
+}
+
+int h2hip_divide_by_vanishing_poly_bn254_fr_device(void* d_a, uint32_t extended_k, const uint64_t* t_evaluations, uint32_t t_len, void* stream) {
+    if (int rc = divide_check(d_a, extended_k, t_evaluations, t_len)) return rc;
+    Entry en("h2hip_divide_by_vanishing_poly_bn254_fr_device", d_a);
+    if (en.rc) return en.rc;
+    return scale_periodic_device(en.c, (Fe*)d_a, 1ull << extended_k, t_evaluations, t_len, (hipStream_t)stream);
+}
+
+int h2hip_divide_by_vanishing_poly_bn254_fr(uint64_t* a, uint32_t extended_k, const uint64_t* t_evaluations, uint32_t t_len) {
+    if (int rc = divide_check(a, extended_k, t_evaluations, t_len)) return rc;
+    Entry en("h2hip_divide_by_vanishing_poly_bn254_fr");
+    if (en.rc) return en.rc;
+    Ctx* c = en.c;
+    size_t bytes = sizeof(Fe) << extended_k;
+    int rc = c->ntt_io.ensure(bytes);
+    if (rc) return rc;
+    H2_CHECK(hipMemcpyAsync(c->ntt_io.p, a, bytes, hipMemcpyHostToDevice, c->stream));
+    rc = scale_periodic_device(c, (Fe*)c->ntt_io.p, 1ull << extended_k, t_evaluations, t_len, c->stream);
+    if (rc) return rc;
+    H2_CHECK(hipMemcpyAsync(a, c->ntt_io.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    H2_CHECK(hipStreamSynchronize(c->stream));
+    return 0;
 }
 
 int h2hip_debug_set_ntt_host_batch(uint64_t run_bytes, uint64_t group_bytes) {
@@ -2120,173 +2145,6 @@ extern "C" int h2hip_columns_pinned_info(size_t* n_columns, size_t* device_bytes
     return 0;
 }
 
-int h2hip_g_to_lagrange_bn254_device(const void* d_g_xy, uint32_t k, void* d_g_lagrange_xy, void* stream) {
-    if (!d_g_xy || !d_g_lagrange_xy || k > 28) {
-        set_error("g_to_lagrange: bad argument");
-        return H2HIP_EINVAL;
-    }
-    Entry en("h2hip_g_to_lagrange_bn254_device", d_g_xy);
-    if (en.rc) return en.rc;
-    return g_to_lagrange_device(en.c, (const Affine*)d_g_xy, k, (Affine*)d_g_lagrange_xy, (hipStream_t)stream);
-}
-
-int h2hip_g_to_lagrange_bn254(const uint64_t* g_xy, uint32_t k, uint64_t* g_lagrange_xy) {
-    if (!g_xy || !g_lagrange_xy || k > 28) {
-        set_error("g_to_lagrange: bad argument");
-        return H2HIP_EINVAL;
-    }
-    Entry en("h2hip_g_to_lagrange_bn254");
-    if (en.rc) return en.rc;
-    Ctx* c = en.c;
-    const size_t bytes = sizeof(Affine) << k;
-    int rc = c->ntt_io.ensure(2 * bytes);
-    if (rc) return rc;
-    Affine* d_in = (Affine*)c->ntt_io.p;
-    Affine* d_out = (Affine*)((char*)c->ntt_io.p + bytes);
-    if ((rc = c->ws_acquire(c->stream))) return rc;
-    H2_CHECK(hipMemcpyAsync(d_in, g_xy, bytes, hipMemcpyHostToDevice, c->stream));
-    if ((rc = g_to_lagrange_device(c, d_in, k, d_out, c->stream))) return rc;
-    H2_CHECK(hipMemcpyAsync(g_lagrange_xy, d_out, bytes, hipMemcpyDeviceToHost, c->stream));
-    H2_CHECK(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-int h2hip_fft_bn254_g1_device(void* d_a_xyz, const uint64_t omega[4], uint32_t log_n, void* stream) {
-    if (!d_a_xyz || !omega || log_n > 28) {
-        set_error("fft_g1: bad argument");
-        return H2HIP_EINVAL;
-    }
-    if (check_fr(omega, "omega")) return H2HIP_EINVAL;
-    Entry en("h2hip_fft_bn254_g1_device", d_a_xyz);
-    if (en.rc) return en.rc;
-    return fft_g1_device(en.c, (Jac*)d_a_xyz, fe_from_u64x4(omega), log_n, (hipStream_t)stream);
-}
-
-int h2hip_fft_bn254_g1(uint64_t* a_xyz, const uint64_t omega[4], uint32_t log_n) {
-    if (!a_xyz || !omega || log_n > 28) {
-        set_error("fft_g1: bad argument");
-        return H2HIP_EINVAL;
-    }
-    if (check_fr(omega, "omega")) return H2HIP_EINVAL;
-    Entry en("h2hip_fft_bn254_g1");
-    if (en.rc) return en.rc;
-    Ctx* c = en.c;
-    const size_t bytes = sizeof(Jac) << log_n;
-    int rc = c->ntt_io.ensure(bytes);
-    if (rc) return rc;
-    H2_CHECK(hipMemcpyAsync(c->ntt_io.p, a_xyz, bytes, hipMemcpyHostToDevice, c->stream));
-    if ((rc = fft_g1_device(c, (Jac*)c->ntt_io.p, fe_from_u64x4(omega), log_n, c->stream))) return rc;
-    H2_CHECK(hipMemcpyAsync(a_xyz, c->ntt_io.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    H2_CHECK(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-int h2hip_kzg_setup_bn254_device(uint32_t k, const uint64_t secret[4], void* d_g_xy, void* d_g_lagrange_xy, void* stream) {
-    if (!secret || !d_g_xy || !d_g_lagrange_xy) {
-        set_error("kzg_setup: null argument");
-        return H2HIP_EINVAL;
-    }
-    if (check_fr(secret, "secret")) return H2HIP_EINVAL;
-    Entry en("h2hip_kzg_setup_bn254_device", d_g_xy);
-    if (en.rc) return en.rc;
-    return kzg_setup_device(en.c, k, fe_from_u64x4(secret), (Affine*)d_g_xy, (Affine*)d_g_lagrange_xy, (hipStream_t)stream);
-}
-
-int h2hip_kzg_setup_bn254(uint32_t k, const uint64_t secret[4], uint64_t* g_xy, uint64_t* g_lagrange_xy) {
-    if (!secret || !g_xy || !g_lagrange_xy || k > 28) {
-        set_error("kzg_setup: bad argument");
-        return H2HIP_EINVAL;
-    }
-    if (check_fr(secret, "secret")) return H2HIP_EINVAL;
-    Entry en("h2hip_kzg_setup_bn254");
-    if (en.rc) return en.rc;
-    Ctx* c = en.c;
-    const size_t bytes = sizeof(Affine) << k;
-    int rc = c->ntt_io.ensure(2 * bytes);
-    if (rc) return rc;
-    Affine* d_g = (Affine*)c->ntt_io.p;
-    Affine* d_gl = (Affine*)((char*)c->ntt_io.p + bytes);
-    if ((rc = kzg_setup_device(c, k, fe_from_u64x4(secret), d_g, d_gl, c->stream))) return rc;
-    H2_CHECK(hipMemcpyAsync(g_xy, d_g, bytes, hipMemcpyDeviceToHost, c->stream));
-    H2_CHECK(hipMemcpyAsync(g_lagrange_xy, d_gl, bytes, hipMemcpyDeviceToHost, c->stream));
-    H2_CHECK(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-int h2hip_evaluate_h_bn254(const h2hip_evalh_desc* desc, uint64_t* values) {
-    if (!desc || !values) {
-        set_error("evaluate_h: null argument");
-        return H2HIP_EINVAL;
-    }
-    if (evaluate_h_validate(desc, values)) return H2HIP_EINVAL;
-    Entry en("h2hip_evaluate_h_bn254");
-    if (en.rc) return en.rc;
-    return evaluate_h_host(en.c, desc, values, false, en.c->stream);
-}
-
-int h2hip_evaluate_h_bn254_device(const h2hip_evalh_desc* desc, void* d_values, void* stream) {
-    if (!desc || !d_values) {
-        set_error("evaluate_h: null argument");
-        return H2HIP_EINVAL;
-    }
-    if (evaluate_h_validate(desc, d_values)) return H2HIP_EINVAL;
-    Entry en("h2hip_evaluate_h_bn254_device", d_values);
-    if (en.rc) return en.rc;
-    return evaluate_h_host(en.c, desc, (uint64_t*)d_values, true, (hipStream_t)stream);
-}
-
-int h2hip_gen_scalars_device(uint64_t seed, uint64_t start, size_t n, void* d_out, void* stream) {
-    if (n && !d_out) {
-        set_error("gen_scalars: null output");
-        return H2HIP_EINVAL;
-    }
-    Entry en("h2hip_gen_scalars_device", d_out);
-    if (en.rc) return en.rc;
-    return gen_scalars_device(seed, start, n, (Fe*)d_out, (hipStream_t)stream);
-}
-
-int h2hip_gen_points_device(uint64_t seed, uint64_t start, size_t n, void* d_out, void* stream) {
-    if (n && !d_out) {
-        set_error("gen_points: null output");
-        return H2HIP_EINVAL;
-    }
-    Entry en("h2hip_gen_points_device", d_out);
-    if (en.rc) return en.rc;
-    return gen_points_device(seed, start, n, (Affine*)d_out, (hipStream_t)stream);
-}
-
-int h2hip_set_msm_window(uint32_t c) {
-    if (c != 0 && (c < 2 || c > 24)) {
-        set_error("msm window must be 0 (auto) or 2..24");
-        return H2HIP_EINVAL;
-    }
-    msm_set_window(c);
-    return 0;
-}
-
-uint32_t h2hip_get_msm_window(size_t n) { return msm_get_window(n); }
-uint32_t h2hip_get_msm_window_fixed_base(size_t n) { return msm_table_window(n); }
-
-// test hook: split inputs above m pairs into consecutive chunks (default 2^26, the 31-bit pair-index limit)
-int h2hip_debug_set_msm_max_chunk(size_t m) {
-    msm_set_max_chunk(m);
-    return 0;
-}
-
-// test / tuning hook: a host-resident MSM of at least min_n pairs streams in `chunks` pieces whose sizes grow by 1 / ratio
-// (ratio_permille / 1000 = upload time over compute time per pair); chunks = 1 turns streaming off; zeros restore the defaults
-int h2hip_debug_set_msm_stream(uint32_t chunks, uint32_t ratio_permille, size_t min_n) {
-    msm_set_stream(chunks, ratio_permille / 1000.0, min_n);
-    return 0;
-}
-
-// test hook, needs no GPU: the chunk sizes a streamed host-slice MSM of n pairs is cut into (chunks / ratio_permille 0 = the
-// defaults in force; with_bases: the points cross PCIe too); returns the number of chunks, sizes[0 .. min(that, cap))
-size_t h2hip_debug_msm_stream_ladder(size_t n, uint32_t chunks, uint32_t ratio_permille, int with_bases, size_t* sizes, size_t cap) {
-    if (!sizes && cap) return 0;
-    return msm_debug_ladder(n, chunks, ratio_permille / 1000.0, with_bases != 0, sizes, cap);
-}
-
 // record form of the window tables pinned from now on: 0 = the engine's choice, 64 = E-form, 80 / 128 = native records at that stride
 int h2hip_debug_set_table_records(uint32_t bytes) {
     if (bytes != 0 && bytes != 64 && bytes != 80 && bytes != 128) {
@@ -2294,164 +2152,6 @@ int h2hip_debug_set_table_records(uint32_t bytes) {
         return H2HIP_EINVAL;
     }
     g_table_records = bytes;
-    return 0;
-}
-
-// tuning hook: buckets above (entries of the MSM) / d go to the chunked path (default 32768; 0 restores it)
-int h2hip_debug_set_msm_heavy_div(size_t d) {
-    msm_set_heavy_div(d);
-    return 0;
-}
-
-// tuning hook: g_to_lagrange layers up to k = 14 -- bit 0: one quad of lanes per butterfly (1, default) or one lane (0); bit 1 set: a
-// normalisation after every layer (default clear: the points stay XYZZ between the layers)
-int h2hip_debug_set_g2l_quad(int on) {
-    ecfft_set_quad((on & 1) != 0);
-    ecfft_set_lazy((on & 2) == 0);
-    return 0;
-}
-
-// tuning hook: a fused run holds at most `entries` entries (default 2^26) and fusing applies up to `max_n` pairs per MSM (default 2^18); 0 = default
-int h2hip_debug_set_msm_fuse_limits(size_t entries, size_t max_n) {
-    msm_set_fuse_limits(entries, max_n);
-    return 0;
-}
-
-// tuning hook: lane budget of the first row/column pass (default 65536 = one wave per SIMD) and its multiplier flavour
-int h2hip_debug_set_msm_rowcol(uint64_t lanes, int use_asm) {
-    msm_set_rowcol(lanes, (uint32_t)use_asm);
-    return 0;
-}
-
-// tuning hook: several lanes per bucket in runs with few buckets (1, default) or always one (0)
-int h2hip_debug_set_msm_split_buckets(int on) {
-    msm_set_split_buckets(on != 0);
-    return 0;
-}
-
-// tuning hook: the reduction tail with one quad of lanes per group operation (1, default) or one lane (0)
-int h2hip_debug_set_msm_plane_tail(int on) {
-    Entry en;
-    if (en.rc) return en.rc;
-    msm_set_plane_tail(on != 0);
-    return 0;
-}
-
-int h2hip_debug_set_msm_quad_tail(int on) {
-    msm_set_quad_tail(on != 0);
-    return 0;
-}
-
-// tuning hook: 1 = order the buckets by size inside each sort bin only (no global pass); 0 = global order (default)
-int h2hip_debug_set_msm_bucket_order(int local) {
-    msm_set_bucket_order(local);
-    return 0;
-}
-
-// tuning hook: level-1 records of runs with multi-tile bins as two arrays (1, default) or as (entry, bucket id) pairs (0)
-int h2hip_debug_set_msm_split_records(int on) {
-    msm_set_split_records(on != 0);
-    return 0;
-}
-
-// tuning hook: target number of entries per coarse bin of the MSM's two-level sort (default 8192; 0 restores it)
-int h2hip_debug_set_msm_bin_entries(size_t d) {
-    msm_set_bin_entries(d);
-    return 0;
-}
-
-// test hook: programs needing more slots than v use the global-workspace form of the evaluate_h kernels (default 256)
-int h2hip_debug_set_evalh_max_local_slots(uint32_t v) {
-    evalh_debug_set_max_local_slots(v);
-    return 0;
-}
-
-// test hook: HBM one group of lookup cosets may take in evaluate_h (0 = default, 2 GB); a small value forces one lookup per group
-int h2hip_debug_set_evalh_lookup_group_bytes(uint64_t v) {
-    evalh_debug_set_lookup_group_bytes(v);
-    return 0;
-}
-
-// test / tuning hook, needs no GPU: compile a graph as evaluate_h would and report the program's size
-int h2hip_debug_evalh_program_muls(const h2hip_graph* g, uint32_t* n_mul) { return evalh_debug_program_muls(g, n_mul) ? H2HIP_EINVAL : 0; }
-
-int h2hip_debug_set_evalh_codegen(int mode, uint32_t max_ops) {
-    Entry en;
-    if (en.rc) return en.rc;
-    evalh_debug_set_codegen(mode, max_ops);
-    return 0;
-}
-
-int h2hip_debug_evalh_codegen_source(const h2hip_graph* g, char* buf, size_t cap, size_t* len, int compile, double* seconds, size_t* code_bytes) {
-    return evalh_debug_codegen_source(g, buf, cap, len, compile, seconds, code_bytes);
-}
-
-int h2hip_debug_evalh_codegen_stats(uint64_t out[5]) {
-    if (!out) return H2HIP_EINVAL;
-    evalh_debug_codegen_stats(out);
-    return 0;
-}
-
-int h2hip_debug_evalh_compile_stats(const h2hip_graph* g, uint32_t* n_ops, uint32_t* n_slots) {
-    return evalh_debug_compile_stats(g, n_ops, n_slots);
-}
-
-// test / tuning hook: batches of small MSMs run fused (default) or pipelined over streams
-int h2hip_debug_set_msm_fuse_small(int on) {
-    msm_set_fuse_small(on != 0);
-    return 0;
-}
-
-int h2hip_debug_set_ntt_smax(uint32_t v) {
-    ntt_set_smax(v);
-    return 0;
-}
-
-// tuning hook: sizes 2^lo..2^hi (within 18..22) take the two-pass plan; hi < lo turns it off
-// tuning hook: HBM (bytes per device) the two-pass plan's full inter-pass twiddle tables may take; 0 = two-level table only
-int h2hip_debug_set_ntt_twiddle_budget(uint64_t bytes) {
-    ntt_set_full_twiddle_budget(bytes);
-    return 0;
-}
-
-// tuning hook: bytes of columns + workspace one launch of a batched transform spans (0 = default)
-int h2hip_debug_set_ntt_batch_bytes(uint64_t bytes) {
-    ntt_set_batch_bytes(bytes);
-    return 0;
-}
-
-// tuning hook: pairs of workgroups per pass from which batched columns of 2^17 / 2^18 points take the two-pass plan (0 = default 512)
-int h2hip_debug_set_ntt_two_pass_batch_wgs(uint64_t v) {
-    ntt_set_two_pass_batch_wgs(v);
-    return 0;
-}
-
-// tuning hook: the largest strided pass (log2 of its M) that reads its inter-pass twiddles from a table (0 = default 24)
-int h2hip_debug_set_ntt_full_max_log_m(uint32_t v) {
-    ntt_set_full_max_log_m(v);
-    return 0;
-}
-
-// A/B hook: 0 = the inverse transform's 1/n is multiplied in by the last pass even where the first pass reads a table (rounds 1-3)
-int h2hip_debug_set_ntt_fold_tables(int on) {
-    ntt_set_fold_tables(on != 0);
-    return 0;
-}
-
-// tuning hook: log2 columns per workgroup of the two-pass kernels (-1 = default)
-int h2hip_debug_set_ntt_two_pass_log_j(int v) {
-    ntt_set_two_pass_log_j(v);
-    return 0;
-}
-
-int h2hip_debug_set_ntt_two_pass(uint32_t lo, uint32_t hi) {
-    ntt_set_two_pass(lo, hi);
-    return 0;
-}
-
-// undocumented tuning knob (not in the public header): CUs reserved for the sort / reduce stages of a batch
-int h2hip_debug_set_reserved_cus(uint32_t k) {
-    msm_set_reserved_cus(k);
     return 0;
 }
 

@@ -294,7 +294,6 @@ using namespace h2;
 
 extern "C" {
 // ---- C ABI (include/halo2hip.h, "witness check") --------------------------------------------------------------------------------------
-// Here rather than in api.hip, for the reason product.hip gives.
 static int ck_out_check(const char* what, uint32_t k, size_t items, uint32_t max_rows, const uint64_t* counts, const uint32_t* rows) {
     if (int rc = check_k(what, k)) return rc;
     if (max_rows > CK_MAX_ROWS) {

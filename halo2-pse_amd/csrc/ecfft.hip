@@ -15,6 +15,7 @@
 // affine output is canonical, so it is compared limb for limb.
 #include <string.h>
 
+#include "../../include/halo2hip_debug.h"
 #include "ecq.h"
 #include "engine.h"
 #include "glv.h"
@@ -314,8 +315,13 @@ __global__ void __launch_bounds__(256) ecfft_twiddle_kernel(GlvScalar* tw, uint6
 }
 
 static bool g_ecfft_quad = true, g_ecfft_lazy = true;
-void ecfft_set_quad(bool on) { g_ecfft_quad = on; }
-void ecfft_set_lazy(bool on) { g_ecfft_lazy = on; }  // k <= 14: no normalisation between the layers (round 4); off: round 3's path
+// tuning hook: g_to_lagrange layers up to k = 14 -- bit 0: one quad of lanes per butterfly (1, default) or one lane (0); bit 1 set: a
+// normalisation after every layer (default clear: the points stay XYZZ between the layers)
+extern "C" int h2hip_debug_set_g2l_quad(int on) {
+    g_ecfft_quad = (on & 1) != 0;
+    g_ecfft_lazy = (on & 2) == 0;  // k <= 14: no normalisation between the layers (round 4); off: round 3's path
+    return 0;
+}
 
 static int normalize_launch(const XYZZ* in, Affine* out, uint64_t n, hipStream_t s) {
     const uint64_t lanes = (n + EC_NORM_CHUNK - 1) / EC_NORM_CHUNK;
@@ -460,3 +466,70 @@ int fft_g1_device(Ctx* c, Jac* d_a, const Fe& omega, uint32_t log_n, hipStream_t
 }
 
 }  // namespace h2
+
+using namespace h2;
+
+extern "C" {
+// ---- C ABI (include/halo2hip.h) ---------------------------------------------------------------------------------------------------
+int h2hip_g_to_lagrange_bn254_device(const void* d_g_xy, uint32_t k, void* d_g_lagrange_xy, void* stream) {
+    if (!d_g_xy || !d_g_lagrange_xy || k > 28) {
+        set_error("g_to_lagrange: bad argument");
+        return H2HIP_EINVAL;
+    }
+    Entry en("h2hip_g_to_lagrange_bn254_device", d_g_xy);
+    if (en.rc) return en.rc;
+    return g_to_lagrange_device(en.c, (const Affine*)d_g_xy, k, (Affine*)d_g_lagrange_xy, (hipStream_t)stream);
+}
+
+int h2hip_g_to_lagrange_bn254(const uint64_t* g_xy, uint32_t k, uint64_t* g_lagrange_xy) {
+    if (!g_xy || !g_lagrange_xy || k > 28) {
+        set_error("g_to_lagrange: bad argument");
+        return H2HIP_EINVAL;
+    }
+    Entry en("h2hip_g_to_lagrange_bn254");
+    if (en.rc) return en.rc;
+    Ctx* c = en.c;
+    const size_t bytes = sizeof(Affine) << k;
+    int rc = c->ntt_io.ensure(2 * bytes);
+    if (rc) return rc;
+    Affine* d_in = (Affine*)c->ntt_io.p;
+    Affine* d_out = (Affine*)((char*)c->ntt_io.p + bytes);
+    if ((rc = c->ws_acquire(c->stream))) return rc;
+    H2_CHECK(hipMemcpyAsync(d_in, g_xy, bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = g_to_lagrange_device(c, d_in, k, d_out, c->stream))) return rc;
+    H2_CHECK(hipMemcpyAsync(g_lagrange_xy, d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+    H2_CHECK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int h2hip_fft_bn254_g1_device(void* d_a_xyz, const uint64_t omega[4], uint32_t log_n, void* stream) {
+    if (!d_a_xyz || !omega || log_n > 28) {
+        set_error("fft_g1: bad argument");
+        return H2HIP_EINVAL;
+    }
+    if (check_fr(omega, "omega")) return H2HIP_EINVAL;
+    Entry en("h2hip_fft_bn254_g1_device", d_a_xyz);
+    if (en.rc) return en.rc;
+    return fft_g1_device(en.c, (Jac*)d_a_xyz, fe_from_u64x4(omega), log_n, (hipStream_t)stream);
+}
+
+int h2hip_fft_bn254_g1(uint64_t* a_xyz, const uint64_t omega[4], uint32_t log_n) {
+    if (!a_xyz || !omega || log_n > 28) {
+        set_error("fft_g1: bad argument");
+        return H2HIP_EINVAL;
+    }
+    if (check_fr(omega, "omega")) return H2HIP_EINVAL;
+    Entry en("h2hip_fft_bn254_g1");
+    if (en.rc) return en.rc;
+    Ctx* c = en.c;
+    const size_t bytes = sizeof(Jac) << log_n;
+    int rc = c->ntt_io.ensure(bytes);
+    if (rc) return rc;
+    H2_CHECK(hipMemcpyAsync(c->ntt_io.p, a_xyz, bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = fft_g1_device(c, (Jac*)c->ntt_io.p, fe_from_u64x4(omega), log_n, c->stream))) return rc;
+    H2_CHECK(hipMemcpyAsync(a_xyz, c->ntt_io.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    H2_CHECK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+}  // extern "C"

@@ -268,7 +268,10 @@ struct Entry {
 };
 int check_fr(const uint64_t v[4], const char* what);  // H2HIP_EINVAL (and set_error) unless v is a reduced Fr element
 
-// ---- what the stage files' entry points and host drivers share (inline: api.hip is also built alone, as plain C++) ----------------
+// ---- what the stage files' entry points and host drivers share (inline: api.hip is also built alone, as plain C++ against a stub
+// runtime, for the sanitizer runs of the engine's host logic).  The rule that build rests on: a stage file owns the extern "C" entry
+// points and the h2hip_debug_* hooks of its stage, api.hip keeps the engine and the entry points whose host logic is the engine's own, and
+// what it calls in a stage file tests/cpp/engine_stubs.cpp stands in for. -----------------------------------------------------------
 // caller memory is only 8-byte aligned (4 x u64); Fe is alignas(16)
 inline Fe fe_from_u64x4(const uint64_t v[4]) {
     Fe o;
@@ -402,21 +405,12 @@ int ntt_device_batch(Ctx* c, Fe* const* h_datas, const Fe* const* h_srcs, size_t
                      hipStream_t s);
 
 int scale_periodic_device(Ctx* c, Fe* d_a, uint64_t n, const uint64_t* h_t, uint32_t t_len, hipStream_t s);
-void ntt_set_smax(uint32_t v);
-void ntt_set_two_pass(uint32_t lo, uint32_t hi);
-void ntt_set_full_twiddle_budget(uint64_t bytes);
-void ntt_set_batch_bytes(uint64_t bytes);
-void ntt_set_two_pass_log_j(int v);
-void ntt_set_full_max_log_m(uint32_t v);
-void ntt_set_fold_tables(bool on);
-void ntt_set_two_pass_batch_wgs(uint64_t v);
+void ntt_set_full_twiddle_budget(uint64_t bytes);  // HALO2_HIP_NTT_TWIDDLE_MB
 
 // ecfft.hip
 int g_to_lagrange_device(Ctx* c, const Affine* d_g, uint32_t k, Affine* d_out, hipStream_t s);
 int ec_normalize_device(const XYZZ* d_in, Affine* d_out, uint64_t n, hipStream_t s);  // batched XYZZ -> affine
 int fft_g1_device(Ctx* c, Jac* d_a, const Fe& omega, uint32_t log_n, hipStream_t s);   // best_fft::<G1>, in place on Jacobian points
-void ecfft_set_quad(bool on);
-void ecfft_set_lazy(bool on);
 
 // gen.hip
 int gen_scalars_device(uint64_t seed, uint64_t start, size_t n, Fe* d_out, hipStream_t s);
@@ -445,13 +439,7 @@ int kzg_setup_device(Ctx* c, uint32_t k, const Fe& s, Affine* d_g, Affine* d_gl,
 const Fe* pinned_column_lookup(Ctx* c, const uint64_t* h_col, size_t elems);
 
 // evalh.hip
-void evalh_debug_set_max_local_slots(uint32_t v);
-void evalh_debug_set_lookup_group_bytes(uint64_t v);
-int evalh_debug_compile_stats(const h2hip_graph* g, uint32_t* n_ops, uint32_t* n_slots);
-int evalh_debug_program_muls(const h2hip_graph* g, uint32_t* n_mul);
 void evalh_debug_set_codegen(int mode, uint32_t max_ops);  // 0 off, 1 background compile (default), 2 compile inline; max_ops 0 = default
-void evalh_debug_codegen_stats(uint64_t out[5]);            // compiled, failed, generated-kernel launches, interpreter launches, disk-cache hits
-int evalh_debug_codegen_source(const h2hip_graph* g, char* buf, size_t cap, size_t* len, int compile, double* seconds, size_t* code_bytes);
 void evalh_modules_free(Ctx* c);                            // unload this device's generated kernels (release_ctx)
 void evalh_rtc_shutdown();                                  // join the compile threads (h2hip_shutdown)
 int evaluate_h_validate(const h2hip_evalh_desc* d, const void* values);
@@ -471,23 +459,9 @@ int check_gates_enqueue(Ctx* c, uint32_t k, const Fe* const* fixed, uint32_t n_f
                         const h2hip_graph* graphs, size_t n_graphs, uint64_t* d_mask, uint32_t words, hipStream_t s);
 
 // msm.hip
-void msm_set_fuse_small(bool on);
 void msm_set_window(uint32_t c);
-void msm_set_max_chunk(size_t m);
 void msm_set_stream(uint32_t chunks, double ratio, size_t min_n);
-size_t msm_debug_ladder(size_t n, uint32_t chunks, double ratio, bool with_bases, size_t* out, size_t cap);
-void msm_set_heavy_div(size_t d);
-void msm_set_bin_entries(size_t d);
-void msm_set_split_records(bool on);
-void msm_set_bucket_order(int local);
-void msm_set_quad_tail(bool on);
-void msm_set_split_buckets(bool on);
-void msm_set_plane_tail(bool on);
-void msm_set_fuse_limits(size_t entries, size_t max_n);
-void msm_set_rowcol(uint64_t lanes, uint32_t flavour);
-void msm_set_reserved_cus(uint32_t k);
 uint32_t msm_get_reserved_cus();
-uint32_t msm_get_window(size_t n);
 // tab != nullptr: fixed-base form over tab's window table (d_bases unused)
 int msm_device(Ctx* c, const Fe* d_scalars, const Affine* d_bases, size_t n, XYZZ* h_out, hipStream_t s, const MsmTable* tab = nullptr);
 int msm_batch_device(Ctx* c, const Fe* const* scalars, bool scalars_on_host, const Affine* d_bases, size_t n, size_t count, XYZZ* h_out,

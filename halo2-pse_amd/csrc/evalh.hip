@@ -520,16 +520,24 @@ void evalh_debug_set_codegen(int mode, uint32_t max_ops) {
     g_evalh_gen_fuse = !(mode & 16);
     g_evalh_codegen_max_ops = max_ops ? max_ops : 1200;
 }
+extern "C" int h2hip_debug_set_evalh_codegen(int mode, uint32_t max_ops) {
+    Entry en;
+    if (en.rc) return en.rc;
+    evalh_debug_set_codegen(mode, max_ops);
+    return 0;
+}
 struct RtcStats {
     std::atomic<uint64_t> compiled{0}, failed{0}, launches{0}, interpreted{0}, disk_hits{0};
 };
 static RtcStats g_rtc_stats;
-void evalh_debug_codegen_stats(uint64_t out[5]) {
+extern "C" int h2hip_debug_evalh_codegen_stats(uint64_t out[5]) {
+    if (!out) return H2HIP_EINVAL;
     out[0] = g_rtc_stats.compiled;
     out[1] = g_rtc_stats.failed;
     out[2] = g_rtc_stats.launches;
     out[3] = g_rtc_stats.interpreted;
     out[4] = g_rtc_stats.disk_hits;
+    return 0;
 }
 
 #include "rtc_headers.inc"
@@ -845,7 +853,8 @@ static void rtc_compile(std::shared_ptr<RtcEntry> e, std::string src, uint64_t k
 }
 
 // test / tooling hook, no GPU needed: the source a graph's program is emitted as, and (compile != 0) what hiprtc makes of it
-int evalh_debug_codegen_source(const h2hip_graph* g, char* buf, size_t cap, size_t* len, int compile, double* seconds, size_t* code_bytes) {
+extern "C" int h2hip_debug_evalh_codegen_source(const h2hip_graph* g, char* buf, size_t cap, size_t* len, int compile, double* seconds,
+                                                size_t* code_bytes) {
     if (!g || !len) {
         set_error("evaluate_h: null argument");
         return 1;
@@ -1014,13 +1023,16 @@ static int slot_plan(uint32_t n_slots, size_t size, SlotPlan* out) {
     return 0;
 }
 
-void evalh_debug_set_max_local_slots(uint32_t v) { g_evalh_max_local_slots = v; }
+// test hook: programs needing more slots than v use the global-workspace form of the evaluate_h kernels (default 256)
+extern "C" int h2hip_debug_set_evalh_max_local_slots(uint32_t v) { g_evalh_max_local_slots = v; return 0; }
 static size_t g_evalh_lookup_group_bytes = (size_t)2 << 30;  // HBM one group of lookup cosets may take (tests shrink it to force several groups)
-void evalh_debug_set_lookup_group_bytes(uint64_t v) { g_evalh_lookup_group_bytes = v ? (size_t)v : (size_t)2 << 30; }
+// test hook: HBM one group of lookup cosets may take in evaluate_h (0 = default, 2 GB); a small value forces one lookup per group
+extern "C" int h2hip_debug_set_evalh_lookup_group_bytes(uint64_t v) { g_evalh_lookup_group_bytes = v ? (size_t)v : (size_t)2 << 30; return 0; }
 
 // field multiplications one row of the compiled program performs (products, squares, Horner steps, inserted reductions, and the
 // exact reduction of the stored value): the numerator of the gates kernel's valu_roofline in bench.py
-int evalh_debug_program_muls(const h2hip_graph* g, uint32_t* n_mul) {
+// test / tuning hook, needs no GPU: compile a graph as evaluate_h would and report the program's size
+extern "C" int h2hip_debug_evalh_program_muls(const h2hip_graph* g, uint32_t* n_mul) {
     if (!g || !n_mul) {
         set_error("evaluate_h: null argument");
         return 1;
@@ -1041,7 +1053,7 @@ int evalh_debug_program_muls(const h2hip_graph* g, uint32_t* n_mul) {
     return 0;
 }
 
-int evalh_debug_compile_stats(const h2hip_graph* g, uint32_t* n_ops, uint32_t* n_slots) {
+extern "C" int h2hip_debug_evalh_compile_stats(const h2hip_graph* g, uint32_t* n_ops, uint32_t* n_slots) {
     if (!g || !n_ops || !n_slots) {
         set_error("evaluate_h: null argument");
         return 1;
@@ -1057,7 +1069,7 @@ int evalh_debug_compile_stats(const h2hip_graph* g, uint32_t* n_ops, uint32_t* n
 }
 
 // Everything a kernel will dereference is checked here, on the host, before any device work: a malformed description is
-// H2HIP_EINVAL, never a GPU fault.  Needs no device (api.hip calls it before the engine is entered).
+// H2HIP_EINVAL, never a GPU fault.  Needs no device (the entry points call it before the engine is entered).
 int evaluate_h_validate(const h2hip_evalh_desc* d, const void* values) {
     const uint32_t k = d->k, ek = d->extended_k;
     if (k > ek || ek > 28 || ek - k > 8) {
@@ -1955,8 +1967,30 @@ int check_gates_enqueue(Ctx* c, uint32_t k, const Fe* const* fixed, uint32_t n_f
 using namespace h2;
 
 extern "C" {
-// ---- C ABI (include/halo2hip.h, evaluate_h one coset of the 2^k domain at a time) ------------------------------------------------------
-// Here rather than in api.hip for the reason product.hip gives: api.hip is also compiled alone against a stub runtime.
+// ---- C ABI (include/halo2hip.h, evaluate_h) ----------------------------------------------------------------------------------------
+int h2hip_evaluate_h_bn254(const h2hip_evalh_desc* desc, uint64_t* values) {
+    if (!desc || !values) {
+        set_error("evaluate_h: null argument");
+        return H2HIP_EINVAL;
+    }
+    if (evaluate_h_validate(desc, values)) return H2HIP_EINVAL;
+    Entry en("h2hip_evaluate_h_bn254");
+    if (en.rc) return en.rc;
+    return evaluate_h_host(en.c, desc, values, false, en.c->stream);
+}
+
+int h2hip_evaluate_h_bn254_device(const h2hip_evalh_desc* desc, void* d_values, void* stream) {
+    if (!desc || !d_values) {
+        set_error("evaluate_h: null argument");
+        return H2HIP_EINVAL;
+    }
+    if (evaluate_h_validate(desc, d_values)) return H2HIP_EINVAL;
+    Entry en("h2hip_evaluate_h_bn254_device", d_values);
+    if (en.rc) return en.rc;
+    return evaluate_h_host(en.c, desc, (uint64_t*)d_values, true, (hipStream_t)stream);
+}
+
+// ---- evaluate_h one coset of the 2^k domain at a time ---------------------------------------------------------------------------------
 int h2hip_evaluate_h_parts_bn254(const h2hip_evalh_parts_desc* desc, uint64_t* values) {
     if (!desc || !values) {
         set_error("evaluate_h: null argument");

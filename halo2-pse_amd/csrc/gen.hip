@@ -89,3 +89,29 @@ int gen_points_device(uint64_t seed, uint64_t start, size_t n, Affine* d_out, hi
 }
 
 }  // namespace h2
+
+using namespace h2;
+
+extern "C" {
+// ---- C ABI (include/halo2hip.h) ---------------------------------------------------------------------------------------------------
+int h2hip_gen_scalars_device(uint64_t seed, uint64_t start, size_t n, void* d_out, void* stream) {
+    if (n && !d_out) {
+        set_error("gen_scalars: null output");
+        return H2HIP_EINVAL;
+    }
+    Entry en("h2hip_gen_scalars_device", d_out);
+    if (en.rc) return en.rc;
+    return gen_scalars_device(seed, start, n, (Fe*)d_out, (hipStream_t)stream);
+}
+
+int h2hip_gen_points_device(uint64_t seed, uint64_t start, size_t n, void* d_out, void* stream) {
+    if (n && !d_out) {
+        set_error("gen_points: null output");
+        return H2HIP_EINVAL;
+    }
+    Entry en("h2hip_gen_points_device", d_out);
+    if (en.rc) return en.rc;
+    return gen_points_device(seed, start, n, (Affine*)d_out, (hipStream_t)stream);
+}
+
+}  // extern "C"

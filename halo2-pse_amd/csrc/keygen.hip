@@ -232,7 +232,6 @@ using namespace h2;
 
 extern "C" {
 // ---- C ABI (include/halo2hip.h, "keygen") -----------------------------------------------------------------------------------------
-// Here rather than in api.hip, for the reason product.hip gives.
 static int kg_domain_check(const char* what, uint32_t k, const uint64_t* omega, const uint64_t* omega_inv, const uint64_t* divisor, uint32_t ek,
                            const uint64_t* ext_omega, const uint64_t* g_coset, const uint64_t* g_coset_inv, KgDomain* d) {
     if (k > 28 || ek > 28 || ek < k) {

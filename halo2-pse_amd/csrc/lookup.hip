@@ -403,7 +403,6 @@ using namespace h2;
 
 extern "C" {
 // ---- C ABI (include/halo2hip.h, "lookup compression and permutation") -----------------------------------------------------------
-// Here rather than in api.hip, for the reason product.hip gives.
 static int compress_check(uint32_t k, const void* const* fixed, uint32_t n_fixed, const void* const* advice, uint32_t n_advice,
                           const void* const* instance, uint32_t n_instance, const uint64_t* challenges, uint32_t n_challenges,
                           const uint64_t* theta, const h2hip_graph* graphs, size_t n_graphs, const void* const* out) {

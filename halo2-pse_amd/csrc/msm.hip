@@ -47,6 +47,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "../../include/halo2hip_debug.h"
 #include "ecq.h"
 #include "engine.h"
 #include "host64.h"
@@ -1146,28 +1147,46 @@ static uint32_t g_window_override = 0;
 static size_t g_heavy_div = 32768;
 static size_t g_bin_entries = 8192;
 static bool g_split_records = true;
-void msm_set_split_records(bool on) { g_split_records = on; }
+// tuning hook: level-1 records of runs with multi-tile bins as two arrays (1, default) or as (entry, bucket id) pairs (0)
+extern "C" int h2hip_debug_set_msm_split_records(int on) { g_split_records = on != 0; return 0; }
 static uint64_t g_rowcol_lanes = 65536;
 static bool g_rowcol_asm = true, g_rowcol_qtree = true;  // first pass: chains on the explicit-mad multiplier, then the quad tree
-void msm_set_rowcol(uint64_t lanes, uint32_t flavour) {
+// tuning hook: lane budget of the first row/column pass (default 65536 = one wave per SIMD) and its multiplier flavour
+extern "C" int h2hip_debug_set_msm_rowcol(uint64_t lanes, int use_asm) {
     g_rowcol_lanes = lanes ? lanes : 65536;
-    g_rowcol_asm = flavour & 1;
-    g_rowcol_qtree = flavour & 2;
+    g_rowcol_asm = (uint32_t)use_asm & 1;
+    g_rowcol_qtree = (uint32_t)use_asm & 2;
+    return 0;
 }
 static bool g_split_buckets = true;
-void msm_set_split_buckets(bool on) { g_split_buckets = on; }
+// tuning hook: several lanes per bucket in runs with few buckets (1, default) or always one (0)
+extern "C" int h2hip_debug_set_msm_split_buckets(int on) { g_split_buckets = on != 0; return 0; }
 static bool g_quad_tail = true;
-void msm_set_quad_tail(bool on) { g_quad_tail = on; }
+// tuning hook: the reduction tail with one quad of lanes per group operation (1, default) or one lane (0)
+extern "C" int h2hip_debug_set_msm_quad_tail(int on) { g_quad_tail = on != 0; return 0; }
 static bool g_global_order = true;  // false: bucket order local to a sort bin (measured 1.3-1.8x slower accumulation)
-void msm_set_bucket_order(int local) { g_global_order = local == 0; }
-void msm_set_bin_entries(size_t d) { g_bin_entries = d ? d : 8192; }
-void msm_set_heavy_div(size_t d) { g_heavy_div = d ? d : 32768; }
+// tuning hook: 1 = order the buckets by size inside each sort bin only (no global pass); 0 = global order (default)
+extern "C" int h2hip_debug_set_msm_bucket_order(int local) { g_global_order = local == 0; return 0; }
+// tuning hook: target number of entries per coarse bin of the MSM's two-level sort (default 8192; 0 restores it)
+extern "C" int h2hip_debug_set_msm_bin_entries(size_t d) { g_bin_entries = d ? d : 8192; return 0; }
+// tuning hook: buckets above (entries of the MSM) / d go to the chunked path (default 32768; 0 restores it)
+extern "C" int h2hip_debug_set_msm_heavy_div(size_t d) { g_heavy_div = d ? d : 32768; return 0; }
 static size_t g_max_chunk = (size_t)1 << 26;
-void msm_set_max_chunk(size_t m) { g_max_chunk = m ? m : ((size_t)1 << 26); }
+// test hook: split inputs above m pairs into consecutive chunks (default 2^26, the 31-bit pair-index limit)
+extern "C" int h2hip_debug_set_msm_max_chunk(size_t m) { g_max_chunk = m ? m : ((size_t)1 << 26); return 0; }
 static uint32_t g_reserved_cus = 0;  // measured on MI355X: every partition (16..96 CUs) was slower than none
-void msm_set_reserved_cus(uint32_t k) { g_reserved_cus = k; }
+// undocumented tuning knob (not in the public header): CUs reserved for the sort / reduce stages of a batch
+extern "C" int h2hip_debug_set_reserved_cus(uint32_t k) { g_reserved_cus = k; return 0; }
 uint32_t msm_get_reserved_cus() { return g_reserved_cus; }
 void msm_set_window(uint32_t c) { g_window_override = c; }
+extern "C" int h2hip_set_msm_window(uint32_t c) {
+    if (c != 0 && (c < 2 || c > 24)) {
+        set_error("msm window must be 0 (auto) or 2..24");
+        return H2HIP_EINVAL;
+    }
+    msm_set_window(c);
+    return 0;
+}
 
 static uint32_t floor_log2(size_t n) {
     uint32_t lg = 0;
@@ -1211,6 +1230,7 @@ uint32_t msm_table_window(size_t n) {
     uint32_t c = lg <= 12 ? 13 : lg <= 17 ? 17 : lg <= 21 ? 20 : 22;  // up to 2^12 points the MSM is all reduction tail: few buckets
     return normalise_window(c);
 }
+extern "C" uint32_t h2hip_get_msm_window_fixed_base(size_t n) { return msm_table_window(n); }
 
 static MsmPlan make_plan(size_t n, bool fused, const MsmTable* tab, uint32_t force_c = 0) {
     MsmPlan p;
@@ -1236,7 +1256,7 @@ static MsmPlan make_plan(size_t n, bool fused, const MsmTable* tab, uint32_t for
     return p;
 }
 
-uint32_t msm_get_window(size_t n) { return make_plan(n, false, nullptr).c; }
+extern "C" uint32_t h2hip_get_msm_window(size_t n) { return make_plan(n, false, nullptr).c; }
 
 // host Horner over the set sums of one MSM in the plain form (arithmetic.rs:46-49): acc = sum_w 2^(pos_w) * S_w
 static XYZZ combine_windows(const XYZZ* ws, const MsmPlan& p) {
@@ -1534,7 +1554,13 @@ static void rowcol_jobs(RowColArgs* ra, const XYZZu* in, XYZZu* out_rows, XYZZu*
 }
 
 static bool g_plane_tail = true;
-void msm_set_plane_tail(bool on) { g_plane_tail = on; }
+// tuning hook: runs with at most 4 bucket sets finish the reduction on the host from bit-plane sums (1, default) or keep the GPU tail (0)
+extern "C" int h2hip_debug_set_msm_plane_tail(int on) {
+    Entry en;
+    if (en.rc) return en.rc;
+    g_plane_tail = on != 0;
+    return 0;
+}
 // whether a run's tail is finished on the host from bit-plane sums (msm_planes_kernel): few sets, one row / column level at least,
 // at most 16 workgroups (2^11 points) per plane, and the sums not wanted in HBM for the RCCL gather
 static bool msm_plane_tail(const Ctx* c, const MsmLayout& L) {
@@ -1821,6 +1847,12 @@ void msm_set_stream(uint32_t chunks, double ratio, size_t min_n) {
     g_stream_ratio = ratio > 0 ? ratio : 0.6;
     g_stream_min_n = min_n ? min_n : ((size_t)1 << 19);
 }
+// test / tuning hook: a host-resident MSM of at least min_n pairs streams in `chunks` pieces whose sizes grow by 1 / ratio
+// (ratio_permille / 1000 = upload time over compute time per pair); chunks = 1 turns streaming off; zeros restore the defaults
+extern "C" int h2hip_debug_set_msm_stream(uint32_t chunks, uint32_t ratio_permille, size_t min_n) {
+    msm_set_stream(chunks, ratio_permille / 1000.0, min_n);
+    return 0;
+}
 
 // The copies are issued by a helper thread (engine.h, copier_*): hipMemcpyAsync from pageable memory returns only when
 // its piece has left the host, and the thread that enqueues the kernels must not sit in it -- with one thread doing both, chunk
@@ -1859,14 +1891,16 @@ static void stream_ladder(size_t units, uint32_t K, double r, size_t quantum, st
     out->push_back(units - used);
 }
 
-// test hook (host only, no GPU): the chunk sizes a streamed MSM of n pairs would use
-size_t msm_debug_ladder(size_t n, uint32_t chunks, double ratio, bool with_bases, size_t* out, size_t cap) {
+// test hook, needs no GPU: the chunk sizes a streamed host-slice MSM of n pairs is cut into (chunks / ratio_permille 0 = the
+// defaults in force; with_bases: the points cross PCIe too); returns the number of chunks, sizes[0 .. min(that, cap))
+extern "C" size_t h2hip_debug_msm_stream_ladder(size_t n, uint32_t chunks, uint32_t ratio_permille, int with_bases, size_t* sizes, size_t cap) {
+    if (!sizes && cap) return 0;
     std::vector<size_t> sz;
     const uint32_t k0 = chunks ? chunks : g_stream_chunks;
-    const double r = ratio > 0 ? ratio : g_stream_ratio;
+    const double r = ratio_permille ? ratio_permille / 1000.0 : g_stream_ratio;
     const uint32_t kk = !chunks && g_stream_chunks_default && n < ((size_t)1 << 20) ? 2 : k0;
     stream_ladder(n, with_bases ? 2 * kk : kk, with_bases ? 2.0 * r : r, 4096, &sz);
-    for (size_t i = 0; i < sz.size() && i < cap; i++) out[i] = sz[i];
+    for (size_t i = 0; i < sz.size() && i < cap; i++) sizes[i] = sz[i];
     return sz.size();
 }
 
@@ -2027,9 +2061,15 @@ static int msm_fused_groups_host(Ctx* c, const Fe* const* h_scalars, const Affin
 
 // measured (tools/fuse_big.py, 8 MSMs per batch, per MSM): 2^19 pairs fused 0.66 ms / pipelined 0.69 ms, 2^20 pairs fused 1.24 / pipelined 1.16
 static size_t g_fuse_entries = (size_t)1 << 26, g_fuse_max_n = (size_t)1 << 19;
-void msm_set_fuse_limits(size_t entries, size_t max_n) { g_fuse_entries = entries ? entries : ((size_t)1 << 26); g_fuse_max_n = max_n ? max_n : ((size_t)1 << 19); }
+// tuning hook: a fused run holds at most `entries` entries (default 2^26) and fusing applies up to `max_n` pairs per MSM (default 2^18); 0 = default
+extern "C" int h2hip_debug_set_msm_fuse_limits(size_t entries, size_t max_n) {
+    g_fuse_entries = entries ? entries : ((size_t)1 << 26);
+    g_fuse_max_n = max_n ? max_n : ((size_t)1 << 19);
+    return 0;
+}
 static bool g_fuse_small = true;
-void msm_set_fuse_small(bool on) { g_fuse_small = on; }
+// test / tuning hook: batches of small MSMs run fused (default) or pipelined over streams
+extern "C" int h2hip_debug_set_msm_fuse_small(int on) { g_fuse_small = on != 0; return 0; }
 
 // count MSMs over the same bases; results (XYZZ) to host memory.  tab != nullptr: the fixed-base form over tab's table
 // (d_bases is then unused).  scalars_on_host: scalars[j] are host pointers.  h_bases != nullptr: the bases are the

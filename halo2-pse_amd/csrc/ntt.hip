@@ -471,17 +471,23 @@ void ntt_twiddles_free(Ctx* c) {
 
 static uint64_t g_ntt_full_budget = (uint64_t)4 << 30;  // HALO2_HIP_NTT_TWIDDLE_MB: HBM the full inter-pass tables may take per device (of 288 GB)
 void ntt_set_full_twiddle_budget(uint64_t bytes) { g_ntt_full_budget = bytes; }
+// tuning hook: HBM (bytes per device) the two-pass plan's full inter-pass twiddle tables may take; 0 = two-level table only
+extern "C" int h2hip_debug_set_ntt_twiddle_budget(uint64_t bytes) { g_ntt_full_budget = bytes; return 0; }
 static size_t g_ntt_batch_bytes = (size_t)2 << 30;  // columns + workspace one batched launch may span (ntt_device_batch)
-void ntt_set_batch_bytes(uint64_t bytes) { g_ntt_batch_bytes = bytes ? (size_t)bytes : (size_t)2 << 30; }
+// tuning hook: bytes of columns + workspace one launch of a batched transform spans (0 = default)
+extern "C" int h2hip_debug_set_ntt_batch_bytes(uint64_t bytes) { g_ntt_batch_bytes = bytes ? (size_t)bytes : (size_t)2 << 30; return 0; }
 // Strided passes of the three-pass plan read their inter-pass twiddles from a table of up to 2^this entries (36 B each: 0.3 / 0.6 GB per domain
 // and direction at 2^23 / 2^24 for the first pass's, 2.4 MB for the second's) while the budget lasts: one multiplication per point fewer than
 // combining the two-level table (2^23 -5 %, 2^24 -2.5 %; at 2^25 and beyond the pass has no memory bandwidth to spare for it and nothing is gained).
 static uint32_t g_ntt_full_max_log_m = 24;
-void ntt_set_full_max_log_m(uint32_t v) { g_ntt_full_max_log_m = v ? v : 24; }
+// tuning hook: the largest strided pass (log2 of its M) that reads its inter-pass twiddles from a table (0 = default 24)
+extern "C" int h2hip_debug_set_ntt_full_max_log_m(uint32_t v) { g_ntt_full_max_log_m = v ? v : 24; return 0; }
 static bool g_ntt_fold_tables = true;  // the inverse's 1/n rides in a scaled copy of the first pass's table (A/B: h2hip_debug_set_ntt_fold_tables)
-void ntt_set_fold_tables(bool on) { g_ntt_fold_tables = on; }
+// A/B hook: 0 = the inverse transform's 1/n is multiplied in by the last pass even where the first pass reads a table (rounds 1-3)
+extern "C" int h2hip_debug_set_ntt_fold_tables(int on) { g_ntt_fold_tables = on != 0; return 0; }
 static int g_ntt2_log_j = -1;  // tuning: columns per workgroup of the two-pass kernels (-1 = the plan's choice)
-void ntt_set_two_pass_log_j(int v) { g_ntt2_log_j = v; }
+// tuning hook: log2 columns per workgroup of the two-pass kernels (-1 = default)
+extern "C" int h2hip_debug_set_ntt_two_pass_log_j(int v) { g_ntt2_log_j = v; return 0; }
 
 static int get_twiddles(Ctx* c, const Fe& omega, uint32_t log_n, hipStream_t s, TwiddleTable* out) {
     TwiddleKey key;
@@ -673,7 +679,7 @@ int scale_periodic_device(Ctx* c, Fe* d_a, uint64_t n, const uint64_t* h_t, uint
 }
 
 static uint32_t g_ntt_smax = 8;
-void ntt_set_smax(uint32_t v) { g_ntt_smax = v < 4 ? 4 : (v > 10 ? 10 : v); }
+extern "C" int h2hip_debug_set_ntt_smax(uint32_t v) { g_ntt_smax = v < 4 ? 4 : (v > 10 ? 10 : v); return 0; }
 // Sizes 2^lo..2^hi take the two-pass plan (tiles of 2^10 or 2^11 points, ntt2_*_kernel): measured on MI355X
 // (tools/ntt_two_pass.py) 14 % faster than three passes at 2^20, 9 % at 2^21, 5 % at 2^22 with two columns per workgroup, 25 / 19 / 12 % with one
 // (round 3); below 2^19 a lone transform brings too few workgroups.
@@ -683,18 +689,21 @@ void ntt_set_smax(uint32_t v) { g_ntt_smax = v < 4 ? 4 : (v > 10 ? 10 : v); }
 static uint32_t g_ntt_two_lo = 19, g_ntt_two_hi = 22, g_ntt_two_batch_lo = 17;
 static uint64_t g_ntt_two_batch_wgs = 512;
 static bool g_ntt_lds_attr[64];
-void ntt_set_two_pass(uint32_t lo, uint32_t hi) {
+// tuning hook: sizes 2^lo..2^hi (within 18..22) take the two-pass plan; hi < lo turns it off
+extern "C" int h2hip_debug_set_ntt_two_pass(uint32_t lo, uint32_t hi) {
     if (lo == 0 && hi == 0) {  // the defaults
         g_ntt_two_lo = 19;
         g_ntt_two_hi = 22;
         g_ntt_two_batch_lo = 17;
-        return;
+        return 0;
     }
     g_ntt_two_lo = lo < 16 ? 16 : lo;
     g_ntt_two_hi = hi > 22 ? 22 : hi;
     g_ntt_two_batch_lo = g_ntt_two_lo < 17 ? g_ntt_two_lo : hi < lo ? 64 : 17;  // hi < lo turns the plan off altogether
+    return 0;
 }
-void ntt_set_two_pass_batch_wgs(uint64_t v) { g_ntt_two_batch_wgs = v ? v : 512; }
+// tuning hook: pairs of workgroups per pass from which batched columns of 2^17 / 2^18 points take the two-pass plan (0 = default 512)
+extern "C" int h2hip_debug_set_ntt_two_pass_batch_wgs(uint64_t v) { g_ntt_two_batch_wgs = v ? v : 512; return 0; }
 
 // pass radices: one pass up to 2^10, otherwise ceil(log_n / smax) passes of near-equal radix
 static int plan_passes(uint32_t log_n, uint32_t s_out[4]) {
@@ -962,7 +971,7 @@ int ntt_device_batch(Ctx* c, Fe* const* h_datas, const Fe* const* h_srcs, size_t
 
 }  // namespace h2
 
-// test hook, needs no GPU: the passes ntt_run would take for this call (here, not in api.hip: that file is also built alone against a stub runtime)
+// test hook, needs no GPU: the passes ntt_run would take for this call
 extern "C" int h2hip_debug_ntt_plan(uint32_t log_n, size_t count, uint32_t radices[4]) {
     if (!radices || log_n > h2::FrP::S) return -1;
     bool two;

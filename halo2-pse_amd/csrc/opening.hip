@@ -449,7 +449,6 @@ using namespace h2;
 
 extern "C" {
 // ---- C ABI (include/halo2hip.h, "opening") ---------------------------------------------------------------------------------
-// Here rather than in api.hip for the reason product.hip gives: api.hip is also compiled alone against a stub runtime.
 static int eval_check(const void* const* polys, const size_t* lens, size_t n_polys, const uint32_t* query_poly, const uint64_t* points,
                       size_t n_queries, const uint64_t* evals) {
     const char* what = "eval_polynomials";

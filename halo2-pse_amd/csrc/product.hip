@@ -490,8 +490,6 @@ using namespace h2;
 
 extern "C" {
 // ---- C ABI (include/halo2hip.h, "grand products") ----------------------------------------------------------------------------------
-// Here rather than in api.hip: api.hip is also compiled alone, as plain C++ against a stub runtime, for the ThreadSanitizer test of the
-// engine's host logic, and the stubs stand in for the kernels of the other translation units only.
 static int products_check_common(const char* what, uint32_t k, uint32_t bf, const uint64_t* blinding, size_t n_outputs) {
     if (int rc = check_k_blinding(what, k, bf)) return rc;
     if (bf && n_outputs && !blinding) {

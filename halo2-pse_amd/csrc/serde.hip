@@ -220,7 +220,6 @@ using namespace h2;
 
 extern "C" {
 // ---- C ABI (include/halo2hip.h, "serialisation") ---------------------------------------------------------------------------------------
-// Here rather than in api.hip, for the reason product.hip gives.
 static int sd_args(const char* what, const void* in, const void* out, bool has_out, size_t n, const uint64_t* invalid, bool has_invalid) {
     if (n > SD_MAX_N) {
         set_error("%s: n = %zu > 2^30", what, n);

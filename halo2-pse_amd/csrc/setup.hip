@@ -117,3 +117,41 @@ int kzg_setup_device(Ctx* c, uint32_t k, const Fe& s, Affine* d_g, Affine* d_gl,
 }
 
 }  // namespace h2
+
+using namespace h2;
+
+extern "C" {
+// ---- C ABI (include/halo2hip.h) ---------------------------------------------------------------------------------------------------
+int h2hip_kzg_setup_bn254_device(uint32_t k, const uint64_t secret[4], void* d_g_xy, void* d_g_lagrange_xy, void* stream) {
+    if (!secret || !d_g_xy || !d_g_lagrange_xy) {
+        set_error("kzg_setup: null argument");
+        return H2HIP_EINVAL;
+    }
+    if (check_fr(secret, "secret")) return H2HIP_EINVAL;
+    Entry en("h2hip_kzg_setup_bn254_device", d_g_xy);
+    if (en.rc) return en.rc;
+    return kzg_setup_device(en.c, k, fe_from_u64x4(secret), (Affine*)d_g_xy, (Affine*)d_g_lagrange_xy, (hipStream_t)stream);
+}
+
+int h2hip_kzg_setup_bn254(uint32_t k, const uint64_t secret[4], uint64_t* g_xy, uint64_t* g_lagrange_xy) {
+    if (!secret || !g_xy || !g_lagrange_xy || k > 28) {
+        set_error("kzg_setup: bad argument");
+        return H2HIP_EINVAL;
+    }
+    if (check_fr(secret, "secret")) return H2HIP_EINVAL;
+    Entry en("h2hip_kzg_setup_bn254");
+    if (en.rc) return en.rc;
+    Ctx* c = en.c;
+    const size_t bytes = sizeof(Affine) << k;
+    int rc = c->ntt_io.ensure(2 * bytes);
+    if (rc) return rc;
+    Affine* d_g = (Affine*)c->ntt_io.p;
+    Affine* d_gl = (Affine*)((char*)c->ntt_io.p + bytes);
+    if ((rc = kzg_setup_device(c, k, fe_from_u64x4(secret), d_g, d_gl, c->stream))) return rc;
+    H2_CHECK(hipMemcpyAsync(g_xy, d_g, bytes, hipMemcpyDeviceToHost, c->stream));
+    H2_CHECK(hipMemcpyAsync(g_lagrange_xy, d_gl, bytes, hipMemcpyDeviceToHost, c->stream));
+    H2_CHECK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+}  // extern "C"

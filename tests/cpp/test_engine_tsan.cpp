@@ -1,5 +1,5 @@
 // Host logic of csrc/api.hip under ThreadSanitizer, no GPU: the file is compiled as plain C++ against a stub HIP
-// runtime (tests/cpp/hipstub: N fake gfx950 devices, device memory = host memory) with the compute kernels' host drivers replaced by
+// runtime (tests/cpp/hipstub: N fake gfx950 devices, device memory = host memory) with what it calls in the stage files replaced by
 // stand-ins (engine_stubs.cpp), and driven from several threads at once:
 //   * entry points that lock ONE context (device-pointer transforms on either device) next to entry points that lock ALL of them
 //     (host-pointer MSMs sharded over the devices, pin / unpin / pinned-info), lock order = device-list order;
