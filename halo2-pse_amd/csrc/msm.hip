@@ -588,12 +588,22 @@ __global__ void __launch_bounds__(256, 4) msm_accum_kernel(const char* __restric
         const PBuf pbuf = reinterpret_cast<PBuf>(lds_raw);
         static_assert(4 * NCH * 64 * sizeof(uint4) <= sizeof(lds_raw), "the point buffer fits the block's LDS");
         const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+        // The instruction's immediate offset is added to the source address AND to the LDS address, so piece ch is one instruction on
+        // the record's address with offset 16 ch, its LDS base moved back by those 16 ch bytes; the bases are scalars formed once.
+        const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)&pbuf[wave][0][0]);
+        auto piece = [&](const char* g, auto ch) __attribute__((always_inline)) {
+            constexpr int CH = decltype(ch)::value;
+            if constexpr (CH < NCH)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
+                                                 (__attribute__((address_space(3))) void*)(uintptr_t)(lds0 + CH * (64 * 16 - 16)), 16, 16 * CH, 0);
+        };
         auto issue = [&](uint32_t v) __attribute__((always_inline)) {
             const char* g = bases + (size_t)(v & 0x7fffffffu) * rec;
-#pragma unroll
-            for (int ch = 0; ch < NCH; ch++)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + 16 * ch),
-                                                 (__attribute__((address_space(3))) void*)&pbuf[wave][ch][0], 16, 0, 0);
+            piece(g, std::integral_constant<int, 0>());
+            piece(g, std::integral_constant<int, 1>());
+            piece(g, std::integral_constant<int, 2>());
+            piece(g, std::integral_constant<int, 3>());
+            piece(g, std::integral_constant<int, 4>());
         };
         uint32_t w[4 * NCH];  // the record's words
         auto take = [&]() __attribute__((always_inline)) {
@@ -608,7 +618,7 @@ __global__ void __launch_bounds__(256, 4) msm_accum_kernel(const char* __restric
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the buffer is free for the next fetch
         };
-        uint32_t acc_id = 1;  // native records: 1 while acc is the identity (xyzzu_add_native)
+        uint32_t acc_st = ACC_IDENTITY;  // what the lane knows of acc (ecu.h ACC_*): the identity, a bucket's first record as it is, or any point
         auto add = [&](uint32_t v) __attribute__((always_inline)) {  // throughput-bound: explicit-mad multiplier
             if constexpr (NATIVE) {
                 AffineU p;
@@ -619,7 +629,7 @@ __global__ void __launch_bounds__(256, 4) msm_accum_kernel(const char* __restric
                 }
                 p.valid = w[18];
                 p.pad = 0;
-                xyzzu_add_native<FqUA>(acc, acc_id, p, (v >> 31) != 0);
+                xyzzu_add_native_st<FqUA>(acc, acc_st, p, (v >> 31) != 0);
             } else {
                 Affine p;
 #pragma unroll
@@ -627,14 +637,14 @@ __global__ void __launch_bounds__(256, 4) msm_accum_kernel(const char* __restric
                     p.x.l[i] = w[i];
                     p.y.l[i] = w[8 + i];
                 }
-                xyzzu_add_affine<FqUA>(acc, p, (v >> 31) != 0);
+                xyzzu_add_affine<FqUA>(acc, acc_st, p, (v >> 31) != 0);
             }
         };
         uint32_t v = vals[s + sub];
         issue(v);
         if (cont) {
             acc = *mine;
-            acc_id = xyzzu_is_identity(acc) ? 1u : 0u;
+            acc_st = xyzzu_is_identity(acc) ? ACC_IDENTITY : ACC_POINT;
         }
         store = true;
         for (uint32_t i = s + sub + S; i < e; i += S) {
@@ -740,11 +750,11 @@ __device__ __noinline__ void msm_heavy_role(const char* __restrict__ bases, uint
     for (uint32_t ci = blockIdx.x; ci < total; ci += hgrid) {
         const HeavyChunk ch = heavy_chunks[ci];
         XYZZu acc = xyzzu_identity();
-        uint32_t acc_id = 1;
+        uint32_t acc_st = ACC_IDENTITY;
         auto fetch = [&](uint32_t v) { return *reinterpret_cast<const Rec*>(bases + (size_t)(v & 0x7fffffffu) * rec); };
         auto add = [&](const Rec& p, uint32_t v) {
-            if constexpr (NATIVE) xyzzu_add_native<FqU>(acc, acc_id, p, (v >> 31) != 0);
-            else xyzzu_add_affine<FqU>(acc, p, (v >> 31) != 0);
+            if constexpr (NATIVE) xyzzu_add_native_st<FqU>(acc, acc_st, p, (v >> 31) != 0);
+            else xyzzu_add_affine<FqU>(acc, acc_st, p, (v >> 31) != 0);
         };
         uint32_t i = ch.begin + threadIdx.x;
         if (i < ch.end) {

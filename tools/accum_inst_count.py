@@ -14,6 +14,12 @@ has 6 products, 2 squares and one two-product form, 6 * 162 + 2 * 126 + 243 = 14
 not an ordinary addition (it skipped it, or took the doubling instead); of the others the one with the fewest VALU instructions is the
 normal path.  The per-block table is printed too, so the choice can be checked by eye.
 
+The UNIT PATH is the addition onto an accumulator that is a bucket's first record (zz = zzz = one: ecu.h xyzzu_add_mixed_nonid with unit set): 1 square,
+2 products and the two fused forms, 2 * 126 + 2 * 162 + 243 = 819 multiply-adds on native records; E-form records keep the two
+products by one, 1143.  It is found the same way: of the paths with at least 700 and fewer than 1400 multiply-adds the one with the
+fewest VALU instructions (a doubling has 945 or more and two exact reductions on top, so it never wins).  The kernel's registers,
+scratch and occupancy are printed from the assembly's resource comment.
+
   python3 tools/accum_inst_count.py [--package DIR] [--json]
 
 --package: the directory holding the Makefile and csrc/ (default: this checkout's); point it at another checkout to count that one.
@@ -28,6 +34,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FULL_ADD_MADS = 1400  # see the docstring
+UNIT_ADD_MADS = 700
 MADS = ("v_mad_u64_u32", "v_mad_i64_i32")
 
 
@@ -59,6 +66,24 @@ def kernels(lines):
             name = None
         elif name:
             body.append(ln)
+    return found
+
+
+def resources(lines):
+    """name -> {vgprs, sgprs, scratch_bytes, occupancy} from the comment block after each msm_accum_kernel"""
+    keys = {"NumVgprs": "vgprs", "NumSgprs": "sgprs", "ScratchSize": "scratch_bytes", "Occupancy": "occupancy"}
+    found, name = {}, None
+    for ln in lines:
+        m = re.match(r"^(_Z\w*msm_accum_kernel\w*):", ln)
+        if m:
+            name = m.group(1)
+            found[name] = {}
+            continue
+        m = re.match(r"^; (\w+): (\d+)\s*$", ln)
+        if name and m and m.group(1) in keys:
+            found[name].setdefault(keys[m.group(1)], int(m.group(2)))
+        elif name and ln.startswith(("_Z", ".amdhsa_kernel")) and found[name]:
+            name = None
     return found
 
 
@@ -99,7 +124,7 @@ def normal_path(body):
     inside = set(by_loop[header])
     index = {b[0]: i for i, b in enumerate(blocks)}
     start = index[header]
-    best = None
+    best = unit = None
     table = [(blocks[i][0],) + count(blocks[i][2]) for i in sorted(inside)]
 
     # walk instruction by instruction: a block may hold several branches
@@ -122,10 +147,12 @@ def normal_path(body):
         leave(i + 1, valu, mad, seen, trail)
 
     def leave(t, valu, mad, seen, trail):
-        nonlocal best
+        nonlocal best, unit
         if t == start:
             if mad >= FULL_ADD_MADS and (best is None or valu < best[0]):
                 best = (valu, mad, list(trail))
+            if UNIT_ADD_MADS <= mad < FULL_ADD_MADS and (unit is None or valu < unit[0]):
+                unit = (valu, mad, list(trail))
             return
         if t not in inside or t in seen:
             return
@@ -133,7 +160,7 @@ def normal_path(body):
 
     sys.setrecursionlimit(10000)
     walk(start, 0, 0, 0, {start}, [header])
-    return header, table, best
+    return header, table, best, unit
 
 
 def short(name):
@@ -149,12 +176,16 @@ def main():
     ap.add_argument("--json", action="store_true")
     args = ap.parse_args()
     res = {}
-    for name, body in sorted(kernels(compile_asm(args.package)).items()):
+    lines = compile_asm(args.package)
+    res_of = resources(lines)
+    for name, body in sorted(kernels(lines).items()):
         r = normal_path(body)
         if not r or not r[2]:
             continue
-        header, table, (valu, mad, trail) = r
+        header, table, (valu, mad, trail), unit = r
         res[short(name)] = {"valu_per_addition": valu, "mad64_per_addition": mad, "loop_header": header, "path": trail,
+                            "unit_path": {"valu_per_addition": unit[0], "mad64_per_addition": unit[1], "path": unit[2]} if unit else None,
+                            "resources": res_of.get(name, {}),
                             "loop_blocks": [{"block": b, "valu": v, "mad64": m} for b, v, m in table]}
     if args.json:
         print(json.dumps(res, indent=1))
@@ -164,6 +195,15 @@ def main():
         print("  VALU instructions per addition : %d" % r["valu_per_addition"])
         print("  64-bit multiply-adds among them: %d" % r["mad64_per_addition"])
         print("  path  : " + " ".join(r["path"]))
+        u = r["unit_path"]
+        if u:
+            print("  unit path (the addition onto a bucket's first record)")
+            print("  VALU instructions per addition : %d" % u["valu_per_addition"])
+            print("  64-bit multiply-adds among them: %d" % u["mad64_per_addition"])
+            print("  path  : " + " ".join(u["path"]))
+        else:
+            print("  unit path: none found")
+        print("  resources: " + ", ".join("%s %d" % kv for kv in sorted(r["resources"].items())))
         print("  blocks of the loop (VALU / 64-bit multiply-adds): " + ", ".join("%s %d/%d" % (b["block"], b["valu"], b["mad64"]) for b in r["loop_blocks"]))
 
 
