@@ -1362,6 +1362,19 @@ class ParamsKZG:
         assert self.g.shape[0] >= size  # :332
         return self._msm(poly, self.g, self._d_g)
 
+    def commit_device(self, d_poly, n=None):
+        """commit for a coefficient polynomial that lives in HBM (n x 32 B): an MSM over g resident in HBM and pinned by its device
+        pointer -- read_custom's copy, or one uploaded at the first call and kept until close"""
+        d_g = self._d_g
+        if d_g is None:
+            d_g = getattr(self, "_d_g_resident", None)
+            if d_g is None:
+                import torch
+                d_g = torch.from_numpy(self.g.view(np.int64)).cuda()
+                bases_pin_device(d_g, self.n)
+                self._d_g_resident = d_g
+        return msm_device(d_poly, d_g, n)
+
     def downsize(self, k):
         """ParamsKZG::downsize (poly/kzg/commitment.rs:267-275)"""
         assert k <= self.k  # :268
@@ -1385,6 +1398,13 @@ class ParamsKZG:
                 else:
                     bases_unpin_device(d)
                     setattr(self, "_d_" + name, None)
+            except H2HipError:
+                pass
+        d = getattr(self, "_d_g_resident", None)
+        if d is not None:
+            self._d_g_resident = None
+            try:
+                bases_unpin_device(d)
             except H2HipError:
                 pass
 
@@ -1682,6 +1702,85 @@ def gen_points_device(seed, n, start=0, device="cuda"):
     _check(lib().h2hip_gen_points_device(ctypes.c_uint64(seed), ctypes.c_uint64(start), ctypes.c_size_t(n), _dptr(out), _stream()),
            "h2hip_gen_points_device")
     return out
+
+
+# ------------------------------------------------------------------ randomness (csrc/random.hip)
+def _seed32(seed):
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("a seed is 32 bytes, got %d" % len(seed))
+    return (ctypes.c_uint8 * 32).from_buffer_copy(seed)
+
+
+def fr_random(seed, n, first_block=0, stream_id=0):
+    """n draws of Fr::random from ChaCha20Rng::from_seed(seed) that has made first_block draws: element i is Fr::from_bytes_wide of
+    ChaCha20 block first_block + i -> (n, 4) uint64 Montgomery.  Below HALO2_HIP_RANDOM_MIN_N elements this runs on the calling thread
+    and needs no GPU.  The seed is as secret as the elements: the engine expands it and adds no entropy."""
+    out = np.zeros((int(n), 4), dtype=np.uint64)
+    _check(lib().h2hip_fr_random_bn254(_seed32(seed), ctypes.c_uint64(stream_id), ctypes.c_uint64(first_block), ctypes.c_size_t(int(n)), _p(out)),
+           "h2hip_fr_random_bn254")
+    return out
+
+
+def fr_random_device(seed, n, first_block=0, stream_id=0, out=None):
+    """the same draws left in HBM: a torch CUDA tensor (n, 4) int64, `out` when given (n x 32 B); the kernel is queued, not waited for"""
+    if out is None:
+        if device_count() < 1:
+            raise H2HipError("fr_random_device: no GPU (no CPU fallback exists)")
+        import torch
+        out = torch.empty((int(n), 4), dtype=torch.int64, device="cuda")
+    _check(lib().h2hip_fr_random_bn254_device(_seed32(seed), ctypes.c_uint64(stream_id), ctypes.c_uint64(first_block), ctypes.c_size_t(int(n)),
+                                              _dptr(out), _stream()), "h2hip_fr_random_bn254_device")
+    return out
+
+
+def fr_from_bytes_wide(data):
+    """Fr::from_bytes_wide over (n, 64) uint8: each 64 bytes as one little-endian integer mod r -> (n, 4) uint64 Montgomery"""
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    if data.ndim != 2 or data.shape[1] != 64:
+        raise ValueError("fr_from_bytes_wide: expected shape (n,64), got %s" % (data.shape,))
+    out = np.zeros((data.shape[0], 4), dtype=np.uint64)
+    _check(lib().h2hip_fr_from_bytes_wide_bn254(_p(data), ctypes.c_size_t(data.shape[0]), _p(out)), "h2hip_fr_from_bytes_wide_bn254")
+    return out
+
+
+def fr_from_bytes_wide_device(d_bytes, d_out, n):
+    """d_bytes: n x 64 B, d_out: n x 32 B (torch CUDA tensors, not overlapping); queued on the current stream"""
+    _check(lib().h2hip_fr_from_bytes_wide_bn254_device(_dptr(d_bytes), ctypes.c_size_t(n), _dptr(d_out), _stream()),
+           "h2hip_fr_from_bytes_wide_bn254_device")
+
+
+class FrRng:
+    """ChaCha20Rng::from_seed(seed) as far as Fr::random uses it: every draw consumes one 64-byte block, so the state is the number of
+    the next block.  draw / draw_device hand out consecutive blocks, which lets a mirror prover take all of a proof's draws from one
+    stream in the reference's order, whichever of them are made on the GPU.  The seed is as secret as everything drawn from it; this
+    object keeps it as Python bytes, which cannot be wiped (the library wipes its own copies, the C++ mirror's FrRng its seed)."""
+
+    def __init__(self, seed, stream_id=0):
+        self.seed, self.stream_id, self.block = bytes(seed), int(stream_id), 0
+        _seed32(self.seed)
+
+    def draw(self, n=1):
+        out = fr_random(self.seed, n, self.block, self.stream_id)
+        self.block += int(n)
+        return out
+
+    def draw_device(self, n, out=None):
+        out = fr_random_device(self.seed, n, self.block, self.stream_id, out)
+        self.block += int(n)
+        return out
+
+
+def vanishing_commit(params, domain, rng):
+    """vanishing::Argument::commit (plonk/vanishing/prover.rs:36-67) with rng an FrRng: the random polynomial of 2^k coefficients is drawn
+    into HBM (blocks [c, c + 2^k) of the stream), its blind is the next draw (block c + 2^k), and the commitment is the MSM over the
+    resident, pinned g.  Returns (the device polynomial (2^k, 4), the blind (4,), the commitment (12,) Jacobian); nothing of 2^k
+    elements crosses PCIe.  Writing the commitment to the transcript stays with the caller."""
+    n = 1 << domain.k
+    assert params.g.shape[0] >= n  # assert!(bases.len() >= size), poly/kzg/commitment.rs:332
+    d_poly = rng.draw_device(n)
+    blind = rng.draw(1)[0]
+    return d_poly, blind, params.commit_device(d_poly, n)
 
 
 def to_numpy_u64(t):

@@ -922,6 +922,7 @@ static void release_ctx(Ctx* c) {
     c->check_flag.release();
     c->serde_ws.release();
     c->serde_io.release();
+    c->random_io.release();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     c->stream = nullptr;
     for (auto e : c->aux_events) (void)hipEventDestroy(e);

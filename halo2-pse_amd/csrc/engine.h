@@ -175,6 +175,7 @@ struct Ctx {
     DevBuf check_ws, check_io;     // check.hip: failure masks, tile counts, row lists and sort keys; the host-pointer forms' columns
     HostBuf check_flag;            // check.hip: the out-of-range flag of a permutation check read back at the end of the call
     DevBuf serde_ws, serde_io;     // serde.hip: failure mask, tile counts and the two result words; the host-pointer forms' elements
+    DevBuf random_io;              // random.hip: the host-pointer forms' elements, from their threshold on
     HostBuf host_ws;               // pinned host memory for the window sums coming back
     HostBuf host_planes;           // ... and for the bit-plane sums of a run whose tail the host finishes (msm.hip msm_planes_finish)
     HostBuf pin_flag;              // one word the device-key fingerprint check writes its verdict to

@@ -76,6 +76,12 @@ struct FrU {  // scalar field, 29-bit limbs
                                           0x11b7bc3cu, 0x1cbd99bau, 0x183340fbu, 0x000e0a77u};
     static constexpr uint32_t P16[9] = {0x00000010u, 0x10fac9f8u, 0x05c2450fu, 0x1d090f37u, 0x185d2833u,
                                         0x0db40c0au, 0x0a6e1411u, 0x05c26340u, 0x030644e7u};
+    // integer -> E-form on the multiplier, for the two halves lo + hi * 2^256 of a 512-bit integer (random_elem.h): fu_mul by WIDE_LO_I
+    // gives lo * 2^256, by WIDE_HI_I hi * 2^512
+    static constexpr uint32_t WIDE_LO_I[9] = {0x142db4dfu, 0x19d6990eu, 0x1472f48cu, 0x06dbe7e3u, 0x0b84d579u,
+                                              0x10f9faf7u, 0x121f4380u, 0x17a112deu, 0x001275c7u};  // 2^517 mod r
+    static constexpr uint32_t WIDE_HI_I[9] = {0x17e007f8u, 0x1c5b7cb8u, 0x0ad4a06cu, 0x08aaffa3u, 0x13abc077u,
+                                              0x0f7013f7u, 0x190d945au, 0x1b1dfff5u, 0x001be8b5u};  // 2^773 mod r
 };
 
 // Same fields with the multiplier's 162 multiply-adds written as explicit v_mad instructions in column order

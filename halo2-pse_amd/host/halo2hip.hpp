@@ -219,6 +219,43 @@ inline void engine_check(int rc, const char* what) {
     if (rc != 0) throw std::runtime_error(std::string(what) + ": " + h2hip_last_error());
 }
 
+// ChaCha20Rng::from_seed(seed) as far as Fr::random uses it (rand_chacha 0.3, halo2curves 0.3.1 as DESIGN.md section 2 records them):
+// every draw consumes one 64-byte block, so the state is the number of the next block, and a whole column of draws is one engine call
+// (h2hip_fr_random_bn254: on the calling thread for a handful, on the GPU from HALO2_HIP_RANDOM_MIN_N elements on).  Draws come out in
+// the stream's order whichever way they are made.  The seed is the caller's entropy and as secret as what is drawn; wiped on destruction.
+class FrRng {
+   public:
+    explicit FrRng(const std::array<uint8_t, 32>& seed, uint64_t stream_id = 0) : seed_(seed), stream_id_(stream_id) {}
+    FrRng(const FrRng&) = delete;
+    FrRng& operator=(const FrRng&) = delete;
+    ~FrRng() {
+        volatile uint8_t* p = seed_.data();
+        for (size_t i = 0; i < 32; i++) p[i] = 0;
+    }
+    uint64_t block() const { return block_; }  // draws made so far
+    // n draws of <Fr as Field>::random(&mut rng)
+    void fill(Fr* out, size_t n) {
+        engine_check(h2hip_fr_random_bn254(seed_.data(), stream_id_, block_, n, n ? out[0].l : nullptr), "h2hip_fr_random_bn254");
+        block_ += n;
+    }
+    Fr operator()() {
+        Fr v;
+        fill(&v, 1);
+        return v;
+    }
+
+   private:
+    std::array<uint8_t, 32> seed_;
+    uint64_t stream_id_, block_ = 0;
+};
+
+// Fr::from_bytes_wide: 64 bytes as one little-endian integer, reduced mod r
+inline Fr fr_from_bytes_wide(const uint8_t bytes[64]) {
+    Fr v;
+    engine_check(h2hip_fr_from_bytes_wide_bn254(bytes, 1, v.l), "h2hip_fr_from_bytes_wide_bn254");
+    return v;
+}
+
 namespace arithmetic {
 
 // pub fn best_multiexp<C: CurveAffine>(coeffs: &[C::Scalar], bases: &[C]) -> C::Curve   (arithmetic.rs:132)
@@ -681,6 +718,27 @@ class ParamsKZG {
 // The grand-product columns of create_proof (h2hip_permutation_products_bn254 / h2hip_lookup_products_bn254).  Blinding values are the
 // caller's, drawn in the reference's order: b per set or lookup, set-major.
 namespace plonk {
+
+// vanishing::Argument::commit (plonk/vanishing/prover.rs:36-67): the random polynomial of 2^k coefficients as ONE engine call instead of
+// 2^k serial draws, then its blind -- the stream's blocks [c, c + 2^k) and c + 2^k, the order the reference's loop draws in -- and the
+// commitment over the pinned g.  This mirror holds host vectors, so the column is generated on the GPU and comes back once; the
+// resident form, where it never leaves HBM, is h2hip_fr_random_bn254_device followed by h2hip_msm_bn254_device.  Writing the
+// commitment to the transcript (:61) stays with the caller.
+namespace vanishing {
+struct Committed {
+    poly::Polynomial<poly::Coeff> random_poly;
+    poly::Blind random_blind;
+};
+struct Argument {
+    static Committed commit(const poly::kzg::ParamsKZG& params, const poly::EvaluationDomain& domain, FrRng& rng, G1* commitment) {
+        Committed c{{std::vector<Fr>(domain.n)}, {Fr::zero()}};  // domain.empty_coeff(), :52
+        rng.fill(c.random_poly.values.data(), c.random_poly.len());  // :53-55
+        c.random_blind.r = rng();                                     // :57
+        *commitment = params.commit(c.random_poly, c.random_blind);   // :60
+        return c;
+    }
+};
+}  // namespace vanishing
 
 // permutation::Argument::commit's z columns (plonk/permutation/prover.rs:96-166): one per set of chunk_len columns, last_z carried
 // from set to set.  columns[c] = p_c resolved from advice / fixed / instance, permutations[c] = pkey.permutations[c].

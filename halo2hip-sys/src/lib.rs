@@ -704,3 +704,34 @@ pub fn try_fr_to_repr<F: Field + 'static>(values: &[F]) -> Option<Vec<[u8; 32]>>
     }
     Some(out)
 }
+
+// ---- randomness (include/halo2hip.h, "randomness") ------------------------------------------------------------------------------------
+
+/// `n` draws of `F::random` as `ChaCha20Rng::from_seed(*seed)` yields them after `first_block` earlier draws: element `i` is
+/// `Fr::from_bytes_wide` of ChaCha20 block `first_block + i` (one draw = eight `next_u64` = one block).  The loop of
+/// `vanishing::Argument::commit` (plonk/vanishing/prover.rs:53-55) as one call.  The seed is the caller's entropy
+/// (`rng.fill_bytes`) and as secret as the polynomial; the engine only expands it.  `None`: not taken, run the original loop.
+pub fn try_fr_random<F: Field + 'static>(seed: &[u8; 32], stream_id: u64, first_block: u64, n: usize) -> Option<Vec<F>> {
+    if !is::<F, Fr>() || !layout_ok() {
+        return None;
+    }
+    let mut out = vec![F::zero(); n];
+    let rc = unsafe { ffi::h2hip_fr_random_bn254(seed.as_ptr(), stream_id, first_block, n, out.as_mut_ptr() as *mut u64) };
+    if rc != 0 {
+        return None;
+    }
+    Some(out)
+}
+
+/// `Fr::from_bytes_wide` over a vector: each 64 bytes as one little-endian integer, reduced mod r.
+pub fn try_fr_from_bytes_wide<F: Field + 'static>(bytes: &[[u8; 64]]) -> Option<Vec<F>> {
+    if !is::<F, Fr>() || !layout_ok() {
+        return None;
+    }
+    let mut out = vec![F::zero(); bytes.len()];
+    let rc = unsafe { ffi::h2hip_fr_from_bytes_wide_bn254(bytes.as_ptr() as *const u8, bytes.len(), out.as_mut_ptr() as *mut u64) };
+    if rc != 0 {
+        return None;
+    }
+    Some(out)
+}

@@ -40,7 +40,9 @@
  * host-pointer MSM has seen it k times (see h2hip_bases_pin); HALO2_HIP_EVALH_CODEGEN=0|1|2 the per-circuit custom-gates kernel of
  * h2hip_evaluate_h_bn254 (0: byte-code interpreter only; 1, default: generated and compiled by hiprtc on a background thread, the interpreter
  * serves until the code object is ready; 2: compiled inline) and HALO2_HIP_CACHE_DIR a directory that keeps those code objects across processes
- * (files there are loaded as GPU code, keyed by a hash of their source: the directory must be writable by the prover's user only).
+ * (files there are loaded as GPU code, keyed by a hash of their source: the directory must be writable by the prover's user only);
+ * HALO2_HIP_RANDOM_MIN_N (default 2^9, read at the first call) the element count from which the host forms of h2hip_fr_random_bn254 /
+ * h2hip_fr_from_bytes_wide_bn254 go to the device; below it they are a handful of draws on the calling thread, by design and not as a fallback.
  */
 #ifndef HALO2HIP_H
 #define HALO2HIP_H
@@ -603,6 +605,27 @@ int h2hip_fr_from_repr_bn254_device(const void* d_repr, size_t n, void* d_out, u
 int h2hip_fr_to_repr_bn254(const uint64_t* in, size_t n, void* repr);
 int h2hip_fr_to_repr_bn254_device(const void* d_in, size_t n, void* d_repr, void* stream);
 
+/* ---- randomness: C::Scalar::random over a whole column, the loop of vanishing::Argument::commit (plonk/vanishing/prover.rs:49-58) ------
+ * Definitions (halo2curves 0.3.1 and rand_chacha 0.3 as DESIGN.md section 2 records them):
+ *   Fr::from_bytes_wide : the 64 bytes read as one little-endian 512-bit integer, reduced mod r; Fr::random = that map on eight next_u64
+ *   ChaCha20Rng::from_seed(seed) : 20 rounds, key = seed, state words 12-13 = 64-bit block counter from 0, words 14-15 = 64-bit stream id
+ * One Fr::random consumes exactly one 64-byte block, so
+ *   fr_random : out[i] = from_bytes_wide(ChaCha20 block (first_block + i) of (seed, stream_id)),  4 x u64 Montgomery limbs,
+ * limb for limb what the reference's loop stores when it is handed ChaCha20Rng::from_seed(seed) that has made first_block draws.  The
+ * generator is counter-based: any range in any order, in one call or several.  fr_from_bytes_wide is the reduction alone over n
+ * 64-byte strings (out must not overlap bytes).
+ * THE SEED IS AS SECRET AS THE POLYNOMIAL: whoever learns it learns every element.  The engine is a deterministic expander and adds no
+ * entropy; the 32 seed bytes are the caller's, from the rng the reference would have drawn the elements from.  The library wipes its
+ * own host copies of the key before a call returns (the kernel receives it as an argument).
+ * n <= 2^32; n == 0 returns 0 and touches nothing.  H2HIP_EINVAL: a null seed, input or output with n > 0; first_block + n > 2^64; a
+ * device pointer that is not 16-byte aligned.  Host forms run the per-element code on the calling thread below HALO2_HIP_RANDOM_MIN_N
+ * elements (default 2^9; no GPU is needed or touched: blinding scalars and blinding rows are a handful of draws) and from there on
+ * generate on the device and download.  _device forms queue their kernel on `stream` and do not wait. */
+int h2hip_fr_random_bn254(const uint8_t seed[32], uint64_t stream_id, uint64_t first_block, size_t n, uint64_t* out);
+int h2hip_fr_random_bn254_device(const uint8_t seed[32], uint64_t stream_id, uint64_t first_block, size_t n, void* d_out, void* stream);
+int h2hip_fr_from_bytes_wide_bn254(const uint8_t* bytes /* n x 64 */, size_t n, uint64_t* out);
+int h2hip_fr_from_bytes_wide_bn254_device(const void* d_bytes, size_t n, void* d_out, void* stream);
+
 /* ---- synthetic workload; same streams as oracle_gen_{scalars,points} ---- */
 
 int h2hip_gen_scalars_device(uint64_t seed, uint64_t start, size_t n, void* d_out, void* stream);
@@ -620,7 +643,8 @@ uint32_t h2hip_get_msm_window_fixed_base(size_t n);
  * Stages: "ntt", "msm_total", "msm_digits", "msm_sort", "msm_accum" (over-full buckets included), "msm_reduce", "g_to_lagrange", "kzg_setup",
  * "evalh_cosets", "evalh_gates", "evalh_perm", "evalh_lookups", "evalh_part_scale" (inside "evalh_cosets") and "evalh_part_io" (the parts form), "products", "opening_eval", "opening_combine", "lookup_compress",
  * "lookup_permute", "check_gates", "check_permutation", "check_lookups" (each check: its kernels, without the delivery of counts / rows),
- * "g1_decompress", "g1_validate", "fr_from_repr" (each with its failure count; the _device forms too), "g1_compress", "fr_to_repr" (host forms). */
+ * "g1_decompress", "g1_validate", "fr_from_repr" (each with its failure count; the _device forms too), "g1_compress", "fr_to_repr" (host forms),
+ * "fr_random", "fr_from_wide" (the _device forms, and the host forms from their threshold on). */
 /* on = 1: every stage (each event record costs the stream ~10 us of gap); on = 2: only the dominant kernel ("msm_accum"),
  * timed through its own dispatch packet with no gap; 0: off */
 int h2hip_profile_enable(int on);

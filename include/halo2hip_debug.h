@@ -106,6 +106,9 @@ int h2hip_debug_lookup_sort_stats(uint32_t out[2]);
 /* keygen: the HBM one group of columns of a host-pointer h2hip_permutation_keygen_bn254 / h2hip_batch_invert_assigned_bn254 call may take
  * (0 = default 1 GB), so that small inputs run several pipelined groups.  Needs no GPU. */
 int h2hip_debug_set_keygen_group(uint64_t group_bytes);
+/* randomness: the element count from which the host forms of h2hip_fr_random_bn254 / h2hip_fr_from_bytes_wide_bn254 go to the device
+ * (1: always; SIZE_MAX: never, the calling thread's loop at any n; 0 restores HALO2_HIP_RANDOM_MIN_N or the default).  Needs no GPU. */
+int h2hip_debug_set_random_min_n(size_t n);
 
 #ifdef __cplusplus
 }
