@@ -498,6 +498,16 @@ static Program compile_graph(const h2hip_graph& g) {
     return P;
 }
 
+// The no-GPU hooks (test / tooling) are given a graph alone: column counts are not known there, so every column index is accepted
+static int compile_any(const h2hip_graph* g, Program* P) {
+    h2hip_evalh_desc any;
+    memset(&any, 0, sizeof(any));
+    any.n_fixed = any.n_advice = any.n_instance = any.n_challenges = 0xffffffffu;
+    if (graph_validate(*g, any, "given")) return 1;
+    *P = compile_graph(*g);
+    return 0;
+}
+
 // ---- the gates kernel generated per circuit (round 4) -------------------------------------------------------------------------------
 // The interpreter above pays, per operation and wave, an eight-dword scalar load of the op, two wave-uniform switches and nine LDS
 // dwords in and out of a slot: 38 k VALU instructions per wave for a 24-gate program whose arithmetic is ~31 k, at 64-75 % of the
@@ -859,11 +869,8 @@ extern "C" int h2hip_debug_evalh_codegen_source(const h2hip_graph* g, char* buf,
         set_error("evaluate_h: null argument");
         return 1;
     }
-    h2hip_evalh_desc any;
-    memset(&any, 0, sizeof(any));
-    any.n_fixed = any.n_advice = any.n_instance = any.n_challenges = 0xffffffffu;
-    if (graph_validate(*g, any, "given")) return 1;
-    const Program P = compile_graph(*g);
+    Program P;
+    if (compile_any(g, &P)) return 1;
     const std::string src = gen_source(*g, P, (compile & 2) != 0);  // bit 1: the graph as a lookup's table expression (evalh_lookup_gen)
     compile &= 1;
     *len = src.size();
@@ -1037,11 +1044,8 @@ extern "C" int h2hip_debug_evalh_program_muls(const h2hip_graph* g, uint32_t* n_
         set_error("evaluate_h: null argument");
         return 1;
     }
-    h2hip_evalh_desc any;
-    memset(&any, 0, sizeof(any));
-    any.n_fixed = any.n_advice = any.n_instance = any.n_challenges = 0xffffffffu;
-    if (graph_validate(*g, any, "given")) return 1;
-    const Program P = compile_graph(*g);
+    Program P;
+    if (compile_any(g, &P)) return 1;
     uint32_t m = 0;
     for (const DevOp& o : P.ops) {
         const uint32_t k = o.op & 0xff;
@@ -1058,11 +1062,8 @@ extern "C" int h2hip_debug_evalh_compile_stats(const h2hip_graph* g, uint32_t* n
         set_error("evaluate_h: null argument");
         return 1;
     }
-    h2hip_evalh_desc any;  // column counts are not known here: accept every column index
-    memset(&any, 0, sizeof(any));
-    any.n_fixed = any.n_advice = any.n_instance = any.n_challenges = 0xffffffffu;
-    if (graph_validate(*g, any, "given")) return 1;
-    const Program P = compile_graph(*g);
+    Program P;
+    if (compile_any(g, &P)) return 1;
     *n_ops = (uint32_t)P.ops.size();
     *n_slots = P.n_slots;
     return 0;
@@ -1130,22 +1131,128 @@ struct MetaBlob {
     }
 };
 
-static void prog_put(MetaBlob& mb, const h2hip_graph& g, const Program& P, ProgDev* out) {
-    std::vector<Fu> hc(g.n_constants);
-    for (uint32_t i = 0; i < g.n_constants; i++) hc[i] = to_i(fe_from_u64x4(g.constants + 4 * (size_t)i));
-    out->constants = mb.put(hc.data(), hc.size());
-    out->rotations = mb.put(g.rotations, g.n_rotations);
-    out->ops = mb.put(P.ops.data(), P.ops.size());
-    out->n_ops = (uint32_t)P.ops.size();
-    out->result = P.result;
+// What a call works out before it touches the device: the program of each of its graphs, where that program's slots live, the largest
+// global slot workspace among them and what the programs take of the metadata region.  Both forms of evaluate_h and the row-graph
+// drivers (lookup compression, the witness check's gates) build one.
+struct CallPlan {
+    std::vector<const h2hip_graph*> graphs;  // the gates graph first when the call has one, then its further graphs in order
+    std::vector<Program> progs;
+    std::vector<SlotPlan> plans;
+    size_t largest = 0;     // the program with the most slots: its plan serves a launch that runs every graph of the call
+    size_t slots_ws = 0;    // bytes of the largest global slot workspace
+    size_t meta_bytes = 0;  // what progs_put takes of the metadata region
+};
+
+static int call_plan(const h2hip_graph* gates, const h2hip_graph* more, size_t n_more, size_t rows, CallPlan* cp) {
+    if (gates) cp->graphs.push_back(gates);
+    for (size_t i = 0; i < n_more; i++) cp->graphs.push_back(more + i);
+    const size_t count = cp->graphs.size();
+    cp->progs.resize(count);
+    cp->plans.resize(count);
+    for (size_t i = 0; i < count; i++) {
+        cp->progs[i] = compile_graph(*cp->graphs[i]);
+        if (int rc = slot_plan(cp->progs[i].n_slots, rows, &cp->plans[i])) return rc;
+        if (cp->plans[i].ws_bytes > cp->slots_ws) cp->slots_ws = cp->plans[i].ws_bytes;
+        if (cp->progs[i].n_slots > cp->progs[cp->largest].n_slots) cp->largest = i;
+        cp->meta_bytes += prog_bytes(*cp->graphs[i], cp->progs[i]);
+    }
+    return 0;
 }
 
-// One launch of the custom gates over `rows` rows of `values`: the kernel generated for this circuit once it is compiled, the
-// interpreter until then (and for programs beyond the generator's limits)
-static int enqueue_gates(Ctx* c, const h2hip_graph& graph, const Program& prog, const SlotPlan& plan, const ProgDev& gd, const ColsDev& cols,
-                         Fe* d_values, Fu* gws, size_t rows, hipStream_t s) {
-    const dim3 block(256);
-    hipFunction_t gen = plan.tier != 0 ? gates_kernel_for(c, graph, prog) : nullptr;
+// Capacity of the metadata region of an evaluate_h call: the programs, the challenges and scalars, a pointer (and the alignment of its
+// table) per column, and `extra_ptrs` pointers in tables of the caller's own
+static size_t evalh_meta_cap(const CallPlan& cp, const h2hip_evalh_desc& d, size_t extra_ptrs) {
+    return align256(64 * 1024 + cp.meta_bytes + ((size_t)d.n_challenges + 28) * sizeof(Fu) +
+                    (8 + 256) * ((size_t)d.n_fixed + d.n_advice + d.n_instance + d.n_perm_sets + 2 * (size_t)d.n_perm_columns + 16) + 8 * extra_ptrs);
+}
+
+// the plan's programs into the metadata image, in the plan's order
+static std::vector<ProgDev> progs_put(MetaBlob& mb, const CallPlan& cp) {
+    std::vector<ProgDev> out(cp.progs.size());
+    std::vector<Fu> hc;
+    for (size_t i = 0; i < out.size(); i++) {
+        const h2hip_graph& g = *cp.graphs[i];
+        hc.resize(g.n_constants);
+        for (uint32_t j = 0; j < g.n_constants; j++) hc[j] = to_i(fe_from_u64x4(g.constants + 4 * (size_t)j));
+        out[i].constants = mb.put(hc.data(), hc.size());
+        out[i].rotations = mb.put(g.rotations, g.n_rotations);
+        out[i].ops = mb.put(cp.progs[i].ops.data(), cp.progs[i].ops.size());
+        out[i].n_ops = (uint32_t)cp.progs[i].ops.size();
+        out[i].result = cp.progs[i].result;
+    }
+    return out;
+}
+
+// The column tables (device pointers, d's counts), d's challenges and its scalars into the metadata image.  Of d only the counts, the
+// challenges and y / beta / gamma / theta are read; a scalar no graph of the call can read may be null and stays zero.
+static ColsDev cols_put(MetaBlob& mb, const h2hip_evalh_desc& d, const Fe* const* fixed, const Fe* const* advice, const Fe* const* instance,
+                        uint32_t log_size, int32_t rot_scale) {
+    ColsDev cols;
+    cols.fixed = mb.put(fixed, d.n_fixed);
+    cols.advice = mb.put(advice, d.n_advice);
+    cols.instance = mb.put(instance, d.n_instance);
+    std::vector<Fu> hch(d.n_challenges);
+    for (uint32_t i = 0; i < d.n_challenges; i++) hch[i] = to_i(fe_from_u64x4(d.challenges + 4 * (size_t)i));
+    cols.challenges = mb.put(hch.data(), hch.size());
+    auto scalar = [](const uint64_t* v) { return v ? to_i(fe_from_u64x4(v)) : fu_zero(); };
+    cols.beta = scalar(d.beta);
+    cols.gamma = scalar(d.gamma);
+    cols.theta = scalar(d.theta);
+    cols.y = scalar(d.y);
+    cols.log_size = log_size;
+    cols.rot_scale = rot_scale;
+    return cols;
+}
+
+// The permutation argument's tables and scalars (all zero for a system without one).  fixed / advice / instance are the host copies of
+// the tables cols_put stored: a permuted column is one of them, by (kind, index) (:404-408).  z, cosets: n_perm_sets and n_perm_columns
+// device pointers; l: l0, l_last, l_active.  delta_start is left to the caller, whose rows decide it.
+static PermDev perm_put(MetaBlob& mb, const h2hip_evalh_desc& d, const Fe* const* fixed, const Fe* const* advice, const Fe* const* instance,
+                        const Fe* const* z, const Fe* const* cosets, const Fe* const* l, const Fu* pow_lo, const Fu* pow_hi, uint32_t pow_bits) {
+    PermDev pd;
+    memset(&pd, 0, sizeof(pd));
+    if (!d.n_perm_sets) return pd;
+    std::vector<const Fe*> pcols(d.n_perm_columns);
+    for (uint32_t j = 0; j < d.n_perm_columns; j++) {
+        const uint32_t kind = d.perm_column_kind[j], idx = d.perm_column_index[j];
+        pcols[j] = kind == H2HIP_ANY_ADVICE ? advice[idx] : kind == H2HIP_ANY_FIXED ? fixed[idx] : instance[idx];
+    }
+    pd.z = mb.put(z, d.n_perm_sets);
+    pd.cols = mb.put(pcols.data(), pcols.size());
+    pd.cosets = mb.put(cosets, d.n_perm_columns);
+    pd.l0 = l[0];
+    pd.l_last = l[1];
+    pd.l_active = l[2];
+    pd.delta = to_i(fe_from_u64x4(d.delta));
+    pd.pow_lo = pow_lo;
+    pd.pow_hi = pow_hi;
+    pd.pow_bits = pow_bits;
+    pd.n_sets = d.n_perm_sets;
+    pd.n_cols = d.n_perm_columns;
+    pd.chunk_len = d.chunk_len;
+    pd.last_rotation = d.last_rotation;
+    return pd;
+}
+
+// f(std::integral_constant<int, T>, bytes): a slot plan's tier as the interpreter kernels' template argument, with the dynamic LDS
+// that tier's slots take
+template <class F>
+static void with_tier(int tier, F f) {
+    switch (tier) {
+        case 4: f(std::integral_constant<int, 4>{}, (size_t)4 * 9 * 256 * 4); break;
+        case 8: f(std::integral_constant<int, 8>{}, (size_t)8 * 9 * 256 * 4); break;
+        case 16: f(std::integral_constant<int, 16>{}, (size_t)EVALH_LDS_HOT * 9 * 256 * 4); break;
+        case 64: f(std::integral_constant<int, 64>{}, (size_t)EVALH_LDS_HOT * 9 * 256 * 4); break;
+        case 256: f(std::integral_constant<int, 256>{}, (size_t)EVALH_LDS_HOT * 9 * 256 * 4); break;
+        default: f(std::integral_constant<int, 0>{}, (size_t)0);
+    }
+}
+
+// One launch of the custom gates (the plan's first program) over `rows` rows of `values`: the kernel generated for this circuit once
+// it is compiled, the interpreter until then (and for programs beyond the generator's limits)
+static int enqueue_gates(Ctx* c, const CallPlan& cp, const ProgDev& gd, const ColsDev& cols, Fe* d_values, size_t rows, hipStream_t s) {
+    const SlotPlan& plan = cp.plans[0];
+    hipFunction_t gen = plan.tier != 0 ? gates_kernel_for(c, *cp.graphs[0], cp.progs[0]) : nullptr;
     if (gen) {
         Fe* vals = d_values;
         void* args[] = {(void*)&cols, (void*)&vals};
@@ -1153,25 +1260,19 @@ static int enqueue_gates(Ctx* c, const h2hip_graph& graph, const Program& prog, 
         g_rtc_stats.launches++;
     } else {
         g_rtc_stats.interpreted++;
-        const dim3 g(plan.lanes / 256);
-        switch (plan.tier) {
-            case 4: hipLaunchKernelGGL(evalh_gates_kernel<4>, g, block, 4 * 9 * 256 * 4, s, gd, cols, d_values, gws, plan.lanes); break;
-            case 8: hipLaunchKernelGGL(evalh_gates_kernel<8>, g, block, 8 * 9 * 256 * 4, s, gd, cols, d_values, gws, plan.lanes); break;
-            case 16: hipLaunchKernelGGL(evalh_gates_kernel<16>, g, block, EVALH_LDS_HOT * 9 * 256 * 4, s, gd, cols, d_values, gws, plan.lanes); break;
-            case 64: hipLaunchKernelGGL(evalh_gates_kernel<64>, g, block, EVALH_LDS_HOT * 9 * 256 * 4, s, gd, cols, d_values, gws, plan.lanes); break;
-            case 256: hipLaunchKernelGGL(evalh_gates_kernel<256>, g, block, EVALH_LDS_HOT * 9 * 256 * 4, s, gd, cols, d_values, gws, plan.lanes); break;
-            default: hipLaunchKernelGGL(evalh_gates_kernel<0>, g, block, 0, s, gd, cols, d_values, gws, plan.lanes);
-        }
+        with_tier(plan.tier, [&](auto tier, size_t lds) {
+            hipLaunchKernelGGL(evalh_gates_kernel<decltype(tier)::value>, dim3(plan.lanes / 256), dim3(256), lds, s, gd, cols, d_values,
+                               (Fu*)c->evalh_slots.p, plan.lanes);
+        });
     }
     H2_CHECK(hipGetLastError());
     return 0;
 }
 
-// ... and of one lookup argument's constraints
-static int enqueue_lookup(Ctx* c, const h2hip_graph& graph, const Program& prog, const SlotPlan& lp, const ProgDev& lg, const LookupDev& ld,
-                          const ColsDev& cols, Fe* d_values, Fu* gws, size_t rows, hipStream_t s) {
-    const dim3 block(256);
-    if (hipFunction_t lgen = gates_kernel_for(c, graph, prog, true)) {  // generated for this circuit, as the gates kernel is
+// ... and of one lookup argument's constraints (program i of the plan)
+static int enqueue_lookup(Ctx* c, const CallPlan& cp, size_t i, const ProgDev& lg, const LookupDev& ld, const ColsDev& cols, Fe* d_values,
+                          size_t rows, hipStream_t s) {
+    if (hipFunction_t lgen = gates_kernel_for(c, *cp.graphs[i], cp.progs[i], true)) {  // generated for this circuit, as the gates kernel is
         Fe* vals = d_values;
         void* args[] = {(void*)&cols, (void*)&ld, (void*)&vals};
         H2_CHECK(hipModuleLaunchKernel(lgen, (uint32_t)((rows + 255) / 256), 1, 1, 256, 1, 1, 0, s, args, nullptr));
@@ -1179,16 +1280,45 @@ static int enqueue_lookup(Ctx* c, const h2hip_graph& graph, const Program& prog,
         return 0;
     }
     g_rtc_stats.interpreted++;
-    const dim3 g(lp.lanes / 256);
-    switch (lp.tier) {
-        case 4: hipLaunchKernelGGL(evalh_lookup_kernel<4>, g, block, 4 * 9 * 256 * 4, s, lg, ld, cols, d_values, gws, lp.lanes); break;
-        case 8: hipLaunchKernelGGL(evalh_lookup_kernel<8>, g, block, 8 * 9 * 256 * 4, s, lg, ld, cols, d_values, gws, lp.lanes); break;
-        case 16: hipLaunchKernelGGL(evalh_lookup_kernel<16>, g, block, EVALH_LDS_HOT * 9 * 256 * 4, s, lg, ld, cols, d_values, gws, lp.lanes); break;
-        case 64: hipLaunchKernelGGL(evalh_lookup_kernel<64>, g, block, EVALH_LDS_HOT * 9 * 256 * 4, s, lg, ld, cols, d_values, gws, lp.lanes); break;
-        case 256: hipLaunchKernelGGL(evalh_lookup_kernel<256>, g, block, EVALH_LDS_HOT * 9 * 256 * 4, s, lg, ld, cols, d_values, gws, lp.lanes); break;
-        default: hipLaunchKernelGGL(evalh_lookup_kernel<0>, g, block, 0, s, lg, ld, cols, d_values, gws, lp.lanes);
-    }
+    const SlotPlan& lp = cp.plans[i];
+    with_tier(lp.tier, [&](auto tier, size_t lds) {
+        hipLaunchKernelGGL(evalh_lookup_kernel<decltype(tier)::value>, dim3(lp.lanes / 256), dim3(256), lds, s, lg, ld, cols, d_values,
+                           (Fu*)c->evalh_slots.p, lp.lanes);
+    });
     H2_CHECK(hipGetLastError());
+    return 0;
+}
+
+// The constraints of `rows` rows folded into `values`, in the reference's order: the custom gates (:334-360), the permutation argument
+// (:362-441) when the system has one, then the lookups (:443-518).  The plan holds the gates program and one program per lookup, pds
+// their device forms.  Every column the kernels read is in place before the call, but for two kinds the pass asks for when their turn
+// comes: perm_ready() before the permutation kernel is queued, and next_group(i, count) before the kernel of lookup i when that lookup
+// opens a group after the first -- the caller then forms the cosets of lookups i .. i + count in the group's buffers, lk[0 .. 3 count)
+// (product, permuted input, permuted table per lookup; the first group's are there from the start).  l: l0, l_last, l_active.
+template <class PermReady, class NextGroup>
+static int constraint_pass(Ctx* c, const CallPlan& cp, const std::vector<ProgDev>& pds, const ColsDev& cols, const PermDev& pd,
+                           const Fe* const* l, const Fe* const* lk, size_t lk_group, Fe* d_values, size_t rows, hipStream_t s,
+                           PermReady perm_ready, NextGroup next_group) {
+    int rc;
+    int t_g = c->timer_begin("evalh_gates", s);
+    if ((rc = enqueue_gates(c, cp, pds[0], cols, d_values, rows, s))) return rc;
+    c->timer_end(t_g, s);
+    if (pd.n_sets) {
+        if ((rc = perm_ready())) return rc;
+        int t_p = c->timer_begin("evalh_perm", s);
+        hipLaunchKernelGGL(evalh_perm_kernel, dim3((uint32_t)((rows + 255) / 256)), dim3(256), 0, s, pd, cols, d_values);
+        H2_CHECK(hipGetLastError());
+        c->timer_end(t_p, s);
+    }
+    const size_t n_lookups = cp.progs.size() - 1;
+    int t_l = n_lookups ? c->timer_begin("evalh_lookups", s) : -1;
+    for (size_t i = 0; i < n_lookups; i++) {
+        const size_t gi = i % lk_group;
+        if (gi == 0 && i && (rc = next_group(i, n_lookups - i < lk_group ? n_lookups - i : lk_group))) return rc;
+        const LookupDev ld = {lk[3 * gi], lk[3 * gi + 1], lk[3 * gi + 2], l[0], l[1], l[2]};
+        if ((rc = enqueue_lookup(c, cp, i + 1, pds[i + 1], ld, cols, d_values, rows, s))) return rc;
+    }
+    c->timer_end(t_l, s);
     return 0;
 }
 
@@ -1241,19 +1371,9 @@ int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, uint64_t* values, bool de
     const uint32_t k = d->k, ek = d->extended_k;
     const size_t n = (size_t)1 << k, size = (size_t)1 << ek;
     const size_t col_bytes = size * sizeof(Fe);
-    // programs first: their slot counts size the workspaces
-    const Program gates_prog = compile_graph(d->custom_gates);
-    std::vector<Program> lookup_progs(d->n_lookups);
-    for (uint32_t i = 0; i < d->n_lookups; i++) lookup_progs[i] = compile_graph(d->lookup_graphs[i]);
     int rc;
-    SlotPlan gates_plan;
-    std::vector<SlotPlan> lookup_plans(d->n_lookups);
-    if ((rc = slot_plan(gates_prog.n_slots, size, &gates_plan))) return rc;
-    size_t slots_ws = gates_plan.ws_bytes;
-    for (uint32_t i = 0; i < d->n_lookups; i++) {
-        if ((rc = slot_plan(lookup_progs[i].n_slots, size, &lookup_plans[i]))) return rc;
-        if (lookup_plans[i].ws_bytes > slots_ws) slots_ws = lookup_plans[i].ws_bytes;
-    }
+    CallPlan cp;  // programs first: their slot counts size the workspaces
+    if ((rc = call_plan(&d->custom_gates, d->lookup_graphs, d->n_lookups, size, &cp))) return rc;
     // ---- device arena: [metadata | columns the engine owns]
     // lookup cosets: three buffers per lookup for as many lookups as 2 GB hold (a group); the first group's transforms join the advice /
     // instance batch, later groups reuse the buffers once the kernels of the group before are queued
@@ -1261,29 +1381,21 @@ int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, uint64_t* values, bool de
     size_t arena_bytes;
     if ((rc = evaluate_h_workspace_bytes(k, ek, d->n_fixed, d->n_advice, d->n_instance, d->n_perm_sets, d->n_perm_columns, d->n_lookups, false, dev, &arena_bytes)))
         return rc;
-    size_t meta_cap = 64 * 1024 + prog_bytes(d->custom_gates, gates_prog) + ((size_t)d->n_challenges + 28) * sizeof(Fu) +
-                      (8 + 256) * ((size_t)d->n_fixed + d->n_advice + d->n_instance + d->n_perm_sets + 2 * (size_t)d->n_perm_columns + 16);
-    for (uint32_t i = 0; i < d->n_lookups; i++) meta_cap += prog_bytes(d->lookup_graphs[i], lookup_progs[i]);
-    meta_cap = (meta_cap + 255) / 256 * 256;
+    const size_t meta_cap = evalh_meta_cap(cp, *d, 0);
     if ((rc = c->evalh_ws.ensure(meta_cap + arena_bytes))) return rc;
-    if (slots_ws && (rc = c->evalh_slots.ensure(slots_ws))) return rc;
-    Fu* const gws = (Fu*)c->evalh_slots.p;
+    if (cp.slots_ws && (rc = c->evalh_slots.ensure(cp.slots_ws))) return rc;
     if ((rc = c->ws_acquire(s))) return rc;
     WsGuard guard(c, s);
     Arena ar;
     ar.base = (char*)c->evalh_ws.p;
-    ar.cap = c->evalh_ws.cap;
+    ar.cap = meta_cap + arena_bytes;  // what was asked for, not what the buffer happens to hold: the sizing function is the contract
     MetaBlob mb;
     mb.dev_base = (char*)ar.take(meta_cap);
     mb.cap = meta_cap;
-    if (!mb.dev_base) {
-        set_error("evaluate_h: arena overflow");
-        return 1;
-    }
-    // where every column will live: an extended coset already in HBM is used in place, anything else gets arena space
+    // ---- where every column will live: an extended coset already in HBM is used in place, anything else gets arena space
     struct Upload { Fe* dst; const uint64_t* src; size_t elems; bool late; };
     std::vector<Upload> uploads;  // host -> device column copies, issued after the metadata; `late`: only the permutation kernel reads it
-    bool bad = false;
+    bool bad = false, any_late = false;
     auto place = [&](const uint64_t* h, size_t elems, bool late = false) -> Fe* {
         if (!h) {
             bad = true;
@@ -1294,7 +1406,10 @@ int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, uint64_t* values, bool de
             if (const Fe* hit = pinned_column_lookup(c, h, elems)) return (Fe*)hit;
         Fe* p = (Fe*)ar.take(col_bytes);
         if (!p) bad = true;
-        else if (!dev) uploads.push_back({p, h, elems, late});
+        else if (!dev) {
+            uploads.push_back({p, h, elems, late});
+            any_late = any_late || late;
+        }
         return p;
     };
     std::vector<const Fe*> fixed(d->n_fixed), advice(d->n_advice), instance(d->n_instance);
@@ -1311,141 +1426,83 @@ int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, uint64_t* values, bool de
         poly_dst[i] = p;
         (i < d->n_advice ? advice[i] : instance[i - d->n_advice]) = p;
     }
-    Fe* const l0 = place(d->l0, size);
-    Fe* const l_last = place(d->l_last, size);
-    Fe* const l_active = place(d->l_active_row, size);
+    const Fe* const l[3] = {place(d->l0, size), place(d->l_last, size), place(d->l_active_row, size)};
     Fe* const d_values = place(values, size);
-    std::vector<const Fe*> z(d->n_perm_sets), pcols(d->n_perm_sets ? d->n_perm_columns : 0), pcosets(d->n_perm_sets ? d->n_perm_columns : 0);
-    if (d->n_perm_sets) {
-        for (uint32_t i = 0; i < d->n_perm_sets; i++) z[i] = place(d->perm_product_cosets[i], size, true);
-        for (uint32_t j = 0; j < d->n_perm_columns; j++) {
-            pcosets[j] = place(d->perm_cosets[j], size, true);
-            const uint32_t kind = d->perm_column_kind[j], idx = d->perm_column_index[j];
-            pcols[j] = kind == H2HIP_ANY_ADVICE ? advice[idx] : kind == H2HIP_ANY_FIXED ? fixed[idx] : instance[idx];  // :404-408
-        }
-    }
+    std::vector<const Fe*> z(d->n_perm_sets), pcosets(d->n_perm_sets ? d->n_perm_columns : 0);
+    for (size_t i = 0; i < z.size(); i++) z[i] = place(d->perm_product_cosets[i], size, true);
+    for (size_t j = 0; j < pcosets.size(); j++) pcosets[j] = place(d->perm_cosets[j], size, true);
     std::vector<Fe*> lbuf(3 * lk_group, nullptr);
     for (size_t t = 0; t < lbuf.size(); t++)
         if (!(lbuf[t] = (Fe*)ar.take(col_bytes))) bad = true;
     for (uint32_t i = 0; i < d->n_lookups; i++)
         if (!d->lookup_product_polys[i] || !d->lookup_permuted_input_polys[i] || !d->lookup_permuted_table_polys[i]) bad = true;
-    auto lookup_poly = [&](uint32_t i, int t) -> const uint64_t* {
-        return t == 0 ? d->lookup_product_polys[i] : t == 1 ? d->lookup_permuted_input_polys[i] : d->lookup_permuted_table_polys[i];
-    };
-    if (!bad)
-        for (size_t i = 0; i < lk_group; i++)  // the first group rides in the main batch
-            for (int t = 0; t < 3; t++) {
-                poly_dst.push_back(lbuf[3 * i + t]);
-                poly_src.push_back(dev ? (const Fe*)lookup_poly((uint32_t)i, t) : nullptr);
-                if (!dev) uploads.push_back({lbuf[3 * i + t], lookup_poly((uint32_t)i, t), n, false});
-            }
-    if (bad) {
+    if (!mb.dev_base || bad) {
         set_error("evaluate_h: null column or arena overflow");
         return 1;
     }
+    // lookups first .. first + count: their polynomials into lbuf -- queued for the transform in place (device form: read where they lie)
+    auto lookup_polys = [&](size_t first, size_t count, std::vector<const Fe*>* srcs) -> int {
+        for (size_t q = 0; q < 3 * count; q++) {
+            const size_t i = first + q / 3;
+            const uint64_t* h = q % 3 == 0 ? d->lookup_product_polys[i] : q % 3 == 1 ? d->lookup_permuted_input_polys[i] : d->lookup_permuted_table_polys[i];
+            srcs->push_back(dev ? (const Fe*)h : nullptr);
+            if (!dev) H2_CHECK(hipMemcpyAsync(lbuf[q], h, n * sizeof(Fe), hipMemcpyHostToDevice, s));
+        }
+        return 0;
+    };
+    // The late uploads (below) go on aux2, which nothing orders after the arena's previous user: ws_acquire made only `s` wait.  What `s`
+    // holds now is earlier calls' work and none of this call's; aux2 will wait for that much.
+    if (any_late) {
+        if ((rc = c->ensure_aux(2))) return rc;
+        H2_CHECK(hipEventRecord(c->aux_events[1], s));
+    }
     // ---- metadata image
-    ColsDev cols;
-    cols.fixed = mb.put(fixed.data(), fixed.size());
-    cols.advice = mb.put(advice.data(), advice.size());
-    cols.instance = mb.put(instance.data(), instance.size());
-    {
-        std::vector<Fu> hch(d->n_challenges);
-        for (uint32_t i = 0; i < d->n_challenges; i++) hch[i] = to_i(fe_from_u64x4(d->challenges + 4 * (size_t)i));
-        cols.challenges = mb.put(hch.data(), hch.size());
-    }
-    cols.beta = to_i(fe_from_u64x4(d->beta));
-    cols.gamma = to_i(fe_from_u64x4(d->gamma));
-    cols.theta = to_i(fe_from_u64x4(d->theta));
-    cols.y = to_i(fe_from_u64x4(d->y));
-    cols.log_size = ek;
-    cols.rot_scale = 1 << (ek - k);
+    const ColsDev cols = cols_put(mb, *d, fixed.data(), advice.data(), instance.data(), ek, 1 << (ek - k));
+    const std::vector<ProgDev> pds = progs_put(mb, cp);
     const Fe ext_omega = fe_from_u64x4(d->extended_omega);
-    ProgDev gd;
-    prog_put(mb, d->custom_gates, gates_prog, &gd);
-    std::vector<ProgDev> lgs(d->n_lookups);
-    for (uint32_t i = 0; i < d->n_lookups; i++) prog_put(mb, d->lookup_graphs[i], lookup_progs[i], &lgs[i]);
-    PermDev pd;
-    memset(&pd, 0, sizeof(pd));
-    if (d->n_perm_sets) {
-        pd.z = mb.put(z.data(), z.size());
-        pd.cols = mb.put(pcols.data(), pcols.size());
-        pd.cosets = mb.put(pcosets.data(), pcosets.size());
-        if ((rc = ntt_power_table(c, ext_omega, ek, s, &pd.pow_lo, &pd.pow_hi, &pd.pow_bits))) return rc;
-        pd.l0 = l0;
-        pd.l_last = l_last;
-        pd.l_active = l_active;
-        pd.delta = to_i(fe_from_u64x4(d->delta));
-        pd.delta_start = to_i(fe_mul<FrP>(fe_from_u64x4(d->beta), fe_from_u64x4(d->zeta)));
-        pd.n_sets = d->n_perm_sets;
-        pd.n_cols = d->n_perm_columns;
-        pd.chunk_len = d->chunk_len;
-        pd.last_rotation = d->last_rotation;
-    }
+    const Fu *pow_lo = nullptr, *pow_hi = nullptr;
+    uint32_t pow_bits = 0;
+    if (d->n_perm_sets && (rc = ntt_power_table(c, ext_omega, ek, s, &pow_lo, &pow_hi, &pow_bits))) return rc;
+    PermDev pd = perm_put(mb, *d, fixed.data(), advice.data(), instance.data(), z.data(), pcosets.data(), l, pow_lo, pow_hi, pow_bits);
+    if (d->n_perm_sets) pd.delta_start = to_i(fe_mul<FrP>(fe_from_u64x4(d->beta), fe_from_u64x4(d->zeta)));  // beta * ZETA (:368)
     if (mb.overflow) {
         set_error("evaluate_h: metadata region overflow");
         return 1;
     }
-    if (!mb.host.empty()) {  // through the pinned ring (or a synchronous copy when large): mb.host dies with this frame
-        int rc_up = c->stage_h2d(mb.dev_base, mb.host.data(), mb.host.size(), s);
-        if (rc_up) return rc_up;
-    }
-    // ---- columns: host -> device copies (host-pointer form), then advice / instance polynomials -> extended cosets
-    //      (:306-323) in one batched transform: distribute_powers_zeta(into_coset) + zero-pad + NTT, as h2hip_coeff_to_extended does
-    // (the permutation argument's own columns -- the product cosets of this proof, and the key's permutation cosets when they are not
-    // pinned -- cross later, on a second stream under the coset transforms and the gates kernel: a copy from pageable memory blocks the
-    // calling thread, not the kernels already queued)
-    bool any_late = false;
-    for (const Upload& u : uploads) {
-        if (u.late) any_late = true;
-        else H2_CHECK(hipMemcpyAsync(u.dst, u.src, u.elems * sizeof(Fe), hipMemcpyHostToDevice, s));
-    }
-    if (any_late && (rc = c->ensure_aux(2))) return rc;
+    // ---- upload: the metadata through the pinned ring (or a synchronous copy when large; mb.host dies with this frame), then the
+    //      host-pointer form's columns.  The permutation argument's own columns -- the product cosets of this proof, and the key's
+    //      permutation cosets when they are not pinned -- cross later, on a second stream under the coset transforms and the gates
+    //      kernel: a copy from pageable memory blocks the calling thread, not the kernels already queued.
+    if (!mb.host.empty() && (rc = c->stage_h2d(mb.dev_base, mb.host.data(), mb.host.size(), s))) return rc;
+    for (const Upload& u : uploads)
+        if (!u.late) H2_CHECK(hipMemcpyAsync(u.dst, u.src, u.elems * sizeof(Fe), hipMemcpyHostToDevice, s));
+    if ((rc = lookup_polys(0, lk_group, &poly_src))) return rc;  // the first group rides in the main batch
+    poly_dst.insert(poly_dst.end(), lbuf.begin(), lbuf.end());
+    // ---- cosets: advice / instance polynomials -> extended cosets (:306-323) in one batched transform: distribute_powers_zeta(into_coset)
+    //      + zero-pad + NTT, as h2hip_coeff_to_extended does
     NttScale sc = NttScale::into_coset(fe_from_u64x4(d->g_coset), fe_from_u64x4(d->g_coset_inv), n);
     int t_c = c->timer_begin("evalh_cosets", s);
     if ((rc = ntt_device_batch(c, poly_dst.data(), poly_src.data(), poly_dst.size(), ext_omega, ek, &sc, s))) return rc;
     c->timer_end(t_c, s);
-    const dim3 grid((uint32_t)((size + 255) / 256)), block(256);
-
-    // ---- custom gates (:334-360)
-    int t_g = c->timer_begin("evalh_gates", s);
-    if ((rc = enqueue_gates(c, d->custom_gates, gates_prog, gates_plan, gd, cols, d_values, gws, size, s))) return rc;
-    c->timer_end(t_g, s);
-
-    // ---- permutations (:362-441)
-    if (any_late) {
+    // ---- the pass
+    auto late_uploads = [&]() -> int {
+        if (!any_late) return 0;
+        H2_CHECK(hipStreamWaitEvent(c->aux2, c->aux_events[1], 0));
         for (const Upload& u : uploads)
             if (u.late) H2_CHECK(hipMemcpyAsync(u.dst, u.src, u.elems * sizeof(Fe), hipMemcpyHostToDevice, c->aux2));
         H2_CHECK(hipEventRecord(c->aux_events[0], c->aux2));
         H2_CHECK(hipStreamWaitEvent(s, c->aux_events[0], 0));
-    }
-    if (d->n_perm_sets) {
-        int t_p = c->timer_begin("evalh_perm", s);
-        hipLaunchKernelGGL(evalh_perm_kernel, grid, block, 0, s, pd, cols, d_values);
-        H2_CHECK(hipGetLastError());
-        c->timer_end(t_p, s);
-    }
-
-    // ---- lookups (:443-518): the three cosets of a lookup are formed in groups (the first group with the columns above), used, and
-    //      the group's buffers reused
-    int t_l = d->n_lookups ? c->timer_begin("evalh_lookups", s) : -1;
-    for (uint32_t i = 0; i < d->n_lookups; i++) {
-        const size_t gi = i % lk_group;
-        if (gi == 0 && i) {  // the next group's cosets
-            const size_t cnt = d->n_lookups - i < lk_group ? d->n_lookups - i : lk_group;
-            std::vector<const Fe*> lsrc(3 * cnt, nullptr);
-            for (size_t q = 0; q < 3 * cnt; q++) {
-                const uint64_t* h = lookup_poly(i + (uint32_t)(q / 3), (int)(q % 3));
-                if (dev) lsrc[q] = (const Fe*)h;
-                else H2_CHECK(hipMemcpyAsync(lbuf[q], h, n * sizeof(Fe), hipMemcpyHostToDevice, s));
-            }
-            if ((rc = ntt_device_batch(c, lbuf.data(), lsrc.data(), 3 * cnt, ext_omega, ek, &sc, s))) return rc;
-        }
-        const LookupDev ld = {lbuf[3 * gi], lbuf[3 * gi + 1], lbuf[3 * gi + 2], l0, l_last, l_active};
-        if ((rc = enqueue_lookup(c, d->lookup_graphs[i], lookup_progs[i], lookup_plans[i], lgs[i], ld, cols, d_values, gws, size, s))) return rc;
-    }
-    c->timer_end(t_l, s);
+        return 0;
+    };
+    auto next_group = [&](size_t first, size_t count) -> int {  // the group's buffers are free: the kernels of the group before are queued
+        std::vector<const Fe*> lsrc;
+        if (int rc_up = lookup_polys(first, count, &lsrc)) return rc_up;
+        return ntt_device_batch(c, lbuf.data(), lsrc.data(), 3 * count, ext_omega, ek, &sc, s);
+    };
+    if ((rc = constraint_pass(c, cp, pds, cols, pd, l, lbuf.data(), lk_group, d_values, size, s, late_uploads, next_group))) return rc;
     if ((rc = guard.release())) return rc;
     if (dev) return 0;
+    // ---- download
     H2_CHECK(hipMemcpyAsync(values, d_values, col_bytes, hipMemcpyDeviceToHost, s));
     H2_CHECK(hipStreamSynchronize(s));
     return 0;
@@ -1570,18 +1627,10 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, uint64
     const size_t n = (size_t)1 << k, size = (size_t)1 << ek;
     const size_t part_bytes = align256(n * sizeof(Fe));
     const uint32_t p_begin = d->part_count ? d->part_begin : 0, p_end = d->part_count ? d->part_begin + d->part_count : 1u << log_p;
-    const Program gates_prog = compile_graph(d->custom_gates);
-    std::vector<Program> lookup_progs(d->n_lookups);
-    for (uint32_t i = 0; i < d->n_lookups; i++) lookup_progs[i] = compile_graph(d->lookup_graphs[i]);
+    const h2hip_evalh_desc f = parts_as_full(*d);  // the counts, the scalars and the permutation layout, where the shared builders read them
     int rc;
-    SlotPlan gates_plan;
-    std::vector<SlotPlan> lookup_plans(d->n_lookups);
-    if ((rc = slot_plan(gates_prog.n_slots, n, &gates_plan))) return rc;
-    size_t slots_ws = gates_plan.ws_bytes;
-    for (uint32_t i = 0; i < d->n_lookups; i++) {
-        if ((rc = slot_plan(lookup_progs[i].n_slots, n, &lookup_plans[i]))) return rc;
-        if (lookup_plans[i].ws_bytes > slots_ws) slots_ws = lookup_plans[i].ws_bytes;
-    }
+    CallPlan cp;
+    if ((rc = call_plan(&d->custom_gates, d->lookup_graphs, d->n_lookups, n, &cp))) return rc;
     // ---- the coefficient columns, in the order of the batch that transforms them: key and witness columns, then the lookups'
     std::vector<const uint64_t*> polys;
     for (uint32_t i = 0; i < d->n_fixed; i++) polys.push_back(d->fixed_polys[i]);
@@ -1603,14 +1652,9 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, uint64
     size_t arena_bytes;
     if ((rc = evaluate_h_workspace_bytes(k, ek, d->n_fixed, d->n_advice, d->n_instance, d->n_perm_sets, d->n_perm_columns, d->n_lookups, true, dev, &arena_bytes)))
         return rc;
-    size_t meta_cap = 64 * 1024 + prog_bytes(d->custom_gates, gates_prog) + ((size_t)d->n_challenges + 28) * sizeof(Fu) +
-                      (8 + 256) * ((size_t)d->n_fixed + d->n_advice + d->n_instance + d->n_perm_sets + 2 * (size_t)d->n_perm_columns + 16) +
-                      8 * (polys.size() + n_part_cols);
-    for (uint32_t i = 0; i < d->n_lookups; i++) meta_cap += prog_bytes(d->lookup_graphs[i], lookup_progs[i]);
-    meta_cap = align256(meta_cap);
+    const size_t meta_cap = evalh_meta_cap(cp, f, polys.size() + n_part_cols);  // this form's own tables: where the polynomials lie, where a part's cosets go
     if ((rc = c->evalh_ws.ensure(meta_cap + arena_bytes))) return rc;
-    if (slots_ws && (rc = c->evalh_slots.ensure(slots_ws))) return rc;
-    Fu* const gws = (Fu*)c->evalh_slots.p;
+    if (cp.slots_ws && (rc = c->evalh_slots.ensure(cp.slots_ws))) return rc;
     if ((rc = c->ws_acquire(s))) return rc;
     WsGuard guard(c, s);
     Arena ar;
@@ -1638,60 +1682,26 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, uint64
     const Fe omega = fe_pow_u64<FrP>(ext_omega, (uint64_t)1 << log_p);
     PartScaleDev sd;
     memset(&sd, 0, sizeof(sd));
-    PermDev pd;
-    memset(&pd, 0, sizeof(pd));
+    const Fu *pow_lo, *pow_hi;  // the 2^k domain's, for the permutation kernel
+    uint32_t pow_bits;
     if ((rc = ntt_power_table(c, ext_omega, ek, s, &sd.pow_lo, &sd.pow_hi, &sd.pow_bits))) return rc;
-    if ((rc = ntt_power_table(c, omega, k, s, &pd.pow_lo, &pd.pow_hi, &pd.pow_bits))) return rc;
+    if ((rc = ntt_power_table(c, omega, k, s, &pow_lo, &pow_hi, &pow_bits))) return rc;
     if ((rc = ntt_power_table(c, ext_omega, ek, s, &sd.pow_lo, &sd.pow_hi, &sd.pow_bits))) return rc;
     // ---- metadata image
     const Fe* const* d_src = mb.put(src.data(), src.size());
     const Fe* const* d_dst = (const Fe* const*)mb.put(part_cols.data(), part_cols.size());
     const Fe* const* col = part_cols.data();  // one part's cosets, in the order of `polys`
-    ColsDev cols;
-    cols.fixed = mb.put(col, d->n_fixed);
-    cols.advice = mb.put(col + d->n_fixed, d->n_advice);
-    cols.instance = mb.put(col + d->n_fixed + d->n_advice, d->n_instance);
-    {
-        std::vector<Fu> hch(d->n_challenges);
-        for (uint32_t i = 0; i < d->n_challenges; i++) hch[i] = to_i(fe_from_u64x4(d->challenges + 4 * (size_t)i));
-        cols.challenges = mb.put(hch.data(), hch.size());
-    }
-    cols.beta = to_i(fe_from_u64x4(d->beta));
-    cols.gamma = to_i(fe_from_u64x4(d->gamma));
-    cols.theta = to_i(fe_from_u64x4(d->theta));
-    cols.y = to_i(fe_from_u64x4(d->y));
-    cols.log_size = k;
-    cols.rot_scale = 1;
-    ProgDev gd;
-    prog_put(mb, d->custom_gates, gates_prog, &gd);
-    std::vector<ProgDev> lgs(d->n_lookups);
-    for (uint32_t i = 0; i < d->n_lookups; i++) prog_put(mb, d->lookup_graphs[i], lookup_progs[i], &lgs[i]);
-    const Fe *l0 = col[at_l0], *l_last = col[at_l0 + 1], *l_active = col[at_l0 + 2];
-    if (d->n_perm_sets) {
-        std::vector<const Fe*> pcols(d->n_perm_columns);
-        for (uint32_t j = 0; j < d->n_perm_columns; j++) {
-            const uint32_t kind = d->perm_column_kind[j], idx = d->perm_column_index[j];
-            pcols[j] = kind == H2HIP_ANY_ADVICE ? col[d->n_fixed + idx] : kind == H2HIP_ANY_FIXED ? col[idx] : col[d->n_fixed + d->n_advice + idx];
-        }
-        pd.z = mb.put(col + at_z, d->n_perm_sets);
-        pd.cols = mb.put(pcols.data(), pcols.size());
-        pd.cosets = mb.put(col + at_z + d->n_perm_sets, d->n_perm_columns);
-        pd.l0 = l0;
-        pd.l_last = l_last;
-        pd.l_active = l_active;
-        pd.delta = to_i(fe_from_u64x4(d->delta));
-        pd.n_sets = d->n_perm_sets;
-        pd.n_cols = d->n_perm_columns;
-        pd.chunk_len = d->chunk_len;
-        pd.last_rotation = d->last_rotation;
-    }
+    const Fe* const* advice = col + d->n_fixed;
+    const ColsDev cols = cols_put(mb, f, col, advice, advice + d->n_advice, k, 1);
+    const std::vector<ProgDev> pds = progs_put(mb, cp);
+    PermDev pd = perm_put(mb, f, col, advice, advice + d->n_advice, col + at_z, col + at_z + d->n_perm_sets, col + at_l0, pow_lo, pow_hi, pow_bits);
     if (mb.overflow) {
         set_error("evaluate_h: metadata region overflow");
         return 1;
     }
+    // ---- upload.  Host form: every coefficient column and `values` cross once, on `s` like everything else of this call.  Of `values`
+    // only the rows of this call's parts cross, in either direction: P rows of consecutive parts are contiguous, so a range of parts is a 2-D copy
     if ((rc = c->stage_h2d(mb.dev_base, mb.host.data(), mb.host.size(), s))) return rc;
-    // ---- host form: every coefficient column and `values` cross once, on `s` like everything else of this call.  Of `values` only the
-    // rows of this call's parts cross, in either direction: P rows of consecutive parts are contiguous, so a range of parts is a 2-D copy
     auto copy_values = [&](Fe* dst, const Fe* from, hipMemcpyKind kind) -> int {
         if (p_end - p_begin == 1u << log_p) {
             H2_CHECK(hipMemcpyAsync(dst, from, size * sizeof(Fe), kind, s));
@@ -1723,36 +1733,24 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, uint64
         return ntt_device_batch(c, part_cols.data() + to, nullptr, count, omega, k, nullptr, s);
     };
     const dim3 grid((uint32_t)((n + 255) / 256)), block(256);
-    const Fe beta_zeta = fe_mul<FrP>(fe_from_u64x4(d->beta), fe_from_u64x4(d->zeta));
+    const Fe beta_zeta = d->n_perm_sets ? fe_mul<FrP>(fe_from_u64x4(d->beta), fe_from_u64x4(d->zeta)) : fe_zero<FrP>();
     for (uint32_t p = p_begin; p < p_end; p++) {
+        // ---- scale and transform: the part's cosets of the key and witness columns and of the first group of lookups
         int t_c = c->timer_begin("evalh_cosets", s);
         if ((rc = to_part(p, 0, 0, n_part_cols))) return rc;
         c->timer_end(t_c, s);
+        // ---- gather
         int t_io = c->timer_begin("evalh_part_io", s);
         hipLaunchKernelGGL(evalh_part_gather_kernel, grid, block, 0, s, (const Fe*)d_values, d_part, k, log_p, p);
         H2_CHECK(hipGetLastError());
         c->timer_end(t_io, s);
-        int t_g = c->timer_begin("evalh_gates", s);
-        if ((rc = enqueue_gates(c, d->custom_gates, gates_prog, gates_plan, gd, cols, d_part, gws, n, s))) return rc;
-        c->timer_end(t_g, s);
-        if (d->n_perm_sets) {
-            pd.delta_start = to_i(fe_mul<FrP>(beta_zeta, fe_pow_u64<FrP>(ext_omega, p)));  // beta g_p; the kernel multiplies by omega^j
-            int t_p = c->timer_begin("evalh_perm", s);
-            hipLaunchKernelGGL(evalh_perm_kernel, grid, block, 0, s, pd, cols, d_part);
-            H2_CHECK(hipGetLastError());
-            c->timer_end(t_p, s);
-        }
-        int t_l = d->n_lookups ? c->timer_begin("evalh_lookups", s) : -1;
-        for (uint32_t i = 0; i < d->n_lookups; i++) {
-            const size_t gi = i % lk_group;
-            if (gi == 0 && i) {  // the next group's cosets, into the group's buffers
-                const size_t cnt = d->n_lookups - i < lk_group ? d->n_lookups - i : lk_group;
-                if ((rc = to_part(p, n_main + 3 * (size_t)i, n_main, 3 * cnt))) return rc;
-            }
-            const LookupDev ld = {col[n_main + 3 * gi], col[n_main + 3 * gi + 1], col[n_main + 3 * gi + 2], l0, l_last, l_active};
-            if ((rc = enqueue_lookup(c, d->lookup_graphs[i], lookup_progs[i], lookup_plans[i], lgs[i], ld, cols, d_part, gws, n, s))) return rc;
-        }
-        c->timer_end(t_l, s);
+        // ---- the pass, over the part's rows: nothing of the permutation's arrives late here, and a later group of lookups is
+        //      scaled and transformed into the group's buffers as the first was
+        if (d->n_perm_sets) pd.delta_start = to_i(fe_mul<FrP>(beta_zeta, fe_pow_u64<FrP>(ext_omega, p)));  // beta g_p; the kernel multiplies by omega^j
+        if ((rc = constraint_pass(c, cp, pds, cols, pd, col + at_l0, col + n_main, lk_group, d_part, n, s, [] { return 0; },
+                                  [&](size_t first, size_t count) { return to_part(p, n_main + 3 * first, n_main, 3 * count); })))
+            return rc;
+        // ---- scatter
         t_io = c->timer_begin("evalh_part_io", s);
         const Fu t_i = d->t_evaluations ? to_i(fe_from_u64x4(d->t_evaluations + 4 * (size_t)p)) : fu_one_i<UF>();
         hipLaunchKernelGGL(evalh_part_scatter_kernel, grid, block, 0, s, (const Fe*)d_part, d_values, k, log_p, p, t_i, d->t_evaluations ? 1 : 0);
@@ -1845,39 +1843,25 @@ static int row_graphs_enqueue(Ctx* c, const char* what, uint32_t k, const Fe* co
                               uint32_t n_advice, const Fe* const* instance, uint32_t n_instance, const uint64_t* challenges, uint32_t n_challenges,
                               const uint64_t* theta, const h2hip_graph* graphs, size_t n_graphs, const void* tail, size_t tail_bytes, hipStream_t s,
                               Launch launch) {
-    const size_t n = (size_t)1 << k;
-    std::vector<Program> progs(n_graphs);
-    uint32_t max_slots = 0;
-    size_t meta_cap = 4096 + ((size_t)n_challenges + n_fixed + n_advice + n_instance) * sizeof(Fu) + n_graphs * (sizeof(ProgDev) + 512) + tail_bytes;
-    for (size_t i = 0; i < n_graphs; i++) {
-        progs[i] = compile_graph(graphs[i]);
-        if (progs[i].n_slots > max_slots) max_slots = progs[i].n_slots;
-        meta_cap += prog_bytes(graphs[i], progs[i]);
-    }
-    meta_cap = (meta_cap + 255) / 256 * 256;
-    SlotPlan plan;
-    int rc = slot_plan(max_slots, n, &plan);
+    if (n_graphs == 0) return 0;
+    CallPlan cp;
+    int rc = call_plan(nullptr, graphs, n_graphs, (size_t)1 << k, &cp);
     if (rc) return rc;
+    const SlotPlan& plan = cp.plans[cp.largest];
+    const size_t meta_cap = align256(4096 + ((size_t)n_challenges + n_fixed + n_advice + n_instance) * sizeof(Fu) + n_graphs * (sizeof(ProgDev) + 512) +
+                                     tail_bytes + cp.meta_bytes);
     if ((rc = c->evalh_ws.ensure(meta_cap))) return rc;
-    if (plan.ws_bytes && (rc = c->evalh_slots.ensure(plan.ws_bytes))) return rc;
+    if (cp.slots_ws && (rc = c->evalh_slots.ensure(cp.slots_ws))) return rc;
     MetaBlob mb;
     mb.dev_base = (char*)c->evalh_ws.p;
     mb.cap = meta_cap;
-    ColsDev cols;
-    memset(&cols, 0, sizeof(cols));
-    cols.fixed = mb.put(fixed, n_fixed);
-    cols.advice = mb.put(advice, n_advice);
-    cols.instance = mb.put(instance, n_instance);
-    {
-        std::vector<Fu> hch(n_challenges);
-        for (uint32_t i = 0; i < n_challenges; i++) hch[i] = to_i(fe_from_u64x4(challenges + 4 * (size_t)i));
-        cols.challenges = mb.put(hch.data(), hch.size());
-    }
-    if (theta) cols.theta = to_i(fe_from_u64x4(theta));
-    cols.log_size = k;
-    cols.rot_scale = 1;
-    std::vector<ProgDev> pd(n_graphs);
-    for (size_t i = 0; i < n_graphs; i++) prog_put(mb, graphs[i], progs[i], &pd[i]);
+    h2hip_evalh_desc d;  // what cols_put reads: rows are read by graphs that see no y, beta or gamma
+    memset(&d, 0, sizeof(d));
+    d.n_fixed = n_fixed, d.n_advice = n_advice, d.n_instance = n_instance;
+    d.challenges = challenges, d.n_challenges = n_challenges;
+    d.theta = theta;
+    const ColsDev cols = cols_put(mb, d, fixed, advice, instance, k, 1);
+    const std::vector<ProgDev> pd = progs_put(mb, cp);
     const ProgDev* d_progs = mb.put(pd.data(), pd.size());
     const void* d_tail = mb.put((const char*)tail, tail_bytes);
     if (mb.overflow) {
@@ -1885,20 +1869,12 @@ static int row_graphs_enqueue(Ctx* c, const char* what, uint32_t k, const Fe* co
         return 1;
     }
     if ((rc = c->stage_h2d(mb.dev_base, mb.host.data(), mb.host.size(), s))) return rc;
-    Fu* const gws = (Fu*)c->evalh_slots.p;
     // the global-workspace form (a graph with more than 256 live values) shares one workspace: one graph per launch
     const uint32_t per_launch = plan.tier == 0 ? 1u : (uint32_t)n_graphs;
     for (size_t g0 = 0; g0 < n_graphs; g0 += per_launch) {
-        const dim3 grid(plan.lanes / 256, per_launch);
-        auto go = [&](auto tier, size_t lds) { launch(tier, grid, lds, d_progs + g0, cols, g0, d_tail, gws, plan.lanes); };
-        switch (plan.tier) {
-            case 4: go(std::integral_constant<int, 4>{}, 4 * 9 * 256 * 4); break;
-            case 8: go(std::integral_constant<int, 8>{}, 8 * 9 * 256 * 4); break;
-            case 16: go(std::integral_constant<int, 16>{}, EVALH_LDS_HOT * 9 * 256 * 4); break;
-            case 64: go(std::integral_constant<int, 64>{}, EVALH_LDS_HOT * 9 * 256 * 4); break;
-            case 256: go(std::integral_constant<int, 256>{}, EVALH_LDS_HOT * 9 * 256 * 4); break;
-            default: go(std::integral_constant<int, 0>{}, 0);
-        }
+        with_tier(plan.tier, [&](auto tier, size_t lds) {
+            launch(tier, dim3(plan.lanes / 256, per_launch), lds, d_progs + g0, cols, g0, d_tail, (Fu*)c->evalh_slots.p, plan.lanes);
+        });
         H2_CHECK(hipGetLastError());
     }
     return 0;

@@ -207,6 +207,71 @@ def test_evaluator_new_builds_the_golden_graphs(evalh_golden):
             assert np.array_equal(f[key], evalh_golden["k3_" + name + "_" + key]), (name, key)
 
 
+def _to_device(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).cuda()
+
+
+def _device_description(case):
+    """-> (holder, tensors): the description of `case` for h2hip_evaluate_h_bn254_device -- every column uploaded (torch tensors, by the
+    case's keys) and its device address put where the host description had the array's"""
+    tens = {key: [_to_device(a) for a in case[key]] for key in ("fixed_cosets", "advice_polys", "instance_polys", "perm_product_cosets", "perm_cosets")}
+    for key in ("l0", "l_last", "l_active_row"):
+        tens[key] = _to_device(case[key])
+    tens["lookups"] = [[_to_device(p) for p in l[1:]] for l in case["lookups"]]
+    hd = DescHolder(case)  # host description first, then swap in the device addresses
+    d = hd.desc
+
+    def table(ts):
+        arr = (ctypes.c_void_p * max(1, len(ts)))(*[t.data_ptr() for t in ts])
+        hd.keep.append(arr)
+        return ctypes.addressof(arr)
+
+    d.fixed_cosets, d.advice_polys, d.instance_polys = table(tens["fixed_cosets"]), table(tens["advice_polys"]), table(tens["instance_polys"])
+    d.perm_product_cosets, d.perm_cosets = table(tens["perm_product_cosets"]), table(tens["perm_cosets"])
+    d.l0, d.l_last, d.l_active_row = tens["l0"].data_ptr(), tens["l_last"].data_ptr(), tens["l_active_row"].data_ptr()
+    d.lookup_product_polys = table([l[0] for l in tens["lookups"]])
+    d.lookup_permuted_input_polys = table([l[1] for l in tens["lookups"]])
+    d.lookup_permuted_table_polys = table([l[2] for l in tens["lookups"]])
+    return hd, tens
+
+
+@pytest.mark.gpu
+def test_gpu_evaluate_h_host_form_behind_an_unsynchronised_device_form(h2, oracle, gates_kernel):
+    """A device-form call queued on the caller's stream and not waited for, followed at once by a host-form call of another system on
+    the same context: both results equal the oracle's, limb for limb.  The two calls share the engine's arena, and the host form sends
+    its permutation columns (three product cosets, five unpinned permutation cosets) over a second internal stream, which must not
+    start before the first call's kernels have read their arena columns; the host-form system has other column counts (8 fixed, 6
+    advice, one lookup against 6, 5 and two), so its arena layout does not coincide with the first call's.  At k = 5 the first call's
+    kernels are too short for a missing order to show in the values: what this test pins is the call sequence -- which no other
+    test runs, the parts tests queue device form behind device form on one stream -- and its results; the order itself is the event
+    evaluate_h_host records on the call's stream after ws_acquire and makes that second stream wait for."""
+    import torch
+    L = h2.lib()
+    # the gate programs of seeds 9 and 13 are the ones test_gpu_evaluate_h_vs_oracle compiled: nothing to compile between the two calls
+    case_d, vin_d = _random_case(oracle, 5, seed=9)
+    case_h, vin_h = _random_case(oracle, 5, seed=13)
+    n, size = 1 << case_h["k"], 1 << case_h["extended_k"]
+    case_h["fixed_cosets"] = case_h["fixed_cosets"] + [oracle.gen_scalars(13500 + i, size) for i in range(2)]
+    case_h["advice_polys"] = case_h["advice_polys"] + [oracle.gen_scalars(13600, n)]
+    case_h["lookups"] = case_h["lookups"][:1]
+    hh, hd_host = DescHolder(case_h), DescHolder(case_d)
+    want_d, want_h = vin_d.copy(), vin_h.copy()
+    assert oracle.lib().oracle_evaluate_h(hd_host.byref(), want_d.ctypes.data_as(ctypes.c_void_p)) == 0
+    assert oracle.lib().oracle_evaluate_h(hh.byref(), want_h.ctypes.data_as(ctypes.c_void_p)) == 0
+    hd, tens = _device_description(case_d)
+    d_values = _to_device(vin_d)
+    got_h = vin_h.copy()
+    torch.cuda.synchronize()
+    stream = torch.cuda.current_stream().cuda_stream
+    rc_d = L.h2hip_evaluate_h_bn254_device(hd.byref(), ctypes.c_void_p(d_values.data_ptr()), ctypes.c_void_p(stream))  # returns with its kernels queued
+    rc_h = L.h2hip_evaluate_h_bn254(hh.byref(), got_h.ctypes.data_as(ctypes.c_void_p))
+    assert rc_d == 0 and rc_h == 0, L.h2hip_last_error()
+    torch.cuda.synchronize()
+    assert np.array_equal(d_values.cpu().numpy().view(np.uint64), want_d)
+    assert np.array_equal(got_h, want_h)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("group_bytes", [0, 1])
 def test_gpu_evaluate_h_device_resident(h2, oracle, group_bytes, gates_kernel):
@@ -220,30 +285,9 @@ def test_gpu_evaluate_h_device_resident(h2, oracle, group_bytes, gates_kernel):
     h = DescHolder(case)
     want = vin.copy()
     assert oracle.lib().oracle_evaluate_h(h.byref(), want.ctypes.data_as(ctypes.c_void_p)) == 0
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).cuda()  # noqa: E731
-    keep = []
-    tens = {}
-    for key in ("fixed_cosets", "advice_polys", "instance_polys", "perm_product_cosets", "perm_cosets"):
-        tens[key] = [dev(a) for a in case[key]]
-    for key in ("l0", "l_last", "l_active_row"):
-        tens[key] = dev(case[key])
-    tens["lookups"] = [[dev(p) for p in l[1:]] for l in case["lookups"]]
+    hd, tens = _device_description(case)
     before = {k: ([t.clone() for t in v] if isinstance(v, list) and not isinstance(v[0], list) else v) for k, v in tens.items() if k != "lookups"}
-    hd = DescHolder(case)  # host description first, then swap in the device addresses
-    d = hd.desc
-
-    def table(ts):
-        arr = (ctypes.c_void_p * max(1, len(ts)))(*[t.data_ptr() for t in ts])
-        keep.append(arr)
-        return ctypes.addressof(arr)
-
-    d.fixed_cosets, d.advice_polys, d.instance_polys = table(tens["fixed_cosets"]), table(tens["advice_polys"]), table(tens["instance_polys"])
-    d.perm_product_cosets, d.perm_cosets = table(tens["perm_product_cosets"]), table(tens["perm_cosets"])
-    d.l0, d.l_last, d.l_active_row = tens["l0"].data_ptr(), tens["l_last"].data_ptr(), tens["l_active_row"].data_ptr()
-    d.lookup_product_polys = table([l[0] for l in tens["lookups"]])
-    d.lookup_permuted_input_polys = table([l[1] for l in tens["lookups"]])
-    d.lookup_permuted_table_polys = table([l[2] for l in tens["lookups"]])
-    d_values = dev(vin)
+    d_values = _to_device(vin)
     stream = torch.cuda.current_stream().cuda_stream
     try:
         rc = h2.lib().h2hip_evaluate_h_bn254_device(hd.byref(), ctypes.c_void_p(d_values.data_ptr()), ctypes.c_void_p(stream))

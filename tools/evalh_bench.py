@@ -6,6 +6,7 @@ gate polynomials over `--advice` advice and `--fixed` fixed columns with rotatio
 
   python tools/evalh_bench.py --k 18 [--check-k 12]     (run on the GPU box)
   python tools/evalh_bench.py --k 18 --parts            (the parts form beside the full form)
+  python tools/evalh_bench.py --k 12 --parts            (launch-bound: `enqueue_us`, the host time of a device-form call, for both forms)
 """
 import argparse
 import ctypes
@@ -38,6 +39,22 @@ def system_expressions(args, rng):
     lookups = [([A(li % args.advice), ('prod', A((li + 1) % args.advice), F(li % args.fixed))], [F((li + 1) % args.fixed), F((li + 2) % args.fixed, 1)])
                for li in range(args.lookups)]
     return gates, lookups
+
+
+def enqueue_us(call, reps=200):
+    """host time of one device-form call in microseconds: the clock around the call alone, its kernels not waited for (median of `reps`
+    after a warm-up; the queue is drained between calls, outside the clock).  At a small k the call is launch-bound and this is what the
+    caller's thread sees of the driver's host work."""
+    import torch
+    call()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        call()
+        ts.append(time.perf_counter() - t0)
+        torch.cuda.synchronize()
+    return float(np.median(ts)) * 1e6
 
 
 def build_system(ev, args, rng):
@@ -196,6 +213,7 @@ def bench(args):
         generated = stats1[2] > stats0[2]
         res["gpu_ms"] = timed()
         res["stage_ms"] = stages()
+        res["enqueue_us"] = enqueue_us(call)
         res["gates_kernel"] = "generated per circuit (hiprtc)" if generated else "interpreter (the program is beyond the generator's limits, or hiprtc is missing)"
         res["first_call_with_inline_compile_s"] = first_call_s
         if check or time_cpu:
@@ -312,6 +330,7 @@ def bench_parts(args):
             torch.cuda.synchronize()
             ts.append(e0.elapsed_time(e1))
         res["gpu_ms"] = float(np.median(ts))
+        res["enqueue_us"] = enqueue_us(call)
         h2.profile_enable(True)
         h2.profile_reset()
         for _ in range(3):
