@@ -337,6 +337,7 @@ static int graph_validate(const h2hip_graph& g, const h2hip_evalh_desc& d, const
 // ---- graph -> program (see the comment at DevOp).  Assumes graph_validate passed.
 struct Program {
     std::vector<DevOp> ops;
+    std::vector<double> mags;  // per op: the tracked magnitude of its result in units of r (step 4 of compile_graph)
     uint32_t n_slots = 0;
     h2hip_value_source result = {EVALH_VS_ZERO, 0, 0};
 };
@@ -468,11 +469,15 @@ static Program compile_graph(const h2hip_graph& g) {
         }
         slot_mag[o.dst] = m;
         P.ops.push_back(o);
+        P.mags.push_back(m);
         pos++;
     }
     if (result.kind == H2HIP_VS_INTERMEDIATE) {
         result.a = slot[result.a];
-        if (slot_mag[result.a] > EVALH_MAG_RESULT) P.ops.push_back({OP_MOV | OP_REDUCE_FLAG, result.a, result, none});
+        if (slot_mag[result.a] > EVALH_MAG_RESULT) {
+            P.ops.push_back({OP_MOV | OP_REDUCE_FLAG, result.a, result, none});
+            P.mags.push_back(slot_mag[result.a] / 169.0 + 1.0);
+        }
     }
     // 5. renumber the slots by how often the program touches them, busiest first: the kernels keep the lowest-numbered
     //    slots in LDS and the rest in scratch
@@ -584,6 +589,60 @@ static bool hiprtc_load() {  // under g_rtc_mu
     return true;
 }
 
+// Two products that meet in a sum or difference share ONE Montgomery reduction (fu_mul_sub: (ab - cd) / 2^261, the columns of both
+// products in one accumulator; a sum passes -c): a product whose only reader is the next ADD / SUB / Horner step on its slot is not
+// emitted where the program has it but inside that reader.  Per gate of the usual shape -- selector * (product - product + ...)
+// folded with y -- that is two of six reductions.  The value is the same field element (the reduced representative may differ by a
+// multiple of r before the closing exact reduction, which the interpreter's magnitude bounds cover: the fused form's bound,
+// (|a||b| + |c||d|) / 169 + 1, is below the sum of the two separate ones).
+// The decision alone, for gen_source and for the program hook (h2hip_debug_evalh_program): per op, the op it is emitted inside, or -1.
+static std::vector<int> fusion_plan(const Program& P, bool fuse) {
+    const size_t n_ops = P.ops.size();
+    std::vector<int> fused_into(n_ops, -1);  // product i is emitted inside op fused_into[i]
+    if (fuse) {
+        auto is_slot = [](const h2hip_value_source& v) { return v.kind == H2HIP_VS_INTERMEDIATE; };
+        for (size_t i = 0; i < n_ops; i++) {
+            const DevOp& m = P.ops[i];
+            if (m.op != OP_MUL) continue;  // (a product carrying a reduction request stays where it is)
+            const uint32_t X = m.dst;
+            int reader = -1;
+            bool ok = true;
+            for (size_t j = i + 1; j < n_ops && ok; j++) {
+                const DevOp& o = P.ops[j];
+                const uint32_t k = o.op & 0xff;
+                const bool rx = is_slot(o.x) && o.x.a == X, ry = is_slot(o.y) && o.y.a == X, rd = k == OP_FMA && o.dst == X;
+                if (reader < 0) {
+                    if (rx || ry || rd) {
+                        // the one reader: an ADD / SUB taking it as either operand (not both), or a Horner step taking it as the addend
+                        if ((k == OP_ADD || k == OP_SUB) && rx != ry && !rd) reader = (int)j;
+                        else if (k == OP_FMA && rx && !ry && !rd) reader = (int)j;
+                        else ok = false;
+                        if (ok && o.dst == X) break;  // the reader overwrites the slot: nothing later sees the product
+                        continue;
+                    }
+                    if (o.dst == X) ok = false;  // overwritten unread: dead code the compiler kept (cannot happen), leave it alone
+                    // the product's own operands must still hold their values when the reader runs
+                    if ((is_slot(m.x) && o.dst == m.x.a) || (is_slot(m.y) && o.dst == m.y.a)) ok = false;
+                } else {
+                    if (rx || ry || rd) ok = false;   // a second reader
+                    else if (o.dst == X) break;       // overwritten: the product was dead after its one reader
+                }
+            }
+            if (ok && reader >= 0 && !(is_slot(P.result) && P.result.a == X && P.ops[reader].dst != X)) fused_into[i] = reader;
+        }
+        // an ADD / SUB fuses only when BOTH operands are such products; a Horner step when its addend is
+        std::vector<int> cnt(n_ops, 0);
+        for (size_t i = 0; i < n_ops; i++)
+            if (fused_into[i] >= 0) cnt[fused_into[i]]++;
+        for (size_t i = 0; i < n_ops; i++)
+            if (fused_into[i] >= 0) {
+                const uint32_t k = P.ops[fused_into[i]].op & 0xff;
+                if ((k == OP_ADD || k == OP_SUB) && cnt[fused_into[i]] != 2) fused_into[i] = -1;
+            }
+    }
+    return fused_into;
+}
+
 // the program as HIP source.  Operands: constants are literals (I-form limbs), slots are locals, a column operand is a load at the
 // row index of its rotation (one index variable per distinct rotation), challenges and beta / gamma / theta / y come with the launch.
 static bool g_evalh_gen_barriers = true;
@@ -661,55 +720,8 @@ static std::string gen_source(const h2hip_graph& g, const Program& P, bool looku
         for (uint32_t i = 1; i < P.n_slots; i++) add(", s%u", i);
         src += ";\n";
     }
-    // Two products that meet in a sum or difference share ONE Montgomery reduction (fu_mul_sub: (ab - cd) / 2^261, the columns of both
-    // products in one accumulator; a sum passes -c): a product whose only reader is the next ADD / SUB / Horner step on its slot is not
-    // emitted where the program has it but inside that reader.  Per gate of the usual shape -- selector * (product - product + ...)
-    // folded with y -- that is two of six reductions.  The value is the same field element (the reduced representative may differ by a
-    // multiple of r before the closing exact reduction, which the interpreter's magnitude bounds cover: the fused form's bound,
-    // (|a||b| + |c||d|) / 169 + 1, is below the sum of the two separate ones).
     const size_t n_ops = P.ops.size();
-    std::vector<int> fused_into(n_ops, -1);  // product i is emitted inside op fused_into[i]
-    if (g_evalh_gen_fuse) {
-        auto is_slot = [](const h2hip_value_source& v) { return v.kind == H2HIP_VS_INTERMEDIATE; };
-        for (size_t i = 0; i < n_ops; i++) {
-            const DevOp& m = P.ops[i];
-            if (m.op != OP_MUL) continue;  // (a product carrying a reduction request stays where it is)
-            const uint32_t X = m.dst;
-            int reader = -1;
-            bool ok = true;
-            for (size_t j = i + 1; j < n_ops && ok; j++) {
-                const DevOp& o = P.ops[j];
-                const uint32_t k = o.op & 0xff;
-                const bool rx = is_slot(o.x) && o.x.a == X, ry = is_slot(o.y) && o.y.a == X, rd = k == OP_FMA && o.dst == X;
-                if (reader < 0) {
-                    if (rx || ry || rd) {
-                        // the one reader: an ADD / SUB taking it as either operand (not both), or a Horner step taking it as the addend
-                        if ((k == OP_ADD || k == OP_SUB) && rx != ry && !rd) reader = (int)j;
-                        else if (k == OP_FMA && rx && !ry && !rd) reader = (int)j;
-                        else ok = false;
-                        if (ok && o.dst == X) break;  // the reader overwrites the slot: nothing later sees the product
-                        continue;
-                    }
-                    if (o.dst == X) ok = false;  // overwritten unread: dead code the compiler kept (cannot happen), leave it alone
-                    // the product's own operands must still hold their values when the reader runs
-                    if ((is_slot(m.x) && o.dst == m.x.a) || (is_slot(m.y) && o.dst == m.y.a)) ok = false;
-                } else {
-                    if (rx || ry || rd) ok = false;   // a second reader
-                    else if (o.dst == X) break;       // overwritten: the product was dead after its one reader
-                }
-            }
-            if (ok && reader >= 0 && !(is_slot(P.result) && P.result.a == X && P.ops[reader].dst != X)) fused_into[i] = reader;
-        }
-        // an ADD / SUB fuses only when BOTH operands are such products; a Horner step when its addend is
-        std::vector<int> cnt(n_ops, 0);
-        for (size_t i = 0; i < n_ops; i++)
-            if (fused_into[i] >= 0) cnt[fused_into[i]]++;
-        for (size_t i = 0; i < n_ops; i++)
-            if (fused_into[i] >= 0) {
-                const uint32_t k = P.ops[fused_into[i]].op & 0xff;
-                if ((k == OP_ADD || k == OP_SUB) && cnt[fused_into[i]] != 2) fused_into[i] = -1;
-            }
-    }
+    const std::vector<int> fused_into = fusion_plan(P, g_evalh_gen_fuse);  // product i is emitted inside op fused_into[i]
     auto product_of = [&](size_t j, const h2hip_value_source& v) -> const DevOp* {  // the product fused into op j that v names
         for (size_t i = 0; i < j; i++)
             if (fused_into[i] == (int)j && v.kind == H2HIP_VS_INTERMEDIATE && P.ops[i].dst == v.a) return &P.ops[i];
@@ -1066,6 +1078,34 @@ extern "C" int h2hip_debug_evalh_compile_stats(const h2hip_graph* g, uint32_t* n
     if (compile_any(g, &P)) return 1;
     *n_ops = (uint32_t)P.ops.size();
     *n_slots = P.n_slots;
+    return 0;
+}
+
+// test hook, needs no GPU: the program itself, as the kernels read it (DevOp words, reduce flags included), the magnitude compile_graph
+// tracked after each op and the generator's fusion decision with fusion on and off
+extern "C" int h2hip_debug_evalh_program(const h2hip_graph* g, uint32_t* ops, size_t cap_ops, uint32_t* n_ops, uint32_t* n_slots, uint32_t result[3],
+                                         double* mags, int32_t* fused_on, int32_t* fused_off) {
+    if (!g || !n_ops || !n_slots || !result) {
+        set_error("evaluate_h: null argument");
+        return 1;
+    }
+    Program P;
+    if (compile_any(g, &P)) return 1;
+    static_assert(sizeof(DevOp) == 8 * sizeof(uint32_t), "a DevOp is the eight words ld_op reads");
+    const size_t n = P.ops.size();
+    *n_ops = (uint32_t)n;
+    *n_slots = P.n_slots;
+    result[0] = P.result.kind;
+    result[1] = P.result.a;
+    result[2] = P.result.b;
+    if (n > cap_ops) return 0;  // the sizes alone: call again with room for n_ops
+    const std::vector<int> on = fusion_plan(P, true), off = fusion_plan(P, false);
+    for (size_t i = 0; i < n; i++) {
+        if (ops) memcpy(ops + 8 * i, &P.ops[i], sizeof(DevOp));
+        if (mags) mags[i] = P.mags[i];
+        if (fused_on) fused_on[i] = on[i];
+        if (fused_off) fused_off[i] = off[i];
+    }
     return 0;
 }
 

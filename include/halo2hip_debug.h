@@ -93,6 +93,14 @@ int h2hip_debug_evalh_codegen_source(const h2hip_graph* g, char* buf, size_t cap
 int h2hip_debug_evalh_codegen_stats(uint64_t out[5]);
 /* evaluate_h: compile a graph as the engine would and report the program's size; needs no GPU */
 int h2hip_debug_evalh_compile_stats(const h2hip_graph* g, uint32_t* n_ops, uint32_t* n_slots);
+/* evaluate_h: the program a graph compiles to; needs no GPU.  *n_ops, *n_slots and result (kind, a, b of the value the row stores; kind 11 =
+ * the field's zero, an empty graph) are always filled; with cap_ops >= *n_ops also, per op and where the pointer is not NULL: ops = 8 words
+ * (op with the reduce flag 0x100, dst slot, x.kind, x.a, x.b, y.kind, y.a, y.b; an INTERMEDIATE operand's a is its slot), mags = the
+ * magnitude in units of r that the compiler tracked for the op's result (after its reduction where it carries one), fused_on / fused_off =
+ * the op inside which the per-circuit generator emits this product (two products meeting in a sum share one reduction), or -1, with the
+ * fusion on (the default) and off (h2hip_debug_set_evalh_codegen mode + 16).  Returns 0 or 1 (malformed graph, null argument). */
+int h2hip_debug_evalh_program(const h2hip_graph* g, uint32_t* ops, size_t cap_ops, uint32_t* n_ops, uint32_t* n_slots, uint32_t result[3],
+                              double* mags, int32_t* fused_on, int32_t* fused_off);
 /* the split of a domain's two-level power table (omega^e = lo[e & (2^lo_bits - 1)] * hi[e >> lo_bits]) that evaluate_h's permutation
  * kernel walks: rows at or beyond 2^lo_bits take the second factor.  Builds the table when the domain has none yet; needs a GPU. */
 int h2hip_debug_evalh_power_table_bits(const uint64_t omega[4], uint32_t log_n, uint32_t* lo_bits);
