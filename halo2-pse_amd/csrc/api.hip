@@ -5,7 +5,7 @@
 // ecfft.hip, setup.hip, gen.hip, product.hip, opening.hip, lookup.hip, keygen.hip, check.hip, serde.hip).  This file keeps init /
 // shutdown / errors / profile, the device memory helpers, the MSM's host and device forms (sharding, fold, RCCL gather), the pins
 // (bases, lazy, columns), the NTT / domain family (batch_over_devices, the host pipeline), h2hip_g1_fold / _batch_normalize /
-// _to_affine, and the hooks that set its own statics (h2hip_debug_set_ntt_host_batch, _set_lazy_pin, _set_table_records,
+// _to_affine, the one Tuning instance with its guards (engine.h), and the hooks of its own settings (h2hip_debug_set_ntt_host_batch, _set_lazy_pin, _set_table_records,
 // _rccl_gather_selftest).  That is also all that runs in the stub build: this file compiled alone, as plain C++ against
 // tests/cpp/hipstub, and linked with tests/cpp/engine_stubs.cpp, which stands in for what this file calls in the stage files.
 #include <dlfcn.h>
@@ -98,7 +98,8 @@ void DevBuf::release() {
 // points.  The other devices only ever run MSM shards (best_multiexp splits its pairs the same way over rayon
 // threads, arithmetic.rs:137-153), each from its own worker thread.
 // Locking (round 3; one process-wide mutex before): g_engine_mu is held shared by every entry point and exclusively by
-// h2hip_init / h2hip_shutdown, so the device list cannot change under a running call.  Each device context has its own
+// h2hip_init / h2hip_shutdown and the setter hooks (TuneWrite), so neither the device list nor a setting can change under a
+// running call.  Each device context has its own
 // mutex: a `_device` entry point locks only the context that owns its pointers, so calls on different GPUs -- and concurrent
 // best_fft callers spread over devices (plonk/permutation/keygen.rs:216-233) -- overlap.  Entry points that touch every
 // device (host-pointer MSMs over several GPUs, pin / unpin, pinned_info) lock all contexts in list order; the lazy-pin
@@ -209,35 +210,14 @@ int Ctx::ws_release(hipStream_t s) {
     return 0;
 }
 
-// aux1 (stage A) and aux2 (stage C) run on a reserved slice of the CUs, aux_b (stage B) on the rest.  The slice
-// takes K/16 of every 16 consecutive CU ids, so it is spread over all XCDs whatever the id -> XCD mapping is.
+// aux1 (stage A), aux2 (stage C) and aux_b (stage B) see every CU: a slice of the CUs reserved for the sort and reduce streams was
+// slower for every split tried ("Tried ..., measured, not kept").  They are still created through the CU-mask call, with
+// a full mask: as plain hipStreamCreate streams the pipelined batch of eight 2^20-pair MSMs measured 1.26 against 1.16 ms per MSM
+// (profiles/tuning_struct/ab.md, first session).
 int Ctx::ensure_aux(size_t n_events) {
-    const uint32_t K = msm_get_reserved_cus();
-    if (aux1 && aux_reserved != K) {
-        H2_CHECK(hipDeviceSynchronize());
-        (void)hipStreamDestroy(aux1);
-        (void)hipStreamDestroy(aux2);
-        (void)hipStreamDestroy(aux_b);
-        aux1 = aux2 = aux_b = nullptr;
-    }
-    if (!aux1) {
-        const int n_cu = sm_count;
-        const uint32_t words = (uint32_t)((n_cu + 31) / 32);
-        std::vector<uint32_t> mask_ac(words, 0), mask_b(words, 0);
-        const uint32_t per16 = (K * 16 + (uint32_t)n_cu - 1) / (uint32_t)n_cu;  // reserved ids out of every 16
-        for (int i = 0; i < n_cu; i++) {
-            bool reserved = K > 0 && (uint32_t)(i % 16) >= 16 - per16;
-            (reserved ? mask_ac : mask_b)[i / 32] |= 1u << (i % 32);
-        }
-        if (K == 0 || per16 >= 16) {  // no partition: every stream sees every CU
-            for (auto& w : mask_ac) w = 0xffffffffu;
-            for (auto& w : mask_b) w = 0xffffffffu;
-        }
-        H2_CHECK(hipExtStreamCreateWithCUMask(&aux1, words, mask_ac.data()));
-        H2_CHECK(hipExtStreamCreateWithCUMask(&aux2, words, mask_ac.data()));
-        H2_CHECK(hipExtStreamCreateWithCUMask(&aux_b, words, mask_b.data()));
-        aux_reserved = K;
-    }
+    const std::vector<uint32_t> every_cu((size_t)(sm_count + 31) / 32, 0xffffffffu);
+    for (hipStream_t* s : {&aux1, &aux2, &aux_b})
+        if (!*s) H2_CHECK(hipExtStreamCreateWithCUMask(s, (uint32_t)every_cu.size(), every_cu.data()));
     while (aux_events.size() < n_events) {
         hipEvent_t e;
         H2_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -256,10 +236,16 @@ struct Config {
     size_t table_max_bytes = (size_t)160 << 30;  // HALO2_HIP_TABLE_MAX_GB: largest window table built at pin time
     bool allow_dup = false;                    // HALO2_HIP_ALLOW_DUPLICATE_DEVICES=1: rehearsal on a one-GPU box
     bool roctx = false;                        // HALO2_HIP_ROCTX=1: roctx range around every entry point
-    uint32_t lazy_pin_after = 0;               // HALO2_HIP_LAZY_PIN=k: a host bases array seen k times unpinned is pinned by the library
     size_t column_cache_bytes = (size_t)64 << 30;  // HALO2_HIP_COLUMN_CACHE_GB: HBM the pinned proving-key columns may take (least recently used dropped first)
 };
 static Config g_cfg;
+
+// ---- tuning (engine.h): the one instance, its reader and the two guards -------------------------------------------------------------
+static Tuning g_tuning;
+const Tuning& tune() { return g_tuning; }
+TuneWrite::TuneWrite() : engine(g_engine_mu) {}
+Tuning* TuneWrite::operator->() const { return &g_tuning; }
+TuneRead::TuneRead() : engine(g_engine_mu) {}
 
 static bool env_u64(const char* name, uint64_t* out) {
     const char* v = getenv(name);
@@ -271,8 +257,10 @@ static bool env_u64(const char* name, uint64_t* out) {
     return true;
 }
 
+// under do_init's exclusive hold of the engine lock: the members are written directly (a TuneWrite here would wait for itself)
 static void read_config() {
     Config c;
+    Tuning& t = g_tuning;
     uint64_t v;
     if (env_u64("HALO2_HIP_MULTI_GPU_MIN_N", &v)) c.multi_gpu_min_n = (size_t)v;
     if (env_u64("HALO2_HIP_MSM_MIN_N", &v)) c.msm_min_n = (size_t)v;
@@ -281,15 +269,23 @@ static void read_config() {
     if (env_u64("HALO2_HIP_TABLE_MAX_GB", &v)) c.table_max_bytes = (size_t)v << 30;
     if (env_u64("HALO2_HIP_ALLOW_DUPLICATE_DEVICES", &v)) c.allow_dup = v != 0;
     if (env_u64("HALO2_HIP_ROCTX", &v)) c.roctx = v != 0;
-    if (env_u64("HALO2_HIP_LAZY_PIN", &v)) c.lazy_pin_after = (uint32_t)v;
+    if (env_u64("HALO2_HIP_LAZY_PIN", &v)) t.lazy_pin_after = (uint32_t)v;
     if (env_u64("HALO2_HIP_COLUMN_CACHE_GB", &v)) c.column_cache_bytes = (size_t)v << 30;
-    if (env_u64("HALO2_HIP_NTT_TWIDDLE_MB", &v)) ntt_set_full_twiddle_budget(v << 20);
-    if (env_u64("HALO2_HIP_EVALH_CODEGEN", &v)) evalh_debug_set_codegen((int)v, 0);
-    if (env_u64("HALO2_HIP_MSM_WINDOW", &v) && v >= 2 && v <= 24) msm_set_window((uint32_t)v);
+    if (env_u64("HALO2_HIP_NTT_TWIDDLE_MB", &v)) t.ntt_full_budget = v << 20;
+    if (env_u64("HALO2_HIP_EVALH_CODEGEN", &v)) {  // as h2hip_debug_set_evalh_codegen(v, 0)
+        t.evalh_codegen = (int)v & 15;
+        t.evalh_gen_fuse = !((int)v & 16);
+        t.evalh_codegen_max_ops = Tuning{}.evalh_codegen_max_ops;
+    }
+    if (env_u64("HALO2_HIP_MSM_WINDOW", &v) && v >= 2 && v <= 24) t.msm_window = (uint32_t)v;
     {  // HALO2_HIP_STREAM=0: host-slice MSMs upload whole arrays ahead of the run (no copier thread); HALO2_HIP_STREAM_MIN_N: threshold
         uint64_t on = 1, min_n = 0;
         const bool has_on = env_u64("HALO2_HIP_STREAM", &on), has_min = env_u64("HALO2_HIP_STREAM_MIN_N", &min_n);
-        if (has_on || has_min) msm_set_stream(has_on && on == 0 ? 1 : 0, 0.0, has_min ? (size_t)min_n : 0);
+        if (has_on || has_min) {  // as h2hip_debug_set_msm_stream(HALO2_HIP_STREAM=0 ? 1 : 0, 0, min_n)
+            t.msm_stream_chunks = has_on && on == 0 ? 1 : 0;
+            t.msm_stream_ratio = Tuning{}.msm_stream_ratio;
+            t.msm_stream_min_n = has_min && min_n ? (size_t)min_n : Tuning{}.msm_stream_min_n;
+        }
     }
     const char* g = getenv("HALO2_HIP_GATHER");
     if (g && !strcmp(g, "rccl")) c.gather_rccl = true;
@@ -770,9 +766,7 @@ static int ntt_host(uint64_t* a, const Fe& omega, uint32_t log_n, const NttScale
 // download in series, 11.6 x the device-resident transform at 2^22 (round 3).  Here column i + 1 crosses PCIe upwards and column
 // i - 1 downwards (full duplex, one copier thread per direction: pageable hipMemcpyAsync blocks its caller) while column i is
 // transformed on the engine's stream: per column max(upload, transform, download) instead of their sum.
-static size_t g_ntt_host_batch_bytes = (size_t)4 << 30;  // device memory one pipelined run may hold; larger batches are cut into runs
-static size_t g_ntt_host_group_bytes = (size_t)2 << 20;  // columns smaller than this are grouped per pipeline step
-
+// A batch is cut into runs of Tuning::ntt_host_batch_bytes of device memory, and small columns are grouped per pipeline step.
 struct PipeDrain {  // every exit: the copiers idle, their streams drained -- nothing touches the caller's columns after the call
     Ctx* c;
     hipStream_t su, sd;
@@ -788,7 +782,7 @@ struct PipeDrain {  // every exit: the copiers idle, their streams drained -- no
 static int ntt_host_pipeline(Ctx* c, const uint64_t* const* in, size_t in_elems, uint64_t* const* out, size_t m, const Fe& omega, uint32_t log_n,
                              const NttScale* sc) {
     const size_t col = sizeof(Fe) << log_n, in_bytes = in_elems * sizeof(Fe);
-    size_t gc = g_ntt_host_group_bytes / col;
+    size_t gc = tune().ntt_host_group_bytes / col;
     if (gc < 1) gc = 1;
     const size_t G = (m + gc - 1) / gc;
     int rc;
@@ -827,7 +821,7 @@ static int ntt_host_pipeline(Ctx* c, const uint64_t* const* in, size_t in_elems,
 static int ntt_host_batch_on(Ctx* c, const uint64_t* const* in, size_t in_elems, uint64_t* const* out, size_t count, const Fe& omega, uint32_t log_n,
                              const NttScale* sc) {
     const size_t col = sizeof(Fe) << log_n;
-    size_t per = g_ntt_host_batch_bytes / col;
+    size_t per = tune().ntt_host_batch_bytes / col;
     if (per < 2) per = 2;
     const bool threads = count > 1 && copier_ready(c, false) && copier_ready(c, true);
     for (size_t i0 = 0; i0 < count; i0 += per) {
@@ -1327,7 +1321,6 @@ int h2hip_msm_bn254_batch_device(const void* const* d_scalars, const void* d_bas
     return 0;
 }
 
-static uint32_t g_table_records = 0;  // h2hip_debug_set_table_records
 
 // Pin points [lo, hi) of the caller's array on device context c (worker thread of that device, or the caller's for
 // device 0): device copy + window table.  d_src != nullptr: the points already live on this device.
@@ -1353,7 +1346,7 @@ static int pin_on_device(Ctx* c, const void* key, const uint64_t* h_points, cons
     if (g_cfg.fixed_base && n <= ((size_t)1 << 26)) {
         cw = msm_table_window(n);
         W = (255 + cw - 1) / cw;
-        rec = msm_table_rec(n, g_table_records);
+        rec = msm_table_rec(n, tune().table_records);
         if ((size_t)W * n * rec > g_cfg.table_max_bytes) rec = sizeof(Affine);  // the native table would be refused: the E-form one may still fit
         if ((size_t)W * n * rec > g_cfg.table_max_bytes) cw = 0, W = 1;
     }
@@ -1478,7 +1471,7 @@ static void lazy_forget(const void* key) {
 
 // called by the host-pointer MSMs after pinned_validate; pins `bases_xy` when it has been seen often enough
 static void lazy_pin_consider(const uint64_t* bases_xy, size_t n) {
-    if (!g_cfg.lazy_pin_after || n < 1024) return;
+    if (!tune().lazy_pin_after || n < 1024) return;
     const void* key = (const void*)bases_xy;
     if (ctx()->pinned.count(key)) {  // in use: refresh its place in the LRU order if it is ours
         for (size_t i = 0; i + 1 < g_lazy_pinned.size(); i++)
@@ -1509,7 +1502,7 @@ static void lazy_pin_consider(const uint64_t* bases_xy, size_t n) {
     if (e->count && (e->n != n || memcmp(e->sample, sample, sizeof(sample)) != 0)) e->count = 0;  // another array at this address
     e->n = n;
     memcpy(e->sample, sample, sizeof(sample));
-    if (++e->count < g_cfg.lazy_pin_after) return;
+    if (++e->count < tune().lazy_pin_after) return;
     lazy_forget(key);
     while (g_lazy_pinned.size() >= H2_LAZY_MAX) {
         (void)unpin_everywhere(g_lazy_pinned.front());
@@ -1521,14 +1514,12 @@ static void lazy_pin_consider(const uint64_t* bases_xy, size_t n) {
 uint32_t h2hip_lazy_pin_after(void) {
     if (ensure_init()) return 0;
     std::shared_lock<std::shared_mutex> lk(g_engine_mu);
-    return g_cfg.lazy_pin_after;
+    return tune().lazy_pin_after;
 }
 
 // test hook: the knob without the environment
 int h2hip_debug_set_lazy_pin(uint32_t after) {
-    Entry en("h2hip_debug_set_lazy_pin");
-    if (en.rc) return en.rc;
-    g_cfg.lazy_pin_after = after;
+    TuneWrite()->lazy_pin_after = after;
     return 0;
 }
 
@@ -2052,8 +2043,9 @@ int h2hip_divide_by_vanishing_poly_bn254_fr(uint64_t* a, uint32_t extended_k, co
 }
 
 int h2hip_debug_set_ntt_host_batch(uint64_t run_bytes, uint64_t group_bytes) {
-    g_ntt_host_batch_bytes = run_bytes ? (size_t)run_bytes : (size_t)4 << 30;
-    g_ntt_host_group_bytes = group_bytes ? (size_t)group_bytes : (size_t)2 << 20;
+    TuneWrite t;
+    t->ntt_host_batch_bytes = run_bytes ? (size_t)run_bytes : Tuning{}.ntt_host_batch_bytes;
+    t->ntt_host_group_bytes = group_bytes ? (size_t)group_bytes : Tuning{}.ntt_host_group_bytes;
     return 0;
 }
 
@@ -2152,7 +2144,7 @@ int h2hip_debug_set_table_records(uint32_t bytes) {
         set_error("debug_set_table_records: 0, 64, 80 or 128 expected");
         return H2HIP_EINVAL;
     }
-    g_table_records = bytes;
+    TuneWrite()->table_records = bytes;
     return 0;
 }
 

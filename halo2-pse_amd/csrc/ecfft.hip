@@ -314,12 +314,12 @@ __global__ void __launch_bounds__(256) ecfft_twiddle_kernel(GlvScalar* tw, uint6
     tw[tid] = glv_decompose(c.l);
 }
 
-static bool g_ecfft_quad = true, g_ecfft_lazy = true;
 // tuning hook: g_to_lagrange layers up to k = 14 -- bit 0: one quad of lanes per butterfly (1, default) or one lane (0); bit 1 set: a
 // normalisation after every layer (default clear: the points stay XYZZ between the layers)
 extern "C" int h2hip_debug_set_g2l_quad(int on) {
-    g_ecfft_quad = (on & 1) != 0;
-    g_ecfft_lazy = (on & 2) == 0;  // k <= 14: no normalisation between the layers (round 4); off: round 3's path
+    TuneWrite t;
+    t->ecfft_quad = (on & 1) != 0;
+    t->ecfft_lazy = (on & 2) == 0;  // k <= 14: no normalisation between the layers (round 4); off: round 3's path
     return 0;
 }
 
@@ -381,7 +381,7 @@ static int ecfft_device(Ctx* c, const Affine* d_in, uint32_t k, Affine* d_out, c
         H2_CHECK(hipGetLastError());
     }
     const Affine* src = d_in;
-    if (g_ecfft_quad && g_ecfft_lazy && k >= 1 && k <= 14) {
+    if (tune().ecfft_quad && tune().ecfft_lazy && k >= 1 && k <= 14) {
         // small transforms: the points stay XYZZ across the layers (in place), one normalisation at the very end
         for (uint32_t layer = 0; layer < k; layer++) {
             EcfftLayerX L = {d_in, d_xyzz, d_tw, k, layer};
@@ -400,7 +400,7 @@ static int ecfft_device(Ctx* c, const Affine* d_in, uint32_t k, Affine* d_out, c
     }
     for (uint32_t layer = 0; layer < k; layer++) {
         EcfftLayer L = {src, d_xyzz, d_tw, k, layer};
-        if (g_ecfft_quad && k <= 14)  // few butterflies per layer (<= 2^13: fewer lanes than SIMD slots even four to a butterfly)
+        if (tune().ecfft_quad && k <= 14)  // few butterflies per layer (<= 2^13: fewer lanes than SIMD slots even four to a butterfly)
             hipLaunchKernelGGL(ecfft_layer_quad_kernel, dim3((uint32_t)((2 * n + 255) / 256)), dim3(256), 0, s, L);
         else
             hipLaunchKernelGGL(ecfft_layer_kernel, dim3((uint32_t)((n / 2 + 255) / 256)), dim3(256), 0, s, L);

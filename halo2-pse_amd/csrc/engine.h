@@ -218,7 +218,6 @@ struct Ctx {
     int ws_release(hipStream_t s);
     // internal streams + events for the MSM's window-group pipeline
     hipStream_t aux1 = nullptr, aux2 = nullptr, aux_b = nullptr;
-    uint32_t aux_reserved = 0xffffffffu;  // CU reservation the aux streams were created with
     std::vector<hipEvent_t> aux_events;
     int ensure_aux(size_t n_events);
     // evalh.hip: the per-circuit gates kernels loaded on this device, by source hash -> (hipModule_t, hipFunction_t); a pair of nulls
@@ -268,6 +267,88 @@ struct Entry {
     ~Entry();
 };
 int check_fr(const uint64_t v[4], const char* what);  // H2HIP_EINVAL (and set_error) unless v is a reduced Fr element
+
+// ---- tuning: every knob of the library, its default written once, here.  One instance lives in api.hip (which is also built alone,
+// against the stub runtime).  The rule: an entry point reads tune() under the engine lock its Entry holds shared; a hook that reads
+// without an Entry takes a TuneRead; a setter hook validates its arguments, takes a TuneWrite and assigns -- "0 restores the default"
+// is Tuning{}.member.  read_config (api.hip) writes the environment-backed members under h2hip_init's exclusive lock.  The settings
+// survive h2hip_shutdown; the environment-backed ones are read again at the next init.
+struct Tuning {
+    // -- MSM: plan and sort
+    uint32_t msm_window = 0;      // h2hip_set_msm_window / HALO2_HIP_MSM_WINDOW: forced window width (0 = by size, plain_window / msm_table_window)
+    size_t msm_heavy_div = 32768;  // buckets with more than (entries of the MSM) / this entries take the chunked path (make_plan)
+    size_t msm_bin_entries = 8192;  // target entries per coarse bin of the two-level sort
+    bool msm_split_records = true;  // level-1 records of runs with multi-tile bins as two arrays, or as (entry, bucket id) pairs (msm_l2_kernel)
+    bool msm_split_buckets = true;  // several lanes per bucket in runs with few buckets, or always one
+    size_t msm_max_chunk = (size_t)1 << 26;  // inputs above this many pairs are split into consecutive chunks: the 31-bit pair-index limit
+    // -- MSM: reduction
+    uint64_t msm_rowcol_lanes = 65536;  // lane budget of the first row/column pass: one wave per SIMD (rowcol_jobs)
+    bool msm_quad_tail = true;   // the reduction tail with one quad of lanes per group operation, or one lane
+    bool msm_plane_tail = true;  // runs with at most 4 bucket sets finish the reduction on the host from bit-plane sums, or keep the GPU tail
+    // -- MSM: host-resident scalars (msm.hip, "the upload runs under the work": the sweep behind chunks and ratio is quoted there)
+    uint32_t msm_stream_chunks = 0;  // pieces a streamed MSM is cut into; 1 = no streaming; 0 = by size: three, two below 2^20 pairs (stream_chunks)
+    double msm_stream_ratio = 0.6;   // upload time over compute time per pair: the chunk sizes grow by its inverse
+    size_t msm_stream_min_n = (size_t)1 << 19;  // 2^19 pairs: 1.13 -> 1.04 ms (two chunks); 2^18: 0.72 -> 0.80 ms, not worth it
+    // -- MSM: batches.  measured (tools/fuse_big.py, 8 MSMs per batch, per MSM): 2^19 pairs fused 0.66 ms / pipelined 0.69 ms, 2^20 pairs
+    // fused 1.24 / pipelined 1.16
+    size_t msm_fuse_entries = (size_t)1 << 26, msm_fuse_max_n = (size_t)1 << 19;  // entries a fused run holds at most; pairs per MSM up to which batches are fused
+    bool msm_fuse_small = true;  // batches of small MSMs run fused, or pipelined over streams
+    // -- pins (api.hip)
+    uint32_t table_records = 0;   // record form of the window tables pinned from now on (msm_table_rec): 0 = the engine's choice
+    uint32_t lazy_pin_after = 0;  // HALO2_HIP_LAZY_PIN=k: a host bases array seen k times unpinned is pinned by the library (0 = never)
+    // -- NTT: plans
+    uint32_t ntt_smax = 8;  // largest log2 tile of a pass.  measured (tools/ntt_sweep.py): 256-point tiles are best up to 2^24; beyond, 512-point
+                            // tiles save a whole pass, and while this is at its default plan_passes takes 9 there
+    // Sizes 2^lo..2^hi take the two-pass plan (tiles of 2^10 or 2^11 points, ntt2_*_kernel): measured on MI355X
+    // (tools/ntt_two_pass.py) 14 % faster than three passes at 2^20, 9 % at 2^21, 5 % at 2^22 with two columns per workgroup, 25 / 19 / 12 % with one
+    // (round 3); below 2^19 a lone transform brings too few workgroups.
+    // Batched columns of 2^17 / 2^18 points take it too once the batch brings ntt_two_batch_wgs workgroup pairs per pass (tools/ntt_batch_rate.py, with one
+    // column per workgroup: a lone 2^18 transform 0.068 against 0.052 ms for three passes, two of them 0.041 against 0.048 each; four of 2^17 0.021 / 0.026;
+    // a lone 2^19 already 0.078 / 0.091).
+    uint32_t ntt_two_lo = 19, ntt_two_hi = 22, ntt_two_batch_lo = 17;
+    uint64_t ntt_two_batch_wgs = 512;
+    int ntt_two_log_j = -1;  // log2 columns per workgroup of the two-pass kernels (-1 = the plan's choice)
+    // -- NTT: twiddle tables
+    uint64_t ntt_full_budget = (uint64_t)4 << 30;  // HALO2_HIP_NTT_TWIDDLE_MB: HBM the full inter-pass tables may take per device (of 288 GB); 0 = two-level table only
+    // Strided passes of the three-pass plan read their inter-pass twiddles from a table of up to 2^this entries (36 B each: 0.3 / 0.6 GB per domain
+    // and direction at 2^23 / 2^24 for the first pass's, 2.4 MB for the second's) while the budget lasts: one multiplication per point fewer than
+    // combining the two-level table (2^23 -5 %, 2^24 -2.5 %; at 2^25 and beyond the pass has no memory bandwidth to spare for it and nothing is gained).
+    uint32_t ntt_full_max_log_m = 24;
+    bool ntt_fold_tables = true;  // the inverse's 1/n rides in a scaled copy of the first pass's table; off: the last pass multiplies it in (rounds 1-3)
+    // -- NTT: batches
+    size_t ntt_batch_bytes = (size_t)2 << 30;       // columns + workspace one batched launch may span (ntt_device_batch)
+    size_t ntt_host_batch_bytes = (size_t)4 << 30;  // host-pointer batches: device memory one pipelined run may hold; larger batches are cut into runs
+    size_t ntt_host_group_bytes = (size_t)2 << 20;  // ... and columns smaller than this are grouped per pipeline step
+    // -- evaluate_h.  codegen: the per-circuit gates kernel -- 0 off, 1 compiled on a background thread (HALO2_HIP_EVALH_CODEGEN), 2 inline (tests)
+    int evalh_codegen = 1;
+    // Programs beyond these stay with the interpreter.  hiprtc takes ~20 ms per operation (0.6 s for a dozen, 4 s for 190, 7 s for 315:
+    // every field multiplication is ~200 inlined instructions), and a program with many values alive at once spends minutes in the
+    // register allocator (100 live slots = 900 VGPRs of state: 205 s) for a kernel that would spill anyway (EVALH_CODEGEN_MAX_SLOTS).
+    uint32_t evalh_codegen_max_ops = 1200;
+    bool evalh_gen_fuse = true;  // two products meeting in a sum share one reduction (gen_source); codegen mode + 16 turns it off (A/B, tests)
+    uint32_t evalh_max_local_slots = 256;  // programs needing more slots use the global-workspace form of the kernels (tests force it)
+    size_t evalh_lookup_group_bytes = (size_t)2 << 30;  // HBM one group of lookup cosets may take (tests shrink it to force several groups)
+    // -- the smaller stages
+    bool ecfft_quad = true, ecfft_lazy = true;  // g_to_lagrange / fft_g1 up to k = 14: one quad of lanes per butterfly; the points stay XYZZ between the layers
+    uint32_t lookup_sort_block = 0;  // forced in-LDS sort block of the lookup permutation (0 = LK_TILE)
+    uint32_t open_rows = 0, open_threads = 0;  // opening: forced tile shape, rows per thread and threads per tile (0 = by size)
+    size_t keygen_group_bytes = (size_t)1 << 30;  // HBM one group of columns of a host-pointer keygen call may take (two groups are alive)
+    size_t random_min_n = 0;  // element count from which the host forms of the randomness go to the device (0 = HALO2_HIP_RANDOM_MIN_N or its default, random.hip)
+};
+const Tuning& tune();
+// A setter's hold on the settings: the engine lock taken exclusively, as h2hip_shutdown takes it, so it waits for every running call and
+// the next one sees the new value.  It does not initialise the engine, touches no GPU and opens no roctx range.  Not from inside a
+// call that holds an Entry or a TuneRead (a callback of the library): that would wait for itself.
+struct TuneWrite {
+    std::unique_lock<std::shared_mutex> engine;
+    TuneWrite();
+    Tuning* operator->() const;
+};
+// ... and a query hook's, which reads tune() without an Entry: the lock shared, again without initialising anything
+struct TuneRead {
+    std::shared_lock<std::shared_mutex> engine;
+    TuneRead();
+};
 
 // ---- what the stage files' entry points and host drivers share (inline: api.hip is also built alone, as plain C++ against a stub
 // runtime, for the sanitizer runs of the engine's host logic).  The rule that build rests on: a stage file owns the extern "C" entry
@@ -406,7 +487,6 @@ int ntt_device_batch(Ctx* c, Fe* const* h_datas, const Fe* const* h_srcs, size_t
                      hipStream_t s);
 
 int scale_periodic_device(Ctx* c, Fe* d_a, uint64_t n, const uint64_t* h_t, uint32_t t_len, hipStream_t s);
-void ntt_set_full_twiddle_budget(uint64_t bytes);  // HALO2_HIP_NTT_TWIDDLE_MB
 
 // ecfft.hip
 int g_to_lagrange_device(Ctx* c, const Affine* d_g, uint32_t k, Affine* d_out, hipStream_t s);
@@ -440,7 +520,6 @@ int kzg_setup_device(Ctx* c, uint32_t k, const Fe& s, Affine* d_g, Affine* d_gl,
 const Fe* pinned_column_lookup(Ctx* c, const uint64_t* h_col, size_t elems);
 
 // evalh.hip
-void evalh_debug_set_codegen(int mode, uint32_t max_ops);  // 0 off, 1 background compile (default), 2 compile inline; max_ops 0 = default
 void evalh_modules_free(Ctx* c);                            // unload this device's generated kernels (release_ctx)
 void evalh_rtc_shutdown();                                  // join the compile threads (h2hip_shutdown)
 int evaluate_h_validate(const h2hip_evalh_desc* d, const void* values);
@@ -460,9 +539,6 @@ int check_gates_enqueue(Ctx* c, uint32_t k, const Fe* const* fixed, uint32_t n_f
                         const h2hip_graph* graphs, size_t n_graphs, uint64_t* d_mask, uint32_t words, hipStream_t s);
 
 // msm.hip
-void msm_set_window(uint32_t c);
-void msm_set_stream(uint32_t chunks, double ratio, size_t min_n);
-uint32_t msm_get_reserved_cus();
 // tab != nullptr: fixed-base form over tab's window table (d_bases unused)
 int msm_device(Ctx* c, const Fe* d_scalars, const Affine* d_bases, size_t n, XYZZ* h_out, hipStream_t s, const MsmTable* tab = nullptr);
 int msm_batch_device(Ctx* c, const Fe* const* scalars, bool scalars_on_host, const Affine* d_bases, size_t n, size_t count, XYZZ* h_out,

@@ -523,22 +523,14 @@ static int compile_any(const h2hip_graph* g, Program* P) {
 // operation for operation, so the values are the same limb for limb.  Compilation takes a second or more: it runs on a background
 // thread the first time a program is seen (HALO2_HIP_EVALH_CODEGEN=1, default) while the interpreter serves the calls in between;
 // code objects are cached per process by source hash and, with HALO2_HIP_CACHE_DIR set, on disk.  =2 compiles inline (tests), =0 off.
-static int g_evalh_codegen = 1;
-// Programs beyond these stay with the interpreter.  hiprtc takes ~20 ms per operation (0.6 s for a dozen, 4 s for 190, 7 s for 315:
-// every field multiplication is ~200 inlined instructions), and a program with many values alive at once spends minutes in the
-// register allocator (100 live slots = 900 VGPRs of state: 205 s) for a kernel that would spill anyway.
-static uint32_t g_evalh_codegen_max_ops = 1200;
+// Programs of more than Tuning::evalh_codegen_max_ops operations, or with more values alive at once than this, stay with the interpreter.
 #define EVALH_CODEGEN_MAX_SLOTS 48
-static bool g_evalh_gen_fuse = true;  // two products meeting in a sum share one reduction (gen_source); mode + 16 turns it off (A/B, tests)
-void evalh_debug_set_codegen(int mode, uint32_t max_ops) {
-    g_evalh_codegen = mode & 15;
-    g_evalh_gen_fuse = !(mode & 16);
-    g_evalh_codegen_max_ops = max_ops ? max_ops : 1200;
-}
+// mode: 0 off, 1 background compile (default), 2 compile inline; + 16: without the fusion of two products; max_ops 0 restores the default
 extern "C" int h2hip_debug_set_evalh_codegen(int mode, uint32_t max_ops) {
-    Entry en;
-    if (en.rc) return en.rc;
-    evalh_debug_set_codegen(mode, max_ops);
+    TuneWrite t;
+    t->evalh_codegen = mode & 15;
+    t->evalh_gen_fuse = !(mode & 16);
+    t->evalh_codegen_max_ops = max_ops ? max_ops : Tuning{}.evalh_codegen_max_ops;
     return 0;
 }
 struct RtcStats {
@@ -645,11 +637,11 @@ static std::vector<int> fusion_plan(const Program& P, bool fuse) {
 
 // the program as HIP source.  Operands: constants are literals (I-form limbs), slots are locals, a column operand is a load at the
 // row index of its rotation (one index variable per distinct rotation), challenges and beta / gamma / theta / y come with the launch.
-static bool g_evalh_gen_barriers = true;
+static constexpr bool EVALH_GEN_BARRIERS = true;
 // lookup: the program is a lookup argument's compressed table expression (evaluated with PreviousValue = 0, :466-480) and the kernel ends
 // with that argument's five constraints (lookup_row, evalh_dev.h) instead of storing the program's result.
 static std::string gen_source(const h2hip_graph& g, const Program& P, bool lookup = false) {
-    const bool sched_barriers = g_evalh_gen_barriers;
+    const bool sched_barriers = EVALH_GEN_BARRIERS;
     std::string src;
     src.reserve(64 * P.ops.size() + 4096);
     char buf[512];
@@ -721,7 +713,7 @@ static std::string gen_source(const h2hip_graph& g, const Program& P, bool looku
         src += ";\n";
     }
     const size_t n_ops = P.ops.size();
-    const std::vector<int> fused_into = fusion_plan(P, g_evalh_gen_fuse);  // product i is emitted inside op fused_into[i]
+    const std::vector<int> fused_into = fusion_plan(P, tune().evalh_gen_fuse);  // product i is emitted inside op fused_into[i]
     auto product_of = [&](size_t j, const h2hip_value_source& v) -> const DevOp* {  // the product fused into op j that v names
         for (size_t i = 0; i < j; i++)
             if (fused_into[i] == (int)j && v.kind == H2HIP_VS_INTERMEDIATE && P.ops[i].dst == v.a) return &P.ops[i];
@@ -882,6 +874,7 @@ extern "C" int h2hip_debug_evalh_codegen_source(const h2hip_graph* g, char* buf,
         return 1;
     }
     Program P;
+    TuneRead r;
     if (compile_any(g, &P)) return 1;
     const std::string src = gen_source(*g, P, (compile & 2) != 0);  // bit 1: the graph as a lookup's table expression (evalh_lookup_gen)
     compile &= 1;
@@ -932,13 +925,13 @@ static uint64_t program_fingerprint(const h2hip_graph& g, const Program& P, bool
     if (!P.ops.empty()) h = fnv1a64_raw((const char*)P.ops.data(), P.ops.size() * sizeof(DevOp), h);
     if (g.n_constants) h = fnv1a64_raw((const char*)g.constants, (size_t)g.n_constants * 32, h);
     if (g.n_rotations) h = fnv1a64_raw((const char*)g.rotations, (size_t)g.n_rotations * sizeof(int32_t), h);
-    const uint32_t tail[6] = {P.result.kind, P.result.a, P.result.b, P.n_slots, lookup ? 1u : 0u, (g_evalh_gen_fuse ? 1u : 0u) | (g_evalh_gen_barriers ? 2u : 0u)};
+    const uint32_t tail[6] = {P.result.kind, P.result.a, P.result.b, P.n_slots, lookup ? 1u : 0u, (tune().evalh_gen_fuse ? 1u : 0u) | (EVALH_GEN_BARRIERS ? 2u : 0u)};
     return fnv1a64_raw((const char*)tail, sizeof(tail), h);
 }
 static std::map<uint64_t, uint64_t> g_rtc_key_of;  // program fingerprint -> source key (under g_rtc_mu)
 
 static hipFunction_t gates_kernel_for(Ctx* c, const h2hip_graph& g, const Program& P, bool lookup = false) {
-    if (g_evalh_codegen <= 0 || (P.ops.empty() && !lookup) || P.ops.size() > g_evalh_codegen_max_ops || P.n_slots > EVALH_CODEGEN_MAX_SLOTS) return nullptr;
+    if (tune().evalh_codegen <= 0 || (P.ops.empty() && !lookup) || P.ops.size() > tune().evalh_codegen_max_ops || P.n_slots > EVALH_CODEGEN_MAX_SLOTS) return nullptr;
     const uint64_t fp = program_fingerprint(g, P, lookup);
     {
         std::lock_guard<std::mutex> lk(g_rtc_mu);
@@ -963,7 +956,7 @@ static hipFunction_t gates_kernel_for(Ctx* c, const h2hip_graph& g, const Progra
         auto it = g_rtc.find(key);
         if (it != g_rtc.end()) {
             e = it->second;
-            if (g_evalh_codegen >= 2 && e->th.joinable()) e->th.join();  // tests: wait for a compile another call started
+            if (tune().evalh_codegen >= 2 && e->th.joinable()) e->th.join();  // tests: wait for a compile another call started
         } else {
             if (!hiprtc_load()) return nullptr;
             try {
@@ -973,7 +966,7 @@ static hipFunction_t gates_kernel_for(Ctx* c, const h2hip_graph& g, const Progra
                 return nullptr;
             }
             mine = true;
-            if (g_evalh_codegen == 1) {
+            if (tune().evalh_codegen == 1) {
                 try {
                     e->th = std::thread(rtc_compile, e, src, key);
                     mine = false;
@@ -1019,11 +1012,9 @@ struct SlotPlan {
     size_t ws_bytes; // global workspace (tier 0)
 };
 
-static uint32_t g_evalh_max_local_slots = 256;  // debug knob (tests force the global-workspace form with it)
-
 static int slot_plan(uint32_t n_slots, size_t size, SlotPlan* out) {
     const uint32_t all = (uint32_t)((size + 255) / 256 * 256);
-    if (n_slots <= g_evalh_max_local_slots && n_slots <= 256) {
+    if (n_slots <= tune().evalh_max_local_slots && n_slots <= 256) {
         out->tier = n_slots <= 4 ? 4 : n_slots <= 8 ? 8 : n_slots <= 16 ? 16 : n_slots <= 64 ? 64 : 256;
         out->lanes = all;
         out->ws_bytes = 0;
@@ -1043,10 +1034,9 @@ static int slot_plan(uint32_t n_slots, size_t size, SlotPlan* out) {
 }
 
 // test hook: programs needing more slots than v use the global-workspace form of the evaluate_h kernels (default 256)
-extern "C" int h2hip_debug_set_evalh_max_local_slots(uint32_t v) { g_evalh_max_local_slots = v; return 0; }
-static size_t g_evalh_lookup_group_bytes = (size_t)2 << 30;  // HBM one group of lookup cosets may take (tests shrink it to force several groups)
-// test hook: HBM one group of lookup cosets may take in evaluate_h (0 = default, 2 GB); a small value forces one lookup per group
-extern "C" int h2hip_debug_set_evalh_lookup_group_bytes(uint64_t v) { g_evalh_lookup_group_bytes = v ? (size_t)v : (size_t)2 << 30; return 0; }
+extern "C" int h2hip_debug_set_evalh_max_local_slots(uint32_t v) { TuneWrite()->evalh_max_local_slots = v; return 0; }
+// test hook: HBM one group of lookup cosets may take in evaluate_h (0 restores the default); a small value forces one lookup per group
+extern "C" int h2hip_debug_set_evalh_lookup_group_bytes(uint64_t v) { TuneWrite()->evalh_lookup_group_bytes = v ? (size_t)v : Tuning{}.evalh_lookup_group_bytes; return 0; }
 
 // field multiplications one row of the compiled program performs (products, squares, Horner steps, inserted reductions, and the
 // exact reduction of the stored value): the numerator of the gates kernel's valu_roofline in bench.py
@@ -1362,10 +1352,10 @@ static int constraint_pass(Ctx* c, const CallPlan& cp, const std::vector<ProgDev
     return 0;
 }
 
-// lookups whose three cosets are resident at once: as many as g_evalh_lookup_group_bytes hold, at least one
+// lookups whose three cosets are resident at once: as many as Tuning::evalh_lookup_group_bytes hold, at least one
 static size_t lookup_group(size_t n_lookups, size_t col_bytes) {
     if (!n_lookups) return 0;
-    const size_t fit = g_evalh_lookup_group_bytes / (3 * col_bytes);
+    const size_t fit = tune().evalh_lookup_group_bytes / (3 * col_bytes);
     return n_lookups <= fit ? n_lookups : fit ? fit : 1;
 }
 

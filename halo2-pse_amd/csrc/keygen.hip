@@ -16,7 +16,6 @@
 //   kg_scatter_kernel  out[row] *= inverse, over the sparse Rational cells of every column (the inversion is product.hip's);
 //   kg_units_kernel / kg_active_kernel  the three unit-like columns and 1 - (l_last + l_blind) around their transforms.
 #include <string.h>
-#include <atomic>
 #include <vector>
 #include "engine.h"
 #include "fe_io.h"
@@ -25,8 +24,6 @@ namespace h2 {
 
 #define KG_THREADS 256
 #define KG_MAX_COLUMNS 65535  // one grid row per column
-
-static std::atomic<size_t> g_kg_group_bytes{(size_t)1 << 30};  // HBM one group of columns of a host-pointer call may take (two groups are alive)
 
 struct KgDomain {
     uint32_t k, ek;
@@ -328,7 +325,7 @@ int h2hip_permutation_keygen_bn254(uint32_t k, const uint64_t omega[4], const ui
     const bool need_poly = polys || cosets;
     const size_t map_b = n * 8, col_b = n * sizeof(Fe), ext_b = len * sizeof(Fe);
     const size_t per_col = map_b + col_b + (need_poly ? col_b : 0) + (cosets ? ext_b : 0);
-    size_t gc = g_kg_group_bytes.load() / per_col;
+    size_t gc = tune().keygen_group_bytes / per_col;
     if (gc < 1) gc = 1;
     if (gc > n_columns) gc = n_columns;
     const size_t groups = (n_columns + gc - 1) / gc;
@@ -493,7 +490,7 @@ int h2hip_batch_invert_assigned_bn254(uint32_t k, const uint64_t* const* numerat
     Ctx* c = en.c;
     hipStream_t s = c->stream;
     // the sparse part whole (one inversion over all columns, poly.rs:192-200), the columns that have Rational cells in groups
-    size_t gc = g_kg_group_bytes.load() / col_b;
+    size_t gc = tune().keygen_group_bytes / col_b;
     if (gc < 1) gc = 1;
     if (gc > rat_cols.size()) gc = rat_cols.size();
     Carve io;
@@ -582,7 +579,7 @@ int h2hip_key_lagrange_columns_bn254(uint32_t k, const uint64_t omega_inv[4], co
 }
 
 int h2hip_debug_set_keygen_group(uint64_t group_bytes) {
-    g_kg_group_bytes = group_bytes ? (size_t)group_bytes : (size_t)1 << 30;
+    TuneWrite()->keygen_group_bytes = group_bytes ? (size_t)group_bytes : Tuning{}.keygen_group_bytes;
     return 0;
 }
 

@@ -37,7 +37,6 @@ namespace h2 {
 #define LK_E (LK_TILE / LK_THREADS)   // consecutive keys / rows per thread
 #define LK_MAX_COUNT 32767            // lookups per call: 2 count sorted columns in grid.y
 
-static uint32_t g_lk_block = 0;            // h2hip_debug_set_lookup_sort: forced in-LDS sort block (0 = LK_TILE)
 static uint32_t g_lk_last[2] = {0, 0};     // block keys and merge passes of the last sort (a permute or a lookup-check call)
 
 // merge path: how many of the first d outputs of merge(A[0 .. na), B[0 .. nb)) come from A (on ties A first)
@@ -278,7 +277,7 @@ __global__ __launch_bounds__(LK_THREADS) void lk_final_kernel(const LkPerm* P, u
 // src[q] -> canonical keys, rows u .. n - 1 as all-ones keys at the end.  src, k0 and k1 are device tables of `cols` device pointers
 // (k0[q], k1[q]: two key buffers of 2^k elements per column); the sorted keys end in k1[q] when lookup_sort_passes(k) is odd, else in k0[q].
 static uint32_t lk_sort_block(uint32_t ts) {
-    const uint32_t block = g_lk_block ? g_lk_block : LK_TILE;
+    const uint32_t block = tune().lookup_sort_block ? tune().lookup_sort_block : LK_TILE;
     return block > ts ? ts : block;
 }
 uint32_t lookup_sort_passes(uint32_t k) {
@@ -550,7 +549,7 @@ int h2hip_debug_set_lookup_sort(uint32_t lds_keys) {
         set_error("debug_set_lookup_sort: the in-LDS sort block must be a power of two in [4, %d], or 0", LK_TILE);
         return H2HIP_EINVAL;
     }
-    g_lk_block = lds_keys;
+    TuneWrite()->lookup_sort_block = lds_keys;
     return 0;
 }
 

@@ -347,16 +347,15 @@ __device__ __forceinline__ uint32_t size_class(uint32_t cnt, uint32_t bin_shift)
 // A4: one workgroup per coarse bin -- counting sort of its entries on the low L bits of the bucket id, through LDS, one
 // tile of MSM_STAGE entries at a time (16 per lane, held in registers between the tile's count and its placement);
 // every bucket's share of a tile leaves as one contiguous run.  A bin of at most one tile is read from HBM once, a
-// larger one twice (count, place).  Also writes, for the bin's 2^L buckets: start / counts (empty buckets included) and
-// the accumulate order -- the bin's buckets by descending size class, so that the 64 lanes of an accumulate wave (which
-// takes 64 consecutive entries of perm) get buckets of equal length.
+// larger one twice (count, place).  Also writes, for the bin's 2^L buckets: start / counts (empty buckets included), and
+// adds their sizes to class_hist, the 256 class counts from which msm_bucket_scatter_kernel makes the accumulate order.
 // SPLIT: the records come as two arrays (entries, low key bits): a bin of several tiles is read twice -- once for its buckets'
 // sizes, once to place -- and the first read then takes 2 instead of 8 bytes per entry (at 2^24 pairs: 0.4 instead of 1.6 GB).
 template <bool SPLIT>
 __global__ void __launch_bounds__(1024) msm_l2_kernel(const uint2* __restrict__ tmp, const uint32_t* __restrict__ tmp_e, const uint16_t* __restrict__ tmp_k,
                                                       const uint32_t* __restrict__ coarse_start, uint32_t L,
                                                       uint32_t bin_shift, uint32_t* __restrict__ vals, uint32_t* __restrict__ start,
-                                                      uint32_t* __restrict__ counts, uint32_t* __restrict__ perm, uint32_t* __restrict__ class_hist) {
+                                                      uint32_t* __restrict__ counts, uint32_t* __restrict__ class_hist) {
     constexpr uint32_t NBMAX = 1u << MSM_MAX_L, EPT = MSM_STAGE / 1024;
     __shared__ uint32_t sval[MSM_STAGE];
     __shared__ uint16_t skey[MSM_STAGE];
@@ -418,20 +417,7 @@ __global__ void __launch_bounds__(1024) msm_l2_kernel(const uint2* __restrict__ 
         }
     }
     __syncthreads();
-    if (class_hist) {
-        if (t < 256 && cls[t]) atomicAdd(&class_hist[t], cls[t]);
-    } else {
-        // the bin's buckets in descending size-class order: exclusive scan of the 256 class counts (tdelta is free here)
-        uint32_t dummy;
-        const uint32_t c0 = block_scan_base<1024>(cls, 256, 1, ps, &dummy);
-        if (t < 256) tdelta[t] = c0;
-        __syncthreads();
-        for (uint32_t j = 0; j < per; j++) {
-            const uint32_t k = t * per + j;
-            if (k < nb) perm[gb0 + atomicAdd(&tdelta[size_class(tcur[k], bin_shift)], 1u)] = gb0 + k;
-        }
-        __syncthreads();
-    }
+    if (t < 256 && cls[t]) atomicAdd(&class_hist[t], cls[t]);
     for (uint32_t base = cs; base < ce; base += MSM_STAGE) {
         const uint32_t tile_n = ce - base < MSM_STAGE ? ce - base : MSM_STAGE;
         // the next tile's records are fetched while this one is counted, placed and written out
@@ -510,7 +496,6 @@ __global__ void __launch_bounds__(1024) msm_bucket_scatter_kernel(const uint32_t
             }
         }
     }
-    if (!perm) return;  // bucket order local to the sort bins (debug knob): only the list above
     if (t < 256) lh[t] = 0;
     uint32_t total;
     const uint32_t excl = block_scan_base<1024>(hist, 256, 1, ps, &total);  // exclusive scan of the class counts (every block repeats it)
@@ -1153,48 +1138,29 @@ __global__ void __launch_bounds__(256) msm_table_native_kernel(const Affine* __r
     if (i < n) *reinterpret_cast<AffineU*>(out + i * rec) = affineu_from_ext(row[i]);
 }
 
-static uint32_t g_window_override = 0;
-static size_t g_heavy_div = 32768;
-static size_t g_bin_entries = 8192;
-static bool g_split_records = true;
+// ---- the MSM's hooks over its settings (engine.h, Tuning): validate, take the write guard, assign ----
 // tuning hook: level-1 records of runs with multi-tile bins as two arrays (1, default) or as (entry, bucket id) pairs (0)
-extern "C" int h2hip_debug_set_msm_split_records(int on) { g_split_records = on != 0; return 0; }
-static uint64_t g_rowcol_lanes = 65536;
-static bool g_rowcol_asm = true, g_rowcol_qtree = true;  // first pass: chains on the explicit-mad multiplier, then the quad tree
-// tuning hook: lane budget of the first row/column pass (default 65536 = one wave per SIMD) and its multiplier flavour
-extern "C" int h2hip_debug_set_msm_rowcol(uint64_t lanes, int use_asm) {
-    g_rowcol_lanes = lanes ? lanes : 65536;
-    g_rowcol_asm = (uint32_t)use_asm & 1;
-    g_rowcol_qtree = (uint32_t)use_asm & 2;
-    return 0;
-}
-static bool g_split_buckets = true;
+extern "C" int h2hip_debug_set_msm_split_records(int on) { TuneWrite()->msm_split_records = on != 0; return 0; }
+// tuning hook: lane budget of the first row/column pass (0 restores the default)
+extern "C" int h2hip_debug_set_msm_rowcol(uint64_t lanes) { TuneWrite()->msm_rowcol_lanes = lanes ? lanes : Tuning{}.msm_rowcol_lanes; return 0; }
 // tuning hook: several lanes per bucket in runs with few buckets (1, default) or always one (0)
-extern "C" int h2hip_debug_set_msm_split_buckets(int on) { g_split_buckets = on != 0; return 0; }
-static bool g_quad_tail = true;
+extern "C" int h2hip_debug_set_msm_split_buckets(int on) { TuneWrite()->msm_split_buckets = on != 0; return 0; }
 // tuning hook: the reduction tail with one quad of lanes per group operation (1, default) or one lane (0)
-extern "C" int h2hip_debug_set_msm_quad_tail(int on) { g_quad_tail = on != 0; return 0; }
-static bool g_global_order = true;  // false: bucket order local to a sort bin (measured 1.3-1.8x slower accumulation)
-// tuning hook: 1 = order the buckets by size inside each sort bin only (no global pass); 0 = global order (default)
-extern "C" int h2hip_debug_set_msm_bucket_order(int local) { g_global_order = local == 0; return 0; }
-// tuning hook: target number of entries per coarse bin of the MSM's two-level sort (default 8192; 0 restores it)
-extern "C" int h2hip_debug_set_msm_bin_entries(size_t d) { g_bin_entries = d ? d : 8192; return 0; }
-// tuning hook: buckets above (entries of the MSM) / d go to the chunked path (default 32768; 0 restores it)
-extern "C" int h2hip_debug_set_msm_heavy_div(size_t d) { g_heavy_div = d ? d : 32768; return 0; }
-static size_t g_max_chunk = (size_t)1 << 26;
-// test hook: split inputs above m pairs into consecutive chunks (default 2^26, the 31-bit pair-index limit)
-extern "C" int h2hip_debug_set_msm_max_chunk(size_t m) { g_max_chunk = m ? m : ((size_t)1 << 26); return 0; }
-static uint32_t g_reserved_cus = 0;  // measured on MI355X: every partition (16..96 CUs) was slower than none
-// undocumented tuning knob (not in the public header): CUs reserved for the sort / reduce stages of a batch
-extern "C" int h2hip_debug_set_reserved_cus(uint32_t k) { g_reserved_cus = k; return 0; }
-uint32_t msm_get_reserved_cus() { return g_reserved_cus; }
-void msm_set_window(uint32_t c) { g_window_override = c; }
+extern "C" int h2hip_debug_set_msm_quad_tail(int on) { TuneWrite()->msm_quad_tail = on != 0; return 0; }
+// tuning hook: runs with at most 4 bucket sets finish the reduction on the host from bit-plane sums (1, default) or keep the GPU tail (0)
+extern "C" int h2hip_debug_set_msm_plane_tail(int on) { TuneWrite()->msm_plane_tail = on != 0; return 0; }
+// tuning hook: target number of entries per coarse bin of the MSM's two-level sort (0 restores the default)
+extern "C" int h2hip_debug_set_msm_bin_entries(size_t d) { TuneWrite()->msm_bin_entries = d ? d : Tuning{}.msm_bin_entries; return 0; }
+// tuning hook: buckets above (entries of the MSM) / d go to the chunked path (0 restores the default)
+extern "C" int h2hip_debug_set_msm_heavy_div(size_t d) { TuneWrite()->msm_heavy_div = d ? d : Tuning{}.msm_heavy_div; return 0; }
+// test hook: split inputs above m pairs into consecutive chunks (0 restores the default, the 31-bit pair-index limit)
+extern "C" int h2hip_debug_set_msm_max_chunk(size_t m) { TuneWrite()->msm_max_chunk = m ? m : Tuning{}.msm_max_chunk; return 0; }
 extern "C" int h2hip_set_msm_window(uint32_t c) {
     if (c != 0 && (c < 2 || c > 24)) {
         set_error("msm window must be 0 (auto) or 2..24");
         return H2HIP_EINVAL;
     }
-    msm_set_window(c);
+    TuneWrite()->msm_window = c;
     return 0;
 }
 
@@ -1206,7 +1172,7 @@ static uint32_t floor_log2(size_t n) {
 
 // window width of the plain form
 static uint32_t plain_window(size_t n, bool fused) {
-    if (g_window_override) return g_window_override;
+    if (tune().msm_window) return tune().msm_window;
     const uint32_t lg = floor_log2(n);
     // enough buckets to fill 256 CUs, few enough that the reduction stays small, and 254 mod c large so
     // that the top window is not a handful of over-full buckets
@@ -1232,7 +1198,7 @@ static uint32_t normalise_window(uint32_t c) {
 }
 
 uint32_t msm_table_window(size_t n) {
-    if (g_window_override) return normalise_window(g_window_override);
+    if (tune().msm_window) return normalise_window(tune().msm_window);
     const uint32_t lg = floor_log2(n);
     // swept on MI355X (tools/msm_bench.py --windows): up to 2^17 points c = 17 (a lone MSM would take c = 20 -- 0.70 instead
     // of 0.78 ms at 2^17 -- but the prover's fused batches pay the 2 * 2^(c-1) additions of the reduction once per MSM:
@@ -1240,7 +1206,10 @@ uint32_t msm_table_window(size_t n) {
     uint32_t c = lg <= 12 ? 13 : lg <= 17 ? 17 : lg <= 21 ? 20 : 22;  // up to 2^12 points the MSM is all reduction tail: few buckets
     return normalise_window(c);
 }
-extern "C" uint32_t h2hip_get_msm_window_fixed_base(size_t n) { return msm_table_window(n); }
+extern "C" uint32_t h2hip_get_msm_window_fixed_base(size_t n) {
+    TuneRead r;
+    return msm_table_window(n);
+}
 
 static MsmPlan make_plan(size_t n, bool fused, const MsmTable* tab, uint32_t force_c = 0) {
     MsmPlan p;
@@ -1257,7 +1226,7 @@ static MsmPlan make_plan(size_t n, bool fused, const MsmTable* tab, uint32_t for
     // A lone lane adds ~6 us per entry, and the kernel cannot finish faster than 2 * n*W / 65536 add-times
     // anyway (64 lanes x 1024 SIMDs): buckets above that go to the chunked path, or one lane's chain
     // (e.g. the few buckets of a narrow top window) sets the kernel's duration.
-    size_t t = (n * p.W) / g_heavy_div;
+    size_t t = (n * p.W) / tune().msm_heavy_div;
     if (t < 32) t = 32;
     const size_t mean = (p.shared ? n * p.W : n) >> p.cb;  // few buckets (narrow windows): the ordinary bucket is not "over-full"
     if (t < 8 * mean) t = 8 * mean;  // the buckets the narrow windows use hold twice the mean
@@ -1266,7 +1235,10 @@ static MsmPlan make_plan(size_t n, bool fused, const MsmTable* tab, uint32_t for
     return p;
 }
 
-extern "C" uint32_t h2hip_get_msm_window(size_t n) { return make_plan(n, false, nullptr).c; }
+extern "C" uint32_t h2hip_get_msm_window(size_t n) {
+    TuneRead r;
+    return make_plan(n, false, nullptr).c;
+}
 
 // host Horner over the set sums of one MSM in the plain form (arithmetic.rs:46-49): acc = sum_w 2^(pos_w) * S_w
 static XYZZ combine_windows(const XYZZ* ws, const MsmPlan& p) {
@@ -1338,7 +1310,7 @@ static int msm_layout(size_t n, MsmLayout* L, uint32_t fuse, const MsmTable* tab
     // level-1 coarse bins: about one level-2 tile (MSM_STAGE entries) each, at most MSM_MAX_C1 of them (so that the
     // runs a level-1 workgroup writes stay long), at most 2^MSM_MAX_L buckets each, never straddling two sets
     uint32_t want = 1;
-    while (want < MSM_MAX_C1 && (size_t)want * g_bin_entries < L->E) want <<= 1;
+    while (want < MSM_MAX_C1 && (size_t)want * tune().msm_bin_entries < L->E) want <<= 1;
     uint32_t Lb = 0;
     while (Lb < p.cb && Lb < MSM_MAX_L && (K64 >> Lb) > want) Lb++;
     while ((K64 >> Lb) > MSM_MAX_C1) {
@@ -1363,7 +1335,7 @@ static int msm_layout(size_t n, MsmLayout* L, uint32_t fuse, const MsmTable* tab
     // least two entries per lane
     L->split_log = 0;
     while (L->split_log < 3 && ((uint64_t)L->K << (L->split_log + 1)) <= (1u << 18) && (mean_bucket >> (L->split_log + 1)) >= 2) L->split_log++;
-    if (!g_split_buckets) L->split_log = 0;
+    if (!tune().msm_split_buckets) L->split_log = 0;
     if (force_split >= 0) L->split_log = (uint32_t)force_split;
     L->max_chunks = L->E / p.chunk + L->E / p.heavy_t + 16;  // sum of ceil(cnt/chunk) over buckets with cnt > heavy_t
     L->max_heavy = L->E / p.heavy_t + 16;
@@ -1465,7 +1437,7 @@ static int msm_stage_a(Ctx* c, const MsmLayout& L, char* base, const Fe* const* 
                        (const uint32_t*)bin_total, cstart, (uint32_t*)(base + L.o_toff));
     H2_CHECK(hipGetLastError());
     // bins of several level-2 tiles: split records (see msm_l2_kernel)
-    const bool split = g_split_records && L.E / L.C1 > MSM_STAGE;
+    const bool split = tune().msm_split_records && L.E / L.C1 > MSM_STAGE;
     a.tmp_e = (uint32_t*)(base + L.o_tmp);
     a.tmp_k = (uint16_t*)(base + L.o_tmp + L.E * 4);
     if (split)
@@ -1476,14 +1448,14 @@ static int msm_stage_a(Ctx* c, const MsmLayout& L, char* base, const Fe* const* 
     uint32_t* hist = (uint32_t*)(base + L.o_hist);
     if (split)
         hipLaunchKernelGGL(msm_l2_kernel<true>, dim3(L.C1), dim3(1024), 0, s, (const uint2*)nullptr, (const uint32_t*)a.tmp_e, (const uint16_t*)a.tmp_k, cstart,
-                           L.L, L.bin_shift, vals, start, counts, perm, g_global_order ? hist : (uint32_t*)nullptr);
+                           L.L, L.bin_shift, vals, start, counts, hist);
     else
         hipLaunchKernelGGL(msm_l2_kernel<false>, dim3(L.C1), dim3(1024), 0, s, (const uint2*)(base + L.o_tmp), (const uint32_t*)nullptr,
-                           (const uint16_t*)nullptr, cstart, L.L, L.bin_shift, vals, start, counts, perm, g_global_order ? hist : (uint32_t*)nullptr);
+                           (const uint16_t*)nullptr, cstart, L.L, L.bin_shift, vals, start, counts, hist);
     H2_CHECK(hipGetLastError());
-    // size-ordered bucket permutation (skipped under the local-order debug knob) and the list of over-full buckets with their chunks
+    // size-ordered bucket permutation and the list of over-full buckets with their chunks
     hipLaunchKernelGGL(msm_bucket_scatter_kernel, dim3((L.K + 1024 * MSM_BS_PER - 1) / (1024 * MSM_BS_PER)), dim3(1024), 0, s, (const uint32_t*)counts,
-                       (const uint32_t*)start, L.K, L.bin_shift, p.heavy_t, p.chunk, hist, g_global_order ? perm : (uint32_t*)nullptr,
+                       (const uint32_t*)start, L.K, L.bin_shift, p.heavy_t, p.chunk, hist, perm,
                        (uint32_t*)(base + L.o_hcnt), (HeavyBucket*)(base + L.o_hb), (HeavyChunk*)(base + L.o_hc));
     H2_CHECK(hipGetLastError());
     c->timer_end(t1, s);
@@ -1540,7 +1512,8 @@ static void rowcol_jobs(RowColArgs* ra, const XYZZu* in, XYZZu* out_rows, XYZZu*
     const uint64_t elems = (uint64_t)n_arr << (log_rows + log_cols);
     // one wave per SIMD while that keeps the chains at 16 terms (a second wave only shares the SIMD: measured 0.273 against 0.276 ms
     // for a 2^20-pair MSM), two once they would grow longer (2^21 buckets: 0.66 against 0.70 ms)
-    const uint64_t budget = (2 * elems) >> 4 > g_rowcol_lanes ? 2 * g_rowcol_lanes : g_rowcol_lanes;
+    const uint64_t lanes = tune().msm_rowcol_lanes;
+    const uint64_t budget = (2 * elems) >> 4 > lanes ? 2 * lanes : lanes;
     uint32_t t_log = 1;
     while (!quad && (2 * elems) >> t_log > budget) t_log++;
     for (uint32_t kind = 0; kind < 2; kind++) {
@@ -1563,18 +1536,10 @@ static void rowcol_jobs(RowColArgs* ra, const XYZZu* in, XYZZu* out_rows, XYZZu*
     }
 }
 
-static bool g_plane_tail = true;
-// tuning hook: runs with at most 4 bucket sets finish the reduction on the host from bit-plane sums (1, default) or keep the GPU tail (0)
-extern "C" int h2hip_debug_set_msm_plane_tail(int on) {
-    Entry en;
-    if (en.rc) return en.rc;
-    g_plane_tail = on != 0;
-    return 0;
-}
 // whether a run's tail is finished on the host from bit-plane sums (msm_planes_kernel): few sets, one row / column level at least,
 // at most 16 workgroups (2^11 points) per plane, and the sums not wanted in HBM for the RCCL gather
 static bool msm_plane_tail(const Ctx* c, const MsmLayout& L) {
-    return g_plane_tail && g_quad_tail && L.levels >= 1 && L.n_sets <= MSM_PLANE_SETS_MAX && L.rb <= 11 && L.s <= 11 && L.rb >= 1 && L.s >= 1 &&
+    return tune().msm_plane_tail && tune().msm_quad_tail && L.levels >= 1 && L.n_sets <= MSM_PLANE_SETS_MAX && L.rb <= 11 && L.s <= 11 && L.rb >= 1 && L.s >= 1 &&
            L.s + 1 + L.rb <= MSM_PLANES_MAX && !c->gather_want;
 }
 static inline uint32_t msm_planes_per_set(const MsmLayout& L) { return L.rb + L.s + 1; }
@@ -1608,7 +1573,7 @@ static int msm_stage_c(Ctx* c, const MsmLayout& L, char* base, XYZZ* h_sums, hip
     const uint32_t ns = L.n_sets, cb = L.p.cb;
     // few sets: the second row/column pass and the final scaling are latency chains on a handful of waves -- one quad of
     // lanes per group operation (ecq.h).  Many sets (fused batches of the plain form) fill the chip: one lane each.
-    const bool quad = g_quad_tail && ns <= 64;
+    const bool quad = tune().msm_quad_tail && ns <= 64;
     int t4 = c->timer_begin("msm_reduce", s);
     FinalArgs fa;
     memset(&fa, 0, sizeof(fa));
@@ -1628,12 +1593,7 @@ static int msm_stage_c(Ctx* c, const MsmLayout& L, char* base, XYZZ* h_sums, hip
         memset(&ra, 0, sizeof(ra));
         uint32_t nblk = 0;
         rowcol_jobs(&ra, buckets, RA, CA, ns, L.rb, L.s, &nblk);
-        if (g_rowcol_qtree)
-            hipLaunchKernelGGL(msm_rowcol_qtree_kernel<FqUA>, dim3(nblk), dim3(256), 0, s, ra);
-        else if (g_rowcol_asm)
-            hipLaunchKernelGGL(msm_rowcol_kernel<FqUA>, dim3(nblk), dim3(256), 0, s, ra);
-        else
-            hipLaunchKernelGGL(msm_rowcol_kernel<FqU>, dim3(nblk), dim3(256), 0, s, ra);
+        hipLaunchKernelGGL(msm_rowcol_qtree_kernel<FqUA>, dim3(nblk), dim3(256), 0, s, ra);
         H2_CHECK(hipGetLastError());
         if (h_planes && msm_plane_tail(c, L)) {
             PlaneArgs pa;
@@ -1760,7 +1720,7 @@ static int msm_batch_chunk(Ctx* c, const Fe* const* d_scalars, bool scalars_on_h
     } else {
         // Three internal streams.  A full-size accumulate holds every wave slot for ~0.65 ms at a time, so the other
         // stages only partly overlap with it (trace: profiles/): measured gain 17 % at 2^20, 37 % at 2^17.  Reserving
-        // CUs for stages A/C with CU-masked streams (h2hip_debug_set_reserved_cus) was slower for every split tried.
+        // CUs for stages A/C with CU-masked streams was slower for every split tried ("Tried ..., measured, not kept").
         rc = c->ensure_aux(3 * count + 2);
         if (rc) return rc;
         hipStream_t a1 = c->aux1, a2 = c->aux2, sb = c->aux_b;
@@ -1847,20 +1807,16 @@ static int msm_fused_chunk(Ctx* c, const Fe* const* d_scalars, bool scalars_on_h
 // against 1.87 / 7.35 / 27.8 ms with the whole upload first and 1.27 / 4.60 / 17.0 ms device-resident.  With the bases crossing
 // too (unpinned, 96 B per pair) the run is upload-bound: more and nearly equal chunks (6 at 3 x 0.4), 2.55 / 8.3 / 31.3 ms
 // against 3.44 / 13.2 / 51.2 ms.
-static uint32_t g_stream_chunks = 3;
-static bool g_stream_chunks_default = true;  // below 2^20 pairs the default is two chunks; an explicit setting is taken as given
-static double g_stream_ratio = 0.6;
-static size_t g_stream_min_n = (size_t)1 << 19;  // 2^19 pairs: 1.13 -> 1.04 ms (two chunks); 2^18: 0.72 -> 0.80 ms, not worth it
-void msm_set_stream(uint32_t chunks, double ratio, size_t min_n) {
-    g_stream_chunks = chunks ? chunks : 3;
-    g_stream_chunks_default = chunks == 0;
-    g_stream_ratio = ratio > 0 ? ratio : 0.6;
-    g_stream_min_n = min_n ? min_n : ((size_t)1 << 19);
-}
+// the chunks of a streamed run of n pairs (or of a batch's columns: n = SIZE_MAX): an explicit setting is taken as given, the default is
+// three, and two below 2^20 pairs
+static uint32_t stream_chunks(size_t n) { return tune().msm_stream_chunks ? tune().msm_stream_chunks : n < ((size_t)1 << 20) ? 2 : 3; }
 // test / tuning hook: a host-resident MSM of at least min_n pairs streams in `chunks` pieces whose sizes grow by 1 / ratio
 // (ratio_permille / 1000 = upload time over compute time per pair); chunks = 1 turns streaming off; zeros restore the defaults
 extern "C" int h2hip_debug_set_msm_stream(uint32_t chunks, uint32_t ratio_permille, size_t min_n) {
-    msm_set_stream(chunks, ratio_permille / 1000.0, min_n);
+    TuneWrite t;
+    t->msm_stream_chunks = chunks;
+    t->msm_stream_ratio = ratio_permille ? ratio_permille / 1000.0 : Tuning{}.msm_stream_ratio;
+    t->msm_stream_min_n = min_n ? min_n : Tuning{}.msm_stream_min_n;
     return 0;
 }
 
@@ -1906,9 +1862,9 @@ static void stream_ladder(size_t units, uint32_t K, double r, size_t quantum, st
 extern "C" size_t h2hip_debug_msm_stream_ladder(size_t n, uint32_t chunks, uint32_t ratio_permille, int with_bases, size_t* sizes, size_t cap) {
     if (!sizes && cap) return 0;
     std::vector<size_t> sz;
-    const uint32_t k0 = chunks ? chunks : g_stream_chunks;
-    const double r = ratio_permille ? ratio_permille / 1000.0 : g_stream_ratio;
-    const uint32_t kk = !chunks && g_stream_chunks_default && n < ((size_t)1 << 20) ? 2 : k0;
+    TuneRead rd;
+    const double r = ratio_permille ? ratio_permille / 1000.0 : tune().msm_stream_ratio;
+    const uint32_t kk = chunks ? chunks : stream_chunks(n);
     stream_ladder(n, with_bases ? 2 * kk : kk, with_bases ? 2.0 * r : r, 4096, &sz);
     for (size_t i = 0; i < sz.size() && i < cap; i++) sizes[i] = sz[i];
     return sz.size();
@@ -1917,8 +1873,9 @@ extern "C" size_t h2hip_debug_msm_stream_ladder(size_t n, uint32_t chunks, uint3
 static int msm_stream_host(Ctx* c, const Fe* h_scalars, const Affine* h_bases, const Affine* d_points, const MsmTable* tab, size_t n, XYZZ* h_out,
                            hipStream_t s) {
     std::vector<size_t> sz;
-    const uint32_t kk = g_stream_chunks_default && n < ((size_t)1 << 20) ? 2 : g_stream_chunks;
-    stream_ladder(n, h_bases ? 2 * kk : kk, h_bases ? 2.0 * g_stream_ratio : g_stream_ratio, 4096, &sz);
+    const uint32_t kk = stream_chunks(n);
+    const double r = tune().msm_stream_ratio;
+    stream_ladder(n, h_bases ? 2 * kk : kk, h_bases ? 2.0 * r : r, 4096, &sz);
     const size_t K = sz.size();
     MsmLayout Lt;
     int rc = msm_layout(n, &Lt, 1, tab);
@@ -1996,7 +1953,7 @@ static int msm_stream_host(Ctx* c, const Fe* h_scalars, const Affine* h_bases, c
 static int msm_fused_groups_host(Ctx* c, const Fe* const* h_scalars, const Affine* d_points, const MsmTable* tab, size_t n, size_t count,
                                  size_t fuse_max, XYZZ* h_out, hipStream_t s) {
     std::vector<size_t> ladder, groups;
-    stream_ladder(count, g_stream_chunks, g_stream_ratio * 0.85, 1, &ladder);  // 16 columns: 2 + 5 + 9
+    stream_ladder(count, stream_chunks(SIZE_MAX), tune().msm_stream_ratio * 0.85, 1, &ladder);  // 16 columns: 2 + 5 + 9
     for (size_t g : ladder)
         for (size_t o = 0; o < g; o += fuse_max) groups.push_back(g - o < fuse_max ? g - o : fuse_max);
     const size_t G = groups.size();
@@ -2069,17 +2026,15 @@ static int msm_fused_groups_host(Ctx* c, const Fe* const* h_scalars, const Affin
     return guard.release();
 }
 
-// measured (tools/fuse_big.py, 8 MSMs per batch, per MSM): 2^19 pairs fused 0.66 ms / pipelined 0.69 ms, 2^20 pairs fused 1.24 / pipelined 1.16
-static size_t g_fuse_entries = (size_t)1 << 26, g_fuse_max_n = (size_t)1 << 19;
-// tuning hook: a fused run holds at most `entries` entries (default 2^26) and fusing applies up to `max_n` pairs per MSM (default 2^18); 0 = default
+// tuning hook: a fused run holds at most `entries` entries and fusing applies up to `max_n` pairs per MSM; 0 restores a default
 extern "C" int h2hip_debug_set_msm_fuse_limits(size_t entries, size_t max_n) {
-    g_fuse_entries = entries ? entries : ((size_t)1 << 26);
-    g_fuse_max_n = max_n ? max_n : ((size_t)1 << 19);
+    TuneWrite t;
+    t->msm_fuse_entries = entries ? entries : Tuning{}.msm_fuse_entries;
+    t->msm_fuse_max_n = max_n ? max_n : Tuning{}.msm_fuse_max_n;
     return 0;
 }
-static bool g_fuse_small = true;
 // test / tuning hook: batches of small MSMs run fused (default) or pipelined over streams
-extern "C" int h2hip_debug_set_msm_fuse_small(int on) { g_fuse_small = on != 0; return 0; }
+extern "C" int h2hip_debug_set_msm_fuse_small(int on) { TuneWrite()->msm_fuse_small = on != 0; return 0; }
 
 // count MSMs over the same bases; results (XYZZ) to host memory.  tab != nullptr: the fixed-base form over tab's table
 // (d_bases is then unused).  scalars_on_host: scalars[j] are host pointers.  h_bases != nullptr: the bases are the
@@ -2094,7 +2049,7 @@ int msm_batch_device(Ctx* c, const Fe* const* d_scalars, bool scalars_on_host, c
     }
     if (tab) h_bases = nullptr;
     // the entry index lives in 31 bits: split very large inputs
-    const size_t max_chunk = g_max_chunk;
+    const size_t max_chunk = tune().msm_max_chunk;
     std::vector<const Fe*> ptrs(count);
     std::vector<XYZZ> part(count);
     if (n > max_chunk) c->gather_off = SIZE_MAX / 2;  // several runs per MSM: their sums are added on the host
@@ -2110,8 +2065,8 @@ int msm_batch_device(Ctx* c, const Fe* const* d_scalars, bool scalars_on_host, c
             tsub = &sub;
             points = (const Affine*)sub.table;  // (opaque when the records are native: msm_stage_b takes the record size from the table)
         }
-        const bool stream = scalars_on_host && g_stream_chunks > 1 && copier_ready(c, false);
-        if (stream && count == 1 && m >= g_stream_min_n) {  // a lone host-resident MSM: chunks stream in under the work
+        const bool stream = scalars_on_host && tune().msm_stream_chunks != 1 && copier_ready(c, false);
+        if (stream && count == 1 && m >= tune().msm_stream_min_n) {  // a lone host-resident MSM: chunks stream in under the work
             int rc = msm_stream_host(c, ptrs[0], h_bases ? h_bases + o : nullptr, points, tsub, m, part.data(), s);
             if (rc) return rc;
             xyzz_add(h_out[0], part[0]);
@@ -2129,13 +2084,13 @@ int msm_batch_device(Ctx* c, const Fe* const* d_scalars, bool scalars_on_host, c
         const MsmPlan fp = make_plan(m, true, tsub);
         const size_t per_msm = m * fp.W;
         const size_t sets = fp.shared ? 1 : fp.W;
-        size_t fuse_max = per_msm ? g_fuse_entries / per_msm : 0;
+        size_t fuse_max = per_msm ? tune().msm_fuse_entries / per_msm : 0;
         const size_t by_buckets = (((size_t)MSM_MAX_C1 << MSM_MAX_L) >> fp.cb) / sets, by_sets = MSM_MAX_C1 / sets;
         if (fuse_max > by_buckets) fuse_max = by_buckets;
         if (fuse_max > by_sets) fuse_max = by_sets;
-        if (g_fuse_small && count > 1 && m <= g_fuse_max_n && fuse_max >= 2) {
+        if (tune().msm_fuse_small && count > 1 && m <= tune().msm_fuse_max_n && fuse_max >= 2) {
             // (up to seven host columns the whole upload first is faster than groups: 6 x 2^17 1.64 against 1.72 ms, 10: 2.59 / 2.23, 16: 4.01 / 3.23 -- tools/fused_host_sweep.py)
-            if (stream && count * m >= g_stream_min_n && (count >= 8 || !g_stream_chunks_default)) {
+            if (stream && count * m >= tune().msm_stream_min_n && (count >= 8 || tune().msm_stream_chunks)) {
                 int rc = msm_fused_groups_host(c, ptrs.data(), points, tsub, m, count, fuse_max, part.data(), s);
                 if (rc) return rc;
             } else {

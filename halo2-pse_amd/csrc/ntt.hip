@@ -469,25 +469,31 @@ void ntt_twiddles_free(Ctx* c) {
     c->tw_full_bytes = 0;
 }
 
-static uint64_t g_ntt_full_budget = (uint64_t)4 << 30;  // HALO2_HIP_NTT_TWIDDLE_MB: HBM the full inter-pass tables may take per device (of 288 GB)
-void ntt_set_full_twiddle_budget(uint64_t bytes) { g_ntt_full_budget = bytes; }
+// ---- the NTT's hooks over its settings (engine.h, Tuning) ----
 // tuning hook: HBM (bytes per device) the two-pass plan's full inter-pass twiddle tables may take; 0 = two-level table only
-extern "C" int h2hip_debug_set_ntt_twiddle_budget(uint64_t bytes) { g_ntt_full_budget = bytes; return 0; }
-static size_t g_ntt_batch_bytes = (size_t)2 << 30;  // columns + workspace one batched launch may span (ntt_device_batch)
-// tuning hook: bytes of columns + workspace one launch of a batched transform spans (0 = default)
-extern "C" int h2hip_debug_set_ntt_batch_bytes(uint64_t bytes) { g_ntt_batch_bytes = bytes ? (size_t)bytes : (size_t)2 << 30; return 0; }
-// Strided passes of the three-pass plan read their inter-pass twiddles from a table of up to 2^this entries (36 B each: 0.3 / 0.6 GB per domain
-// and direction at 2^23 / 2^24 for the first pass's, 2.4 MB for the second's) while the budget lasts: one multiplication per point fewer than
-// combining the two-level table (2^23 -5 %, 2^24 -2.5 %; at 2^25 and beyond the pass has no memory bandwidth to spare for it and nothing is gained).
-static uint32_t g_ntt_full_max_log_m = 24;
-// tuning hook: the largest strided pass (log2 of its M) that reads its inter-pass twiddles from a table (0 = default 24)
-extern "C" int h2hip_debug_set_ntt_full_max_log_m(uint32_t v) { g_ntt_full_max_log_m = v ? v : 24; return 0; }
-static bool g_ntt_fold_tables = true;  // the inverse's 1/n rides in a scaled copy of the first pass's table (A/B: h2hip_debug_set_ntt_fold_tables)
+extern "C" int h2hip_debug_set_ntt_twiddle_budget(uint64_t bytes) { TuneWrite()->ntt_full_budget = bytes; return 0; }
+// tuning hook: bytes of columns + workspace one launch of a batched transform spans (0 restores the default)
+extern "C" int h2hip_debug_set_ntt_batch_bytes(uint64_t bytes) { TuneWrite()->ntt_batch_bytes = bytes ? (size_t)bytes : Tuning{}.ntt_batch_bytes; return 0; }
+// tuning hook: the largest strided pass (log2 of its M) that reads its inter-pass twiddles from a table (0 restores the default)
+extern "C" int h2hip_debug_set_ntt_full_max_log_m(uint32_t v) { TuneWrite()->ntt_full_max_log_m = v ? v : Tuning{}.ntt_full_max_log_m; return 0; }
 // A/B hook: 0 = the inverse transform's 1/n is multiplied in by the last pass even where the first pass reads a table (rounds 1-3)
-extern "C" int h2hip_debug_set_ntt_fold_tables(int on) { g_ntt_fold_tables = on != 0; return 0; }
-static int g_ntt2_log_j = -1;  // tuning: columns per workgroup of the two-pass kernels (-1 = the plan's choice)
+extern "C" int h2hip_debug_set_ntt_fold_tables(int on) { TuneWrite()->ntt_fold_tables = on != 0; return 0; }
 // tuning hook: log2 columns per workgroup of the two-pass kernels (-1 = default)
-extern "C" int h2hip_debug_set_ntt_two_pass_log_j(int v) { g_ntt2_log_j = v; return 0; }
+extern "C" int h2hip_debug_set_ntt_two_pass_log_j(int v) { TuneWrite()->ntt_two_log_j = v; return 0; }
+// tuning hook: largest log2 tile of a pass, clamped to 4..10
+extern "C" int h2hip_debug_set_ntt_smax(uint32_t v) { TuneWrite()->ntt_smax = v < 4 ? 4 : (v > 10 ? 10 : v); return 0; }
+// tuning hook: sizes 2^lo..2^hi (within 16..22) take the two-pass plan; hi < lo turns it off; 0, 0 restores the defaults
+extern "C" int h2hip_debug_set_ntt_two_pass(uint32_t lo, uint32_t hi) {
+    const Tuning d;
+    const bool reset = lo == 0 && hi == 0;
+    TuneWrite t;
+    t->ntt_two_lo = reset ? d.ntt_two_lo : lo < 16 ? 16 : lo;
+    t->ntt_two_hi = reset ? d.ntt_two_hi : hi > 22 ? 22 : hi;
+    t->ntt_two_batch_lo = !reset && t->ntt_two_lo < d.ntt_two_batch_lo ? t->ntt_two_lo : !reset && hi < lo ? 64 : d.ntt_two_batch_lo;  // hi < lo turns the plan off altogether
+    return 0;
+}
+// tuning hook: pairs of workgroups per pass from which batched columns of 2^17 / 2^18 points take the two-pass plan (0 restores the default)
+extern "C" int h2hip_debug_set_ntt_two_pass_batch_wgs(uint64_t v) { TuneWrite()->ntt_two_batch_wgs = v ? v : Tuning{}.ntt_two_batch_wgs; return 0; }
 
 static int get_twiddles(Ctx* c, const Fe& omega, uint32_t log_n, hipStream_t s, TwiddleTable* out) {
     TwiddleKey key;
@@ -616,7 +622,7 @@ static int get_full_twiddles(Ctx* c, const Fe& omega, const NttPass& p, bool two
         }
         if (!t.full[k] && free_slot < 0) free_slot = k;
     }
-    if (free_slot < 0 || c->tw_full_bytes + bytes > g_ntt_full_budget) return 0;
+    if (free_slot < 0 || c->tw_full_bytes + bytes > tune().ntt_full_budget) return 0;
     NttPass q = p;
     if (scale) {  // built from the scaled copy of `lo`: tw_pow(q, e) = scale * omega^e for every e
         const Fu* lo_s = nullptr;
@@ -678,32 +684,7 @@ int scale_periodic_device(Ctx* c, Fe* d_a, uint64_t n, const uint64_t* h_t, uint
     return guard.release();
 }
 
-static uint32_t g_ntt_smax = 8;
-extern "C" int h2hip_debug_set_ntt_smax(uint32_t v) { g_ntt_smax = v < 4 ? 4 : (v > 10 ? 10 : v); return 0; }
-// Sizes 2^lo..2^hi take the two-pass plan (tiles of 2^10 or 2^11 points, ntt2_*_kernel): measured on MI355X
-// (tools/ntt_two_pass.py) 14 % faster than three passes at 2^20, 9 % at 2^21, 5 % at 2^22 with two columns per workgroup, 25 / 19 / 12 % with one
-// (round 3); below 2^19 a lone transform brings too few workgroups.
-// Batched columns of 2^17 / 2^18 points take it too once the batch brings g_ntt_two_batch_wgs workgroup pairs per pass (tools/ntt_batch_rate.py, with one
-// column per workgroup: a lone 2^18 transform 0.068 against 0.052 ms for three passes, two of them 0.041 against 0.048 each; four of 2^17 0.021 / 0.026;
-// a lone 2^19 already 0.078 / 0.091).
-static uint32_t g_ntt_two_lo = 19, g_ntt_two_hi = 22, g_ntt_two_batch_lo = 17;
-static uint64_t g_ntt_two_batch_wgs = 512;
 static bool g_ntt_lds_attr[64];
-// tuning hook: sizes 2^lo..2^hi (within 18..22) take the two-pass plan; hi < lo turns it off
-extern "C" int h2hip_debug_set_ntt_two_pass(uint32_t lo, uint32_t hi) {
-    if (lo == 0 && hi == 0) {  // the defaults
-        g_ntt_two_lo = 19;
-        g_ntt_two_hi = 22;
-        g_ntt_two_batch_lo = 17;
-        return 0;
-    }
-    g_ntt_two_lo = lo < 16 ? 16 : lo;
-    g_ntt_two_hi = hi > 22 ? 22 : hi;
-    g_ntt_two_batch_lo = g_ntt_two_lo < 17 ? g_ntt_two_lo : hi < lo ? 64 : 17;  // hi < lo turns the plan off altogether
-    return 0;
-}
-// tuning hook: pairs of workgroups per pass from which batched columns of 2^17 / 2^18 points take the two-pass plan (0 = default 512)
-extern "C" int h2hip_debug_set_ntt_two_pass_batch_wgs(uint64_t v) { g_ntt_two_batch_wgs = v ? v : 512; return 0; }
 
 // pass radices: one pass up to 2^10, otherwise ceil(log_n / smax) passes of near-equal radix
 static int plan_passes(uint32_t log_n, uint32_t s_out[4]) {
@@ -712,7 +693,7 @@ static int plan_passes(uint32_t log_n, uint32_t s_out[4]) {
         return 1;
     }
     // measured (tools/ntt_sweep.py): 256-point tiles are best up to 2^24; beyond, 512-point tiles save a whole pass
-    const uint32_t smax = (g_ntt_smax == 8 && log_n > 24) ? 9 : g_ntt_smax;
+    const uint32_t smax = (tune().ntt_smax == Tuning{}.ntt_smax && log_n > 24) ? 9 : tune().ntt_smax;
     int P = (int)((log_n + smax - 1) / smax);
     if (P > 4) P = 4;
     uint32_t base = log_n / P, rem = log_n % P;
@@ -723,8 +704,9 @@ static int plan_passes(uint32_t log_n, uint32_t s_out[4]) {
 // The plan ntt_run takes for `count` transforms of 2^log_n points: the number of passes, their tile radices (first pass first) in S,
 // and in *two whether they are the two-pass plan's (ntt2_*_kernel).  h2hip_debug_ntt_plan reports the same.
 static int ntt_plan(uint32_t log_n, size_t count, uint32_t S[4], bool* two) {
-    *two = log_n <= g_ntt_two_hi &&
-           (log_n >= g_ntt_two_lo || (log_n >= g_ntt_two_batch_lo && ((uint64_t)count << (log_n - (log_n + 1) / 2 - 1)) >= g_ntt_two_batch_wgs));
+    const Tuning& t = tune();
+    *two = log_n <= t.ntt_two_hi &&
+           (log_n >= t.ntt_two_lo || (log_n >= t.ntt_two_batch_lo && ((uint64_t)count << (log_n - (log_n + 1) / 2 - 1)) >= t.ntt_two_batch_wgs));
     if (*two) {
         S[0] = (log_n + 1) / 2;
         S[1] = log_n - S[0];
@@ -836,16 +818,16 @@ static int ntt_run(Ctx* c, size_t count, Fe* const* h_datas, const Fe* const* h_
         // no longer do and the table costs 7 % instead
         p.log_m = log_n;
         const Fu* full0 = nullptr;
-        if (log_n <= 21 && g_ntt_full_budget) {
+        if (log_n <= 21 && tune().ntt_full_budget) {
             // one output constant (the inverse's 1/n): a copy of the table that carries it, and pass 2 closes with the direct reduction
-            if (p.out_scale == 2 && sc && g_ntt_fold_tables) {
+            if (p.out_scale == 2 && sc && tune().ntt_fold_tables) {
                 if ((rc = get_full_twiddles(c, omega, p, true, s, &full0, &sc->out3[0]))) return rc;
                 folded = full0 != nullptr;
             }
             if (!full0 && (rc = get_full_twiddles(c, omega, p, true, s, &full0))) return rc;
         }
         p.log_j = 0;  // one column / block per workgroup, neighbours grouped per XCD (ntt2_strided_kernel); two columns one after the other: see there
-        if (g_ntt2_log_j >= 0 && g_ntt2_log_j <= 3) p.log_j = (uint32_t)g_ntt2_log_j;
+        if (tune().ntt_two_log_j >= 0 && tune().ntt_two_log_j <= 3) p.log_j = (uint32_t)tune().ntt_two_log_j;
         for (int t = 0; t < 2; t++) {
             p.s = S[t];
             p.first = (t == 0);
@@ -904,9 +886,9 @@ static int ntt_run(Ctx* c, size_t count, Fe* const* h_datas, const Fe* const* h_
             // a table of up to 2^20 entries (38 MB) stays cache-resident next to the data: every strided pass but the first of a large transform
             p.tw_full = nullptr;
             p.tw_lo = tw.lo;  // (before a table is built from it: pass_twiddle_build_kernel reads p)
-            if (log_m <= g_ntt_full_max_log_m && g_ntt_full_budget) {
+            if (log_m <= tune().ntt_full_max_log_m && tune().ntt_full_budget) {
                 const Fu* full = nullptr;
-                if (t == 0 && p.out_scale == 2 && sc && g_ntt_fold_tables) {  // as in the two-pass plan: the first pass's table carries the one output constant
+                if (t == 0 && p.out_scale == 2 && sc && tune().ntt_fold_tables) {  // as in the two-pass plan: the first pass's table carries the one output constant
                     if ((rc = get_full_twiddles(c, omega, p, false, s, &full, &sc->out3[0]))) return rc;
                     folded = full != nullptr;
                 }
@@ -957,7 +939,7 @@ int ntt_device_batch(Ctx* c, Fe* const* h_datas, const Fe* const* h_srcs, size_t
     // per launch -- from a measurement on the three-pass kernels of round 1; with the two-pass kernels a lone 2^20 column is 512
     // workgroups, two per CU where four fit: eighteen 2^18 -> 2^20 coset NTTs 0.139 -> 0.105 ms each in one launch per pass, ten
     // 2^17 -> 2^19 0.073 -> 0.062; from 2^22 up it makes no difference: tools/ntt_batch_rate.py.)
-    size_t per = g_ntt_batch_bytes / (2 * (sizeof(Fe) << log_n));
+    size_t per = tune().ntt_batch_bytes / (2 * (sizeof(Fe) << log_n));
     if (per < 1) per = 1;
     std::vector<const Fe*> firsts(count);
     for (size_t i = 0; i < count; i++) firsts[i] = (h_srcs && h_srcs[i]) ? h_srcs[i] : h_datas[i];
@@ -975,5 +957,6 @@ int ntt_device_batch(Ctx* c, Fe* const* h_datas, const Fe* const* h_srcs, size_t
 extern "C" int h2hip_debug_ntt_plan(uint32_t log_n, size_t count, uint32_t radices[4]) {
     if (!radices || log_n > h2::FrP::S) return -1;
     bool two;
+    h2::TuneRead r;
     return h2::ntt_plan(log_n, count, radices, &two);
 }

@@ -38,8 +38,6 @@ namespace h2 {
 
 typedef FrUA OpU;
 
-static uint32_t g_open_rows = 0, g_open_threads = 0;  // h2hip_debug_set_opening_tile: forced tile shape (0 = default)
-
 // s + y * v for canonical s, v (E-form) and an I-form power y (fu_from_ext): value < 0.2 p + 2 p, back to canonical
 __device__ __forceinline__ Fe op_axpy(const Fe& s, const Fu& y, const Fe& v) {
     return fu_canon_fast<OpU>(fu_mul_subh<OpU>(fu_slice(v), y, fu_neg(fu_slice(s))));
@@ -254,8 +252,8 @@ static uint32_t ilog2(uint64_t v) {
 static void open_shape(uint64_t elems, uint32_t max_r, uint32_t* R, uint32_t* B) {
     uint32_t r = 1;
     while (r < max_r && ((uint64_t)r * 2) << 17 <= elems) r *= 2;
-    *R = g_open_rows ? g_open_rows : r;
-    *B = g_open_threads ? g_open_threads : OPEN_MAX_THREADS;
+    *R = tune().open_rows ? tune().open_rows : r;
+    *B = tune().open_threads ? tune().open_threads : OPEN_MAX_THREADS;
 }
 
 static void pow_table(const Fe& x, Fu* out) {  // x^(2^b), I-form
@@ -654,8 +652,9 @@ int h2hip_debug_set_opening_tile(uint32_t rows_per_thread, uint32_t threads_per_
         set_error("debug_set_opening_tile: rows per thread (<= 64) and threads per tile (<= %d) must be powers of two or 0", OPEN_MAX_THREADS);
         return H2HIP_EINVAL;
     }
-    g_open_rows = rows_per_thread;
-    g_open_threads = threads_per_tile;
+    TuneWrite t;
+    t->open_rows = rows_per_thread;
+    t->open_threads = threads_per_tile;
     return 0;
 }
 

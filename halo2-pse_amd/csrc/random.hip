@@ -24,10 +24,13 @@ namespace h2 {
 // are generated on the device and downloaded.  HALO2_HIP_RANDOM_MIN_N; the default is the measured break-even ("Randomness")
 #define RN_HOST_MIN_N_DEFAULT ((size_t)1 << 9)
 
-static size_t g_rn_min_n = 0;  // h2hip_debug_set_random_min_n (0 = no wish)
-
+// Read before any Entry (a call below the threshold never starts the engine), hence under a TuneRead; for the same reason the
+// environment is read here, on the first call, and not with the engine's configuration at init.
 static size_t rn_host_min_n() {
-    if (g_rn_min_n) return g_rn_min_n;
+    {
+        TuneRead r;
+        if (tune().random_min_n) return tune().random_min_n;
+    }
     static const size_t v = [] {
         const char* e = getenv("HALO2_HIP_RANDOM_MIN_N");
         if (!e || !*e) return RN_HOST_MIN_N_DEFAULT;
@@ -204,7 +207,7 @@ int h2hip_fr_from_bytes_wide_bn254(const uint8_t* bytes, size_t n, uint64_t* out
 
 // ---- debug hook (include/halo2hip_debug.h) ------------------------------------------------------------------------------------------------
 int h2hip_debug_set_random_min_n(size_t n) {
-    g_rn_min_n = n;
+    TuneWrite()->random_min_n = n;
     return 0;
 }
 

@@ -8,13 +8,8 @@
 
 namespace h2 {
 
-void msm_set_window(uint32_t) {}
-void msm_set_stream(uint32_t, double, size_t) {}
-void ntt_set_full_twiddle_budget(uint64_t) {}
-uint32_t msm_get_reserved_cus() { return 0; }
 uint32_t msm_table_window(size_t) { return 13; }
 void ntt_twiddles_free(Ctx*) {}
-void evalh_debug_set_codegen(int, uint32_t) {}
 void evalh_modules_free(Ctx*) {}
 void evalh_rtc_shutdown() {}
 int scale_periodic_device(Ctx*, Fe*, uint64_t, const uint64_t*, uint32_t, hipStream_t) { return 0; }

@@ -6,6 +6,8 @@
 //   * the single-slot hand-off to the per-device Worker threads (on_devices) from concurrent callers;
 //   * the copier threads (upload / download) of the host-pointer batched transforms, incl. several runs per call;
 //   * h2hip_init / h2hip_shutdown racing with running entry points and with the threshold getters the Rust shim calls per best_multiexp;
+//   * setter hooks (h2hip_debug_set_ntt_host_batch, _set_table_records) called in a loop from a thread of their own while all of the
+//     above runs: a setter takes the engine lock exclusively, the entry points read the settings under their shared hold;
 //   * the no-GPU path (H2_STUB_DEVICES=0): cached failure, getters answer "never".
 // Results are not checked for arithmetic (no kernels run): what is checked is status codes, that copies through the pipeline arrive
 // intact (the stand-in transform adds one to every word), and that TSan reports nothing (it makes the process exit non-zero).
@@ -34,6 +36,19 @@ extern "C" void* h2stub_device_alloc(int device, size_t bytes);  // engine_stubs
 
 static const uint64_t ONE[4] = {0xac96341c4ffffffbULL, 0x36fc76959f60cd29ULL, 0x666ea36f7879462eULL, 0x0e0a77c19a07df2fULL};  // R mod r: Fr one, reduced
 
+// the settings thread of the concurrent phases: the run size of the host-pointer batched transforms between the small values used
+// further down and the defaults, the record form of the window tables between 64, 128 and the engine's choice
+static void setter_loop(const std::atomic<bool>& stop, std::atomic<unsigned>& rounds) {
+    for (unsigned it = 0; !stop.load(); it++) {
+        CHECK((it & 1 ? h2hip_debug_set_ntt_host_batch(0, 0) : h2hip_debug_set_ntt_host_batch(3 * (32 << 10), 2 * (32 << 10))) == 0);
+        CHECK(h2hip_debug_set_table_records(it % 3 == 0 ? 64 : it % 3 == 1 ? 128 : 0) == 0);
+        rounds++;
+        std::this_thread::sleep_for(std::chrono::microseconds(200));  // (glibc's rwlock prefers readers; see the shutdown loop below)
+    }
+    CHECK(h2hip_debug_set_ntt_host_batch(0, 0) == 0);
+    CHECK(h2hip_debug_set_table_records(0) == 0);
+}
+
 int main() {
     const size_t n = 1 << 12;
     // ---- two devices
@@ -42,8 +57,10 @@ int main() {
     CHECK(h2hip_num_devices() == 2);
     std::vector<uint64_t> bases(n * 8, 0), scalars(n * 4, 0);
     for (size_t i = 0; i < n; i++) scalars[4 * i] = i;
-    std::atomic<bool> stop{false};
+    std::atomic<bool> stop{false}, stop_setter{false};
+    std::atomic<unsigned> set_rounds{0};
     std::vector<std::thread> th;
+    std::thread setter(setter_loop, std::cref(stop_setter), std::ref(set_rounds));
     // host-pointer MSMs (all-device lock, on_devices) + pin / unpin of the same array
     for (int t = 0; t < 3; t++)
         th.emplace_back([&, t] {
@@ -126,6 +143,12 @@ int main() {
     th[th.size() - 2].join();
     th[th.size() - 1].join();
     th.clear();
+    stop_setter.store(true);
+    setter.join();
+    // (a setter waits for the running calls, and glibc's rwlock prefers readers: a dozen threads calling in closed loops leave it
+    // few turns -- the count is printed, not bounded; the one turn it has at the latest when the callers are done is certain)
+    printf("setter rounds among the concurrent callers: %u\n", set_rounds.load());
+    CHECK(set_rounds.load() >= 1);
     // small runs force several pipelined runs and grouped steps in one call
     h2hip_debug_set_ntt_host_batch(3 * (32 << 10), 2 * (32 << 10));
     {
@@ -140,6 +163,9 @@ int main() {
 
     // ---- shutdown / init cycles racing with callers (every call either runs or re-initialises lazily; none may crash or deadlock)
     stop.store(false);
+    stop_setter.store(false);
+    set_rounds.store(0);
+    setter = std::thread(setter_loop, std::cref(stop_setter), std::ref(set_rounds));
     for (int t = 0; t < 3; t++)
         th.emplace_back([&] {
             uint64_t out[12];
@@ -158,8 +184,12 @@ int main() {
         CHECK(rc == 0 || rc == H2HIP_EINVAL);
     }
     stop.store(true);
+    stop_setter.store(true);
     for (auto& t : th) t.join();
     th.clear();
+    setter.join();
+    printf("setter rounds among the shutdown / init cycles: %u\n", set_rounds.load());
+    CHECK(set_rounds.load() >= 1);
     h2hip_shutdown();
 
     // ---- no GPU: the failure is cached, the getters say "never", explicit init retries

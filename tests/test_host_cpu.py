@@ -92,7 +92,8 @@ def test_host_code_under_asan_ubsan(tmp_path):
 def test_engine_host_logic_under_tsan(tmp_path):
     """the multi-device host logic of csrc/api.hip -- per-context locks under the shared engine lock, the
     single-slot hand-off to the per-device Worker threads, the copier threads of the host-pointer batched transforms, init /
-    shutdown racing with callers, the cached no-GPU state -- never ran on two distinct GPUs.  Here api.hip is compiled as plain
+    shutdown racing with callers, setter hooks called in a loop beside them, the cached no-GPU state -- never ran on two distinct
+    GPUs.  Here api.hip is compiled as plain
     C++ against a stub HIP runtime with two fake devices (tests/cpp/hipstub) and driven from a dozen threads under
     ThreadSanitizer (tests/cpp/test_engine_tsan.cpp); TSan turns any report into a non-zero exit."""
     csrc = os.path.join(ROOT, "halo2-pse_amd", "csrc")
