@@ -257,6 +257,75 @@ def columns_pinned_info():
     return n.value, b.value
 
 
+_part_pins = {}  # address -> weakref.finalize on the array (or the tensor's storage) whose part cosets are pinned
+
+
+def _part_unpin_address(addr):
+    _part_pins.pop(addr, None)
+    try:
+        lib().h2hip_part_cosets_unpin((ctypes.c_void_p * 1)(addr), ctypes.c_size_t(1))
+    except Exception:
+        pass
+
+
+def part_cosets_pin(polys, domain):
+    """keep all P part cosets of a proving key's coefficient-form polynomials (pk.fixed_polys, pk.l0 / l_last / l_active_row as
+    polynomials, pk.permutation.polys: (2^k, 4) uint64 arrays, or torch CUDA tensors of 2^k x 32 B) in HBM across evaluate_h_parts calls
+    over `domain` (h2hip_part_cosets_pin[_device]), keyed by their addresses.  An entry goes when its array (a tensor's storage) does;
+    a device tensor must stay unchanged until then."""
+    import weakref
+    polys = list(polys)
+    if not polys:
+        return
+    host = isinstance(polys[0], np.ndarray)
+    consts = (ctypes.c_uint32(domain.k), ctypes.c_uint32(domain.extended_k), _p(domain.extended_omega), _p(domain.g_coset), _p(domain.g_coset_inv))
+    if host:
+        for a in polys:
+            assert a.dtype == np.uint64 and a.flags["C_CONTIGUOUS"] and a.shape == (1 << domain.k, 4)
+        _check(lib().h2hip_part_cosets_pin(_host_ptrs(polys), ctypes.c_size_t(len(polys)), *consts), "h2hip_part_cosets_pin")
+    else:
+        for t in polys:
+            assert t.numel() * t.element_size() == 32 << domain.k
+        _check(lib().h2hip_part_cosets_pin_device(_ptr_array(polys), ctypes.c_size_t(len(polys)), *consts, _stream()), "h2hip_part_cosets_pin_device")
+    for a in polys:
+        addr = a.ctypes.data if host else a.data_ptr()
+        old = _part_pins.pop(addr, None)
+        if old is not None:
+            old.detach()
+        try:
+            _part_pins[addr] = weakref.finalize(a if host else a.untyped_storage(), _part_unpin_address, addr)
+            _part_pins[addr].atexit = False  # at exit the engine's shutdown frees every entry
+        except TypeError:  # a read-only view that cannot be weakly referenced: the caller unpins
+            pass
+
+
+def part_cosets_unpin(polys):
+    polys = list(polys)
+    if not polys:
+        return
+    addrs = [a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr() for a in polys]
+    for addr in addrs:
+        fin = _part_pins.pop(addr, None)
+        if fin is not None:
+            fin.detach()
+    _check(lib().h2hip_part_cosets_unpin((ctypes.c_void_p * len(addrs))(*addrs), ctypes.c_size_t(len(addrs))), "h2hip_part_cosets_unpin")
+
+
+def part_cosets_pinned_info():
+    """(polynomials, bytes of HBM) the pinned part cosets hold"""
+    n, b = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(lib().h2hip_part_cosets_pinned_info(ctypes.byref(n), ctypes.byref(b)), "h2hip_part_cosets_pinned_info")
+    return n.value, b.value
+
+
+def evalh_parts_stats():
+    """the calling thread's last evaluate_h_parts call (h2hip_debug_evalh_parts_stats): columns scaled and transformed and columns served
+    from pins (both summed over parts), column bytes uploaded, arena bytes"""
+    out = (ctypes.c_uint64 * 4)()
+    _check(lib().h2hip_debug_evalh_parts_stats(out), "h2hip_debug_evalh_parts_stats")
+    return tuple(int(x) for x in out)
+
+
 def bases_pinned_info(bases):
     """(points, window bits, windows, bytes of HBM) of a pinned host array or device tensor"""
     ptr = _p(bases) if isinstance(bases, np.ndarray) else _dptr(bases)
@@ -961,6 +1030,17 @@ class EvaluationDomain:
                "h2hip_coeff_to_extended_bn254_fr")
         return out
 
+    def coeff_to_extended_part(self, a, part):
+        """upstream halo2's coeff_to_extended_part: rows j * P + part (P = 2^(extended_k - k)) of coeff_to_extended(a), 2^k elements"""
+        self._device_field()
+        a = _u64(a, 4)
+        assert a.shape[0] == 1 << self.k
+        out = np.zeros((1 << self.k, 4), dtype=np.uint64)
+        _check(lib().h2hip_coeff_to_extended_part_bn254_fr(_p(a), ctypes.c_uint32(self.k), ctypes.c_uint32(self.extended_k), ctypes.c_uint32(part),
+                                                           _p(self.extended_omega), _p(self.g_coset), _p(self.g_coset_inv), _p(out)),
+               "h2hip_coeff_to_extended_part_bn254_fr")
+        return out
+
     def extended_to_coeff(self, a):
         """poly/domain.rs:281-303 (including the truncate at :299-300)"""
         self._device_field()
@@ -1468,6 +1548,14 @@ def coeff_to_extended_device(d_a, k, extended_k, extended_omega, g_coset, g_cose
            "h2hip_coeff_to_extended_bn254_fr_device")
 
 
+def coeff_to_extended_part_device(d_a, k, extended_k, part, extended_omega, g_coset, g_coset_inv, d_out=None):
+    """part `part` of coeff_to_extended(d_a) into d_out (2^k elements each; d_out None: in place); queued on the current stream"""
+    d_out = d_a if d_out is None else d_out
+    _check(lib().h2hip_coeff_to_extended_part_bn254_fr_device(_dptr(d_a), ctypes.c_uint32(k), ctypes.c_uint32(extended_k), ctypes.c_uint32(part),
+                                                              _p(_fe(extended_omega)), _p(_fe(g_coset)), _p(_fe(g_coset_inv)), _dptr(d_out),
+                                                              _stream()), "h2hip_coeff_to_extended_part_bn254_fr_device")
+
+
 def extended_to_coeff_device(d_a, extended_k, extended_omega_inv, extended_ifft_divisor, g_coset, g_coset_inv):
     _check(lib().h2hip_extended_to_coeff_bn254_fr_device(_dptr(d_a), ctypes.c_uint32(extended_k), _p(_fe(extended_omega_inv)),
                                                          _p(_fe(extended_ifft_divisor)), _p(_fe(g_coset)), _p(_fe(g_coset_inv)), _stream()),
@@ -1493,6 +1581,17 @@ def coeff_to_extended_batch_device(d_list, k, extended_k, extended_omega, g_cose
     _check(lib().h2hip_coeff_to_extended_bn254_fr_batch_device(_ptr_array(d_list), ctypes.c_size_t(len(d_list)), ctypes.c_uint32(k),
                                                                ctypes.c_uint32(extended_k), _p(_fe(extended_omega)), _p(_fe(g_coset)),
                                                                _p(_fe(g_coset_inv)), _stream()), "h2hip_coeff_to_extended_bn254_fr_batch_device")
+
+
+def coeff_to_extended_part_batch_device(d_list, d_out_list, parts, k, extended_k, extended_omega, g_coset, g_coset_inv):
+    """transform i: part parts[i] of coeff_to_extended(d_list[i]) into d_out_list[i], one launch per pass; a source may feed several
+    transforms (all P parts of one polynomial), and an output may be its own source only where that source feeds no other transform"""
+    assert len(d_list) == len(d_out_list) == len(parts)
+    h_parts = (ctypes.c_uint32 * max(1, len(parts)))(*[int(p) for p in parts])
+    _check(lib().h2hip_coeff_to_extended_part_bn254_fr_batch_device(_ptr_array(d_list), _ptr_array(d_out_list), h_parts, ctypes.c_size_t(len(d_list)),
+                                                                    ctypes.c_uint32(k), ctypes.c_uint32(extended_k), _p(_fe(extended_omega)),
+                                                                    _p(_fe(g_coset)), _p(_fe(g_coset_inv)), _stream()),
+           "h2hip_coeff_to_extended_part_bn254_fr_batch_device")
 
 def permutation_products_device(k, omega, delta, beta, gamma, d_columns, d_permutations, chunk_len, blinding, blinding_factors, d_z):
     """device form of permutation_products: torch CUDA tensors of 2^k x 32 B in, the n_sets tensors of d_z written; queued on the

@@ -882,6 +882,9 @@ static void release_ctx(Ctx* c) {
     for (auto& kv : c->pinned_cols) (void)hipFree(kv.second.d);
     c->pinned_cols.clear();
     c->pinned_cols_bytes = 0;
+    for (auto& kv : c->pinned_parts) (void)hipFree(kv.second.d);
+    c->pinned_parts.clear();
+    c->pinned_parts_bytes = 0;
     c->pin_flag.release();
     c->ntt_ws.release();
     c->ntt_io.release();
@@ -1033,7 +1036,7 @@ static int msm_device_keyed(Ctx* c, const Fe* const* d_scalars, const Affine* d_
 }
 
 // (pinned proving-key columns: see h2hip_columns_pin further down)
-static void column_sample(const uint64_t* h_col, size_t elems, uint8_t* out) {
+void column_sample(const uint64_t* h_col, size_t elems, uint8_t* out) {
     for (uint32_t k = 0; k < H2_COL_SAMPLES; k++) memcpy(out + 32 * k, h_col + 4 * pin_sample_index(elems, k), 32);
 }
 
@@ -1052,6 +1055,33 @@ const Fe* pinned_column_lookup(Ctx* c, const uint64_t* h_col, size_t elems) {
     }
     pc.last_use = ++c->pinned_cols_tick;
     return (const Fe*)pc.d;
+}
+
+// (the Entry of the caller holds the engine lock shared: the configuration cannot change under it)
+int pinned_make_room(Ctx* c, size_t bytes, bool* fits) {
+    const size_t budget = g_cfg.column_cache_bytes;
+    *fits = bytes <= budget;
+    if (!*fits) return 0;
+    while (c->pinned_cols_bytes + c->pinned_parts_bytes + bytes > budget) {  // least recently used first, whichever kind it is
+        auto vc = c->pinned_cols.end();
+        for (auto it = c->pinned_cols.begin(); it != c->pinned_cols.end(); ++it)
+            if (vc == c->pinned_cols.end() || it->second.last_use < vc->second.last_use) vc = it;
+        auto vp = c->pinned_parts.end();
+        for (auto it = c->pinned_parts.begin(); it != c->pinned_parts.end(); ++it)
+            if (vp == c->pinned_parts.end() || it->second.last_use < vp->second.last_use) vp = it;
+        if (vc == c->pinned_cols.end() && vp == c->pinned_parts.end()) break;
+        H2_CHECK(hipDeviceSynchronize());  // a queued evaluate_h may still read the copy
+        if (vp == c->pinned_parts.end() || (vc != c->pinned_cols.end() && vc->second.last_use < vp->second.last_use)) {
+            (void)hipFree(vc->second.d);
+            c->pinned_cols_bytes -= vc->second.elems * sizeof(Fe);
+            c->pinned_cols.erase(vc);
+        } else {
+            (void)hipFree(vp->second.d);
+            c->pinned_parts_bytes -= vp->second.bytes();
+            c->pinned_parts.erase(vp);
+        }
+    }
+    return 0;
 }
 
 }  // namespace h2
@@ -2071,19 +2101,11 @@ extern "C" int h2hip_columns_pin(const uint64_t* const* cols, size_t count, size
     if (en.rc) return en.rc;
     Ctx* c = en.c;  // evaluate_h runs on the engine's first device
     const size_t bytes = elems * sizeof(Fe);
-    const size_t budget = g_cfg.column_cache_bytes;  // (the Entry above holds the engine lock shared: the configuration cannot change under it)
     for (size_t i = 0; i < count; i++) {
         if (pinned_column_lookup(c, cols[i], elems)) continue;  // already there (and still the same array)
-        while (!c->pinned_cols.empty() && c->pinned_cols_bytes + bytes > budget) {  // least recently used first
-            auto victim = c->pinned_cols.begin();
-            for (auto it = c->pinned_cols.begin(); it != c->pinned_cols.end(); ++it)
-                if (it->second.last_use < victim->second.last_use) victim = it;
-            H2_CHECK(hipDeviceSynchronize());
-            (void)hipFree(victim->second.d);
-            c->pinned_cols_bytes -= victim->second.elems * sizeof(Fe);
-            c->pinned_cols.erase(victim);
-        }
-        if (bytes > budget) continue;  // does not fit at all: the call stays correct, this column is uploaded per call
+        bool fits;
+        if (int rc = pinned_make_room(c, bytes, &fits)) return rc;  // the budget and its LRU are shared with the pinned part cosets
+        if (!fits) continue;  // does not fit at all: the call stays correct, this column is uploaded per call
         PinnedColumn pc;
         if (hipMalloc(&pc.d, bytes) != hipSuccess) {
             (void)hipGetLastError();

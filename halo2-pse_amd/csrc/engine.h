@@ -126,6 +126,19 @@ struct PinnedColumn {
     uint8_t sample[H2_COL_SAMPLES * 32];
 };
 
+// All P = 2^(ek - k) part cosets of one coefficient-form polynomial of a proving key (h2hip_part_cosets_pin, evalh.hip), part-major: part p
+// is the 2^k elements at d + p * 2^k.  Keyed by the caller's pointer -- a map of its own, so the same pointer may also be a pinned column
+// -- and by the domain; host keys are guarded by the column fingerprint, device keys by the caller's contract.
+struct PinnedParts {
+    void* d = nullptr;
+    uint32_t k = 0, ek = 0;
+    Fe ext_omega, g_coset;
+    bool device_key = false;
+    uint64_t last_use = 0;
+    uint8_t sample[H2_COL_SAMPLES * 32];
+    size_t bytes() const { return sizeof(Fe) << ek; }
+};
+
 struct StageTimer {
     std::string name;
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -199,6 +212,8 @@ struct Ctx {
     std::map<const void*, PinnedColumn> pinned_cols;  // h2hip_columns_pin: the host-pointer evaluate_h finds a proving key's constant columns here
     size_t pinned_cols_bytes = 0;
     uint64_t pinned_cols_tick = 0;
+    std::map<const void*, PinnedParts> pinned_parts;  // h2hip_part_cosets_pin: the parts form of evaluate_h finds the key's part cosets here
+    size_t pinned_parts_bytes = 0;                    // (one budget, one LRU clock with the pinned columns: pinned_make_room)
     // profiling
     bool profiling = false;        // every stage bracketed by a pair of events (each record costs the stream ~10 us)
     bool profiling_kernel = false; // only the dominant kernel, timed through its own dispatch (hipExtLaunchKernelGGL): no gap
@@ -328,6 +343,7 @@ struct Tuning {
     bool evalh_gen_fuse = true;  // two products meeting in a sum share one reduction (gen_source); codegen mode + 16 turns it off (A/B, tests)
     uint32_t evalh_max_local_slots = 256;  // programs needing more slots use the global-workspace form of the kernels (tests force it)
     size_t evalh_lookup_group_bytes = (size_t)2 << 30;  // HBM one group of lookup cosets may take (tests shrink it to force several groups)
+    bool evalh_part_fused = false;  // parts form: the unpinned columns' coset scaling in the transform's first-pass load (ntt_part_device_batch), or evalh_part_scale_kernel + plain transform (DESIGN.md 5 has the A/B)
     // -- the smaller stages
     bool ecfft_quad = true, ecfft_lazy = true;  // g_to_lagrange / fft_g1 up to k = 14: one quad of lanes per butterfly; the points stay XYZZ between the layers
     uint32_t lookup_sort_block = 0;  // forced in-LDS sort block of the lookup permutation (0 = LK_TILE)
@@ -482,6 +498,15 @@ struct NttScale {
 void ntt_twiddles_free(Ctx* c);
 int ntt_device(Ctx* c, Fe* d_data, const Fe& omega, uint32_t log_n, const NttScale* sc, hipStream_t s, const Fe* d_src = nullptr);
 
+// the part mode of the first-pass load (ntt.hip, NttPart), as ntt_run takes it: the extended domain whose power table the load reads
+// and the part of each transform of the launch (host array)
+struct NttPartMode {
+    Fe ext_omega;
+    uint32_t ext_k;
+    const uint32_t* parts;
+};
+int ntt_part_device_batch(Ctx* c, Fe* const* h_outs, const Fe* const* h_srcs, const uint32_t* parts, size_t count, uint32_t k, uint32_t ext_k,
+                          const Fe& ext_omega, const Fe& g_coset, const Fe& g_coset_inv, hipStream_t s);
 int ntt_power_table(Ctx* c, const Fe& omega, uint32_t log_n, hipStream_t s, const Fu** lo, const Fu** hi, uint32_t* lo_bits);
 int ntt_device_batch(Ctx* c, Fe* const* h_datas, const Fe* const* h_srcs, size_t count, const Fe& omega, uint32_t log_n, const NttScale* sc,
                      hipStream_t s);
@@ -518,6 +543,11 @@ int kzg_setup_device(Ctx* c, uint32_t k, const Fe& s, Affine* d_g, Affine* d_gl,
 
 // api.hip: the device copy of a pinned host column whose fingerprint still matches the caller's memory, or nullptr
 const Fe* pinned_column_lookup(Ctx* c, const uint64_t* h_col, size_t elems);
+// api.hip: the fingerprint of a host column (H2_COL_SAMPLES elements); room for `bytes` more in the budget the pinned columns and the
+// pinned part cosets share (HALO2_HIP_COLUMN_CACHE_GB), least recently used entries of either kind dropped first -- false: `bytes`
+// exceed the whole budget, nothing was dropped
+void column_sample(const uint64_t* h_col, size_t elems, uint8_t* out);
+int pinned_make_room(Ctx* c, size_t bytes, bool* fits);
 
 // evalh.hip
 void evalh_modules_free(Ctx* c);                            // unload this device's generated kernels (release_ctx)

@@ -1651,7 +1651,39 @@ static int evaluate_h_parts_validate(const h2hip_evalh_parts_desc* d, const void
     return 0;
 }
 
-// dev as in evaluate_h_host.  Host form: every coefficient column crosses once (2^k elements), `values` crosses both ways once.
+// ---- pinned part cosets (h2hip_part_cosets_pin below).  The entry of `key` for this domain: part p is the 2^k elements at the result
+// + p * 2^k.  A host key's fingerprint is compared with the caller's memory on every use, and on a mismatch the entry is dropped --
+// after a device synchronisation, since a queued call may still read it -- and the call goes on as if nothing were pinned; a device key
+// rests on the caller's contract, because the device form never waits for a verdict.
+static const Fe* pinned_parts_lookup(Ctx* c, const void* key, bool dev, uint32_t k, uint32_t ek, const Fe& ext_omega, const Fe& g_coset) {
+    auto it = c->pinned_parts.find(key);
+    if (it == c->pinned_parts.end()) return nullptr;
+    PinnedParts& pp = it->second;
+    if (pp.device_key != dev || pp.k != k || pp.ek != ek || memcmp(&pp.ext_omega, &ext_omega, sizeof(Fe)) != 0 ||
+        memcmp(&pp.g_coset, &g_coset, sizeof(Fe)) != 0)
+        return nullptr;  // pinned for another domain, or another kind of key: not this call's
+    if (!dev) {
+        uint8_t now[H2_COL_SAMPLES * 32];
+        column_sample((const uint64_t*)key, (size_t)1 << k, now);
+        if (memcmp(now, pp.sample, sizeof(now)) != 0) {  // another array lives at this address now: forget the entry
+            (void)hipDeviceSynchronize();
+            (void)hipFree(pp.d);
+            c->pinned_parts_bytes -= pp.bytes();
+            c->pinned_parts.erase(it);
+            return nullptr;
+        }
+    }
+    pp.last_use = ++c->pinned_cols_tick;
+    return (const Fe*)pp.d;
+}
+
+// what the last parts call of this thread did (h2hip_debug_evalh_parts_stats): columns scaled and transformed and columns served from
+// pins, both summed over the call's parts; column bytes uploaded (host form); arena bytes taken behind the metadata
+static thread_local uint64_t g_parts_stats[4];
+
+// dev as in evaluate_h_host.  Host form: every coefficient column that is not pinned crosses once (2^k elements), `values` crosses both
+// ways once.  A key polynomial (fixed_polys, the three Lagrange polynomials, perm_polys) whose part cosets are pinned is read, for part p,
+// where the pin holds that part: no upload, no scale, no transform, no copy and no arena slot.  Any subset of them may hit.
 static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, uint64_t* values, bool dev, hipStream_t s) {
     const uint32_t k = d->k, ek = d->extended_k, log_p = ek - k;
     const size_t n = (size_t)1 << k, size = (size_t)1 << ek;
@@ -1677,12 +1709,41 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, uint64
     for (uint32_t i = 0; i < d->n_lookups; i++)
         polys.push_back(d->lookup_product_polys[i]), polys.push_back(d->lookup_permuted_input_polys[i]), polys.push_back(d->lookup_permuted_table_polys[i]);
     const size_t lk_group = lookup_group(d->n_lookups, part_bytes);
-    const size_t n_part_cols = n_main + 3 * lk_group;
-    // ---- device arena: [metadata | (host form) coefficient columns | one part's cosets | the part's rows of values | (host form) values]
+    const Fe ext_omega = fe_from_u64x4(d->extended_omega);
+    const Fe omega = fe_pow_u64<FrP>(ext_omega, (uint64_t)1 << log_p);
+    const Fe g_coset = fe_from_u64x4(d->g_coset), g_coset_inv = fe_from_u64x4(d->g_coset_inv);
+    // ---- the key's polynomials whose part cosets are pinned; the others are `live`: uploaded (host form), scaled and transformed per part
+    std::vector<const Fe*> pin(n_main, nullptr);
+    {
+        auto look = [&](size_t i) { pin[i] = pinned_parts_lookup(c, polys[i], dev, k, ek, ext_omega, g_coset); };
+        for (uint32_t i = 0; i < d->n_fixed; i++) look(i);
+        for (size_t i = 0; i < 3; i++) look(at_l0 + i);
+        if (d->n_perm_sets)
+            for (uint32_t j = 0; j < d->n_perm_columns; j++) look(at_z + d->n_perm_sets + j);
+    }
+    std::vector<size_t> slot(polys.size(), SIZE_MAX);  // polys index -> index among the live columns
+    std::vector<const uint64_t*> live;
+    size_t n_live_main = 0;
+    for (size_t i = 0; i < polys.size(); i++) {
+        if (i < n_main && pin[i]) continue;
+        slot[i] = live.size();
+        live.push_back(polys[i]);
+        if (i < n_main) n_live_main++;
+    }
+    const size_t n_pinned = n_main - n_live_main;
+    const size_t n_part_cols = n_live_main + 3 * lk_group;  // arena columns of one part: the live key and witness columns, one group of lookups
+    const size_t n_sets = n_pinned ? p_end - p_begin : 1;   // column-pointer tables: one set per part once a pinned column's address depends on it
+    // ---- device arena: [metadata | (host form) the live coefficient columns | one part's cosets of them | the part's rows of values |
+    //      (host form) values].  h2hip_evaluate_h_workspace_bytes is the upper bound, reached when nothing is pinned: a pinned column takes
+    //      neither a coset slot nor, in the host form, a coefficient slot.
     size_t arena_bytes;
     if ((rc = evaluate_h_workspace_bytes(k, ek, d->n_fixed, d->n_advice, d->n_instance, d->n_perm_sets, d->n_perm_columns, d->n_lookups, true, dev, &arena_bytes)))
         return rc;
-    const size_t meta_cap = evalh_meta_cap(cp, f, polys.size() + n_part_cols);  // this form's own tables: where the polynomials lie, where a part's cosets go
+    arena_bytes -= n_pinned * part_bytes * (dev ? 1 : 2);
+    const size_t set_bytes = (8 + 256) * ((size_t)d->n_fixed + d->n_advice + d->n_instance + d->n_perm_sets + 2 * (size_t)d->n_perm_columns + 16) +
+                             ((size_t)d->n_challenges + 28) * sizeof(Fu) + 256;
+    // this form's own tables: where the live polynomials lie, where a part's cosets go; and the further sets of column tables
+    const size_t meta_cap = evalh_meta_cap(cp, f, live.size() + n_part_cols) + align256((n_sets - 1) * set_bytes);
     if ((rc = c->evalh_ws.ensure(meta_cap + arena_bytes))) return rc;
     if (cp.slots_ws && (rc = c->evalh_slots.ensure(cp.slots_ws))) return rc;
     if ((rc = c->ws_acquire(s))) return rc;
@@ -1693,8 +1754,9 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, uint64
     MetaBlob mb;
     mb.dev_base = (char*)ar.take(meta_cap);
     mb.cap = meta_cap;
-    std::vector<const Fe*> src(polys.size());
-    for (size_t i = 0; i < polys.size(); i++) src[i] = dev ? (const Fe*)polys[i] : (const Fe*)ar.take(part_bytes);
+    const size_t arena_begin = ar.off;
+    std::vector<const Fe*> src(live.size());
+    for (size_t i = 0; i < live.size(); i++) src[i] = dev ? (const Fe*)live[i] : (const Fe*)ar.take(part_bytes);
     std::vector<Fe*> part_cols(n_part_cols);
     for (size_t i = 0; i < n_part_cols; i++) part_cols[i] = (Fe*)ar.take(part_bytes);
     Fe* const d_part = (Fe*)ar.take(part_bytes);
@@ -1703,13 +1765,14 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, uint64
         set_error("evaluate_h: arena overflow");
         return 1;
     }
+    g_parts_stats[0] = g_parts_stats[1] = 0;
+    g_parts_stats[2] = dev ? 0 : live.size() * n * sizeof(Fe);
+    g_parts_stats[3] = ar.off - arena_begin;
     // ---- the two domains' power tables.  A table handed out by ntt_power_table lives until the twiddle cache is cleared, which only
     // the insertion of a domain the cache does not hold yet can do (ntt.hip, get_twiddles).  So both domains are brought into the cache
     // first -- the second request may clear it, in which case the third puts the extended domain back into a cache of one -- and only
     // then are the pointers kept.  Everything this call transforms afterwards is over (omega, k), a cache hit that inserts nothing, and
     // the context's lock keeps other calls out until this one has queued its last kernel: no kernel queued below can outlive its table.
-    const Fe ext_omega = fe_from_u64x4(d->extended_omega);
-    const Fe omega = fe_pow_u64<FrP>(ext_omega, (uint64_t)1 << log_p);
     PartScaleDev sd;
     memset(&sd, 0, sizeof(sd));
     const Fu *pow_lo, *pow_hi;  // the 2^k domain's, for the permutation kernel
@@ -1717,19 +1780,28 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, uint64
     if ((rc = ntt_power_table(c, ext_omega, ek, s, &sd.pow_lo, &sd.pow_hi, &sd.pow_bits))) return rc;
     if ((rc = ntt_power_table(c, omega, k, s, &pow_lo, &pow_hi, &pow_bits))) return rc;
     if ((rc = ntt_power_table(c, ext_omega, ek, s, &sd.pow_lo, &sd.pow_hi, &sd.pow_bits))) return rc;
-    // ---- metadata image
+    // ---- metadata image.  A part's cosets in the order of `polys`: a pinned column where the pin holds that part, a live one in its arena
+    // slot, which every part reuses; without a pin the one set serves every part
     const Fe* const* d_src = mb.put(src.data(), src.size());
     const Fe* const* d_dst = (const Fe* const*)mb.put(part_cols.data(), part_cols.size());
-    const Fe* const* col = part_cols.data();  // one part's cosets, in the order of `polys`
-    const Fe* const* advice = col + d->n_fixed;
-    const ColsDev cols = cols_put(mb, f, col, advice, advice + d->n_advice, k, 1);
+    std::vector<std::vector<const Fe*>> colp(n_sets, std::vector<const Fe*>(n_main + 3 * lk_group));
+    std::vector<ColsDev> cols_p(n_sets);
+    std::vector<PermDev> pd_p(n_sets);
+    for (size_t t = 0; t < n_sets; t++) {
+        const size_t p = p_begin + t;
+        for (size_t i = 0; i < n_main; i++) colp[t][i] = pin[i] ? pin[i] + p * n : part_cols[slot[i]];
+        for (size_t i = 0; i < 3 * lk_group; i++) colp[t][n_main + i] = part_cols[n_live_main + i];
+        const Fe* const* col = colp[t].data();
+        const Fe* const* advice = col + d->n_fixed;
+        cols_p[t] = cols_put(mb, f, col, advice, advice + d->n_advice, k, 1);
+        pd_p[t] = perm_put(mb, f, col, advice, advice + d->n_advice, col + at_z, col + at_z + d->n_perm_sets, col + at_l0, pow_lo, pow_hi, pow_bits);
+    }
     const std::vector<ProgDev> pds = progs_put(mb, cp);
-    PermDev pd = perm_put(mb, f, col, advice, advice + d->n_advice, col + at_z, col + at_z + d->n_perm_sets, col + at_l0, pow_lo, pow_hi, pow_bits);
     if (mb.overflow) {
         set_error("evaluate_h: metadata region overflow");
         return 1;
     }
-    // ---- upload.  Host form: every coefficient column and `values` cross once, on `s` like everything else of this call.  Of `values`
+    // ---- upload.  Host form: every live coefficient column and `values` cross once, on `s` like everything else of this call.  Of `values`
     // only the rows of this call's parts cross, in either direction: P rows of consecutive parts are contiguous, so a range of parts is a 2-D copy
     if ((rc = c->stage_h2d(mb.dev_base, mb.host.data(), mb.host.size(), s))) return rc;
     auto copy_values = [&](Fe* dst, const Fe* from, hipMemcpyKind kind) -> int {
@@ -1742,15 +1814,24 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, uint64
         return 0;
     };
     if (!dev) {
-        for (size_t i = 0; i < polys.size(); i++) H2_CHECK(hipMemcpyAsync((void*)src[i], polys[i], n * sizeof(Fe), hipMemcpyHostToDevice, s));
+        for (size_t i = 0; i < live.size(); i++) H2_CHECK(hipMemcpyAsync((void*)src[i], live[i], n * sizeof(Fe), hipMemcpyHostToDevice, s));
         if ((rc = copy_values(d_values, (const Fe*)values, hipMemcpyHostToDevice))) return rc;
     }
     sd.log_n = k;
     sd.c3[0] = fu_one_i<UF>();
-    sd.c3[1] = to_i(fe_from_u64x4(d->g_coset));
-    sd.c3[2] = to_i(fe_from_u64x4(d->g_coset_inv));
-    // columns first .. first + count of `polys` -> part_cols[to ..], scaled for part p and transformed over the 2^k domain
+    sd.c3[1] = to_i(g_coset);
+    sd.c3[2] = to_i(g_coset_inv);
+    const bool fused = tune().evalh_part_fused;
+    std::vector<uint32_t> same_part;
+    // live columns first .. first + count -> part_cols[to ..], scaled for part p and transformed over the 2^k domain: the scale kernel and
+    // a plain transform, or (Tuning::evalh_part_fused) the transform whose first-pass load scales
     auto to_part = [&](uint32_t p, size_t first, size_t to, size_t count) -> int {
+        if (!count) return 0;
+        g_parts_stats[0] += count;
+        if (fused) {
+            same_part.assign(count, p);
+            return ntt_part_device_batch(c, part_cols.data() + to, src.data() + first, same_part.data(), count, k, ek, ext_omega, g_coset, g_coset_inv, s);
+        }
         sd.src = d_src + first;
         sd.dst = d_dst + to;
         sd.n_cols = (uint32_t)count;
@@ -1765,7 +1846,11 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, uint64
     const dim3 grid((uint32_t)((n + 255) / 256)), block(256);
     const Fe beta_zeta = d->n_perm_sets ? fe_mul<FrP>(fe_from_u64x4(d->beta), fe_from_u64x4(d->zeta)) : fe_zero<FrP>();
     for (uint32_t p = p_begin; p < p_end; p++) {
-        // ---- scale and transform: the part's cosets of the key and witness columns and of the first group of lookups
+        const size_t t = n_sets > 1 ? p - p_begin : 0;
+        const Fe* const* col = colp[t].data();
+        PermDev& pd = pd_p[t];
+        g_parts_stats[1] += n_pinned;
+        // ---- scale and transform: the part's cosets of the live key and witness columns and of the first group of lookups
         int t_c = c->timer_begin("evalh_cosets", s);
         if ((rc = to_part(p, 0, 0, n_part_cols))) return rc;
         c->timer_end(t_c, s);
@@ -1777,8 +1862,8 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, uint64
         // ---- the pass, over the part's rows: nothing of the permutation's arrives late here, and a later group of lookups is
         //      scaled and transformed into the group's buffers as the first was
         if (d->n_perm_sets) pd.delta_start = to_i(fe_mul<FrP>(beta_zeta, fe_pow_u64<FrP>(ext_omega, p)));  // beta g_p; the kernel multiplies by omega^j
-        if ((rc = constraint_pass(c, cp, pds, cols, pd, col + at_l0, col + n_main, lk_group, d_part, n, s, [] { return 0; },
-                                  [&](size_t first, size_t count) { return to_part(p, n_main + 3 * first, n_main, 3 * count); })))
+        if ((rc = constraint_pass(c, cp, pds, cols_p[t], pd, col + at_l0, col + n_main, lk_group, d_part, n, s, [] { return 0; },
+                                  [&](size_t first, size_t count) { return to_part(p, n_live_main + 3 * first, n_live_main, 3 * count); })))
             return rc;
         // ---- scatter
         t_io = c->timer_begin("evalh_part_io", s);
@@ -2027,6 +2112,133 @@ int h2hip_evaluate_h_workspace_bytes(uint32_t k, uint32_t extended_k, uint32_t n
                ? H2HIP_EINVAL
                : 0;
 }
+
+// ---- pinned part cosets ------------------------------------------------------------------------------------------------------------
+// The parts form takes every column as a polynomial of 2^k coefficients and transforms it once per part; a proving key's polynomials are
+// the same for every proof.  A pin keeps all P part cosets of such a polynomial in HBM (2^extended_k elements, part-major), built with one
+// batched coeff_to_extended_part call per polynomial (its source read P times, P outputs), and evaluate_h_parts_host reads a part where
+// the pin holds it.  The budget and its LRU clock are the pinned columns' (HALO2_HIP_COLUMN_CACHE_GB).
+static int part_cosets_pin(const void* const* polys, size_t count, uint32_t k, uint32_t ek, const uint64_t* extended_omega, const uint64_t* g_coset,
+                           const uint64_t* g_coset_inv, bool dev, hipStream_t stream) {
+    if ((count && !polys) || !extended_omega || !g_coset || !g_coset_inv || k > ek || ek > 28 || ek - k > 8) {
+        set_error("part_cosets_pin: bad argument");
+        return H2HIP_EINVAL;
+    }
+    for (size_t i = 0; i < count; i++)
+        if (!polys[i]) {
+            set_error("part_cosets_pin: null polynomial %zu", i);
+            return H2HIP_EINVAL;
+        }
+    if (check_fr(extended_omega, "extended_omega") || check_fr(g_coset, "g_coset") || check_fr(g_coset_inv, "g_coset_inv")) return H2HIP_EINVAL;
+    if (!count) return 0;
+    Entry en("h2hip_part_cosets_pin");  // evaluate_h runs on the engine's first device
+    if (en.rc) return en.rc;
+    Ctx* c = en.c;
+    hipStream_t s = dev ? stream : c->stream;
+    const Fe w = fe_from_u64x4(extended_omega), g = fe_from_u64x4(g_coset), gi = fe_from_u64x4(g_coset_inv);
+    const size_t n = (size_t)1 << k, P = (size_t)1 << (ek - k), bytes = sizeof(Fe) << ek;
+    for (size_t i = 0; i < count; i++) {
+        if (pinned_parts_lookup(c, polys[i], dev, k, ek, w, g)) continue;  // already there (and, a host key, still the same array)
+        auto old = c->pinned_parts.find(polys[i]);
+        if (old != c->pinned_parts.end()) {  // pinned for another domain: this one replaces it
+            H2_CHECK(hipDeviceSynchronize());
+            (void)hipFree(old->second.d);
+            c->pinned_parts_bytes -= old->second.bytes();
+            c->pinned_parts.erase(old);
+        }
+        bool fits;
+        if (int rc = pinned_make_room(c, bytes, &fits)) return rc;
+        if (!fits) continue;  // larger than the whole budget: left unpinned, every call stays correct
+        PinnedParts pp;
+        if (hipMalloc(&pp.d, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("part_cosets_pin: out of device memory after %zu of %zu polynomials (the rest is transformed per call)", i, count);
+            return H2HIP_ENOMEM;
+        }
+        const Fe* src = (const Fe*)polys[i];
+        int rc = 0;
+        if (!dev) {  // the coefficients cross once, into the transform staging buffer: no output may be the source of the others
+            if ((rc = c->ntt_io.ensure(n * sizeof(Fe))) == 0 &&
+                hipMemcpyAsync(c->ntt_io.p, polys[i], n * sizeof(Fe), hipMemcpyHostToDevice, s) != hipSuccess) {
+                set_error("part_cosets_pin: upload failed");
+                rc = H2HIP_EDEVICE;
+            }
+            src = (const Fe*)c->ntt_io.p;
+        }
+        std::vector<Fe*> outs(P);
+        std::vector<const Fe*> srcs(P, src);
+        std::vector<uint32_t> parts(P);
+        for (size_t p = 0; p < P; p++) outs[p] = (Fe*)pp.d + p * n, parts[p] = (uint32_t)p;
+        if (!rc) rc = ntt_part_device_batch(c, outs.data(), srcs.data(), parts.data(), P, k, ek, w, g, gi, s);
+        if (!rc && hipStreamSynchronize(s) != hipSuccess) {  // the staging buffer is free again, and the entry is complete before it is listed
+            set_error("part_cosets_pin: building the part cosets failed");
+            rc = H2HIP_EDEVICE;
+        }
+        if (rc) {
+            (void)hipDeviceSynchronize();
+            (void)hipFree(pp.d);
+            return rc;
+        }
+        pp.k = k, pp.ek = ek, pp.ext_omega = w, pp.g_coset = g, pp.device_key = dev;
+        pp.last_use = ++c->pinned_cols_tick;
+        memset(pp.sample, 0, sizeof(pp.sample));
+        if (!dev) column_sample((const uint64_t*)polys[i], n, pp.sample);
+        c->pinned_parts[polys[i]] = pp;
+        c->pinned_parts_bytes += bytes;
+    }
+    return 0;
+}
+
+int h2hip_part_cosets_pin(const uint64_t* const* polys, size_t count, uint32_t k, uint32_t extended_k, const uint64_t extended_omega[4],
+                          const uint64_t g_coset[4], const uint64_t g_coset_inv[4]) {
+    return part_cosets_pin((const void* const*)polys, count, k, extended_k, extended_omega, g_coset, g_coset_inv, false, nullptr);
+}
+
+int h2hip_part_cosets_pin_device(const void* const* d_polys, size_t count, uint32_t k, uint32_t extended_k, const uint64_t extended_omega[4],
+                                 const uint64_t g_coset[4], const uint64_t g_coset_inv[4], void* stream) {
+    return part_cosets_pin(d_polys, count, k, extended_k, extended_omega, g_coset, g_coset_inv, true, (hipStream_t)stream);
+}
+
+int h2hip_part_cosets_unpin(const void* const* polys, size_t count) {
+    if (count && !polys) return H2HIP_EINVAL;
+    {
+        TuneRead r;  // the engine lock shared, without starting the engine: nothing is pinned in one that is not running
+        if (!ctx()->ready) return 0;
+    }
+    Entry en("h2hip_part_cosets_unpin");
+    if (en.rc) return en.rc;
+    Ctx* c = en.c;
+    bool synced = false;
+    for (size_t i = 0; i < count; i++) {
+        auto it = c->pinned_parts.find(polys[i]);
+        if (it == c->pinned_parts.end()) continue;
+        if (!synced) {
+            H2_CHECK(hipDeviceSynchronize());  // a queued evaluate_h may still read the entry
+            synced = true;
+        }
+        (void)hipFree(it->second.d);
+        c->pinned_parts_bytes -= it->second.bytes();
+        c->pinned_parts.erase(it);
+    }
+    return 0;
+}
+
+int h2hip_part_cosets_pinned_info(size_t* n_polys, size_t* device_bytes) {
+    Entry en("h2hip_part_cosets_pinned_info");
+    if (en.rc) return en.rc;
+    if (n_polys) *n_polys = en.c->pinned_parts.size();
+    if (device_bytes) *device_bytes = en.c->pinned_parts_bytes;
+    return 0;
+}
+
+// test hook: what the last parts call of the calling thread did (g_parts_stats)
+int h2hip_debug_evalh_parts_stats(uint64_t out[4]) {
+    if (!out) return H2HIP_EINVAL;
+    memcpy(out, g_parts_stats, sizeof(g_parts_stats));
+    return 0;
+}
+// A/B hook: 1 = the parts form scales its unpinned columns in the transform's first-pass load, 0 = with evalh_part_scale_kernel (default)
+int h2hip_debug_evalh_part_fused(int on) { TuneWrite()->evalh_part_fused = on != 0; return 0; }
 
 int h2hip_debug_evalh_power_table_bits(const uint64_t omega[4], uint32_t log_n, uint32_t* lo_bits) {
     if (!omega || !lo_bits || log_n > 28) {

@@ -60,6 +60,16 @@ struct NttPass {
 __device__ __forceinline__ const Fe* ntt_src(const NttPass& p) { return p.srcs ? p.srcs[blockIdx.y] : p.src; }
 __device__ __forceinline__ Fe* ntt_dst(const NttPass& p) { return p.dsts ? p.dsts[blockIdx.y] : p.dst; }
 
+// The second input-scale mode of the first-pass load (the *_part_kernel instances, coeff_to_extended_part): element gi is multiplied by
+// g_p^gi = in3[gi mod 3] * extended_omega^(part * gi), the power from the EXTENDED domain's two-level table.  A kernel argument of its
+// own, so that NttPass -- and with it every kernel that does not take this mode -- stays as it is.
+struct NttPart {
+    const Fu *pow_lo, *pow_hi;  // ntt_power_table of (extended_omega, extended_k): I-form canonical
+    uint32_t pow_bits;
+    uint32_t part;              // the one transform's part ...
+    const uint32_t* parts;      // ... or, in a batch, the part of transform blockIdx.y (device array); null: `part`
+};
+
 #define NTT_THREADS 256
 #ifndef NTT2_OWN_FINAL
 #define NTT2_OWN_FINAL 0  // the same in pass 2, whose rows are contiguous: the lanes' 32-byte loads scatter and the pass measures 1 % slower (A/B builds)
@@ -189,7 +199,19 @@ __device__ __forceinline__ void dft_lds(Fu* x, const Fu* wtab, uint32_t s, uint3
     }
 }
 
-__device__ __forceinline__ Fu ntt_load(const NttPass& p, const Fe* src, uint64_t gi) {
+// PART (compile time): the load of coeff_to_extended_part.  Every element is read (in_len = n) and multiplied by g_p^gi; part * gi <
+// P * 2^k = 2^extended_k indexes the extended domain's table without a reduction.  Magnitudes: the table entries and in3 are canonical, so
+// the two products that form the power lie in [0, 1.01 r) with limbs below 2^29 -- evalh_part_scale_kernel's `g`, operand for operand --
+// and the data product, one fu_mul of a canonical E-form element as in the zeta path, leaves a fresh value below 1.01 r
+// (tests/cpp/test_ntt_part_bounds.cpp).
+template <bool PART>
+__device__ __forceinline__ Fu ntt_load(const NttPass& p, const NttPart& q, const Fe* src, uint64_t gi) {
+    if (PART) {
+        const uint32_t e = (q.parts ? q.parts[blockIdx.y] : q.part) * (uint32_t)gi;  // < 2^28
+        Fu g = fu_mul<FrUA>(q.pow_lo[e & ((1u << q.pow_bits) - 1)], q.pow_hi[e >> q.pow_bits]);
+        g = fu_mul<FrUA>(g, pick3(p.in3, (uint32_t)gi % 3u));
+        return fu_mul<FrUA>(fu_slice(src[gi]), g);
+    }
     if (p.first) {
         if (gi >= p.in_len) return fu_zero();
         Fu v = fu_slice(src[gi]);
@@ -204,7 +226,8 @@ __device__ __forceinline__ Fu ntt_load(const NttPass& p, const Fe* src, uint64_t
 
 extern __shared__ __align__(16) unsigned char ntt_lds_raw[];
 
-__global__ void __launch_bounds__(NTT_THREADS) ntt_strided_kernel(NttPass p) {
+template <bool PART>
+__device__ __forceinline__ void ntt_strided_body(const NttPass& p, const NttPart& q) {
     const Fe* src = ntt_src(p);
     Fe* dst = ntt_dst(p);
     Fu* x = reinterpret_cast<Fu*>(ntt_lds_raw);
@@ -216,7 +239,7 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_strided_kernel(NttPass p) {
     const uint64_t lo0 = (u & ((1ull << log_gpb) - 1)) << p.log_j;
     for (uint32_t idx = threadIdx.x; idx < (R << p.log_j); idx += NTT_THREADS) {
         uint32_t r = idx >> p.log_j, jj = idx & (J - 1);
-        x[lds_swz((jj << p.s) + bitrev(r, p.s))] = ntt_load(p, src, base + ((uint64_t)r << log_l) + lo0 + jj);
+        x[lds_swz((jj << p.s) + bitrev(r, p.s))] = ntt_load<PART>(p, q, src, base + ((uint64_t)r << log_l) + lo0 + jj);
     }
     __syncthreads();
     dft_lds(x, p.stage_tw, p.s, p.log_j);
@@ -228,8 +251,11 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_strided_kernel(NttPass p) {
         dst[base + ((uint64_t)k << log_l) + lo] = fu_mul_canon<FrUA>(x[lds_swz((jj << p.s) + k)], w);
     }
 }
+__global__ void __launch_bounds__(NTT_THREADS) ntt_strided_kernel(NttPass p) { ntt_strided_body<false>(p, NttPart{}); }
+__global__ void __launch_bounds__(NTT_THREADS) ntt_strided_part_kernel(NttPass p, NttPart q) { ntt_strided_body<true>(p, q); }
 
-__global__ void __launch_bounds__(NTT_THREADS) ntt_final_kernel(NttPass p) {
+template <bool PART>
+__device__ __forceinline__ void ntt_final_body(const NttPass& p, const NttPart& q) {
     const Fe* src = ntt_src(p);
     Fe* dst = ntt_dst(p);
     Fu* x = reinterpret_cast<Fu*>(ntt_lds_raw);
@@ -243,7 +269,7 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_final_kernel(NttPass p) {
             bi = (bi << p.prev_s[t]) | (v & ((1ull << p.prev_s[t]) - 1));
             v >>= p.prev_s[t];
         }
-        x[lds_swz((jj << p.s) + bitrev(r, p.s))] = ntt_load(p, src, (bi << p.s) + r);
+        x[lds_swz((jj << p.s) + bitrev(r, p.s))] = ntt_load<PART>(p, q, src, (bi << p.s) + r);
     }
     __syncthreads();
     dft_lds(x, p.stage_tw, p.s, p.log_j);
@@ -255,6 +281,8 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_final_kernel(NttPass p) {
         dst[oi] = p.out_scale ? fu_mul_canon<FrUA>(v, out_const(p, oi)) : fu_canon_fast<FrUA>(v);  // no constant: reduce directly
     }
 }
+__global__ void __launch_bounds__(NTT_THREADS) ntt_final_kernel(NttPass p) { ntt_final_body<false>(p, NttPart{}); }
+__global__ void __launch_bounds__(NTT_THREADS) ntt_final_part_kernel(NttPass p, NttPart q) { ntt_final_body<true>(p, q); }
 
 // E-form canonical Fe -> I-form canonical limbs (x * 2^5 mod r), sliced
 __host__ __device__ __forceinline__ Fu fu_i_from_fe(const Fe& x) {
@@ -359,7 +387,8 @@ __device__ __forceinline__ uint64_t xcd_group(uint32_t b, uint32_t g) {
 // row are read and written one column at a time.  Measured (FETCH_SIZE): the pass fetches 2.04 x what it consumes -- every
 // piece brings its 64-byte sector and the neighbouring column asks for it again after 16 MB have passed through the XCD's
 // L2 -- which the Infinity Cache absorbs; holding the second column's pieces in registers meanwhile cost more in spills.
-__global__ void __launch_bounds__(512, 4) ntt2_strided_kernel(NttPass p) {
+template <bool PART>
+__device__ __forceinline__ void ntt2_strided_body(const NttPass& p, const NttPart& q) {
     const Fe* src = ntt_src(p);
     Fe* dst = ntt_dst(p);
     Fu* x = reinterpret_cast<Fu*>(ntt_lds_raw);
@@ -378,7 +407,7 @@ __global__ void __launch_bounds__(512, 4) ntt2_strided_kernel(NttPass p) {
         Fu v[4], y[4];
         four([&](uint32_t m) __attribute__((always_inline)) {
             const uint64_t r = (NTT2_OWN_ROWS ? bitrev(threadIdx.x, p.s - 2) : threadIdx.x) + m * T;  // rows are a stride apart whichever lane takes them: the lane takes those of its own points
-            v[m] = ntt_load(p, src, (r << log_l) + lo);
+            v[m] = ntt_load<PART>(p, q, src, (r << log_l) + lo);
         });
         dft_col<NTT2_OWN_ROWS>(x, p.stage_tw, p.s, v, y, quarter);
         four([&](uint32_t m) __attribute__((always_inline)) {
@@ -388,6 +417,8 @@ __global__ void __launch_bounds__(512, 4) ntt2_strided_kernel(NttPass p) {
         });
     }
 }
+__global__ void __launch_bounds__(512, 4) ntt2_strided_kernel(NttPass p) { ntt2_strided_body<false>(p, NttPart{}); }
+__global__ void __launch_bounds__(512, 4) ntt2_strided_part_kernel(NttPass p, NttPart q) { ntt2_strided_body<true>(p, q); }
 
 // pass 2 of 2: contiguous blocks v0 .. v0 + J - 1 of R points; output k of block v goes to k * (N / R) + v
 __global__ void __launch_bounds__(512, 4) ntt2_final_kernel(NttPass p) {
@@ -440,9 +471,12 @@ __global__ void stage_twiddle_build_kernel(Fe omega, uint32_t shift, uint32_t co
 // n = 1: best_fft is the identity; only the fused scales apply
 __global__ void ntt_n1_kernel(NttPass p) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
-        Fu v = ntt_load(p, ntt_src(p), 0);
+        Fu v = ntt_load<false>(p, NttPart{}, ntt_src(p), 0);
         ntt_dst(p)[0] = fu_mul_canon<FrUA>(v, p.out_scale ? p.out3[0] : fu_one_i<FrUA>());
     }
+}
+__global__ void ntt_n1_part_kernel(NttPass p, NttPart q) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) ntt_dst(p)[0] = fu_mul_canon<FrUA>(ntt_load<true>(p, q, ntt_src(p), 0), fu_one_i<FrUA>());
 }
 
 __global__ void twiddle_build_kernel(Fe omega, Fu* lo, uint32_t n_lo, Fu* hi, uint32_t n_hi, uint32_t lo_bits) {
@@ -721,8 +755,9 @@ static int ntt_plan(uint32_t log_n, size_t count, uint32_t S[4], bool* two) {
 
 // The passes of `count` same-size transforms, each launched once with gridDim.y = count.  count == 1: plain pointers
 // (d_data, first_src); count > 1: h_datas / h_firsts are host arrays of device pointers.
+// pm (optional): the first pass loads in the part mode (NttPart); pm->parts holds `count` parts, sc->in3 the three zeta constants.
 static int ntt_run(Ctx* c, size_t count, Fe* const* h_datas, const Fe* const* h_firsts, const Fe& omega, uint32_t log_n, const NttScale* sc,
-                   hipStream_t s) {
+                   hipStream_t s, const NttPartMode* pm = nullptr) {
     if (log_n > FrP::S) {
         set_error("ntt: log_n=%u exceeds the 2-adicity of Fr (28)", log_n);
         return 1;
@@ -759,18 +794,26 @@ static int ntt_run(Ctx* c, size_t count, Fe* const* h_datas, const Fe* const* h_
         if (rc) return rc;
         ws = (Fe*)c->ntt_ws.p;
     }
-    // device pointer lists for a batch: [data | first source | workspace]
+    // device pointer lists for a batch: [data | first source | workspace | (part mode) the transforms' parts, two to a slot]
     Fe* const* l_data = nullptr;
     const Fe* const* l_first = nullptr;
     Fe* const* l_ws = nullptr;
+    NttPart q;
+    memset(&q, 0, sizeof(q));
+    if (pm) q.part = pm->parts[0];
     if (count > 1) {
-        rc = c->ntt_ptrs.ensure(3 * count * sizeof(void*));
+        const size_t part_slots = pm ? (count + 1) / 2 : 0;
+        rc = c->ntt_ptrs.ensure((3 * count + part_slots) * sizeof(void*));
         if (rc) return rc;
-        std::vector<const void*> h(3 * count);
+        std::vector<const void*> h(3 * count + part_slots);
         for (size_t i = 0; i < count; i++) {
             h[i] = h_datas[i];
             h[count + i] = h_firsts[i];
             h[2 * count + i] = ws ? ws + (i << log_n) : nullptr;
+        }
+        if (pm) {
+            memcpy(h.data() + 3 * count, pm->parts, count * sizeof(uint32_t));
+            q.parts = (const uint32_t*)((const void* const*)c->ntt_ptrs.p + 3 * count);
         }
         if ((rc = c->stage_h2d(c->ntt_ptrs.p, h.data(), h.size() * sizeof(void*), s))) return rc;  // through the pinned ring: `h` dies with this frame
         l_data = (Fe* const*)c->ntt_ptrs.p;
@@ -791,14 +834,34 @@ static int ntt_run(Ctx* c, size_t count, Fe* const* h_datas, const Fe* const* h_
     if (log_n == 0) {
         bind(FIRST, DATA);
         p.first = 1;
-        hipLaunchKernelGGL(ntt_n1_kernel, dim3(1, (uint32_t)count), dim3(64), 0, s, p);
+        if (pm) {  // g_p^0 = 1, but the load is the one every size takes: it reads entry 0 of both levels of the extended domain's table
+            TwiddleTable ext;
+            if ((rc = get_twiddles(c, pm->ext_omega, pm->ext_k, s, &ext))) return rc;
+            q.pow_lo = ext.lo;
+            q.pow_hi = ext.hi;
+            q.pow_bits = ext.lo_bits;
+            hipLaunchKernelGGL(ntt_n1_part_kernel, dim3(1, (uint32_t)count), dim3(64), 0, s, p, q);
+        } else
+            hipLaunchKernelGGL(ntt_n1_kernel, dim3(1, (uint32_t)count), dim3(64), 0, s, p);
         H2_CHECK(hipGetLastError());
         c->timer_end(tid, s);
         return guard.release();
     }
     TwiddleTable tw;
-    rc = get_twiddles(c, omega, log_n, s, &tw);
-    if (rc) return rc;
+    if (pm) {
+        // Both domains are brought into the cache before a pointer is kept: the insertion of a domain the cache does not hold yet may
+        // clear it (get_twiddles), so the extended domain is asked for, then this transform's, then the extended one again -- which by
+        // then is either a hit or the second entry of a fresh cache.
+        TwiddleTable ext;
+        if ((rc = get_twiddles(c, pm->ext_omega, pm->ext_k, s, &ext))) return rc;
+        if ((rc = get_twiddles(c, omega, log_n, s, &tw))) return rc;
+        if ((rc = get_twiddles(c, pm->ext_omega, pm->ext_k, s, &ext))) return rc;
+        q.pow_lo = ext.lo;
+        q.pow_hi = ext.hi;
+        q.pow_bits = ext.lo_bits;
+    } else if ((rc = get_twiddles(c, omega, log_n, s, &tw))) {
+        return rc;
+    }
     if ((rc = get_stage_twiddles(c, omega, log_n, S[0], S[P - 1], s, &tw))) return rc;  // the plans hand out at most two radices
     p.tw_lo = tw.lo;
     p.tw_hi = tw.hi;
@@ -810,6 +873,9 @@ static int ntt_run(Ctx* c, size_t count, Fe* const* h_datas, const Fe* const* h_
         H2_CHECK(hipFuncSetAttribute((const void*)ntt2_final_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 73728));
         H2_CHECK(hipFuncSetAttribute((const void*)ntt_strided_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 73728));
         H2_CHECK(hipFuncSetAttribute((const void*)ntt_final_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 73728));
+        H2_CHECK(hipFuncSetAttribute((const void*)ntt2_strided_part_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 73728));
+        H2_CHECK(hipFuncSetAttribute((const void*)ntt_strided_part_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 73728));
+        H2_CHECK(hipFuncSetAttribute((const void*)ntt_final_part_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 73728));
         g_ntt_lds_attr[c->device] = true;
     }
     if (two) {
@@ -853,7 +919,9 @@ static int ntt_run(Ctx* c, size_t count, Fe* const* h_datas, const Fe* const* h_
             bind(t == 0 ? FIRST : WS, t == 0 ? WS : DATA);
             const dim3 grid(1u << (log_n - p.s - p.log_j), (uint32_t)count), block(1u << (p.s - 2));
             const size_t lds = sizeof(Fu) << p.s;
-            if (t == 0)
+            if (t == 0 && pm)
+                hipLaunchKernelGGL(ntt2_strided_part_kernel, grid, block, lds, s, p, q);
+            else if (t == 0)
                 hipLaunchKernelGGL(ntt2_strided_kernel, grid, block, lds, s, p);
             else
                 hipLaunchKernelGGL(ntt2_final_kernel, grid, block, lds, s, p);
@@ -911,10 +979,15 @@ static int ntt_run(Ctx* c, size_t count, Fe* const* h_datas, const Fe* const* h_
             set_error("ntt: grid too large");
             return 1;
         }
-        if (final)
-            hipLaunchKernelGGL(ntt_final_kernel, dim3((uint32_t)grid, (uint32_t)count), dim3(NTT_THREADS), lds, s, p);
+        const dim3 g3((uint32_t)grid, (uint32_t)count);
+        if (t == 0 && pm && final)
+            hipLaunchKernelGGL(ntt_final_part_kernel, g3, dim3(NTT_THREADS), lds, s, p, q);
+        else if (t == 0 && pm)
+            hipLaunchKernelGGL(ntt_strided_part_kernel, g3, dim3(NTT_THREADS), lds, s, p, q);
+        else if (final)
+            hipLaunchKernelGGL(ntt_final_kernel, g3, dim3(NTT_THREADS), lds, s, p);
         else
-            hipLaunchKernelGGL(ntt_strided_kernel, dim3((uint32_t)grid, (uint32_t)count), dim3(NTT_THREADS), lds, s, p);
+            hipLaunchKernelGGL(ntt_strided_kernel, g3, dim3(NTT_THREADS), lds, s, p);
         H2_CHECK(hipGetLastError());
         log_m -= p.s;
     }
@@ -925,6 +998,27 @@ static int ntt_run(Ctx* c, size_t count, Fe* const* h_datas, const Fe* const* h_
 int ntt_device(Ctx* c, Fe* d_data, const Fe& omega, uint32_t log_n, const NttScale* sc, hipStream_t s, const Fe* d_src) {
     const Fe* first = d_src ? d_src : d_data;
     return ntt_run(c, 1, &d_data, &first, omega, log_n, sc, s);
+}
+
+// coeff_to_extended_part: transform i writes h_outs[i] = part parts[i] of coeff_to_extended(h_srcs[i]), 2^k elements both, one launch per
+// pass for as many transforms as a plain batch takes.  An output may be its own source where that source feeds no other transform.
+int ntt_part_device_batch(Ctx* c, Fe* const* h_outs, const Fe* const* h_srcs, const uint32_t* parts, size_t count, uint32_t k, uint32_t ext_k,
+                          const Fe& ext_omega, const Fe& g_coset, const Fe& g_coset_inv, hipStream_t s) {
+    if (k > ext_k || ext_k > FrP::S) {
+        set_error("coeff_to_extended_part: k = %u, extended_k = %u", k, ext_k);
+        return 1;
+    }
+    const Fe omega = fe_pow_u64<FrP>(ext_omega, (uint64_t)1 << (ext_k - k));
+    const NttScale sc = NttScale::into_coset(g_coset, g_coset_inv);  // in3 = 1, zeta, zeta^2: the part mode's load picks among them
+    size_t per = tune().ntt_batch_bytes / (2 * (sizeof(Fe) << k));
+    if (per < 1) per = 1;
+    for (size_t i = 0; i < count; i += per) {
+        const size_t m = count - i < per ? count - i : per;
+        const NttPartMode pm = {ext_omega, ext_k, parts + i};
+        int rc = ntt_run(c, m, h_outs + i, h_srcs + i, omega, k, &sc, s, &pm);
+        if (rc) return rc;
+    }
+    return 0;
 }
 
 // `count` transforms of the same size and scale, one launch per pass.  h_srcs (optional, host array): transform i reads its
@@ -952,6 +1046,72 @@ int ntt_device_batch(Ctx* c, Fe* const* h_datas, const Fe* const* h_srcs, size_t
 }
 
 }  // namespace h2
+
+// ---- coeff_to_extended_part's entry points (include/halo2hip.h): this stage's own, next to its code ----
+using namespace h2;
+
+// coeff_to_extended_part (upstream halo2's per-part conversion): what its three forms accept, checked before any device work
+static int parse_coeff_to_extended_part(bool ptrs, uint32_t k, uint32_t extended_k, const uint32_t* parts, size_t count, const uint64_t* extended_omega,
+                                        const uint64_t* g_coset, const uint64_t* g_coset_inv) {
+    if (!ptrs || !extended_omega || !g_coset || !g_coset_inv || k > extended_k || extended_k > 28) {
+        set_error("coeff_to_extended_part: bad argument");
+        return H2HIP_EINVAL;
+    }
+    for (size_t i = 0; i < count; i++)
+        if (parts[i] >> (extended_k - k)) {
+            set_error("coeff_to_extended_part: part %u of %u", parts[i], 1u << (extended_k - k));
+            return H2HIP_EINVAL;
+        }
+    if (check_fr(extended_omega, "extended_omega") || check_fr(g_coset, "g_coset") || check_fr(g_coset_inv, "g_coset_inv")) return H2HIP_EINVAL;
+    return 0;
+}
+
+extern "C" int h2hip_coeff_to_extended_part_bn254_fr_device(const void* d_a, uint32_t k, uint32_t extended_k, uint32_t part, const uint64_t extended_omega[4],
+                                                 const uint64_t g_coset[4], const uint64_t g_coset_inv[4], void* d_out, void* stream) {
+    if (int rc = parse_coeff_to_extended_part(d_a && d_out, k, extended_k, &part, 1, extended_omega, g_coset, g_coset_inv)) return rc;
+    Entry en("h2hip_coeff_to_extended_part_bn254_fr_device", d_out);
+    if (en.rc) return en.rc;
+    Fe* out = (Fe*)d_out;
+    const Fe* src = (const Fe*)d_a;
+    return ntt_part_device_batch(en.c, &out, &src, &part, 1, k, extended_k, fe_from_u64x4(extended_omega), fe_from_u64x4(g_coset),
+                                 fe_from_u64x4(g_coset_inv), (hipStream_t)stream);
+}
+
+extern "C" int h2hip_coeff_to_extended_part_bn254_fr(const uint64_t* a, uint32_t k, uint32_t extended_k, uint32_t part, const uint64_t extended_omega[4],
+                                          const uint64_t g_coset[4], const uint64_t g_coset_inv[4], uint64_t* out) {
+    if (int rc = parse_coeff_to_extended_part(a && out, k, extended_k, &part, 1, extended_omega, g_coset, g_coset_inv)) return rc;
+    Entry en("h2hip_coeff_to_extended_part_bn254_fr");
+    if (en.rc) return en.rc;
+    Ctx* c = en.c;
+    const size_t bytes = sizeof(Fe) << k;
+    if (int rc = c->ntt_io.ensure(bytes)) return rc;
+    H2_CHECK(hipMemcpyAsync(c->ntt_io.p, a, bytes, hipMemcpyHostToDevice, c->stream));
+    Fe* d = (Fe*)c->ntt_io.p;
+    const Fe* src = d;
+    if (int rc = ntt_part_device_batch(c, &d, &src, &part, 1, k, extended_k, fe_from_u64x4(extended_omega), fe_from_u64x4(g_coset),
+                                       fe_from_u64x4(g_coset_inv), c->stream))
+        return rc;
+    H2_CHECK(hipMemcpyAsync(out, c->ntt_io.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    H2_CHECK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int h2hip_coeff_to_extended_part_bn254_fr_batch_device(const void* const* d_a, void* const* d_out, const uint32_t* parts, size_t count, uint32_t k,
+                                                       uint32_t extended_k, const uint64_t extended_omega[4], const uint64_t g_coset[4],
+                                                       const uint64_t g_coset_inv[4], void* stream) {
+    if (int rc = parse_coeff_to_extended_part(!count || (d_a && d_out && parts), k, extended_k, parts, count, extended_omega, g_coset, g_coset_inv))
+        return rc;
+    for (size_t i = 0; i < count; i++)
+        if (!d_a[i] || !d_out[i]) {
+            set_error("coeff_to_extended_part_batch: null column %zu", i);
+            return H2HIP_EINVAL;
+        }
+    if (!count) return 0;
+    Entry en("h2hip_coeff_to_extended_part_bn254_fr_batch_device", d_out[0]);
+    if (en.rc) return en.rc;
+    return ntt_part_device_batch(en.c, (Fe* const*)d_out, (const Fe* const*)d_a, parts, count, k, extended_k, fe_from_u64x4(extended_omega),
+                                 fe_from_u64x4(g_coset), fe_from_u64x4(g_coset_inv), (hipStream_t)stream);
+}
 
 // test hook, needs no GPU: the passes ntt_run would take for this call
 extern "C" int h2hip_debug_ntt_plan(uint32_t log_n, size_t count, uint32_t radices[4]) {

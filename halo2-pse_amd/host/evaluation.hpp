@@ -490,6 +490,28 @@ class Evaluator {  // :182-189
         engine_check(h2hip_evaluate_h_parts_bn254(&desc, values[0].l), "h2hip_evaluate_h_parts_bn254");
     }
 
+    // The part cosets of a proving key's coefficient-form polynomials (fixed_polys, l0 / l_last / l_active_row, permutation.polys) kept in
+    // HBM for evaluate_h_parts while this object lives: the pin in the constructor, the unpin in the destructor, so an exception between
+    // the two cannot leave entries keyed by freed vectors.  A polynomial the engine does not pin (budget, memory) is transformed per call.
+    class PartCosetsPin {
+    public:
+        template <class Domain>
+        PartCosetsPin(const Domain& d, const std::vector<const std::vector<Fr>*>& polys) {
+            for (auto* c : polys)
+                if (c && c->size() == (size_t(1) << d.k)) ptrs_.push_back((*c)[0].l);
+            if (!ptrs_.empty())
+                (void)h2hip_part_cosets_pin(ptrs_.data(), ptrs_.size(), d.k, d.extended_k, d.extended_omega.l, d.g_coset.l, d.g_coset_inv.l);
+        }
+        PartCosetsPin(const PartCosetsPin&) = delete;
+        PartCosetsPin& operator=(const PartCosetsPin&) = delete;
+        ~PartCosetsPin() {
+            if (!ptrs_.empty()) (void)h2hip_part_cosets_unpin((const void* const*)ptrs_.data(), ptrs_.size());
+        }
+
+    private:
+        std::vector<const uint64_t*> ptrs_;
+    };
+
     // ProvingKey's Drop (patch 0006): release the device copies of the key's constant columns
     static void release_key_columns(const std::vector<const std::vector<Fr>*>& columns) {
         std::vector<const uint64_t*> ptrs;

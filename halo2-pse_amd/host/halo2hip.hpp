@@ -525,6 +525,16 @@ class EvaluationDomain {
         return out;
     }
 
+    // upstream halo2's coeff_to_extended_part: rows j * P + part (P = 2^(extended_k - k)) of coeff_to_extended(a), 2^k elements
+    std::vector<Fr> coeff_to_extended_part(const Polynomial<Coeff>& a, uint32_t part) const {
+        if (a.values.size() != (size_t(1) << k)) throw std::logic_error("assertion failed: a.values.len() == 1 << self.k");
+        if (part >> (extended_k - k)) throw std::logic_error("assertion failed: part < 1 << (self.extended_k - self.k)");
+        std::vector<Fr> out(size_t(1) << k);
+        engine_check(h2hip_coeff_to_extended_part_bn254_fr(a.values[0].l, k, extended_k, part, extended_omega.l, g_coset.l, g_coset_inv.l, out[0].l),
+                     "coeff_to_extended_part");
+        return out;
+    }
+
     // extended_to_coeff (poly/domain.rs:281-303)
     std::vector<Fr> extended_to_coeff(Polynomial<ExtendedLagrangeCoeff> a) const {
         if (a.values.size() != extended_len()) throw std::logic_error("assertion failed: a.values.len() == self.extended_len()");  // :282

@@ -227,6 +227,42 @@ pub fn try_coeff_to_extended_in_place<G: 'static, S: 'static>(a: &mut [G], k: u3
     unsafe { ffi::h2hip_coeff_to_extended_bn254_fr(p as *const u64, k, p, extended_k, fr_ptr(extended_omega), fr_ptr(g_coset), fr_ptr(g_coset_inv)) == 0 }
 }
 
+/// Upstream halo2's `coeff_to_extended_part`: rows `j * P + part` (P = 2^(extended_k - k)) of `coeff_to_extended(a)`; `a` and `out` hold
+/// 2^k elements each.  The coset scaling is fused into the transform's first pass.
+#[allow(clippy::too_many_arguments)]
+pub fn try_coeff_to_extended_part<G: 'static, S: 'static>(a: &[G], k: u32, extended_k: u32, part: u32, extended_omega: &S, g_coset: &S, g_coset_inv: &S, out: &mut [G]) -> bool {
+    if k > extended_k || extended_k >= usize::BITS || a.len() != 1usize << k || out.len() != 1usize << k || (part >> (extended_k - k)) != 0 {
+        return false;
+    }
+    if fft_guards::<G, S>(extended_omega, extended_k).is_none() {
+        return false;
+    }
+    unsafe {
+        ffi::h2hip_coeff_to_extended_part_bn254_fr(a.as_ptr() as *const u64, k, extended_k, part, fr_ptr(extended_omega), fr_ptr(g_coset), fr_ptr(g_coset_inv), out.as_mut_ptr() as *mut u64) == 0
+    }
+}
+
+/// Keep all P part cosets of a proving key's coefficient-form polynomials (`pk.fixed_polys`, `pk.l0` / `l_last` / `l_active_row` as
+/// polynomials, `pk.permutation.polys`; 2^k elements each) in HBM for `try_evaluate_h_parts`: idempotent, fingerprint-guarded like the
+/// pinned columns, and sharing their budget.  `false` only means the polynomials are transformed per call.  Call `part_cosets_unpin`
+/// before the `Vec`s are freed (`ProvingKey`'s `Drop`).
+pub fn try_part_cosets_pin<F: 'static, S: 'static>(polys: &[&[F]], k: u32, extended_k: u32, extended_omega: &S, g_coset: &S, g_coset_inv: &S) -> bool {
+    if !is::<F, Fr>() || !is::<S, Fr>() || polys.is_empty() || k > extended_k || extended_k >= usize::BITS || polys.iter().any(|c| c.len() != 1usize << k) {
+        return false;
+    }
+    let ptrs: Vec<*const u64> = polys.iter().map(|c| c.as_ptr() as *const u64).collect();
+    unsafe { ffi::h2hip_part_cosets_pin(ptrs.as_ptr(), ptrs.len(), k, extended_k, fr_ptr(extended_omega), fr_ptr(g_coset), fr_ptr(g_coset_inv)) == 0 }
+}
+
+/// Release the part cosets `try_part_cosets_pin` keeps (unknown pointers are ignored, other element types are a no-op).
+pub fn part_cosets_unpin<F: 'static>(polys: &[&[F]]) {
+    if !is::<F, Fr>() || polys.is_empty() {
+        return;
+    }
+    let ptrs: Vec<*const std::os::raw::c_void> = polys.iter().map(|c| c.as_ptr() as *const std::os::raw::c_void).collect();
+    unsafe { ffi::h2hip_part_cosets_unpin(ptrs.as_ptr(), ptrs.len()) };
+}
+
 /// `coeff_to_extended` for several polynomials in one pipelined call (plonk/evaluation.rs:306-323 extends every advice and
 /// instance column): `a[i]` holds 2^k coefficients, `out[i]` receives 2^extended_k evaluations.
 pub fn try_coeff_to_extended_batch<G: 'static, S: 'static>(a: &[&[G]], k: u32, out: &mut [&mut [G]], extended_k: u32, extended_omega: &S, g_coset: &S, g_coset_inv: &S) -> bool {

@@ -42,7 +42,9 @@
  * serves until the code object is ready; 2: compiled inline) and HALO2_HIP_CACHE_DIR a directory that keeps those code objects across processes
  * (files there are loaded as GPU code, keyed by a hash of their source: the directory must be writable by the prover's user only);
  * HALO2_HIP_RANDOM_MIN_N (default 2^9, read at the first call) the element count from which the host forms of h2hip_fr_random_bn254 /
- * h2hip_fr_from_bytes_wide_bn254 go to the device; below it they are a handful of draws on the calling thread, by design and not as a fallback.
+ * h2hip_fr_from_bytes_wide_bn254 go to the device; below it they are a handful of draws on the calling thread, by design and not as a fallback;
+ * HALO2_HIP_COLUMN_CACHE_GB (default 64) the HBM that h2hip_columns_pin's columns and h2hip_part_cosets_pin's part cosets may take
+ * together, least recently used entries of either kind dropped first.
  */
 #ifndef HALO2HIP_H
 #define HALO2HIP_H
@@ -179,6 +181,23 @@ int h2hip_coeff_to_extended_bn254_fr(const uint64_t* a, uint32_t k, uint64_t* ou
 /* device form: d_a holds 2^extended_k elements of which the first 2^k are the input */
 int h2hip_coeff_to_extended_bn254_fr_device(void* d_a, uint32_t k, uint32_t extended_k, const uint64_t extended_omega[4],
                                             const uint64_t g_coset[4], const uint64_t g_coset_inv[4], void* stream);
+
+/* One part of coeff_to_extended (upstream halo2's coeff_to_extended_part), 2^k elements in and out:
+ * out[j] = row j * P + part of h2hip_coeff_to_extended_bn254_fr(a): the 2^k-point transform of a[m] * g_p^m over omega = extended_omega^P,
+ * g_p = g_coset * extended_omega^part, P = 2^(extended_k - k), part < P.  Limb for limb the full conversion's rows.  The scaling by g_p^m
+ * is fused into the transform's first-pass load.  k > extended_k, extended_k > 28, part >= P or a null pointer: H2HIP_EINVAL before any
+ * device work. */
+int h2hip_coeff_to_extended_part_bn254_fr(const uint64_t* a, uint32_t k, uint32_t extended_k, uint32_t part, const uint64_t extended_omega[4],
+                                          const uint64_t g_coset[4], const uint64_t g_coset_inv[4], uint64_t* out);      /* out may equal a */
+/* device form: d_a and d_out hold 2^k elements each and may be equal */
+int h2hip_coeff_to_extended_part_bn254_fr_device(const void* d_a, uint32_t k, uint32_t extended_k, uint32_t part, const uint64_t extended_omega[4],
+                                                 const uint64_t g_coset[4], const uint64_t g_coset_inv[4], void* d_out, void* stream);
+/* count transforms in one launch per pass; d_a[i] / d_out[i] device pointers in host arrays, parts[i] the part of transform i (host array), so
+ * all P parts of one polynomial are one call with d_a[i] equal for all i.  d_out[i] may equal d_a[i] only where that source feeds no other i.
+ * count == 0 writes nothing.  The transforms run on the device that owns d_out[0]. */
+int h2hip_coeff_to_extended_part_bn254_fr_batch_device(const void* const* d_a, void* const* d_out, const uint32_t* parts, size_t count, uint32_t k,
+                                                       uint32_t extended_k, const uint64_t extended_omega[4], const uint64_t g_coset[4],
+                                                       const uint64_t g_coset_inv[4], void* stream);
 
 /* EvaluationDomain::extended_to_coeff (poly/domain.rs:281-303) without the final truncate:
  * ifft(a, extended_omega_inv, extended_k, extended_ifft_divisor) then
@@ -390,10 +409,32 @@ int h2hip_evaluate_h_parts_bn254(const h2hip_evalh_parts_desc* desc, uint64_t* v
 int h2hip_evaluate_h_parts_bn254_device(const h2hip_evalh_parts_desc* desc, void* d_values, void* stream);
 /* HBM the engine itself allocates for the columns of one evaluate_h call and, in the host-pointer forms, its copy of `values` (the
  * metadata and the slot workspace of programs with more than 256 live values come on top).  parts_form / device_form select among the
- * four entry points above.  Host only: needs no device. */
+ * four entry points above.  For the parts form this is the upper bound, reached when no part cosets are pinned (below): a pinned
+ * polynomial takes no arena column.  Host only: needs no device. */
 int h2hip_evaluate_h_workspace_bytes(uint32_t k, uint32_t extended_k, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance,
                                      uint32_t n_perm_sets, uint32_t n_perm_columns, uint32_t n_lookups, int parts_form, int device_form,
                                      size_t* bytes);
+
+/* ---- pinned part cosets: the parts form's counterpart of h2hip_columns_pin.
+ * Keep all P part cosets of each coefficient-form polynomial (2^k elements; pk.fixed_polys, pk.l0 / l_last / l_active_row as polynomials,
+ * pk.permutation.polys) in HBM, 2^extended_k elements per polynomial, part-major, keyed by the pointer and the domain.
+ * h2hip_evaluate_h_parts_bn254[_device] looks up fixed_polys, the three Lagrange polynomials and perm_polys; for a pinned one, part p is
+ * read where the pin holds it: no upload, no scaling, no transform, no arena column.  Any subset may be pinned, and results are limb for
+ * limb those of the unpinned call.
+ * Host keys behave as h2hip_columns_pin's: idempotent; 16 sampled elements are compared with the caller's memory on every use, and on a
+ * mismatch the entry is dropped and the call uploads and transforms as if nothing were pinned; HALO2_HIP_COLUMN_CACHE_GB and its LRU
+ * are shared with the pinned columns; a polynomial larger than the budget is left unpinned.  The same pointer may also be pinned with
+ * h2hip_columns_pin (elems = 2^k, for the opening calls): the two are separate entries.
+ * Device keys: the device form never waits for its kernels, so no verdict could be read back.  Instead of a guard there is a contract: the
+ * buffer stays alive and unchanged from the pin until h2hip_part_cosets_unpin.  The pin reads it on `stream` and returns when the entry
+ * is built.
+ * k <= extended_k <= 28, extended_k - k <= 8; count == 0 does nothing. */
+int h2hip_part_cosets_pin(const uint64_t* const* polys, size_t count, uint32_t k, uint32_t extended_k, const uint64_t extended_omega[4],
+                          const uint64_t g_coset[4], const uint64_t g_coset_inv[4]);
+int h2hip_part_cosets_pin_device(const void* const* d_polys, size_t count, uint32_t k, uint32_t extended_k, const uint64_t extended_omega[4],
+                                 const uint64_t g_coset[4], const uint64_t g_coset_inv[4], void* stream);
+int h2hip_part_cosets_unpin(const void* const* polys, size_t count);       /* host or device keys; unknown pointers ignored */
+int h2hip_part_cosets_pinned_info(size_t* n_polys, size_t* device_bytes);
 
 /* ---- grand products: permutation::Argument::commit (plonk/permutation/prover.rs:96-166) and lookup::Permuted::commit_product
  * (plonk/lookup/prover.rs:194-249) -- the z columns create_proof builds between the advice commits and evaluate_h ----------------

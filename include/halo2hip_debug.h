@@ -108,6 +108,13 @@ int h2hip_debug_evalh_program(const h2hip_graph* g, uint32_t* ops, size_t cap_op
 /* the split of a domain's two-level power table (omega^e = lo[e & (2^lo_bits - 1)] * hi[e >> lo_bits]) that evaluate_h's permutation
  * kernel walks: rows at or beyond 2^lo_bits take the second factor.  Builds the table when the domain has none yet; needs a GPU. */
 int h2hip_debug_evalh_power_table_bits(const uint64_t omega[4], uint32_t log_n, uint32_t* lo_bits);
+/* the last h2hip_evaluate_h_parts_bn254[_device] call of the calling thread: out[0] = columns scaled and transformed, summed over the
+ * call's parts; out[1] = columns served from pinned part cosets, summed over parts; out[2] = column bytes uploaded (host form; `values`
+ * not counted); out[3] = arena bytes taken behind the metadata */
+int h2hip_debug_evalh_parts_stats(uint64_t out[4]);
+/* A/B: 1 = the parts form scales its unpinned columns inside the transform's first-pass load (as h2hip_coeff_to_extended_part_* always
+ * does); 0 = with the scale kernel in front of a plain transform (default) */
+int h2hip_debug_evalh_part_fused(int on);
 /* opening (evaluations and combine / divide): force the tile shape, consecutive rows per thread (power of two <= 64) and threads per
  * tile (power of two <= 256), so that small inputs span many tiles; 0 restores the size-based default. */
 int h2hip_debug_set_opening_tile(uint32_t rows_per_thread, uint32_t threads_per_tile);

@@ -5,7 +5,8 @@ gate polynomials over `--advice` advice and `--fixed` fixed columns with rotatio
 `--perm` columns, `--lookups` lookups.  Columns come from the engine's on-device generator.
 
   python tools/evalh_bench.py --k 18 [--check-k 12]     (run on the GPU box)
-  python tools/evalh_bench.py --k 18 --parts            (the parts form beside the full form)
+  python tools/evalh_bench.py --k 18 --parts            (the parts form beside the full form; also with the key's part cosets pinned,
+                                                         and with the coset scaling fused into the transform's first-pass load)
   python tools/evalh_bench.py --k 12 --parts            (launch-bound: `enqueue_us`, the host time of a device-form call, for both forms)
 """
 import argparse
@@ -293,6 +294,7 @@ def bench_parts(args):
                 case[name] = [conv(t) for t in v] if isinstance(v, list) else conv(v)
         case["lookups"] = [tuple(conv(t) for t in l) for l in cols["lookups"]]
         hd = evaluator.describe_parts(case) if form == "parts" else evaluator.describe(case)
+        hd.case = case  # the host arrays themselves: a pin is keyed by their addresses
         if on_device:
             for name, v in cols.items():
                 if name != "lookups":
@@ -301,8 +303,22 @@ def bench_parts(args):
                 setattr(hd.desc, name, table([l[t] for l in cols["lookups"]]))
         return hd
 
-    def measure(form, cols):
+    def key_of(c):
+        return list(c["fixed_polys"]) + [c["l0_poly"], c["l_last_poly"], c["l_active_row_poly"]] + list(c["perm_polys"])
+
+    def parts_stats():
+        names = ("columns_transformed", "columns_from_pins", "uploaded_column_bytes", "arena_bytes")
+        return dict(zip(names, h2.evalh_parts_stats()))
+
+    def measure(form, cols, pin=False, fused=False):
+        """pin: the key's part cosets pinned for each leg (device tensors, then the host arrays); fused: the unpinned columns scaled in
+        the transform's first-pass load instead of by the scale kernel (h2hip_debug_evalh_part_fused)"""
         res = {}
+        dom = h2.EvaluationDomain.new(4, k)
+        L.h2hip_debug_evalh_part_fused(ctypes.c_int(1 if fused else 0))
+        if pin:
+            h2.part_cosets_pin(key_of(cols), dom)
+            res["pinned_info_device_form"] = h2.part_cosets_pinned_info()
         fn_dev = L.h2hip_evaluate_h_parts_bn254_device if form == "parts" else L.h2hip_evaluate_h_bn254_device
         fn_host = L.h2hip_evaluate_h_parts_bn254 if form == "parts" else L.h2hip_evaluate_h_bn254
         hd = describe(form, cols, True)
@@ -330,6 +346,9 @@ def bench_parts(args):
             torch.cuda.synchronize()
             ts.append(e0.elapsed_time(e1))
         res["gpu_ms"] = float(np.median(ts))
+        res["gpu_ms_runs"] = ts
+        if form == "parts":
+            res["stats_device_form"] = parts_stats()
         res["enqueue_us"] = enqueue_us(call)
         h2.profile_enable(True)
         h2.profile_reset()
@@ -342,7 +361,12 @@ def bench_parts(args):
             tot, cnt = h2.profile_get(name)
             res["stage_ms"][name] = tot / 3 if cnt else None  # per call: a stage runs once per part in the parts form
         # host pointers: what a patched prover's Vec<F>s cost, PCIe included
+        if pin:
+            h2.part_cosets_unpin(key_of(cols))
         hh = describe(form, cols, False)
+        if pin:
+            h2.part_cosets_pin(key_of(hh.case), dom)
+            res["pinned_info_host_form"] = h2.part_cosets_pinned_info()
         vals = host(v0).copy()
 
         def host_call():
@@ -354,8 +378,14 @@ def bench_parts(args):
         free1 = torch.cuda.mem_get_info()[0]
         host_call()
         res["engine_hbm_MiB_host_form_on_top"] = (free1 - torch.cuda.mem_get_info()[0]) / 2**20
-        res["host_ms"] = float(np.median([host_call() for _ in range(5)]))
+        res["host_ms_runs"] = [host_call() for _ in range(5)]
+        res["host_ms"] = float(np.median(res["host_ms_runs"]))
         res["host_matches_device"] = bool(np.array_equal(vals, host(result)))
+        if form == "parts":
+            res["stats_host_form"] = parts_stats()
+        if pin:
+            h2.part_cosets_unpin(key_of(hh.case))
+        L.h2hip_debug_evalh_part_fused(ctypes.c_int(0))
         n_small = args.advice + 3 * args.lookups
         n_key = args.fixed + args.perm + 3 + n_sets
         up = (n_key + n_small) * (32 << k) if form == "parts" else n_key * (32 << ek) + n_small * (32 << k)
@@ -368,6 +398,9 @@ def bench_parts(args):
     out = {"k": k, "extended_k": ek, "gates": args.gates, "advice": args.advice, "fixed": args.fixed, "perm_columns": args.perm, "perm_sets": n_sets,
            "lookups": args.lookups, "iters": args.iters}
     out["parts"], got = measure("parts", polys)
+    out["parts_fused_load"], got_f = measure("parts", polys, fused=True)
+    out["parts_pinned"], got_p = measure("parts", polys, pin=True)
+    assert torch.equal(got, got_f) and torch.equal(got, got_p), "the fused load or the pinned part cosets change the result"
     # the full form's columns: the extended cosets of the same polynomials, formed by the engine
     cosets = {}
     for name, v in polys.items():
