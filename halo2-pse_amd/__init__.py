@@ -429,6 +429,21 @@ def lookup_products(k, beta, gamma, compressed_inputs, compressed_tables, permut
     return z
 
 
+def shuffle_products(k, gamma, compressed_inputs, compressed_shuffles, blinding, blinding_factors):
+    """shuffle::Argument::commit_product's z columns (upstream PSE halo2; include/halo2hip.h states the definition), one per shuffle:
+    lists of (2^k, 4) uint64 compressed columns A, S; blinding is (count * blinding_factors, 4).  Returns the list of z columns."""
+    n = 1 << int(k)
+    a, s = _cols(compressed_inputs, n, "compressed_inputs"), _cols(compressed_shuffles, n, "compressed_shuffles")
+    count = len(a)
+    if len(s) != count:
+        raise ValueError("shuffle columns differ in count")
+    bl = _blinding(blinding, count, int(blinding_factors))
+    z = [np.zeros((n, 4), dtype=np.uint64) for _ in range(count)]
+    _check(lib().h2hip_shuffle_products_bn254(ctypes.c_uint32(k), _p(_fe(gamma)), _host_ptrs(a), _host_ptrs(s), ctypes.c_size_t(count), _p(bl),
+                                              ctypes.c_uint32(blinding_factors), _host_ptrs(z)), "h2hip_shuffle_products_bn254")
+    return z
+
+
 def batch_invert(a):
     """ff's BatchInvert on a (n, 4) uint64 array of Montgomery Fr elements: a new array of the inverses, zeros stay zero"""
     out = _u64(a, 4).copy()
@@ -522,6 +537,28 @@ def commit_permuted(params, domain, lookups, theta, blinding, blinding_factors, 
     return out
 
 
+def commit_shuffle_products(params, domain, shuffles, theta, gamma, blinding, blinding_factors, blinds, fixed=(), advice=(), instance=(),
+                            challenges=()):
+    """shuffle::Argument::commit_product (upstream PSE halo2) for every shuffle of one instance, composed as commit_permuted is:
+    compress the input and shuffle expressions with theta, build the grand product z with gamma, commit z in Lagrange form with the
+    caller's blind (blinds[j]) and take it to coefficient form, batched.  shuffles: [(input_exprs, shuffle_exprs)] expression tuples;
+    blinding as for shuffle_products.  Returns one dict per shuffle: compressed_input / compressed_shuffle, product (Lagrange),
+    product_poly (coefficients) and product_commitment (Jacobian (12,) uint64)."""
+    from .evaluation import flatten_graph, lookup_compress_graphs
+    k = int(domain.k)
+    graphs = []
+    for inp, shf in shuffles:
+        gi, gs = lookup_compress_graphs(inp, shf)
+        graphs += [flatten_graph(gi), flatten_graph(gs)]
+    comp = lookup_compress(k, graphs, theta, fixed, advice, instance, challenges)
+    z = shuffle_products(k, gamma, comp[0::2], comp[1::2], blinding, blinding_factors)
+    if len(blinds) != len(shuffles):
+        raise ValueError("blinds: expected one per shuffle")
+    polys = domain.lagrange_to_coeff_batch(z)
+    return [{"compressed_input": comp[2 * j], "compressed_shuffle": comp[2 * j + 1], "product": z[j], "product_poly": polys[j],
+             "product_commitment": params.commit_lagrange(z[j], blinds[j])} for j in range(len(shuffles))]
+
+
 # ------------------------------------------------------------------ witness check: MockProver::verify's three column-wide loops
 def _check_out(items, max_rows):
     max_rows = int(max_rows)
@@ -587,18 +624,35 @@ def check_lookups(k, compressed_inputs, compressed_tables, blinding_factors, max
     return _check_result(counts, rows, len(a), max_rows)
 
 
+def check_shuffles(k, compressed_inputs, compressed_shuffles, blinding_factors, max_rows=16):
+    """The shuffle argument's witness check on compressed columns (lookup_compress): input rows below u = 2^k - blinding_factors - 1
+    whose value occurs a different number of times among the input rows below u than among the shuffle rows below u.  Returns
+    (counts, rows) per shuffle as check_gates does."""
+    n = 1 << int(k)
+    a, s = _cols(compressed_inputs, n, "compressed_inputs"), _cols(compressed_shuffles, n, "compressed_shuffles")
+    if len(a) != len(s):
+        raise ValueError("compressed inputs and shuffles differ in count")
+    counts, rows, prow = _check_out(len(a), max_rows)
+    _check(lib().h2hip_check_shuffles_bn254(ctypes.c_uint32(k), _host_ptrs(a), _host_ptrs(s), ctypes.c_size_t(len(a)),
+                                            ctypes.c_uint32(blinding_factors), ctypes.c_uint32(max_rows), _p(counts), prow),
+           "h2hip_check_shuffles_bn254")
+    return _check_result(counts, rows, len(a), max_rows)
+
+
 def _failures(kind, counts, rows):
     return [(kind, j, int(r)) for j in range(len(counts)) for r in rows[j][:min(int(counts[j]), rows.shape[1])]]
 
 
 def verify_witness(k, gate_polys, lookups, theta, blinding_factors, permutation_columns, mapping, fixed=(), advice=(), instance=(),
-                   challenges=(), max_rows=64):
+                   challenges=(), max_rows=64, shuffles=()):
     """The three column-wide loops of MockProver::verify over one instance's columns: gate_polys are expression tuples (evaluation.py;
     every gate's polynomials in cs.gates order), lookups [(input_exprs, table_exprs)], compressed here with the caller's theta;
     permutation_columns [(kind, index)] with kind 'advice' / 'fixed' / 'instance' names the permutation argument's columns, mapping its
     Assembly's (m, 2^k, 2) uint32 pairs (None, or m = 0: no copy constraint).  Challenges and theta are the caller's: the engine draws
     nothing.  Returns the failures as ("gate", graph_index, row), ("lookup", lookup_index, row), ("permutation", column, row) tuples in
-    verify's order (dev.rs:933-938), at most the max_rows lowest rows of each constraint; an empty list is a satisfied witness."""
+    verify's order (dev.rs:933-938), at most the max_rows lowest rows of each constraint; an empty list is a satisfied witness.
+    shuffles [(input_exprs, shuffle_exprs)] (the argument of upstream PSE halo2) are compressed with the same theta and reported as
+    ("shuffle", shuffle_index, row) after the lookups; the default checks none."""
     from .evaluation import flatten_graph, gate_check_graphs, lookup_compress_graphs
     k = int(k)
     out = []
@@ -612,6 +666,13 @@ def verify_witness(k, gate_polys, lookups, theta, blinding_factors, permutation_
     if lg:
         comp = lookup_compress(k, lg, theta, fixed, advice, instance, challenges)
         out += _failures("lookup", *check_lookups(k, comp[0::2], comp[1::2], blinding_factors, max_rows))
+    sg = []
+    for inp, shf in shuffles:
+        gi, gs = lookup_compress_graphs(inp, shf)
+        sg += [flatten_graph(gi), flatten_graph(gs)]
+    if sg:
+        comp = lookup_compress(k, sg, theta, fixed, advice, instance, challenges)
+        out += _failures("shuffle", *check_shuffles(k, comp[0::2], comp[1::2], blinding_factors, max_rows))
     if mapping is not None and len(permutation_columns):
         pools = {"advice": advice, "fixed": fixed, "instance": instance}
         cols = [pools[kind][int(i)] for kind, i in permutation_columns]
@@ -1613,6 +1674,15 @@ def lookup_products_device(k, beta, gamma, d_compressed_inputs, d_compressed_tab
                                                     _stream()), "h2hip_lookup_products_bn254_device")
 
 
+def shuffle_products_device(k, gamma, d_compressed_inputs, d_compressed_shuffles, blinding, blinding_factors, d_z):
+    """device form of shuffle_products; queued on the current stream, not waited for"""
+    bl = _blinding(blinding, len(d_z), int(blinding_factors))
+    _check(lib().h2hip_shuffle_products_bn254_device(ctypes.c_uint32(k), _p(_fe(gamma)), _ptr_array(d_compressed_inputs),
+                                                     _ptr_array(d_compressed_shuffles), ctypes.c_size_t(len(d_z)), _p(bl),
+                                                     ctypes.c_uint32(blinding_factors), _ptr_array(d_z), _stream()),
+           "h2hip_shuffle_products_bn254_device")
+
+
 def batch_invert_device(d_a, n=None):
     """BatchInvert in place on a torch CUDA tensor of n x 32 B; queued on the current stream, not waited for"""
     n = d_a.numel() * d_a.element_size() // 32 if n is None else int(n)
@@ -1706,6 +1776,16 @@ def check_lookups_device(k, d_compressed_inputs, d_compressed_tables, blinding_f
     _check(lib().h2hip_check_lookups_bn254_device(ctypes.c_uint32(k), _ptr_array(d_compressed_inputs), _ptr_array(d_compressed_tables),
                                                   ctypes.c_size_t(count), ctypes.c_uint32(blinding_factors), ctypes.c_uint32(max_rows), _p(counts),
                                                   prow, _stream()), "h2hip_check_lookups_bn254_device")
+    return _check_result(counts, rows, count, max_rows)
+
+
+def check_shuffles_device(k, d_compressed_inputs, d_compressed_shuffles, blinding_factors, max_rows=16):
+    """check_shuffles over torch CUDA tensors; queued on the current stream, waited for once"""
+    count = len(d_compressed_inputs)
+    counts, rows, prow = _check_out(count, max_rows)
+    _check(lib().h2hip_check_shuffles_bn254_device(ctypes.c_uint32(k), _ptr_array(d_compressed_inputs), _ptr_array(d_compressed_shuffles),
+                                                   ctypes.c_size_t(count), ctypes.c_uint32(blinding_factors), ctypes.c_uint32(max_rows),
+                                                   _p(counts), prow, _stream()), "h2hip_check_shuffles_bn254_device")
     return _check_result(counts, rows, count, max_rows)
 
 

@@ -11,6 +11,10 @@
 //                                   never dereferenced and raises the call's flag;
 //   lookups      lookup.hip's sort of table[0 .. u) (rows >= u become all-ones keys, above every canonical value), then
 //                ck_lookup_kernel   one binary search per input row i < u on canonical keys.
+//   shuffles     (the argument of upstream PSE halo2) the same sort of input[0 .. u) and shuffle[0 .. u), then
+//                ck_shuffle_kernel  the value of input row i < u must occur equally often in both: lower and upper bound in each.
+//                Upstream's MockProver reports the mismatching positions of the two sorted lists; this is the per-row form that the
+//                counts / rows convention needs, and it fails somewhere exactly when the multisets differ.
 // The same tail follows, in the pattern of lk_count_kernel / lk_scan_kernel:
 //   ck_count_kernel    (tiles x items): the set bits of a tile of 256 words (16 384 rows);
 //   ck_scan_kernel     one workgroup per item: exclusive scan of the tile counts, the total is the item's count;
@@ -63,6 +67,36 @@ __global__ void __launch_bounds__(CK_THREADS) ck_lookup_kernel(const Fe* const* 
             else hi = mid;
         }
         bad = lo >= u || !fe_eq(fe_ld(t, lo), v);
+    }
+    const uint64_t bits = __ballot(bad);
+    if ((i & 63) == 0) mask[(size_t)j * words + (i >> 6)] = bits;
+}
+
+// first index in t[0 .. u) (canonical keys, ascending) whose key is not below v (upper: is above v)
+__device__ __forceinline__ uint64_t ck_bound(const Fe* t, uint64_t u, const Fe& v, bool upper) {
+    uint64_t lo = 0, hi = u;
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        const Fe m = fe_ld(t, mid);
+        if (upper ? !key_lt(v, m) : key_lt(m, v)) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// in[j]: the compressed input, Montgomery form; sa[j], ss[j]: the canonical keys of input and shuffle rows 0 .. u - 1 in ascending order.
+// Row i < u fails when its value's multiplicity differs between the two: four binary searches, every index below u.
+__global__ void __launch_bounds__(CK_THREADS) ck_shuffle_kernel(const Fe* const* in, const Fe* const* sa, const Fe* const* ss, uint64_t* mask,
+                                                                uint32_t words, uint32_t k, uint64_t u) {
+    const uint64_t n = 1ull << k, i = blockIdx.x * (uint64_t)CK_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t j = blockIdx.y;
+    bool bad = false;
+    if (i < u) {
+        const Fe v = fe_to_canonical<FrP>(fe_ld(in[j], i));
+        const uint64_t in_a = ck_bound(sa[j], u, v, true) - ck_bound(sa[j], u, v, false);
+        const uint64_t in_s = ck_bound(ss[j], u, v, true) - ck_bound(ss[j], u, v, false);
+        bad = in_a != in_s;
     }
     const uint64_t bits = __ballot(bad);
     if ((i & 63) == 0) mask[(size_t)j * words + (i >> 6)] = bits;
@@ -251,6 +285,47 @@ static int check_lookups_device(Ctx* c, uint32_t k, const Fe* const* in, const F
     const Fe* const* d_sorted = lookup_sort_passes(k) & 1 ? (const Fe* const*)d_k1 : (const Fe* const*)d_k0;
     hipLaunchKernelGGL(ck_lookup_kernel, dim3((uint32_t)((n + CK_THREADS - 1) / CK_THREADS), (uint32_t)count), dim3(CK_THREADS), 0, s, d_in,
                        d_sorted, w.mask, w.words, k, u);
+    H2_CHECK(hipGetLastError());
+    if ((rc = ck_tail(w, count, max_rows, s))) return rc;
+    c->timer_end(tm, s);
+    if ((rc = ck_deliver(w, count, max_rows, counts, rows, s))) return rc;
+    if ((rc = guard.release())) return rc;
+    H2_CHECK(hipStreamSynchronize(s));
+    return 0;
+}
+
+// Both columns of every shuffle go through the lookup sort in one batch (2 count columns), then one multiplicity test per input row.
+static int check_shuffles_device(Ctx* c, uint32_t k, const Fe* const* in, const Fe* const* sh, size_t count, uint32_t bf, uint32_t max_rows,
+                                 uint64_t* counts, uint32_t* rows, hipStream_t s) {
+    const uint64_t n = 1ull << k, u = n - bf - 1;
+    const size_t col_bytes = n * sizeof(Fe), cols = 2 * count;
+    // the check's own share: three pointer tables of 2 count entries (sources: inputs then shuffles; key buffers 0 and 1), then the buffers
+    Carve ex;
+    const size_t o_ptr = ex.take(3 * cols * sizeof(void*)), o_keys = ex.take_packed(2 * cols * col_bytes);
+    int rc = c->ws_acquire(s);
+    if (rc) return rc;
+    WsGuard guard(c, s);
+    CkWs w;
+    if ((rc = ck_prepare(c, k, count, max_rows, ex.total, s, &w))) return rc;
+    Fe* keys = (Fe*)(w.extra + o_keys);
+    std::vector<const void*> blob(3 * cols);
+    for (size_t j = 0; j < count; j++) {
+        blob[j] = in[j];
+        blob[count + j] = sh[j];
+    }
+    for (size_t q = 0; q < cols; q++) {
+        blob[cols + q] = keys + q * n;
+        blob[2 * cols + q] = keys + (cols + q) * n;
+    }
+    if ((rc = c->stage_h2d(w.extra + o_ptr, blob.data(), blob.size() * sizeof(void*), s))) return rc;
+    const Fe* const* d_src = (const Fe* const*)(w.extra + o_ptr);
+    Fe* const* d_k0 = (Fe* const*)(d_src + cols);
+    Fe* const* d_k1 = (Fe* const*)(d_src + 2 * cols);
+    int tm = c->timer_begin("check_shuffles", s);
+    if ((rc = lookup_sort_enqueue(d_src, d_k0, d_k1, (uint32_t)cols, k, u, s))) return rc;
+    const Fe* const* d_sorted = lookup_sort_passes(k) & 1 ? (const Fe* const*)d_k1 : (const Fe* const*)d_k0;
+    hipLaunchKernelGGL(ck_shuffle_kernel, dim3((uint32_t)((n + CK_THREADS - 1) / CK_THREADS), (uint32_t)count), dim3(CK_THREADS), 0, s, d_src,
+                       d_sorted, d_sorted + count, w.mask, w.words, k, u);
     H2_CHECK(hipGetLastError());
     if ((rc = ck_tail(w, count, max_rows, s))) return rc;
     c->timer_end(tm, s);
@@ -454,6 +529,48 @@ int h2hip_check_lookups_bn254(uint32_t k, const uint64_t* const* compressed_inpu
     }
     if (int rc = up.run(0, nullptr)) return rc;
     return check_lookups_device(c, k, d_in.data(), d_tab.data(), count, blinding_factors, max_rows, counts, rows, c->stream);
+}
+
+static int ck_shuffles_check(uint32_t k, const void* const* in, const void* const* sh, size_t count, uint32_t bf, uint32_t max_rows,
+                             const uint64_t* counts, const uint32_t* rows) {
+    const char* what = "check_shuffles";
+    if (int rc = check_k_blinding(what, k, bf)) return rc;
+    if (count > CK_MAX_LOOKUPS) {
+        set_error("%s: count %zu > %d", what, count, CK_MAX_LOOKUPS);
+        return H2HIP_EINVAL;
+    }
+    if (int rc = ck_out_check(what, k, count, max_rows, counts, rows)) return rc;
+    if (check_ptrs(what, in, count, "compressed_input") || check_ptrs(what, sh, count, "compressed_shuffle")) return H2HIP_EINVAL;
+    return 0;
+}
+
+int h2hip_check_shuffles_bn254_device(uint32_t k, const void* const* d_compressed_input, const void* const* d_compressed_shuffle, size_t count,
+                                      uint32_t blinding_factors, uint32_t max_rows, uint64_t* counts, uint32_t* rows, void* stream) {
+    if (int rc = ck_shuffles_check(k, d_compressed_input, d_compressed_shuffle, count, blinding_factors, max_rows, counts, rows)) return rc;
+    if (count == 0) return 0;
+    Entry en("h2hip_check_shuffles_bn254_device", d_compressed_input[0]);
+    if (en.rc) return en.rc;
+    return check_shuffles_device(en.c, k, (const Fe* const*)d_compressed_input, (const Fe* const*)d_compressed_shuffle, count, blinding_factors,
+                                 max_rows, counts, rows, (hipStream_t)stream);
+}
+
+int h2hip_check_shuffles_bn254(uint32_t k, const uint64_t* const* compressed_input, const uint64_t* const* compressed_shuffle, size_t count,
+                               uint32_t blinding_factors, uint32_t max_rows, uint64_t* counts, uint32_t* rows) {
+    if (int rc = ck_shuffles_check(k, (const void* const*)compressed_input, (const void* const*)compressed_shuffle, count, blinding_factors,
+                                   max_rows, counts, rows))
+        return rc;
+    if (count == 0) return 0;
+    Entry en("h2hip_check_shuffles_bn254");
+    if (en.rc) return en.rc;
+    Ctx* c = en.c;
+    std::vector<const Fe*> d_in(count), d_sh(count);
+    CkUpload up{c, c->stream, (size_t)1 << k, {}};
+    for (size_t j = 0; j < count; j++) {
+        up.want(compressed_input[j], &d_in[j]);
+        up.want(compressed_shuffle[j], &d_sh[j]);
+    }
+    if (int rc = up.run(0, nullptr)) return rc;
+    return check_shuffles_device(c, k, d_in.data(), d_sh.data(), count, blinding_factors, max_rows, counts, rows, c->stream);
 }
 
 }  // extern "C"

@@ -530,6 +530,9 @@ int permutation_products_device(Ctx* c, uint32_t k, const Fe& omega, const Fe& d
 int lookup_products_device(Ctx* c, uint32_t k, const Fe& beta, const Fe& gamma, const Fe* const* inputs_tables,
                            const Fe* const* permuted, size_t count, const uint64_t* blinding, uint32_t bf, Fe* const* z, hipStream_t s);
 int batch_invert_device(Ctx* c, Fe* d_a, uint64_t n, hipStream_t s);
+// the shuffle argument's grand products: inputs[j] = A_j, shuffles[j] = S_j
+int shuffle_products_device(Ctx* c, uint32_t k, const Fe& gamma, const Fe* const* inputs, const Fe* const* shuffles, size_t count,
+                            const uint64_t* blinding, uint32_t bf, Fe* const* z, hipStream_t s);
 // lookup.hip: commit_permuted's A' / S' of `count` lookups from device columns; waits for s once, H2HIP_ELOOKUP when an input value is
 // missing from its table
 int lookup_permute_device(Ctx* c, uint32_t k, const Fe* const* in, const Fe* const* tab, size_t count, const uint64_t* blinding, uint32_t bf,
@@ -553,7 +556,7 @@ int pinned_make_room(Ctx* c, size_t bytes, bool* fits);
 void evalh_modules_free(Ctx* c);                            // unload this device's generated kernels (release_ctx)
 void evalh_rtc_shutdown();                                  // join the compile threads (h2hip_shutdown)
 int evaluate_h_validate(const h2hip_evalh_desc* d, const void* values);
-int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, uint64_t* values, bool dev, hipStream_t s);
+int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, const h2hip_evalh_shuffles* sh, uint64_t* values, bool dev, hipStream_t s);
 // lookup compression (commit_permuted's compressed expressions) on the interpreter: validation needs no device; the run is enqueued on s
 int lookup_compress_validate(uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance, uint32_t n_challenges, const h2hip_graph* graphs,
                              size_t n_graphs);

@@ -280,6 +280,37 @@ __global__ void __launch_bounds__(256) evalh_lookup_kernel(ProgDev g, LookupDev 
     }
 }
 
+// One shuffle argument's share of a row (the shuffle argument of upstream PSE halo2: include/halo2hip.h, h2hip_evalh_shuffles).  ga and
+// gs are the input and the shuffle side's programs, a = A + gamma and s = S + gamma their values; both run on one Slots object, which
+// the host sizes for the larger plan of the two, and a is held in registers while gs runs.  Magnitudes in units of r in brackets.
+struct ShuffleDev {
+    const Fe* product;  // extended coset of z
+    const Fe *l0, *l_last, *l_active;
+};
+template <int MAXI>
+__global__ void __launch_bounds__(256) evalh_shuffle_kernel(ProgDev ga, ProgDev gs, ShuffleDev sh, ColsDev c, Fe* values, Fu* gws, uint32_t lanes) {
+    const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= lanes) return;
+    Slots<MAXI> slots(gws + tid, lanes);
+    const Fu one = fu_one_i<UF>();
+    for (uint64_t row = tid; row < (1ull << c.log_size); row += lanes) {
+        const uint32_t idx = (uint32_t)row;
+        const uint32_t r_next = rot_idx(idx, 1, c.rot_scale, c.log_size);
+        const Fu a = prog_eval(ga, c, idx, fu_zero(), slots);  // [< 15 a slot, < 32 a column or a constant]
+        const Fu s = prog_eval(gs, c, idx, fu_zero(), slots);  // [< 32]
+        const Fu z = ld_i(sh.product[idx]);                    // [32]
+        Fu v = ld_i(values[idx]);                              // [32]
+        // l_0(X) * (1 - z(X)) = 0
+        v = fold_y(v, c.y, subn(one, z), ld_i(sh.l0[idx]));                                   // [1.2] + [33 * 32 / 169 + 1 = 7.3] = [8.5]
+        // l_last(X) * (z(X)^2 - z(X)) = 0
+        v = fold_y(v, c.y, subn(fu_sqr<UF>(z), z), ld_i(sh.l_last[idx]));                     // [1.1] + [(7.1 + 32) * 32 / 169 + 1 = 8.4] = [9.5]
+        // (1 - (l_last + l_blind)) * (z(wX) s - z(X) a) = 0: the difference of the two products with one reduction
+        const Fu diff = fu_mul_sub<UF>(ld_i(sh.product[r_next]), s, z, a);                    // [(32 * 32 + 32 * 32) / 169 + 1 = 13.2]
+        v = fold_y(v, c.y, diff, ld_i(sh.l_active[idx]));                                     // [1.1] + [13.2 * 32 / 169 + 1 = 3.5] = [4.6]
+        values[idx] = out_e(v);  // [< 15]
+    }
+}
+
 // ---------------------------------------------------------------------------------------------- host side
 
 // E-form canonical element -> I-form canonical limbs (x * 2^5 mod r, sliced): how constants, challenges and the
@@ -1138,6 +1169,38 @@ int evaluate_h_validate(const h2hip_evalh_desc* d, const void* values) {
     return 0;
 }
 
+// The shuffle stage of a call whose description `d` passed evaluate_h_validate: the tables, every graph's indices, and what a shuffle
+// graph may read -- not beta, y or the previous value, which no kernel of the stage supplies.  Needs no device.
+static bool shuffle_vs_allowed(const h2hip_value_source& v) { return v.kind != H2HIP_VS_BETA && v.kind != H2HIP_VS_Y && v.kind != H2HIP_VS_PREVIOUS; }
+static int evaluate_h_shuffles_validate(const h2hip_evalh_desc* d, const h2hip_evalh_shuffles* sh) {
+    if (!sh || !sh->n_shuffles) return 0;
+    if (sh->n_shuffles > 65535) {
+        set_error("evaluate_h: %u shuffles > 65535", sh->n_shuffles);
+        return 1;
+    }
+    if (!sh->graphs) {
+        set_error("evaluate_h: null shuffle graphs");
+        return 1;
+    }
+    if (check_ptrs("evaluate_h", (const void* const*)sh->product_polys, sh->n_shuffles, "shuffle product_polys")) return 1;
+    for (size_t i = 0; i < 2 * (size_t)sh->n_shuffles; i++) {
+        const h2hip_graph& g = sh->graphs[i];
+        if (graph_validate(g, *d, "shuffle")) return 1;
+        for (uint32_t q = 0; q < g.n_calculations; q++) {
+            const h2hip_calculation& cl = g.calculations[q];
+            bool ok = shuffle_vs_allowed(cl.x);
+            if (cl.op == H2HIP_CALC_ADD || cl.op == H2HIP_CALC_SUB || cl.op == H2HIP_CALC_MUL || cl.op == H2HIP_CALC_HORNER) ok = ok && shuffle_vs_allowed(cl.y);
+            if (cl.op == H2HIP_CALC_HORNER)
+                for (uint32_t t = 0; ok && t < cl.parts_count; t++) ok = shuffle_vs_allowed(g.parts[cl.parts_offset + t]);
+            if (!ok) {
+                set_error("evaluate_h: shuffle graph %zu, calculation %u reads beta, y or the previous value", i, q);
+                return 1;
+            }
+        }
+    }
+    return 0;
+}
+
 // Everything small the kernels read (programs, constants, rotations, column-pointer tables, challenges, the power table)
 // is laid out in one host image of a metadata region at the head of the arena and uploaded with ONE copy before any kernel
 // is queued.  A copy from pageable memory is synchronous in HIP and ordered after the stream's earlier work, so a copy
@@ -1166,6 +1229,7 @@ struct MetaBlob {
 // drivers (lookup compression, the witness check's gates) build one.
 struct CallPlan {
     std::vector<const h2hip_graph*> graphs;  // the gates graph first when the call has one, then its further graphs in order
+    size_t n_lookups = 0, n_shuffles = 0;    // evaluate_h: the further graphs are n_lookups lookup graphs, then 2 n_shuffles shuffle graphs
     std::vector<Program> progs;
     std::vector<SlotPlan> plans;
     size_t largest = 0;     // the program with the most slots: its plan serves a launch that runs every graph of the call
@@ -1173,9 +1237,13 @@ struct CallPlan {
     size_t meta_bytes = 0;  // what progs_put takes of the metadata region
 };
 
-static int call_plan(const h2hip_graph* gates, const h2hip_graph* more, size_t n_more, size_t rows, CallPlan* cp) {
+static int call_plan(const h2hip_graph* gates, const h2hip_graph* more, size_t n_more, size_t rows, CallPlan* cp,
+                     const h2hip_evalh_shuffles* sh = nullptr) {
     if (gates) cp->graphs.push_back(gates);
     for (size_t i = 0; i < n_more; i++) cp->graphs.push_back(more + i);
+    cp->n_lookups = n_more;
+    cp->n_shuffles = sh ? sh->n_shuffles : 0;  // two programs per shuffle, behind the lookups'
+    for (size_t i = 0; i < 2 * cp->n_shuffles; i++) cp->graphs.push_back(sh->graphs + i);
     const size_t count = cp->graphs.size();
     cp->progs.resize(count);
     cp->plans.resize(count);
@@ -1319,16 +1387,32 @@ static int enqueue_lookup(Ctx* c, const CallPlan& cp, size_t i, const ProgDev& l
     return 0;
 }
 
+// ... and of one shuffle argument's (programs i and i + 1 of the plan): always the interpreter, on the slot plan of the program with
+// more slots -- its tier holds the other's slots too, and its global workspace, if it needs one, is within the call's largest
+static int enqueue_shuffle(Ctx* c, const CallPlan& cp, size_t i, const std::vector<ProgDev>& pds, const ShuffleDev& sd, const ColsDev& cols,
+                           Fe* d_values, hipStream_t s) {
+    const SlotPlan& sp = cp.plans[cp.progs[i].n_slots >= cp.progs[i + 1].n_slots ? i : i + 1];
+    with_tier(sp.tier, [&](auto tier, size_t lds) {
+        hipLaunchKernelGGL(evalh_shuffle_kernel<decltype(tier)::value>, dim3(sp.lanes / 256), dim3(256), lds, s, pds[i], pds[i + 1], sd, cols,
+                           d_values, (Fu*)c->evalh_slots.p, sp.lanes);
+    });
+    H2_CHECK(hipGetLastError());
+    return 0;
+}
+
 // The constraints of `rows` rows folded into `values`, in the reference's order: the custom gates (:334-360), the permutation argument
 // (:362-441) when the system has one, then the lookups (:443-518).  The plan holds the gates program and one program per lookup, pds
 // their device forms.  Every column the kernels read is in place before the call, but for two kinds the pass asks for when their turn
 // comes: perm_ready() before the permutation kernel is queued, and next_group(i, count) before the kernel of lookup i when that lookup
 // opens a group after the first -- the caller then forms the cosets of lookups i .. i + count in the group's buffers, lk[0 .. 3 count)
 // (product, permuted input, permuted table per lookup; the first group's are there from the start).  l: l0, l_last, l_active.
-template <class PermReady, class NextGroup>
+// The shuffles follow (h2hip_evalh_shuffles): programs 1 + n_lookups + 2j and + 2j + 1 of the plan are shuffle j's.  Their product cosets
+// are formed a group at a time as well, one column per shuffle in shz[0 .. sh_group); next_shuffles(first, count) is asked for every
+// group, the first included, when its turn comes.
+template <class PermReady, class NextGroup, class NextShuffles>
 static int constraint_pass(Ctx* c, const CallPlan& cp, const std::vector<ProgDev>& pds, const ColsDev& cols, const PermDev& pd,
-                           const Fe* const* l, const Fe* const* lk, size_t lk_group, Fe* d_values, size_t rows, hipStream_t s,
-                           PermReady perm_ready, NextGroup next_group) {
+                           const Fe* const* l, const Fe* const* lk, size_t lk_group, const Fe* const* shz, size_t sh_group, Fe* d_values,
+                           size_t rows, hipStream_t s, PermReady perm_ready, NextGroup next_group, NextShuffles next_shuffles) {
     int rc;
     int t_g = c->timer_begin("evalh_gates", s);
     if ((rc = enqueue_gates(c, cp, pds[0], cols, d_values, rows, s))) return rc;
@@ -1340,7 +1424,7 @@ static int constraint_pass(Ctx* c, const CallPlan& cp, const std::vector<ProgDev
         H2_CHECK(hipGetLastError());
         c->timer_end(t_p, s);
     }
-    const size_t n_lookups = cp.progs.size() - 1;
+    const size_t n_lookups = cp.n_lookups;
     int t_l = n_lookups ? c->timer_begin("evalh_lookups", s) : -1;
     for (size_t i = 0; i < n_lookups; i++) {
         const size_t gi = i % lk_group;
@@ -1349,6 +1433,16 @@ static int constraint_pass(Ctx* c, const CallPlan& cp, const std::vector<ProgDev
         if ((rc = enqueue_lookup(c, cp, i + 1, pds[i + 1], ld, cols, d_values, rows, s))) return rc;
     }
     c->timer_end(t_l, s);
+    for (size_t j = 0; j < cp.n_shuffles; j++) {
+        const size_t gj = j % sh_group;
+        if (gj == 0) {  // the group's cosets; their transforms are not the stage's own time
+            if ((rc = next_shuffles(j, cp.n_shuffles - j < sh_group ? cp.n_shuffles - j : sh_group))) return rc;
+        }
+        int t_s = c->timer_begin("evalh_shuffles", s);
+        const ShuffleDev sd = {shz[gj], l[0], l[1], l[2]};
+        if ((rc = enqueue_shuffle(c, cp, 1 + n_lookups + 2 * j, pds, sd, cols, d_values, s))) return rc;
+        c->timer_end(t_s, s);
+    }
     return 0;
 }
 
@@ -1358,6 +1452,12 @@ static size_t lookup_group(size_t n_lookups, size_t col_bytes) {
     const size_t fit = tune().evalh_lookup_group_bytes / (3 * col_bytes);
     return n_lookups <= fit ? n_lookups : fit ? fit : 1;
 }
+// ... and shuffles whose one coset is: the same bound
+static size_t shuffle_group(size_t n_shuffles, size_t col_bytes) {
+    if (!n_shuffles) return 0;
+    const size_t fit = tune().evalh_lookup_group_bytes / col_bytes;
+    return n_shuffles <= fit ? n_shuffles : fit ? fit : 1;
+}
 
 // The arena every form of evaluate_h allocates behind its metadata region: the columns the engine itself keeps resident and, in the
 // host-pointer forms, its copy of `values`.  The call paths size their arena here and h2hip_evaluate_h_workspace_bytes reports it.
@@ -1365,8 +1465,9 @@ static size_t lookup_group(size_t n_lookups, size_t col_bytes) {
 //               the cosets the call itself forms (advice, instance, one group of lookups).
 //   parts form: columns of 2^k.  One part's cosets of EVERY column (the key's too: they arrive as polynomials), one group of lookups
 //               and the part's rows of `values`; host: also the coefficient columns, uploaded once, and `values`.
+//   Both forms: one product coset per shuffle of a group (h2hip_evalh_shuffles) on top; nothing for a call without shuffles.
 static int evaluate_h_workspace_bytes(uint32_t k, uint32_t ek, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance, uint32_t n_perm_sets,
-                                      uint32_t n_perm_columns, uint32_t n_lookups, bool parts, bool dev, size_t* bytes) {
+                                      uint32_t n_perm_columns, uint32_t n_lookups, uint32_t n_shuffles, bool parts, bool dev, size_t* bytes) {
     if (!bytes) {
         set_error("evaluate_h: null argument");
         return 1;
@@ -1381,14 +1482,15 @@ static int evaluate_h_workspace_bytes(uint32_t k, uint32_t ek, uint32_t n_fixed,
         const size_t n_cols = dev ? (size_t)n_advice + n_instance + 3 * lk_group
                                   : (size_t)n_fixed + n_advice + n_instance + 3 /* l0, l_last, l_active */ + n_perm_sets + n_perm_columns +
                                         3 * lk_group /* lookup cosets, reused per group */ + 1 /* values */;
-        *bytes = n_cols * (col_bytes + 256) + 4096;
+        *bytes = (n_cols + shuffle_group(n_shuffles, col_bytes)) * (col_bytes + 256) + 4096;
         return 0;
     }
     const size_t part_bytes = align256(sizeof(Fe) << k);
     const size_t key_and_witness = (size_t)n_fixed + n_advice + n_instance + 3 + (n_perm_sets ? (size_t)n_perm_sets + n_perm_columns : 0);
-    const size_t resident = key_and_witness + 3 * lookup_group(n_lookups, part_bytes) + 1 /* the part's rows of values */;
+    const size_t resident = key_and_witness + 3 * lookup_group(n_lookups, part_bytes) + shuffle_group(n_shuffles, part_bytes) +
+                            1 /* the part's rows of values */;
     *bytes = resident * part_bytes;
-    if (!dev) *bytes += (key_and_witness + 3 * (size_t)n_lookups) * part_bytes + align256(col_bytes);
+    if (!dev) *bytes += (key_and_witness + 3 * (size_t)n_lookups + n_shuffles) * part_bytes + align256(col_bytes);
     return 0;
 }
 
@@ -1397,19 +1499,20 @@ static int evaluate_h_workspace_bytes(uint32_t k, uint32_t ek, uint32_t n_fixed,
 // dev = true:  the columns and `values` are device memory (extended cosets are used where they lie, the first NTT pass reads
 //              coefficient-form polynomials where they lie); the graphs, challenges and scalars stay host pointers; the
 //              kernels are queued on `s` and the call returns without waiting for them.
-int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, uint64_t* values, bool dev, hipStream_t s) {
+int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, const h2hip_evalh_shuffles* sh, uint64_t* values, bool dev, hipStream_t s) {
     const uint32_t k = d->k, ek = d->extended_k;
     const size_t n = (size_t)1 << k, size = (size_t)1 << ek;
     const size_t col_bytes = size * sizeof(Fe);
     int rc;
     CallPlan cp;  // programs first: their slot counts size the workspaces
-    if ((rc = call_plan(&d->custom_gates, d->lookup_graphs, d->n_lookups, size, &cp))) return rc;
+    if ((rc = call_plan(&d->custom_gates, d->lookup_graphs, d->n_lookups, size, &cp, sh))) return rc;
     // ---- device arena: [metadata | columns the engine owns]
     // lookup cosets: three buffers per lookup for as many lookups as 2 GB hold (a group); the first group's transforms join the advice /
     // instance batch, later groups reuse the buffers once the kernels of the group before are queued
-    const size_t lk_group = lookup_group(d->n_lookups, col_bytes);
+    const size_t lk_group = lookup_group(d->n_lookups, col_bytes), sh_group = shuffle_group(cp.n_shuffles, col_bytes);
     size_t arena_bytes;
-    if ((rc = evaluate_h_workspace_bytes(k, ek, d->n_fixed, d->n_advice, d->n_instance, d->n_perm_sets, d->n_perm_columns, d->n_lookups, false, dev, &arena_bytes)))
+    if ((rc = evaluate_h_workspace_bytes(k, ek, d->n_fixed, d->n_advice, d->n_instance, d->n_perm_sets, d->n_perm_columns, d->n_lookups,
+                                         (uint32_t)cp.n_shuffles, false, dev, &arena_bytes)))
         return rc;
     const size_t meta_cap = evalh_meta_cap(cp, *d, 0);
     if ((rc = c->evalh_ws.ensure(meta_cap + arena_bytes))) return rc;
@@ -1466,6 +1569,9 @@ int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, uint64_t* values, bool de
         if (!(lbuf[t] = (Fe*)ar.take(col_bytes))) bad = true;
     for (uint32_t i = 0; i < d->n_lookups; i++)
         if (!d->lookup_product_polys[i] || !d->lookup_permuted_input_polys[i] || !d->lookup_permuted_table_polys[i]) bad = true;
+    std::vector<Fe*> shbuf(sh_group, nullptr);  // one group of shuffle product cosets
+    for (size_t t = 0; t < shbuf.size(); t++)
+        if (!(shbuf[t] = (Fe*)ar.take(col_bytes))) bad = true;
     if (!mb.dev_base || bad) {
         set_error("evaluate_h: null column or arena overflow");
         return 1;
@@ -1529,7 +1635,18 @@ int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, uint64_t* values, bool de
         if (int rc_up = lookup_polys(first, count, &lsrc)) return rc_up;
         return ntt_device_batch(c, lbuf.data(), lsrc.data(), 3 * count, ext_omega, ek, &sc, s);
     };
-    if ((rc = constraint_pass(c, cp, pds, cols, pd, l, lbuf.data(), lk_group, d_values, size, s, late_uploads, next_group))) return rc;
+    auto next_shuffles = [&](size_t first, size_t count) -> int {  // every group, the first too: product polynomials -> extended cosets
+        std::vector<const Fe*> zsrc(count, nullptr);
+        for (size_t q = 0; q < count; q++) {
+            const uint64_t* h = sh->product_polys[first + q];
+            if (dev) zsrc[q] = (const Fe*)h;
+            else H2_CHECK(hipMemcpyAsync(shbuf[q], h, n * sizeof(Fe), hipMemcpyHostToDevice, s));
+        }
+        return ntt_device_batch(c, shbuf.data(), zsrc.data(), count, ext_omega, ek, &sc, s);
+    };
+    if ((rc = constraint_pass(c, cp, pds, cols, pd, l, lbuf.data(), lk_group, shbuf.data(), sh_group, d_values, size, s, late_uploads, next_group,
+                              next_shuffles)))
+        return rc;
     if ((rc = guard.release())) return rc;
     if (dev) return 0;
     // ---- download
@@ -1684,7 +1801,8 @@ static thread_local uint64_t g_parts_stats[4];
 // dev as in evaluate_h_host.  Host form: every coefficient column that is not pinned crosses once (2^k elements), `values` crosses both
 // ways once.  A key polynomial (fixed_polys, the three Lagrange polynomials, perm_polys) whose part cosets are pinned is read, for part p,
 // where the pin holds that part: no upload, no scale, no transform, no copy and no arena slot.  Any subset of them may hit.
-static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, uint64_t* values, bool dev, hipStream_t s) {
+static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, const h2hip_evalh_shuffles* sh, uint64_t* values, bool dev,
+                                 hipStream_t s) {
     const uint32_t k = d->k, ek = d->extended_k, log_p = ek - k;
     const size_t n = (size_t)1 << k, size = (size_t)1 << ek;
     const size_t part_bytes = align256(n * sizeof(Fe));
@@ -1692,7 +1810,7 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, uint64
     const h2hip_evalh_desc f = parts_as_full(*d);  // the counts, the scalars and the permutation layout, where the shared builders read them
     int rc;
     CallPlan cp;
-    if ((rc = call_plan(&d->custom_gates, d->lookup_graphs, d->n_lookups, n, &cp))) return rc;
+    if ((rc = call_plan(&d->custom_gates, d->lookup_graphs, d->n_lookups, n, &cp, sh))) return rc;
     // ---- the coefficient columns, in the order of the batch that transforms them: key and witness columns, then the lookups'
     std::vector<const uint64_t*> polys;
     for (uint32_t i = 0; i < d->n_fixed; i++) polys.push_back(d->fixed_polys[i]);
@@ -1708,7 +1826,9 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, uint64
     const size_t n_main = polys.size();  // every part transforms these; the lookups follow in groups
     for (uint32_t i = 0; i < d->n_lookups; i++)
         polys.push_back(d->lookup_product_polys[i]), polys.push_back(d->lookup_permuted_input_polys[i]), polys.push_back(d->lookup_permuted_table_polys[i]);
-    const size_t lk_group = lookup_group(d->n_lookups, part_bytes);
+    const size_t at_sh = polys.size();  // the shuffles' product polynomials, one each, follow the lookups'
+    for (size_t j = 0; j < cp.n_shuffles; j++) polys.push_back(sh->product_polys[j]);
+    const size_t lk_group = lookup_group(d->n_lookups, part_bytes), sh_group = shuffle_group(cp.n_shuffles, part_bytes);
     const Fe ext_omega = fe_from_u64x4(d->extended_omega);
     const Fe omega = fe_pow_u64<FrP>(ext_omega, (uint64_t)1 << log_p);
     const Fe g_coset = fe_from_u64x4(d->g_coset), g_coset_inv = fe_from_u64x4(d->g_coset_inv);
@@ -1731,13 +1851,15 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, uint64
         if (i < n_main) n_live_main++;
     }
     const size_t n_pinned = n_main - n_live_main;
-    const size_t n_part_cols = n_live_main + 3 * lk_group;  // arena columns of one part: the live key and witness columns, one group of lookups
+    const size_t n_first_cols = n_live_main + 3 * lk_group;   // what a part transforms at once: the live key and witness columns, one group of lookups
+    const size_t n_part_cols = n_first_cols + sh_group;      // arena columns of one part: those, and one group of shuffle products
     const size_t n_sets = n_pinned ? p_end - p_begin : 1;   // column-pointer tables: one set per part once a pinned column's address depends on it
     // ---- device arena: [metadata | (host form) the live coefficient columns | one part's cosets of them | the part's rows of values |
     //      (host form) values].  h2hip_evaluate_h_workspace_bytes is the upper bound, reached when nothing is pinned: a pinned column takes
     //      neither a coset slot nor, in the host form, a coefficient slot.
     size_t arena_bytes;
-    if ((rc = evaluate_h_workspace_bytes(k, ek, d->n_fixed, d->n_advice, d->n_instance, d->n_perm_sets, d->n_perm_columns, d->n_lookups, true, dev, &arena_bytes)))
+    if ((rc = evaluate_h_workspace_bytes(k, ek, d->n_fixed, d->n_advice, d->n_instance, d->n_perm_sets, d->n_perm_columns, d->n_lookups,
+                                         (uint32_t)cp.n_shuffles, true, dev, &arena_bytes)))
         return rc;
     arena_bytes -= n_pinned * part_bytes * (dev ? 1 : 2);
     const size_t set_bytes = (8 + 256) * ((size_t)d->n_fixed + d->n_advice + d->n_instance + d->n_perm_sets + 2 * (size_t)d->n_perm_columns + 16) +
@@ -1852,7 +1974,7 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, uint64
         g_parts_stats[1] += n_pinned;
         // ---- scale and transform: the part's cosets of the live key and witness columns and of the first group of lookups
         int t_c = c->timer_begin("evalh_cosets", s);
-        if ((rc = to_part(p, 0, 0, n_part_cols))) return rc;
+        if ((rc = to_part(p, 0, 0, n_first_cols))) return rc;
         c->timer_end(t_c, s);
         // ---- gather
         int t_io = c->timer_begin("evalh_part_io", s);
@@ -1862,8 +1984,10 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, uint64
         // ---- the pass, over the part's rows: nothing of the permutation's arrives late here, and a later group of lookups is
         //      scaled and transformed into the group's buffers as the first was
         if (d->n_perm_sets) pd.delta_start = to_i(fe_mul<FrP>(beta_zeta, fe_pow_u64<FrP>(ext_omega, p)));  // beta g_p; the kernel multiplies by omega^j
-        if ((rc = constraint_pass(c, cp, pds, cols_p[t], pd, col + at_l0, col + n_main, lk_group, d_part, n, s, [] { return 0; },
-                                  [&](size_t first, size_t count) { return to_part(p, n_live_main + 3 * first, n_live_main, 3 * count); })))
+        if ((rc = constraint_pass(c, cp, pds, cols_p[t], pd, col + at_l0, col + n_main, lk_group, part_cols.data() + n_first_cols, sh_group, d_part,
+                                  n, s, [] { return 0; },
+                                  [&](size_t first, size_t count) { return to_part(p, n_live_main + 3 * first, n_live_main, 3 * count); },
+                                  [&](size_t first, size_t count) { return to_part(p, slot[at_sh] + first, n_first_cols, count); })))
             return rc;
         // ---- scatter
         t_io = c->timer_begin("evalh_part_io", s);
@@ -2059,58 +2183,84 @@ using namespace h2;
 
 extern "C" {
 // ---- C ABI (include/halo2hip.h, evaluate_h) ----------------------------------------------------------------------------------------
-int h2hip_evaluate_h_bn254(const h2hip_evalh_desc* desc, uint64_t* values) {
+// The four calls without the suffix are the NULL case of the four with it: one validation, one code path.
+int h2hip_evaluate_h_shuffles_bn254(const h2hip_evalh_desc* desc, const h2hip_evalh_shuffles* shuffles, uint64_t* values) {
     if (!desc || !values) {
         set_error("evaluate_h: null argument");
         return H2HIP_EINVAL;
     }
-    if (evaluate_h_validate(desc, values)) return H2HIP_EINVAL;
+    if (evaluate_h_validate(desc, values) || evaluate_h_shuffles_validate(desc, shuffles)) return H2HIP_EINVAL;
     Entry en("h2hip_evaluate_h_bn254");
     if (en.rc) return en.rc;
-    return evaluate_h_host(en.c, desc, values, false, en.c->stream);
+    return evaluate_h_host(en.c, desc, shuffles, values, false, en.c->stream);
 }
+int h2hip_evaluate_h_bn254(const h2hip_evalh_desc* desc, uint64_t* values) { return h2hip_evaluate_h_shuffles_bn254(desc, nullptr, values); }
 
-int h2hip_evaluate_h_bn254_device(const h2hip_evalh_desc* desc, void* d_values, void* stream) {
+int h2hip_evaluate_h_shuffles_bn254_device(const h2hip_evalh_desc* desc, const h2hip_evalh_shuffles* shuffles, void* d_values, void* stream) {
     if (!desc || !d_values) {
         set_error("evaluate_h: null argument");
         return H2HIP_EINVAL;
     }
-    if (evaluate_h_validate(desc, d_values)) return H2HIP_EINVAL;
+    if (evaluate_h_validate(desc, d_values) || evaluate_h_shuffles_validate(desc, shuffles)) return H2HIP_EINVAL;
     Entry en("h2hip_evaluate_h_bn254_device", d_values);
     if (en.rc) return en.rc;
-    return evaluate_h_host(en.c, desc, (uint64_t*)d_values, true, (hipStream_t)stream);
+    return evaluate_h_host(en.c, desc, shuffles, (uint64_t*)d_values, true, (hipStream_t)stream);
+}
+int h2hip_evaluate_h_bn254_device(const h2hip_evalh_desc* desc, void* d_values, void* stream) {
+    return h2hip_evaluate_h_shuffles_bn254_device(desc, nullptr, d_values, stream);
 }
 
 // ---- evaluate_h one coset of the 2^k domain at a time ---------------------------------------------------------------------------------
-int h2hip_evaluate_h_parts_bn254(const h2hip_evalh_parts_desc* desc, uint64_t* values) {
+int h2hip_evaluate_h_parts_shuffles_bn254(const h2hip_evalh_parts_desc* desc, const h2hip_evalh_shuffles* shuffles, uint64_t* values) {
     if (!desc || !values) {
         set_error("evaluate_h: null argument");
         return H2HIP_EINVAL;
     }
     if (evaluate_h_parts_validate(desc, values)) return H2HIP_EINVAL;
+    {
+        const h2hip_evalh_desc f = parts_as_full(*desc);
+        if (evaluate_h_shuffles_validate(&f, shuffles)) return H2HIP_EINVAL;
+    }
     Entry en("h2hip_evaluate_h_parts_bn254");
     if (en.rc) return en.rc;
-    return evaluate_h_parts_host(en.c, desc, values, false, en.c->stream);
+    return evaluate_h_parts_host(en.c, desc, shuffles, values, false, en.c->stream);
+}
+int h2hip_evaluate_h_parts_bn254(const h2hip_evalh_parts_desc* desc, uint64_t* values) {
+    return h2hip_evaluate_h_parts_shuffles_bn254(desc, nullptr, values);
 }
 
-int h2hip_evaluate_h_parts_bn254_device(const h2hip_evalh_parts_desc* desc, void* d_values, void* stream) {
+int h2hip_evaluate_h_parts_shuffles_bn254_device(const h2hip_evalh_parts_desc* desc, const h2hip_evalh_shuffles* shuffles, void* d_values,
+                                                 void* stream) {
     if (!desc || !d_values) {
         set_error("evaluate_h: null argument");
         return H2HIP_EINVAL;
     }
     if (evaluate_h_parts_validate(desc, d_values)) return H2HIP_EINVAL;
+    {
+        const h2hip_evalh_desc f = parts_as_full(*desc);
+        if (evaluate_h_shuffles_validate(&f, shuffles)) return H2HIP_EINVAL;
+    }
     Entry en("h2hip_evaluate_h_parts_bn254_device", d_values);
     if (en.rc) return en.rc;
-    return evaluate_h_parts_host(en.c, desc, (uint64_t*)d_values, true, (hipStream_t)stream);
+    return evaluate_h_parts_host(en.c, desc, shuffles, (uint64_t*)d_values, true, (hipStream_t)stream);
+}
+int h2hip_evaluate_h_parts_bn254_device(const h2hip_evalh_parts_desc* desc, void* d_values, void* stream) {
+    return h2hip_evaluate_h_parts_shuffles_bn254_device(desc, nullptr, d_values, stream);
 }
 
+int h2hip_evaluate_h_shuffles_workspace_bytes(uint32_t k, uint32_t extended_k, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance,
+                                              uint32_t n_perm_sets, uint32_t n_perm_columns, uint32_t n_lookups, uint32_t n_shuffles,
+                                              int parts_form, int device_form, size_t* bytes) {
+    return evaluate_h_workspace_bytes(k, extended_k, n_fixed, n_advice, n_instance, n_perm_sets, n_perm_columns, n_lookups, n_shuffles,
+                                      parts_form != 0, device_form != 0, bytes)
+               ? H2HIP_EINVAL
+               : 0;
+}
 int h2hip_evaluate_h_workspace_bytes(uint32_t k, uint32_t extended_k, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance,
                                      uint32_t n_perm_sets, uint32_t n_perm_columns, uint32_t n_lookups, int parts_form, int device_form,
                                      size_t* bytes) {
-    return evaluate_h_workspace_bytes(k, extended_k, n_fixed, n_advice, n_instance, n_perm_sets, n_perm_columns, n_lookups, parts_form != 0,
-                                      device_form != 0, bytes)
-               ? H2HIP_EINVAL
-               : 0;
+    return h2hip_evaluate_h_shuffles_workspace_bytes(k, extended_k, n_fixed, n_advice, n_instance, n_perm_sets, n_perm_columns, n_lookups, 0,
+                                                     parts_form, device_form, bytes);
 }
 
 // ---- pinned part cosets ------------------------------------------------------------------------------------------------------------

@@ -6,6 +6,8 @@
 //       z[0] = last_z, z[i] = z[i-1] mv_{i-1}, blinding rows, last_z = z[u] carried into the next set;
 //   lookup::Permuted::commit_product (plonk/lookup/prover.rs:194-249): the same with
 //       lp_i = (A_i + beta)(S_i + gamma) * inv((A'_i + beta)(S'_i + gamma)), z[0] = 1;
+//   shuffle::Argument::commit_product (upstream PSE halo2, later than the reference: DESIGN.md §2): the same with
+//       sp_i = (A_i + gamma) * inv(S_i + gamma), z[0] = 1;
 //   ff::BatchInvert (prover.rs:117, lookup/prover.rs:208), where a zero stays zero.
 //
 // Plan (Grand products).  With e_0 = 1, e_i = num_{i-1} and d_i = den_i (d_u = 1), every z row i <= u is
@@ -39,8 +41,8 @@ struct ProdDesc {         // one argument (permutation set, lookup, or the array
     Fe* tile_d;
     Fe* meta;             // [0] = inv(prod d'), [1] = end value z[u] / last_z
     uint32_t* j0;
-    const Fe* const* p;   // permutation: the set's columns p_c; lookup: {A, S}
-    const Fe* const* s;   // permutation: the set's s_c; lookup: {A', S'}
+    const Fe* const* p;   // permutation: the set's columns p_c; lookup: {A, S}; shuffle: {A}
+    const Fe* const* s;   // permutation: the set's s_c; lookup: {A', S'}; shuffle: {S}
     const Fe* blind;      // blinding_factors values for rows n - b .. n - 1
     uint32_t ncols;       // columns in the set
     uint32_t col0;        // global index of the set's first column (delta^c)
@@ -61,7 +63,7 @@ struct ProdParams {
     const Fe* delta_pow;  // delta^c, c < n_columns (permutation)
 };
 
-enum { PROD_PERM = 0, PROD_LOOKUP = 1, PROD_INVERT = 2 };
+enum { PROD_PERM = 0, PROD_LOOKUP = 1, PROD_INVERT = 2, PROD_SHUFFLE = 3 };
 
 __device__ __forceinline__ Fe prod_one() { return fe_one<FrP>(); }
 __device__ __forceinline__ Fe prod_nz(const Fe& x) { return fe_is_zero(x) ? prod_one() : x; }
@@ -201,6 +203,8 @@ __global__ __launch_bounds__(PROD_THREADS) void prod_fraction_kernel(const ProdD
                             e = c ? fe_mul<FrP>(e, f) : f;
                         }
                         bw = fe_mul<FrP>(bw, omega);
+                    } else if (KIND == PROD_SHUFFLE) {
+                        e = fe_add<FrP>(fe_ld(D.p[0], t), P.gamma);
                     } else {
                         e = fe_mul<FrP>(fe_add<FrP>(fe_ld(D.p[0], t), P.beta), fe_add<FrP>(fe_ld(D.p[1], t), P.gamma));
                     }
@@ -211,6 +215,8 @@ __global__ __launch_bounds__(PROD_THREADS) void prod_fraction_kernel(const ProdD
                             Fe f = fe_add<FrP>(fe_add<FrP>(fe_ld(D.p[c], i), fe_mul<FrP>(P.beta, fe_ld(D.s[c], i))), P.gamma);
                             d = c ? fe_mul<FrP>(d, f) : f;
                         }
+                    } else if (KIND == PROD_SHUFFLE) {
+                        d = fe_add<FrP>(fe_ld(D.s[0], i), P.gamma);
                     } else {
                         d = fe_mul<FrP>(fe_add<FrP>(fe_ld(D.s[0], i), P.beta), fe_add<FrP>(fe_ld(D.s[1], i), P.gamma));
                     }
@@ -336,8 +342,8 @@ static uint32_t prod_rows_per_thread(uint64_t L, size_t n_args) {
     return R;
 }
 
-// kind: PROD_PERM / PROD_LOOKUP / PROD_INVERT.  cols / perms: host arrays of device pointers (for lookups cols[2j], cols[2j + 1] =
-// A, S and perms[2j], perms[2j + 1] = A', S' of lookup j).  n_args outputs z[a] (2^k or n elements, device).  Enqueued on s.
+// kind: PROD_PERM / PROD_LOOKUP / PROD_INVERT / PROD_SHUFFLE.  cols / perms: host arrays of device pointers (for lookups cols[2j],
+// cols[2j + 1] = A, S and perms[2j], perms[2j + 1] = A', S' of lookup j; for shuffles cols[j] = A, perms[j] = S of shuffle j).  n_args outputs z[a] (2^k or n elements, device).  Enqueued on s.
 static int products_run(Ctx* c, int kind, uint64_t n, uint64_t L, uint64_t u, const Fe& omega, const Fe& delta, const Fe& beta,
                         const Fe& gamma, const Fe* const* cols, const Fe* const* perms, uint32_t n_columns, uint32_t chunk_len,
                         size_t n_args, const uint64_t* blinding, uint32_t bf, Fe* const* z, hipStream_t s) {
@@ -356,7 +362,7 @@ static int products_run(Ctx* c, int kind, uint64_t n, uint64_t L, uint64_t u, co
     const size_t o_tile_e = arg.take(tiles * sizeof(Fe)), o_tile_d = arg.take(tiles * sizeof(Fe));
     const size_t o_meta = arg.take(2 * sizeof(Fe));
     // the blob the kernels read: descriptors, pointer tables, omega^(2^b), delta^c, blinding
-    const size_t n_ptr = kind == PROD_PERM ? 2 * (size_t)n_columns : (kind == PROD_LOOKUP ? 4 * n_args : 0);
+    const size_t n_ptr = kind == PROD_PERM ? 2 * (size_t)n_columns : kind == PROD_LOOKUP ? 4 * n_args : kind == PROD_SHUFFLE ? 2 * n_args : 0;
     const size_t n_delta = kind == PROD_PERM ? n_columns : 0;
     Carve blob;
     const size_t o_desc = blob.take(n_args * sizeof(ProdDesc));
@@ -411,6 +417,10 @@ static int products_run(Ctx* c, int kind, uint64_t n, uint64_t L, uint64_t u, co
             D.ncols = 2;
             D.p = ptr.d + 4 * a;
             D.s = ptr.d + 4 * a + 2;
+        } else if (kind == PROD_SHUFFLE) {
+            D.ncols = 1;
+            D.p = ptr.d + 2 * a;
+            D.s = ptr.d + 2 * a + 1;
         }
     }
     if (kind == PROD_PERM) {
@@ -424,6 +434,11 @@ static int products_run(Ctx* c, int kind, uint64_t n, uint64_t L, uint64_t u, co
             ptr.h[4 * a + 1] = cols[2 * a + 1];
             ptr.h[4 * a + 2] = perms[2 * a];
             ptr.h[4 * a + 3] = perms[2 * a + 1];
+        }
+    } else if (kind == PROD_SHUFFLE) {
+        for (size_t a = 0; a < n_args; a++) {
+            ptr.h[2 * a] = cols[a];
+            ptr.h[2 * a + 1] = perms[a];
         }
     }
     if ((rc = c->stage_h2d(img.d, img.h, blob.total, s))) return rc;
@@ -447,6 +462,8 @@ static int products_run(Ctx* c, int kind, uint64_t n, uint64_t L, uint64_t u, co
         hipLaunchKernelGGL(prod_fraction_kernel<PROD_PERM>, grid, dim3(PROD_THREADS), 0, s, desc.d, P);
     } else if (kind == PROD_LOOKUP) {
         hipLaunchKernelGGL(prod_fraction_kernel<PROD_LOOKUP>, grid, dim3(PROD_THREADS), 0, s, desc.d, P);
+    } else if (kind == PROD_SHUFFLE) {
+        hipLaunchKernelGGL(prod_fraction_kernel<PROD_SHUFFLE>, grid, dim3(PROD_THREADS), 0, s, desc.d, P);
     } else {
         hipLaunchKernelGGL(prod_fraction_kernel<PROD_INVERT>, grid, dim3(PROD_THREADS), 0, s, desc.d, P);
     }
@@ -476,6 +493,15 @@ int lookup_products_device(Ctx* c, uint32_t k, const Fe& beta, const Fe& gamma, 
     const uint64_t n = 1ull << k, u = n - bf - 1;
     Fe one = fe_one<FrP>();
     return products_run(c, PROD_LOOKUP, n, u + 1, u, one, one, beta, gamma, inputs_tables, permuted, 0, 1, count, blinding, bf, z, s);
+}
+
+// shuffle::Argument::commit_product: z[0] = 1, z[i] = z[i-1] (A[i-1] + gamma) inv(S[i-1] + gamma); the fraction kernel's PROD_SHUFFLE
+// branch is the only code of its own, the scans, the one inversion and the zero rule are the lookups'
+int shuffle_products_device(Ctx* c, uint32_t k, const Fe& gamma, const Fe* const* inputs, const Fe* const* shuffles, size_t count,
+                            const uint64_t* blinding, uint32_t bf, Fe* const* z, hipStream_t s) {
+    const uint64_t n = 1ull << k, u = n - bf - 1;
+    Fe one = fe_one<FrP>();
+    return products_run(c, PROD_SHUFFLE, n, u + 1, u, one, one, one, gamma, inputs, shuffles, 0, 1, count, blinding, bf, z, s);
 }
 
 int batch_invert_device(Ctx* c, Fe* d_a, uint64_t n, hipStream_t s) {
@@ -656,6 +682,67 @@ int h2hip_lookup_products_bn254(uint32_t k, const uint64_t beta[4], const uint64
     }
     rc = lookup_products_device(c, k, fe_from_u64x4(beta), fe_from_u64x4(gamma), in.data(), perm.data(), count, blinding, blinding_factors,
                                 d_z.data(), s);
+    if (rc) return rc;
+    for (size_t j = 0; j < count; j++) H2_CHECK(hipMemcpyAsync(z[j], d_z[j], bytes, hipMemcpyDeviceToHost, s));
+    H2_CHECK(hipStreamSynchronize(s));
+    return 0;
+}
+
+static int shuffle_check(uint32_t k, const uint64_t gamma[4], const void* const* a, const void* const* s, size_t count, const uint64_t* blinding,
+                         uint32_t bf, const void* const* z) {
+    const char* what = "shuffle_products";
+    if (!gamma) {
+        set_error("%s: null scalar", what);
+        return H2HIP_EINVAL;
+    }
+    if (check_fr(gamma, "gamma")) return H2HIP_EINVAL;
+    if (count > 65535) {
+        set_error("%s: count %zu > 65535", what, count);
+        return H2HIP_EINVAL;
+    }
+    if (int rc = products_check_common(what, k, bf, blinding, count)) return rc;
+    if (check_ptrs(what, a, count, "compressed_input") || check_ptrs(what, s, count, "compressed_shuffle") || check_ptrs(what, z, count, "z"))
+        return H2HIP_EINVAL;
+    return 0;
+}
+
+int h2hip_shuffle_products_bn254_device(uint32_t k, const uint64_t gamma[4], const void* const* d_compressed_input,
+                                        const void* const* d_compressed_shuffle, size_t count, const uint64_t* blinding,
+                                        uint32_t blinding_factors, void* const* d_z, void* stream) {
+    if (int rc = shuffle_check(k, gamma, d_compressed_input, d_compressed_shuffle, count, blinding, blinding_factors, (const void* const*)d_z))
+        return rc;
+    if (count == 0) return 0;
+    Entry en("h2hip_shuffle_products_bn254_device", d_z[0]);
+    if (en.rc) return en.rc;
+    return shuffle_products_device(en.c, k, fe_from_u64x4(gamma), (const Fe* const*)d_compressed_input, (const Fe* const*)d_compressed_shuffle,
+                                   count, blinding, blinding_factors, (Fe* const*)d_z, (hipStream_t)stream);
+}
+
+int h2hip_shuffle_products_bn254(uint32_t k, const uint64_t gamma[4], const uint64_t* const* compressed_input,
+                                 const uint64_t* const* compressed_shuffle, size_t count, const uint64_t* blinding, uint32_t blinding_factors,
+                                 uint64_t* const* z) {
+    if (int rc = shuffle_check(k, gamma, (const void* const*)compressed_input, (const void* const*)compressed_shuffle, count, blinding,
+                               blinding_factors, (const void* const*)z))
+        return rc;
+    if (count == 0) return 0;
+    Entry en("h2hip_shuffle_products_bn254");
+    if (en.rc) return en.rc;
+    Ctx* c = en.c;
+    hipStream_t s = c->stream;
+    const size_t n = (size_t)1 << k, bytes = n * sizeof(Fe);
+    int rc = c->prod_io.ensure(3 * count * bytes);
+    if (rc) return rc;
+    char* io = (char*)c->prod_io.p;
+    std::vector<const Fe*> in(count), sh(count);
+    std::vector<Fe*> d_z(count);
+    for (size_t j = 0; j < count; j++) {
+        in[j] = (const Fe*)(io + (3 * j) * bytes);
+        sh[j] = (const Fe*)(io + (3 * j + 1) * bytes);
+        d_z[j] = (Fe*)(io + (3 * j + 2) * bytes);
+        H2_CHECK(hipMemcpyAsync((void*)in[j], compressed_input[j], bytes, hipMemcpyHostToDevice, s));
+        H2_CHECK(hipMemcpyAsync((void*)sh[j], compressed_shuffle[j], bytes, hipMemcpyHostToDevice, s));
+    }
+    rc = shuffle_products_device(c, k, fe_from_u64x4(gamma), in.data(), sh.data(), count, blinding, blinding_factors, d_z.data(), s);
     if (rc) return rc;
     for (size_t j = 0; j < count; j++) H2_CHECK(hipMemcpyAsync(z[j], d_z[j], bytes, hipMemcpyDeviceToHost, s));
     H2_CHECK(hipStreamSynchronize(s));

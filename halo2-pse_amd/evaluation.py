@@ -6,6 +6,8 @@
   Evaluator        Evaluator::new (:221-279) from gate polynomials + lookup argument expressions, and evaluate_h
                    (:280-522) which hands the flattened description to h2hip_evaluate_h_bn254[_device]
   ValueSource / Calculation / Graph / EvalhDesc    ctypes mirrors of the h2hip_* structs;  DescHolder builds one from numpy arrays
+  EvalhShuffles / ShufflesHolder / shuffle_graphs / shuffle_required_degree    the shuffle argument of upstream PSE halo2, which is later
+                   than the reference (h2hip_evalh_shuffles; the definitions are the header's)
   EvalhPartsDesc / PartsDescHolder / Evaluator.evaluate_h_parts    the same one coset of the 2^k domain at a time, every column given
                    as a polynomial of 2^k coefficients (h2hip_evaluate_h_parts_bn254[_device])
 
@@ -154,6 +156,43 @@ def lookup_compress_graphs(input_exprs, table_exprs):
     return tuple(out)
 
 
+def shuffle_graphs(input_exprs, shuffle_exprs):
+    """The two graphs of one shuffle argument (h2hip_evalh_shuffles; upstream PSE halo2's Evaluator::new, the argument is later than the
+    reference): per side, add_expression of each expression, Horner(Constant(0), parts, Theta), then Add(that, Gamma) -- the values
+    A + gamma and S + gamma.  Returns (input graph, shuffle graph)."""
+    out = []
+    for exprs in (input_exprs, shuffle_exprs):
+        g = GraphEvaluator()
+        parts = tuple(g.add_expression(e) for e in exprs)
+        compressed = g.add_calculation((CALC_HORNER, (VS_CONSTANT, 0, 0), (VS_THETA, 0, 0), parts))
+        g.add_calculation((CALC_ADD, compressed, (VS_GAMMA, 0, 0), ()))
+        out.append(g)
+    return tuple(out)
+
+
+def expression_degree(e):
+    """Expression::degree (plonk/circuit.rs): a column query counts one, a constant or a challenge nothing"""
+    tag = e[0]
+    if tag in ('const', 'challenge'):
+        return 0
+    if tag in ('fixed', 'advice', 'instance'):
+        return 1
+    if tag in ('neg', 'scaled'):
+        return expression_degree(e[1])
+    if tag == 'sum':
+        return max(expression_degree(e[1]), expression_degree(e[2]))
+    if tag == 'prod':
+        return expression_degree(e[1]) + expression_degree(e[2])
+    raise ValueError(tag)
+
+
+def shuffle_required_degree(input_exprs, shuffle_exprs):
+    """shuffle::Argument::required_degree: 2 + max(1, the degree of every input expression, of every shuffle expression)"""
+    if len(input_exprs) != len(shuffle_exprs) or not len(input_exprs):
+        raise ValueError("a shuffle has m >= 1 input expressions and as many shuffle expressions")
+    return 2 + max([1] + [expression_degree(e) for e in list(input_exprs) + list(shuffle_exprs)])
+
+
 def gate_check_graphs(gate_polys):
     """The witness check's graphs (h2hip_check_gates_bn254): one per gate polynomial, add_expression of that polynomial alone, its value
     designated by a closing Store calculation -- so a bare query or a constant is a polynomial like any other.  None stands for the
@@ -229,8 +268,36 @@ class EvalhDesc(ctypes.Structure):
     ]
 
 
+class EvalhShuffles(ctypes.Structure):
+    """h2hip_evalh_shuffles"""
+    _fields_ = [("n_shuffles", ctypes.c_uint32), ("graphs", ctypes.c_void_p), ("product_polys", ctypes.c_void_p)]
+
+
 def _ptr(a):
     return a.ctypes.data if a is not None and a.size else None
+
+
+class ShufflesHolder:
+    """Builds an h2hip_evalh_shuffles from [(flattened input graph, flattened shuffle graph, product polynomial (2^k, 4) u64)] and keeps
+    every buffer alive; byref() of an empty list is NULL, the call without shuffles"""
+
+    def __init__(self, shuffles):
+        self.keep = []
+        s = EvalhShuffles()
+        s.n_shuffles = len(shuffles)
+        graphs = (Graph * max(1, 2 * len(shuffles)))()
+        polys = []
+        for j, (g_in, g_sh, poly) in enumerate(shuffles):
+            graphs[2 * j] = graph_struct(g_in, self.keep)
+            graphs[2 * j + 1] = graph_struct(g_sh, self.keep)
+            polys.append(np.ascontiguousarray(poly, dtype=np.uint64))
+        table = (ctypes.c_void_p * max(1, len(polys)))(*[a.ctypes.data for a in polys])
+        self.keep += [graphs, polys, table]
+        s.graphs, s.product_polys = ctypes.addressof(graphs), ctypes.addressof(table)
+        self.desc = s
+
+    def byref(self):
+        return ctypes.byref(self.desc) if self.desc.n_shuffles else None
 
 
 class DescHolder:
@@ -335,6 +402,19 @@ def evaluate_h_workspace_bytes(k, extended_k, n_fixed, n_advice, n_instance, n_p
     return out.value
 
 
+def evaluate_h_shuffles_workspace_bytes(k, extended_k, n_fixed, n_advice, n_instance, n_perm_sets, n_perm_columns, n_lookups, n_shuffles,
+                                        parts_form, device_form):
+    """evaluate_h_workspace_bytes for a call with n_shuffles shuffles (h2hip_evaluate_h_shuffles_workspace_bytes; no GPU needed)"""
+    from . import _check, lib
+    out = ctypes.c_size_t()
+    u = ctypes.c_uint32
+    _check(lib().h2hip_evaluate_h_shuffles_workspace_bytes(u(k), u(extended_k), u(n_fixed), u(n_advice), u(n_instance), u(n_perm_sets),
+                                                           u(n_perm_columns), u(n_lookups), u(n_shuffles), ctypes.c_int(bool(parts_form)),
+                                                           ctypes.c_int(bool(device_form)), ctypes.byref(out)),
+           "evaluate_h_shuffles_workspace_bytes")
+    return out.value
+
+
 def graph_struct(g, keep):
     """one flattened graph (flatten_graph dict) -> h2hip_graph; the arrays it points into are appended to `keep`"""
     c = lambda a, dt: keep.append(np.ascontiguousarray(a, dtype=dt)) or keep[-1]  # noqa: E731
@@ -362,16 +442,28 @@ GraphBuilder = GraphEvaluator  # older name used by the tests
 
 
 class Evaluator:
-    """Evaluator (evaluation.rs:182-189): custom_gates + one GraphEvaluator per lookup."""
+    """Evaluator (evaluation.rs:182-189): custom_gates + one GraphEvaluator per lookup, and (upstream PSE halo2, later than the
+    reference) a pair of GraphEvaluators per shuffle."""
 
-    def __init__(self, custom_gates, lookups):
-        self.custom_gates, self.lookups = custom_gates, lookups
+    def __init__(self, custom_gates, lookups, shuffles=()):
+        self.custom_gates, self.lookups, self.shuffles = custom_gates, lookups, list(shuffles)
 
     @classmethod
-    def new(cls, gate_polys, lookup_arguments=()):
+    def new(cls, gate_polys, lookup_arguments=(), shuffle_arguments=()):
         """Evaluator::new (:221-279).  gate_polys: every gate's polynomials in cs.gates order, flattened;
-        lookup_arguments: [(input_expressions, table_expressions)]"""
-        return cls(custom_gates_graph(list(gate_polys)), [lookup_graph(i, t) for i, t in lookup_arguments])
+        lookup_arguments: [(input_expressions, table_expressions)]; shuffle_arguments: [(input_expressions, shuffle_expressions)]"""
+        return cls(custom_gates_graph(list(gate_polys)), [lookup_graph(i, t) for i, t in lookup_arguments],
+                   [shuffle_graphs(i, s) for i, s in shuffle_arguments])
+
+    def describe_shuffles(self, case):
+        """the shuffle stage of a call: case["shuffles"], when present, holds one product polynomial (2^k, 4) u64 per shuffle of this
+        Evaluator, in order.  None: the case has no such entry and the call is the one without shuffles."""
+        polys = case.get("shuffles")
+        if polys is None:
+            return None
+        if len(polys) != len(self.shuffles):
+            raise ValueError("shuffles: expected %d product polynomials, got %d" % (len(self.shuffles), len(polys)))
+        return ShufflesHolder([(flatten_graph(gi), flatten_graph(gs), z) for (gi, gs), z in zip(self.shuffles, polys)])
 
     def describe(self, case):
         """case as for DescHolder minus `custom` and the graphs inside `lookups` (3-tuples of polynomials there)"""
@@ -400,13 +492,23 @@ class Evaluator:
             full["t_evaluations"] = t_evaluations
         h = self.describe_parts(full)
         values = np.ascontiguousarray(values, dtype=np.uint64)
+        sh = self.describe_shuffles(case)
+        if sh is not None:
+            _check(lib().h2hip_evaluate_h_parts_shuffles_bn254(h.byref(), sh.byref(), values.ctypes.data_as(ctypes.c_void_p)),
+                   "evaluate_h_parts_shuffles")
+            return values
         _check(lib().h2hip_evaluate_h_parts_bn254(h.byref(), values.ctypes.data_as(ctypes.c_void_p)), "evaluate_h_parts")
         return values
 
     def evaluate_h(self, case, values):
-        """evaluate_h for one circuit instance (:280-522): values (2^extended_k, 4) u64 is folded in place and returned"""
+        """evaluate_h for one circuit instance (:280-522): values (2^extended_k, 4) u64 is folded in place and returned.  A "shuffles"
+        entry of the case (one product polynomial per shuffle of this Evaluator) adds the shuffle stage after the lookups."""
         from . import _check, lib
         h = self.describe(case)
         values = np.ascontiguousarray(values, dtype=np.uint64)
+        sh = self.describe_shuffles(case)
+        if sh is not None:
+            _check(lib().h2hip_evaluate_h_shuffles_bn254(h.byref(), sh.byref(), values.ctypes.data_as(ctypes.c_void_p)), "evaluate_h_shuffles")
+            return values
         _check(lib().h2hip_evaluate_h_bn254(h.byref(), values.ctypes.data_as(ctypes.c_void_p)), "evaluate_h")
         return values

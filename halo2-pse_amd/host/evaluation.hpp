@@ -4,6 +4,7 @@
 //   plonk::ValueSource       evaluation.rs:37-60   (same variant order: the derived PartialOrd is (kind, a, b))
 //   plonk::Calculation       evaluation.rs:108-127
 //   plonk::GraphEvaluator    evaluation.rs:191-201, :526-706  add_rotation / add_constant / add_calculation / add_expression
+//   plonk::shuffle::Argument the shuffle argument of upstream PSE halo2 (later than the reference): required_degree, compress, commit_product
 //   plonk::Evaluator         evaluation.rs:182-189, new :221-279, evaluate_h :280-522 -> h2hip_evaluate_h_bn254, and coset by coset of the
 //                            2^k domain from coefficient-form columns (evaluate_h_parts -> h2hip_evaluate_h_parts_bn254)
 //
@@ -11,6 +12,7 @@
 // constant folding), so the flattened graph has the calculations the reference builds, in the same order.
 // There is no CPU evaluation here: evaluate_h hands the flattened description to the engine.
 #pragma once
+#include <algorithm>
 #include <memory>
 #include <tuple>
 
@@ -235,6 +237,78 @@ struct LookupArgument {
     std::vector<Expr> input_expressions, table_expressions;
 };
 
+// Expression::degree (plonk/circuit.rs): a column query counts one, a constant or a challenge nothing
+inline size_t expression_degree(const Expr& e) {
+    switch (e->kind) {
+        case Expression::Constant:
+        case Expression::Challenge: return 0;
+        case Expression::Fixed:
+        case Expression::Advice:
+        case Expression::Instance: return 1;
+        case Expression::Negated:
+        case Expression::Scaled: return expression_degree(e->a);
+        case Expression::Sum: return std::max(expression_degree(e->a), expression_degree(e->b));
+        case Expression::Product: return expression_degree(e->a) + expression_degree(e->b);
+    }
+    throw std::logic_error("unreachable");
+}
+
+// The shuffle argument of upstream PSE halo2 (plonk/shuffle.rs there; later than the reference, so include/halo2hip.h states the
+// definitions): m >= 1 input expressions and as many shuffle expressions.
+namespace shuffle {
+struct Argument {
+    std::vector<Expr> input_expressions, shuffle_expressions;
+
+    // 2 + max(1, the degree of every input expression, of every shuffle expression)
+    size_t required_degree() const {
+        if (input_expressions.empty() || input_expressions.size() != shuffle_expressions.size())
+            throw std::logic_error("shuffle: m >= 1 input expressions and as many shuffle expressions expected");
+        size_t d = 1;
+        for (const auto& e : input_expressions) d = std::max(d, expression_degree(e));
+        for (const auto& e : shuffle_expressions) d = std::max(d, expression_degree(e));
+        return 2 + d;
+    }
+
+    // one side's graph: add_expression of each expression, Horner(Constant(0), parts, Theta) -- the theta fold lookup_compress_graphs
+    // builds for a lookup -- and, for the evaluator, Add(that, Gamma) last
+    static GraphEvaluator side_graph(const std::vector<Expr>& expressions, bool add_gamma) {
+        GraphEvaluator g;
+        std::vector<ValueSource> p;
+        for (const auto& e : expressions) p.push_back(g.add_expression(e));
+        const ValueSource compressed = g.add_calculation(Calculation::Horner(ValueSource::Constant(0), p, ValueSource::Theta()));
+        if (add_gamma) g.add_calculation(Calculation::Add(compressed, ValueSource::Gamma()));
+        return g;
+    }
+    // the compression's two graphs, input side then shuffle side: their values are A and S
+    std::pair<GraphEvaluator, GraphEvaluator> compress_graphs() const {
+        return {side_graph(input_expressions, false), side_graph(shuffle_expressions, false)};
+    }
+    // the evaluator's two graphs (h2hip_evalh_shuffles): their values are A + gamma and S + gamma
+    std::pair<GraphEvaluator, GraphEvaluator> evaluator_graphs() const {
+        return {side_graph(input_expressions, true), side_graph(shuffle_expressions, true)};
+    }
+
+    using Col = poly::Polynomial<poly::LagrangeCoeff>;
+    // A and S over the n Lagrange rows (h2hip_lookup_compress_bn254)
+    std::pair<Col, Col> compress(const poly::EvaluationDomain& domain, const std::vector<const Col*>& fixed, const std::vector<const Col*>& advice,
+                                 const std::vector<const Col*>& instance, const std::vector<Fr>& challenges, const Fr& theta) const {
+        const auto g = compress_graphs();
+        const FlatGraph fi = g.first.flatten(), fs = g.second.flatten();
+        auto out = lookup_compress(domain, {fi.abi(), fs.abi()}, fixed, advice, instance, challenges, theta);
+        return {std::move(out[0]), std::move(out[1])};
+    }
+
+    // commit_product: compress, then the grand product z (h2hip_shuffle_products_bn254) with the caller's blinding_factors blinding
+    // values.  Committing z and taking it to coefficient form stay with the caller, as for the lookups' products.
+    Col commit_product(const poly::EvaluationDomain& domain, const std::vector<const Col*>& fixed, const std::vector<const Col*>& advice,
+                       const std::vector<const Col*>& instance, const std::vector<Fr>& challenges, const Fr& theta, const Fr& gamma,
+                       const std::vector<Fr>& blinding, size_t blinding_factors) const {
+        const auto c = compress(domain, fixed, advice, instance, challenges, theta);
+        return std::move(shuffle_products(domain, {&c.first}, {&c.second}, gamma, blinding, blinding_factors)[0]);
+    }
+};
+}  // namespace shuffle
+
 // the per-instance inputs of evaluate_h that are not part of the Evaluator (evaluation.rs:280-305): what the reference
 // reads from pk, the domain and the prover's committed structures.  Every vector of Fr is one polynomial.
 struct EvaluateHInputs {
@@ -252,6 +326,8 @@ struct EvaluateHInputs {
     uint32_t blinding_factors = 5;                                     // last_rotation = -(blinding_factors + 1) (:365)
     // lookups (lookup::prover::Committed): product_poly, permuted_input_poly, permuted_table_poly per lookup
     std::vector<std::array<const std::vector<Fr>*, 3>> lookups;
+    // shuffles: product_poly per shuffle, coefficient form, n each (one per shuffle of the Evaluator)
+    std::vector<const std::vector<Fr>*> shuffles;
 };
 
 // evaluate_h_parts' inputs: EvaluateHInputs with every column a polynomial of n coefficients -- pk.fixed_polys, pk.l0 / l_last /
@@ -268,6 +344,7 @@ struct EvaluateHPartsInputs {
     uint32_t cs_degree = 3;
     uint32_t blinding_factors = 5;
     std::vector<std::array<const std::vector<Fr>*, 3>> lookups;
+    std::vector<const std::vector<Fr>*> shuffles;  // product_poly per shuffle
     uint32_t part_begin = 0, part_count = 0;  // the parts (cosets of the 2^k domain) to compute; 0, 0 = all 2^(extended_k - k)
     bool divide_by_vanishing_poly = false;    // the last instance's call: the rows leave multiplied by domain->t_evaluations
 };
@@ -302,9 +379,33 @@ class Evaluator {  // :182-189
   public:
     GraphEvaluator custom_gates;
     std::vector<GraphEvaluator> lookups;
+    std::vector<std::pair<GraphEvaluator, GraphEvaluator>> shuffles;  // upstream PSE halo2's: input side, shuffle side per shuffle
+
+    // the shuffles' graphs and product polynomials as h2hip_evalh_shuffles; owns what the struct points into
+    struct ShufflesAbi {
+        std::vector<FlatGraph> flat;
+        std::vector<h2hip_graph> graphs;
+        std::vector<const uint64_t*> polys;
+        h2hip_evalh_shuffles abi;
+        const h2hip_evalh_shuffles* ptr() const { return abi.n_shuffles ? &abi : nullptr; }
+    };
+    void shuffles_abi(const std::vector<const std::vector<Fr>*>& product_polys, size_t n, ShufflesAbi& out) const {
+        if (product_polys.size() != shuffles.size()) throw std::logic_error("evaluate_h: one product polynomial per shuffle expected");
+        for (size_t j = 0; j < shuffles.size(); j++) {
+            if (!product_polys[j] || product_polys[j]->size() != n) throw std::logic_error("evaluate_h: polynomial of the wrong length");
+            out.flat.push_back(shuffles[j].first.flatten());
+            out.flat.push_back(shuffles[j].second.flatten());
+            out.polys.push_back(product_polys[j]->data()->l);
+        }
+        for (const auto& f : out.flat) out.graphs.push_back(f.abi());
+        out.abi.n_shuffles = (uint32_t)shuffles.size();
+        out.abi.graphs = out.graphs.data();
+        out.abi.product_polys = out.polys.data();
+    }
 
     // Evaluator::new (:221-279): gate_polys = cs.gates.iter().flat_map(|gate| gate.polynomials()), lookups = cs.lookups
-    static Evaluator create(const std::vector<Expr>& gate_polys, const std::vector<LookupArgument>& lookup_arguments) {
+    static Evaluator create(const std::vector<Expr>& gate_polys, const std::vector<LookupArgument>& lookup_arguments,
+                            const std::vector<shuffle::Argument>& shuffle_arguments = {}) {
         Evaluator ev;
         std::vector<ValueSource> parts;
         for (const auto& poly : gate_polys) parts.push_back(ev.custom_gates.add_expression(poly));
@@ -323,6 +424,7 @@ class Evaluator {  // :182-189
             graph.add_calculation(Calculation::Mul(lc, right_gamma));
             ev.lookups.push_back(std::move(graph));
         }
+        for (const auto& sh : shuffle_arguments) ev.shuffles.push_back(sh.evaluator_graphs());
         return ev;
     }
 
@@ -407,7 +509,9 @@ class Evaluator {  // :182-189
             key.push_back(desc.l_active_row);
             (void)h2hip_columns_pin(key.data(), key.size(), size);
         }
-        engine_check(h2hip_evaluate_h_bn254(&desc, values[0].l), "h2hip_evaluate_h_bn254");
+        ShufflesAbi sh;
+        shuffles_abi(in.shuffles, n, sh);
+        engine_check(h2hip_evaluate_h_shuffles_bn254(&desc, sh.ptr(), values[0].l), "h2hip_evaluate_h_bn254");
     }
 
     // the same one coset of the 2^k domain at a time (h2hip_evaluate_h_parts_bn254): rows of `values` outside the parts asked for are
@@ -487,7 +591,9 @@ class Evaluator {  // :182-189
         desc.part_begin = in.part_begin;
         desc.part_count = in.part_count;
         desc.t_evaluations = in.divide_by_vanishing_poly ? d.t_evaluations[0].l : nullptr;
-        engine_check(h2hip_evaluate_h_parts_bn254(&desc, values[0].l), "h2hip_evaluate_h_parts_bn254");
+        ShufflesAbi sh;
+        shuffles_abi(in.shuffles, n, sh);
+        engine_check(h2hip_evaluate_h_parts_shuffles_bn254(&desc, sh.ptr(), values[0].l), "h2hip_evaluate_h_parts_bn254");
     }
 
     // The part cosets of a proving key's coefficient-form polynomials (fixed_polys, l0 / l_last / l_active_row, permutation.polys) kept in

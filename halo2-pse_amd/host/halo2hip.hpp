@@ -807,6 +807,30 @@ inline std::vector<poly::Polynomial<poly::LagrangeCoeff>> lookup_products(
     return z;
 }
 
+// The shuffle argument's z columns (shuffle::Argument::commit_product of upstream PSE halo2, which is later than the reference:
+// include/halo2hip.h states the definition), one per shuffle: inputs / shuffles are the compressed expressions A, S
+inline std::vector<poly::Polynomial<poly::LagrangeCoeff>> shuffle_products(
+    const poly::EvaluationDomain& domain, const std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>& inputs,
+    const std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>& shuffles, const Fr& gamma, const std::vector<Fr>& blinding,
+    size_t blinding_factors) {
+    const size_t count = inputs.size();
+    if (shuffles.size() != count) throw std::logic_error("shuffle columns differ in count");
+    if (blinding.size() != count * blinding_factors) throw std::logic_error("blinding: count * blinding_factors values expected");
+    std::vector<const uint64_t*> a, s;
+    for (size_t j = 0; j < count; j++) {
+        if (inputs[j]->len() != domain.n || shuffles[j]->len() != domain.n) throw std::logic_error("column length != n");
+        a.push_back(inputs[j]->values[0].l);
+        s.push_back(shuffles[j]->values[0].l);
+    }
+    std::vector<poly::Polynomial<poly::LagrangeCoeff>> z(count, poly::Polynomial<poly::LagrangeCoeff>{std::vector<Fr>(domain.n)});
+    std::vector<uint64_t*> zp;
+    for (auto& col : z) zp.push_back(col.values[0].l);
+    engine_check(h2hip_shuffle_products_bn254(domain.k, gamma.l, a.data(), s.data(), count, blinding.empty() ? nullptr : blinding[0].l,
+                                              uint32_t(blinding_factors), zp.data()),
+                 "shuffle_products");
+    return z;
+}
+
 // lookup::Argument::commit_permuted's compression (plonk/lookup/prover.rs:90-115): out[g] = graphs[g] over the n Lagrange rows.  Each
 // graph is one side of a lookup, add_expression of its expressions then Horner(Constant(0), parts, Theta) (evaluation.hpp
 // lookup_compress_graphs builds them); fixed / advice / instance are the Lagrange columns the graphs index.
@@ -1016,7 +1040,7 @@ inline ProvingKeyColumns keygen_pk(const poly::EvaluationDomain& domain, const s
 namespace dev {
 
 struct VerifyFailure {
-    enum Kind { Gate, Lookup, Permutation } kind;  // index: the gate polynomial (graph), the lookup, the permutation column
+    enum Kind { Gate, Lookup, Permutation, Shuffle } kind;  // index: the gate polynomial (graph), the lookup, the permutation column, the shuffle
     size_t index;
     uint32_t row;
     bool operator==(const VerifyFailure& o) const { return kind == o.kind && index == o.index && row == o.row; }
@@ -1030,11 +1054,13 @@ struct Columns {
 // gate_graphs: one graph per gate polynomial (evaluation.hpp gate_check_graphs); lookup_graphs: input side then table side of every lookup
 // (evaluation.hpp lookup_compress_graphs), compressed with theta; permutation_columns: the argument's columns, resolved, with their
 // assembly (nullptr: no copy constraint).  Failures in verify's order (dev.rs:933-938): gates, lookups, permutation; of each
-// constraint at most its max_rows lowest rows.  An empty vector is a satisfied witness.
+// constraint at most its max_rows lowest rows.  An empty vector is a satisfied witness.  shuffle_graphs: input side then shuffle side of
+// every shuffle (the argument of upstream PSE halo2; the same compression graphs), reported after the lookups; none by default.
 inline std::vector<VerifyFailure> verify(const poly::EvaluationDomain& domain, const Columns& cols, const std::vector<h2hip_graph>& gate_graphs,
                                          const std::vector<h2hip_graph>& lookup_graphs, const Fr& theta, size_t blinding_factors,
                                          const std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>& permutation_columns,
-                                         const plonk::permutation::keygen::Assembly* assembly, uint32_t max_rows = 64) {
+                                         const plonk::permutation::keygen::Assembly* assembly, uint32_t max_rows = 64,
+                                         const std::vector<h2hip_graph>& shuffle_graphs = {}) {
     auto ptrs = [&](const std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>& cs) {
         std::vector<const uint64_t*> p;
         for (auto* c : cs) {
@@ -1076,6 +1102,20 @@ inline std::vector<VerifyFailure> verify(const poly::EvaluationDomain& domain, c
                                                rows.data()),
                      "check_lookups");
         collect(VerifyFailure::Lookup);
+    }
+    if (!shuffle_graphs.empty()) {
+        if (shuffle_graphs.size() % 2) throw std::logic_error("shuffle_graphs: an input and a shuffle graph per shuffle expected");
+        const auto comp = plonk::lookup_compress(domain, shuffle_graphs, cols.fixed, cols.advice, cols.instance, cols.challenges, theta);
+        std::vector<const uint64_t*> in, sh;
+        for (size_t j = 0; j < comp.size(); j += 2) {
+            in.push_back(comp[j].values[0].l);
+            sh.push_back(comp[j + 1].values[0].l);
+        }
+        prepare(in.size());
+        engine_check(h2hip_check_shuffles_bn254(domain.k, in.data(), sh.data(), in.size(), uint32_t(blinding_factors), max_rows, counts.data(),
+                                                rows.data()),
+                     "check_shuffles");
+        collect(VerifyFailure::Shuffle);
     }
     if (assembly && !permutation_columns.empty()) {
         const auto p = ptrs(permutation_columns);

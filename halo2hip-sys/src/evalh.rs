@@ -156,6 +156,16 @@ pub struct EvalhPartsDesc {
     pub t_evaluations: *const u64,
 }
 
+/// `h2hip_evalh_shuffles`: the shuffle arguments of one circuit instance, beside either description.  `graphs` holds two graphs per
+/// shuffle (input side, shuffle side), `product_polys` one coefficient-form polynomial of 2^k elements per shuffle.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct EvalhShuffles {
+    pub n_shuffles: u32,
+    pub graphs: *const h2hip_graph,
+    pub product_polys: *const *const u64,
+}
+
 // ---- owning builder -------------------------------------------------------------------------------------------------
 /// A `GraphEvaluator` flattened into plain vectors.  halo2_proofs builds one per graph once per proving key; `view()`
 /// lends it to the engine for the duration of a call.
@@ -271,9 +281,34 @@ pub struct EvalHInput<'a, F> {
     pub lookup_permuted_table_polys: Vec<&'a [F]>,
 }
 
+/// The shuffle arguments of one circuit instance (the argument of upstream PSE halo2: include/halo2hip.h, `h2hip_evalh_shuffles`):
+/// `graphs[2 j]` and `graphs[2 j + 1]` are the input and the shuffle side of shuffle j, `product_polys[j]` its grand product in
+/// coefficient form (2^k elements).
+pub struct ShufflesInput<'a, F> {
+    pub graphs: &'a [FlatGraph],
+    pub product_polys: Vec<&'a [F]>,
+}
+
+/// the C view of a `ShufflesInput` and the tables it points into; None when the lengths do not fit
+fn shuffles_view<F>(sh: &ShufflesInput<'_, F>, n: usize) -> Option<(Vec<h2hip_graph>, Vec<*const u64>)> {
+    if sh.graphs.len() != 2 * sh.product_polys.len() || !sh.product_polys.iter().all(|s| s.len() == n) {
+        return None;
+    }
+    Some((sh.graphs.iter().map(|g| g.view()).collect(), sh.product_polys.iter().map(|s| s.as_ptr() as *const u64).collect()))
+}
+
 /// Safe front of `h2hip_evaluate_h_bn254`: checks the element type and every slice length, builds the pointer tables, calls
 /// the engine.  `values` (2^extended_k elements) is read and written.  false: the engine declined, run the CPU body.
 pub fn try_evaluate_h<F: 'static + Copy>(inp: &EvalHInput<'_, F>, values: &mut [F]) -> bool {
+    evaluate_h_with(inp, None, values)
+}
+
+/// `try_evaluate_h` with the shuffle stage after the lookups (`h2hip_evaluate_h_shuffles_bn254`)
+pub fn try_evaluate_h_shuffles<F: 'static + Copy>(inp: &EvalHInput<'_, F>, shuffles: &ShufflesInput<'_, F>, values: &mut [F]) -> bool {
+    evaluate_h_with(inp, Some(shuffles), values)
+}
+
+fn evaluate_h_with<F: 'static + Copy>(inp: &EvalHInput<'_, F>, shuffles: Option<&ShufflesInput<'_, F>>, values: &mut [F]) -> bool {
     if std::any::TypeId::of::<F>() != std::any::TypeId::of::<halo2curves::bn256::Fr>() || std::mem::size_of::<F>() != 32 {
         return false;
     }
@@ -360,7 +395,19 @@ pub fn try_evaluate_h<F: 'static + Copy>(inp: &EvalHInput<'_, F>, values: &mut [
     key_columns.push(desc.l_last);
     key_columns.push(desc.l_active_row);
     let _ = unsafe { super::ffi::h2hip_columns_pin(key_columns.as_ptr(), key_columns.len(), en) };
-    let rc: c_int = unsafe { super::ffi::h2hip_evaluate_h_bn254(&desc as *const h2hip_evalh_desc, values.as_mut_ptr() as *mut u64) };
+    let rc: c_int = match shuffles {
+        None => unsafe { super::ffi::h2hip_evaluate_h_bn254(&desc as *const h2hip_evalh_desc, values.as_mut_ptr() as *mut u64) },
+        Some(sh) => {
+            let (views, polys) = match shuffles_view(sh, n) {
+                Some(v) => v,
+                None => return false,
+            };
+            let c_sh = EvalhShuffles { n_shuffles: polys.len() as u32, graphs: views.as_ptr(), product_polys: polys.as_ptr() };
+            unsafe {
+                super::ffi::h2hip_evaluate_h_shuffles_bn254(&desc as *const h2hip_evalh_desc, &c_sh as *const EvalhShuffles, values.as_mut_ptr() as *mut u64)
+            }
+        }
+    };
     rc == 0
 }
 
@@ -421,6 +468,15 @@ pub struct EvalHPartsInput<'a, F> {
 /// engine.  `values` (2^extended_k elements) is read and written on the rows of the requested parts only.  false: the engine declined,
 /// run the CPU body.
 pub fn try_evaluate_h_parts<F: 'static + Copy>(inp: &EvalHPartsInput<'_, F>, values: &mut [F]) -> bool {
+    evaluate_h_parts_with(inp, None, values)
+}
+
+/// `try_evaluate_h_parts` with the shuffle stage after the lookups (`h2hip_evaluate_h_parts_shuffles_bn254`)
+pub fn try_evaluate_h_parts_shuffles<F: 'static + Copy>(inp: &EvalHPartsInput<'_, F>, shuffles: &ShufflesInput<'_, F>, values: &mut [F]) -> bool {
+    evaluate_h_parts_with(inp, Some(shuffles), values)
+}
+
+fn evaluate_h_parts_with<F: 'static + Copy>(inp: &EvalHPartsInput<'_, F>, shuffles: Option<&ShufflesInput<'_, F>>, values: &mut [F]) -> bool {
     if std::any::TypeId::of::<F>() != std::any::TypeId::of::<halo2curves::bn256::Fr>() || std::mem::size_of::<F>() != 32 {
         return false;
     }
@@ -505,6 +561,18 @@ pub fn try_evaluate_h_parts<F: 'static + Copy>(inp: &EvalHPartsInput<'_, F>, val
         part_count: inp.part_count,
         t_evaluations: inp.t_evaluations.map_or(std::ptr::null(), |t| t.as_ptr() as *const u64),
     };
-    let rc: c_int = unsafe { super::ffi::h2hip_evaluate_h_parts_bn254(&desc as *const EvalhPartsDesc, values.as_mut_ptr() as *mut u64) };
+    let rc: c_int = match shuffles {
+        None => unsafe { super::ffi::h2hip_evaluate_h_parts_bn254(&desc as *const EvalhPartsDesc, values.as_mut_ptr() as *mut u64) },
+        Some(sh) => {
+            let (views, polys) = match shuffles_view(sh, n) {
+                Some(v) => v,
+                None => return false,
+            };
+            let c_sh = EvalhShuffles { n_shuffles: polys.len() as u32, graphs: views.as_ptr(), product_polys: polys.as_ptr() };
+            unsafe {
+                super::ffi::h2hip_evaluate_h_parts_shuffles_bn254(&desc as *const EvalhPartsDesc, &c_sh as *const EvalhShuffles, values.as_mut_ptr() as *mut u64)
+            }
+        }
+    };
     rc == 0
 }

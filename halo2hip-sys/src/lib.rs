@@ -347,6 +347,33 @@ pub fn try_lookup_products<F: Field + 'static>(k: u32, beta: &F, gamma: &F, comp
     Some(z)
 }
 
+/// The shuffle argument's z columns (`shuffle::Argument::commit_product` of upstream PSE halo2, later than the reference; the
+/// definition is include/halo2hip.h's) for several shuffles in one call: the compressed input and shuffle expressions of each, as
+/// `try_lookup_compress` folds them, `blinding` shuffle-major.  `None` on any failure.
+pub fn try_shuffle_products<F: Field + 'static>(k: u32, gamma: &F, compressed_inputs: &[&[F]], compressed_shuffles: &[&[F]], blinding: &[F],
+                                                blinding_factors: usize) -> Option<Vec<Vec<F>>> {
+    let count = compressed_inputs.len();
+    if !is::<F, Fr>() || !layout_ok() || k > 28 || compressed_shuffles.len() != count {
+        return None;
+    }
+    let n = 1usize << k;
+    if compressed_inputs.iter().chain(compressed_shuffles.iter()).any(|c| c.len() != n) || blinding.len() != count * blinding_factors || blinding_factors + 1 >= n {
+        return None;
+    }
+    let ptrs = |cols: &[&[F]]| -> Vec<*const u64> { cols.iter().map(|c| c.as_ptr() as *const u64).collect() };
+    let (a, s) = (ptrs(compressed_inputs), ptrs(compressed_shuffles));
+    let mut z: Vec<Vec<F>> = (0..count).map(|_| vec![F::zero(); n]).collect();
+    let zp: Vec<*mut u64> = z.iter_mut().map(|c| c.as_mut_ptr() as *mut u64).collect();
+    let rc = unsafe {
+        ffi::h2hip_shuffle_products_bn254(k, fr_ptr(gamma), a.as_ptr(), s.as_ptr(), count, blinding.as_ptr() as *const u64, blinding_factors as u32,
+                                          zp.as_ptr())
+    };
+    if rc != 0 {
+        return None;
+    }
+    Some(z)
+}
+
 /// `commit_permuted`'s compressed expressions (plonk/lookup/prover.rs:90-115): `graphs[g]` (an input or table side of a lookup, built
 /// as `add_expression` of each expression and `Horner(Constant(0), parts, Theta)`) over the Lagrange columns.  `None` on any failure.
 #[allow(clippy::too_many_arguments)]
@@ -651,6 +678,32 @@ pub fn try_check_lookups<F: Field + 'static>(k: u32, compressed_inputs: &[&[F]],
     let rc = unsafe {
         ffi::h2hip_check_lookups_bn254(k, a.as_ptr(), s.as_ptr(), count, blinding_factors as u32, max_rows as u32, counts.as_mut_ptr(),
                                        rows.as_mut_ptr())
+    };
+    if rc != 0 {
+        return None;
+    }
+    Some(check_report(counts, rows, max_rows))
+}
+
+/// The shuffle argument's witness check on compressed columns: the input rows below u = 2^k - blinding_factors - 1 whose value occurs
+/// a different number of times among the input rows below u than among the shuffle rows below u (`h2hip_check_shuffles_bn254`).
+pub fn try_check_shuffles<F: Field + 'static>(k: u32, compressed_inputs: &[&[F]], compressed_shuffles: &[&[F]], blinding_factors: usize,
+                                              max_rows: usize) -> Option<CheckReport> {
+    let count = compressed_inputs.len();
+    if !is::<F, Fr>() || !layout_ok() || k > 28 || count > 32767 || compressed_shuffles.len() != count || max_rows > 65535 {
+        return None;
+    }
+    let n = 1usize << k;
+    if compressed_inputs.iter().chain(compressed_shuffles.iter()).any(|c| c.len() != n) || blinding_factors + 1 >= n {
+        return None;
+    }
+    let ptrs = |cols: &[&[F]]| -> Vec<*const u64> { cols.iter().map(|c| c.as_ptr() as *const u64).collect() };
+    let (a, s) = (ptrs(compressed_inputs), ptrs(compressed_shuffles));
+    let mut counts = vec![0u64; count];
+    let mut rows = vec![u32::MAX; count * max_rows];
+    let rc = unsafe {
+        ffi::h2hip_check_shuffles_bn254(k, a.as_ptr(), s.as_ptr(), count, blinding_factors as u32, max_rows as u32, counts.as_mut_ptr(),
+                                        rows.as_mut_ptr())
     };
     if rc != 0 {
         return None;

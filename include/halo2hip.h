@@ -415,6 +415,35 @@ int h2hip_evaluate_h_workspace_bytes(uint32_t k, uint32_t extended_k, uint32_t n
                                      uint32_t n_perm_sets, uint32_t n_perm_columns, uint32_t n_lookups, int parts_form, int device_form,
                                      size_t* bytes);
 
+/* The shuffle argument's share of h(X) (upstream PSE halo2's Evaluator::shuffles; later than the reference).  The
+ * two descriptors above carry no size field and keep their layout; a circuit's shuffles travel beside them:
+ *   graphs[2j]      the input side of shuffle j:  add_expression of each input expression, Horner(Constant(0), parts, Theta), Add(that, Gamma)
+ *   graphs[2j + 1]  the shuffle side, built the same way
+ *   product_polys[j]  the grand product z_j in coefficient form, 2^k elements (h2hip_shuffle_products_bn254, then lagrange_to_coeff)
+ * A graph's value is the target of its last calculation (zero for an empty graph); call the two a = A + gamma and s = S + gamma.  After
+ * the custom gates, the permutation argument and every lookup of the instance, shuffle j (before shuffle j + 1) folds, with zc the
+ * extended coset of z_j and r_next the row one rotation on,
+ *   v = v y + (1 - zc[idx]) l0[idx];   v = v y + (zc[idx]^2 - zc[idx]) l_last[idx];   v = v y + l_active_row[idx] (zc[r_next] s - zc[idx] a).
+ * A shuffle graph may read fixed, advice, instance, challenge, constant, intermediate, theta and gamma; beta, y or the previous value is
+ * H2HIP_EINVAL before any device work.  The shuffle graphs run on the byte-code interpreter (no kernel is generated for them).
+ * shuffles == NULL or n_shuffles == 0 is the call without the suffix, limb for limb; in the parts form t_evaluations still multiplies
+ * last.  n_shuffles <= 65535. */
+typedef struct h2hip_evalh_shuffles {
+    uint32_t n_shuffles;
+    const h2hip_graph* graphs;
+    const uint64_t* const* product_polys;
+} h2hip_evalh_shuffles;
+int h2hip_evaluate_h_shuffles_bn254(const h2hip_evalh_desc* desc, const h2hip_evalh_shuffles* shuffles, uint64_t* values);
+int h2hip_evaluate_h_shuffles_bn254_device(const h2hip_evalh_desc* desc, const h2hip_evalh_shuffles* shuffles, void* d_values, void* stream);
+int h2hip_evaluate_h_parts_shuffles_bn254(const h2hip_evalh_parts_desc* desc, const h2hip_evalh_shuffles* shuffles, uint64_t* values);
+int h2hip_evaluate_h_parts_shuffles_bn254_device(const h2hip_evalh_parts_desc* desc, const h2hip_evalh_shuffles* shuffles, void* d_values,
+                                                 void* stream);
+/* h2hip_evaluate_h_workspace_bytes for a call with n_shuffles shuffles (0: the same number): the product cosets of one group of shuffles
+ * come on top, and in the host parts form their coefficient columns */
+int h2hip_evaluate_h_shuffles_workspace_bytes(uint32_t k, uint32_t extended_k, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance,
+                                              uint32_t n_perm_sets, uint32_t n_perm_columns, uint32_t n_lookups, uint32_t n_shuffles,
+                                              int parts_form, int device_form, size_t* bytes);
+
 /* ---- pinned part cosets: the parts form's counterpart of h2hip_columns_pin.
  * Keep all P part cosets of each coefficient-form polynomial (2^k elements; pk.fixed_polys, pk.l0 / l_last / l_active_row as polynomials,
  * pk.permutation.polys) in HBM, 2^extended_k elements per polynomial, part-major, keyed by the pointer and the domain.
@@ -464,6 +493,17 @@ int h2hip_lookup_products_bn254_device(uint32_t k, const uint64_t beta[4], const
                                        const void* const* d_compressed_table, const void* const* d_permuted_input,
                                        const void* const* d_permuted_table, size_t count, const uint64_t* blinding, uint32_t blinding_factors,
                                        void* const* d_z, void* stream);
+/* The shuffle argument's grand product (shuffle::Argument::commit_product of upstream PSE halo2, which is later than the reference this
+ * engine follows: DESIGN.md section 2).  With A_j, S_j the compressed input and shuffle expressions of shuffle j -- the theta fold
+ * h2hip_lookup_compress_bn254 computes -- z_j[0] = 1, z_j[i] = z_j[i-1] * (A_j + gamma) * inv(S_j + gamma) at row i - 1 for 1 <= i <= u,
+ * rows n - b .. n - 1 = blinding[j * b ..].  inv is ff's BatchInvert as above: after a zero denominator z is zero.  A valid shuffle ends in
+ * z[u] = 1; the engine does not check that.  Pointer tables, blinding order, the _device form and count == 0 are the lookup call's. */
+int h2hip_shuffle_products_bn254(uint32_t k, const uint64_t gamma[4], const uint64_t* const* compressed_input,
+                                 const uint64_t* const* compressed_shuffle, size_t count, const uint64_t* blinding, uint32_t blinding_factors,
+                                 uint64_t* const* z);
+int h2hip_shuffle_products_bn254_device(uint32_t k, const uint64_t gamma[4], const void* const* d_compressed_input,
+                                        const void* const* d_compressed_shuffle, size_t count, const uint64_t* blinding,
+                                        uint32_t blinding_factors, void* const* d_z, void* stream);
 /* ff::BatchInvert (permutation/prover.rs:117, lookup/prover.rs:208): a[i] <- a[i]^-1 in place, zeros stay zero; n <= 2^30 */
 int h2hip_batch_invert_bn254_fr(uint64_t* a, size_t n);
 int h2hip_batch_invert_bn254_fr_device(void* d_a, size_t n, void* stream);
@@ -616,6 +656,15 @@ int h2hip_check_lookups_bn254(uint32_t k, const uint64_t* const* compressed_inpu
                               uint32_t blinding_factors, uint32_t max_rows, uint64_t* counts, uint32_t* rows);
 int h2hip_check_lookups_bn254_device(uint32_t k, const void* const* d_compressed_input, const void* const* d_compressed_table, size_t count,
                                      uint32_t blinding_factors, uint32_t max_rows, uint64_t* counts, uint32_t* rows, void* stream);
+/* Shuffles (the argument of upstream PSE halo2): shuffle j fails at input row i < u when compressed_input[j][i]
+ * occurs a different number of times among compressed_input[j][0 .. u) than among compressed_shuffle[j][0 .. u).  Rows >= u are never
+ * reported and never counted.  Both multisets have u elements, so they differ exactly when some row fails.  Upstream's MockProver
+ * reports the mismatching positions of the two sorted lists instead; this is the per-row form the counts / rows convention above needs.
+ * blinding_factors + 1 < n, count <= 32767; the columns and the theta-collision caveat are those of the lookup check. */
+int h2hip_check_shuffles_bn254(uint32_t k, const uint64_t* const* compressed_input, const uint64_t* const* compressed_shuffle, size_t count,
+                               uint32_t blinding_factors, uint32_t max_rows, uint64_t* counts, uint32_t* rows);
+int h2hip_check_shuffles_bn254_device(uint32_t k, const void* const* d_compressed_input, const void* const* d_compressed_shuffle, size_t count,
+                                      uint32_t blinding_factors, uint32_t max_rows, uint64_t* counts, uint32_t* rows, void* stream);
 
 /* ---- serialisation: the per-element work of SerdeFormat (helpers.rs:8-20) in ParamsKZG::read_custom / write_custom
  * (poly/kzg/commitment.rs:142-244) and Polynomial::read / write (poly.rs:152-177) ------------------------------------------------------
