@@ -1538,10 +1538,11 @@ static void rowcol_jobs(RowColArgs* ra, const XYZZu* in, XYZZu* out_rows, XYZZu*
 
 // whether a run's tail is finished on the host from bit-plane sums (msm_planes_kernel): few sets, one row / column level at least,
 // at most 16 workgroups (2^11 points) per plane, and the sums not wanted in HBM for the RCCL gather
-static bool msm_plane_tail(const Ctx* c, const MsmLayout& L) {
+static bool msm_plane_tail(bool gather_want, const MsmLayout& L) {
     return tune().msm_plane_tail && tune().msm_quad_tail && L.levels >= 1 && L.n_sets <= MSM_PLANE_SETS_MAX && L.rb <= 11 && L.s <= 11 && L.rb >= 1 && L.s >= 1 &&
-           L.s + 1 + L.rb <= MSM_PLANES_MAX && !c->gather_want;
+           L.s + 1 + L.rb <= MSM_PLANES_MAX && !gather_want;
 }
+static bool msm_plane_tail(const Ctx* c, const MsmLayout& L) { return msm_plane_tail(c->gather_want, L); }
 static inline uint32_t msm_planes_per_set(const MsmLayout& L) { return L.rb + L.s + 1; }
 
 // host side of the plane tail: set = sum_j 2^j C-plane_j + sum_j 2^(s + j) R-plane_j, as one Horner from the top (planes: [C 0..s | R 0..rb-1])
@@ -1658,6 +1659,46 @@ static int msm_stage_c(Ctx* c, const MsmLayout& L, char* base, XYZZ* h_sums, hip
         c->gather_off += bytes;
     }
     return 0;
+}
+
+// test hook, needs no GPU: what stage C does for one run of `fuse` MSMs of n pairs each under the settings in force (table_c = 0: the plain
+// form; otherwise the fixed-base form over a window table of that width).  out[0..13) = n_sets, cb, levels, s, rb, s2, s3, split_log,
+// heavy_t, the tail (0 lane: msm_rowcol_kernel / msm_final_kernel, 1 quad: msm_rowcol_quad_kernel / msm_final_quad_kernel, 2 planes:
+// msm_planes_kernel and the host's Horner), c, W, the heavy chunk; out[13] = the row/column jobs that run (0, 2, or 6 with a second pass)
+// and out[14..] their g_log in launch order (first pass rows, columns; second pass RR, RC, CR, CC).  Returns the words the plan has (those
+// beyond cap are not written), or -1 where msm_layout refuses the run.
+extern "C" int h2hip_debug_msm_reduce_plan(size_t n, uint32_t fuse, uint32_t table_c, uint32_t* out, size_t cap) {
+    if ((!out && cap) || n == 0 || fuse == 0) return -1;
+    TuneRead rd;
+    MsmTable tab;
+    if (table_c) {
+        tab.c = normalise_window(table_c);
+        tab.W = (255 + tab.c - 1) / tab.c;
+        tab.stride = n;
+    }
+    MsmLayout L;
+    if (msm_layout(n, &L, fuse, table_c ? &tab : nullptr)) return -1;
+    const bool planes = msm_plane_tail(false, L);
+    const bool quad = tune().msm_quad_tail && L.n_sets <= 64;
+    std::vector<uint32_t> v = {L.n_sets, L.p.cb, L.levels, L.s, L.rb, L.s2, L.s3, L.split_log, L.p.heavy_t, planes ? 2u : quad ? 1u : 0u,
+                               L.p.c,    L.p.W,  L.p.chunk};
+    RowColArgs ra;
+    uint32_t nblk = 0, n_jobs = 0, g_log[6];
+    if (L.levels >= 1) {
+        memset(&ra, 0, sizeof(ra));
+        rowcol_jobs(&ra, nullptr, nullptr, nullptr, L.n_sets, L.rb, L.s, &nblk);
+        for (uint32_t i = 0; i < ra.n_jobs; i++) g_log[n_jobs++] = ra.job[i].g_log;
+    }
+    if (L.levels == 2 && !planes) {
+        memset(&ra, 0, sizeof(ra));
+        rowcol_jobs(&ra, nullptr, nullptr, nullptr, L.n_sets, L.rb - L.s2, L.s2, &nblk, quad);
+        rowcol_jobs(&ra, nullptr, nullptr, nullptr, L.n_sets, L.s - L.s3, L.s3, &nblk, quad);
+        for (uint32_t i = 0; i < ra.n_jobs; i++) g_log[n_jobs++] = ra.job[i].g_log;
+    }
+    v.push_back(n_jobs);
+    v.insert(v.end(), g_log, g_log + n_jobs);
+    for (size_t i = 0; i < v.size() && i < cap; i++) out[i] = v[i];
+    return (int)v.size();
 }
 
 // sets per MSM and the host-side finish

@@ -47,6 +47,12 @@ int h2hip_debug_set_msm_split_buckets(int on);
 int h2hip_debug_set_msm_plane_tail(int on);
 /* reduction tail: one quad of lanes per group operation (1, default) or one lane each (0) */
 int h2hip_debug_set_msm_quad_tail(int on);
+/* needs no GPU: the geometry of the bucket reduction of one run of `fuse` MSMs of n pairs each under the settings in force; table_c = 0 is
+ * the plain form, otherwise the fixed-base form over a window table of that width.  out[0..13) = n_sets, cb, levels, s, rb, s2, s3,
+ * split_log, heavy_t, tail (0 = lane, 1 = quad, 2 = bit planes finished on the host), c, W, entries per heavy chunk; out[13] = the
+ * row/column jobs that run and out[14..] the g_log of each in launch order (first pass: rows, columns; second pass: RR, RC, CR, CC).
+ * Returns the plan's length in words (what lies beyond cap is not written), or -1 for a run the engine refuses */
+int h2hip_debug_msm_reduce_plan(size_t n, uint32_t fuse, uint32_t table_c, uint32_t* out, size_t cap);
 /* level-1 sort records of runs whose bins span several level-2 tiles: entries and key bits as two arrays (1, default) or 8-byte pairs (0) */
 int h2hip_debug_set_msm_split_records(int on);
 /* target entries per coarse bin of the MSM's two-level sort (0 restores the default) */

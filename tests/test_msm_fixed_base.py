@@ -131,7 +131,9 @@ def test_host_finished_tail_equals_the_gpu_tail_and_the_oracle(h2, oracle, golde
     """round 4: a run with few bucket sets stops at the bit-plane sums of its row / column sums and the host finishes with one Horner
     (msm_planes_kernel + msm_planes_finish).  Same group element as the all-GPU tail (h2hip_debug_set_msm_plane_tail(0)) and as the
     oracle -- on uniform scalars, on columns that put everything into one bucket (planes that are one point or the identity), on r - 1
-    and on scalars whose digits make equal points meet inside the plane trees (doubling) -- plain and fixed-base, lone and a fused pair."""
+    and on scalars whose digits make equal points meet inside the plane trees (doubling) -- plain and fixed-base, lone and a fused pair.
+    The exceptional additions here are incidental; tests/test_msm_reduce_edges.py places them one by one (bucket sums chosen by the test, in
+    every kernel of every tail, with an integer model that says which addition of which stage each case makes exceptional)."""
     L = h2.lib()
     n = 1 << 12
     bs = oracle.gen_points(0x5EED0002, n, num_threads=NT)
