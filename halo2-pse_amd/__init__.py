@@ -559,6 +559,86 @@ def commit_shuffle_products(params, domain, shuffles, theta, gamma, blinding, bl
              "product_commitment": params.commit_lagrange(z[j], blinds[j])} for j in range(len(shuffles))]
 
 
+def _mv_inputs(compressed_inputs, n, count):
+    """the flat, argument-major input table of the mv-lookup calls: one list of columns per argument -> (columns, n_inputs array)"""
+    if len(compressed_inputs) != count:
+        raise ValueError("mvlookup: %d input lists for %d tables" % (len(compressed_inputs), count))
+    flat = [c for cols in compressed_inputs for c in cols]
+    n_in = np.array([len(cols) for cols in compressed_inputs] or [0], dtype=np.uint32)
+    return (_cols(flat, n, "compressed_inputs") if n is not None else flat), n_in
+
+
+def mvlookup_multiplicities(k, compressed_inputs, compressed_tables, blinding_factors, partial=False):
+    """The logUp (mv-lookup) argument's multiplicity columns (include/halo2hip.h states the definition): compressed_inputs[j] is the list
+    of argument j's (2^k, 4) uint64 compressed input columns, compressed_tables[j] its table.  Returns the list of m columns, Montgomery
+    form.  Raises H2HipLookupError when an input value is missing from its table -- unless partial=True, which returns (m, message or
+    None): the engine writes the counts of the values it found either way."""
+    n = 1 << int(k)
+    t = _cols(compressed_tables, n, "compressed_tables")
+    f, n_in = _mv_inputs(compressed_inputs, n, len(t))
+    m = [np.zeros((n, 4), dtype=np.uint64) for _ in t]
+    rc = lib().h2hip_mvlookup_multiplicities_bn254(ctypes.c_uint32(k), _host_ptrs(f), _p(n_in), _host_ptrs(t), ctypes.c_size_t(len(t)),
+                                                   ctypes.c_uint32(blinding_factors), _host_ptrs(m))
+    if partial and rc == H2HIP_ELOOKUP:
+        return m, lib().h2hip_last_error().decode()
+    _check_lookup(rc, "h2hip_mvlookup_multiplicities_bn254")
+    return (m, None) if partial else m
+
+
+def mvlookup_sums(k, beta, compressed_inputs, compressed_tables, m, blinding, blinding_factors):
+    """The mv-lookup grand sums phi (include/halo2hip.h): inputs and tables as for mvlookup_multiplicities, m their multiplicity columns;
+    blinding is (count * blinding_factors, 4).  Returns the list of phi columns."""
+    n = 1 << int(k)
+    t, mm = _cols(compressed_tables, n, "compressed_tables"), _cols(m, n, "m")
+    if len(mm) != len(t):
+        raise ValueError("mvlookup: m and tables differ in count")
+    f, n_in = _mv_inputs(compressed_inputs, n, len(t))
+    bl = _blinding(blinding, len(t), int(blinding_factors))
+    phi = [np.zeros((n, 4), dtype=np.uint64) for _ in t]
+    _check(lib().h2hip_mvlookup_sums_bn254(ctypes.c_uint32(k), _p(_fe(beta)), _host_ptrs(f), _p(n_in), _host_ptrs(t), _host_ptrs(mm),
+                                           ctypes.c_size_t(len(t)), _p(bl), ctypes.c_uint32(blinding_factors), _host_ptrs(phi)),
+           "h2hip_mvlookup_sums_bn254")
+    return phi
+
+
+def mvlookup_sum_rows(k, blinding_factors, count):
+    """test hook: the rows one thread of the grand sum's scan takes in a call of `count` arguments (the code's own rule; no GPU)"""
+    out = ctypes.c_uint32(0)
+    _check(lib().h2hip_debug_mvlookup_sum_rows(ctypes.c_uint32(k), ctypes.c_uint32(blinding_factors), ctypes.c_size_t(count), ctypes.byref(out)),
+           "h2hip_debug_mvlookup_sum_rows")
+    return out.value
+
+
+def commit_mvlookup(params, domain, lookups, theta, beta, blinding, blinding_factors, blinds, fixed=(), advice=(), instance=(), challenges=()):
+    """The mv-lookup prover steps for every argument of one instance, composed as commit_permuted is: compress every input tuple and the
+    table tuple with theta, count the multiplicities, commit m in Lagrange form, build the grand sum phi with beta, commit phi, and
+    take both to coefficient form, batched.  lookups: [([input_exprs, ...], table_exprs)] expression tuples, several inputs sharing one
+    table; blinding as for mvlookup_sums (phi's rows); blinds[2j], blinds[2j + 1] the blinds of m_j and phi_j.  Returns one dict per
+    argument: compressed_inputs / compressed_table, m / phi (Lagrange), m_poly / phi_poly (coefficients), m_commitment / phi_commitment."""
+    from .evaluation import flatten_graph, lookup_compress_graphs
+    k = int(domain.k)
+    graphs, n_in = [], []
+    for inputs, tab in lookups:
+        for inp in inputs:
+            graphs.append(flatten_graph(lookup_compress_graphs(inp, tab)[0]))
+        graphs.append(flatten_graph(lookup_compress_graphs(inputs[0], tab)[1]))
+        n_in.append(len(inputs))
+    comp = lookup_compress(k, graphs, theta, fixed, advice, instance, challenges)
+    f, t, at = [], [], 0
+    for kj in n_in:
+        f.append(comp[at:at + kj])
+        t.append(comp[at + kj])
+        at += kj + 1
+    if len(blinds) != 2 * len(lookups):
+        raise ValueError("blinds: expected two per argument")
+    m = mvlookup_multiplicities(k, f, t, blinding_factors)
+    m_commit = [params.commit_lagrange(m[j], blinds[2 * j]) for j in range(len(lookups))]
+    phi = mvlookup_sums(k, beta, f, t, m, blinding, blinding_factors)
+    polys = domain.lagrange_to_coeff_batch([c for j in range(len(lookups)) for c in (m[j], phi[j])])
+    return [{"compressed_inputs": f[j], "compressed_table": t[j], "m": m[j], "phi": phi[j], "m_poly": polys[2 * j], "phi_poly": polys[2 * j + 1],
+             "m_commitment": m_commit[j], "phi_commitment": params.commit_lagrange(phi[j], blinds[2 * j + 1])} for j in range(len(lookups))]
+
+
 # ------------------------------------------------------------------ witness check: MockProver::verify's three column-wide loops
 def _check_out(items, max_rows):
     max_rows = int(max_rows)
@@ -644,7 +724,7 @@ def _failures(kind, counts, rows):
 
 
 def verify_witness(k, gate_polys, lookups, theta, blinding_factors, permutation_columns, mapping, fixed=(), advice=(), instance=(),
-                   challenges=(), max_rows=64, shuffles=()):
+                   challenges=(), max_rows=64, shuffles=(), mvlookups=()):
     """The three column-wide loops of MockProver::verify over one instance's columns: gate_polys are expression tuples (evaluation.py;
     every gate's polynomials in cs.gates order), lookups [(input_exprs, table_exprs)], compressed here with the caller's theta;
     permutation_columns [(kind, index)] with kind 'advice' / 'fixed' / 'instance' names the permutation argument's columns, mapping its
@@ -652,7 +732,9 @@ def verify_witness(k, gate_polys, lookups, theta, blinding_factors, permutation_
     nothing.  Returns the failures as ("gate", graph_index, row), ("lookup", lookup_index, row), ("permutation", column, row) tuples in
     verify's order (dev.rs:933-938), at most the max_rows lowest rows of each constraint; an empty list is a satisfied witness.
     shuffles [(input_exprs, shuffle_exprs)] (the argument of upstream PSE halo2) are compressed with the same theta and reported as
-    ("shuffle", shuffle_index, row) after the lookups; the default checks none."""
+    ("shuffle", shuffle_index, row) after the lookups; the default checks none.  mvlookups [([input_exprs, ...], table_exprs)] (the
+    logUp argument) go through the lookup check with the table repeated per input tuple and are reported after the shuffles as
+    ("mvlookup", input_index, row), the input tuples counted over all arguments in order."""
     from .evaluation import flatten_graph, gate_check_graphs, lookup_compress_graphs
     k = int(k)
     out = []
@@ -673,6 +755,15 @@ def verify_witness(k, gate_polys, lookups, theta, blinding_factors, permutation_
     if sg:
         comp = lookup_compress(k, sg, theta, fixed, advice, instance, challenges)
         out += _failures("shuffle", *check_shuffles(k, comp[0::2], comp[1::2], blinding_factors, max_rows))
+    mg, pairs = [], []  # pairs: (graph of an input tuple, graph of its argument's table) as indices into mg
+    for inputs, tab in mvlookups:
+        first = len(mg)
+        mg += [flatten_graph(lookup_compress_graphs(inp, tab)[0]) for inp in inputs]
+        mg.append(flatten_graph(lookup_compress_graphs(inputs[0], tab)[1]))
+        pairs += [(first + t, len(mg) - 1) for t in range(len(inputs))]
+    if mg:
+        comp = lookup_compress(k, mg, theta, fixed, advice, instance, challenges)
+        out += _failures("mvlookup", *check_lookups(k, [comp[i] for i, _ in pairs], [comp[t] for _, t in pairs], blinding_factors, max_rows))
     if mapping is not None and len(permutation_columns):
         pools = {"advice": advice, "fixed": fixed, "instance": instance}
         cols = [pools[kind][int(i)] for kind, i in permutation_columns]
@@ -1681,6 +1772,25 @@ def shuffle_products_device(k, gamma, d_compressed_inputs, d_compressed_shuffles
                                                      _ptr_array(d_compressed_shuffles), ctypes.c_size_t(len(d_z)), _p(bl),
                                                      ctypes.c_uint32(blinding_factors), _ptr_array(d_z), _stream()),
            "h2hip_shuffle_products_bn254_device")
+
+
+def mvlookup_multiplicities_device(k, d_compressed_inputs, d_compressed_tables, blinding_factors, d_m):
+    """mvlookup_multiplicities over torch CUDA tensors (d_compressed_inputs[j]: the list of argument j's input tensors); queued on the
+    current stream, which the call then waits for once (the verdict).  Raises H2HipLookupError when an input value is missing; d_m is
+    written either way."""
+    flat, n_in = _mv_inputs(d_compressed_inputs, None, len(d_compressed_tables))
+    _check_lookup(lib().h2hip_mvlookup_multiplicities_bn254_device(ctypes.c_uint32(k), _ptr_array(flat), _p(n_in), _ptr_array(d_compressed_tables),
+                                                                   ctypes.c_size_t(len(d_compressed_tables)), ctypes.c_uint32(blinding_factors),
+                                                                   _ptr_array(d_m), _stream()), "h2hip_mvlookup_multiplicities_bn254_device")
+
+
+def mvlookup_sums_device(k, beta, d_compressed_inputs, d_compressed_tables, d_m, blinding, blinding_factors, d_phi):
+    """device form of mvlookup_sums; queued on the current stream, not waited for"""
+    flat, n_in = _mv_inputs(d_compressed_inputs, None, len(d_compressed_tables))
+    bl = _blinding(blinding, len(d_phi), int(blinding_factors))
+    _check(lib().h2hip_mvlookup_sums_bn254_device(ctypes.c_uint32(k), _p(_fe(beta)), _ptr_array(flat), _p(n_in), _ptr_array(d_compressed_tables),
+                                                  _ptr_array(d_m), ctypes.c_size_t(len(d_phi)), _p(bl), ctypes.c_uint32(blinding_factors),
+                                                  _ptr_array(d_phi), _stream()), "h2hip_mvlookup_sums_bn254_device")
 
 
 def batch_invert_device(d_a, n=None):

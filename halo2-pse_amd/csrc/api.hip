@@ -906,6 +906,7 @@ static void release_ctx(Ctx* c) {
     c->gen_table.release();
     c->prod_ws.release();
     c->prod_io.release();
+    c->mvsum_ws.release();
     c->open_ws.release();
     c->open_io.release();
     c->lookup_ws.release();

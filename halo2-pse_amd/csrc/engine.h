@@ -180,6 +180,7 @@ struct Ctx {
     std::recursive_mutex mu;       // serialises entry points: re-entrant callers (rayon workers) are safe
     DevBuf ntt_ws, ntt_io, msm_scalars[3], msm_bases, msm_slot[3], misc, evalh_ws, evalh_slots, ecfft_ws, ntt_ptrs, gather, gen_table;
     DevBuf prod_ws, prod_io;       // product.hip: scans' workspace; the host-pointer forms' columns
+    DevBuf mvsum_ws;               // product.hip: the mv-lookup grand sum's denominators, partial sums and descriptors
     DevBuf open_ws, open_io;       // opening.hip: scans' workspace and tables; evaluations and the host-pointer forms' columns
     DevBuf lookup_ws, lookup_io;   // lookup.hip: sort keys, marks and scans; the host-pointer forms' columns
     HostBuf lookup_flag;           // lookup.hip: the per-lookup not-found flags read back at the end of a permute call
@@ -533,6 +534,12 @@ int batch_invert_device(Ctx* c, Fe* d_a, uint64_t n, hipStream_t s);
 // the shuffle argument's grand products: inputs[j] = A_j, shuffles[j] = S_j
 int shuffle_products_device(Ctx* c, uint32_t k, const Fe& gamma, const Fe* const* inputs, const Fe* const* shuffles, size_t count,
                             const uint64_t* blinding, uint32_t bf, Fe* const* z, hipStream_t s);
+// the logUp (mv-lookup) argument's grand sums: inputs flat and argument-major (n_inputs[j] columns of argument j), tables[j], m[j] -> phi[j]
+int mvlookup_sums_device(Ctx* c, uint32_t k, const Fe& beta, const Fe* const* inputs, const uint32_t* n_inputs, const Fe* const* tables,
+                         const Fe* const* m, size_t count, const uint64_t* blinding, uint32_t bf, Fe* const* phi, hipStream_t s);
+// lookup.hip: the mv-lookup multiplicity columns m[j]; waits for s once, H2HIP_ELOOKUP (every m still written) when an input value is missing
+int mvlookup_multiplicities_device(Ctx* c, uint32_t k, const Fe* const* in, const uint32_t* n_inputs, const Fe* const* tab, size_t count,
+                                   uint32_t bf, Fe* const* m, hipStream_t s);
 // lookup.hip: commit_permuted's A' / S' of `count` lookups from device columns; waits for s once, H2HIP_ELOOKUP when an input value is
 // missing from its table
 int lookup_permute_device(Ctx* c, uint32_t k, const Fe* const* in, const Fe* const* tab, size_t count, const uint64_t* blinding, uint32_t bf,
@@ -556,7 +563,8 @@ int pinned_make_room(Ctx* c, size_t bytes, bool* fits);
 void evalh_modules_free(Ctx* c);                            // unload this device's generated kernels (release_ctx)
 void evalh_rtc_shutdown();                                  // join the compile threads (h2hip_shutdown)
 int evaluate_h_validate(const h2hip_evalh_desc* d, const void* values);
-int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, const h2hip_evalh_shuffles* sh, uint64_t* values, bool dev, hipStream_t s);
+int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, const h2hip_evalh_mvlookups* mv, const h2hip_evalh_shuffles* sh, uint64_t* values,
+                    bool dev, hipStream_t s);
 // lookup compression (commit_permuted's compressed expressions) on the interpreter: validation needs no device; the run is enqueued on s
 int lookup_compress_validate(uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance, uint32_t n_challenges, const h2hip_graph* graphs,
                              size_t n_graphs);

@@ -311,6 +311,46 @@ __global__ void __launch_bounds__(256) evalh_shuffle_kernel(ProgDev ga, ProgDev 
     }
 }
 
+// One logUp (mv-lookup) argument's share of a row (include/halo2hip.h, h2hip_evalh_mvlookups).  progs holds the argument's K input
+// programs, then its table program; each value is (theta fold) + beta.  The programs run in turn on one Slots object, which the host
+// sizes for the largest plan among them, and between two of them only P = prod f_c, Q = sum_c prod_{l != c} f_l (streamed as
+// Q <- Q f + P; P <- P f: no inversion on the coset) stay in registers; the table program runs last, so tau is never held across one.
+// Magnitudes in units of r in brackets: P_0 = 1, P <- P f [P 32 / 169 + 1 <= 1.3]; Q_0 = 0, Q <- Q f + P [Q 32 / 169 + 1 + 1.3 <= 2.9].
+struct MvLookupDev {
+    const Fe *phi, *m;  // extended cosets of the grand sum and of the multiplicities
+    const Fe *l0, *l_last, *l_active;
+};
+template <int MAXI>
+__global__ void __launch_bounds__(256) evalh_mvlookup_kernel(const ProgDev* __restrict__ progs, uint32_t n_inputs, MvLookupDev mv, ColsDev c,
+                                                             Fe* values, Fu* gws, uint32_t lanes) {
+    const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= lanes) return;
+    Slots<MAXI> slots(gws + tid, lanes);
+    for (uint64_t row = tid; row < (1ull << c.log_size); row += lanes) {
+        const uint32_t idx = (uint32_t)row;
+        const uint32_t r_next = rot_idx(idx, 1, c.rot_scale, c.log_size);
+        Fu P = fu_one_i<UF>(), Q = fu_zero();
+        for (uint32_t t = 0; t < n_inputs; t++) {
+            const Fu f = prog_eval(progs[t], c, idx, fu_zero(), slots);  // [< 32]
+            Q = addn(mul_i(Q, f), P);                                    // [<= 2.9]
+            P = mul_i(P, f);                                             // [<= 1.3]
+        }
+        const Fu tau = prog_eval(progs[n_inputs], c, idx, fu_zero(), slots);  // [< 32]
+        const Fu pc = ld_i(mv.phi[idx]);                                      // [32]
+        Fu v = ld_i(values[idx]);                                             // [32]
+        // l_0(X) * phi(X) = 0
+        v = fold_y(v, c.y, pc, ld_i(mv.l0[idx]));                             // [1.2] + [32 * 32 / 169 + 1 = 7.1] = [8.3]
+        // l_last(X) * phi(X) = 0
+        v = fold_y(v, c.y, pc, ld_i(mv.l_last[idx]));                         // [1.1] + [7.1] = [8.2]
+        // (1 - (l_last + l_blind)) * (tau P (phi(wX) - phi(X)) - tau Q + m P) = 0: the first two products leave with one reduction
+        const Fu tp = mul_i(tau, P);                                                        // [32 * 1.3 / 169 + 1 = 1.3]
+        const Fu e = addn(fu_mul_sub<UF>(tp, subn(ld_i(mv.phi[r_next]), pc), tau, Q),       // [(1.3 * 64 + 32 * 2.9) / 169 + 1 = 2.1]
+                          mul_i(ld_i(mv.m[idx]), P));                                       // + [32 * 1.3 / 169 + 1 = 1.3] = [3.4]
+        v = fold_y(v, c.y, e, ld_i(mv.l_active[idx]));                                      // [1.1] + [3.4 * 32 / 169 + 1 = 1.7] = [2.8]
+        values[idx] = out_e(v);  // [< 15]
+    }
+}
+
 // ---------------------------------------------------------------------------------------------- host side
 
 // E-form canonical element -> I-form canonical limbs (x * 2^5 mod r, sliced): how constants, challenges and the
@@ -1201,6 +1241,48 @@ static int evaluate_h_shuffles_validate(const h2hip_evalh_desc* d, const h2hip_e
     return 0;
 }
 
+// The mv-lookup stage of such a call (h2hip_evalh_mvlookups): the tables, the limits, every graph's indices, and what a graph may read --
+// not gamma, y or the previous value.  Needs no device.
+static bool mvlookup_vs_allowed(const h2hip_value_source& v) { return v.kind != H2HIP_VS_GAMMA && v.kind != H2HIP_VS_Y && v.kind != H2HIP_VS_PREVIOUS; }
+static int evaluate_h_mvlookups_validate(const h2hip_evalh_desc* d, const h2hip_evalh_mvlookups* mv) {
+    if (!mv || !mv->n_args) return 0;
+    if (mv->n_args > 65535) {
+        set_error("evaluate_h: %u mv-lookup arguments > 65535", mv->n_args);
+        return 1;
+    }
+    if (!mv->n_inputs || !mv->graphs) {
+        set_error("evaluate_h: null mv-lookup n_inputs or graphs");
+        return 1;
+    }
+    if (check_ptrs("evaluate_h", (const void* const*)mv->phi_polys, mv->n_args, "mv-lookup phi_polys") ||
+        check_ptrs("evaluate_h", (const void* const*)mv->m_polys, mv->n_args, "mv-lookup m_polys"))
+        return 1;
+    size_t n_graphs = 0;
+    for (uint32_t j = 0; j < mv->n_args; j++) {
+        if (mv->n_inputs[j] < 1 || mv->n_inputs[j] > 255) {
+            set_error("evaluate_h: mv-lookup n_inputs[%u] = %u, not in [1, 255]", j, mv->n_inputs[j]);
+            return 1;
+        }
+        n_graphs += mv->n_inputs[j] + 1;
+    }
+    for (size_t i = 0; i < n_graphs; i++) {
+        const h2hip_graph& g = mv->graphs[i];
+        if (graph_validate(g, *d, "mv-lookup")) return 1;
+        for (uint32_t q = 0; q < g.n_calculations; q++) {
+            const h2hip_calculation& cl = g.calculations[q];
+            bool ok = mvlookup_vs_allowed(cl.x);
+            if (cl.op == H2HIP_CALC_ADD || cl.op == H2HIP_CALC_SUB || cl.op == H2HIP_CALC_MUL || cl.op == H2HIP_CALC_HORNER) ok = ok && mvlookup_vs_allowed(cl.y);
+            if (cl.op == H2HIP_CALC_HORNER)
+                for (uint32_t t = 0; ok && t < cl.parts_count; t++) ok = mvlookup_vs_allowed(g.parts[cl.parts_offset + t]);
+            if (!ok) {
+                set_error("evaluate_h: mv-lookup graph %zu, calculation %u reads gamma, y or the previous value", i, q);
+                return 1;
+            }
+        }
+    }
+    return 0;
+}
+
 // Everything small the kernels read (programs, constants, rotations, column-pointer tables, challenges, the power table)
 // is laid out in one host image of a metadata region at the head of the arena and uploaded with ONE copy before any kernel
 // is queued.  A copy from pageable memory is synchronous in HIP and ordered after the stream's earlier work, so a copy
@@ -1229,7 +1311,9 @@ struct MetaBlob {
 // drivers (lookup compression, the witness check's gates) build one.
 struct CallPlan {
     std::vector<const h2hip_graph*> graphs;  // the gates graph first when the call has one, then its further graphs in order
-    size_t n_lookups = 0, n_shuffles = 0;    // evaluate_h: the further graphs are n_lookups lookup graphs, then 2 n_shuffles shuffle graphs
+    size_t n_lookups = 0, n_shuffles = 0;    // evaluate_h: the further graphs are n_lookups lookup graphs, the mv-lookups', then 2 n_shuffles shuffle graphs
+    std::vector<uint32_t> mv_inputs;         // evaluate_h: K_j per mv-lookup argument; its K_j + 1 graphs follow those of argument j - 1
+    size_t n_mv_graphs = 0;
     std::vector<Program> progs;
     std::vector<SlotPlan> plans;
     size_t largest = 0;     // the program with the most slots: its plan serves a launch that runs every graph of the call
@@ -1238,10 +1322,16 @@ struct CallPlan {
 };
 
 static int call_plan(const h2hip_graph* gates, const h2hip_graph* more, size_t n_more, size_t rows, CallPlan* cp,
-                     const h2hip_evalh_shuffles* sh = nullptr) {
+                     const h2hip_evalh_shuffles* sh = nullptr, const h2hip_evalh_mvlookups* mv = nullptr) {
     if (gates) cp->graphs.push_back(gates);
     for (size_t i = 0; i < n_more; i++) cp->graphs.push_back(more + i);
     cp->n_lookups = n_more;
+    for (uint32_t j = 0; mv && j < mv->n_args; j++) {  // K_j + 1 programs per mv-lookup argument, behind the lookups'
+        cp->mv_inputs.push_back(mv->n_inputs[j]);
+        cp->n_mv_graphs += mv->n_inputs[j] + 1;
+    }
+    for (size_t i = 0; i < cp->n_mv_graphs; i++) cp->graphs.push_back(mv->graphs + i);
+    cp->meta_bytes += cp->n_mv_graphs ? cp->n_mv_graphs * sizeof(ProgDev) + 256 : 0;  // the device table of their programs (mv_progs_put)
     cp->n_shuffles = sh ? sh->n_shuffles : 0;  // two programs per shuffle, behind the lookups'
     for (size_t i = 0; i < 2 * cp->n_shuffles; i++) cp->graphs.push_back(sh->graphs + i);
     const size_t count = cp->graphs.size();
@@ -1279,6 +1369,12 @@ static std::vector<ProgDev> progs_put(MetaBlob& mb, const CallPlan& cp) {
         out[i].result = cp.progs[i].result;
     }
     return out;
+}
+
+// the mv-lookup programs once more, as the one device table evalh_mvlookup_kernel indexes (nullptr for a call without mv-lookups)
+static const ProgDev* mv_progs_put(MetaBlob& mb, const CallPlan& cp, const std::vector<ProgDev>& pds) {
+    if (!cp.n_mv_graphs) return nullptr;
+    return mb.put(pds.data() + (pds.size() - 2 * cp.n_shuffles - cp.n_mv_graphs), cp.n_mv_graphs);
 }
 
 // The column tables (device pointers, d's counts), d's challenges and its scalars into the metadata image.  Of d only the counts, the
@@ -1400,6 +1496,22 @@ static int enqueue_shuffle(Ctx* c, const CallPlan& cp, size_t i, const std::vect
     return 0;
 }
 
+// ... and of one mv-lookup argument's (programs i .. i + n_inputs of the plan, d_progs their device table): always the interpreter, on
+// the slot plan of the program with the most slots among them
+static int enqueue_mvlookup(Ctx* c, const CallPlan& cp, size_t i, uint32_t n_inputs, const ProgDev* d_progs, const MvLookupDev& md,
+                            const ColsDev& cols, Fe* d_values, hipStream_t s) {
+    size_t big = i;
+    for (size_t t = i; t <= i + n_inputs; t++)
+        if (cp.progs[t].n_slots > cp.progs[big].n_slots) big = t;
+    const SlotPlan& sp = cp.plans[big];
+    with_tier(sp.tier, [&](auto tier, size_t lds) {
+        hipLaunchKernelGGL(evalh_mvlookup_kernel<decltype(tier)::value>, dim3(sp.lanes / 256), dim3(256), lds, s, d_progs, n_inputs, md, cols,
+                           d_values, (Fu*)c->evalh_slots.p, sp.lanes);
+    });
+    H2_CHECK(hipGetLastError());
+    return 0;
+}
+
 // The constraints of `rows` rows folded into `values`, in the reference's order: the custom gates (:334-360), the permutation argument
 // (:362-441) when the system has one, then the lookups (:443-518).  The plan holds the gates program and one program per lookup, pds
 // their device forms.  Every column the kernels read is in place before the call, but for two kinds the pass asks for when their turn
@@ -1408,11 +1520,14 @@ static int enqueue_shuffle(Ctx* c, const CallPlan& cp, size_t i, const std::vect
 // (product, permuted input, permuted table per lookup; the first group's are there from the start).  l: l0, l_last, l_active.
 // The shuffles follow (h2hip_evalh_shuffles): programs 1 + n_lookups + 2j and + 2j + 1 of the plan are shuffle j's.  Their product cosets
 // are formed a group at a time as well, one column per shuffle in shz[0 .. sh_group); next_shuffles(first, count) is asked for every
-// group, the first included, when its turn comes.
-template <class PermReady, class NextGroup, class NextShuffles>
+// group, the first included, when its turn comes.  Between the lookups and the shuffles run the mv-lookups (h2hip_evalh_mvlookups),
+// grouped the same way: mvz[2 g], mvz[2 g + 1] are the phi and m cosets of the group's g-th argument, next_mv(first, count) forms them,
+// d_mv_progs is the device table of their programs (mv_progs_put).
+template <class PermReady, class NextGroup, class NextMv, class NextShuffles>
 static int constraint_pass(Ctx* c, const CallPlan& cp, const std::vector<ProgDev>& pds, const ColsDev& cols, const PermDev& pd,
-                           const Fe* const* l, const Fe* const* lk, size_t lk_group, const Fe* const* shz, size_t sh_group, Fe* d_values,
-                           size_t rows, hipStream_t s, PermReady perm_ready, NextGroup next_group, NextShuffles next_shuffles) {
+                           const Fe* const* l, const Fe* const* lk, size_t lk_group, const ProgDev* d_mv_progs, const Fe* const* mvz,
+                           size_t mv_group, const Fe* const* shz, size_t sh_group, Fe* d_values, size_t rows, hipStream_t s,
+                           PermReady perm_ready, NextGroup next_group, NextMv next_mv, NextShuffles next_shuffles) {
     int rc;
     int t_g = c->timer_begin("evalh_gates", s);
     if ((rc = enqueue_gates(c, cp, pds[0], cols, d_values, rows, s))) return rc;
@@ -1433,6 +1548,17 @@ static int constraint_pass(Ctx* c, const CallPlan& cp, const std::vector<ProgDev
         if ((rc = enqueue_lookup(c, cp, i + 1, pds[i + 1], ld, cols, d_values, rows, s))) return rc;
     }
     c->timer_end(t_l, s);
+    const size_t n_mv = cp.mv_inputs.size();
+    for (size_t j = 0, at = 0; j < n_mv; at += cp.mv_inputs[j] + 1, j++) {
+        const size_t gj = j % mv_group;
+        if (gj == 0) {  // the group's cosets; their transforms are not the stage's own time
+            if ((rc = next_mv(j, n_mv - j < mv_group ? n_mv - j : mv_group))) return rc;
+        }
+        int t_m = c->timer_begin("evalh_mvlookups", s);
+        const MvLookupDev md = {mvz[2 * gj], mvz[2 * gj + 1], l[0], l[1], l[2]};
+        if ((rc = enqueue_mvlookup(c, cp, 1 + n_lookups + at, cp.mv_inputs[j], d_mv_progs + at, md, cols, d_values, s))) return rc;
+        c->timer_end(t_m, s);
+    }
     for (size_t j = 0; j < cp.n_shuffles; j++) {
         const size_t gj = j % sh_group;
         if (gj == 0) {  // the group's cosets; their transforms are not the stage's own time
@@ -1440,7 +1566,7 @@ static int constraint_pass(Ctx* c, const CallPlan& cp, const std::vector<ProgDev
         }
         int t_s = c->timer_begin("evalh_shuffles", s);
         const ShuffleDev sd = {shz[gj], l[0], l[1], l[2]};
-        if ((rc = enqueue_shuffle(c, cp, 1 + n_lookups + 2 * j, pds, sd, cols, d_values, s))) return rc;
+        if ((rc = enqueue_shuffle(c, cp, 1 + n_lookups + cp.n_mv_graphs + 2 * j, pds, sd, cols, d_values, s))) return rc;
         c->timer_end(t_s, s);
     }
     return 0;
@@ -1459,15 +1585,24 @@ static size_t shuffle_group(size_t n_shuffles, size_t col_bytes) {
     return n_shuffles <= fit ? n_shuffles : fit ? fit : 1;
 }
 
+// ... and mv-lookup arguments whose two cosets (phi, m) are: the same bound
+static size_t mvlookup_group(size_t n_args, size_t col_bytes) {
+    if (!n_args) return 0;
+    const size_t fit = tune().evalh_lookup_group_bytes / (2 * col_bytes);
+    return n_args <= fit ? n_args : fit ? fit : 1;
+}
+
 // The arena every form of evaluate_h allocates behind its metadata region: the columns the engine itself keeps resident and, in the
 // host-pointer forms, its copy of `values`.  The call paths size their arena here and h2hip_evaluate_h_workspace_bytes reports it.
 //   full form:  columns of 2^ek.  Host: every column of the description, the lookup cosets of one group and `values`; device: only
 //               the cosets the call itself forms (advice, instance, one group of lookups).
 //   parts form: columns of 2^k.  One part's cosets of EVERY column (the key's too: they arrive as polynomials), one group of lookups
 //               and the part's rows of `values`; host: also the coefficient columns, uploaded once, and `values`.
-//   Both forms: one product coset per shuffle of a group (h2hip_evalh_shuffles) on top; nothing for a call without shuffles.
+//   Both forms: one product coset per shuffle of a group (h2hip_evalh_shuffles) and two cosets per mv-lookup argument of a group
+//               (h2hip_evalh_mvlookups) on top; nothing for a call without them.
 static int evaluate_h_workspace_bytes(uint32_t k, uint32_t ek, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance, uint32_t n_perm_sets,
-                                      uint32_t n_perm_columns, uint32_t n_lookups, uint32_t n_shuffles, bool parts, bool dev, size_t* bytes) {
+                                      uint32_t n_perm_columns, uint32_t n_lookups, uint32_t n_mv, uint32_t n_shuffles, bool parts, bool dev,
+                                      size_t* bytes) {
     if (!bytes) {
         set_error("evaluate_h: null argument");
         return 1;
@@ -1482,15 +1617,15 @@ static int evaluate_h_workspace_bytes(uint32_t k, uint32_t ek, uint32_t n_fixed,
         const size_t n_cols = dev ? (size_t)n_advice + n_instance + 3 * lk_group
                                   : (size_t)n_fixed + n_advice + n_instance + 3 /* l0, l_last, l_active */ + n_perm_sets + n_perm_columns +
                                         3 * lk_group /* lookup cosets, reused per group */ + 1 /* values */;
-        *bytes = (n_cols + shuffle_group(n_shuffles, col_bytes)) * (col_bytes + 256) + 4096;
+        *bytes = (n_cols + 2 * mvlookup_group(n_mv, col_bytes) + shuffle_group(n_shuffles, col_bytes)) * (col_bytes + 256) + 4096;
         return 0;
     }
     const size_t part_bytes = align256(sizeof(Fe) << k);
     const size_t key_and_witness = (size_t)n_fixed + n_advice + n_instance + 3 + (n_perm_sets ? (size_t)n_perm_sets + n_perm_columns : 0);
-    const size_t resident = key_and_witness + 3 * lookup_group(n_lookups, part_bytes) + shuffle_group(n_shuffles, part_bytes) +
-                            1 /* the part's rows of values */;
+    const size_t resident = key_and_witness + 3 * lookup_group(n_lookups, part_bytes) + 2 * mvlookup_group(n_mv, part_bytes) +
+                            shuffle_group(n_shuffles, part_bytes) + 1 /* the part's rows of values */;
     *bytes = resident * part_bytes;
-    if (!dev) *bytes += (key_and_witness + 3 * (size_t)n_lookups + n_shuffles) * part_bytes + align256(col_bytes);
+    if (!dev) *bytes += (key_and_witness + 3 * (size_t)n_lookups + 2 * (size_t)n_mv + n_shuffles) * part_bytes + align256(col_bytes);
     return 0;
 }
 
@@ -1499,20 +1634,22 @@ static int evaluate_h_workspace_bytes(uint32_t k, uint32_t ek, uint32_t n_fixed,
 // dev = true:  the columns and `values` are device memory (extended cosets are used where they lie, the first NTT pass reads
 //              coefficient-form polynomials where they lie); the graphs, challenges and scalars stay host pointers; the
 //              kernels are queued on `s` and the call returns without waiting for them.
-int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, const h2hip_evalh_shuffles* sh, uint64_t* values, bool dev, hipStream_t s) {
+int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, const h2hip_evalh_mvlookups* mv, const h2hip_evalh_shuffles* sh, uint64_t* values,
+                    bool dev, hipStream_t s) {
     const uint32_t k = d->k, ek = d->extended_k;
     const size_t n = (size_t)1 << k, size = (size_t)1 << ek;
     const size_t col_bytes = size * sizeof(Fe);
     int rc;
     CallPlan cp;  // programs first: their slot counts size the workspaces
-    if ((rc = call_plan(&d->custom_gates, d->lookup_graphs, d->n_lookups, size, &cp, sh))) return rc;
+    if ((rc = call_plan(&d->custom_gates, d->lookup_graphs, d->n_lookups, size, &cp, sh, mv))) return rc;
     // ---- device arena: [metadata | columns the engine owns]
     // lookup cosets: three buffers per lookup for as many lookups as 2 GB hold (a group); the first group's transforms join the advice /
     // instance batch, later groups reuse the buffers once the kernels of the group before are queued
     const size_t lk_group = lookup_group(d->n_lookups, col_bytes), sh_group = shuffle_group(cp.n_shuffles, col_bytes);
+    const size_t n_mv = cp.mv_inputs.size(), mv_group = mvlookup_group(n_mv, col_bytes);
     size_t arena_bytes;
     if ((rc = evaluate_h_workspace_bytes(k, ek, d->n_fixed, d->n_advice, d->n_instance, d->n_perm_sets, d->n_perm_columns, d->n_lookups,
-                                         (uint32_t)cp.n_shuffles, false, dev, &arena_bytes)))
+                                         (uint32_t)n_mv, (uint32_t)cp.n_shuffles, false, dev, &arena_bytes)))
         return rc;
     const size_t meta_cap = evalh_meta_cap(cp, *d, 0);
     if ((rc = c->evalh_ws.ensure(meta_cap + arena_bytes))) return rc;
@@ -1569,6 +1706,9 @@ int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, const h2hip_evalh_shuffle
         if (!(lbuf[t] = (Fe*)ar.take(col_bytes))) bad = true;
     for (uint32_t i = 0; i < d->n_lookups; i++)
         if (!d->lookup_product_polys[i] || !d->lookup_permuted_input_polys[i] || !d->lookup_permuted_table_polys[i]) bad = true;
+    std::vector<Fe*> mvbuf(2 * mv_group, nullptr);  // one group of mv-lookup cosets: phi, m per argument
+    for (size_t t = 0; t < mvbuf.size(); t++)
+        if (!(mvbuf[t] = (Fe*)ar.take(col_bytes))) bad = true;
     std::vector<Fe*> shbuf(sh_group, nullptr);  // one group of shuffle product cosets
     for (size_t t = 0; t < shbuf.size(); t++)
         if (!(shbuf[t] = (Fe*)ar.take(col_bytes))) bad = true;
@@ -1595,6 +1735,7 @@ int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, const h2hip_evalh_shuffle
     // ---- metadata image
     const ColsDev cols = cols_put(mb, *d, fixed.data(), advice.data(), instance.data(), ek, 1 << (ek - k));
     const std::vector<ProgDev> pds = progs_put(mb, cp);
+    const ProgDev* d_mv_progs = mv_progs_put(mb, cp, pds);
     const Fe ext_omega = fe_from_u64x4(d->extended_omega);
     const Fu *pow_lo = nullptr, *pow_hi = nullptr;
     uint32_t pow_bits = 0;
@@ -1644,8 +1785,17 @@ int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, const h2hip_evalh_shuffle
         }
         return ntt_device_batch(c, shbuf.data(), zsrc.data(), count, ext_omega, ek, &sc, s);
     };
-    if ((rc = constraint_pass(c, cp, pds, cols, pd, l, lbuf.data(), lk_group, shbuf.data(), sh_group, d_values, size, s, late_uploads, next_group,
-                              next_shuffles)))
+    auto next_mv = [&](size_t first, size_t count) -> int {  // every group, the first too: phi and m polynomials -> extended cosets
+        std::vector<const Fe*> msrc(2 * count, nullptr);
+        for (size_t q = 0; q < 2 * count; q++) {
+            const uint64_t* h = q & 1 ? mv->m_polys[first + q / 2] : mv->phi_polys[first + q / 2];
+            if (dev) msrc[q] = (const Fe*)h;
+            else H2_CHECK(hipMemcpyAsync(mvbuf[q], h, n * sizeof(Fe), hipMemcpyHostToDevice, s));
+        }
+        return ntt_device_batch(c, mvbuf.data(), msrc.data(), 2 * count, ext_omega, ek, &sc, s);
+    };
+    if ((rc = constraint_pass(c, cp, pds, cols, pd, l, lbuf.data(), lk_group, d_mv_progs, mvbuf.data(), mv_group, shbuf.data(), sh_group, d_values,
+                              size, s, late_uploads, next_group, next_mv, next_shuffles)))
         return rc;
     if ((rc = guard.release())) return rc;
     if (dev) return 0;
@@ -1801,8 +1951,8 @@ static thread_local uint64_t g_parts_stats[4];
 // dev as in evaluate_h_host.  Host form: every coefficient column that is not pinned crosses once (2^k elements), `values` crosses both
 // ways once.  A key polynomial (fixed_polys, the three Lagrange polynomials, perm_polys) whose part cosets are pinned is read, for part p,
 // where the pin holds that part: no upload, no scale, no transform, no copy and no arena slot.  Any subset of them may hit.
-static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, const h2hip_evalh_shuffles* sh, uint64_t* values, bool dev,
-                                 hipStream_t s) {
+static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, const h2hip_evalh_mvlookups* mv, const h2hip_evalh_shuffles* sh,
+                                 uint64_t* values, bool dev, hipStream_t s) {
     const uint32_t k = d->k, ek = d->extended_k, log_p = ek - k;
     const size_t n = (size_t)1 << k, size = (size_t)1 << ek;
     const size_t part_bytes = align256(n * sizeof(Fe));
@@ -1810,7 +1960,7 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, const 
     const h2hip_evalh_desc f = parts_as_full(*d);  // the counts, the scalars and the permutation layout, where the shared builders read them
     int rc;
     CallPlan cp;
-    if ((rc = call_plan(&d->custom_gates, d->lookup_graphs, d->n_lookups, n, &cp, sh))) return rc;
+    if ((rc = call_plan(&d->custom_gates, d->lookup_graphs, d->n_lookups, n, &cp, sh, mv))) return rc;
     // ---- the coefficient columns, in the order of the batch that transforms them: key and witness columns, then the lookups'
     std::vector<const uint64_t*> polys;
     for (uint32_t i = 0; i < d->n_fixed; i++) polys.push_back(d->fixed_polys[i]);
@@ -1826,9 +1976,12 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, const 
     const size_t n_main = polys.size();  // every part transforms these; the lookups follow in groups
     for (uint32_t i = 0; i < d->n_lookups; i++)
         polys.push_back(d->lookup_product_polys[i]), polys.push_back(d->lookup_permuted_input_polys[i]), polys.push_back(d->lookup_permuted_table_polys[i]);
-    const size_t at_sh = polys.size();  // the shuffles' product polynomials, one each, follow the lookups'
+    const size_t at_mv = polys.size(), n_mv = cp.mv_inputs.size();  // the mv-lookups' phi and m polynomials, a pair each, follow the lookups'
+    for (size_t j = 0; j < n_mv; j++) polys.push_back(mv->phi_polys[j]), polys.push_back(mv->m_polys[j]);
+    const size_t at_sh = polys.size();  // the shuffles' product polynomials, one each, follow those
     for (size_t j = 0; j < cp.n_shuffles; j++) polys.push_back(sh->product_polys[j]);
     const size_t lk_group = lookup_group(d->n_lookups, part_bytes), sh_group = shuffle_group(cp.n_shuffles, part_bytes);
+    const size_t mv_group = mvlookup_group(n_mv, part_bytes);
     const Fe ext_omega = fe_from_u64x4(d->extended_omega);
     const Fe omega = fe_pow_u64<FrP>(ext_omega, (uint64_t)1 << log_p);
     const Fe g_coset = fe_from_u64x4(d->g_coset), g_coset_inv = fe_from_u64x4(d->g_coset_inv);
@@ -1852,14 +2005,15 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, const 
     }
     const size_t n_pinned = n_main - n_live_main;
     const size_t n_first_cols = n_live_main + 3 * lk_group;   // what a part transforms at once: the live key and witness columns, one group of lookups
-    const size_t n_part_cols = n_first_cols + sh_group;      // arena columns of one part: those, and one group of shuffle products
+    const size_t at_sh_cols = n_first_cols + 2 * mv_group;   // ... behind them one group of mv-lookup cosets
+    const size_t n_part_cols = at_sh_cols + sh_group;        // arena columns of one part: those, and one group of shuffle products
     const size_t n_sets = n_pinned ? p_end - p_begin : 1;   // column-pointer tables: one set per part once a pinned column's address depends on it
     // ---- device arena: [metadata | (host form) the live coefficient columns | one part's cosets of them | the part's rows of values |
     //      (host form) values].  h2hip_evaluate_h_workspace_bytes is the upper bound, reached when nothing is pinned: a pinned column takes
     //      neither a coset slot nor, in the host form, a coefficient slot.
     size_t arena_bytes;
     if ((rc = evaluate_h_workspace_bytes(k, ek, d->n_fixed, d->n_advice, d->n_instance, d->n_perm_sets, d->n_perm_columns, d->n_lookups,
-                                         (uint32_t)cp.n_shuffles, true, dev, &arena_bytes)))
+                                         (uint32_t)n_mv, (uint32_t)cp.n_shuffles, true, dev, &arena_bytes)))
         return rc;
     arena_bytes -= n_pinned * part_bytes * (dev ? 1 : 2);
     const size_t set_bytes = (8 + 256) * ((size_t)d->n_fixed + d->n_advice + d->n_instance + d->n_perm_sets + 2 * (size_t)d->n_perm_columns + 16) +
@@ -1919,6 +2073,7 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, const 
         pd_p[t] = perm_put(mb, f, col, advice, advice + d->n_advice, col + at_z, col + at_z + d->n_perm_sets, col + at_l0, pow_lo, pow_hi, pow_bits);
     }
     const std::vector<ProgDev> pds = progs_put(mb, cp);
+    const ProgDev* d_mv_progs = mv_progs_put(mb, cp, pds);
     if (mb.overflow) {
         set_error("evaluate_h: metadata region overflow");
         return 1;
@@ -1984,10 +2139,11 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, const 
         // ---- the pass, over the part's rows: nothing of the permutation's arrives late here, and a later group of lookups is
         //      scaled and transformed into the group's buffers as the first was
         if (d->n_perm_sets) pd.delta_start = to_i(fe_mul<FrP>(beta_zeta, fe_pow_u64<FrP>(ext_omega, p)));  // beta g_p; the kernel multiplies by omega^j
-        if ((rc = constraint_pass(c, cp, pds, cols_p[t], pd, col + at_l0, col + n_main, lk_group, part_cols.data() + n_first_cols, sh_group, d_part,
-                                  n, s, [] { return 0; },
+        if ((rc = constraint_pass(c, cp, pds, cols_p[t], pd, col + at_l0, col + n_main, lk_group, d_mv_progs, part_cols.data() + n_first_cols,
+                                  mv_group, part_cols.data() + at_sh_cols, sh_group, d_part, n, s, [] { return 0; },
                                   [&](size_t first, size_t count) { return to_part(p, n_live_main + 3 * first, n_live_main, 3 * count); },
-                                  [&](size_t first, size_t count) { return to_part(p, slot[at_sh] + first, n_first_cols, count); })))
+                                  [&](size_t first, size_t count) { return to_part(p, slot[at_mv] + 2 * first, n_first_cols, 2 * count); },
+                                  [&](size_t first, size_t count) { return to_part(p, slot[at_sh] + first, at_sh_cols, count); })))
             return rc;
         // ---- scatter
         t_io = c->timer_begin("evalh_part_io", s);
@@ -2183,78 +2339,98 @@ using namespace h2;
 
 extern "C" {
 // ---- C ABI (include/halo2hip.h, evaluate_h) ----------------------------------------------------------------------------------------
-// The four calls without the suffix are the NULL case of the four with it: one validation, one code path.
-int h2hip_evaluate_h_shuffles_bn254(const h2hip_evalh_desc* desc, const h2hip_evalh_shuffles* shuffles, uint64_t* values) {
+// The eight calls without _ext are NULL cases of the four with it: one validation, one code path.
+int h2hip_evaluate_h_ext_bn254(const h2hip_evalh_desc* desc, const h2hip_evalh_mvlookups* mvlookups, const h2hip_evalh_shuffles* shuffles,
+                               uint64_t* values) {
     if (!desc || !values) {
         set_error("evaluate_h: null argument");
         return H2HIP_EINVAL;
     }
-    if (evaluate_h_validate(desc, values) || evaluate_h_shuffles_validate(desc, shuffles)) return H2HIP_EINVAL;
+    if (evaluate_h_validate(desc, values) || evaluate_h_mvlookups_validate(desc, mvlookups) || evaluate_h_shuffles_validate(desc, shuffles))
+        return H2HIP_EINVAL;
     Entry en("h2hip_evaluate_h_bn254");
     if (en.rc) return en.rc;
-    return evaluate_h_host(en.c, desc, shuffles, values, false, en.c->stream);
+    return evaluate_h_host(en.c, desc, mvlookups, shuffles, values, false, en.c->stream);
 }
-int h2hip_evaluate_h_bn254(const h2hip_evalh_desc* desc, uint64_t* values) { return h2hip_evaluate_h_shuffles_bn254(desc, nullptr, values); }
+int h2hip_evaluate_h_shuffles_bn254(const h2hip_evalh_desc* desc, const h2hip_evalh_shuffles* shuffles, uint64_t* values) {
+    return h2hip_evaluate_h_ext_bn254(desc, nullptr, shuffles, values);
+}
+int h2hip_evaluate_h_bn254(const h2hip_evalh_desc* desc, uint64_t* values) { return h2hip_evaluate_h_ext_bn254(desc, nullptr, nullptr, values); }
 
-int h2hip_evaluate_h_shuffles_bn254_device(const h2hip_evalh_desc* desc, const h2hip_evalh_shuffles* shuffles, void* d_values, void* stream) {
+int h2hip_evaluate_h_ext_bn254_device(const h2hip_evalh_desc* desc, const h2hip_evalh_mvlookups* mvlookups, const h2hip_evalh_shuffles* shuffles,
+                                      void* d_values, void* stream) {
     if (!desc || !d_values) {
         set_error("evaluate_h: null argument");
         return H2HIP_EINVAL;
     }
-    if (evaluate_h_validate(desc, d_values) || evaluate_h_shuffles_validate(desc, shuffles)) return H2HIP_EINVAL;
+    if (evaluate_h_validate(desc, d_values) || evaluate_h_mvlookups_validate(desc, mvlookups) || evaluate_h_shuffles_validate(desc, shuffles))
+        return H2HIP_EINVAL;
     Entry en("h2hip_evaluate_h_bn254_device", d_values);
     if (en.rc) return en.rc;
-    return evaluate_h_host(en.c, desc, shuffles, (uint64_t*)d_values, true, (hipStream_t)stream);
+    return evaluate_h_host(en.c, desc, mvlookups, shuffles, (uint64_t*)d_values, true, (hipStream_t)stream);
+}
+int h2hip_evaluate_h_shuffles_bn254_device(const h2hip_evalh_desc* desc, const h2hip_evalh_shuffles* shuffles, void* d_values, void* stream) {
+    return h2hip_evaluate_h_ext_bn254_device(desc, nullptr, shuffles, d_values, stream);
 }
 int h2hip_evaluate_h_bn254_device(const h2hip_evalh_desc* desc, void* d_values, void* stream) {
-    return h2hip_evaluate_h_shuffles_bn254_device(desc, nullptr, d_values, stream);
+    return h2hip_evaluate_h_ext_bn254_device(desc, nullptr, nullptr, d_values, stream);
 }
 
 // ---- evaluate_h one coset of the 2^k domain at a time ---------------------------------------------------------------------------------
-int h2hip_evaluate_h_parts_shuffles_bn254(const h2hip_evalh_parts_desc* desc, const h2hip_evalh_shuffles* shuffles, uint64_t* values) {
+static int parts_extras_validate(const h2hip_evalh_parts_desc* desc, const h2hip_evalh_mvlookups* mvlookups, const h2hip_evalh_shuffles* shuffles) {
+    const h2hip_evalh_desc f = parts_as_full(*desc);
+    return evaluate_h_mvlookups_validate(&f, mvlookups) || evaluate_h_shuffles_validate(&f, shuffles);
+}
+int h2hip_evaluate_h_parts_ext_bn254(const h2hip_evalh_parts_desc* desc, const h2hip_evalh_mvlookups* mvlookups,
+                                     const h2hip_evalh_shuffles* shuffles, uint64_t* values) {
     if (!desc || !values) {
         set_error("evaluate_h: null argument");
         return H2HIP_EINVAL;
     }
-    if (evaluate_h_parts_validate(desc, values)) return H2HIP_EINVAL;
-    {
-        const h2hip_evalh_desc f = parts_as_full(*desc);
-        if (evaluate_h_shuffles_validate(&f, shuffles)) return H2HIP_EINVAL;
-    }
+    if (evaluate_h_parts_validate(desc, values) || parts_extras_validate(desc, mvlookups, shuffles)) return H2HIP_EINVAL;
     Entry en("h2hip_evaluate_h_parts_bn254");
     if (en.rc) return en.rc;
-    return evaluate_h_parts_host(en.c, desc, shuffles, values, false, en.c->stream);
+    return evaluate_h_parts_host(en.c, desc, mvlookups, shuffles, values, false, en.c->stream);
+}
+int h2hip_evaluate_h_parts_shuffles_bn254(const h2hip_evalh_parts_desc* desc, const h2hip_evalh_shuffles* shuffles, uint64_t* values) {
+    return h2hip_evaluate_h_parts_ext_bn254(desc, nullptr, shuffles, values);
 }
 int h2hip_evaluate_h_parts_bn254(const h2hip_evalh_parts_desc* desc, uint64_t* values) {
-    return h2hip_evaluate_h_parts_shuffles_bn254(desc, nullptr, values);
+    return h2hip_evaluate_h_parts_ext_bn254(desc, nullptr, nullptr, values);
 }
 
-int h2hip_evaluate_h_parts_shuffles_bn254_device(const h2hip_evalh_parts_desc* desc, const h2hip_evalh_shuffles* shuffles, void* d_values,
-                                                 void* stream) {
+int h2hip_evaluate_h_parts_ext_bn254_device(const h2hip_evalh_parts_desc* desc, const h2hip_evalh_mvlookups* mvlookups,
+                                            const h2hip_evalh_shuffles* shuffles, void* d_values, void* stream) {
     if (!desc || !d_values) {
         set_error("evaluate_h: null argument");
         return H2HIP_EINVAL;
     }
-    if (evaluate_h_parts_validate(desc, d_values)) return H2HIP_EINVAL;
-    {
-        const h2hip_evalh_desc f = parts_as_full(*desc);
-        if (evaluate_h_shuffles_validate(&f, shuffles)) return H2HIP_EINVAL;
-    }
+    if (evaluate_h_parts_validate(desc, d_values) || parts_extras_validate(desc, mvlookups, shuffles)) return H2HIP_EINVAL;
     Entry en("h2hip_evaluate_h_parts_bn254_device", d_values);
     if (en.rc) return en.rc;
-    return evaluate_h_parts_host(en.c, desc, shuffles, (uint64_t*)d_values, true, (hipStream_t)stream);
+    return evaluate_h_parts_host(en.c, desc, mvlookups, shuffles, (uint64_t*)d_values, true, (hipStream_t)stream);
+}
+int h2hip_evaluate_h_parts_shuffles_bn254_device(const h2hip_evalh_parts_desc* desc, const h2hip_evalh_shuffles* shuffles, void* d_values,
+                                                 void* stream) {
+    return h2hip_evaluate_h_parts_ext_bn254_device(desc, nullptr, shuffles, d_values, stream);
 }
 int h2hip_evaluate_h_parts_bn254_device(const h2hip_evalh_parts_desc* desc, void* d_values, void* stream) {
-    return h2hip_evaluate_h_parts_shuffles_bn254_device(desc, nullptr, d_values, stream);
+    return h2hip_evaluate_h_parts_ext_bn254_device(desc, nullptr, nullptr, d_values, stream);
 }
 
+int h2hip_evaluate_h_ext_workspace_bytes(uint32_t k, uint32_t extended_k, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance,
+                                         uint32_t n_perm_sets, uint32_t n_perm_columns, uint32_t n_lookups, uint32_t n_mvlookups,
+                                         uint32_t n_shuffles, int parts_form, int device_form, size_t* bytes) {
+    return evaluate_h_workspace_bytes(k, extended_k, n_fixed, n_advice, n_instance, n_perm_sets, n_perm_columns, n_lookups, n_mvlookups,
+                                      n_shuffles, parts_form != 0, device_form != 0, bytes)
+               ? H2HIP_EINVAL
+               : 0;
+}
 int h2hip_evaluate_h_shuffles_workspace_bytes(uint32_t k, uint32_t extended_k, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance,
                                               uint32_t n_perm_sets, uint32_t n_perm_columns, uint32_t n_lookups, uint32_t n_shuffles,
                                               int parts_form, int device_form, size_t* bytes) {
-    return evaluate_h_workspace_bytes(k, extended_k, n_fixed, n_advice, n_instance, n_perm_sets, n_perm_columns, n_lookups, n_shuffles,
-                                      parts_form != 0, device_form != 0, bytes)
-               ? H2HIP_EINVAL
-               : 0;
+    return h2hip_evaluate_h_ext_workspace_bytes(k, extended_k, n_fixed, n_advice, n_instance, n_perm_sets, n_perm_columns, n_lookups, 0,
+                                                n_shuffles, parts_form, device_form, bytes);
 }
 int h2hip_evaluate_h_workspace_bytes(uint32_t k, uint32_t extended_k, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance,
                                      uint32_t n_perm_sets, uint32_t n_perm_columns, uint32_t n_lookups, int parts_form, int device_form,

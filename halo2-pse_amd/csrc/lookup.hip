@@ -25,6 +25,7 @@
 //   6. lk_compact_kernel     L compacted in ascending order;
 //   7. lk_final_kernel       A', S'[first] = A'[first], S'[R[j]] = L[|L| - 1 - j], the blinding rows, back to Montgomery form.
 // The host reads the not-found flags once, after the last kernel.  No kernel uses scratch (profiles/lookup_resources.txt).
+// The sort also serves the logUp (mv-lookup) argument's multiplicity column, in a variant that carries each key's row (further down).
 #include <string.h>
 #include <vector>
 #include "engine.h"
@@ -51,9 +52,19 @@ __device__ __forceinline__ uint32_t lk_split(const Fe* A, uint32_t na, const Fe*
 }
 
 // ---- 1. canonical keys, blocks of `block` keys sorted in LDS --------------------------------------------------------------------
-// ts = min(LK_TILE, n) keys per workgroup; block <= ts, both powers of two
-__global__ __launch_bounds__(LK_THREADS) void lk_block_sort_kernel(const Fe* const* src, Fe* const* dst, uint64_t u, uint32_t ts, uint32_t block) {
+// ts = min(LK_TILE, n) keys per workgroup; block <= ts, both powers of two.  ROWS: every key carries its row as a ninth word, the
+// tie-break of equal keys (the mv-lookup multiplicities: a lower bound in the sorted table then lands on the lowest row of a run);
+// rdst[q] receives the rows.  The key-only instantiation compiles to what it was before the template (profiles/lookup_resources.txt).
+template <bool ROWS>
+__device__ __forceinline__ bool lk_pair_lt(const Fe& a, uint32_t ra, const Fe& b, uint32_t rb) {
+    if (!ROWS) return key_lt(a, b);
+    return key_lt(a, b) || (ra < rb && !key_lt(b, a));
+}
+template <bool ROWS>
+__global__ __launch_bounds__(LK_THREADS) void lk_block_sort_kernel(const Fe* const* src, Fe* const* dst, uint32_t* const* rdst, uint64_t u,
+                                                                   uint32_t ts, uint32_t block) {
     __shared__ Fe sk[LK_TILE];
+    __shared__ uint32_t sr[ROWS ? LK_TILE : 1];
     const Fe* in = src[blockIdx.y];
     Fe* out = dst[blockIdx.y];
     const uint64_t base = (uint64_t)blockIdx.x * ts;
@@ -67,6 +78,7 @@ __global__ __launch_bounds__(LK_THREADS) void lk_block_sort_kernel(const Fe* con
             for (int j = 0; j < 8; j++) v.l[j] = 0xffffffffu;
         }
         sk[i] = v;
+        if (ROWS) sr[i] = (uint32_t)r;
     }
     __syncthreads();
     for (uint32_t kk = 2; kk <= block; kk <<= 1)
@@ -75,22 +87,38 @@ __global__ __launch_bounds__(LK_THREADS) void lk_block_sort_kernel(const Fe* con
                 const uint32_t i = 2 * t - (t & (j - 1)), l = i + j;  // the pair (i, i + j), bit j of i clear
                 const bool asc = kk == block || (i & kk) == 0;         // the last stage sorts every block ascending
                 const Fe a = sk[i], b = sk[l];
-                if (key_lt(b, a) == asc) {
+                const uint32_t ra = ROWS ? sr[i] : 0u, rb = ROWS ? sr[l] : 0u;
+                if (lk_pair_lt<ROWS>(b, rb, a, ra) == asc) {
                     sk[i] = b;
                     sk[l] = a;
+                    if (ROWS) {
+                        sr[i] = rb;
+                        sr[l] = ra;
+                    }
                 }
             }
             __syncthreads();
         }
     for (uint32_t i = threadIdx.x; i < ts; i += LK_THREADS) fe_st(out, base + i, sk[i]);
+    if (ROWS) {
+        uint32_t* rout = rdst[blockIdx.y];
+        for (uint32_t i = threadIdx.x; i < ts; i += LK_THREADS) rout[base + i] = sr[i];
+    }
 }
 
 // ---- 2. one merge pass: sorted runs of w keys -> runs of 2w ---------------------------------------------------------------------
-__global__ __launch_bounds__(LK_THREADS) void lk_merge_kernel(const Fe* const* src, Fe* const* dst, uint32_t w, uint32_t ts) {
+// ROWS: the rows travel with their keys (rsrc[q] -> rdst[q]).  The merge takes run A first on ties and every row of A is below every
+// row of B (runs are consecutive row ranges), so equal keys stay in row order without a compare of the rows.
+template <bool ROWS>
+__global__ __launch_bounds__(LK_THREADS) void lk_merge_kernel(const Fe* const* src, Fe* const* dst, const uint32_t* const* rsrc,
+                                                              uint32_t* const* rdst, uint32_t w, uint32_t ts) {
     __shared__ Fe sk[LK_TILE];
+    __shared__ uint32_t sr[ROWS ? LK_TILE : 1];
     __shared__ uint32_t s_a[2];
     const Fe* in = src[blockIdx.y];
     Fe* out = dst[blockIdx.y];
+    const uint32_t* rin = ROWS ? rsrc[blockIdx.y] : nullptr;
+    uint32_t* rout = ROWS ? rdst[blockIdx.y] : nullptr;
     const uint64_t o0 = (uint64_t)blockIdx.x * ts;
     const uint32_t tid = threadIdx.x, t = tid * LK_E;
     const Fe *A, *B;
@@ -106,12 +134,16 @@ __global__ __launch_bounds__(LK_THREADS) void lk_merge_kernel(const Fe* const* s
         na = a1 - a0;
         nb = ts - na;
         for (uint32_t i = tid; i < ts; i += LK_THREADS) sk[i] = i < na ? fe_ld(gA, a0 + i) : fe_ld(gB, b0 + (i - na));
+        if (ROWS)
+            for (uint32_t i = tid; i < ts; i += LK_THREADS) sr[i] = i < na ? rin[pbase + a0 + i] : rin[pbase + w + b0 + (i - na)];
         __syncthreads();
         A = sk;
         B = sk + na;
         d = t;
     } else {  // whole pairs of runs inside the tile
         for (uint32_t i = tid; i < ts; i += LK_THREADS) sk[i] = fe_ld(in, o0 + i);
+        if (ROWS)
+            for (uint32_t i = tid; i < ts; i += LK_THREADS) sr[i] = rin[o0 + i];
         __syncthreads();
         const uint32_t pb = t / (2 * w) * (2 * w);
         A = sk + pb;
@@ -125,6 +157,7 @@ __global__ __launch_bounds__(LK_THREADS) void lk_merge_kernel(const Fe* const* s
     for (int e = 0; e < LK_E; e++) {  // LK_E <= 2w: a thread's outputs lie in one pair
         const bool take_a = ib >= nb || (ia < na && !key_lt(B[ib], A[ia]));
         const Fe x = take_a ? A[ia] : B[ib];
+        if (ROWS) rout[o0 + t + e] = sr[(take_a ? A + ia : B + ib) - sk];
         if (take_a) ia++;
         else ib++;
         fe_st(out, o0 + t + e, x);
@@ -286,21 +319,33 @@ uint32_t lookup_sort_passes(uint32_t k) {
     for (uint64_t w = lk_sort_block((uint32_t)(n < LK_TILE ? n : LK_TILE)); w < n; w <<= 1) passes++;
     return passes;
 }
-int lookup_sort_enqueue(const Fe* const* d_src, Fe* const* d_k0, Fe* const* d_k1, uint32_t cols, uint32_t k, uint64_t u, hipStream_t s) {
+// d_r0 / d_r1 (both or neither): two row buffers of 2^k words per column; the sort then carries each key's row and breaks ties by it
+static int lk_sort_enqueue(const Fe* const* d_src, Fe* const* d_k0, Fe* const* d_k1, uint32_t* const* d_r0, uint32_t* const* d_r1, uint32_t cols,
+                           uint32_t k, uint64_t u, hipStream_t s) {
     const uint64_t n = 1ull << k;
     const uint32_t ts = (uint32_t)(n < LK_TILE ? n : LK_TILE), tiles = (uint32_t)(n / ts), block = lk_sort_block(ts);
     const uint32_t passes = lookup_sort_passes(k);
-    hipLaunchKernelGGL(lk_block_sort_kernel, dim3(tiles, cols), dim3(LK_THREADS), 0, s, d_src, d_k0, u, ts, block);
+    uint32_t* const* no_rows = nullptr;
+    if (d_r0) hipLaunchKernelGGL(lk_block_sort_kernel<true>, dim3(tiles, cols), dim3(LK_THREADS), 0, s, d_src, d_k0, d_r0, u, ts, block);
+    else hipLaunchKernelGGL(lk_block_sort_kernel<false>, dim3(tiles, cols), dim3(LK_THREADS), 0, s, d_src, d_k0, no_rows, u, ts, block);
     H2_CHECK(hipGetLastError());
     uint32_t w = block;
     for (uint32_t p = 0; p < passes; p++, w <<= 1) {
         const Fe* const* from = p & 1 ? (const Fe* const*)d_k1 : (const Fe* const*)d_k0;
-        hipLaunchKernelGGL(lk_merge_kernel, dim3(tiles, cols), dim3(LK_THREADS), 0, s, from, p & 1 ? d_k0 : d_k1, w, ts);
+        if (d_r0)
+            hipLaunchKernelGGL(lk_merge_kernel<true>, dim3(tiles, cols), dim3(LK_THREADS), 0, s, from, p & 1 ? d_k0 : d_k1,
+                               (const uint32_t* const*)(p & 1 ? d_r1 : d_r0), p & 1 ? d_r0 : d_r1, w, ts);
+        else
+            hipLaunchKernelGGL(lk_merge_kernel<false>, dim3(tiles, cols), dim3(LK_THREADS), 0, s, from, p & 1 ? d_k0 : d_k1,
+                               (const uint32_t* const*)nullptr, no_rows, w, ts);
         H2_CHECK(hipGetLastError());
     }
     g_lk_last[0] = block;
     g_lk_last[1] = passes;
     return 0;
+}
+int lookup_sort_enqueue(const Fe* const* d_src, Fe* const* d_k0, Fe* const* d_k1, uint32_t cols, uint32_t k, uint64_t u, hipStream_t s) {
+    return lk_sort_enqueue(d_src, d_k0, d_k1, nullptr, nullptr, cols, k, u, s);
 }
 
 // Validated arguments; columns and outputs are device pointers (in[j], tab[j], pa[j], pt[j] for lookup j), blinding host memory.
@@ -393,6 +438,160 @@ int lookup_permute_device(Ctx* c, uint32_t k, const Fe* const* in, const Fe* con
             set_error("lookup_permute: lookup %zu: an input value is not in the table (ConstraintSystemFailure)", j);
             return H2HIP_ELOOKUP;
         }
+    return 0;
+}
+
+// ---- the logUp (mv-lookup) argument's multiplicity column (include/halo2hip.h, h2hip_mvlookup_multiplicities_bn254) ---------------
+// Plan (mv-lookup).  Per argument the table's (canonical key, row) pairs of rows < u are sorted by the launches above,
+// the row breaking ties, so the lower bound of a value is the lowest table row that holds it.  Then
+//   mv_count_kernel   (tiles x input columns): one lane per input cell -- lower bound in the sorted table, one 32-bit atomic add at the
+//                     found row.  Integer counts do not depend on the order of the additions.  Lanes of a wave that found the same row
+//                     are added up first (MV_ROUNDS leaders, each one atomic for all its followers): the rows of a disabled selector
+//                     all hit one value, and without this every one of them is an atomic on one address;
+//   mv_final_kernel   (tiles x arguments): counts -> Montgomery form, rows >= u zero.
+// A missing value raises its input column's flag: a ballot per wave, an OR over the workgroup's waves, one plain store.  The host reads
+// the flags once and names the lowest (argument, input).
+#ifndef MV_ROUNDS
+#define MV_ROUNDS 4  // leaders per wave; measured against 0, 1 and 64 (mv-lookup)
+#endif
+struct MvArg {             // one argument
+    const Fe* tkeys;       // sorted canonical table keys, all-ones from position u on
+    const uint32_t* trows; // their rows
+    uint32_t* cnt;         // 2^k counts, zero on entry
+    Fe* m;                 // output, Montgomery form
+};
+struct MvCol {             // one input column
+    const Fe* in;          // compressed input, Montgomery form
+    uint32_t arg;
+    uint32_t pad;
+};
+
+__global__ __launch_bounds__(LK_THREADS) void mv_count_kernel(const MvArg* args, const MvCol* cols, uint32_t* flags, uint64_t u) {
+    __shared__ uint32_t s_bad[LK_THREADS / 64];
+    const MvCol C = cols[blockIdx.y];
+    const MvArg A = args[C.arg];
+    const uint64_t i = (uint64_t)blockIdx.x * LK_THREADS + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    bool found = false, bad = false;
+    uint32_t row = 0xffffffffu;
+    if (i < u) {
+        const Fe v = fe_to_canonical<FrP>(fe_ld(C.in, i));
+        uint64_t lo = 0, hi = u;
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi) >> 1;
+            if (key_lt(fe_ld(A.tkeys, mid), v)) lo = mid + 1;
+            else hi = mid;
+        }
+        found = lo < u && fe_eq(fe_ld(A.tkeys, lo), v);
+        bad = !found;
+        if (found) row = A.trows[lo];
+    }
+    // every lane of the wave is here: the lanes that found the leader's row leave with one atomic
+    uint64_t todo = __ballot(found);
+    for (int round = 0; round < MV_ROUNDS && todo; round++) {
+        const int leader = __ffsll((unsigned long long)todo) - 1;
+        const uint32_t r = (uint32_t)__shfl((int)row, leader);
+        const uint64_t same = __ballot(found && row == r) & todo;
+        if (lane == (uint32_t)leader) atomicAdd(A.cnt + r, (uint32_t)__popcll(same));
+        todo &= ~same;
+    }
+    if ((todo >> lane) & 1ull) atomicAdd(A.cnt + row, 1u);
+    const uint64_t wave_bad = __ballot(bad);
+    if (lane == 0) s_bad[threadIdx.x >> 6] = wave_bad != 0;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t any = 0;
+        for (uint32_t w = 0; w < LK_THREADS / 64; w++) any |= s_bad[w];
+        if (any) flags[blockIdx.y] = 1u;
+    }
+}
+
+__global__ __launch_bounds__(LK_THREADS) void mv_final_kernel(const MvArg* args, uint64_t u, uint64_t n) {
+    const MvArg A = args[blockIdx.y];
+    const uint64_t i = (uint64_t)blockIdx.x * LK_THREADS + threadIdx.x;
+    if (i >= n) return;
+    Fe v = fe_zero<FrP>();
+    if (i < u) {
+        v.l[0] = A.cnt[i];
+        v = fe_from_canonical<FrP>(v);
+    }
+    fe_st(A.m, i, v);
+}
+
+// Validated arguments; in (flat, argument-major), tab and m are device pointers.  Enqueues everything on s, then waits for s once to
+// read the flags: H2HIP_ELOOKUP names the lowest failing (argument, input column); every m is written either way.
+int mvlookup_multiplicities_device(Ctx* c, uint32_t k, const Fe* const* in, const uint32_t* n_inputs, const Fe* const* tab, size_t count,
+                                   uint32_t bf, Fe* const* m, hipStream_t s) {
+    if (count == 0) return 0;
+    const uint64_t n = 1ull << k, u = n - bf - 1;
+    const uint32_t passes = lookup_sort_passes(k);
+    size_t total_in = 0;
+    for (size_t j = 0; j < count; j++) total_in += n_inputs[j];
+    const size_t col_bytes = n * sizeof(Fe), row_bytes = n * sizeof(uint32_t);
+    Carve blob;
+    const size_t o_arg = blob.take(count * sizeof(MvArg)), o_col = blob.take(total_in * sizeof(MvCol)), o_ptr = blob.take(5 * count * sizeof(void*));
+    Carve ws;
+    const size_t o_keys = ws.take_packed(2 * count * col_bytes), o_rows = ws.take_packed(2 * count * row_bytes);
+    const size_t o_cnt = ws.take(count * row_bytes), o_flag = ws.take(total_in * sizeof(uint32_t)), o_blob = ws.take(blob.total);
+    int rc = c->ws_acquire(s);
+    if (rc) return rc;
+    WsGuard guard(c, s);
+    if ((rc = c->lookup_ws.ensure(ws.total))) return rc;
+    if ((rc = c->lookup_flag.ensure(total_in * sizeof(uint32_t)))) return rc;
+    char* base = (char*)c->lookup_ws.p;
+    Fe* keys = (Fe*)(base + o_keys);
+    uint32_t* rows = (uint32_t*)(base + o_rows);
+    uint32_t* cnt = (uint32_t*)(base + o_cnt);
+    uint32_t* d_flag = (uint32_t*)(base + o_flag);
+    std::vector<char> h(blob.total, 0);
+    const Blob img{h.data(), base + o_blob};
+    const Mirror<MvArg> arg = img.at<MvArg>(o_arg);
+    const Mirror<MvCol> col = img.at<MvCol>(o_col);
+    const Mirror<const Fe*> src = img.at<const Fe*>(o_ptr);  // one table: sources [0, count), key buffers 0 and 1, row buffers 0 and 1
+    const Mirror<Fe*> kbuf = img.at<Fe*>(o_ptr);
+    const Mirror<uint32_t*> rbuf = img.at<uint32_t*>(o_ptr);
+    size_t q = 0;
+    for (size_t j = 0; j < count; j++) {
+        src.h[j] = tab[j];
+        kbuf.h[count + j] = keys + j * n;
+        kbuf.h[2 * count + j] = keys + (count + j) * n;
+        rbuf.h[3 * count + j] = rows + j * n;
+        rbuf.h[4 * count + j] = rows + (count + j) * n;
+        MvArg& A = arg.h[j];
+        A.tkeys = passes & 1 ? kbuf.h[2 * count + j] : kbuf.h[count + j];  // where the last pass leaves them
+        A.trows = passes & 1 ? rbuf.h[4 * count + j] : rbuf.h[3 * count + j];
+        A.cnt = cnt + j * n;
+        A.m = m[j];
+        for (uint32_t t = 0; t < n_inputs[j]; t++, q++) {
+            col.h[q].in = in[q];
+            col.h[q].arg = (uint32_t)j;
+        }
+    }
+    if ((rc = c->stage_h2d(img.d, img.h, blob.total, s))) return rc;
+    H2_CHECK(hipMemsetAsync(cnt, 0, count * row_bytes, s));
+    H2_CHECK(hipMemsetAsync(d_flag, 0, total_in * sizeof(uint32_t), s));
+    int tm = c->timer_begin("mvlookup_multiplicities", s);
+    if ((rc = lk_sort_enqueue(src.d, kbuf.d + count, kbuf.d + 2 * count, rbuf.d + 3 * count, rbuf.d + 4 * count, (uint32_t)count, k, u, s))) return rc;
+    const uint32_t tiles_u = (uint32_t)((u + LK_THREADS - 1) / LK_THREADS), tiles_n = (uint32_t)((n + LK_THREADS - 1) / LK_THREADS);
+    for (size_t c0 = 0; c0 < total_in; c0 += 65535) {  // grid.y holds 65535 columns
+        const size_t cn = total_in - c0 < 65535 ? total_in - c0 : 65535;
+        hipLaunchKernelGGL(mv_count_kernel, dim3(tiles_u, (uint32_t)cn), dim3(LK_THREADS), 0, s, arg.d, col.d + c0, d_flag + c0, u);
+        H2_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(mv_final_kernel, dim3(tiles_n, (uint32_t)count), dim3(LK_THREADS), 0, s, arg.d, u, n);
+    H2_CHECK(hipGetLastError());
+    c->timer_end(tm, s);
+    H2_CHECK(hipMemcpyAsync(c->lookup_flag.p, d_flag, total_in * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if ((rc = guard.release())) return rc;
+    H2_CHECK(hipStreamSynchronize(s));  // the caller must know before it commits
+    const uint32_t* flags = (const uint32_t*)c->lookup_flag.p;
+    q = 0;
+    for (size_t j = 0; j < count; j++)
+        for (uint32_t t = 0; t < n_inputs[j]; t++, q++)
+            if (flags[q]) {
+                set_error("mvlookup_multiplicities: argument %zu, input %u: an input value is not in the table (ConstraintSystemFailure)", j, t);
+                return H2HIP_ELOOKUP;
+            }
     return 0;
 }
 
@@ -542,6 +741,83 @@ int h2hip_lookup_permute_bn254(uint32_t k, const uint64_t* const* compressed_inp
     }
     H2_CHECK(hipStreamSynchronize(s));
     return 0;
+}
+
+// ---- the mv-lookup multiplicities ------------------------------------------------------------------------------------------------
+static int multiplicities_check(uint32_t k, const void* const* in, const uint32_t* n_inputs, const void* const* tab, size_t count, uint32_t bf,
+                                const void* const* m, size_t* total_in) {
+    const char* what = "mvlookup_multiplicities";
+    if (int rc = check_k_blinding(what, k, bf)) return rc;
+    if (count > 65535) {
+        set_error("%s: count %zu > 65535", what, count);
+        return H2HIP_EINVAL;
+    }
+    if (count && !n_inputs) {
+        set_error("%s: null n_inputs", what);
+        return H2HIP_EINVAL;
+    }
+    size_t total = 0;
+    for (size_t j = 0; j < count; j++) {
+        if (n_inputs[j] < 1 || n_inputs[j] > 255) {
+            set_error("%s: n_inputs[%zu] = %u, not in [1, 255]", what, j, n_inputs[j]);
+            return H2HIP_EINVAL;
+        }
+        if (((uint64_t)n_inputs[j] << k) > 0xffffffffull) {  // every cell could hit one row: the counts are 32-bit
+            set_error("%s: n_inputs[%zu] = %u columns of 2^%u rows exceed a 32-bit count", what, j, n_inputs[j], k);
+            return H2HIP_EINVAL;
+        }
+        total += n_inputs[j];
+    }
+    if (check_ptrs(what, in, total, "compressed_input") || check_ptrs(what, tab, count, "compressed_table") || check_ptrs(what, m, count, "m"))
+        return H2HIP_EINVAL;
+    *total_in = total;
+    return 0;
+}
+
+int h2hip_mvlookup_multiplicities_bn254_device(uint32_t k, const void* const* d_compressed_inputs, const uint32_t* n_inputs,
+                                               const void* const* d_compressed_tables, size_t count, uint32_t blinding_factors, void* const* d_m,
+                                               void* stream) {
+    size_t total_in;
+    if (int rc = multiplicities_check(k, d_compressed_inputs, n_inputs, d_compressed_tables, count, blinding_factors, (const void* const*)d_m, &total_in))
+        return rc;
+    if (count == 0) return 0;
+    Entry en("h2hip_mvlookup_multiplicities_bn254_device", d_m[0]);
+    if (en.rc) return en.rc;
+    return mvlookup_multiplicities_device(en.c, k, (const Fe* const*)d_compressed_inputs, n_inputs, (const Fe* const*)d_compressed_tables, count,
+                                          blinding_factors, (Fe* const*)d_m, (hipStream_t)stream);
+}
+
+int h2hip_mvlookup_multiplicities_bn254(uint32_t k, const uint64_t* const* compressed_inputs, const uint32_t* n_inputs,
+                                        const uint64_t* const* compressed_tables, size_t count, uint32_t blinding_factors, uint64_t* const* m) {
+    size_t total_in;
+    if (int rc = multiplicities_check(k, (const void* const*)compressed_inputs, n_inputs, (const void* const*)compressed_tables, count,
+                                      blinding_factors, (const void* const*)m, &total_in))
+        return rc;
+    if (count == 0) return 0;
+    Entry en("h2hip_mvlookup_multiplicities_bn254");
+    if (en.rc) return en.rc;
+    Ctx* c = en.c;
+    hipStream_t s = c->stream;
+    const size_t n = (size_t)1 << k, bytes = n * sizeof(Fe);
+    int rc = c->lookup_io.ensure((total_in + 2 * count) * bytes);
+    if (rc) return rc;
+    char* io = (char*)c->lookup_io.p;
+    std::vector<const Fe*> in(total_in), tab(count);
+    std::vector<Fe*> d_m(count);
+    for (size_t q = 0; q < total_in; q++) {
+        in[q] = (const Fe*)(io + q * bytes);
+        H2_CHECK(hipMemcpyAsync((void*)in[q], compressed_inputs[q], bytes, hipMemcpyHostToDevice, s));
+    }
+    for (size_t j = 0; j < count; j++) {
+        tab[j] = (const Fe*)(io + (total_in + 2 * j) * bytes);
+        d_m[j] = (Fe*)(io + (total_in + 2 * j + 1) * bytes);
+        H2_CHECK(hipMemcpyAsync((void*)tab[j], compressed_tables[j], bytes, hipMemcpyHostToDevice, s));
+    }
+    const int verdict = mvlookup_multiplicities_device(c, k, in.data(), n_inputs, tab.data(), count, blinding_factors, d_m.data(), s);
+    if (verdict && verdict != H2HIP_ELOOKUP) return verdict;
+    for (size_t j = 0; j < count; j++) H2_CHECK(hipMemcpyAsync(m[j], d_m[j], bytes, hipMemcpyDeviceToHost, s));  // written either way
+    H2_CHECK(hipStreamSynchronize(s));
+    return verdict;
 }
 
 int h2hip_debug_set_lookup_sort(uint32_t lds_keys) {

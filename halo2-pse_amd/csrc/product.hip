@@ -8,6 +8,8 @@
 //       lp_i = (A_i + beta)(S_i + gamma) * inv((A'_i + beta)(S'_i + gamma)), z[0] = 1;
 //   shuffle::Argument::commit_product (upstream PSE halo2, later than the reference: DESIGN.md §2): the same with
 //       sp_i = (A_i + gamma) * inv(S_i + gamma), z[0] = 1;
+//   the logUp (mv-lookup) argument's grand sum (later than the reference too: DESIGN.md §2), additive where those are products:
+//       phi[0] = 0, phi[i] = phi[i-1] + sum_c inv(F_c[i-1] + beta) - M[i-1] inv(T[i-1] + beta) -- its kernels are mvs_* below;
 //   ff::BatchInvert (prover.rs:117, lookup/prover.rs:208), where a zero stays zero.
 //
 // Plan (Grand products).  With e_0 = 1, e_i = num_{i-1} and d_i = den_i (d_u = 1), every z row i <= u is
@@ -333,6 +335,111 @@ __global__ __launch_bounds__(PROD_THREADS) void prod_apply_kernel(const ProdDesc
         for (uint32_t j = tid; j < P.bf; j += PROD_THREADS) fe_st(D.z, P.u + 1 + j, D.blind[j]);
 }
 
+// ---- the logUp (mv-lookup) argument's grand sum (include/halo2hip.h, h2hip_mvlookup_sums_bn254) ----------------------------
+// phi[0] = 0, phi[i] = phi[i-1] + sum_c inv(F_c[i-1] + beta) - M[i-1] inv(T[i-1] + beta) for 1 <= i <= u.  Plan (DESIGN.md §5,
+// mv-lookup): every denominator of the call -- (K_j + 1) u per argument -- goes into one array, which the PROD_INVERT path above
+// inverts with ONE field inversion (a zero stays zero, so that term drops out and the sum goes on); then an additive reduce-then-scan
+// with the products' three stages and no inter-workgroup waiting:
+//   mvs_sum_kernel    (tiles x arguments): the terms of R consecutive rows per thread, per-thread and per-tile sums;
+//   mvs_tiles_kernel  (one workgroup per argument): exclusive scan of the tile sums;
+//   mvs_apply_kernel  (tiles x arguments): phi rows 0 .. u from the prefixes (the terms are formed again: K + 1 loads and one product
+//                     are cheaper than a column of terms written and read), the blinding rows.
+struct MvSumDesc {        // one argument
+    const Fe* inv;        // the inverted denominators: input c at inv + c u, the table at inv + K u
+    const Fe* m;          // multiplicities (2^k)
+    Fe* phi;              // output column (2^k)
+    Fe* thr;              // per-thread sums, tiles x PROD_THREADS
+    Fe* tile;             // per-tile sums, then their exclusive scan
+    const Fe* blind;      // blinding_factors values for rows n - b .. n - 1
+    uint32_t K;           // input columns
+    uint32_t pad;
+};
+struct MvDenCol {         // one column of denominators
+    const Fe* col;
+    Fe* out;
+};
+
+__global__ __launch_bounds__(PROD_THREADS) void mvs_den_kernel(const MvDenCol* cols, uint64_t u, Fe beta) {
+    const MvDenCol C = cols[blockIdx.y];
+    const uint64_t i = (uint64_t)blockIdx.x * PROD_THREADS + threadIdx.x;
+    if (i < u) fe_st(C.out, i, fe_add<FrP>(fe_ld(C.col, i), beta));
+}
+
+__device__ __forceinline__ Fe mvs_term(const MvSumDesc& D, uint64_t u, uint64_t i) {
+    Fe t = fe_ld(D.inv, i);
+    for (uint32_t c = 1; c < D.K; c++) t = fe_add<FrP>(t, fe_ld(D.inv, c * u + i));
+    return fe_sub<FrP>(t, fe_mul<FrP>(fe_ld(D.m, i), fe_ld(D.inv, D.K * u + i)));
+}
+
+// exclusive sum over the threads in order; *total = sum of all; lds holds PROD_THREADS elements
+__device__ Fe block_sum_excl(Fe v, Fe* lds, Fe* total) {
+    const uint32_t t = threadIdx.x;
+    lds[t] = v;
+    __syncthreads();
+    for (uint32_t off = 1; off < PROD_THREADS; off <<= 1) {
+        Fe o = t >= off ? lds[t - off] : fe_zero<FrP>();
+        __syncthreads();
+        v = fe_add<FrP>(v, o);
+        lds[t] = v;
+        __syncthreads();
+    }
+    Fe ex = t ? lds[t - 1] : fe_zero<FrP>();
+    if (total) *total = lds[PROD_THREADS - 1];
+    __syncthreads();
+    return ex;
+}
+
+// P.L = u + 1 indices (the rows of phi the scan writes); index i < u carries the term of row i
+__global__ __launch_bounds__(PROD_THREADS) void mvs_sum_kernel(const MvSumDesc* descs, ProdParams P) {
+    __shared__ Fe lds[PROD_THREADS];
+    const MvSumDesc D = descs[blockIdx.y];
+    const uint32_t tid = threadIdx.x, tile = blockIdx.x;
+    const uint64_t ti = (uint64_t)tile * PROD_THREADS + tid, i0 = ti * P.R;
+    Fe sum = fe_zero<FrP>();
+    if (i0 < P.u) {
+        const uint64_t i1 = i0 + P.R < P.u ? i0 + P.R : P.u;
+        for (uint64_t i = i0; i < i1; i++) sum = fe_add<FrP>(sum, mvs_term(D, P.u, i));
+    }
+    fe_st(D.thr, ti, sum);
+    lds[tid] = sum;
+    __syncthreads();
+    for (uint32_t h = PROD_THREADS / 2; h > 0; h >>= 1) {
+        if (tid < h) lds[tid] = fe_add<FrP>(lds[tid], lds[tid + h]);
+        __syncthreads();
+    }
+    if (tid == 0) fe_st(D.tile, tile, lds[0]);
+}
+
+__global__ __launch_bounds__(PROD_THREADS) void mvs_tiles_kernel(const MvSumDesc* descs, ProdParams P) {
+    __shared__ Fe lds[PROD_THREADS];
+    const MvSumDesc D = descs[blockIdx.x];
+    const uint32_t tid = threadIdx.x, T = P.tiles;
+    Fe carry = fe_zero<FrP>(), tot;
+    for (uint32_t base = 0; base < T; base += PROD_THREADS) {
+        const uint32_t j = base + tid;
+        Fe ex = block_sum_excl(j < T ? fe_ld(D.tile, j) : fe_zero<FrP>(), lds, &tot);
+        if (j < T) fe_st(D.tile, j, fe_add<FrP>(carry, ex));
+        carry = fe_add<FrP>(carry, tot);
+    }
+}
+
+__global__ __launch_bounds__(PROD_THREADS) void mvs_apply_kernel(const MvSumDesc* descs, ProdParams P) {
+    __shared__ Fe lds[PROD_THREADS];
+    const MvSumDesc D = descs[blockIdx.y];
+    const uint32_t tid = threadIdx.x, tile = blockIdx.x;
+    const uint64_t ti = (uint64_t)tile * PROD_THREADS + tid, i0 = ti * P.R;
+    Fe acc = fe_add<FrP>(fe_ld(D.tile, tile), block_sum_excl(fe_ld(D.thr, ti), lds, nullptr));
+    if (i0 < P.L) {
+        const uint64_t i1 = i0 + P.R < P.L ? i0 + P.R : P.L;
+        for (uint64_t i = i0; i < i1; i++) {
+            fe_st(D.phi, i, acc);
+            if (i < P.u) acc = fe_add<FrP>(acc, mvs_term(D, P.u, i));
+        }
+    }
+    if (tile == 0)
+        for (uint32_t j = tid; j < P.bf; j += PROD_THREADS) fe_st(D.phi, P.u + 1 + j, D.blind[j]);
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------
 static uint32_t prod_rows_per_thread(uint64_t L, size_t n_args) {
     // about 2^17 threads in flight over all arguments (8 waves per CU): fewer rows per thread when the call is small
@@ -508,6 +615,78 @@ int batch_invert_device(Ctx* c, Fe* d_a, uint64_t n, hipStream_t s) {
     Fe one = fe_one<FrP>();
     Fe* z[1] = {d_a};
     return products_run(c, PROD_INVERT, n, n, n, one, one, one, one, nullptr, nullptr, 0, 1, 1, nullptr, 0, z, s);
+}
+
+// The grand sums of `count` mv-lookup arguments.  The denominators live in mvsum_ws, not in the workspace batch_invert_device takes.
+int mvlookup_sums_device(Ctx* c, uint32_t k, const Fe& beta, const Fe* const* inputs, const uint32_t* n_inputs, const Fe* const* tables,
+                         const Fe* const* m, size_t count, const uint64_t* blinding, uint32_t bf, Fe* const* phi, hipStream_t s) {
+    if (count == 0) return 0;
+    const uint64_t n = 1ull << k, u = n - bf - 1, L = u + 1;
+    size_t n_cols = count;  // denominator columns: every input, every table
+    for (size_t j = 0; j < count; j++) n_cols += n_inputs[j];
+    const uint32_t R = prod_rows_per_thread(L, count);
+    const uint64_t tile_rows = (uint64_t)PROD_THREADS * R, tiles = (L + tile_rows - 1) / tile_rows;
+    Carve arg;
+    const size_t o_thr = arg.take(tiles * PROD_THREADS * sizeof(Fe)), o_tile = arg.take(tiles * sizeof(Fe));
+    Carve blob;
+    const size_t o_desc = blob.take(count * sizeof(MvSumDesc)), o_col = blob.take(n_cols * sizeof(MvDenCol));
+    const size_t o_blind = blob.take(count * (size_t)bf * sizeof(Fe));
+    Carve ws;
+    const size_t o_den = ws.take(n_cols * u * sizeof(Fe)), o_args = ws.take(count * arg.total), o_blob = ws.take(blob.total);
+    int rc = c->ws_acquire(s);
+    if (rc) return rc;
+    WsGuard guard(c, s);
+    if ((rc = c->mvsum_ws.ensure(ws.total))) return rc;
+    char* base = (char*)c->mvsum_ws.p;
+    Fe* den = (Fe*)(base + o_den);
+    std::vector<char> h(blob.total, 0);
+    const Blob img{h.data(), base + o_blob};
+    const Mirror<MvSumDesc> desc = img.at<MvSumDesc>(o_desc);
+    const Mirror<MvDenCol> col = img.at<MvDenCol>(o_col);
+    const Mirror<Fe> blind = img.at<Fe>(o_blind);
+    if (bf) memcpy(blind.h, blinding, count * (size_t)bf * sizeof(Fe));
+    size_t q = 0, qi = 0;
+    for (size_t j = 0; j < count; j++) {
+        MvSumDesc& D = desc.h[j];
+        char* ab = base + o_args + j * arg.total;
+        D.inv = den + q * u;
+        D.m = m[j];
+        D.phi = phi[j];
+        D.thr = (Fe*)(ab + o_thr);
+        D.tile = (Fe*)(ab + o_tile);
+        D.blind = blind.d + j * (size_t)bf;
+        D.K = n_inputs[j];
+        for (uint32_t t = 0; t <= n_inputs[j]; t++, q++) {
+            col.h[q].col = t < n_inputs[j] ? inputs[qi++] : tables[j];
+            col.h[q].out = den + q * u;
+        }
+    }
+    if ((rc = c->stage_h2d(img.d, img.h, blob.total, s))) return rc;
+    ProdParams P;
+    memset(&P, 0, sizeof(P));
+    P.n = n;
+    P.L = L;
+    P.u = u;
+    P.R = R;
+    P.tiles = (uint32_t)tiles;
+    P.bf = bf;
+    int tm = c->timer_begin("mvlookup_sums", s);
+    const uint32_t den_tiles = (uint32_t)((u + PROD_THREADS - 1) / PROD_THREADS);
+    for (size_t c0 = 0; c0 < n_cols; c0 += 65535) {  // grid.y holds 65535 columns
+        const size_t cn = n_cols - c0 < 65535 ? n_cols - c0 : 65535;
+        hipLaunchKernelGGL(mvs_den_kernel, dim3(den_tiles, (uint32_t)cn), dim3(PROD_THREADS), 0, s, col.d + c0, u, beta);
+        H2_CHECK(hipGetLastError());
+    }
+    if ((rc = batch_invert_device(c, den, n_cols * u, s))) return rc;  // the call's one field inversion
+    const dim3 grid((uint32_t)tiles, (uint32_t)count);
+    hipLaunchKernelGGL(mvs_sum_kernel, grid, dim3(PROD_THREADS), 0, s, desc.d, P);
+    H2_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(mvs_tiles_kernel, dim3((uint32_t)count), dim3(PROD_THREADS), 0, s, desc.d, P);
+    H2_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(mvs_apply_kernel, grid, dim3(PROD_THREADS), 0, s, desc.d, P);
+    H2_CHECK(hipGetLastError());
+    c->timer_end(tm, s);
+    return guard.release();
 }
 
 }  // namespace h2
@@ -746,6 +925,103 @@ int h2hip_shuffle_products_bn254(uint32_t k, const uint64_t gamma[4], const uint
     if (rc) return rc;
     for (size_t j = 0; j < count; j++) H2_CHECK(hipMemcpyAsync(z[j], d_z[j], bytes, hipMemcpyDeviceToHost, s));
     H2_CHECK(hipStreamSynchronize(s));
+    return 0;
+}
+
+static int mvsums_check(uint32_t k, const uint64_t beta[4], const void* const* in, const uint32_t* n_inputs, const void* const* tab,
+                        const void* const* m, size_t count, const uint64_t* blinding, uint32_t bf, const void* const* phi, size_t* total_in) {
+    const char* what = "mvlookup_sums";
+    if (!beta) {
+        set_error("%s: null scalar", what);
+        return H2HIP_EINVAL;
+    }
+    if (check_fr(beta, "beta")) return H2HIP_EINVAL;
+    if (count > 65535) {
+        set_error("%s: count %zu > 65535", what, count);
+        return H2HIP_EINVAL;
+    }
+    if (int rc = products_check_common(what, k, bf, blinding, count)) return rc;
+    if (count && !n_inputs) {
+        set_error("%s: null n_inputs", what);
+        return H2HIP_EINVAL;
+    }
+    size_t total = 0;
+    for (size_t j = 0; j < count; j++) {
+        if (n_inputs[j] < 1 || n_inputs[j] > 255) {
+            set_error("%s: n_inputs[%zu] = %u, not in [1, 255]", what, j, n_inputs[j]);
+            return H2HIP_EINVAL;
+        }
+        total += n_inputs[j];
+    }
+    if (((total + count) << k) > ((size_t)1 << 30)) {  // one batch inversion takes them all
+        set_error("%s: %zu columns of 2^%u denominators > 2^30", what, total + count, k);
+        return H2HIP_EINVAL;
+    }
+    if (check_ptrs(what, in, total, "compressed_input") || check_ptrs(what, tab, count, "compressed_table") || check_ptrs(what, m, count, "m") ||
+        check_ptrs(what, phi, count, "phi"))
+        return H2HIP_EINVAL;
+    *total_in = total;
+    return 0;
+}
+
+int h2hip_mvlookup_sums_bn254_device(uint32_t k, const uint64_t beta[4], const void* const* d_compressed_inputs, const uint32_t* n_inputs,
+                                     const void* const* d_compressed_tables, const void* const* d_m, size_t count, const uint64_t* blinding,
+                                     uint32_t blinding_factors, void* const* d_phi, void* stream) {
+    size_t total_in;
+    if (int rc = mvsums_check(k, beta, d_compressed_inputs, n_inputs, d_compressed_tables, d_m, count, blinding, blinding_factors,
+                              (const void* const*)d_phi, &total_in))
+        return rc;
+    if (count == 0) return 0;
+    Entry en("h2hip_mvlookup_sums_bn254_device", d_phi[0]);
+    if (en.rc) return en.rc;
+    return mvlookup_sums_device(en.c, k, fe_from_u64x4(beta), (const Fe* const*)d_compressed_inputs, n_inputs, (const Fe* const*)d_compressed_tables,
+                                (const Fe* const*)d_m, count, blinding, blinding_factors, (Fe* const*)d_phi, (hipStream_t)stream);
+}
+
+int h2hip_mvlookup_sums_bn254(uint32_t k, const uint64_t beta[4], const uint64_t* const* compressed_inputs, const uint32_t* n_inputs,
+                              const uint64_t* const* compressed_tables, const uint64_t* const* m, size_t count, const uint64_t* blinding,
+                              uint32_t blinding_factors, uint64_t* const* phi) {
+    size_t total_in;
+    if (int rc = mvsums_check(k, beta, (const void* const*)compressed_inputs, n_inputs, (const void* const*)compressed_tables,
+                              (const void* const*)m, count, blinding, blinding_factors, (const void* const*)phi, &total_in))
+        return rc;
+    if (count == 0) return 0;
+    Entry en("h2hip_mvlookup_sums_bn254");
+    if (en.rc) return en.rc;
+    Ctx* c = en.c;
+    hipStream_t s = c->stream;
+    const size_t n = (size_t)1 << k, bytes = n * sizeof(Fe);
+    int rc = c->prod_io.ensure((total_in + 3 * count) * bytes);
+    if (rc) return rc;
+    char* io = (char*)c->prod_io.p;
+    std::vector<const Fe*> in(total_in), tab(count), d_m(count);
+    std::vector<Fe*> d_phi(count);
+    for (size_t q = 0; q < total_in; q++) {
+        in[q] = (const Fe*)(io + q * bytes);
+        H2_CHECK(hipMemcpyAsync((void*)in[q], compressed_inputs[q], bytes, hipMemcpyHostToDevice, s));
+    }
+    for (size_t j = 0; j < count; j++) {
+        tab[j] = (const Fe*)(io + (total_in + 3 * j) * bytes);
+        d_m[j] = (const Fe*)(io + (total_in + 3 * j + 1) * bytes);
+        d_phi[j] = (Fe*)(io + (total_in + 3 * j + 2) * bytes);
+        H2_CHECK(hipMemcpyAsync((void*)tab[j], compressed_tables[j], bytes, hipMemcpyHostToDevice, s));
+        H2_CHECK(hipMemcpyAsync((void*)d_m[j], m[j], bytes, hipMemcpyHostToDevice, s));
+    }
+    rc = mvlookup_sums_device(c, k, fe_from_u64x4(beta), in.data(), n_inputs, tab.data(), d_m.data(), count, blinding, blinding_factors,
+                              d_phi.data(), s);
+    if (rc) return rc;
+    for (size_t j = 0; j < count; j++) H2_CHECK(hipMemcpyAsync(phi[j], d_phi[j], bytes, hipMemcpyDeviceToHost, s));
+    H2_CHECK(hipStreamSynchronize(s));
+    return 0;
+}
+
+// rows per thread of the grand sum's scan for a call of `count` arguments: the rule the code itself applies (tests pick their case by it)
+int h2hip_debug_mvlookup_sum_rows(uint32_t k, uint32_t blinding_factors, size_t count, uint32_t* rows) {
+    if (!rows || check_k_blinding("debug_mvlookup_sum_rows", k, blinding_factors)) {
+        if (!rows) set_error("debug_mvlookup_sum_rows: null argument");
+        return H2HIP_EINVAL;
+    }
+    *rows = prod_rows_per_thread(((uint64_t)1 << k) - blinding_factors, count);
     return 0;
 }
 

@@ -8,6 +8,8 @@
   ValueSource / Calculation / Graph / EvalhDesc    ctypes mirrors of the h2hip_* structs;  DescHolder builds one from numpy arrays
   EvalhShuffles / ShufflesHolder / shuffle_graphs / shuffle_required_degree    the shuffle argument of upstream PSE halo2, which is later
                    than the reference (h2hip_evalh_shuffles; the definitions are the header's)
+  EvalhMvLookups / MvLookupsHolder / mvlookup_graphs / mvlookup_required_degree    the logUp (mv-lookup) argument of the upstream forks that
+                   replaced the permuted-column lookup, also later than the reference (h2hip_evalh_mvlookups; the header's definitions)
   EvalhPartsDesc / PartsDescHolder / Evaluator.evaluate_h_parts    the same one coset of the 2^k domain at a time, every column given
                    as a polynomial of 2^k coefficients (h2hip_evaluate_h_parts_bn254[_device])
 
@@ -193,6 +195,31 @@ def shuffle_required_degree(input_exprs, shuffle_exprs):
     return 2 + max([1] + [expression_degree(e) for e in list(input_exprs) + list(shuffle_exprs)])
 
 
+def mvlookup_graphs(inputs_exprs, table_exprs):
+    """The K + 1 graphs of one mv-lookup argument (h2hip_evalh_mvlookups): inputs_exprs is the list of the K input expression tuples that
+    share the table.  Per tuple, add_expression of each expression, Horner(Constant(0), parts, Theta), then Add(that, Beta) -- the values
+    F_c + beta and T + beta.  Returns (input graph 0, ..., input graph K - 1, table graph)."""
+    if not len(inputs_exprs):
+        raise ValueError("an mv-lookup argument has K >= 1 input tuples")
+    out = []
+    for exprs in list(inputs_exprs) + [table_exprs]:
+        g = GraphEvaluator()
+        parts = tuple(g.add_expression(e) for e in exprs)
+        compressed = g.add_calculation((CALC_HORNER, (VS_CONSTANT, 0, 0), (VS_THETA, 0, 0), parts))
+        g.add_calculation((CALC_ADD, compressed, (VS_BETA, 0, 0), ()))
+        out.append(g)
+    return tuple(out)
+
+
+def mvlookup_required_degree(inputs_exprs, table_exprs):
+    """2 + d_t + sum_c d_c: each d the largest degree in that tuple, at least 1 (the third constraint multiplies l_active_row, one row
+    of phi or m, tau and every f_c)"""
+    if not len(inputs_exprs):
+        raise ValueError("an mv-lookup argument has K >= 1 input tuples")
+    d = lambda exprs: max([1] + [expression_degree(e) for e in exprs])  # noqa: E731
+    return 2 + d(table_exprs) + sum(d(inp) for inp in inputs_exprs)
+
+
 def gate_check_graphs(gate_polys):
     """The witness check's graphs (h2hip_check_gates_bn254): one per gate polynomial, add_expression of that polynomial alone, its value
     designated by a closing Store calculation -- so a bare query or a constant is a polynomial like any other.  None stands for the
@@ -273,8 +300,43 @@ class EvalhShuffles(ctypes.Structure):
     _fields_ = [("n_shuffles", ctypes.c_uint32), ("graphs", ctypes.c_void_p), ("product_polys", ctypes.c_void_p)]
 
 
+class EvalhMvLookups(ctypes.Structure):
+    """h2hip_evalh_mvlookups"""
+    _fields_ = [("n_args", ctypes.c_uint32), ("n_inputs", ctypes.c_void_p), ("graphs", ctypes.c_void_p), ("phi_polys", ctypes.c_void_p),
+                ("m_polys", ctypes.c_void_p)]
+
+
 def _ptr(a):
     return a.ctypes.data if a is not None and a.size else None
+
+
+class MvLookupsHolder:
+    """Builds an h2hip_evalh_mvlookups from [(flattened graphs: K inputs then the table, phi polynomial, m polynomial)] and keeps every
+    buffer alive; byref() of an empty list is NULL, the call without mv-lookups"""
+
+    def __init__(self, arguments):
+        self.keep = []
+        s = EvalhMvLookups()
+        s.n_args = len(arguments)
+        n_graphs = sum(len(gs) for gs, _, _ in arguments)
+        graphs = (Graph * max(1, n_graphs))()
+        n_inputs = np.array([len(gs) - 1 for gs, _, _ in arguments] or [0], dtype=np.uint32)
+        phis, ms, at = [], [], 0
+        for gs, phi, m in arguments:
+            for g in gs:
+                graphs[at] = graph_struct(g, self.keep)
+                at += 1
+            phis.append(np.ascontiguousarray(phi, dtype=np.uint64))
+            ms.append(np.ascontiguousarray(m, dtype=np.uint64))
+        t_phi = (ctypes.c_void_p * max(1, len(phis)))(*[a.ctypes.data for a in phis])
+        t_m = (ctypes.c_void_p * max(1, len(ms)))(*[a.ctypes.data for a in ms])
+        self.keep += [graphs, n_inputs, phis, ms, t_phi, t_m]
+        s.n_inputs, s.graphs = n_inputs.ctypes.data, ctypes.addressof(graphs)
+        s.phi_polys, s.m_polys = ctypes.addressof(t_phi), ctypes.addressof(t_m)
+        self.desc = s
+
+    def byref(self):
+        return ctypes.byref(self.desc) if self.desc.n_args else None
 
 
 class ShufflesHolder:
@@ -415,6 +477,20 @@ def evaluate_h_shuffles_workspace_bytes(k, extended_k, n_fixed, n_advice, n_inst
     return out.value
 
 
+def evaluate_h_ext_workspace_bytes(k, extended_k, n_fixed, n_advice, n_instance, n_perm_sets, n_perm_columns, n_lookups, n_mvlookups,
+                                   n_shuffles, parts_form, device_form):
+    """evaluate_h_workspace_bytes for a call with n_mvlookups mv-lookup arguments and n_shuffles shuffles
+    (h2hip_evaluate_h_ext_workspace_bytes; no GPU needed)"""
+    from . import _check, lib
+    out = ctypes.c_size_t()
+    u = ctypes.c_uint32
+    _check(lib().h2hip_evaluate_h_ext_workspace_bytes(u(k), u(extended_k), u(n_fixed), u(n_advice), u(n_instance), u(n_perm_sets),
+                                                      u(n_perm_columns), u(n_lookups), u(n_mvlookups), u(n_shuffles),
+                                                      ctypes.c_int(bool(parts_form)), ctypes.c_int(bool(device_form)), ctypes.byref(out)),
+           "evaluate_h_ext_workspace_bytes")
+    return out.value
+
+
 def graph_struct(g, keep):
     """one flattened graph (flatten_graph dict) -> h2hip_graph; the arrays it points into are appended to `keep`"""
     c = lambda a, dt: keep.append(np.ascontiguousarray(a, dtype=dt)) or keep[-1]  # noqa: E731
@@ -443,17 +519,28 @@ GraphBuilder = GraphEvaluator  # older name used by the tests
 
 class Evaluator:
     """Evaluator (evaluation.rs:182-189): custom_gates + one GraphEvaluator per lookup, and (upstream PSE halo2, later than the
-    reference) a pair of GraphEvaluators per shuffle."""
+    reference) a pair of GraphEvaluators per shuffle and K + 1 GraphEvaluators per mv-lookup argument."""
 
-    def __init__(self, custom_gates, lookups, shuffles=()):
-        self.custom_gates, self.lookups, self.shuffles = custom_gates, lookups, list(shuffles)
+    def __init__(self, custom_gates, lookups, shuffles=(), mv_lookups=()):
+        self.custom_gates, self.lookups, self.shuffles, self.mv_lookups = custom_gates, lookups, list(shuffles), list(mv_lookups)
 
     @classmethod
-    def new(cls, gate_polys, lookup_arguments=(), shuffle_arguments=()):
+    def new(cls, gate_polys, lookup_arguments=(), shuffle_arguments=(), mvlookup_arguments=()):
         """Evaluator::new (:221-279).  gate_polys: every gate's polynomials in cs.gates order, flattened;
-        lookup_arguments: [(input_expressions, table_expressions)]; shuffle_arguments: [(input_expressions, shuffle_expressions)]"""
+        lookup_arguments: [(input_expressions, table_expressions)]; shuffle_arguments: [(input_expressions, shuffle_expressions)];
+        mvlookup_arguments: [([input_expressions, ...], table_expressions)], several input tuples sharing one table"""
         return cls(custom_gates_graph(list(gate_polys)), [lookup_graph(i, t) for i, t in lookup_arguments],
-                   [shuffle_graphs(i, s) for i, s in shuffle_arguments])
+                   [shuffle_graphs(i, s) for i, s in shuffle_arguments], [mvlookup_graphs(i, t) for i, t in mvlookup_arguments])
+
+    def describe_mvlookups(self, case):
+        """the mv-lookup stage of a call: case["mvlookups"], when present, holds one (phi polynomial, m polynomial) pair of (2^k, 4) u64
+        per mv-lookup argument of this Evaluator, in order.  None: the case has no such entry."""
+        polys = case.get("mvlookups")
+        if polys is None:
+            return None
+        if len(polys) != len(self.mv_lookups):
+            raise ValueError("mvlookups: expected %d (phi, m) pairs, got %d" % (len(self.mv_lookups), len(polys)))
+        return MvLookupsHolder([([flatten_graph(g) for g in gs], phi, m) for gs, (phi, m) in zip(self.mv_lookups, polys)])
 
     def describe_shuffles(self, case):
         """the shuffle stage of a call: case["shuffles"], when present, holds one product polynomial (2^k, 4) u64 per shuffle of this
@@ -492,7 +579,11 @@ class Evaluator:
             full["t_evaluations"] = t_evaluations
         h = self.describe_parts(full)
         values = np.ascontiguousarray(values, dtype=np.uint64)
-        sh = self.describe_shuffles(case)
+        sh, mv = self.describe_shuffles(case), self.describe_mvlookups(case)
+        if mv is not None:
+            _check(lib().h2hip_evaluate_h_parts_ext_bn254(h.byref(), mv.byref(), sh.byref() if sh is not None else None,
+                                                          values.ctypes.data_as(ctypes.c_void_p)), "evaluate_h_parts_ext")
+            return values
         if sh is not None:
             _check(lib().h2hip_evaluate_h_parts_shuffles_bn254(h.byref(), sh.byref(), values.ctypes.data_as(ctypes.c_void_p)),
                    "evaluate_h_parts_shuffles")
@@ -506,7 +597,11 @@ class Evaluator:
         from . import _check, lib
         h = self.describe(case)
         values = np.ascontiguousarray(values, dtype=np.uint64)
-        sh = self.describe_shuffles(case)
+        sh, mv = self.describe_shuffles(case), self.describe_mvlookups(case)
+        if mv is not None:
+            _check(lib().h2hip_evaluate_h_ext_bn254(h.byref(), mv.byref(), sh.byref() if sh is not None else None,
+                                                    values.ctypes.data_as(ctypes.c_void_p)), "evaluate_h_ext")
+            return values
         if sh is not None:
             _check(lib().h2hip_evaluate_h_shuffles_bn254(h.byref(), sh.byref(), values.ctypes.data_as(ctypes.c_void_p)), "evaluate_h_shuffles")
             return values

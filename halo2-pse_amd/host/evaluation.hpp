@@ -5,6 +5,8 @@
 //   plonk::Calculation       evaluation.rs:108-127
 //   plonk::GraphEvaluator    evaluation.rs:191-201, :526-706  add_rotation / add_constant / add_calculation / add_expression
 //   plonk::shuffle::Argument the shuffle argument of upstream PSE halo2 (later than the reference): required_degree, compress, commit_product
+//   plonk::mv_lookup::Argument the logUp (mv-lookup) argument of the upstream forks that replaced the permuted-column lookup (later than the
+//                            reference): required_degree, compress, commit_multiplicities, commit_sum
 //   plonk::Evaluator         evaluation.rs:182-189, new :221-279, evaluate_h :280-522 -> h2hip_evaluate_h_bn254, and coset by coset of the
 //                            2^k domain from coefficient-form columns (evaluate_h_parts -> h2hip_evaluate_h_parts_bn254)
 //
@@ -309,6 +311,75 @@ struct Argument {
 };
 }  // namespace shuffle
 
+// The logUp (mv-lookup) argument (include/halo2hip.h states the definitions): K >= 1 input tuples that share one table tuple.
+namespace mv_lookup {
+struct Argument {
+    std::vector<std::vector<Expr>> inputs_expressions;
+    std::vector<Expr> table_expressions;
+
+    // 2 + d_t + sum_c d_c: each d the largest degree in that tuple, at least 1
+    size_t required_degree() const {
+        if (inputs_expressions.empty()) throw std::logic_error("mv_lookup: K >= 1 input tuples expected");
+        auto d = [](const std::vector<Expr>& exprs) {
+            size_t m = 1;
+            for (const auto& e : exprs) m = std::max(m, expression_degree(e));
+            return m;
+        };
+        size_t sum = 2 + d(table_expressions);
+        for (const auto& inp : inputs_expressions) sum += d(inp);
+        return sum;
+    }
+
+    // the compression's K + 1 graphs, inputs then table: their values are F_c and T
+    std::vector<GraphEvaluator> compress_graphs() const { return graphs(false); }
+    // the evaluator's K + 1 graphs (h2hip_evalh_mvlookups): their values are F_c + beta and T + beta
+    std::vector<GraphEvaluator> evaluator_graphs() const { return graphs(true); }
+
+    using Col = poly::Polynomial<poly::LagrangeCoeff>;
+    // F_0 .. F_{K-1}, then T, over the n Lagrange rows (h2hip_lookup_compress_bn254)
+    std::vector<Col> compress(const poly::EvaluationDomain& domain, const std::vector<const Col*>& fixed, const std::vector<const Col*>& advice,
+                              const std::vector<const Col*>& instance, const std::vector<Fr>& challenges, const Fr& theta) const {
+        std::vector<FlatGraph> flat;
+        for (const auto& g : compress_graphs()) flat.push_back(g.flatten());
+        std::vector<h2hip_graph> abi;
+        for (const auto& f : flat) abi.push_back(f.abi());
+        return lookup_compress(domain, abi, fixed, advice, instance, challenges, theta);
+    }
+    // the multiplicity column m of compressed columns (compress()'s result): h2hip_mvlookup_multiplicities_bn254.  Committing m stays
+    // with the caller.
+    Col commit_multiplicities(const poly::EvaluationDomain& domain, const std::vector<Col>& compressed, size_t blinding_factors) const {
+        return std::move(mvlookup_multiplicities(domain, {input_ptrs(compressed)}, {&compressed.back()}, blinding_factors)[0]);
+    }
+    // the grand sum phi (h2hip_mvlookup_sums_bn254) with the caller's blinding_factors blinding values
+    Col commit_sum(const poly::EvaluationDomain& domain, const std::vector<Col>& compressed, const Col& m, const Fr& beta,
+                   const std::vector<Fr>& blinding, size_t blinding_factors) const {
+        return std::move(mvlookup_sums(domain, {input_ptrs(compressed)}, {&compressed.back()}, {&m}, beta, blinding, blinding_factors)[0]);
+    }
+
+  private:
+    std::vector<GraphEvaluator> graphs(bool add_beta) const {
+        if (inputs_expressions.empty()) throw std::logic_error("mv_lookup: K >= 1 input tuples expected");
+        std::vector<GraphEvaluator> out;
+        for (size_t t = 0; t <= inputs_expressions.size(); t++) {
+            const std::vector<Expr>& exprs = t < inputs_expressions.size() ? inputs_expressions[t] : table_expressions;
+            GraphEvaluator g;
+            std::vector<ValueSource> p;
+            for (const auto& e : exprs) p.push_back(g.add_expression(e));
+            const ValueSource compressed = g.add_calculation(Calculation::Horner(ValueSource::Constant(0), p, ValueSource::Theta()));
+            if (add_beta) g.add_calculation(Calculation::Add(compressed, ValueSource::Beta()));
+            out.push_back(std::move(g));
+        }
+        return out;
+    }
+    std::vector<const Col*> input_ptrs(const std::vector<Col>& compressed) const {
+        if (compressed.size() != inputs_expressions.size() + 1) throw std::logic_error("mv_lookup: K + 1 compressed columns expected");
+        std::vector<const Col*> p;
+        for (size_t t = 0; t + 1 < compressed.size(); t++) p.push_back(&compressed[t]);
+        return p;
+    }
+};
+}  // namespace mv_lookup
+
 // the per-instance inputs of evaluate_h that are not part of the Evaluator (evaluation.rs:280-305): what the reference
 // reads from pk, the domain and the prover's committed structures.  Every vector of Fr is one polynomial.
 struct EvaluateHInputs {
@@ -328,6 +399,8 @@ struct EvaluateHInputs {
     std::vector<std::array<const std::vector<Fr>*, 3>> lookups;
     // shuffles: product_poly per shuffle, coefficient form, n each (one per shuffle of the Evaluator)
     std::vector<const std::vector<Fr>*> shuffles;
+    // mv-lookups: (phi_poly, m_poly) per argument of the Evaluator, coefficient form, n each
+    std::vector<std::array<const std::vector<Fr>*, 2>> mv_lookups;
 };
 
 // evaluate_h_parts' inputs: EvaluateHInputs with every column a polynomial of n coefficients -- pk.fixed_polys, pk.l0 / l_last /
@@ -345,6 +418,7 @@ struct EvaluateHPartsInputs {
     uint32_t blinding_factors = 5;
     std::vector<std::array<const std::vector<Fr>*, 3>> lookups;
     std::vector<const std::vector<Fr>*> shuffles;  // product_poly per shuffle
+    std::vector<std::array<const std::vector<Fr>*, 2>> mv_lookups;  // (phi_poly, m_poly) per mv-lookup argument
     uint32_t part_begin = 0, part_count = 0;  // the parts (cosets of the 2^k domain) to compute; 0, 0 = all 2^(extended_k - k)
     bool divide_by_vanishing_poly = false;    // the last instance's call: the rows leave multiplied by domain->t_evaluations
 };
@@ -403,9 +477,39 @@ class Evaluator {  // :182-189
         out.abi.product_polys = out.polys.data();
     }
 
+    std::vector<std::vector<GraphEvaluator>> mv_lookups;  // the logUp argument's: K input graphs, then the table graph, per argument
+
+    // the mv-lookups' graphs and polynomials as h2hip_evalh_mvlookups; owns what the struct points into
+    struct MvLookupsAbi {
+        std::vector<FlatGraph> flat;
+        std::vector<h2hip_graph> graphs;
+        std::vector<uint32_t> n_inputs;
+        std::vector<const uint64_t*> phi, m;
+        h2hip_evalh_mvlookups abi;
+        const h2hip_evalh_mvlookups* ptr() const { return abi.n_args ? &abi : nullptr; }
+    };
+    void mv_lookups_abi(const std::vector<std::array<const std::vector<Fr>*, 2>>& polys, size_t n, MvLookupsAbi& out) const {
+        if (polys.size() != mv_lookups.size()) throw std::logic_error("evaluate_h: one (phi, m) pair of polynomials per mv-lookup expected");
+        for (size_t j = 0; j < mv_lookups.size(); j++) {
+            for (const auto* p : polys[j])
+                if (!p || p->size() != n) throw std::logic_error("evaluate_h: polynomial of the wrong length");
+            for (const auto& g : mv_lookups[j]) out.flat.push_back(g.flatten());
+            out.n_inputs.push_back((uint32_t)mv_lookups[j].size() - 1);
+            out.phi.push_back(polys[j][0]->data()->l);
+            out.m.push_back(polys[j][1]->data()->l);
+        }
+        for (const auto& f : out.flat) out.graphs.push_back(f.abi());
+        out.abi.n_args = (uint32_t)mv_lookups.size();
+        out.abi.n_inputs = out.n_inputs.data();
+        out.abi.graphs = out.graphs.data();
+        out.abi.phi_polys = out.phi.data();
+        out.abi.m_polys = out.m.data();
+    }
+
     // Evaluator::new (:221-279): gate_polys = cs.gates.iter().flat_map(|gate| gate.polynomials()), lookups = cs.lookups
     static Evaluator create(const std::vector<Expr>& gate_polys, const std::vector<LookupArgument>& lookup_arguments,
-                            const std::vector<shuffle::Argument>& shuffle_arguments = {}) {
+                            const std::vector<shuffle::Argument>& shuffle_arguments = {},
+                            const std::vector<mv_lookup::Argument>& mvlookup_arguments = {}) {
         Evaluator ev;
         std::vector<ValueSource> parts;
         for (const auto& poly : gate_polys) parts.push_back(ev.custom_gates.add_expression(poly));
@@ -425,6 +529,7 @@ class Evaluator {  // :182-189
             ev.lookups.push_back(std::move(graph));
         }
         for (const auto& sh : shuffle_arguments) ev.shuffles.push_back(sh.evaluator_graphs());
+        for (const auto& mv : mvlookup_arguments) ev.mv_lookups.push_back(mv.evaluator_graphs());
         return ev;
     }
 
@@ -511,7 +616,9 @@ class Evaluator {  // :182-189
         }
         ShufflesAbi sh;
         shuffles_abi(in.shuffles, n, sh);
-        engine_check(h2hip_evaluate_h_shuffles_bn254(&desc, sh.ptr(), values[0].l), "h2hip_evaluate_h_bn254");
+        MvLookupsAbi mv;
+        mv_lookups_abi(in.mv_lookups, n, mv);
+        engine_check(h2hip_evaluate_h_ext_bn254(&desc, mv.ptr(), sh.ptr(), values[0].l), "h2hip_evaluate_h_bn254");
     }
 
     // the same one coset of the 2^k domain at a time (h2hip_evaluate_h_parts_bn254): rows of `values` outside the parts asked for are
@@ -593,7 +700,9 @@ class Evaluator {  // :182-189
         desc.t_evaluations = in.divide_by_vanishing_poly ? d.t_evaluations[0].l : nullptr;
         ShufflesAbi sh;
         shuffles_abi(in.shuffles, n, sh);
-        engine_check(h2hip_evaluate_h_parts_shuffles_bn254(&desc, sh.ptr(), values[0].l), "h2hip_evaluate_h_parts_bn254");
+        MvLookupsAbi mv;
+        mv_lookups_abi(in.mv_lookups, n, mv);
+        engine_check(h2hip_evaluate_h_parts_ext_bn254(&desc, mv.ptr(), sh.ptr(), values[0].l), "h2hip_evaluate_h_parts_bn254");
     }
 
     // The part cosets of a proving key's coefficient-form polynomials (fixed_polys, l0 / l_last / l_active_row, permutation.polys) kept in

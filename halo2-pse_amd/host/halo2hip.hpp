@@ -831,6 +831,61 @@ inline std::vector<poly::Polynomial<poly::LagrangeCoeff>> shuffle_products(
     return z;
 }
 
+// The logUp (mv-lookup) argument's multiplicity columns, one per argument (include/halo2hip.h states the definition): inputs[j] are the
+// compressed input columns that share tables[j].  Throws EngineError when an input value is missing from its table.
+inline std::vector<poly::Polynomial<poly::LagrangeCoeff>> mvlookup_multiplicities(
+    const poly::EvaluationDomain& domain, const std::vector<std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>>& inputs,
+    const std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>& tables, size_t blinding_factors) {
+    const size_t count = tables.size();
+    if (inputs.size() != count) throw std::logic_error("mv-lookup inputs and tables differ in count");
+    std::vector<const uint64_t*> f, t;
+    std::vector<uint32_t> n_inputs;
+    for (size_t j = 0; j < count; j++) {
+        if (tables[j]->len() != domain.n) throw std::logic_error("column length != n");
+        t.push_back(tables[j]->values[0].l);
+        n_inputs.push_back(uint32_t(inputs[j].size()));
+        for (const auto* c : inputs[j]) {
+            if (c->len() != domain.n) throw std::logic_error("column length != n");
+            f.push_back(c->values[0].l);
+        }
+    }
+    std::vector<poly::Polynomial<poly::LagrangeCoeff>> m(count, poly::Polynomial<poly::LagrangeCoeff>{std::vector<Fr>(domain.n)});
+    std::vector<uint64_t*> mp;
+    for (auto& col : m) mp.push_back(col.values[0].l);
+    engine_check(h2hip_mvlookup_multiplicities_bn254(domain.k, f.data(), n_inputs.data(), t.data(), count, uint32_t(blinding_factors), mp.data()),
+                 "mvlookup_multiplicities");
+    return m;
+}
+
+// ... and its grand sums phi, one per argument, from the same columns and the multiplicities
+inline std::vector<poly::Polynomial<poly::LagrangeCoeff>> mvlookup_sums(
+    const poly::EvaluationDomain& domain, const std::vector<std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>>& inputs,
+    const std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>& tables, const std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>& m,
+    const Fr& beta, const std::vector<Fr>& blinding, size_t blinding_factors) {
+    const size_t count = tables.size();
+    if (inputs.size() != count || m.size() != count) throw std::logic_error("mv-lookup columns differ in count");
+    if (blinding.size() != count * blinding_factors) throw std::logic_error("blinding: count * blinding_factors values expected");
+    std::vector<const uint64_t*> f, t, mm;
+    std::vector<uint32_t> n_inputs;
+    for (size_t j = 0; j < count; j++) {
+        if (tables[j]->len() != domain.n || m[j]->len() != domain.n) throw std::logic_error("column length != n");
+        t.push_back(tables[j]->values[0].l);
+        mm.push_back(m[j]->values[0].l);
+        n_inputs.push_back(uint32_t(inputs[j].size()));
+        for (const auto* c : inputs[j]) {
+            if (c->len() != domain.n) throw std::logic_error("column length != n");
+            f.push_back(c->values[0].l);
+        }
+    }
+    std::vector<poly::Polynomial<poly::LagrangeCoeff>> phi(count, poly::Polynomial<poly::LagrangeCoeff>{std::vector<Fr>(domain.n)});
+    std::vector<uint64_t*> pp;
+    for (auto& col : phi) pp.push_back(col.values[0].l);
+    engine_check(h2hip_mvlookup_sums_bn254(domain.k, beta.l, f.data(), n_inputs.data(), t.data(), mm.data(), count,
+                                           blinding.empty() ? nullptr : blinding[0].l, uint32_t(blinding_factors), pp.data()),
+                 "mvlookup_sums");
+    return phi;
+}
+
 // lookup::Argument::commit_permuted's compression (plonk/lookup/prover.rs:90-115): out[g] = graphs[g] over the n Lagrange rows.  Each
 // graph is one side of a lookup, add_expression of its expressions then Horner(Constant(0), parts, Theta) (evaluation.hpp
 // lookup_compress_graphs builds them); fixed / advice / instance are the Lagrange columns the graphs index.
@@ -1040,7 +1095,8 @@ inline ProvingKeyColumns keygen_pk(const poly::EvaluationDomain& domain, const s
 namespace dev {
 
 struct VerifyFailure {
-    enum Kind { Gate, Lookup, Permutation, Shuffle } kind;  // index: the gate polynomial (graph), the lookup, the permutation column, the shuffle
+    // index: the gate polynomial (graph), the lookup, the permutation column, the shuffle, the mv-lookup's input column (counted over all arguments)
+    enum Kind { Gate, Lookup, Permutation, Shuffle, MvLookup } kind;
     size_t index;
     uint32_t row;
     bool operator==(const VerifyFailure& o) const { return kind == o.kind && index == o.index && row == o.row; }
@@ -1060,7 +1116,8 @@ inline std::vector<VerifyFailure> verify(const poly::EvaluationDomain& domain, c
                                          const std::vector<h2hip_graph>& lookup_graphs, const Fr& theta, size_t blinding_factors,
                                          const std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>& permutation_columns,
                                          const plonk::permutation::keygen::Assembly* assembly, uint32_t max_rows = 64,
-                                         const std::vector<h2hip_graph>& shuffle_graphs = {}) {
+                                         const std::vector<h2hip_graph>& shuffle_graphs = {}, const std::vector<h2hip_graph>& mvlookup_graphs = {},
+                                         const std::vector<uint32_t>& mvlookup_n_inputs = {}) {
     auto ptrs = [&](const std::vector<const poly::Polynomial<poly::LagrangeCoeff>*>& cs) {
         std::vector<const uint64_t*> p;
         for (auto* c : cs) {
@@ -1116,6 +1173,27 @@ inline std::vector<VerifyFailure> verify(const poly::EvaluationDomain& domain, c
                                                 rows.data()),
                      "check_shuffles");
         collect(VerifyFailure::Shuffle);
+    }
+    // mv-lookups (the logUp argument; mv_lookup::Argument::compress_graphs of every argument, K_j inputs then the table, with
+    // mvlookup_n_inputs[j] = K_j): the lookup check with the table repeated per input column, reported after the shuffles
+    if (!mvlookup_graphs.empty()) {
+        const auto comp = plonk::lookup_compress(domain, mvlookup_graphs, cols.fixed, cols.advice, cols.instance, cols.challenges, theta);
+        std::vector<const uint64_t*> in, tab;
+        size_t at = 0;
+        for (uint32_t K : mvlookup_n_inputs) {
+            if (at + K + 1 > comp.size()) throw std::logic_error("mvlookup_graphs: K + 1 graphs per argument expected");
+            for (uint32_t t = 0; t < K; t++) {
+                in.push_back(comp[at + t].values[0].l);
+                tab.push_back(comp[at + K].values[0].l);
+            }
+            at += K + 1;
+        }
+        if (at != comp.size()) throw std::logic_error("mvlookup_graphs: K + 1 graphs per argument expected");
+        prepare(in.size());
+        engine_check(h2hip_check_lookups_bn254(domain.k, in.data(), tab.data(), in.size(), uint32_t(blinding_factors), max_rows, counts.data(),
+                                               rows.data()),
+                     "check_lookups");
+        collect(VerifyFailure::MvLookup);
     }
     if (assembly && !permutation_columns.empty()) {
         const auto p = ptrs(permutation_columns);

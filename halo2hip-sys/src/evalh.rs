@@ -166,6 +166,19 @@ pub struct EvalhShuffles {
     pub product_polys: *const *const u64,
 }
 
+/// `h2hip_evalh_mvlookups`: the logUp (mv-lookup) arguments of one circuit instance, beside either description.  Argument j has
+/// `n_inputs[j]` input tuples sharing one table; `graphs` holds its input graphs, then its table graph, behind those of argument j - 1;
+/// `phi_polys` / `m_polys` hold one coefficient-form polynomial of 2^k elements per argument (the grand sum, the multiplicities).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct EvalhMvLookups {
+    pub n_args: u32,
+    pub n_inputs: *const u32,
+    pub graphs: *const h2hip_graph,
+    pub phi_polys: *const *const u64,
+    pub m_polys: *const *const u64,
+}
+
 // ---- owning builder -------------------------------------------------------------------------------------------------
 /// A `GraphEvaluator` flattened into plain vectors.  halo2_proofs builds one per graph once per proving key; `view()`
 /// lends it to the engine for the duration of a call.
@@ -297,18 +310,50 @@ fn shuffles_view<F>(sh: &ShufflesInput<'_, F>, n: usize) -> Option<(Vec<h2hip_gr
     Some((sh.graphs.iter().map(|g| g.view()).collect(), sh.product_polys.iter().map(|s| s.as_ptr() as *const u64).collect()))
 }
 
+/// The mv-lookup arguments of one circuit instance (include/halo2hip.h, `h2hip_evalh_mvlookups`): `n_inputs[j]` input graphs and one
+/// table graph per argument, consecutively in `graphs`; `phi_polys[j]` / `m_polys[j]` its grand sum and multiplicities in coefficient
+/// form (2^k elements).
+pub struct MvLookupsInput<'a, F> {
+    pub n_inputs: &'a [u32],
+    pub graphs: &'a [FlatGraph],
+    pub phi_polys: Vec<&'a [F]>,
+    pub m_polys: Vec<&'a [F]>,
+}
+
+/// the C view of an `MvLookupsInput` and the tables it points into; None when the lengths do not fit
+#[allow(clippy::type_complexity)]
+fn mvlookups_view<F>(mv: &MvLookupsInput<'_, F>, n: usize) -> Option<(Vec<h2hip_graph>, Vec<*const u64>, Vec<*const u64>)> {
+    let n_graphs: usize = mv.n_inputs.iter().map(|&k| k as usize + 1).sum();
+    if mv.graphs.len() != n_graphs || mv.phi_polys.len() != mv.n_inputs.len() || mv.m_polys.len() != mv.n_inputs.len() {
+        return None;
+    }
+    if mv.n_inputs.iter().any(|&k| !(1..=255).contains(&k)) || !mv.phi_polys.iter().chain(mv.m_polys.iter()).all(|s| s.len() == n) {
+        return None;
+    }
+    let ptrs = |cols: &[&[F]]| -> Vec<*const u64> { cols.iter().map(|c| c.as_ptr() as *const u64).collect() };
+    Some((mv.graphs.iter().map(|g| g.view()).collect(), ptrs(&mv.phi_polys), ptrs(&mv.m_polys)))
+}
+
 /// Safe front of `h2hip_evaluate_h_bn254`: checks the element type and every slice length, builds the pointer tables, calls
 /// the engine.  `values` (2^extended_k elements) is read and written.  false: the engine declined, run the CPU body.
 pub fn try_evaluate_h<F: 'static + Copy>(inp: &EvalHInput<'_, F>, values: &mut [F]) -> bool {
-    evaluate_h_with(inp, None, values)
+    evaluate_h_with(inp, None, None, values)
 }
 
 /// `try_evaluate_h` with the shuffle stage after the lookups (`h2hip_evaluate_h_shuffles_bn254`)
 pub fn try_evaluate_h_shuffles<F: 'static + Copy>(inp: &EvalHInput<'_, F>, shuffles: &ShufflesInput<'_, F>, values: &mut [F]) -> bool {
-    evaluate_h_with(inp, Some(shuffles), values)
+    evaluate_h_with(inp, None, Some(shuffles), values)
 }
 
-fn evaluate_h_with<F: 'static + Copy>(inp: &EvalHInput<'_, F>, shuffles: Option<&ShufflesInput<'_, F>>, values: &mut [F]) -> bool {
+/// `try_evaluate_h` with every argument that travels beside the description (`h2hip_evaluate_h_ext_bn254`): the mv-lookup stage after
+/// the halo2 lookups, then the shuffle stage; either may be absent
+pub fn try_evaluate_h_ext<F: 'static + Copy>(inp: &EvalHInput<'_, F>, mvlookups: Option<&MvLookupsInput<'_, F>>,
+                                             shuffles: Option<&ShufflesInput<'_, F>>, values: &mut [F]) -> bool {
+    evaluate_h_with(inp, mvlookups, shuffles, values)
+}
+
+fn evaluate_h_with<F: 'static + Copy>(inp: &EvalHInput<'_, F>, mvlookups: Option<&MvLookupsInput<'_, F>>,
+                                      shuffles: Option<&ShufflesInput<'_, F>>, values: &mut [F]) -> bool {
     if std::any::TypeId::of::<F>() != std::any::TypeId::of::<halo2curves::bn256::Fr>() || std::mem::size_of::<F>() != 32 {
         return false;
     }
@@ -395,18 +440,34 @@ fn evaluate_h_with<F: 'static + Copy>(inp: &EvalHInput<'_, F>, shuffles: Option<
     key_columns.push(desc.l_last);
     key_columns.push(desc.l_active_row);
     let _ = unsafe { super::ffi::h2hip_columns_pin(key_columns.as_ptr(), key_columns.len(), en) };
-    let rc: c_int = match shuffles {
-        None => unsafe { super::ffi::h2hip_evaluate_h_bn254(&desc as *const h2hip_evalh_desc, values.as_mut_ptr() as *mut u64) },
-        Some(sh) => {
-            let (views, polys) = match shuffles_view(sh, n) {
-                Some(v) => v,
-                None => return false,
-            };
-            let c_sh = EvalhShuffles { n_shuffles: polys.len() as u32, graphs: views.as_ptr(), product_polys: polys.as_ptr() };
-            unsafe {
-                super::ffi::h2hip_evaluate_h_shuffles_bn254(&desc as *const h2hip_evalh_desc, &c_sh as *const EvalhShuffles, values.as_mut_ptr() as *mut u64)
-            }
-        }
+    // the extras' tables live until the call returns; an absent extra is a null struct pointer
+    let sh_tabs = match shuffles.map(|sh| shuffles_view(sh, n)) {
+        Some(None) => return false,
+        Some(v) => v,
+        None => None,
+    };
+    let mv_tabs = match mvlookups.map(|mv| mvlookups_view(mv, n)) {
+        Some(None) => return false,
+        Some(v) => v,
+        None => None,
+    };
+    let c_sh = sh_tabs.as_ref().map(|(views, polys)| EvalhShuffles { n_shuffles: polys.len() as u32, graphs: views.as_ptr(), product_polys: polys.as_ptr() });
+    let c_mv = match (mvlookups, mv_tabs.as_ref()) {
+        (Some(mv), Some((views, phi, m))) => Some(EvalhMvLookups {
+            n_args: mv.n_inputs.len() as u32,
+            n_inputs: mv.n_inputs.as_ptr(),
+            graphs: views.as_ptr(),
+            phi_polys: phi.as_ptr(),
+            m_polys: m.as_ptr(),
+        }),
+        _ => None,
+    };
+    if c_mv.is_none() && c_sh.is_none() {
+        return unsafe { super::ffi::h2hip_evaluate_h_bn254(&desc as *const h2hip_evalh_desc, values.as_mut_ptr() as *mut u64) } == 0;
+    }
+    let rc: c_int = unsafe {
+        super::ffi::h2hip_evaluate_h_ext_bn254(&desc as *const h2hip_evalh_desc, c_mv.as_ref().map_or(std::ptr::null(), |c| c as *const EvalhMvLookups),
+                                               c_sh.as_ref().map_or(std::ptr::null(), |c| c as *const EvalhShuffles), values.as_mut_ptr() as *mut u64)
     };
     rc == 0
 }
@@ -468,15 +529,22 @@ pub struct EvalHPartsInput<'a, F> {
 /// engine.  `values` (2^extended_k elements) is read and written on the rows of the requested parts only.  false: the engine declined,
 /// run the CPU body.
 pub fn try_evaluate_h_parts<F: 'static + Copy>(inp: &EvalHPartsInput<'_, F>, values: &mut [F]) -> bool {
-    evaluate_h_parts_with(inp, None, values)
+    evaluate_h_parts_with(inp, None, None, values)
 }
 
 /// `try_evaluate_h_parts` with the shuffle stage after the lookups (`h2hip_evaluate_h_parts_shuffles_bn254`)
 pub fn try_evaluate_h_parts_shuffles<F: 'static + Copy>(inp: &EvalHPartsInput<'_, F>, shuffles: &ShufflesInput<'_, F>, values: &mut [F]) -> bool {
-    evaluate_h_parts_with(inp, Some(shuffles), values)
+    evaluate_h_parts_with(inp, None, Some(shuffles), values)
 }
 
-fn evaluate_h_parts_with<F: 'static + Copy>(inp: &EvalHPartsInput<'_, F>, shuffles: Option<&ShufflesInput<'_, F>>, values: &mut [F]) -> bool {
+/// `try_evaluate_h_parts` with every argument that travels beside the description (`h2hip_evaluate_h_parts_ext_bn254`)
+pub fn try_evaluate_h_parts_ext<F: 'static + Copy>(inp: &EvalHPartsInput<'_, F>, mvlookups: Option<&MvLookupsInput<'_, F>>,
+                                                   shuffles: Option<&ShufflesInput<'_, F>>, values: &mut [F]) -> bool {
+    evaluate_h_parts_with(inp, mvlookups, shuffles, values)
+}
+
+fn evaluate_h_parts_with<F: 'static + Copy>(inp: &EvalHPartsInput<'_, F>, mvlookups: Option<&MvLookupsInput<'_, F>>,
+                                            shuffles: Option<&ShufflesInput<'_, F>>, values: &mut [F]) -> bool {
     if std::any::TypeId::of::<F>() != std::any::TypeId::of::<halo2curves::bn256::Fr>() || std::mem::size_of::<F>() != 32 {
         return false;
     }
@@ -561,18 +629,33 @@ fn evaluate_h_parts_with<F: 'static + Copy>(inp: &EvalHPartsInput<'_, F>, shuffl
         part_count: inp.part_count,
         t_evaluations: inp.t_evaluations.map_or(std::ptr::null(), |t| t.as_ptr() as *const u64),
     };
-    let rc: c_int = match shuffles {
-        None => unsafe { super::ffi::h2hip_evaluate_h_parts_bn254(&desc as *const EvalhPartsDesc, values.as_mut_ptr() as *mut u64) },
-        Some(sh) => {
-            let (views, polys) = match shuffles_view(sh, n) {
-                Some(v) => v,
-                None => return false,
-            };
-            let c_sh = EvalhShuffles { n_shuffles: polys.len() as u32, graphs: views.as_ptr(), product_polys: polys.as_ptr() };
-            unsafe {
-                super::ffi::h2hip_evaluate_h_parts_shuffles_bn254(&desc as *const EvalhPartsDesc, &c_sh as *const EvalhShuffles, values.as_mut_ptr() as *mut u64)
-            }
-        }
+    let sh_tabs = match shuffles.map(|sh| shuffles_view(sh, n)) {
+        Some(None) => return false,
+        Some(v) => v,
+        None => None,
+    };
+    let mv_tabs = match mvlookups.map(|mv| mvlookups_view(mv, n)) {
+        Some(None) => return false,
+        Some(v) => v,
+        None => None,
+    };
+    let c_sh = sh_tabs.as_ref().map(|(views, polys)| EvalhShuffles { n_shuffles: polys.len() as u32, graphs: views.as_ptr(), product_polys: polys.as_ptr() });
+    let c_mv = match (mvlookups, mv_tabs.as_ref()) {
+        (Some(mv), Some((views, phi, m))) => Some(EvalhMvLookups {
+            n_args: mv.n_inputs.len() as u32,
+            n_inputs: mv.n_inputs.as_ptr(),
+            graphs: views.as_ptr(),
+            phi_polys: phi.as_ptr(),
+            m_polys: m.as_ptr(),
+        }),
+        _ => None,
+    };
+    if c_mv.is_none() && c_sh.is_none() {
+        return unsafe { super::ffi::h2hip_evaluate_h_parts_bn254(&desc as *const EvalhPartsDesc, values.as_mut_ptr() as *mut u64) } == 0;
+    }
+    let rc: c_int = unsafe {
+        super::ffi::h2hip_evaluate_h_parts_ext_bn254(&desc as *const EvalhPartsDesc, c_mv.as_ref().map_or(std::ptr::null(), |c| c as *const EvalhMvLookups),
+                                                     c_sh.as_ref().map_or(std::ptr::null(), |c| c as *const EvalhShuffles), values.as_mut_ptr() as *mut u64)
     };
     rc == 0
 }

@@ -374,6 +374,67 @@ pub fn try_shuffle_products<F: Field + 'static>(k: u32, gamma: &F, compressed_in
     Some(z)
 }
 
+/// The logUp (mv-lookup) argument's multiplicity columns (the definition is include/halo2hip.h's): `compressed_inputs[j]` holds the
+/// compressed input columns of argument j, which share `compressed_tables[j]`.  The count of a value goes to the lowest table row that
+/// holds it.  `None` on any failure, a value missing from its table (`H2HIP_ELOOKUP`) included.
+pub fn try_mvlookup_multiplicities<F: Field + 'static>(k: u32, compressed_inputs: &[&[&[F]]], compressed_tables: &[&[F]],
+                                                       blinding_factors: usize) -> Option<Vec<Vec<F>>> {
+    let count = compressed_tables.len();
+    if !is::<F, Fr>() || !layout_ok() || k > 28 || count > 65535 || compressed_inputs.len() != count {
+        return None;
+    }
+    let n = 1usize << k;
+    if compressed_inputs.iter().any(|cols| cols.is_empty() || cols.len() > 255 || cols.iter().any(|c| c.len() != n)) {
+        return None;
+    }
+    if compressed_tables.iter().any(|c| c.len() != n) || blinding_factors + 1 >= n {
+        return None;
+    }
+    let n_inputs: Vec<u32> = compressed_inputs.iter().map(|cols| cols.len() as u32).collect();
+    let f: Vec<*const u64> = compressed_inputs.iter().flat_map(|cols| cols.iter().map(|c| c.as_ptr() as *const u64)).collect();
+    let t: Vec<*const u64> = compressed_tables.iter().map(|c| c.as_ptr() as *const u64).collect();
+    let mut m: Vec<Vec<F>> = (0..count).map(|_| vec![F::zero(); n]).collect();
+    let mp: Vec<*mut u64> = m.iter_mut().map(|c| c.as_mut_ptr() as *mut u64).collect();
+    let rc = unsafe {
+        ffi::h2hip_mvlookup_multiplicities_bn254(k, f.as_ptr(), n_inputs.as_ptr(), t.as_ptr(), count, blinding_factors as u32, mp.as_ptr())
+    };
+    if rc != 0 {
+        return None;
+    }
+    Some(m)
+}
+
+/// The mv-lookup grand sums phi (include/halo2hip.h): inputs and tables as for `try_mvlookup_multiplicities`, `m` their multiplicity
+/// columns, `blinding` argument-major (`blinding_factors` values per argument).  `None` on any failure.
+pub fn try_mvlookup_sums<F: Field + 'static>(k: u32, beta: &F, compressed_inputs: &[&[&[F]]], compressed_tables: &[&[F]], m: &[&[F]],
+                                             blinding: &[F], blinding_factors: usize) -> Option<Vec<Vec<F>>> {
+    let count = compressed_tables.len();
+    if !is::<F, Fr>() || !layout_ok() || k > 28 || count > 65535 || compressed_inputs.len() != count || m.len() != count {
+        return None;
+    }
+    let n = 1usize << k;
+    if compressed_inputs.iter().any(|cols| cols.is_empty() || cols.len() > 255 || cols.iter().any(|c| c.len() != n)) {
+        return None;
+    }
+    if compressed_tables.iter().chain(m.iter()).any(|c| c.len() != n) || blinding.len() != count * blinding_factors || blinding_factors + 1 >= n {
+        return None;
+    }
+    let n_inputs: Vec<u32> = compressed_inputs.iter().map(|cols| cols.len() as u32).collect();
+    let f: Vec<*const u64> = compressed_inputs.iter().flat_map(|cols| cols.iter().map(|c| c.as_ptr() as *const u64)).collect();
+    let ptrs = |cols: &[&[F]]| -> Vec<*const u64> { cols.iter().map(|c| c.as_ptr() as *const u64).collect() };
+    let (t, mm) = (ptrs(compressed_tables), ptrs(m));
+    let mut phi: Vec<Vec<F>> = (0..count).map(|_| vec![F::zero(); n]).collect();
+    let pp: Vec<*mut u64> = phi.iter_mut().map(|c| c.as_mut_ptr() as *mut u64).collect();
+    let rc = unsafe {
+        ffi::h2hip_mvlookup_sums_bn254(k, fr_ptr(beta), f.as_ptr(), n_inputs.as_ptr(), t.as_ptr(), mm.as_ptr(), count, blinding.as_ptr() as *const u64,
+                                       blinding_factors as u32, pp.as_ptr())
+    };
+    if rc != 0 {
+        return None;
+    }
+    Some(phi)
+}
+
 /// `commit_permuted`'s compressed expressions (plonk/lookup/prover.rs:90-115): `graphs[g]` (an input or table side of a lookup, built
 /// as `add_expression` of each expression and `Horner(Constant(0), parts, Theta)`) over the Lagrange columns.  `None` on any failure.
 #[allow(clippy::too_many_arguments)]

@@ -444,6 +444,43 @@ int h2hip_evaluate_h_shuffles_workspace_bytes(uint32_t k, uint32_t extended_k, u
                                               uint32_t n_perm_sets, uint32_t n_perm_columns, uint32_t n_lookups, uint32_t n_shuffles,
                                               int parts_form, int device_form, size_t* bytes);
 
+/* The logUp (mv-lookup) argument's share of h(X) (the definitions: "grand products" below, h2hip_mvlookup_multiplicities_bn254; DESIGN.md
+ * section 2).  Like the shuffles, a circuit's mv-lookups travel beside the unchanged descriptors.  Argument j has K_j = n_inputs[j] input
+ * tuples sharing one table; its K_j + 1 graphs lie consecutively in `graphs`, behind those of argument j - 1: the input graphs, then the
+ * table graph, each add_expression of the tuple's expressions, Horner(Constant(0), parts, Theta), Add(that, Beta).  A graph's value is
+ * the target of its last calculation (zero for an empty graph); call them f_0 .. f_{K-1} and tau, and
+ *   P = prod_c f_c,   Q = sum_c prod_{l != c} f_l   (streamed as Q <- Q f + P; P <- P f: no inversion on the coset).
+ * phi_polys[j] / m_polys[j] are the grand sum and the multiplicities in coefficient form, 2^k elements (h2hip_mvlookup_sums_bn254 /
+ * h2hip_mvlookup_multiplicities_bn254, then lagrange_to_coeff); pc, mc their extended cosets, r_next the row one rotation on.  After the
+ * custom gates, the permutation argument and every halo2 lookup of the descriptor, and before the shuffles, argument j folds
+ *   v = v y + l0[idx] pc[idx];   v = v y + l_last[idx] pc[idx];
+ *   v = v y + l_active_row[idx] (tau P (pc[r_next] - pc[idx]) - tau Q + mc[idx] P).
+ * A graph may read fixed, advice, instance, challenge, constant, intermediate, theta and beta; gamma, y or the previous value is
+ * H2HIP_EINVAL before any device work.  The graphs run on the byte-code interpreter (no kernel is generated for them).
+ * required_degree = 2 + d_t + sum_c d_c, each d the largest degree in that tuple, at least 1.  K_j in [1, 255], n_args <= 65535. */
+typedef struct h2hip_evalh_mvlookups {
+    uint32_t n_args;
+    const uint32_t* n_inputs;
+    const h2hip_graph* graphs;
+    const uint64_t* const* phi_polys;
+    const uint64_t* const* m_polys;
+} h2hip_evalh_mvlookups;
+/* evaluate_h with every argument that travels beside the descriptors; this family ends the growth of suffixes.  Either extra may be
+ * NULL (or empty): mvlookups == NULL is the _shuffles call, both NULL the call without a suffix, limb for limb. */
+int h2hip_evaluate_h_ext_bn254(const h2hip_evalh_desc* desc, const h2hip_evalh_mvlookups* mvlookups, const h2hip_evalh_shuffles* shuffles,
+                               uint64_t* values);
+int h2hip_evaluate_h_ext_bn254_device(const h2hip_evalh_desc* desc, const h2hip_evalh_mvlookups* mvlookups, const h2hip_evalh_shuffles* shuffles,
+                                      void* d_values, void* stream);
+int h2hip_evaluate_h_parts_ext_bn254(const h2hip_evalh_parts_desc* desc, const h2hip_evalh_mvlookups* mvlookups,
+                                     const h2hip_evalh_shuffles* shuffles, uint64_t* values);
+int h2hip_evaluate_h_parts_ext_bn254_device(const h2hip_evalh_parts_desc* desc, const h2hip_evalh_mvlookups* mvlookups,
+                                            const h2hip_evalh_shuffles* shuffles, void* d_values, void* stream);
+/* h2hip_evaluate_h_shuffles_workspace_bytes for a call with n_mvlookups mv-lookup arguments as well (0: the same number): the phi and m
+ * cosets of one group of arguments come on top, and in the host parts form their coefficient columns */
+int h2hip_evaluate_h_ext_workspace_bytes(uint32_t k, uint32_t extended_k, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance,
+                                         uint32_t n_perm_sets, uint32_t n_perm_columns, uint32_t n_lookups, uint32_t n_mvlookups,
+                                         uint32_t n_shuffles, int parts_form, int device_form, size_t* bytes);
+
 /* ---- pinned part cosets: the parts form's counterpart of h2hip_columns_pin.
  * Keep all P part cosets of each coefficient-form polynomial (2^k elements; pk.fixed_polys, pk.l0 / l_last / l_active_row as polynomials,
  * pk.permutation.polys) in HBM, 2^extended_k elements per polynomial, part-major, keyed by the pointer and the domain.
@@ -504,6 +541,38 @@ int h2hip_shuffle_products_bn254(uint32_t k, const uint64_t gamma[4], const uint
 int h2hip_shuffle_products_bn254_device(uint32_t k, const uint64_t gamma[4], const void* const* d_compressed_input,
                                         const void* const* d_compressed_shuffle, size_t count, const uint64_t* blinding,
                                         uint32_t blinding_factors, void* const* d_z, void* stream);
+/* The logarithmic-derivative lookup argument ("mv-lookup", logUp) of the upstream forks that replaced the permuted-column lookup.  It is
+ * later than the reference this engine follows and its source is not part of this repository, so the definitions are stated here
+ *  and a Python-integer model pins them (tests/mvlookup_util.py).  n = 2^k, b = blinding_factors, u = n - b - 1.
+ * Argument j has K_j = n_inputs[j] >= 1 compressed input columns F_{j,0} .. F_{j,K_j-1} and one compressed table column T_j, each the
+ * theta fold h2hip_lookup_compress_bn254 computes (one graph per column).  compressed_inputs is one flat table, argument-major:
+ * F_{0,0} .. F_{0,K_0-1}, F_{1,0}, ...
+ *
+ * Multiplicities.  For i < u: M_j[i] = 0 if some i' < i has T_j[i'] = T_j[i]; otherwise the number of pairs (c, r), r < u, with
+ * F_{j,c}[r] = T_j[i].  Rows u .. n - 1 are zero (no blinding rows go into m).  The output is Montgomery form, ready to commit.  Upstream
+ * finds the table row by a binary search in a sorted list, so with repeated table values it is implementation-defined which row of a run
+ * takes the count; this engine fixes the LOWEST row.  A proof is valid either way, but not byte-identical to a given upstream build when
+ * a table repeats values.  If an input row r < u holds a value absent from T_j[0 .. u), every output is still written (the counts of the
+ * values that were found) and the call returns H2HIP_ELOOKUP; h2hip_last_error() names the lowest failing (argument, input column).
+ * The _device form queues on `stream` and waits for it once to read that verdict, as h2hip_lookup_permute_bn254_device does.
+ * K_j in [1, 255] with K_j * 2^k < 2^32 (the counts are 32-bit), count <= 65535, blinding_factors + 1 < n; count == 0 writes nothing.
+ *
+ * Grand sum.  phi_j[0] = 0; for 1 <= i <= u: phi_j[i] = phi_j[i-1] + sum_c inv(F_{j,c}[i-1] + beta) - M_j[i-1] * inv(T_j[i-1] + beta);
+ * rows n - b .. n - 1 = blinding[j * b ..], drawn by the caller in argument order.  inv is ff's BatchInvert, inv(0) = 0: that term is
+ * zero and the sum simply goes on (no "zero from here on", unlike the products).  The whole call takes one field inversion.  A valid
+ * argument ends in phi_j[u] = 0; the engine does not check that.  The (sum_j K_j + count) * 2^k denominators of a call must not
+ * exceed 2^30.  The _device form queues on `stream` and does not wait. */
+int h2hip_mvlookup_multiplicities_bn254(uint32_t k, const uint64_t* const* compressed_inputs, const uint32_t* n_inputs,
+                                        const uint64_t* const* compressed_tables, size_t count, uint32_t blinding_factors, uint64_t* const* m);
+int h2hip_mvlookup_multiplicities_bn254_device(uint32_t k, const void* const* d_compressed_inputs, const uint32_t* n_inputs,
+                                               const void* const* d_compressed_tables, size_t count, uint32_t blinding_factors, void* const* d_m,
+                                               void* stream);
+int h2hip_mvlookup_sums_bn254(uint32_t k, const uint64_t beta[4], const uint64_t* const* compressed_inputs, const uint32_t* n_inputs,
+                              const uint64_t* const* compressed_tables, const uint64_t* const* m, size_t count, const uint64_t* blinding,
+                              uint32_t blinding_factors, uint64_t* const* phi);
+int h2hip_mvlookup_sums_bn254_device(uint32_t k, const uint64_t beta[4], const void* const* d_compressed_inputs, const uint32_t* n_inputs,
+                                     const void* const* d_compressed_tables, const void* const* d_m, size_t count, const uint64_t* blinding,
+                                     uint32_t blinding_factors, void* const* d_phi, void* stream);
 /* ff::BatchInvert (permutation/prover.rs:117, lookup/prover.rs:208): a[i] <- a[i]^-1 in place, zeros stay zero; n <= 2^30 */
 int h2hip_batch_invert_bn254_fr(uint64_t* a, size_t n);
 int h2hip_batch_invert_bn254_fr_device(void* d_a, size_t n, void* stream);

@@ -134,6 +134,9 @@ int h2hip_debug_set_keygen_group(uint64_t group_bytes);
 /* randomness: the element count from which the host forms of h2hip_fr_random_bn254 / h2hip_fr_from_bytes_wide_bn254 go to the device
  * (1: always; SIZE_MAX: never, the calling thread's loop at any n; 0 restores HALO2_HIP_RANDOM_MIN_N or the default). */
 int h2hip_debug_set_random_min_n(size_t n);
+/* mv-lookup grand sum: the consecutive rows one thread of the scan takes in a call of `count` arguments at this k and blinding_factors --
+ * the rule h2hip_mvlookup_sums_bn254 itself applies (the grand products' rule).  Needs no GPU. */
+int h2hip_debug_mvlookup_sum_rows(uint32_t k, uint32_t blinding_factors, size_t count, uint32_t* rows);
 
 #ifdef __cplusplus
 }
