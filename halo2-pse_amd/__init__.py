@@ -724,7 +724,7 @@ def _failures(kind, counts, rows):
 
 
 def verify_witness(k, gate_polys, lookups, theta, blinding_factors, permutation_columns, mapping, fixed=(), advice=(), instance=(),
-                   challenges=(), max_rows=64, shuffles=(), mvlookups=()):
+                   challenges=(), max_rows=64, shuffles=(), mvlookups=(), copies=None):
     """The three column-wide loops of MockProver::verify over one instance's columns: gate_polys are expression tuples (evaluation.py;
     every gate's polynomials in cs.gates order), lookups [(input_exprs, table_exprs)], compressed here with the caller's theta;
     permutation_columns [(kind, index)] with kind 'advice' / 'fixed' / 'instance' names the permutation argument's columns, mapping its
@@ -734,9 +734,15 @@ def verify_witness(k, gate_polys, lookups, theta, blinding_factors, permutation_
     shuffles [(input_exprs, shuffle_exprs)] (the argument of upstream PSE halo2) are compressed with the same theta and reported as
     ("shuffle", shuffle_index, row) after the lookups; the default checks none.  mvlookups [([input_exprs, ...], table_exprs)] (the
     logUp argument) go through the lookup check with the table repeated per input tuple and are reported after the shuffles as
-    ("mvlookup", input_index, row), the input tuples counted over all arguments in order."""
+    ("mvlookup", input_index, row), the input tuples counted over all arguments in order.  copies (a (C, 4) array or a CopyList) stands
+    in for mapping, which is then None: the copy constraints themselves, turned into the ordered mapping by permutation_mapping."""
     from .evaluation import flatten_graph, gate_check_graphs, lookup_compress_graphs
     k = int(k)
+    if copies is not None:
+        if mapping is not None:
+            raise ValueError("verify_witness: give mapping or copies, not both")
+        if len(permutation_columns):
+            mapping = permutation_mapping(k, len(permutation_columns), copies.array() if isinstance(copies, CopyList) else copies)
     out = []
     graphs = [flatten_graph(g) for g in gate_check_graphs(gate_polys)]
     if graphs:
@@ -811,6 +817,54 @@ class PermutationAssembly:
         tmp = mapping[lc, lr].copy()                                           # :98-100: the cells named in the call
         mapping[lc, lr] = mapping[rc, rr]
         mapping[rc, rr] = tmp
+
+
+def _copies_array(copies):
+    c = np.ascontiguousarray(np.asarray(copies, dtype=np.uint32).reshape(-1, 4))
+    return c if c.shape[0] else np.zeros((0, 4), dtype=np.uint32)
+
+
+def permutation_mapping(k, n_columns, copies):
+    """The ordered permutation mapping of a circuit's copy constraints (include/halo2hip.h, "permutation mapping from copy
+    constraints"): copies is a (C, 4) array of (left_column, left_row, right_column, right_row); every cell maps to the next cell of its
+    connected component in ascending column * 2^k + row order, the last one to the least.  Returns the (m, 2^k, 2) uint32 array that
+    permutation_keygen, check_permutation and verify_witness take.  The same cycles as PermutationAssembly.copy builds for these
+    constraints, in an order of its own: valid, not byte-identical."""
+    k, m = int(k), int(n_columns)
+    c = _copies_array(copies)
+    if not (0 <= k < 1 << 32 and 0 <= m < 1 << 32):
+        raise ValueError("k and n_columns must fit 32 bits")
+    # arguments beyond the limits go to the library, which names the limit: it reads no table then, so none of that size is made
+    within = k <= 28 and m <= 65535 and (m << k) <= 1 << 32
+    out = np.zeros((m, 1 << k, 2) if within else (min(m, 65536), 1, 2), dtype=np.uint32)
+    _check(lib().h2hip_permutation_mapping(ctypes.c_uint32(k), ctypes.c_uint32(m), _p(c) if c.shape[0] else None, ctypes.c_size_t(c.shape[0]),
+                                           _host_ptrs([out[j] for j in range(out.shape[0])])), "h2hip_permutation_mapping")
+    return out
+
+
+class CopyList:
+    """The copy constraints of a circuit, recorded: `copy` makes PermutationAssembly.copy's column and row checks and appends, and
+    `mapping()` builds the ordered mapping on the engine (permutation_mapping).  The order of the calls does not matter."""
+
+    def __init__(self, n, n_columns):
+        self.n, self.n_columns = int(n), int(n_columns)
+        if self.n < 1 or self.n & (self.n - 1):
+            raise ValueError("n must be a power of two")
+        self.copies = []
+
+    def copy(self, left_column, left_row, right_column, right_row):
+        lc, lr, rc, rr = int(left_column), int(left_row), int(right_column), int(right_row)
+        if not (0 <= lc < self.n_columns and 0 <= rc < self.n_columns):
+            raise ValueError("column not in the permutation")
+        if not (0 <= lr < self.n and 0 <= rr < self.n):
+            raise ValueError("row out of bounds")
+        self.copies.append((lc, lr, rc, rr))
+
+    def array(self):
+        return _copies_array(self.copies)
+
+    def mapping(self):
+        return permutation_mapping(self.n.bit_length() - 1, self.n_columns, self.array())
 
 
 def _domain_args(domain):
@@ -898,13 +952,17 @@ def key_lagrange_columns(domain, blinding_factors):
     return tuple(cols)
 
 
-def keygen_columns(params, domain, fixed, mapping, blinding_factors, delta=None):
+def keygen_columns(params, domain, fixed, mapping, blinding_factors, delta=None, copies=None):
     """The columns of keygen_vk + keygen_pk (plonk/keygen.rs:203-367) that are data-parallel, composed from the calls above: `fixed` is
     a list of (2^k, 4) Lagrange columns (batch_invert_assigned and compress_selectors applied), or of
     (numerators, rat_rows, rat_denoms) triples, which are inverted here (:298); mapping is the assembly's.  Returns a dict under the names
     evaluation.py's describe() takes -- fixed_cosets, perm_cosets, l0, l_last, l_active_row -- plus fixed_values, fixed_polys,
-    fixed_commitments, permutations (the list permutation_products takes), perm_polys, permutation_commitments (Jacobian (12,) uint64)."""
+    fixed_commitments, permutations (the list permutation_products takes), perm_polys, permutation_commitments (Jacobian (12,) uint64).
+    copies (a CopyList, or an (n_columns, (C, 4) array) pair) stands in for mapping, which is then None: the permutation's columns come
+    from permutation_keygen_from_copies, and the key is valid for the circuit, not byte-identical to the reference's."""
     k, n = int(domain.k), 1 << int(domain.k)
+    if copies is not None and mapping is not None:
+        raise ValueError("keygen_columns: give mapping or copies, not both")
     fixed = list(fixed)
     if fixed and isinstance(fixed[0], tuple):
         fixed_values = batch_invert_assigned(k, [f[0] for f in fixed], [f[1] for f in fixed], [f[2] for f in fixed])
@@ -912,7 +970,11 @@ def keygen_columns(params, domain, fixed, mapping, blinding_factors, delta=None)
         fixed_values = _cols(fixed, n, "fixed")
     fixed_polys = domain.lagrange_to_coeff_batch(fixed_values)                      # :306-309
     fixed_cosets = domain.coeff_to_extended_batch(fixed_polys)                      # :311-314
-    perm = permutation_keygen(domain, mapping, delta=delta)                         # :316-318
+    if copies is None:
+        perm = permutation_keygen(domain, mapping, delta=delta)                     # :316-318
+    else:
+        m_c, cp = (copies.n_columns, copies.array()) if isinstance(copies, CopyList) else copies
+        perm = permutation_keygen_from_copies(domain, m_c, cp, delta=delta)
     l0, l_last, l_active_row = key_lagrange_columns(domain, blinding_factors)       # :320-351
     commit = lambda cols: list(best_multiexp_batch(cols, params.g_lagrange)) if cols else []
     return {"fixed_values": fixed_values, "fixed_polys": fixed_polys, "fixed_cosets": fixed_cosets,
@@ -1911,6 +1973,13 @@ def lookup_sort_stats():
     return int(out[0]), int(out[1])
 
 
+def copies_sort_plan(n_copies):
+    """(block, merge passes) of permutation_mapping's sort for n_copies copies: the keys one workgroup sorts in LDS, and the passes after"""
+    out = (ctypes.c_uint32 * 2)()
+    _check(lib().h2hip_debug_copies_sort_plan(ctypes.c_size_t(n_copies), out), "h2hip_debug_copies_sort_plan")
+    return int(out[0]), int(out[1])
+
+
 def _opt_ptr_array(tensors):
     return None if tensors is None else _ptr_array(tensors)
 
@@ -1923,6 +1992,36 @@ def permutation_keygen_device(domain, d_mapping, d_permutations=None, d_polys=No
     _check(lib().h2hip_permutation_keygen_bn254_device(*_domain_args(domain), _p(d), _ptr_array(d_mapping), ctypes.c_uint32(len(d_mapping)),
                                                        _opt_ptr_array(d_permutations), _opt_ptr_array(d_polys), _opt_ptr_array(d_cosets),
                                                        _stream()), "h2hip_permutation_keygen_bn254_device")
+
+
+def permutation_mapping_device(k, n_columns, d_copies, d_mapping, n_copies=None):
+    """permutation_mapping over torch CUDA tensors: d_copies holds n_copies x 16 B (None with no copy), d_mapping[j] receives 2^k
+    (column, row) uint32 pairs (8 B per cell).  Queued on the current stream, which the call waits for once at its end (the flag of a
+    copy out of range: H2HipError, the mapping of the valid copies written)."""
+    if n_copies is None:
+        n_copies = 0 if d_copies is None else d_copies.numel() * d_copies.element_size() // 16
+    _check(lib().h2hip_permutation_mapping_device(ctypes.c_uint32(k), ctypes.c_uint32(n_columns), None if d_copies is None else _dptr(d_copies),
+                                                  ctypes.c_size_t(n_copies), _ptr_array(d_mapping), _stream()), "h2hip_permutation_mapping_device")
+
+
+def permutation_keygen_from_copies(domain, n_columns, copies, want=_KEYGEN_FORMS, delta=None):
+    """permutation_keygen from the copy constraints themselves: the copies are uploaded (16 B each), permutation_mapping_device builds
+    the ordered mapping in device memory and permutation_keygen_device reads it there, so the 8-byte-per-cell mapping never crosses
+    PCIe.  Returns what permutation_keygen(domain, permutation_mapping(k, n_columns, copies), want, delta) returns."""
+    import torch
+    want = _keygen_want(want)
+    k, m = int(domain.k), int(n_columns)
+    n = 1 << k
+    c = _copies_array(copies)
+    sizes = {"permutations": n, "polys": n, "cosets": domain.extended_len()}
+    if m == 0:
+        return {w: [] for w in want}
+    d_copies = torch.from_numpy(c.view(np.int32)).cuda() if c.shape[0] else None
+    d_map = [torch.empty((n, 2), dtype=torch.int32, device="cuda") for _ in range(m)]
+    permutation_mapping_device(k, m, d_copies, d_map, c.shape[0])
+    d_out = {w: [torch.empty((sizes[w], 4), dtype=torch.int64, device="cuda") for _ in range(m)] for w in want}
+    permutation_keygen_device(domain, d_map, d_out.get("permutations"), d_out.get("polys"), d_out.get("cosets"), delta)
+    return {w: [to_numpy_u64(t) for t in d_out[w]] for w in want}
 
 
 def batch_invert_assigned_device(k, d_numerators, d_rat_rows, rat_counts, d_rat_denoms, d_out):

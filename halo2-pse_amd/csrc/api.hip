@@ -918,6 +918,9 @@ static void release_ctx(Ctx* c) {
     c->check_ws.release();
     c->check_io.release();
     c->check_flag.release();
+    c->copies_ws.release();
+    c->copies_io.release();
+    c->copies_flag.release();
     c->serde_ws.release();
     c->serde_io.release();
     c->random_io.release();

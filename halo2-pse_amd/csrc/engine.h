@@ -188,6 +188,8 @@ struct Ctx {
     HostBuf keygen_flag;           // keygen.hip: the out-of-range flag of a permutation keygen read back at the end of the call
     DevBuf check_ws, check_io;     // check.hip: failure masks, tile counts, row lists and sort keys; the host-pointer forms' columns
     HostBuf check_flag;            // check.hip: the out-of-range flag of a permutation check read back at the end of the call
+    DevBuf copies_ws, copies_io;   // copies.hip: parents, sort keys, flag and pointer blob; the host-pointer form's copies and mapping
+    HostBuf copies_flag;           // copies.hip: the invalid-copy flag of a device-form mapping call read back at the end of the call
     DevBuf serde_ws, serde_io;     // serde.hip: failure mask, tile counts and the two result words; the host-pointer forms' elements
     DevBuf random_io;              // random.hip: the host-pointer forms' elements, from their threshold on
     HostBuf host_ws;               // pinned host memory for the window sums coming back

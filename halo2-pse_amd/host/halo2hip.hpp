@@ -990,9 +990,45 @@ struct VerifyingKey {
 };
 
 namespace keygen {
+using Cell = std::pair<uint32_t, uint32_t>;  // (column, row)
+
+// What Assembly and CopyAssembly share: build_vk / build_pk's columns (:105-242) from a mapping, on the engine
+inline ProvingKey build_from_mapping(const std::vector<std::vector<Cell>>& mapping, const poly::EvaluationDomain& domain, bool perms, bool polys,
+                                     bool cosets) {
+    const size_t m = mapping.size();
+    static_assert(sizeof(Cell) == 8, "a (column, row) pair is two interleaved uint32_t");
+    ProvingKey pk;
+    std::vector<const uint32_t*> mp(m);
+    std::vector<uint64_t*> a(m), b(m), c(m);
+    if (perms) pk.permutations.resize(m);
+    if (polys) pk.polys.resize(m);
+    if (cosets) pk.cosets.resize(m);
+    for (size_t j = 0; j < m; j++) {
+        if (mapping[j].size() != domain.n) throw std::logic_error("mapping column length != n");
+        mp[j] = &mapping[j][0].first;
+        if (perms) pk.permutations[j].values.resize(domain.n), a[j] = pk.permutations[j].values[0].l;
+        if (polys) pk.polys[j].values.resize(domain.n), b[j] = pk.polys[j].values[0].l;
+        if (cosets) pk.cosets[j].values.resize(domain.extended_len()), c[j] = pk.cosets[j].values[0].l;
+    }
+    Fr delta = Fr::delta();
+    engine_check(h2hip_permutation_keygen_bn254(domain.k, domain.omega.l, domain.omega_inv.l, domain.ifft_divisor.l, domain.extended_k,
+                                                domain.extended_omega.l, domain.g_coset.l, domain.g_coset_inv.l, delta.l, mp.data(), uint32_t(m),
+                                                perms ? a.data() : nullptr, polys ? b.data() : nullptr, cosets ? c.data() : nullptr),
+                 "permutation_keygen");
+    return pk;
+}
+// build_vk's commitments (:153-162): the sigma columns committed in Lagrange form as one batch
+inline VerifyingKey commit_permutations(const poly::kzg::ParamsKZG& params, const ProvingKey& pk) {
+    std::vector<const poly::Polynomial<poly::LagrangeCoeff>*> ptrs;
+    for (auto& c : pk.permutations) ptrs.push_back(&c);
+    VerifyingKey vk;
+    for (auto& c : params.commit_lagrange_many(ptrs)) vk.commitments.push_back(c.to_affine());
+    return vk;
+}
+
 // permutation::keygen::Assembly (plonk/permutation/keygen.rs:16-242); columns are the argument's column indices
 struct Assembly {
-    using Cell = std::pair<uint32_t, uint32_t>;
+    using Cell = keygen::Cell;
     std::vector<std::vector<Cell>> mapping, aux;
     std::vector<std::vector<size_t>> sizes;
 
@@ -1023,12 +1059,7 @@ struct Assembly {
 
     // build_vk (:105-165): the sigma columns on the engine, committed in Lagrange form as one batch
     VerifyingKey build_vk(const poly::kzg::ParamsKZG& params, const poly::EvaluationDomain& domain) const {
-        ProvingKey pk = build(domain, true, false, false);
-        std::vector<const poly::Polynomial<poly::LagrangeCoeff>*> ptrs;
-        for (auto& c : pk.permutations) ptrs.push_back(&c);
-        VerifyingKey vk;
-        for (auto& c : params.commit_lagrange_many(ptrs)) vk.commitments.push_back(c.to_affine());  // :153-162
-        return vk;
+        return commit_permutations(params, build(domain, true, false, false));  // :153-162
     }
 
     // build_pk (:167-242)
@@ -1036,28 +1067,43 @@ struct Assembly {
 
    private:
     ProvingKey build(const poly::EvaluationDomain& domain, bool perms, bool polys, bool cosets) const {
-        const size_t m = mapping.size();
-        static_assert(sizeof(Cell) == 8, "a (column, row) pair is two interleaved uint32_t");
-        ProvingKey pk;
-        std::vector<const uint32_t*> mp(m);
-        std::vector<uint64_t*> a(m), b(m), c(m);
-        if (perms) pk.permutations.resize(m);
-        if (polys) pk.polys.resize(m);
-        if (cosets) pk.cosets.resize(m);
-        for (size_t j = 0; j < m; j++) {
-            if (mapping[j].size() != domain.n) throw std::logic_error("mapping column length != n");
-            mp[j] = &mapping[j][0].first;
-            if (perms) pk.permutations[j].values.resize(domain.n), a[j] = pk.permutations[j].values[0].l;
-            if (polys) pk.polys[j].values.resize(domain.n), b[j] = pk.polys[j].values[0].l;
-            if (cosets) pk.cosets[j].values.resize(domain.extended_len()), c[j] = pk.cosets[j].values[0].l;
-        }
-        Fr delta = Fr::delta();
-        engine_check(h2hip_permutation_keygen_bn254(domain.k, domain.omega.l, domain.omega_inv.l, domain.ifft_divisor.l, domain.extended_k,
-                                                    domain.extended_omega.l, domain.g_coset.l, domain.g_coset_inv.l, delta.l, mp.data(), uint32_t(m),
-                                                    perms ? a.data() : nullptr, polys ? b.data() : nullptr, cosets ? c.data() : nullptr),
-                     "permutation_keygen");
-        return pk;
+        return build_from_mapping(mapping, domain, perms, polys, cosets);
     }
+};
+
+// The copy constraints recorded, and the mapping built from them on the engine (h2hip_permutation_mapping): the ordered mapping of
+// include/halo2hip.h -- every cell to the next cell of its connected component in ascending column * n + row order -- which does not depend
+// on the order of the copy calls.  Same copy / build_vk / build_pk surface as Assembly, same cycles for the same constraints; the key is
+// valid for the circuit, not byte-identical to the one Assembly builds.
+struct CopyAssembly {
+    using Cell = keygen::Cell;
+    size_t n, n_columns;
+    std::vector<uint32_t> copies;  // (left_column, left_row, right_column, right_row) per copy
+
+    CopyAssembly(size_t n_, size_t n_columns_) : n(n_), n_columns(n_columns_) {
+        if (n == 0 || (n & (n - 1))) throw std::logic_error("n must be a power of two");
+    }
+
+    void copy(size_t left_column, size_t left_row, size_t right_column, size_t right_row) {  // Assembly::copy's checks (:55-71)
+        if (left_column >= n_columns || right_column >= n_columns) throw std::out_of_range("ColumnNotInPermutation");
+        if (left_row >= n || right_row >= n) throw std::out_of_range("BoundsFailure");
+        for (size_t v : {left_column, left_row, right_column, right_row}) copies.push_back(uint32_t(v));
+    }
+
+    std::vector<std::vector<Cell>> mapping() const {
+        uint32_t k = 0;
+        while ((size_t(1) << k) < n) k++;
+        std::vector<std::vector<Cell>> mp(n_columns, std::vector<Cell>(n));
+        std::vector<uint32_t*> ptrs(n_columns);
+        for (size_t j = 0; j < n_columns; j++) ptrs[j] = &mp[j][0].first;
+        engine_check(h2hip_permutation_mapping(k, uint32_t(n_columns), copies.data(), copies.size() / 4, ptrs.data()), "permutation_mapping");
+        return mp;
+    }
+
+    VerifyingKey build_vk(const poly::kzg::ParamsKZG& params, const poly::EvaluationDomain& domain) const {
+        return commit_permutations(params, build_from_mapping(mapping(), domain, true, false, false));
+    }
+    ProvingKey build_pk(const poly::EvaluationDomain& domain) const { return build_from_mapping(mapping(), domain, true, true, true); }
 };
 }  // namespace keygen
 }  // namespace permutation
@@ -1072,8 +1118,9 @@ struct ProvingKeyColumns {
     permutation::ProvingKey permutation;
 };
 
-inline ProvingKeyColumns keygen_pk(const poly::EvaluationDomain& domain, const std::vector<std::vector<Assigned>>& fixed,
-                                   const permutation::keygen::Assembly& assembly, size_t blinding_factors) {
+template <class AssemblyT>  // permutation::keygen::Assembly or CopyAssembly
+inline ProvingKeyColumns keygen_pk_with(const poly::EvaluationDomain& domain, const std::vector<std::vector<Assigned>>& fixed,
+                                        const AssemblyT& assembly, size_t blinding_factors) {
     ProvingKeyColumns pk;
     pk.fixed_values = batch_invert_assigned(domain, fixed);                    // :298
     pk.fixed_polys = domain.lagrange_to_coeff_batch(pk.fixed_values);          // :306-309
@@ -1085,6 +1132,15 @@ inline ProvingKeyColumns keygen_pk(const poly::EvaluationDomain& domain, const s
                                                   pk.l_last.values[0].l, pk.l_active_row.values[0].l),
                  "key_lagrange_columns");                                      // :320-351
     return pk;
+}
+inline ProvingKeyColumns keygen_pk(const poly::EvaluationDomain& domain, const std::vector<std::vector<Assigned>>& fixed,
+                                   const permutation::keygen::Assembly& assembly, size_t blinding_factors) {
+    return keygen_pk_with(domain, fixed, assembly, blinding_factors);
+}
+// ... from the recorded copy constraints: the permutation's columns are those of the ordered mapping (valid, not byte-identical)
+inline ProvingKeyColumns keygen_pk(const poly::EvaluationDomain& domain, const std::vector<std::vector<Assigned>>& fixed,
+                                   const permutation::keygen::CopyAssembly& assembly, size_t blinding_factors) {
+    return keygen_pk_with(domain, fixed, assembly, blinding_factors);
 }
 
 }  // namespace plonk

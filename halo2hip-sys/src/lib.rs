@@ -611,6 +611,27 @@ pub fn try_permutation_keygen<F: Field + 'static>(domain: &KeygenDomain<F>, delt
     Some(PermutationKeyColumns { permutations: perms, polys, cosets })
 }
 
+/// The permutation mapping from the copy constraints themselves, `[left_column, left_row, right_column, right_row]` each, in place of
+/// the serial `Assembly::copy` loop (plonk/permutation/keygen.rs:46-103): every cell maps to the next cell of its connected component in
+/// ascending `column * 2^k + row` order, the last one to the least (include/halo2hip.h).  The result is what `try_permutation_keygen` and
+/// `try_check_permutation` take as `mapping`.  It has the cycles `Assembly::copy` builds for the same constraints, in an order of its
+/// own, so a key built from it is valid, not byte-identical: prover and verifier must both use it.  `None` on any failure, a copy out
+/// of range included.
+pub fn try_permutation_mapping(k: u32, n_columns: usize, copies: &[[u32; 4]]) -> Option<Vec<Vec<[u32; 2]>>> {
+    if k > 28 || n_columns > 65535 || ((n_columns as u64) << k) > (1u64 << 32) || copies.len() > (1usize << 30) {
+        return None;
+    }
+    let n = 1usize << k;
+    let mut mapping: Vec<Vec<[u32; 2]>> = (0..n_columns).map(|_| vec![[0u32; 2]; n]).collect();
+    let mp: Vec<*mut u32> = mapping.iter_mut().map(|c| c.as_mut_ptr() as *mut u32).collect();
+    let cp = if copies.is_empty() { std::ptr::null() } else { copies.as_ptr() as *const u32 };
+    let rc = unsafe { ffi::h2hip_permutation_mapping(k, n_columns as u32, cp, copies.len(), mp.as_ptr()) };
+    if rc != 0 {
+        return None;
+    }
+    Some(mapping)
+}
+
 /// `batch_invert_assigned` (poly.rs:180-209) over columns the caller has flattened from `Assigned<F>`: `numerators[j]` (zero for `Zero`,
 /// `x` for `Trivial(x)`), and for the `Rational` cells their ascending rows `rat_rows[j]` and denominators `rat_denoms[j]`.  One
 /// inversion over all columns.  `None` on any failure.

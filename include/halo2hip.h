@@ -682,6 +682,28 @@ int h2hip_key_lagrange_columns_bn254(uint32_t k, const uint64_t omega_inv[4], co
 int h2hip_key_lagrange_columns_bn254_device(uint32_t k, const uint64_t omega_inv[4], const uint64_t ifft_divisor[4], uint32_t extended_k,
                                             const uint64_t extended_omega[4], const uint64_t g_coset[4], const uint64_t g_coset_inv[4],
                                             uint32_t blinding_factors, void* d_l0, void* d_l_last, void* d_l_active_row, void* stream);
+/* Permutation mapping from copy constraints: the `mapping` that h2hip_permutation_keygen_bn254, h2hip_check_permutation_bn254 and their
+ * _device forms take, built from the list of a circuit's copies instead of by Assembly::copy (plonk/permutation/keygen.rs:46-103), whose
+ * result depends on the order of the calls and which is serial by construction.  The definition is later than the reference (upstream PSE
+ * halo2's thread-safe-region assembly builds such an ordered mapping); it is stated here and pinned by tests/copies_util.py:
+ *   cells are numbered id(c, r) = c 2^k + r, for c < n_columns and r < 2^k;
+ *   a copy is four uint32_t (left_column, left_row, right_column, right_row), 16 bytes; the copies are the edges of a graph on the cells;
+ *   for every cell x, mapping[c][r] is the cell of x's connected component with the least id greater than id(x), or, if there is none,
+ *   the component's least cell;
+ *   a cell that no copy touches maps to itself; self-copies and repeated copies change nothing;
+ *   the result does not depend on the order of the copies or on which side of a copy is left.
+ * The permutation has the same cycles (as sets of cells) as Assembly::copy produces for the same constraints, so any key built from it is
+ * a valid key for the circuit: valid, not byte-identical -- it is not the reference's sigma polynomials or verifying key for that circuit,
+ * and a prover and a verifier must both use keys from the same mapping.
+ * mapping[j] receives 2^k interleaved (column, row) pairs, 8 bytes per cell.  k <= 28, n_columns <= 65535, n_columns 2^k <= 2^32 (cell
+ * ids are 32-bit) and n_copies <= 2^30: beyond any of these the call returns H2HIP_EINVAL.  n_copies == 0 writes the identity;
+ * n_columns == 0 writes nothing.  A copy with a column >= n_columns or a row >= 2^k is H2HIP_EINVAL: the host form finds it before any
+ * device work and names the lowest offending copy index; the _device form ignores the bad copies, writes the mapping of the valid ones,
+ * synchronises `stream` once at the end of the call to read its flag and returns H2HIP_EINVAL.  Host form: only the copies are uploaded
+ * and the mapping is downloaded.  _device form: d_copies (16-byte aligned) and d_mapping[j] (8-byte aligned, else H2HIP_EINVAL; no column
+ * aliases another or the copies) are device pointers, the pointer table is host memory read before the call returns, kernels are queued on `stream`. */
+int h2hip_permutation_mapping(uint32_t k, uint32_t n_columns, const uint32_t* copies, size_t n_copies, uint32_t* const* mapping);
+int h2hip_permutation_mapping_device(uint32_t k, uint32_t n_columns, const void* d_copies, size_t n_copies, void* const* d_mapping, void* stream);
 
 /* ---- witness check: the three column-wide loops of MockProver::verify (dev.rs:603-1300) over the prover's own columns -----------------
  * n = 2^k, k <= 28.  Each call checks n_items constraints over the rows and reports, per constraint, how many rows fail and which are
@@ -803,7 +825,8 @@ uint32_t h2hip_get_msm_window_fixed_base(size_t n);
  * "evalh_cosets", "evalh_gates", "evalh_perm", "evalh_lookups", "evalh_part_scale" (inside "evalh_cosets") and "evalh_part_io" (the parts form), "products", "opening_eval", "opening_combine", "lookup_compress",
  * "lookup_permute", "check_gates", "check_permutation", "check_lookups" (each check: its kernels, without the delivery of counts / rows),
  * "g1_decompress", "g1_validate", "fr_from_repr" (each with its failure count; the _device forms too), "g1_compress", "fr_to_repr" (host forms),
- * "fr_random", "fr_from_wide" (the _device forms, and the host forms from their threshold on). */
+ * "fr_random", "fr_from_wide" (the _device forms, and the host forms from their threshold on), "copies_components", "copies_sort",
+ * "copies_scatter" (the three parts of h2hip_permutation_mapping[_device]). */
 /* on = 1: every stage (each event record costs the stream ~10 us of gap); on = 2: only the dominant kernel ("msm_accum"),
  * timed through its own dispatch packet with no gap; 0: off */
 int h2hip_profile_enable(int on);

@@ -137,6 +137,10 @@ int h2hip_debug_set_random_min_n(size_t n);
 /* mv-lookup grand sum: the consecutive rows one thread of the scan takes in a call of `count` arguments at this k and blinding_factors --
  * the rule h2hip_mvlookup_sums_bn254 itself applies (the grand products' rule).  Needs no GPU. */
 int h2hip_debug_mvlookup_sum_rows(uint32_t k, uint32_t blinding_factors, size_t count, uint32_t* rows);
+/* permutation mapping from copies: the sort of a call with n_copies copies -- out[0] = the keys one workgroup sorts in LDS (the block: the
+ * 2 n_copies endpoint keys are padded to a multiple of it), out[1] = the merge passes that follow.  The block is fixed (no setter: tests
+ * choose their copy counts around it).  Needs no GPU. */
+int h2hip_debug_copies_sort_plan(size_t n_copies, uint32_t out[2]);
 
 #ifdef __cplusplus
 }
