@@ -272,11 +272,7 @@ static void read_config() {
     if (env_u64("HALO2_HIP_LAZY_PIN", &v)) t.lazy_pin_after = (uint32_t)v;
     if (env_u64("HALO2_HIP_COLUMN_CACHE_GB", &v)) c.column_cache_bytes = (size_t)v << 30;
     if (env_u64("HALO2_HIP_NTT_TWIDDLE_MB", &v)) t.ntt_full_budget = v << 20;
-    if (env_u64("HALO2_HIP_EVALH_CODEGEN", &v)) {  // as h2hip_debug_set_evalh_codegen(v, 0)
-        t.evalh_codegen = (int)v & 15;
-        t.evalh_gen_fuse = !((int)v & 16);
-        t.evalh_codegen_max_ops = Tuning{}.evalh_codegen_max_ops;
-    }
+    if (env_u64("HALO2_HIP_EVALH_CODEGEN", &v)) evalh_codegen_apply(&t, (int)v, 0);  // as h2hip_debug_set_evalh_codegen(v, 0)
     if (env_u64("HALO2_HIP_MSM_WINDOW", &v) && v >= 2 && v <= 24) t.msm_window = (uint32_t)v;
     {  // HALO2_HIP_STREAM=0: host-slice MSMs upload whole arrays ahead of the run (no copier thread); HALO2_HIP_STREAM_MIN_N: threshold
         uint64_t on = 1, min_n = 0;

@@ -344,6 +344,9 @@ struct Tuning {
     // register allocator (100 live slots = 900 VGPRs of state: 205 s) for a kernel that would spill anyway (EVALH_CODEGEN_MAX_SLOTS).
     uint32_t evalh_codegen_max_ops = 1200;
     bool evalh_gen_fuse = true;  // two products meeting in a sum share one reduction (gen_source); codegen mode + 16 turns it off (A/B, tests)
+    // the stages whose arguments get a generated kernel of their own beside the gates and the halo2 lookups (gen_stage_source): the default
+    // set is what the measurement of DESIGN.md 5 decided; codegen mode + 32 turns both off, + 64 both on
+    bool evalh_gen_shuffle = true, evalh_gen_mvlookup = true;
     uint32_t evalh_max_local_slots = 256;  // programs needing more slots use the global-workspace form of the kernels (tests force it)
     size_t evalh_lookup_group_bytes = (size_t)2 << 30;  // HBM one group of lookup cosets may take (tests shrink it to force several groups)
     bool evalh_part_fused = false;  // parts form: the unpinned columns' coset scaling in the transform's first-pass load (ntt_part_device_batch), or evalh_part_scale_kernel + plain transform (DESIGN.md 5 has the A/B)
@@ -355,6 +358,16 @@ struct Tuning {
     size_t random_min_n = 0;  // element count from which the host forms of the randomness go to the device (0 = HALO2_HIP_RANDOM_MIN_N or its default, random.hip)
 };
 const Tuning& tune();
+// h2hip_debug_set_evalh_codegen(mode, max_ops) and HALO2_HIP_EVALH_CODEGEN=mode: bits 0-3 the mode, + 16 without the fusion, the two-bit
+// field at + 32 / + 64 the stage kernels (0 = the default set, + 32 none, + 64 both); max_ops 0 restores the default
+inline void evalh_codegen_apply(Tuning* t, int mode, uint32_t max_ops) {
+    t->evalh_codegen = mode & 15;
+    t->evalh_gen_fuse = !(mode & 16);
+    const int stages = (mode >> 5) & 3;
+    t->evalh_gen_shuffle = stages == 0 ? Tuning{}.evalh_gen_shuffle : stages >= 2;
+    t->evalh_gen_mvlookup = stages == 0 ? Tuning{}.evalh_gen_mvlookup : stages >= 2;
+    t->evalh_codegen_max_ops = max_ops ? max_ops : Tuning{}.evalh_codegen_max_ops;
+}
 // A setter's hold on the settings: the engine lock taken exclusively, as h2hip_shutdown takes it, so it waits for every running call and
 // the next one sees the new value.  It does not initialise the engine, touches no GPU and opens no roctx range.  Not from inside a
 // call that holds an Entry or a TuneRead (a callback of the library): that would wait for itself.

@@ -280,46 +280,27 @@ __global__ void __launch_bounds__(256) evalh_lookup_kernel(ProgDev g, LookupDev 
     }
 }
 
-// One shuffle argument's share of a row (the shuffle argument of upstream PSE halo2: include/halo2hip.h, h2hip_evalh_shuffles).  ga and
-// gs are the input and the shuffle side's programs, a = A + gamma and s = S + gamma their values; both run on one Slots object, which
-// the host sizes for the larger plan of the two, and a is held in registers while gs runs.  Magnitudes in units of r in brackets.
-struct ShuffleDev {
-    const Fe* product;  // extended coset of z
-    const Fe *l0, *l_last, *l_active;
-};
+// One shuffle argument's share of a row: ga and gs are the input and the shuffle side's programs, a = A + gamma and s = S + gamma their
+// values; both run on one Slots object, which the host sizes for the larger plan of the two, and a is held in registers while gs runs.
+// The three terms are shuffle_row's (evalh_dev.h), which the kernel generated per argument ends with too.
 template <int MAXI>
 __global__ void __launch_bounds__(256) evalh_shuffle_kernel(ProgDev ga, ProgDev gs, ShuffleDev sh, ColsDev c, Fe* values, Fu* gws, uint32_t lanes) {
     const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
     if (tid >= lanes) return;
     Slots<MAXI> slots(gws + tid, lanes);
-    const Fu one = fu_one_i<UF>();
     for (uint64_t row = tid; row < (1ull << c.log_size); row += lanes) {
         const uint32_t idx = (uint32_t)row;
-        const uint32_t r_next = rot_idx(idx, 1, c.rot_scale, c.log_size);
         const Fu a = prog_eval(ga, c, idx, fu_zero(), slots);  // [< 15 a slot, < 32 a column or a constant]
         const Fu s = prog_eval(gs, c, idx, fu_zero(), slots);  // [< 32]
-        const Fu z = ld_i(sh.product[idx]);                    // [32]
-        Fu v = ld_i(values[idx]);                              // [32]
-        // l_0(X) * (1 - z(X)) = 0
-        v = fold_y(v, c.y, subn(one, z), ld_i(sh.l0[idx]));                                   // [1.2] + [33 * 32 / 169 + 1 = 7.3] = [8.5]
-        // l_last(X) * (z(X)^2 - z(X)) = 0
-        v = fold_y(v, c.y, subn(fu_sqr<UF>(z), z), ld_i(sh.l_last[idx]));                     // [1.1] + [(7.1 + 32) * 32 / 169 + 1 = 8.4] = [9.5]
-        // (1 - (l_last + l_blind)) * (z(wX) s - z(X) a) = 0: the difference of the two products with one reduction
-        const Fu diff = fu_mul_sub<UF>(ld_i(sh.product[r_next]), s, z, a);                    // [(32 * 32 + 32 * 32) / 169 + 1 = 13.2]
-        v = fold_y(v, c.y, diff, ld_i(sh.l_active[idx]));                                     // [1.1] + [13.2 * 32 / 169 + 1 = 3.5] = [4.6]
-        values[idx] = out_e(v);  // [< 15]
+        shuffle_row(sh, c, idx, a, s, values);
     }
 }
 
-// One logUp (mv-lookup) argument's share of a row (include/halo2hip.h, h2hip_evalh_mvlookups).  progs holds the argument's K input
-// programs, then its table program; each value is (theta fold) + beta.  The programs run in turn on one Slots object, which the host
-// sizes for the largest plan among them, and between two of them only P = prod f_c, Q = sum_c prod_{l != c} f_l (streamed as
-// Q <- Q f + P; P <- P f: no inversion on the coset) stay in registers; the table program runs last, so tau is never held across one.
+// One logUp (mv-lookup) argument's share of a row.  progs holds the argument's K input programs, then its table program; each value is
+// (theta fold) + beta.  The programs run in turn on one Slots object, which the host sizes for the largest plan among them, and between
+// two of them only P = prod f_c, Q = sum_c prod_{l != c} f_l (streamed as Q <- Q f + P; P <- P f: no inversion on the coset) stay in
+// registers; the table program runs last, so tau is never held across one.  The three terms are mvlookup_row's (evalh_dev.h).
 // Magnitudes in units of r in brackets: P_0 = 1, P <- P f [P 32 / 169 + 1 <= 1.3]; Q_0 = 0, Q <- Q f + P [Q 32 / 169 + 1 + 1.3 <= 2.9].
-struct MvLookupDev {
-    const Fe *phi, *m;  // extended cosets of the grand sum and of the multiplicities
-    const Fe *l0, *l_last, *l_active;
-};
 template <int MAXI>
 __global__ void __launch_bounds__(256) evalh_mvlookup_kernel(const ProgDev* __restrict__ progs, uint32_t n_inputs, MvLookupDev mv, ColsDev c,
                                                              Fe* values, Fu* gws, uint32_t lanes) {
@@ -328,7 +309,6 @@ __global__ void __launch_bounds__(256) evalh_mvlookup_kernel(const ProgDev* __re
     Slots<MAXI> slots(gws + tid, lanes);
     for (uint64_t row = tid; row < (1ull << c.log_size); row += lanes) {
         const uint32_t idx = (uint32_t)row;
-        const uint32_t r_next = rot_idx(idx, 1, c.rot_scale, c.log_size);
         Fu P = fu_one_i<UF>(), Q = fu_zero();
         for (uint32_t t = 0; t < n_inputs; t++) {
             const Fu f = prog_eval(progs[t], c, idx, fu_zero(), slots);  // [< 32]
@@ -336,18 +316,7 @@ __global__ void __launch_bounds__(256) evalh_mvlookup_kernel(const ProgDev* __re
             P = mul_i(P, f);                                             // [<= 1.3]
         }
         const Fu tau = prog_eval(progs[n_inputs], c, idx, fu_zero(), slots);  // [< 32]
-        const Fu pc = ld_i(mv.phi[idx]);                                      // [32]
-        Fu v = ld_i(values[idx]);                                             // [32]
-        // l_0(X) * phi(X) = 0
-        v = fold_y(v, c.y, pc, ld_i(mv.l0[idx]));                             // [1.2] + [32 * 32 / 169 + 1 = 7.1] = [8.3]
-        // l_last(X) * phi(X) = 0
-        v = fold_y(v, c.y, pc, ld_i(mv.l_last[idx]));                         // [1.1] + [7.1] = [8.2]
-        // (1 - (l_last + l_blind)) * (tau P (phi(wX) - phi(X)) - tau Q + m P) = 0: the first two products leave with one reduction
-        const Fu tp = mul_i(tau, P);                                                        // [32 * 1.3 / 169 + 1 = 1.3]
-        const Fu e = addn(fu_mul_sub<UF>(tp, subn(ld_i(mv.phi[r_next]), pc), tau, Q),       // [(1.3 * 64 + 32 * 2.9) / 169 + 1 = 2.1]
-                          mul_i(ld_i(mv.m[idx]), P));                                       // + [32 * 1.3 / 169 + 1 = 1.3] = [3.4]
-        v = fold_y(v, c.y, e, ld_i(mv.l_active[idx]));                                      // [1.1] + [3.4 * 32 / 169 + 1 = 1.7] = [2.8]
-        values[idx] = out_e(v);  // [< 15]
+        mvlookup_row(mv, c, idx, tau, P, Q, values);
     }
 }
 
@@ -595,17 +564,27 @@ static int compile_any(const h2hip_graph* g, Program* P) {
 // thread the first time a program is seen (HALO2_HIP_EVALH_CODEGEN=1, default) while the interpreter serves the calls in between;
 // code objects are cached per process by source hash and, with HALO2_HIP_CACHE_DIR set, on disk.  =2 compiles inline (tests), =0 off.
 // Programs of more than Tuning::evalh_codegen_max_ops operations, or with more values alive at once than this, stay with the interpreter.
+// A halo2 lookup's table expression, a shuffle's two programs and an mv-lookup argument's K + 1 are generated the same way, one kernel
+// per argument that ends with the stage's row function of evalh_dev.h (GenKind below); the limits then count a kernel's programs together.
 #define EVALH_CODEGEN_MAX_SLOTS 48
-// mode: 0 off, 1 background compile (default), 2 compile inline; + 16: without the fusion of two products; max_ops 0 restores the default
+// mode: 0 off, 1 background compile (default), 2 compile inline; + 16: without the fusion of two products; the two-bit field at + 32 / + 64
+// selects the generated kernels of the shuffle and mv-lookup stages: 0 the default set (Tuning::evalh_gen_shuffle / evalh_gen_mvlookup),
+// + 32 none (gates and lookups keep theirs), + 64 both; max_ops 0 restores the default
 extern "C" int h2hip_debug_set_evalh_codegen(int mode, uint32_t max_ops) {
     TuneWrite t;
-    t->evalh_codegen = mode & 15;
-    t->evalh_gen_fuse = !(mode & 16);
-    t->evalh_codegen_max_ops = max_ops ? max_ops : Tuning{}.evalh_codegen_max_ops;
+    evalh_codegen_apply(t.operator->(), mode, max_ops);
     return 0;
 }
 struct RtcStats {
     std::atomic<uint64_t> compiled{0}, failed{0}, launches{0}, interpreted{0}, disk_hits{0};
+    // per kind (GenKind): launches of a generated kernel and of the interpreter.  launches / interpreted above are the gates' and the
+    // lookups' alone, as before the stage kernels existed (tools/evalh_bench.py reads them)
+    std::atomic<uint64_t> gen[4] = {}, interp[4] = {};
+    std::atomic<uint64_t> pending{0};  // background compilations queued or running
+    void launched(int kind, bool generated) {
+        (generated ? gen : interp)[kind]++;
+        if (kind <= 1) (generated ? launches : interpreted)++;
+    }
 };
 static RtcStats g_rtc_stats;
 extern "C" int h2hip_debug_evalh_codegen_stats(uint64_t out[5]) {
@@ -615,6 +594,15 @@ extern "C" int h2hip_debug_evalh_codegen_stats(uint64_t out[5]) {
     out[2] = g_rtc_stats.launches;
     out[3] = g_rtc_stats.interpreted;
     out[4] = g_rtc_stats.disk_hits;
+    return 0;
+}
+extern "C" int h2hip_debug_evalh_codegen_stage_stats(uint64_t out[9]) {
+    if (!out) return H2HIP_EINVAL;
+    for (int k = 0; k < 4; k++) {
+        out[2 * k] = g_rtc_stats.gen[k];
+        out[2 * k + 1] = g_rtc_stats.interp[k];
+    }
+    out[8] = g_rtc_stats.pending;
     return 0;
 }
 
@@ -709,29 +697,114 @@ static std::vector<int> fusion_plan(const Program& P, bool fuse) {
 // the program as HIP source.  Operands: constants are literals (I-form limbs), slots are locals, a column operand is a load at the
 // row index of its rotation (one index variable per distinct rotation), challenges and beta / gamma / theta / y come with the launch.
 static constexpr bool EVALH_GEN_BARRIERS = true;
-// lookup: the program is a lookup argument's compressed table expression (evaluated with PreviousValue = 0, :466-480) and the kernel ends
-// with that argument's five constraints (lookup_row, evalh_dev.h) instead of storing the program's result.
-static std::string gen_source(const h2hip_graph& g, const Program& P, bool lookup = false) {
-    const bool sched_barriers = EVALH_GEN_BARRIERS;
-    std::string src;
-    src.reserve(64 * P.ops.size() + 4096);
+// What one generated kernel is made of: kind and the programs in the order the kernel runs them.
+//   gates     one program; the row stores its result
+//   lookup    one program, a lookup argument's compressed table expression (evaluated with PreviousValue = 0, :466-480); the kernel ends
+//             with that argument's five constraints (lookup_row, evalh_dev.h) instead of storing the program's result
+//   shuffle   two programs, the input side's then the shuffle side's; the kernel ends with shuffle_row
+//   mvlookup  K + 1 programs, the K input tuples' in argument order then the table's; the kernel ends with mvlookup_row
+enum GenKind { GEN_GATES = 0, GEN_LOOKUP = 1, GEN_SHUFFLE = 2, GEN_MVLOOKUP = 3, GEN_KINDS = 4 };
+static const char* const GEN_KERNEL_NAME[GEN_KINDS] = {"evalh_gates_gen", "evalh_lookup_gen", "evalh_shuffle_gen", "evalh_mvlookup_gen"};
+struct GenUnit {
+    GenKind kind;
+    std::vector<const h2hip_graph*> graphs;
+    std::vector<const Program*> progs;
+    bool stage() const { return kind >= GEN_SHUFFLE; }
+    size_t n_ops() const {
+        size_t n = 0;
+        for (const Program* P : progs) n += P->ops.size();
+        return n;
+    }
+    uint32_t n_slots() const {  // locals the programs share: slot s of one program is slot s of the next
+        uint32_t n = 0;
+        for (const Program* P : progs) n = std::max(n, P->n_slots);
+        return n;
+    }
+    // values alive at once: the largest program's slots and what the kernel holds across programs (a shuffle's a; an mv-lookup's P and Q)
+    uint32_t n_live() const { return n_slots() + (kind == GEN_SHUFFLE ? 1u : kind == GEN_MVLOOKUP ? 2u : 0u); }
+};
+static GenUnit gen_unit(GenKind kind, const h2hip_graph* const* graphs, const Program* progs, size_t n) {
+    GenUnit u;
+    u.kind = kind;
+    for (size_t i = 0; i < n; i++) {
+        u.graphs.push_back(graphs[i]);
+        u.progs.push_back(progs + i);
+    }
+    return u;
+}
+// within the generator's limits (beyond them the stage keeps the interpreter): an empty gates program has no kernel, an empty graph of
+// another kind has value zero and is generated as that
+static bool gen_within_limits(const GenUnit& u) {
+    if (u.kind == GEN_GATES && u.progs[0]->ops.empty()) return false;
+    return u.n_ops() <= tune().evalh_codegen_max_ops && u.n_live() <= EVALH_CODEGEN_MAX_SLOTS;
+}
+
+// How program `prog` of a kernel spells its operands.  The lone program of a gates / lookup kernel: constants K<i>, one row index r<i> per
+// entry of its rotations table.  A program of a stage kernel: constants K<prog>_<i> (literals per program), row indices by rotation VALUE
+// (rp<v> / rm<v>), so that a rotation two programs use is formed once; column pointers are named by (kind, index) in both.
+struct GenNames {
+    const h2hip_graph* g;
+    int prog;  // < 0: the lone program
+};
+static const char* const gen_tab_name[3] = {"fixed", "advice", "instance"};
+static const char gen_col_name[3] = {'F', 'A', 'N'};
+static std::string gen_rot_value_name(int32_t rotation) {
+    char t[32];
+    const int64_t v = rotation;
+    snprintf(t, sizeof(t), v < 0 ? "rm%lld" : "rp%lld", (long long)(v < 0 ? -v : v));
+    return t;
+}
+static std::string gen_rot_name(const GenNames& nm, uint32_t b) {
+    if (nm.prog >= 0) return gen_rot_value_name(nm.g->rotations[b]);
+    char t[32];
+    snprintf(t, sizeof(t), "r%u", b);
+    return t;
+}
+static std::string gen_operand(const GenNames& nm, const h2hip_value_source& v) {
+    char t[96];
+    switch (v.kind) {
+        case H2HIP_VS_CONSTANT:
+            if (nm.prog < 0) snprintf(t, sizeof(t), "K%u", v.a);
+            else snprintf(t, sizeof(t), "K%d_%u", nm.prog, v.a);
+            break;
+        case H2HIP_VS_INTERMEDIATE: snprintf(t, sizeof(t), "s%u", v.a); break;
+        case H2HIP_VS_FIXED: case H2HIP_VS_ADVICE: case H2HIP_VS_INSTANCE:
+            snprintf(t, sizeof(t), "ld_i(%c%u[%s])", gen_col_name[v.kind - H2HIP_VS_FIXED], v.a, gen_rot_name(nm, v.b).c_str());
+            break;
+        case H2HIP_VS_CHALLENGE: snprintf(t, sizeof(t), "ld_const_fu(c.challenges, %u)", v.a); break;
+        case H2HIP_VS_BETA: return "c.beta";
+        case H2HIP_VS_GAMMA: return "c.gamma";
+        case H2HIP_VS_THETA: return "c.theta";
+        case H2HIP_VS_Y: return "c.y";
+        case H2HIP_VS_PREVIOUS: return "prev";
+        default: return "fu_zero()";
+    }
+    return t;
+}
+static void gen_add(std::string& src, const char* fmt, ...) {
     char buf[512];
-    auto add = [&](const char* fmt, ...) {
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(buf, sizeof(buf), fmt, ap);
-        va_end(ap);
-        src += buf;
-    };
-    std::vector<uint8_t> use_const(g.n_constants, 0), use_rot(g.n_rotations, 0);
-    std::vector<std::vector<uint8_t>> use_col(3);
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    src += buf;
+}
+// what a program reads, noted for the declarations in front of the first statement
+struct GenUses {
+    std::vector<uint8_t> consts, rots;
+    std::vector<uint8_t> cols[3];
+};
+static GenUses gen_uses(const h2hip_graph& g, const Program& P) {
+    GenUses u;
+    u.consts.assign(g.n_constants, 0);
+    u.rots.assign(g.n_rotations, 0);
     auto note = [&](const h2hip_value_source& v) {
-        if (v.kind == H2HIP_VS_CONSTANT) use_const[v.a] = 1;
+        if (v.kind == H2HIP_VS_CONSTANT) u.consts[v.a] = 1;
         if (v.kind == H2HIP_VS_FIXED || v.kind == H2HIP_VS_ADVICE || v.kind == H2HIP_VS_INSTANCE) {
-            std::vector<uint8_t>& u = use_col[v.kind - H2HIP_VS_FIXED];
-            if (u.size() <= v.a) u.resize((size_t)v.a + 1, 0);
-            u[v.a] = 1;
-            use_rot[v.b] = 1;
+            std::vector<uint8_t>& c = u.cols[v.kind - H2HIP_VS_FIXED];
+            if (c.size() <= v.a) c.resize((size_t)v.a + 1, 0);
+            c[v.a] = 1;
+            u.rots[v.b] = 1;
         }
     };
     for (const DevOp& o : P.ops) {
@@ -739,52 +812,21 @@ static std::string gen_source(const h2hip_graph& g, const Program& P, bool looku
         note(o.y);
     }
     note(P.result);
-    static const char* const tab_name[3] = {"fixed", "advice", "instance"};
-    static const char col_name[3] = {'F', 'A', 'N'};
-    auto operand = [&](const h2hip_value_source& v) -> std::string {
-        char t[96];
-        switch (v.kind) {
-            case H2HIP_VS_CONSTANT: snprintf(t, sizeof(t), "K%u", v.a); break;
-            case H2HIP_VS_INTERMEDIATE: snprintf(t, sizeof(t), "s%u", v.a); break;
-            case H2HIP_VS_FIXED: case H2HIP_VS_ADVICE: case H2HIP_VS_INSTANCE:
-                snprintf(t, sizeof(t), "ld_i(%c%u[r%u])", col_name[v.kind - H2HIP_VS_FIXED], v.a, v.b);
-                break;
-            case H2HIP_VS_CHALLENGE: snprintf(t, sizeof(t), "ld_const_fu(c.challenges, %u)", v.a); break;
-            case H2HIP_VS_BETA: return "c.beta";
-            case H2HIP_VS_GAMMA: return "c.gamma";
-            case H2HIP_VS_THETA: return "c.theta";
-            case H2HIP_VS_Y: return "c.y";
-            case H2HIP_VS_PREVIOUS: return "prev";
-            default: return "fu_zero()";
+    return u;
+}
+static void gen_constants(std::string& src, const GenNames& nm, const GenUses& u) {
+    for (uint32_t i = 0; i < nm.g->n_constants; i++)
+        if (u.consts[i]) {
+            const Fu k = to_i(fe_from_u64x4(nm.g->constants + 4 * (size_t)i));
+            gen_add(src, "    const Fu %s = {{%d, %d, %d, %d, %d, %d, %d, %d, %d}};\n", gen_operand(nm, {H2HIP_VS_CONSTANT, i, 0}).c_str(), k.l[0], k.l[1],
+                    k.l[2], k.l[3], k.l[4], k.l[5], k.l[6], k.l[7], k.l[8]);
         }
-        return t;
-    };
-    src += "#include \"evalh_dev.h\"\nusing namespace h2;\n";
-    src += lookup ? "extern \"C\" __global__ void __launch_bounds__(256) evalh_lookup_gen(ColsDev c, LookupDev l, Fe* values) {\n"
-                  : "extern \"C\" __global__ void __launch_bounds__(256) evalh_gates_gen(ColsDev c, Fe* __restrict__ values) {\n";
-    src += "    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;\n"
-           "    if (idx >= (1u << c.log_size)) return;\n";
-    src += lookup ? "    const Fu prev = fu_zero();\n"
-                  : "    const Fe prev_e = values[idx];\n"
-                    "    const Fu prev = ld_i(prev_e);\n";
-    src += "    (void)prev;\n";
-    for (uint32_t i = 0; i < g.n_constants; i++)
-        if (use_const[i]) {
-            const Fu k = to_i(fe_from_u64x4(g.constants + 4 * (size_t)i));
-            add("    const Fu K%u = {{%d, %d, %d, %d, %d, %d, %d, %d, %d}};\n", i, k.l[0], k.l[1], k.l[2], k.l[3], k.l[4], k.l[5], k.l[6], k.l[7], k.l[8]);
-        }
-    for (int t = 0; t < 3; t++)
-        for (uint32_t i = 0; i < use_col[t].size(); i++)
-            if (use_col[t][i]) add("    const Fe* __restrict__ %c%u = ld_const_col(c.%s, %u);\n", col_name[t], i, tab_name[t], i);
-    for (uint32_t i = 0; i < g.n_rotations; i++)
-        if (use_rot[i]) add("    const uint32_t r%u = rot_idx(idx, %d, c.rot_scale, c.log_size);\n", i, g.rotations[i]);
-    if (P.n_slots) {
-        src += "    Fu s0";
-        for (uint32_t i = 1; i < P.n_slots; i++) add(", s%u", i);
-        src += ";\n";
-    }
+}
+// the statements of one program: one per operation, a fused product inside its reader (fusion_plan), one scheduling region each
+static void gen_ops(std::string& src, const GenNames& nm, const Program& P) {
     const size_t n_ops = P.ops.size();
     const std::vector<int> fused_into = fusion_plan(P, tune().evalh_gen_fuse);  // product i is emitted inside op fused_into[i]
+    auto operand = [&](const h2hip_value_source& v) { return gen_operand(nm, v); };
     auto product_of = [&](size_t j, const h2hip_value_source& v) -> const DevOp* {  // the product fused into op j that v names
         for (size_t i = 0; i < j; i++)
             if (fused_into[i] == (int)j && v.kind == H2HIP_VS_INTERMEDIATE && P.ops[i].dst == v.a) return &P.ops[i];
@@ -798,41 +840,127 @@ static std::string gen_source(const h2hip_graph& g, const Program& P, bool looku
         const DevOp *px = product_of(q, o.x), *py = product_of(q, o.y);
         const uint32_t kind = o.op & 0xff;
         if ((kind == OP_ADD || kind == OP_SUB) && px && py) {
-            add("    s%u = fu_mul_sub<UF>(%s, %s, ", dst, operand(px->x).c_str(), operand(px->y).c_str());
-            add(kind == OP_SUB ? "%s, %s);\n" : "fu_neg(%s), %s);\n", operand(py->x).c_str(), operand(py->y).c_str());
+            gen_add(src, "    s%u = fu_mul_sub<UF>(%s, %s, ", dst, operand(px->x).c_str(), operand(px->y).c_str());
+            gen_add(src, kind == OP_SUB ? "%s, %s);\n" : "fu_neg(%s), %s);\n", operand(py->x).c_str(), operand(py->y).c_str());
         } else if (kind == OP_FMA && px) {
-            add("    s%u = fu_mul_sub<UF>(s%u, %s, fu_neg(%s), %s);\n", dst, dst, y.c_str(), operand(px->x).c_str(), operand(px->y).c_str());
+            gen_add(src, "    s%u = fu_mul_sub<UF>(s%u, %s, fu_neg(%s), %s);\n", dst, dst, y.c_str(), operand(px->x).c_str(), operand(px->y).c_str());
         } else
         switch (kind) {
-            case OP_ADD: add("    s%u = addn(%s, %s);\n", dst, x.c_str(), y.c_str()); break;
-            case OP_SUB: add("    s%u = subn(%s, %s);\n", dst, x.c_str(), y.c_str()); break;
-            case OP_MUL: add("    s%u = mul_i(%s, %s);\n", dst, x.c_str(), y.c_str()); break;
-            case OP_SQR: add("    s%u = fu_sqr<UF>(%s);\n", dst, x.c_str()); break;
-            case OP_DBL: add("    s%u = fu_norm(fu_dbl(%s));\n", dst, x.c_str()); break;
-            case OP_NEG: add("    s%u = fu_norm(fu_neg(%s));\n", dst, x.c_str()); break;
-            case OP_FMA: add("    s%u = addn(mul_i(s%u, %s), %s);\n", dst, dst, y.c_str(), x.c_str()); break;
-            default: add("    s%u = %s;\n", dst, x.c_str());  // OP_MOV
+            case OP_ADD: gen_add(src, "    s%u = addn(%s, %s);\n", dst, x.c_str(), y.c_str()); break;
+            case OP_SUB: gen_add(src, "    s%u = subn(%s, %s);\n", dst, x.c_str(), y.c_str()); break;
+            case OP_MUL: gen_add(src, "    s%u = mul_i(%s, %s);\n", dst, x.c_str(), y.c_str()); break;
+            case OP_SQR: gen_add(src, "    s%u = fu_sqr<UF>(%s);\n", dst, x.c_str()); break;
+            case OP_DBL: gen_add(src, "    s%u = fu_norm(fu_dbl(%s));\n", dst, x.c_str()); break;
+            case OP_NEG: gen_add(src, "    s%u = fu_norm(fu_neg(%s));\n", dst, x.c_str()); break;
+            case OP_FMA: gen_add(src, "    s%u = addn(mul_i(s%u, %s), %s);\n", dst, dst, y.c_str(), x.c_str()); break;
+            default: gen_add(src, "    s%u = %s;\n", dst, x.c_str());  // OP_MOV
         }
-        if (o.op & OP_REDUCE_FLAG) add("    s%u = mul_i(s%u, fu_one_i<UF>());\n", dst, dst);
+        if (o.op & OP_REDUCE_FLAG) gen_add(src, "    s%u = mul_i(s%u, fu_one_i<UF>());\n", dst, dst);
         // one scheduling region per operation: the whole program as ONE basic block (tens of thousands of instructions) costs the
         // scheduler and the register allocator minutes and buys nothing -- a field multiplication already fills the pipeline
-        if (sched_barriers) src += "    __builtin_amdgcn_sched_barrier(0);\n";
+        if (EVALH_GEN_BARRIERS) src += "    __builtin_amdgcn_sched_barrier(0);\n";
     }
+}
+static void gen_slots(std::string& src, uint32_t n_slots) {
+    if (!n_slots) return;
+    src += "    Fu s0";
+    for (uint32_t i = 1; i < n_slots; i++) gen_add(src, ", s%u", i);
+    src += ";\n";
+}
+
+// a gates or a lookup kernel: one program
+static std::string gen_source(const h2hip_graph& g, const Program& P, bool lookup = false) {
+    std::string src;
+    src.reserve(64 * P.ops.size() + 4096);
+    const GenNames nm = {&g, -1};
+    const GenUses u = gen_uses(g, P);
+    src += "#include \"evalh_dev.h\"\nusing namespace h2;\n";
+    src += lookup ? "extern \"C\" __global__ void __launch_bounds__(256) evalh_lookup_gen(ColsDev c, LookupDev l, Fe* values) {\n"
+                  : "extern \"C\" __global__ void __launch_bounds__(256) evalh_gates_gen(ColsDev c, Fe* __restrict__ values) {\n";
+    src += "    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;\n"
+           "    if (idx >= (1u << c.log_size)) return;\n";
+    src += lookup ? "    const Fu prev = fu_zero();\n"
+                  : "    const Fe prev_e = values[idx];\n"
+                    "    const Fu prev = ld_i(prev_e);\n";
+    src += "    (void)prev;\n";
+    gen_constants(src, nm, u);
+    for (int t = 0; t < 3; t++)
+        for (uint32_t i = 0; i < u.cols[t].size(); i++)
+            if (u.cols[t][i]) gen_add(src, "    const Fe* __restrict__ %c%u = ld_const_col(c.%s, %u);\n", gen_col_name[t], i, gen_tab_name[t], i);
+    for (uint32_t i = 0; i < g.n_rotations; i++)
+        if (u.rots[i]) gen_add(src, "    const uint32_t r%u = rot_idx(idx, %d, c.rot_scale, c.log_size);\n", i, g.rotations[i]);
+    gen_slots(src, P.n_slots);
+    gen_ops(src, nm, P);
     if (lookup) {
-        add("    lookup_row(l, c, idx, %s, values);\n}\n", operand(P.result).c_str());
+        gen_add(src, "    lookup_row(l, c, idx, %s, values);\n}\n", gen_operand(nm, P.result).c_str());
         return src;
     }
     switch (P.result.kind) {  // prog_result_e
         case H2HIP_VS_FIXED: case H2HIP_VS_ADVICE: case H2HIP_VS_INSTANCE:
-            add("    values[idx] = %c%u[r%u];\n", col_name[P.result.kind - H2HIP_VS_FIXED], P.result.a, P.result.b);
+            gen_add(src, "    values[idx] = %c%u[r%u];\n", gen_col_name[P.result.kind - H2HIP_VS_FIXED], P.result.a, P.result.b);
             break;
         case H2HIP_VS_PREVIOUS: src += "    (void)prev_e;\n"; break;
         case EVALH_VS_ZERO: src += "    values[idx] = fe_zero<FrP>();\n"; break;
-        default: add("    values[idx] = out_e(%s);\n", operand(P.result).c_str());
+        default: gen_add(src, "    values[idx] = out_e(%s);\n", gen_operand(nm, P.result).c_str());
     }
     src += "}\n";
     return src;
 }
+
+// A stage kernel: the programs of one shuffle or one mv-lookup argument in ONE straight-line kernel that ends with the stage's row
+// function.  A column pointer is loaded once per distinct (kind, index) and a rotated row index formed once per distinct rotation value
+// across all the programs -- the tuples of an argument typically share selectors and columns, which the interpreter loads once per
+// program; the slot locals are one set, reused from one program to the next, and what crosses from one program to the next is held in
+// locals of its own (a; P and Q).  Magnitudes entering the row functions: each program's result is what the interpreter's is -- a slot
+// [< 15] (compile_graph's closing reduction is an operation of the program like any other; a fused pair's bound is below the separate
+// ones', see fusion_plan), a column [< 32], a constant, challenge, theta, beta or gamma [<= 1], an empty graph [0] -- so a, s, f_c and
+// tau are [< 32], P [<= 1.3] and Q [<= 2.9] as shuffle_row and mvlookup_row assume (evalh_dev.h).
+static std::string gen_stage_source(const GenUnit& u) {
+    std::string src;
+    src.reserve(64 * u.n_ops() + 4096);
+    const size_t n = u.progs.size();
+    src += "#include \"evalh_dev.h\"\nusing namespace h2;\n";
+    src += u.kind == GEN_SHUFFLE ? "extern \"C\" __global__ void __launch_bounds__(256) evalh_shuffle_gen(ColsDev c, ShuffleDev sh, Fe* values) {\n"
+                                 : "extern \"C\" __global__ void __launch_bounds__(256) evalh_mvlookup_gen(ColsDev c, MvLookupDev mv, Fe* values) {\n";
+    src += "    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;\n"
+           "    if (idx >= (1u << c.log_size)) return;\n";
+    std::vector<GenUses> uses(n);
+    std::vector<uint8_t> cols[3];
+    std::vector<int32_t> rots;  // distinct rotation values, in order of first use
+    for (size_t p = 0; p < n; p++) {
+        uses[p] = gen_uses(*u.graphs[p], *u.progs[p]);
+        gen_constants(src, {u.graphs[p], (int)p}, uses[p]);
+        for (int t = 0; t < 3; t++) {
+            if (cols[t].size() < uses[p].cols[t].size()) cols[t].resize(uses[p].cols[t].size(), 0);
+            for (size_t i = 0; i < uses[p].cols[t].size(); i++) cols[t][i] |= uses[p].cols[t][i];
+        }
+        for (uint32_t i = 0; i < u.graphs[p]->n_rotations; i++)
+            if (uses[p].rots[i] && std::find(rots.begin(), rots.end(), u.graphs[p]->rotations[i]) == rots.end()) rots.push_back(u.graphs[p]->rotations[i]);
+    }
+    for (int t = 0; t < 3; t++)
+        for (uint32_t i = 0; i < cols[t].size(); i++)
+            if (cols[t][i]) gen_add(src, "    const Fe* __restrict__ %c%u = ld_const_col(c.%s, %u);\n", gen_col_name[t], i, gen_tab_name[t], i);
+    for (int32_t v : rots) gen_add(src, "    const uint32_t %s = rot_idx(idx, %d, c.rot_scale, c.log_size);\n", gen_rot_value_name(v).c_str(), v);
+    gen_slots(src, u.n_slots());
+    if (u.kind == GEN_MVLOOKUP) src += "    Fu P = fu_one_i<UF>(), Q = fu_zero();\n";
+    for (size_t p = 0; p < n; p++) {
+        const GenNames nm = {u.graphs[p], (int)p};
+        gen_ops(src, nm, *u.progs[p]);
+        const std::string r = gen_operand(nm, u.progs[p]->result);
+        if (u.kind == GEN_SHUFFLE) {
+            if (p == 0) gen_add(src, "    const Fu a = %s;\n", r.c_str());
+            else gen_add(src, "    shuffle_row(sh, c, idx, a, %s, values);\n", r.c_str());
+        } else if (p + 1 < n) {  // input tuple p: Q = Q f + P; P = P f
+            gen_add(src, "    {\n        const Fu f = %s;\n        Q = addn(mul_i(Q, f), P);\n        P = mul_i(P, f);\n    }\n", r.c_str());
+            if (EVALH_GEN_BARRIERS) src += "    __builtin_amdgcn_sched_barrier(0);\n";
+        } else {
+            gen_add(src, "    mvlookup_row(mv, c, idx, %s, P, Q, values);\n", r.c_str());
+        }
+    }
+    src += "}\n";
+    return src;
+}
+static std::string gen_unit_source(const GenUnit& u) { return u.stage() ? gen_stage_source(u) : gen_source(*u.graphs[0], *u.progs[0], u.kind == GEN_LOOKUP); }
 
 static uint64_t fnv1a64_raw(const char* p, size_t n, uint64_t h) {
     for (size_t i = 0; i < n; i++) {
@@ -865,6 +993,10 @@ struct RtcEntry {
     }
 };
 static std::map<uint64_t, std::shared_ptr<RtcEntry>> g_rtc;
+// Background compilations (mode 1) that may be queued or running when a stage kernel asks for one more.  At the bound the call skips its
+// request -- nothing is recorded, a later call asks again -- and the interpreter serves: a process that meets many distinct arguments once
+// each (a test suite does) then leaves seconds of queued compiles behind it, not minutes.  Gates and lookup kernels are always queued.
+static constexpr uint64_t EVALH_RTC_MAX_PENDING = 8;
 
 static std::string rtc_cache_path(uint64_t key) {
     const char* dir = getenv("HALO2_HIP_CACHE_DIR");
@@ -894,8 +1026,9 @@ static void rtc_compile(std::shared_ptr<RtcEntry> e, std::string src, uint64_t k
         }
     }
     if (!ok) {
-        // one compilation at a time: a circuit brings a gates kernel and one kernel per lookup, each on its own background thread, and
-        // nothing here relies on the run-time compiler being re-entrant
+        // one compilation at a time: a circuit brings a gates kernel and one kernel per lookup, shuffle and mv-lookup argument, each on its
+        // own background thread, and nothing here relies on the run-time compiler being re-entrant.  So queued compilations wait in
+        // line, at ~20 ms per operation, and a process joins them when it ends: EVALH_RTC_MAX_PENDING bounds the line for stage kernels.
         static std::mutex compile_mu;
         std::lock_guard<std::mutex> one(compile_mu);
         hiprtcProgram prog = nullptr;
@@ -937,25 +1070,7 @@ static void rtc_compile(std::shared_ptr<RtcEntry> e, std::string src, uint64_t k
     }
 }
 
-// test / tooling hook, no GPU needed: the source a graph's program is emitted as, and (compile != 0) what hiprtc makes of it
-extern "C" int h2hip_debug_evalh_codegen_source(const h2hip_graph* g, char* buf, size_t cap, size_t* len, int compile, double* seconds,
-                                                size_t* code_bytes) {
-    if (!g || !len) {
-        set_error("evaluate_h: null argument");
-        return 1;
-    }
-    Program P;
-    TuneRead r;
-    if (compile_any(g, &P)) return 1;
-    const std::string src = gen_source(*g, P, (compile & 2) != 0);  // bit 1: the graph as a lookup's table expression (evalh_lookup_gen)
-    compile &= 1;
-    *len = src.size();
-    if (buf && cap) {
-        const size_t m = src.size() < cap - 1 ? src.size() : cap - 1;
-        memcpy(buf, src.data(), m);
-        buf[m] = 0;
-    }
-    if (!compile) return 0;
+static int rtc_compile_for_hook(const std::string& src, double* seconds, size_t* code_bytes) {
     {
         std::lock_guard<std::mutex> lk(g_rtc_mu);
         if (!hiprtc_load()) {
@@ -973,6 +1088,72 @@ extern "C" int h2hip_debug_evalh_codegen_source(const h2hip_graph* g, char* buf,
     }
     return 0;
 }
+static void copy_source(const std::string& src, char* buf, size_t cap, size_t* len) {
+    *len = src.size();
+    if (buf && cap) {
+        const size_t m = src.size() < cap - 1 ? src.size() : cap - 1;
+        memcpy(buf, src.data(), m);
+        buf[m] = 0;
+    }
+}
+
+// test / tooling hook, no GPU needed: the source a graph's program is emitted as, and (compile != 0) what hiprtc makes of it
+extern "C" int h2hip_debug_evalh_codegen_source(const h2hip_graph* g, char* buf, size_t cap, size_t* len, int compile, double* seconds,
+                                                size_t* code_bytes) {
+    if (!g || !len) {
+        set_error("evaluate_h: null argument");
+        return 1;
+    }
+    Program P;
+    TuneRead r;
+    if (compile_any(g, &P)) return 1;
+    const std::string src = gen_source(*g, P, (compile & 2) != 0);  // bit 1: the graph as a lookup's table expression (evalh_lookup_gen)
+    copy_source(src, buf, cap, len);
+    if (!(compile & 1)) return 0;
+    return rtc_compile_for_hook(src, seconds, code_bytes);
+}
+
+static bool shuffle_vs_allowed(const h2hip_value_source& v);
+static bool mvlookup_vs_allowed(const h2hip_value_source& v);
+// ... and the source of a stage kernel: kind 1 = a shuffle's two graphs (input side, shuffle side), kind 2 = an mv-lookup argument's
+// K + 1 graphs (the K input tuples', then the table's).  3: beyond the generator's limits -- the engine keeps the interpreter
+extern "C" int h2hip_debug_evalh_codegen_stage_source(const h2hip_graph* graphs, uint32_t n_graphs, int kind, char* buf, size_t cap, size_t* len,
+                                                      int compile, double* seconds, size_t* code_bytes) {
+    if (!graphs || !len || (kind != 1 && kind != 2) || (kind == 1 && n_graphs != 2) || (kind == 2 && (n_graphs < 2 || n_graphs > 256))) {
+        set_error("evaluate_h: stage source: null argument, or a kind / number of graphs that is no shuffle (1: two graphs) or mv-lookup (2: K + 1)");
+        return 1;
+    }
+    TuneRead r;
+    std::vector<Program> progs(n_graphs);
+    std::vector<const h2hip_graph*> gp(n_graphs);
+    for (uint32_t i = 0; i < n_graphs; i++) {
+        const h2hip_graph& g = graphs[i];
+        if (compile_any(&g, &progs[i])) return 1;
+        gp[i] = &g;
+        auto allowed = [&](const h2hip_value_source& v) { return kind == 1 ? shuffle_vs_allowed(v) : mvlookup_vs_allowed(v); };
+        for (uint32_t q = 0; q < g.n_calculations; q++) {  // as evaluate_h_shuffles_validate / evaluate_h_mvlookups_validate
+            const h2hip_calculation& cl = g.calculations[q];
+            bool ok = allowed(cl.x);
+            if (cl.op == H2HIP_CALC_ADD || cl.op == H2HIP_CALC_SUB || cl.op == H2HIP_CALC_MUL || cl.op == H2HIP_CALC_HORNER) ok = ok && allowed(cl.y);
+            if (cl.op == H2HIP_CALC_HORNER)
+                for (uint32_t t = 0; ok && t < cl.parts_count; t++) ok = allowed(g.parts[cl.parts_offset + t]);
+            if (!ok) {
+                set_error("evaluate_h: %s graph %u, calculation %u reads a value the stage does not supply", kind == 1 ? "shuffle" : "mv-lookup", i, q);
+                return 1;
+            }
+        }
+    }
+    const GenUnit u = gen_unit(kind == 1 ? GEN_SHUFFLE : GEN_MVLOOKUP, gp.data(), progs.data(), n_graphs);
+    if (!gen_within_limits(u)) {
+        *len = 0;
+        set_error("evaluate_h: stage kernel beyond the generator's limits (%zu operations, %u live values)", u.n_ops(), u.n_live());
+        return 3;
+    }
+    const std::string src = gen_stage_source(u);
+    copy_source(src, buf, cap, len);
+    if (!(compile & 1)) return 0;
+    return rtc_compile_for_hook(src, seconds, code_bytes);
+}
 
 // join the compile threads (h2hip_shutdown, after the contexts are released); the compiled code stays cached for a later init
 void evalh_rtc_shutdown() {
@@ -987,71 +1168,116 @@ void evalh_modules_free(Ctx* c) {
     c->evalh_mods.clear();
 }
 
-// the generated kernel for this program on this device, or nullptr: not wanted, not compiled yet (the interpreter serves this
-// call), or not compilable (it serves every call)
-// what gen_source reads of a program, hashed: every call of evaluate_h comes here, and writing (and hashing) 20 KB of source each time to
-// find a kernel that is already loaded is ~150 us of host time per call
-static uint64_t program_fingerprint(const h2hip_graph& g, const Program& P, bool lookup) {
+// what the generator reads of a kernel's programs, hashed: every call of evaluate_h comes here, and writing (and hashing) 20 KB of source
+// each time to find a kernel that is already loaded is ~150 us of host time per call.  The kind and every program of the kernel.
+static uint64_t unit_fingerprint(const GenUnit& u) {
     uint64_t h = 0xcbf29ce484222325ull;
-    if (!P.ops.empty()) h = fnv1a64_raw((const char*)P.ops.data(), P.ops.size() * sizeof(DevOp), h);
-    if (g.n_constants) h = fnv1a64_raw((const char*)g.constants, (size_t)g.n_constants * 32, h);
-    if (g.n_rotations) h = fnv1a64_raw((const char*)g.rotations, (size_t)g.n_rotations * sizeof(int32_t), h);
-    const uint32_t tail[6] = {P.result.kind, P.result.a, P.result.b, P.n_slots, lookup ? 1u : 0u, (tune().evalh_gen_fuse ? 1u : 0u) | (EVALH_GEN_BARRIERS ? 2u : 0u)};
+    for (size_t p = 0; p < u.progs.size(); p++) {
+        const h2hip_graph& g = *u.graphs[p];
+        const Program& P = *u.progs[p];
+        if (!P.ops.empty()) h = fnv1a64_raw((const char*)P.ops.data(), P.ops.size() * sizeof(DevOp), h);
+        if (g.n_constants) h = fnv1a64_raw((const char*)g.constants, (size_t)g.n_constants * 32, h);
+        if (g.n_rotations) h = fnv1a64_raw((const char*)g.rotations, (size_t)g.n_rotations * sizeof(int32_t), h);
+        const uint32_t tail[7] = {P.result.kind, P.result.a, P.result.b, P.n_slots, (uint32_t)P.ops.size(), g.n_constants, g.n_rotations};
+        h = fnv1a64_raw((const char*)tail, sizeof(tail), h);
+    }
+    const uint32_t tail[3] = {(uint32_t)u.kind, (uint32_t)u.progs.size(), (tune().evalh_gen_fuse ? 1u : 0u) | (EVALH_GEN_BARRIERS ? 2u : 0u)};
     return fnv1a64_raw((const char*)tail, sizeof(tail), h);
 }
-static std::map<uint64_t, uint64_t> g_rtc_key_of;  // program fingerprint -> source key (under g_rtc_mu)
+// fingerprint -> the kernel's source key and how far it has come (under g_rtc_mu).  A kernel that failed, or is still compiling, costs a
+// call this lookup, not a gen_source and a hash of its source.
+struct RtcKnown {
+    uint64_t key;
+    int state;  // RtcEntry's: 0 compiling, 1 ready, 2 failed
+};
+static std::map<uint64_t, RtcKnown> g_rtc_known;
 
-static hipFunction_t gates_kernel_for(Ctx* c, const h2hip_graph& g, const Program& P, bool lookup = false) {
-    if (tune().evalh_codegen <= 0 || (P.ops.empty() && !lookup) || P.ops.size() > tune().evalh_codegen_max_ops || P.n_slots > EVALH_CODEGEN_MAX_SLOTS) return nullptr;
-    const uint64_t fp = program_fingerprint(g, P, lookup);
+static void rtc_compile_background(std::shared_ptr<RtcEntry> e, std::string src, uint64_t key) {
+    rtc_compile(e, std::move(src), key);
+    g_rtc_stats.pending--;
+}
+
+// the generated kernel for these programs on this device, or nullptr: not wanted, not compiled yet (the interpreter serves this call), or
+// not compilable (it serves every call)
+static hipFunction_t kernel_for(Ctx* c, const GenUnit& u) {
+    const int mode = tune().evalh_codegen;
+    if (mode <= 0 || !gen_within_limits(u)) return nullptr;
+    if ((u.kind == GEN_SHUFFLE && !tune().evalh_gen_shuffle) || (u.kind == GEN_MVLOOKUP && !tune().evalh_gen_mvlookup)) return nullptr;
+    const uint64_t fp = unit_fingerprint(u);
+    std::shared_ptr<RtcEntry> e;
+    uint64_t key = 0;
     {
         std::lock_guard<std::mutex> lk(g_rtc_mu);
-        auto known = g_rtc_key_of.find(fp);
-        if (known != g_rtc_key_of.end()) {
-            auto hit = c->evalh_mods.find(known->second);
+        auto known = g_rtc_known.find(fp);
+        if (known != g_rtc_known.end()) {
+            if (known->second.state == 2) return nullptr;
+            key = known->second.key;
+            auto hit = c->evalh_mods.find(key);
             if (hit != c->evalh_mods.end()) return (hipFunction_t)hit->second.second;
+            e = g_rtc[key];
+            if (known->second.state == 0) {
+                if (mode >= 2 && e->th.joinable()) e->th.join();  // tests: wait for a compile another call started
+                std::lock_guard<std::mutex> le(e->m);
+                known->second.state = e->state;
+                if (e->state != 1) return nullptr;
+            }
+        } else if (u.stage() && mode == 1 && g_rtc_stats.pending >= EVALH_RTC_MAX_PENDING) {
+            return nullptr;  // the line of background compilations is full: ask again on a later call
         }
     }
-    std::string src = gen_source(g, P, lookup);
-    const uint64_t key = fnv1a64(src);
-    {
-        std::lock_guard<std::mutex> lk(g_rtc_mu);
-        g_rtc_key_of[fp] = key;
-    }
-    auto hit = c->evalh_mods.find(key);
-    if (hit != c->evalh_mods.end()) return (hipFunction_t)hit->second.second;
-    std::shared_ptr<RtcEntry> e;
-    bool mine = false;  // this call created the entry and compiles it inline
-    {
-        std::lock_guard<std::mutex> lk(g_rtc_mu);
-        auto it = g_rtc.find(key);
-        if (it != g_rtc.end()) {
-            e = it->second;
-            if (tune().evalh_codegen >= 2 && e->th.joinable()) e->th.join();  // tests: wait for a compile another call started
-        } else {
-            if (!hiprtc_load()) return nullptr;
-            try {
-                e = std::make_shared<RtcEntry>();
-                g_rtc[key] = e;
-            } catch (...) {
-                return nullptr;
-            }
-            mine = true;
-            if (tune().evalh_codegen == 1) {
+    if (!e) {
+        std::string src = gen_unit_source(u);
+        key = fnv1a64(src);
+        auto hit = c->evalh_mods.find(key);
+        if (hit != c->evalh_mods.end()) {  // the source of another fingerprint, already on this device (the fusion switch left it unchanged)
+            std::lock_guard<std::mutex> lk(g_rtc_mu);
+            g_rtc_known[fp] = {key, hit->second.second ? 1 : 2};
+            return (hipFunction_t)hit->second.second;
+        }
+        bool mine = false;  // this call created the entry and compiles it inline
+        {
+            std::lock_guard<std::mutex> lk(g_rtc_mu);
+            auto it = g_rtc.find(key);
+            if (it != g_rtc.end()) {
+                e = it->second;
+                if (mode >= 2 && e->th.joinable()) e->th.join();
+            } else {
+                if (!hiprtc_load()) return nullptr;
                 try {
-                    e->th = std::thread(rtc_compile, e, src, key);
-                    mine = false;
-                } catch (...) {  // no thread to be had: compile inline
+                    e = std::make_shared<RtcEntry>();
+                    g_rtc[key] = e;
+                } catch (...) {
+                    return nullptr;
+                }
+                mine = true;
+                if (mode == 1) {
+                    g_rtc_stats.pending++;
+                    try {
+                        e->th = std::thread(rtc_compile_background, e, src, key);
+                        mine = false;
+                    } catch (...) {  // no thread to be had: compile inline
+                        g_rtc_stats.pending--;
+                    }
                 }
             }
+            g_rtc_known[fp] = {key, 0};
         }
+        if (mine) rtc_compile(e, src, key);
+        int state;
+        {
+            std::lock_guard<std::mutex> le(e->m);
+            state = e->state;
+        }
+        if (state != 0) {
+            std::lock_guard<std::mutex> lk(g_rtc_mu);
+            g_rtc_known[fp].state = state;
+        }
+        if (state != 1) return nullptr;
     }
-    if (mine) rtc_compile(e, src, key);
     std::lock_guard<std::mutex> lk(e->m);
-    if (e->state != 1) return nullptr;
     hipModule_t mod = nullptr;
     hipFunction_t fn = nullptr;
-    if (hipModuleLoadData(&mod, e->code.data()) != hipSuccess || hipModuleGetFunction(&fn, mod, lookup ? "evalh_lookup_gen" : "evalh_gates_gen") != hipSuccess) {
+    if (hipModuleLoadData(&mod, e->code.data()) != hipSuccess || hipModuleGetFunction(&fn, mod, GEN_KERNEL_NAME[u.kind]) != hipSuccess) {
         (void)hipGetLastError();
         if (mod) (void)hipModuleUnload(mod);
         c->evalh_mods[key] = {nullptr, nullptr};  // do not try again on this device
@@ -1060,6 +1286,8 @@ static hipFunction_t gates_kernel_for(Ctx* c, const h2hip_graph& g, const Progra
     c->evalh_mods[key] = {(void*)mod, (void*)fn};
     return fn;
 }
+// programs first .. first + n of a call's plan as one kernel
+static hipFunction_t kernel_for(Ctx* c, GenKind kind, const struct CallPlan& cp, size_t first, size_t n);
 
 struct Arena {
     char* base = nullptr;
@@ -1442,23 +1670,30 @@ static void with_tier(int tier, F f) {
     }
 }
 
+static hipFunction_t kernel_for(Ctx* c, GenKind kind, const CallPlan& cp, size_t first, size_t n) {
+    return kernel_for(c, gen_unit(kind, cp.graphs.data() + first, cp.progs.data() + first, n));
+}
+// a generated kernel takes one lane per row: (columns, [the stage's descriptor,] values)
+static int launch_generated(hipFunction_t fn, GenKind kind, const ColsDev& cols, const void* stage, Fe* d_values, hipStream_t s) {
+    Fe* vals = d_values;
+    void* with_stage[] = {(void*)&cols, (void*)stage, (void*)&vals};
+    void* without[] = {(void*)&cols, (void*)&vals};
+    const size_t rows = (size_t)1 << cols.log_size;
+    H2_CHECK(hipModuleLaunchKernel(fn, (uint32_t)((rows + 255) / 256), 1, 1, 256, 1, 1, 0, s, stage ? with_stage : without, nullptr));
+    g_rtc_stats.launched(kind, true);
+    return 0;
+}
+
 // One launch of the custom gates (the plan's first program) over `rows` rows of `values`: the kernel generated for this circuit once
 // it is compiled, the interpreter until then (and for programs beyond the generator's limits)
 static int enqueue_gates(Ctx* c, const CallPlan& cp, const ProgDev& gd, const ColsDev& cols, Fe* d_values, size_t rows, hipStream_t s) {
     const SlotPlan& plan = cp.plans[0];
-    hipFunction_t gen = plan.tier != 0 ? gates_kernel_for(c, *cp.graphs[0], cp.progs[0]) : nullptr;
-    if (gen) {
-        Fe* vals = d_values;
-        void* args[] = {(void*)&cols, (void*)&vals};
-        H2_CHECK(hipModuleLaunchKernel(gen, (uint32_t)((rows + 255) / 256), 1, 1, 256, 1, 1, 0, s, args, nullptr));
-        g_rtc_stats.launches++;
-    } else {
-        g_rtc_stats.interpreted++;
-        with_tier(plan.tier, [&](auto tier, size_t lds) {
-            hipLaunchKernelGGL(evalh_gates_kernel<decltype(tier)::value>, dim3(plan.lanes / 256), dim3(256), lds, s, gd, cols, d_values,
-                               (Fu*)c->evalh_slots.p, plan.lanes);
-        });
-    }
+    if (hipFunction_t gen = plan.tier != 0 ? kernel_for(c, GEN_GATES, cp, 0, 1) : nullptr) return launch_generated(gen, GEN_GATES, cols, nullptr, d_values, s);
+    g_rtc_stats.launched(GEN_GATES, false);
+    with_tier(plan.tier, [&](auto tier, size_t lds) {
+        hipLaunchKernelGGL(evalh_gates_kernel<decltype(tier)::value>, dim3(plan.lanes / 256), dim3(256), lds, s, gd, cols, d_values,
+                           (Fu*)c->evalh_slots.p, plan.lanes);
+    });
     H2_CHECK(hipGetLastError());
     return 0;
 }
@@ -1466,14 +1701,9 @@ static int enqueue_gates(Ctx* c, const CallPlan& cp, const ProgDev& gd, const Co
 // ... and of one lookup argument's constraints (program i of the plan)
 static int enqueue_lookup(Ctx* c, const CallPlan& cp, size_t i, const ProgDev& lg, const LookupDev& ld, const ColsDev& cols, Fe* d_values,
                           size_t rows, hipStream_t s) {
-    if (hipFunction_t lgen = gates_kernel_for(c, *cp.graphs[i], cp.progs[i], true)) {  // generated for this circuit, as the gates kernel is
-        Fe* vals = d_values;
-        void* args[] = {(void*)&cols, (void*)&ld, (void*)&vals};
-        H2_CHECK(hipModuleLaunchKernel(lgen, (uint32_t)((rows + 255) / 256), 1, 1, 256, 1, 1, 0, s, args, nullptr));
-        g_rtc_stats.launches++;
-        return 0;
-    }
-    g_rtc_stats.interpreted++;
+    if (hipFunction_t lgen = kernel_for(c, GEN_LOOKUP, cp, i, 1))  // generated for this circuit, as the gates kernel is
+        return launch_generated(lgen, GEN_LOOKUP, cols, &ld, d_values, s);
+    g_rtc_stats.launched(GEN_LOOKUP, false);
     const SlotPlan& lp = cp.plans[i];
     with_tier(lp.tier, [&](auto tier, size_t lds) {
         hipLaunchKernelGGL(evalh_lookup_kernel<decltype(tier)::value>, dim3(lp.lanes / 256), dim3(256), lds, s, lg, ld, cols, d_values,
@@ -1483,10 +1713,14 @@ static int enqueue_lookup(Ctx* c, const CallPlan& cp, size_t i, const ProgDev& l
     return 0;
 }
 
-// ... and of one shuffle argument's (programs i and i + 1 of the plan): always the interpreter, on the slot plan of the program with
-// more slots -- its tier holds the other's slots too, and its global workspace, if it needs one, is within the call's largest
+// ... and of one shuffle argument's (programs i and i + 1 of the plan): the kernel generated for the pair where the stage's kernels are
+// wanted (Tuning::evalh_gen_shuffle) and the pair is within the generator's limits; otherwise, and until that kernel is compiled, the
+// interpreter, on the slot plan of the program with more slots -- its tier holds the other's slots too, and its global workspace, if it
+// needs one, is within the call's largest
 static int enqueue_shuffle(Ctx* c, const CallPlan& cp, size_t i, const std::vector<ProgDev>& pds, const ShuffleDev& sd, const ColsDev& cols,
                            Fe* d_values, hipStream_t s) {
+    if (hipFunction_t gen = kernel_for(c, GEN_SHUFFLE, cp, i, 2)) return launch_generated(gen, GEN_SHUFFLE, cols, &sd, d_values, s);
+    g_rtc_stats.launched(GEN_SHUFFLE, false);
     const SlotPlan& sp = cp.plans[cp.progs[i].n_slots >= cp.progs[i + 1].n_slots ? i : i + 1];
     with_tier(sp.tier, [&](auto tier, size_t lds) {
         hipLaunchKernelGGL(evalh_shuffle_kernel<decltype(tier)::value>, dim3(sp.lanes / 256), dim3(256), lds, s, pds[i], pds[i + 1], sd, cols,
@@ -1496,10 +1730,13 @@ static int enqueue_shuffle(Ctx* c, const CallPlan& cp, size_t i, const std::vect
     return 0;
 }
 
-// ... and of one mv-lookup argument's (programs i .. i + n_inputs of the plan, d_progs their device table): always the interpreter, on
-// the slot plan of the program with the most slots among them
+// ... and of one mv-lookup argument's (programs i .. i + n_inputs of the plan, d_progs their device table): the kernel generated for
+// the K + 1 programs under the same conditions (Tuning::evalh_gen_mvlookup); otherwise the interpreter, on the slot plan of the program
+// with the most slots among them
 static int enqueue_mvlookup(Ctx* c, const CallPlan& cp, size_t i, uint32_t n_inputs, const ProgDev* d_progs, const MvLookupDev& md,
                             const ColsDev& cols, Fe* d_values, hipStream_t s) {
+    if (hipFunction_t gen = kernel_for(c, GEN_MVLOOKUP, cp, i, (size_t)n_inputs + 1)) return launch_generated(gen, GEN_MVLOOKUP, cols, &md, d_values, s);
+    g_rtc_stats.launched(GEN_MVLOOKUP, false);
     size_t big = i;
     for (size_t t = i; t <= i + n_inputs; t++)
         if (cp.progs[t].n_slots > cp.progs[big].n_slots) big = t;

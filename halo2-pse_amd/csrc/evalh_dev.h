@@ -1,5 +1,5 @@
 // evalh_dev.h -- what the evaluate_h kernels share with the per-circuit gates kernel that evalh.hip generates and compiles at
-// run time (hiprtc): the columns descriptor, the scalar-load helpers and the I-form field helpers.  Device only.  This file, field.h,
+// run time (hiprtc): the columns descriptor, the scalar-load helpers and the I-form field helpers, and the row functions of the lookup, shuffle and mv-lookup stages.  Device only.  This file, field.h,
 // fieldu.h and fieldu_chain.inc are embedded in the library as text (csrc/rtc_headers.inc, made by tools/embed_headers.py) and
 // handed to hiprtc as in-memory headers, so the generated kernel is built from the very arithmetic the rest of the engine runs.
 #pragma once
@@ -82,6 +82,55 @@ __device__ __forceinline__ void lookup_row(const LookupDev& l, const ColsDev& c,
     // (1 - (l_last + l_blind)) * (a' - s') * (a'(X) - a'(w^-1 X)) = 0
     v = fold_y(v, c.y, mul_i(a_minus_s, subn(a_, ld_i(l.pin[r_prev]))), l_active);                  // [1.1] + [(64 * 64 / 169 + 1 = 25.3) * 32 / 169 + 1 = 5.8] = [6.9]
     values[idx] = out_e(v);
+}
+
+// One shuffle argument's share of a row (the shuffle argument of upstream PSE halo2: include/halo2hip.h, h2hip_evalh_shuffles), given the
+// two sides' values of that row, a = A + gamma and s = S + gamma: shared by the interpreter's shuffle kernel and the one generated per
+// argument.  a, s: a program's result, [< 15] a slot (compile_graph brings a slot holding the result below EVALH_MAG_RESULT; the generator's
+// fused form of it is bounded by less, see fusion_plan), [< 32] a column, [<= 1] a constant, a challenge, theta or gamma, [0] an empty
+// graph: [< 32] in every case, which is what the brackets below assume.
+struct ShuffleDev {
+    const Fe* product;  // extended coset of z
+    const Fe *l0, *l_last, *l_active;
+};
+__device__ __forceinline__ void shuffle_row(const ShuffleDev& sh, const ColsDev& c, uint32_t idx, const Fu& a, const Fu& s, Fe* values) {
+    const Fu one = fu_one_i<UF>();
+    const uint32_t r_next = rot_idx(idx, 1, c.rot_scale, c.log_size);
+    const Fu z = ld_i(sh.product[idx]);                    // [32]
+    Fu v = ld_i(values[idx]);                              // [32]
+    // l_0(X) * (1 - z(X)) = 0
+    v = fold_y(v, c.y, subn(one, z), ld_i(sh.l0[idx]));                                   // [1.2] + [33 * 32 / 169 + 1 = 7.3] = [8.5]
+    // l_last(X) * (z(X)^2 - z(X)) = 0
+    v = fold_y(v, c.y, subn(fu_sqr<UF>(z), z), ld_i(sh.l_last[idx]));                     // [1.1] + [(7.1 + 32) * 32 / 169 + 1 = 8.4] = [9.5]
+    // (1 - (l_last + l_blind)) * (z(wX) s - z(X) a) = 0: the difference of the two products with one reduction
+    const Fu diff = fu_mul_sub<UF>(ld_i(sh.product[r_next]), s, z, a);                    // [(32 * 32 + 32 * 32) / 169 + 1 = 13.2]
+    v = fold_y(v, c.y, diff, ld_i(sh.l_active[idx]));                                     // [1.1] + [13.2 * 32 / 169 + 1 = 3.5] = [4.6]
+    values[idx] = out_e(v);  // [< 15]
+}
+
+// One logUp (mv-lookup) argument's share of a row (include/halo2hip.h, h2hip_evalh_mvlookups), given the table tuple's value tau and, over
+// the K input tuples' values f_c, P = prod f_c and Q = sum_c prod_{l != c} f_l, streamed by the caller as Q <- Q f + P; P <- P f from
+// P_0 = 1, Q_0 = 0 (no inversion on the coset).  Each f_c and tau is a program's result, [< 32] as for the shuffle's a and s above, so
+// P <- P f is [P 32 / 169 + 1 <= 1.3] and Q <- Q f + P is [Q 32 / 169 + 1 + 1.3 <= 2.9] for every K.
+struct MvLookupDev {
+    const Fe *phi, *m;  // extended cosets of the grand sum and of the multiplicities
+    const Fe *l0, *l_last, *l_active;
+};
+__device__ __forceinline__ void mvlookup_row(const MvLookupDev& mv, const ColsDev& c, uint32_t idx, const Fu& tau, const Fu& P, const Fu& Q,
+                                             Fe* values) {
+    const uint32_t r_next = rot_idx(idx, 1, c.rot_scale, c.log_size);
+    const Fu pc = ld_i(mv.phi[idx]);                                      // [32]
+    Fu v = ld_i(values[idx]);                                             // [32]
+    // l_0(X) * phi(X) = 0
+    v = fold_y(v, c.y, pc, ld_i(mv.l0[idx]));                             // [1.2] + [32 * 32 / 169 + 1 = 7.1] = [8.3]
+    // l_last(X) * phi(X) = 0
+    v = fold_y(v, c.y, pc, ld_i(mv.l_last[idx]));                         // [1.1] + [7.1] = [8.2]
+    // (1 - (l_last + l_blind)) * (tau P (phi(wX) - phi(X)) - tau Q + m P) = 0: the first two products leave with one reduction
+    const Fu tp = mul_i(tau, P);                                                        // [32 * 1.3 / 169 + 1 = 1.3]
+    const Fu e = addn(fu_mul_sub<UF>(tp, subn(ld_i(mv.phi[r_next]), pc), tau, Q),       // [(1.3 * 64 + 32 * 2.9) / 169 + 1 = 2.1]
+                      mul_i(ld_i(mv.m[idx]), P));                                       // + [32 * 1.3 / 169 + 1 = 1.3] = [3.4]
+    v = fold_y(v, c.y, e, ld_i(mv.l_active[idx]));                                      // [1.1] + [3.4 * 32 / 169 + 1 = 1.7] = [2.8]
+    values[idx] = out_e(v);  // [< 15]
 }
 
 }  // namespace h2

@@ -37,9 +37,9 @@
  * HALO2_HIP_NTT_TWIDDLE_MB (default 4096) HBM per device for the full inter-pass twiddle tables of 2^20-, 2^21-, 2^23- and 2^24-point
  * transforms (36 bytes per point, domain and direction; without room the two-level table serves, one multiplication more per point);
  * HALO2_HIP_LAZY_PIN=k (default 0 = off) lets the library pin a host bases array by itself once a
- * host-pointer MSM has seen it k times (see h2hip_bases_pin); HALO2_HIP_EVALH_CODEGEN=0|1|2 the per-circuit custom-gates kernel of
- * h2hip_evaluate_h_bn254 (0: byte-code interpreter only; 1, default: generated and compiled by hiprtc on a background thread, the interpreter
- * serves until the code object is ready; 2: compiled inline) and HALO2_HIP_CACHE_DIR a directory that keeps those code objects across processes
+ * host-pointer MSM has seen it k times (see h2hip_bases_pin); HALO2_HIP_EVALH_CODEGEN=0|1|2 the kernels the evaluate_h calls generate per
+ * circuit: the gates', one per lookup, shuffle and mv-lookup argument (0: byte-code interpreter only; 1, default: compiled by hiprtc on a background
+ * thread, the interpreter serves until then; 2: inline; + 32 / + 64: no / both stage kernels) and HALO2_HIP_CACHE_DIR a directory that keeps those code objects across processes
  * (files there are loaded as GPU code, keyed by a hash of their source: the directory must be writable by the prover's user only);
  * HALO2_HIP_RANDOM_MIN_N (default 2^9, read at the first call) the element count from which the host forms of h2hip_fr_random_bn254 /
  * h2hip_fr_from_bytes_wide_bn254 go to the device; below it they are a handful of draws on the calling thread, by design and not as a fallback;
@@ -425,7 +425,7 @@ int h2hip_evaluate_h_workspace_bytes(uint32_t k, uint32_t extended_k, uint32_t n
  * extended coset of z_j and r_next the row one rotation on,
  *   v = v y + (1 - zc[idx]) l0[idx];   v = v y + (zc[idx]^2 - zc[idx]) l_last[idx];   v = v y + l_active_row[idx] (zc[r_next] s - zc[idx] a).
  * A shuffle graph may read fixed, advice, instance, challenge, constant, intermediate, theta and gamma; beta, y or the previous value is
- * H2HIP_EINVAL before any device work.  The shuffle graphs run on the byte-code interpreter (no kernel is generated for them).
+ * H2HIP_EINVAL before any device work.  A shuffle's two graphs run as one kernel generated for the pair, or on the byte-code interpreter.
  * shuffles == NULL or n_shuffles == 0 is the call without the suffix, limb for limb; in the parts form t_evaluations still multiplies
  * last.  n_shuffles <= 65535. */
 typedef struct h2hip_evalh_shuffles {
@@ -456,7 +456,7 @@ int h2hip_evaluate_h_shuffles_workspace_bytes(uint32_t k, uint32_t extended_k, u
  *   v = v y + l0[idx] pc[idx];   v = v y + l_last[idx] pc[idx];
  *   v = v y + l_active_row[idx] (tau P (pc[r_next] - pc[idx]) - tau Q + mc[idx] P).
  * A graph may read fixed, advice, instance, challenge, constant, intermediate, theta and beta; gamma, y or the previous value is
- * H2HIP_EINVAL before any device work.  The graphs run on the byte-code interpreter (no kernel is generated for them).
+ * H2HIP_EINVAL before any device work.  An argument's K + 1 graphs run as one kernel generated for them, or on the byte-code interpreter.
  * required_degree = 2 + d_t + sum_c d_c, each d the largest degree in that tuple, at least 1.  K_j in [1, 255], n_args <= 65535. */
 typedef struct h2hip_evalh_mvlookups {
     uint32_t n_args;

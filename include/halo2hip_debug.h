@@ -91,16 +91,31 @@ int h2hip_debug_set_evalh_max_local_slots(uint32_t v);
 int h2hip_debug_set_evalh_lookup_group_bytes(uint64_t v);
 /* evaluate_h: field multiplications per row of the program a graph compiles to; needs no GPU */
 int h2hip_debug_evalh_program_muls(const h2hip_graph* g, uint32_t* n_mul);
-/* evaluate_h: the per-circuit gates kernel (hiprtc): 0 off, 1 compiled on a background thread while the interpreter serves (default;
- * HALO2_HIP_EVALH_CODEGEN), 2 compiled inline; + 16: without the fusion of two products into one reduction; max_ops: programs with more operations (or more than 48
- * values alive at once) stay with the interpreter (0 restores the default) */
+/* evaluate_h: the kernels generated per circuit (hiprtc) -- the custom gates', one per halo2 lookup and, where the stage's are wanted, one
+ * per shuffle and per mv-lookup argument.  mode bits 0-3: 0 off, 1 compiled on a background thread while the interpreter serves (default;
+ * HALO2_HIP_EVALH_CODEGEN takes the same number), 2 compiled inline; + 16: without the fusion of two products into one reduction; the two-bit
+ * field at + 32 / + 64 selects the shuffle and mv-lookup kernels: 0 the default set (`struct Tuning`), + 32 none (gates and lookups keep
+ * theirs), + 64 both.  max_ops: kernels with more operations over all their programs (or more than 48 values alive at once) stay with the
+ * interpreter (0 restores the default).  (1, 0) restores every default. */
 int h2hip_debug_set_evalh_codegen(int mode, uint32_t max_ops);
 /* the HIP source a graph's program is emitted as (buf may be NULL: *len alone), and with bit 0 of `compile` set what hiprtc makes of it for
  * gfx950 (seconds, bytes of code object); bit 1: the graph as a lookup argument's table expression (evalh_lookup_gen) instead of the custom
  * gates (evalh_gates_gen); needs no GPU.  Returns 0, 1 (malformed graph) or 2 (hiprtc missing / rejected the source). */
 int h2hip_debug_evalh_codegen_source(const h2hip_graph* g, char* buf, size_t cap, size_t* len, int compile, double* seconds, size_t* code_bytes);
-/* out: programs compiled, compilations failed, launches of a generated kernel, launches of the interpreter, disk-cache hits */
+/* ... and the source of a stage kernel, one kernel from several programs: kind 1 = a shuffle (n_graphs == 2: the input side's graph, then the
+ * shuffle side's; evalh_shuffle_gen), kind 2 = an mv-lookup argument (n_graphs == K + 1: the K input tuples' graphs, then the table's;
+ * evalh_mvlookup_gen).  Host only.  Returns 0, 1 (malformed input: a bad kind or count, a malformed graph, a graph reading a value the stage
+ * does not supply), 2 (hiprtc missing / rejected the source) or 3 (the kernel is beyond the generator's limits -- operations over all
+ * programs, values alive at once -- and the engine would keep the interpreter; *len = 0). */
+int h2hip_debug_evalh_codegen_stage_source(const h2hip_graph* graphs, uint32_t n_graphs, int kind, char* buf, size_t cap, size_t* len, int compile,
+                                           double* seconds, size_t* code_bytes);
+/* out: kernels compiled, compilations failed, launches of a generated kernel, launches of the interpreter, disk-cache hits.  compiled,
+ * failed and disk hits count every generated kernel, the shuffles' and mv-lookups' included; the two launch counts are the gates' and
+ * the halo2 lookups' alone, as they were before those stages had kernels (h2hip_debug_evalh_codegen_stage_stats has every stage's). */
 int h2hip_debug_evalh_codegen_stats(uint64_t out[5]);
+/* out[0 .. 8): launches of a generated kernel, then of the interpreter, for the gates, the halo2 lookups, the shuffles and the mv-lookups in
+ * that order; out[8]: background compilations queued or running (a stage kernel is queued only while fewer than 8 are) */
+int h2hip_debug_evalh_codegen_stage_stats(uint64_t out[9]);
 /* evaluate_h: compile a graph as the engine would and report the program's size; needs no GPU */
 int h2hip_debug_evalh_compile_stats(const h2hip_graph* g, uint32_t* n_ops, uint32_t* n_slots);
 /* evaluate_h: the program a graph compiles to; needs no GPU.  *n_ops, *n_slots and result (kind, a, b of the value the row stores; kind 11 =

@@ -4,12 +4,16 @@ K = 4 inputs per table.  Every pair comes from the same process and the same run
   multiplicities   mvlookup_multiplicities_device for uniform inputs and for all rows hitting one table value, beside
                    lookup_permute_device of the K (input, table) pairs the halo2 lookup needs for the same inputs
   sums             mvlookup_sums_device beside lookup_products_device of those K lookups
-  evaluate_h       the stage's time per argument (stage "evalh_mvlookups": the interpreter's evalh_mvlookup_kernel, its coset transforms
-                   not included) on the evalh-bench system (24 gate polynomials over 12 advice and 10 fixed columns, 9 permutation
+  evaluate_h       the stage's time per argument (stage "evalh_mvlookups": the kernel generated per argument or the interpreter's
+                   evalh_mvlookup_kernel, as --codegen says; its coset transforms not included) on the evalh-bench system (24 gate polynomials over 12 advice and 10 fixed columns, 9 permutation
                    columns, 2 lookups) beside K times the lookup stage's time per lookup (stage "evalh_lookups": generated kernels)
 The clocks the card reports go into the record.
 
-  python tools/mvlookup_bench.py [--k 18] [--reps 5] [--out profiles/mvlookup_bench.json]     (run on the GPU box)
+--codegen is the mode of h2hip_debug_set_evalh_codegen for the evaluate_h part (2 + 32: the mv-lookups on the interpreter; 2 + 64: generated),
+--exprs the expressions a tuple, --inputs the values of K, --stage-only leaves the multiplicities and the sums out.  The first call's wall
+time (the inline compilations) and the launches the stage counters saw are recorded.
+
+  python tools/mvlookup_bench.py [--k 18] [--inputs 1,4] [--exprs 2] [--codegen 2] [--reps 5] [--stage-only] [--out profiles/mvlookup_bench.json]     (run on the GPU box)
 """
 import argparse
 import ctypes
@@ -17,6 +21,7 @@ import json
 import os
 import statistics
 import sys
+import time
 
 import numpy as np
 
@@ -25,23 +30,25 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from __graft_entry__ import load_pkg  # noqa: E402
 import evalh_bench  # noqa: E402
-from shuffle_bench import clocks  # noqa: E402
+from shuffle_bench import clocks, side, stage_counters  # noqa: E402
 
 B = 5
 R_MOD = evalh_bench.R_MOD
 ARGS = 2  # mv-lookup arguments in the evaluate_h system
 
 
-def evalh_stage(h2, ev, orc, torch, k, K, reps):
+def evalh_stage(h2, ev, orc, torch, k, K, reps, exprs=2, codegen=2):
     """stage medians of evaluate_h on the evalh-bench system with ARGS mv-lookup arguments of K input pairs each"""
     L = h2.lib()
     sa = evalh_bench.default_args()
     gates, lookups = evalh_bench.system_expressions(sa, np.random.default_rng(1))
     A = lambda c, r=0: ('advice', c, r)  # noqa: E731
     F = lambda c, r=0: ('fixed', c, r)  # noqa: E731
-    # as wide as the bench system's lookups: two expressions a tuple, one of them a product with a fixed column
-    mv = [([[A((j + 2 * t) % sa.advice), ('prod', A((j + 2 * t + 1) % sa.advice), F((j + t) % sa.fixed))] for t in range(K)],
-           [F((j + 1) % sa.fixed), F((j + 2) % sa.fixed, 1)]) for j in range(ARGS)]
+    if exprs == 2:  # as wide as the bench system's lookups: two expressions a tuple, one of them a product with a fixed column
+        mv = [([[A((j + 2 * t) % sa.advice), ('prod', A((j + 2 * t + 1) % sa.advice), F((j + t) % sa.fixed))] for t in range(K)],
+               [F((j + 1) % sa.fixed), F((j + 2) % sa.fixed, 1)]) for j in range(ARGS)]
+    else:  # the K tuples of an argument share selectors and columns; the table is fixed columns
+        mv = [([side(sa, j, exprs, 2 * t) for t in range(K)], [F((j + 1 + t) % sa.fixed, t % 2) for t in range(exprs)]) for j in range(ARGS)]
     evaluator = ev.Evaluator.new(gates, lookups, [], mv)
     ek = k + 2
     n, size = 1 << k, 1 << ek
@@ -84,9 +91,12 @@ def evalh_stage(h2, ev, orc, torch, k, K, reps):
         rc = L.h2hip_evaluate_h_ext_bn254_device(hd.byref(), hm.byref(), None, ctypes.c_void_p(d_values.data_ptr()), stream)
         assert rc == 0, L.h2hip_last_error()
 
-    L.h2hip_debug_set_evalh_codegen(ctypes.c_int(2), ctypes.c_uint32(0))  # the lookups' and the gates' kernels generated and compiled inline
+    L.h2hip_debug_set_evalh_codegen(ctypes.c_int(codegen), ctypes.c_uint32(0))  # mode 2: the kernels generated and compiled inline
+    t0 = time.time()
     call()
     torch.cuda.synchronize()
+    first_call_s = time.time() - t0
+    counters0 = stage_counters(L)
     per = {"evalh_lookups": [], "evalh_mvlookups": [], "evalh_gates": [], "evalh_perm": [], "evalh_cosets": []}
     for _ in range(reps):
         h2.profile_enable(True)
@@ -98,14 +108,23 @@ def evalh_stage(h2, ev, orc, torch, k, K, reps):
             per[name].append(h2.profile_get(name)[0])
     L.h2hip_debug_set_evalh_codegen(ctypes.c_int(1), ctypes.c_uint32(0))
     med = {name: statistics.median(v) for name, v in per.items()}
-    return {"stage_ms_median": med, "ms_per_lookup": med["evalh_lookups"] / max(1, sa.lookups), "ms_per_mvlookup": med["evalh_mvlookups"] / ARGS,
-            "ms_K_lookups": K * med["evalh_lookups"] / max(1, sa.lookups)}
+    out = {"stage_ms_median": med, "ms_per_lookup": med["evalh_lookups"] / max(1, sa.lookups), "ms_per_mvlookup": med["evalh_mvlookups"] / ARGS,
+           "ms_per_mvlookup_runs": [v / ARGS for v in per["evalh_mvlookups"]], "ms_K_lookups": K * med["evalh_lookups"] / max(1, sa.lookups),
+           "exprs_per_tuple": exprs, "codegen": codegen, "first_call_s": first_call_s}
+    counters1 = stage_counters(L)
+    if counters1:
+        out["stage_launches_generated_interpreted"] = {name: [b[0] - a[0], b[1] - a[1]] for (name, a), b in zip(counters0.items(), counters1.values())}
+    return out
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--k", type=int, default=18)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--inputs", default="1,4", help="the values of K, inputs per table")
+    ap.add_argument("--exprs", type=int, default=2, help="expressions a tuple in the evaluate_h part")
+    ap.add_argument("--codegen", type=int, default=2, help="h2hip_debug_set_evalh_codegen mode for the evaluate_h part")
+    ap.add_argument("--stage-only", action="store_true", help="the evaluate_h part alone")
     ap.add_argument("--out")
     args = ap.parse_args()
     import importlib
@@ -137,7 +156,10 @@ def main():
     tab = h2.gen_scalars_device(2000, n)  # distinct values
     g = torch.Generator(device="cuda")
     g.manual_seed(7)
-    for K in (1, 4):
+    for K in [int(x) for x in args.inputs.split(",")]:
+        if args.stage_only:
+            rec["K"][str(K)] = {"evaluate_h": evalh_stage(h2, ev, orc, torch, k, K, args.reps, args.exprs, args.codegen)}
+            continue
         uniform = [tab[torch.randint(0, u, (n,), device="cuda", generator=g)].contiguous() for _ in range(K)]
         one = [tab[u // 2].repeat(n, 1).contiguous() for _ in range(K)]
         m, phi = [torch.empty_like(tab)], [torch.empty_like(tab)]
@@ -153,7 +175,7 @@ def main():
         r["lookup_products"] = timed(lambda: h2.lookup_products_device(k, beta, gamma, uniform, [tab] * K, pa, pt, orc.gen_scalars(77, K * B), B, z))
         torch.cuda.synchronize()
         r["phi_u_is_zero"] = bool((phi[0][u] == 0).all().item())
-        r["evaluate_h"] = evalh_stage(h2, ev, orc, torch, k, K, args.reps)
+        r["evaluate_h"] = evalh_stage(h2, ev, orc, torch, k, K, args.reps, args.exprs, args.codegen)
         rec["K"][str(K)] = r
     rec["clocks_after"] = clocks()
     print(json.dumps(rec), flush=True)

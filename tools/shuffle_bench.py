@@ -2,14 +2,18 @@
 """The shuffle argument beside the lookup argument on the evalh-bench system (24 gate polynomials over 12 advice and 10 fixed columns, 9
 permutation columns, 2 lookups) with --shuffles shuffles added, device-resident, at k (extended_k = k + 2).  Three pairs, each from the
 same process and the same run, medians of --reps:
-  evaluate_h   the shuffle stage's time per shuffle (stage "evalh_shuffles": the interpreter's evalh_shuffle_kernel, its coset transform
-               not included) beside the lookup stage's time per lookup (stage "evalh_lookups": generated kernels, the cosets of the first
-               group are formed before the stage)
+  evaluate_h   the shuffle stage's time per shuffle (stage "evalh_shuffles": the kernel generated per shuffle or the interpreter's
+               evalh_shuffle_kernel, as --codegen says; its coset transform not included) beside the lookup stage's time per lookup (stage
+               "evalh_lookups": generated kernels, the cosets of the first group are formed before the stage)
   products     shuffle_products_device beside lookup_products_device at equal count
   check        check_shuffles_device beside check_lookups_device at equal count
 The clocks the card reports go into the record.
 
-  python tools/shuffle_bench.py [--k 18] [--shuffles 2] [--reps 5] [--out profiles/shuffle_bench.json]     (run on the GPU box)
+--codegen is the mode of h2hip_debug_set_evalh_codegen for the evaluate_h part (2: every kernel of the default set generated and compiled
+inline; 2 + 32: the shuffles on the interpreter; 2 + 64: the shuffles generated), --exprs the expressions a side, --stage-only leaves the
+products and the check out.  The first call's wall time (the inline compilations) and the launches the stage counters saw are recorded.
+
+  python tools/shuffle_bench.py [--k 18] [--shuffles 2] [--exprs 2] [--codegen 2] [--reps 5] [--stage-only] [--out profiles/shuffle_bench.json]     (run on the GPU box)
 """
 import argparse
 import ctypes
@@ -18,6 +22,7 @@ import os
 import statistics
 import subprocess
 import sys
+import time
 
 import numpy as np
 
@@ -39,10 +44,34 @@ def clocks():
         return ["unavailable: %r" % (e,)]
 
 
+def stage_counters(L):
+    """launches of a generated kernel and of the interpreter per stage, or None with a library from before the stage kernels"""
+    if not hasattr(L, "h2hip_debug_evalh_codegen_stage_stats"):
+        return None
+    out = (ctypes.c_uint64 * 9)()
+    L.h2hip_debug_evalh_codegen_stage_stats(out)
+    return {name: [int(out[2 * i]), int(out[2 * i + 1])] for i, name in enumerate(("gates", "lookups", "shuffles", "mvlookups"))}
+
+
+def side(sa, j, m, shift):
+    """m expressions over the bench system's columns: every second one a product with a fixed column, every third one rotated, so that
+    the expressions of a side share selectors and columns as a circuit's do"""
+    A = lambda c, r=0: ('advice', c, r)  # noqa: E731
+    F = lambda c, r=0: ('fixed', c, r)  # noqa: E731
+    out = []
+    for t in range(m):
+        a = A((j + shift + t) % sa.advice, 1 if t % 3 == 2 else 0)
+        out.append(('prod', a, F((j + t // 2) % sa.fixed)) if t % 2 else a)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--k", type=int, default=18)
     ap.add_argument("--shuffles", type=int, default=2)
+    ap.add_argument("--exprs", type=int, default=2, help="expressions a side")
+    ap.add_argument("--codegen", type=int, default=2, help="h2hip_debug_set_evalh_codegen mode for the evaluate_h part")
+    ap.add_argument("--stage-only", action="store_true", help="the evaluate_h part alone")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out")
     args = ap.parse_args()
@@ -58,9 +87,11 @@ def main():
     gates, lookups = evalh_bench.system_expressions(sa, np.random.default_rng(1))
     A = lambda c, r=0: ('advice', c, r)  # noqa: E731
     F = lambda c, r=0: ('fixed', c, r)  # noqa: E731
-    # as wide as the bench system's lookups: two expressions a side, one of them a product with a fixed column, one rotated
-    shuffles = [([A(j % sa.advice), ('prod', A((j + 1) % sa.advice), F(j % sa.fixed))], [A((j + 2) % sa.advice), A((j + 3) % sa.advice, 1)])
-                for j in range(args.shuffles)]
+    if args.exprs == 2:  # as wide as the bench system's lookups: two expressions a side, one of them a product with a fixed column, one rotated
+        shuffles = [([A(j % sa.advice), ('prod', A((j + 1) % sa.advice), F(j % sa.fixed))], [A((j + 2) % sa.advice), A((j + 3) % sa.advice, 1)])
+                    for j in range(args.shuffles)]
+    else:
+        shuffles = [(side(sa, j, args.exprs, 0), side(sa, j, args.exprs, 5)) for j in range(args.shuffles)]
     evaluator = ev.Evaluator.new(gates, lookups, shuffles)
     k, ek = args.k, args.k + 2
     n, size = 1 << k, 1 << ek
@@ -103,10 +134,13 @@ def main():
         rc = L.h2hip_evaluate_h_shuffles_bn254_device(hd.byref(), hs.byref(), ctypes.c_void_p(d_values.data_ptr()), stream)
         assert rc == 0, L.h2hip_last_error()
 
-    L.h2hip_debug_set_evalh_codegen(ctypes.c_int(2), ctypes.c_uint32(0))  # the lookups' and the gates' kernels generated and compiled inline
+    L.h2hip_debug_set_evalh_codegen(ctypes.c_int(args.codegen), ctypes.c_uint32(0))  # mode 2: the kernels generated and compiled inline
+    t0 = time.time()
     call()
     torch.cuda.synchronize()
-    rec = {"k": k, "extended_k": ek, "lookups": sa.lookups, "shuffles": args.shuffles, "reps": args.reps, "clocks_before": clocks()}
+    rec = {"k": k, "extended_k": ek, "lookups": sa.lookups, "shuffles": args.shuffles, "exprs_per_side": args.exprs, "codegen": args.codegen,
+           "first_call_s": time.time() - t0, "reps": args.reps, "clocks_before": clocks()}
+    counters0 = stage_counters(L)
     per = {"evalh_lookups": [], "evalh_shuffles": [], "evalh_gates": [], "evalh_perm": [], "evalh_cosets": []}
     for _ in range(args.reps):
         h2.profile_enable(True)
@@ -120,6 +154,17 @@ def main():
     rec["stage_ms_median"] = {name: statistics.median(v) for name, v in per.items()}
     rec["ms_per_lookup"] = rec["stage_ms_median"]["evalh_lookups"] / max(1, sa.lookups)
     rec["ms_per_shuffle"] = rec["stage_ms_median"]["evalh_shuffles"] / max(1, args.shuffles)
+    rec["ms_per_shuffle_runs"] = [v / max(1, args.shuffles) for v in per["evalh_shuffles"]]
+    counters1 = stage_counters(L)
+    if counters1:
+        rec["stage_launches_generated_interpreted"] = {name: [b[0] - a[0], b[1] - a[1]] for (name, a), b in zip(counters0.items(), counters1.values())}
+    if args.stage_only:
+        rec["clocks_after"] = clocks()
+        print(json.dumps(rec), flush=True)
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump(rec, f, indent=1)
+        return
 
     def timed(fn):
         ts = []
