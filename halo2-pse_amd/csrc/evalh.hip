@@ -1113,8 +1113,45 @@ extern "C" int h2hip_debug_evalh_codegen_source(const h2hip_graph* g, char* buf,
     return rtc_compile_for_hook(src, seconds, code_bytes);
 }
 
-static bool shuffle_vs_allowed(const h2hip_value_source& v);
-static bool mvlookup_vs_allowed(const h2hip_value_source& v);
+// The three grouped arguments behind the gates and the permutation, in the order of the call plan and of the pass.  Per argument a stage
+// has `cosets` product polynomials, formed as cosets in buffers that a group of arguments shares (stage_group), and one kernel that folds
+// the argument's programs into `values`: 1 per lookup, K_j + 1 per mv-lookup argument, 2 per shuffle.
+// `eager` is what the lookups alone have from before the other two existed: the cosets of their first group are formed in the batch of
+// the advice and instance columns (later groups on demand, like every group of the other stages), and their profile interval is one per
+// pass, those later transforms included, where the others' is one per argument without its group's transform.
+enum { ST_LOOKUP = 0, ST_MVLOOKUP = 1, ST_SHUFFLE = 2, N_STAGES = 3 };
+#define VS_BIT(kind) (1u << H2HIP_VS_##kind)
+struct Stage {
+    GenKind kind;
+    uint32_t cosets;
+    const char* profile;
+    uint32_t barred;  // value sources (VS_BIT) the stage's graphs may not read: no kernel of the stage supplies them
+    bool eager;
+};
+static const Stage STAGES[N_STAGES] = {
+    {GEN_LOOKUP, 3, "evalh_lookups", 0, true},
+    {GEN_MVLOOKUP, 2, "evalh_mvlookups", VS_BIT(GAMMA) | VS_BIT(Y) | VS_BIT(PREVIOUS), false},
+    {GEN_SHUFFLE, 1, "evalh_shuffles", VS_BIT(BETA) | VS_BIT(Y) | VS_BIT(PREVIOUS), false},
+};
+
+// every operand of every calculation of g, Horner parts included, is a value source of a kind in `allowed` (VS_BIT); *bad: the first
+// calculation that reads another
+static bool graph_reads_only(const h2hip_graph& g, uint32_t allowed, uint32_t* bad) {
+    auto ok = [&](const h2hip_value_source& v) { return v.kind < 32 && (allowed >> v.kind & 1); };
+    for (uint32_t q = 0; q < g.n_calculations; q++) {
+        const h2hip_calculation& cl = g.calculations[q];
+        bool fine = ok(cl.x);
+        if (cl.op == H2HIP_CALC_ADD || cl.op == H2HIP_CALC_SUB || cl.op == H2HIP_CALC_MUL || cl.op == H2HIP_CALC_HORNER) fine = fine && ok(cl.y);
+        if (cl.op == H2HIP_CALC_HORNER)
+            for (uint32_t t = 0; fine && t < cl.parts_count; t++) fine = ok(g.parts[cl.parts_offset + t]);
+        if (!fine) {
+            *bad = q;
+            return false;
+        }
+    }
+    return true;
+}
+
 // ... and the source of a stage kernel: kind 1 = a shuffle's two graphs (input side, shuffle side), kind 2 = an mv-lookup argument's
 // K + 1 graphs (the K input tuples', then the table's).  3: beyond the generator's limits -- the engine keeps the interpreter
 extern "C" int h2hip_debug_evalh_codegen_stage_source(const h2hip_graph* graphs, uint32_t n_graphs, int kind, char* buf, size_t cap, size_t* len,
@@ -1124,26 +1161,18 @@ extern "C" int h2hip_debug_evalh_codegen_stage_source(const h2hip_graph* graphs,
         return 1;
     }
     TuneRead r;
+    const Stage& st = STAGES[kind == 1 ? ST_SHUFFLE : ST_MVLOOKUP];
     std::vector<Program> progs(n_graphs);
     std::vector<const h2hip_graph*> gp(n_graphs);
-    for (uint32_t i = 0; i < n_graphs; i++) {
-        const h2hip_graph& g = graphs[i];
-        if (compile_any(&g, &progs[i])) return 1;
-        gp[i] = &g;
-        auto allowed = [&](const h2hip_value_source& v) { return kind == 1 ? shuffle_vs_allowed(v) : mvlookup_vs_allowed(v); };
-        for (uint32_t q = 0; q < g.n_calculations; q++) {  // as evaluate_h_shuffles_validate / evaluate_h_mvlookups_validate
-            const h2hip_calculation& cl = g.calculations[q];
-            bool ok = allowed(cl.x);
-            if (cl.op == H2HIP_CALC_ADD || cl.op == H2HIP_CALC_SUB || cl.op == H2HIP_CALC_MUL || cl.op == H2HIP_CALC_HORNER) ok = ok && allowed(cl.y);
-            if (cl.op == H2HIP_CALC_HORNER)
-                for (uint32_t t = 0; ok && t < cl.parts_count; t++) ok = allowed(g.parts[cl.parts_offset + t]);
-            if (!ok) {
-                set_error("evaluate_h: %s graph %u, calculation %u reads a value the stage does not supply", kind == 1 ? "shuffle" : "mv-lookup", i, q);
-                return 1;
-            }
+    for (uint32_t i = 0, q; i < n_graphs; i++) {
+        if (compile_any(&graphs[i], &progs[i])) return 1;
+        gp[i] = &graphs[i];
+        if (!graph_reads_only(graphs[i], ~st.barred, &q)) {
+            set_error("evaluate_h: %s graph %u, calculation %u reads a value the stage does not supply", kind == 1 ? "shuffle" : "mv-lookup", i, q);
+            return 1;
         }
     }
-    const GenUnit u = gen_unit(kind == 1 ? GEN_SHUFFLE : GEN_MVLOOKUP, gp.data(), progs.data(), n_graphs);
+    const GenUnit u = gen_unit(st.kind, gp.data(), progs.data(), n_graphs);
     if (!gen_within_limits(u)) {
         *len = 0;
         set_error("evaluate_h: stage kernel beyond the generator's limits (%zu operations, %u live values)", u.n_ops(), u.n_live());
@@ -1439,7 +1468,6 @@ int evaluate_h_validate(const h2hip_evalh_desc* d, const void* values) {
 
 // The shuffle stage of a call whose description `d` passed evaluate_h_validate: the tables, every graph's indices, and what a shuffle
 // graph may read -- not beta, y or the previous value, which no kernel of the stage supplies.  Needs no device.
-static bool shuffle_vs_allowed(const h2hip_value_source& v) { return v.kind != H2HIP_VS_BETA && v.kind != H2HIP_VS_Y && v.kind != H2HIP_VS_PREVIOUS; }
 static int evaluate_h_shuffles_validate(const h2hip_evalh_desc* d, const h2hip_evalh_shuffles* sh) {
     if (!sh || !sh->n_shuffles) return 0;
     if (sh->n_shuffles > 65535) {
@@ -1451,19 +1479,12 @@ static int evaluate_h_shuffles_validate(const h2hip_evalh_desc* d, const h2hip_e
         return 1;
     }
     if (check_ptrs("evaluate_h", (const void* const*)sh->product_polys, sh->n_shuffles, "shuffle product_polys")) return 1;
+    uint32_t q;
     for (size_t i = 0; i < 2 * (size_t)sh->n_shuffles; i++) {
-        const h2hip_graph& g = sh->graphs[i];
-        if (graph_validate(g, *d, "shuffle")) return 1;
-        for (uint32_t q = 0; q < g.n_calculations; q++) {
-            const h2hip_calculation& cl = g.calculations[q];
-            bool ok = shuffle_vs_allowed(cl.x);
-            if (cl.op == H2HIP_CALC_ADD || cl.op == H2HIP_CALC_SUB || cl.op == H2HIP_CALC_MUL || cl.op == H2HIP_CALC_HORNER) ok = ok && shuffle_vs_allowed(cl.y);
-            if (cl.op == H2HIP_CALC_HORNER)
-                for (uint32_t t = 0; ok && t < cl.parts_count; t++) ok = shuffle_vs_allowed(g.parts[cl.parts_offset + t]);
-            if (!ok) {
-                set_error("evaluate_h: shuffle graph %zu, calculation %u reads beta, y or the previous value", i, q);
-                return 1;
-            }
+        if (graph_validate(sh->graphs[i], *d, "shuffle")) return 1;
+        if (!graph_reads_only(sh->graphs[i], ~STAGES[ST_SHUFFLE].barred, &q)) {
+            set_error("evaluate_h: shuffle graph %zu, calculation %u reads beta, y or the previous value", i, q);
+            return 1;
         }
     }
     return 0;
@@ -1471,7 +1492,6 @@ static int evaluate_h_shuffles_validate(const h2hip_evalh_desc* d, const h2hip_e
 
 // The mv-lookup stage of such a call (h2hip_evalh_mvlookups): the tables, the limits, every graph's indices, and what a graph may read --
 // not gamma, y or the previous value.  Needs no device.
-static bool mvlookup_vs_allowed(const h2hip_value_source& v) { return v.kind != H2HIP_VS_GAMMA && v.kind != H2HIP_VS_Y && v.kind != H2HIP_VS_PREVIOUS; }
 static int evaluate_h_mvlookups_validate(const h2hip_evalh_desc* d, const h2hip_evalh_mvlookups* mv) {
     if (!mv || !mv->n_args) return 0;
     if (mv->n_args > 65535) {
@@ -1493,19 +1513,12 @@ static int evaluate_h_mvlookups_validate(const h2hip_evalh_desc* d, const h2hip_
         }
         n_graphs += mv->n_inputs[j] + 1;
     }
+    uint32_t q;
     for (size_t i = 0; i < n_graphs; i++) {
-        const h2hip_graph& g = mv->graphs[i];
-        if (graph_validate(g, *d, "mv-lookup")) return 1;
-        for (uint32_t q = 0; q < g.n_calculations; q++) {
-            const h2hip_calculation& cl = g.calculations[q];
-            bool ok = mvlookup_vs_allowed(cl.x);
-            if (cl.op == H2HIP_CALC_ADD || cl.op == H2HIP_CALC_SUB || cl.op == H2HIP_CALC_MUL || cl.op == H2HIP_CALC_HORNER) ok = ok && mvlookup_vs_allowed(cl.y);
-            if (cl.op == H2HIP_CALC_HORNER)
-                for (uint32_t t = 0; ok && t < cl.parts_count; t++) ok = mvlookup_vs_allowed(g.parts[cl.parts_offset + t]);
-            if (!ok) {
-                set_error("evaluate_h: mv-lookup graph %zu, calculation %u reads gamma, y or the previous value", i, q);
-                return 1;
-            }
+        if (graph_validate(mv->graphs[i], *d, "mv-lookup")) return 1;
+        if (!graph_reads_only(mv->graphs[i], ~STAGES[ST_MVLOOKUP].barred, &q)) {
+            set_error("evaluate_h: mv-lookup graph %zu, calculation %u reads gamma, y or the previous value", i, q);
+            return 1;
         }
     }
     return 0;
@@ -1539,9 +1552,8 @@ struct MetaBlob {
 // drivers (lookup compression, the witness check's gates) build one.
 struct CallPlan {
     std::vector<const h2hip_graph*> graphs;  // the gates graph first when the call has one, then its further graphs in order
-    size_t n_lookups = 0, n_shuffles = 0;    // evaluate_h: the further graphs are n_lookups lookup graphs, the mv-lookups', then 2 n_shuffles shuffle graphs
-    std::vector<uint32_t> mv_inputs;         // evaluate_h: K_j per mv-lookup argument; its K_j + 1 graphs follow those of argument j - 1
-    size_t n_mv_graphs = 0;
+    struct Arg { size_t first, n; };         // an argument's programs: first .. first + n of the plan
+    std::vector<Arg> args[N_STAGES];         // evaluate_h: the further graphs are the lookups', the mv-lookups', then the shuffles', argument by argument
     std::vector<Program> progs;
     std::vector<SlotPlan> plans;
     size_t largest = 0;     // the program with the most slots: its plan serves a launch that runs every graph of the call
@@ -1552,16 +1564,16 @@ struct CallPlan {
 static int call_plan(const h2hip_graph* gates, const h2hip_graph* more, size_t n_more, size_t rows, CallPlan* cp,
                      const h2hip_evalh_shuffles* sh = nullptr, const h2hip_evalh_mvlookups* mv = nullptr) {
     if (gates) cp->graphs.push_back(gates);
-    for (size_t i = 0; i < n_more; i++) cp->graphs.push_back(more + i);
-    cp->n_lookups = n_more;
-    for (uint32_t j = 0; mv && j < mv->n_args; j++) {  // K_j + 1 programs per mv-lookup argument, behind the lookups'
-        cp->mv_inputs.push_back(mv->n_inputs[j]);
-        cp->n_mv_graphs += mv->n_inputs[j] + 1;
-    }
-    for (size_t i = 0; i < cp->n_mv_graphs; i++) cp->graphs.push_back(mv->graphs + i);
-    cp->meta_bytes += cp->n_mv_graphs ? cp->n_mv_graphs * sizeof(ProgDev) + 256 : 0;  // the device table of their programs (mv_progs_put)
-    cp->n_shuffles = sh ? sh->n_shuffles : 0;  // two programs per shuffle, behind the lookups'
-    for (size_t i = 0; i < 2 * cp->n_shuffles; i++) cp->graphs.push_back(sh->graphs + i);
+    auto argument = [&](int stage, const h2hip_graph* g, size_t n) {  // the next n graphs of a stage's table are one argument's
+        cp->args[stage].push_back({cp->graphs.size(), n});
+        for (size_t i = 0; i < n; i++) cp->graphs.push_back(g + i);
+        return g + n;
+    };
+    for (size_t i = 0; i < n_more; i++) argument(ST_LOOKUP, more + i, 1);
+    const h2hip_graph* g = mv ? mv->graphs : nullptr;
+    for (uint32_t j = 0; mv && j < mv->n_args; j++) g = argument(ST_MVLOOKUP, g, (size_t)mv->n_inputs[j] + 1);  // the K_j input tuples', then the table's
+    if (mv && mv->n_args) cp->meta_bytes += (size_t)(g - mv->graphs) * sizeof(ProgDev) + 256;  // the device table of their programs (mv_progs_put)
+    for (uint32_t j = 0; sh && j < sh->n_shuffles; j++) argument(ST_SHUFFLE, sh->graphs + 2 * (size_t)j, 2);  // the input side's, then the shuffle side's
     const size_t count = cp->graphs.size();
     cp->progs.resize(count);
     cp->plans.resize(count);
@@ -1601,8 +1613,9 @@ static std::vector<ProgDev> progs_put(MetaBlob& mb, const CallPlan& cp) {
 
 // the mv-lookup programs once more, as the one device table evalh_mvlookup_kernel indexes (nullptr for a call without mv-lookups)
 static const ProgDev* mv_progs_put(MetaBlob& mb, const CallPlan& cp, const std::vector<ProgDev>& pds) {
-    if (!cp.n_mv_graphs) return nullptr;
-    return mb.put(pds.data() + (pds.size() - 2 * cp.n_shuffles - cp.n_mv_graphs), cp.n_mv_graphs);
+    const std::vector<CallPlan::Arg>& args = cp.args[ST_MVLOOKUP];
+    if (args.empty()) return nullptr;
+    return mb.put(pds.data() + args.front().first, args.back().first + args.back().n - args.front().first);
 }
 
 // The column tables (device pointers, d's counts), d's challenges and its scalars into the metadata image.  Of d only the counts, the
@@ -1698,135 +1711,113 @@ static int enqueue_gates(Ctx* c, const CallPlan& cp, const ProgDev& gd, const Co
     return 0;
 }
 
-// ... and of one lookup argument's constraints (program i of the plan)
-static int enqueue_lookup(Ctx* c, const CallPlan& cp, size_t i, const ProgDev& lg, const LookupDev& ld, const ColsDev& cols, Fe* d_values,
-                          size_t rows, hipStream_t s) {
-    if (hipFunction_t lgen = kernel_for(c, GEN_LOOKUP, cp, i, 1))  // generated for this circuit, as the gates kernel is
-        return launch_generated(lgen, GEN_LOOKUP, cols, &ld, d_values, s);
-    g_rtc_stats.launched(GEN_LOOKUP, false);
-    const SlotPlan& lp = cp.plans[i];
-    with_tier(lp.tier, [&](auto tier, size_t lds) {
-        hipLaunchKernelGGL(evalh_lookup_kernel<decltype(tier)::value>, dim3(lp.lanes / 256), dim3(256), lds, s, lg, ld, cols, d_values,
-                           (Fu*)c->evalh_slots.p, lp.lanes);
-    });
-    H2_CHECK(hipGetLastError());
-    return 0;
-}
+// What a pass reads of the metadata region: the plan's programs (pds, and mv_progs, the device table of the mv-lookups'), the column
+// tables, the permutation's, and l0, l_last, l_active
+struct PassMeta {
+    const std::vector<ProgDev>& pds;
+    const ProgDev* mv_progs;
+    const ColsDev& cols;
+    const PermDev& pd;
+    const Fe* const* l;
+};
 
-// ... and of one shuffle argument's (programs i and i + 1 of the plan): the kernel generated for the pair where the stage's kernels are
-// wanted (Tuning::evalh_gen_shuffle) and the pair is within the generator's limits; otherwise, and until that kernel is compiled, the
-// interpreter, on the slot plan of the program with more slots -- its tier holds the other's slots too, and its global workspace, if it
-// needs one, is within the call's largest
-static int enqueue_shuffle(Ctx* c, const CallPlan& cp, size_t i, const std::vector<ProgDev>& pds, const ShuffleDev& sd, const ColsDev& cols,
-                           Fe* d_values, hipStream_t s) {
-    if (hipFunction_t gen = kernel_for(c, GEN_SHUFFLE, cp, i, 2)) return launch_generated(gen, GEN_SHUFFLE, cols, &sd, d_values, s);
-    g_rtc_stats.launched(GEN_SHUFFLE, false);
-    const SlotPlan& sp = cp.plans[cp.progs[i].n_slots >= cp.progs[i + 1].n_slots ? i : i + 1];
-    with_tier(sp.tier, [&](auto tier, size_t lds) {
-        hipLaunchKernelGGL(evalh_shuffle_kernel<decltype(tier)::value>, dim3(sp.lanes / 256), dim3(256), lds, s, pds[i], pds[i + 1], sd, cols,
-                           d_values, (Fu*)c->evalh_slots.p, sp.lanes);
-    });
-    H2_CHECK(hipGetLastError());
-    return 0;
-}
-
-// ... and of one mv-lookup argument's (programs i .. i + n_inputs of the plan, d_progs their device table): the kernel generated for
-// the K + 1 programs under the same conditions (Tuning::evalh_gen_mvlookup); otherwise the interpreter, on the slot plan of the program
-// with the most slots among them
-static int enqueue_mvlookup(Ctx* c, const CallPlan& cp, size_t i, uint32_t n_inputs, const ProgDev* d_progs, const MvLookupDev& md,
-                            const ColsDev& cols, Fe* d_values, hipStream_t s) {
-    if (hipFunction_t gen = kernel_for(c, GEN_MVLOOKUP, cp, i, (size_t)n_inputs + 1)) return launch_generated(gen, GEN_MVLOOKUP, cols, &md, d_values, s);
-    g_rtc_stats.launched(GEN_MVLOOKUP, false);
-    size_t big = i;
-    for (size_t t = i; t <= i + n_inputs; t++)
+// ... and of one argument of a stage (programs a.first .. a.first + a.n of the plan; z: its cosets, STAGES[stage].cosets of them): the
+// kernel generated for its programs where that is wanted (a stage's switch, Tuning::evalh_gen_shuffle / evalh_gen_mvlookup), within the
+// generator's limits and compiled; otherwise the interpreter, on the slot plan of the first program with the most slots among them -- its
+// tier holds the others' slots too, and its global workspace, if it needs one, is within the call's largest
+static int enqueue_argument(Ctx* c, int stage, const CallPlan& cp, CallPlan::Arg a, const PassMeta& m, const Fe* const* z, Fe* d_values,
+                            hipStream_t s) {
+    const GenKind kind = STAGES[stage].kind;
+    const Fe* const* l = m.l;
+    union {
+        LookupDev lookup;
+        MvLookupDev mv;
+        ShuffleDev shuffle;
+    } dev;  // the stage's descriptor: its cosets, then l0, l_last, l_active
+    switch (stage) {
+        case ST_LOOKUP: dev.lookup = {z[0], z[1], z[2], l[0], l[1], l[2]}; break;
+        case ST_MVLOOKUP: dev.mv = {z[0], z[1], l[0], l[1], l[2]}; break;
+        default: dev.shuffle = {z[0], l[0], l[1], l[2]};
+    }
+    if (hipFunction_t gen = kernel_for(c, kind, cp, a.first, a.n)) return launch_generated(gen, kind, m.cols, &dev, d_values, s);
+    g_rtc_stats.launched(kind, false);
+    size_t big = a.first;
+    for (size_t t = a.first; t < a.first + a.n; t++)
         if (cp.progs[t].n_slots > cp.progs[big].n_slots) big = t;
     const SlotPlan& sp = cp.plans[big];
-    with_tier(sp.tier, [&](auto tier, size_t lds) {
-        hipLaunchKernelGGL(evalh_mvlookup_kernel<decltype(tier)::value>, dim3(sp.lanes / 256), dim3(256), lds, s, d_progs, n_inputs, md, cols,
-                           d_values, (Fu*)c->evalh_slots.p, sp.lanes);
-    });
+    const dim3 grid(sp.lanes / 256), block(256);
+    Fu* const slots = (Fu*)c->evalh_slots.p;
+    const ProgDev* pd = m.pds.data() + a.first;
+    switch (stage) {
+        case ST_LOOKUP:
+            with_tier(sp.tier, [&](auto tier, size_t lds) {
+                hipLaunchKernelGGL(evalh_lookup_kernel<decltype(tier)::value>, grid, block, lds, s, pd[0], dev.lookup, m.cols, d_values, slots, sp.lanes);
+            });
+            break;
+        case ST_SHUFFLE:
+            with_tier(sp.tier, [&](auto tier, size_t lds) {
+                hipLaunchKernelGGL(evalh_shuffle_kernel<decltype(tier)::value>, grid, block, lds, s, pd[0], pd[1], dev.shuffle, m.cols, d_values, slots, sp.lanes);
+            });
+            break;
+        default:  // the kernel indexes the device table: this argument's programs lie where they do among the stage's
+            with_tier(sp.tier, [&](auto tier, size_t lds) {
+                hipLaunchKernelGGL(evalh_mvlookup_kernel<decltype(tier)::value>, grid, block, lds, s,
+                                   m.mv_progs + (a.first - cp.args[ST_MVLOOKUP][0].first), (uint32_t)(a.n - 1), dev.mv, m.cols, d_values, slots, sp.lanes);
+            });
+    }
     H2_CHECK(hipGetLastError());
     return 0;
 }
 
-// The constraints of `rows` rows folded into `values`, in the reference's order: the custom gates (:334-360), the permutation argument
-// (:362-441) when the system has one, then the lookups (:443-518).  The plan holds the gates program and one program per lookup, pds
-// their device forms.  Every column the kernels read is in place before the call, but for two kinds the pass asks for when their turn
-// comes: perm_ready() before the permutation kernel is queued, and next_group(i, count) before the kernel of lookup i when that lookup
-// opens a group after the first -- the caller then forms the cosets of lookups i .. i + count in the group's buffers, lk[0 .. 3 count)
-// (product, permuted input, permuted table per lookup; the first group's are there from the start).  l: l0, l_last, l_active.
-// The shuffles follow (h2hip_evalh_shuffles): programs 1 + n_lookups + 2j and + 2j + 1 of the plan are shuffle j's.  Their product cosets
-// are formed a group at a time as well, one column per shuffle in shz[0 .. sh_group); next_shuffles(first, count) is asked for every
-// group, the first included, when its turn comes.  Between the lookups and the shuffles run the mv-lookups (h2hip_evalh_mvlookups),
-// grouped the same way: mvz[2 g], mvz[2 g + 1] are the phi and m cosets of the group's g-th argument, next_mv(first, count) forms them,
-// d_mv_progs is the device table of their programs (mv_progs_put).
-template <class PermReady, class NextGroup, class NextMv, class NextShuffles>
-static int constraint_pass(Ctx* c, const CallPlan& cp, const std::vector<ProgDev>& pds, const ColsDev& cols, const PermDev& pd,
-                           const Fe* const* l, const Fe* const* lk, size_t lk_group, const ProgDev* d_mv_progs, const Fe* const* mvz,
-                           size_t mv_group, const Fe* const* shz, size_t sh_group, Fe* d_values, size_t rows, hipStream_t s,
-                           PermReady perm_ready, NextGroup next_group, NextMv next_mv, NextShuffles next_shuffles) {
+// arguments of a stage whose cosets are resident at once (a group): as many as Tuning::evalh_lookup_group_bytes hold, at least one
+static size_t stage_group(size_t n_args, size_t cosets, size_t col_bytes) {
+    if (!n_args) return 0;
+    const size_t fit = tune().evalh_lookup_group_bytes / (cosets * col_bytes);
+    return n_args <= fit ? n_args : fit ? fit : 1;
+}
+// a stage's group as a pass sees it: z[cosets * g ..] are the cosets of the group's g-th argument, `group` arguments share the buffers
+struct StageBufs {
+    const Fe* const* z;
+    size_t group;
+};
+
+// The constraints of the rows of `values` (2^cols.log_size of them), folded in the reference's order: the custom gates (:334-360), the
+// permutation argument (:362-441) when the system has one, the lookups (:443-518), then the mv-lookups (h2hip_evalh_mvlookups) and the
+// shuffles (h2hip_evalh_shuffles): the plan's first program, then the arguments of STAGES row by row.  Every column the kernels read is
+// in place before the call, but for two kinds the pass asks for when their turn comes: perm_ready() before the permutation kernel is
+// queued, and form_group(stage, first, count) before the kernel of argument `first` of a stage when that argument opens a group -- the
+// caller then forms the cosets of arguments first .. first + count in the group's buffers, which the kernels of the group before, all
+// queued by then, were the last to read.  An eager stage is not asked for its first group: those cosets are there from the start.
+template <class PermReady, class FormGroup>
+static int constraint_pass(Ctx* c, const CallPlan& cp, const PassMeta& m, const StageBufs (&bufs)[N_STAGES], Fe* d_values, hipStream_t s,
+                           PermReady perm_ready, FormGroup form_group) {
     int rc;
+    const size_t rows = (size_t)1 << m.cols.log_size;
     int t_g = c->timer_begin("evalh_gates", s);
-    if ((rc = enqueue_gates(c, cp, pds[0], cols, d_values, rows, s))) return rc;
+    if ((rc = enqueue_gates(c, cp, m.pds[0], m.cols, d_values, rows, s))) return rc;
     c->timer_end(t_g, s);
-    if (pd.n_sets) {
+    if (m.pd.n_sets) {
         if ((rc = perm_ready())) return rc;
         int t_p = c->timer_begin("evalh_perm", s);
-        hipLaunchKernelGGL(evalh_perm_kernel, dim3((uint32_t)((rows + 255) / 256)), dim3(256), 0, s, pd, cols, d_values);
+        hipLaunchKernelGGL(evalh_perm_kernel, dim3((uint32_t)((rows + 255) / 256)), dim3(256), 0, s, m.pd, m.cols, d_values);
         H2_CHECK(hipGetLastError());
         c->timer_end(t_p, s);
     }
-    const size_t n_lookups = cp.n_lookups;
-    int t_l = n_lookups ? c->timer_begin("evalh_lookups", s) : -1;
-    for (size_t i = 0; i < n_lookups; i++) {
-        const size_t gi = i % lk_group;
-        if (gi == 0 && i && (rc = next_group(i, n_lookups - i < lk_group ? n_lookups - i : lk_group))) return rc;
-        const LookupDev ld = {lk[3 * gi], lk[3 * gi + 1], lk[3 * gi + 2], l[0], l[1], l[2]};
-        if ((rc = enqueue_lookup(c, cp, i + 1, pds[i + 1], ld, cols, d_values, rows, s))) return rc;
-    }
-    c->timer_end(t_l, s);
-    const size_t n_mv = cp.mv_inputs.size();
-    for (size_t j = 0, at = 0; j < n_mv; at += cp.mv_inputs[j] + 1, j++) {
-        const size_t gj = j % mv_group;
-        if (gj == 0) {  // the group's cosets; their transforms are not the stage's own time
-            if ((rc = next_mv(j, n_mv - j < mv_group ? n_mv - j : mv_group))) return rc;
+    for (int st = 0; st < N_STAGES; st++) {
+        const std::vector<CallPlan::Arg>& args = cp.args[st];
+        const bool eager = STAGES[st].eager;
+        const size_t group = bufs[st].group;
+        int t_pass = eager && !args.empty() ? c->timer_begin(STAGES[st].profile, s) : -1;
+        for (size_t j = 0; j < args.size(); j++) {
+            const size_t g = j % group;
+            if (g == 0 && (j || !eager) && (rc = form_group(st, j, args.size() - j < group ? args.size() - j : group))) return rc;
+            int t_arg = eager ? -1 : c->timer_begin(STAGES[st].profile, s);  // the group's transforms are not the argument's own time
+            if ((rc = enqueue_argument(c, st, cp, args[j], m, bufs[st].z + STAGES[st].cosets * g, d_values, s))) return rc;
+            c->timer_end(t_arg, s);
         }
-        int t_m = c->timer_begin("evalh_mvlookups", s);
-        const MvLookupDev md = {mvz[2 * gj], mvz[2 * gj + 1], l[0], l[1], l[2]};
-        if ((rc = enqueue_mvlookup(c, cp, 1 + n_lookups + at, cp.mv_inputs[j], d_mv_progs + at, md, cols, d_values, s))) return rc;
-        c->timer_end(t_m, s);
-    }
-    for (size_t j = 0; j < cp.n_shuffles; j++) {
-        const size_t gj = j % sh_group;
-        if (gj == 0) {  // the group's cosets; their transforms are not the stage's own time
-            if ((rc = next_shuffles(j, cp.n_shuffles - j < sh_group ? cp.n_shuffles - j : sh_group))) return rc;
-        }
-        int t_s = c->timer_begin("evalh_shuffles", s);
-        const ShuffleDev sd = {shz[gj], l[0], l[1], l[2]};
-        if ((rc = enqueue_shuffle(c, cp, 1 + n_lookups + cp.n_mv_graphs + 2 * j, pds, sd, cols, d_values, s))) return rc;
-        c->timer_end(t_s, s);
+        c->timer_end(t_pass, s);
     }
     return 0;
-}
-
-// lookups whose three cosets are resident at once: as many as Tuning::evalh_lookup_group_bytes hold, at least one
-static size_t lookup_group(size_t n_lookups, size_t col_bytes) {
-    if (!n_lookups) return 0;
-    const size_t fit = tune().evalh_lookup_group_bytes / (3 * col_bytes);
-    return n_lookups <= fit ? n_lookups : fit ? fit : 1;
-}
-// ... and shuffles whose one coset is: the same bound
-static size_t shuffle_group(size_t n_shuffles, size_t col_bytes) {
-    if (!n_shuffles) return 0;
-    const size_t fit = tune().evalh_lookup_group_bytes / col_bytes;
-    return n_shuffles <= fit ? n_shuffles : fit ? fit : 1;
-}
-
-// ... and mv-lookup arguments whose two cosets (phi, m) are: the same bound
-static size_t mvlookup_group(size_t n_args, size_t col_bytes) {
-    if (!n_args) return 0;
-    const size_t fit = tune().evalh_lookup_group_bytes / (2 * col_bytes);
-    return n_args <= fit ? n_args : fit ? fit : 1;
 }
 
 // The arena every form of evaluate_h allocates behind its metadata region: the columns the engine itself keeps resident and, in the
@@ -1837,9 +1828,9 @@ static size_t mvlookup_group(size_t n_args, size_t col_bytes) {
 //               and the part's rows of `values`; host: also the coefficient columns, uploaded once, and `values`.
 //   Both forms: one product coset per shuffle of a group (h2hip_evalh_shuffles) and two cosets per mv-lookup argument of a group
 //               (h2hip_evalh_mvlookups) on top; nothing for a call without them.
+// n_args: the arguments of each stage of STAGES.
 static int evaluate_h_workspace_bytes(uint32_t k, uint32_t ek, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance, uint32_t n_perm_sets,
-                                      uint32_t n_perm_columns, uint32_t n_lookups, uint32_t n_mv, uint32_t n_shuffles, bool parts, bool dev,
-                                      size_t* bytes) {
+                                      uint32_t n_perm_columns, const size_t (&n_args)[N_STAGES], bool parts, bool dev, size_t* bytes) {
     if (!bytes) {
         set_error("evaluate_h: null argument");
         return 1;
@@ -1848,22 +1839,33 @@ static int evaluate_h_workspace_bytes(uint32_t k, uint32_t ek, uint32_t n_fixed,
         set_error("evaluate_h: bad domain (k = %u, extended_k = %u)", k, ek);
         return 1;
     }
-    const size_t col_bytes = sizeof(Fe) << ek;
+    const size_t col_bytes = sizeof(Fe) << ek, part_bytes = align256(sizeof(Fe) << k);
+    size_t group_cols = 0, stage_polys = 0;  // the cosets of one group of every stage (reused per group); every argument's polynomials
+    for (int st = 0; st < N_STAGES; st++) {
+        group_cols += STAGES[st].cosets * stage_group(n_args[st], STAGES[st].cosets, parts ? part_bytes : col_bytes);
+        stage_polys += STAGES[st].cosets * n_args[st];
+    }
     if (!parts) {
-        const size_t lk_group = lookup_group(n_lookups, col_bytes);
-        const size_t n_cols = dev ? (size_t)n_advice + n_instance + 3 * lk_group
-                                  : (size_t)n_fixed + n_advice + n_instance + 3 /* l0, l_last, l_active */ + n_perm_sets + n_perm_columns +
-                                        3 * lk_group /* lookup cosets, reused per group */ + 1 /* values */;
-        *bytes = (n_cols + 2 * mvlookup_group(n_mv, col_bytes) + shuffle_group(n_shuffles, col_bytes)) * (col_bytes + 256) + 4096;
+        const size_t n_cols = dev ? (size_t)n_advice + n_instance
+                                  : (size_t)n_fixed + n_advice + n_instance + 3 /* l0, l_last, l_active */ + n_perm_sets + n_perm_columns + 1 /* values */;
+        *bytes = (n_cols + group_cols) * (col_bytes + 256) + 4096;
         return 0;
     }
-    const size_t part_bytes = align256(sizeof(Fe) << k);
     const size_t key_and_witness = (size_t)n_fixed + n_advice + n_instance + 3 + (n_perm_sets ? (size_t)n_perm_sets + n_perm_columns : 0);
-    const size_t resident = key_and_witness + 3 * lookup_group(n_lookups, part_bytes) + 2 * mvlookup_group(n_mv, part_bytes) +
-                            shuffle_group(n_shuffles, part_bytes) + 1 /* the part's rows of values */;
-    *bytes = resident * part_bytes;
-    if (!dev) *bytes += (key_and_witness + 3 * (size_t)n_lookups + 2 * (size_t)n_mv + n_shuffles) * part_bytes + align256(col_bytes);
+    *bytes = (key_and_witness + group_cols + 1 /* the part's rows of values */) * part_bytes;
+    if (!dev) *bytes += (key_and_witness + stage_polys) * part_bytes + align256(col_bytes);
     return 0;
+}
+
+// polynomial q (of STAGES[stage].cosets) of a stage's argument j, in the order the stage's descriptor holds their cosets.  Of d only the
+// lookup tables are read: parts_as_full carries them for the parts form.
+static const uint64_t* stage_poly(int stage, size_t j, size_t q, const h2hip_evalh_desc& d, const h2hip_evalh_mvlookups* mv,
+                                  const h2hip_evalh_shuffles* sh) {
+    switch (stage) {
+        case ST_LOOKUP: return (q == 0 ? d.lookup_product_polys : q == 1 ? d.lookup_permuted_input_polys : d.lookup_permuted_table_polys)[j];
+        case ST_MVLOOKUP: return (q == 0 ? mv->phi_polys : mv->m_polys)[j];
+        default: return sh->product_polys[j];
+    }
 }
 
 // dev = false: every column pointer in `d` and `values` are host memory (the reference's Vec<F>s); values is updated in place
@@ -1880,13 +1882,17 @@ int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, const h2hip_evalh_mvlooku
     CallPlan cp;  // programs first: their slot counts size the workspaces
     if ((rc = call_plan(&d->custom_gates, d->lookup_graphs, d->n_lookups, size, &cp, sh, mv))) return rc;
     // ---- device arena: [metadata | columns the engine owns]
-    // lookup cosets: three buffers per lookup for as many lookups as 2 GB hold (a group); the first group's transforms join the advice /
-    // instance batch, later groups reuse the buffers once the kernels of the group before are queued
-    const size_t lk_group = lookup_group(d->n_lookups, col_bytes), sh_group = shuffle_group(cp.n_shuffles, col_bytes);
-    const size_t n_mv = cp.mv_inputs.size(), mv_group = mvlookup_group(n_mv, col_bytes);
+    // a stage's cosets: buffers for as many of its arguments as 2 GB hold (a group), reused once the kernels of the group before are
+    // queued; the first group of the lookups joins the advice / instance batch
+    size_t n_args[N_STAGES];
+    StageBufs bufs[N_STAGES];
+    for (int st = 0; st < N_STAGES; st++) {
+        n_args[st] = cp.args[st].size();
+        bufs[st].group = stage_group(n_args[st], STAGES[st].cosets, col_bytes);
+    }
     size_t arena_bytes;
-    if ((rc = evaluate_h_workspace_bytes(k, ek, d->n_fixed, d->n_advice, d->n_instance, d->n_perm_sets, d->n_perm_columns, d->n_lookups,
-                                         (uint32_t)n_mv, (uint32_t)cp.n_shuffles, false, dev, &arena_bytes)))
+    if ((rc = evaluate_h_workspace_bytes(k, ek, d->n_fixed, d->n_advice, d->n_instance, d->n_perm_sets, d->n_perm_columns, n_args, false, dev,
+                                         &arena_bytes)))
         return rc;
     const size_t meta_cap = evalh_meta_cap(cp, *d, 0);
     if ((rc = c->evalh_ws.ensure(meta_cap + arena_bytes))) return rc;
@@ -1938,28 +1944,27 @@ int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, const h2hip_evalh_mvlooku
     std::vector<const Fe*> z(d->n_perm_sets), pcosets(d->n_perm_sets ? d->n_perm_columns : 0);
     for (size_t i = 0; i < z.size(); i++) z[i] = place(d->perm_product_cosets[i], size, true);
     for (size_t j = 0; j < pcosets.size(); j++) pcosets[j] = place(d->perm_cosets[j], size, true);
-    std::vector<Fe*> lbuf(3 * lk_group, nullptr);
-    for (size_t t = 0; t < lbuf.size(); t++)
-        if (!(lbuf[t] = (Fe*)ar.take(col_bytes))) bad = true;
-    for (uint32_t i = 0; i < d->n_lookups; i++)
-        if (!d->lookup_product_polys[i] || !d->lookup_permuted_input_polys[i] || !d->lookup_permuted_table_polys[i]) bad = true;
-    std::vector<Fe*> mvbuf(2 * mv_group, nullptr);  // one group of mv-lookup cosets: phi, m per argument
-    for (size_t t = 0; t < mvbuf.size(); t++)
-        if (!(mvbuf[t] = (Fe*)ar.take(col_bytes))) bad = true;
-    std::vector<Fe*> shbuf(sh_group, nullptr);  // one group of shuffle product cosets
-    for (size_t t = 0; t < shbuf.size(); t++)
-        if (!(shbuf[t] = (Fe*)ar.take(col_bytes))) bad = true;
+    std::vector<Fe*> zbuf[N_STAGES];  // one group of each stage's cosets, argument by argument
+    for (int st = 0; st < N_STAGES; st++) {
+        zbuf[st].assign(STAGES[st].cosets * bufs[st].group, nullptr);
+        for (Fe*& p : zbuf[st])
+            if (!(p = (Fe*)ar.take(col_bytes))) bad = true;
+        bufs[st].z = zbuf[st].data();
+        for (size_t q = 0; q < STAGES[st].cosets * n_args[st]; q++)
+            if (!stage_poly(st, q / STAGES[st].cosets, q % STAGES[st].cosets, *d, mv, sh)) bad = true;
+    }
     if (!mb.dev_base || bad) {
         set_error("evaluate_h: null column or arena overflow");
         return 1;
     }
-    // lookups first .. first + count: their polynomials into lbuf -- queued for the transform in place (device form: read where they lie)
-    auto lookup_polys = [&](size_t first, size_t count, std::vector<const Fe*>* srcs) -> int {
-        for (size_t q = 0; q < 3 * count; q++) {
-            const size_t i = first + q / 3;
-            const uint64_t* h = q % 3 == 0 ? d->lookup_product_polys[i] : q % 3 == 1 ? d->lookup_permuted_input_polys[i] : d->lookup_permuted_table_polys[i];
+    // arguments first .. first + count of a stage: their polynomials into the stage's buffers -- queued for the transform in place
+    // (device form: read where they lie, srcs says where)
+    auto stage_polys = [&](int st, size_t first, size_t count, std::vector<const Fe*>* srcs) -> int {
+        const size_t cosets = STAGES[st].cosets;
+        for (size_t q = 0; q < cosets * count; q++) {
+            const uint64_t* h = stage_poly(st, first + q / cosets, q % cosets, *d, mv, sh);
             srcs->push_back(dev ? (const Fe*)h : nullptr);
-            if (!dev) H2_CHECK(hipMemcpyAsync(lbuf[q], h, n * sizeof(Fe), hipMemcpyHostToDevice, s));
+            if (!dev) H2_CHECK(hipMemcpyAsync(zbuf[st][q], h, n * sizeof(Fe), hipMemcpyHostToDevice, s));
         }
         return 0;
     };
@@ -1990,8 +1995,11 @@ int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, const h2hip_evalh_mvlooku
     if (!mb.host.empty() && (rc = c->stage_h2d(mb.dev_base, mb.host.data(), mb.host.size(), s))) return rc;
     for (const Upload& u : uploads)
         if (!u.late) H2_CHECK(hipMemcpyAsync(u.dst, u.src, u.elems * sizeof(Fe), hipMemcpyHostToDevice, s));
-    if ((rc = lookup_polys(0, lk_group, &poly_src))) return rc;  // the first group rides in the main batch
-    poly_dst.insert(poly_dst.end(), lbuf.begin(), lbuf.end());
+    for (int st = 0; st < N_STAGES; st++) {  // the first group of an eager stage (the lookups) rides in the main batch
+        if (!STAGES[st].eager) continue;
+        if ((rc = stage_polys(st, 0, bufs[st].group, &poly_src))) return rc;
+        poly_dst.insert(poly_dst.end(), zbuf[st].begin(), zbuf[st].end());
+    }
     // ---- cosets: advice / instance polynomials -> extended cosets (:306-323) in one batched transform: distribute_powers_zeta(into_coset)
     //      + zero-pad + NTT, as h2hip_coeff_to_extended does
     NttScale sc = NttScale::into_coset(fe_from_u64x4(d->g_coset), fe_from_u64x4(d->g_coset_inv), n);
@@ -2008,32 +2016,12 @@ int evaluate_h_host(Ctx* c, const h2hip_evalh_desc* d, const h2hip_evalh_mvlooku
         H2_CHECK(hipStreamWaitEvent(s, c->aux_events[0], 0));
         return 0;
     };
-    auto next_group = [&](size_t first, size_t count) -> int {  // the group's buffers are free: the kernels of the group before are queued
-        std::vector<const Fe*> lsrc;
-        if (int rc_up = lookup_polys(first, count, &lsrc)) return rc_up;
-        return ntt_device_batch(c, lbuf.data(), lsrc.data(), 3 * count, ext_omega, ek, &sc, s);
+    auto form_group = [&](int st, size_t first, size_t count) -> int {  // the group's buffers are free: the kernels of the group before are queued
+        std::vector<const Fe*> zsrc;
+        if (int rc_up = stage_polys(st, first, count, &zsrc)) return rc_up;
+        return ntt_device_batch(c, zbuf[st].data(), zsrc.data(), zsrc.size(), ext_omega, ek, &sc, s);
     };
-    auto next_shuffles = [&](size_t first, size_t count) -> int {  // every group, the first too: product polynomials -> extended cosets
-        std::vector<const Fe*> zsrc(count, nullptr);
-        for (size_t q = 0; q < count; q++) {
-            const uint64_t* h = sh->product_polys[first + q];
-            if (dev) zsrc[q] = (const Fe*)h;
-            else H2_CHECK(hipMemcpyAsync(shbuf[q], h, n * sizeof(Fe), hipMemcpyHostToDevice, s));
-        }
-        return ntt_device_batch(c, shbuf.data(), zsrc.data(), count, ext_omega, ek, &sc, s);
-    };
-    auto next_mv = [&](size_t first, size_t count) -> int {  // every group, the first too: phi and m polynomials -> extended cosets
-        std::vector<const Fe*> msrc(2 * count, nullptr);
-        for (size_t q = 0; q < 2 * count; q++) {
-            const uint64_t* h = q & 1 ? mv->m_polys[first + q / 2] : mv->phi_polys[first + q / 2];
-            if (dev) msrc[q] = (const Fe*)h;
-            else H2_CHECK(hipMemcpyAsync(mvbuf[q], h, n * sizeof(Fe), hipMemcpyHostToDevice, s));
-        }
-        return ntt_device_batch(c, mvbuf.data(), msrc.data(), 2 * count, ext_omega, ek, &sc, s);
-    };
-    if ((rc = constraint_pass(c, cp, pds, cols, pd, l, lbuf.data(), lk_group, d_mv_progs, mvbuf.data(), mv_group, shbuf.data(), sh_group, d_values,
-                              size, s, late_uploads, next_group, next_mv, next_shuffles)))
-        return rc;
+    if ((rc = constraint_pass(c, cp, {pds, d_mv_progs, cols, pd, l}, bufs, d_values, s, late_uploads, form_group))) return rc;
     if ((rc = guard.release())) return rc;
     if (dev) return 0;
     // ---- download
@@ -2210,15 +2198,14 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, const 
         for (uint32_t i = 0; i < d->n_perm_sets; i++) polys.push_back(d->perm_product_polys[i]);
         for (uint32_t j = 0; j < d->n_perm_columns; j++) polys.push_back(d->perm_polys[j]);
     }
-    const size_t n_main = polys.size();  // every part transforms these; the lookups follow in groups
-    for (uint32_t i = 0; i < d->n_lookups; i++)
-        polys.push_back(d->lookup_product_polys[i]), polys.push_back(d->lookup_permuted_input_polys[i]), polys.push_back(d->lookup_permuted_table_polys[i]);
-    const size_t at_mv = polys.size(), n_mv = cp.mv_inputs.size();  // the mv-lookups' phi and m polynomials, a pair each, follow the lookups'
-    for (size_t j = 0; j < n_mv; j++) polys.push_back(mv->phi_polys[j]), polys.push_back(mv->m_polys[j]);
-    const size_t at_sh = polys.size();  // the shuffles' product polynomials, one each, follow those
-    for (size_t j = 0; j < cp.n_shuffles; j++) polys.push_back(sh->product_polys[j]);
-    const size_t lk_group = lookup_group(d->n_lookups, part_bytes), sh_group = shuffle_group(cp.n_shuffles, part_bytes);
-    const size_t mv_group = mvlookup_group(n_mv, part_bytes);
+    const size_t n_main = polys.size();  // every part transforms these; the stages' polynomials follow, argument by argument, in groups
+    size_t n_args[N_STAGES], at_stage[N_STAGES], group[N_STAGES];
+    for (int st = 0; st < N_STAGES; st++) {
+        n_args[st] = cp.args[st].size();
+        at_stage[st] = polys.size();
+        for (size_t q = 0; q < STAGES[st].cosets * n_args[st]; q++) polys.push_back(stage_poly(st, q / STAGES[st].cosets, q % STAGES[st].cosets, f, mv, sh));
+        group[st] = stage_group(n_args[st], STAGES[st].cosets, part_bytes);
+    }
     const Fe ext_omega = fe_from_u64x4(d->extended_omega);
     const Fe omega = fe_pow_u64<FrP>(ext_omega, (uint64_t)1 << log_p);
     const Fe g_coset = fe_from_u64x4(d->g_coset), g_coset_inv = fe_from_u64x4(d->g_coset_inv);
@@ -2241,16 +2228,18 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, const 
         if (i < n_main) n_live_main++;
     }
     const size_t n_pinned = n_main - n_live_main;
-    const size_t n_first_cols = n_live_main + 3 * lk_group;   // what a part transforms at once: the live key and witness columns, one group of lookups
-    const size_t at_sh_cols = n_first_cols + 2 * mv_group;   // ... behind them one group of mv-lookup cosets
-    const size_t n_part_cols = at_sh_cols + sh_group;        // arena columns of one part: those, and one group of shuffle products
+    size_t cols_at[N_STAGES + 1];  // arena columns of one part: the live key and witness columns, then one group of cosets per stage
+    cols_at[0] = n_live_main;
+    for (int st = 0; st < N_STAGES; st++) cols_at[st + 1] = cols_at[st] + STAGES[st].cosets * group[st];
+    const size_t n_first_cols = cols_at[ST_LOOKUP + 1];  // what a part transforms at once: the live columns and the first group of lookups
+    const size_t n_part_cols = cols_at[N_STAGES];
     const size_t n_sets = n_pinned ? p_end - p_begin : 1;   // column-pointer tables: one set per part once a pinned column's address depends on it
     // ---- device arena: [metadata | (host form) the live coefficient columns | one part's cosets of them | the part's rows of values |
     //      (host form) values].  h2hip_evaluate_h_workspace_bytes is the upper bound, reached when nothing is pinned: a pinned column takes
     //      neither a coset slot nor, in the host form, a coefficient slot.
     size_t arena_bytes;
-    if ((rc = evaluate_h_workspace_bytes(k, ek, d->n_fixed, d->n_advice, d->n_instance, d->n_perm_sets, d->n_perm_columns, d->n_lookups,
-                                         (uint32_t)n_mv, (uint32_t)cp.n_shuffles, true, dev, &arena_bytes)))
+    if ((rc = evaluate_h_workspace_bytes(k, ek, d->n_fixed, d->n_advice, d->n_instance, d->n_perm_sets, d->n_perm_columns, n_args, true, dev,
+                                         &arena_bytes)))
         return rc;
     arena_bytes -= n_pinned * part_bytes * (dev ? 1 : 2);
     const size_t set_bytes = (8 + 256) * ((size_t)d->n_fixed + d->n_advice + d->n_instance + d->n_perm_sets + 2 * (size_t)d->n_perm_columns + 16) +
@@ -2297,13 +2286,12 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, const 
     // slot, which every part reuses; without a pin the one set serves every part
     const Fe* const* d_src = mb.put(src.data(), src.size());
     const Fe* const* d_dst = (const Fe* const*)mb.put(part_cols.data(), part_cols.size());
-    std::vector<std::vector<const Fe*>> colp(n_sets, std::vector<const Fe*>(n_main + 3 * lk_group));
+    std::vector<std::vector<const Fe*>> colp(n_sets, std::vector<const Fe*>(n_main));
     std::vector<ColsDev> cols_p(n_sets);
     std::vector<PermDev> pd_p(n_sets);
     for (size_t t = 0; t < n_sets; t++) {
         const size_t p = p_begin + t;
         for (size_t i = 0; i < n_main; i++) colp[t][i] = pin[i] ? pin[i] + p * n : part_cols[slot[i]];
-        for (size_t i = 0; i < 3 * lk_group; i++) colp[t][n_main + i] = part_cols[n_live_main + i];
         const Fe* const* col = colp[t].data();
         const Fe* const* advice = col + d->n_fixed;
         cols_p[t] = cols_put(mb, f, col, advice, advice + d->n_advice, k, 1);
@@ -2357,6 +2345,8 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, const 
         c->timer_end(t_s, s);
         return ntt_device_batch(c, part_cols.data() + to, nullptr, count, omega, k, nullptr, s);
     };
+    StageBufs bufs[N_STAGES];  // the stages' groups of cosets are the same arena columns in every part
+    for (int st = 0; st < N_STAGES; st++) bufs[st] = {part_cols.data() + cols_at[st], group[st]};
     const dim3 grid((uint32_t)((n + 255) / 256)), block(256);
     const Fe beta_zeta = d->n_perm_sets ? fe_mul<FrP>(fe_from_u64x4(d->beta), fe_from_u64x4(d->zeta)) : fe_zero<FrP>();
     for (uint32_t p = p_begin; p < p_end; p++) {
@@ -2373,14 +2363,13 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, const 
         hipLaunchKernelGGL(evalh_part_gather_kernel, grid, block, 0, s, (const Fe*)d_values, d_part, k, log_p, p);
         H2_CHECK(hipGetLastError());
         c->timer_end(t_io, s);
-        // ---- the pass, over the part's rows: nothing of the permutation's arrives late here, and a later group of lookups is
-        //      scaled and transformed into the group's buffers as the first was
+        // ---- the pass, over the part's rows: nothing of the permutation's arrives late here, and a group of a stage's arguments is
+        //      scaled and transformed into the stage's buffers as the first group of lookups was
         if (d->n_perm_sets) pd.delta_start = to_i(fe_mul<FrP>(beta_zeta, fe_pow_u64<FrP>(ext_omega, p)));  // beta g_p; the kernel multiplies by omega^j
-        if ((rc = constraint_pass(c, cp, pds, cols_p[t], pd, col + at_l0, col + n_main, lk_group, d_mv_progs, part_cols.data() + n_first_cols,
-                                  mv_group, part_cols.data() + at_sh_cols, sh_group, d_part, n, s, [] { return 0; },
-                                  [&](size_t first, size_t count) { return to_part(p, n_live_main + 3 * first, n_live_main, 3 * count); },
-                                  [&](size_t first, size_t count) { return to_part(p, slot[at_mv] + 2 * first, n_first_cols, 2 * count); },
-                                  [&](size_t first, size_t count) { return to_part(p, slot[at_sh] + first, at_sh_cols, count); })))
+        if ((rc = constraint_pass(c, cp, {pds, d_mv_progs, cols_p[t], pd, col + at_l0}, bufs, d_part, s, [] { return 0; },
+                                  [&](int st, size_t first, size_t count) {  // a stage's live columns lie in the order of its arguments
+                                      return to_part(p, slot[at_stage[st]] + STAGES[st].cosets * first, cols_at[st], STAGES[st].cosets * count);
+                                  })))
             return rc;
         // ---- scatter
         t_io = c->timer_begin("evalh_part_io", s);
@@ -2414,11 +2403,6 @@ __global__ void __launch_bounds__(256) lookup_compress_kernel(const ProgDev* pro
     }
 }
 
-static bool compress_vs_allowed(const h2hip_value_source& v, bool theta) {
-    return v.kind != H2HIP_VS_BETA && v.kind != H2HIP_VS_GAMMA && v.kind != H2HIP_VS_Y && v.kind != H2HIP_VS_PREVIOUS &&
-           (theta || v.kind != H2HIP_VS_THETA);
-}
-
 // graphs the interpreter runs over Lagrange rows: `theta`: the compression's graphs may read theta, a gate polynomial's may not
 static int row_graphs_validate(const char* what, bool theta, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance, uint32_t n_challenges,
                                const h2hip_graph* graphs, size_t n_graphs) {
@@ -2436,20 +2420,13 @@ static int row_graphs_validate(const char* what, bool theta, uint32_t n_fixed, u
     d.n_advice = n_advice;
     d.n_instance = n_instance;
     d.n_challenges = n_challenges;
+    const uint32_t barred = VS_BIT(BETA) | VS_BIT(GAMMA) | VS_BIT(Y) | VS_BIT(PREVIOUS) | (theta ? 0 : VS_BIT(THETA));
+    uint32_t q;
     for (size_t i = 0; i < n_graphs; i++) {
-        const h2hip_graph& g = graphs[i];
-        if (graph_validate(g, d, theta ? "lookup compression" : "gate check")) return H2HIP_EINVAL;
-        for (uint32_t q = 0; q < g.n_calculations; q++) {
-            const h2hip_calculation& cl = g.calculations[q];
-            bool ok = compress_vs_allowed(cl.x, theta);
-            if (cl.op == H2HIP_CALC_ADD || cl.op == H2HIP_CALC_SUB || cl.op == H2HIP_CALC_MUL || cl.op == H2HIP_CALC_HORNER)
-                ok = ok && compress_vs_allowed(cl.y, theta);
-            if (cl.op == H2HIP_CALC_HORNER)
-                for (uint32_t t = 0; ok && t < cl.parts_count; t++) ok = compress_vs_allowed(g.parts[cl.parts_offset + t], theta);
-            if (!ok) {
-                set_error("%s: graph %zu, calculation %u reads beta, gamma, %sy or the previous value", what, i, q, theta ? "" : "theta, ");
-                return H2HIP_EINVAL;
-            }
+        if (graph_validate(graphs[i], d, theta ? "lookup compression" : "gate check")) return H2HIP_EINVAL;
+        if (!graph_reads_only(graphs[i], ~barred, &q)) {
+            set_error("%s: graph %zu, calculation %u reads beta, gamma, %sy or the previous value", what, i, q, theta ? "" : "theta, ");
+            return H2HIP_EINVAL;
         }
     }
     return 0;
@@ -2658,8 +2635,9 @@ int h2hip_evaluate_h_parts_bn254_device(const h2hip_evalh_parts_desc* desc, void
 int h2hip_evaluate_h_ext_workspace_bytes(uint32_t k, uint32_t extended_k, uint32_t n_fixed, uint32_t n_advice, uint32_t n_instance,
                                          uint32_t n_perm_sets, uint32_t n_perm_columns, uint32_t n_lookups, uint32_t n_mvlookups,
                                          uint32_t n_shuffles, int parts_form, int device_form, size_t* bytes) {
-    return evaluate_h_workspace_bytes(k, extended_k, n_fixed, n_advice, n_instance, n_perm_sets, n_perm_columns, n_lookups, n_mvlookups,
-                                      n_shuffles, parts_form != 0, device_form != 0, bytes)
+    const size_t n_args[N_STAGES] = {n_lookups, n_mvlookups, n_shuffles};  // in the order of STAGES
+    return evaluate_h_workspace_bytes(k, extended_k, n_fixed, n_advice, n_instance, n_perm_sets, n_perm_columns, n_args, parts_form != 0,
+                                      device_form != 0, bytes)
                ? H2HIP_EINVAL
                : 0;
 }

@@ -429,6 +429,50 @@ def test_gpu_more_arguments_than_a_coset_group(h2, oracle, entry):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("entry", ENTRIES)
+def test_gpu_a_coset_group_with_a_remainder(h2, oracle, entry):
+    """group bytes of four columns of the form under test: the three mv-lookup arguments (two cosets each) run as a group of two and a
+    group of one, the two shuffles (one coset each) share a group and the lookup (three cosets) is a group of one"""
+    h2.init()
+    sy = _system(oracle, 4, 5, 417, "with_all", 3)
+    want = _want(h2, oracle, sy)
+    column = 32 << (5 if entry.startswith("parts") else 7)
+    L = h2.lib()
+    L.h2hip_debug_set_evalh_lookup_group_bytes(ctypes.c_uint64(4 * column))
+    try:
+        got = _run(h2, sy, entry, sy.vin)
+    finally:
+        L.h2hip_debug_set_evalh_lookup_group_bytes(ctypes.c_uint64(0))
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.gpu
+def test_gpu_profile_intervals_per_stage(h2, oracle):
+    """the intervals the bench tools divide: one of the gates, the permutation and the lookups per pass (the lookups' holds the transforms
+    of their later groups), one per mv-lookup argument and per shuffle (the transforms of their groups excluded); a pass per call in the
+    full form and per part (P = 4) in the parts form, whatever the grouping"""
+    h2.init()
+    sy = _system(oracle, 4, 5, 417, "with_all", 3)
+    want = _want(h2, oracle, sy)
+    stages = ("evalh_gates", "evalh_perm", "evalh_lookups", "evalh_mvlookups", "evalh_shuffles")
+    L = h2.lib()
+    h2.profile_enable(True)
+    try:
+        for entry, passes in (("full_host", 1), ("parts_host", 4)):
+            for group_bytes in (0, 1):
+                L.h2hip_debug_set_evalh_lookup_group_bytes(ctypes.c_uint64(group_bytes))
+                h2.profile_reset()
+                assert np.array_equal(_run(h2, sy, entry, sy.vin), want)
+                counts = [h2.profile_get(stage)[1] for stage in stages]
+                print(entry, group_bytes, counts)
+                assert counts == [passes, passes, passes, 3 * passes, 2 * passes], (entry, group_bytes)
+    finally:
+        L.h2hip_debug_set_evalh_lookup_group_bytes(ctypes.c_uint64(0))
+        h2.profile_enable(False)
+        h2.profile_reset()
+
+
+@pytest.mark.gpu
 def test_gpu_two_instances_then_t_evaluations(h2, oracle):
     """two circuit instances chained through values in both forms; t_evaluations on the last call of the parts form, applied after every
     stage, gives divide_by_vanishing_poly of the two-instance h"""
