@@ -1092,15 +1092,29 @@ def _fr_vanishing(roots, z):
     return acc
 
 
+def _combine_any(polys, scalars, sub=None, roots=(), scale=None, out=None, accumulate=False):
+    """poly_combine for host columns, poly_combine_device for torch CUDA tensors (the result a new (L - len(roots), 4) tensor unless
+    `out` is given): what lets the multiopen compositions below serve a prover whose polynomials live in HBM"""
+    if isinstance(polys[0], np.ndarray):
+        return poly_combine(polys, scalars, sub=sub, roots=roots, scale=scale, out=out, accumulate=accumulate)
+    import torch
+    if out is None:
+        L = polys[0].numel() * polys[0].element_size() // 32
+        out = torch.zeros((max(0, L - len(roots)), 4), dtype=torch.int64, device=polys[0].device)
+    poly_combine_device(polys, scalars, out, sub=sub, roots=roots, scale=scale, accumulate=accumulate)
+    return out
+
+
 def gwc_witnesses(polys, point_groups, v):
     """GWC's witness polynomials (poly/kzg/multiopen/gwc/prover.rs:61-89), one per point, as (n - 1, 4) arrays.  point_groups is
-    construct_intermediate_sets' output in order: a list of (point, [(poly index, eval), ...]); evals and challenges are Montgomery limbs."""
+    construct_intermediate_sets' output in order: a list of (point, [(poly index, eval), ...]); evals and challenges are Montgomery limbs.
+    polys: numpy arrays, or torch CUDA tensors (the witnesses are then tensors too, queued on the current stream)."""
     vv = fr_to_int(v)
     out = []
     for point, queries in point_groups:
         pw = _fr_powers(vv, len(queries))
         ev = sum(pw[i] * fr_to_int(e) for i, (_, e) in enumerate(queries)) % FR_MODULUS
-        out.append(poly_combine([polys[j] for j, _ in queries], [fr_from_int(x) for x in pw], sub=[fr_from_int(ev)], roots=[point]))
+        out.append(_combine_any([polys[j] for j, _ in queries], [fr_from_int(x) for x in pw], sub=[fr_from_int(ev)], roots=[point]))
     return out
 
 
@@ -1116,14 +1130,18 @@ def _shplonk_sets(rotation_sets):
 
 def shplonk_h(polys, rotation_sets, y, v):
     """SHPLONK's first quotient h_x (shplonk/prover.rs:138-203): rotation_sets in construct_intermediate_sets' order, each
-    (points, [(poly index, [eval at each point]), ...]); polys are (n, 4) coefficient arrays.  Returns h_x, (n, 4)."""
+    (points, [(poly index, [eval at each point]), ...]); polys are (n, 4) coefficient arrays, or torch CUDA tensors.  Returns h_x, (n, 4)."""
     yy, vv = fr_to_int(y), fr_to_int(v)
     n = polys[0].shape[0]
-    h = np.zeros((n, 4), dtype=np.uint64)
+    if isinstance(polys[0], np.ndarray):
+        h = np.zeros((n, 4), dtype=np.uint64)
+    else:
+        import torch
+        h = torch.zeros((n, 4), dtype=torch.int64, device=polys[0].device)
     for i, (pts, coms, interp) in enumerate(_shplonk_sets(rotation_sets)):
         py = _fr_powers(yy, len(coms))
         sub = [sum(py[c] * interp[c][t] for c in range(len(coms))) % FR_MODULUS for t in range(len(pts))]
-        poly_combine([polys[j] for j, _ in coms], [fr_from_int(x) for x in py], sub=[fr_from_int(x) for x in sub],
+        _combine_any([polys[j] for j, _ in coms], [fr_from_int(x) for x in py], sub=[fr_from_int(x) for x in sub],
                      roots=[fr_from_int(x) for x in pts], scale=fr_from_int(pow(vv, i, FR_MODULUS)), out=h, accumulate=i > 0)
     return h
 
@@ -1151,7 +1169,7 @@ def shplonk_final(polys, rotation_sets, h_x, y, v, u):
             const = (const + w * _fr_eval(interp[c], uu)) % p
     cols.append(h_x)
     scal.append(-_fr_vanishing(super_set, uu) % p)
-    return poly_combine(cols, [fr_from_int(x) for x in scal], sub=[fr_from_int(const)], roots=[u], scale=fr_from_int(pow(z0, -1, p)))
+    return _combine_any(cols, [fr_from_int(x) for x in scal], sub=[fr_from_int(const)], roots=[u], scale=fr_from_int(pow(z0, -1, p)))
 
 
 

@@ -12,6 +12,8 @@
                    replaced the permuted-column lookup, also later than the reference (h2hip_evalh_mvlookups; the header's definitions)
   EvalhPartsDesc / PartsDescHolder / Evaluator.evaluate_h_parts    the same one coset of the 2^k domain at a time, every column given
                    as a polynomial of 2^k coefficients (h2hip_evaluate_h_parts_bn254[_device])
+  DeviceDescHolder / DevicePartsDescHolder / Evaluator.evaluate_h_device / evaluate_h_parts_device    the same calls over columns that
+                   are torch CUDA tensors, queued on a stream (the _device entry points)
 
 Expression trees are tuples:  ('const', int) ('fixed', col, rot) ('advice', col, rot) ('instance', col, rot)
 ('challenge', i) ('neg', e) ('sum', e, e) ('prod', e, e) ('scaled', e, int)   (plonk/circuit.rs Expression).
@@ -310,11 +312,26 @@ def _ptr(a):
     return a.ctypes.data if a is not None and a.size else None
 
 
+def _column(a, keep, device):
+    """the address of one column for a descriptor, the column appended to `keep`: a contiguous uint64 numpy array for the host forms, a
+    contiguous torch CUDA tensor for the _device forms -- never the other, since the engine would read a host address as HBM"""
+    if device:
+        if not (hasattr(a, "data_ptr") and a.is_cuda and a.is_contiguous()):
+            raise TypeError("a _device form takes contiguous torch CUDA tensors for its columns")
+        keep.append(a)
+        return a.data_ptr() if a.numel() else None
+    if hasattr(a, "data_ptr"):
+        raise TypeError("a host form takes numpy columns; use the _device form for torch tensors")
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    keep.append(a)
+    return _ptr(a)
+
+
 class MvLookupsHolder:
     """Builds an h2hip_evalh_mvlookups from [(flattened graphs: K inputs then the table, phi polynomial, m polynomial)] and keeps every
     buffer alive; byref() of an empty list is NULL, the call without mv-lookups"""
 
-    def __init__(self, arguments):
+    def __init__(self, arguments, device=False):
         self.keep = []
         s = EvalhMvLookups()
         s.n_args = len(arguments)
@@ -326,11 +343,11 @@ class MvLookupsHolder:
             for g in gs:
                 graphs[at] = graph_struct(g, self.keep)
                 at += 1
-            phis.append(np.ascontiguousarray(phi, dtype=np.uint64))
-            ms.append(np.ascontiguousarray(m, dtype=np.uint64))
-        t_phi = (ctypes.c_void_p * max(1, len(phis)))(*[a.ctypes.data for a in phis])
-        t_m = (ctypes.c_void_p * max(1, len(ms)))(*[a.ctypes.data for a in ms])
-        self.keep += [graphs, n_inputs, phis, ms, t_phi, t_m]
+            phis.append(_column(phi, self.keep, device))
+            ms.append(_column(m, self.keep, device))
+        t_phi = (ctypes.c_void_p * max(1, len(phis)))(*phis)
+        t_m = (ctypes.c_void_p * max(1, len(ms)))(*ms)
+        self.keep += [graphs, n_inputs, t_phi, t_m]
         s.n_inputs, s.graphs = n_inputs.ctypes.data, ctypes.addressof(graphs)
         s.phi_polys, s.m_polys = ctypes.addressof(t_phi), ctypes.addressof(t_m)
         self.desc = s
@@ -343,7 +360,7 @@ class ShufflesHolder:
     """Builds an h2hip_evalh_shuffles from [(flattened input graph, flattened shuffle graph, product polynomial (2^k, 4) u64)] and keeps
     every buffer alive; byref() of an empty list is NULL, the call without shuffles"""
 
-    def __init__(self, shuffles):
+    def __init__(self, shuffles, device=False):
         self.keep = []
         s = EvalhShuffles()
         s.n_shuffles = len(shuffles)
@@ -352,9 +369,9 @@ class ShufflesHolder:
         for j, (g_in, g_sh, poly) in enumerate(shuffles):
             graphs[2 * j] = graph_struct(g_in, self.keep)
             graphs[2 * j + 1] = graph_struct(g_sh, self.keep)
-            polys.append(np.ascontiguousarray(poly, dtype=np.uint64))
-        table = (ctypes.c_void_p * max(1, len(polys)))(*[a.ctypes.data for a in polys])
-        self.keep += [graphs, polys, table]
+            polys.append(_column(poly, self.keep, device))
+        table = (ctypes.c_void_p * max(1, len(polys)))(*polys)
+        self.keep += [graphs, table]
         s.graphs, s.product_polys = ctypes.addressof(graphs), ctypes.addressof(table)
         self.desc = s
 
@@ -371,6 +388,8 @@ class DescHolder:
     perm_product_cosets (ns, size, 4), perm_column_kind / perm_column_index u32, perm_cosets (ncols, size, 4), chunk_len, last_rotation;
     lookups: list of (graph dict, product_poly, permuted_input_poly, permuted_table_poly)"""
 
+    device = False  # DeviceDescHolder: the columns are torch CUDA tensors
+
     def __init__(self, case):
         self.keep = []
         d = EvalhDesc()
@@ -378,7 +397,7 @@ class DescHolder:
         d.k, d.extended_k = int(case["k"]), int(case["extended_k"])
         for f in ("extended_omega", "g_coset", "g_coset_inv", "y", "beta", "gamma", "theta", "zeta", "delta"):
             setattr(d, f, _ptr(c(case[f])))
-        d.l0, d.l_last, d.l_active_row = _ptr(c(case["l0"])), _ptr(c(case["l_last"])), _ptr(c(case["l_active_row"]))
+        d.l0, d.l_last, d.l_active_row = (_column(case[f], self.keep, self.device) for f in ("l0", "l_last", "l_active_row"))
         d.n_fixed, d.fixed_cosets = self._ptr_array(case["fixed_cosets"])
         d.n_advice, d.advice_polys = self._ptr_array(case["advice_polys"])
         d.n_instance, d.instance_polys = self._ptr_array(case["instance_polys"])
@@ -408,9 +427,9 @@ class DescHolder:
         return a
 
     def _ptr_array(self, arrs):
-        arrs = [self._c(a) for a in arrs]
-        n = len(arrs)
-        p = (ctypes.c_void_p * max(1, n))(*[a.ctypes.data for a in arrs])
+        addrs = [_column(a, self.keep, self.device) for a in arrs]
+        n = len(addrs)
+        p = (ctypes.c_void_p * max(1, n))(*addrs)
         self.keep.append(p)
         return n, ctypes.addressof(p)
 
@@ -451,6 +470,17 @@ class PartsDescHolder(DescHolder):
         t = case.get("t_evaluations")
         d.t_evaluations = None if t is None else _ptr(self._c(t))
         self.desc = d
+
+
+class DeviceDescHolder(DescHolder):
+    """DescHolder for h2hip_evaluate_h_bn254_device: the same case with torch CUDA tensors in place of the numpy columns (the scalars,
+    challenges, graphs and pointer tables stay host memory); the tensors are kept alive with the tables"""
+    device = True
+
+
+class DevicePartsDescHolder(PartsDescHolder):
+    """PartsDescHolder for h2hip_evaluate_h_parts_bn254_device; t_evaluations stays a host array"""
+    device = True
 
 
 def evaluate_h_workspace_bytes(k, extended_k, n_fixed, n_advice, n_instance, n_perm_sets, n_perm_columns, n_lookups, parts_form, device_form):
@@ -532,7 +562,7 @@ class Evaluator:
         return cls(custom_gates_graph(list(gate_polys)), [lookup_graph(i, t) for i, t in lookup_arguments],
                    [shuffle_graphs(i, s) for i, s in shuffle_arguments], [mvlookup_graphs(i, t) for i, t in mvlookup_arguments])
 
-    def describe_mvlookups(self, case):
+    def describe_mvlookups(self, case, device=False):
         """the mv-lookup stage of a call: case["mvlookups"], when present, holds one (phi polynomial, m polynomial) pair of (2^k, 4) u64
         per mv-lookup argument of this Evaluator, in order.  None: the case has no such entry."""
         polys = case.get("mvlookups")
@@ -540,9 +570,9 @@ class Evaluator:
             return None
         if len(polys) != len(self.mv_lookups):
             raise ValueError("mvlookups: expected %d (phi, m) pairs, got %d" % (len(self.mv_lookups), len(polys)))
-        return MvLookupsHolder([([flatten_graph(g) for g in gs], phi, m) for gs, (phi, m) in zip(self.mv_lookups, polys)])
+        return MvLookupsHolder([([flatten_graph(g) for g in gs], phi, m) for gs, (phi, m) in zip(self.mv_lookups, polys)], device)
 
-    def describe_shuffles(self, case):
+    def describe_shuffles(self, case, device=False):
         """the shuffle stage of a call: case["shuffles"], when present, holds one product polynomial (2^k, 4) u64 per shuffle of this
         Evaluator, in order.  None: the case has no such entry and the call is the one without shuffles."""
         polys = case.get("shuffles")
@@ -550,21 +580,73 @@ class Evaluator:
             return None
         if len(polys) != len(self.shuffles):
             raise ValueError("shuffles: expected %d product polynomials, got %d" % (len(self.shuffles), len(polys)))
-        return ShufflesHolder([(flatten_graph(gi), flatten_graph(gs), z) for (gi, gs), z in zip(self.shuffles, polys)])
+        return ShufflesHolder([(flatten_graph(gi), flatten_graph(gs), z) for (gi, gs), z in zip(self.shuffles, polys)], device)
 
-    def describe(self, case):
-        """case as for DescHolder minus `custom` and the graphs inside `lookups` (3-tuples of polynomials there)"""
+    def describe(self, case, device=False):
+        """case as for DescHolder minus `custom` and the graphs inside `lookups` (3-tuples of polynomials there); device: the columns
+        are torch CUDA tensors (DeviceDescHolder)"""
         full = dict(case)
         full["custom"] = flatten_graph(self.custom_gates)
         full["lookups"] = [(flatten_graph(g), *polys) for g, polys in zip(self.lookups, case["lookups"])]
-        return DescHolder(full)
+        return DeviceDescHolder(full) if device else DescHolder(full)
 
-    def describe_parts(self, case):
+    def describe_parts(self, case, device=False):
         """case as for PartsDescHolder minus `custom` and the graphs inside `lookups`"""
         full = dict(case)
         full["custom"] = flatten_graph(self.custom_gates)
         full["lookups"] = [(flatten_graph(g), *polys) for g, polys in zip(self.lookups, case["lookups"])]
-        return PartsDescHolder(full)
+        return DevicePartsDescHolder(full) if device else PartsDescHolder(full)
+
+    @staticmethod
+    def _device_values(d_values, extended_k, stream):
+        import torch
+        if not (hasattr(d_values, "data_ptr") and d_values.is_cuda and d_values.is_contiguous()):
+            raise TypeError("d_values: a contiguous torch CUDA tensor")
+        if d_values.numel() * d_values.element_size() != 32 << int(extended_k):
+            raise ValueError("d_values: expected 2^extended_k elements of 32 bytes")
+        s = torch.cuda.current_stream().cuda_stream if stream is None else getattr(stream, "cuda_stream", stream)
+        return ctypes.c_void_p(d_values.data_ptr()), ctypes.c_void_p(s)
+
+    def evaluate_h_device(self, case, d_values, stream=None):
+        """evaluate_h with every column resident in HBM: `case` has evaluate_h's keys with torch CUDA tensors (n x 32 B each) in place
+        of the numpy columns, d_values (2^extended_k x 32 B) is folded in place.  The kernels are queued on `stream` (a torch stream or
+        a raw handle; None: the current stream) and not waited for; the holder keeps the tensors and pointer tables alive until the
+        call has returned, and the caller keeps the tensors until the stream has passed the call."""
+        from . import _check, lib
+        h = self.describe(case, device=True)
+        pv, ps = self._device_values(d_values, case["extended_k"], stream)
+        sh, mv = self.describe_shuffles(case, True), self.describe_mvlookups(case, True)
+        if mv is not None:
+            _check(lib().h2hip_evaluate_h_ext_bn254_device(h.byref(), mv.byref(), sh.byref() if sh is not None else None, pv, ps),
+                   "evaluate_h_ext_device")
+        elif sh is not None:
+            _check(lib().h2hip_evaluate_h_shuffles_bn254_device(h.byref(), sh.byref(), pv, ps), "evaluate_h_shuffles_device")
+        else:
+            _check(lib().h2hip_evaluate_h_bn254_device(h.byref(), pv, ps), "evaluate_h_device")
+        del h, sh, mv
+        return d_values
+
+    def evaluate_h_parts_device(self, case, d_values, parts=None, t_evaluations=None, stream=None):
+        """evaluate_h_parts with every coefficient-form column resident in HBM (torch CUDA tensors under evaluate_h_parts' keys);
+        parts and t_evaluations (a host array) as there.  Queued on `stream`, not waited for."""
+        from . import _check, lib
+        full = dict(case)
+        if parts is not None:
+            full["part_begin"], full["part_count"] = parts
+        if t_evaluations is not None:
+            full["t_evaluations"] = t_evaluations
+        h = self.describe_parts(full, device=True)
+        pv, ps = self._device_values(d_values, case["extended_k"], stream)
+        sh, mv = self.describe_shuffles(case, True), self.describe_mvlookups(case, True)
+        if mv is not None:
+            _check(lib().h2hip_evaluate_h_parts_ext_bn254_device(h.byref(), mv.byref(), sh.byref() if sh is not None else None, pv, ps),
+                   "evaluate_h_parts_ext_device")
+        elif sh is not None:
+            _check(lib().h2hip_evaluate_h_parts_shuffles_bn254_device(h.byref(), sh.byref(), pv, ps), "evaluate_h_parts_shuffles_device")
+        else:
+            _check(lib().h2hip_evaluate_h_parts_bn254_device(h.byref(), pv, ps), "evaluate_h_parts_device")
+        del h, sh, mv
+        return d_values
 
     def evaluate_h_parts(self, case, values, parts=None, t_evaluations=None):
         """evaluate_h for one circuit instance, one coset of the 2^k domain at a time, from coefficient-form columns: values
