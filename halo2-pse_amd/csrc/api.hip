@@ -900,26 +900,20 @@ static void release_ctx(Ctx* c) {
     c->ntt_ptrs.release();
     c->gather.release();
     c->gen_table.release();
+    c->host_io.release();
     c->prod_ws.release();
-    c->prod_io.release();
     c->mvsum_ws.release();
     c->open_ws.release();
     c->open_io.release();
     c->lookup_ws.release();
-    c->lookup_io.release();
     c->lookup_flag.release();
     c->keygen_ws.release();
-    c->keygen_io.release();
     c->keygen_flag.release();
     c->check_ws.release();
-    c->check_io.release();
     c->check_flag.release();
     c->copies_ws.release();
-    c->copies_io.release();
     c->copies_flag.release();
     c->serde_ws.release();
-    c->serde_io.release();
-    c->random_io.release();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     c->stream = nullptr;
     for (auto e : c->aux_events) (void)hipEventDestroy(e);

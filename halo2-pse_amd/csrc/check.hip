@@ -335,34 +335,6 @@ static int check_shuffles_device(Ctx* c, uint32_t k, const Fe* const* in, const 
     return 0;
 }
 
-// The host forms' columns: one pinned with h2hip_columns_pin is read where it lies, the others are uploaded into check_io on s.
-// check_io is not one of the shared workspaces the WsGuard orders: only the host forms touch it, always on the engine's own stream, and
-// each of them synchronises that stream before it returns (and holds the context's lock until then), so its uploads are queued ahead
-// of the guard without a second user to order against.  Everything the _device forms share with other calls is under the guard.
-struct CkUpload {
-    Ctx* c;
-    hipStream_t s;
-    size_t n;
-    std::vector<std::pair<const uint64_t*, const Fe**>> todo;
-    void want(const uint64_t* h, const Fe** d) {
-        *d = pinned_column_lookup(c, h, n);
-        if (!*d) todo.push_back({h, d});
-    }
-    // `more` bytes follow the columns in check_io; *tail points at them
-    int run(size_t more, char** tail) {
-        const size_t bytes = n * sizeof(Fe);
-        int rc = c->check_io.ensure(todo.size() * bytes + more);
-        if (rc) return rc;
-        char* io = (char*)c->check_io.p;
-        for (size_t q = 0; q < todo.size(); q++) {
-            H2_CHECK(hipMemcpyAsync(io + q * bytes, todo[q].first, bytes, hipMemcpyHostToDevice, s));
-            *todo[q].second = (const Fe*)(io + q * bytes);
-        }
-        if (tail) *tail = io + todo.size() * bytes;
-        return 0;
-    }
-};
-
 }  // namespace h2
 
 using namespace h2;
@@ -428,13 +400,16 @@ int h2hip_check_gates_bn254(uint32_t k, const uint64_t* const* fixed_values, uin
     if (en.rc) return en.rc;
     Ctx* c = en.c;
     std::vector<const Fe*> d_fixed(n_fixed), d_advice(n_advice), d_instance(n_instance);
-    CkUpload up{c, c->stream, (size_t)1 << k, {}};
-    for (uint32_t j = 0; j < n_fixed; j++) up.want(fixed_values[j], &d_fixed[j]);
-    for (uint32_t j = 0; j < n_advice; j++) up.want(advice_values[j], &d_advice[j]);
-    for (uint32_t j = 0; j < n_instance; j++) up.want(instance_values[j], &d_instance[j]);
-    if (int rc = up.run(0, nullptr)) return rc;
-    return check_gates_device(c, k, d_fixed.data(), n_fixed, d_advice.data(), n_advice, d_instance.data(), n_instance, challenges, n_challenges,
-                              graphs, n_graphs, max_rows, counts, rows, c->stream);
+    const size_t bytes = sizeof(Fe) << k;
+    HostIo io(c, c->host_io, c->stream);  // the host forms' columns: one pinned with h2hip_columns_pin is read where it lies
+    for (uint32_t j = 0; j < n_fixed; j++) io.in(fixed_values[j], bytes, &d_fixed[j], true);
+    for (uint32_t j = 0; j < n_advice; j++) io.in(advice_values[j], bytes, &d_advice[j], true);
+    for (uint32_t j = 0; j < n_instance; j++) io.in(instance_values[j], bytes, &d_instance[j], true);
+    if (int rc = io.upload()) return rc;
+    if (int rc = check_gates_device(c, k, d_fixed.data(), n_fixed, d_advice.data(), n_advice, d_instance.data(), n_instance, challenges,
+                                    n_challenges, graphs, n_graphs, max_rows, counts, rows, c->stream))
+        return rc;
+    return io.finish();
 }
 
 static int ck_perm_check(uint32_t k, const void* const* columns, const void* const* mapping, uint32_t m, uint32_t max_rows, const uint64_t* counts,
@@ -477,16 +452,12 @@ int h2hip_check_permutation_bn254(uint32_t k, const uint64_t* const* columns, co
     hipStream_t s = c->stream;
     std::vector<const Fe*> d_cols(n_columns);
     std::vector<const uint32_t*> d_maps(n_columns);
-    CkUpload up{c, s, n, {}};
-    for (uint32_t j = 0; j < n_columns; j++) up.want(columns[j], &d_cols[j]);
-    const size_t map_b = n * 8;
-    char* tail = nullptr;
-    if (int rc = up.run(n_columns * map_b, &tail)) return rc;
-    for (uint32_t j = 0; j < n_columns; j++) {
-        H2_CHECK(hipMemcpyAsync(tail + j * map_b, mapping[j], map_b, hipMemcpyHostToDevice, s));
-        d_maps[j] = (const uint32_t*)(tail + j * map_b);
-    }
-    return check_permutation_device(c, k, d_cols.data(), d_maps.data(), n_columns, max_rows, counts, rows, s);
+    HostIo io(c, c->host_io, s);
+    for (uint32_t j = 0; j < n_columns; j++) io.in(columns[j], n * sizeof(Fe), &d_cols[j], true);
+    for (uint32_t j = 0; j < n_columns; j++) io.in(mapping[j], n * 8, &d_maps[j]);  // the mapping follows the columns
+    if (int rc = io.upload()) return rc;
+    if (int rc = check_permutation_device(c, k, d_cols.data(), d_maps.data(), n_columns, max_rows, counts, rows, s)) return rc;
+    return io.finish();
 }
 
 static int ck_lookups_check(uint32_t k, const void* const* in, const void* const* tab, size_t count, uint32_t bf, uint32_t max_rows,
@@ -522,13 +493,14 @@ int h2hip_check_lookups_bn254(uint32_t k, const uint64_t* const* compressed_inpu
     if (en.rc) return en.rc;
     Ctx* c = en.c;
     std::vector<const Fe*> d_in(count), d_tab(count);
-    CkUpload up{c, c->stream, (size_t)1 << k, {}};
+    HostIo io(c, c->host_io, c->stream);
     for (size_t j = 0; j < count; j++) {
-        up.want(compressed_input[j], &d_in[j]);
-        up.want(compressed_table[j], &d_tab[j]);
+        io.in(compressed_input[j], sizeof(Fe) << k, &d_in[j], true);
+        io.in(compressed_table[j], sizeof(Fe) << k, &d_tab[j], true);
     }
-    if (int rc = up.run(0, nullptr)) return rc;
-    return check_lookups_device(c, k, d_in.data(), d_tab.data(), count, blinding_factors, max_rows, counts, rows, c->stream);
+    if (int rc = io.upload()) return rc;
+    if (int rc = check_lookups_device(c, k, d_in.data(), d_tab.data(), count, blinding_factors, max_rows, counts, rows, c->stream)) return rc;
+    return io.finish();
 }
 
 static int ck_shuffles_check(uint32_t k, const void* const* in, const void* const* sh, size_t count, uint32_t bf, uint32_t max_rows,
@@ -564,13 +536,14 @@ int h2hip_check_shuffles_bn254(uint32_t k, const uint64_t* const* compressed_inp
     if (en.rc) return en.rc;
     Ctx* c = en.c;
     std::vector<const Fe*> d_in(count), d_sh(count);
-    CkUpload up{c, c->stream, (size_t)1 << k, {}};
+    HostIo io(c, c->host_io, c->stream);
     for (size_t j = 0; j < count; j++) {
-        up.want(compressed_input[j], &d_in[j]);
-        up.want(compressed_shuffle[j], &d_sh[j]);
+        io.in(compressed_input[j], sizeof(Fe) << k, &d_in[j], true);
+        io.in(compressed_shuffle[j], sizeof(Fe) << k, &d_sh[j], true);
     }
-    if (int rc = up.run(0, nullptr)) return rc;
-    return check_shuffles_device(c, k, d_in.data(), d_sh.data(), count, blinding_factors, max_rows, counts, rows, c->stream);
+    if (int rc = io.upload()) return rc;
+    if (int rc = check_shuffles_device(c, k, d_in.data(), d_sh.data(), count, blinding_factors, max_rows, counts, rows, c->stream)) return rc;
+    return io.finish();
 }
 
 }  // extern "C"

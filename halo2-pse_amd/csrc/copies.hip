@@ -361,20 +361,20 @@ int h2hip_permutation_mapping(uint32_t k, uint32_t n_columns, const uint32_t* co
     Ctx* c = en.c;
     hipStream_t s = c->stream;
     const size_t map_b = n * 8;
-    Carve io;
-    const size_t o_copies = io.take(n_copies * 16), o_maps = io.take((size_t)n_columns * map_b);
-    int rc = c->copies_io.ensure(io.total);
+    char *d_copies = nullptr, *d_map = nullptr;
+    HostIo io(c, c->host_io, s, true);
+    io.in(copies, n_copies * 16, &d_copies);
+    const size_t o_maps = io.room((size_t)n_columns * map_b, &d_map);
+    for (uint32_t j = 0; j < n_columns; j++) io.out_at(mapping[j], map_b, o_maps + j * map_b);
+    int rc = c->ws_acquire(s);
     if (rc) return rc;
-    char* base = (char*)c->copies_io.p;
-    std::vector<void*> d_maps(n_columns);
-    for (uint32_t j = 0; j < n_columns; j++) d_maps[j] = base + o_maps + j * map_b;
-    if ((rc = c->ws_acquire(s))) return rc;
     WsGuard guard(c, s);
-    if (n_copies) H2_CHECK(hipMemcpyAsync(base + o_copies, copies, n_copies * 16, hipMemcpyHostToDevice, s));
+    if ((rc = io.upload())) return rc;
+    std::vector<void*> d_maps(n_columns);
+    for (uint32_t j = 0; j < n_columns; j++) d_maps[j] = d_map + j * map_b;
     uint32_t* d_flag = nullptr;
-    if ((rc = copies_mapping_enqueue(c, k, n_columns, base + o_copies, n_copies, d_maps.data(), s, &d_flag))) return rc;
-    for (uint32_t j = 0; j < n_columns; j++) H2_CHECK(hipMemcpyAsync(mapping[j], d_maps[j], map_b, hipMemcpyDeviceToHost, s));
-    H2_CHECK(hipStreamSynchronize(s));
+    if ((rc = copies_mapping_enqueue(c, k, n_columns, d_copies, n_copies, d_maps.data(), s, &d_flag))) return rc;
+    if ((rc = io.finish())) return rc;
     return guard.release();
 }
 

@@ -179,19 +179,19 @@ struct Ctx {
     hipStream_t stream = nullptr;  // the engine's own stream (host-pointer entry points)
     std::recursive_mutex mu;       // serialises entry points: re-entrant callers (rayon workers) are safe
     DevBuf ntt_ws, ntt_io, msm_scalars[3], msm_bases, msm_slot[3], misc, evalh_ws, evalh_slots, ecfft_ws, ntt_ptrs, gather, gen_table;
-    DevBuf prod_ws, prod_io;       // product.hip: scans' workspace; the host-pointer forms' columns
+    DevBuf host_io;                // every stage file's host-pointer forms: the caller's columns on their way in and out (HostIo, below)
+    DevBuf prod_ws;                // product.hip: scans' workspace
     DevBuf mvsum_ws;               // product.hip: the mv-lookup grand sum's denominators, partial sums and descriptors
-    DevBuf open_ws, open_io;       // opening.hip: scans' workspace and tables; evaluations and the host-pointer forms' columns
-    DevBuf lookup_ws, lookup_io;   // lookup.hip: sort keys, marks and scans; the host-pointer forms' columns
+    DevBuf open_ws, open_io;       // opening.hip: scans' workspace and tables; the evaluations of both forms of eval_polynomials
+    DevBuf lookup_ws;              // lookup.hip: sort keys, marks and scans
     HostBuf lookup_flag;           // lookup.hip: the per-lookup not-found flags read back at the end of a permute call
-    DevBuf keygen_ws, keygen_io;   // keygen.hip: power tables, flag, pointer blobs and inverses; the host-pointer forms' columns
+    DevBuf keygen_ws;              // keygen.hip: power tables, flag, pointer blobs and inverses
     HostBuf keygen_flag;           // keygen.hip: the out-of-range flag of a permutation keygen read back at the end of the call
-    DevBuf check_ws, check_io;     // check.hip: failure masks, tile counts, row lists and sort keys; the host-pointer forms' columns
+    DevBuf check_ws;               // check.hip: failure masks, tile counts, row lists and sort keys
     HostBuf check_flag;            // check.hip: the out-of-range flag of a permutation check read back at the end of the call
-    DevBuf copies_ws, copies_io;   // copies.hip: parents, sort keys, flag and pointer blob; the host-pointer form's copies and mapping
+    DevBuf copies_ws;              // copies.hip: parents, sort keys, flag and pointer blob
     HostBuf copies_flag;           // copies.hip: the invalid-copy flag of a device-form mapping call read back at the end of the call
-    DevBuf serde_ws, serde_io;     // serde.hip: failure mask, tile counts and the two result words; the host-pointer forms' elements
-    DevBuf random_io;              // random.hip: the host-pointer forms' elements, from their threshold on
+    DevBuf serde_ws;               // serde.hip: failure mask, tile counts and the two result words
     HostBuf host_ws;               // pinned host memory for the window sums coming back
     HostBuf host_planes;           // ... and for the bit-plane sums of a run whose tail the host finishes (msm.hip msm_planes_finish)
     HostBuf pin_flag;              // one word the device-key fingerprint check writes its verdict to
@@ -468,6 +468,84 @@ struct Blob {
         return {(T*)(h + off), (T*)(d + off)};
     }
 };
+// api.hip: the device copy of a pinned host column whose fingerprint still matches the caller's memory, or nullptr
+const Fe* pinned_column_lookup(Ctx* c, const uint64_t* h_col, size_t elems);
+
+// The staging of a host-pointer form: the caller's columns cross PCIe through slots of Ctx::host_io, on the call's stream.  Plan
+// first, without a HIP call: in / out / room take slots in call order through a Carve (packed, or each rounded to 256 bytes with
+// `aligned`), and a column pinned with h2hip_columns_pin is read where it lies and takes none.  upload() then sizes the buffer
+// once, fills in the device pointers and queues the uploads in the order they were registered; the device driver runs; finish()
+// queues the downloads and waits for the stream.  A further round over the same slots registers its copies with in_at / out_at.
+// The drain rule: once a copy from or into the caller's memory may be queued, no exit leaves it queued -- the destructor waits for
+// the stream on every return that finish() did not complete, so a caller may free its columns after an error as after a success.
+// host_io is not one of the shared workspaces the WsGuard orders: only the host forms touch it, always on the engine's own stream;
+// each holds the context's lock until it returns and has waited for that stream by then, and none calls another, so two forms
+// never hold the buffer at once and its uploads are queued ahead of the guard without a second user to order against.
+// Everything the _device forms share with other calls is under the guard.
+struct HostIo {
+    struct Copy {
+        void* h;
+        size_t off, bytes;
+    };
+    Ctx* c;
+    DevBuf& buf;
+    hipStream_t s;
+    bool aligned;
+    Carve carve;
+    std::vector<std::pair<void*, size_t>> ptrs;  // where a slot's device pointer goes (an object pointer of any type), and the slot's offset
+    std::vector<Copy> ins, outs;
+    bool queued = false;
+    HostIo(Ctx* c_, DevBuf& buf_, hipStream_t s_, bool aligned_ = false) : c(c_), buf(buf_), s(s_), aligned(aligned_) {}
+    HostIo(const HostIo&) = delete;
+    ~HostIo() {
+        if (queued) (void)hipStreamSynchronize(s);
+    }
+    template <class T>
+    size_t room(size_t bytes, T** d) {  // a region only the device touches; the slot's offset, for in_at / out_at
+        const size_t off = aligned ? carve.take(bytes) : carve.take_packed(bytes);
+        ptrs.push_back({(void*)d, off});
+        return off;
+    }
+    void in_at(const void* h, size_t bytes, size_t off) { ins.push_back({(void*)h, off, bytes}); }
+    void out_at(void* h, size_t bytes, size_t off) { outs.push_back({h, off, bytes}); }
+    template <class T>
+    void in(const void* h, size_t bytes, T** d, bool try_pinned = false) {
+        if (try_pinned && (*d = (T*)pinned_column_lookup(c, (const uint64_t*)h, bytes / sizeof(Fe)))) return;
+        in_at(h, bytes, room(bytes, d));
+    }
+    template <class T>
+    size_t out(void* h, size_t bytes, T** d) {
+        const size_t off = room(bytes, d);
+        out_at(h, bytes, off);
+        return off;
+    }
+    int upload() {
+        if (int rc = buf.ensure(carve.total)) return rc;
+        for (const auto& pd : ptrs) {
+            void* p = (char*)buf.p + pd.second;
+            memcpy(pd.first, &p, sizeof p);
+        }
+        for (const Copy& j : ins) {
+            if (!j.bytes) continue;
+            queued = true;
+            H2_CHECK(hipMemcpyAsync((char*)buf.p + j.off, j.h, j.bytes, hipMemcpyHostToDevice, s));
+        }
+        ins.clear();
+        return 0;
+    }
+    int finish() {
+        for (const Copy& j : outs) {
+            if (!j.bytes) continue;
+            queued = true;
+            H2_CHECK(hipMemcpyAsync(j.h, (char*)buf.p + j.off, j.bytes, hipMemcpyDeviceToHost, s));
+        }
+        outs.clear();
+        H2_CHECK(hipStreamSynchronize(s));
+        queued = false;
+        return 0;
+    }
+};
+
 Ctx* ctx();             // the primary device's context (device_ids[0] of h2hip_init)
 int n_devices();        // devices the engine was initialised with (>= 1 once ready)
 Ctx* ctx_at(int i);     // context of the i-th device of h2hip_init's list
@@ -566,8 +644,6 @@ int lookup_sort_enqueue(const Fe* const* d_src, Fe* const* d_k0, Fe* const* d_k1
 // setup.hip
 int kzg_setup_device(Ctx* c, uint32_t k, const Fe& s, Affine* d_g, Affine* d_gl, hipStream_t stream);
 
-// api.hip: the device copy of a pinned host column whose fingerprint still matches the caller's memory, or nullptr
-const Fe* pinned_column_lookup(Ctx* c, const uint64_t* h_col, size_t elems);
 // api.hip: the fingerprint of a host column (H2_COL_SAMPLES elements); room for `bytes` more in the budget the pinned columns and the
 // pinned part cosets share (HALO2_HIP_COLUMN_CACHE_GB), least recently used entries of either kind dropped first -- false: `bytes`
 // exceed the whole budget, nothing was dropped

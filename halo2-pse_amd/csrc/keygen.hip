@@ -330,7 +330,7 @@ int h2hip_permutation_keygen_bn254(uint32_t k, const uint64_t omega[4], const ui
     if (gc > n_columns) gc = n_columns;
     const size_t groups = (n_columns + gc - 1) / gc;
     const size_t bufs = groups > 1 ? 2 : 1;
-    int rc = c->keygen_io.ensure(bufs * gc * per_col);
+    int rc = c->host_io.ensure(bufs * gc * per_col);
     if (rc) return rc;
     const bool piped = groups > 1 && copier_ready(c, true);
     if (piped && (rc = c->ensure_aux(2))) return rc;
@@ -350,7 +350,7 @@ int h2hip_permutation_keygen_bn254(uint32_t k, const uint64_t omega[4], const ui
     for (size_t g = 0; g < groups; g++) {
         const size_t j0 = g * gc, cnt = n_columns - j0 < gc ? n_columns - j0 : gc;
         if (piped && g >= 2 && (rc = copier_wait(c, true, jobs_through[g - 2]))) return rc;  // this buffer's earlier columns have left
-        char* base = (char*)c->keygen_io.p + (g % bufs) * gc * per_col;
+        char* base = (char*)c->host_io.p + (g % bufs) * gc * per_col;
         std::vector<const uint32_t*> d_map(cnt);
         std::vector<Fe*> d_perm(cnt), d_poly(cnt), d_coset(cnt);
         for (size_t j = 0; j < cnt; j++) {
@@ -493,38 +493,40 @@ int h2hip_batch_invert_assigned_bn254(uint32_t k, const uint64_t* const* numerat
     size_t gc = tune().keygen_group_bytes / col_b;
     if (gc < 1) gc = 1;
     if (gc > rat_cols.size()) gc = rat_cols.size();
-    Carve io;
-    const size_t o_inv = io.take(total * sizeof(Fe)), o_rows = io.take(total * sizeof(uint32_t)), o_cols = io.take_packed(gc * col_b);
-    int rc = c->keygen_io.ensure(io.total);
-    if (rc) return rc;
-    if ((rc = c->ws_acquire(s))) return rc;
-    WsGuard guard(c, s);
-    if ((rc = c->keygen_ws.ensure(align256(gc * sizeof(KgScatter))))) return rc;
-    Fe* inv = (Fe*)((char*)c->keygen_io.p + o_inv);
-    uint32_t* rows = (uint32_t*)((char*)c->keygen_io.p + o_rows);
-    char* cols = (char*)c->keygen_io.p + o_cols;
+    Fe* inv = nullptr;
+    uint32_t* rows = nullptr;
+    char* cols = nullptr;
+    HostIo io(c, c->host_io, s, true);
+    const size_t o_inv = io.room(total * sizeof(Fe), &inv), o_rows = io.room(total * sizeof(uint32_t), &rows);
+    io.aligned = false;  // the columns of a group lie packed
+    const size_t o_cols = io.room(gc * col_b, &cols);
     std::vector<size_t> offs(rat_cols.size(), 0);
     size_t off = 0;
     for (size_t q = 0; q < rat_cols.size(); q++) {
         const size_t j = rat_cols[q], cnt = rat_counts[j];
         offs[q] = off;
-        H2_CHECK(hipMemcpyAsync(inv + off, rat_denoms[j], cnt * sizeof(Fe), hipMemcpyHostToDevice, s));
-        H2_CHECK(hipMemcpyAsync(rows + off, rat_rows[j], cnt * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        io.in_at(rat_denoms[j], cnt * sizeof(Fe), o_inv + off * sizeof(Fe));
+        io.in_at(rat_rows[j], cnt * sizeof(uint32_t), o_rows + off * sizeof(uint32_t));
         off += cnt;
     }
+    int rc = c->ws_acquire(s);
+    if (rc) return rc;
+    WsGuard guard(c, s);
+    if ((rc = c->keygen_ws.ensure(align256(gc * sizeof(KgScatter))))) return rc;
+    if ((rc = io.upload())) return rc;
     if ((rc = batch_invert_device(c, inv, total, s))) return rc;
-    for (size_t q0 = 0; q0 < rat_cols.size(); q0 += gc) {
+    for (size_t q0 = 0; q0 < rat_cols.size(); q0 += gc) {  // one round of the staging per group, over the same slots
         const size_t cnt = rat_cols.size() - q0 < gc ? rat_cols.size() - q0 : gc;
         std::vector<KgScatter> descs;
         for (size_t q = 0; q < cnt; q++) {
             const size_t j = rat_cols[q0 + q];
-            Fe* d_col = (Fe*)(cols + q * col_b);
-            H2_CHECK(hipMemcpyAsync(d_col, numerators[j], col_b, hipMemcpyHostToDevice, s));
-            descs.push_back(KgScatter{d_col, rows + offs[q0 + q], offs[q0 + q], (uint32_t)rat_counts[j], 0});
+            io.in_at(numerators[j], col_b, o_cols + q * col_b);
+            io.out_at(out[j], col_b, o_cols + q * col_b);
+            descs.push_back(KgScatter{(Fe*)(cols + q * col_b), rows + offs[q0 + q], offs[q0 + q], (uint32_t)rat_counts[j], 0});
         }
+        if ((rc = io.upload())) return rc;
         if ((rc = kg_scatter(c, n, descs, (char*)c->keygen_ws.p, inv, s))) return rc;
-        for (size_t q = 0; q < cnt; q++) H2_CHECK(hipMemcpyAsync(out[rat_cols[q0 + q]], cols + q * col_b, col_b, hipMemcpyDeviceToHost, s));
-        H2_CHECK(hipStreamSynchronize(s));
+        if ((rc = io.finish())) return rc;
     }
     return guard.release();
 }
@@ -567,15 +569,15 @@ int h2hip_key_lagrange_columns_bn254(uint32_t k, const uint64_t omega_inv[4], co
     Ctx* c = en.c;
     hipStream_t s = c->stream;
     const size_t ext_b = sizeof(Fe) << extended_k;
-    int rc = c->keygen_io.ensure(3 * ext_b);
+    Fe *d_l0 = nullptr, *d_l_last = nullptr, *d_l_active = nullptr;
+    HostIo io(c, c->host_io, s);
+    io.out(l0, ext_b, &d_l0);
+    io.out(l_last, ext_b, &d_l_last);
+    io.out(l_active_row, ext_b, &d_l_active);
+    int rc = io.upload();
     if (rc) return rc;
-    char* io = (char*)c->keygen_io.p;
-    if ((rc = kg_lagrange_device(c, d, blinding_factors, (Fe*)io, (Fe*)(io + ext_b), (Fe*)(io + 2 * ext_b), s))) return rc;
-    H2_CHECK(hipMemcpyAsync(l0, io, ext_b, hipMemcpyDeviceToHost, s));
-    H2_CHECK(hipMemcpyAsync(l_last, io + ext_b, ext_b, hipMemcpyDeviceToHost, s));
-    H2_CHECK(hipMemcpyAsync(l_active_row, io + 2 * ext_b, ext_b, hipMemcpyDeviceToHost, s));
-    H2_CHECK(hipStreamSynchronize(s));
-    return 0;
+    if ((rc = kg_lagrange_device(c, d, blinding_factors, d_l0, d_l_last, d_l_active, s))) return rc;
+    return io.finish();
 }
 
 int h2hip_debug_set_keygen_group(uint64_t group_bytes) {

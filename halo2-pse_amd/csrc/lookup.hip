@@ -664,36 +664,21 @@ int h2hip_lookup_compress_bn254(uint32_t k, const uint64_t* const* fixed_values,
     if (en.rc) return en.rc;
     Ctx* c = en.c;
     hipStream_t s = c->stream;
-    const size_t n = (size_t)1 << k, bytes = n * sizeof(Fe);
-    // fixed columns pinned with h2hip_columns_pin are read where they lie; the witness columns and the rest cross PCIe
-    std::vector<const Fe*> d_fixed(n_fixed, nullptr), d_advice(n_advice), d_instance(n_instance);
+    const size_t bytes = sizeof(Fe) << k;
+    std::vector<const Fe*> d_fixed(n_fixed), d_advice(n_advice), d_instance(n_instance);
     std::vector<Fe*> d_out(n_graphs);
-    size_t unpinned = 0;
-    for (uint32_t j = 0; j < n_fixed; j++) {
-        d_fixed[j] = pinned_column_lookup(c, fixed_values[j], n);
-        if (!d_fixed[j]) unpinned++;
-    }
-    int rc = c->lookup_io.ensure((unpinned + n_advice + n_instance + n_graphs) * bytes);
+    HostIo io(c, c->host_io, s);
+    // fixed columns pinned with h2hip_columns_pin are read where they lie; the witness columns and the rest cross PCIe
+    for (uint32_t j = 0; j < n_fixed; j++) io.in(fixed_values[j], bytes, &d_fixed[j], true);
+    for (uint32_t j = 0; j < n_advice; j++) io.in(advice_values[j], bytes, &d_advice[j]);
+    for (uint32_t j = 0; j < n_instance; j++) io.in(instance_values[j], bytes, &d_instance[j]);
+    for (size_t g = 0; g < n_graphs; g++) io.out(out[g], bytes, &d_out[g]);
+    int rc = io.upload();
     if (rc) return rc;
-    char* io = (char*)c->lookup_io.p;
-    size_t slot = 0;
-    auto up = [&](const uint64_t* src) -> const Fe* {
-        Fe* d = (Fe*)(io + slot++ * bytes);
-        return hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, s) == hipSuccess ? d : nullptr;
-    };
-    for (uint32_t j = 0; j < n_fixed; j++)
-        if (!d_fixed[j] && !(d_fixed[j] = up(fixed_values[j]))) return H2HIP_EDEVICE;
-    for (uint32_t j = 0; j < n_advice; j++)
-        if (!(d_advice[j] = up(advice_values[j]))) return H2HIP_EDEVICE;
-    for (uint32_t j = 0; j < n_instance; j++)
-        if (!(d_instance[j] = up(instance_values[j]))) return H2HIP_EDEVICE;
-    for (size_t g = 0; g < n_graphs; g++) d_out[g] = (Fe*)(io + slot++ * bytes);
     rc = lookup_compress_device(c, k, d_fixed.data(), n_fixed, d_advice.data(), n_advice, d_instance.data(), n_instance, challenges, n_challenges,
                                 theta, graphs, n_graphs, d_out.data(), s);
     if (rc) return rc;
-    for (size_t g = 0; g < n_graphs; g++) H2_CHECK(hipMemcpyAsync(out[g], d_out[g], bytes, hipMemcpyDeviceToHost, s));
-    H2_CHECK(hipStreamSynchronize(s));
-    return 0;
+    return io.finish();
 }
 
 int h2hip_lookup_permute_bn254_device(uint32_t k, const void* const* d_compressed_input, const void* const* d_compressed_table, size_t count,
@@ -719,28 +704,21 @@ int h2hip_lookup_permute_bn254(uint32_t k, const uint64_t* const* compressed_inp
     if (en.rc) return en.rc;
     Ctx* c = en.c;
     hipStream_t s = c->stream;
-    const size_t n = (size_t)1 << k, bytes = n * sizeof(Fe);
-    int rc = c->lookup_io.ensure(4 * count * bytes);
-    if (rc) return rc;
-    char* io = (char*)c->lookup_io.p;
+    const size_t bytes = sizeof(Fe) << k;
     std::vector<const Fe*> in(count), tab(count);
     std::vector<Fe*> pa(count), pt(count);
+    HostIo io(c, c->host_io, s);
     for (size_t j = 0; j < count; j++) {
-        in[j] = (const Fe*)(io + (4 * j) * bytes);
-        tab[j] = (const Fe*)(io + (4 * j + 1) * bytes);
-        pa[j] = (Fe*)(io + (4 * j + 2) * bytes);
-        pt[j] = (Fe*)(io + (4 * j + 3) * bytes);
-        H2_CHECK(hipMemcpyAsync((void*)in[j], compressed_input[j], bytes, hipMemcpyHostToDevice, s));
-        H2_CHECK(hipMemcpyAsync((void*)tab[j], compressed_table[j], bytes, hipMemcpyHostToDevice, s));
+        io.in(compressed_input[j], bytes, &in[j]);
+        io.in(compressed_table[j], bytes, &tab[j]);
+        io.out(permuted_input[j], bytes, &pa[j]);
+        io.out(permuted_table[j], bytes, &pt[j]);
     }
+    int rc = io.upload();
+    if (rc) return rc;
     rc = lookup_permute_device(c, k, in.data(), tab.data(), count, blinding, blinding_factors, pa.data(), pt.data(), s);
     if (rc) return rc;
-    for (size_t j = 0; j < count; j++) {
-        H2_CHECK(hipMemcpyAsync(permuted_input[j], pa[j], bytes, hipMemcpyDeviceToHost, s));
-        H2_CHECK(hipMemcpyAsync(permuted_table[j], pt[j], bytes, hipMemcpyDeviceToHost, s));
-    }
-    H2_CHECK(hipStreamSynchronize(s));
-    return 0;
+    return io.finish();
 }
 
 // ---- the mv-lookup multiplicities ------------------------------------------------------------------------------------------------
@@ -798,25 +776,19 @@ int h2hip_mvlookup_multiplicities_bn254(uint32_t k, const uint64_t* const* compr
     if (en.rc) return en.rc;
     Ctx* c = en.c;
     hipStream_t s = c->stream;
-    const size_t n = (size_t)1 << k, bytes = n * sizeof(Fe);
-    int rc = c->lookup_io.ensure((total_in + 2 * count) * bytes);
-    if (rc) return rc;
-    char* io = (char*)c->lookup_io.p;
+    const size_t bytes = sizeof(Fe) << k;
     std::vector<const Fe*> in(total_in), tab(count);
     std::vector<Fe*> d_m(count);
-    for (size_t q = 0; q < total_in; q++) {
-        in[q] = (const Fe*)(io + q * bytes);
-        H2_CHECK(hipMemcpyAsync((void*)in[q], compressed_inputs[q], bytes, hipMemcpyHostToDevice, s));
-    }
+    HostIo io(c, c->host_io, s);
+    for (size_t q = 0; q < total_in; q++) io.in(compressed_inputs[q], bytes, &in[q]);
     for (size_t j = 0; j < count; j++) {
-        tab[j] = (const Fe*)(io + (total_in + 2 * j) * bytes);
-        d_m[j] = (Fe*)(io + (total_in + 2 * j + 1) * bytes);
-        H2_CHECK(hipMemcpyAsync((void*)tab[j], compressed_tables[j], bytes, hipMemcpyHostToDevice, s));
+        io.in(compressed_tables[j], bytes, &tab[j]);
+        io.out(m[j], bytes, &d_m[j]);
     }
+    if (int rc = io.upload()) return rc;
     const int verdict = mvlookup_multiplicities_device(c, k, in.data(), n_inputs, tab.data(), count, blinding_factors, d_m.data(), s);
     if (verdict && verdict != H2HIP_ELOOKUP) return verdict;
-    for (size_t j = 0; j < count; j++) H2_CHECK(hipMemcpyAsync(m[j], d_m[j], bytes, hipMemcpyDeviceToHost, s));  // written either way
-    H2_CHECK(hipStreamSynchronize(s));
+    if (int rc = io.finish()) return rc;  // the m are written either way
     return verdict;
 }
 

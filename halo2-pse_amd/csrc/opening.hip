@@ -486,7 +486,7 @@ static int eval_finish(Ctx* c, const Fe* const* d_polys, const size_t* lens, siz
     memcpy(pts.data(), points, n_queries * sizeof(Fe));
     int rc = c->open_io.ensure(align256(n_queries * sizeof(Fe)));
     if (rc) return rc;
-    // open_io holds the evaluations at its start; the host form's uploaded polynomials follow at an offset of their own
+    // open_io holds the evaluations of both forms (the host form's uploaded polynomials are in host_io): this form runs on any stream
     if ((rc = eval_run(c, d_polys, lens, n_polys, query_poly, pts.data(), n_queries, (Fe*)c->open_io.p, s))) return rc;
     H2_CHECK(hipMemcpyAsync(evals, c->open_io.p, n_queries * sizeof(Fe), hipMemcpyDeviceToHost, s));
     H2_CHECK(hipStreamSynchronize(s));
@@ -518,20 +518,12 @@ int h2hip_eval_polynomials_bn254(const uint64_t* const* polys, const size_t* len
     std::vector<char> queried(n_polys, 0);
     for (size_t q = 0; q < n_queries; q++) queried[query_poly[q]] = 1;
     std::vector<const Fe*> d(n_polys, nullptr);
-    const size_t head = align256(n_queries * sizeof(Fe));
-    size_t bytes = head;
+    HostIo io(c, c->host_io, s, true);
     for (size_t j = 0; j < n_polys; j++)
-        if (queried[j] && lens[j] && !(d[j] = pinned_column_lookup(c, polys[j], lens[j]))) bytes += align256(lens[j] * sizeof(Fe));
-    int rc = c->open_io.ensure(bytes);
-    if (rc) return rc;
-    size_t off = head;
-    for (size_t j = 0; j < n_polys; j++)
-        if (queried[j] && lens[j] && !d[j]) {
-            d[j] = (const Fe*)((char*)c->open_io.p + off);
-            H2_CHECK(hipMemcpyAsync((void*)d[j], polys[j], lens[j] * sizeof(Fe), hipMemcpyHostToDevice, s));
-            off += align256(lens[j] * sizeof(Fe));
-        }
-    return eval_finish(c, d.data(), lens, n_polys, query_poly, points, n_queries, evals, s);
+        if (queried[j] && lens[j]) io.in(polys[j], lens[j] * sizeof(Fe), &d[j], true);
+    if (int rc = io.upload()) return rc;
+    if (int rc = eval_finish(c, d.data(), lens, n_polys, query_poly, points, n_queries, evals, s)) return rc;
+    return io.finish();
 }
 
 static int combine_check(const void* const* polys, size_t len, const uint64_t* scalars, size_t n_polys, const uint64_t* sub, size_t sub_len,
@@ -618,28 +610,21 @@ int h2hip_poly_combine_bn254_fr(const uint64_t* const* polys, size_t len, const 
     if (en.rc) return en.rc;
     Ctx* c = en.c;
     hipStream_t s = c->stream;
-    const size_t bytes = align256(len * sizeof(Fe));
     std::vector<const Fe*> d(n_polys, nullptr);
-    size_t need = bytes;  // the output first
+    Fe* d_out = nullptr;
+    HostIo io(c, c->host_io, s, true);
+    const size_t o_out = io.room(len * sizeof(Fe), &d_out);  // the output first
     for (size_t j = 0; j < n_polys; j++)
-        if (len && !(d[j] = pinned_column_lookup(c, polys[j], len))) need += bytes;
-    int rc = c->open_io.ensure(need);
+        if (len) io.in(polys[j], len * sizeof(Fe), &d[j], true);
+    if (accumulate) io.in_at(out, Lout * sizeof(Fe), o_out);
+    io.out_at(out, Lout * sizeof(Fe), o_out);
+    int rc = io.upload();
     if (rc) return rc;
-    Fe* d_out = (Fe*)c->open_io.p;
-    size_t off = bytes;
-    for (size_t j = 0; j < n_polys; j++)
-        if (len && !d[j]) {
-            d[j] = (const Fe*)((char*)c->open_io.p + off);
-            H2_CHECK(hipMemcpyAsync((void*)d[j], polys[j], len * sizeof(Fe), hipMemcpyHostToDevice, s));
-            off += bytes;
-        }
-    if (accumulate && Lout) H2_CHECK(hipMemcpyAsync(d_out, out, Lout * sizeof(Fe), hipMemcpyHostToDevice, s));
     std::vector<Fe> h_rem(1);
     rc = combine_run(c, d.data(), len, (const Fe*)scalars, n_polys, (const Fe*)sub, sub_len, (const Fe*)roots, n_roots, fe_from_u64x4(scale),
                      accumulate != 0, d_out, remainder != nullptr, h_rem.data(), s);
     if (rc) return rc;
-    if (Lout) H2_CHECK(hipMemcpyAsync(out, d_out, Lout * sizeof(Fe), hipMemcpyDeviceToHost, s));
-    H2_CHECK(hipStreamSynchronize(s));
+    if ((rc = io.finish())) return rc;
     if (!accumulate && out_len > Lout) memset(out + 4 * Lout, 0, (out_len - Lout) * sizeof(Fe));
     if (remainder) memcpy(remainder, h_rem.data(), sizeof(Fe));
     return 0;

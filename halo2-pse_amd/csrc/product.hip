@@ -778,36 +778,20 @@ int h2hip_permutation_products_bn254(uint32_t k, const uint64_t omega[4], const 
     if (en.rc) return en.rc;
     Ctx* c = en.c;
     hipStream_t s = c->stream;
-    const size_t n = (size_t)1 << k, bytes = n * sizeof(Fe);
-    // the key's columns s_c come from the h2hip_columns_pin cache when pinned; only the witness columns and the rest cross PCIe
-    std::vector<const Fe*> d_perm(n_columns, nullptr);
-    size_t unpinned = 0;
-    for (uint32_t j = 0; j < n_columns; j++) {
-        d_perm[j] = pinned_column_lookup(c, permutations[j], n);
-        if (!d_perm[j]) unpinned++;
-    }
-    int rc = c->prod_io.ensure((n_columns + unpinned + n_sets) * bytes);
-    if (rc) return rc;
-    char* io = (char*)c->prod_io.p;
-    std::vector<const Fe*> d_cols(n_columns);
+    const size_t bytes = sizeof(Fe) << k;
+    std::vector<const Fe*> d_cols(n_columns), d_perm(n_columns);
     std::vector<Fe*> d_z(n_sets);
-    size_t slot = 0;
-    for (uint32_t j = 0; j < n_columns; j++) {  // uploads on the call's own stream, ahead of its kernels
-        d_cols[j] = (const Fe*)(io + slot++ * bytes);
-        H2_CHECK(hipMemcpyAsync((void*)d_cols[j], columns[j], bytes, hipMemcpyHostToDevice, s));
-    }
-    for (uint32_t j = 0; j < n_columns; j++)
-        if (!d_perm[j]) {
-            d_perm[j] = (const Fe*)(io + slot++ * bytes);
-            H2_CHECK(hipMemcpyAsync((void*)d_perm[j], permutations[j], bytes, hipMemcpyHostToDevice, s));
-        }
-    for (size_t t = 0; t < n_sets; t++) d_z[t] = (Fe*)(io + slot++ * bytes);
+    HostIo io(c, c->host_io, s);
+    for (uint32_t j = 0; j < n_columns; j++) io.in(columns[j], bytes, &d_cols[j]);
+    // the key's columns s_c come from the h2hip_columns_pin cache when pinned; only the witness columns and the rest cross PCIe
+    for (uint32_t j = 0; j < n_columns; j++) io.in(permutations[j], bytes, &d_perm[j], true);
+    for (size_t t = 0; t < n_sets; t++) io.out(z[t], bytes, &d_z[t]);
+    int rc = io.upload();  // on the call's own stream, ahead of its kernels
+    if (rc) return rc;
     rc = permutation_products_device(c, k, fe_from_u64x4(omega), fe_from_u64x4(delta), fe_from_u64x4(beta), fe_from_u64x4(gamma),
                                      d_cols.data(), d_perm.data(), n_columns, chunk_len, blinding, blinding_factors, d_z.data(), s);
     if (rc) return rc;
-    for (size_t t = 0; t < n_sets; t++) H2_CHECK(hipMemcpyAsync(z[t], d_z[t], bytes, hipMemcpyDeviceToHost, s));
-    H2_CHECK(hipStreamSynchronize(s));
-    return 0;
+    return io.finish();
 }
 
 int h2hip_lookup_products_bn254_device(uint32_t k, const uint64_t beta[4], const uint64_t gamma[4], const void* const* d_compressed_input,
@@ -844,27 +828,23 @@ int h2hip_lookup_products_bn254(uint32_t k, const uint64_t beta[4], const uint64
     if (en.rc) return en.rc;
     Ctx* c = en.c;
     hipStream_t s = c->stream;
-    const size_t n = (size_t)1 << k, bytes = n * sizeof(Fe);
-    int rc = c->prod_io.ensure(5 * count * bytes);
-    if (rc) return rc;
-    char* io = (char*)c->prod_io.p;
+    const size_t bytes = sizeof(Fe) << k;
     std::vector<const Fe*> in(2 * count), perm(2 * count);
     std::vector<Fe*> d_z(count);
-    const uint64_t* const* src[4] = {compressed_input, compressed_table, permuted_input, permuted_table};
-    for (size_t j = 0; j < count; j++) {
-        const Fe** dst[4] = {&in[2 * j], &in[2 * j + 1], &perm[2 * j], &perm[2 * j + 1]};
-        for (int q = 0; q < 4; q++) {
-            *dst[q] = (const Fe*)(io + (5 * j + q) * bytes);
-            H2_CHECK(hipMemcpyAsync((void*)*dst[q], src[q][j], bytes, hipMemcpyHostToDevice, s));
-        }
-        d_z[j] = (Fe*)(io + (5 * j + 4) * bytes);
+    HostIo io(c, c->host_io, s);
+    for (size_t j = 0; j < count; j++) {  // A, S, A', S', z per lookup
+        io.in(compressed_input[j], bytes, &in[2 * j]);
+        io.in(compressed_table[j], bytes, &in[2 * j + 1]);
+        io.in(permuted_input[j], bytes, &perm[2 * j]);
+        io.in(permuted_table[j], bytes, &perm[2 * j + 1]);
+        io.out(z[j], bytes, &d_z[j]);
     }
+    int rc = io.upload();
+    if (rc) return rc;
     rc = lookup_products_device(c, k, fe_from_u64x4(beta), fe_from_u64x4(gamma), in.data(), perm.data(), count, blinding, blinding_factors,
                                 d_z.data(), s);
     if (rc) return rc;
-    for (size_t j = 0; j < count; j++) H2_CHECK(hipMemcpyAsync(z[j], d_z[j], bytes, hipMemcpyDeviceToHost, s));
-    H2_CHECK(hipStreamSynchronize(s));
-    return 0;
+    return io.finish();
 }
 
 static int shuffle_check(uint32_t k, const uint64_t gamma[4], const void* const* a, const void* const* s, size_t count, const uint64_t* blinding,
@@ -908,24 +888,20 @@ int h2hip_shuffle_products_bn254(uint32_t k, const uint64_t gamma[4], const uint
     if (en.rc) return en.rc;
     Ctx* c = en.c;
     hipStream_t s = c->stream;
-    const size_t n = (size_t)1 << k, bytes = n * sizeof(Fe);
-    int rc = c->prod_io.ensure(3 * count * bytes);
-    if (rc) return rc;
-    char* io = (char*)c->prod_io.p;
+    const size_t bytes = sizeof(Fe) << k;
     std::vector<const Fe*> in(count), sh(count);
     std::vector<Fe*> d_z(count);
+    HostIo io(c, c->host_io, s);
     for (size_t j = 0; j < count; j++) {
-        in[j] = (const Fe*)(io + (3 * j) * bytes);
-        sh[j] = (const Fe*)(io + (3 * j + 1) * bytes);
-        d_z[j] = (Fe*)(io + (3 * j + 2) * bytes);
-        H2_CHECK(hipMemcpyAsync((void*)in[j], compressed_input[j], bytes, hipMemcpyHostToDevice, s));
-        H2_CHECK(hipMemcpyAsync((void*)sh[j], compressed_shuffle[j], bytes, hipMemcpyHostToDevice, s));
+        io.in(compressed_input[j], bytes, &in[j]);
+        io.in(compressed_shuffle[j], bytes, &sh[j]);
+        io.out(z[j], bytes, &d_z[j]);
     }
+    int rc = io.upload();
+    if (rc) return rc;
     rc = shuffle_products_device(c, k, fe_from_u64x4(gamma), in.data(), sh.data(), count, blinding, blinding_factors, d_z.data(), s);
     if (rc) return rc;
-    for (size_t j = 0; j < count; j++) H2_CHECK(hipMemcpyAsync(z[j], d_z[j], bytes, hipMemcpyDeviceToHost, s));
-    H2_CHECK(hipStreamSynchronize(s));
-    return 0;
+    return io.finish();
 }
 
 static int mvsums_check(uint32_t k, const uint64_t beta[4], const void* const* in, const uint32_t* n_inputs, const void* const* tab,
@@ -990,29 +966,22 @@ int h2hip_mvlookup_sums_bn254(uint32_t k, const uint64_t beta[4], const uint64_t
     if (en.rc) return en.rc;
     Ctx* c = en.c;
     hipStream_t s = c->stream;
-    const size_t n = (size_t)1 << k, bytes = n * sizeof(Fe);
-    int rc = c->prod_io.ensure((total_in + 3 * count) * bytes);
-    if (rc) return rc;
-    char* io = (char*)c->prod_io.p;
+    const size_t bytes = sizeof(Fe) << k;
     std::vector<const Fe*> in(total_in), tab(count), d_m(count);
     std::vector<Fe*> d_phi(count);
-    for (size_t q = 0; q < total_in; q++) {
-        in[q] = (const Fe*)(io + q * bytes);
-        H2_CHECK(hipMemcpyAsync((void*)in[q], compressed_inputs[q], bytes, hipMemcpyHostToDevice, s));
-    }
+    HostIo io(c, c->host_io, s);
+    for (size_t q = 0; q < total_in; q++) io.in(compressed_inputs[q], bytes, &in[q]);
     for (size_t j = 0; j < count; j++) {
-        tab[j] = (const Fe*)(io + (total_in + 3 * j) * bytes);
-        d_m[j] = (const Fe*)(io + (total_in + 3 * j + 1) * bytes);
-        d_phi[j] = (Fe*)(io + (total_in + 3 * j + 2) * bytes);
-        H2_CHECK(hipMemcpyAsync((void*)tab[j], compressed_tables[j], bytes, hipMemcpyHostToDevice, s));
-        H2_CHECK(hipMemcpyAsync((void*)d_m[j], m[j], bytes, hipMemcpyHostToDevice, s));
+        io.in(compressed_tables[j], bytes, &tab[j]);
+        io.in(m[j], bytes, &d_m[j]);
+        io.out(phi[j], bytes, &d_phi[j]);
     }
+    int rc = io.upload();
+    if (rc) return rc;
     rc = mvlookup_sums_device(c, k, fe_from_u64x4(beta), in.data(), n_inputs, tab.data(), d_m.data(), count, blinding, blinding_factors,
                               d_phi.data(), s);
     if (rc) return rc;
-    for (size_t j = 0; j < count; j++) H2_CHECK(hipMemcpyAsync(phi[j], d_phi[j], bytes, hipMemcpyDeviceToHost, s));
-    H2_CHECK(hipStreamSynchronize(s));
-    return 0;
+    return io.finish();
 }
 
 // rows per thread of the grand sum's scan for a call of `count` arguments: the rule the code itself applies (tests pick their case by it)
@@ -1054,14 +1023,13 @@ int h2hip_batch_invert_bn254_fr(uint64_t* a, size_t n) {
     if (en.rc) return en.rc;
     Ctx* c = en.c;
     hipStream_t s = c->stream;
-    const size_t bytes = n * sizeof(Fe);
-    int rc = c->prod_io.ensure(bytes);
+    Fe* d_a = nullptr;
+    HostIo io(c, c->host_io, s);
+    io.in_at(a, n * sizeof(Fe), io.out(a, n * sizeof(Fe), &d_a));  // in place: one slot both ways
+    int rc = io.upload();
     if (rc) return rc;
-    H2_CHECK(hipMemcpyAsync(c->prod_io.p, a, bytes, hipMemcpyHostToDevice, s));
-    if ((rc = batch_invert_device(c, (Fe*)c->prod_io.p, n, s))) return rc;
-    H2_CHECK(hipMemcpyAsync(a, c->prod_io.p, bytes, hipMemcpyDeviceToHost, s));
-    H2_CHECK(hipStreamSynchronize(s));
-    return 0;
+    if ((rc = batch_invert_device(c, d_a, n, s))) return rc;
+    return io.finish();
 }
 
 }  // extern "C"

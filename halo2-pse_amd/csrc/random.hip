@@ -82,19 +82,19 @@ static int rn_wide_device(Ctx* c, const void* d_bytes, size_t n, void* d_out, hi
     return 0;
 }
 
-// The host forms from the threshold on: generate into random_io, download.  random_io is touched by the host forms only, on the
-// engine's own stream, each of which synchronises that stream before it returns (as serde.hip says of serde_io).
+// The host forms from the threshold on: generate into the staging buffer (engine.h, HostIo), download.
 static int rn_random_host(const ChaChaKey& key, uint64_t first_block, size_t n, uint64_t* out) {
     Entry en("h2hip_fr_random_bn254");
     if (en.rc) return en.rc;
     Ctx* c = en.c;
     hipStream_t s = c->stream;
-    int rc = c->random_io.ensure(n * 32);
+    char* d_out = nullptr;
+    HostIo io(c, c->host_io, s);
+    io.out(out, n * 32, &d_out);
+    int rc = io.upload();
     if (rc) return rc;
-    if ((rc = rn_random_device(c, key, first_block, n, c->random_io.p, s))) return rc;
-    H2_CHECK(hipMemcpyAsync(out, c->random_io.p, n * 32, hipMemcpyDeviceToHost, s));
-    H2_CHECK(hipStreamSynchronize(s));
-    return 0;
+    if ((rc = rn_random_device(c, key, first_block, n, d_out, s))) return rc;
+    return io.finish();
 }
 
 static int rn_wide_host(const uint8_t* bytes, size_t n, uint64_t* out) {
@@ -102,16 +102,14 @@ static int rn_wide_host(const uint8_t* bytes, size_t n, uint64_t* out) {
     if (en.rc) return en.rc;
     Ctx* c = en.c;
     hipStream_t s = c->stream;
-    Carve io;
-    const size_t o_in = io.take(n * 64), o_out = io.take(n * 32);
-    int rc = c->random_io.ensure(io.total);
+    char *d_in = nullptr, *d_out = nullptr;
+    HostIo io(c, c->host_io, s, true);
+    io.in(bytes, n * 64, &d_in);
+    io.out(out, n * 32, &d_out);
+    int rc = io.upload();
     if (rc) return rc;
-    char* base = (char*)c->random_io.p;
-    H2_CHECK(hipMemcpyAsync(base + o_in, bytes, n * 64, hipMemcpyHostToDevice, s));
-    if ((rc = rn_wide_device(c, base + o_in, n, base + o_out, s))) return rc;
-    H2_CHECK(hipMemcpyAsync(out, base + o_out, n * 32, hipMemcpyDeviceToHost, s));
-    H2_CHECK(hipStreamSynchronize(s));
-    return 0;
+    if ((rc = rn_wide_device(c, d_in, n, d_out, s))) return rc;
+    return io.finish();
 }
 
 }  // namespace h2

@@ -165,26 +165,21 @@ static int sd_fallible_device(Ctx* c, SdOp op, const void* d_in, void* d_out, si
     return 0;
 }
 
-// The host forms: upload into serde_io, convert there, download.  serde_io is touched by the host forms only, on the engine's own
-// stream, each of which synchronises that stream before it returns (as check.hip's CkUpload says of check_io).
+// The host forms: upload into the staging buffer (engine.h, HostIo), convert there, download.
 static int sd_fallible_host(const char* name, SdOp op, const void* in, size_t in_elem, void* out, size_t out_elem, size_t n, uint64_t invalid[2]) {
     Entry en(name);
     if (en.rc) return en.rc;
     Ctx* c = en.c;
     hipStream_t s = c->stream;
-    Carve io;
-    const size_t o_in = io.take(n * in_elem), o_out = io.take(n * out_elem);
-    int rc = c->serde_io.ensure(io.total);
-    if (rc) return rc;
-    char* base = (char*)c->serde_io.p;
-    H2_CHECK(hipMemcpyAsync(base + o_in, in, n * in_elem, hipMemcpyHostToDevice, s));
-    rc = sd_fallible_device(c, op, base + o_in, base + o_out, n, invalid, s);
-    if (rc && rc != H2HIP_EENCODING) return rc;
-    if (out_elem) {  // all of the output is written, the failing elements as zeros
-        H2_CHECK(hipMemcpyAsync(out, base + o_out, n * out_elem, hipMemcpyDeviceToHost, s));
-        H2_CHECK(hipStreamSynchronize(s));
-    }
-    return rc;
+    char *d_in = nullptr, *d_out = nullptr;
+    HostIo io(c, c->host_io, s, true);
+    io.in(in, n * in_elem, &d_in);
+    io.out(out, n * out_elem, &d_out);  // (nothing when out_elem is 0: the validation)
+    if (int rc = io.upload()) return rc;
+    const int verdict = sd_fallible_device(c, op, d_in, d_out, n, invalid, s);
+    if (verdict && verdict != H2HIP_EENCODING) return verdict;
+    if (int rc = io.finish()) return rc;  // all of the output is written, the failing elements as zeros
+    return verdict;
 }
 
 static int sd_plain_device(bool compress, const void* d_in, void* d_out, size_t n, hipStream_t s) {
@@ -200,18 +195,16 @@ static int sd_plain_host(const char* name, bool compress, const void* in, size_t
     if (en.rc) return en.rc;
     Ctx* c = en.c;
     hipStream_t s = c->stream;
-    Carve io;
-    const size_t o_in = io.take(n * in_elem), o_out = io.take(n * 32);
-    int rc = c->serde_io.ensure(io.total);
+    char *d_in = nullptr, *d_out = nullptr;
+    HostIo io(c, c->host_io, s, true);
+    io.in(in, n * in_elem, &d_in);
+    io.out(out, n * 32, &d_out);
+    int rc = io.upload();
     if (rc) return rc;
-    char* base = (char*)c->serde_io.p;
-    H2_CHECK(hipMemcpyAsync(base + o_in, in, n * in_elem, hipMemcpyHostToDevice, s));
     int tm = c->timer_begin(compress ? "g1_compress" : "fr_to_repr", s);
-    if ((rc = sd_plain_device(compress, base + o_in, base + o_out, n, s))) return rc;
+    if ((rc = sd_plain_device(compress, d_in, d_out, n, s))) return rc;
     c->timer_end(tm, s);
-    H2_CHECK(hipMemcpyAsync(out, base + o_out, n * 32, hipMemcpyDeviceToHost, s));
-    H2_CHECK(hipStreamSynchronize(s));
-    return 0;
+    return io.finish();
 }
 
 }  // namespace h2

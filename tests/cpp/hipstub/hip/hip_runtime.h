@@ -10,6 +10,7 @@
 
 #include <map>
 #include <mutex>
+#include <vector>
 
 #define __global__
 #define __device__
@@ -56,6 +57,25 @@ inline Allocs& allocs() {
     static Allocs a;
     return a;
 }
+// Opt-in, for a single-threaded program (tests/cpp/test_host_io.cpp); off by default, and then only read.  `on`: every
+// hipMemcpyAsync and hipStreamSynchronize is logged, and the size of every hipMalloc.  fail_copy = N: the N-th hipMemcpyAsync from
+// now (0 = the next one) is logged and fails; fail_malloc: every hipMalloc fails.
+struct Call {
+    char kind;  // 'U' host to device, 'D' device to host, 'C' another copy, 'S' hipStreamSynchronize
+    const void *dst, *src;
+    size_t bytes;
+    hipStream_t stream;
+};
+struct Trace {
+    bool on = false, fail_malloc = false;
+    long fail_copy = -1;
+    std::vector<Call> calls;
+    std::vector<size_t> mallocs;
+};
+inline Trace& trace() {
+    static Trace t;
+    return t;
+}
 }  // namespace h2stub
 
 inline const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "success" : "stub error"; }
@@ -81,6 +101,10 @@ inline hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) {
 }
 inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
 inline hipError_t hipMalloc(void** p, size_t bytes) {
+    if (h2stub::trace().on) {
+        h2stub::trace().mallocs.push_back(bytes);
+        if (h2stub::trace().fail_malloc) return hipErrorOutOfMemory;
+    }
     *p = calloc(1, bytes ? bytes : 1);
     if (!*p) return hipErrorOutOfMemory;
     std::lock_guard<std::mutex> lk(h2stub::allocs().m);
@@ -114,7 +138,12 @@ inline hipError_t hipPointerGetAttributes(hipPointerAttribute_t* at, const void*
     at->device = it->second.second;
     return hipSuccess;
 }
-inline hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind, hipStream_t) {
+inline hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
+    if (h2stub::trace().on) {
+        h2stub::Trace& t = h2stub::trace();
+        t.calls.push_back({kind == hipMemcpyHostToDevice ? 'U' : kind == hipMemcpyDeviceToHost ? 'D' : 'C', dst, src, bytes, s});
+        if (t.fail_copy >= 0 && t.fail_copy-- == 0) return hipErrorUnknown;
+    }
     memmove(dst, src, bytes);
     return hipSuccess;
 }
@@ -131,7 +160,10 @@ inline hipError_t hipStreamDestroy(hipStream_t s) {
     free(s);
     return hipSuccess;
 }
-inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
+inline hipError_t hipStreamSynchronize(hipStream_t s) {
+    if (h2stub::trace().on) h2stub::trace().calls.push_back({'S', nullptr, nullptr, 0, s});
+    return hipSuccess;
+}
 inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
 inline hipError_t hipEventCreate(hipEvent_t* e) {
     *e = (hipEvent_t)malloc(8);

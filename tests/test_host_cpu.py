@@ -129,6 +129,23 @@ def test_engine_host_logic_under_asan(tmp_path):
     assert "AddressSanitizer" not in r.stderr and "LeakSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-6000:]
 
 
+def test_host_io_staging_under_asan(tmp_path):
+    """The host-pointer forms' staging helper (csrc/engine.h, HostIo) as its own program on the stub runtime, which logs every copy and
+    stream wait and fails one on request (tests/cpp/test_host_io.cpp): slot layout, pinned lookup, copy order, and the drain on every
+    error exit, under AddressSanitizer + UndefinedBehaviorSanitizer."""
+    csrc = os.path.join(ROOT, "halo2-pse_amd", "csrc")
+    cpp = os.path.join(ROOT, "tests", "cpp")
+    exe = str(tmp_path / "test_host_io")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+                           "-Wall", "-Wno-unknown-pragmas", "-I" + os.path.join(cpp, "hipstub"), "-I" + csrc,
+                           "-x", "c++", os.path.join(csrc, "api.hip"), os.path.join(cpp, "engine_stubs.cpp"), os.path.join(cpp, "test_host_io.cpp"),
+                           "-o", exe, "-lpthread", "-ldl"])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0 and "host io: ok" in r.stdout, r.stdout[-3000:] + r.stderr[-6000:]
+    assert "AddressSanitizer" not in r.stderr and "LeakSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-6000:]
+
+
 def test_bench_spawns_its_ranks_when_started_bare():
     """`python bench.py --gpus 2` with no WORLD_SIZE must start two ranks itself (the driver's launch shape) instead of
     exiting with a usage error.  There is no GPU here, so both ranks stop with the no-GPU message and the parent hands the
