@@ -875,12 +875,7 @@ static void release_ctx(Ctx* c) {
         if (kv.second.d_sample) (void)hipFree(kv.second.d_sample);
     }
     c->pinned.clear();
-    for (auto& kv : c->pinned_cols) (void)hipFree(kv.second.d);
-    c->pinned_cols.clear();
-    c->pinned_cols_bytes = 0;
-    for (auto& kv : c->pinned_parts) (void)hipFree(kv.second.d);
-    c->pinned_parts.clear();
-    c->pinned_parts_bytes = 0;
+    c->pins.clear();
     c->pin_flag.release();
     c->ntt_ws.release();
     c->ntt_io.release();
@@ -1034,47 +1029,97 @@ void column_sample(const uint64_t* h_col, size_t elems, uint8_t* out) {
     for (uint32_t k = 0; k < H2_COL_SAMPLES; k++) memcpy(out + 32 * k, h_col + 4 * pin_sample_index(elems, k), 32);
 }
 
-const Fe* pinned_column_lookup(Ctx* c, const uint64_t* h_col, size_t elems) {
-    auto it = c->pinned_cols.find(h_col);
-    if (it == c->pinned_cols.end()) return nullptr;
-    PinnedColumn& pc = it->second;
-    uint8_t now[H2_COL_SAMPLES * 32];
-    if (pc.elems == elems) column_sample(h_col, elems, now);
-    if (pc.elems != elems || memcmp(now, pc.sample, sizeof(now)) != 0) {  // another array lives at this address now: forget the copy
-        (void)hipDeviceSynchronize();
-        (void)hipFree(pc.d);
-        c->pinned_cols_bytes -= pc.elems * sizeof(Fe);
-        c->pinned_cols.erase(it);
-        return nullptr;
+// ---- the pin cache (engine.h, PinCache)
+Pin* PinCache::find(Kind kind, const void* key) {
+    auto it = pins.find({kind, key});
+    return it == pins.end() ? nullptr : &it->second;
+}
+
+void PinCache::drop(Pin* p) {
+    (void)hipFree(p->d);
+    p->d = nullptr;
+    auto it = pins.find({p->kind, p->key});
+    if (it == pins.end() || &it->second != p) return;  // never listed
+    bytes[p->kind] -= p->bytes;
+    count[p->kind]--;
+    pins.erase(it);
+}
+
+const Fe* PinCache::lookup(Kind kind, const void* key, bool dev, size_t elems, const PinDomain& dom) {
+    Pin* p = find(kind, key);
+    if (!p || p->device_key != dev || !(p->dom == dom)) return nullptr;
+    if (!dev) {
+        uint8_t now[H2_COL_SAMPLES * 32];
+        if (p->elems == elems) column_sample((const uint64_t*)key, elems, now);
+        if (p->elems != elems || memcmp(now, p->sample, sizeof(now)) != 0) {  // another array lives at this address now: forget the copy
+            (void)hipDeviceSynchronize();
+            drop(p);
+            return nullptr;
+        }
     }
-    pc.last_use = ++c->pinned_cols_tick;
-    return (const Fe*)pc.d;
+    p->last_use = ++tick;
+    return (const Fe*)p->d;
+}
+
+int PinCache::make_room(size_t need, size_t budget, bool* fits) {
+    *fits = need <= budget;
+    if (!*fits) return 0;
+    while (bytes[COLUMN] + bytes[PARTS] + need > budget) {
+        Pin* lru = nullptr;
+        for (auto& kv : pins)
+            if (!lru || kv.second.last_use < lru->last_use) lru = &kv.second;
+        if (!lru) break;
+        H2_CHECK(hipDeviceSynchronize());  // a queued evaluate_h may still read the copy
+        drop(lru);
+    }
+    return 0;
+}
+
+void PinCache::insert(Pin p) {
+    if (!p.device_key) column_sample((const uint64_t*)p.key, p.elems, p.sample);
+    p.last_use = ++tick;
+    bytes[p.kind] += p.bytes;
+    count[p.kind]++;
+    pins[{p.kind, p.key}] = p;
+}
+
+void PinCache::clear() {
+    while (!pins.empty()) drop(&pins.begin()->second);
+}
+
+const Fe* pinned_column_lookup(Ctx* c, const uint64_t* h_col, size_t elems) {
+    return c->pins.lookup(PinCache::COLUMN, h_col, false, elems, PinDomain());
 }
 
 // (the Entry of the caller holds the engine lock shared: the configuration cannot change under it)
-int pinned_make_room(Ctx* c, size_t bytes, bool* fits) {
-    const size_t budget = g_cfg.column_cache_bytes;
-    *fits = bytes <= budget;
-    if (!*fits) return 0;
-    while (c->pinned_cols_bytes + c->pinned_parts_bytes + bytes > budget) {  // least recently used first, whichever kind it is
-        auto vc = c->pinned_cols.end();
-        for (auto it = c->pinned_cols.begin(); it != c->pinned_cols.end(); ++it)
-            if (vc == c->pinned_cols.end() || it->second.last_use < vc->second.last_use) vc = it;
-        auto vp = c->pinned_parts.end();
-        for (auto it = c->pinned_parts.begin(); it != c->pinned_parts.end(); ++it)
-            if (vp == c->pinned_parts.end() || it->second.last_use < vp->second.last_use) vp = it;
-        if (vc == c->pinned_cols.end() && vp == c->pinned_parts.end()) break;
-        H2_CHECK(hipDeviceSynchronize());  // a queued evaluate_h may still read the copy
-        if (vp == c->pinned_parts.end() || (vc != c->pinned_cols.end() && vc->second.last_use < vp->second.last_use)) {
-            (void)hipFree(vc->second.d);
-            c->pinned_cols_bytes -= vc->second.elems * sizeof(Fe);
-            c->pinned_cols.erase(vc);
-        } else {
-            (void)hipFree(vp->second.d);
-            c->pinned_parts_bytes -= vp->second.bytes();
-            c->pinned_parts.erase(vp);
-        }
+int pinned_make_room(Ctx* c, size_t bytes, bool* fits) { return c->pins.make_room(bytes, g_cfg.column_cache_bytes, fits); }
+
+int pinned_unpin(PinCache::Kind kind, const void* const* keys, size_t count, const char* name) {
+    if (count && !keys) return H2HIP_EINVAL;
+    {
+        TuneRead r;  // the engine lock shared, without starting the engine: nothing is pinned in one that is not running
+        if (!ctx()->ready) return 0;
     }
+    Entry en(name);
+    if (en.rc) return en.rc;
+    bool synced = false;
+    for (size_t i = 0; i < count; i++) {
+        Pin* p = en.c->pins.find(kind, keys[i]);
+        if (!p) continue;
+        if (!synced) {
+            H2_CHECK(hipDeviceSynchronize());  // a queued evaluate_h may still read the copy
+            synced = true;
+        }
+        en.c->pins.drop(p);
+    }
+    return 0;
+}
+
+int pinned_info(PinCache::Kind kind, size_t* n, size_t* device_bytes, const char* name) {
+    Entry en(name);
+    if (en.rc) return en.rc;
+    if (n) *n = en.c->pins.count[kind];
+    if (device_bytes) *device_bytes = en.c->pins.bytes[kind];
     return 0;
 }
 
@@ -2100,7 +2145,8 @@ extern "C" int h2hip_columns_pin(const uint64_t* const* cols, size_t count, size
         bool fits;
         if (int rc = pinned_make_room(c, bytes, &fits)) return rc;  // the budget and its LRU are shared with the pinned part cosets
         if (!fits) continue;  // does not fit at all: the call stays correct, this column is uploaded per call
-        PinnedColumn pc;
+        Pin pc;
+        pc.kind = PinCache::COLUMN, pc.key = cols[i], pc.bytes = bytes, pc.elems = elems;
         if (hipMalloc(&pc.d, bytes) != hipSuccess) {
             (void)hipGetLastError();
             set_error("columns_pin: out of device memory after %zu of %zu columns (the rest is uploaded per call)", i, count);
@@ -2109,49 +2155,21 @@ extern "C" int h2hip_columns_pin(const uint64_t* const* cols, size_t count, size
         hipError_t e = hipMemcpyAsync(pc.d, cols[i], bytes, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) {
-            (void)hipFree(pc.d);
+            c->pins.drop(&pc);
             set_error("columns_pin: upload failed: %s", hipGetErrorString(e));
             return H2HIP_EDEVICE;
         }
-        pc.elems = elems;
-        pc.last_use = ++c->pinned_cols_tick;
-        column_sample(cols[i], elems, pc.sample);
-        c->pinned_cols[cols[i]] = pc;
-        c->pinned_cols_bytes += bytes;
+        c->pins.insert(pc);
     }
     return 0;
 }
 
 extern "C" int h2hip_columns_unpin(const uint64_t* const* cols, size_t count) {
-    if (count && !cols) return H2HIP_EINVAL;
-    {
-        std::shared_lock<std::shared_mutex> lk(g_engine_mu);
-        if (!ctx()->ready) return 0;  // nothing is pinned in an engine that is not running; the call never starts it
-    }
-    Entry en("h2hip_columns_unpin");
-    if (en.rc) return en.rc;
-    Ctx* c = en.c;
-    bool synced = false;
-    for (size_t i = 0; i < count; i++) {
-        auto it = c->pinned_cols.find(cols[i]);
-        if (it == c->pinned_cols.end()) continue;
-        if (!synced) {
-            H2_CHECK(hipDeviceSynchronize());  // a queued evaluate_h may still read the copy
-            synced = true;
-        }
-        (void)hipFree(it->second.d);
-        c->pinned_cols_bytes -= it->second.elems * sizeof(Fe);
-        c->pinned_cols.erase(it);
-    }
-    return 0;
+    return pinned_unpin(PinCache::COLUMN, (const void* const*)cols, count, "h2hip_columns_unpin");
 }
 
 extern "C" int h2hip_columns_pinned_info(size_t* n_columns, size_t* device_bytes) {
-    Entry en("h2hip_columns_pinned_info");
-    if (en.rc) return en.rc;
-    if (n_columns) *n_columns = en.c->pinned_cols.size();
-    if (device_bytes) *device_bytes = en.c->pinned_cols_bytes;
-    return 0;
+    return pinned_info(PinCache::COLUMN, n_columns, device_bytes, "h2hip_columns_pinned_info");
 }
 
 // record form of the window tables pinned from now on: 0 = the engine's choice, 64 = E-form, 80 / 128 = native records at that stride

@@ -116,27 +116,55 @@ struct PinnedBases {
 
 struct Ctx;
 
-// A constant column of a proving key (pk.fixed_cosets, pk.l0 / l_last / l_active_row, pk.permutation.cosets) kept in HBM across
-// evaluate_h calls, keyed by the host pointer and guarded by a fingerprint as the pinned bases are (api.hip, h2hip_columns_pin)
+// ---- the pin cache (api.hip): a proving key's constant data kept in HBM across evaluate_h calls, under one budget
+// (HALO2_HIP_COLUMN_CACHE_GB) and one LRU clock.  Two kinds of entry, keyed by (kind, the caller's pointer), so that the same pointer
+// may be pinned as both:
+//   COLUMN  h2hip_columns_pin: a column in evaluation form (pk.fixed_cosets, pk.l0 / l_last / l_active_row, pk.permutation.cosets),
+//           `elems` elements, keyed by its host pointer;
+//   PARTS   h2hip_part_cosets_pin (evalh.hip builds them): all P = 2^(ek - k) part cosets of one coefficient-form polynomial,
+//           part-major -- part p is the 2^k elements at d + p * 2^k --, keyed by a host or a device pointer and tagged with the domain.
+// A host key is guarded by a fingerprint as the pinned bases are: H2_COL_SAMPLES sampled elements of the caller's `elems`-element array
+// (column_sample), compared on every lookup, so a freed and reused allocation at the same address misses; a device key rests on the
+// caller's contract, because the device form never waits for a verdict.
 #define H2_COL_SAMPLES 16
-struct PinnedColumn {
-    void* d = nullptr;
-    size_t elems = 0;
-    uint64_t last_use = 0;
-    uint8_t sample[H2_COL_SAMPLES * 32];
-};
-
-// All P = 2^(ek - k) part cosets of one coefficient-form polynomial of a proving key (h2hip_part_cosets_pin, evalh.hip), part-major: part p
-// is the 2^k elements at d + p * 2^k.  Keyed by the caller's pointer -- a map of its own, so the same pointer may also be a pinned column
-// -- and by the domain; host keys are guarded by the column fingerprint, device keys by the caller's contract.
-struct PinnedParts {
-    void* d = nullptr;
+struct PinDomain {  // what a PARTS entry was built for; all zero in a COLUMN entry
     uint32_t k = 0, ek = 0;
-    Fe ext_omega, g_coset;
+    Fe ext_omega = {}, g_coset = {};
+    bool operator==(const PinDomain& o) const {
+        return k == o.k && ek == o.ek && memcmp(&ext_omega, &o.ext_omega, sizeof(Fe)) == 0 && memcmp(&g_coset, &o.g_coset, sizeof(Fe)) == 0;
+    }
+};
+struct Pin {
+    int kind = 0;               // PinCache::Kind
+    const void* key = nullptr;  // the caller's pointer
+    void* d = nullptr;
+    size_t bytes = 0;
+    size_t elems = 0;  // elements of the caller's array, the length the fingerprint sampled: the column's, or 2^k coefficients
     bool device_key = false;
+    PinDomain dom;
     uint64_t last_use = 0;
-    uint8_t sample[H2_COL_SAMPLES * 32];
-    size_t bytes() const { return sizeof(Fe) << ek; }
+    uint8_t sample[H2_COL_SAMPLES * 32] = {};
+};
+struct PinCache {
+    enum Kind { COLUMN = 0, PARTS = 1 };
+    std::map<std::pair<int, const void*>, Pin> pins;
+    size_t count[2] = {0, 0}, bytes[2] = {0, 0};  // by kind
+    uint64_t tick = 0;
+    Pin* find(Kind kind, const void* key);
+    // the device copy of `key` for this call, or nullptr.  An entry with the other kind of key or another domain is not this call's and
+    // stays.  A host key whose array has another length now, or other sampled elements, is dropped (behind a device synchronisation: a
+    // queued call may still read it).  A hit advances the clock.  COLUMN: dev = false, dom = PinDomain().
+    const Fe* lookup(Kind kind, const void* key, bool dev, size_t elems, const PinDomain& dom);
+    // room for `need` more bytes within `budget`: least recently used entries of either kind are dropped, each behind a device
+    // synchronisation, until it fits.  *fits = false: `need` exceeds the whole budget, nothing was dropped.
+    int make_room(size_t need, size_t budget, bool* fits);
+    // list p (kind, key, d, bytes, elems, device_key, dom set by the caller, d filled and complete; no entry of that kind and key is
+    // listed): takes a host key's fingerprint and stamps the clock
+    void insert(Pin p);
+    // The one place a pin's device memory is freed and its bytes leave the count.  p is a listed entry -- the caller has synchronised
+    // the device if a queued kernel may read it, once per public call is enough -- or one whose upload or build failed before insert().
+    void drop(Pin* p);
+    void clear();  // release_ctx, behind its device synchronisation
 };
 
 struct StageTimer {
@@ -212,11 +240,7 @@ struct Ctx {
     std::map<TwiddleKey, TwiddleTable> twiddles;
     size_t tw_full_bytes = 0;  // HBM held by the two-pass plan's full inter-pass twiddle tables
     std::map<const void*, PinnedBases> pinned;
-    std::map<const void*, PinnedColumn> pinned_cols;  // h2hip_columns_pin: the host-pointer evaluate_h finds a proving key's constant columns here
-    size_t pinned_cols_bytes = 0;
-    uint64_t pinned_cols_tick = 0;
-    std::map<const void*, PinnedParts> pinned_parts;  // h2hip_part_cosets_pin: the parts form of evaluate_h finds the key's part cosets here
-    size_t pinned_parts_bytes = 0;                    // (one budget, one LRU clock with the pinned columns: pinned_make_room)
+    PinCache pins;  // h2hip_columns_pin, h2hip_part_cosets_pin: both forms of evaluate_h find a proving key's constant data here
     // profiling
     bool profiling = false;        // every stage bracketed by a pair of events (each record costs the stream ~10 us)
     bool profiling_kernel = false; // only the dominant kernel, timed through its own dispatch (hipExtLaunchKernelGGL): no gap
@@ -644,11 +668,12 @@ int lookup_sort_enqueue(const Fe* const* d_src, Fe* const* d_k0, Fe* const* d_k1
 // setup.hip
 int kzg_setup_device(Ctx* c, uint32_t k, const Fe& s, Affine* d_g, Affine* d_gl, hipStream_t stream);
 
-// api.hip: the fingerprint of a host column (H2_COL_SAMPLES elements); room for `bytes` more in the budget the pinned columns and the
-// pinned part cosets share (HALO2_HIP_COLUMN_CACHE_GB), least recently used entries of either kind dropped first -- false: `bytes`
-// exceed the whole budget, nothing was dropped
+// api.hip: the fingerprint of a host column (H2_COL_SAMPLES elements); PinCache::make_room with the configured budget
+// (HALO2_HIP_COLUMN_CACHE_GB); the bodies of the two kinds' unpin and pinned_info entry points -- unpin never starts a stopped engine
 void column_sample(const uint64_t* h_col, size_t elems, uint8_t* out);
 int pinned_make_room(Ctx* c, size_t bytes, bool* fits);
+int pinned_unpin(PinCache::Kind kind, const void* const* keys, size_t count, const char* name);
+int pinned_info(PinCache::Kind kind, size_t* n, size_t* device_bytes, const char* name);
 
 // evalh.hip
 void evalh_modules_free(Ctx* c);                            // unload this device's generated kernels (release_ctx)

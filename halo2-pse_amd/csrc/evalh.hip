@@ -2144,29 +2144,9 @@ static int evaluate_h_parts_validate(const h2hip_evalh_parts_desc* d, const void
 }
 
 // ---- pinned part cosets (h2hip_part_cosets_pin below).  The entry of `key` for this domain: part p is the 2^k elements at the result
-// + p * 2^k.  A host key's fingerprint is compared with the caller's memory on every use, and on a mismatch the entry is dropped --
-// after a device synchronisation, since a queued call may still read it -- and the call goes on as if nothing were pinned; a device key
-// rests on the caller's contract, because the device form never waits for a verdict.
-static const Fe* pinned_parts_lookup(Ctx* c, const void* key, bool dev, uint32_t k, uint32_t ek, const Fe& ext_omega, const Fe& g_coset) {
-    auto it = c->pinned_parts.find(key);
-    if (it == c->pinned_parts.end()) return nullptr;
-    PinnedParts& pp = it->second;
-    if (pp.device_key != dev || pp.k != k || pp.ek != ek || memcmp(&pp.ext_omega, &ext_omega, sizeof(Fe)) != 0 ||
-        memcmp(&pp.g_coset, &g_coset, sizeof(Fe)) != 0)
-        return nullptr;  // pinned for another domain, or another kind of key: not this call's
-    if (!dev) {
-        uint8_t now[H2_COL_SAMPLES * 32];
-        column_sample((const uint64_t*)key, (size_t)1 << k, now);
-        if (memcmp(now, pp.sample, sizeof(now)) != 0) {  // another array lives at this address now: forget the entry
-            (void)hipDeviceSynchronize();
-            (void)hipFree(pp.d);
-            c->pinned_parts_bytes -= pp.bytes();
-            c->pinned_parts.erase(it);
-            return nullptr;
-        }
-    }
-    pp.last_use = ++c->pinned_cols_tick;
-    return (const Fe*)pp.d;
+// + p * 2^k (engine.h, PinCache::lookup: a stale host key is dropped and the call goes on as if nothing were pinned)
+static const Fe* part_cosets_lookup(Ctx* c, const void* key, bool dev, const PinDomain& dom) {
+    return c->pins.lookup(PinCache::PARTS, key, dev, (size_t)1 << dom.k, dom);
 }
 
 // what the last parts call of this thread did (h2hip_debug_evalh_parts_stats): columns scaled and transformed and columns served from
@@ -2212,7 +2192,9 @@ static int evaluate_h_parts_host(Ctx* c, const h2hip_evalh_parts_desc* d, const 
     // ---- the key's polynomials whose part cosets are pinned; the others are `live`: uploaded (host form), scaled and transformed per part
     std::vector<const Fe*> pin(n_main, nullptr);
     {
-        auto look = [&](size_t i) { pin[i] = pinned_parts_lookup(c, polys[i], dev, k, ek, ext_omega, g_coset); };
+        PinDomain dom;
+        dom.k = k, dom.ek = ek, dom.ext_omega = ext_omega, dom.g_coset = g_coset;
+        auto look = [&](size_t i) { pin[i] = part_cosets_lookup(c, polys[i], dev, dom); };
         for (uint32_t i = 0; i < d->n_fixed; i++) look(i);
         for (size_t i = 0; i < 3; i++) look(at_l0 + i);
         if (d->n_perm_sets)
@@ -2678,19 +2660,19 @@ static int part_cosets_pin(const void* const* polys, size_t count, uint32_t k, u
     hipStream_t s = dev ? stream : c->stream;
     const Fe w = fe_from_u64x4(extended_omega), g = fe_from_u64x4(g_coset), gi = fe_from_u64x4(g_coset_inv);
     const size_t n = (size_t)1 << k, P = (size_t)1 << (ek - k), bytes = sizeof(Fe) << ek;
+    PinDomain dom;
+    dom.k = k, dom.ek = ek, dom.ext_omega = w, dom.g_coset = g;
     for (size_t i = 0; i < count; i++) {
-        if (pinned_parts_lookup(c, polys[i], dev, k, ek, w, g)) continue;  // already there (and, a host key, still the same array)
-        auto old = c->pinned_parts.find(polys[i]);
-        if (old != c->pinned_parts.end()) {  // pinned for another domain: this one replaces it
+        if (part_cosets_lookup(c, polys[i], dev, dom)) continue;  // already there (and, a host key, still the same array)
+        if (Pin* old = c->pins.find(PinCache::PARTS, polys[i])) {  // pinned for another domain: this one replaces it
             H2_CHECK(hipDeviceSynchronize());
-            (void)hipFree(old->second.d);
-            c->pinned_parts_bytes -= old->second.bytes();
-            c->pinned_parts.erase(old);
+            c->pins.drop(old);
         }
         bool fits;
         if (int rc = pinned_make_room(c, bytes, &fits)) return rc;
         if (!fits) continue;  // larger than the whole budget: left unpinned, every call stays correct
-        PinnedParts pp;
+        Pin pp;
+        pp.kind = PinCache::PARTS, pp.key = polys[i], pp.bytes = bytes, pp.elems = n, pp.device_key = dev, pp.dom = dom;
         if (hipMalloc(&pp.d, bytes) != hipSuccess) {
             (void)hipGetLastError();
             set_error("part_cosets_pin: out of device memory after %zu of %zu polynomials (the rest is transformed per call)", i, count);
@@ -2717,15 +2699,10 @@ static int part_cosets_pin(const void* const* polys, size_t count, uint32_t k, u
         }
         if (rc) {
             (void)hipDeviceSynchronize();
-            (void)hipFree(pp.d);
+            c->pins.drop(&pp);
             return rc;
         }
-        pp.k = k, pp.ek = ek, pp.ext_omega = w, pp.g_coset = g, pp.device_key = dev;
-        pp.last_use = ++c->pinned_cols_tick;
-        memset(pp.sample, 0, sizeof(pp.sample));
-        if (!dev) column_sample((const uint64_t*)polys[i], n, pp.sample);
-        c->pinned_parts[polys[i]] = pp;
-        c->pinned_parts_bytes += bytes;
+        c->pins.insert(pp);
     }
     return 0;
 }
@@ -2740,36 +2717,10 @@ int h2hip_part_cosets_pin_device(const void* const* d_polys, size_t count, uint3
     return part_cosets_pin(d_polys, count, k, extended_k, extended_omega, g_coset, g_coset_inv, true, (hipStream_t)stream);
 }
 
-int h2hip_part_cosets_unpin(const void* const* polys, size_t count) {
-    if (count && !polys) return H2HIP_EINVAL;
-    {
-        TuneRead r;  // the engine lock shared, without starting the engine: nothing is pinned in one that is not running
-        if (!ctx()->ready) return 0;
-    }
-    Entry en("h2hip_part_cosets_unpin");
-    if (en.rc) return en.rc;
-    Ctx* c = en.c;
-    bool synced = false;
-    for (size_t i = 0; i < count; i++) {
-        auto it = c->pinned_parts.find(polys[i]);
-        if (it == c->pinned_parts.end()) continue;
-        if (!synced) {
-            H2_CHECK(hipDeviceSynchronize());  // a queued evaluate_h may still read the entry
-            synced = true;
-        }
-        (void)hipFree(it->second.d);
-        c->pinned_parts_bytes -= it->second.bytes();
-        c->pinned_parts.erase(it);
-    }
-    return 0;
-}
+int h2hip_part_cosets_unpin(const void* const* polys, size_t count) { return pinned_unpin(PinCache::PARTS, polys, count, "h2hip_part_cosets_unpin"); }
 
 int h2hip_part_cosets_pinned_info(size_t* n_polys, size_t* device_bytes) {
-    Entry en("h2hip_part_cosets_pinned_info");
-    if (en.rc) return en.rc;
-    if (n_polys) *n_polys = en.c->pinned_parts.size();
-    if (device_bytes) *device_bytes = en.c->pinned_parts_bytes;
-    return 0;
+    return pinned_info(PinCache::PARTS, n_polys, device_bytes, "h2hip_part_cosets_pinned_info");
 }
 
 // test hook: what the last parts call of the calling thread did (g_parts_stats)

@@ -59,15 +59,16 @@ inline Allocs& allocs() {
 }
 // Opt-in, for a single-threaded program (tests/cpp/test_host_io.cpp); off by default, and then only read.  `on`: every
 // hipMemcpyAsync and hipStreamSynchronize is logged, and the size of every hipMalloc.  fail_copy = N: the N-th hipMemcpyAsync from
-// now (0 = the next one) is logged and fails; fail_malloc: every hipMalloc fails.
+// now (0 = the next one) is logged and fails; fail_malloc: every hipMalloc fails.  `frees` (with `on`, tests/cpp/test_pin_cache.cpp): every
+// hipFree of a non-null pointer and every hipDeviceSynchronize is logged too.
 struct Call {
-    char kind;  // 'U' host to device, 'D' device to host, 'C' another copy, 'S' hipStreamSynchronize
+    char kind;  // 'U' host to device, 'D' device to host, 'C' another copy, 'S' hipStreamSynchronize, 'F' hipFree (dst), 'Y' hipDeviceSynchronize
     const void *dst, *src;
     size_t bytes;
     hipStream_t stream;
 };
 struct Trace {
-    bool on = false, fail_malloc = false;
+    bool on = false, fail_malloc = false, frees = false;
     long fail_copy = -1;
     std::vector<Call> calls;
     std::vector<size_t> mallocs;
@@ -99,7 +100,10 @@ inline hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) {
     p->multiProcessorCount = 256;
     return hipSuccess;
 }
-inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
+inline hipError_t hipDeviceSynchronize() {
+    if (h2stub::trace().on && h2stub::trace().frees) h2stub::trace().calls.push_back({'Y', nullptr, nullptr, 0, nullptr});
+    return hipSuccess;
+}
 inline hipError_t hipMalloc(void** p, size_t bytes) {
     if (h2stub::trace().on) {
         h2stub::trace().mallocs.push_back(bytes);
@@ -113,6 +117,7 @@ inline hipError_t hipMalloc(void** p, size_t bytes) {
 }
 inline hipError_t hipFree(void* p) {
     if (!p) return hipSuccess;
+    if (h2stub::trace().on && h2stub::trace().frees) h2stub::trace().calls.push_back({'F', p, nullptr, 0, nullptr});
     {
         std::lock_guard<std::mutex> lk(h2stub::allocs().m);
         h2stub::allocs().by_ptr.erase(p);

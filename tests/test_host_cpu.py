@@ -146,6 +146,24 @@ def test_host_io_staging_under_asan(tmp_path):
     assert "AddressSanitizer" not in r.stderr and "LeakSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-6000:]
 
 
+def test_pin_cache_under_asan(tmp_path):
+    """The cache of pinned columns and pinned part cosets (csrc/engine.h, PinCache) as its own program on the stub runtime, which logs
+    every hipFree and hipDeviceSynchronize (tests/cpp/test_pin_cache.cpp): with a budget of three small entries, eviction in clock order
+    across both kinds behind a device synchronisation, the oversized request, the fingerprint and domain rules of a lookup, one pointer
+    under both kinds, and every entry freed exactly once, under AddressSanitizer + UndefinedBehaviorSanitizer with leak detection on."""
+    csrc = os.path.join(ROOT, "halo2-pse_amd", "csrc")
+    cpp = os.path.join(ROOT, "tests", "cpp")
+    exe = str(tmp_path / "test_pin_cache")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+                           "-Wall", "-Wno-unknown-pragmas", "-I" + os.path.join(cpp, "hipstub"), "-I" + csrc,
+                           "-x", "c++", os.path.join(csrc, "api.hip"), os.path.join(cpp, "engine_stubs.cpp"), os.path.join(cpp, "test_pin_cache.cpp"),
+                           "-o", exe, "-lpthread", "-ldl"])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0 and "pin cache: ok" in r.stdout, r.stdout[-3000:] + r.stderr[-6000:]
+    assert "AddressSanitizer" not in r.stderr and "LeakSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-6000:]
+
+
 def test_bench_spawns_its_ranks_when_started_bare():
     """`python bench.py --gpus 2` with no WORLD_SIZE must start two ranks itself (the driver's launch shape) instead of
     exiting with a usage error.  There is no GPU here, so both ranks stop with the no-GPU message and the parent hands the
