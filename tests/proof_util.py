@@ -1,6 +1,7 @@
 """Helpers of the proof tests: the package's transcript / prover / verifier modules (loaded through conftest.load_pkg(), as evalh_util
 does), Python-integer affine arithmetic on bn256 G1 for closing the verifier's check with the setup secret, and the SYSTEM of
-check_util.py as a ConstraintSystem with a witness whose selector is one on a few rows only, so that its instance column is short."""
+check_util.py as a ConstraintSystem with a witness whose selector is one on a few rows only, so that its instance column is short, and
+Setup: params and keys of any System (systems_util.py has the family), that SYSTEM by default."""
 import importlib
 import random
 
@@ -98,35 +99,86 @@ def instance_of(cols):
     return [cols["instance"][0][:ACTIVE + 1]]
 
 
-class Setup:
-    """params, proving key and verifying key of the SYSTEM at one k (one fixed-column assignment serves every witness of the tests)"""
+PLACEHOLDER_CHALLENGES = (7, 11, 13)  # stand in for the transcript's challenges where columns are built without a proof
 
-    def __init__(self, k, seed=0xC0FFEE):
-        self.k, self.n = k, 1 << k
-        self.cs = system_cs()
+
+class System:
+    """One constraint system of the proof tests.  cs: its prover.ConstraintSystem; copies: (column, row, column, row) over
+    cs.permutation; k: the size it runs at; columns(seed, k, b, fixed, challenges): canonical-integer columns {"fixed", "advice",
+    "instance"} of a witness that satisfies the system by construction -- fixed (None: drawn from the seed) holds the fixed columns of
+    an earlier call, for another witness under the same key, challenges the cs.num_challenges challenge values the advice columns of
+    later phases are computed from; instance_of(cols): the instance values create_proof and verify_proof take; n_instances: how many
+    proof instances prove() makes by default."""
+
+    def __init__(self, name, cs, copies, k, columns, instance_of, n_instances=1):
+        self.name, self.cs, self.copies, self.k = name, cs, list(copies), k
+        self.columns, self.instance_of, self.n_instances = columns, instance_of, n_instances
+
+
+def _system_entry_columns(seed, k, b, fixed=None, challenges=None):
+    return system_columns(seed, k, b, table=None if fixed is None else fixed[1])
+
+
+def system_entry():
+    """the SYSTEM of check_util.py (its columns do not depend on the challenge)"""
+    return System("system", system_cs(), cu.SYSTEM_COPIES, 5, _system_entry_columns, instance_of)
+
+
+class Setup:
+    """params, proving key and verifying key of one system at one k (one fixed-column assignment serves every witness of the tests);
+    system defaults to the SYSTEM of check_util.py, k to the system's own"""
+
+    def __init__(self, k=None, seed=0xC0FFEE, system=None):
+        self.system = system_entry() if system is None else system
+        self.k = self.system.k if k is None else k
+        self.n = 1 << self.k
+        self.cs = self.system.cs
         self.b = self.cs.blinding_factors()
         self.u = self.n - self.b - 1
-        self.cols = system_columns(seed, k, self.b)
-        self.params = h2.ParamsKZG.setup(k, SECRET)
+        self.seed = seed
+        self.cols = self.columns(seed)
+        self.params = h2.ParamsKZG.setup(self.k, SECRET)
         self.fixed = [to_mont(c) for c in self.cols["fixed"]]
-        self.pk = prover.ProvingKey.build(self.params, self.cs, self.fixed, cu.SYSTEM_COPIES, VK_REPR)
+        self.pk = prover.ProvingKey.build(self.params, self.cs, self.fixed, self.system.copies, VK_REPR)
+
+    def columns(self, seed, challenges=None):
+        """the witness of `seed` under this key's fixed columns (the key's own seed draws them), for the given challenges"""
+        challenges = list(PLACEHOLDER_CHALLENGES[:self.cs.num_challenges]) if challenges is None else list(challenges)
+        fixed = None if seed == self.seed else self.cols["fixed"]
+        return self.system.columns(seed, self.k, self.b, fixed, challenges)
+
+    def witness_of(self, seed):
+        """a witness that follows the challenges it is handed: challenges -> columns"""
+        return lambda challenges: self.columns(seed, challenges)
+
+    def default_witnesses(self):
+        return [self.witness_of(self.seed + i) for i in range(self.system.n_instances)]
 
     def witness_fn(self, columns_per_instance, resident):
-        """create_proof's witness callback over canonical-integer advice columns: a and b in phase 0, c in phase 1, fresh arrays (the
-        prover consumes them), uploaded by the callback when resident"""
+        """create_proof's witness callback over canonical-integer advice columns (a dict of columns, or a function from the challenges
+        to one): the advice columns of the phase in column order, fresh arrays (the prover consumes them), uploaded by the callback
+        when resident.  A challenge is handed over exactly when its phase has passed."""
+        cs = self.cs
+
         def witness(i, phase, challenges):
-            assert (challenges[0] is None) == (phase == 0)
-            adv = columns_per_instance[i]["advice"]
-            out = [to_mont(c) for c in (adv[:2] if phase == 0 else adv[2:])]
+            assert [c is None for c in challenges] == [p >= phase for p in cs.challenge_phase]
+            entry = columns_per_instance[i]
+            cols = entry([0 if c is None else c for c in challenges]) if callable(entry) else entry
+            out = [to_mont(cols["advice"][c]) for c, p in enumerate(cs.advice_column_phase) if p == phase]
             if resident:
                 import torch
                 out = [torch.from_numpy(a.view(np.int64)).cuda() for a in out]
             return out
         return witness
 
+    def instances_of(self, columns_per_instance):
+        """the instance values of each witness (they do not depend on the challenges)"""
+        placeholder = list(PLACEHOLDER_CHALLENGES[:self.cs.num_challenges])
+        return [self.system.instance_of(c(placeholder) if callable(c) else c) for c in columns_per_instance]
+
     def prove(self, columns_per_instance=None, multiopen="shplonk", form="parts", resident=True, seed=b"\x07" * 32, instances=None):
-        columns_per_instance = [self.cols] if columns_per_instance is None else columns_per_instance
-        instances = [instance_of(c) for c in columns_per_instance] if instances is None else instances
+        columns_per_instance = self.default_witnesses() if columns_per_instance is None else columns_per_instance
+        instances = self.instances_of(columns_per_instance) if instances is None else instances
         return prover.create_proof(self.params, self.pk, instances, self.witness_fn(columns_per_instance, resident), transcript.Blake2bWrite(),
                                    seed, multiopen=multiopen, form=form, resident=resident)
 
