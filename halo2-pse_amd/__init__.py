@@ -7,6 +7,9 @@ reference (halo2_proofs::arithmetic::{best_multiexp, best_fft}, poly::Evaluation
 poly::kzg::ParamsKZG).  There is no CPU fallback here: if the library or the GPU is
 missing, calls raise.
 
+Every entry point's prototype is stated once, in _abi.py (generated from the headers by tools/gen_ctypes_abi.py) and bound by
+lib(): call sites pass plain Python ints and bools for the by-value parameters, and ctypes refuses a wrong argument count.
+
 Arrays: numpy uint64 -- Fr elements (n,4), G1Affine (n,8), G1 Jacobian (12,): 4 x u64 LE limbs,
 Montgomery form (halo2curves' in-memory / RawBytes layout).
 """
@@ -16,9 +19,10 @@ import subprocess
 
 import numpy as np
 
+from ._abi import PROTOTYPES
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HALO2_HIP_LIB") or os.path.join(_HERE, "libhalo2hip.so")  # HALO2_HIP_LIB: another build of the library (A/B measurements)
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "halo2hip.h")
 
 _lib = None
 
@@ -50,15 +54,16 @@ def lib():
         except ImportError:
             pass
         L = ctypes.CDLL(LIB_PATH)
-        L.h2hip_last_error.restype = ctypes.c_char_p
-        L.h2hip_version.restype = ctypes.c_char_p
-        L.h2hip_get_msm_window.restype = ctypes.c_uint32
-        L.h2hip_get_msm_window.argtypes = [ctypes.c_size_t]
-        L.h2hip_get_msm_window_fixed_base.restype = ctypes.c_uint32
-        L.h2hip_get_msm_window_fixed_base.argtypes = [ctypes.c_size_t]
-        L.h2hip_msm_min_n.restype = ctypes.c_size_t
-        L.h2hip_ntt_min_log_n.restype = ctypes.c_uint32
-        L.h2hip_lazy_pin_after.restype = ctypes.c_uint32
+        # every entry point's prototype, generated from the headers (tools/gen_ctypes_abi.py): ctypes then converts plain ints at the
+        # declared width and refuses a wrong argument count.  Bare argtypes would let a cdecl function take surplus arguments; naming
+        # each parameter an input (paramflags) makes the count exact.  Another build (HALO2_HIP_LIB) may lack a name; tests/test_abi.py
+        # holds the in-tree one to all of them.
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            try:
+                fn = ctypes.CFUNCTYPE(restype, *argtypes)((name, L), ((1,),) * len(argtypes))
+            except AttributeError:
+                continue
+            setattr(L, name, fn)
         # release streams, workspaces and worker threads while the HIP runtime is still alive (a profiler's own
         # finalisation otherwise meets them in the static destructors at process exit)
         import atexit
@@ -121,7 +126,7 @@ def best_multiexp(coeffs, bases):
     coeffs, bases = _u64(coeffs, 4), _u64(bases, 8)
     assert coeffs.shape[0] == bases.shape[0]  # assert_eq!(coeffs.len(), bases.len()), arithmetic.rs:133
     out = np.zeros(12, dtype=np.uint64)
-    _check(lib().h2hip_msm_bn254(_p(coeffs), _p(bases), ctypes.c_size_t(coeffs.shape[0]), _p(out)), "h2hip_msm_bn254")
+    _check(lib().h2hip_msm_bn254(_p(coeffs), _p(bases), coeffs.shape[0], _p(out)), "h2hip_msm_bn254")
     return out
 
 
@@ -136,7 +141,7 @@ def best_multiexp_batch(coeffs_list, bases):
     count = len(cols)
     ptrs = (ctypes.c_void_p * count)(*[c.ctypes.data for c in cols])
     out = np.zeros((count, 12), dtype=np.uint64)
-    _check(lib().h2hip_msm_bn254_batch(ptrs, _p(bases), ctypes.c_size_t(n), ctypes.c_size_t(count), _p(out)), "h2hip_msm_bn254_batch")
+    _check(lib().h2hip_msm_bn254_batch(ptrs, _p(bases), n, count, _p(out)), "h2hip_msm_bn254_batch")
     return out
 
 
@@ -144,7 +149,7 @@ def best_fft(a, omega, log_n):
     """halo2_proofs::arithmetic::best_fft (arithmetic.rs:171-234) for G = bn256::Fr; in place on `a`."""
     assert a.dtype == np.uint64 and a.flags["C_CONTIGUOUS"]
     assert a.shape == (1 << log_n, 4)  # assert_eq!(n, 1 << log_n), arithmetic.rs:184
-    _check(lib().h2hip_ntt_bn254_fr(_p(a), _p(_fe(omega)), ctypes.c_uint32(log_n)), "h2hip_ntt_bn254_fr")
+    _check(lib().h2hip_ntt_bn254_fr(_p(a), _p(_fe(omega)), log_n), "h2hip_ntt_bn254_fr")
 
 
 def _host_ptrs(arrays):
@@ -156,7 +161,7 @@ def best_fft_batch(columns, omega, log_n):
     for a in columns:
         assert a.dtype == np.uint64 and a.flags["C_CONTIGUOUS"] and a.shape == (1 << log_n, 4)
     if columns:
-        _check(lib().h2hip_ntt_bn254_fr_batch(_host_ptrs(columns), ctypes.c_size_t(len(columns)), _p(_fe(omega)), ctypes.c_uint32(log_n)),
+        _check(lib().h2hip_ntt_bn254_fr_batch(_host_ptrs(columns), len(columns), _p(_fe(omega)), log_n),
                "h2hip_ntt_bn254_fr_batch")
 
 
@@ -165,14 +170,14 @@ def g_to_lagrange(g, k):
     g = _u64(g, 8)
     assert g.shape[0] == 1 << k
     out = np.zeros((1 << k, 8), dtype=np.uint64)
-    _check(lib().h2hip_g_to_lagrange_bn254(_p(g), ctypes.c_uint32(k), _p(out)), "h2hip_g_to_lagrange_bn254")
+    _check(lib().h2hip_g_to_lagrange_bn254(_p(g), k, _p(out)), "h2hip_g_to_lagrange_bn254")
     return out
 
 
 def best_fft_g1(a_xyz, omega, log_n):
     """halo2_proofs::arithmetic::best_fft for G = bn256::G1 (arithmetic.rs:171-234): in place on (2^log_n, 12) Jacobian points"""
     assert a_xyz.dtype == np.uint64 and a_xyz.flags["C_CONTIGUOUS"] and a_xyz.shape == (1 << log_n, 12)
-    _check(lib().h2hip_fft_bn254_g1(_p(a_xyz), _p(_fe(omega)), ctypes.c_uint32(log_n)), "h2hip_fft_bn254_g1")
+    _check(lib().h2hip_fft_bn254_g1(_p(a_xyz), _p(_fe(omega)), log_n), "h2hip_fft_bn254_g1")
 
 
 def g1_to_affine(xyz):
@@ -185,13 +190,13 @@ def g1_to_affine(xyz):
 def g1_fold(partials):
     partials = np.ascontiguousarray(partials, dtype=np.uint64).reshape(-1, 12)
     out = np.zeros(12, dtype=np.uint64)
-    _check(lib().h2hip_g1_fold(_p(partials), ctypes.c_size_t(partials.shape[0]), _p(out)), "h2hip_g1_fold")
+    _check(lib().h2hip_g1_fold(_p(partials), partials.shape[0], _p(out)), "h2hip_g1_fold")
     return out
 
 
 def bases_pin(bases):
     assert bases.dtype == np.uint64 and bases.flags["C_CONTIGUOUS"]
-    _check(lib().h2hip_bases_pin(_p(bases), ctypes.c_size_t(bases.shape[0])), "h2hip_bases_pin")
+    _check(lib().h2hip_bases_pin(_p(bases), bases.shape[0]), "h2hip_bases_pin")
 
 
 def bases_unpin(bases):
@@ -216,7 +221,7 @@ def bases_pin_device(d_bases, n=None):
     without bases_unpin_device the entry goes with it (the library's own fingerprint check is the second line of defence)."""
     import weakref
     n = d_bases.numel() * d_bases.element_size() // 64 if n is None else int(n)
-    _check(lib().h2hip_bases_pin_device(_dptr(d_bases), ctypes.c_size_t(n), _stream()), "h2hip_bases_pin_device")
+    _check(lib().h2hip_bases_pin_device(_dptr(d_bases), n, _stream()), "h2hip_bases_pin_device")
     addr = d_bases.data_ptr()
     old = _device_pins.pop(addr, None)
     if old is not None:
@@ -241,13 +246,13 @@ def columns_pin(columns):
         return
     for a in cols:
         assert a.dtype == np.uint64 and a.flags["C_CONTIGUOUS"] and a.shape == cols[0].shape and a.shape[1] == 4
-    _check(lib().h2hip_columns_pin(_host_ptrs(cols), ctypes.c_size_t(len(cols)), ctypes.c_size_t(cols[0].shape[0])), "h2hip_columns_pin")
+    _check(lib().h2hip_columns_pin(_host_ptrs(cols), len(cols), cols[0].shape[0]), "h2hip_columns_pin")
 
 
 def columns_unpin(columns):
     cols = list(columns)
     if cols:
-        _check(lib().h2hip_columns_unpin(_host_ptrs(cols), ctypes.c_size_t(len(cols))), "h2hip_columns_unpin")
+        _check(lib().h2hip_columns_unpin(_host_ptrs(cols), len(cols)), "h2hip_columns_unpin")
 
 
 def columns_pinned_info():
@@ -263,7 +268,7 @@ _part_pins = {}  # address -> weakref.finalize on the array (or the tensor's sto
 def _part_unpin_address(addr):
     _part_pins.pop(addr, None)
     try:
-        lib().h2hip_part_cosets_unpin((ctypes.c_void_p * 1)(addr), ctypes.c_size_t(1))
+        lib().h2hip_part_cosets_unpin((ctypes.c_void_p * 1)(addr), 1)
     except Exception:
         pass
 
@@ -278,15 +283,15 @@ def part_cosets_pin(polys, domain):
     if not polys:
         return
     host = isinstance(polys[0], np.ndarray)
-    consts = (ctypes.c_uint32(domain.k), ctypes.c_uint32(domain.extended_k), _p(domain.extended_omega), _p(domain.g_coset), _p(domain.g_coset_inv))
+    consts = (domain.k, domain.extended_k, _p(domain.extended_omega), _p(domain.g_coset), _p(domain.g_coset_inv))
     if host:
         for a in polys:
             assert a.dtype == np.uint64 and a.flags["C_CONTIGUOUS"] and a.shape == (1 << domain.k, 4)
-        _check(lib().h2hip_part_cosets_pin(_host_ptrs(polys), ctypes.c_size_t(len(polys)), *consts), "h2hip_part_cosets_pin")
+        _check(lib().h2hip_part_cosets_pin(_host_ptrs(polys), len(polys), *consts), "h2hip_part_cosets_pin")
     else:
         for t in polys:
             assert t.numel() * t.element_size() == 32 << domain.k
-        _check(lib().h2hip_part_cosets_pin_device(_ptr_array(polys), ctypes.c_size_t(len(polys)), *consts, _stream()), "h2hip_part_cosets_pin_device")
+        _check(lib().h2hip_part_cosets_pin_device(_ptr_array(polys), len(polys), *consts, _stream()), "h2hip_part_cosets_pin_device")
     for a in polys:
         addr = a.ctypes.data if host else a.data_ptr()
         old = _part_pins.pop(addr, None)
@@ -308,7 +313,7 @@ def part_cosets_unpin(polys):
         fin = _part_pins.pop(addr, None)
         if fin is not None:
             fin.detach()
-    _check(lib().h2hip_part_cosets_unpin((ctypes.c_void_p * len(addrs))(*addrs), ctypes.c_size_t(len(addrs))), "h2hip_part_cosets_unpin")
+    _check(lib().h2hip_part_cosets_unpin((ctypes.c_void_p * len(addrs))(*addrs), len(addrs)), "h2hip_part_cosets_unpin")
 
 
 def part_cosets_pinned_info():
@@ -405,9 +410,9 @@ def permutation_products(k, omega, delta, beta, gamma, columns, permutations, ch
     n_sets = -(-len(cols) // int(chunk_len)) if chunk_len else 0
     bl = _blinding(blinding, n_sets, int(blinding_factors))
     z = [np.zeros((n, 4), dtype=np.uint64) for _ in range(n_sets)]
-    _check(lib().h2hip_permutation_products_bn254(ctypes.c_uint32(k), _p(_fe(omega)), _p(_fe(delta)), _p(_fe(beta)), _p(_fe(gamma)),
-                                                  _host_ptrs(cols), _host_ptrs(perms), ctypes.c_uint32(len(cols)), ctypes.c_uint32(chunk_len),
-                                                  _p(bl), ctypes.c_uint32(blinding_factors), _host_ptrs(z)),
+    _check(lib().h2hip_permutation_products_bn254(k, _p(_fe(omega)), _p(_fe(delta)), _p(_fe(beta)), _p(_fe(gamma)),
+                                                  _host_ptrs(cols), _host_ptrs(perms), len(cols), chunk_len,
+                                                  _p(bl), blinding_factors, _host_ptrs(z)),
            "h2hip_permutation_products_bn254")
     return z
 
@@ -423,8 +428,8 @@ def lookup_products(k, beta, gamma, compressed_inputs, compressed_tables, permut
         raise ValueError("lookup columns differ in count")
     bl = _blinding(blinding, count, int(blinding_factors))
     z = [np.zeros((n, 4), dtype=np.uint64) for _ in range(count)]
-    _check(lib().h2hip_lookup_products_bn254(ctypes.c_uint32(k), _p(_fe(beta)), _p(_fe(gamma)), _host_ptrs(a), _host_ptrs(s), _host_ptrs(ap),
-                                             _host_ptrs(sp), ctypes.c_size_t(count), _p(bl), ctypes.c_uint32(blinding_factors), _host_ptrs(z)),
+    _check(lib().h2hip_lookup_products_bn254(k, _p(_fe(beta)), _p(_fe(gamma)), _host_ptrs(a), _host_ptrs(s), _host_ptrs(ap),
+                                             _host_ptrs(sp), count, _p(bl), blinding_factors, _host_ptrs(z)),
            "h2hip_lookup_products_bn254")
     return z
 
@@ -439,15 +444,15 @@ def shuffle_products(k, gamma, compressed_inputs, compressed_shuffles, blinding,
         raise ValueError("shuffle columns differ in count")
     bl = _blinding(blinding, count, int(blinding_factors))
     z = [np.zeros((n, 4), dtype=np.uint64) for _ in range(count)]
-    _check(lib().h2hip_shuffle_products_bn254(ctypes.c_uint32(k), _p(_fe(gamma)), _host_ptrs(a), _host_ptrs(s), ctypes.c_size_t(count), _p(bl),
-                                              ctypes.c_uint32(blinding_factors), _host_ptrs(z)), "h2hip_shuffle_products_bn254")
+    _check(lib().h2hip_shuffle_products_bn254(k, _p(_fe(gamma)), _host_ptrs(a), _host_ptrs(s), count, _p(bl),
+                                              blinding_factors, _host_ptrs(z)), "h2hip_shuffle_products_bn254")
     return z
 
 
 def batch_invert(a):
     """ff's BatchInvert on a (n, 4) uint64 array of Montgomery Fr elements: a new array of the inverses, zeros stay zero"""
     out = _u64(a, 4).copy()
-    _check(lib().h2hip_batch_invert_bn254_fr(_p(out), ctypes.c_size_t(out.shape[0])), "h2hip_batch_invert_bn254_fr")
+    _check(lib().h2hip_batch_invert_bn254_fr(_p(out), out.shape[0]), "h2hip_batch_invert_bn254_fr")
     return out
 
 
@@ -479,9 +484,9 @@ def lookup_compress(k, graphs, theta, fixed=(), advice=(), instance=(), challeng
     arr, keep = graph_array(graphs)
     ch, n_ch = _lookup_challenges(challenges)
     out = [np.zeros((n, 4), dtype=np.uint64) for _ in graphs]
-    _check(lib().h2hip_lookup_compress_bn254(ctypes.c_uint32(k), _host_ptrs(fx), ctypes.c_uint32(len(fx)), _host_ptrs(ad), ctypes.c_uint32(len(ad)),
-                                             _host_ptrs(ins), ctypes.c_uint32(len(ins)), _p(ch), ctypes.c_uint32(n_ch), _p(_fe(theta)), arr,
-                                             ctypes.c_size_t(len(graphs)), _host_ptrs(out)), "h2hip_lookup_compress_bn254")
+    _check(lib().h2hip_lookup_compress_bn254(k, _host_ptrs(fx), len(fx), _host_ptrs(ad), len(ad),
+                                             _host_ptrs(ins), len(ins), _p(ch), n_ch, _p(_fe(theta)), arr,
+                                             len(graphs), _host_ptrs(out)), "h2hip_lookup_compress_bn254")
     del keep
     return out
 
@@ -504,8 +509,8 @@ def lookup_permute(k, compressed_inputs, compressed_tables, blinding, blinding_f
     bl = _lookup_blinding(blinding, len(a), int(blinding_factors))
     pa = [np.zeros((n, 4), dtype=np.uint64) for _ in a]
     pt = [np.zeros((n, 4), dtype=np.uint64) for _ in a]
-    _check_lookup(lib().h2hip_lookup_permute_bn254(ctypes.c_uint32(k), _host_ptrs(a), _host_ptrs(t), ctypes.c_size_t(len(a)), _p(bl),
-                                                   ctypes.c_uint32(blinding_factors), _host_ptrs(pa), _host_ptrs(pt)), "h2hip_lookup_permute_bn254")
+    _check_lookup(lib().h2hip_lookup_permute_bn254(k, _host_ptrs(a), _host_ptrs(t), len(a), _p(bl),
+                                                   blinding_factors, _host_ptrs(pa), _host_ptrs(pt)), "h2hip_lookup_permute_bn254")
     return pa, pt
 
 
@@ -577,8 +582,8 @@ def mvlookup_multiplicities(k, compressed_inputs, compressed_tables, blinding_fa
     t = _cols(compressed_tables, n, "compressed_tables")
     f, n_in = _mv_inputs(compressed_inputs, n, len(t))
     m = [np.zeros((n, 4), dtype=np.uint64) for _ in t]
-    rc = lib().h2hip_mvlookup_multiplicities_bn254(ctypes.c_uint32(k), _host_ptrs(f), _p(n_in), _host_ptrs(t), ctypes.c_size_t(len(t)),
-                                                   ctypes.c_uint32(blinding_factors), _host_ptrs(m))
+    rc = lib().h2hip_mvlookup_multiplicities_bn254(k, _host_ptrs(f), _p(n_in), _host_ptrs(t), len(t),
+                                                   blinding_factors, _host_ptrs(m))
     if partial and rc == H2HIP_ELOOKUP:
         return m, lib().h2hip_last_error().decode()
     _check_lookup(rc, "h2hip_mvlookup_multiplicities_bn254")
@@ -595,8 +600,8 @@ def mvlookup_sums(k, beta, compressed_inputs, compressed_tables, m, blinding, bl
     f, n_in = _mv_inputs(compressed_inputs, n, len(t))
     bl = _blinding(blinding, len(t), int(blinding_factors))
     phi = [np.zeros((n, 4), dtype=np.uint64) for _ in t]
-    _check(lib().h2hip_mvlookup_sums_bn254(ctypes.c_uint32(k), _p(_fe(beta)), _host_ptrs(f), _p(n_in), _host_ptrs(t), _host_ptrs(mm),
-                                           ctypes.c_size_t(len(t)), _p(bl), ctypes.c_uint32(blinding_factors), _host_ptrs(phi)),
+    _check(lib().h2hip_mvlookup_sums_bn254(k, _p(_fe(beta)), _host_ptrs(f), _p(n_in), _host_ptrs(t), _host_ptrs(mm),
+                                           len(t), _p(bl), blinding_factors, _host_ptrs(phi)),
            "h2hip_mvlookup_sums_bn254")
     return phi
 
@@ -604,7 +609,7 @@ def mvlookup_sums(k, beta, compressed_inputs, compressed_tables, m, blinding, bl
 def mvlookup_sum_rows(k, blinding_factors, count):
     """test hook: the rows one thread of the grand sum's scan takes in a call of `count` arguments (the code's own rule; no GPU)"""
     out = ctypes.c_uint32(0)
-    _check(lib().h2hip_debug_mvlookup_sum_rows(ctypes.c_uint32(k), ctypes.c_uint32(blinding_factors), ctypes.c_size_t(count), ctypes.byref(out)),
+    _check(lib().h2hip_debug_mvlookup_sum_rows(k, blinding_factors, count, ctypes.byref(out)),
            "h2hip_debug_mvlookup_sum_rows")
     return out.value
 
@@ -661,9 +666,9 @@ def check_gates(k, graphs, fixed=(), advice=(), instance=(), challenges=(), max_
     arr, keep = graph_array(graphs)
     ch, n_ch = _lookup_challenges(challenges)
     counts, rows, prow = _check_out(len(graphs), max_rows)
-    _check(lib().h2hip_check_gates_bn254(ctypes.c_uint32(k), _host_ptrs(fx), ctypes.c_uint32(len(fx)), _host_ptrs(ad), ctypes.c_uint32(len(ad)),
-                                         _host_ptrs(ins), ctypes.c_uint32(len(ins)), _p(ch), ctypes.c_uint32(n_ch), arr,
-                                         ctypes.c_size_t(len(graphs)), ctypes.c_uint32(max_rows), _p(counts), prow), "h2hip_check_gates_bn254")
+    _check(lib().h2hip_check_gates_bn254(k, _host_ptrs(fx), len(fx), _host_ptrs(ad), len(ad),
+                                         _host_ptrs(ins), len(ins), _p(ch), n_ch, arr,
+                                         len(graphs), max_rows, _p(counts), prow), "h2hip_check_gates_bn254")
     del keep
     return _check_result(counts, rows, len(graphs), max_rows)
 
@@ -685,8 +690,8 @@ def check_permutation(k, columns, mapping, max_rows=16):
         raise ValueError("columns and mapping differ in count")
     maps = [mp[j] for j in range(len(cols))]
     counts, rows, prow = _check_out(len(cols), max_rows)
-    _check(lib().h2hip_check_permutation_bn254(ctypes.c_uint32(k), _host_ptrs(cols), _host_ptrs(maps), ctypes.c_uint32(len(cols)),
-                                               ctypes.c_uint32(max_rows), _p(counts), prow), "h2hip_check_permutation_bn254")
+    _check(lib().h2hip_check_permutation_bn254(k, _host_ptrs(cols), _host_ptrs(maps), len(cols),
+                                               max_rows, _p(counts), prow), "h2hip_check_permutation_bn254")
     return _check_result(counts, rows, len(cols), max_rows)
 
 
@@ -698,8 +703,8 @@ def check_lookups(k, compressed_inputs, compressed_tables, blinding_factors, max
     if len(a) != len(t):
         raise ValueError("compressed inputs and tables differ in count")
     counts, rows, prow = _check_out(len(a), max_rows)
-    _check(lib().h2hip_check_lookups_bn254(ctypes.c_uint32(k), _host_ptrs(a), _host_ptrs(t), ctypes.c_size_t(len(a)),
-                                           ctypes.c_uint32(blinding_factors), ctypes.c_uint32(max_rows), _p(counts), prow),
+    _check(lib().h2hip_check_lookups_bn254(k, _host_ptrs(a), _host_ptrs(t), len(a),
+                                           blinding_factors, max_rows, _p(counts), prow),
            "h2hip_check_lookups_bn254")
     return _check_result(counts, rows, len(a), max_rows)
 
@@ -713,8 +718,8 @@ def check_shuffles(k, compressed_inputs, compressed_shuffles, blinding_factors, 
     if len(a) != len(s):
         raise ValueError("compressed inputs and shuffles differ in count")
     counts, rows, prow = _check_out(len(a), max_rows)
-    _check(lib().h2hip_check_shuffles_bn254(ctypes.c_uint32(k), _host_ptrs(a), _host_ptrs(s), ctypes.c_size_t(len(a)),
-                                            ctypes.c_uint32(blinding_factors), ctypes.c_uint32(max_rows), _p(counts), prow),
+    _check(lib().h2hip_check_shuffles_bn254(k, _host_ptrs(a), _host_ptrs(s), len(a),
+                                            blinding_factors, max_rows, _p(counts), prow),
            "h2hip_check_shuffles_bn254")
     return _check_result(counts, rows, len(a), max_rows)
 
@@ -837,7 +842,7 @@ def permutation_mapping(k, n_columns, copies):
     # arguments beyond the limits go to the library, which names the limit: it reads no table then, so none of that size is made
     within = k <= 28 and m <= 65535 and (m << k) <= 1 << 32
     out = np.zeros((m, 1 << k, 2) if within else (min(m, 65536), 1, 2), dtype=np.uint32)
-    _check(lib().h2hip_permutation_mapping(ctypes.c_uint32(k), ctypes.c_uint32(m), _p(c) if c.shape[0] else None, ctypes.c_size_t(c.shape[0]),
+    _check(lib().h2hip_permutation_mapping(k, m, _p(c) if c.shape[0] else None, c.shape[0],
                                            _host_ptrs([out[j] for j in range(out.shape[0])])), "h2hip_permutation_mapping")
     return out
 
@@ -868,7 +873,7 @@ class CopyList:
 
 
 def _domain_args(domain):
-    return (ctypes.c_uint32(domain.k), _p(domain.omega), _p(domain.omega_inv), _p(domain.ifft_divisor), ctypes.c_uint32(domain.extended_k),
+    return (domain.k, _p(domain.omega), _p(domain.omega_inv), _p(domain.ifft_divisor), domain.extended_k,
             _p(domain.extended_omega), _p(domain.g_coset), _p(domain.g_coset_inv))
 
 
@@ -898,7 +903,7 @@ def permutation_keygen(domain, mapping, want=_KEYGEN_FORMS, delta=None):
     out = {w: [np.zeros((sizes[w], 4), dtype=np.uint64) for _ in range(m)] for w in want}
     tabs = [(_host_ptrs(out[w]) if w in out else None) for w in _KEYGEN_FORMS]
     d = fr_from_int(FR_DELTA) if delta is None else _fe(delta)
-    _check(lib().h2hip_permutation_keygen_bn254(*_domain_args(domain), _p(d), _host_ptrs(rows), ctypes.c_uint32(m), *tabs),
+    _check(lib().h2hip_permutation_keygen_bn254(*_domain_args(domain), _p(d), _host_ptrs(rows), m, *tabs),
            "h2hip_permutation_keygen_bn254")
     return out
 
@@ -937,7 +942,7 @@ def batch_invert_assigned(k, numerators, rat_rows=None, rat_denoms=None, in_plac
     rp = (ctypes.c_void_p * max(1, m))(*[(r.ctypes.data if r.shape[0] else None) for r in rows])
     dp = (ctypes.c_void_p * max(1, m))(*[(d.ctypes.data if d.shape[0] else None) for d in dens])
     cnt = (ctypes.c_size_t * max(1, m))(*counts)
-    _check(lib().h2hip_batch_invert_assigned_bn254(ctypes.c_uint32(k), _host_ptrs(nums), rp, cnt, dp, ctypes.c_size_t(m), _host_ptrs(outs)),
+    _check(lib().h2hip_batch_invert_assigned_bn254(k, _host_ptrs(nums), rp, cnt, dp, m, _host_ptrs(outs)),
            "h2hip_batch_invert_assigned_bn254")
     return outs
 
@@ -945,9 +950,9 @@ def batch_invert_assigned(k, numerators, rat_rows=None, rat_denoms=None, in_plac
 def key_lagrange_columns(domain, blinding_factors):
     """pk.l0, pk.l_last, pk.l_active_row (plonk/keygen.rs:320-351): three (2^extended_k, 4) columns"""
     cols = [np.zeros((domain.extended_len(), 4), dtype=np.uint64) for _ in range(3)]
-    _check(lib().h2hip_key_lagrange_columns_bn254(ctypes.c_uint32(domain.k), _p(domain.omega_inv), _p(domain.ifft_divisor),
-                                                  ctypes.c_uint32(domain.extended_k), _p(domain.extended_omega), _p(domain.g_coset),
-                                                  _p(domain.g_coset_inv), ctypes.c_uint32(blinding_factors), _p(cols[0]), _p(cols[1]), _p(cols[2])),
+    _check(lib().h2hip_key_lagrange_columns_bn254(domain.k, _p(domain.omega_inv), _p(domain.ifft_divisor),
+                                                  domain.extended_k, _p(domain.extended_omega), _p(domain.g_coset),
+                                                  _p(domain.g_coset_inv), blinding_factors, _p(cols[0]), _p(cols[1]), _p(cols[2])),
            "h2hip_key_lagrange_columns_bn254")
     return tuple(cols)
 
@@ -1002,8 +1007,8 @@ def eval_polynomials(polys, query_poly, points):
     if qp.shape[0] != nq:
         raise ValueError("query_poly and points differ in length")
     out = np.zeros((max(1, nq), 4), dtype=np.uint64)
-    _check(lib().h2hip_eval_polynomials_bn254(_host_ptrs(ps) if ps else None, lens, ctypes.c_size_t(len(ps)), _p(qp if nq else np.zeros(1, np.uint32)),
-                                              _p(pts), ctypes.c_size_t(nq), _p(out)), "h2hip_eval_polynomials_bn254")
+    _check(lib().h2hip_eval_polynomials_bn254(_host_ptrs(ps) if ps else None, lens, len(ps), _p(qp if nq else np.zeros(1, np.uint32)),
+                                              _p(pts), nq, _p(out)), "h2hip_eval_polynomials_bn254")
     return out[:nq]
 
 
@@ -1034,9 +1039,9 @@ def poly_combine(polys, scalars, sub=None, roots=(), scale=None, out=None, accum
     else:
         assert out.dtype == np.uint64 and out.flags["C_CONTIGUOUS"] and out.ndim == 2 and out.shape[1] == 4
     rem = np.zeros(4, dtype=np.uint64)
-    _check(lib().h2hip_poly_combine_bn254_fr(_host_ptrs(ps) if ps else None, ctypes.c_size_t(L), _p(sc), ctypes.c_size_t(len(ps)), _p(sb),
-                                             ctypes.c_size_t(n_sub), _p(rt), ctypes.c_size_t(n_roots), _p(sl), ctypes.c_uint32(1 if accumulate else 0),
-                                             _p(out) if out.shape[0] else None, ctypes.c_size_t(out.shape[0]), _p(rem) if remainder else None),
+    _check(lib().h2hip_poly_combine_bn254_fr(_host_ptrs(ps) if ps else None, L, _p(sc), len(ps), _p(sb),
+                                             n_sub, _p(rt), n_roots, _p(sl), 1 if accumulate else 0,
+                                             _p(out) if out.shape[0] else None, out.shape[0], _p(rem) if remainder else None),
            "h2hip_poly_combine_bn254_fr")
     return (out, rem) if remainder else out
 
@@ -1247,7 +1252,7 @@ class EvaluationDomain:
         self._device_field()
         a = _u64(a, 4).copy()
         assert a.shape[0] == 1 << self.k
-        _check(lib().h2hip_ifft_bn254_fr(_p(a), _p(self.omega_inv), ctypes.c_uint32(self.k), _p(self.ifft_divisor)),
+        _check(lib().h2hip_ifft_bn254_fr(_p(a), _p(self.omega_inv), self.k, _p(self.ifft_divisor)),
                "h2hip_ifft_bn254_fr")
         return a
 
@@ -1257,7 +1262,7 @@ class EvaluationDomain:
         a = _u64(a, 4)
         assert a.shape[0] == 1 << self.k
         out = np.zeros((self.extended_len(), 4), dtype=np.uint64)
-        _check(lib().h2hip_coeff_to_extended_bn254_fr(_p(a), ctypes.c_uint32(self.k), _p(out), ctypes.c_uint32(self.extended_k),
+        _check(lib().h2hip_coeff_to_extended_bn254_fr(_p(a), self.k, _p(out), self.extended_k,
                                                       _p(self.extended_omega), _p(self.g_coset), _p(self.g_coset_inv)),
                "h2hip_coeff_to_extended_bn254_fr")
         return out
@@ -1268,7 +1273,7 @@ class EvaluationDomain:
         a = _u64(a, 4)
         assert a.shape[0] == 1 << self.k
         out = np.zeros((1 << self.k, 4), dtype=np.uint64)
-        _check(lib().h2hip_coeff_to_extended_part_bn254_fr(_p(a), ctypes.c_uint32(self.k), ctypes.c_uint32(self.extended_k), ctypes.c_uint32(part),
+        _check(lib().h2hip_coeff_to_extended_part_bn254_fr(_p(a), self.k, self.extended_k, part,
                                                            _p(self.extended_omega), _p(self.g_coset), _p(self.g_coset_inv), _p(out)),
                "h2hip_coeff_to_extended_part_bn254_fr")
         return out
@@ -1278,7 +1283,7 @@ class EvaluationDomain:
         self._device_field()
         a = _u64(a, 4).copy()
         assert a.shape[0] == self.extended_len()
-        _check(lib().h2hip_extended_to_coeff_bn254_fr(_p(a), ctypes.c_uint32(self.extended_k), _p(self.extended_omega_inv),
+        _check(lib().h2hip_extended_to_coeff_bn254_fr(_p(a), self.extended_k, _p(self.extended_omega_inv),
                                                       _p(self.extended_ifft_divisor), _p(self.g_coset), _p(self.g_coset_inv)),
                "h2hip_extended_to_coeff_bn254_fr")
         return a[: self.n * self.quotient_poly_degree]
@@ -1293,7 +1298,7 @@ class EvaluationDomain:
         for a in cols:
             assert a.shape[0] == 1 << self.k
         if cols:
-            _check(lib().h2hip_ifft_bn254_fr_batch(_host_ptrs(cols), ctypes.c_size_t(len(cols)), _p(self.omega_inv), ctypes.c_uint32(self.k),
+            _check(lib().h2hip_ifft_bn254_fr_batch(_host_ptrs(cols), len(cols), _p(self.omega_inv), self.k,
                                                    _p(self.ifft_divisor)), "h2hip_ifft_bn254_fr_batch")
         return cols
 
@@ -1304,8 +1309,8 @@ class EvaluationDomain:
             assert a.shape[0] == 1 << self.k
         outs = [np.empty((self.extended_len(), 4), dtype=np.uint64) for _ in cols]
         if cols:
-            _check(lib().h2hip_coeff_to_extended_bn254_fr_batch(_host_ptrs(cols), ctypes.c_uint32(self.k), _host_ptrs(outs), ctypes.c_size_t(len(cols)),
-                                                                ctypes.c_uint32(self.extended_k), _p(self.extended_omega), _p(self.g_coset),
+            _check(lib().h2hip_coeff_to_extended_bn254_fr_batch(_host_ptrs(cols), self.k, _host_ptrs(outs), len(cols),
+                                                                self.extended_k, _p(self.extended_omega), _p(self.g_coset),
                                                                 _p(self.g_coset_inv)), "h2hip_coeff_to_extended_bn254_fr_batch")
         return outs
 
@@ -1315,7 +1320,7 @@ class EvaluationDomain:
         for a in cols:
             assert a.shape[0] == self.extended_len()
         if cols:
-            _check(lib().h2hip_extended_to_coeff_bn254_fr_batch(_host_ptrs(cols), ctypes.c_size_t(len(cols)), ctypes.c_uint32(self.extended_k),
+            _check(lib().h2hip_extended_to_coeff_bn254_fr_batch(_host_ptrs(cols), len(cols), self.extended_k,
                                                                 _p(self.extended_omega_inv), _p(self.extended_ifft_divisor), _p(self.g_coset),
                                                                 _p(self.g_coset_inv)), "h2hip_extended_to_coeff_bn254_fr_batch")
         return [a[: self.n * self.quotient_poly_degree] for a in cols]
@@ -1326,7 +1331,7 @@ class EvaluationDomain:
         a = _u64(a, 4).copy()
         t = self.t_evaluations if t_evaluations is None else _u64(t_evaluations, 4)
         assert a.shape[0] == self.extended_len()
-        _check(lib().h2hip_divide_by_vanishing_poly_bn254_fr(_p(a), ctypes.c_uint32(self.extended_k), _p(t), ctypes.c_uint32(t.shape[0])),
+        _check(lib().h2hip_divide_by_vanishing_poly_bn254_fr(_p(a), self.extended_k, _p(t), t.shape[0]),
                "h2hip_divide_by_vanishing_poly_bn254_fr")
         return a
 
@@ -1375,7 +1380,7 @@ def g1_from_bytes(data):
     data = _bytes32(data, "g1_from_bytes")
     n = data.shape[0]
     out, invalid = np.zeros((n, 8), dtype=np.uint64), np.zeros(2, dtype=np.uint64)
-    _check_encoding(lib().h2hip_g1_decompress_bn254(_p(data), ctypes.c_size_t(n), _p(out), _p(invalid)), "h2hip_g1_decompress_bn254", invalid, out)
+    _check_encoding(lib().h2hip_g1_decompress_bn254(_p(data), n, _p(out), _p(invalid)), "h2hip_g1_decompress_bn254", invalid, out)
     return out
 
 
@@ -1384,7 +1389,7 @@ def g1_to_bytes(points):
     points = _u64(points, 8)
     n = points.shape[0]
     out = np.zeros((n, 32), dtype=np.uint8)
-    _check(lib().h2hip_g1_compress_bn254(_p(points), ctypes.c_size_t(n), _p(out)), "h2hip_g1_compress_bn254")
+    _check(lib().h2hip_g1_compress_bn254(_p(points), n, _p(out)), "h2hip_g1_compress_bn254")
     return out
 
 
@@ -1392,7 +1397,7 @@ def g1_validate(points):
     """read_raw's checks (SerdeFormat::RawBytes read) on (n, 8) uint64 points; H2HipEncodingError when one fails"""
     points = _u64(points, 8)
     invalid = np.zeros(2, dtype=np.uint64)
-    _check_encoding(lib().h2hip_g1_validate_bn254(_p(points), ctypes.c_size_t(points.shape[0]), _p(invalid)), "h2hip_g1_validate_bn254", invalid)
+    _check_encoding(lib().h2hip_g1_validate_bn254(_p(points), points.shape[0], _p(invalid)), "h2hip_g1_validate_bn254", invalid)
 
 
 def fr_from_repr(data):
@@ -1400,7 +1405,7 @@ def fr_from_repr(data):
     data = _bytes32(data, "fr_from_repr")
     n = data.shape[0]
     out, invalid = np.zeros((n, 4), dtype=np.uint64), np.zeros(2, dtype=np.uint64)
-    _check_encoding(lib().h2hip_fr_from_repr_bn254(_p(data), ctypes.c_size_t(n), _p(out), _p(invalid)), "h2hip_fr_from_repr_bn254", invalid, out)
+    _check_encoding(lib().h2hip_fr_from_repr_bn254(_p(data), n, _p(out), _p(invalid)), "h2hip_fr_from_repr_bn254", invalid, out)
     return out
 
 
@@ -1408,7 +1413,7 @@ def fr_to_repr(a):
     """Fr::to_repr over an array: (n, 4) uint64 Montgomery -> (n, 32) uint8"""
     a = _u64(a, 4)
     out = np.zeros((a.shape[0], 32), dtype=np.uint8)
-    _check(lib().h2hip_fr_to_repr_bn254(_p(a), ctypes.c_size_t(a.shape[0]), _p(out)), "h2hip_fr_to_repr_bn254")
+    _check(lib().h2hip_fr_to_repr_bn254(_p(a), a.shape[0], _p(out)), "h2hip_fr_to_repr_bn254")
     return out
 
 
@@ -1638,7 +1643,7 @@ class ParamsKZG:
         size = poly.shape[0]
         if d_bases is None:
             out = np.zeros(12, dtype=np.uint64)
-            _check(lib().h2hip_msm_bn254(_p(poly), _p(host_bases), ctypes.c_size_t(size), _p(out)), "h2hip_msm_bn254")
+            _check(lib().h2hip_msm_bn254(_p(poly), _p(host_bases), size, _p(out)), "h2hip_msm_bn254")
             return out
         import torch
         return msm_device(torch.from_numpy(poly.view(np.int64)).cuda(), d_bases, size)
@@ -1653,7 +1658,7 @@ class ParamsKZG:
         n = 1 << int(k)
         g = np.zeros((n, 8), dtype=np.uint64)
         gl = np.zeros((n, 8), dtype=np.uint64)
-        _check(lib().h2hip_kzg_setup_bn254(ctypes.c_uint32(k), _p(s), _p(g), _p(gl)), "h2hip_kzg_setup_bn254")
+        _check(lib().h2hip_kzg_setup_bn254(k, _p(s), _p(g), _p(gl)), "h2hip_kzg_setup_bn254")
         return cls(k, g, gl)
 
     def commit_lagrange(self, poly, blind=None):
@@ -1749,7 +1754,7 @@ def msm_device(d_scalars, d_bases, n=None):
     nb = d_scalars.numel() * d_scalars.element_size()
     n = nb // 32 if n is None else int(n)
     out = np.zeros(12, dtype=np.uint64)
-    _check(lib().h2hip_msm_bn254_device(_dptr(d_scalars), _dptr(d_bases), ctypes.c_size_t(n), _p(out), _stream()), "h2hip_msm_bn254_device")
+    _check(lib().h2hip_msm_bn254_device(_dptr(d_scalars), _dptr(d_bases), n, _p(out), _stream()), "h2hip_msm_bn254_device")
     return out
 
 
@@ -1760,22 +1765,22 @@ def msm_batch_device(d_scalars_list, d_bases, n=None):
         n = d_scalars_list[0].numel() * d_scalars_list[0].element_size() // 32
     ptrs = (ctypes.c_void_p * count)(*[t.data_ptr() for t in d_scalars_list])
     out = np.zeros((count, 12), dtype=np.uint64)
-    _check(lib().h2hip_msm_bn254_batch_device(ptrs, _dptr(d_bases), ctypes.c_size_t(n), ctypes.c_size_t(count), _p(out), _stream()),
+    _check(lib().h2hip_msm_bn254_batch_device(ptrs, _dptr(d_bases), n, count, _p(out), _stream()),
            "h2hip_msm_bn254_batch_device")
     return out
 
 
 def ntt_device(d_a, omega, log_n):
-    _check(lib().h2hip_ntt_bn254_fr_device(_dptr(d_a), _p(_fe(omega)), ctypes.c_uint32(log_n), _stream()), "h2hip_ntt_bn254_fr_device")
+    _check(lib().h2hip_ntt_bn254_fr_device(_dptr(d_a), _p(_fe(omega)), log_n, _stream()), "h2hip_ntt_bn254_fr_device")
 
 
 def ifft_device(d_a, omega_inv, log_n, divisor):
-    _check(lib().h2hip_ifft_bn254_fr_device(_dptr(d_a), _p(_fe(omega_inv)), ctypes.c_uint32(log_n), _p(_fe(divisor)), _stream()),
+    _check(lib().h2hip_ifft_bn254_fr_device(_dptr(d_a), _p(_fe(omega_inv)), log_n, _p(_fe(divisor)), _stream()),
            "h2hip_ifft_bn254_fr_device")
 
 
 def coeff_to_extended_device(d_a, k, extended_k, extended_omega, g_coset, g_coset_inv):
-    _check(lib().h2hip_coeff_to_extended_bn254_fr_device(_dptr(d_a), ctypes.c_uint32(k), ctypes.c_uint32(extended_k), _p(_fe(extended_omega)),
+    _check(lib().h2hip_coeff_to_extended_bn254_fr_device(_dptr(d_a), k, extended_k, _p(_fe(extended_omega)),
                                                          _p(_fe(g_coset)), _p(_fe(g_coset_inv)), _stream()),
            "h2hip_coeff_to_extended_bn254_fr_device")
 
@@ -1783,13 +1788,13 @@ def coeff_to_extended_device(d_a, k, extended_k, extended_omega, g_coset, g_cose
 def coeff_to_extended_part_device(d_a, k, extended_k, part, extended_omega, g_coset, g_coset_inv, d_out=None):
     """part `part` of coeff_to_extended(d_a) into d_out (2^k elements each; d_out None: in place); queued on the current stream"""
     d_out = d_a if d_out is None else d_out
-    _check(lib().h2hip_coeff_to_extended_part_bn254_fr_device(_dptr(d_a), ctypes.c_uint32(k), ctypes.c_uint32(extended_k), ctypes.c_uint32(part),
+    _check(lib().h2hip_coeff_to_extended_part_bn254_fr_device(_dptr(d_a), k, extended_k, part,
                                                               _p(_fe(extended_omega)), _p(_fe(g_coset)), _p(_fe(g_coset_inv)), _dptr(d_out),
                                                               _stream()), "h2hip_coeff_to_extended_part_bn254_fr_device")
 
 
 def extended_to_coeff_device(d_a, extended_k, extended_omega_inv, extended_ifft_divisor, g_coset, g_coset_inv):
-    _check(lib().h2hip_extended_to_coeff_bn254_fr_device(_dptr(d_a), ctypes.c_uint32(extended_k), _p(_fe(extended_omega_inv)),
+    _check(lib().h2hip_extended_to_coeff_bn254_fr_device(_dptr(d_a), extended_k, _p(_fe(extended_omega_inv)),
                                                          _p(_fe(extended_ifft_divisor)), _p(_fe(g_coset)), _p(_fe(g_coset_inv)), _stream()),
            "h2hip_extended_to_coeff_bn254_fr_device")
 
@@ -1800,18 +1805,18 @@ def _ptr_array(tensors):
 
 def ntt_batch_device(d_list, omega, log_n):
     """the same NTT over every tensor of d_list, one launch per pass"""
-    _check(lib().h2hip_ntt_bn254_fr_batch_device(_ptr_array(d_list), ctypes.c_size_t(len(d_list)), _p(_fe(omega)), ctypes.c_uint32(log_n), _stream()),
+    _check(lib().h2hip_ntt_bn254_fr_batch_device(_ptr_array(d_list), len(d_list), _p(_fe(omega)), log_n, _stream()),
            "h2hip_ntt_bn254_fr_batch_device")
 
 
 def ifft_batch_device(d_list, omega_inv, log_n, divisor):
-    _check(lib().h2hip_ifft_bn254_fr_batch_device(_ptr_array(d_list), ctypes.c_size_t(len(d_list)), _p(_fe(omega_inv)), ctypes.c_uint32(log_n),
+    _check(lib().h2hip_ifft_bn254_fr_batch_device(_ptr_array(d_list), len(d_list), _p(_fe(omega_inv)), log_n,
                                                   _p(_fe(divisor)), _stream()), "h2hip_ifft_bn254_fr_batch_device")
 
 
 def coeff_to_extended_batch_device(d_list, k, extended_k, extended_omega, g_coset, g_coset_inv):
-    _check(lib().h2hip_coeff_to_extended_bn254_fr_batch_device(_ptr_array(d_list), ctypes.c_size_t(len(d_list)), ctypes.c_uint32(k),
-                                                               ctypes.c_uint32(extended_k), _p(_fe(extended_omega)), _p(_fe(g_coset)),
+    _check(lib().h2hip_coeff_to_extended_bn254_fr_batch_device(_ptr_array(d_list), len(d_list), k,
+                                                               extended_k, _p(_fe(extended_omega)), _p(_fe(g_coset)),
                                                                _p(_fe(g_coset_inv)), _stream()), "h2hip_coeff_to_extended_bn254_fr_batch_device")
 
 
@@ -1820,8 +1825,8 @@ def coeff_to_extended_part_batch_device(d_list, d_out_list, parts, k, extended_k
     transforms (all P parts of one polynomial), and an output may be its own source only where that source feeds no other transform"""
     assert len(d_list) == len(d_out_list) == len(parts)
     h_parts = (ctypes.c_uint32 * max(1, len(parts)))(*[int(p) for p in parts])
-    _check(lib().h2hip_coeff_to_extended_part_bn254_fr_batch_device(_ptr_array(d_list), _ptr_array(d_out_list), h_parts, ctypes.c_size_t(len(d_list)),
-                                                                    ctypes.c_uint32(k), ctypes.c_uint32(extended_k), _p(_fe(extended_omega)),
+    _check(lib().h2hip_coeff_to_extended_part_bn254_fr_batch_device(_ptr_array(d_list), _ptr_array(d_out_list), h_parts, len(d_list),
+                                                                    k, extended_k, _p(_fe(extended_omega)),
                                                                     _p(_fe(g_coset)), _p(_fe(g_coset_inv)), _stream()),
            "h2hip_coeff_to_extended_part_bn254_fr_batch_device")
 
@@ -1829,9 +1834,9 @@ def permutation_products_device(k, omega, delta, beta, gamma, d_columns, d_permu
     """device form of permutation_products: torch CUDA tensors of 2^k x 32 B in, the n_sets tensors of d_z written; queued on the
     current stream, not waited for"""
     bl = _blinding(blinding, len(d_z), int(blinding_factors))
-    _check(lib().h2hip_permutation_products_bn254_device(ctypes.c_uint32(k), _p(_fe(omega)), _p(_fe(delta)), _p(_fe(beta)), _p(_fe(gamma)),
-                                                         _ptr_array(d_columns), _ptr_array(d_permutations), ctypes.c_uint32(len(d_columns)),
-                                                         ctypes.c_uint32(chunk_len), _p(bl), ctypes.c_uint32(blinding_factors), _ptr_array(d_z),
+    _check(lib().h2hip_permutation_products_bn254_device(k, _p(_fe(omega)), _p(_fe(delta)), _p(_fe(beta)), _p(_fe(gamma)),
+                                                         _ptr_array(d_columns), _ptr_array(d_permutations), len(d_columns),
+                                                         chunk_len, _p(bl), blinding_factors, _ptr_array(d_z),
                                                          _stream()), "h2hip_permutation_products_bn254_device")
 
 
@@ -1839,18 +1844,18 @@ def lookup_products_device(k, beta, gamma, d_compressed_inputs, d_compressed_tab
                            blinding_factors, d_z):
     """device form of lookup_products; queued on the current stream, not waited for"""
     bl = _blinding(blinding, len(d_z), int(blinding_factors))
-    _check(lib().h2hip_lookup_products_bn254_device(ctypes.c_uint32(k), _p(_fe(beta)), _p(_fe(gamma)), _ptr_array(d_compressed_inputs),
+    _check(lib().h2hip_lookup_products_bn254_device(k, _p(_fe(beta)), _p(_fe(gamma)), _ptr_array(d_compressed_inputs),
                                                     _ptr_array(d_compressed_tables), _ptr_array(d_permuted_inputs), _ptr_array(d_permuted_tables),
-                                                    ctypes.c_size_t(len(d_z)), _p(bl), ctypes.c_uint32(blinding_factors), _ptr_array(d_z),
+                                                    len(d_z), _p(bl), blinding_factors, _ptr_array(d_z),
                                                     _stream()), "h2hip_lookup_products_bn254_device")
 
 
 def shuffle_products_device(k, gamma, d_compressed_inputs, d_compressed_shuffles, blinding, blinding_factors, d_z):
     """device form of shuffle_products; queued on the current stream, not waited for"""
     bl = _blinding(blinding, len(d_z), int(blinding_factors))
-    _check(lib().h2hip_shuffle_products_bn254_device(ctypes.c_uint32(k), _p(_fe(gamma)), _ptr_array(d_compressed_inputs),
-                                                     _ptr_array(d_compressed_shuffles), ctypes.c_size_t(len(d_z)), _p(bl),
-                                                     ctypes.c_uint32(blinding_factors), _ptr_array(d_z), _stream()),
+    _check(lib().h2hip_shuffle_products_bn254_device(k, _p(_fe(gamma)), _ptr_array(d_compressed_inputs),
+                                                     _ptr_array(d_compressed_shuffles), len(d_z), _p(bl),
+                                                     blinding_factors, _ptr_array(d_z), _stream()),
            "h2hip_shuffle_products_bn254_device")
 
 
@@ -1859,8 +1864,8 @@ def mvlookup_multiplicities_device(k, d_compressed_inputs, d_compressed_tables, 
     current stream, which the call then waits for once (the verdict).  Raises H2HipLookupError when an input value is missing; d_m is
     written either way."""
     flat, n_in = _mv_inputs(d_compressed_inputs, None, len(d_compressed_tables))
-    _check_lookup(lib().h2hip_mvlookup_multiplicities_bn254_device(ctypes.c_uint32(k), _ptr_array(flat), _p(n_in), _ptr_array(d_compressed_tables),
-                                                                   ctypes.c_size_t(len(d_compressed_tables)), ctypes.c_uint32(blinding_factors),
+    _check_lookup(lib().h2hip_mvlookup_multiplicities_bn254_device(k, _ptr_array(flat), _p(n_in), _ptr_array(d_compressed_tables),
+                                                                   len(d_compressed_tables), blinding_factors,
                                                                    _ptr_array(d_m), _stream()), "h2hip_mvlookup_multiplicities_bn254_device")
 
 
@@ -1868,15 +1873,15 @@ def mvlookup_sums_device(k, beta, d_compressed_inputs, d_compressed_tables, d_m,
     """device form of mvlookup_sums; queued on the current stream, not waited for"""
     flat, n_in = _mv_inputs(d_compressed_inputs, None, len(d_compressed_tables))
     bl = _blinding(blinding, len(d_phi), int(blinding_factors))
-    _check(lib().h2hip_mvlookup_sums_bn254_device(ctypes.c_uint32(k), _p(_fe(beta)), _ptr_array(flat), _p(n_in), _ptr_array(d_compressed_tables),
-                                                  _ptr_array(d_m), ctypes.c_size_t(len(d_phi)), _p(bl), ctypes.c_uint32(blinding_factors),
+    _check(lib().h2hip_mvlookup_sums_bn254_device(k, _p(_fe(beta)), _ptr_array(flat), _p(n_in), _ptr_array(d_compressed_tables),
+                                                  _ptr_array(d_m), len(d_phi), _p(bl), blinding_factors,
                                                   _ptr_array(d_phi), _stream()), "h2hip_mvlookup_sums_bn254_device")
 
 
 def batch_invert_device(d_a, n=None):
     """BatchInvert in place on a torch CUDA tensor of n x 32 B; queued on the current stream, not waited for"""
     n = d_a.numel() * d_a.element_size() // 32 if n is None else int(n)
-    _check(lib().h2hip_batch_invert_bn254_fr_device(_dptr(d_a), ctypes.c_size_t(n), _stream()), "h2hip_batch_invert_bn254_fr_device")
+    _check(lib().h2hip_batch_invert_bn254_fr_device(_dptr(d_a), n, _stream()), "h2hip_batch_invert_bn254_fr_device")
 
 
 def eval_polynomials_device(d_polys, query_poly, points, lens=None):
@@ -1886,8 +1891,8 @@ def eval_polynomials_device(d_polys, query_poly, points, lens=None):
     qp = np.ascontiguousarray(query_poly, dtype=np.uint32).reshape(-1)
     pts, nq = _fes(points, "points")
     out = np.zeros((max(1, nq), 4), dtype=np.uint64)
-    _check(lib().h2hip_eval_polynomials_bn254_device(_ptr_array(d_polys), ln, ctypes.c_size_t(len(lens)), _p(qp if nq else np.zeros(1, np.uint32)),
-                                                     _p(pts), ctypes.c_size_t(nq), _p(out), _stream()), "h2hip_eval_polynomials_bn254_device")
+    _check(lib().h2hip_eval_polynomials_bn254_device(_ptr_array(d_polys), ln, len(lens), _p(qp if nq else np.zeros(1, np.uint32)),
+                                                     _p(pts), nq, _p(out), _stream()), "h2hip_eval_polynomials_bn254_device")
     return out[:nq]
 
 
@@ -1898,16 +1903,16 @@ def poly_combine_device(d_polys, scalars, d_out, sub=None, roots=(), scale=None,
     out_len = d_out.numel() * d_out.element_size() // 32 if out_len is None else int(out_len)
     sc, n_sc, sb, n_sub, rt, n_roots, sl = _combine_args(scalars, sub, roots, scale)
     rem = np.zeros(4, dtype=np.uint64)
-    _check(lib().h2hip_poly_combine_bn254_fr_device(_ptr_array(d_polys), ctypes.c_size_t(L), _p(sc), ctypes.c_size_t(len(d_polys)), _p(sb),
-                                                    ctypes.c_size_t(n_sub), _p(rt), ctypes.c_size_t(n_roots), _p(sl),
-                                                    ctypes.c_uint32(1 if accumulate else 0), _dptr(d_out), ctypes.c_size_t(out_len),
+    _check(lib().h2hip_poly_combine_bn254_fr_device(_ptr_array(d_polys), L, _p(sc), len(d_polys), _p(sb),
+                                                    n_sub, _p(rt), n_roots, _p(sl),
+                                                    1 if accumulate else 0, _dptr(d_out), out_len,
                                                     _p(rem) if remainder else None, _stream()), "h2hip_poly_combine_bn254_fr_device")
     return rem if remainder else None
 
 
 def set_opening_tile(rows_per_thread=0, threads_per_tile=0):
     """test hook: force the opening kernels' tile shape (0, 0 = default)"""
-    _check(lib().h2hip_debug_set_opening_tile(ctypes.c_uint32(rows_per_thread), ctypes.c_uint32(threads_per_tile)), "h2hip_debug_set_opening_tile")
+    _check(lib().h2hip_debug_set_opening_tile(rows_per_thread, threads_per_tile), "h2hip_debug_set_opening_tile")
 
 
 
@@ -1917,9 +1922,9 @@ def lookup_compress_device(k, graphs, theta, d_out, d_fixed=(), d_advice=(), d_i
     from .evaluation import graph_array
     arr, keep = graph_array(graphs)
     ch, n_ch = _lookup_challenges(challenges)
-    _check(lib().h2hip_lookup_compress_bn254_device(ctypes.c_uint32(k), _ptr_array(d_fixed), ctypes.c_uint32(len(d_fixed)), _ptr_array(d_advice),
-                                                    ctypes.c_uint32(len(d_advice)), _ptr_array(d_instance), ctypes.c_uint32(len(d_instance)), _p(ch),
-                                                    ctypes.c_uint32(n_ch), _p(_fe(theta)), arr, ctypes.c_size_t(len(graphs)), _ptr_array(d_out),
+    _check(lib().h2hip_lookup_compress_bn254_device(k, _ptr_array(d_fixed), len(d_fixed), _ptr_array(d_advice),
+                                                    len(d_advice), _ptr_array(d_instance), len(d_instance), _p(ch),
+                                                    n_ch, _p(_fe(theta)), arr, len(graphs), _ptr_array(d_out),
                                                     _stream()), "h2hip_lookup_compress_bn254_device")
     del keep
 
@@ -1928,8 +1933,8 @@ def lookup_permute_device(k, d_compressed_inputs, d_compressed_tables, blinding,
     """lookup_permute over torch CUDA tensors; queued on the current stream, which the call then waits for once (the not-found flags).
     Raises H2HipLookupError when an input value is missing from its table."""
     bl = _lookup_blinding(blinding, len(d_compressed_inputs), int(blinding_factors))
-    _check_lookup(lib().h2hip_lookup_permute_bn254_device(ctypes.c_uint32(k), _ptr_array(d_compressed_inputs), _ptr_array(d_compressed_tables),
-                                                          ctypes.c_size_t(len(d_compressed_inputs)), _p(bl), ctypes.c_uint32(blinding_factors),
+    _check_lookup(lib().h2hip_lookup_permute_bn254_device(k, _ptr_array(d_compressed_inputs), _ptr_array(d_compressed_tables),
+                                                          len(d_compressed_inputs), _p(bl), blinding_factors,
                                                           _ptr_array(d_permuted_inputs), _ptr_array(d_permuted_tables), _stream()),
                   "h2hip_lookup_permute_bn254_device")
 
@@ -1941,9 +1946,9 @@ def check_gates_device(k, graphs, d_fixed=(), d_advice=(), d_instance=(), challe
     arr, keep = graph_array(graphs)
     ch, n_ch = _lookup_challenges(challenges)
     counts, rows, prow = _check_out(len(graphs), max_rows)
-    _check(lib().h2hip_check_gates_bn254_device(ctypes.c_uint32(k), _ptr_array(d_fixed), ctypes.c_uint32(len(d_fixed)), _ptr_array(d_advice),
-                                                ctypes.c_uint32(len(d_advice)), _ptr_array(d_instance), ctypes.c_uint32(len(d_instance)), _p(ch),
-                                                ctypes.c_uint32(n_ch), arr, ctypes.c_size_t(len(graphs)), ctypes.c_uint32(max_rows), _p(counts),
+    _check(lib().h2hip_check_gates_bn254_device(k, _ptr_array(d_fixed), len(d_fixed), _ptr_array(d_advice),
+                                                len(d_advice), _ptr_array(d_instance), len(d_instance), _p(ch),
+                                                n_ch, arr, len(graphs), max_rows, _p(counts),
                                                 prow, _stream()), "h2hip_check_gates_bn254_device")
     del keep
     return _check_result(counts, rows, len(graphs), max_rows)
@@ -1953,8 +1958,8 @@ def check_permutation_device(k, d_columns, d_mapping, max_rows=16):
     """check_permutation over torch CUDA tensors: d_mapping[j] holds 2^k (column, row) uint32 pairs (8 B per cell).  Queued on the
     current stream, waited for once; a pair out of range is not followed and raises H2HipError (H2HIP_EINVAL)."""
     counts, rows, prow = _check_out(len(d_columns), max_rows)
-    _check(lib().h2hip_check_permutation_bn254_device(ctypes.c_uint32(k), _ptr_array(d_columns), _ptr_array(d_mapping),
-                                                      ctypes.c_uint32(len(d_columns)), ctypes.c_uint32(max_rows), _p(counts), prow, _stream()),
+    _check(lib().h2hip_check_permutation_bn254_device(k, _ptr_array(d_columns), _ptr_array(d_mapping),
+                                                      len(d_columns), max_rows, _p(counts), prow, _stream()),
            "h2hip_check_permutation_bn254_device")
     return _check_result(counts, rows, len(d_columns), max_rows)
 
@@ -1963,8 +1968,8 @@ def check_lookups_device(k, d_compressed_inputs, d_compressed_tables, blinding_f
     """check_lookups over torch CUDA tensors; queued on the current stream, waited for once"""
     count = len(d_compressed_inputs)
     counts, rows, prow = _check_out(count, max_rows)
-    _check(lib().h2hip_check_lookups_bn254_device(ctypes.c_uint32(k), _ptr_array(d_compressed_inputs), _ptr_array(d_compressed_tables),
-                                                  ctypes.c_size_t(count), ctypes.c_uint32(blinding_factors), ctypes.c_uint32(max_rows), _p(counts),
+    _check(lib().h2hip_check_lookups_bn254_device(k, _ptr_array(d_compressed_inputs), _ptr_array(d_compressed_tables),
+                                                  count, blinding_factors, max_rows, _p(counts),
                                                   prow, _stream()), "h2hip_check_lookups_bn254_device")
     return _check_result(counts, rows, count, max_rows)
 
@@ -1973,15 +1978,15 @@ def check_shuffles_device(k, d_compressed_inputs, d_compressed_shuffles, blindin
     """check_shuffles over torch CUDA tensors; queued on the current stream, waited for once"""
     count = len(d_compressed_inputs)
     counts, rows, prow = _check_out(count, max_rows)
-    _check(lib().h2hip_check_shuffles_bn254_device(ctypes.c_uint32(k), _ptr_array(d_compressed_inputs), _ptr_array(d_compressed_shuffles),
-                                                   ctypes.c_size_t(count), ctypes.c_uint32(blinding_factors), ctypes.c_uint32(max_rows),
+    _check(lib().h2hip_check_shuffles_bn254_device(k, _ptr_array(d_compressed_inputs), _ptr_array(d_compressed_shuffles),
+                                                   count, blinding_factors, max_rows,
                                                    _p(counts), prow, _stream()), "h2hip_check_shuffles_bn254_device")
     return _check_result(counts, rows, count, max_rows)
 
 
 def set_lookup_sort(lds_keys=0):
     """test hook: force the lookup sort's in-LDS block (a power of two in [4, 1024]; 0 = default)"""
-    _check(lib().h2hip_debug_set_lookup_sort(ctypes.c_uint32(lds_keys)), "h2hip_debug_set_lookup_sort")
+    _check(lib().h2hip_debug_set_lookup_sort(lds_keys), "h2hip_debug_set_lookup_sort")
 
 
 def lookup_sort_stats():
@@ -1994,7 +1999,7 @@ def lookup_sort_stats():
 def copies_sort_plan(n_copies):
     """(block, merge passes) of permutation_mapping's sort for n_copies copies: the keys one workgroup sorts in LDS, and the passes after"""
     out = (ctypes.c_uint32 * 2)()
-    _check(lib().h2hip_debug_copies_sort_plan(ctypes.c_size_t(n_copies), out), "h2hip_debug_copies_sort_plan")
+    _check(lib().h2hip_debug_copies_sort_plan(n_copies, out), "h2hip_debug_copies_sort_plan")
     return int(out[0]), int(out[1])
 
 
@@ -2007,7 +2012,7 @@ def permutation_keygen_device(domain, d_mapping, d_permutations=None, d_polys=No
     of m tensors (2^k x 32 B; cosets 2^extended_k x 32 B) or None.  Queued on the current stream, which the call waits for once at its end
     (the out-of-range flag)."""
     d = fr_from_int(FR_DELTA) if delta is None else _fe(delta)
-    _check(lib().h2hip_permutation_keygen_bn254_device(*_domain_args(domain), _p(d), _ptr_array(d_mapping), ctypes.c_uint32(len(d_mapping)),
+    _check(lib().h2hip_permutation_keygen_bn254_device(*_domain_args(domain), _p(d), _ptr_array(d_mapping), len(d_mapping),
                                                        _opt_ptr_array(d_permutations), _opt_ptr_array(d_polys), _opt_ptr_array(d_cosets),
                                                        _stream()), "h2hip_permutation_keygen_bn254_device")
 
@@ -2018,8 +2023,8 @@ def permutation_mapping_device(k, n_columns, d_copies, d_mapping, n_copies=None)
     copy out of range: H2HipError, the mapping of the valid copies written)."""
     if n_copies is None:
         n_copies = 0 if d_copies is None else d_copies.numel() * d_copies.element_size() // 16
-    _check(lib().h2hip_permutation_mapping_device(ctypes.c_uint32(k), ctypes.c_uint32(n_columns), None if d_copies is None else _dptr(d_copies),
-                                                  ctypes.c_size_t(n_copies), _ptr_array(d_mapping), _stream()), "h2hip_permutation_mapping_device")
+    _check(lib().h2hip_permutation_mapping_device(k, n_columns, None if d_copies is None else _dptr(d_copies),
+                                                  n_copies, _ptr_array(d_mapping), _stream()), "h2hip_permutation_mapping_device")
 
 
 def permutation_keygen_from_copies(domain, n_columns, copies, want=_KEYGEN_FORMS, delta=None):
@@ -2048,56 +2053,56 @@ def batch_invert_assigned_device(k, d_numerators, d_rat_rows, rat_counts, d_rat_
     m = len(d_numerators)
     opt = lambda ts: (ctypes.c_void_p * max(1, m))(*[(None if t is None else t.data_ptr()) for t in ts])
     cnt = (ctypes.c_size_t * max(1, m))(*[int(x) for x in rat_counts])
-    _check(lib().h2hip_batch_invert_assigned_bn254_device(ctypes.c_uint32(k), _ptr_array(d_numerators), opt(d_rat_rows), cnt, opt(d_rat_denoms),
-                                                          ctypes.c_size_t(m), _ptr_array(d_out), _stream()),
+    _check(lib().h2hip_batch_invert_assigned_bn254_device(k, _ptr_array(d_numerators), opt(d_rat_rows), cnt, opt(d_rat_denoms),
+                                                          m, _ptr_array(d_out), _stream()),
            "h2hip_batch_invert_assigned_bn254_device")
 
 
 def key_lagrange_columns_device(domain, blinding_factors, d_l0, d_l_last, d_l_active_row):
     """key_lagrange_columns into three torch CUDA tensors of 2^extended_k x 32 B; queued on the current stream, not waited for"""
-    _check(lib().h2hip_key_lagrange_columns_bn254_device(ctypes.c_uint32(domain.k), _p(domain.omega_inv), _p(domain.ifft_divisor),
-                                                         ctypes.c_uint32(domain.extended_k), _p(domain.extended_omega), _p(domain.g_coset),
-                                                         _p(domain.g_coset_inv), ctypes.c_uint32(blinding_factors), _dptr(d_l0), _dptr(d_l_last),
+    _check(lib().h2hip_key_lagrange_columns_bn254_device(domain.k, _p(domain.omega_inv), _p(domain.ifft_divisor),
+                                                         domain.extended_k, _p(domain.extended_omega), _p(domain.g_coset),
+                                                         _p(domain.g_coset_inv), blinding_factors, _dptr(d_l0), _dptr(d_l_last),
                                                          _dptr(d_l_active_row), _stream()), "h2hip_key_lagrange_columns_bn254_device")
 
 
 def set_keygen_group(group_bytes=0):
     """test hook: the HBM one group of columns of a host-pointer keygen call takes (0 = default), so that small inputs run several groups"""
-    _check(lib().h2hip_debug_set_keygen_group(ctypes.c_uint64(group_bytes)), "h2hip_debug_set_keygen_group")
+    _check(lib().h2hip_debug_set_keygen_group(group_bytes), "h2hip_debug_set_keygen_group")
 
 
 def g1_from_bytes_device(d_bytes, d_points, n):
     """d_bytes: n x 32 B, d_points: n x 64 B (torch CUDA tensors); H2HipEncodingError when an encoding is invalid (d_points is written whole)"""
     invalid = np.zeros(2, dtype=np.uint64)
-    _check_encoding(lib().h2hip_g1_decompress_bn254_device(_dptr(d_bytes), ctypes.c_size_t(n), _dptr(d_points), _p(invalid), _stream()),
+    _check_encoding(lib().h2hip_g1_decompress_bn254_device(_dptr(d_bytes), n, _dptr(d_points), _p(invalid), _stream()),
                     "h2hip_g1_decompress_bn254_device", invalid)
 
 
 def g1_to_bytes_device(d_points, d_bytes, n):
-    _check(lib().h2hip_g1_compress_bn254_device(_dptr(d_points), ctypes.c_size_t(n), _dptr(d_bytes), _stream()), "h2hip_g1_compress_bn254_device")
+    _check(lib().h2hip_g1_compress_bn254_device(_dptr(d_points), n, _dptr(d_bytes), _stream()), "h2hip_g1_compress_bn254_device")
 
 
 def g1_validate_device(d_points, n):
     invalid = np.zeros(2, dtype=np.uint64)
-    _check_encoding(lib().h2hip_g1_validate_bn254_device(_dptr(d_points), ctypes.c_size_t(n), _p(invalid), _stream()),
+    _check_encoding(lib().h2hip_g1_validate_bn254_device(_dptr(d_points), n, _p(invalid), _stream()),
                     "h2hip_g1_validate_bn254_device", invalid)
 
 
 def fr_from_repr_device(d_repr, d_out, n):
     """d_out may be d_repr"""
     invalid = np.zeros(2, dtype=np.uint64)
-    _check_encoding(lib().h2hip_fr_from_repr_bn254_device(_dptr(d_repr), ctypes.c_size_t(n), _dptr(d_out), _p(invalid), _stream()),
+    _check_encoding(lib().h2hip_fr_from_repr_bn254_device(_dptr(d_repr), n, _dptr(d_out), _p(invalid), _stream()),
                     "h2hip_fr_from_repr_bn254_device", invalid)
 
 
 def fr_to_repr_device(d_in, d_repr, n):
-    _check(lib().h2hip_fr_to_repr_bn254_device(_dptr(d_in), ctypes.c_size_t(n), _dptr(d_repr), _stream()), "h2hip_fr_to_repr_bn254_device")
+    _check(lib().h2hip_fr_to_repr_bn254_device(_dptr(d_in), n, _dptr(d_repr), _stream()), "h2hip_fr_to_repr_bn254_device")
 
 
 def gen_scalars_device(seed, n, start=0, device="cuda"):
     import torch
     out = torch.empty((n, 4), dtype=torch.int64, device=device)
-    _check(lib().h2hip_gen_scalars_device(ctypes.c_uint64(seed), ctypes.c_uint64(start), ctypes.c_size_t(n), _dptr(out), _stream()),
+    _check(lib().h2hip_gen_scalars_device(seed, start, n, _dptr(out), _stream()),
            "h2hip_gen_scalars_device")
     return out
 
@@ -2105,7 +2110,7 @@ def gen_scalars_device(seed, n, start=0, device="cuda"):
 def gen_points_device(seed, n, start=0, device="cuda"):
     import torch
     out = torch.empty((n, 8), dtype=torch.int64, device=device)
-    _check(lib().h2hip_gen_points_device(ctypes.c_uint64(seed), ctypes.c_uint64(start), ctypes.c_size_t(n), _dptr(out), _stream()),
+    _check(lib().h2hip_gen_points_device(seed, start, n, _dptr(out), _stream()),
            "h2hip_gen_points_device")
     return out
 
@@ -2123,7 +2128,7 @@ def fr_random(seed, n, first_block=0, stream_id=0):
     ChaCha20 block first_block + i -> (n, 4) uint64 Montgomery.  Below HALO2_HIP_RANDOM_MIN_N elements this runs on the calling thread
     and needs no GPU.  The seed is as secret as the elements: the engine expands it and adds no entropy."""
     out = np.zeros((int(n), 4), dtype=np.uint64)
-    _check(lib().h2hip_fr_random_bn254(_seed32(seed), ctypes.c_uint64(stream_id), ctypes.c_uint64(first_block), ctypes.c_size_t(int(n)), _p(out)),
+    _check(lib().h2hip_fr_random_bn254(_seed32(seed), stream_id, first_block, int(n), _p(out)),
            "h2hip_fr_random_bn254")
     return out
 
@@ -2135,7 +2140,7 @@ def fr_random_device(seed, n, first_block=0, stream_id=0, out=None):
             raise H2HipError("fr_random_device: no GPU (no CPU fallback exists)")
         import torch
         out = torch.empty((int(n), 4), dtype=torch.int64, device="cuda")
-    _check(lib().h2hip_fr_random_bn254_device(_seed32(seed), ctypes.c_uint64(stream_id), ctypes.c_uint64(first_block), ctypes.c_size_t(int(n)),
+    _check(lib().h2hip_fr_random_bn254_device(_seed32(seed), stream_id, first_block, int(n),
                                               _dptr(out), _stream()), "h2hip_fr_random_bn254_device")
     return out
 
@@ -2146,13 +2151,13 @@ def fr_from_bytes_wide(data):
     if data.ndim != 2 or data.shape[1] != 64:
         raise ValueError("fr_from_bytes_wide: expected shape (n,64), got %s" % (data.shape,))
     out = np.zeros((data.shape[0], 4), dtype=np.uint64)
-    _check(lib().h2hip_fr_from_bytes_wide_bn254(_p(data), ctypes.c_size_t(data.shape[0]), _p(out)), "h2hip_fr_from_bytes_wide_bn254")
+    _check(lib().h2hip_fr_from_bytes_wide_bn254(_p(data), data.shape[0], _p(out)), "h2hip_fr_from_bytes_wide_bn254")
     return out
 
 
 def fr_from_bytes_wide_device(d_bytes, d_out, n):
     """d_bytes: n x 64 B, d_out: n x 32 B (torch CUDA tensors, not overlapping); queued on the current stream"""
-    _check(lib().h2hip_fr_from_bytes_wide_bn254_device(_dptr(d_bytes), ctypes.c_size_t(n), _dptr(d_out), _stream()),
+    _check(lib().h2hip_fr_from_bytes_wide_bn254_device(_dptr(d_bytes), n, _dptr(d_out), _stream()),
            "h2hip_fr_from_bytes_wide_bn254_device")
 
 
@@ -2195,7 +2200,7 @@ def to_numpy_u64(t):
 
 # ------------------------------------------------------------------ tuning / measurement
 def set_msm_window(c):
-    _check(lib().h2hip_set_msm_window(ctypes.c_uint32(c)), "h2hip_set_msm_window")
+    _check(lib().h2hip_set_msm_window(c), "h2hip_set_msm_window")
 
 
 def get_msm_window(n):

@@ -487,9 +487,8 @@ def evaluate_h_workspace_bytes(k, extended_k, n_fixed, n_advice, n_instance, n_p
     """HBM the engine allocates for the columns of one evaluate_h call and its copy of `values` (h2hip_evaluate_h_workspace_bytes; no GPU needed)"""
     from . import _check, lib
     out = ctypes.c_size_t()
-    u = ctypes.c_uint32
-    _check(lib().h2hip_evaluate_h_workspace_bytes(u(k), u(extended_k), u(n_fixed), u(n_advice), u(n_instance), u(n_perm_sets), u(n_perm_columns),
-                                                  u(n_lookups), ctypes.c_int(bool(parts_form)), ctypes.c_int(bool(device_form)), ctypes.byref(out)),
+    _check(lib().h2hip_evaluate_h_workspace_bytes(k, extended_k, n_fixed, n_advice, n_instance, n_perm_sets, n_perm_columns,
+                                                  n_lookups, bool(parts_form), bool(device_form), ctypes.byref(out)),
            "evaluate_h_workspace_bytes")
     return out.value
 
@@ -499,10 +498,9 @@ def evaluate_h_shuffles_workspace_bytes(k, extended_k, n_fixed, n_advice, n_inst
     """evaluate_h_workspace_bytes for a call with n_shuffles shuffles (h2hip_evaluate_h_shuffles_workspace_bytes; no GPU needed)"""
     from . import _check, lib
     out = ctypes.c_size_t()
-    u = ctypes.c_uint32
-    _check(lib().h2hip_evaluate_h_shuffles_workspace_bytes(u(k), u(extended_k), u(n_fixed), u(n_advice), u(n_instance), u(n_perm_sets),
-                                                           u(n_perm_columns), u(n_lookups), u(n_shuffles), ctypes.c_int(bool(parts_form)),
-                                                           ctypes.c_int(bool(device_form)), ctypes.byref(out)),
+    _check(lib().h2hip_evaluate_h_shuffles_workspace_bytes(k, extended_k, n_fixed, n_advice, n_instance, n_perm_sets,
+                                                           n_perm_columns, n_lookups, n_shuffles, bool(parts_form),
+                                                           bool(device_form), ctypes.byref(out)),
            "evaluate_h_shuffles_workspace_bytes")
     return out.value
 
@@ -513,10 +511,9 @@ def evaluate_h_ext_workspace_bytes(k, extended_k, n_fixed, n_advice, n_instance,
     (h2hip_evaluate_h_ext_workspace_bytes; no GPU needed)"""
     from . import _check, lib
     out = ctypes.c_size_t()
-    u = ctypes.c_uint32
-    _check(lib().h2hip_evaluate_h_ext_workspace_bytes(u(k), u(extended_k), u(n_fixed), u(n_advice), u(n_instance), u(n_perm_sets),
-                                                      u(n_perm_columns), u(n_lookups), u(n_mvlookups), u(n_shuffles),
-                                                      ctypes.c_int(bool(parts_form)), ctypes.c_int(bool(device_form)), ctypes.byref(out)),
+    _check(lib().h2hip_evaluate_h_ext_workspace_bytes(k, extended_k, n_fixed, n_advice, n_instance, n_perm_sets,
+                                                      n_perm_columns, n_lookups, n_mvlookups, n_shuffles,
+                                                      bool(parts_form), bool(device_form), ctypes.byref(out)),
            "evaluate_h_ext_workspace_bytes")
     return out.value
 

@@ -362,8 +362,8 @@ class _Device:
             self.pk.ev.evaluate_h_device(case, values)
             if t_evaluations is not None:                                                                  # vanishing/prover.rs:84
                 t = np.ascontiguousarray(t_evaluations, dtype=np.uint64)
-                _check(lib().h2hip_divide_by_vanishing_poly_bn254_fr_device(_dptr(values), ctypes.c_uint32(self.dom.extended_k),
-                                                                            t.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint32(t.shape[0]),
+                _check(lib().h2hip_divide_by_vanishing_poly_bn254_fr_device(_dptr(values), self.dom.extended_k,
+                                                                            t.ctypes.data_as(ctypes.c_void_p), t.shape[0],
                                                                             _stream()), "h2hip_divide_by_vanishing_poly_bn254_fr_device")
                 self.torch.cuda.current_stream().synchronize()  # t is read by the queued kernel's launch; keep it until then
         return values

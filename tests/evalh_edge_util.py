@@ -444,7 +444,6 @@ def compiled_program(h2, flat):
     G = graph_struct(flat, keep)
     L = h2.lib()
     n_ops, n_slots, res = ctypes.c_uint32(), ctypes.c_uint32(), (ctypes.c_uint32 * 3)()
-    L.h2hip_debug_evalh_program.restype = ctypes.c_int
     rc = L.h2hip_debug_evalh_program(ctypes.byref(G), None, ctypes.c_size_t(0), ctypes.byref(n_ops), ctypes.byref(n_slots), res, None, None, None)
     assert rc == 0, L.h2hip_last_error()
     n = n_ops.value

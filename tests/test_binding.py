@@ -2,7 +2,8 @@
 reference tree it patches.  No Rust toolchain exists in this image, so nothing here compiles Rust:
   * halo2hip-sys/src/ffi.rs is the translation of include/halo2hip.h by tools/gen_rust_extern.py -- regenerated and compared;
   * every `extern "C"` name is exported by libhalo2hip.so, with the header's arity;
-  * the #[repr(C)] structs of halo2hip-sys/src/evalh.rs list the header's fields, in the header's order, with matching types;
+  * the #[repr(C)] structs of halo2hip-sys/src/evalh.rs list the header's fields, in the header's order, with matching types, and so
+    do the ctypes Structures of halo2-pse_amd/evaluation.py (the Python binding's prototypes: tests/test_ctypes_abi.py);
   * patches/*.patch apply with no fuzz to the reference files they touch, checked against hashes of those files' hunk regions
     recorded by tests/golden/make_patch_golden.py (the reference tree itself is not needed)."""
 import os
@@ -52,9 +53,10 @@ C2R = {"uint32_t": "u32", "int32_t": "i32", "const uint64_t*": "*const u64", "co
 
 
 def _c_structs():
+    """{typedef name: [(field, C type)]} of every struct include/halo2hip.h defines, fields in the header's order"""
     text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "halo2hip.h")).read(), flags=re.S)
     out = {}
-    for body, name in re.findall(r"typedef struct \{(.*?)\}\s*(h2hip_[a-z_]+);", text, flags=re.S):
+    for body, name in re.findall(r"typedef struct(?: h2hip_[a-z_]+)? \{(.*?)\}\s*(h2hip_[a-z_]+);", text, flags=re.S):
         fields = []
         for decl in body.split(";"):
             decl = " ".join(decl.split())
@@ -64,14 +66,14 @@ def _c_structs():
             m = re.match(r"^(.*?)([a-z_0-9]+)$", parts[0])
             first_type, first_name = m.group(1).strip(), m.group(2)
             if len(parts) == 1:
-                fields.append((first_name, C2R[first_type.replace(" *", "*")]))
+                fields.append((first_name, first_type.replace(" *", "*")))
                 continue
             base = first_type.rstrip("* ")  # `const uint64_t *a, *b`: the stars belong to the declarators
             for k, part in enumerate(parts):
                 decl_k = (first_type[len(base):] + first_name) if k == 0 else part
                 decl_k = decl_k.replace(" ", "")
                 stars = len(decl_k) - len(decl_k.lstrip("*"))
-                fields.append((decl_k.lstrip("*"), C2R[base + "*" * stars]))
+                fields.append((decl_k.lstrip("*"), base + "*" * stars))
         out[name] = fields
     return out
 
@@ -86,9 +88,28 @@ def _rust_structs():
 
 def test_repr_c_structs_match_the_header_field_for_field():
     c, r = _c_structs(), _rust_structs()
-    assert set(c) == {"h2hip_value_source", "h2hip_calculation", "h2hip_graph", "h2hip_evalh_desc"} == set(r)
-    for name in c:
-        assert r[name] == c[name], name
+    assert {"h2hip_value_source", "h2hip_calculation", "h2hip_graph", "h2hip_evalh_desc"} == set(r) <= set(c)
+    for name in r:
+        assert r[name] == [(field, C2R[t]) for field, t in c[name]], name
+
+
+PY_STRUCTS = {"h2hip_value_source": "ValueSource", "h2hip_calculation": "Calculation", "h2hip_graph": "Graph", "h2hip_evalh_desc": "EvalhDesc",
+              "h2hip_evalh_parts_desc": "EvalhPartsDesc", "h2hip_evalh_shuffles": "EvalhShuffles", "h2hip_evalh_mvlookups": "EvalhMvLookups"}
+
+
+def test_ctypes_structures_match_the_header_field_for_field(h2):
+    """the ctypes mirrors of halo2-pse_amd/evaluation.py list every struct's fields in the header's order; a uint32_t is c_uint32, an
+    int32_t c_int32, a nested struct its own mirror and any pointer c_void_p"""
+    import ctypes
+    import importlib
+    ev = importlib.import_module("halo2_pse_amd.evaluation")
+    c = _c_structs()
+    assert set(c) == set(PY_STRUCTS)
+    by_value = {"uint32_t": ctypes.c_uint32, "int32_t": ctypes.c_int32}
+    by_value.update({name: getattr(ev, cls) for name, cls in PY_STRUCTS.items()})
+    for name, cls in PY_STRUCTS.items():
+        want = [(field, ctypes.c_void_p if t.endswith("*") else by_value[t]) for field, t in c[name]]
+        assert getattr(ev, cls)._fields_ == want, name
 
 
 def test_enum_constants_match_the_header():

@@ -119,7 +119,6 @@ def test_fusion_applies_per_program_and_follows_the_switch(h2):
 
 def test_beyond_the_limits_and_malformed_input(h2):
     L = h2.lib()
-    L.h2hip_last_error.restype = ctypes.c_char_p
     three = shuffle_graphs(*THREE)
     assert stage_source(h2, three, SHUFFLE, compile=False)[0] == 0
     with codegen(h2, 1, max_ops=5):  # the two programs have more than five operations between them

@@ -208,7 +208,6 @@ def test_stream_chunk_ladder_host_logic(h2):
     inputs collapse to fewer pieces, and below 2^20 pairs the default is two"""
     import ctypes
     L = h2.lib()
-    L.h2hip_debug_msm_stream_ladder.restype = ctypes.c_size_t
 
     def ladder(n, chunks=0, permille=0, with_bases=0):
         out = (ctypes.c_size_t * 32)()

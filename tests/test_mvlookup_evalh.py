@@ -269,7 +269,6 @@ def test_mvlookup_graphs_have_the_documented_shape():
 def test_evaluate_h_ext_rejections_need_no_gpu(h2, oracle):
     """H2HIP_EINVAL with a named error from each of the four entry points, before any device work"""
     L = h2.lib()
-    L.h2hip_last_error.restype = ctypes.c_char_p
     sy = _system(oracle, 4, 4, 7, "with_all")
     flat = [([flatten_graph(g) for g in gs], phi, m) for gs, phi, m in zip(sy.ev.mv_lookups, sy.phi, sy.m)]
 

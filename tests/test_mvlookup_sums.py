@@ -84,7 +84,6 @@ def test_model_sum_of_a_valid_argument_ends_in_zero_and_of_an_invalid_one_does_n
 def test_rejections_need_no_gpu(h2):
     """H2HIP_EINVAL and a named error before the engine is entered"""
     L = h2.lib()
-    L.h2hip_last_error.restype = ctypes.c_char_p
     buf = (ctypes.c_uint64 * 64)()
     one = (ctypes.c_uint64 * 4)(1, 0, 0, 0)
     tab = (ctypes.c_void_p * 1)(ctypes.addressof(buf))

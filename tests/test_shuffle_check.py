@@ -65,7 +65,6 @@ def _device(h2, k, a, s, max_rows):
 def test_rejections_need_no_gpu(h2):
     """H2HIP_EINVAL and a named error before the engine is entered: a NULL table, b + 1 >= n, k > 28, null outputs, max_rows too large"""
     L = h2.lib()
-    L.h2hip_last_error.restype = ctypes.c_char_p
     buf = (ctypes.c_uint64 * 64)()
     tab = (ctypes.c_void_p * 1)(ctypes.addressof(buf))
     u32, sz = ctypes.c_uint32, ctypes.c_size_t

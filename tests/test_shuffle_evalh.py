@@ -228,7 +228,6 @@ def test_evaluate_h_shuffles_rejections_need_no_gpu(h2, oracle):
     """H2HIP_EINVAL with a named error from each of the four entry points, before any device work: NULL tables, a null product polynomial,
     a graph reading beta, y or the previous value, an index out of range, k > 28"""
     L = h2.lib()
-    L.h2hip_last_error.restype = ctypes.c_char_p
     sy = _system(oracle, 4, 4, 7, True)
     flat = [(flatten_graph(gi), flatten_graph(gs), z) for (gi, gs), z in zip(sy.ev.shuffles, sy.z)]
 

@@ -75,7 +75,6 @@ def test_model_product_of_a_valid_shuffle_ends_in_one():
 def test_rejections_need_no_gpu(h2):
     """H2HIP_EINVAL and a named error before the engine is entered: a NULL table, b + 1 >= n, k > 28, a null scalar"""
     L = h2.lib()
-    L.h2hip_last_error.restype = ctypes.c_char_p
     buf = (ctypes.c_uint64 * 64)()
     one = (ctypes.c_uint64 * 4)(1, 0, 0, 0)
     tab = (ctypes.c_void_p * 1)(ctypes.addressof(buf))

@@ -54,9 +54,6 @@ from __graft_entry__ import load_pkg
 calls = json.loads(sys.argv[2])
 L = load_pkg().lib()
 CT = {"uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t, "int": ctypes.c_int}
-L.h2hip_debug_msm_stream_ladder.restype = ctypes.c_size_t
-L.h2hip_get_msm_window.restype = ctypes.c_uint32
-L.h2hip_get_msm_window_fixed_base.restype = ctypes.c_uint32
 
 def observe():
     out = {}
