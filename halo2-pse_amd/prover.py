@@ -2,29 +2,43 @@
 points, with every column resident in HBM from the first commit to the last opening.
 
   ConstraintSystem   a plain description of plonk/circuit.rs's ConstraintSystem: column counts, phases, gate polynomials, lookup
-                     arguments and permutation columns as the expression tuples of evaluation.py; degree (:1974-2002), blinding_factors
-                     (:2006-2031), phases (:1962-1970) and the query lists (query_*_index :1571-1627) are derived from it
+                     arguments, shuffles, mv-lookups and permutation columns as the expression tuples of evaluation.py; degree
+                     (:1974-2002), blinding_factors (:2006-2031), phases (:1962-1970) and the query lists (query_*_index :1571-1627)
+                     are derived from it
   ProvingKey.build   keygen_vk + keygen_pk's columns through keygen_columns, uploaded once; the fixed and permutation commitments are
                      the verifying key (VerifyingKey)
   create_proof       prover.rs, step by step (the line numbers are beside each step), with lookup/prover.rs, permutation/prover.rs and
                      vanishing/prover.rs in their places and the multiopen provers of poly/kzg/multiopen/{gwc,shplonk}/prover.rs at the end
 
 Both KZG provers set QUERY_INSTANCE = false (gwc/prover.rs, shplonk/prover.rs:111), so instance values go into the transcript as scalars
-(prover.rs:90-93) and instance columns are neither committed nor opened; the QUERY_INSTANCE branch (IPA) is not restated.  The shuffle and
-mv-lookup arguments are later than the reference and are not part of this prover; ARGUMENT_STAGES names the places they would take.
+(prover.rs:90-93) and instance columns are neither committed nor opened; the QUERY_INSTANCE branch (IPA) is not restated.
+
+Later arguments.  The shuffle argument (upstream PSE halo2) and the logUp "mv-lookup" argument (the forks that replaced the permuted-column
+lookup) are later than the reference; both coexist with the halo2 lookup here, as they do in h2hip_evaluate_h_ext_*.  ARGUMENT_STAGES
+lists every stage between theta and y in the order it runs, each with its per-instance loop outermost:
+  theta | permuted columns A', S' of the halo2 lookups | mv-lookup multiplicities m | beta, gamma | permutation products | lookup products
+        | mv-lookup grand sums phi | shuffle products z | random polynomial | y
+h(X) folds gates, permutation, halo2 lookups, mv-lookups, shuffles (include/halo2hip.h); evaluations and opening queries follow the
+lookups' in the same order: per mv-lookup phi(x), phi(wx), m(x), then per shuffle z(x), z(wx).  Like the reference's arguments, the prover
+does not check that a shuffle's product ends in one: the proof is made and the verifier refuses it.  An mv-lookup input its table lacks
+raises H2HipLookupError, as a halo2 lookup's does.
 
 Query order.  The reference registers a query the first time configure() asks for it.  A plain description has no configure(), so the order
 is fixed here as that of a configure() which enables equality on the permutation columns first (enable_equality queries Rotation::cur,
 :1516-1520), then creates the gates in order (each polynomial read left to right), then the lookups (input expressions, then table
-expressions).  Prover and verifier derive the same lists from the same description.
+expressions), then the mv-lookups (each argument's input tuples in order, then its table), then the shuffles (input expressions, then
+shuffle expressions).  Prover and verifier derive the same lists from the same description.
 
 Random draws.  Everything random comes from one FrRng(seed) (ChaCha20, one 64-byte block per Fr::random), in the reference's order:
   1. per phase, per instance: (b + 1) blinding rows for each advice column of the phase, column by column (prover.rs:350-354), then one
      commitment blind per column (:357-360)
   2. per instance, per lookup: 2(b + 1) rows for A' and S' (permute_expression_pair, lookup/prover.rs:391-475), then the two commitment
      blinds (:129)
+  2b. per instance, per mv-lookup: one commitment blind for m (m has no blinding rows: its rows u .. n - 1 are zero)
   3. per instance, per permutation set: b rows of z (permutation/prover.rs:162-164), then its blind (:168)
   4. per instance, per lookup: b rows of z (lookup/prover.rs:247), then its blind (:290)
+  4b. per instance, per mv-lookup: b rows of phi, then its blind
+  4c. per instance, per shuffle: b rows of z, then its blind
   5. the 2^k coefficients of the vanishing argument's random polynomial, drawn in HBM (vanishing/prover.rs:50-53), then its blind (:55)
   6. one blind per piece of h(X) (vanishing/prover.rs:95-98)
 The KZG commitment ignores its blind (poly/kzg/commitment.rs:281-292), as ParamsKZG does here; the blinds are drawn to keep the stream in
@@ -45,14 +59,18 @@ import numpy as np
 from . import (FR_DELTA, FR_MODULUS, FR_ZETA, CopyList, EvaluationDomain, FrRng, H2HipError, _check, _dptr, _stream, best_multiexp_batch,
                columns_pin, columns_unpin, commit_permuted, eval_polynomials, eval_polynomials_device, extended_to_coeff_device, fr_from_int,
                fr_random, fr_to_int, g1_to_affine, g1_to_bytes, gwc_witnesses, ifft_batch_device, coeff_to_extended_batch_device,
-               keygen_columns, lib, lookup_compress_device, lookup_permute_device, lookup_products, lookup_products_device, msm_batch_device,
+               keygen_columns, lib, lookup_compress, lookup_compress_device, lookup_permute_device, lookup_products, lookup_products_device,
+               msm_batch_device, mvlookup_multiplicities, mvlookup_multiplicities_device, mvlookup_sums, mvlookup_sums_device,
                part_cosets_pin, part_cosets_unpin, permutation_products, permutation_products_device, poly_combine, poly_combine_device,
-               shplonk_final, shplonk_h, bases_pin_device)
-from .evaluation import ANY_ADVICE, ANY_FIXED, ANY_INSTANCE, Evaluator, expression_degree, flatten_graph, lookup_compress_graphs
+               shplonk_final, shplonk_h, shuffle_products, shuffle_products_device, bases_pin_device)
+from .evaluation import (ANY_ADVICE, ANY_FIXED, ANY_INSTANCE, Evaluator, expression_degree, flatten_graph, lookup_compress_graphs,
+                         mvlookup_required_degree, shuffle_required_degree)
 from .transcript import point_from_bytes
 
-# the arguments create_proof runs between theta and y, in order; a shuffle or mv-lookup stage would be listed (and run) after "lookups"
-ARGUMENT_STAGES = ("lookups", "permutation")
+# the stages create_proof runs between theta and y, in order (beta and gamma are squeezed after "mvlookup_multiplicities"); each stage
+# enters its name into proof.stages as it starts, and tests/test_proof_arguments.py compares that list, and the order of the stages'
+# commitments in proof.transfers, with this one
+ARGUMENT_STAGES = ("lookup_permuted", "mvlookup_multiplicities", "permutation_products", "lookup_products", "mvlookup_sums", "shuffle_products")
 _ANY = {"advice": ANY_ADVICE, "fixed": ANY_FIXED, "instance": ANY_INSTANCE}
 ZERO = ("const", 0)
 
@@ -60,14 +78,18 @@ ZERO = ("const", 0)
 class ConstraintSystem:
     """plonk/circuit.rs ConstraintSystem as data.  gates: every gate's polynomials in cs.gates order, flattened (None is the zero
     polynomial); lookups: [(input_exprs, table_exprs)]; permutation: [(kind, index)] with kind 'advice' / 'fixed' / 'instance';
-    advice_column_phase[c] / challenge_phase[j]: the phase of advice column c / challenge j (default: everything in phase 0)."""
+    advice_column_phase[c] / challenge_phase[j]: the phase of advice column c / challenge j (default: everything in phase 0).
+    shuffles: [(input_exprs, shuffle_exprs)], m >= 1 expressions a side; mv_lookups: [([input_exprs, ...], table_exprs)], K in [1, 255]
+    input tuples sharing one table, every tuple as long as the table's."""
 
     def __init__(self, num_fixed_columns, num_advice_columns, num_instance_columns, gates, lookups=(), permutation=(),
-                 advice_column_phase=None, challenge_phase=(), minimum_degree=None):
+                 advice_column_phase=None, challenge_phase=(), minimum_degree=None, shuffles=(), mv_lookups=()):
         self.num_fixed_columns, self.num_advice_columns = int(num_fixed_columns), int(num_advice_columns)
         self.num_instance_columns = int(num_instance_columns)
         self.gates = list(gates)
         self.lookups = [(list(i), list(t)) for i, t in lookups]
+        self.shuffles = [(list(i), list(s)) for i, s in shuffles]
+        self.mv_lookups = [([list(i) for i in inputs], list(t)) for inputs, t in mv_lookups]
         self.permutation = [(str(kind), int(i)) for kind, i in permutation]
         self.advice_column_phase = [0] * self.num_advice_columns if advice_column_phase is None else [int(p) for p in advice_column_phase]
         self.challenge_phase = [int(p) for p in challenge_phase]
@@ -78,6 +100,14 @@ class ConstraintSystem:
         for inp, tab in self.lookups:
             if len(inp) != len(tab) or not inp:
                 raise ValueError("a lookup has m >= 1 input expressions and as many table expressions")
+        for inp, shf in self.shuffles:
+            if len(inp) != len(shf) or not inp:
+                raise ValueError("a shuffle has m >= 1 input expressions and as many shuffle expressions")
+        for inputs, tab in self.mv_lookups:
+            if not 1 <= len(inputs) <= 255:
+                raise ValueError("an mv-lookup argument has K in [1, 255] input tuples")
+            if not tab or any(len(inp) != len(tab) for inp in inputs):
+                raise ValueError("an mv-lookup's table has m >= 1 expressions and every input tuple as many")
         counts = {"advice": self.num_advice_columns, "fixed": self.num_fixed_columns, "instance": self.num_instance_columns}
         self.advice_queries, self.fixed_queries, self.instance_queries = [], [], []
         pools = {"advice": self.advice_queries, "fixed": self.fixed_queries, "instance": self.instance_queries}
@@ -113,6 +143,12 @@ class ConstraintSystem:
         for inp, tab in self.lookups:
             for e in inp + tab:
                 walk(e)
+        for inputs, tab in self.mv_lookups:
+            for e in [e for inp in inputs for e in inp] + tab:
+                walk(e)
+        for inp, shf in self.shuffles:
+            for e in inp + shf:
+                walk(e)
         self.num_advice_queries = [sum(1 for c, _ in self.advice_queries if c == j) for j in range(self.num_advice_columns)]  # :1597
 
     def gate_polynomials(self):
@@ -124,6 +160,8 @@ class ConstraintSystem:
         degree = 3                                                                       # permutation.required_degree, permutation.rs:34-67
         degree = max(degree, max([max(4, 2 + max([1] + [expression_degree(e) for e in inp]) + max([1] + [expression_degree(e) for e in tab]))
                                   for inp, tab in self.lookups] or [1]))                 # lookup.rs:37-97
+        degree = max([degree] + [shuffle_required_degree(inp, shf) for inp, shf in self.shuffles])
+        degree = max([degree] + [mvlookup_required_degree(inputs, tab) for inputs, tab in self.mv_lookups])
         degree = max(degree, max([expression_degree(p) for p in self.gates if p is not None] or [0]))
         return max(degree, self.minimum_degree or 1)
 
@@ -216,7 +254,7 @@ class ProvingKey:
         self.d_g, self.d_g_lagrange = up(params.g), up(params.g_lagrange)
         bases_pin_device(self.d_g, n)
         bases_pin_device(self.d_g_lagrange, n)
-        self.ev = Evaluator.new(cs.gate_polynomials(), cs.lookups)
+        self.ev = Evaluator.new(cs.gate_polynomials(), cs.lookups, shuffle_arguments=cs.shuffles, mvlookup_arguments=cs.mv_lookups)
         self.vk = VerifyingKey(cs, k, self.vk_repr, points_to_ints(host["fixed_commitments"]), points_to_ints(host["permutation_commitments"]))
         self._pinned = False
         if pin:
@@ -255,10 +293,11 @@ class ProvingKey:
 
 
 class Proof:
-    """what create_proof returns: the proof bytes and the host/device moves the prover made, (direction, bytes, what)"""
+    """what create_proof returns: the proof bytes, the host/device moves the prover made, (direction, bytes, what), and the stages it
+    ran between theta and y, in order (ARGUMENT_STAGES names them)"""
 
     def __init__(self):
-        self.bytes, self.transfers, self.challenges = b"", [], {}
+        self.bytes, self.transfers, self.challenges, self.stages = b"", [], {}, []
 
     def total(self, direction):
         return sum(nbytes for d, nbytes, _ in self.transfers if d == direction)
@@ -325,9 +364,7 @@ class _Device:
         for inp, tab in lookups:
             gi, gt = lookup_compress_graphs(inp, tab)
             graphs += [flatten_graph(gi), flatten_graph(gt)]
-        comp = [self.zeros(self.n) for _ in graphs]
-        self.note("h2d", 32 * (1 + len(challenges)), "theta and challenges (lookup_compress)")
-        lookup_compress_device(self.k, graphs, theta, comp, fixed, advice, instance, challenges)           # :90-115
+        comp = self.compress(graphs, theta, fixed, advice, instance, challenges, "lookup_compress")        # :90-115
         pa, pt = [self.zeros(self.n) for _ in lookups], [self.zeros(self.n) for _ in lookups]
         self.note("h2d", blinding.nbytes, "lookup blinding rows")
         lookup_permute_device(self.k, comp[0::2], comp[1::2], blinding, self.b, pa, pt)                    # :118-126
@@ -349,6 +386,31 @@ class _Device:
         self.note("h2d", 64 + blinding.nbytes, "beta, gamma and lookup product blinding rows")
         lookup_products_device(self.k, beta, gamma, [p["compressed_input"] for p in permuted], [p["compressed_table"] for p in permuted],
                                [p["permuted_input"] for p in permuted], [p["permuted_table"] for p in permuted], blinding, self.b, z)
+        return z
+
+    def compress(self, graphs, theta, fixed, advice, instance, challenges, what):
+        """the theta folds of one instance's tuples, one column per graph of lookup_compress_graphs"""
+        comp = [self.zeros(self.n) for _ in graphs]
+        self.note("h2d", 32 * (1 + len(challenges)), "theta and challenges (%s)" % what)
+        lookup_compress_device(self.k, graphs, theta, comp, fixed, advice, instance, challenges)
+        return comp
+
+    def mvlookup_multiplicities(self, inputs, tables):
+        m = [self.zeros(self.n) for _ in tables]
+        self.note("d2h", 4 * sum(len(cols) for cols in inputs), "mv-lookup verdict flags (one per input column)")
+        mvlookup_multiplicities_device(self.k, inputs, tables, self.b, m)
+        return m
+
+    def mvlookup_sums(self, beta, inputs, tables, m, blinding):
+        phi = [self.zeros(self.n) for _ in tables]
+        self.note("h2d", 32 + blinding.nbytes, "beta and mv-lookup sum blinding rows")
+        mvlookup_sums_device(self.k, beta, inputs, tables, m, blinding, self.b, phi)
+        return phi
+
+    def shuffle_products(self, gamma, inputs, shuffles, blinding):
+        z = [self.zeros(self.n) for _ in inputs]
+        self.note("h2d", 32 + blinding.nbytes, "gamma and shuffle product blinding rows")
+        shuffle_products_device(self.k, gamma, inputs, shuffles, blinding, self.b, z)
         return z
 
     def random_poly(self, rng):
@@ -461,6 +523,30 @@ class _Host:
         self._cols("d2h", z, "lookup_products: z")
         return z
 
+    def compress(self, graphs, theta, fixed, advice, instance, challenges, what):
+        self._cols("h2d", list(fixed) + list(advice) + list(instance), what + ": columns")
+        comp = lookup_compress(self.k, graphs, theta, fixed, advice, instance, challenges)
+        self._cols("d2h", comp, what + ": compressed columns")
+        return comp
+
+    def mvlookup_multiplicities(self, inputs, tables):
+        self._cols("h2d", [c for cols in inputs for c in cols] + list(tables), "mvlookup_multiplicities: columns")
+        m = mvlookup_multiplicities(self.k, inputs, tables, self.b)
+        self._cols("d2h", m, "mvlookup_multiplicities: m")
+        return m
+
+    def mvlookup_sums(self, beta, inputs, tables, m, blinding):
+        self._cols("h2d", [c for cols in inputs for c in cols] + list(tables) + list(m), "mvlookup_sums: columns")
+        phi = mvlookup_sums(self.k, beta, inputs, tables, m, blinding, self.b)
+        self._cols("d2h", phi, "mvlookup_sums: phi")
+        return phi
+
+    def shuffle_products(self, gamma, inputs, shuffles, blinding):
+        self._cols("h2d", list(inputs) + list(shuffles), "shuffle_products: columns")
+        z = shuffle_products(self.k, gamma, inputs, shuffles, blinding, self.b)
+        self._cols("d2h", z, "shuffle_products: z")
+        return z
+
     def random_poly(self, rng):
         """the same blocks of the stream as the resident path draws in HBM"""
         out = fr_random(rng.seed, self.n, rng.block, rng.stream_id)
@@ -471,6 +557,7 @@ class _Host:
     def evaluate_h(self, case, values, form, t_evaluations):
         moved = [case[key] for key in ("advice_polys", "instance_polys")] + [list(l) for l in case["lookups"]]
         moved.append(case["perm_product_polys" if form == "parts" else "perm_product_cosets"])
+        moved += [list(pair) for pair in case.get("mvlookups", ())] + [list(case.get("shuffles", ()))]
         self._cols("h2d", [c for group in moved for c in group] + [values], "evaluate_h: columns and values")
         if form == "parts":
             values = self.pk.ev.evaluate_h_parts(case, values, t_evaluations=t_evaluations)
@@ -654,6 +741,7 @@ def create_proof(params, pk, instances, witness, transcript, seed, multiopen="sh
     theta_m = fr_from_int(theta)
 
     # ---- lookups: permuted columns (:406-431)
+    proof.stages.append("lookup_permuted")
     permuted = []
     for i in range(N):
         blinding = []
@@ -666,11 +754,36 @@ def create_proof(params, pk, instances, witness, transcript, seed, multiopen="sh
             transcript.write_point(c)                                                                      # lookup/prover.rs:143, :146
         permuted.append(out)
 
+    # ---- mv-lookups: the compressed columns (kept until the grand sums) and the multiplicities m, committed before beta exists
+    proof.stages.append("mvlookup_multiplicities")
+    mv_graphs, mv_inputs = [], [len(inputs) for inputs, _ in cs.mv_lookups]
+    for inputs, tab in cs.mv_lookups:
+        mv_graphs += [flatten_graph(lookup_compress_graphs(inp, tab)[0]) for inp in inputs]
+        mv_graphs.append(flatten_graph(lookup_compress_graphs(inputs[0], tab)[1]))
+    mv_columns, mv_m = [], []
+    for i in range(N):
+        for _ in cs.mv_lookups:
+            rng.draw(1)                                                                                    # draw 2b (blinds; KZG ignores them)
+        f, t, m = [], [], []
+        if cs.mv_lookups:
+            comp = be.compress(mv_graphs, theta_m, key["fixed_values"], advice[i], instance_values[i], ch_mont, "mv-lookup compression")
+            at = 0
+            for kj in mv_inputs:
+                f.append(comp[at:at + kj])
+                t.append(comp[at + kj])
+                at += kj + 1
+            m = be.mvlookup_multiplicities(f, t)
+        for c in points_to_ints(be.commit(m, True, "mv-lookup multiplicity commitments")):
+            transcript.write_point(c)
+        mv_columns.append((f, t))
+        mv_m.append(m)
+
     beta = transcript.squeeze_challenge()                                                                  # :434
     gamma = transcript.squeeze_challenge()                                                                 # :437
     beta_m, gamma_m = fr_from_int(beta), fr_from_int(gamma)
 
     # ---- permutation products (:440-457, permutation/prover.rs:45-191)
+    proof.stages.append("permutation_products")
     chunk_len, n_sets = cs.chunk_len(), cs.num_permutation_sets()
     perm_polys = []
     for i in range(N):
@@ -687,6 +800,7 @@ def create_proof(params, pk, instances, witness, transcript, seed, multiopen="sh
         perm_polys.append(be.lagrange_to_coeff(z))                                                         # :172
 
     # ---- lookup products (:459-468, lookup/prover.rs:167-305)
+    proof.stages.append("lookup_products")
     lookup_polys = []
     for i in range(N):
         blinding = []
@@ -697,6 +811,42 @@ def create_proof(params, pk, instances, witness, transcript, seed, multiopen="sh
         for c in points_to_ints(be.commit(z, True, "lookup product commitments")):                         # :291-295
             transcript.write_point(c)
         lookup_polys.append(be.lagrange_to_coeff(z))                                                       # :292
+
+    # ---- mv-lookup grand sums over the kept compressed columns and m
+    proof.stages.append("mvlookup_sums")
+    mv_polys = []
+    for i in range(N):
+        blinding = []
+        for _ in cs.mv_lookups:
+            blinding.append(rng.draw(b))                                                                   # draw 4b
+            rng.draw(1)
+        (f, t), m = mv_columns[i], mv_m[i]
+        phi = be.mvlookup_sums(beta_m, f, t, m, np.concatenate(blinding)) if cs.mv_lookups else []
+        for c in points_to_ints(be.commit(phi, True, "mv-lookup sum commitments")):
+            transcript.write_point(c)
+        polys = be.lagrange_to_coeff(list(phi) + list(m))
+        mv_polys.append([(polys[j], polys[len(phi) + j]) for j in range(len(phi))])
+        mv_columns[i] = mv_m[i] = None                                                                     # the compressed columns are done
+
+    # ---- shuffle products (upstream shuffle::Argument::commit_product)
+    proof.stages.append("shuffle_products")
+    shuffle_graphs = []
+    for inp, shf in cs.shuffles:
+        gi, gs = lookup_compress_graphs(inp, shf)
+        shuffle_graphs += [flatten_graph(gi), flatten_graph(gs)]
+    shuffle_polys = []
+    for i in range(N):
+        blinding = []
+        for _ in cs.shuffles:
+            blinding.append(rng.draw(b))                                                                   # draw 4c
+            rng.draw(1)
+        z = []
+        if cs.shuffles:
+            comp = be.compress(shuffle_graphs, theta_m, key["fixed_values"], advice[i], instance_values[i], ch_mont, "shuffle compression")
+            z = be.shuffle_products(gamma_m, comp[0::2], comp[1::2], np.concatenate(blinding))
+        for c in points_to_ints(be.commit(z, True, "shuffle product commitments")):
+            transcript.write_point(c)
+        shuffle_polys.append(be.lagrange_to_coeff(z))
 
     # ---- the vanishing argument's random polynomial (:471, vanishing/prover.rs:37-65)
     random_poly = be.random_poly(rng)
@@ -723,6 +873,10 @@ def create_proof(params, pk, instances, witness, transcript, seed, multiopen="sh
         case = dict(common, advice_polys=advice_polys[i], instance_polys=instance_polys[i],
                     lookups=[(lookup_polys[i][j], permuted[i][j]["permuted_input_poly"], permuted[i][j]["permuted_table_poly"])
                              for j in range(len(cs.lookups))])
+        if cs.mv_lookups:
+            case["mvlookups"] = mv_polys[i]
+        if cs.shuffles:
+            case["shuffles"] = shuffle_polys[i]
         if form == "parts":
             case["perm_product_polys"] = perm_polys[i]
         else:
@@ -778,6 +932,24 @@ def create_proof(params, pk, instances, witness, transcript, seed, multiopen="sh
         for e in evs:
             transcript.write_scalar(e)
         lookup_evals.append(evs)
+    mv_evals = []
+    for i in range(N):                                                                                     # phi(x), phi(wx), m(x) per argument
+        polys, qp, pts = [], [], []
+        for j, (phi, m) in enumerate(mv_polys[i]):
+            polys += [phi, m]
+            qp += [2 * j, 2 * j, 2 * j + 1]
+            pts += [x, x_next, x]
+        evs = be.evaluate(polys, qp, pts, "mv-lookup evaluations")
+        for e in evs:
+            transcript.write_scalar(e)
+        mv_evals.append(evs)
+    shuffle_evals = []
+    for i in range(N):                                                                                     # z(x), z(wx) per shuffle
+        qp = [j for j in range(len(cs.shuffles)) for _ in range(2)]
+        evs = be.evaluate(shuffle_polys[i], qp, [x, x_next] * len(cs.shuffles), "shuffle evaluations")
+        for e in evs:
+            transcript.write_scalar(e)
+        shuffle_evals.append(evs)
 
     # ---- the opening queries (:599-645): (polynomial id, point, evaluation) with ids into `polys`
     polys, queries = [], []
@@ -808,6 +980,13 @@ def create_proof(params, pk, instances, witness, transcript, seed, multiopen="sh
             z_id, a_id, s_id = (poly_id(p) for p in (lookup_polys[i][j], permuted[i][j]["permuted_input_poly"], permuted[i][j]["permuted_table_poly"]))
             z_x, z_next, a_x, a_inv, s_x = lookup_evals[i][5 * j:5 * j + 5]
             queries += [(z_id, x, z_x), (a_id, x, a_x), (s_id, x, s_x), (a_id, x_inv, a_inv), (z_id, x_next, z_next)]
+        for j, (phi, m) in enumerate(mv_polys[i]):
+            phi_id, m_id = poly_id(phi), poly_id(m)
+            phi_x, phi_next, m_x = mv_evals[i][3 * j:3 * j + 3]
+            queries += [(phi_id, x, phi_x), (phi_id, x_next, phi_next), (m_id, x, m_x)]
+        for j, z in enumerate(shuffle_polys[i]):
+            z_id = poly_id(z)
+            queries += [(z_id, x, shuffle_evals[i][2 * j]), (z_id, x_next, shuffle_evals[i][2 * j + 1])]
     for q, (c, r) in enumerate(cs.fixed_queries):                                                          # :632-642
         queries.append((fixed_ids[c], rotate_omega(dom, x, r), fixed_evals[q]))
     for j in range(len(cs.permutation)):                                                                   # :643, permutation/prover.rs:210-219

@@ -6,7 +6,11 @@ Scalars are integers mod r, points are (x, y) integer pairs or None (transcript.
 below.  Nothing here touches the GPU or grows with 2^k: the cost is a few dozen scalar multiplications, and one field inversion per
 instance value.  verify_proof returns the two G1 points (left, right) of the reference's DualMSM (poly/kzg/msm.rs); the proof is valid
 iff e(left, s_g2) = e(right, g2), which the caller closes with a pairing library (pairings are out of scope here).  Both KZG verifiers
-set QUERY_INSTANCE = false: the instance values are absorbed as scalars and their evaluations computed from l_i(x) (:84-90, :176-214)."""
+set QUERY_INSTANCE = false: the instance values are absorbed as scalars and their evaluations computed from l_i(x) (:84-90, :176-214).
+
+The shuffle and mv-lookup (logUp) arguments are later than the reference; their commitments, evaluations, expressions and queries are
+read and built in the order prover.py's docstring fixes (mv-lookups before shuffles, both after the halo2 lookups), and their share of
+h(x) is mvlookup_expressions / shuffle_expressions below: include/halo2hip.h's fold at one point instead of one coset row."""
 from .prover import ZERO, construct_intermediate_sets_gwc, construct_intermediate_sets_shplonk
 from .transcript import FQ_MODULUS, FR_MODULUS, TranscriptError
 
@@ -144,6 +148,32 @@ def evaluate_expression(e, fixed_evals, advice_evals, instance_evals, challenges
     if tag == "scaled":
         return ev(e[1]) * e[2] % R
     raise ValueError(tag)
+
+
+def compress_evals(values, theta):
+    """the theta fold of a tuple's values: acc = acc theta + e, from zero (lookup/verifier.rs:116-134)"""
+    acc = 0
+    for v in values:
+        acc = (acc * theta + v) % R
+    return acc
+
+
+def mvlookup_expressions(l_0, l_last, l_active, beta, inputs, table, phi_x, phi_next, m_x):
+    """the three expressions of one mv-lookup argument, in fold order.  inputs: the theta folds F_c of its K input tuples, table: the
+    fold T of its table; with f_c = F_c + beta, tau = T + beta, P = prod f_c and Q = sum_c prod_{l != c} f_l:
+    l_0 phi(x), l_last phi(x), l_active (tau P (phi(wx) - phi(x)) - tau Q + m(x) P)"""
+    tau, P, Qs = (table + beta) % R, 1, 0
+    for F in inputs:                                                                     # Q <- Q f + P; P <- P f
+        f = (F + beta) % R
+        Qs = (Qs * f + P) % R
+        P = P * f % R
+    return [l_0 * phi_x % R, l_last * phi_x % R, l_active * (tau * P % R * (phi_next - phi_x) - tau * Qs + m_x * P) % R]
+
+
+def shuffle_expressions(l_0, l_last, l_active, gamma, a, s, z_x, z_next):
+    """the three expressions of one shuffle, in fold order.  a / s: the theta folds A, S of its input and shuffle tuples:
+    l_0 (1 - z(x)), l_last (z(x)^2 - z(x)), l_active (z(wx) (S + gamma) - z(x) (A + gamma))"""
+    return [l_0 * (1 - z_x) % R, l_last * (z_x * z_x - z_x) % R, l_active * (z_next * (s + gamma) - z_x * (a + gamma)) % R]
 
 
 def _g0(params_vk):
@@ -291,12 +321,15 @@ def verify_proof(params_vk, vk, instances, transcript, multiopen="shplonk"):
 
     theta = transcript.squeeze_challenge()                                               # :123
     lookups_permuted = [[(transcript.read_point(), transcript.read_point()) for _ in cs.lookups] for _ in range(num_proofs)]   # :125-134
+    mvlookups_m = [[transcript.read_point() for _ in cs.mv_lookups] for _ in range(num_proofs)]
     beta = transcript.squeeze_challenge()                                                # :137
     gamma = transcript.squeeze_challenge()                                               # :140
     chunk_len = vk.cs_degree - 2
     chunks = [cs.permutation[i:i + chunk_len] for i in range(0, len(cs.permutation), chunk_len)]
     permutations_committed = [[transcript.read_point() for _ in chunks] for _ in range(num_proofs)]                            # :142-147
     lookups_product = [[transcript.read_point() for _ in cs.lookups] for _ in range(num_proofs)]                               # :149-158
+    mvlookups_phi = [[transcript.read_point() for _ in cs.mv_lookups] for _ in range(num_proofs)]
+    shuffles_product = [[transcript.read_point() for _ in cs.shuffles] for _ in range(num_proofs)]
     random_poly_commitment = transcript.read_point()                                     # :160
     y = transcript.squeeze_challenge()                                                   # :163
     h_commitments = [transcript.read_point() for _ in range(vk.cs_degree - 1)]           # :165, get_quotient_poly_degree
@@ -328,6 +361,8 @@ def verify_proof(params_vk, vk, instances, transcript, multiopen="shplonk"):
             sets.append((ev, nxt, transcript.read_scalar() if t < len(chunks) - 1 else None))
         permutations_evaluated.append(sets)
     lookups_evaluated = [[tuple(transcript.read_scalar() for _ in range(5)) for _ in cs.lookups] for _ in range(num_proofs)]   # :232-240
+    mvlookups_evaluated = [[tuple(transcript.read_scalar() for _ in range(3)) for _ in cs.mv_lookups] for _ in range(num_proofs)]
+    shuffles_evaluated = [[tuple(transcript.read_scalar() for _ in range(2)) for _ in cs.shuffles] for _ in range(num_proofs)]
 
     # ---- the expected h(x) (:244-324)
     l_evals = dom.l_i_range(x, xn, range(-(b + 1), 1))                                   # :249-252
@@ -369,6 +404,12 @@ def verify_proof(params_vk, vk, instances, transcript, multiopen="shplonk"):
             expressions.append((left - right) * active_rows % R)
             expressions.append(l_0 * (a_x - s_x) % R)
             expressions.append((a_x - s_x) * (a_x - a_inv) % R * active_rows % R)
+        for (inputs, tab), (phi_x, phi_next, m_x) in zip(cs.mv_lookups, mvlookups_evaluated[i]):
+            folds = [compress_evals([ev(e) for e in exprs], theta) for exprs in inputs + [tab]]
+            expressions += mvlookup_expressions(l_0, l_last, active_rows, beta, folds[:-1], folds[-1], phi_x, phi_next, m_x)
+        for (inp, shf), (z_x, z_next) in zip(cs.shuffles, shuffles_evaluated[i]):
+            a, s = (compress_evals([ev(e) for e in exprs], theta) for exprs in (inp, shf))
+            expressions += shuffle_expressions(l_0, l_last, active_rows, gamma, a, s, z_x, z_next)
     expected_h_eval = 0                                                                  # vanishing/verifier.rs:97-98
     for v in expressions:
         expected_h_eval = (expected_h_eval * y + v) % R
@@ -404,6 +445,13 @@ def verify_proof(params_vk, vk, instances, transcript, multiopen="shplonk"):
             z_id, a_id, s_id = cid(lookups_product[i][j]), cid(lookups_permuted[i][j][0]), cid(lookups_permuted[i][j][1])
             z_x, z_next, a_x, a_inv, s_x = lookups_evaluated[i][j]
             queries += [(z_id, x, z_x), (a_id, x, a_x), (s_id, x, s_x), (a_id, x_inv, a_inv), (z_id, x_next, z_next)]
+        for j in range(len(cs.mv_lookups)):
+            phi_id, m_id = cid(mvlookups_phi[i][j]), cid(mvlookups_m[i][j])
+            phi_x, phi_next, m_x = mvlookups_evaluated[i][j]
+            queries += [(phi_id, x, phi_x), (phi_id, x_next, phi_next), (m_id, x, m_x)]
+        for j in range(len(cs.shuffles)):
+            z_id = cid(shuffles_product[i][j])
+            queries += [(z_id, x, shuffles_evaluated[i][j][0]), (z_id, x_next, shuffles_evaluated[i][j][1])]
     for q, (c, r) in enumerate(cs.fixed_queries):                                        # :374-386
         queries.append((fixed_ids[c], dom.rotate_omega(x, r), fixed_evals[q]))
     for j in range(len(vk.permutation_commitments)):                                     # :387, permutation/verifier.rs:241-251

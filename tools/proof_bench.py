@@ -7,7 +7,11 @@ other selector zero, a drawn from the table, every odd row's a copied from the e
 Reports the median of 5 of create_proof with resident columns and from host columns, parts and full form, both multiopen schemes for the
 resident parts form; the engine's per-stage times of one profiled proof (profile_get); and what the prover moved (proof.transfers).
 Every proof is verified once (Python integers; the pairing equation closed with the setup secret).
-  python tools/proof_bench.py [--k K] [--reps N]     (run on the GPU box)"""
+  python tools/proof_bench.py [--k K] [--reps N]     (run on the GPU box)
+
+--arguments measures the later arguments instead: the same circuit with an mv-lookup (logUp) [a] in [sl] in place of its halo2 lookup
+and one shuffle e <-> d (d holds e's usable rows in reverse), resident and host columns, parts form, SHPLONK, beside the lookup
+circuit's same two legs in the same process (the comparison row), each with its stage times and transfer sums."""
 import json
 import os
 import random
@@ -23,8 +27,10 @@ from __graft_entry__ import load_pkg  # noqa: E402
 R = 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001
 Q = 0x30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47
 SECRET = 0x5EC2E7
-STAGES = ("msm_total", "ntt_batch", "lookup_compress", "lookup_permute", "lookup_products", "evalh_cosets", "evalh_part_scale", "evalh_part_io",
-          "evalh_gates", "evalh_gates_gen", "evalh_perm", "evalh_lookups", "evalh_lookup_gen", "eval_polynomials", "opening_eval", "opening_combine")
+STAGES = ("msm_total", "ntt_batch", "lookup_compress", "lookup_permute", "products", "evalh_cosets", "evalh_part_scale", "evalh_part_io",
+          "evalh_gates", "evalh_gates_gen", "evalh_perm", "evalh_lookups", "evalh_lookup_gen", "eval_polynomials", "opening_eval", "opening_combine",
+          "mvlookup_multiplicities", "mvlookup_sums", "evalh_mvlookups", "evalh_mvlookup_gen", "evalh_shuffles",
+          "evalh_shuffle_gen")  # "products": the one timer of the permutation, lookup and shuffle grand products
 
 
 def to_mont(vals):
@@ -57,17 +63,20 @@ def g1_mul(p, k):
     return acc
 
 
-def circuit(prover):
+def circuit(prover, arguments=False):
     A = lambda c, r=0: ("advice", c, r)  # noqa: E731
     F = lambda c, r=0: ("fixed", c, r)  # noqa: E731
     e_, a_, b_, c_, d_ = range(5)
     sf, sm, sa, sb, sc, sl = range(6)
     gate = ("sum", ("sum", ("sum", ("sum", ("prod", A(a_), F(sa)), ("prod", A(b_), F(sb))), ("prod", ("prod", A(a_), A(b_)), F(sm))),
                     ("neg", ("prod", A(c_), F(sc)))), ("prod", F(sf), ("prod", A(d_, 1), A(e_, -1))))
-    return prover.ConstraintSystem(6, 5, 0, [gate], [([A(a_)], [F(sl)])], [("advice", a_), ("advice", b_), ("advice", c_)])
+    permutation = [("advice", a_), ("advice", b_), ("advice", c_)]
+    if arguments:
+        return prover.ConstraintSystem(6, 5, 0, [gate], [], permutation, mv_lookups=[([[A(a_)]], [F(sl)])], shuffles=[([A(e_)], [A(d_)])])
+    return prover.ConstraintSystem(6, 5, 0, [gate], [([A(a_)], [F(sl)])], permutation)
 
 
-def assignment(k, b, seed=17):
+def assignment(k, b, seed=17, arguments=False):
     rng = random.Random(seed)
     n, u = 1 << k, (1 << k) - b - 1
     rnd = lambda: rng.randrange(R)  # noqa: E731
@@ -83,36 +92,31 @@ def assignment(k, b, seed=17):
     zero = [0] * n
     fixed = [zero, on, zero, zero, on, table]  # sf, sm, sa, sb, sc, sl
     advice = [[rnd() for _ in range(n)], a, bb, c, [rnd() for _ in range(n)]]  # e, a, b, c, d
+    if arguments:  # d: a shuffle of e's usable rows (sf = 0: the gate reads neither)
+        advice[4][:u] = advice[0][:u][::-1]
     return [to_mont(col) for col in fixed], [to_mont(col) for col in advice], copies
 
 
-def main():
-    import importlib
+ALL_LEGS = ((True, "parts", "shplonk"), (True, "full", "shplonk"), (True, "parts", "gwc"), (False, "parts", "shplonk"), (False, "full", "shplonk"))
+ARGUMENT_LEGS = ((True, "parts", "shplonk"), (False, "parts", "shplonk"))
+
+
+def measure(mods, k, reps, arguments, legs):
+    """one circuit: its key, the median of `reps` proofs per leg (each leg's proof verified, the legs' bytes compared), and the stage
+    times of one profiled proof with resident and with host columns (parts form, SHPLONK)"""
     import torch
-    args = sys.argv[1:]
-    k = int(args[args.index("--k") + 1]) if "--k" in args else 17
-    reps = int(args[args.index("--reps") + 1]) if "--reps" in args else 5
-    h2 = load_pkg()
-    h2.init()
-    prover = importlib.import_module("halo2_pse_amd.prover")
-    verifier = importlib.import_module("halo2_pse_amd.verifier")
-    tr = importlib.import_module("halo2_pse_amd.transcript")
-    cs = circuit(prover)
+    h2, prover, verifier, tr = mods
+    cs = circuit(prover, arguments)
     t0 = time.perf_counter()
-    fixed, advice, copies = assignment(k, cs.blinding_factors())
+    fixed, advice, copies = assignment(k, cs.blinding_factors(), arguments=arguments)
     params = h2.ParamsKZG.setup(k, SECRET)
     pk = prover.ProvingKey.build(params, cs, fixed, copies, 0x17)
     setup_s = time.perf_counter() - t0
     d_advice = [torch.from_numpy(a.view(np.int64)).cuda() for a in advice]
 
-    def witness_for(resident):
-        def witness(i, phase, challenges):  # fresh columns: the prover consumes them (the copies are outside the clock)
-            return [c.clone() for c in d_advice] if resident else [c.copy() for c in advice]
-        return witness
-
     def prove(resident, form, multiopen):
-        w = witness_for(resident)
-        cols = w(0, 0, [])
+        # fresh columns: the prover consumes them (the copies are outside the clock)
+        cols = [c.clone() for c in d_advice] if resident else [c.copy() for c in advice]
         torch.cuda.synchronize()
         t = time.perf_counter()
         proof = prover.create_proof(params, pk, [[]], lambda i, phase, ch: cols, tr.Blake2bWrite(), b"\x11" * 32, multiopen=multiopen, form=form,
@@ -120,11 +124,9 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t) * 1e3, proof
 
-    out = {"k": k, "circuit": "circuit-layout.rs shape: 5 advice, 6 fixed, 1 gate, 1 lookup, 3 permutation columns (2 sets)", "reps": reps,
-           "stat": "median, host clock around create_proof, stream synchronised", "setup_s": round(setup_s, 2), "legs": {}}
+    out = {"degree": cs.degree(), "extended_k": pk.domain.extended_k, "setup_s": round(setup_s, 2), "legs": {}}
     reference_bytes = {}
-    for resident, form, multiopen in ((True, "parts", "shplonk"), (True, "full", "shplonk"), (True, "parts", "gwc"), (False, "parts", "shplonk"),
-                                      (False, "full", "shplonk")):
+    for resident, form, multiopen in legs:
         prove(resident, form, multiopen)  # warm-up: kernel generation, window tables, arenas
         ts, proof = [], None
         for _ in range(reps):
@@ -152,6 +154,24 @@ def main():
         out["stages_%s_parts_shplonk" % ("resident" if resident else "host")] = stages
     h2.profile_enable(False)
     pk.close()
+    return out
+
+
+def main():
+    import importlib
+    args = sys.argv[1:]
+    k = int(args[args.index("--k") + 1]) if "--k" in args else 17
+    reps = int(args[args.index("--reps") + 1]) if "--reps" in args else 5
+    h2 = load_pkg()
+    h2.init()
+    mods = (h2,) + tuple(importlib.import_module("halo2_pse_amd." + m) for m in ("prover", "verifier", "transcript"))
+    out = {"k": k, "reps": reps, "stat": "median, host clock around create_proof, stream synchronised"}
+    if "--arguments" in args:
+        out["circuits"] = {name: measure(mods, k, reps, arguments, ARGUMENT_LEGS) for name, arguments in (("lookup", False), ("mvlookup_shuffle", True))}
+    else:
+        res = measure(mods, k, reps, False, ALL_LEGS)
+        out["circuit"] = "circuit-layout.rs shape: 5 advice, 6 fixed, 1 gate, 1 lookup, 3 permutation columns (2 sets)"
+        out.update({key: val for key, val in res.items() if key not in ("degree", "extended_k")})
     print(json.dumps(out))
 
 
