@@ -7,8 +7,8 @@ reference (halo2_proofs::arithmetic::{best_multiexp, best_fft}, poly::Evaluation
 poly::kzg::ParamsKZG).  There is no CPU fallback here: if the library or the GPU is
 missing, calls raise.
 
-Every entry point's prototype is stated once, in _abi.py (generated from the headers by tools/gen_ctypes_abi.py) and bound by
-lib(): call sites pass plain Python ints and bools for the by-value parameters, and ctypes refuses a wrong argument count.
+Every entry point's prototype is stated once, in _abi.py and _abi_ipa.py (generated from the headers by tools/gen_ctypes_abi.py) and
+bound by lib(): call sites pass plain Python ints and bools for the by-value parameters, and ctypes refuses a wrong argument count.
 
 Arrays: numpy uint64 -- Fr elements (n,4), G1Affine (n,8), G1 Jacobian (12,): 4 x u64 LE limbs,
 Montgomery form (halo2curves' in-memory / RawBytes layout).
@@ -20,6 +20,7 @@ import subprocess
 import numpy as np
 
 from ._abi import PROTOTYPES
+from ._abi_ipa import PROTOTYPES as PROTOTYPES_IPA
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HALO2_HIP_LIB") or os.path.join(_HERE, "libhalo2hip.so")  # HALO2_HIP_LIB: another build of the library (A/B measurements)
@@ -58,7 +59,8 @@ def lib():
         # declared width and refuses a wrong argument count.  Bare argtypes would let a cdecl function take surplus arguments; naming
         # each parameter an input (paramflags) makes the count exact.  Another build (HALO2_HIP_LIB) may lack a name; tests/test_abi.py
         # holds the in-tree one to all of them.
-        for name, (restype, argtypes) in PROTOTYPES.items():
+        # The inner-product argument's entry points (include/halo2hip_ipa.h) have a table of their own, _abi_ipa.py, applied after the first.
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_IPA.items()):
             try:
                 fn = ctypes.CFUNCTYPE(restype, *argtypes)((name, L), ((1,),) * len(argtypes))
             except AttributeError:

@@ -909,6 +909,8 @@ static void release_ctx(Ctx* c) {
     c->copies_ws.release();
     c->copies_flag.release();
     c->serde_ws.release();
+    c->ipa_ws.release();
+    c->ipa_vals.release();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     c->stream = nullptr;
     for (auto e : c->aux_events) (void)hipEventDestroy(e);

@@ -220,6 +220,8 @@ struct Ctx {
     DevBuf copies_ws;              // copies.hip: parents, sort keys, flag and pointer blob
     HostBuf copies_flag;           // copies.hip: the invalid-copy flag of a device-form mapping call read back at the end of the call
     DevBuf serde_ws;               // serde.hip: failure mask, tile counts and the two result words
+    DevBuf ipa_ws;                 // ipa.hip: the byte table, the blocks' partial inner products and the two values
+    HostBuf ipa_vals;              // ipa.hip: the two inner products read back at the end of a call
     HostBuf host_ws;               // pinned host memory for the window sums coming back
     HostBuf host_planes;           // ... and for the bit-plane sums of a run whose tail the host finishes (msm.hip msm_planes_finish)
     HostBuf pin_flag;              // one word the device-key fingerprint check writes its verdict to
@@ -379,6 +381,7 @@ struct Tuning {
     uint32_t lookup_sort_block = 0;  // forced in-LDS sort block of the lookup permutation (0 = LK_TILE)
     uint32_t open_rows = 0, open_threads = 0;  // opening: forced tile shape, rows per thread and threads per tile (0 = by size)
     size_t keygen_group_bytes = (size_t)1 << 30;  // HBM one group of columns of a host-pointer keygen call may take (two groups are alive)
+    size_t ipa_quad_max_half = (size_t)1 << 13;  // h2hip_ipa_set_collapse_quad: a collapse of at most this many points per half takes one quad of lanes per point
     size_t random_min_n = 0;  // element count from which the host forms of the randomness go to the device (0 = HALO2_HIP_RANDOM_MIN_N or its default, random.hip)
 };
 const Tuning& tune();

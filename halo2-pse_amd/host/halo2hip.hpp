@@ -1380,3 +1380,5 @@ inline ShplonkQuotients shplonk(const std::vector<RotationSet>& sets, const Fr& 
 }  // namespace kzg
 }  // namespace poly
 }  // namespace halo2_proofs
+
+#include "ipa.hpp"  // transcript::Blake2b{Write,Read} and poly::ipa, the inner-product-argument commitment scheme

@@ -1,0 +1,663 @@
+// ipa.hpp -- the C++ mirror of the reference's inner-product-argument commitment scheme at C = bn256::G1Affine, over the C ABI
+// (include/halo2hip_ipa.h and the device MSM of include/halo2hip.h).  Included by halo2hip.hpp; same error behaviour.
+//
+//   halo2_proofs::transcript::{Blake2bWrite, Blake2bRead}   halo2_proofs/src/transcript.rs (Challenge255 over Blake2b, "Halo2-Transcript")
+//   poly::ipa::ParamsIPA                                     poly/ipa/commitment.rs:29-232
+//   poly::ipa::{create_proof, verify_proof, compute_b}       poly/ipa/commitment/{prover,verifier}.rs
+//   poly::ipa::MSMIPA                                        poly/ipa/msm.rs
+//   poly::ipa::{GuardIPA, SingleStrategy}                    poly/ipa/strategy.rs
+//   poly::ipa::{construct_intermediate_sets, ProverIPA, VerifierIPA}   poly/ipa/multiopen.rs, multiopen/{prover,verifier}.rs
+//
+// Polynomials are host vectors, as everywhere in this mirror; an opening uploads p', b and G' once and keeps them in device memory
+// across its k rounds (the round calls exist only in _device form), so per round two Jacobian sums, two values and a challenge move.
+// The handful of group operations per round, and the verifier's terms outside g, run on the host over ec.h.  Draw order and the
+// generator derivation of ParamsIPA::new_ are DESIGN.md section 2's; halo2-pse_amd/ipa.py is the same composition in Python, and
+// tests/test_ipa_mirror.py compares the two byte for byte.
+#pragma once
+#include <functional>
+#include <map>
+
+#include "../../include/halo2hip_ipa.h"
+#include "halo2hip.hpp"
+
+namespace halo2_proofs {
+
+// ---- BLAKE2b (RFC 7693), digest 64 bytes, no key, a 16-byte personalisation; copyable, so a digest can be taken mid-stream --------
+class Blake2b {
+   public:
+    explicit Blake2b(const char personal[16]) {
+        static const uint64_t IV[8] = {0x6a09e667f3bcc908ull, 0xbb67ae8584caa73bull, 0x3c6ef372fe94f82bull, 0xa54ff53a5f1d36f1ull,
+                                       0x510e527fade682d1ull, 0x9b05688c2b3e6c1full, 0x1f83d9abfb41bd6bull, 0x5be0cd19137e2179ull};
+        for (int i = 0; i < 8; i++) h_[i] = IV[i];
+        h_[0] ^= 0x01010000ull ^ 64ull;  // digest length 64, key length 0, fanout 1, depth 1
+        uint64_t p[2];
+        std::memcpy(p, personal, 16);  // parameter block bytes 48 .. 63
+        h_[6] ^= p[0];
+        h_[7] ^= p[1];
+    }
+    void update(const uint8_t* in, size_t len) {
+        while (len) {
+            if (buflen_ == 128) {  // a full block is compressed only when more input follows: the last one is final()'s
+                t_ += 128;
+                compress(false);
+                buflen_ = 0;
+            }
+            const size_t take = len < 128 - buflen_ ? len : 128 - buflen_;
+            std::memcpy(buf_ + buflen_, in, take);
+            buflen_ += take, in += take, len -= take;
+        }
+    }
+    std::array<uint8_t, 64> digest() const {  // of what has been absorbed so far; the state is left as it is
+        Blake2b c = *this;
+        c.t_ += c.buflen_;
+        std::memset(c.buf_ + c.buflen_, 0, 128 - c.buflen_);
+        c.compress(true);
+        std::array<uint8_t, 64> out;
+        std::memcpy(out.data(), c.h_, 64);
+        return out;
+    }
+
+   private:
+    uint64_t h_[8], t_ = 0;
+    uint8_t buf_[128] = {};
+    size_t buflen_ = 0;
+    static uint64_t rotr(uint64_t x, int n) { return x >> n | x << (64 - n); }
+    void compress(bool last) {
+        static const uint8_t SIGMA[12][16] = {
+            {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}, {14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3},
+            {11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4}, {7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8},
+            {9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13}, {2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9},
+            {12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11}, {13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10},
+            {6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5}, {10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0},
+            {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}, {14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3}};
+        static const uint64_t IV[8] = {0x6a09e667f3bcc908ull, 0xbb67ae8584caa73bull, 0x3c6ef372fe94f82bull, 0xa54ff53a5f1d36f1ull,
+                                       0x510e527fade682d1ull, 0x9b05688c2b3e6c1full, 0x1f83d9abfb41bd6bull, 0x5be0cd19137e2179ull};
+        uint64_t m[16], v[16];
+        std::memcpy(m, buf_, 128);
+        for (int i = 0; i < 8; i++) v[i] = h_[i], v[8 + i] = IV[i];
+        v[12] ^= t_;  // the high counter word stays zero: transcripts are far below 2^64 bytes
+        if (last) v[14] = ~v[14];
+        auto G = [&](int a, int b, int c, int d, uint64_t x, uint64_t y) {
+            v[a] = v[a] + v[b] + x, v[d] = rotr(v[d] ^ v[a], 32);
+            v[c] = v[c] + v[d], v[b] = rotr(v[b] ^ v[c], 24);
+            v[a] = v[a] + v[b] + y, v[d] = rotr(v[d] ^ v[a], 16);
+            v[c] = v[c] + v[d], v[b] = rotr(v[b] ^ v[c], 63);
+        };
+        for (int r = 0; r < 12; r++) {
+            const uint8_t* s = SIGMA[r];
+            G(0, 4, 8, 12, m[s[0]], m[s[1]]), G(1, 5, 9, 13, m[s[2]], m[s[3]]), G(2, 6, 10, 14, m[s[4]], m[s[5]]), G(3, 7, 11, 15, m[s[6]], m[s[7]]);
+            G(0, 5, 10, 15, m[s[8]], m[s[9]]), G(1, 6, 11, 12, m[s[10]], m[s[11]]), G(2, 7, 8, 13, m[s[12]], m[s[13]]), G(3, 4, 9, 14, m[s[14]], m[s[15]]);
+        }
+        for (int i = 0; i < 8; i++) h_[i] ^= v[i] ^ v[8 + i];
+    }
+};
+
+// ---- G1 on the host (ec.h), for the few group operations outside the engine ---------------------------------------------------------
+namespace g1 {
+inline h2::Affine in(const G1Affine& p) {
+    h2::Affine a;
+    std::memcpy(&a, &p, 64);
+    return a;
+}
+inline G1Affine out(const h2::XYZZ& p) {
+    const h2::Affine a = h2::xyzz_to_affine(p);
+    G1Affine o;
+    std::memcpy(&o, &a, 64);
+    return o;
+}
+inline bool is_identity(const G1Affine& p) { return h2::affine_is_identity(in(p)); }
+inline G1Affine neg(const G1Affine& p) {
+    const h2::Affine a = h2::affine_neg(in(p));
+    G1Affine o;
+    std::memcpy(&o, &a, 64);
+    return o;
+}
+struct Term {
+    Fr scalar;
+    G1Affine point;
+};
+// sum of [s] P: one doubling chain shared by all terms
+inline G1Affine sum(const std::vector<Term>& terms) {
+    std::vector<h2::Fe> k;
+    std::vector<h2::Affine> p;
+    for (const Term& t : terms)
+        if (!is_identity(t.point) && !(t.scalar == Fr::zero())) k.push_back(h2::fe_to_canonical<h2::FrP>(t.scalar.fe())), p.push_back(in(t.point));
+    h2::XYZZ acc = h2::xyzz_identity();
+    for (int bit = 253; bit >= 0; bit--) {
+        acc = h2::xyzz_double(acc);
+        for (size_t i = 0; i < k.size(); i++)
+            if ((k[i].l[bit >> 5] >> (bit & 31)) & 1) h2::xyzz_add_mixed(acc, p[i]);
+    }
+    return out(acc);
+}
+}  // namespace g1
+
+// ---- transcript.rs: Blake2bWrite / Blake2bRead with Challenge255 -----------------------------------------------------------------------
+namespace transcript {
+struct Error : std::runtime_error {  // the reference's io::Error
+    using std::runtime_error::runtime_error;
+};
+inline std::array<uint8_t, 32> scalar_to_bytes(const Fr& s) {  // Fr::to_repr
+    const h2::Fe c = h2::fe_to_canonical<h2::FrP>(s.fe());
+    std::array<uint8_t, 32> o;
+    std::memcpy(o.data(), c.l, 32);
+    return o;
+}
+inline std::array<uint8_t, 32> point_to_bytes(const G1Affine& p) {  // G1Affine::to_bytes
+    std::array<uint8_t, 32> o{};
+    if (g1::is_identity(p)) return o;
+    h2::Fe x, y;
+    std::memcpy(x.l, p.x, 32), std::memcpy(y.l, p.y, 32);
+    h2::Fe xc = h2::fe_to_canonical<h2::FqP>(x);
+    xc.l[7] |= (h2::fe_to_canonical<h2::FqP>(y).l[0] & 1u) << 31;
+    std::memcpy(o.data(), xc.l, 32);
+    return o;
+}
+class Blake2bBase {
+   public:
+    Blake2bBase() : state_("Halo2-Transcript") {}  // :123-126 / :302-305
+    Fr squeeze_challenge() {                       // :371-376, Challenge255::new / get_scalar :499-513
+        const uint8_t prefix = 0;
+        state_.update(&prefix, 1);
+        return fr_from_bytes_wide(state_.digest().data());
+    }
+    void common_point(const G1Affine& p) {  // :378-390
+        if (g1::is_identity(p)) throw Error("cannot write points at infinity to the transcript");
+        if (!h2::affine_on_curve(g1::in(p))) throw Error("point not on the curve");
+        h2::Fe x, y;
+        std::memcpy(x.l, p.x, 32), std::memcpy(y.l, p.y, 32);
+        const h2::Fe c[2] = {h2::fe_to_canonical<h2::FqP>(x), h2::fe_to_canonical<h2::FqP>(y)};
+        const uint8_t prefix = 1;
+        state_.update(&prefix, 1);
+        state_.update(reinterpret_cast<const uint8_t*>(c), 64);
+    }
+    void common_scalar(const Fr& s) {  // :392-397
+        const uint8_t prefix = 2;
+        state_.update(&prefix, 1);
+        state_.update(scalar_to_bytes(s).data(), 32);
+    }
+
+   private:
+    Blake2b state_;
+};
+class Blake2bWrite : public Blake2bBase {
+   public:
+    void write_point(const G1Affine& p) {  // :341-345
+        common_point(p);
+        const auto b = point_to_bytes(p);
+        proof_.insert(proof_.end(), b.begin(), b.end());
+    }
+    void write_scalar(const Fr& s) {  // :346-350
+        common_scalar(s);
+        const auto b = scalar_to_bytes(s);
+        proof_.insert(proof_.end(), b.begin(), b.end());
+    }
+    std::vector<uint8_t> finalize() const { return proof_; }  // :311-314
+
+   private:
+    std::vector<uint8_t> proof_;
+};
+class Blake2bRead : public Blake2bBase {
+   public:
+    explicit Blake2bRead(std::vector<uint8_t> proof) : proof_(std::move(proof)) {}
+    G1Affine read_point() {  // :151-160
+        G1Affine p;
+        if (!serde::g1_from_bytes_host(take(), p)) throw Error("invalid point encoding in proof");
+        common_point(p);
+        return p;
+    }
+    Fr read_scalar() {  // :162-174
+        h2::Fe c;
+        std::memcpy(c.l, take(), 32);
+        if (!h2::fe_is_canonical<h2::FrP>(c)) throw Error("invalid field element encoding in proof");
+        const Fr s = Fr::from_fe(h2::fe_from_canonical<h2::FrP>(c));
+        common_scalar(s);
+        return s;
+    }
+
+   private:
+    std::vector<uint8_t> proof_;
+    size_t at_ = 0;
+    const uint8_t* take() {
+        if (at_ + 32 > proof_.size()) throw Error("short read");
+        at_ += 32;
+        return proof_.data() + at_ - 32;
+    }
+};
+}  // namespace transcript
+
+namespace poly {
+namespace ipa {
+
+struct Error : std::runtime_error {  // Error::{OpeningError, SamplingError, ConstraintSystemFailure}, or an unwrap the reference panics on
+    using std::runtime_error::runtime_error;
+};
+
+// device memory of one opening (h2hip_device_alloc), freed with the object
+class DeviceBuf {
+   public:
+    explicit DeviceBuf(size_t bytes) { engine_check(h2hip_device_alloc(bytes, &p_), "h2hip_device_alloc"); }
+    DeviceBuf(const DeviceBuf&) = delete;
+    DeviceBuf& operator=(const DeviceBuf&) = delete;
+    ~DeviceBuf() { (void)h2hip_device_free(p_); }
+    void* at(size_t byte_offset = 0) const { return static_cast<char*>(p_) + byte_offset; }
+
+   private:
+    void* p_ = nullptr;
+};
+
+// ParamsIPA (commitment.rs:29-36)
+struct ParamsIPA {
+    uint32_t k = 0;
+    uint64_t n = 0;
+    std::vector<G1Affine> g, g_lagrange;
+    G1Affine w{}, u{};
+
+    // the caller's generators
+    static ParamsIPA from_parts(std::vector<G1Affine> g, const G1Affine& w, const G1Affine& u) {
+        ParamsIPA p;
+        while ((uint64_t(1) << p.k) < g.size()) p.k++;
+        if (g.size() != (size_t(1) << p.k)) throw std::logic_error("ParamsIPA::from_parts: g is not 2^k points");
+        p.n = g.size();
+        p.g_lagrange = arithmetic::g_to_lagrange(g, p.k);
+        p.g = std::move(g);
+        p.w = w, p.u = u;
+        return p;
+    }
+    // the point of one message by DESIGN.md section 2's rule: h = BLAKE2b-512(person "Halo2-Parameters", M || ctr LE32), x = h[0:48] mod q,
+    // sign = h[63] & 1, the first counter with x != 0 and x^3 + 3 a square
+    static G1Affine hash_to_curve(const std::vector<uint8_t>& message) {
+        for (uint32_t ctr = 0;; ctr++) {
+            Blake2b st("Halo2-Parameters");
+            st.update(message.data(), message.size());
+            const uint8_t c[4] = {uint8_t(ctr), uint8_t(ctr >> 8), uint8_t(ctr >> 16), uint8_t(ctr >> 24)};
+            st.update(c, 4);
+            const auto h = st.digest();
+            uint32_t rem[8] = {0};  // h[0:48] mod q, one bit at a time: rem < q < 2^254 throughout
+            for (int bit = 383; bit >= 0; bit--) {
+                uint32_t carry = (h[size_t(bit) >> 3] >> (bit & 7)) & 1u;
+                for (int j = 0; j < 8; j++) {
+                    const uint32_t top = rem[j] >> 31;
+                    rem[j] = rem[j] << 1 | carry;
+                    carry = top;
+                }
+                h2::Fe o;
+                h2::fe_cond_sub<h2::FqP>(o, rem);
+                std::memcpy(rem, o.l, 32);
+            }
+            uint8_t enc[32];
+            std::memcpy(enc, rem, 32);
+            if (serde::all_zero(enc, 32)) continue;  // x = 0: the identity's encoding or an invalid one, no generator
+            enc[31] |= uint8_t((h[63] & 1u) << 7);
+            G1Affine p;
+            if (serde::g1_from_bytes_host(enc, p)) return p;
+        }
+    }
+    // ParamsProver::new (:158-211) with that derivation; messages [0] || i LE32 for g[i], [1] for w, [2] for u
+    static ParamsIPA new_(uint32_t k) {
+        if (k >= 32) throw std::logic_error("assertion failed: k < 32");  // :161
+        std::vector<G1Affine> g(size_t(1) << k);
+        for (size_t i = 0; i < g.size(); i++) g[i] = hash_to_curve({0, uint8_t(i), uint8_t(i >> 8), uint8_t(i >> 16), uint8_t(i >> 24)});
+        return from_parts(std::move(g), hash_to_curve({1}), hash_to_curve({2}));
+    }
+    // commit (:216-227) / commit_lagrange (:92-107): the MSM over g (g_lagrange) plus [r] W
+    G1Affine commit(const std::vector<Fr>& poly, const Fr& r) const { return commit_over(g, poly, r); }
+    G1Affine commit_lagrange(const std::vector<Fr>& poly, const Fr& r) const { return commit_over(g_lagrange, poly, r); }
+
+   private:
+    G1Affine commit_over(const std::vector<G1Affine>& bases, const std::vector<Fr>& poly, const Fr& r) const {
+        if (poly.size() != n) throw std::logic_error("assertion failed: poly.len() == params.n");
+        return g1::sum({{Fr::one(), arithmetic::best_multiexp(poly, bases).to_affine()}, {r, w}});
+    }
+};
+
+// MSMIPA (msm.rs): scalars for g, w, u and a map x -> (scalar, y) of other terms, merged where two points share x
+class MSMIPA {
+   public:
+    explicit MSMIPA(const ParamsIPA& params) : params(&params) {}
+    const ParamsIPA* params;
+    void append_term(const Fr& scalar, const G1Affine& point) {  // :71-91
+        if (g1::is_identity(point)) return;
+        std::array<uint64_t, 4> x;
+        std::memcpy(x.data(), point.x, 32);
+        auto it = other_.find(x);
+        if (it == other_.end()) {
+            other_[x] = {scalar, point};
+        } else if (it->second.point == point) {
+            it->second.scalar = it->second.scalar + scalar;
+        } else {
+            if (!(g1::neg(it->second.point) == point)) throw std::logic_error("assertion failed: *our_y == -y");
+            it->second.scalar = it->second.scalar - scalar;
+        }
+    }
+    void add_msm(const MSMIPA& o) {  // :94-120
+        for (const auto& kv : o.other_) append_term(kv.second.scalar, kv.second.point);
+        if (o.has_g_) add_to_g_scalars(o.g_scalars_);
+        if (o.has_w_) add_to_w_scalar(o.w_scalar_);
+        if (o.has_u_) add_to_u_scalar(o.u_scalar_);
+    }
+    void scale(const Fr& factor) {  // :122-135
+        for (Fr& s : g_scalars_) s = s * factor;
+        for (auto& kv : other_) kv.second.scalar = kv.second.scalar * factor;
+        w_scalar_ = w_scalar_ * factor, u_scalar_ = u_scalar_ * factor;
+    }
+    void add_constant_term(const Fr& c) {  // :190-198
+        ensure_g();
+        g_scalars_[0] = g_scalars_[0] + c;
+    }
+    void add_to_g_scalars(const std::vector<Fr>& s) {  // :202-211
+        if (s.size() != params->n) throw std::logic_error("assertion failed: scalars.len() == params.n");
+        ensure_g();
+        for (size_t i = 0; i < s.size(); i++) g_scalars_[i] = g_scalars_[i] + s[i];
+    }
+    void add_to_w_scalar(const Fr& s) { w_scalar_ = w_scalar_ + s, has_w_ = true; }  // :213-215
+    void add_to_u_scalar(const Fr& s) { u_scalar_ = u_scalar_ + s, has_u_ = true; }  // :218-220
+    G1Affine eval() const {  // :141-174: the g part on the engine, the rest on the host
+        std::vector<g1::Term> terms;
+        for (const auto& kv : other_) terms.push_back(kv.second);
+        if (has_w_) terms.push_back({w_scalar_, params->w});
+        if (has_u_) terms.push_back({u_scalar_, params->u});
+        if (has_g_) terms.push_back({Fr::one(), arithmetic::best_multiexp(g_scalars_, params->g).to_affine()});
+        return g1::sum(terms);
+    }
+    bool check() const { return g1::is_identity(eval()); }  // :137-139
+
+   private:
+    std::vector<Fr> g_scalars_;
+    Fr w_scalar_ = Fr::zero(), u_scalar_ = Fr::zero();
+    bool has_g_ = false, has_w_ = false, has_u_ = false;
+    std::map<std::array<uint64_t, 4>, g1::Term> other_;
+    void ensure_g() {
+        if (!has_g_) g_scalars_.assign(params->n, Fr::zero()), has_g_ = true;
+    }
+};
+
+// compute_s (strategy.rs:161-176) on the engine
+inline std::vector<Fr> compute_s(const std::vector<Fr>& u, const Fr& init) {
+    if (u.empty() || u.size() > 28) throw std::logic_error("assertion failed: !u.is_empty()");
+    std::vector<Fr> s(size_t(1) << u.size());
+    engine_check(h2hip_ipa_compute_s_bn254_fr(u[0].l, uint32_t(u.size()), init.l, s[0].l), "h2hip_ipa_compute_s_bn254_fr");
+    return s;
+}
+// prod (1 + u_{k-1-i} x^(2^i))  (commitment/verifier.rs:98-106)
+inline Fr compute_b(const Fr& x, const std::vector<Fr>& u) {
+    Fr tmp = Fr::one(), cur = x;
+    for (size_t i = u.size(); i-- > 0;) {
+        tmp = tmp * (Fr::one() + u[i] * cur);
+        cur = cur * cur;
+    }
+    return tmp;
+}
+
+// commitment::create_proof (commitment/prover.rs:29-153).  Draws, in order: the 2^k coefficients of s_poly, s_poly_blind, per round
+// l_j_randomness then r_j_randomness.
+inline void create_proof(const ParamsIPA& params, FrRng& rng, transcript::Blake2bWrite& tr, const std::vector<Fr>& p_poly, const Fr& p_blind,
+                         const Fr& x_3) {
+    const size_t n = params.n;
+    const uint32_t k = params.k;
+    if (p_poly.size() != n) throw std::logic_error("assertion failed: p_poly.len() == params.n");  // :43
+    std::vector<Fr> s_poly(n);
+    rng.fill(s_poly.data(), n);                                                // :47-50
+    s_poly[0] = s_poly[0] - arithmetic::eval_polynomial(s_poly, x_3);          // :52-54
+    const Fr s_blind = rng();                                                  // :56
+    tr.write_point(params.commit(s_poly, s_blind));                            // :59-60
+    const Fr xi = tr.squeeze_challenge(), z = tr.squeeze_challenge();          // :65, :69
+    std::vector<Fr> p_prime = arithmetic::poly_combine({&s_poly, &p_poly}, {xi, Fr::one()}, {}, {}, Fr::one(), n);  // :73
+    p_prime[0] = p_prime[0] - arithmetic::eval_polynomial(p_prime, x_3);       // :74-75
+    Fr f = s_blind * xi + p_blind;                                             // :76-80
+    DeviceBuf d_p(32 * n), d_b(32 * n), d_g(64 * n);
+    engine_check(h2hip_memcpy_h2d(d_p.at(), p_prime[0].l, 32 * n, nullptr), "h2hip_memcpy_h2d");
+    engine_check(h2hip_memcpy_h2d(d_g.at(), params.g[0].x, 64 * n, nullptr), "h2hip_memcpy_h2d");  // :99
+    engine_check(h2hip_ipa_powers_bn254_fr_device(x_3.l, n, d_b.at(), nullptr), "h2hip_ipa_powers_bn254_fr_device");  // :88-95
+    Fr values[2] = {Fr::zero(), Fr::zero()};
+    if (k) engine_check(h2hip_ipa_inner_products_bn254_fr_device(d_p.at(), d_b.at(), n / 2, values[0].l, nullptr), "h2hip_ipa_inner_products");
+    for (uint32_t j = 0; j < k; j++) {                                         // :102
+        const size_t half = size_t(1) << (k - j - 1);
+        G1 l_g, r_g;
+        engine_check(h2hip_msm_bn254_device(d_p.at(32 * half), d_g.at(), half, l_g.x, nullptr), "h2hip_msm_bn254_device");  // :109
+        engine_check(h2hip_msm_bn254_device(d_p.at(), d_g.at(64 * half), half, r_g.x, nullptr), "h2hip_msm_bn254_device");  // :110
+        const Fr l_rand = rng(), r_rand = rng();                               // :113-114
+        tr.write_point(g1::sum({{Fr::one(), l_g.to_affine()}, {values[0] * z, params.u}, {l_rand, params.w}}));  // :115-121
+        tr.write_point(g1::sum({{Fr::one(), r_g.to_affine()}, {values[1] * z, params.u}, {r_rand, params.w}}));  // :116-122
+        const Fr u_j = tr.squeeze_challenge();                                 // :124
+        if (u_j == Fr::zero()) throw Error("create_proof: a challenge u_j is zero");  // :125 unwraps
+        const Fr u_j_inv = u_j.invert();
+        engine_check(h2hip_ipa_fold_bn254_fr_device(d_p.at(), d_b.at(), half, u_j_inv.l, u_j.l, half >= 2 ? values[0].l : nullptr, nullptr),
+                     "h2hip_ipa_fold_bn254_fr_device");                        // :129-134, with the next round's :111-112
+        engine_check(h2hip_ipa_collapse_bn254_device(d_g.at(), half, u_j.l, nullptr), "h2hip_ipa_collapse_bn254_device");  // :137
+        f = f + l_rand * u_j_inv + r_rand * u_j;                               // :141-142
+    }
+    Fr c;
+    engine_check(h2hip_memcpy_d2h(c.l, d_p.at(), 32, nullptr), "h2hip_memcpy_d2h");
+    engine_check(h2hip_stream_synchronize(nullptr), "h2hip_stream_synchronize");
+    tr.write_scalar(c);                                                        // :147-150
+    tr.write_scalar(f);
+}
+
+// GuardIPA (strategy.rs:24-77)
+struct GuardIPA {
+    MSMIPA msm;
+    Fr neg_c;
+    std::vector<Fr> u;
+    MSMIPA use_challenges() {  // :51-56
+        msm.add_to_g_scalars(compute_s(u, neg_c));
+        return msm;
+    }
+    G1Affine compute_g() const { return arithmetic::best_multiexp(compute_s(u, Fr::one()), msm.params->g).to_affine(); }  // :72-76
+};
+
+// commitment::verify_proof (commitment/verifier.rs:22-95)
+inline GuardIPA verify_proof(const ParamsIPA& params, MSMIPA msm, transcript::Blake2bRead& tr, const Fr& x, const Fr& v) {
+    try {
+        msm.add_constant_term(Fr::zero() - v);                                 // :32
+        const G1Affine s_commitment = tr.read_point();                         // :33
+        const Fr xi = tr.squeeze_challenge();                                  // :34
+        msm.append_term(xi, s_commitment);                                     // :35
+        const Fr z = tr.squeeze_challenge();                                   // :37
+        std::vector<Fr> u;
+        for (uint32_t j = 0; j < params.k; j++) {                              // :40-66 (batch_invert leaves a zero as it is)
+            const G1Affine l = tr.read_point(), r = tr.read_point();
+            const Fr u_j = tr.squeeze_challenge();
+            msm.append_term(u_j == Fr::zero() ? u_j : u_j.invert(), l);
+            msm.append_term(u_j, r);
+            u.push_back(u_j);
+        }
+        const Fr c = tr.read_scalar(), f = tr.read_scalar();                   // :79-81
+        const Fr neg_c = Fr::zero() - c;
+        msm.add_to_u_scalar(neg_c * compute_b(x, u) * z);                      // :82-84
+        msm.add_to_w_scalar(Fr::zero() - f);                                   // :85
+        return GuardIPA{std::move(msm), neg_c, std::move(u)};
+    } catch (const transcript::Error& e) {
+        throw Error(std::string("verify_proof: ") + e.what());
+    }
+}
+
+// SingleStrategy (strategy.rs:121-158)
+class SingleStrategy {
+   public:
+    explicit SingleStrategy(const ParamsIPA& params) : msm_(params) {}
+    void process(const std::function<GuardIPA(MSMIPA)>& f) {  // Error (ConstraintSystemFailure) unless the proof verifies
+        if (!f(msm_).use_challenges().check()) throw Error("the opening does not verify");
+    }
+
+   private:
+    MSMIPA msm_;
+};
+
+// construct_intermediate_sets (multiopen.rs:66-176) over queries that name their commitment by address, as the reference compares them
+struct CommitmentData {
+    const void* commitment;
+    size_t set_index = 0;
+    std::vector<size_t> point_indices;
+    std::vector<Fr> evals;
+};
+struct Query {
+    const void* commitment;
+    Fr point, eval;
+};
+inline std::pair<std::vector<CommitmentData>, std::vector<std::vector<Fr>>> construct_intermediate_sets(const std::vector<Query>& queries) {
+    std::vector<CommitmentData> map;
+    std::vector<Fr> points;  // index = order of first appearance (:76-96)
+    auto point_index = [&](const Fr& p) {
+        for (size_t i = 0; i < points.size(); i++)
+            if (points[i] == p) return i;
+        points.push_back(p);
+        return points.size() - 1;
+    };
+    auto find = [&](const void* c) -> CommitmentData* {
+        for (auto& d : map)
+            if (d.commitment == c) return &d;
+        return nullptr;
+    };
+    for (const Query& q : queries) {
+        const size_t idx = point_index(q.point);
+        if (CommitmentData* d = find(q.commitment)) {
+            d->point_indices.push_back(idx);
+        } else {
+            map.push_back({q.commitment, 0, {idx}, {}});
+        }
+    }
+    std::vector<std::vector<size_t>> sets;  // ordered point-index sets, index = order of first appearance (:105-121)
+    auto set_of = [](const CommitmentData& d) {
+        std::vector<size_t> s;
+        for (size_t i : d.point_indices) {
+            auto it = s.begin();
+            while (it != s.end() && *it < i) ++it;
+            if (it == s.end() || *it != i) s.insert(it, i);
+        }
+        return s;
+    };
+    for (auto& d : map) {
+        const auto s = set_of(d);
+        size_t at = 0;
+        while (at < sets.size() && sets[at] != s) at++;
+        if (at == sets.size()) sets.push_back(s);
+        d.set_index = at;
+        d.evals.assign(d.point_indices.size(), Fr::zero());  // :124-127
+    }
+    for (const Query& q : queries) {  // :130-164
+        CommitmentData* d = find(q.commitment);
+        const auto& s = sets[d->set_index];
+        const size_t idx = point_index(q.point);
+        for (size_t i = 0; i < s.size(); i++)
+            if (s[i] == idx) d->evals[i] = q.eval;
+    }
+    std::vector<std::vector<Fr>> point_sets;  // :167-173
+    for (const auto& s : sets) {
+        point_sets.emplace_back();
+        for (size_t i : s) point_sets.back().push_back(points[i]);
+    }
+    return {map, point_sets};
+}
+
+struct ProverQuery {  // poly/query.rs: two queries name the same commitment when they hold the same polynomial object
+    Fr point;
+    const std::vector<Fr>* poly;
+    Fr blind;
+};
+struct VerifierQuery {  // CommitmentReference::Commitment: the same commitment when they hold the same object
+    const G1Affine* commitment;
+    Fr point, eval;
+};
+
+// ProverIPA (multiopen/prover.rs); q_prime_blind is the first draw
+class ProverIPA {
+   public:
+    explicit ProverIPA(const ParamsIPA& params) : params_(params) {}
+    void create_proof(FrRng& rng, transcript::Blake2bWrite& tr, const std::vector<ProverQuery>& queries) const {
+        const size_t n = params_.n;
+        const Fr one = Fr::one();
+        const Fr x_1 = tr.squeeze_challenge(), x_2 = tr.squeeze_challenge();  // :42-43
+        std::vector<Query> tagged;
+        std::map<const void*, Fr> blinds;
+        for (const auto& q : queries) tagged.push_back({q.poly, q.point, Fr::zero()}), blinds.emplace(q.poly, q.blind);
+        const auto sets = construct_intermediate_sets(tagged);                // :45
+        std::vector<std::vector<Fr>> q_polys(sets.second.size());
+        std::vector<Fr> q_blinds(sets.second.size(), Fr::zero());
+        for (const auto& d : sets.first) {                                    // :53-71
+            const auto* poly = static_cast<const std::vector<Fr>*>(d.commitment);
+            auto& q = q_polys[d.set_index];
+            q = q.empty() ? *poly : arithmetic::poly_combine({&q, poly}, {x_1, one}, {}, {}, one, n);
+            q_blinds[d.set_index] = q_blinds[d.set_index] * x_1 + blinds.at(d.commitment);
+        }
+        std::vector<Fr> q_prime;
+        for (size_t i = 0; i < q_polys.size(); i++) {                         // :74-95: kate_division by each point, resized to n
+            const std::vector<Fr> quot = arithmetic::poly_combine({&q_polys[i]}, {one}, {}, sets.second[i], one, n);
+            q_prime = q_prime.empty() ? quot : arithmetic::poly_combine({&q_prime, &quot}, {x_2, one}, {}, {}, one, n);
+        }
+        const Fr q_prime_blind = rng();                                       // :97
+        tr.write_point(params_.commit(q_prime, q_prime_blind));               // :98-100
+        const Fr x_3 = tr.squeeze_challenge();                                // :102
+        for (const auto& q : q_polys) tr.write_scalar(arithmetic::eval_polynomial(q, x_3));  // :106-108
+        const Fr x_4 = tr.squeeze_challenge();                                // :110
+        std::vector<Fr> p_poly = q_prime;
+        Fr p_blind = q_prime_blind;
+        for (size_t i = 0; i < q_polys.size(); i++) {                         // :112-120
+            p_poly = arithmetic::poly_combine({&p_poly, &q_polys[i]}, {x_4, one}, {}, {}, one, n);
+            p_blind = p_blind * x_4 + q_blinds[i];
+        }
+        ipa::create_proof(params_, rng, tr, p_poly, p_blind, x_3);            // :122
+    }
+
+   private:
+    const ParamsIPA& params_;
+};
+
+// VerifierIPA (multiopen/verifier.rs)
+class VerifierIPA {
+   public:
+    explicit VerifierIPA(const ParamsIPA& params) : params_(params) {}
+    GuardIPA verify_proof(transcript::Blake2bRead& tr, const std::vector<VerifierQuery>& queries, MSMIPA msm) const {
+        const Fr x_1 = tr.squeeze_challenge(), x_2 = tr.squeeze_challenge();  // :50, :54
+        std::vector<Query> tagged;
+        for (const auto& q : queries) tagged.push_back({q.commitment, q.point, q.eval});
+        const auto sets = construct_intermediate_sets(tagged);                // :56
+        std::vector<MSMIPA> q_commitments(sets.second.size(), MSMIPA(params_));  // :60
+        std::vector<std::vector<Fr>> q_eval_sets;
+        for (const auto& ps : sets.second) q_eval_sets.emplace_back(ps.size(), Fr::zero());  // :64-67
+        for (const auto& d : sets.first) {                                    // :69-95
+            q_commitments[d.set_index].scale(x_1);
+            q_commitments[d.set_index].append_term(Fr::one(), *static_cast<const G1Affine*>(d.commitment));
+            auto& evals = q_eval_sets[d.set_index];
+            for (size_t i = 0; i < evals.size() && i < d.evals.size(); i++) evals[i] = evals[i] * x_1 + d.evals[i];
+        }
+        G1Affine q_prime;
+        Fr x_3;
+        std::vector<Fr> u;
+        try {
+            q_prime = tr.read_point();                                        // :99
+            x_3 = tr.squeeze_challenge();                                     // :103
+            for (size_t i = 0; i < q_eval_sets.size(); i++) u.push_back(tr.read_scalar());  // :107-110
+        } catch (const transcript::Error& e) {
+            throw Error(std::string("verify_proof: ") + e.what());            // Error::SamplingError
+        }
+        Fr msm_eval = Fr::zero();
+        for (size_t i = 0; i < u.size(); i++) {                               // :114-128
+            const std::vector<Fr> r_poly = arithmetic::lagrange_interpolate(sets.second[i], q_eval_sets[i]);
+            Fr r_eval = Fr::zero();
+            for (size_t j = r_poly.size(); j-- > 0;) r_eval = r_eval * x_3 + r_poly[j];
+            Fr ev = u[i] - r_eval;
+            for (const Fr& p : sets.second[i]) {
+                if (x_3 == p) throw Error("verify_proof: x_3 is one of the points");  // :124 unwraps
+                ev = ev * (x_3 - p).invert();
+            }
+            msm_eval = msm_eval * x_2 + ev;
+        }
+        const Fr x_4 = tr.squeeze_challenge();                                // :132
+        msm.append_term(Fr::one(), q_prime);                                  // :135
+        Fr v = msm_eval;
+        for (size_t i = 0; i < u.size(); i++) {                               // :136-143
+            msm.scale(x_4);
+            msm.add_msm(q_commitments[i]);
+            v = v * x_4 + u[i];
+        }
+        return ipa::verify_proof(params_, std::move(msm), tr, x_3, v);       // :146
+    }
+
+   private:
+    const ParamsIPA& params_;
+};
+
+}  // namespace ipa
+}  // namespace poly
+}  // namespace halo2_proofs

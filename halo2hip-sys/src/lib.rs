@@ -18,6 +18,8 @@
 
 pub mod evalh;
 pub mod ffi;
+mod ffi_ipa;
+pub mod ipa;
 
 use ff::{Field, PrimeField};
 use halo2curves::bn256::{Fr, G1Affine, G1};
