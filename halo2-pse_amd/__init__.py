@@ -7,7 +7,7 @@ reference (halo2_proofs::arithmetic::{best_multiexp, best_fft}, poly::Evaluation
 poly::kzg::ParamsKZG).  There is no CPU fallback here: if the library or the GPU is
 missing, calls raise.
 
-Every entry point's prototype is stated once, in _abi.py and _abi_ipa.py (generated from the headers by tools/gen_ctypes_abi.py) and
+Every entry point's prototype is stated once, in _abi.py, _abi_ipa.py and _abi_g1.py (generated from the headers by tools/gen_ctypes_abi.py) and
 bound by lib(): call sites pass plain Python ints and bools for the by-value parameters, and ctypes refuses a wrong argument count.
 
 Arrays: numpy uint64 -- Fr elements (n,4), G1Affine (n,8), G1 Jacobian (12,): 4 x u64 LE limbs,
@@ -20,6 +20,7 @@ import subprocess
 import numpy as np
 
 from ._abi import PROTOTYPES
+from ._abi_g1 import PROTOTYPES as PROTOTYPES_G1
 from ._abi_ipa import PROTOTYPES as PROTOTYPES_IPA
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -59,8 +60,9 @@ def lib():
         # declared width and refuses a wrong argument count.  Bare argtypes would let a cdecl function take surplus arguments; naming
         # each parameter an input (paramflags) makes the count exact.  Another build (HALO2_HIP_LIB) may lack a name; tests/test_abi.py
         # holds the in-tree one to all of them.
-        # The inner-product argument's entry points (include/halo2hip_ipa.h) have a table of their own, _abi_ipa.py, applied after the first.
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_IPA.items()):
+        # The inner-product argument's entry points (include/halo2hip_ipa.h) have a table of their own, _abi_ipa.py, applied after the first; the host group
+        # sums (include/halo2hip_g1.h) have _abi_g1.py, applied after those two.
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_IPA.items()) + list(PROTOTYPES_G1.items()):
             try:
                 fn = ctypes.CFUNCTYPE(restype, *argtypes)((name, L), ((1,),) * len(argtypes))
             except AttributeError:
@@ -379,6 +381,66 @@ def fr_from_int(v):
 def fr_to_int(limbs):
     m = sum(int(x) << (64 * i) for i, x in enumerate(np.asarray(limbs, dtype=np.uint64).reshape(4)))
     return m * pow(_FR_R, -1, FR_MODULUS) % FR_MODULUS
+
+
+# ------------------------------------------------------------------ few-term group sums on the host (include/halo2hip_g1.h)
+FQ_MODULUS = 0x30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47
+_FQ_R = (1 << 256) % FQ_MODULUS
+_FQ_R_INV = pow(_FQ_R, -1, FQ_MODULUS)
+
+
+def g1_from_int(point):
+    """an affine integer pair (None: the identity) -> (8,) uint64 Montgomery limbs"""
+    if point is None:
+        return np.zeros(8, dtype=np.uint64)
+    x, y = point[0] * _FQ_R % FQ_MODULUS, point[1] * _FQ_R % FQ_MODULUS
+    return np.array([(v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for v in (x, y) for i in range(4)], dtype=np.uint64)
+
+
+def g1_to_int(limbs):
+    """(8,) uint64 Montgomery limbs -> an affine integer pair, None for (0, 0)"""
+    v = [int(w) for w in np.asarray(limbs, dtype=np.uint64).reshape(8)]
+    x = sum(w << (64 * i) for i, w in enumerate(v[:4])) * _FQ_R_INV % FQ_MODULUS
+    y = sum(w << (64 * i) for i, w in enumerate(v[4:])) * _FQ_R_INV % FQ_MODULUS
+    return None if x == 0 and y == 0 else (x, y)
+
+
+def g1_linear_combinations_limbs(addends, scalars, points, m=None):
+    """h2hip_g1_linear_combinations_bn254 on limbs: addends (m, 12) Jacobian or None, scalars (m, t, 4) Montgomery, points (t, 8)
+    affine -> (m, 8) affine.  Host code on the calling thread: no GPU, no engine lock."""
+    points = np.zeros((0, 8), dtype=np.uint64) if points is None else _u64(points).reshape(-1, 8)
+    t = points.shape[0]
+    if addends is not None:
+        addends = _u64(addends).reshape(-1, 12)
+        m = addends.shape[0] if m is None else m
+        if addends.shape[0] != m:
+            raise ValueError("g1_linear_combinations: %d addends for %d sums" % (addends.shape[0], m))
+    scalars = _u64(scalars).reshape(-1, 4) if t else np.zeros((0, 4), dtype=np.uint64)
+    if m is None:
+        m = scalars.shape[0] // t if t else 0
+    if scalars.shape[0] != m * t:
+        raise ValueError("g1_linear_combinations: %d scalars for %d sums of %d terms" % (scalars.shape[0], m, t))
+    out = np.zeros((m, 8), dtype=np.uint64)
+    _check(lib().h2hip_g1_linear_combinations_bn254(None if addends is None else _p(addends), _p(scalars) if m * t else None,
+                                                    _p(points) if t else None, m, t, _p(out) if m else None),
+           "h2hip_g1_linear_combinations_bn254")
+    return out
+
+
+def g1_linear_combinations(addends, scalars, points):
+    """out[j] = addends[j] + sum_i [scalars[j][i]] points[i] on the host (include/halo2hip_g1.h).  addends: the engine's Jacobian sums
+    ((m, 12) uint64, or a list of (12,) arrays) or None; scalars: m rows of t integers; points: t affine integer pairs (None: the
+    identity).  Returns m affine integer pairs, None for the identity, as transcript.write_point takes them."""
+    rows = [list(row) for row in scalars]
+    t = len(points)
+    if any(len(row) != t for row in rows):
+        raise ValueError("g1_linear_combinations: every row of scalars has one scalar per point")
+    if addends is not None:
+        addends = np.stack([_u64(a).reshape(12) for a in addends]) if len(addends) else np.zeros((0, 12), dtype=np.uint64)
+    m = len(rows) if addends is None or t else addends.shape[0]
+    limbs = np.stack([fr_from_int(s) for row in rows for s in row]) if m * t else np.zeros((0, 4), dtype=np.uint64)
+    pts = np.stack([g1_from_int(p) for p in points]) if t else None
+    return [g1_to_int(row) for row in g1_linear_combinations_limbs(addends, limbs, pts, m)]
 
 # ------------------------------------------------------------------ grand products (permutation / lookup arguments), BatchInvert
 def _cols(arrays, n, what):
@@ -1350,8 +1412,6 @@ class SerdeFormat(enum.Enum):
 
 
 H2HIP_EENCODING = 5
-FQ_MODULUS = 0x30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47
-_FQ_R = (1 << 256) % FQ_MODULUS
 
 
 class H2HipEncodingError(H2HipError):

@@ -23,7 +23,9 @@
 
 #include "../../include/halo2hip.h"
 #include "../../include/halo2hip_debug.h"
+#include "../../include/halo2hip_g1.h"
 #include "engine.h"
+#include "g1_host.h"
 
 // the optional lazy pin cache (further down, inside the extern "C" block: declared with that linkage here too, g++ insists)
 extern "C" {
@@ -1812,6 +1814,17 @@ int h2hip_g1_to_affine(const uint64_t xyz[12], uint64_t xy[8]) {
     memcpy(&j, xyz, 96);
     Affine a = xyzz_to_affine(jac_to_xyzz(j));
     memcpy(xy, &a, 64);
+    return 0;
+}
+
+// few-term sums on the calling thread (include/halo2hip_g1.h): no Entry, no engine lock, no HIP call
+int h2hip_g1_linear_combinations_bn254(const uint64_t* addends_xyz, const uint64_t* scalars, const uint64_t* points_xy, size_t m, size_t t,
+                                       uint64_t* out_xy) {
+    char why[160];
+    if (g1h::linear_combinations(addends_xyz, scalars, points_xy, m, t, out_xy, why, sizeof(why))) {
+        set_error("g1_linear_combinations: %s", why);
+        return H2HIP_EINVAL;
+    }
     return 0;
 }
 

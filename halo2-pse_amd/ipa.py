@@ -11,8 +11,10 @@
 
 Scalars are Python integers in [0, r), points affine integer pairs (None: the identity), the transcript is transcript.py's Blake2bWrite /
 Blake2bRead.  Everything of 2^k elements lives in HBM as torch CUDA tensors of Montgomery limbs: the engine folds, collapses, reduces
-and multiplies; the transcript, the draws and the handful of group operations per round stay here, on integers.  There is no CPU
-fallback: without a GPU the calls raise H2HipError.
+and multiplies; the transcript and the draws stay here, and the handful of group operations between the MSMs -- the + [r] W of a
+commitment, the [value z] U + [rand] W of a round, the other terms of MSMIPA.eval -- are one host call of the library each
+(h2hip_g1_linear_combinations_bn254, include/halo2hip_g1.h: dependent chains of a few hundred group operations, faster on a host core
+than on GPU lanes).  There is no CPU fallback for the rest: without a GPU the calls raise H2HipError.
 
 Draw order (one FrRng): ProverIPA.create_proof draws q_prime_blind first; create_proof then draws the 2^k coefficients of s_poly in HBM
 (element i = the next block i), s_poly_blind, and per round l_j_randomness then r_j_randomness.
@@ -29,48 +31,24 @@ import hashlib
 import numpy as np
 
 from . import (FQ_MODULUS, FR_MODULUS, H2HIP_EENCODING, H2HipError, _check, _dptr, _fe, _p, _stream, _u64, bases_pin_device,
-               bases_unpin_device, device_count, eval_polynomials_device, fr_from_int, fr_to_int, g1_to_affine, g1_to_bytes, g_to_lagrange,
-               lib, msm_batch_device, msm_device, poly_combine_device, to_numpy_u64)
+               bases_unpin_device, device_count, eval_polynomials_device, fr_from_int, fr_to_int, g1_linear_combinations,
+               g1_to_bytes, g1_to_int, g_to_lagrange, lib, msm_batch_device, msm_device, poly_combine_device, to_numpy_u64)
 from .transcript import TranscriptError, point_from_bytes
 from .verifier import _affine, _interpolate_eval, _jac, _jac_add, _jac_double
 
 R, Q = FR_MODULUS, FQ_MODULUS
-_FQ_R = (1 << 256) % Q
 GENERATOR_PERSONAL = b"Halo2-Parameters"
+_LINCOMB_TERMS = 4096  # the most terms one h2hip_g1_linear_combinations_bn254 call takes
 
 
 class IPAError(ValueError):
     """the reference's Error::{OpeningError, SamplingError, ConstraintSystemFailure}, or an unwrap it would panic on (a zero challenge)"""
 
 
-# ------------------------------------------------------------------ points between the engine's limbs and integers
-def _limbs(m):
-    return [(m >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)]
-
-
-def g1_from_int(point):
-    """an affine integer pair (None: the identity) -> (8,) uint64 Montgomery limbs"""
-    if point is None:
-        return np.zeros(8, dtype=np.uint64)
-    return np.array(_limbs(point[0] * _FQ_R % Q) + _limbs(point[1] * _FQ_R % Q), dtype=np.uint64)
-
-
-def g1_to_int(limbs):
-    """(8,) uint64 Montgomery limbs -> an affine integer pair, None for (0, 0)"""
-    v = [int(x) for x in np.asarray(limbs, dtype=np.uint64).reshape(8)]
-    inv = pow(_FQ_R, -1, Q)
-    x = sum(w << (64 * i) for i, w in enumerate(v[:4])) * inv % Q
-    y = sum(w << (64 * i) for i, w in enumerate(v[4:])) * inv % Q
-    return None if x == 0 and y == 0 else (x, y)
-
-
-def jac_to_int(xyz):
-    """the engine's (12,) Jacobian result -> an affine integer pair"""
-    return g1_to_int(g1_to_affine(xyz))
-
-
+# ------------------------------------------------------------------ group sums on integers
 def _point_sum(terms):
-    """sum of [s] P over (s, P) pairs of integers: one doubling chain shared by all terms (Straus)"""
+    """sum of [s] P over (s, P) pairs of integers: one doubling chain shared by all terms (Straus).  For the places that hold integers
+    only; where an engine sum is one of the terms, g1_linear_combinations (include/halo2hip_g1.h) adds it in the library."""
     live = [(s % R, _jac(p)) for s, p in terms if p is not None and s % R]
     acc = (0, 1, 0)
     for bit in range(max((s.bit_length() for s, _ in live), default=0) - 1, -1, -1):
@@ -332,7 +310,7 @@ class ParamsIPA:
         for d in d_polys:
             assert d.numel() * d.element_size() == 32 * self.n  # the reference zips poly and bases: equal lengths
         sums = msm_batch_device(d_polys, d_bases, self.n) if len(d_polys) > 1 else [msm_device(d_polys[0], d_bases, self.n)]
-        return [_point_sum([(1, jac_to_int(s)), (r, self.w)]) for s, r in zip(sums, blinds)]
+        return g1_linear_combinations(sums, [[r] for r in blinds], [self.w])                                # + [r] W, one shared inversion
 
     def commit(self, poly, r):
         """poly: (n, 4) uint64 or a torch CUDA tensor of n x 32 B; r an integer -> the commitment as an affine integer pair"""
@@ -380,12 +358,11 @@ def create_proof(params, rng, transcript, p_poly, p_blind, x_3, resident=True):
     values = inner_products_device(d_pp, d_b, n // 2) if k else None
     for j in range(k):                                                                 # :102
         half = 1 << (k - j - 1)
-        l_g = jac_to_int(msm_device(d_pp[half:], d_gp, half))                          # :109
-        r_g = jac_to_int(msm_device(d_pp, d_gp[half:], half))                          # :110
+        l_g = msm_device(d_pp[half:], d_gp, half)                                      # :109
+        r_g = msm_device(d_pp, d_gp[half:], half)                                      # :110
         value_l, value_r = values                                                      # :111-112
         l_rand, r_rand = [fr_to_int(e) for e in rng.draw(2)]                           # :113-114
-        l_j = _point_sum([(1, l_g), (value_l * z, params.u), (l_rand, params.w)])      # :115
-        r_j = _point_sum([(1, r_g), (value_r * z, params.u), (r_rand, params.w)])      # :116
+        l_j, r_j = g1_linear_combinations([l_g, r_g], [[value_l * z, l_rand], [value_r * z, r_rand]], [params.u, params.w])   # :115-116
         transcript.write_point(l_j)                                                    # :121
         transcript.write_point(r_j)
         u_j = transcript.squeeze_challenge()                                           # :124
@@ -483,9 +460,12 @@ class MSMIPA:
             terms.append((self.w_scalar, self.params.w))
         if self.u_scalar is not None:
             terms.append((self.u_scalar, self.params.u))
-        if self.has_g:
-            terms.append((1, jac_to_int(msm_device(self.g_column(), self.params.d_g(), self.params.n))))
-        return _point_sum(terms)
+        addend = [msm_device(self.g_column(), self.params.d_g(), self.params.n)] if self.has_g else None
+        # one call (m = 1); only an accumulator over very many proofs has more terms than a call takes
+        chunks = [terms[at:at + _LINCOMB_TERMS] for at in range(0, len(terms), _LINCOMB_TERMS)] or [[]]
+        sums = [g1_linear_combinations(addend if i == 0 else None, [[s for s, _ in part]], [p for _, p in part])[0]
+                for i, part in enumerate(chunks)]
+        return sums[0] if len(sums) == 1 else _point_sum([(1, p) for p in sums])
 
     def check(self):                                                                   # :137-139
         return self.eval() is None
@@ -507,7 +487,7 @@ class GuardIPA:
 
     def compute_g(self):                                                               # :72-76
         params = self.msm.params
-        return jac_to_int(msm_device(compute_s_device(self.u, 1), params.d_g(), params.n))
+        return g1_linear_combinations([msm_device(compute_s_device(self.u, 1), params.d_g(), params.n)], [[]], [])[0]
 
 
 def verify_proof(params, msm, transcript, x, v):

@@ -11,7 +11,11 @@ points, with every column resident in HBM from the first commit to the last open
                      vanishing/prover.rs in their places and the multiopen provers of poly/kzg/multiopen/{gwc,shplonk}/prover.rs at the end
 
 Both KZG provers set QUERY_INSTANCE = false (gwc/prover.rs, shplonk/prover.rs:111), so instance values go into the transcript as scalars
-(prover.rs:90-93) and instance columns are neither committed nor opened; the QUERY_INSTANCE branch (IPA) is not restated.
+(prover.rs:90-93) and instance columns are neither committed nor opened.  multiopen="ipa" (params an ipa.ParamsIPA, the key built over
+them) is the QUERY_INSTANCE = true branch (poly/ipa/multiopen/prover.rs:25): instance columns are committed with Blind::default() = 1 and
+the commitments absorbed (:100-117), their evaluations written before the advice evaluations (:521-541) and opened first within each
+instance (:607-617); every commitment is MSM + [blind] W (the + [blind] W through h2hip_g1_linear_combinations_bn254 on the host), every
+query carries its commitment's blind, and ipa.ProverIPA goes on with the same FrRng.
 
 Later arguments.  The shuffle argument (upstream PSE halo2) and the logUp "mv-lookup" argument (the forks that replaced the permuted-column
 lookup) are later than the reference; both coexist with the halo2 lookup here, as they do in h2hip_evaluate_h_ext_*.  ARGUMENT_STAGES
@@ -42,7 +46,7 @@ Random draws.  Everything random comes from one FrRng(seed) (ChaCha20, one 64-by
   5. the 2^k coefficients of the vanishing argument's random polynomial, drawn in HBM (vanishing/prover.rs:50-53), then its blind (:55)
   6. one blind per piece of h(X) (vanishing/prover.rs:95-98)
 The KZG commitment ignores its blind (poly/kzg/commitment.rs:281-292), as ParamsKZG does here; the blinds are drawn to keep the stream in
-step.  A proof is valid for the verifier of verifier.py; it is not byte-identical to a Rust run, whose rng is not ChaCha20 from this seed.
+step.  The IPA commitment is MSM + [blind] W, and the opening continues the stream (ipa.py lists its draws).  A proof is valid for the verifier of verifier.py; it is not byte-identical to a Rust run, whose rng is not ChaCha20 from this seed.
 
 Residency.  With resident=True no array of 2^k or more field elements is passed to or returned by any call made here: witness() hands over
 torch CUDA tensors, which this prover blinds, commits, transforms (in place: they are consumed) and opens where they lie.  What does cross
@@ -62,7 +66,7 @@ from . import (FR_DELTA, FR_MODULUS, FR_ZETA, CopyList, EvaluationDomain, FrRng,
                keygen_columns, lib, lookup_compress, lookup_compress_device, lookup_permute_device, lookup_products, lookup_products_device,
                msm_batch_device, mvlookup_multiplicities, mvlookup_multiplicities_device, mvlookup_sums, mvlookup_sums_device,
                part_cosets_pin, part_cosets_unpin, permutation_products, permutation_products_device, poly_combine, poly_combine_device,
-               shplonk_final, shplonk_h, shuffle_products, shuffle_products_device, bases_pin_device)
+               shplonk_final, shplonk_h, shuffle_products, shuffle_products_device, bases_pin_device, g1_linear_combinations)
 from .evaluation import (ANY_ADVICE, ANY_FIXED, ANY_INSTANCE, Evaluator, expression_degree, flatten_graph, lookup_compress_graphs,
                          mvlookup_required_degree, shuffle_required_degree)
 from .transcript import point_from_bytes
@@ -189,8 +193,8 @@ class VerifyingKey:
     """plonk.rs VerifyingKey as far as verify_proof reads it: the constraint system, k, the fixed and permutation commitments (affine
     points as integer pairs) and the caller's vk_repr, which stands in for transcript_repr"""
 
-    def __init__(self, cs, k, vk_repr, fixed_commitments, permutation_commitments):
-        self.cs, self.k, self.vk_repr = cs, int(k), int(vk_repr) % FR_MODULUS
+    def __init__(self, cs, k, vk_repr, fixed_commitments, permutation_commitments, scheme="kzg"):
+        self.cs, self.k, self.vk_repr, self.scheme = cs, int(k), int(vk_repr) % FR_MODULUS, scheme  # scheme: "kzg" or "ipa" params
         self.fixed_commitments, self.permutation_commitments = list(fixed_commitments), list(permutation_commitments)
         self.cs_degree = cs.degree()
 
@@ -201,6 +205,11 @@ def points_to_ints(jacobian):
         return []
     affine = np.stack([g1_to_affine(p) for p in jacobian])
     return [point_from_bytes(row.tobytes()) for row in g1_to_bytes(affine)]
+
+
+def _is_ipa(params):
+    from . import ipa  # ipa.py imports verifier.py, which imports this module
+    return isinstance(params, ipa.ParamsIPA)
 
 
 def _lagrange_unit_columns(n, b):
@@ -219,7 +228,8 @@ class ProvingKey:
 
     @classmethod
     def build(cls, params, cs, fixed, copies_or_mapping, vk_repr, pin=True):
-        """fixed: the (2^k, 4) Lagrange columns; copies_or_mapping: a CopyList, a list or (C, 4) array of (column, row, column, row)
+        """params: a ParamsKZG, or an ipa.ParamsIPA (the key then commits with Blind::default() = 1 and shares the params' pinned
+        generators); fixed: the (2^k, 4) Lagrange columns; copies_or_mapping: a CopyList, a list or (C, 4) array of (column, row, column, row)
         copy constraints over cs.permutation, or the assembly's (m, 2^k, 2) mapping; vk_repr: the scalar the transcript starts with.
         pin: keep the part cosets (parts form) and, for the host forms, the extended cosets of the key's columns in HBM."""
         import torch
@@ -251,11 +261,20 @@ class ProvingKey:
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).cuda()  # noqa: E731
         self.dev = {key: ([up(a) for a in val] if isinstance(val, list) else up(val)) for key, val in host.items()
                     if key not in ("fixed_commitments", "permutation_commitments")}
-        self.d_g, self.d_g_lagrange = up(params.g), up(params.g_lagrange)
-        bases_pin_device(self.d_g, n)
-        bases_pin_device(self.d_g_lagrange, n)
+        self.scheme = "ipa" if _is_ipa(params) else "kzg"
+        if self.scheme == "ipa":
+            # the params' own resident, pinned generators; and commit_lagrange(col, Blind::default()) with Blind::default() = one
+            # (poly/commitment.rs:195-199, plonk/keygen.rs:249, plonk/permutation/keygen.rs:159): each key commitment is the MSM plus W
+            self.d_g, self.d_g_lagrange = params.d_g(), params.d_g_lagrange()
+            key_commitments = [g1_linear_combinations(host[name], [[1]] * len(host[name]), [params.w]) if len(host[name]) else []
+                               for name in ("fixed_commitments", "permutation_commitments")]
+        else:
+            self.d_g, self.d_g_lagrange = up(params.g), up(params.g_lagrange)
+            bases_pin_device(self.d_g, n)
+            bases_pin_device(self.d_g_lagrange, n)
+            key_commitments = [points_to_ints(host["fixed_commitments"]), points_to_ints(host["permutation_commitments"])]
         self.ev = Evaluator.new(cs.gate_polynomials(), cs.lookups, shuffle_arguments=cs.shuffles, mvlookup_arguments=cs.mv_lookups)
-        self.vk = VerifyingKey(cs, k, self.vk_repr, points_to_ints(host["fixed_commitments"]), points_to_ints(host["permutation_commitments"]))
+        self.vk = VerifyingKey(cs, k, self.vk_repr, key_commitments[0], key_commitments[1], scheme=self.scheme)
         self._pinned = False
         if pin:
             self.pin()
@@ -333,12 +352,14 @@ class _Device:
         col.view(-1, 4)[start:start + values.shape[0]] = self.torch.from_numpy(values.view(np.int64)).to(col.device)
         self.note("h2d", values.nbytes, what)
 
-    def commit(self, cols, lagrange, what):
+    def commit(self, cols, lagrange, what, blinds=None):
+        """Jacobian sums; with blinds (IPA: poly/ipa/commitment.rs:92-107, :216-227) the commitments MSM + [r] W as affine integer
+        pairs.  Either way the MSM is the _device batch and 96 B per commitment come back"""
         if not cols:
             return []
         out = msm_batch_device(cols, self.pk.d_g_lagrange if lagrange else self.pk.d_g, cols[0].numel() * cols[0].element_size() // 32)
         self.note("d2h", out.nbytes, what)
-        return list(out)
+        return list(out) if blinds is None else g1_linear_combinations(out, [[r] for r in blinds], [self.pk.params.w])
 
     def lagrange_to_coeff(self, cols):
         """in place"""
@@ -357,9 +378,9 @@ class _Device:
             coeff_to_extended_batch_device(outs, d.k, d.extended_k, d.extended_omega, d.g_coset, d.g_coset_inv)
         return outs
 
-    def commit_permuted(self, lookups, theta, blinding, fixed, advice, instance, challenges):
+    def commit_permuted(self, lookups, theta, blinding, fixed, advice, instance, challenges, blinds=None):
         """lookup::Argument::commit_permuted (lookup/prover.rs:64-158) for every lookup of one instance, the composition of the host
-        commit_permuted over the _device entry points"""
+        commit_permuted over the _device entry points; blinds as for commit, two per lookup"""
         graphs = []
         for inp, tab in lookups:
             gi, gt = lookup_compress_graphs(inp, tab)
@@ -368,7 +389,7 @@ class _Device:
         pa, pt = [self.zeros(self.n) for _ in lookups], [self.zeros(self.n) for _ in lookups]
         self.note("h2d", blinding.nbytes, "lookup blinding rows")
         lookup_permute_device(self.k, comp[0::2], comp[1::2], blinding, self.b, pa, pt)                    # :118-126
-        coms = self.commit([c for j in range(len(lookups)) for c in (pa[j], pt[j])], True, "permuted commitments")  # :129-140
+        coms = self.commit([c for j in range(len(lookups)) for c in (pa[j], pt[j])], True, "permuted commitments", blinds)  # :129-140
         polys = self.lagrange_to_coeff([c.clone() for j in range(len(lookups)) for c in (pa[j], pt[j])])
         return [{"compressed_input": comp[2 * j], "compressed_table": comp[2 * j + 1], "permuted_input": pa[j], "permuted_table": pt[j],
                  "permuted_input_commitment": coms[2 * j], "permuted_table_commitment": coms[2 * j + 1],
@@ -482,13 +503,13 @@ class _Host:
         values = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)
         col[start:start + values.shape[0]] = values
 
-    def commit(self, cols, lagrange, what):
+    def commit(self, cols, lagrange, what, blinds=None):
         if not cols:
             return []
         self._cols("h2d", cols, what + ": columns")
         out = best_multiexp_batch(cols, self.pk.params.g_lagrange if lagrange else self.pk.params.g[:cols[0].shape[0]])
         self.note("d2h", out.nbytes, what)
-        return list(out)
+        return list(out) if blinds is None else g1_linear_combinations(out, [[r] for r in blinds], [self.pk.params.w])
 
     def lagrange_to_coeff(self, cols):
         self._cols("h2d", cols, "lagrange_to_coeff")
@@ -501,10 +522,10 @@ class _Host:
         self._cols("d2h", outs, "coeff_to_extended")
         return outs
 
-    def commit_permuted(self, lookups, theta, blinding, fixed, advice, instance, challenges):
+    def commit_permuted(self, lookups, theta, blinding, fixed, advice, instance, challenges, blinds=None):
         self._cols("h2d", list(fixed) + list(advice) + list(instance), "commit_permuted: columns")
-        out = commit_permuted(self.pk.params, self.dom, lookups, theta, blinding, self.b, [None] * (2 * len(lookups)), fixed, advice, instance,
-                              challenges)
+        out = commit_permuted(self.pk.params, self.dom, lookups, theta, blinding, self.b, blinds or [None] * (2 * len(lookups)), fixed, advice,
+                              instance, challenges)
         self._cols("d2h", [c for d in out for key, c in d.items() if not key.endswith("commitment")], "commit_permuted: columns")
         return out
 
@@ -659,7 +680,24 @@ def _multiopen_shplonk(be, transcript, polys, queries):
     transcript.write_point(points_to_ints(be.commit([final], False, "final commitment (shplonk)"))[0])     # :280-281
 
 
-MULTIOPEN = {"gwc": _multiopen_gwc, "shplonk": _multiopen_shplonk}
+def _multiopen_ipa(be, transcript, rng, queries):
+    """ProverIPA::create_proof (poly/ipa/multiopen/prover.rs) over queries (point, poly, blind).  ProverIPA tells commitments apart by
+    the tensor's device address, so a polynomial is handed over as the same tensor at each of its points; a host column (resident=False)
+    is uploaded once, the first time it is queried."""
+    from . import ipa
+    if not be.resident:
+        import torch
+        uploaded = {}
+        for _, poly, _ in queries:
+            if id(poly) not in uploaded:
+                uploaded[id(poly)] = torch.from_numpy(np.ascontiguousarray(poly).view(np.int64)).cuda()
+                be.note("h2d", poly.nbytes, "opening: a queried polynomial")
+        queries = [(point, uploaded[id(poly)], blind) for point, poly, blind in queries]
+    be.note("h2d", 32 * len(queries), "opening points (ipa)")
+    ipa.ProverIPA(be.pk.params).create_proof(rng, transcript, queries)
+
+
+MULTIOPEN = {"gwc": _multiopen_gwc, "shplonk": _multiopen_shplonk}  # the KZG schemes; "ipa" is _multiopen_ipa, whose queries carry blinds
 
 
 def rotate_omega(domain, x, rotation):
@@ -676,12 +714,16 @@ def create_proof(params, pk, instances, witness, transcript, seed, multiopen="sh
     limbs; `challenges` holds the challenges of earlier phases as integers, None where not yet drawn.  The columns are consumed: their
     last blinding_factors + 1 rows are overwritten and, when resident, they are transformed in place.  transcript: a Blake2bWrite;
     seed: 32 bytes for FrRng.  Returns a Proof (bytes = transcript.finalize())."""
-    if multiopen not in MULTIOPEN:
-        raise ValueError("multiopen: 'shplonk' or 'gwc'")
+    if multiopen not in MULTIOPEN and multiopen != "ipa":
+        raise ValueError("multiopen: 'shplonk', 'gwc' or 'ipa'")
     if form not in ("parts", "full"):
         raise ValueError("form: 'parts' or 'full'")
     if pk.params is not params:
         raise ValueError("the proving key was built over other params")
+    ipa = multiopen == "ipa"                                                                               # P::QUERY_INSTANCE
+    if ipa != (pk.scheme == "ipa"):
+        raise ValueError("multiopen %r with %s params: 'ipa' goes with an ipa.ParamsIPA and a key built over it, 'shplonk' and 'gwc' with "
+                         "KZG params" % (multiopen, "IPA" if pk.scheme == "ipa" else "KZG"))
     cs, dom, k, n, b, u = pk.cs, pk.domain, pk.k, pk.n, pk.b, pk.u
     proof = Proof()
     be = (_Device if resident else _Host)(pk, proof)
@@ -694,26 +736,42 @@ def create_proof(params, pk, instances, witness, transcript, seed, multiopen="sh
         if len(inst) != cs.num_instance_columns:
             raise ValueError("InvalidInstances")
 
+    def blind():
+        """one commitment blind from the stream, as an integer (KZG ignores it, IPA commits with it)"""
+        return fr_to_int(rng.draw(1)[0])
+
+    def commit(cols, lagrange, what, blinds):
+        """the commitments of `cols` as affine integer pairs: KZG's ignore the blinds, IPA's are MSM + [blind] W"""
+        if ipa:
+            return be.commit(cols, lagrange, what, blinds=blinds)
+        return points_to_ints(be.commit(cols, lagrange, what))
+
     transcript.common_scalar(pk.vk_repr)                                                                   # :64 hash_into
 
-    # ---- instance columns (:79-132); QUERY_INSTANCE = false: the values are absorbed, nothing is committed
+    # ---- instance columns (:79-132).  QUERY_INSTANCE = false (KZG): the values are absorbed, nothing is committed; true (IPA): the
+    # values are not absorbed (:91-93), each column is committed with Blind::default() = 1 and the commitments absorbed (:100-117)
     instance_values = []
     for inst in instances:
         cols = []
         for values in inst:
             if len(values) > u:
                 raise ValueError("InstanceTooLarge")                                                       # :87-89
-            for v in values:
-                transcript.common_scalar(int(v) % FR_MODULUS)                                              # :91-93
+            if not ipa:
+                for v in values:
+                    transcript.common_scalar(int(v) % FR_MODULUS)                                          # :91-93
             col = be.zeros(n)
             if len(values):
                 be.set_rows(col, 0, np.stack([fr_from_int(v) for v in values]), "instance values")
             cols.append(col)
+        if ipa:
+            for c in commit(cols, True, "instance commitments", [1] * len(cols)):                          # :100-117, one batched MSM
+                transcript.common_point(c)
         instance_values.append(cols)
     instance_polys = [be.lagrange_to_coeff([be.clone(c) for c in cols]) for cols in instance_values]       # :119-125
 
     # ---- advice columns, phase by phase (:284-401)
     advice = [[None] * cs.num_advice_columns for _ in range(N)]
+    advice_blinds = [[None] * cs.num_advice_columns for _ in range(N)]
     challenges = {}
     for phase in cs.phases():                                                                              # :295
         column_indices = [c for c, p in enumerate(cs.advice_column_phase) if p == phase]                   # :296-307
@@ -724,13 +782,13 @@ def create_proof(params, pk, instances, witness, transcript, seed, multiopen="sh
             for col in cols:
                 be.check_column(col, n)
             rows = [rng.draw(b + 1) for _ in cols]                                                         # :350-354
-            [rng.draw(1) for _ in cols]                                                                    # :357-360 (blinds; KZG ignores them)
+            blinds = [blind() for _ in cols]                                                               # :357-360
             for col, r in zip(cols, rows):
                 be.set_rows(col, u, r, "advice blinding rows")
-            for c in points_to_ints(be.commit(cols, True, "advice commitments")):                          # :361-377
+            for c in commit(cols, True, "advice commitments", blinds):                                     # :361-377
                 transcript.write_point(c)
-            for c, col in zip(column_indices, cols):                                                       # :378-383
-                advice[i][c] = col
+            for c, col, r in zip(column_indices, cols, blinds):                                            # :378-383
+                advice[i][c], advice_blinds[i][c] = col, r
         for j, p in enumerate(cs.challenge_phase):                                                         # :386-392
             if p == phase:
                 challenges[j] = transcript.squeeze_challenge()
@@ -742,17 +800,20 @@ def create_proof(params, pk, instances, witness, transcript, seed, multiopen="sh
 
     # ---- lookups: permuted columns (:406-431)
     proof.stages.append("lookup_permuted")
-    permuted = []
+    permuted, permuted_blinds = [], []
     for i in range(N):
-        blinding = []
+        blinding, blinds = [], []
         for _ in cs.lookups:
             blinding.append(rng.draw(2 * (b + 1)))                                                         # lookup/prover.rs:391-475
-            rng.draw(2)                                                                                    # :129 (two blinds)
+            blinds += [blind(), blind()]                                                                   # :129-140 (A', then S')
         blinding = np.concatenate(blinding) if blinding else np.zeros((0, 4), dtype=np.uint64)
-        out = be.commit_permuted(cs.lookups, theta_m, blinding, key["fixed_values"], advice[i], instance_values[i], ch_mont) if cs.lookups else []
-        for c in points_to_ints([c for d in out for c in (d["permuted_input_commitment"], d["permuted_table_commitment"])]):
+        out = be.commit_permuted(cs.lookups, theta_m, blinding, key["fixed_values"], advice[i], instance_values[i], ch_mont,
+                                 blinds=blinds if ipa else None) if cs.lookups else []
+        coms = [c for d in out for c in (d["permuted_input_commitment"], d["permuted_table_commitment"])]
+        for c in coms if ipa else points_to_ints(coms):
             transcript.write_point(c)                                                                      # lookup/prover.rs:143, :146
         permuted.append(out)
+        permuted_blinds.append(blinds)
 
     # ---- mv-lookups: the compressed columns (kept until the grand sums) and the multiplicities m, committed before beta exists
     proof.stages.append("mvlookup_multiplicities")
@@ -760,10 +821,9 @@ def create_proof(params, pk, instances, witness, transcript, seed, multiopen="sh
     for inputs, tab in cs.mv_lookups:
         mv_graphs += [flatten_graph(lookup_compress_graphs(inp, tab)[0]) for inp in inputs]
         mv_graphs.append(flatten_graph(lookup_compress_graphs(inputs[0], tab)[1]))
-    mv_columns, mv_m = [], []
+    mv_columns, mv_m, mv_m_blinds = [], [], []
     for i in range(N):
-        for _ in cs.mv_lookups:
-            rng.draw(1)                                                                                    # draw 2b (blinds; KZG ignores them)
+        mv_m_blinds.append([blind() for _ in cs.mv_lookups])                                               # draw 2b
         f, t, m = [], [], []
         if cs.mv_lookups:
             comp = be.compress(mv_graphs, theta_m, key["fixed_values"], advice[i], instance_values[i], ch_mont, "mv-lookup compression")
@@ -773,7 +833,7 @@ def create_proof(params, pk, instances, witness, transcript, seed, multiopen="sh
                 t.append(comp[at + kj])
                 at += kj + 1
             m = be.mvlookup_multiplicities(f, t)
-        for c in points_to_ints(be.commit(m, True, "mv-lookup multiplicity commitments")):
+        for c in commit(m, True, "mv-lookup multiplicity commitments", mv_m_blinds[i]):
             transcript.write_point(c)
         mv_columns.append((f, t))
         mv_m.append(m)
@@ -785,45 +845,48 @@ def create_proof(params, pk, instances, witness, transcript, seed, multiopen="sh
     # ---- permutation products (:440-457, permutation/prover.rs:45-191)
     proof.stages.append("permutation_products")
     chunk_len, n_sets = cs.chunk_len(), cs.num_permutation_sets()
-    perm_polys = []
+    perm_polys, perm_blinds = [], []
     for i in range(N):
         pools = {"advice": advice[i], "fixed": key["fixed_values"], "instance": instance_values[i]}
-        blinding = []
+        blinding, blinds = [], []
         for _ in range(n_sets):
             blinding.append(rng.draw(b))                                                                   # permutation/prover.rs:162-164
-            rng.draw(1)                                                                                    # :168
+            blinds.append(blind())                                                                         # :168
         z = []
         if n_sets:
             z = be.permutation_products(beta_m, gamma_m, [pools[kind][c] for kind, c in cs.permutation], chunk_len, n_sets, np.concatenate(blinding))
-        for c in points_to_ints(be.commit(z, True, "permutation product commitments")):                    # :170-181
+        for c in commit(z, True, "permutation product commitments", blinds):                               # :170-181
             transcript.write_point(c)
         perm_polys.append(be.lagrange_to_coeff(z))                                                         # :172
+        perm_blinds.append(blinds)
 
     # ---- lookup products (:459-468, lookup/prover.rs:167-305)
     proof.stages.append("lookup_products")
-    lookup_polys = []
+    lookup_polys, lookup_blinds = [], []
     for i in range(N):
-        blinding = []
+        blinding, blinds = [], []
         for _ in cs.lookups:
             blinding.append(rng.draw(b))                                                                   # lookup/prover.rs:247
-            rng.draw(1)                                                                                    # :290
+            blinds.append(blind())                                                                         # :290
         z = be.lookup_products(beta_m, gamma_m, permuted[i], np.concatenate(blinding)) if cs.lookups else []
-        for c in points_to_ints(be.commit(z, True, "lookup product commitments")):                         # :291-295
+        for c in commit(z, True, "lookup product commitments", blinds):                                    # :291-295
             transcript.write_point(c)
         lookup_polys.append(be.lagrange_to_coeff(z))                                                       # :292
+        lookup_blinds.append(blinds)
 
     # ---- mv-lookup grand sums over the kept compressed columns and m
     proof.stages.append("mvlookup_sums")
-    mv_polys = []
+    mv_polys, mv_phi_blinds = [], []
     for i in range(N):
-        blinding = []
+        blinding, blinds = [], []
         for _ in cs.mv_lookups:
             blinding.append(rng.draw(b))                                                                   # draw 4b
-            rng.draw(1)
+            blinds.append(blind())
         (f, t), m = mv_columns[i], mv_m[i]
         phi = be.mvlookup_sums(beta_m, f, t, m, np.concatenate(blinding)) if cs.mv_lookups else []
-        for c in points_to_ints(be.commit(phi, True, "mv-lookup sum commitments")):
+        for c in commit(phi, True, "mv-lookup sum commitments", blinds):
             transcript.write_point(c)
+        mv_phi_blinds.append(blinds)
         polys = be.lagrange_to_coeff(list(phi) + list(m))
         mv_polys.append([(polys[j], polys[len(phi) + j]) for j in range(len(phi))])
         mv_columns[i] = mv_m[i] = None                                                                     # the compressed columns are done
@@ -834,24 +897,25 @@ def create_proof(params, pk, instances, witness, transcript, seed, multiopen="sh
     for inp, shf in cs.shuffles:
         gi, gs = lookup_compress_graphs(inp, shf)
         shuffle_graphs += [flatten_graph(gi), flatten_graph(gs)]
-    shuffle_polys = []
+    shuffle_polys, shuffle_blinds = [], []
     for i in range(N):
-        blinding = []
+        blinding, blinds = [], []
         for _ in cs.shuffles:
             blinding.append(rng.draw(b))                                                                   # draw 4c
-            rng.draw(1)
+            blinds.append(blind())
         z = []
         if cs.shuffles:
             comp = be.compress(shuffle_graphs, theta_m, key["fixed_values"], advice[i], instance_values[i], ch_mont, "shuffle compression")
             z = be.shuffle_products(gamma_m, comp[0::2], comp[1::2], np.concatenate(blinding))
-        for c in points_to_ints(be.commit(z, True, "shuffle product commitments")):
+        for c in commit(z, True, "shuffle product commitments", blinds):
             transcript.write_point(c)
         shuffle_polys.append(be.lagrange_to_coeff(z))
+        shuffle_blinds.append(blinds)
 
     # ---- the vanishing argument's random polynomial (:471, vanishing/prover.rs:37-65)
     random_poly = be.random_poly(rng)
-    rng.draw(1)
-    transcript.write_point(points_to_ints(be.commit([random_poly], False, "random polynomial commitment"))[0])
+    random_blind = blind()                                                                                 # vanishing/prover.rs:55-58
+    transcript.write_point(commit([random_poly], False, "random polynomial commitment", [random_blind])[0])
 
     y = transcript.squeeze_challenge()                                                                     # :474
 
@@ -886,8 +950,8 @@ def create_proof(params, pk, instances, witness, transcript, seed, multiopen="sh
     # ---- the pieces of h(X) (:516, vanishing/prover.rs:69-120)
     h_coeffs = be.extended_to_coeff(values)                                                                # :87
     h_pieces = [be.piece(h_coeffs, i) for i in range(dom.quotient_poly_degree)]                            # :90-93, views
-    [rng.draw(1) for _ in h_pieces]                                                                        # :95-98
-    for c in points_to_ints(be.commit(h_pieces, False, "h piece commitments")):                            # :101-113
+    h_blinds = [blind() for _ in h_pieces]                                                                 # :95-98
+    for c in commit(h_pieces, False, "h piece commitments", h_blinds):                                     # :101-113
         transcript.write_point(c)
 
     x = transcript.squeeze_challenge()                                                                     # :518
@@ -895,6 +959,13 @@ def create_proof(params, pk, instances, witness, transcript, seed, multiopen="sh
     x_next, x_inv, x_last = rotate_omega(dom, x, 1), rotate_omega(dom, x, -1), rotate_omega(dom, x, -(b + 1))
 
     # ---- evaluations, one call per group of polynomials, in the order the verifier reads them (:543-597)
+    instance_evals = []
+    for i in range(N if ipa else 0):                                                                       # :521-541 (QUERY_INSTANCE)
+        evs = be.evaluate(instance_polys[i], [c for c, _ in cs.instance_queries], [rotate_omega(dom, x, r) for _, r in cs.instance_queries],
+                          "instance evaluations")
+        for e in evs:
+            transcript.write_scalar(e)
+        instance_evals.append(evs)
     advice_evals = []
     for i in range(N):                                                                                     # :544-561
         evs = be.evaluate(advice_polys[i], [c for c, _ in cs.advice_queries], [rotate_omega(dom, x, r) for _, r in cs.advice_queries], "advice evaluations")
@@ -951,20 +1022,26 @@ def create_proof(params, pk, instances, witness, transcript, seed, multiopen="sh
             transcript.write_scalar(e)
         shuffle_evals.append(evs)
 
-    # ---- the opening queries (:599-645): (polynomial id, point, evaluation) with ids into `polys`
-    polys, queries = [], []
+    # ---- the opening queries (:599-645): (polynomial id, point, evaluation) with ids into `polys`; poly_blinds[id] is the blind of the
+    # polynomial's commitment, which only IPA's queries carry (KZG's commitments have none)
+    polys, poly_blinds, queries = [], [], []
 
-    def poly_id(p):
+    def poly_id(p, r=0):
         polys.append(p)
+        poly_blinds.append(r)
         return len(polys) - 1
 
-    fixed_ids = [poly_id(p) for p in key["fixed_polys"]]
-    common_ids = [poly_id(p) for p in key["perm_polys"]]
+    fixed_ids = [poly_id(p, 1) for p in key["fixed_polys"]]                                                # Blind::default() :640
+    common_ids = [poly_id(p, 1) for p in key["perm_polys"]]                                                # permutation/prover.rs:217
     for i in range(N):
-        ids = [poly_id(p) for p in advice_polys[i]]
+        if ipa:                                                                                            # :607-617, Blind::default()
+            ids = [poly_id(p, 1) for p in instance_polys[i]]
+            for q, (c, r) in enumerate(cs.instance_queries):
+                queries.append((ids[c], rotate_omega(dom, x, r), instance_evals[i][q]))
+        ids = [poly_id(p, r) for p, r in zip(advice_polys[i], advice_blinds[i])]
         for q, (c, r) in enumerate(cs.advice_queries):                                                     # :618-628
             queries.append((ids[c], rotate_omega(dom, x, r), advice_evals[i][q]))
-        ids = [poly_id(p) for p in perm_polys[i]]                                                          # :629, permutation/prover.rs:283-327
+        ids = [poly_id(p, r) for p, r in zip(perm_polys[i], perm_blinds[i])]                               # :629, permutation/prover.rs:283-327
         at = 0
         last = {}
         for t in range(n_sets):
@@ -977,24 +1054,32 @@ def create_proof(params, pk, instances, witness, transcript, seed, multiopen="sh
         for t in reversed(range(n_sets - 1)):                                                              # .rev().skip(1)
             queries.append((ids[t], x_last, last[t]))
         for j in range(len(cs.lookups)):                                                                   # :630, lookup/prover.rs:341-380
-            z_id, a_id, s_id = (poly_id(p) for p in (lookup_polys[i][j], permuted[i][j]["permuted_input_poly"], permuted[i][j]["permuted_table_poly"]))
+            z_id, a_id, s_id = (poly_id(p, r) for p, r in ((lookup_polys[i][j], lookup_blinds[i][j]),
+                                                           (permuted[i][j]["permuted_input_poly"], permuted_blinds[i][2 * j]),
+                                                           (permuted[i][j]["permuted_table_poly"], permuted_blinds[i][2 * j + 1])))
             z_x, z_next, a_x, a_inv, s_x = lookup_evals[i][5 * j:5 * j + 5]
             queries += [(z_id, x, z_x), (a_id, x, a_x), (s_id, x, s_x), (a_id, x_inv, a_inv), (z_id, x_next, z_next)]
         for j, (phi, m) in enumerate(mv_polys[i]):
-            phi_id, m_id = poly_id(phi), poly_id(m)
+            phi_id, m_id = poly_id(phi, mv_phi_blinds[i][j]), poly_id(m, mv_m_blinds[i][j])
             phi_x, phi_next, m_x = mv_evals[i][3 * j:3 * j + 3]
             queries += [(phi_id, x, phi_x), (phi_id, x_next, phi_next), (m_id, x, m_x)]
         for j, z in enumerate(shuffle_polys[i]):
-            z_id = poly_id(z)
+            z_id = poly_id(z, shuffle_blinds[i][j])
             queries += [(z_id, x, shuffle_evals[i][2 * j]), (z_id, x_next, shuffle_evals[i][2 * j + 1])]
     for q, (c, r) in enumerate(cs.fixed_queries):                                                          # :632-642
         queries.append((fixed_ids[c], rotate_omega(dom, x, r), fixed_evals[q]))
     for j in range(len(cs.permutation)):                                                                   # :643, permutation/prover.rs:210-219
         queries.append((common_ids[j], x, common_evals[j]))
-    queries.append((poly_id(h_poly), x, h_eval))                                                           # :645, vanishing/prover.rs:157-172
-    queries.append((poly_id(random_poly), x, random_eval))
+    h_blind = 0                                                                                            # vanishing/prover.rs:137-143
+    for r in reversed(h_blinds):
+        h_blind = (h_blind * xn + r) % FR_MODULUS
+    queries.append((poly_id(h_poly, h_blind), x, h_eval))                                                  # :645, vanishing/prover.rs:157-172
+    queries.append((poly_id(random_poly, random_blind), x, random_eval))
 
-    MULTIOPEN[multiopen](be, transcript, polys, queries)                                                   # :647-650
+    if ipa:                                                                                                # :647-650; the same FrRng goes on
+        _multiopen_ipa(be, transcript, rng, [(point, polys[pid], poly_blinds[pid]) for pid, point, _ in queries])
+    else:
+        MULTIOPEN[multiopen](be, transcript, polys, queries)
     proof.bytes = transcript.finalize()
     proof.challenges = {"theta": theta, "beta": beta, "gamma": gamma, "y": y, "x": x, "challenges": challenge_list}
     return proof

@@ -3,15 +3,20 @@ verifiers (plonk/permutation/verifier.rs, plonk/lookup/verifier.rs, plonk/vanish
 (poly/kzg/multiopen/gwc/verifier.rs:48-129, poly/kzg/multiopen/shplonk/verifier.rs:53-147).
 
 Scalars are integers mod r, points are (x, y) integer pairs or None (transcript.py); G1 arithmetic is the textbook Jacobian formulas
-below.  Nothing here touches the GPU or grows with 2^k: the cost is a few dozen scalar multiplications, and one field inversion per
-instance value.  verify_proof returns the two G1 points (left, right) of the reference's DualMSM (poly/kzg/msm.rs); the proof is valid
+below.  Nothing on the KZG paths touches the GPU or grows with 2^k: the cost is a few dozen scalar multiplications, and one field
+inversion per instance value.  verify_proof returns the two G1 points (left, right) of the reference's DualMSM (poly/kzg/msm.rs); the proof is valid
 iff e(left, s_g2) = e(right, g2), which the caller closes with a pairing library (pairings are out of scope here).  Both KZG verifiers
 set QUERY_INSTANCE = false: the instance values are absorbed as scalars and their evaluations computed from l_i(x) (:84-90, :176-214).
 
 The shuffle and mv-lookup (logUp) arguments are later than the reference; their commitments, evaluations, expressions and queries are
 read and built in the order prover.py's docstring fixes (mv-lookups before shuffles, both after the halo2 lookups), and their share of
-h(x) is mvlookup_expressions / shuffle_expressions below: include/halo2hip.h's fold at one point instead of one coset row."""
-from .prover import ZERO, construct_intermediate_sets_gwc, construct_intermediate_sets_shplonk
+h(x) is mvlookup_expressions / shuffle_expressions below: include/halo2hip.h's fold at one point instead of one coset row.
+
+multiopen="ipa" is the same function with QUERY_INSTANCE = true (poly/ipa/multiopen/verifier.rs:33) over ipa.py: the instance columns are
+committed (one batched MSM per proof over the params' pinned g_lagrange) instead of absorbed, their evaluations are read from the proof,
+every commitment is an ipa.Commitment handle, h_commitment an MSMIPA, and the caller's strategy closes the check with one MSM of 2^k
+terms on the GPU -- no pairing and no setup secret, so that path is accepted or rejected here, end to end."""
+from .prover import ZERO, _is_ipa, construct_intermediate_sets_gwc, construct_intermediate_sets_shplonk
 from .transcript import FQ_MODULUS, FR_MODULUS, TranscriptError
 
 R, Q = FR_MODULUS, FQ_MODULUS
@@ -281,13 +286,33 @@ MULTIOPEN = {"gwc": _verify_gwc, "shplonk": _verify_shplonk}
 
 
 # ------------------------------------------------------------------ verify_proof
-def verify_proof(params_vk, vk, instances, transcript, multiopen="shplonk"):
+def verify_proof(params_vk, vk, instances, transcript, multiopen="shplonk", strategy=None):
     """plonk/verifier.rs:27-399.  params_vk: the verifier's params (a ParamsKZG, or any object with k and g0); vk: a VerifyingKey;
     instances: as for create_proof; transcript: a Blake2bRead over the proof.  Returns (left, right), affine integer pairs (None: the
     identity).  A malformed proof -- short, a bad point encoding, a non-canonical scalar -- raises TranscriptError; instances that do
-    not fit the key raise VerifyError."""
-    if multiopen not in MULTIOPEN:
-        raise ValueError("multiopen: 'shplonk' or 'gwc'")
+    not fit the key raise VerifyError.
+
+    multiopen="ipa" (QUERY_INSTANCE = true, poly/ipa/multiopen/verifier.rs:33): params_vk is an ipa.ParamsIPA, vk the key built over
+    it, and `strategy` -- an ipa.SingleStrategy or ipa.AccumulatorStrategy -- is required: the instance columns are committed here and
+    the commitments absorbed, their evaluations read from the proof, and the opening check is
+    strategy.process(lambda msm: VerifierIPA(params).verify_proof(transcript, queries, msm)), whose value is returned (SingleStrategy
+    raises ipa.IPAError unless the proof verifies; AccumulatorStrategy returns itself for finalize()).  Nothing else closes the check:
+    an IPA opening is valid when one MSM is the identity, and the strategy evaluates it on the GPU."""
+    if multiopen != "ipa" and multiopen not in MULTIOPEN:
+        raise ValueError("multiopen: 'shplonk', 'gwc' or 'ipa'")
+    use_ipa = multiopen == "ipa"
+    if use_ipa:
+        from . import ipa  # ipa.py imports this module
+        if not isinstance(params_vk, ipa.ParamsIPA):
+            raise ValueError("multiopen 'ipa' takes an ipa.ParamsIPA")
+        if strategy is None:
+            raise ValueError("multiopen 'ipa' needs a strategy: an ipa.SingleStrategy or ipa.AccumulatorStrategy")
+    elif strategy is not None:
+        raise ValueError("strategy belongs to multiopen 'ipa': the KZG verifiers return (left, right) for the caller's pairing")
+    elif _is_ipa(params_vk):
+        raise ValueError("multiopen %r takes KZG params, not an ipa.ParamsIPA" % (multiopen,))
+    if use_ipa != (getattr(vk, "scheme", "kzg") == "ipa"):
+        raise ValueError("multiopen %r with the verifying key of %s params" % (multiopen, "IPA" if not use_ipa else "KZG"))
     cs = vk.cs
     if int(params_vk.k) != vk.k:
         raise VerifyError("the params and the verifying key differ in k")
@@ -302,11 +327,29 @@ def verify_proof(params_vk, vk, instances, transcript, multiopen="shplonk"):
     instances = [[[int(v) % R for v in values] for values in inst] for inst in instances]
     num_proofs = len(instances)                                                          # :71
 
+    instance_commitments = []
+    if use_ipa:                                                                          # :48-69: zero-padded columns, Blind::default() = 1
+        import numpy as np
+        from . import fr_from_int
+        for inst in instances:
+            cols = []
+            for values in inst:
+                col = np.zeros((n, 4), dtype=np.uint64)
+                if values:
+                    col[:len(values)] = np.stack([fr_from_int(v) for v in values])
+                cols.append(col)
+            instance_commitments.append(params_vk.commit_lagrange_many(cols, [1] * len(cols)) if cols else [])
+
     transcript.common_scalar(vk.vk_repr)                                                 # :74 hash_into
-    for inst in instances:                                                               # :84-90
-        for values in inst:
-            for v in values:
-                transcript.common_scalar(v)
+    if use_ipa:
+        for coms in instance_commitments:                                                # :76-82
+            for c in coms:
+                transcript.common_point(c)
+    else:
+        for inst in instances:                                                           # :84-90
+            for values in inst:
+                for v in values:
+                    transcript.common_scalar(v)
 
     advice_commitments = [[None] * cs.num_advice_columns for _ in range(num_proofs)]     # :94-120
     challenges = [0] * cs.num_challenges
@@ -336,18 +379,20 @@ def verify_proof(params_vk, vk, instances, transcript, multiopen="shplonk"):
     x = transcript.squeeze_challenge()                                                   # :169
     xn = pow(x, n, R)
 
-    # instance evaluations from l_i(x) (:176-214)
-    rots = [r for _, r in cs.instance_queries]
-    min_rotation, max_rotation = min([0] + rots), max([0] + rots)
-    max_instance_len = max([len(values) for inst in instances for values in inst] or [0])
-    l_i_s = dom.l_i_range(x, xn, range(-max_rotation, max_instance_len + abs(min_rotation)))
-    instance_evals = []
-    for inst in instances:
-        evs = []
-        for column, rotation in cs.instance_queries:
-            offset = max_rotation - rotation
-            evs.append(sum(v * l for v, l in zip(inst[column], l_i_s[offset:offset + len(inst[column])])) % R)
-        instance_evals.append(evs)
+    if use_ipa:                                                                          # :170-175: read, not computed
+        instance_evals = [[transcript.read_scalar() for _ in cs.instance_queries] for _ in range(num_proofs)]
+    else:                                                                                # instance evaluations from l_i(x) (:176-214)
+        rots = [r for _, r in cs.instance_queries]
+        min_rotation, max_rotation = min([0] + rots), max([0] + rots)
+        max_instance_len = max([len(values) for inst in instances for values in inst] or [0])
+        l_i_s = dom.l_i_range(x, xn, range(-max_rotation, max_instance_len + abs(min_rotation)))
+        instance_evals = []
+        for inst in instances:
+            evs = []
+            for column, rotation in cs.instance_queries:
+                offset = max_rotation - rotation
+                evs.append(sum(v * l for v, l in zip(inst[column], l_i_s[offset:offset + len(inst[column])])) % R)
+            instance_evals.append(evs)
 
     advice_evals = [[transcript.read_scalar() for _ in cs.advice_queries] for _ in range(num_proofs)]     # :217-219
     fixed_evals = [transcript.read_scalar() for _ in cs.fixed_queries]                   # :221
@@ -416,7 +461,7 @@ def verify_proof(params_vk, vk, instances, transcript, multiopen="shplonk"):
     if xn == 1:
         raise VerifyError("x lies in the domain")                                        # invert().unwrap()
     expected_h_eval = expected_h_eval * pow(xn - 1, -1, R) % R
-    h_commitment = MSM()                                                                 # :100-110
+    h_commitment = params_vk.empty_msm() if use_ipa else MSM()                           # :100-110
     for c in reversed(h_commitments):
         h_commitment.scale(xn)
         h_commitment.append_term(1, c)
@@ -425,6 +470,9 @@ def verify_proof(params_vk, vk, instances, transcript, multiopen="shplonk"):
     commitments, queries = [], []
 
     def cid(c):
+        """one id per commitment, shared by all its queries; for IPA the id's entry is the ipa.Commitment handle VerifierIPA compares"""
+        if use_ipa:
+            c = ipa.Commitment(msm=c) if isinstance(c, ipa.MSMIPA) else ipa.Commitment(point=c)
         commitments.append(c)
         return len(commitments) - 1
 
@@ -432,6 +480,10 @@ def verify_proof(params_vk, vk, instances, transcript, multiopen="shplonk"):
     fixed_ids = [cid(c) for c in vk.fixed_commitments]
     common_ids = [cid(c) for c in vk.permutation_commitments]
     for i in range(num_proofs):
+        if use_ipa:                                                                      # :343-355: instance queries first
+            ids = [cid(c) for c in instance_commitments[i]]
+            for q, (c, r) in enumerate(cs.instance_queries):
+                queries.append((ids[c], dom.rotate_omega(x, r), instance_evals[i][q]))
         ids = [cid(c) for c in advice_commitments[i]]
         for q, (c, r) in enumerate(cs.advice_queries):                                   # :356-364
             queries.append((ids[c], dom.rotate_omega(x, r), advice_evals[i][q]))
@@ -459,6 +511,15 @@ def verify_proof(params_vk, vk, instances, transcript, multiopen="shplonk"):
     queries.append((cid(h_commitment), x, expected_h_eval))                              # :388, vanishing/verifier.rs:122-137
     queries.append((cid(random_poly_commitment), x, random_eval))
 
+    if use_ipa:                                                                          # :393-398
+        handles = [(commitments[c], point, ev) for c, point, ev in queries]
+
+        def opening(msm):
+            guard = ipa.VerifierIPA(params_vk).verify_proof(transcript, handles, msm)
+            if transcript.remaining():
+                raise TranscriptError("%d bytes follow the proof" % transcript.remaining())
+            return guard
+        return strategy.process(opening)
     left, right = MULTIOPEN[multiopen](transcript, _g0(params_vk), commitments, queries)   # :393-398
     if transcript.remaining():
         raise TranscriptError("%d bytes follow the proof" % transcript.remaining())

@@ -18,7 +18,9 @@
 
 pub mod evalh;
 pub mod ffi;
+mod ffi_g1;
 mod ffi_ipa;
+pub mod g1;
 pub mod ipa;
 
 use ff::{Field, PrimeField};

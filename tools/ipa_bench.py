@@ -4,7 +4,8 @@ Per k of --ks (default 17 and 20):
   opening_resident   one commitment::create_proof from a polynomial in HBM: wall time, and -- from a second set of runs that wait after
                      every call -- the split into collapse, normalise (the engine's stage timers), the two MSMs and the fold with its
                      inner products (wall around the calls), the rest being the host between calls; the wall time of every round of the
-                     median run, whose smallest rounds are the floor a round trip per challenge sets
+                     median run, whose smallest rounds are the floor a round trip per challenge sets (round_floor_ms; the same of
+                     every timed run in round_floor_ms_runs, for the spread)
   opening_host       the same from a host polynomial (one upload)
   multiopen          ProverIPA::create_proof on the queries of config 5 (tests/opening_util.py CONFIG5_SETS, the ones tools/opening_bench.py
                      times for SHPLONK): 21 polynomials, 26 queries, 4 points.  The time includes the commitment to q' and the whole
@@ -143,6 +144,9 @@ def bench_k(h2, ipa, T, k, reps):
         mid = splits[len(splits) // 2]
         rec["opening_split"] = mid
         rec["round_floor_ms"] = min(mid["round_ms"][-4:]) if mid["round_ms"] else None
+        # the same figure and the host share of every timed run, for the run-to-run spread beside the median run's
+        rec["round_floor_ms_runs"] = [min(s["round_ms"][-4:]) for s in splits if s["round_ms"]]
+        rec["host_between_calls_ms_runs"] = [s["host_between_calls_ms"] for s in splits]
         # verification: read the proof on the host, then compute_s and the MSM over the pinned g
         proof = open_(d_poly, True)
         commitment = params.commit(d_poly, blind)

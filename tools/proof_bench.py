@@ -11,7 +11,11 @@ Every proof is verified once (Python integers; the pairing equation closed with 
 
 --arguments measures the later arguments instead: the same circuit with an mv-lookup (logUp) [a] in [sl] in place of its halo2 lookup
 and one shuffle e <-> d (d holds e's usable rows in reverse), resident and host columns, parts form, SHPLONK, beside the lookup
-circuit's same two legs in the same process (the comparison row), each with its stage times and transfer sums."""
+circuit's same two legs in the same process (the comparison row), each with its stage times and transfer sums.
+
+--multiopen ipa measures the same circuit over the IPA commitment scheme (ipa.ParamsIPA.new(k), the key built over it, multiopen="ipa",
+every proof verified by ipa.SingleStrategy -- no secret) with resident and host columns, parts form, beside the SHPLONK proof of the
+same circuit with resident columns in the same process: the like-for-like pair."""
 import json
 import os
 import random
@@ -30,7 +34,8 @@ SECRET = 0x5EC2E7
 STAGES = ("msm_total", "ntt_batch", "lookup_compress", "lookup_permute", "products", "evalh_cosets", "evalh_part_scale", "evalh_part_io",
           "evalh_gates", "evalh_gates_gen", "evalh_perm", "evalh_lookups", "evalh_lookup_gen", "eval_polynomials", "opening_eval", "opening_combine",
           "mvlookup_multiplicities", "mvlookup_sums", "evalh_mvlookups", "evalh_mvlookup_gen", "evalh_shuffles",
-          "evalh_shuffle_gen")  # "products": the one timer of the permutation, lookup and shuffle grand products
+          "evalh_shuffle_gen", "ipa_collapse", "ipa_normalize", "ipa_fold",
+          "ipa_inner_products")  # "products": the one timer of the permutation, lookup and shuffle grand products
 
 
 def to_mont(vals):
@@ -99,17 +104,19 @@ def assignment(k, b, seed=17, arguments=False):
 
 ALL_LEGS = ((True, "parts", "shplonk"), (True, "full", "shplonk"), (True, "parts", "gwc"), (False, "parts", "shplonk"), (False, "full", "shplonk"))
 ARGUMENT_LEGS = ((True, "parts", "shplonk"), (False, "parts", "shplonk"))
+IPA_LEGS = ((True, "parts", "ipa"), (False, "parts", "ipa"))
 
 
-def measure(mods, k, reps, arguments, legs):
+def measure(mods, k, reps, arguments, legs, ipa=None):
     """one circuit: its key, the median of `reps` proofs per leg (each leg's proof verified, the legs' bytes compared), and the stage
-    times of one profiled proof with resident and with host columns (parts form, SHPLONK)"""
+    times of one profiled proof with resident and with host columns (parts form; SHPLONK, or IPA when `ipa` is the ipa module and the
+    legs are IPA's)"""
     import torch
     h2, prover, verifier, tr = mods
     cs = circuit(prover, arguments)
     t0 = time.perf_counter()
     fixed, advice, copies = assignment(k, cs.blinding_factors(), arguments=arguments)
-    params = h2.ParamsKZG.setup(k, SECRET)
+    params = ipa.ParamsIPA.new(k) if ipa else h2.ParamsKZG.setup(k, SECRET)
     pk = prover.ProvingKey.build(params, cs, fixed, copies, 0x17)
     setup_s = time.perf_counter() - t0
     d_advice = [torch.from_numpy(a.view(np.int64)).cuda() for a in advice]
@@ -132,17 +139,23 @@ def measure(mods, k, reps, arguments, legs):
         for _ in range(reps):
             ms, proof = prove(resident, form, multiopen)
             ts.append(ms)
-        left, right = verifier.verify_proof(params, pk.vk, [[]], tr.Blake2bRead(proof.bytes), multiopen)
-        assert g1_mul(left, SECRET) == right, "the verifier rejects the proof"
+        t_verify = time.perf_counter()
+        if ipa:  # SingleStrategy raises unless the opening's MSM is the identity
+            verifier.verify_proof(params, pk.vk, [[]], tr.Blake2bRead(proof.bytes), multiopen, strategy=ipa.SingleStrategy(params))
+        else:
+            left, right = verifier.verify_proof(params, pk.vk, [[]], tr.Blake2bRead(proof.bytes), multiopen)
+            assert g1_mul(left, SECRET) == right, "the verifier rejects the proof"
+        verify_ms = (time.perf_counter() - t_verify) * 1e3
         assert reference_bytes.setdefault(multiopen, proof.bytes) == proof.bytes, "the legs' proofs differ"
         name = "%s_%s_%s" % ("resident" if resident else "host", form, multiopen)
         out["legs"][name] = {"ms": round(sorted(ts)[len(ts) // 2], 3), "reps_ms": [round(t, 3) for t in ts], "proof_bytes": len(proof.bytes),
                              "h2d_bytes": proof.total("h2d"), "d2h_bytes": proof.total("d2h"),
-                             "largest_transfer": max(proof.transfers, key=lambda t: t[1])}
+                             "largest_transfer": max(proof.transfers, key=lambda t: t[1]), "verify_ms": round(verify_ms, 3)}
+    scheme = "ipa" if ipa else "shplonk"
     h2.profile_enable(True)
-    for resident in (True, False):
+    for resident in sorted({resident for resident, _, _ in legs}, reverse=True):
         h2.profile_reset()
-        prove(resident, "parts", "shplonk")
+        prove(resident, "parts", scheme)
         stages = {}
         for s in STAGES:
             try:
@@ -151,9 +164,11 @@ def measure(mods, k, reps, arguments, legs):
                 continue
             if cnt:
                 stages[s] = {"ms": round(ms, 4), "count": cnt}
-        out["stages_%s_parts_shplonk" % ("resident" if resident else "host")] = stages
+        out["stages_%s_parts_%s" % ("resident" if resident else "host", scheme)] = stages
     h2.profile_enable(False)
     pk.close()
+    if ipa:
+        params.close()
     return out
 
 
@@ -166,7 +181,13 @@ def main():
     h2.init()
     mods = (h2,) + tuple(importlib.import_module("halo2_pse_amd." + m) for m in ("prover", "verifier", "transcript"))
     out = {"k": k, "reps": reps, "stat": "median, host clock around create_proof, stream synchronised"}
-    if "--arguments" in args:
+    if "--multiopen" in args:
+        if args[args.index("--multiopen") + 1] != "ipa":
+            raise SystemExit("--multiopen ipa (the KZG schemes are the default run's legs)")
+        ipa = importlib.import_module("halo2_pse_amd.ipa")
+        out["circuits"] = {"shplonk": measure(mods, k, reps, False, ((True, "parts", "shplonk"),)),
+                           "ipa": measure(mods, k, reps, False, IPA_LEGS, ipa=ipa)}
+    elif "--arguments" in args:
         out["circuits"] = {name: measure(mods, k, reps, arguments, ARGUMENT_LEGS) for name, arguments in (("lookup", False), ("mvlookup_shuffle", True))}
     else:
         res = measure(mods, k, reps, False, ALL_LEGS)
