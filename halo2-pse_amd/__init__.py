@@ -7,7 +7,8 @@ reference (halo2_proofs::arithmetic::{best_multiexp, best_fft}, poly::Evaluation
 poly::kzg::ParamsKZG).  There is no CPU fallback here: if the library or the GPU is
 missing, calls raise.
 
-Every entry point's prototype is stated once, in _abi.py, _abi_ipa.py and _abi_g1.py (generated from the headers by tools/gen_ctypes_abi.py) and
+Every entry point's prototype is stated once, in _abi.py, _abi_ipa.py, _abi_g1.py and _abi_pairing.py (generated from the headers by
+tools/gen_ctypes_abi.py) and
 bound by lib(): call sites pass plain Python ints and bools for the by-value parameters, and ctypes refuses a wrong argument count.
 
 Arrays: numpy uint64 -- Fr elements (n,4), G1Affine (n,8), G1 Jacobian (12,): 4 x u64 LE limbs,
@@ -22,6 +23,7 @@ import numpy as np
 from ._abi import PROTOTYPES
 from ._abi_g1 import PROTOTYPES as PROTOTYPES_G1
 from ._abi_ipa import PROTOTYPES as PROTOTYPES_IPA
+from ._abi_pairing import PROTOTYPES as PROTOTYPES_PAIRING
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HALO2_HIP_LIB") or os.path.join(_HERE, "libhalo2hip.so")  # HALO2_HIP_LIB: another build of the library (A/B measurements)
@@ -61,8 +63,10 @@ def lib():
         # each parameter an input (paramflags) makes the count exact.  Another build (HALO2_HIP_LIB) may lack a name; tests/test_abi.py
         # holds the in-tree one to all of them.
         # The inner-product argument's entry points (include/halo2hip_ipa.h) have a table of their own, _abi_ipa.py, applied after the first; the host group
-        # sums (include/halo2hip_g1.h) have _abi_g1.py, applied after those two.
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(PROTOTYPES_IPA.items()) + list(PROTOTYPES_G1.items()):
+        # sums (include/halo2hip_g1.h) have _abi_g1.py, applied after those two; the host pairing (include/halo2hip_pairing.h) has
+        # _abi_pairing.py, applied last.
+        for name, (restype, argtypes) in (list(PROTOTYPES.items()) + list(PROTOTYPES_IPA.items()) + list(PROTOTYPES_G1.items()) +
+                                          list(PROTOTYPES_PAIRING.items())):
             try:
                 fn = ctypes.CFUNCTYPE(restype, *argtypes)((name, L), ((1,),) * len(argtypes))
             except AttributeError:
@@ -1616,6 +1620,27 @@ def write_polynomial_slice(polys, writer, format):
 
 
 # ------------------------------------------------------------------ poly/kzg/commitment.rs
+# EIP-197's generator of G2 as 128 raw bytes (x.c0 || x.c1 || y.c0 || y.c1, Montgomery): G2Affine::generator()
+G2_GENERATOR = b"".join((c * _FQ_R % FQ_MODULUS).to_bytes(32, "little") for c in (
+    0x1800deef121f1e76426a00665e5c4479674322d4f75edadd46debd5cd992f6ed, 0x198e9393920d483a7260bfb731fb5d25f1aa493335a9e71297e485b7aef312c2,
+    0x12c85ea5db8c6deb4aab71808dcb408fe3d1e7690c43d37b4ce6cc0166fa7daa, 0x090689d0585ff075ec9e99ad690c3395bc4b313370b38ef355acdadcd122975b))
+
+
+class ParamsStructure:
+    """what ParamsKZG.check_structure found: `failed` names the relations that do not hold (of "identity", "subgroup", "pairing",
+    "powers", "lagrange"); true when none failed"""
+
+    def __init__(self, failed):
+        self.failed = tuple(failed)
+        self.ok = not self.failed
+
+    def __bool__(self):
+        return self.ok
+
+    def __repr__(self):
+        return "ParamsStructure(ok)" if self.ok else "ParamsStructure(failed: %s)" % ", ".join(self.failed)
+
+
 class ParamsKZG:
     """poly::kzg::commitment::ParamsKZG<Bn256> (poly/kzg/commitment.rs:22-30): g and g_lagrange
     are pinned on the GPU for the life of the object; commit / commit_lagrange are
@@ -1623,7 +1648,7 @@ class ParamsKZG:
 
     def __init__(self, k, g, g_lagrange=None, g2=None, s_g2=None):
         """g_lagrange None: derived from g with g_to_lagrange, as downsize does (:274).  g2 / s_g2: the verifier's two G2 points, 128 raw
-        bytes each (x.c0 || x.c1 || y.c0 || y.c1, Montgomery), carried for read / write only; zeros (the identity) when not given"""
+        bytes each (x.c0 || x.c1 || y.c0 || y.c1, Montgomery), which kzg.DualMSM.check pairs with; zeros (the identity) when not given"""
         self.k, self.n = int(k), 1 << int(k)
         self.g = _u64(g, 8).copy()
         self.g_lagrange = g_to_lagrange(self.g, self.k) if g_lagrange is None else _u64(g_lagrange, 8).copy()
@@ -1713,7 +1738,8 @@ class ParamsKZG:
     @classmethod
     def setup(cls, k, secret):
         """ParamsKZG::setup (poly/kzg/commitment.rs:61-129) with the secret given (an int, or 4 Montgomery limbs) instead
-        of drawn from an rng: g[i] = [s^i] G1, g_lagrange[i] = [l_i(s)] G1, computed on the GPU"""
+        of drawn from an rng: g[i] = [s^i] G1, g_lagrange[i] = [l_i(s)] G1, computed on the GPU; g2 = the generator of G2 and
+        s_g2 = [s] g2 (:118-119), on the host (h2hip_g2_mul_bn254)"""
         if not 0 <= int(k) <= FR_S:
             raise H2HipError("kzg_setup: assertion failed: k <= Fr::S")  # :64 (before any allocation of 2^k points)
         s = fr_from_int(secret) if isinstance(secret, int) else _fe(secret)
@@ -1721,7 +1747,9 @@ class ParamsKZG:
         g = np.zeros((n, 8), dtype=np.uint64)
         gl = np.zeros((n, 8), dtype=np.uint64)
         _check(lib().h2hip_kzg_setup_bn254(k, _p(s), _p(g), _p(gl)), "h2hip_kzg_setup_bn254")
-        return cls(k, g, gl)
+        s_g2 = np.zeros(16, dtype=np.uint64)
+        _check(lib().h2hip_g2_mul_bn254(_p(np.frombuffer(G2_GENERATOR, dtype=np.uint64)), _p(s), _p(s_g2)), "h2hip_g2_mul_bn254")
+        return cls(k, g, gl, G2_GENERATOR, s_g2.tobytes())
 
     def commit_lagrange(self, poly, blind=None):
         poly = _u64(poly, 4)
@@ -1741,9 +1769,8 @@ class ParamsKZG:
         assert self.g.shape[0] >= size  # :332
         return self._msm(poly, self.g, self._d_g)
 
-    def commit_device(self, d_poly, n=None):
-        """commit for a coefficient polynomial that lives in HBM (n x 32 B): an MSM over g resident in HBM and pinned by its device
-        pointer -- read_custom's copy, or one uploaded at the first call and kept until close"""
+    def _resident_g(self):
+        """g in HBM, pinned by its device pointer: read_custom's copy, or one uploaded at the first call and kept until close"""
         d_g = self._d_g
         if d_g is None:
             d_g = getattr(self, "_d_g_resident", None)
@@ -1752,7 +1779,77 @@ class ParamsKZG:
                 d_g = torch.from_numpy(self.g.view(np.int64)).cuda()
                 bases_pin_device(d_g, self.n)
                 self._d_g_resident = d_g
-        return msm_device(d_poly, d_g, n)
+        return d_g
+
+    def commit_device(self, d_poly, n=None):
+        """commit for a coefficient polynomial that lives in HBM (n x 32 B): an MSM over g resident in HBM and pinned by its device
+        pointer -- read_custom's copy, or one uploaded at the first call and kept until close"""
+        return msm_device(d_poly, self._resident_g(), n)
+
+    def check_structure(self, seed, timings=None):
+        """Is this a structured reference string?  A file's points are checked one by one when it is read; this checks the three
+        relations between them, with randomness drawn from FrRng(seed) (32 bytes), and returns a ParamsStructure that names what
+        failed.  The MSMs, the draws and the transform run on the GPU, the pairings on the host.
+          (a) "identity": g[0], g2 or s_g2 is the identity; "subgroup": g2 or s_g2 is not on the twist or not in the subgroup of
+              order r.  When (a) fails the pairing checks of (b) are not made (the library refuses such points).
+          (b) "pairing": e(g[0], s_g2) != e(g[1], g2) -- s_g2 does not carry the s of g; "powers": with rho_i, i < n - 1, drawn in HBM,
+              A = sum rho_i g[i] and B = sum rho_i g[i + 1] (two device MSMs), e(A, s_g2) != e(B, g2) -- g is not the powers of one s.
+              "powers" is judged only when "pairing" holds.  B's bases are a device-to-device copy of g[1..n): the MSM takes its bases
+              at a buffer's own alignment and that copy is not pinned.
+          (c) "lagrange": with c of n elements drawn, commit_lagrange(c) != commit(lagrange_to_coeff(c)) -- g_lagrange is not g's
+              Lagrange basis.
+        At k = 0 there is no g[1]: (b) is vacuous, nothing ties s_g2 to g, and only (a) and (c) are checked.
+        timings: a dict that receives the host-clock milliseconds of the "pairing" calls, of (b)'s draw and two "msm"s and of (c)'s
+        "transform" and its two "commit"s (tools/pairing_bench.py)."""
+        import ctypes
+        import time
+        import torch
+        rng = FrRng(seed)
+        spent = {"pairing": 0.0, "msm": 0.0, "transform": 0.0, "commit": 0.0}
+
+        def clock(what, f):
+            t = time.perf_counter()
+            out = f()
+            spent[what] += (time.perf_counter() - t) * 1e3
+            return out
+        n, failed = self.n, []
+        g2s = [np.frombuffer(bytes(pt), dtype=np.uint64) for pt in (self.g2, self.s_g2)]
+        if not self.g[0].any() or not all(pt.any() for pt in g2s):
+            failed.append("identity")
+        for pt in g2s:
+            on, sub = ctypes.c_int(0), ctypes.c_int(0)
+            rc = lib().h2hip_g2_check_bn254(_p(pt), ctypes.byref(on), ctypes.byref(sub))
+            if (rc or not (on.value and sub.value)) and "subgroup" not in failed:
+                failed.append("subgroup")
+        if n > 1 and not failed:
+            g2_pair = np.stack([g2s[1], g2s[0]])                      # s_g2, g2
+
+            def holds(a, b):
+                """e(a, s_g2) e(-b, g2) = 1; -b negates y, on Montgomery limbs as on the value"""
+                pts = np.stack([a, b])
+                y = int.from_bytes(pts[1, 4:].tobytes(), "little")
+                pts[1, 4:] = np.frombuffer((-y % FQ_MODULUS).to_bytes(32, "little"), dtype=np.uint64)
+                ok = ctypes.c_int(0)
+                _check(clock("pairing", lambda: lib().h2hip_pairing_check_bn254(_p(pts), _p(g2_pair), 2, ctypes.byref(ok))),
+                       "h2hip_pairing_check_bn254")
+                return ok.value == 1
+            if not holds(self.g[0], self.g[1]):
+                failed.append("pairing")
+            else:
+                d_g = self._resident_g()
+                d_shifted = d_g.reshape(-1)[8:8 * n].clone()          # g[1..n) at its own buffer's start
+                d_rho = rng.draw_device(n - 1)
+                a, b = clock("msm", lambda: (g1_to_affine(msm_device(d_rho, d_g, n - 1)), g1_to_affine(msm_device(d_rho, d_shifted, n - 1))))
+                if not holds(a, b):
+                    failed.append("powers")
+        c = rng.draw(n)
+        domain = EvaluationDomain.new(2, self.k)
+        coeff = c if self.k == 0 else clock("transform", lambda: domain.lagrange_to_coeff(c))
+        if not clock("commit", lambda: np.array_equal(g1_to_affine(self.commit_lagrange(c)), g1_to_affine(self.commit(coeff)))):
+            failed.append("lagrange")
+        if timings is not None:
+            timings.update(spent)
+        return ParamsStructure(failed)
 
     def downsize(self, k):
         """ParamsKZG::downsize (poly/kzg/commitment.rs:267-275)"""

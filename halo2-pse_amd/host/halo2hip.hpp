@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/halo2hip.h"
+#include "../../include/halo2hip_pairing.h"
 #include "../csrc/ec.h"  // host-side Fr / Fq / G1 arithmetic for domain constants and SRS checks (no HIP needed)
 
 namespace halo2_proofs {
@@ -142,6 +143,22 @@ inline bool fq2_sqrt(const Fq2& a, Fq2* r) {
         return true;
     }
     return false;
+}
+// G2Affine::generator(): EIP-197's generator, raw
+inline std::array<uint8_t, 128> g2_generator() {
+    static const uint32_t canonical[4][8] = {
+        {0xd992f6edu, 0x46debd5cu, 0xf75edaddu, 0x674322d4u, 0x5e5c4479u, 0x426a0066u, 0x121f1e76u, 0x1800deefu},   // x.c0
+        {0xaef312c2u, 0x97e485b7u, 0x35a9e712u, 0xf1aa4933u, 0x31fb5d25u, 0x7260bfb7u, 0x920d483au, 0x198e9393u},   // x.c1
+        {0x66fa7daau, 0x4ce6cc01u, 0x0c43d37bu, 0xe3d1e769u, 0x8dcb408fu, 0x4aab7180u, 0xdb8c6debu, 0x12c85ea5u},   // y.c0
+        {0xd122975bu, 0x55acdadcu, 0x70b38ef3u, 0xbc4b3133u, 0x690c3395u, 0xec9e99adu, 0x585ff075u, 0x090689d0u}};  // y.c1
+    std::array<uint8_t, 128> raw;
+    for (int i = 0; i < 4; i++) {
+        Fe c;
+        std::memcpy(c.l, canonical[i], 32);
+        const Fe m = h2::fe_from_canonical<Q>(c);
+        std::memcpy(raw.data() + 32 * i, m.l, 32);
+    }
+    return raw;
 }
 inline bool all_zero(const uint8_t* p, size_t n) {
     for (size_t i = 0; i < n; i++)
@@ -567,7 +584,7 @@ class ParamsKZG {
     uint32_t k = 0;
     uint64_t n = 0;
     std::vector<G1Affine> g, g_lagrange;
-    std::array<uint8_t, 128> g2{}, s_g2{};  // raw bytes, carried for read / write only (pairing is not on this path)
+    std::array<uint8_t, 128> g2{}, s_g2{};  // raw bytes: what poly::kzg::DualMSM::check (kzg.hpp) pairs with
 
     ParamsKZG() = default;
     ParamsKZG(const ParamsKZG&) = delete;
@@ -576,7 +593,7 @@ class ParamsKZG {
 
     // setup (poly/kzg/commitment.rs:61-129) with the secret supplied: the reference draws `s` from its rng argument
     // (:72, "MUST NOT be used in production"); everything after that line is what runs here, on the GPU.
-    // g2 / s_g2 (:118-119) are the verifier's half and stay zero.
+    // g2 = G2Affine::generator() and s_g2 = [s] g2 (:118-119) on the host (h2hip_g2_mul_bn254).
     static void setup(uint32_t k, const Fr& s, ParamsKZG& p) {
         if (k > Fr::S) throw std::logic_error("assertion failed: k <= E::Scalar::S");  // :64
         p.unpin();
@@ -585,6 +602,11 @@ class ParamsKZG {
         p.g.resize(p.n);
         p.g_lagrange.resize(p.n);
         engine_check(h2hip_kzg_setup_bn254(k, s.l, p.g[0].x, p.g_lagrange[0].x), "h2hip_kzg_setup_bn254");
+        p.g2 = serde::g2_generator();
+        uint64_t in[16], out[16];
+        std::memcpy(in, p.g2.data(), 128);
+        engine_check(h2hip_g2_mul_bn254(in, s.l, out), "h2hip_g2_mul_bn254");
+        std::memcpy(p.s_g2.data(), out, 128);
         p.pin();
     }
     // the reference's signature: `rng` is any callable returning an Fr (<E::Scalar>::random(rng), :72)
@@ -1382,3 +1404,4 @@ inline ShplonkQuotients shplonk(const std::vector<RotationSet>& sets, const Fr& 
 }  // namespace halo2_proofs
 
 #include "ipa.hpp"  // transcript::Blake2b{Write,Read} and poly::ipa, the inner-product-argument commitment scheme
+#include "kzg.hpp"  // poly::kzg::{MSMKZG, DualMSM, GuardKZG, SingleStrategy, AccumulatorStrategy}: the pairing that closes a KZG check

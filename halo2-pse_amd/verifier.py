@@ -4,9 +4,11 @@ verifiers (plonk/permutation/verifier.rs, plonk/lookup/verifier.rs, plonk/vanish
 
 Scalars are integers mod r, points are (x, y) integer pairs or None (transcript.py); G1 arithmetic is the textbook Jacobian formulas
 below.  Nothing on the KZG paths touches the GPU or grows with 2^k: the cost is a few dozen scalar multiplications, and one field
-inversion per instance value.  verify_proof returns the two G1 points (left, right) of the reference's DualMSM (poly/kzg/msm.rs); the proof is valid
-iff e(left, s_g2) = e(right, g2), which the caller closes with a pairing library (pairings are out of scope here).  Both KZG verifiers
-set QUERY_INSTANCE = false: the instance values are absorbed as scalars and their evaluations computed from l_i(x) (:84-90, :176-214).
+inversion per instance value.  The proof is valid iff e(left, s_g2) = e(right, g2) for the two channels of the reference's DualMSM
+(poly/kzg/msm.rs).  With a kzg.SingleStrategy or kzg.AccumulatorStrategy the multiopen verifier adds its terms, unevaluated, to the
+strategy's DualMSM and the strategy closes the check with the library's host pairing (kzg.py, include/halo2hip_pairing.h): the proof is
+accepted or refused here, without the setup secret.  Without a strategy verify_proof returns the two G1 points (left, right).  Both KZG
+verifiers set QUERY_INSTANCE = false: the instance values are absorbed as scalars and their evaluations computed from l_i(x) (:84-90, :176-214).
 
 The shuffle and mv-lookup (logUp) arguments are later than the reference; their commitments, evaluations, expressions and queries are
 read and built in the order prover.py's docstring fixes (mv-lookups before shuffles, both after the halo2 lookups), and their share of
@@ -201,7 +203,7 @@ def _commitment_msm(commitments, cid, factor):
 
 
 def _verify_gwc(transcript, g0, commitments, queries):
-    """VerifierGWC::verify_proof (gwc/verifier.rs:48-129) -> (left, right)"""
+    """VerifierGWC::verify_proof (gwc/verifier.rs:48-129) -> the terms it adds to a DualMSM's (left, right), unevaluated"""
     v = transcript.squeeze_challenge()                                                   # :62
     groups = construct_intermediate_sets_gwc(queries)                                    # :64
     w = [transcript.read_point() for _ in groups]                                        # :66-68
@@ -224,7 +226,7 @@ def _verify_gwc(transcript, g0, commitments, queries):
     right.add_msm(witness_with_aux)                                                      # :123
     right.add_msm(commitment_multi)                                                      # :124
     right.append_term(-eval_multi, g0)                                                   # :125-126
-    return witness.eval(), right.eval()                                                  # :121
+    return witness, right                                                                # :121
 
 
 def _interpolate_eval(points, evals, u):
@@ -248,7 +250,7 @@ def _vanishing(points, u):
 
 
 def _verify_shplonk(transcript, g0, commitments, queries):
-    """VerifierSHPLONK::verify_proof (shplonk/verifier.rs:53-147) -> (left, right)"""
+    """VerifierSHPLONK::verify_proof (shplonk/verifier.rs:53-147) -> the terms it adds to a DualMSM's (left, right), unevaluated"""
     rotation_sets, super_point_set = construct_intermediate_sets_shplonk(queries)        # :67-71
     y = transcript.squeeze_challenge()                                                   # :73
     v = transcript.squeeze_challenge()                                                   # :74
@@ -279,18 +281,25 @@ def _verify_shplonk(transcript, g0, commitments, queries):
     outer.append_term(-r_outer_acc, g0)                                                  # :135-136
     outer.append_term(-z_0, h1)                                                          # :137
     outer.append_term(u, h2)                                                             # :138
-    return h2, outer.eval()                                                              # :140-144
+    return MSM([(1, h2)]), outer                                                         # :140-144
 
 
 MULTIOPEN = {"gwc": _verify_gwc, "shplonk": _verify_shplonk}
+
+
+def _is_kzg_strategy(strategy):
+    from . import kzg  # kzg.py imports this module
+    return isinstance(strategy, kzg.STRATEGIES)
 
 
 # ------------------------------------------------------------------ verify_proof
 def verify_proof(params_vk, vk, instances, transcript, multiopen="shplonk", strategy=None):
     """plonk/verifier.rs:27-399.  params_vk: the verifier's params (a ParamsKZG, or any object with k and g0); vk: a VerifyingKey;
     instances: as for create_proof; transcript: a Blake2bRead over the proof.  Returns (left, right), affine integer pairs (None: the
-    identity).  A malformed proof -- short, a bad point encoding, a non-canonical scalar -- raises TranscriptError; instances that do
-    not fit the key raise VerifyError.
+    identity), when strategy is None.  With strategy a kzg.SingleStrategy or kzg.AccumulatorStrategy over params that carry g2 and s_g2,
+    the value of strategy.process(...) is returned instead: SingleStrategy raises VerifyError unless e(left, s_g2) = e(right, g2) and
+    returns None, AccumulatorStrategy returns itself for finalize().  A malformed proof -- short, a bad point encoding, a non-canonical
+    scalar -- raises TranscriptError; instances that do not fit the key raise VerifyError.
 
     multiopen="ipa" (QUERY_INSTANCE = true, poly/ipa/multiopen/verifier.rs:33): params_vk is an ipa.ParamsIPA, vk the key built over
     it, and `strategy` -- an ipa.SingleStrategy or ipa.AccumulatorStrategy -- is required: the instance columns are committed here and
@@ -301,13 +310,17 @@ def verify_proof(params_vk, vk, instances, transcript, multiopen="shplonk", stra
     if multiopen != "ipa" and multiopen not in MULTIOPEN:
         raise ValueError("multiopen: 'shplonk', 'gwc' or 'ipa'")
     use_ipa = multiopen == "ipa"
+    if not use_ipa and strategy is not None:
+        from . import kzg  # kzg.py imports this module
     if use_ipa:
         from . import ipa  # ipa.py imports this module
         if not isinstance(params_vk, ipa.ParamsIPA):
             raise ValueError("multiopen 'ipa' takes an ipa.ParamsIPA")
         if strategy is None:
             raise ValueError("multiopen 'ipa' needs a strategy: an ipa.SingleStrategy or ipa.AccumulatorStrategy")
-    elif strategy is not None:
+        if _is_kzg_strategy(strategy):
+            raise ValueError("a kzg strategy belongs to multiopen 'shplonk' or 'gwc': multiopen 'ipa' takes an ipa strategy")
+    elif strategy is not None and not _is_kzg_strategy(strategy):
         raise ValueError("strategy belongs to multiopen 'ipa': the KZG verifiers return (left, right) for the caller's pairing")
     elif _is_ipa(params_vk):
         raise ValueError("multiopen %r takes KZG params, not an ipa.ParamsIPA" % (multiopen,))
@@ -520,7 +533,17 @@ def verify_proof(params_vk, vk, instances, transcript, multiopen="shplonk", stra
                 raise TranscriptError("%d bytes follow the proof" % transcript.remaining())
             return guard
         return strategy.process(opening)
-    left, right = MULTIOPEN[multiopen](transcript, _g0(params_vk), commitments, queries)   # :393-398
+    if strategy is not None:                                                             # :393-398
+
+        def opening(msm_accumulator):
+            left, right = MULTIOPEN[multiopen](transcript, _g0(params_vk), commitments, queries)
+            if transcript.remaining():
+                raise TranscriptError("%d bytes follow the proof" % transcript.remaining())
+            msm_accumulator.left.add_msm(left)                                           # gwc/verifier.rs:121, shplonk/verifier.rs:140-142
+            msm_accumulator.right.add_msm(right)                                         # gwc/verifier.rs:123-126, shplonk/verifier.rs:144
+            return kzg.GuardKZG(msm_accumulator)
+        return strategy.process(opening)
+    left, right = MULTIOPEN[multiopen](transcript, _g0(params_vk), commitments, queries)
     if transcript.remaining():
         raise TranscriptError("%d bytes follow the proof" % transcript.remaining())
-    return left, right
+    return left.eval(), right.eval()

@@ -20,8 +20,10 @@ pub mod evalh;
 pub mod ffi;
 mod ffi_g1;
 mod ffi_ipa;
+mod ffi_pairing;
 pub mod g1;
 pub mod ipa;
+pub mod pairing;
 
 use ff::{Field, PrimeField};
 use halo2curves::bn256::{Fr, G1Affine, G1};
