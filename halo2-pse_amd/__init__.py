@@ -7,7 +7,7 @@ reference (halo2_proofs::arithmetic::{best_multiexp, best_fft}, poly::Evaluation
 poly::kzg::ParamsKZG).  There is no CPU fallback here: if the library or the GPU is
 missing, calls raise.
 
-Every entry point's prototype is stated once, in _abi.py, _abi_ipa.py, _abi_g1.py and _abi_pairing.py (generated from the headers by
+Every entry point's prototype is stated once, in _abi.py, _abi_ipa.py, _abi_ipa_round.py, _abi_g1.py and _abi_pairing.py (generated from the headers by
 tools/gen_ctypes_abi.py) and
 bound by lib(): call sites pass plain Python ints and bools for the by-value parameters, and ctypes refuses a wrong argument count.
 
@@ -23,6 +23,7 @@ import numpy as np
 from ._abi import PROTOTYPES
 from ._abi_g1 import PROTOTYPES as PROTOTYPES_G1
 from ._abi_ipa import PROTOTYPES as PROTOTYPES_IPA
+from ._abi_ipa_round import PROTOTYPES as PROTOTYPES_IPA_ROUND
 from ._abi_pairing import PROTOTYPES as PROTOTYPES_PAIRING
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -64,9 +65,9 @@ def lib():
         # holds the in-tree one to all of them.
         # The inner-product argument's entry points (include/halo2hip_ipa.h) have a table of their own, _abi_ipa.py, applied after the first; the host group
         # sums (include/halo2hip_g1.h) have _abi_g1.py, applied after those two; the host pairing (include/halo2hip_pairing.h) has
-        # _abi_pairing.py, applied last.
+        # _abi_pairing.py, applied after those; the round as one call (include/halo2hip_ipa_round.h) has _abi_ipa_round.py, applied last.
         for name, (restype, argtypes) in (list(PROTOTYPES.items()) + list(PROTOTYPES_IPA.items()) + list(PROTOTYPES_G1.items()) +
-                                          list(PROTOTYPES_PAIRING.items())):
+                                          list(PROTOTYPES_PAIRING.items()) + list(PROTOTYPES_IPA_ROUND.items())):
             try:
                 fn = ctypes.CFUNCTYPE(restype, *argtypes)((name, L), ((1,),) * len(argtypes))
             except AttributeError:

@@ -382,6 +382,7 @@ struct Tuning {
     uint32_t open_rows = 0, open_threads = 0;  // opening: forced tile shape, rows per thread and threads per tile (0 = by size)
     size_t keygen_group_bytes = (size_t)1 << 30;  // HBM one group of columns of a host-pointer keygen call may take (two groups are alive)
     size_t ipa_quad_max_half = (size_t)1 << 13;  // h2hip_ipa_set_collapse_quad: a collapse of at most this many points per half takes one quad of lanes per point
+    bool ipa_round_call = true;  // h2hip_ipa_set_round_call: the wrappers' openings run one h2hip_ipa_round call per round, or the separate calls
     size_t random_min_n = 0;  // element count from which the host forms of the randomness go to the device (0 = HALO2_HIP_RANDOM_MIN_N or its default, random.hip)
 };
 const Tuning& tune();
@@ -703,6 +704,9 @@ int check_gates_enqueue(Ctx* c, uint32_t k, const Fe* const* fixed, uint32_t n_f
 int msm_device(Ctx* c, const Fe* d_scalars, const Affine* d_bases, size_t n, XYZZ* h_out, hipStream_t s, const MsmTable* tab = nullptr);
 int msm_batch_device(Ctx* c, const Fe* const* scalars, bool scalars_on_host, const Affine* d_bases, size_t n, size_t count, XYZZ* h_out,
                      hipStream_t s, const MsmTable* tab = nullptr, const Affine* h_bases = nullptr);
+// the two MSMs of an IPA round over p (2 half scalars) and g (2 half points) -> h_out[0] = L, h_out[1] = R; waits for s once
+int msm_pair_device(Ctx* c, const Fe* d_p, const Affine* d_g, size_t half, XYZZ h_out[2], hipStream_t s);
+size_t msm_pair_fused_max_half(size_t limit);  // the largest half <= limit that runs as one two-set run under the tuning in force (0: none)
 uint32_t msm_table_window(size_t n);  // window width a table for n pinned points is built with
 int msm_table_build(Ctx* c, const Affine* d_points, size_t n, uint32_t cw, Affine* d_table, hipStream_t s);
 

@@ -1,6 +1,8 @@
 // ipa.hip -- the inner-product argument over BN254 G1 (halo2_proofs/src/poly/ipa/): what an opening's k rounds and the verifier's
 // vector s do to 2^k elements.  The composition -- transcript, draws, the L_j / R_j MSMs (msm.hip) and the handful of host group
-// operations per round -- is the caller's; include/halo2hip_ipa.h states the contract.
+// operations per round -- is the caller's; include/halo2hip_ipa.h states the contract.  A round is also ONE call (ipa_round_device,
+// include/halo2hip_ipa_round.h): the fold and the collapse by the challenge before it, the inner products and both MSMs as one run of the
+// MSM pipeline (msm.hip msm_pair_device), queued on one stream with one wait.
 //   ipa_collapse_kernel       g[i] + [u] g[half + i] (prover.rs:155-167), one lane per point: the scalar is the same for every point, so
 //                             it is recoded once on the host (ipa_elem.h: GLV halves in joint sparse form) and every lane walks the same
 //                             columns -- a uniform branch over four per-lane points in registers instead of ecfft.hip's 15-entry
@@ -259,6 +261,43 @@ static int ipa_fold_device(Ctx* c, Fe* d_p, Fe* d_b, size_t half, const Fe& u_in
     return guard.release();
 }
 
+// One round after the challenge of the round before it: [the fold of p and b and the collapse of g at 2 half, by that challenge,] the
+// inner products and the two MSMs at half -- everything queued on s, and the one wait is the pair MSM's.  The values travel ahead of
+// it: their copy into pinned memory is queued before the collapse and the MSM stages, so the MSM's wait delivers them too.  With u the
+// fold and the inner products are ipa_fold_inner_kernel, as in h2hip_ipa_fold with next_values.
+static int ipa_round_device(Ctx* c, Fe* d_p, Fe* d_b, Affine* d_g, size_t half, const Fe* u, const Fe* u_inv, XYZZ* h_sums, uint64_t* values,
+                            hipStream_t s) {
+    {
+        IpaWs w;
+        int rc = ipa_ws(c, &w);
+        if (rc) return rc;
+        if ((rc = c->ipa_vals.ensure(2 * sizeof(Fe)))) return rc;
+        if ((rc = c->ws_acquire(s))) return rc;
+        WsGuard guard(c, s);
+        const uint32_t blocks = ipa_blocks(half);
+        if (u) {
+            int tm = c->timer_begin("ipa_fold", s);
+            hipLaunchKernelGGL(ipa_fold_inner_kernel, dim3(blocks), dim3(IPA_THREADS), 0, s, d_p, d_b, (uint64_t)(2 * half), *u_inv, *u, w.part);
+            H2_CHECK(hipGetLastError());
+            c->timer_end(tm, s);
+        } else {
+            int tm = c->timer_begin("ipa_inner_products", s);
+            hipLaunchKernelGGL(ipa_inner_kernel, dim3(blocks), dim3(IPA_THREADS), 0, s, (const Fe*)d_p, (const Fe*)d_b, (uint64_t)half, w.part);
+            H2_CHECK(hipGetLastError());
+            c->timer_end(tm, s);
+        }
+        hipLaunchKernelGGL(ipa_final_kernel, dim3(1), dim3(IPA_THREADS), 0, s, (const Fe*)w.part, blocks, w.vals);
+        H2_CHECK(hipGetLastError());
+        H2_CHECK(hipMemcpyAsync(c->ipa_vals.p, w.vals, 2 * sizeof(Fe), hipMemcpyDeviceToHost, s));
+        if ((rc = guard.release())) return rc;
+    }
+    if (u)
+        if (int rc = ipa_collapse_device(c, d_g, 2 * half, *u, s)) return rc;
+    if (int rc = msm_pair_device(c, d_p, d_g, half, h_sums, s)) return rc;  // waits for s
+    memcpy(values, c->ipa_vals.p, 2 * sizeof(Fe));
+    return 0;
+}
+
 }  // namespace h2
 
 using namespace h2;
@@ -401,6 +440,80 @@ int h2hip_ipa_compute_s_bn254_fr(const uint64_t* u, uint32_t k, const uint64_t i
     if (rc) return rc;
     if ((rc = ipa_s_run(c, u, k, init, d_s, c->stream))) return rc;
     return io.finish();
+}
+
+static int ipa_round_half(const char* what, size_t half) {
+    if (half < 1 || half > IPA_MAX_HALF / 2) {
+        set_error("%s: half = %zu is outside 1 .. 2^26", what, half);
+        return H2HIP_EINVAL;
+    }
+    return 0;
+}
+
+static void ipa_sum_out(const XYZZ& r, uint64_t out_xyz[12]) {
+    const Jac j = xyzz_to_jac(r);
+    memcpy(out_xyz, &j, 96);
+}
+
+int h2hip_ipa_round_msms_bn254_device(const void* d_p, const void* d_g_xy, size_t half, uint64_t out_l[12], uint64_t out_r[12], void* stream) {
+    if (int rc = ipa_round_half("ipa_round_msms", half)) return rc;
+    if (int rc = ipa_dptr("ipa_round_msms", d_p, "d_p")) return rc;
+    if (int rc = ipa_dptr("ipa_round_msms", d_g_xy, "d_g_xy")) return rc;
+    if (int rc = ipa_ptr("ipa_round_msms", out_l, "out_l")) return rc;
+    if (int rc = ipa_ptr("ipa_round_msms", out_r, "out_r")) return rc;
+    Entry en("h2hip_ipa_round_msms_bn254_device", d_p);
+    if (en.rc) return en.rc;
+    XYZZ sums[2];
+    if (int rc = msm_pair_device(en.c, (const Fe*)d_p, (const Affine*)d_g_xy, half, sums, (hipStream_t)stream)) return rc;
+    ipa_sum_out(sums[0], out_l);
+    ipa_sum_out(sums[1], out_r);
+    return 0;
+}
+
+int h2hip_ipa_round_bn254_device(void* d_p, void* d_b, void* d_g_xy, size_t half, const uint64_t u[4], const uint64_t u_inv[4], uint64_t out_l[12],
+                                 uint64_t out_r[12], uint64_t values[8], void* stream) {
+    if (int rc = ipa_round_half("ipa_round", half)) return rc;
+    if (int rc = ipa_dptr("ipa_round", d_p, "d_p")) return rc;
+    if (int rc = ipa_dptr("ipa_round", d_b, "d_b")) return rc;
+    if (int rc = ipa_dptr("ipa_round", d_g_xy, "d_g_xy")) return rc;
+    if (int rc = ipa_ptr("ipa_round", out_l, "out_l")) return rc;
+    if (int rc = ipa_ptr("ipa_round", out_r, "out_r")) return rc;
+    if (int rc = ipa_ptr("ipa_round", values, "values")) return rc;
+    if ((u != nullptr) != (u_inv != nullptr)) {
+        set_error("ipa_round: %s given without %s", u ? "u" : "u_inv", u ? "u_inv" : "u");
+        return H2HIP_EINVAL;
+    }
+    Fe fu, fu_inv;
+    if (u) {
+        if (int rc = ipa_scalar("ipa_round", u, "u")) return rc;
+        if (int rc = ipa_scalar("ipa_round", u_inv, "u_inv")) return rc;
+        fu = fe_from_u64x4(u);
+        fu_inv = fe_from_u64x4(u_inv);
+    }
+    Entry en("h2hip_ipa_round_bn254_device", d_p);
+    if (en.rc) return en.rc;
+    XYZZ sums[2];
+    if (int rc = ipa_round_device(en.c, (Fe*)d_p, (Fe*)d_b, (Affine*)d_g_xy, half, u ? &fu : nullptr, u ? &fu_inv : nullptr, sums, values,
+                                  (hipStream_t)stream))
+        return rc;
+    ipa_sum_out(sums[0], out_l);
+    ipa_sum_out(sums[1], out_r);
+    return 0;
+}
+
+size_t h2hip_ipa_round_msms_fused_max_half(void) {
+    TuneRead r;
+    return msm_pair_fused_max_half(IPA_MAX_HALF / 2);
+}
+
+int h2hip_ipa_set_round_call(int on) {
+    TuneWrite()->ipa_round_call = on != 0;
+    return 0;
+}
+
+int h2hip_ipa_get_round_call(void) {
+    TuneRead r;
+    return tune().ipa_round_call ? 1 : 0;
 }
 
 int h2hip_ipa_set_collapse_quad(size_t max_half) {

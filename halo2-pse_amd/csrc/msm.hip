@@ -51,6 +51,7 @@
 #include "ecq.h"
 #include "engine.h"
 #include "host64.h"
+#include "msm_pair.h"
 
 namespace h2 {
 
@@ -144,7 +145,10 @@ __device__ __forceinline__ Fe fr_to_canonical(const Fe& x) {
 #define MSM_SCATTER_XG 4u  // log2 of the tiles of the scatter pass that share an XCD (0: workgroups take the tiles in order); A/B builds: 2, 3, 4, 6 -> sort of 2^24 pairs 1.89, 1.87, 1.85, 1.84 ms (2.02 in order)
 #endif
 
-// A1: histogram of the tile over the coarse bins
+// A1: histogram of the tile over the coarse bins.  PAIR (the two sums of an IPA round as one two-set run, msm_pair.h): lane t of MSM y's
+// tiles works on point y n + t of the 2 n, whose scalar sits at the rotated index of a.scalars_one and whose index is the entry (the
+// record of the bases the accumulation reads); the bucket sets are MSM y's, as in every fused run
+template <bool PAIR = false>
 __global__ void __launch_bounds__(256) msm_l1_count_kernel(L1Args a) {
     __shared__ uint32_t lh[MSM_MAX_C1];
     if (a.chk_flag && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 4 * H2_PIN_SAMPLES) {  // 16 points x 4 pieces of 16 B
@@ -157,12 +161,12 @@ __global__ void __launch_bounds__(256) msm_l1_count_kernel(L1Args a) {
     }
     for (uint32_t b = threadIdx.x; b < a.C1; b += 256) lh[b] = 0;
     __syncthreads();
-    const Fe* __restrict__ scalars = a.list ? a.list[blockIdx.y] : a.scalars_one;
+    const Fe* __restrict__ scalars = PAIR ? a.scalars_one : a.list ? a.list[blockIdx.y] : a.scalars_one;
     const uint32_t set0 = a.shared ? blockIdx.y : blockIdx.y * a.W;
     for (uint32_t t = threadIdx.x; t < a.tile; t += 256) {
         const uint32_t i = blockIdx.x * a.tile + t;
         if (i < a.n) {
-            const Fe sc = fr_to_canonical(scalars[i]);
+            const Fe sc = fr_to_canonical(scalars[PAIR ? msm_pair_scalar_index(msm_pair_point(blockIdx.y, i, a.n), a.n) : i]);
             for_each_digit(sc, a.c, a.q, a.W, [&](uint32_t w, uint32_t slot, uint32_t) {
                 const uint32_t gb = ((set0 + (a.shared ? 0u : w)) << a.cb) | slot;
                 atomicAdd(&lh[gb >> a.L], 1u);
@@ -221,7 +225,7 @@ __device__ __forceinline__ uint32_t block_scan_base(const uint32_t* cnt, uint32_
 // every bin's share as one contiguous run at the offset A2c computed for (tile, bin).  What bounds this pass is how HBM takes
 // the writes: with 3-entry runs (or a scattered 8-byte store per entry) every run is a partial-line write and the pass ran at
 // 0.6 TB/s; hence at most MSM_MAX_C1 bins for a tile of up to MSM_STAGE entries.
-template <bool SPLIT>
+template <bool SPLIT, bool PAIR = false>
 __global__ void __launch_bounds__(1024) msm_l1_scatter_kernel(L1Args a) {
     __shared__ uint2 stage[MSM_STAGE];
     __shared__ uint32_t cur[MSM_MAX_C1];   // entries per bin, then the bin's cursor in `stage`
@@ -237,12 +241,12 @@ __global__ void __launch_bounds__(1024) msm_l1_scatter_kernel(L1Args a) {
     }
     const size_t row = (size_t)(blockIdx.y * gridDim.x + tx) * a.C1;
     for (uint32_t b = threadIdx.x; b < a.C1; b += 1024) cur[b] = a.tile_hist[row + b];
-    const Fe* __restrict__ scalars = a.list ? a.list[blockIdx.y] : a.scalars_one;
+    const Fe* __restrict__ scalars = PAIR ? a.scalars_one : a.list ? a.list[blockIdx.y] : a.scalars_one;
     const uint32_t set0 = a.shared ? blockIdx.y : blockIdx.y * a.W;
     const uint32_t i = tx * a.tile + threadIdx.x;
     const bool live = threadIdx.x < a.tile && i < a.n;
     Fe sc;
-    if (live) sc = fr_to_canonical(scalars[i]);
+    if (live) sc = fr_to_canonical(scalars[PAIR ? msm_pair_scalar_index(msm_pair_point(blockIdx.y, i, a.n), a.n) : i]);
     __syncthreads();
     uint32_t total;
     uint32_t run = block_scan_base<1024>(cur, a.C1, 1, ps, &total);  // C1 <= 1024: one bin per lane
@@ -256,7 +260,7 @@ __global__ void __launch_bounds__(1024) msm_l1_scatter_kernel(L1Args a) {
         for_each_digit(sc, a.c, a.q, a.W, [&](uint32_t w, uint32_t slot, uint32_t neg) {
             const uint32_t gb = ((set0 + (a.shared ? 0u : w)) << a.cb) | slot;
             const uint32_t pos = atomicAdd(&cur[gb >> a.L], 1u);
-            stage[pos] = make_uint2((a.shared ? w * a.stride + i : i) | (neg << 31), gb);
+            stage[pos] = make_uint2((PAIR ? msm_pair_point(blockIdx.y, i, a.n) : a.shared ? w * a.stride + i : i) | (neg << 31), gb);
         });
     }
     __syncthreads();
@@ -1387,7 +1391,9 @@ static int msm_layout(size_t n, MsmLayout* L, uint32_t fuse, const MsmTable* tab
 }
 
 // stage A (memory-bound): digits, two-level counting sort by bucket, size order
-static int msm_stage_a(Ctx* c, const MsmLayout& L, char* base, const Fe* const* d_scalars_list, const MsmTable* tab, hipStream_t s) {
+// pair: the two-set run of msm_pair_device -- L.fuse = 2, d_scalars_list[0] the 2 n scalars both MSMs read through the rotated index
+static int msm_stage_a(Ctx* c, const MsmLayout& L, char* base, const Fe* const* d_scalars_list, const MsmTable* tab, hipStream_t s,
+                       bool pair = false) {
     const MsmPlan& p = L.p;
     const size_t n = L.n;
     uint32_t* cstart = (uint32_t*)(base + L.o_cstart);
@@ -1397,7 +1403,7 @@ static int msm_stage_a(Ctx* c, const MsmLayout& L, char* base, const Fe* const* 
     L1Args a;
     a.scalars_one = d_scalars_list[0];
     a.list = nullptr;
-    if (L.fuse > 1) {  // the scalar arrays' addresses, read by the kernels per blockIdx.y (staged through pinned memory)
+    if (L.fuse > 1 && !pair) {  // the scalar arrays' addresses, read by the kernels per blockIdx.y (staged through pinned memory)
         int rc = c->stage_h2d(base + L.o_ptrs, d_scalars_list, L.fuse * sizeof(void*), s);
         if (rc) return rc;
         a.list = (const Fe* const*)(base + L.o_ptrs);
@@ -1423,7 +1429,10 @@ static int msm_stage_a(Ctx* c, const MsmLayout& L, char* base, const Fe* const* 
     c->pin_chk = Ctx::PinCheck();  // once per call
     uint32_t* chsum = (uint32_t*)(base + L.o_chsum);
     const dim3 tiles(L.tiles_x, L.fuse), chunks(L.n_tchunks, (L.C1 + 255) / 256);
-    hipLaunchKernelGGL(msm_l1_count_kernel, tiles, dim3(256), 0, s, a);
+    if (pair)
+        hipLaunchKernelGGL(msm_l1_count_kernel<true>, tiles, dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL(msm_l1_count_kernel<false>, tiles, dim3(256), 0, s, a);
     H2_CHECK(hipGetLastError());
     c->timer_end(t0, s);
     int t1 = c->timer_begin("msm_sort", s);
@@ -1440,7 +1449,11 @@ static int msm_stage_a(Ctx* c, const MsmLayout& L, char* base, const Fe* const* 
     const bool split = tune().msm_split_records && L.E / L.C1 > MSM_STAGE;
     a.tmp_e = (uint32_t*)(base + L.o_tmp);
     a.tmp_k = (uint16_t*)(base + L.o_tmp + L.E * 4);
-    if (split)
+    if (pair && split)
+        hipLaunchKernelGGL((msm_l1_scatter_kernel<true, true>), tiles, dim3(1024), 0, s, a);
+    else if (pair)
+        hipLaunchKernelGGL((msm_l1_scatter_kernel<false, true>), tiles, dim3(1024), 0, s, a);
+    else if (split)
         hipLaunchKernelGGL(msm_l1_scatter_kernel<true>, tiles, dim3(1024), 0, s, a);
     else
         hipLaunchKernelGGL(msm_l1_scatter_kernel<false>, tiles, dim3(1024), 0, s, a);
@@ -1714,8 +1727,9 @@ static inline XYZZ finish_msm(const XYZZ* sums, const MsmPlan& p) { return p.sha
 // so that every accumulate launch is full-size while the sort of the next MSM and the reduction of the previous
 // one run underneath it.
 // scalars_on_host: d_scalars[j] are host pointers, uploaded into three device slots ahead of stage A.
+// points_step: MSM j reads the points d_points + j * points_step (plain form; 0: every MSM the same -- msm_pair_device's fall-back sets it)
 static int msm_batch_chunk(Ctx* c, const Fe* const* d_scalars, bool scalars_on_host, const Affine* d_points, const MsmTable* tab, size_t n,
-                           size_t count, XYZZ* h_out, hipStream_t s) {
+                           size_t count, XYZZ* h_out, hipStream_t s, size_t points_step = 0) {
     MsmLayout L;
     int rc = msm_layout(n, &L, 1, tab);
     if (rc) return rc;
@@ -1778,7 +1792,7 @@ static int msm_batch_chunk(Ctx* c, const Fe* const* d_scalars, bool scalars_on_h
             if ((rc = msm_stage_a(c, L, base, &sc, tab, a1))) return rc;
             H2_CHECK(hipEventRecord(ev[1 + 3 * j], a1));
             H2_CHECK(hipStreamWaitEvent(sb, ev[1 + 3 * j], 0));
-            if ((rc = msm_stage_b(c, L, base, d_points, rec_bytes(tab), sb))) return rc;
+            if ((rc = msm_stage_b(c, L, base, d_points + j * points_step, rec_bytes(tab), sb))) return rc;
             H2_CHECK(hipEventRecord(ev[2 + 3 * j], sb));
             H2_CHECK(hipStreamWaitEvent(a2, ev[2 + 3 * j], 0));
             if ((rc = msm_stage_c(c, L, base, h_ws + j * spm, a2))) return rc;
@@ -1797,8 +1811,9 @@ static int msm_batch_chunk(Ctx* c, const Fe* const* d_scalars, bool scalars_on_h
 // the sets of all of them.  The bucket reduction is a chain of dependent EC operations -- its duration hardly
 // depends on the size -- and dominates a 2^17-pair MSM; pipelining whole MSMs over streams only overlaps those
 // chains, fusing pays for one.  Sort and accumulate become one large launch each.
+// pair (count = 2, device scalars): the two sums of an IPA round -- d_scalars[0] holds 2 n scalars and d_points 2 n points (msm_pair.h)
 static int msm_fused_chunk(Ctx* c, const Fe* const* d_scalars, bool scalars_on_host, const Affine* d_points, const MsmTable* tab, size_t n,
-                           size_t count, XYZZ* h_out, hipStream_t s) {
+                           size_t count, XYZZ* h_out, hipStream_t s, bool pair = false) {
     MsmLayout L;
     int rc = msm_layout(n, &L, (uint32_t)count, tab);
     if (rc) return rc;
@@ -1823,7 +1838,7 @@ static int msm_fused_chunk(Ctx* c, const Fe* const* d_scalars, bool scalars_on_h
     }
     char* base = (char*)c->msm_slot[0].p;
     int t_all = c->timer_begin("msm_total", s);
-    if ((rc = msm_stage_a(c, L, base, list.data(), tab, s))) return rc;
+    if ((rc = msm_stage_a(c, L, base, list.data(), tab, s, pair))) return rc;
     if ((rc = msm_stage_b(c, L, base, d_points, rec_bytes(tab), s))) return rc;
     if ((rc = msm_stage_c(c, L, base, h_ws, s, h_pl))) return rc;
     c->timer_end(t_all, s);
@@ -2154,6 +2169,46 @@ int msm_batch_device(Ctx* c, const Fe* const* d_scalars, bool scalars_on_host, c
 // Sum of coeffs[i]*bases[i] for device-resident inputs; result (XYZZ) to host memory.
 int msm_device(Ctx* c, const Fe* d_scalars, const Affine* d_bases, size_t n, XYZZ* h_out, hipStream_t s, const MsmTable* tab) {
     return msm_batch_device(c, &d_scalars, false, d_bases, n, 1, h_out, s, tab, nullptr);
+}
+
+// ---- the two MSMs of an IPA round (ipa/commitment/prover.rs:109-110) -------------------------------------------------------------
+// h_out[0] = <p[half .. 2 half), g[0 .. half)>, h_out[1] = <p[0 .. half), g[half .. 2 half)>.  They read the same two arrays, so up to
+// msm_pair_fused_max_half() they are ONE run of the pipeline over the 2 half points, with the scalar of a point at the rotated index and
+// the buckets in two groups of sets (msm_pair.h; the digit and entry stage's pair kernels): one digit pass, one sort, one accumulation,
+// one reduction and one wait instead of two of each.  g changes every round, so the form is the plain one.  Above that size: the two
+// MSMs pipelined over the three streams of msm_batch_chunk, each over its own half of g; still one wait (per run of msm_max_chunk pairs).
+static bool msm_pair_fused(size_t half) {
+    const MsmPlan fp = make_plan(half, true, nullptr);
+    return msm_pair_fits(half, fp.W, fp.cb, tune().msm_fuse_entries, tune().msm_fuse_max_n, (uint64_t)MSM_MAX_C1 << MSM_MAX_L, MSM_MAX_C1);
+}
+
+size_t msm_pair_fused_max_half(size_t limit) {
+    return msm_pair_max_half(
+        [](uint32_t lg) {
+            const MsmPlan fp = make_plan((size_t)1 << lg, true, nullptr);  // the window follows floor(log2 half) (plain_window)
+            return MsmPairWindows{fp.W, fp.cb};
+        },
+        tune().msm_fuse_entries, tune().msm_fuse_max_n, (uint64_t)MSM_MAX_C1 << MSM_MAX_L, MSM_MAX_C1, limit);
+}
+
+int msm_pair_device(Ctx* c, const Fe* d_p, const Affine* d_g, size_t half, XYZZ h_out[2], hipStream_t s) {
+    h_out[0] = h_out[1] = xyzz_identity();
+    if (half == 0) return 0;
+    if (msm_pair_fused(half)) {
+        const Fe* both[2] = {d_p, d_p};  // one array: the pair kernels read it through the rotated index
+        return msm_fused_chunk(c, both, false, d_g, nullptr, half, 2, h_out, s, true);
+    }
+    const size_t max_chunk = tune().msm_max_chunk;
+    if (half > max_chunk) c->gather_off = SIZE_MAX / 2;  // several runs: their sums are added on the host
+    for (size_t o = 0; o < half; o += max_chunk) {
+        const size_t m = half - o < max_chunk ? half - o : max_chunk;
+        const Fe* ptrs[2] = {d_p + half + o, d_p + o};
+        XYZZ part[2];
+        if (int rc = msm_batch_chunk(c, ptrs, false, d_g + o, nullptr, m, 2, part, s, half)) return rc;
+        xyzz_add(h_out[0], part[0]);
+        xyzz_add(h_out[1], part[1]);
+    }
+    return 0;
 }
 
 // Build the fixed-base table for n device-resident points: rows 0..W-1 of n points each, row j = 2^(pos_j) * P with pos_j the

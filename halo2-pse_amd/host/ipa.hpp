@@ -410,23 +410,40 @@ inline void create_proof(const ParamsIPA& params, FrRng& rng, transcript::Blake2
     engine_check(h2hip_memcpy_h2d(d_g.at(), params.g[0].x, 64 * n, nullptr), "h2hip_memcpy_h2d");  // :99
     engine_check(h2hip_ipa_powers_bn254_fr_device(x_3.l, n, d_b.at(), nullptr), "h2hip_ipa_powers_bn254_fr_device");  // :88-95
     Fr values[2] = {Fr::zero(), Fr::zero()};
-    if (k) engine_check(h2hip_ipa_inner_products_bn254_fr_device(d_p.at(), d_b.at(), n / 2, values[0].l, nullptr), "h2hip_ipa_inner_products");
+    // One engine call per round (h2hip_ipa_round_bn254_device: the fold and the collapse by the challenge before it, the inner products and
+    // both MSMs, one wait), or -- h2hip_ipa_set_round_call(0) -- the separate calls.  The same draws, the same transcript, the same bytes.
+    const bool round_call = h2hip_ipa_get_round_call() != 0;
+    if (k && !round_call)
+        engine_check(h2hip_ipa_inner_products_bn254_fr_device(d_p.at(), d_b.at(), n / 2, values[0].l, nullptr), "h2hip_ipa_inner_products");
+    Fr u_prev = Fr::zero(), u_prev_inv = Fr::zero();
     for (uint32_t j = 0; j < k; j++) {                                         // :102
         const size_t half = size_t(1) << (k - j - 1);
         G1 l_g, r_g;
-        engine_check(h2hip_msm_bn254_device(d_p.at(32 * half), d_g.at(), half, l_g.x, nullptr), "h2hip_msm_bn254_device");  // :109
-        engine_check(h2hip_msm_bn254_device(d_p.at(), d_g.at(64 * half), half, r_g.x, nullptr), "h2hip_msm_bn254_device");  // :110
+        if (round_call) {  // :129-137 of round j - 1, then :109-112
+            engine_check(h2hip_ipa_round_bn254_device(d_p.at(), d_b.at(), d_g.at(), half, j ? u_prev.l : nullptr, j ? u_prev_inv.l : nullptr, l_g.x,
+                                                      r_g.x, values[0].l, nullptr),
+                         "h2hip_ipa_round_bn254_device");
+        } else {
+            engine_check(h2hip_msm_bn254_device(d_p.at(32 * half), d_g.at(), half, l_g.x, nullptr), "h2hip_msm_bn254_device");  // :109
+            engine_check(h2hip_msm_bn254_device(d_p.at(), d_g.at(64 * half), half, r_g.x, nullptr), "h2hip_msm_bn254_device");  // :110
+        }
         const Fr l_rand = rng(), r_rand = rng();                               // :113-114
         tr.write_point(g1::sum({{Fr::one(), l_g.to_affine()}, {values[0] * z, params.u}, {l_rand, params.w}}));  // :115-121
         tr.write_point(g1::sum({{Fr::one(), r_g.to_affine()}, {values[1] * z, params.u}, {r_rand, params.w}}));  // :116-122
         const Fr u_j = tr.squeeze_challenge();                                 // :124
         if (u_j == Fr::zero()) throw Error("create_proof: a challenge u_j is zero");  // :125 unwraps
         const Fr u_j_inv = u_j.invert();
-        engine_check(h2hip_ipa_fold_bn254_fr_device(d_p.at(), d_b.at(), half, u_j_inv.l, u_j.l, half >= 2 ? values[0].l : nullptr, nullptr),
-                     "h2hip_ipa_fold_bn254_fr_device");                        // :129-134, with the next round's :111-112
-        engine_check(h2hip_ipa_collapse_bn254_device(d_g.at(), half, u_j.l, nullptr), "h2hip_ipa_collapse_bn254_device");  // :137
+        if (round_call) {
+            u_prev = u_j, u_prev_inv = u_j_inv;  // folded and collapsed by the next round's call
+        } else {
+            engine_check(h2hip_ipa_fold_bn254_fr_device(d_p.at(), d_b.at(), half, u_j_inv.l, u_j.l, half >= 2 ? values[0].l : nullptr, nullptr),
+                         "h2hip_ipa_fold_bn254_fr_device");                    // :129-134, with the next round's :111-112
+            engine_check(h2hip_ipa_collapse_bn254_device(d_g.at(), half, u_j.l, nullptr), "h2hip_ipa_collapse_bn254_device");  // :137
+        }
         f = f + l_rand * u_j_inv + r_rand * u_j;                               // :141-142
     }
+    if (round_call && k)  // the last fold, for c = p'[0]; the last collapse (:137) gives a g' that nothing reads, and is dropped
+        engine_check(h2hip_ipa_fold_bn254_fr_device(d_p.at(), d_b.at(), 1, u_prev_inv.l, u_prev.l, nullptr, nullptr), "h2hip_ipa_fold_bn254_fr_device");
     Fr c;
     engine_check(h2hip_memcpy_d2h(c.l, d_p.at(), 32, nullptr), "h2hip_memcpy_d2h");
     engine_check(h2hip_stream_synchronize(nullptr), "h2hip_stream_synchronize");

@@ -14,7 +14,10 @@ Blake2bRead.  Everything of 2^k elements lives in HBM as torch CUDA tensors of M
 and multiplies; the transcript and the draws stay here, and the handful of group operations between the MSMs -- the + [r] W of a
 commitment, the [value z] U + [rand] W of a round, the other terms of MSMIPA.eval -- are one host call of the library each
 (h2hip_g1_linear_combinations_bn254, include/halo2hip_g1.h: dependent chains of a few hundred group operations, faster on a host core
-than on GPU lanes).  There is no CPU fallback for the rest: without a GPU the calls raise H2HipError.
+than on GPU lanes).  A round of an opening is one engine call (round_device, include/halo2hip_ipa_round.h: the fold and the collapse by
+the challenge before it, the inner products and both MSMs from one run of the MSM pipeline, one wait); set_round_call(False) runs the
+separate calls instead, with the same draws, transcript and bytes.  There is no CPU fallback for the rest: without a GPU the calls raise
+H2HipError.
 
 Draw order (one FrRng): ProverIPA.create_proof draws q_prime_blind first; create_proof then draws the 2^k coefficients of s_poly in HBM
 (element i = the next block i), s_poly_blind, and per round l_j_randomness then r_j_randomness.
@@ -156,6 +159,36 @@ def fold_device(d_p, d_b, half, u_inv, u, next_values=False):
     _check(lib().h2hip_ipa_fold_bn254_fr_device(_dptr(d_p), _dptr(d_b), int(half), _p(_fr(u_inv)), _p(_fr(u)),
                                                 _p(values) if next_values else None, _stream()), "h2hip_ipa_fold_bn254_fr_device")
     return (fr_to_int(values[0]), fr_to_int(values[1])) if next_values else None
+
+
+def round_msms_device(d_p, d_g, half):
+    """(L, R) = (<p[half:2 half], g[:half]>, <p[:half], g[half:2 half]>) as Jacobian limbs (12,), the form msm_device returns: both MSMs of
+    a round from one engine call (one run of the MSM pipeline up to round_msms_fused_max_half()); waits for the stream"""
+    out = np.zeros((2, 12), dtype=np.uint64)
+    _check(lib().h2hip_ipa_round_msms_bn254_device(_dptr(d_p), _dptr(d_g), int(half), _p(out[0]), _p(out[1]), _stream()),
+           "h2hip_ipa_round_msms_bn254_device")
+    return out[0], out[1]
+
+
+def round_msms_fused_max_half():
+    """the largest half whose two MSMs run as one two-set run under the settings in force"""
+    return int(lib().h2hip_ipa_round_msms_fused_max_half())
+
+
+def round_device(d_p, d_b, d_g, half, u=None, u_inv=None):
+    """one round after the challenge u of the round before it (None: the first round): fold p, b and collapse g at 2 half by u, then
+    L, R and the inner products at half -> (L, R, (value_l, value_r)); one engine call, one wait"""
+    out, values = np.zeros((2, 12), dtype=np.uint64), np.zeros((2, 4), dtype=np.uint64)
+    _check(lib().h2hip_ipa_round_bn254_device(_dptr(d_p), _dptr(d_b), _dptr(d_g), int(half), None if u is None else _p(_fr(u)),
+                                              None if u_inv is None else _p(_fr(u_inv)), _p(out[0]), _p(out[1]), _p(values), _stream()),
+           "h2hip_ipa_round_bn254_device")
+    return out[0], out[1], (fr_to_int(values[0]), fr_to_int(values[1]))
+
+
+def set_round_call(on=True):
+    """tuning: create_proof runs one round call per round (the default) or the separate calls; returns the value in force"""
+    _check(lib().h2hip_ipa_set_round_call(1 if on else 0), "h2hip_ipa_set_round_call")
+    return bool(lib().h2hip_ipa_get_round_call())
 
 
 def _challenges(u):
@@ -355,11 +388,18 @@ def create_proof(params, rng, transcript, p_poly, p_blind, x_3, resident=True):
     f = (s_blind * xi + p_blind) % R                                                   # :76-80
     d_b = powers_device(x_3, n)                                                        # :88-95
     d_gp = d_g.clone()                                                                 # :99
-    values = inner_products_device(d_pp, d_b, n // 2) if k else None
+    # one engine call per round (round_device: the fold and the collapse by the challenge before it, the inner products and both MSMs,
+    # one wait), or -- set_round_call(False) -- the separate calls; the draws, the transcript and the bytes are the same
+    round_call = bool(lib().h2hip_ipa_get_round_call())
+    values = inner_products_device(d_pp, d_b, n // 2) if k and not round_call else None
+    u_j = u_j_inv = None
     for j in range(k):                                                                 # :102
         half = 1 << (k - j - 1)
-        l_g = msm_device(d_pp[half:], d_gp, half)                                      # :109
-        r_g = msm_device(d_pp, d_gp[half:], half)                                      # :110
+        if round_call:
+            l_g, r_g, values = round_device(d_pp, d_b, d_gp, half, u_j, u_j_inv)       # :129-137 of round j - 1, then :109-112
+        else:
+            l_g = msm_device(d_pp[half:], d_gp, half)                                  # :109
+            r_g = msm_device(d_pp, d_gp[half:], half)                                  # :110
         value_l, value_r = values                                                      # :111-112
         l_rand, r_rand = [fr_to_int(e) for e in rng.draw(2)]                           # :113-114
         l_j, r_j = g1_linear_combinations([l_g, r_g], [[value_l * z, l_rand], [value_r * z, r_rand]], [params.u, params.w])   # :115-116
@@ -369,9 +409,12 @@ def create_proof(params, rng, transcript, p_poly, p_blind, x_3, resident=True):
         if u_j == 0:
             raise IPAError("create_proof: the challenge u_%d is zero" % j)             # :125 unwraps
         u_j_inv = pow(u_j, -1, R)
-        values = fold_device(d_pp, d_b, half, u_j_inv, u_j, next_values=half >= 2)      # :129-134
-        collapse_device(d_gp, half, u_j)                                               # :137
+        if not round_call:
+            values = fold_device(d_pp, d_b, half, u_j_inv, u_j, next_values=half >= 2)  # :129-134
+            collapse_device(d_gp, half, u_j)                                           # :137
         f = (f + l_rand * u_j_inv + r_rand * u_j) % R                                  # :141-142
+    if round_call and k:
+        fold_device(d_pp, d_b, 1, u_j_inv, u_j)   # the last fold, for c; the last collapse (:137) gives a g' nothing reads: dropped
     c = _read_elem(d_pp)                                                               # :147
     transcript.write_scalar(c)                                                         # :149-150
     transcript.write_scalar(f)

@@ -20,9 +20,11 @@ pub mod evalh;
 pub mod ffi;
 mod ffi_g1;
 mod ffi_ipa;
+mod ffi_ipa_round;
 mod ffi_pairing;
 pub mod g1;
 pub mod ipa;
+pub mod ipa_round;
 pub mod pairing;
 
 use ff::{Field, PrimeField};

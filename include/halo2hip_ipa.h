@@ -7,8 +7,8 @@
  * with its text before the engine is entered, so it needs no GPU.
  *
  * The engine draws and orders nothing: challenges are the caller's (the transcript's), and so is the order of the rounds.  The L_j / R_j
- * of a round are h2hip_msm_bn254_device on (p + half, g, half) and (p, g + half, half); their [value * z] U + [rand] W parts, and every
- * other handful of group operations, stay with the caller.
+ * of a round are h2hip_msm_bn254_device on (p + half, g, half) and (p, g + half, half), or both from h2hip_ipa_round_msms / h2hip_ipa_round
+ * below; their [value * z] U + [rand] W parts, and every other handful of group operations, stay with the caller.
  *
  * The round calls (powers, inner_products, fold) exist only in _device form: the state of an opening -- p', b and g' -- lives in
  * device memory across its k rounds, and the wrappers own the single upload.  _device forms queue on `stream` and do not synchronise
@@ -58,4 +58,8 @@ size_t h2hip_ipa_get_collapse_quad(void);
 #ifdef __cplusplus
 }
 #endif
+
+/* a round as one call -- h2hip_ipa_round_msms_bn254_device, h2hip_ipa_round_bn254_device and their knob: declared in a file of their
+ * own (with its own generated binding tables), and part of this header */
+#include "halo2hip_ipa_round.h"
 #endif

@@ -7,6 +7,12 @@ Per k of --ks (default 17 and 20):
                      median run, whose smallest rounds are the floor a round trip per challenge sets (round_floor_ms; the same of
                      every timed run in round_floor_ms_runs, for the spread)
   opening_host       the same from a host polynomial (one upload)
+                     Both paths of the opening are timed: the round call (h2hip_ipa_round, the default; the figures above) and, under
+                     "separate_calls", the same figures with ipa.set_round_call(False).  In the round-call path the split has
+                     round_call_ms (wall around round_device: the fold and the collapse by the challenge before, the inner products and
+                     both MSMs) and a round runs from the end of one round_device to the end of the next, so round j holds the fold and
+                     the collapse of round j - 1 (at twice its size) and the list closes with the last fold; msm_total_ms is the
+                     engine's stage timer over every MSM run of the opening, in both paths
   multiopen          ProverIPA::create_proof on the queries of config 5 (tests/opening_util.py CONFIG5_SETS, the ones tools/opening_bench.py
                      times for SHPLONK): 21 polynomials, 26 queries, 4 points.  The time includes the commitment to q' and the whole
                      opening that follows; opening_bench's SHPLONK stages are the quotient kernels alone
@@ -75,7 +81,8 @@ class Split:
     def __init__(self, ipa):
         import torch
         self.ipa, self.torch, self.t = ipa, torch, {}
-        self.names = ("msm_device", "fold_device", "collapse_device", "inner_products_device", "powers_device")
+        self.names = ("msm_device", "fold_device", "collapse_device", "inner_products_device", "powers_device", "round_device")
+        self.round_call = bool(ipa.lib().h2hip_ipa_get_round_call())
         self.saved = {n: getattr(ipa, n) for n in self.names}
         self.rounds, self.mark = [], None
 
@@ -96,7 +103,8 @@ class Split:
             self.torch.cuda.synchronize()
             now = time.perf_counter()
             self.t[name] = self.t.get(name, 0.0) + (now - t0) * 1e3
-            if name == "collapse_device":  # the last call of a round
+            # the last call of a round: the collapse, or the round call (and the fold that closes the opening)
+            if name == ("round_device" if self.round_call else "collapse_device") or (self.round_call and name == "fold_device"):
                 if self.mark is not None:
                     self.rounds.append((now - self.mark) * 1e3)
                 self.mark = now
@@ -121,32 +129,44 @@ def bench_k(h2, ipa, T, k, reps):
             ipa.create_proof(params, h2.FrRng(SEED), w, poly, blind, x_3, resident=resident)
             return w.finalize()
 
-        rec["opening_resident"] = med(wall(lambda: open_(d_poly, True), reps))
-        rec["opening_host"] = med(wall(lambda: open_(h_poly, False), reps))
-        splits = []
-        for r in range(1 + reps):
-            h2.profile_enable(True)
-            h2.profile_reset()
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            with Split(ipa) as sp:
-                open_(d_poly, True)
-            total = (time.perf_counter() - t0) * 1e3
-            h2.profile_enable(False)
-            if r == 0:
-                continue
-            collapse, normalise = h2.profile_get("ipa_collapse")[0], h2.profile_get("ipa_normalize")[0]
-            calls = sum(sp.t.values())
-            splits.append({"total_ms": total, "collapse_ms": collapse, "normalise_ms": normalise, "msm_ms": sp.t["msm_device"],
-                           "fold_and_inner_products_ms": sp.t["fold_device"] + sp.t["inner_products_device"],
-                           "collapse_call_ms": sp.t["collapse_device"], "host_between_calls_ms": total - calls, "round_ms": sp.rounds})
-        splits.sort(key=lambda s: s["total_ms"])
-        mid = splits[len(splits) // 2]
-        rec["opening_split"] = mid
-        rec["round_floor_ms"] = min(mid["round_ms"][-4:]) if mid["round_ms"] else None
-        # the same figure and the host share of every timed run, for the run-to-run spread beside the median run's
-        rec["round_floor_ms_runs"] = [min(s["round_ms"][-4:]) for s in splits if s["round_ms"]]
-        rec["host_between_calls_ms_runs"] = [s["host_between_calls_ms"] for s in splits]
+        def opening_figures():
+            out = {"opening_resident": med(wall(lambda: open_(d_poly, True), reps)), "opening_host": med(wall(lambda: open_(h_poly, False), reps))}
+            splits = []
+            for r in range(1 + reps):
+                h2.profile_enable(True)
+                h2.profile_reset()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                with Split(ipa) as sp:
+                    open_(d_poly, True)
+                total = (time.perf_counter() - t0) * 1e3
+                h2.profile_enable(False)
+                if r == 0:
+                    continue
+                collapse, normalise = h2.profile_get("ipa_collapse")[0], h2.profile_get("ipa_normalize")[0]
+                calls = sum(sp.t.values())
+                splits.append({"total_ms": total, "collapse_ms": collapse, "normalise_ms": normalise, "msm_ms": sp.t["msm_device"],
+                               "msm_total_ms": h2.profile_get("msm_total")[0], "round_call_ms": sp.t.get("round_device", 0.0),
+                               "fold_and_inner_products_ms": sp.t.get("fold_device", 0.0) + sp.t.get("inner_products_device", 0.0),
+                               "collapse_call_ms": sp.t.get("collapse_device", 0.0), "host_between_calls_ms": total - calls, "round_ms": sp.rounds})
+            splits.sort(key=lambda s: s["total_ms"])
+            mid = splits[len(splits) // 2]
+            out["opening_split"] = mid
+            out["round_floor_ms"] = min(mid["round_ms"][-4:]) if mid["round_ms"] else None
+            # the same figure and the host share of every timed run, for the run-to-run spread beside the median run's
+            out["round_floor_ms_runs"] = [min(s["round_ms"][-4:]) for s in splits if s["round_ms"]]
+            out["host_between_calls_ms_runs"] = [s["host_between_calls_ms"] for s in splits]
+            # every round of every timed run, for the spread of a round at a given half
+            out["round_ms_runs"] = [s["round_ms"] for s in splits]
+            return out
+
+        try:
+            ipa.set_round_call(True)
+            rec.update(opening_figures())
+            ipa.set_round_call(False)
+            rec["separate_calls"] = opening_figures()
+        finally:
+            ipa.set_round_call(True)
         # verification: read the proof on the host, then compute_s and the MSM over the pinned g
         proof = open_(d_poly, True)
         commitment = params.commit(d_poly, blind)
